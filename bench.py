@@ -6,11 +6,11 @@ The JOB is fixed: BASELINE config 4 = 4 000 synthetic partitions x 500 reads = 2
 freddie_amd/scatter.py -- no collective: partitions share nothing).  A STEP is one pass of the hot path over the rank's
 whole share of the job as ONE batch of up to 2 M reads (where HBM allows eight contexts to hold it: BATCH_READS) that takes turns on the contexts of the
 GPU (eight by default); since round 6 a step is PASSES_PER_STEP = 16 such passes (a timed region of 20 steps is then 1.2 s instead of
-0.076 s; reads are counted per pass, so `value` is unchanged by it).  It is timed twice, K steps each, between barriers:
+0.076 s; reads are counted per pass, so `value` is unchanged by it).  It is timed K steps between barriers (twice with --full):
   value               with the inputs RESIDENT IN HBM when the timed part starts (every context holds a batch of the share;
                       a pass = ``fseg_run`` of every batch: histogram .. labels recomputed from the inputs, results left in HBM
                       and checked from one fetch per context afterwards) -- the contract's reading of ``value``;
-  value_h2h           the way the drop-in CLI does it, PCIe inside: every batch ``fseg_upload`` (host arrays -> HBM) ->
+  value_h2h           (--full) the way the drop-in CLI does it, PCIe inside: every batch ``fseg_upload`` (host arrays -> HBM) ->
                       ``fseg_run`` -> ``fseg_results_packed`` (final positions and the label matrix at two bits per label in host
                       memory), one batch's copies overlapping the others' kernels; nothing is replayed.  Rounds 1-4 reported this
                       rate as ``value``; it depends on the box's host as much as on the GPU (300-409 M reads/s box to box).
@@ -18,10 +18,23 @@ GPU (eight by default); since round 6 a step is PASSES_PER_STEP = 16 such passes
 py/freddie_segment.py:681-735, minus the file I/O which the ``e2e`` leg adds), ``ms_per_step`` = the time of the whole job,
 ``scaling`` = "strong".
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload config4|config2|config3|config5|config1]
-  python bench.py --workload cluster-many|cluster-big|isoforms      (rows N3 / N4 of SURVEY 8f: their own metrics, 1 GPU)
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload config4|config2|config3|config5|config1] [--full]
+                  [--dump-outputs DIR]
+  python bench.py --workload cluster-many|cluster-big|isoforms [--full]     (rows N3 / N4 of SURVEY 8f: their own metrics, 1 GPU)
 
-Prints ONE JSON line (rank 0) with, besides the driver's fields:
+A plain run sets up, warms up, times the K steps of `value` and prints the line: the driver's fields, `value_is`, the result
+checksums of the resident region, `sync_timeouts`, `roofline_path` (from byte counts noted in the warm-up) and `config`.
+``--full`` adds everything below, each in runs of its own: the host memory -> host memory region, the stage-alone rooflines, the
+other configs, the CPU baselines, the end-to-end leg and rows N3 / N4 (``--no-*`` skip single legs of a --full run).
+``--dump-outputs DIR``: after the timed steps, what the last step computed (rank 0's share of the job, partition by partition in
+the share's order; rank r of an N-rank run writes rank<r>_*.npy), as .npy files of float64 / float32:
+  final_pos.npy, final_pos_offsets.npy   every final position; partition i's are final_pos[off[i]:off[i+1]]
+  label_offsets.npy                      partition i's labels are the global label indices off[i] .. off[i+1]-1
+  label_sample_index.npy, label_sample.npy   a fixed, seeded sample of the labels (0 / 1 / 2): DUMP_LABELS in all, the same
+                                         indices in each partition whatever the batching
+The inputs depend only on the arguments (seeded generator), so two builds' dumps compare output for output.
+
+Prints ONE JSON line (rank 0) with, besides the driver's fields (with --full):
   roofline              the interval-scoring stage ALONE on the GPU (one context, one resident batch of the job replayed, HIP
                         events around the stage on the library's own streams): algorithmic bytes 4*(N+K)*R + 4*R per partition
                          over that time -- the figure the per-kernel medians of profiles/ reproduce
@@ -116,6 +129,10 @@ BATCH_READS = int(os.environ.get("FREDDIE_BENCH_BATCH_READS", "0")) or default_b
 # driver's 20 steps were a timed region of 0.076 s -- too short for anything that samples the GPU from outside.  Reads are counted
 # per pass: `value` does not depend on this number, `ms_per_step` is the time of PASSES_PER_STEP passes.
 PASSES_PER_STEP = int(os.environ.get("FREDDIE_BENCH_PASSES", "16"))
+# --dump-outputs: labels in the seeded sample, spread evenly over the job's partitions (4 bytes each as values + 8 as indices,
+# beside every final position as float64: about 38 MB for config5, the largest job)
+DUMP_LABELS = 1 << 21
+DUMP_SEED = 20261016
 
 
 def popcount_bytes(a):
@@ -504,6 +521,41 @@ def one_shot_steps(ctxs, batches, order, collect=None):
         raise errors[0]
 
 
+def dump_batch(part_ids, res, per_part):
+    """--dump-outputs: copies of a batch's results (part_final_off, final_pos, label_off of ``Context.results(packed=True)``) and
+    its labels at ``per_part`` seeded indices of every partition, drawn from the partition's index in the job (the same
+    whatever the batching)."""
+    pfo, fp, lo, packed = res
+    idx, val = [np.empty(0, np.int64)], [np.empty(0, np.int64)]
+    for i, p in enumerate(part_ids):
+        n = int(lo[i + 1] - lo[i])
+        if n:
+            g = int(lo[i]) + np.sort(np.random.default_rng([DUMP_SEED, p]).integers(0, n, per_part))
+            idx.append(g)
+            val.append((packed[g >> 2] >> (2 * (g & 3))) & 3)          # (label g: bits 2(g & 3).. of byte g >> 2)
+    return np.array(pfo), np.array(fp), np.array(lo), np.concatenate(idx), np.concatenate(val)
+
+
+def write_outputs(out_dir, prefix, dumped):
+    """--dump-outputs: the dump_batch() records of the share's batches, in order, as one set of arrays over the share."""
+    os.makedirs(out_dir, exist_ok=True)
+    f_off, l_off, fps, s_idx, s_val = [np.empty(0)], [np.empty(0)], [np.empty(0)], [np.empty(0)], [np.empty(0)]
+    f_base = l_base = 0
+    for pfo, fp, lo, si, sv in dumped:
+        f_off.append(pfo[:-1] + f_base)
+        l_off.append(lo[:-1] + l_base)
+        fps.append(fp)
+        s_idx.append(si + l_base)
+        s_val.append(sv)
+        f_base += int(pfo[-1])
+        l_base += int(lo[-1])
+    arrays = {"final_pos": (fps, np.float64), "final_pos_offsets": (f_off + [[f_base]], np.float64),
+              "label_offsets": (l_off + [[l_base]], np.float64), "label_sample_index": (s_idx, np.float64),
+              "label_sample": (s_val, np.float32)}
+    for name, (parts, dtype) in arrays.items():
+        np.save(os.path.join(out_dir, prefix + name + ".npy"), np.concatenate(parts).astype(dtype))
+
+
 def scoring_roofline(alg_bytes, score_ms, committed, extra=None):
     achieved = alg_bytes / (score_ms * 1e-3) / 1e9 if score_ms > 0 else 0.0
     r = {"kernel": "interval-scoring stage: k_solve<16|32|60> (coverage, pair labels, in/out counts of a problem, in LDS) + k_dpw<16|32|60> (its DP, "
@@ -524,15 +576,22 @@ def main():
     ap.add_argument("--steps", type=int, default=20, help="timed steps; a step is the whole job (config4 on one GPU: 8 batches, ~7 ms)")
     ap.add_argument("--warmup", type=int, default=3, help="untimed steps before them (at least one; more until the GPU has been busy for 0.5 s)")
     ap.add_argument("--workload", default="config4", choices=sorted(synth.WORKLOADS) + list(NEXT_ROW_WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip both CPU-oracle legs")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the CLI end-to-end leg")
-    ap.add_argument("--no-extras", action="store_true", help="skip config2's roofline, the replay and the HBM-resident legs")
-    ap.add_argument("--no-next-rows", action="store_true", help="skip the short runs of rows N3 / N4 (cluster-many, cluster-big, isoforms) in `next_rows`")
+    ap.add_argument("--full", action="store_true", help="also every figure beside the headline: the host memory -> host memory region, "
+                    "the stage-alone rooflines, the other configs, the CPU baselines, the end-to-end leg, rows N3 / N4")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed to DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip both CPU-oracle legs")
+    ap.add_argument("--no-e2e", action="store_true", help="(--full) skip the CLI end-to-end leg")
+    ap.add_argument("--no-extras", action="store_true", help="(--full) skip config2's roofline, the replay and the HBM-resident legs")
+    ap.add_argument("--no-next-rows", action="store_true", help="(--full) skip the short runs of rows N3 / N4 (cluster-many, cluster-big, isoforms) in `next_rows`")
     ap.add_argument("--e2e-reads", type=int, default=2000000, help="reads of the end-to-end job (default: the whole 2 M-read job)")
     ap.add_argument("--contexts", type=int, default=8, help="contexts per GPU the steps alternate between (each on one stream while "
                     "the others have work in flight: two per hardware queue; 4: -20 %%, 16: -30 %%)")
     args = ap.parse_args()
+    if not args.full:
+        args.no_cpu_baseline = args.no_e2e = args.no_extras = args.no_next_rows = True
     if args.workload in NEXT_ROW_WORKLOADS:
+        if args.dump_outputs:
+            ap.error("--dump-outputs: the segmentation workloads only")
         return run_next_row(args)
 
     rank = int(os.environ.get("RANK", "0"))
@@ -675,16 +734,19 @@ def main():
             # two bits per label) is summed in the warm-up pass instead: label_popcount below
             checksum[0] += int(res[0][-1]) + int(res[2][-1]) + int(res[1].sum(dtype=np.int64))
 
-    # the timed steps: K passes over the share, batch after batch, as one stream of work for the contexts (step boundaries
-    # are not barriers: the CLI does not stop between batches either); consecutive batch-steps go to consecutive contexts
+    # (--full) `value_h2h`, the timed steps host memory -> host memory: K passes over the share, batch after batch, as one stream of
+    # work for the contexts (step boundaries are not barriers: the CLI does not stop between batches either); consecutive
+    # batch-steps go to consecutive contexts
     n_passes = args.steps * PASSES_PER_STEP
-    order = [i % n_b for i in range(n_passes * n_b)] if n_b else []
-    barrier()
-    t0 = time.perf_counter()
-    if order:
-        one_shot_steps(ctxs, batches, order, collect)
-    barrier()
-    dt = time.perf_counter() - t0
+    order, dt = [], 0.0
+    if args.full:
+        order = [i % n_b for i in range(n_passes * n_b)] if n_b else []
+        barrier()
+        t0 = time.perf_counter()
+        if order:
+            one_shot_steps(ctxs, batches, order, collect)
+        barrier()
+        dt = time.perf_counter() - t0
     n_reads = sum(batches[bi].n_reads for bi in order)
 
     # ---- `value`: the same K passes with the inputs RESIDENT IN HBM when the timed part starts (the contract's reading: a rate that
@@ -702,6 +764,10 @@ def main():
         dist.all_reduce(tg, op=dist.ReduceOp.MAX, group=coll)  # (every rank meets the same barriers)
         n_groups = int(tg[0])
     dt_res, reads_res, chk_res, pop_res, sync_timeouts, forked_runs = 0.0, 0, 0, 0, 0, 0
+    dumped = []
+    if args.dump_outputs:
+        mine, per_batch = plan_job(args.workload, rank, args.gpus)
+        dump_per_part = max(1, DUMP_LABELS // job_parts)
     for gi in range(n_groups):
         grp = list(range(gi * n_ctx, min(n_b, (gi + 1) * n_ctx)))
         runs = [0] * n_ctx
@@ -739,6 +805,9 @@ def main():
                 if pop != bk.label_popcount:
                     raise SystemExit("resident region: context %d left labels with popcount %d, the batch's is %d" % (k, pop, bk.label_popcount))
                 pop_res += pop
+                if args.dump_outputs and k < len(grp):               # (context k < len(grp) is the first that holds batch grp[k])
+                    bi = grp[k]
+                    dumped.append(dump_batch(mine[bi * per_batch:(bi + 1) * per_batch], res, dump_per_part))
             sy = ctxs[k].tap("sync")
             if len(sy) > 7:                                    # (a library of an earlier round under FSEG_LIB has no such counters)
                 sync_timeouts += int(sy[6]); forked_runs += int(sy[7])
@@ -760,11 +829,66 @@ def main():
         dt_max, total_reads, checksum_all = dt_res, float(reads_res), chk_res
         path_bytes_all, pop_res_all, sync_timeouts_all, forked_runs_all = float(path_bytes), pop_res, sync_timeouts, forked_runs
 
+    if args.dump_outputs:
+        write_outputs(args.dump_outputs, "rank%d_" % rank if world > 1 else "", dumped)
+
     if rank == 0:
         lib_hash = _lib.load().fseg_source_hash().decode()
-        committed = committed_counters(args.workload, lib_hash)
         sizes = ctxs[0].sizes()
         _, per = plan_job(args.workload, 0, args.gpus)
+        out = {
+            "metric": "reads segmented/sec (whole node)",
+            "value": total_reads / dt_max,
+            "unit": "reads/s",
+            "n_gpus": args.gpus,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "warmup_steps_run": n_warm_steps,
+            "ms_per_step": dt_max / args.steps * 1e3,
+            "passes_per_step": PASSES_PER_STEP,
+            "ms_per_pass": dt_max / max(1, n_passes) * 1e3,
+            "higher_is_better": True,
+            "scaling": "strong",
+            "vs_baseline": None,
+            "dtype": "u32",
+            "dtype_detail": "u32 bit-planes + popcount for scoring, int32 (int64 for very large partitions) DP sums, f64 Gaussian smoothing / threshold",
+            "data": "synthetic",
+            "value_is": "inputs resident in HBM when the timed part starts (the contract's reading; rounds 1-4 reported the host memory -> host "
+                        "memory rate here, now `value_h2h`): a step = fseg_run of every batch of the rank's share of the fixed job, distinct "
+                        "batches, %d contexts per GPU each holding a batch of the share, everything recomputed from the inputs each pass, results "
+                        "left in HBM (checked: one fetch per context after the timed part)" % len(ctxs),
+            "timed_s": dt_max,
+            # the fraction of the HBM roofline that belongs to `value` / `value_h2h`: SURVEY 8(d)'s algorithmic bytes of EVERY stage of the
+            # path (histogram, smoothing, threshold, candidates, interval scoring, labels) of one pass over the job, over the time of a pass
+            "roofline_path": {"bound": "hbm", "unit": "GB/s", "peak": HBM_PEAK_GBS * args.gpus, "algorithmic_bytes_per_pass": path_bytes_all,
+                              "achieved": path_bytes_all * n_passes / dt_max / 1e9 if dt_max > 0 else 0.0,
+                              "frac": path_bytes_all * n_passes / dt_max / 1e9 / (HBM_PEAK_GBS * args.gpus) if dt_max > 0 else 0.0,
+                              "what": "sum of the stages' algorithmic bytes (SURVEY 8d, every input once, every output once, reference dtypes) of one pass "
+                                      "over the job / time of a pass / (8 TB/s x GPUs): `frac` for `value` (inputs resident), `frac_h2h` for `value_h2h`"},
+            # device-side waiters (k_wait_word) of the scoring stage that reached their time limit in this process's contexts (each costs the
+            # limit + a rerun of its batch): must be 0; forked_runs = runs that owned the device (side streams in use)
+            "sync_timeouts": sync_timeouts_all,
+            "forked_runs": forked_runs_all,
+            # what carried the barriers and the reduction of the ranks' (time, reads, checksums): RCCL one GPU per rank, or gloo
+            "rank_sync": None if dist is None else (coll_note or ("rccl" if coll is not None else "gloo")),
+            "result_label_popcount_resident": pop_res_all,
+            "config": {"workload": args.workload, "partitions": job_parts, "reads": job_reads,
+                       "batches_per_step_rank0": n_b, "partitions_per_batch": per, "reads_per_batch": batches[0].n_reads if n_b else 0,
+                       "reads_per_partition": wl["n_reads"], "contexts_per_gpu": len(ctxs), "scatter": "static LPT over %d rank(s), no collective" % args.gpus,
+                       "candidates_last_batch": sizes["n_cand"], "dp_problems_last_batch": sizes["n_problems"],
+                       "positions_last_batch": sizes["n_positions"], "params": {k: params[k] for k in ("sigma", "threshold_rate")}},
+            "library_source_hash": lib_hash,
+            # counts of final positions and label bytes + the sum of the final positions, of every batch of every timed step,
+            # summed over the ranks: a property of the job (every partition exactly once per step), whatever N and however a
+            # rank's share is cut into batches; result_label_popcount: the labels that are '1' or '2' in one pass over the job
+            # (counted in the warm-up pass, outside the timed region)
+            "result_checksum": checksum_all,
+            "result_checksum_per_pass": checksum_all // max(1, n_passes),
+            "result_label_popcount": label_pop_all,
+        }
+
+    if rank == 0 and args.full:
+        committed = committed_counters(args.workload, lib_hash)
         reps = 20
         ctx = ctxs[0]
         for c2 in ctxs:
@@ -819,28 +943,7 @@ def main():
             roofline_stages[k] = e
         ctx.set_profiling(2)
 
-        out = {
-            "metric": "reads segmented/sec (whole node)",
-            "value": total_reads / dt_max,
-            "unit": "reads/s",
-            "n_gpus": args.gpus,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "warmup_steps_run": n_warm_steps,
-            "ms_per_step": dt_max / args.steps * 1e3,
-            "passes_per_step": PASSES_PER_STEP,
-            "ms_per_pass": dt_max / max(1, n_passes) * 1e3,
-            "higher_is_better": True,
-            "scaling": "strong",
-            "vs_baseline": None,
-            "dtype": "u32",
-            "dtype_detail": "u32 bit-planes + popcount for scoring, int32 (int64 for very large partitions) DP sums, f64 Gaussian smoothing / threshold",
-            "data": "synthetic",
-            "value_is": "inputs resident in HBM when the timed part starts (the contract's reading; rounds 1-4 reported the host memory -> host "
-                        "memory rate here, now `value_h2h`): a step = fseg_run of every batch of the rank's share of the fixed job, distinct "
-                        "batches, %d contexts per GPU each holding a batch of the share, everything recomputed from the inputs each pass, results "
-                        "left in HBM (checked: one fetch per context after the timed part)" % len(ctxs),
-            "timed_s": dt_max,
+        out.update({
             # rounds 1-4's `value` (pinned host memory -> results in host memory) continues HERE, at the top level
             "value_h2h": reads_h2h / dt_h2h if dt_h2h > 0 else 0.0,
             "ms_per_step_h2h": dt_h2h / args.steps * 1e3,
@@ -850,27 +953,6 @@ def main():
                             "%d contexts per GPU taking turns (PCIe-inclusive; what the CLI's workers do per batch); the figure BENCH_r01..r04 "
                             "report as `value`" % len(ctxs),
             "result_checksum_h2h": checksum_h2h,
-            # the fraction of the HBM roofline that belongs to `value` / `value_h2h`: SURVEY 8(d)'s algorithmic bytes of EVERY stage of the
-            # path (histogram, smoothing, threshold, candidates, interval scoring, labels) of one pass over the job, over the time of a pass
-            "roofline_path": {"bound": "hbm", "unit": "GB/s", "peak": HBM_PEAK_GBS * args.gpus, "algorithmic_bytes_per_pass": path_bytes_all,
-                              "achieved": path_bytes_all * n_passes / dt_max / 1e9 if dt_max > 0 else 0.0,
-                              "frac": path_bytes_all * n_passes / dt_max / 1e9 / (HBM_PEAK_GBS * args.gpus) if dt_max > 0 else 0.0,
-                              "achieved_h2h": path_bytes_all * n_passes / dt_h2h / 1e9 if dt_h2h > 0 else 0.0,
-                              "frac_h2h": path_bytes_all * n_passes / dt_h2h / 1e9 / (HBM_PEAK_GBS * args.gpus) if dt_h2h > 0 else 0.0,
-                              "what": "sum of the stages' algorithmic bytes (SURVEY 8d, every input once, every output once, reference dtypes) of one pass "
-                                      "over the job / time of a pass / (8 TB/s x GPUs): `frac` for `value` (inputs resident), `frac_h2h` for `value_h2h`"},
-            # device-side waiters (k_wait_word) of the scoring stage that reached their time limit in this process's contexts (each costs the
-            # limit + a rerun of its batch): must be 0; forked_runs = runs that owned the device (side streams in use)
-            "sync_timeouts": sync_timeouts_all,
-            "forked_runs": forked_runs_all,
-            # what carried the barriers and the reduction of the ranks' (time, reads, checksums): RCCL one GPU per rank, or gloo
-            "rank_sync": None if dist is None else (coll_note or ("rccl" if coll is not None else "gloo")),
-            "result_label_popcount_resident": pop_res_all,
-            "config": {"workload": args.workload, "partitions": job_parts, "reads": job_reads,
-                       "batches_per_step_rank0": n_b, "partitions_per_batch": per, "reads_per_batch": batches[0].n_reads if n_b else 0,
-                       "reads_per_partition": wl["n_reads"], "contexts_per_gpu": len(ctxs), "scatter": "static LPT over %d rank(s), no collective" % args.gpus,
-                       "candidates_last_batch": sizes["n_cand"], "dp_problems_last_batch": sizes["n_problems"],
-                       "positions_last_batch": sizes["n_positions"], "params": {k: params[k] for k in ("sigma", "threshold_rate")}},
             "roofline": roofline,
             "roofline_concurrent": scoring_roofline(alg_total[0] / max(1, len(order)), score_ms_total[0] / max(1, len(order)), committed,
                                                     {"measured": "the same bracket inside the timed steps (the other contexts' kernels run inside it)"}),
@@ -879,15 +961,9 @@ def main():
                                     "interval_scoring includes the DP" % n_st,
             "valu_util": (committed or {}).get("valu_util"),
             "valu_util_source": (committed or {}).get("valu_source"),
-            "library_source_hash": lib_hash,
-            # counts of final positions and label bytes + the sum of the final positions, of every batch of every timed step,
-            # summed over the ranks: a property of the job (every partition exactly once per step), whatever N and however a
-            # rank's share is cut into batches; result_label_popcount: the labels that are '1' or '2' in one pass over the job
-            # (counted in the warm-up pass, outside the timed region)
-            "result_checksum": checksum_all,
-            "result_checksum_per_pass": checksum_all // max(1, n_passes),
-            "result_label_popcount": label_pop_all,
-        }
+        })
+        out["roofline_path"].update(achieved_h2h=path_bytes_all * n_passes / dt_h2h / 1e9 if dt_h2h > 0 else 0.0,
+                                    frac_h2h=path_bytes_all * n_passes / dt_h2h / 1e9 / (HBM_PEAK_GBS * args.gpus) if dt_h2h > 0 else 0.0)
         out["value_resident_replay"] = {"value": batches[0].n_reads * reps / dt_r, "unit": "reads/s", "ms_per_step": dt_r / reps * 1e3,
                                         "what": "replay of one resident batch of the job (%d reads): no copies, no arena sizing (a batch, not the job)" % batches[0].n_reads}
         if not args.no_extras:
@@ -1008,6 +1084,7 @@ def main():
                 ctx.close()
             ctxs = []
             out["next_rows"] = next_rows_summary()
+    if rank == 0:
         print(json.dumps(out))
     for ctx in ctxs:
         ctx.close()

@@ -12,7 +12,7 @@ import sys
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-COMMON = ["--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-e2e", "--no-extras", "--contexts", "2"]
+COMMON = ["--full", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-e2e", "--no-extras", "--contexts", "2"]
 
 
 def _free_port():
@@ -61,7 +61,7 @@ def test_two_ranks_on_one_gpu_report_the_same_job():
 def _ranks(n, workload, env_extra):
     """bench.py under torch.distributed.run with n gloo ranks on the one card, and the one-rank run of the same job."""
     env = dict(os.environ, FREDDIE_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0", FREDDIE_BENCH_PASSES="2", **env_extra)
-    common = ["--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-e2e", "--no-extras", "--workload", workload, "--contexts", "8"]
+    common = ["--full", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-e2e", "--no-extras", "--workload", workload, "--contexts", "8"]
     many = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=%d" % n, "--master-addr", "127.0.0.1",
                            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", str(n)] + common,
                           cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=1500)
@@ -111,3 +111,49 @@ def test_the_rccl_branch_with_the_one_rank_a_one_gpu_box_allows():
     assert r["rank_sync"] == "rccl", (r["rank_sync"], run.stderr[-2000:])
     assert r["n_gpus"] == 1 and r["value"] > 0 and r["value_h2h"] > 0 and r["sync_timeouts"] == 0
     assert r["result_checksum"] == r["result_checksum_h2h"] > 0
+
+
+@pytest.mark.gpu
+def test_plain_run_and_the_outputs_of_its_last_step(tmp_path):
+    """A plain run times the headline and nothing else (no host memory -> host memory region, no stage-alone figures), and
+    --dump-outputs writes what its last timed step computed: the same arrays as a --full run of the job cut into other batches
+    (four of 500 k reads on two contexts: two groups), the line's per-pass checksum, and the oracle's results where checked."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    import util
+    from freddie_amd import pack, synth
+    runs = {}
+    for name, batch_reads, extra in (("plain", "1000000", []), ("full", "500000", ["--full", "--no-cpu-baseline", "--no-e2e", "--no-extras"])):
+        d = tmp_path / name
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--contexts", "2",
+                            "--dump-outputs", str(d)] + extra, cwd=ROOT, env=dict(os.environ, FREDDIE_BENCH_BATCH_READS=batch_reads, FREDDIE_BENCH_PASSES="2"),
+                           stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
+        assert p.returncode == 0, p.stderr[-3000:]
+        runs[name] = (_last_json(p.stdout), {f[:-4]: np.load(str(d / f)) for f in sorted(os.listdir(str(d)))})
+    (plain, got), (full, got_full) = runs["plain"], runs["full"]
+    assert plain["steps"] == 3 and plain["passes_per_step"] == 2 and plain["value"] > 0 and plain["ms_per_step"] > 0
+    assert plain["ms_per_step"] == pytest.approx(plain["timed_s"] * 1e3 / 3)
+    for k in ("metric", "unit", "higher_is_better", "dtype", "result_checksum", "result_label_popcount"):
+        assert plain[k] == full[k], k
+    assert plain["config"]["batches_per_step_rank0"] == 2 and full["config"]["batches_per_step_rank0"] == 4
+    for k in ("value_h2h", "roofline", "roofline_stages", "value_resident_replay", "cpu_baseline", "e2e"):
+        assert k not in plain and k in full, k
+    assert sorted(got) == sorted(got_full) == ["final_pos", "final_pos_offsets", "label_offsets", "label_sample", "label_sample_index"]
+    for k, a in got.items():
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, got_full[k]), k
+    assert sum(a.nbytes for a in got.values()) <= 64 << 20
+    fp, f_off, l_off = got["final_pos"], got["final_pos_offsets"], got["label_offsets"]
+    assert len(f_off) == len(l_off) == 4001 and f_off[-1] == len(fp)
+    assert len(fp) + int(l_off[-1]) + int(fp.sum()) == plain["result_checksum_per_pass"]
+    idx = got["label_sample_index"].astype(np.int64)
+    assert len(idx) == bench.DUMP_LABELS // 4000 * 4000 and np.all(np.diff(idx) >= 0) and idx[-1] < l_off[-1]
+    w = dict(synth.WORKLOADS["config4"])
+    w.pop("n_partitions")
+    for i in (0, 1999, 3999):
+        g = synth.generate(i, with_seq=False, **w)
+        o = util.run_oracle(pack.pack_partition(g.iv_start, g.iv_end, g.read_exon_off, g.ex_ts, g.ex_te, dedupe=True), dict(bench.PARAMS["default"]))
+        assert np.array_equal(fp[int(f_off[i]):int(f_off[i + 1])], o["final_pos"]), i
+        mine = (idx >= l_off[i]) & (idx < l_off[i + 1])
+        assert mine.sum() == bench.DUMP_LABELS // 4000
+        assert np.array_equal(got["label_sample"][mine], np.asarray(o["labels"]).ravel()[idx[mine] - int(l_off[i])]), i

@@ -2,7 +2,7 @@
 """Measurement of row N3 (clustering pre-ILP graph work) on MI355X: pairwise compatibility + pruning of a batch of
 synthetic preprocessed tints through include/freddie_cluster.h.
 
-    python bench.py --workload cluster-many|cluster-big [--steps K] [--no-cpu-baseline]     (with the CPU baseline)
+    python bench.py --full --workload cluster-many|cluster-big [--steps K] [--no-cpu-baseline]     (with the CPU baseline)
     python tools/cluster_bench.py [--workload many|big] [--steps K]                          (GPU side only)
 
 One JSON line: read pairs tested per second of the CALL (packed host arrays in -> pruned adjacency in host memory: copies,

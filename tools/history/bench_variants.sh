@@ -7,5 +7,5 @@ i=0
 for cfg in "$@"; do
   i=$((i+1))
   echo "== $cfg"
-  env $cfg timeout -k 10 400 python bench.py --no-cpu-baseline --no-e2e --steps 192 > $O/bench_$i.json 2> $O/bench_$i.err; python profiles/benchsum.py < $O/bench_$i.json | head -1
+  env $cfg timeout -k 10 400 python bench.py --full --no-cpu-baseline --no-e2e --steps 192 > $O/bench_$i.json 2> $O/bench_$i.err; python profiles/benchsum.py < $O/bench_$i.json | head -1
 done

@@ -7,5 +7,5 @@ i=0
 for cfg in "$@"; do
   i=$((i+1))
   echo "== $WL $cfg"
-  env $cfg timeout -k 10 500 python bench.py --workload $WL --no-cpu-baseline --no-e2e --steps $ST > $O/bench_${WL}_$i.json 2> $O/bench_${WL}_$i.err; python profiles/benchsum.py < $O/bench_${WL}_$i.json | head -1
+  env $cfg timeout -k 10 500 python bench.py --full --workload $WL --no-cpu-baseline --no-e2e --steps $ST > $O/bench_${WL}_$i.json 2> $O/bench_${WL}_$i.err; python profiles/benchsum.py < $O/bench_${WL}_$i.json | head -1
 done

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Measurement of row N4 (isoform consensus counts + boundary votes) on MI355X through include/freddie_isoforms.h.
 
-    python bench.py --workload isoforms [--steps K] [--no-cpu-baseline]                                (with the CPU baseline)
+    python bench.py --full --workload isoforms [--steps K] [--no-cpu-baseline]                         (with the CPU baseline)
     python tools/isoforms_bench.py [--isoforms N] [--reads-per-isoform R] [--segments M] [--steps K]     (GPU side only)
 
 One JSON line: reads processed per second of the two CALLS (host arrays in -> counts / votes in host memory; the 300 MB of

@@ -11,11 +11,11 @@ mkdir -p $O
 # limit is 20 minutes); default: everything
 if [[ "${PART:-all}" =~ ^(all|1)$ ]]; then
 # 1. the driver's command, plain and under the kernel trace (same command: the averages must agree with the line's events)
-python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err; python profiles/benchsum.py < $O/bench_default.json
+python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err; python profiles/benchsum.py < $O/bench_default.json
 # (FREDDIE_BENCH_PASSES=1: a step = ONE pass over the job, as until round 5.  With the default 16 passes a step -- 330 k dispatches in
 # the process -- rocprofv3 7.2 dies of a SIGSEGV inside its own queue interception a few seconds in, whichever library is loaded,
 # round 5's too; one stream per context (FSEG_NO_FORK=1) survives.  Kernel durations do not depend on the number of passes.)
-FREDDIE_BENCH_PASSES=1 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o p -- python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-e2e > $O/bench_under_rocprof.json 2> $O/stats.err
+FREDDIE_BENCH_PASSES=1 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o p -- python3 bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-e2e > $O/bench_under_rocprof.json 2> $O/stats.err
 python profiles/benchsum.py < $O/bench_under_rocprof.json | head -1
 python profiles/trace_medians.py $O/stats/p_kernel_trace.csv > $O/config4_kernel_medians_8ctx.txt
 python tools/waiter_trace.py $O/stats/p_kernel_trace.csv 3 > $O/config4_waiters_8ctx.txt
@@ -55,10 +55,10 @@ rocprofv3 --kernel-trace --output-format csv -d $O/trace3c -o p -- python3 tools
 python tools/stage_timeline.py $O/trace3c/p_kernel_trace.csv > $O/config3_stage_timeline.txt; python tools/stage_span.py $O/trace3c/p_kernel_trace.csv > $O/config3_stage_span.txt; grep replay $O/replay_config3_plan.txt | cut -c1-120 >> $O/config3_stage_span.txt; cat $O/config3_stage_span.txt
 rm -rf $O/trace3c
 # 4. the other workloads, rows N3 / N4, end to end, the host alone
-for w in config2 config3 config5; do python bench.py --workload $w --no-cpu-baseline --no-e2e > $O/${w}_bench.json 2>/dev/null; python profiles/benchsum.py < $O/${w}_bench.json | head -1; done
-python bench.py --workload cluster-many > $O/n3_cluster_many_bench.json 2>/dev/null
-python bench.py --workload cluster-big --steps 2 --no-cpu-baseline > $O/n3_cluster_big_bench.json 2>/dev/null
-python bench.py --workload isoforms > $O/n4_isoforms_bench.json 2>/dev/null
+for w in config2 config3 config5; do python bench.py --full --workload $w --no-cpu-baseline --no-e2e > $O/${w}_bench.json 2>/dev/null; python profiles/benchsum.py < $O/${w}_bench.json | head -1; done
+python bench.py --full --workload cluster-many > $O/n3_cluster_many_bench.json 2>/dev/null
+python bench.py --full --workload cluster-big --steps 2 --no-cpu-baseline > $O/n3_cluster_big_bench.json 2>/dev/null
+python bench.py --full --workload isoforms > $O/n4_isoforms_bench.json 2>/dev/null
 python tools/e2e_bench.py --partitions 4000 --reads 500 --generate-only --keep /dev/shm/e2e_$T > /dev/null
 for t in 8 16 32; do python tools/e2e_bench.py --partitions 4000 --reads 500 --threads $t --sidecar off --repeat 2 --timing --keep /dev/shm/e2e_$T >> $O/e2e.log 2>&1; done
 rm -rf /dev/shm/e2e_$T
@@ -74,6 +74,6 @@ grep "e2e\[" $O/e2e.log; cat $O/host_ceiling.txt
 fi
 if [[ "${PART:-all}" =~ ^(all|1)$ ]]; then
 # the driver's command once more, now that profiles/traffic.json carries this library's hash: bench_default.json (again) holds roofline.traffic / valu_util
-python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err; python profiles/benchsum.py < $O/bench_default.json
+python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err; python profiles/benchsum.py < $O/bench_default.json
 rm -rf $O/stats/*.csv.tmp
 fi
