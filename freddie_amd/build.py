@@ -7,6 +7,8 @@
   ``freddie_amd.cluster_prep.build``)
 * ``libfreddie_isoforms.so`` -- gfx950 kernels + C-ABI of the isoform-consensus stage's per-read loops (hipcc; built by
   ``freddie_amd.isoforms.build``)
+* ``libfreddie_vis.so`` -- gfx950 kernels + C-ABI of the segmentation-visualisation script's per-object loop (hipcc; built by
+  ``freddie_amd.segment_vis.build``)
 * ``synth/libfreddie_synth.so`` -- synthetic split-partition generator (gcc; test/bench infrastructure)
 
 The oracle (``oracle/``) is test infrastructure and is built by ``oracle/Makefile``; it is never
@@ -153,11 +155,12 @@ def build_host(force=False, verbose=False):
 
 
 def build_all(force=False, verbose=False):
-    from . import cluster_prep, isoforms, synth
+    from . import cluster_prep, isoforms, segment_vis, synth
     build_seg(force, verbose)
     build_host(force, verbose)
     cluster_prep.build(force, verbose)
     isoforms.build(force, verbose)
+    segment_vis.build(force, verbose)
     synth.build(force)
     return SEG_SO
 
