@@ -8,10 +8,11 @@ Reference map (file:line of vpc-ccg/freddie ``py/freddie_cluster.py``):
   preprocess_ilp :277-328      -> preprocess_ilp()        I / C / FL / garbage_cost, poly-tail categories
   split_list_evenly :112-116   -> split_list_evenly()
   partition_reads :196-274     -> partition_reads(), partition_reads_batch()
-       unique structures :203-215 (host), pairwise compatibility :217-234 and edge pruning :240-255 (GPU),
-       connected components :256-257, even split and incompatible pairs :258-274 (host)
-The ILP (run_ilp, Gurobi) and everything after it are out of scope.  There is no CPU implementation of the two
-quadratic loops in this package: without the HIP library partition_reads() raises.
+       unique structures :203-215 (host); pairwise compatibility :217-234, edge pruning :240-255, connected components
+       :256-257, even split and incompatible pairs :258-274 (GPU: Context.partition, flat arrays)
+The ILP (run_ilp, Gurobi) and everything after it are out of scope.  There is no CPU implementation of the quadratic
+loops in this package: without the HIP library partition_reads() raises.  FCLU_HOST_PARTITIONS=1 keeps :256-274 on the
+host, behind the GPU's graph (adjacency_matrix + _components + _partitions_from_graph): for A/B runs and timings.
 """
 import ctypes
 import os
@@ -147,18 +148,31 @@ def split_list_evenly(l, m):
 # ---------------------------------------------------------------------------------------------------------------
 CLUSTER_SO = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libfreddie_cluster.so")
 CLUSTER_SRC = [os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "freddie_cluster.hip")]
-EXPORTS = ["fclu_abi_version", "fclu_create", "fclu_destroy", "fclu_last_error", "fclu_compat_graph", "fclu_last_timing"]
+EXPORTS = ["fclu_abi_version", "fclu_create", "fclu_destroy", "fclu_last_error", "fclu_compat_graph", "fclu_last_timing",
+           "fclu_partition", "fclu_partition_adj", "fclu_partition_results", "fclu_partition_timing"]
+ERR_UNSUPPORTED = 3
 _lib = None
 
 
 class ClusterError(RuntimeError):
-    pass
+    """code: the library's return value (FCLU_ERR_*), or None when the error is this module's own."""
+
+    def __init__(self, message, code=None):
+        RuntimeError.__init__(self, message)
+        self.code = code
 
 
 class _Batch(ctypes.Structure):
     _fields_ = [("n_tint", ctypes.c_int32), ("row_off", ctypes.c_void_p), ("n_seg", ctypes.c_void_p),
                 ("bits_off", ctypes.c_void_p), ("bits", ctypes.c_void_p), ("first", ctypes.c_void_p),
                 ("last", ctypes.c_void_p), ("tail", ctypes.c_void_p), ("adj_off", ctypes.c_void_p)]
+
+
+class _Parts(ctypes.Structure):
+    _fields_ = [("n_tint", ctypes.c_int32), ("n_rows", ctypes.c_int64), ("n_part", ctypes.c_int64), ("n_rids", ctypes.c_int64),
+                ("n_pairs", ctypes.c_int64), ("tint_part_off", ctypes.c_void_p), ("part_node_off", ctypes.c_void_p),
+                ("part_nodes", ctypes.c_void_p), ("part_rid_off", ctypes.c_void_p), ("part_rids", ctypes.c_void_p),
+                ("part_pair_off", ctypes.c_void_p), ("pairs", ctypes.c_void_p), ("label", ctypes.c_void_p)]
 
 
 def build(force=False, verbose=False):
@@ -187,8 +201,24 @@ def load():
     L.fclu_compat_graph.argtypes = [vp, ctypes.POINTER(_Batch), ctypes.c_int32, vp, vp]
     L.fclu_last_timing.restype = ctypes.c_int
     L.fclu_last_timing.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
+    L.fclu_partition.restype = ctypes.c_int
+    L.fclu_partition.argtypes = [vp, ctypes.POINTER(_Batch), vp, vp, ctypes.c_int32]
+    L.fclu_partition_adj.restype = ctypes.c_int
+    L.fclu_partition_adj.argtypes = [vp, ctypes.c_int32, vp, vp, vp, vp, vp, ctypes.c_int32]
+    L.fclu_partition_results.restype = ctypes.c_int
+    L.fclu_partition_results.argtypes = [vp, ctypes.POINTER(_Parts)]
+    L.fclu_partition_timing.restype = ctypes.c_int
+    L.fclu_partition_timing.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
     _lib = L
     return L
+
+
+def _copy_out(ptr, n, dtype):
+    """numpy copy of n items behind a pointer of the library (its buffers live only until the context's next call)."""
+    dtype = np.dtype(dtype)
+    if n == 0:
+        return np.zeros(0, dtype)
+    return np.frombuffer((ctypes.c_char * (n * dtype.itemsize)).from_address(ptr), dtype, n).copy()
 
 
 class Context:
@@ -202,8 +232,8 @@ class Context:
             raise ClusterError("fclu_create: " + self._L.fclu_last_error(None).decode())
         self._h = h
 
-    def compat_graph(self, packed, prune=True):
-        """packed: pack_structures() of a batch.  Returns (adj uint64[adj_off[-1]], rounds int32[n_tint])."""
+    @staticmethod
+    def _batch(packed):
         b = _Batch(n_tint=packed["n_tint"])
         keep = []
         for name, dt in (("row_off", np.int64), ("n_seg", np.int32), ("bits_off", np.int64), ("bits", np.uint32),
@@ -211,12 +241,67 @@ class Context:
             a = np.ascontiguousarray(packed[name], dt)
             keep.append(a)
             setattr(b, name, a.ctypes.data if a.size else None)
+        return b, keep
+
+    def compat_graph(self, packed, prune=True):
+        """packed: pack_structures() of a batch.  Returns (adj uint64[adj_off[-1]], rounds int32[n_tint])."""
+        b, keep = self._batch(packed)
         adj = np.zeros(max(int(packed["adj_off"][-1]), 1), np.uint64)
         rounds = np.zeros(packed["n_tint"], np.int32)
         rc = self._L.fclu_compat_graph(self._h, ctypes.byref(b), 1 if prune else 0, adj.ctypes.data, rounds.ctypes.data)
         if rc != 0:
-            raise ClusterError("fclu_compat_graph: " + self._L.fclu_last_error(self._h).decode())
+            raise ClusterError("fclu_compat_graph: " + self._L.fclu_last_error(self._h).decode(), rc)
         return adj[:int(packed["adj_off"][-1])], rounds
+
+    def _partition_arrays(self, what, rc):
+        if rc != 0:
+            raise ClusterError(what + ": " + self._L.fclu_last_error(self._h).decode(), rc)
+        p = _Parts()
+        rc = self._L.fclu_partition_results(self._h, ctypes.byref(p))
+        if rc != 0:
+            raise ClusterError("fclu_partition_results: " + self._L.fclu_last_error(self._h).decode(), rc)
+        P = int(p.n_part)
+        return dict(tint_part_off=_copy_out(p.tint_part_off, p.n_tint + 1, np.int64),
+                    part_node_off=_copy_out(p.part_node_off, P + 1, np.int64), part_nodes=_copy_out(p.part_nodes, int(p.n_rows), np.int32),
+                    part_rid_off=_copy_out(p.part_rid_off, P + 1, np.int64), part_rids=_copy_out(p.part_rids, int(p.n_rids), np.int32),
+                    part_pair_off=_copy_out(p.part_pair_off, P + 1, np.int64),
+                    pairs=_copy_out(p.pairs, 2 * int(p.n_pairs), np.int32).reshape(-1, 2), label=_copy_out(p.label, int(p.n_rows), np.int32))
+
+    @staticmethod
+    def _members(members):
+        mem_off = np.ascontiguousarray(members["mem_off"], np.int64)
+        mem = np.ascontiguousarray(members["mem"], np.int32)
+        return mem_off, mem
+
+    def partition(self, packed, members, maximum_ilp_size):
+        """partition_reads() behind the dedupe for a batch, on the device: packed = pack_structures(), members = pack_members().
+        Returns numpy arrays (include/freddie_cluster.h, fclu_parts): tint_part_off [T+1]; per partition part_node_off /
+        part_rid_off / part_pair_off [P+1] into part_nodes (node indices local to the tint), part_rids and pairs (int32 [n, 2]);
+        label (the smallest node of each unique read's component)."""
+        b, keep = self._batch(packed)
+        mem_off, mem = self._members(members)
+        if mem_off.size != int(packed["row_off"][-1]) + 1:
+            raise ClusterError("partition: mem_off has %d entries for %d rows" % (mem_off.size, int(packed["row_off"][-1])))
+        rc = self._L.fclu_partition(self._h, ctypes.byref(b), mem_off.ctypes.data, mem.ctypes.data if mem.size else None,
+                                    int(maximum_ilp_size))
+        return self._partition_arrays("fclu_partition", rc)
+
+    def partition_adj(self, row_off, adj_off, adj, members, maximum_ilp_size):
+        """The same behind a graph of the caller's: adj in the layout compat_graph() returns (symmetric, empty diagonal)."""
+        row_off = np.ascontiguousarray(row_off, np.int64)
+        adj_off = np.ascontiguousarray(adj_off, np.int64)
+        adj = np.ascontiguousarray(adj, np.uint64)
+        mem_off, mem = self._members(members)
+        if row_off.size < 2 or adj_off.size != row_off.size or adj.size != int(adj_off[-1]) or mem_off.size != int(row_off[-1]) + 1:
+            raise ClusterError("partition_adj: array lengths do not match (row_off, adj_off: T + 1; adj: adj_off[-1]; mem_off: rows + 1)")
+        rc = self._L.fclu_partition_adj(self._h, row_off.size - 1, row_off.ctypes.data, adj_off.ctypes.data, adj.ctypes.data if adj.size else None,
+                                        mem_off.ctypes.data, mem.ctypes.data if mem.size else None, int(maximum_ilp_size))
+        return self._partition_arrays("fclu_partition_adj", rc)
+
+    def partition_timing(self):
+        a, b = ctypes.c_float(), ctypes.c_float()
+        self._L.fclu_partition_timing(self._h, ctypes.byref(a), ctypes.byref(b))
+        return dict(components_ms=a.value, pairs_ms=b.value)
 
     def last_timing(self):
         a, b = ctypes.c_float(), ctypes.c_float()
@@ -279,6 +364,15 @@ def pack_structures(unique_per_tint):
                 last=np.array(last, np.int32), tail=np.array(tail, np.uint8), adj_off=adj_off)
 
 
+def pack_members(unique_per_tint):
+    """dict(mem_off int64[rows + 1], mem int32): the rep ids of every unique row of the batch, rows in pack_structures() order."""
+    counts = [len(u[1]) for uniq in unique_per_tint for u in uniq]
+    mem_off = np.zeros(len(counts) + 1, np.int64)
+    np.cumsum(counts, out=mem_off[1:])
+    mem = np.fromiter((rid for uniq in unique_per_tint for u in uniq for rid in u[1]), np.int32, int(mem_off[-1]))
+    return dict(mem_off=mem_off, mem=mem)
+
+
 def adjacency_matrix(adj, packed, t):
     """Boolean N_t x N_t matrix of tint t from the packed result."""
     n = int(packed["row_off"][t + 1] - packed["row_off"][t])
@@ -319,13 +413,48 @@ def _partitions_from_graph(unique, A, maximum_ilp_size, verbose):
     return parts
 
 
-def partition_reads_batch(tints, maximum_ilp_size, ctx, verbose=True):
-    """partition_reads() of several preprocessed tints with one device call; sets tint['partitions'] on each."""
+def partition_arrays_batch(tints, maximum_ilp_size, ctx):
+    """partition_reads() of several preprocessed tints as the flat arrays of Context.partition(): one device call."""
+    uniq = [unique_structures(t) for t in tints]
+    return ctx.partition(pack_structures(uniq), pack_members(uniq), maximum_ilp_size)
+
+
+def _partitions_from_arrays(arr, t, verbose):
+    """tint['partitions'] of tint t of the batch: [(rep ids, [(rid_1, rid_2), ...]), ...]."""
+    parts = []
+    node_off, rid_off, pair_off = arr["part_node_off"], arr["part_rid_off"], arr["part_pair_off"]
+    for q in range(int(arr["tint_part_off"][t]), int(arr["tint_part_off"][t + 1])):
+        if verbose:
+            c = arr["part_nodes"][node_off[q]:node_off[q + 1]].tolist()
+            print(len(c), c[:10])                           # the reference prints this line (:262)
+        pairs = arr["pairs"][pair_off[q]:pair_off[q + 1]]
+        parts.append((arr["part_rids"][rid_off[q]:rid_off[q + 1]].tolist(), list(zip(pairs[:, 0].tolist(), pairs[:, 1].tolist()))))
+    return parts
+
+
+def _partition_reads_host_tail(tints, maximum_ilp_size, ctx, verbose):
     uniq = [unique_structures(t) for t in tints]
     packed = pack_structures(uniq)
     adj, _ = ctx.compat_graph(packed, prune=True)
     for t, tint in enumerate(tints):
         tint["partitions"] = _partitions_from_graph(uniq[t], adjacency_matrix(adj, packed, t), maximum_ilp_size, verbose)
+
+
+def partition_reads_batch(tints, maximum_ilp_size, ctx, verbose=True):
+    """partition_reads() of several preprocessed tints with one device call; sets tint['partitions'] on each.  A batch whose
+    pair list the library refuses as too large for one call goes tint by tint."""
+    if os.environ.get("FCLU_HOST_PARTITIONS", "0") == "1":
+        return _partition_reads_host_tail(tints, maximum_ilp_size, ctx, verbose)
+    try:
+        arr = partition_arrays_batch(tints, maximum_ilp_size, ctx)
+    except ClusterError as e:
+        if e.code != ERR_UNSUPPORTED or len(tints) < 2:
+            raise
+        for tint in tints:
+            partition_reads_batch([tint], maximum_ilp_size, ctx, verbose)
+        return
+    for t, tint in enumerate(tints):
+        tint["partitions"] = _partitions_from_arrays(arr, t, verbose)
 
 
 def partition_reads(tint, maximum_ilp_size, ctx=None, verbose=True):

@@ -1,6 +1,7 @@
 // freddie_cluster.hip -- gfx950 kernels + C-ABI (include/freddie_cluster.h) for the pre-ILP work of the clustering
 // stage: the pairwise read-compatibility graph of partition_reads() (py/freddie_cluster.py:217-234) and its iterated
-// edge pruning (:240-255), for a batch of tints per call.
+// edge pruning (:240-255), for a batch of tints per call; and, behind the pruned graph on the device, the rest of the function
+// (fclu_partition): connected components (:256-257), the even split (:258-260) and the incompatible rep pairs (:261-273).
 //
 // Reads are bit rows (bit s = the read covers segment s), so the reference's two list comprehensions over the
 // overlap [f, l] (:229, :232) become popcounts of (a & b & mask) and ((a ^ b) & mask).  The graph is a symmetric
@@ -12,6 +13,8 @@
 #include "freddie_cluster.h"
 
 #include <hip/hip_runtime.h>
+#include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_scan.hpp>
 
 #include <algorithm>
 #include <cstdarg>
@@ -32,7 +35,8 @@ constexpr int kMaxWords = 300;      // uint32 words per read row the LDS staging
 struct TintDesc {
     i64 row0, bits_off, adj_off;
     int n, n_seg, w, aw;            // rows, segments, uint32 words per read row, uint64 words per adjacency row
-    int in_lds, pad;                // the tint's pruning runs whole in one workgroup's LDS (k_prune_lds): the per-pass kernels skip its rows
+    int in_lds;                     // the tint's pruning runs whole in one workgroup's LDS (k_prune_lds): the per-pass kernels skip its rows
+    int cc_lds;                     // the same for its connected components (k_cc_lds)
 };
 
 __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
@@ -400,9 +404,225 @@ __global__ void __launch_bounds__(256) k_prune_lds(const int *small_tints, const
     if (threadIdx.x == 0) rounds[t] = n_rounds;
 }
 
+// ================================================================================================================
+// The rest of partition_reads() (py/freddie_cluster.py:256-274) on the pruned matrix, where the pruning left it.
+// ================================================================================================================
+// ---- connected components (:256-257) -------------------------------------------------------------------------
+// parent[] over the rows of the whole batch (global row indices; a row starts as its own parent).  A pass is
+//   hook:  m = the smallest parent among v's neighbours; when m < parent[v], both parent[v] and parent[parent[v]] take m (atomic min)
+//   jump:  parent[v] = the root of v's chain (follow parent until it stops moving)
+// and passes repeat until one changes nothing (hooking plus pointer jumping in the style of Shiloach-Vishkin / FastSV: a path of
+// 1 000 nodes takes about ten passes, where neighbour-minimum propagation alone takes 1 000).  Every value a parent ever holds is a
+// node of v's own component that is no larger than v, and values only fall; so a read that races with a write sees an older, larger,
+// still valid value, and the one state in which a pass changes nothing is parent[v] = the smallest node of v's component: its
+// label, which orders the components as networkx yields them (by first node).
+__global__ void __launch_bounds__(256) k_cc_init(i64 n_rows_total, int *parent) {
+    for (i64 r = (i64)blockIdx.x * blockDim.x + threadIdx.x; r < n_rows_total; r += (i64)gridDim.x * blockDim.x) parent[r] = (int)r;
+}
+
+// `gate`: as in the pruning passes, the "something changed" word of the previous pass of the burst.
+__global__ void __launch_bounds__(256) k_cc_hook(i64 n_rows_total, const int *row_tint, const TintDesc *tints, const u64 *adj, int *parent,
+                                                 int *pass_any, const int *gate) {
+    if (gate && *gate == 0) return;
+    const int lane = lane_id();
+    const i64 wave_g = ((i64)blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = ((i64)gridDim.x * blockDim.x) >> 6;
+    for (i64 r = wave_g; r < n_rows_total; r += n_waves) {
+        const TintDesc d = tints[row_tint[r]];
+        if (d.cc_lds) continue;
+        const u64 *a = adj + d.adj_off + (r - d.row0) * d.aw;
+        const int pv = parent[r];
+        int m = pv;
+        for (int z = lane; z < d.aw; z += 64) {
+            u64 word = a[z];
+            while (word) {
+                const int u = z * 64 + __ffsll((long long)word) - 1;
+                word &= word - 1;
+                const int pu = parent[d.row0 + u];
+                m = pu < m ? pu : m;
+            }
+        }
+        for (int s = 32; s >= 1; s >>= 1) { const int o = __shfl_xor(m, s); m = o < m ? o : m; }
+        if (lane == 0 && m < pv) { atomicMin(&parent[pv], m); atomicMin(&parent[r], m); *pass_any = 1; }
+    }
+}
+
+__global__ void __launch_bounds__(256) k_cc_jump(i64 n_rows_total, const int *row_tint, const TintDesc *tints, int *parent, int *pass_any,
+                                                 const int *gate) {
+    if (gate && *gate == 0) return;
+    for (i64 r = (i64)blockIdx.x * blockDim.x + threadIdx.x; r < n_rows_total; r += (i64)gridDim.x * blockDim.x) {
+        if (tints[row_tint[r]].cc_lds) continue;
+        const int p0 = parent[r];
+        int p = p0, q = parent[p];
+        while (q != p) { p = q; q = parent[p]; }          // (strictly falling: it ends at a root)
+        if (p != p0) { parent[r] = p; *pass_any = 1; }
+    }
+}
+
+// A tint whose matrix fits one workgroup's LDS (the pruning's own criterion, kPruneLdsWords): the same passes by one workgroup, to the
+// end, with no flag to the host.
+__global__ void __launch_bounds__(256) k_cc_lds(const int *small_tints, const TintDesc *tints, const u64 *adj, int *parent) {
+    extern __shared__ __align__(16) unsigned char lds_raw[];
+    __shared__ int s_changed;
+    const TintDesc d = tints[small_tints[blockIdx.x]];
+    const int n = d.n, aw = d.aw, nw = n * aw;
+    u64 *A = reinterpret_cast<u64 *>(lds_raw);
+    int *par = reinterpret_cast<int *>(A + nw);
+    for (int x = threadIdx.x; x < nw; x += blockDim.x) A[x] = adj[d.adj_off + x];
+    for (int v = threadIdx.x; v < n; v += blockDim.x) par[v] = v;
+    for (;;) {
+        if (threadIdx.x == 0) s_changed = 0;
+        __syncthreads();
+        for (int v = threadIdx.x; v < n; v += blockDim.x) {
+            const int pv = par[v];
+            int m = pv;
+            for (int z = 0; z < aw; ++z) {
+                u64 word = A[v * aw + z];
+                while (word) {
+                    const int u = z * 64 + __ffsll((long long)word) - 1;
+                    word &= word - 1;
+                    const int pu = par[u];
+                    m = pu < m ? pu : m;
+                }
+            }
+            if (m < pv) { atomicMin(&par[pv], m); atomicMin(&par[v], m); s_changed = 1; }
+        }
+        __syncthreads();
+        for (int v = threadIdx.x; v < n; v += blockDim.x) {
+            const int p0 = par[v];
+            int p = p0, q = par[p];
+            while (q != p) { p = q; q = par[p]; }
+            if (p != p0) { par[v] = p; s_changed = 1; }
+        }
+        __syncthreads();
+        const int any = s_changed;
+        __syncthreads();                                        // (everybody has read the flag before the next pass clears it)
+        if (!any) break;
+    }
+    for (int v = threadIdx.x; v < n; v += blockDim.x) parent[d.row0 + v] = (int)d.row0 + par[v];
+}
+
+// ---- even split of the components (:258-260, split_list_evenly :112-116) -----------------------------------------
+// The rows of the batch, sorted (stable) by their label, are the partitions' node lists laid end to end: tints in order, in a tint
+// the components by their smallest node, in a component the nodes ascending, and a chunk is a run of s of them.  skey / sval = label
+// and row at sorted position k.  A label is its component's smallest row, so it is also the row at the component's first position.
+__global__ void __launch_bounds__(256) k_bounds(i64 n_rows_total, const unsigned *skey, int *comp_start, int *comp_end) {
+    for (i64 k = (i64)blockIdx.x * blockDim.x + threadIdx.x; k < n_rows_total; k += (i64)gridDim.x * blockDim.x) {
+        const unsigned key = skey[k];
+        if (k == 0 || skey[k - 1] != key) comp_start[key] = (int)k;
+        if (k == n_rows_total - 1 || skey[k + 1] != key) comp_end[key] = (int)(k + 1);
+    }
+}
+
+// Per sorted position (and one entry behind the last, all zero, for the scans): does a chunk start here, where does this one end,
+// how many rep ids does the node stand for; and the two per-row outputs, label and node, local to the tint.
+__global__ void __launch_bounds__(256) k_chunk(i64 n_rows_total, i64 max_size, const unsigned *skey, const int *sval, const int *comp_start,
+                                               const int *comp_end, const i64 *mem_off, const int *row_tint, const TintDesc *tints,
+                                               const int *parent, i64 *head, int *chunk_end, i64 *smult, int *label_out, int *node_out) {
+    for (i64 k = (i64)blockIdx.x * blockDim.x + threadIdx.x; k <= n_rows_total; k += (i64)gridDim.x * blockDim.x) {
+        if (k == n_rows_total) { head[k] = 0; smult[k] = 0; continue; }
+        const unsigned key = skey[k];
+        const i64 st = comp_start[key], n = comp_end[key] - st;
+        const i64 p = (n + max_size - 1) / max_size, s = (n + p - 1) / p;      // :113-114 in integers
+        const i64 pos = k - st, ch = pos / s;
+        head[k] = pos == ch * s ? 1 : 0;
+        const i64 ce = st + (ch + 1) * s;
+        chunk_end[k] = (int)(ce < st + n ? ce : st + n);
+        const int v = sval[k];
+        smult[k] = mem_off[v + 1] - mem_off[v];
+        node_out[k] = v - (int)tints[row_tint[v]].row0;
+        label_out[k] = parent[k] - (int)tints[row_tint[k]].row0;
+    }
+}
+
+// ---- incompatible pairs (:261-273) ------------------------------------------------------------------------------
+// A wave per sorted position k = (partition, node i): the nodes j behind it in its chunk, 64 at a time (lane = j); a lane whose j
+// has no edge to i stands for mult(i) * mult(j) pairs.  EMIT = false: the wave's total, cnt[k].  EMIT = true: the pairs themselves,
+// behind pair_base[k] (the exclusive scan of cnt) in the reference's loop order -- j ascending (a prefix sum over the lanes), then
+// rid_1 of i, then rid_2 of j.  A lane writes its own block when it is small (multiplicity 1: the lanes' pairs are neighbours in
+// memory); a block of more than kLanePairs pairs is written by the whole wave.
+constexpr int kLanePairs = 16;
+
+template <bool EMIT>
+__global__ void __launch_bounds__(256) k_pairs(i64 n_rows_total, const int *sval, const int *chunk_end, const i64 *smult, const int *row_tint,
+                                               const TintDesc *tints, const u64 *adj, i64 *cnt, const i64 *pair_base, const i64 *mem_off,
+                                               const int *mem, int2 *pairs) {
+    const int lane = lane_id();
+    const i64 wave_g = ((i64)blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = ((i64)gridDim.x * blockDim.x) >> 6;
+    for (i64 k = wave_g; k < n_rows_total; k += n_waves) {
+        const int i = sval[k];
+        const TintDesc d = tints[row_tint[i]];
+        const u64 *row = adj + d.adj_off + (i64)(i - d.row0) * d.aw;
+        const i64 mi = smult[k], ce = chunk_end[k];
+        const int *mem_i = mem + mem_off[i];
+        const i64 base_k = EMIT ? pair_base[k] : 0;
+        i64 run = 0;                                           // sum of mult(j) over the non-neighbours j taken so far
+        for (i64 k0 = k + 1; k0 < ce; k0 += 64) {
+            const i64 k2 = k0 + lane;
+            i64 w = 0;
+            int jrow = 0;
+            if (k2 < ce) {
+                jrow = sval[k2];
+                const int j = jrow - (int)d.row0;
+                if (!((row[j >> 6] >> (j & 63)) & 1ull)) w = smult[k2];
+            }
+            i64 inc = w;
+            for (int s = 1; s < 64; s <<= 1) { const i64 o = __shfl_up(inc, s); if (lane >= s) inc += o; }
+            if (EMIT) {
+                const i64 base = base_k + mi * (run + inc - w), block = mi * w;
+                if (block > 0 && block <= kLanePairs) {
+                    const int *mem_j = mem + mem_off[jrow];
+                    i64 x = base;
+                    for (i64 a = 0; a < mi; ++a) for (i64 b = 0; b < w; ++b) pairs[x++] = make_int2(mem_i[a], mem_j[b]);
+                }
+                u64 big = __ballot(block > kLanePairs);
+                while (big) {
+                    const int L = __ffsll((long long)big) - 1;
+                    big &= big - 1;
+                    const i64 bL = __shfl(base, L), wL = __shfl(w, L);
+                    const int *mem_j = mem + mem_off[__shfl(jrow, L)];
+                    for (i64 x = lane; x < mi * wL; x += 64) { const i64 a = x / wL; pairs[bL + x] = make_int2(mem_i[a], mem_j[x - a * wL]); }
+                }
+            }
+            run += __shfl(inc, 63);
+        }
+        if (!EMIT && lane == 0) cnt[k] = mi * run;
+    }
+}
+
+// ---- partition members: the rep ids of a partition's nodes, end to end ---------------------------------------------
+__global__ void __launch_bounds__(256) k_members(i64 n_rows_total, const int *sval, const i64 *smult, const i64 *rid_pos, const i64 *mem_off,
+                                                 const int *mem, int *part_rids) {
+    const int lane = lane_id();
+    const i64 wave_g = ((i64)blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = ((i64)gridDim.x * blockDim.x) >> 6;
+    for (i64 k = wave_g; k < n_rows_total; k += n_waves) {
+        const int *src = mem + mem_off[sval[k]];
+        int *dst = part_rids + rid_pos[k];
+        for (i64 x = lane; x < smult[k]; x += 64) dst[x] = src[x];
+    }
+}
+
+// ---- the offset arrays: partition q starts where the q-th chunk head stands (part_id = exclusive scan of head) -----------
+__global__ void __launch_bounds__(256) k_offsets(i64 n_rows_total, int n_tint, const TintDesc *tints, const i64 *head, const i64 *part_id,
+                                                 const i64 *rid_pos, const i64 *pair_base, i64 *tint_part_off, i64 *part_node_off,
+                                                 i64 *part_rid_off, i64 *part_pair_off) {
+    const i64 last = n_rows_total > n_tint ? n_rows_total : n_tint;
+    for (i64 k = (i64)blockIdx.x * blockDim.x + threadIdx.x; k <= last; k += (i64)gridDim.x * blockDim.x) {
+        if (k == n_rows_total || (k < n_rows_total && head[k])) {
+            const i64 q = part_id[k];
+            part_node_off[q] = k; part_rid_off[q] = rid_pos[k]; part_pair_off[q] = pair_base[k];
+        }
+        if (k <= n_tint) tint_part_off[k] = part_id[k < n_tint ? tints[k].row0 : n_rows_total];
+    }
+}
+
 }  // namespace
 
 struct GrowBuf {              // device buffer that lives with the context and only ever grows
+    void *p = nullptr;
+    size_t cap = 0;
+    template <typename T> T *as() const { return reinterpret_cast<T *>(p); }
+};
+struct HostBuf {              // the same in pinned host memory
     void *p = nullptr;
     size_t cap = 0;
     template <typename T> T *as() const { return reinterpret_cast<T *>(p); }
@@ -416,6 +636,16 @@ struct fclu_ctx {
     GrowBuf tints, tiles, row_tint, bits, first, last, tail, adj[2], deg, changed, word_tint, tint_word0, deg1, pass_any, small_tints, small_rounds;
     int *h_flags = nullptr;   // pinned: per-pass flags of a burst + per-tint flags
     size_t h_flags_cap = 0;
+    // fclu_partition(): the batch the last graph call left on the device, work arrays, results (pinned, context-owned)
+    std::vector<TintDesc> h_tints;
+    int adj_cur = 0;
+    hipEvent_t pev[6] = {};
+    float components_ms = 0.f, pairs_ms = 0.f;
+    GrowBuf parent, skey, rows, sval, comp_start, comp_end, chunk_end, head, part_id, smult, rid_pos, cnt, pair_base, d_label, d_nodes,
+            d_tint_part_off, d_part_node_off, d_part_rid_off, d_part_pair_off, mem_off, mem, d_part_rids, d_pairs, tmp;
+    HostBuf h_cc_flags, h_tint_part_off, h_part_node_off, h_part_nodes, h_part_rid_off, h_part_rids, h_part_pair_off, h_pairs, h_label;
+    fclu_parts parts = {};
+    bool have_parts = false;
 };
 
 namespace {
@@ -442,11 +672,21 @@ hipError_t grow(GrowBuf &b, size_t bytes) {
 }
 constexpr int kBurst = 4;     // pruning passes enqueued per host round trip
 
+// connected components of a tint in one workgroup's LDS: the pruning's criterion; FCLU_PART_LDS=0: never (tests)
+int cc_in_lds(int n, int aw) {
+    const char *e = getenv("FCLU_PART_LDS");
+    return (!(e && e[0] == '0') && n > 0 && (i64)n * aw <= kPruneLdsWords) ? 1 : 0;
+}
+
 #define HIP_TRY(c, expr)                                                                                     \
     do {                                                                                                     \
         hipError_t e__ = (expr);                                                                             \
         if (e__ != hipSuccess) return fail((c), FCLU_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e__));      \
     } while (0)
+
+int compat_device(fclu_ctx *c, const fclu_batch *b, int32_t prune, uint64_t *adj_out, int32_t *rounds_out);
+int check_members(fclu_ctx *c, i64 R, const int64_t *mem_off, const int32_t *mem, int32_t maximum_ilp_size);
+int partition_device(fclu_ctx *c, int T, i64 R, const int64_t *mem_off, const int32_t *mem, int32_t maximum_ilp_size);
 
 }  // namespace
 
@@ -468,6 +708,9 @@ int fclu_create(int device, fclu_ctx **out) {
     e = hipSetDevice(device);
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
     for (int i = 0; e == hipSuccess && i < 3; ++i) e = hipEventCreate(&c->ev[i]);
+    for (int i = 0; e == hipSuccess && i < 6; ++i) e = hipEventCreate(&c->pev[i]);
+    if (e == hipSuccess)
+        e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_cc_lds), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
     if (e == hipSuccess)
         e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_compat<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 2 * kTile * (kMaxWords | 1) * 4);
@@ -490,9 +733,16 @@ void fclu_destroy(fclu_ctx *c) {
     (void)hipSetDevice(c->device);
     if (c->stream) { (void)hipStreamSynchronize(c->stream); (void)hipStreamDestroy(c->stream); }
     for (int i = 0; i < 3; ++i) if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
+    for (int i = 0; i < 6; ++i) if (c->pev[i]) (void)hipEventDestroy(c->pev[i]);
     GrowBuf *bufs[] = {&c->tints, &c->tiles, &c->row_tint, &c->bits, &c->first, &c->last, &c->tail, &c->adj[0], &c->adj[1], &c->deg,
-                       &c->changed, &c->word_tint, &c->tint_word0, &c->deg1, &c->pass_any, &c->small_tints, &c->small_rounds};
+                       &c->changed, &c->word_tint, &c->tint_word0, &c->deg1, &c->pass_any, &c->small_tints, &c->small_rounds,
+                       &c->parent, &c->skey, &c->rows, &c->sval, &c->comp_start, &c->comp_end, &c->chunk_end, &c->head, &c->part_id, &c->smult,
+                       &c->rid_pos, &c->cnt, &c->pair_base, &c->d_label, &c->d_nodes, &c->d_tint_part_off, &c->d_part_node_off,
+                       &c->d_part_rid_off, &c->d_part_pair_off, &c->mem_off, &c->mem, &c->d_part_rids, &c->d_pairs, &c->tmp};
     for (GrowBuf *b : bufs) if (b->p) (void)hipFree(b->p);
+    HostBuf *hbufs[] = {&c->h_cc_flags, &c->h_tint_part_off, &c->h_part_node_off, &c->h_part_nodes, &c->h_part_rid_off, &c->h_part_rids,
+                        &c->h_part_pair_off, &c->h_pairs, &c->h_label};
+    for (HostBuf *b : hbufs) if (b->p) (void)hipHostFree(b->p);
     if (c->h_flags) (void)hipHostFree(c->h_flags);
     delete c;
 }
@@ -501,6 +751,16 @@ const char *fclu_last_error(const fclu_ctx *c) { return c ? c->err.c_str() : g_c
 
 int fclu_compat_graph(fclu_ctx *c, const fclu_batch *b, int32_t prune, uint64_t *adj_out, int32_t *rounds_out) {
     if (!c || !b || !adj_out) return FCLU_ERR_ARG;
+    return compat_device(c, b, prune, adj_out, rounds_out);
+}
+
+}  // extern "C"
+
+namespace {
+
+// The graph of a batch: compatibility, then pruning.  The pruned matrix stays on the device in c->adj[c->adj_cur] (with the tints'
+// descriptors in c->tints / c->h_tints and c->row_tint) for fclu_partition(); adj_out may be null.
+int compat_device(fclu_ctx *c, const fclu_batch *b, int32_t prune, uint64_t *adj_out, int32_t *rounds_out) {
     if (b->n_tint <= 0) return fail(c, FCLU_ERR_ARG, "fclu_compat_graph: empty batch");
     HIP_TRY(c, hipSetDevice(c->device));
     const int T = b->n_tint;
@@ -528,7 +788,8 @@ int fclu_compat_graph(fclu_ctx *c, const fclu_batch *b, int32_t prune, uint64_t 
         d.w = (d.n_seg + 31) / 32; if (d.w < 1) d.w = 1;
         d.aw = (d.n + 63) / 64;
         d.bits_off = b->bits_off[t]; d.adj_off = b->adj_off[t];
-        d.in_lds = (prune && lds_ok && d.n > 0 && d.n <= 65535 && (i64)d.n * d.aw <= lds_words) ? 1 : 0; d.pad = 0;
+        d.in_lds = (prune && lds_ok && d.n > 0 && d.n <= 65535 && (i64)d.n * d.aw <= lds_words) ? 1 : 0;
+        d.cc_lds = cc_in_lds(d.n, d.aw);
         if (d.in_lds) { small_tints.push_back(t); small_lds = std::max(small_lds, ((size_t)2 * d.n * d.aw + d.aw) * 8 + (size_t)d.n * 2 + 16); }
         else if (d.n > 0) { any_large = true; max_aw_large = std::max(max_aw_large, d.aw); }
         if (b->bits_off[t + 1] - d.bits_off != (i64)d.n * d.w) return fail(c, FCLU_ERR_ARG, "tint %d: bits_off does not match rows x words", t);
@@ -559,6 +820,8 @@ int fclu_compat_graph(fclu_ctx *c, const fclu_batch *b, int32_t prune, uint64_t 
     const int n_tiles = (int)tiles.size();
     if (rounds_out) for (int t = 0; t < T; ++t) rounds_out[t] = 0;
     c->compat_ms = c->prune_ms = 0.f;
+    c->h_tints = tints;
+    c->adj_cur = 0;
     if (n_tiles == 0 || R == 0) return FCLU_OK;
 
     GrowBuf &d_tints = c->tints, &d_tiles = c->tiles, &d_row_tint = c->row_tint, &d_bits = c->bits, &d_first = c->first, &d_last = c->last,
@@ -666,7 +929,8 @@ int fclu_compat_graph(fclu_ctx *c, const fclu_batch *b, int32_t prune, uint64_t 
         }
     }
     HIP_TRY(c, hipEventRecord(c->ev[2], s));
-    HIP_TRY(c, hipMemcpyAsync(adj_out, d_adj[cur].p, (size_t)n_adj * 8, hipMemcpyDeviceToHost, s));
+    c->adj_cur = cur;
+    if (adj_out) HIP_TRY(c, hipMemcpyAsync(adj_out, d_adj[cur].p, (size_t)n_adj * 8, hipMemcpyDeviceToHost, s));
     std::vector<int> small_rounds;
     if (prune && rounds_out && !small_tints.empty()) {
         small_rounds.resize((size_t)T);
@@ -677,6 +941,282 @@ int fclu_compat_graph(fclu_ctx *c, const fclu_batch *b, int32_t prune, uint64_t 
     HIP_TRY(c, hipGetLastError());
     (void)hipEventElapsedTime(&c->compat_ms, c->ev[0], c->ev[1]);
     (void)hipEventElapsedTime(&c->prune_ms, c->ev[1], c->ev[2]);
+    return FCLU_OK;
+}
+
+
+// ---- partition_reads() behind the graph (:256-274) ---------------------------------------------------------------
+int check_members(fclu_ctx *c, i64 R, const int64_t *mem_off, const int32_t *mem, int32_t maximum_ilp_size) {
+    if (maximum_ilp_size < 1) return fail(c, FCLU_ERR_ARG, "maximum_ilp_size is %d: it must be at least 1", (int)maximum_ilp_size);
+    if (R < 0 || R >= (1ll << 31)) return fail(c, FCLU_ERR_ARG, "bad row count %lld", R);
+    if (!mem_off) return fail(c, FCLU_ERR_ARG, "mem_off is null");
+    if (mem_off[0] != 0) return fail(c, FCLU_ERR_ARG, "mem_off[0] is %lld, not 0", (i64)mem_off[0]);
+    for (i64 r = 0; r < R; ++r)
+        if (mem_off[r + 1] < mem_off[r]) return fail(c, FCLU_ERR_ARG, "mem_off is not monotone at row %lld (%lld after %lld)", r, (i64)mem_off[r + 1], (i64)mem_off[r]);
+    if (mem_off[R] > 0 && !mem) return fail(c, FCLU_ERR_ARG, "mem is null");
+    return FCLU_OK;
+}
+
+hipError_t grow_host(HostBuf &b, size_t bytes) {
+    if (b.p && bytes <= b.cap) return hipSuccess;
+    if (b.p) { hipError_t e = hipHostFree(b.p); b.p = nullptr; b.cap = 0; if (e != hipSuccess) return e; }
+    const size_t want = (bytes ? bytes : 16) + bytes / 4;
+    hipError_t e = hipHostMalloc(&b.p, want, hipHostMallocDefault);
+    if (e == hipSuccess) b.cap = want;
+    return e;
+}
+
+int bits_for(i64 n) { int b = 1; while (b < 32 && (1ll << b) < n) ++b; return b; }
+
+// c->tints / c->h_tints / c->row_tint describe the batch and c->adj[c->adj_cur] holds its pruned matrices.
+int partition_device(fclu_ctx *c, int T, i64 R, const int64_t *mem_off, const int32_t *mem, int32_t maximum_ilp_size) {
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    c->components_ms = c->pairs_ms = 0.f;
+    fclu_parts &out = c->parts;
+    HIP_TRY(c, grow_host(c->h_tint_part_off, (size_t)(T + 1) * 8));
+    if (R == 0) {                                            // nothing but empty tints
+        HIP_TRY(c, grow_host(c->h_part_node_off, 8)); HIP_TRY(c, grow_host(c->h_part_rid_off, 8)); HIP_TRY(c, grow_host(c->h_part_pair_off, 8));
+        HIP_TRY(c, grow_host(c->h_part_nodes, 0)); HIP_TRY(c, grow_host(c->h_part_rids, 0)); HIP_TRY(c, grow_host(c->h_pairs, 0)); HIP_TRY(c, grow_host(c->h_label, 0));
+        memset(c->h_tint_part_off.p, 0, (size_t)(T + 1) * 8);
+        *c->h_part_node_off.as<i64>() = *c->h_part_rid_off.as<i64>() = *c->h_part_pair_off.as<i64>() = 0;
+        out.n_tint = T; out.n_rows = out.n_part = out.n_rids = out.n_pairs = 0;
+    } else {
+        const u64 *d_adj = c->adj[c->adj_cur].as<u64>();
+        const TintDesc *d_tints = c->tints.as<TintDesc>();
+        const int *d_row_tint = c->row_tint.as<int>();
+        const i64 n_mem = mem_off[R];
+        std::vector<int> small;
+        size_t small_lds = 0;
+        bool any_large = false;
+        for (int t = 0; t < T; ++t) {
+            const TintDesc &d = c->h_tints[(size_t)t];
+            if (d.cc_lds) { small.push_back(t); small_lds = std::max(small_lds, (size_t)d.n * d.aw * 8 + (size_t)d.n * 4); }
+            else if (d.n > 0) any_large = true;
+        }
+        const size_t R1 = (size_t)R + 1;
+        HIP_TRY(c, grow(c->parent, (size_t)R * 4)); HIP_TRY(c, grow(c->skey, (size_t)R * 4));
+        HIP_TRY(c, grow(c->rows, (size_t)R * 4)); HIP_TRY(c, grow(c->sval, (size_t)R * 4));
+        HIP_TRY(c, grow(c->comp_start, (size_t)R * 4)); HIP_TRY(c, grow(c->comp_end, (size_t)R * 4)); HIP_TRY(c, grow(c->chunk_end, (size_t)R * 4));
+        HIP_TRY(c, grow(c->head, R1 * 8)); HIP_TRY(c, grow(c->part_id, R1 * 8)); HIP_TRY(c, grow(c->smult, R1 * 8)); HIP_TRY(c, grow(c->rid_pos, R1 * 8));
+        HIP_TRY(c, grow(c->cnt, R1 * 8)); HIP_TRY(c, grow(c->pair_base, R1 * 8));
+        HIP_TRY(c, grow(c->d_label, (size_t)R * 4)); HIP_TRY(c, grow(c->d_nodes, (size_t)R * 4));
+        HIP_TRY(c, grow(c->d_tint_part_off, (size_t)(T + 1) * 8)); HIP_TRY(c, grow(c->d_part_node_off, R1 * 8));
+        HIP_TRY(c, grow(c->d_part_rid_off, R1 * 8)); HIP_TRY(c, grow(c->d_part_pair_off, R1 * 8));
+        HIP_TRY(c, grow(c->mem_off, R1 * 8)); HIP_TRY(c, grow(c->mem, (size_t)n_mem * 4)); HIP_TRY(c, grow(c->d_part_rids, (size_t)n_mem * 4));
+        HIP_TRY(c, grow(c->small_tints, small.size() * 4 + 4));
+        HIP_TRY(c, grow(c->pass_any, (size_t)kBurst * 4));
+        HIP_TRY(c, grow_host(c->h_cc_flags, (size_t)kBurst * 4 + 16));
+        const int end_bit = bits_for(R);
+        size_t sort_bytes = 0, scan_bytes = 0;
+        HIP_TRY(c, rocprim::radix_sort_pairs(nullptr, sort_bytes, c->parent.as<unsigned>(), c->skey.as<unsigned>(), c->rows.as<int>(), c->sval.as<int>(),
+                                             (size_t)R, 0u, (unsigned)end_bit, s));
+        HIP_TRY(c, rocprim::exclusive_scan(nullptr, scan_bytes, c->head.as<i64>(), c->part_id.as<i64>(), (i64)0, R1, rocprim::plus<i64>(), s));
+        const size_t tmp_bytes = std::max(sort_bytes, scan_bytes);
+        HIP_TRY(c, grow(c->tmp, tmp_bytes));
+        HIP_TRY(c, hipMemcpyAsync(c->mem_off.p, mem_off, R1 * 8, hipMemcpyHostToDevice, s));
+        if (n_mem) HIP_TRY(c, hipMemcpyAsync(c->mem.p, mem, (size_t)n_mem * 4, hipMemcpyHostToDevice, s));
+        if (!small.empty()) HIP_TRY(c, hipMemcpyAsync(c->small_tints.p, small.data(), small.size() * 4, hipMemcpyHostToDevice, s));
+
+        const int row_grid = (int)std::min<i64>((R + 256) / 256, 4096), wave_grid = (int)std::min<i64>((R + 3) / 4, 65536);
+        int *d_parent = c->parent.as<int>();
+        // ---- components
+        HIP_TRY(c, hipEventRecord(c->pev[0], s));
+        hipLaunchKernelGGL(k_cc_init, dim3(row_grid), dim3(256), 0, s, R, d_parent);
+        hipLaunchKernelGGL(k_cc_init, dim3(row_grid), dim3(256), 0, s, R, c->rows.as<int>());     // (the sort's values: the rows themselves)
+        if (!small.empty())
+            hipLaunchKernelGGL(k_cc_lds, dim3((unsigned)small.size()), dim3(256), small_lds, s, c->small_tints.as<int>(), d_tints, d_adj, d_parent);
+        if (any_large) {
+            // as in the pruning: kBurst passes per host round trip, pass q gated on pass q - 1's "something changed" word
+            int *h_any = c->h_cc_flags.as<int>(), *d_any = c->pass_any.as<int>();
+            bool done = false;
+            for (int burst = 0; !done; ++burst) {
+                if (burst >= (1 << 16)) return fail(c, FCLU_ERR_HIP, "connected components did not converge");
+                HIP_TRY(c, hipMemsetAsync(d_any, 0, (size_t)kBurst * 4, s));
+                for (int q = 0; q < kBurst; ++q) {
+                    const int *gate = q ? d_any + (q - 1) : nullptr;
+                    hipLaunchKernelGGL(k_cc_hook, dim3(wave_grid), dim3(256), 0, s, R, d_row_tint, d_tints, d_adj, d_parent, d_any + q, gate);
+                    hipLaunchKernelGGL(k_cc_jump, dim3(row_grid), dim3(256), 0, s, R, d_row_tint, d_tints, d_parent, d_any + q, gate);
+                }
+                HIP_TRY(c, hipMemcpyAsync(h_any, d_any, (size_t)kBurst * 4, hipMemcpyDeviceToHost, s));
+                HIP_TRY(c, hipStreamSynchronize(s));
+                for (int q = 0; q < kBurst; ++q) if (!h_any[q]) { done = true; break; }
+            }
+        }
+        HIP_TRY(c, hipEventRecord(c->pev[1], s));
+        // ---- even split, members' positions, pair counts
+        HIP_TRY(c, rocprim::radix_sort_pairs(c->tmp.p, sort_bytes, c->parent.as<unsigned>(), c->skey.as<unsigned>(), c->rows.as<int>(), c->sval.as<int>(),
+                                             (size_t)R, 0u, (unsigned)end_bit, s));
+        hipLaunchKernelGGL(k_bounds, dim3(row_grid), dim3(256), 0, s, R, c->skey.as<unsigned>(), c->comp_start.as<int>(), c->comp_end.as<int>());
+        hipLaunchKernelGGL(k_chunk, dim3(row_grid), dim3(256), 0, s, R, (i64)maximum_ilp_size, c->skey.as<unsigned>(), c->sval.as<int>(), c->comp_start.as<int>(),
+                           c->comp_end.as<int>(), c->mem_off.as<i64>(), d_row_tint, d_tints, d_parent, c->head.as<i64>(), c->chunk_end.as<int>(),
+                           c->smult.as<i64>(), c->d_label.as<int>(), c->d_nodes.as<int>());
+        size_t sb = scan_bytes;
+        HIP_TRY(c, rocprim::exclusive_scan(c->tmp.p, sb, c->head.as<i64>(), c->part_id.as<i64>(), (i64)0, R1, rocprim::plus<i64>(), s));
+        sb = scan_bytes;
+        HIP_TRY(c, rocprim::exclusive_scan(c->tmp.p, sb, c->smult.as<i64>(), c->rid_pos.as<i64>(), (i64)0, R1, rocprim::plus<i64>(), s));
+        HIP_TRY(c, hipMemsetAsync(c->cnt.as<i64>() + R, 0, 8, s));
+        HIP_TRY(c, hipEventRecord(c->pev[2], s));
+        hipLaunchKernelGGL(k_pairs<false>, dim3(wave_grid), dim3(256), 0, s, R, c->sval.as<int>(), c->chunk_end.as<int>(), c->smult.as<i64>(), d_row_tint, d_tints,
+                           d_adj, c->cnt.as<i64>(), (const i64 *)nullptr, c->mem_off.as<i64>(), c->mem.as<int>(), (int2 *)nullptr);
+        HIP_TRY(c, hipEventRecord(c->pev[3], s));
+        sb = scan_bytes;
+        HIP_TRY(c, rocprim::exclusive_scan(c->tmp.p, sb, c->cnt.as<i64>(), c->pair_base.as<i64>(), (i64)0, R1, rocprim::plus<i64>(), s));
+        const i64 RT = std::max<i64>(R, T);
+        hipLaunchKernelGGL(k_offsets, dim3((int)std::min<i64>((RT + 256) / 256, 4096)), dim3(256), 0, s, R, T, d_tints, c->head.as<i64>(), c->part_id.as<i64>(),
+                           c->rid_pos.as<i64>(), c->pair_base.as<i64>(), c->d_tint_part_off.as<i64>(), c->d_part_node_off.as<i64>(),
+                           c->d_part_rid_off.as<i64>(), c->d_part_pair_off.as<i64>());
+        i64 *h_tot = reinterpret_cast<i64 *>(c->h_cc_flags.as<int>() + kBurst);            // {partitions, pairs}
+        HIP_TRY(c, hipMemcpyAsync(h_tot, c->part_id.as<i64>() + R, 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipMemcpyAsync(h_tot + 1, c->pair_base.as<i64>() + R, 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipStreamSynchronize(s));
+        HIP_TRY(c, hipGetLastError());
+        const i64 P = h_tot[0], n_pairs = h_tot[1];
+        if (P < 0 || P > R || n_pairs < 0) return fail(c, FCLU_ERR_HIP, "partition totals out of range (%lld partitions, %lld pairs)", P, n_pairs);
+        // ---- the pair list: as large as the graphs make it
+        if (n_pairs > 2147483647ll)
+            return fail(c, FCLU_ERR_UNSUPPORTED, "%lld incompatible pairs in this batch: more than the 2147483647 a call returns", n_pairs);
+        if ((size_t)n_pairs * 8 > c->d_pairs.cap) {
+            if (c->d_pairs.p) { HIP_TRY(c, hipFree(c->d_pairs.p)); c->d_pairs.p = nullptr; c->d_pairs.cap = 0; }
+            size_t free_b = 0, total_b = 0;
+            HIP_TRY(c, hipMemGetInfo(&free_b, &total_b));
+            if ((size_t)n_pairs * 8 + (64u << 20) > free_b)
+                return fail(c, FCLU_ERR_UNSUPPORTED, "%lld incompatible pairs in this batch (%lld bytes) do not fit the device's free memory (%lld bytes)",
+                            n_pairs, n_pairs * 8, (i64)free_b);
+            if (hipMalloc(&c->d_pairs.p, (size_t)n_pairs * 8) != hipSuccess) {
+                (void)hipGetLastError(); c->d_pairs.p = nullptr;
+                return fail(c, FCLU_ERR_UNSUPPORTED, "%lld incompatible pairs in this batch: no device memory for %lld bytes", n_pairs, n_pairs * 8);
+            }
+            c->d_pairs.cap = (size_t)n_pairs * 8;
+        }
+        if ((size_t)n_pairs * 8 > c->h_pairs.cap || !c->h_pairs.p) {
+            if (c->h_pairs.p) { HIP_TRY(c, hipHostFree(c->h_pairs.p)); c->h_pairs.p = nullptr; c->h_pairs.cap = 0; }
+            const size_t want = std::max<size_t>((size_t)n_pairs * 8, 16);
+            if (hipHostMalloc(&c->h_pairs.p, want, hipHostMallocDefault) != hipSuccess) {
+                (void)hipGetLastError(); c->h_pairs.p = nullptr;
+                return fail(c, FCLU_ERR_UNSUPPORTED, "%lld incompatible pairs in this batch: no pinned host memory for %lld bytes", n_pairs, n_pairs * 8);
+            }
+            c->h_pairs.cap = want;
+        }
+        HIP_TRY(c, grow_host(c->h_part_node_off, (size_t)(P + 1) * 8)); HIP_TRY(c, grow_host(c->h_part_rid_off, (size_t)(P + 1) * 8));
+        HIP_TRY(c, grow_host(c->h_part_pair_off, (size_t)(P + 1) * 8));
+        HIP_TRY(c, grow_host(c->h_part_nodes, (size_t)R * 4)); HIP_TRY(c, grow_host(c->h_label, (size_t)R * 4)); HIP_TRY(c, grow_host(c->h_part_rids, (size_t)n_mem * 4));
+        HIP_TRY(c, hipEventRecord(c->pev[4], s));
+        if (n_pairs)
+            hipLaunchKernelGGL(k_pairs<true>, dim3(wave_grid), dim3(256), 0, s, R, c->sval.as<int>(), c->chunk_end.as<int>(), c->smult.as<i64>(), d_row_tint, d_tints,
+                               d_adj, (i64 *)nullptr, c->pair_base.as<i64>(), c->mem_off.as<i64>(), c->mem.as<int>(), c->d_pairs.as<int2>());
+        if (n_mem)
+            hipLaunchKernelGGL(k_members, dim3(wave_grid), dim3(256), 0, s, R, c->sval.as<int>(), c->smult.as<i64>(), c->rid_pos.as<i64>(), c->mem_off.as<i64>(),
+                               c->mem.as<int>(), c->d_part_rids.as<int>());
+        HIP_TRY(c, hipEventRecord(c->pev[5], s));
+        HIP_TRY(c, hipMemcpyAsync(c->h_tint_part_off.p, c->d_tint_part_off.p, (size_t)(T + 1) * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipMemcpyAsync(c->h_part_node_off.p, c->d_part_node_off.p, (size_t)(P + 1) * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipMemcpyAsync(c->h_part_rid_off.p, c->d_part_rid_off.p, (size_t)(P + 1) * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipMemcpyAsync(c->h_part_pair_off.p, c->d_part_pair_off.p, (size_t)(P + 1) * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipMemcpyAsync(c->h_part_nodes.p, c->d_nodes.p, (size_t)R * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipMemcpyAsync(c->h_label.p, c->d_label.p, (size_t)R * 4, hipMemcpyDeviceToHost, s));
+        if (n_mem) HIP_TRY(c, hipMemcpyAsync(c->h_part_rids.p, c->d_part_rids.p, (size_t)n_mem * 4, hipMemcpyDeviceToHost, s));
+        if (n_pairs) HIP_TRY(c, hipMemcpyAsync(c->h_pairs.p, c->d_pairs.p, (size_t)n_pairs * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipStreamSynchronize(s));
+        HIP_TRY(c, hipGetLastError());
+        float a = 0.f, b = 0.f;
+        (void)hipEventElapsedTime(&c->components_ms, c->pev[0], c->pev[1]);
+        (void)hipEventElapsedTime(&a, c->pev[2], c->pev[3]);
+        (void)hipEventElapsedTime(&b, c->pev[4], c->pev[5]);
+        c->pairs_ms = a + b;
+        out.n_tint = T; out.n_rows = R; out.n_part = P; out.n_rids = n_mem; out.n_pairs = n_pairs;
+    }
+    out.tint_part_off = c->h_tint_part_off.as<int64_t>();
+    out.part_node_off = c->h_part_node_off.as<int64_t>(); out.part_nodes = c->h_part_nodes.as<int32_t>();
+    out.part_rid_off = c->h_part_rid_off.as<int64_t>(); out.part_rids = c->h_part_rids.as<int32_t>();
+    out.part_pair_off = c->h_part_pair_off.as<int64_t>(); out.pairs = c->h_pairs.as<int32_t>();
+    out.label = c->h_label.as<int32_t>();
+    c->have_parts = true;
+    return FCLU_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fclu_partition(fclu_ctx *c, const fclu_batch *b, const int64_t *mem_off, const int32_t *mem, int32_t maximum_ilp_size) {
+    if (!c || !b) return FCLU_ERR_ARG;
+    c->have_parts = false;
+    if (b->n_tint <= 0) return fail(c, FCLU_ERR_ARG, "fclu_partition: empty batch");
+    int rc = check_members(c, b->row_off[b->n_tint], mem_off, mem, maximum_ilp_size);
+    if (rc == FCLU_OK) rc = compat_device(c, b, 1, nullptr, nullptr);
+    if (rc == FCLU_OK) rc = partition_device(c, b->n_tint, b->row_off[b->n_tint], mem_off, mem, maximum_ilp_size);
+    return rc;
+}
+
+int fclu_partition_adj(fclu_ctx *c, int32_t n_tint, const int64_t *row_off, const int64_t *adj_off, const uint64_t *adj,
+                       const int64_t *mem_off, const int32_t *mem, int32_t maximum_ilp_size) {
+    if (!c || !row_off || !adj_off) return FCLU_ERR_ARG;
+    c->have_parts = false;
+    if (n_tint <= 0) return fail(c, FCLU_ERR_ARG, "fclu_partition_adj: empty batch");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const int T = n_tint;
+    const i64 R = row_off[T], n_adj = adj_off[T];
+    if (row_off[0] != 0 || adj_off[0] != 0 || R < 0 || R >= (1ll << 31)) return fail(c, FCLU_ERR_ARG, "fclu_partition_adj: bad row_off / adj_off");
+    if (n_adj > 0 && !adj) return FCLU_ERR_ARG;
+    std::vector<TintDesc> tints((size_t)T);
+    std::vector<int> row_tint((size_t)R);
+    for (int t = 0; t < T; ++t) {
+        TintDesc &d = tints[(size_t)t];
+        d = TintDesc();
+        d.row0 = row_off[t];
+        const i64 n = row_off[t + 1] - d.row0;
+        if (n < 0 || n > (1 << 30)) return fail(c, FCLU_ERR_ARG, "tint %d: bad row count", t);
+        d.n = (int)n; d.aw = (d.n + 63) / 64; d.adj_off = adj_off[t]; d.w = 1;
+        d.cc_lds = cc_in_lds(d.n, d.aw);
+        if (adj_off[t + 1] - d.adj_off != (i64)d.n * d.aw) return fail(c, FCLU_ERR_ARG, "tint %d: adj_off does not match rows x words", t);
+        // the matrix is the caller's: symmetric, an empty diagonal, no bit at a column >= N (the kernels index nodes with its bits)
+        const uint64_t *A = adj + d.adj_off;
+        for (i64 r = 0; r < n; ++r) {
+            row_tint[(size_t)(d.row0 + r)] = t;
+            for (int z = 0; z < d.aw; ++z) {
+                uint64_t word = A[r * d.aw + z];
+                if (z == d.aw - 1 && (d.n & 63) && (word >> (d.n & 63)))
+                    return fail(c, FCLU_ERR_ARG, "tint %d row %lld: adjacency bit at a column beyond N = %d", t, r, d.n);
+                while (word) {
+                    const i64 col = (i64)z * 64 + __builtin_ctzll(word);
+                    word &= word - 1;
+                    if (col == r) return fail(c, FCLU_ERR_ARG, "tint %d row %lld: adjacency bit on the diagonal", t, r);
+                    if (!((A[col * d.aw + (r >> 6)] >> (r & 63)) & 1ull))
+                        return fail(c, FCLU_ERR_ARG, "tint %d: adjacency not symmetric: (%lld, %lld) set, (%lld, %lld) not", t, r, col, col, r);
+                }
+            }
+        }
+    }
+    int rc = check_members(c, R, mem_off, mem, maximum_ilp_size);
+    if (rc != FCLU_OK) return rc;
+    c->h_tints = tints;
+    c->adj_cur = 0;
+    c->compat_ms = c->prune_ms = 0.f;
+    if (R > 0) {
+        hipStream_t s = c->stream;
+        HIP_TRY(c, grow(c->tints, tints.size() * sizeof(TintDesc)));
+        HIP_TRY(c, grow(c->row_tint, (size_t)R * 4));
+        HIP_TRY(c, grow(c->adj[0], (size_t)n_adj * 8));
+        HIP_TRY(c, hipMemcpyAsync(c->tints.p, tints.data(), tints.size() * sizeof(TintDesc), hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipMemcpyAsync(c->row_tint.p, row_tint.data(), (size_t)R * 4, hipMemcpyHostToDevice, s));
+        if (n_adj) HIP_TRY(c, hipMemcpyAsync(c->adj[0].p, adj, (size_t)n_adj * 8, hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipStreamSynchronize(s));              // (the host vectors go out of scope)
+    }
+    return partition_device(c, T, R, mem_off, mem, maximum_ilp_size);
+}
+
+int fclu_partition_results(fclu_ctx *c, fclu_parts *out) {
+    if (!c || !out) return FCLU_ERR_ARG;
+    if (!c->have_parts) return fail(c, FCLU_ERR_ARG, "fclu_partition_results: no result (the last fclu_partition call failed or none was made)");
+    *out = c->parts;
+    return FCLU_OK;
+}
+
+int fclu_partition_timing(fclu_ctx *c, float *components_ms, float *pairs_ms) {
+    if (!c) return FCLU_ERR_ARG;
+    if (components_ms) *components_ms = c->components_ms;
+    if (pairs_ms) *pairs_ms = c->pairs_ms;
     return FCLU_OK;
 }
 

@@ -1,13 +1,14 @@
 /*
  * freddie_cluster.h -- C-ABI of the GPU part of the clustering stage's pre-ILP work.
  *
- * It replaces the two quadratic loops of the reference's partition_reads() (py/freddie_cluster.py:196-274):
+ * It replaces everything of the reference's partition_reads() (py/freddie_cluster.py:196-274) behind the dedupe:
  *   - the pairwise read compatibility test            py/freddie_cluster.py:217-234
  *   - the iterated edge pruning of the compatibility graph   py/freddie_cluster.py:240-255
- * for a batch of transcriptional intervals ("tints") at once.  Everything else of partition_reads() -- the dedupe of
- * reads with the same structure (:207-215), connected components, the even split and the incompatible-pair lists
- * (:256-274) -- is host code (freddie_amd/cluster_prep.py), as are read_segment() (:119-172) and preprocess_ilp()
- * (:277-328).  The ILP itself (run_ilp, Gurobi) is out of scope.
+ *   - connected components, the even split of large components and the incompatible rep pairs of every partition
+ *                                                      py/freddie_cluster.py:256-274   (fclu_partition)
+ * for a batch of transcriptional intervals ("tints") at once.  The dedupe of reads with the same structure (:207-215)
+ * is host code (freddie_amd/cluster_prep.py), as are read_segment() (:119-172) and preprocess_ilp() (:277-328).  The ILP
+ * itself (run_ilp, Gurobi) is out of scope.
  *
  * Data layout (caller-owned host arrays, copied by the call):
  *   tint t owns the unique reads row_off[t] .. row_off[t+1]  (N_t of them; "unique" = py/freddie_cluster.py:207-215)
@@ -16,6 +17,16 @@
  *   first[r], last[r] = FL[read] (:301), tail[r] = poly_tail_category 'N','S','E' as 0,1,2 (:291-300)
  * Result: for tint t a symmetric N_t x N_t bit matrix, row r at adj[adj_off[t] + r * AW_t], AW_t = ceil(N_t / 64)
  * uint64 words, bit c of the row = the graph has the edge (r, c) after pruning (prune != 0) or before it (prune == 0).
+ *
+ * fclu_partition() goes on from the pruned matrix without taking it off the device and returns tint['partitions'] of the
+ * whole batch as flat arrays (fclu_parts).  The partitions of the batch are numbered through: tint t owns the partitions
+ * tint_part_off[t] .. tint_part_off[t+1], in the reference's order (components by their smallest node, a component's
+ * chunks in order).  Partition q has
+ *   the nodes  part_nodes[part_node_off[q] .. part_node_off[q+1]]     unique-read indices local to the tint, ascending
+ *   the rep ids part_rids[part_rid_off[q] .. part_rid_off[q+1]]        tint['partitions'][.][0]: its nodes' members, in order
+ *   the pairs  pairs[2 * part_pair_off[q] .. 2 * part_pair_off[q+1]]  tint['partitions'][.][1]: (rid_1, rid_2) two int32 a
+ *                                                                     pair, in the reference's loop order (:263-273)
+ * and label[r] is the smallest node of the component of unique read r (local to its tint).
  */
 #ifndef FREDDIE_CLUSTER_H
 #define FREDDIE_CLUSTER_H
@@ -54,6 +65,39 @@ int fclu_compat_graph(fclu_ctx *c, const fclu_batch *b, int32_t prune, uint64_t 
 
 /* Duration of the kernels of the last fclu_compat_graph() call, from HIP events on the library's stream (ms). */
 int fclu_last_timing(fclu_ctx *c, float *compat_ms, float *prune_ms);
+
+/* ---- the rest of partition_reads(): components, even split, members and incompatible pairs (:256-274) ----
+ * mem_off: int64[row_off[n_tint] + 1], starts at 0 and never falls; mem[mem_off[r] .. mem_off[r+1]] = the rep ids of
+ * unique read r (unique_data[r][1]).  maximum_ilp_size >= 1.
+ * FCLU_ERR_UNSUPPORTED: the batch's pair list has more than 2^31 - 1 pairs or does not fit the device's free memory
+ * (fclu_last_error names the total); a caller splits the batch. */
+int fclu_partition(fclu_ctx *c, const fclu_batch *b, const int64_t *mem_off, const int32_t *mem, int32_t maximum_ilp_size);
+
+/* The same behind a graph of the caller's, in the layout fclu_compat_graph() writes (row_off, adj_off: n_tint + 1).  The
+ * matrix must be symmetric with an empty diagonal and no bit at a column >= N_t: FCLU_ERR_ARG otherwise. */
+int fclu_partition_adj(fclu_ctx *c, int32_t n_tint, const int64_t *row_off, const int64_t *adj_off, const uint64_t *adj,
+                       const int64_t *mem_off, const int32_t *mem, int32_t maximum_ilp_size);
+
+typedef struct fclu_parts {
+    int32_t n_tint;
+    int64_t n_rows, n_part, n_rids, n_pairs;   /* lengths: label / part_nodes, partitions, part_rids, pairs (in pairs) */
+    const int64_t *tint_part_off;              /* n_tint + 1 */
+    const int64_t *part_node_off;              /* n_part + 1 */
+    const int32_t *part_nodes;                 /* n_rows */
+    const int64_t *part_rid_off;               /* n_part + 1 */
+    const int32_t *part_rids;                  /* n_rids */
+    const int64_t *part_pair_off;              /* n_part + 1, counted in pairs */
+    const int32_t *pairs;                      /* 2 * n_pairs */
+    const int32_t *label;                      /* n_rows */
+} fclu_parts;
+
+/* Result of the last successful fclu_partition() / fclu_partition_adj(): pointers into pinned host buffers the context
+ * owns, valid until the context's next call. */
+int fclu_partition_results(fclu_ctx *c, fclu_parts *out);
+
+/* Kernel time of the last partition call behind the graph, from HIP events (ms): the components; the pair count + emit
+ * (with the members' copy).  The graph's own time is fclu_last_timing()'s. */
+int fclu_partition_timing(fclu_ctx *c, float *components_ms, float *pairs_ms);
 
 #ifdef __cplusplus
 }

@@ -4,6 +4,8 @@ synthetic preprocessed tints through include/freddie_cluster.h.
 
     python bench.py --full --workload cluster-many|cluster-big [--steps K] [--no-cpu-baseline]     (with the CPU baseline)
     python tools/cluster_bench.py [--workload many|big] [--steps K]                          (GPU side only)
+    python tools/cluster_bench.py --partitions [--workload many|big] [--steps K] [--host-sample N]
+                       (the whole of partition_reads() behind the dedupe on the device against the host tail it replaces)
 
 One JSON line: read pairs tested per second of the CALL (packed host arrays in -> pruned adjacency in host memory: copies,
 kernels and the pruning loop's host round trips all inside), the kernel times as detail, and the bound of the compatibility
@@ -86,12 +88,70 @@ def run(workload="many", steps=5, cpu_baseline=None):
     return out
 
 
+def run_partitions(workload="many", steps=5, maximum_ilp_size=1000, host_sample=20):
+    """Context.partition() of the workload (graph, components, even split, members, incompatible pairs: packed arrays in,
+    flat arrays out) and, on the first host_sample tints, partition_reads_batch() both ways: the device path and, through
+    FCLU_HOST_PARTITIONS=1, the host tail behind the same device graph (adjacency_matrix + scipy components + the Python pair
+    loop).  Both of those end in tint['partitions'] as Python lists, so they share the cost of building the lists."""
+    w = WORKLOADS[workload]
+    tints = [cu.random_tint(1000 + t, w["n_reps"], w["n_segs"], n_isoforms=8) for t in range(w["n_tints"])]
+    uniq = [cluster_prep.unique_structures(t) for t in tints]
+    packed, members = cluster_prep.pack_structures(uniq), cluster_prep.pack_members(uniq)
+    ctx = cluster_prep.Context(0)
+    arr = ctx.partition(packed, members, maximum_ilp_size)       # warm-up
+    comp, pairs, graph, wall = [], [], [], []
+    for _ in range(steps):
+        t0 = time.perf_counter()
+        arr = ctx.partition(packed, members, maximum_ilp_size)
+        wall.append(time.perf_counter() - t0)
+        tm, tg = ctx.partition_timing(), ctx.last_timing()
+        comp.append(tm["components_ms"]); pairs.append(tm["pairs_ms"]); graph.append(tg["compat_ms"] + tg["prune_ms"])
+    sample = tints[:host_sample]
+
+    def reads_batch(host):
+        if host:
+            os.environ["FCLU_HOST_PARTITIONS"] = "1"
+        else:
+            os.environ.pop("FCLU_HOST_PARTITIONS", None)
+        try:
+            t0 = time.perf_counter()
+            cluster_prep.partition_reads_batch(sample, maximum_ilp_size, ctx, verbose=False)
+            dt = time.perf_counter() - t0
+        finally:
+            os.environ.pop("FCLU_HOST_PARTITIONS", None)
+        return dt, [t["partitions"] for t in sample]
+
+    reads_batch(False)                                           # warm-up of the sample's shapes
+    dev_s, dev_parts = reads_batch(False)
+    host_s, host_parts = reads_batch(True)
+    t0 = time.perf_counter()
+    ctx.partition(cluster_prep.pack_structures(uniq[:host_sample]), cluster_prep.pack_members(uniq[:host_sample]), maximum_ilp_size)
+    arrays_sample_s = time.perf_counter() - t0
+    ctx.close()
+    return {
+        "metric": "partition_reads() behind the dedupe: device arrays against the host tail", "unit": "ms", "data": "synthetic",
+        "config": {"workload": "cluster-" + workload, **w, "maximum_ilp_size": maximum_ilp_size, "steps": steps,
+                   "unique_reads": int(packed["row_off"][-1]), "partitions": int(arr["tint_part_off"][-1]), "incompatible_pairs": int(len(arr["pairs"]))},
+        "whole_batch": {"partition_call_wall_ms": float(np.median(wall)) * 1e3,
+                        "kernel_ms": {"graph (compat + prune)": float(np.mean(graph)), "components": float(np.mean(comp)),
+                                      "pairs (count + emit + members)": float(np.mean(pairs))}},
+        "sample": {"tints": len(sample), "identical_partitions": dev_parts == host_parts,
+                   "partition_call_wall_ms": arrays_sample_s * 1e3,
+                   "partition_reads_batch_device_ms": dev_s * 1e3, "partition_reads_batch_host_tail_ms": host_s * 1e3},
+    }
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workload", default="many", choices=sorted(WORKLOADS))
     ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--partitions", action="store_true", help="measure Context.partition() against the host tail (FCLU_HOST_PARTITIONS=1)")
+    ap.add_argument("--host-sample", type=int, default=20, help="--partitions: tints the two partition_reads_batch() runs take")
     args = ap.parse_args()
-    print(json.dumps(run(args.workload, args.steps)))
+    if args.partitions:
+        print(json.dumps(run_partitions(args.workload, args.steps, host_sample=args.host_sample)))
+    else:
+        print(json.dumps(run(args.workload, args.steps)))
 
 
 if __name__ == "__main__":
