@@ -10,6 +10,8 @@ Reference map (file:line of vpc-ccg/freddie ``py/freddie_cluster.py``):
   partition_reads :196-274     -> partition_reads(), partition_reads_batch()
        unique structures :203-215 (host); pairwise compatibility :217-234, edge pruning :240-255, connected components
        :256-257, even split and incompatible pairs :258-274 (GPU: Context.partition, flat arrays)
+  preprocess_ilp + partition_reads on tints that are not preprocessed yet -> pack_labels(), preprocess_ilp_batch(),
+       cluster_arrays_batch(): I / C / FL, the dedupe and everything behind it in one device call (Context.partition_labels)
 The ILP (run_ilp, Gurobi) and everything after it are out of scope.  There is no CPU implementation of the quadratic
 loops in this package: without the HIP library partition_reads() raises.  FCLU_HOST_PARTITIONS=1 keeps :256-274 on the
 host, behind the GPU's graph (adjacency_matrix + _components + _partitions_from_graph): for A/B runs and timings.
@@ -149,7 +151,8 @@ def split_list_evenly(l, m):
 CLUSTER_SO = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libfreddie_cluster.so")
 CLUSTER_SRC = [os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "freddie_cluster.hip")]
 EXPORTS = ["fclu_abi_version", "fclu_create", "fclu_destroy", "fclu_last_error", "fclu_compat_graph", "fclu_last_timing",
-           "fclu_partition", "fclu_partition_adj", "fclu_partition_results", "fclu_partition_timing"]
+           "fclu_partition", "fclu_partition_adj", "fclu_partition_results", "fclu_partition_timing",
+           "fclu_preprocess", "fclu_preprocess_results", "fclu_partition_reads", "fclu_preprocess_timing"]
 ERR_UNSUPPORTED = 3
 _lib = None
 
@@ -173,6 +176,18 @@ class _Parts(ctypes.Structure):
                 ("n_pairs", ctypes.c_int64), ("tint_part_off", ctypes.c_void_p), ("part_node_off", ctypes.c_void_p),
                 ("part_nodes", ctypes.c_void_p), ("part_rid_off", ctypes.c_void_p), ("part_rids", ctypes.c_void_p),
                 ("part_pair_off", ctypes.c_void_p), ("pairs", ctypes.c_void_p), ("label", ctypes.c_void_p)]
+
+
+class _Reads(ctypes.Structure):
+    _fields_ = [("n_tint", ctypes.c_int32), ("rep_off", ctypes.c_void_p), ("n_seg", ctypes.c_void_p), ("lab_off", ctypes.c_void_p),
+                ("labels", ctypes.c_void_p), ("tail", ctypes.c_void_p)]
+
+
+class _Prep(ctypes.Structure):
+    _fields_ = [("n_tint", ctypes.c_int32), ("n_reps", ctypes.c_int64), ("n_rows", ctypes.c_int64)] + [
+        (name, ctypes.c_void_p) for name in ("row_off", "bits_off", "adj_off", "rep_bits_off", "i_bits", "c_bits", "first", "last",
+                                             "raw_first", "raw_last", "rep_node", "node_rep", "mem_off", "mem", "bits",
+                                             "node_first", "node_last", "node_tail")]
 
 
 def build(force=False, verbose=False):
@@ -209,6 +224,14 @@ def load():
     L.fclu_partition_results.argtypes = [vp, ctypes.POINTER(_Parts)]
     L.fclu_partition_timing.restype = ctypes.c_int
     L.fclu_partition_timing.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
+    L.fclu_preprocess.restype = ctypes.c_int
+    L.fclu_preprocess.argtypes = [vp, ctypes.POINTER(_Reads)]
+    L.fclu_preprocess_results.restype = ctypes.c_int
+    L.fclu_preprocess_results.argtypes = [vp, ctypes.POINTER(_Prep)]
+    L.fclu_partition_reads.restype = ctypes.c_int
+    L.fclu_partition_reads.argtypes = [vp, ctypes.POINTER(_Reads), ctypes.c_int32]
+    L.fclu_preprocess_timing.restype = ctypes.c_int
+    L.fclu_preprocess_timing.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
     _lib = L
     return L
 
@@ -297,6 +320,54 @@ class Context:
         rc = self._L.fclu_partition_adj(self._h, row_off.size - 1, row_off.ctypes.data, adj_off.ctypes.data, adj.ctypes.data if adj.size else None,
                                         mem_off.ctypes.data, mem.ctypes.data if mem.size else None, int(maximum_ilp_size))
         return self._partition_arrays("fclu_partition_adj", rc)
+
+    @staticmethod
+    def _reads(packed):
+        r = _Reads(n_tint=packed["n_tint"])
+        keep = []
+        for name, dt in (("rep_off", np.int64), ("n_seg", np.int32), ("lab_off", np.int64), ("labels", np.uint32), ("tail", np.uint8)):
+            a = np.ascontiguousarray(packed[name], dt)
+            keep.append(a)
+            setattr(r, name, a.ctypes.data if a.size else None)
+        return r, keep
+
+    def _prep_arrays(self):
+        p = _Prep()
+        rc = self._L.fclu_preprocess_results(self._h, ctypes.byref(p))
+        if rc != 0:
+            raise ClusterError("fclu_preprocess_results: " + self._L.fclu_last_error(self._h).decode(), rc)
+        T, N, R = p.n_tint, int(p.n_reps), int(p.n_rows)
+        out = dict(n_tint=T, n_reps=N, n_rows=R)
+        for name in ("row_off", "bits_off", "adj_off", "rep_bits_off"):
+            out[name] = _copy_out(getattr(p, name), T + 1, np.int64)
+        n_rbits, n_bits = int(out["rep_bits_off"][-1]), int(out["bits_off"][-1])
+        for name, n, dt in (("i_bits", n_rbits, np.uint32), ("c_bits", n_rbits, np.uint32), ("first", N, np.int32), ("last", N, np.int32),
+                            ("raw_first", N, np.int32), ("raw_last", N, np.int32), ("rep_node", N, np.int32), ("node_rep", R, np.int32),
+                            ("mem_off", R + 1, np.int64), ("mem", N, np.int32), ("bits", n_bits, np.uint32), ("node_first", R, np.int32),
+                            ("node_last", R, np.int32), ("node_tail", R, np.uint8)):
+            out[name] = _copy_out(getattr(p, name), n, dt)
+        return out
+
+    def preprocess(self, packed):
+        """preprocess_ilp() per rep and the dedupe of a batch, on the device: packed = pack_labels().  Returns numpy arrays named as
+        in include/freddie_cluster.h, fclu_prep (prep_structures() / prep_members() give pack_structures() / pack_members())."""
+        r, keep = self._reads(packed)
+        rc = self._L.fclu_preprocess(self._h, ctypes.byref(r))
+        if rc != 0:
+            raise ClusterError("fclu_preprocess: " + self._L.fclu_last_error(self._h).decode(), rc)
+        return self._prep_arrays()
+
+    def partition_labels(self, packed, maximum_ilp_size):
+        """From label rows to tint['partitions'] of a batch in one device call: (preprocess() arrays, partition() arrays)."""
+        r, keep = self._reads(packed)
+        rc = self._L.fclu_partition_reads(self._h, ctypes.byref(r), int(maximum_ilp_size))
+        parts = self._partition_arrays("fclu_partition_reads", rc)
+        return self._prep_arrays(), parts
+
+    def preprocess_timing(self):
+        a, b = ctypes.c_float(), ctypes.c_float()
+        self._L.fclu_preprocess_timing(self._h, ctypes.byref(a), ctypes.byref(b))
+        return dict(rows_ms=a.value, dedupe_ms=b.value)
 
     def partition_timing(self):
         a, b = ctypes.c_float(), ctypes.c_float()
@@ -413,6 +484,113 @@ def _partitions_from_graph(unique, A, maximum_ilp_size, verbose):
     return parts
 
 
+# ---------------------------------------------------------------------------------------------------------------
+# the front on the device: label rows in, preprocess_ilp() + the dedupe (+ everything behind it) out
+# ---------------------------------------------------------------------------------------------------------------
+def tail_categories(tint):
+    """uint8 per rep: 0 'N', 1 'S', 2 'E' -- the category preprocess_ilp() gives the rep's first read (:291-300)."""
+    reads = tint["reads"]
+    out = np.zeros(len(tint["read_reps"]), np.uint8)
+    for i, members in enumerate(tint["read_reps"]):
+        pt = reads[members[0]]["poly_tail"]
+        if len(pt) == 1:
+            (key, (length, _)), = pt.items()
+            if length > 10:
+                out[i] = 1 if key in ("SA", "ST") else 2 if key in ("EA", "ET") else 0
+    return out
+
+
+def pack_labels(tints):
+    """The fclu_reads arrays (include/freddie_cluster.h) of read_segment() tints: a rep's row is its first read's labels, two bits
+    a label, sixteen labels a uint32 word."""
+    T = len(tints)
+    rep_off = np.zeros(T + 1, np.int64); lab_off = np.zeros(T + 1, np.int64)
+    n_seg = np.zeros(T, np.int32)
+    labels, tails = [], []
+    for t, tint in enumerate(tints):
+        reads, reps = tint["reads"], tint["read_reps"]
+        n, M = len(reps), len(tint["segs"])
+        LW = max((M + 15) // 16, 1)
+        n_seg[t] = M
+        rep_off[t + 1] = rep_off[t] + n
+        lab_off[t + 1] = lab_off[t] + n * LW
+        if n:
+            codes = np.zeros((n, LW * 16), np.uint8)
+            if M:
+                raw = b"".join(bytes(reads[m[0]]["data"][:M]) for m in reps)        # (labels are small ints: one C loop a row)
+                codes[:, :M] = np.frombuffer(raw, np.uint8).reshape(n, M) & 3
+            q = codes.reshape(n, LW * 4, 4)                                          # four labels a byte, the first in the low bits;
+            by = q[:, :, 0] | (q[:, :, 1] << 2) | (q[:, :, 2] << 4) | (q[:, :, 3] << 6)
+            labels.append(np.ascontiguousarray(by).view("<u4").astype(np.uint32, copy=False).reshape(-1))   # words: little-endian
+            tails.append(tail_categories(tint))
+    return dict(n_tint=T, rep_off=rep_off, n_seg=n_seg, lab_off=lab_off,
+                labels=np.concatenate(labels) if labels else np.zeros(0, np.uint32),
+                tail=np.concatenate(tails) if tails else np.zeros(0, np.uint8))
+
+
+def prep_structures(prep, n_seg):
+    """pack_structures() of the batch's unique rows, from Context.preprocess() arrays."""
+    return dict(n_tint=prep["n_tint"], row_off=prep["row_off"], n_seg=np.asarray(n_seg, np.int32), bits_off=prep["bits_off"],
+                bits=prep["bits"], first=prep["node_first"], last=prep["node_last"], tail=prep["node_tail"], adj_off=prep["adj_off"])
+
+
+def prep_members(prep):
+    """pack_members() of the batch's unique rows, from Context.preprocess() arrays."""
+    return dict(mem_off=prep["mem_off"], mem=prep["mem"])
+
+
+def _ilp_data_from_prep(tints, packed, prep, ilp_settings):
+    """Leaves every tint as preprocess_ilp() leaves it, from the device's per-rep arrays."""
+    for t, tint in enumerate(tints):
+        r0, r1 = int(packed["rep_off"][t]), int(packed["rep_off"][t + 1])
+        n, M = r1 - r0, int(packed["n_seg"][t])
+        W = max((M + 31) // 32, 1)
+        b0 = int(prep["rep_bits_off"][t])
+        rows = {}
+        for name in ("i_bits", "c_bits"):
+            words = prep[name][b0:b0 + n * W].reshape(n, W)
+            rows[name] = np.unpackbits(words.view(np.uint8), axis=1, bitorder="little")[:, :M].tolist() if n else []
+        first, last = prep["first"][r0:r1].tolist(), prep["last"][r0:r1].tolist()
+        raw_first, raw_last = prep["raw_first"][r0:r1].tolist(), prep["raw_last"][r0:r1].tolist()
+        tail = packed["tail"][r0:r1].tolist()
+        reads, read_reps = tint["reads"], tint["read_reps"]
+        I, C, FL = dict(), dict(), dict()
+        for i, members in enumerate(read_reps):
+            read = reads[members[0]]
+            I[i], C[i], FL[i] = rows["i_bits"][i], rows["c_bits"][i], (first[i], last[i])
+            cat = "NSE"[tail[i]]
+            if cat == "S":
+                read["gaps"][(-1, raw_first[i])] = next(iter(read["poly_tail"].values()))[1]
+            elif cat == "E":
+                read["gaps"][(raw_last[i], M)] = next(iter(read["poly_tail"].values()))[1]
+            for ridx in members:
+                reads[ridx]["poly_tail_category"] = cat
+                reads[ridx]["gaps"] = read["gaps"]
+        garbage_cost = {}
+        for i in range(len(read_reps)):
+            if ilp_settings["recycle_model"] == "exons":
+                garbage_cost[i] = len(read_reps[i]) * garbage_cost_exons(I=I[i])      # a list: raises like the reference (:314)
+            elif ilp_settings["recycle_model"] == "introns":
+                garbage_cost[i] = len(read_reps[i]) * garbage_cost_introns(C=C[i])  # a list: raises like the reference (:316)
+            elif ilp_settings["recycle_model"] == "constant":
+                garbage_cost[i] = len(read_reps[i]) * 3
+        tint["ilp_data"] = dict(FL=FL, I=I, C=C, garbage_cost=garbage_cost)
+
+
+def preprocess_ilp_batch(tints, ilp_settings, ctx):
+    """preprocess_ilp() of several read_segment() tints with one device call: every tint is left as preprocess_ilp() leaves it."""
+    packed = pack_labels(tints)
+    _ilp_data_from_prep(tints, packed, ctx.preprocess(packed), ilp_settings)
+
+
+def cluster_arrays_batch(tints, maximum_ilp_size, ctx):
+    """From read_segment() tints that are not preprocessed to the flat arrays of Context.partition(), one device call:
+    (pack_labels() arrays, Context.preprocess() arrays, partition arrays)."""
+    packed = pack_labels(tints)
+    prep, parts = ctx.partition_labels(packed, maximum_ilp_size)
+    return packed, prep, parts
+
+
 def partition_arrays_batch(tints, maximum_ilp_size, ctx):
     """partition_reads() of several preprocessed tints as the flat arrays of Context.partition(): one device call."""
     uniq = [unique_structures(t) for t in tints]
@@ -440,18 +618,29 @@ def _partition_reads_host_tail(tints, maximum_ilp_size, ctx, verbose):
         tint["partitions"] = _partitions_from_graph(uniq[t], adjacency_matrix(adj, packed, t), maximum_ilp_size, verbose)
 
 
-def partition_reads_batch(tints, maximum_ilp_size, ctx, verbose=True):
-    """partition_reads() of several preprocessed tints with one device call; sets tint['partitions'] on each.  A batch whose
-    pair list the library refuses as too large for one call goes tint by tint."""
+def partition_reads_batch(tints, maximum_ilp_size, ctx, verbose=True, ilp_settings=None):
+    """partition_reads() of several tints with one device call; sets tint['partitions'] on each.  A batch whose pair list the
+    library refuses as too large for one call goes tint by tint.  Tints without 'ilp_data' (straight from read_segment()) are
+    preprocessed by the same call (cluster_arrays_batch) and left as preprocess_ilp(tint, ilp_settings) leaves them; ilp_settings
+    defaults to the constant recycle model."""
     if os.environ.get("FCLU_HOST_PARTITIONS", "0") == "1":
         return _partition_reads_host_tail(tints, maximum_ilp_size, ctx, verbose)
+    fresh = [t for t in tints if "ilp_data" not in t]
+    if fresh and len(fresh) != len(tints):                               # a mixed batch: each kind its own way
+        done = [t for t in tints if "ilp_data" in t]
+        partition_reads_batch(fresh, maximum_ilp_size, ctx, verbose, ilp_settings)
+        return partition_reads_batch(done, maximum_ilp_size, ctx, verbose, ilp_settings)
     try:
-        arr = partition_arrays_batch(tints, maximum_ilp_size, ctx)
+        if fresh:
+            packed, prep, arr = cluster_arrays_batch(tints, maximum_ilp_size, ctx)
+            _ilp_data_from_prep(tints, packed, prep, ilp_settings or dict(recycle_model="constant"))
+        else:
+            arr = partition_arrays_batch(tints, maximum_ilp_size, ctx)
     except ClusterError as e:
         if e.code != ERR_UNSUPPORTED or len(tints) < 2:
             raise
         for tint in tints:
-            partition_reads_batch([tint], maximum_ilp_size, ctx, verbose)
+            partition_reads_batch([tint], maximum_ilp_size, ctx, verbose, ilp_settings)
         return
     for t, tint in enumerate(tints):
         tint["partitions"] = _partitions_from_arrays(arr, t, verbose)

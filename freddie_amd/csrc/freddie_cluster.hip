@@ -2,6 +2,8 @@
 // stage: the pairwise read-compatibility graph of partition_reads() (py/freddie_cluster.py:217-234) and its iterated
 // edge pruning (:240-255), for a batch of tints per call; and, behind the pruned graph on the device, the rest of the function
 // (fclu_partition): connected components (:256-257), the even split (:258-260) and the incompatible rep pairs (:261-273).
+// In front of the graph (fclu_preprocess, fclu_partition_reads): preprocess_ilp()'s per-rep I / C / FL (:285-310) from label rows at two
+// bits a label, and the dedupe of reps with the same structure (:203-215); the unique rows go to the graph without leaving the device.
 //
 // Reads are bit rows (bit s = the read covers segment s), so the reference's two list comprehensions over the
 // overlap [f, l] (:229, :232) become popcounts of (a & b & mask) and ((a ^ b) & mask).  The graph is a symmetric
@@ -615,6 +617,170 @@ __global__ void __launch_bounds__(256) k_offsets(i64 n_rows_total, int n_tint, c
     }
 }
 
+// ================================================================================================================
+// The front of partition_reads(): preprocess_ilp() per rep (py/freddie_cluster.py:285-310, :175-183) and the dedupe of reps
+// with the same structure (:203-215), from label rows at two bits a label (fclu_reads).
+// ================================================================================================================
+struct PrepTint {
+    i64 rep0, lab_off, rbits_off, slot0;   // first rep; first label word; first word of the reps' I / C rows; first lane slot of k_rows
+    int n, n_seg, lw, w, g_log2;            // reps, segments, label words and bit words per row, log2 of the lanes a rep gets
+};
+
+// the 32 even bits of x, packed
+__device__ __forceinline__ unsigned even_bits(u64 x) {
+    x &= 0x5555555555555555ull;
+    x = (x | (x >> 1)) & 0x3333333333333333ull;
+    x = (x | (x >> 2)) & 0x0f0f0f0f0f0f0f0full;
+    x = (x | (x >> 4)) & 0x00ff00ff00ff00ffull;
+    x = (x | (x >> 8)) & 0x0000ffff0000ffffull;
+    return (unsigned)(x | (x >> 16));
+}
+
+__device__ __forceinline__ unsigned mix32(unsigned h) {
+    h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16;
+    return h;
+}
+
+// bits [f, l] of word w of a row, for any f, l (none when the word lies outside, or l < f)
+__device__ __forceinline__ unsigned span_mask(int f, int l, int w) {
+    if (l < f || w * 32 + 31 < f || w * 32 > l) return 0u;
+    return range_mask(f, l, w);
+}
+
+// ---- per rep: I, C, raw first / last, FL, and the dedupe's sort key ------------------------------------------------
+// A rep gets g = 2^g_log2 lanes (the smallest power of two that holds its W words, 64 at the most), so a wave takes 64 / g reps: rows
+// of one or two words do not cost a wave each.  A tint's slots start at a multiple of 64: a wave works on one tint, and a rep's lanes
+// are g consecutive lanes, so the min / max / sum over its words are xor shuffles below g.  A lane's bit word w comes from the label
+// words 2w and 2w + 1: I = the low bit of each label (2 counts as 0, :287-288), "label is 0" = neither bit; C is that, cut to
+// [first, last] in a second pass over the lane's own words (:308-310).  err[0..2]: the smallest rep with a label 3, with a bit behind
+// its M labels, with a tail category above 2.
+__global__ void __launch_bounds__(256) k_rows(int n_tint, i64 n_slots, const PrepTint *pt, const unsigned *labels, const unsigned char *tail,
+                                              unsigned hash_mask, unsigned *ibits, unsigned *cbits, int *raw_first, int *raw_last, int *first,
+                                              int *last, int *rep_tint, u64 *key, int *val, int *err) {
+    const int lane = lane_id();
+    const i64 wave_g = ((i64)blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = ((i64)gridDim.x * blockDim.x) >> 6;
+    for (i64 s0 = wave_g * 64; s0 < n_slots; s0 += n_waves * 64) {
+        int lo = 0, hi = n_tint - 1;                          // the last tint whose slots start at or before s0 (wave-uniform)
+        while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (pt[mid].slot0 <= s0) lo = mid; else hi = mid - 1; }
+        const int t = __builtin_amdgcn_readfirstlane(lo);
+        const PrepTint d = pt[t];
+        const int g = 1 << d.g_log2, sub = lane & (g - 1);
+        const i64 r = (s0 - d.slot0 + lane) >> d.g_log2;
+        const bool ok = r < d.n;
+        const i64 rep = d.rep0 + (ok ? r : 0);
+        const unsigned *lab = labels + d.lab_off + (ok ? r : 0) * d.lw;
+        unsigned *ib = ibits + d.rbits_off + (ok ? r : 0) * d.w, *cb = cbits + d.rbits_off + (ok ? r : 0) * d.w;
+        int fmin = 0x7fffffff, lmax = -1, bad = 0;
+        unsigned h = 0;
+        if (ok)
+            for (int w = sub; w < d.w; w += g) {
+                const u64 x = (u64)lab[2 * w] | (2 * w + 1 < d.lw ? (u64)lab[2 * w + 1] << 32 : 0ull);
+                int nv = d.n_seg - 32 * w; nv = nv > 32 ? 32 : (nv < 0 ? 0 : nv);
+                const u64 vm = nv >= 32 ? ~0ull : ((1ull << (2 * nv)) - 1ull);
+                const u64 b0 = x & 0x5555555555555555ull, b1 = (x >> 1) & 0x5555555555555555ull;
+                if (b0 & b1 & vm) bad |= 1;
+                if (x & ~vm) bad |= 2;
+                const unsigned iw = even_bits(b0 & ~b1 & vm), zw = even_bits(~(b0 | b1) & vm);
+                ib[w] = iw; cb[w] = zw;
+                if (iw) {
+                    const int a = w * 32 + __ffs((int)iw) - 1, z = w * 32 + 31 - __clz((int)iw);
+                    fmin = a < fmin ? a : fmin; lmax = z > lmax ? z : lmax;
+                }
+                h += mix32(iw ^ ((unsigned)w * 0x9e3779b9u + 0x7f4a7c15u));
+            }
+        for (int s = g >> 1; s >= 1; s >>= 1) {
+            const int of = __shfl_xor(fmin, s), ol = __shfl_xor(lmax, s);
+            fmin = of < fmin ? of : fmin; lmax = ol > lmax ? ol : lmax;
+            h += (unsigned)__shfl_xor((int)h, s);
+        }
+        const int tl = ok ? tail[rep] : 0;
+        if (tl > 2) bad |= 4;
+        const int rf = fmin == 0x7fffffff ? -1 : fmin, rl = fmin == 0x7fffffff ? d.n_seg - 1 : lmax;     // find_segment_read (:175-183)
+        const int f = tl == 1 ? 0 : rf, l = tl == 2 ? d.n_seg - 1 : rl;                                  // the tail's override (:297, :300)
+        if (ok) {
+            for (int w = sub; w < d.w; w += g) cb[w] &= span_mask(f < 0 ? 0 : f, l, w);
+            if (bad & 1) atomicMin(&err[0], (int)rep);
+            if (bad & 2) atomicMin(&err[1], (int)rep);
+            if (bad & 4) atomicMin(&err[2], (int)rep);
+            if (sub == 0) {
+                raw_first[rep] = rf; raw_last[rep] = rl; first[rep] = f; last[rep] = l; rep_tint[rep] = t;
+                const unsigned hh = mix32(h ^ mix32((unsigned)f * 0x9e3779b9u + (unsigned)l) ^ ((unsigned)tl * 0x27d4eb2fu));
+                key[rep] = ((u64)(unsigned)t << 32) | (u64)(hh & hash_mask);
+                val[rep] = (int)rep;
+            }
+        }
+    }
+}
+
+// ---- the dedupe (:203-215) --------------------------------------------------------------------------------------
+// The reps, sorted (stable) by (tint, hash): a bucket = the run of one key, its reps ascending.  The hash only makes the buckets; a
+// rep's class is decided on the whole row: its leader is the FIRST rep of its bucket with the same I row, first, last and tail --
+// the smallest rep of its class, whatever else shares the bucket and however the classes interleave in it.  Without collisions the
+// bucket's first rep answers at once.
+__global__ void __launch_bounds__(256) k_heads(i64 n, const u64 *skey, int *head) {
+    for (i64 k = (i64)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += (i64)gridDim.x * blockDim.x)
+        head[k] = (k > 0 && skey[k - 1] == skey[k]) ? 0 : (int)k;
+}
+
+__global__ void __launch_bounds__(256) k_leader(i64 n, const u64 *skey, const int *sval, const int *bstart, const PrepTint *pt, const unsigned *ibits,
+                                                const int *first, const int *last, const unsigned char *tail, int *leader, int *flag) {
+    for (i64 k = (i64)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += (i64)gridDim.x * blockDim.x) {
+        const PrepTint d = pt[(int)(skey[k] >> 32)];
+        const int rep = sval[k];
+        const unsigned *a = ibits + d.rbits_off + (i64)(rep - d.rep0) * d.w;
+        const int fa = first[rep], la = last[rep], ta = tail[rep];
+        int lead = rep;
+        for (i64 j = bstart[k]; j < k; ++j) {
+            const int other = sval[j];
+            if (first[other] != fa || last[other] != la || tail[other] != ta) continue;
+            const unsigned *b = ibits + d.rbits_off + (i64)(other - d.rep0) * d.w;
+            bool same = true;
+            for (int w = 0; w < d.w; ++w) if (a[w] != b[w]) { same = false; break; }
+            if (same) { lead = other; break; }
+        }
+        leader[rep] = lead;
+        flag[rep] = lead == rep ? 1 : 0;
+    }
+}
+
+// row_off[t] = the number of leaders in front of tint t's first rep (node_id: the exclusive scan of flag, n_reps + 1 entries)
+__global__ void __launch_bounds__(256) k_row_off(int n_tint, i64 n_reps, const PrepTint *pt, const int *node_id, i64 *row_off) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t <= n_tint) row_off[t] = node_id[t < n_tint ? pt[t].rep0 : n_reps];
+}
+
+// Nodes are numbered by their smallest rep (the leader): the leaders' scan IS the numbering.  A rep learns its node; a leader hands
+// its row, first, last and tail to the node's place in the arrays k_compat reads (the batch's layout, fclu_batch).
+__global__ void __launch_bounds__(256) k_nodes(i64 n_reps, const int *rep_tint, const PrepTint *pt, const TintDesc *tints, const int *leader,
+                                               const int *node_id, const unsigned *ibits, const int *first, const int *last,
+                                               const unsigned char *tail, int *rep_node, unsigned *nkey, int *nval, int *node_rep,
+                                               unsigned *bits, int *nfirst, int *nlast, unsigned char *ntail) {
+    for (i64 rep = (i64)blockIdx.x * blockDim.x + threadIdx.x; rep < n_reps; rep += (i64)gridDim.x * blockDim.x) {
+        const int t = rep_tint[rep];
+        const PrepTint p = pt[t];
+        const TintDesc d = tints[t];
+        const int lead = leader[rep], node = node_id[lead];
+        rep_node[rep] = node - (int)d.row0;
+        nkey[rep] = (unsigned)node;
+        nval[rep] = (int)(rep - p.rep0);
+        if (lead == rep) {
+            node_rep[node] = (int)(rep - p.rep0);
+            nfirst[node] = first[rep]; nlast[node] = last[rep]; ntail[node] = tail[rep];
+            const unsigned *src = ibits + p.rbits_off + (rep - p.rep0) * p.w;
+            unsigned *dst = bits + d.bits_off + (i64)(node - d.row0) * d.w;
+            for (int w = 0; w < p.w; ++w) dst[w] = src[w];
+        }
+    }
+}
+
+// the reps sorted (stable) by node are the nodes' member lists end to end, each ascending: node q's starts where its key first stands
+__global__ void __launch_bounds__(256) k_mem_off(i64 n_reps, i64 n_rows, const unsigned *skey, i64 *mem_off) {
+    for (i64 k = (i64)blockIdx.x * blockDim.x + threadIdx.x; k <= n_reps; k += (i64)gridDim.x * blockDim.x) {
+        if (k == n_reps) mem_off[n_rows] = n_reps;
+        else if (k == 0 || skey[k - 1] != skey[k]) mem_off[skey[k]] = k;
+    }
+}
+
 }  // namespace
 
 struct GrowBuf {              // device buffer that lives with the context and only ever grows
@@ -646,6 +812,13 @@ struct fclu_ctx {
     HostBuf h_cc_flags, h_tint_part_off, h_part_node_off, h_part_nodes, h_part_rid_off, h_part_rids, h_part_pair_off, h_pairs, h_label;
     fclu_parts parts = {};
     bool have_parts = false;
+    // fclu_preprocess() / fclu_partition_reads(): device arrays (P_*) and the pinned copies fclu_preprocess_results() hands out (Q_*)
+    GrowBuf pd[32];
+    HostBuf ph[24];
+    hipEvent_t qev[6] = {};
+    float rows_ms = 0.f, dedupe_ms = 0.f;
+    fclu_prep prep = {};
+    bool have_prep = false;
 };
 
 namespace {
@@ -686,7 +859,7 @@ int cc_in_lds(int n, int aw) {
 
 int compat_device(fclu_ctx *c, const fclu_batch *b, int32_t prune, uint64_t *adj_out, int32_t *rounds_out);
 int check_members(fclu_ctx *c, i64 R, const int64_t *mem_off, const int32_t *mem, int32_t maximum_ilp_size);
-int partition_device(fclu_ctx *c, int T, i64 R, const int64_t *mem_off, const int32_t *mem, int32_t maximum_ilp_size);
+int partition_device(fclu_ctx *c, int T, i64 R, const int64_t *mem_off, const int32_t *mem, i64 n_mem_device, int32_t maximum_ilp_size);
 
 }  // namespace
 
@@ -709,6 +882,7 @@ int fclu_create(int device, fclu_ctx **out) {
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
     for (int i = 0; e == hipSuccess && i < 3; ++i) e = hipEventCreate(&c->ev[i]);
     for (int i = 0; e == hipSuccess && i < 6; ++i) e = hipEventCreate(&c->pev[i]);
+    for (int i = 0; e == hipSuccess && i < 6; ++i) e = hipEventCreate(&c->qev[i]);
     if (e == hipSuccess)
         e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_cc_lds), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
     if (e == hipSuccess)
@@ -734,6 +908,9 @@ void fclu_destroy(fclu_ctx *c) {
     if (c->stream) { (void)hipStreamSynchronize(c->stream); (void)hipStreamDestroy(c->stream); }
     for (int i = 0; i < 3; ++i) if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
     for (int i = 0; i < 6; ++i) if (c->pev[i]) (void)hipEventDestroy(c->pev[i]);
+    for (int i = 0; i < 6; ++i) if (c->qev[i]) (void)hipEventDestroy(c->qev[i]);
+    for (GrowBuf &b : c->pd) if (b.p) (void)hipFree(b.p);
+    for (HostBuf &b : c->ph) if (b.p) (void)hipHostFree(b.p);
     GrowBuf *bufs[] = {&c->tints, &c->tiles, &c->row_tint, &c->bits, &c->first, &c->last, &c->tail, &c->adj[0], &c->adj[1], &c->deg,
                        &c->changed, &c->word_tint, &c->tint_word0, &c->deg1, &c->pass_any, &c->small_tints, &c->small_rounds,
                        &c->parent, &c->skey, &c->rows, &c->sval, &c->comp_start, &c->comp_end, &c->chunk_end, &c->head, &c->part_id, &c->smult,
@@ -758,20 +935,36 @@ int fclu_compat_graph(fclu_ctx *c, const fclu_batch *b, int32_t prune, uint64_t 
 
 namespace {
 
-// The graph of a batch: compatibility, then pruning.  The pruned matrix stays on the device in c->adj[c->adj_cur] (with the tints'
-// descriptors in c->tints / c->h_tints and c->row_tint) for fclu_partition(); adj_out may be null.
-int compat_device(fclu_ctx *c, const fclu_batch *b, int32_t prune, uint64_t *adj_out, int32_t *rounds_out) {
-    if (b->n_tint <= 0) return fail(c, FCLU_ERR_ARG, "fclu_compat_graph: empty batch");
-    HIP_TRY(c, hipSetDevice(c->device));
-    const int T = b->n_tint;
-    const i64 R = b->row_off[T];
-    // host-side shape checks: the kernels index with these and nothing else
-    std::vector<TintDesc> tints((size_t)T);
-    std::vector<int4> tiles;
-    std::vector<int> row_tint((size_t)R);
-    std::vector<int2> word_tint;                         // every adjacency word column of every tint: (tint, word)
-    std::vector<i64> tint_word0((size_t)T + 1, 0);
+// What the host derives from a batch's shape (stage_tints) and the graph kernels are launched with (compat_run).
+struct Staged {
+    int T = 0, n_tiles = 0, max_w = 1, max_aw_large = 0, n_words = 0;
+    i64 R = 0, n_bits = 0, n_adj = 0;
+    bool any_large = false, empty = false;
     std::vector<int> small_tints;                        // pruned whole in LDS (k_prune_lds); FCLU_PRUNE_LDS=0: none (tests)
+    size_t small_lds = 0;
+    // what the uploads read: alive until the call that staged them has synchronised
+    std::vector<TintDesc> tints;
+    std::vector<int4> tiles;
+    std::vector<int> row_tint;
+    std::vector<int2> word_tint;                         // every adjacency word column of every tint: (tint, word)
+    std::vector<i64> tint_word0;
+};
+
+// Host staging of a batch: the shape checks, the tints' descriptors, tiles and row / word maps, device buffers grown and the maps
+// uploaded.  b: the caller's rows, checked against their tint (fclu_compat_graph, fclu_partition), or null when the rows were made on
+// the device (fclu_partition_reads: first / last / tail in range and bits inside [first, last] by construction).
+int stage_tints(fclu_ctx *c, int T, const int64_t *row_off, const int32_t *n_seg, const int64_t *bits_off, const int64_t *adj_off,
+                int32_t prune, const fclu_batch *b, Staged &st) {
+    HIP_TRY(c, hipSetDevice(c->device));
+    const i64 R = row_off[T];
+    // host-side shape checks: the kernels index with these and nothing else
+    std::vector<TintDesc> &tints = st.tints;
+    std::vector<int4> &tiles = st.tiles;
+    std::vector<int> &row_tint = st.row_tint;
+    std::vector<int2> &word_tint = st.word_tint;
+    std::vector<i64> &tint_word0 = st.tint_word0;
+    std::vector<int> &small_tints = st.small_tints;
+    tints.assign((size_t)T, TintDesc()); row_tint.assign((size_t)R, 0); tint_word0.assign((size_t)T + 1, 0);
     const char *lds_env = getenv("FCLU_PRUNE_LDS");
     const bool lds_ok = !(lds_env && lds_env[0] == '0');
     const char *ldsw_env = getenv("FCLU_PRUNE_LDS_WORDS");                // (tests: a lower limit, so that small tints take both ways in one batch)
@@ -781,23 +974,24 @@ int compat_device(fclu_ctx *c, const fclu_batch *b, int32_t prune, uint64_t *adj
     int max_w = 1, max_aw_large = 0;
     for (int t = 0; t < T; ++t) {
         TintDesc &d = tints[(size_t)t];
-        d.row0 = b->row_off[t];
-        const i64 n = b->row_off[t + 1] - d.row0;
-        if (n < 0 || n > (1 << 30) || b->n_seg[t] < 0) return fail(c, FCLU_ERR_ARG, "tint %d: bad row count or segment count", t);
-        d.n = (int)n; d.n_seg = b->n_seg[t];
+        d.row0 = row_off[t];
+        const i64 n = row_off[t + 1] - d.row0;
+        if (n < 0 || n > (1 << 30) || n_seg[t] < 0) return fail(c, FCLU_ERR_ARG, "tint %d: bad row count or segment count", t);
+        d.n = (int)n; d.n_seg = n_seg[t];
         d.w = (d.n_seg + 31) / 32; if (d.w < 1) d.w = 1;
         d.aw = (d.n + 63) / 64;
-        d.bits_off = b->bits_off[t]; d.adj_off = b->adj_off[t];
+        d.bits_off = bits_off[t]; d.adj_off = adj_off[t];
         d.in_lds = (prune && lds_ok && d.n > 0 && d.n <= 65535 && (i64)d.n * d.aw <= lds_words) ? 1 : 0;
         d.cc_lds = cc_in_lds(d.n, d.aw);
         if (d.in_lds) { small_tints.push_back(t); small_lds = std::max(small_lds, ((size_t)2 * d.n * d.aw + d.aw) * 8 + (size_t)d.n * 2 + 16); }
         else if (d.n > 0) { any_large = true; max_aw_large = std::max(max_aw_large, d.aw); }
-        if (b->bits_off[t + 1] - d.bits_off != (i64)d.n * d.w) return fail(c, FCLU_ERR_ARG, "tint %d: bits_off does not match rows x words", t);
-        if (b->adj_off[t + 1] - d.adj_off != (i64)d.n * d.aw) return fail(c, FCLU_ERR_ARG, "tint %d: adj_off does not match rows x words", t);
+        if (bits_off[t + 1] - d.bits_off != (i64)d.n * d.w) return fail(c, FCLU_ERR_ARG, "tint %d: bits_off does not match rows x words", t);
+        if (adj_off[t + 1] - d.adj_off != (i64)d.n * d.aw) return fail(c, FCLU_ERR_ARG, "tint %d: adj_off does not match rows x words", t);
         if (d.w > kMaxWords) return fail(c, FCLU_ERR_UNSUPPORTED, "tint %d has %d segments; this build stages at most %d", t, d.n_seg, kMaxWords * 32);
         if (d.w > max_w) max_w = d.w;
         for (i64 r = 0; r < n; ++r) {
             row_tint[(size_t)(d.row0 + r)] = t;
+            if (!b) continue;
             const int f = b->first[d.row0 + r], l = b->last[d.row0 + r];
             if (f < -1 || l >= (d.n_seg > 0 ? d.n_seg : 1) || b->tail[d.row0 + r] > 2) return fail(c, FCLU_ERR_ARG, "tint %d read %lld: first/last/tail out of range", t, r);
             // a read's bits lie inside [first, last] (first / last ARE its first and last covered segment, :175-183): k_compat counts on it
@@ -816,13 +1010,15 @@ int compat_device(fclu_ctx *c, const fclu_batch *b, int32_t prune, uint64_t *adj
         for (int z = 0; z < d.aw; ++z) word_tint.push_back(make_int2(t, z));
         tint_word0[(size_t)t + 1] = (i64)word_tint.size();
     }
-    const i64 n_bits = b->bits_off[T], n_adj = b->adj_off[T];
+    const i64 n_bits = bits_off[T], n_adj = adj_off[T];
     const int n_tiles = (int)tiles.size();
-    if (rounds_out) for (int t = 0; t < T; ++t) rounds_out[t] = 0;
+    st.T = T; st.R = R; st.n_bits = n_bits; st.n_adj = n_adj; st.n_tiles = n_tiles; st.max_w = max_w; st.max_aw_large = max_aw_large;
+    st.any_large = any_large; st.small_lds = small_lds; st.n_words = (int)word_tint.size();
     c->compat_ms = c->prune_ms = 0.f;
     c->h_tints = tints;
     c->adj_cur = 0;
-    if (n_tiles == 0 || R == 0) return FCLU_OK;
+    st.empty = n_tiles == 0 || R == 0;
+    if (st.empty) return FCLU_OK;
 
     GrowBuf &d_tints = c->tints, &d_tiles = c->tiles, &d_row_tint = c->row_tint, &d_bits = c->bits, &d_first = c->first, &d_last = c->last,
             &d_tail = c->tail, &d_deg = c->deg, &d_changed = c->changed, &d_word_tint = c->word_tint, &d_tint_word0 = c->tint_word0,
@@ -860,10 +1056,23 @@ int compat_device(fclu_ctx *c, const fclu_batch *b, int32_t prune, uint64_t *adj
     HIP_TRY(c, hipMemcpyAsync(d_row_tint.p, row_tint.data(), (size_t)R * 4, hipMemcpyHostToDevice, s));
     HIP_TRY(c, hipMemcpyAsync(d_word_tint.p, word_tint.data(), word_tint.size() * sizeof(int2), hipMemcpyHostToDevice, s));
     HIP_TRY(c, hipMemcpyAsync(d_tint_word0.p, tint_word0.data(), tint_word0.size() * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(c, hipMemcpyAsync(d_bits.p, b->bits, (size_t)n_bits * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(c, hipMemcpyAsync(d_first.p, b->first, (size_t)R * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(c, hipMemcpyAsync(d_last.p, b->last, (size_t)R * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(c, hipMemcpyAsync(d_tail.p, b->tail, (size_t)R, hipMemcpyHostToDevice, s));
+    return FCLU_OK;
+}
+
+// The graph of a staged batch whose rows (c->bits / first / last / tail) are on the device: compatibility, then pruning.  The pruned
+// matrix stays on the device in c->adj[c->adj_cur] (with the tints' descriptors in c->tints / c->h_tints and c->row_tint) for
+// partition_device(); adj_out may be null.
+int compat_run(fclu_ctx *c, const Staged &st, int32_t prune, uint64_t *adj_out, int32_t *rounds_out) {
+    const int T = st.T, n_tiles = st.n_tiles, max_w = st.max_w, max_aw_large = st.max_aw_large;
+    const i64 R = st.R, n_adj = st.n_adj;
+    const bool any_large = st.any_large;
+    const std::vector<int> &small_tints = st.small_tints;
+    const size_t small_lds = st.small_lds;
+    GrowBuf &d_tints = c->tints, &d_tiles = c->tiles, &d_row_tint = c->row_tint, &d_bits = c->bits, &d_first = c->first, &d_last = c->last,
+            &d_tail = c->tail, &d_deg = c->deg, &d_changed = c->changed, &d_word_tint = c->word_tint, &d_tint_word0 = c->tint_word0,
+            &d_deg1 = c->deg1, &d_pass_any = c->pass_any;
+    GrowBuf *d_adj = c->adj;
+    hipStream_t s = c->stream;
 
     const int grid = n_tiles < 8192 ? n_tiles : 8192;
     // rows of at most kRankWords words: the rank tables ride along (FCLU_RANK=0 keeps the masked sums: tests)
@@ -894,7 +1103,7 @@ int compat_device(fclu_ctx *c, const fclu_batch *b, int32_t prune, uint64_t *adj
         const char *edge_env = getenv("FCLU_PRUNE_EDGES");
         const bool edge_walk = max_aw_large <= kEdgeChunks * 64 && !(edge_env && edge_env[0] == '0');
         const int edge_chunks = (max_aw_large + 63) / 64 > 0 ? (max_aw_large + 63) / 64 : 1;
-        const int n_words = (int)word_tint.size();
+        const int n_words = st.n_words;
         int *h_any = c->h_flags, *h_changed = c->h_flags + kBurst;
         bool done = false;
         for (int burst = 0; burst < (1 << 18) && !done; ++burst) {
@@ -944,6 +1153,22 @@ int compat_device(fclu_ctx *c, const fclu_batch *b, int32_t prune, uint64_t *adj
     return FCLU_OK;
 }
 
+// The graph of a batch of the caller's rows: staging with every check, the rows' upload, the kernels.
+int compat_device(fclu_ctx *c, const fclu_batch *b, int32_t prune, uint64_t *adj_out, int32_t *rounds_out) {
+    if (b->n_tint <= 0) return fail(c, FCLU_ERR_ARG, "fclu_compat_graph: empty batch");
+    Staged st;
+    const int rc = stage_tints(c, b->n_tint, b->row_off, b->n_seg, b->bits_off, b->adj_off, prune, b, st);
+    if (rc != FCLU_OK) return rc;
+    if (rounds_out) for (int t = 0; t < st.T; ++t) rounds_out[t] = 0;
+    if (st.empty) return FCLU_OK;
+    hipStream_t s = c->stream;
+    HIP_TRY(c, hipMemcpyAsync(c->bits.p, b->bits, (size_t)st.n_bits * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(c->first.p, b->first, (size_t)st.R * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(c->last.p, b->last, (size_t)st.R * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(c->tail.p, b->tail, (size_t)st.R, hipMemcpyHostToDevice, s));
+    return compat_run(c, st, prune, adj_out, rounds_out);
+}
+
 
 // ---- partition_reads() behind the graph (:256-274) ---------------------------------------------------------------
 int check_members(fclu_ctx *c, i64 R, const int64_t *mem_off, const int32_t *mem, int32_t maximum_ilp_size) {
@@ -968,8 +1193,9 @@ hipError_t grow_host(HostBuf &b, size_t bytes) {
 
 int bits_for(i64 n) { int b = 1; while (b < 32 && (1ll << b) < n) ++b; return b; }
 
-// c->tints / c->h_tints / c->row_tint describe the batch and c->adj[c->adj_cur] holds its pruned matrices.
-int partition_device(fclu_ctx *c, int T, i64 R, const int64_t *mem_off, const int32_t *mem, int32_t maximum_ilp_size) {
+// c->tints / c->h_tints / c->row_tint describe the batch and c->adj[c->adj_cur] holds its pruned matrices.  mem_off null: the members
+// are on the device already (c->mem_off, c->mem: n_mem_device rep ids), where the dedupe left them.
+int partition_device(fclu_ctx *c, int T, i64 R, const int64_t *mem_off, const int32_t *mem, i64 n_mem_device, int32_t maximum_ilp_size) {
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = c->stream;
     c->components_ms = c->pairs_ms = 0.f;
@@ -985,7 +1211,7 @@ int partition_device(fclu_ctx *c, int T, i64 R, const int64_t *mem_off, const in
         const u64 *d_adj = c->adj[c->adj_cur].as<u64>();
         const TintDesc *d_tints = c->tints.as<TintDesc>();
         const int *d_row_tint = c->row_tint.as<int>();
-        const i64 n_mem = mem_off[R];
+        const i64 n_mem = mem_off ? mem_off[R] : n_mem_device;
         std::vector<int> small;
         size_t small_lds = 0;
         bool any_large = false;
@@ -1014,8 +1240,10 @@ int partition_device(fclu_ctx *c, int T, i64 R, const int64_t *mem_off, const in
         HIP_TRY(c, rocprim::exclusive_scan(nullptr, scan_bytes, c->head.as<i64>(), c->part_id.as<i64>(), (i64)0, R1, rocprim::plus<i64>(), s));
         const size_t tmp_bytes = std::max(sort_bytes, scan_bytes);
         HIP_TRY(c, grow(c->tmp, tmp_bytes));
-        HIP_TRY(c, hipMemcpyAsync(c->mem_off.p, mem_off, R1 * 8, hipMemcpyHostToDevice, s));
-        if (n_mem) HIP_TRY(c, hipMemcpyAsync(c->mem.p, mem, (size_t)n_mem * 4, hipMemcpyHostToDevice, s));
+        if (mem_off) {
+            HIP_TRY(c, hipMemcpyAsync(c->mem_off.p, mem_off, R1 * 8, hipMemcpyHostToDevice, s));
+            if (n_mem) HIP_TRY(c, hipMemcpyAsync(c->mem.p, mem, (size_t)n_mem * 4, hipMemcpyHostToDevice, s));
+        }
         if (!small.empty()) HIP_TRY(c, hipMemcpyAsync(c->small_tints.p, small.data(), small.size() * 4, hipMemcpyHostToDevice, s));
 
         const int row_grid = (int)std::min<i64>((R + 256) / 256, 4096), wave_grid = (int)std::min<i64>((R + 3) / 4, 65536);
@@ -1135,9 +1363,238 @@ int partition_device(fclu_ctx *c, int T, i64 R, const int64_t *mem_off, const in
     return FCLU_OK;
 }
 
+
+// ---- preprocess_ilp() + the dedupe of a batch of label rows ----------------------------------------------------------
+enum { P_TINTS, P_LABELS, P_TAIL, P_IBITS, P_CBITS, P_RFIRST, P_RLAST, P_FIRST, P_LAST, P_REP_TINT, P_KEY, P_SKEY, P_VAL, P_SVAL, P_HEAD,
+       P_BSTART, P_LEADER, P_FLAG, P_NODE_ID, P_ROW_OFF, P_REP_NODE, P_NODE_REP, P_NKEY, P_SNKEY, P_NVAL, P_ERR, P_TMP };
+enum { Q_ROW_OFF, Q_BITS_OFF, Q_ADJ_OFF, Q_RBITS_OFF, Q_IBITS, Q_CBITS, Q_FIRST, Q_LAST, Q_RFIRST, Q_RLAST, Q_REP_NODE, Q_NODE_REP, Q_MEM_OFF,
+       Q_MEM, Q_BITS, Q_NFIRST, Q_NLAST, Q_NTAIL, Q_ERR };
+
+// Rows, dedupe and the staging of the unique rows as a batch: behind it c->bits / first / last / tail hold the nodes in fclu_batch's
+// layout, c->mem_off / c->mem their members, st what compat_run() needs, and the pinned copies of everything are on their way (the
+// caller synchronises).  Between the two halves only row_off (n_tint + 1 counts) and the three error words come back to the host.
+int preprocess_device(fclu_ctx *c, const fclu_reads *rd, int32_t prune, Staged &st, i64 &n_reps_out) {
+    c->have_prep = false;
+    c->rows_ms = c->dedupe_ms = 0.f;
+    if (!rd || rd->n_tint <= 0) return fail(c, FCLU_ERR_ARG, "fclu_preprocess: empty batch");
+    if (!rd->rep_off || !rd->n_seg || !rd->lab_off) return fail(c, FCLU_ERR_ARG, "fclu_preprocess: rep_off, n_seg or lab_off is null");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const int T = rd->n_tint;
+    if (rd->rep_off[0] != 0 || rd->lab_off[0] != 0) return fail(c, FCLU_ERR_ARG, "fclu_preprocess: rep_off and lab_off start at 0");
+    std::vector<PrepTint> pt((size_t)T);
+    std::vector<int64_t> rbits_off((size_t)T + 1, 0);
+    i64 n_slots = 0;
+    for (int t = 0; t < T; ++t) {
+        PrepTint &d = pt[(size_t)t];
+        const i64 n = rd->rep_off[t + 1] - rd->rep_off[t];
+        if (n < 0 || n > (1 << 30) || rd->n_seg[t] < 0)
+            return fail(c, FCLU_ERR_ARG, "tint %d: negative or too large rep count (%lld) or segment count (%d)", t, n, (int)rd->n_seg[t]);
+        if (rd->n_seg[t] > kMaxWords * 32)
+            return fail(c, FCLU_ERR_UNSUPPORTED, "tint %d has %d segments; this build stages at most %d", t, (int)rd->n_seg[t], kMaxWords * 32);
+        d.rep0 = rd->rep_off[t]; d.lab_off = rd->lab_off[t]; d.rbits_off = rbits_off[(size_t)t]; d.slot0 = n_slots;
+        d.n = (int)n; d.n_seg = rd->n_seg[t];
+        d.lw = std::max((d.n_seg + 15) / 16, 1); d.w = std::max((d.n_seg + 31) / 32, 1);
+        d.g_log2 = 0; while (d.g_log2 < 6 && (1 << d.g_log2) < d.w) ++d.g_log2;
+        if (rd->lab_off[t + 1] - d.lab_off != n * d.lw)
+            return fail(c, FCLU_ERR_ARG, "tint %d: lab_off does not match reps x words (%lld words for %lld reps of %d)", t,
+                        (i64)(rd->lab_off[t + 1] - d.lab_off), n, d.lw);
+        rbits_off[(size_t)t + 1] = d.rbits_off + n * d.w;
+        n_slots += ((n << d.g_log2) + 63) / 64 * 64;
+    }
+    const i64 N = rd->rep_off[T], n_lab = rd->lab_off[T], n_rbits = rbits_off[(size_t)T];
+    if (N >= 0x7f7f7f7fll) return fail(c, FCLU_ERR_ARG, "fclu_preprocess: %lld reps in one batch", N);
+    if (N > 0 && (!rd->labels || !rd->tail)) return fail(c, FCLU_ERR_ARG, "fclu_preprocess: labels or tail is null");
+    n_reps_out = N;
+    const char *hb_env = getenv("FCLU_HASH_BITS");           // (tests: a hash cut to n bits forces collisions; 0: one bucket a tint)
+    unsigned hash_mask = 0xffffffffu;
+    if (hb_env && hb_env[0] >= '0' && hb_env[0] <= '9' && atoi(hb_env) < 32) hash_mask = (1u << atoi(hb_env)) - 1u;
+
+    GrowBuf *D = c->pd;
+    HostBuf *H = c->ph;
+    hipStream_t s = c->stream;
+    const size_t N1 = (size_t)N + 1;
+    HIP_TRY(c, grow_host(H[Q_ROW_OFF], (size_t)(T + 1) * 8)); HIP_TRY(c, grow_host(H[Q_BITS_OFF], (size_t)(T + 1) * 8));
+    HIP_TRY(c, grow_host(H[Q_ADJ_OFF], (size_t)(T + 1) * 8)); HIP_TRY(c, grow_host(H[Q_RBITS_OFF], (size_t)(T + 1) * 8));
+    HIP_TRY(c, grow_host(H[Q_ERR], 16));
+    HIP_TRY(c, grow_host(H[Q_IBITS], (size_t)n_rbits * 4)); HIP_TRY(c, grow_host(H[Q_CBITS], (size_t)n_rbits * 4));
+    for (int q : {Q_FIRST, Q_LAST, Q_RFIRST, Q_RLAST, Q_REP_NODE, Q_MEM}) HIP_TRY(c, grow_host(H[q], (size_t)N * 4));
+    memcpy(H[Q_RBITS_OFF].p, rbits_off.data(), (size_t)(T + 1) * 8);
+    i64 *h_row_off = H[Q_ROW_OFF].as<i64>(), *h_bits_off = H[Q_BITS_OFF].as<i64>(), *h_adj_off = H[Q_ADJ_OFF].as<i64>();
+    int *h_err = H[Q_ERR].as<int>();
+    if (N > 0) {
+        HIP_TRY(c, grow(D[P_TINTS], pt.size() * sizeof(PrepTint)));
+        HIP_TRY(c, grow(D[P_LABELS], (size_t)n_lab * 4)); HIP_TRY(c, grow(D[P_TAIL], (size_t)N));
+        HIP_TRY(c, grow(D[P_IBITS], (size_t)n_rbits * 4)); HIP_TRY(c, grow(D[P_CBITS], (size_t)n_rbits * 4));
+        for (int q : {P_RFIRST, P_RLAST, P_FIRST, P_LAST, P_REP_TINT, P_VAL, P_SVAL, P_HEAD, P_BSTART, P_LEADER, P_REP_NODE, P_NODE_REP, P_NKEY, P_SNKEY, P_NVAL})
+            HIP_TRY(c, grow(D[q], (size_t)N * 4));
+        HIP_TRY(c, grow(D[P_FLAG], N1 * 4)); HIP_TRY(c, grow(D[P_NODE_ID], N1 * 4));
+        HIP_TRY(c, grow(D[P_KEY], (size_t)N * 8)); HIP_TRY(c, grow(D[P_SKEY], (size_t)N * 8));
+        HIP_TRY(c, grow(D[P_ROW_OFF], (size_t)(T + 1) * 8)); HIP_TRY(c, grow(D[P_ERR], 16));
+        HIP_TRY(c, grow(c->mem, (size_t)N * 4));
+        const unsigned key_bits = 32u + (unsigned)bits_for(T), node_bits = (unsigned)bits_for(N);
+        size_t sort_a = 0, sort_b = 0, scan_a = 0, scan_b = 0;
+        HIP_TRY(c, rocprim::radix_sort_pairs(nullptr, sort_a, D[P_KEY].as<u64>(), D[P_SKEY].as<u64>(), D[P_VAL].as<int>(), D[P_SVAL].as<int>(), (size_t)N, 0u, key_bits, s));
+        HIP_TRY(c, rocprim::radix_sort_pairs(nullptr, sort_b, D[P_NKEY].as<unsigned>(), D[P_SNKEY].as<unsigned>(), D[P_NVAL].as<int>(), c->mem.as<int>(), (size_t)N, 0u, node_bits, s));
+        HIP_TRY(c, rocprim::inclusive_scan(nullptr, scan_a, D[P_HEAD].as<int>(), D[P_BSTART].as<int>(), (size_t)N, rocprim::maximum<int>(), s));
+        HIP_TRY(c, rocprim::exclusive_scan(nullptr, scan_b, D[P_FLAG].as<int>(), D[P_NODE_ID].as<int>(), 0, N1, rocprim::plus<int>(), s));
+        const size_t tmp_bytes = std::max(std::max(sort_a, sort_b), std::max(scan_a, scan_b));
+        HIP_TRY(c, grow(D[P_TMP], tmp_bytes));
+        HIP_TRY(c, hipMemcpyAsync(D[P_TINTS].p, pt.data(), pt.size() * sizeof(PrepTint), hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipMemcpyAsync(D[P_LABELS].p, rd->labels, (size_t)n_lab * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipMemcpyAsync(D[P_TAIL].p, rd->tail, (size_t)N, hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipMemsetAsync(D[P_ERR].p, 0x7f, 16, s));
+        HIP_TRY(c, hipMemsetAsync(D[P_FLAG].as<int>() + N, 0, 4, s));
+        const int rep_grid = (int)std::min<i64>((N + 255) / 256, 4096);
+        const PrepTint *d_pt = D[P_TINTS].as<PrepTint>();
+        HIP_TRY(c, hipEventRecord(c->qev[0], s));
+        hipLaunchKernelGGL(k_rows, dim3((unsigned)std::min<i64>((n_slots + 255) / 256, 65536)), dim3(256), 0, s, T, n_slots, d_pt, D[P_LABELS].as<unsigned>(),
+                           D[P_TAIL].as<unsigned char>(), hash_mask, D[P_IBITS].as<unsigned>(), D[P_CBITS].as<unsigned>(), D[P_RFIRST].as<int>(),
+                           D[P_RLAST].as<int>(), D[P_FIRST].as<int>(), D[P_LAST].as<int>(), D[P_REP_TINT].as<int>(), D[P_KEY].as<u64>(), D[P_VAL].as<int>(),
+                           D[P_ERR].as<int>());
+        HIP_TRY(c, hipEventRecord(c->qev[1], s));
+        // refusals first: a tail above 2 or a label 3 has no meaning, and the sort's keys of such a batch are not needed
+        HIP_TRY(c, hipMemcpyAsync(h_err, D[P_ERR].p, 16, hipMemcpyDeviceToHost, s));
+        size_t tb = tmp_bytes;
+        HIP_TRY(c, rocprim::radix_sort_pairs(D[P_TMP].p, tb, D[P_KEY].as<u64>(), D[P_SKEY].as<u64>(), D[P_VAL].as<int>(), D[P_SVAL].as<int>(), (size_t)N, 0u, key_bits, s));
+        hipLaunchKernelGGL(k_heads, dim3(rep_grid), dim3(256), 0, s, N, D[P_SKEY].as<u64>(), D[P_HEAD].as<int>());
+        tb = tmp_bytes;
+        HIP_TRY(c, rocprim::inclusive_scan(D[P_TMP].p, tb, D[P_HEAD].as<int>(), D[P_BSTART].as<int>(), (size_t)N, rocprim::maximum<int>(), s));
+        hipLaunchKernelGGL(k_leader, dim3(rep_grid), dim3(256), 0, s, N, D[P_SKEY].as<u64>(), D[P_SVAL].as<int>(), D[P_BSTART].as<int>(), d_pt,
+                           D[P_IBITS].as<unsigned>(), D[P_FIRST].as<int>(), D[P_LAST].as<int>(), D[P_TAIL].as<unsigned char>(), D[P_LEADER].as<int>(),
+                           D[P_FLAG].as<int>());
+        tb = tmp_bytes;
+        HIP_TRY(c, rocprim::exclusive_scan(D[P_TMP].p, tb, D[P_FLAG].as<int>(), D[P_NODE_ID].as<int>(), 0, N1, rocprim::plus<int>(), s));
+        hipLaunchKernelGGL(k_row_off, dim3((unsigned)(T + 256) / 256), dim3(256), 0, s, T, N, d_pt, D[P_NODE_ID].as<int>(), D[P_ROW_OFF].as<i64>());
+        HIP_TRY(c, hipEventRecord(c->qev[2], s));
+        HIP_TRY(c, hipMemcpyAsync(h_row_off, D[P_ROW_OFF].p, (size_t)(T + 1) * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipStreamSynchronize(s));
+        HIP_TRY(c, hipGetLastError());
+        const int kinds[3] = {2, 0, 1};                      // the tail first: it is the caller's own byte, the labels come from a file
+        for (int k : kinds) {
+            if (h_err[k] == 0x7f7f7f7f) continue;
+            const i64 rep = h_err[k];
+            int t = 0;
+            while (t + 1 < T && rd->rep_off[t + 1] <= rep) ++t;
+            const i64 r = rep - rd->rep_off[t];
+            if (k == 2) return fail(c, FCLU_ERR_ARG, "tint %d rep %lld: tail category %d (0 'N', 1 'S', 2 'E')", t, r, (int)rd->tail[rep]);
+            if (k == 0) return fail(c, FCLU_ERR_ARG, "tint %d rep %lld: a label with code 3 (labels are 0, 1, 2)", t, r);
+            return fail(c, FCLU_ERR_ARG, "tint %d rep %lld: a nonzero bit beyond the tint's %d labels", t, r, (int)rd->n_seg[t]);
+        }
+    } else {
+        memset(h_row_off, 0, (size_t)(T + 1) * 8);
+    }
+    // ---- the unique rows as a batch
+    h_bits_off[0] = h_adj_off[0] = 0;
+    for (int t = 0; t < T; ++t) {
+        const i64 n = h_row_off[t + 1] - h_row_off[t];
+        if (n < 0 || n > rd->rep_off[t + 1] - rd->rep_off[t]) return fail(c, FCLU_ERR_HIP, "tint %d: %lld unique rows of %lld reps", t, n, (i64)(rd->rep_off[t + 1] - rd->rep_off[t]));
+        h_bits_off[t + 1] = h_bits_off[t] + n * pt[(size_t)t].w;
+        h_adj_off[t + 1] = h_adj_off[t] + n * ((n + 63) / 64);
+    }
+    const i64 R = h_row_off[T], n_bits = h_bits_off[T];
+    int rc = stage_tints(c, T, H[Q_ROW_OFF].as<int64_t>(), rd->n_seg, H[Q_BITS_OFF].as<int64_t>(), H[Q_ADJ_OFF].as<int64_t>(), prune, nullptr, st);
+    if (rc != FCLU_OK) return rc;
+    HIP_TRY(c, grow_host(H[Q_NODE_REP], (size_t)R * 4)); HIP_TRY(c, grow_host(H[Q_MEM_OFF], (size_t)(R + 1) * 8));
+    HIP_TRY(c, grow_host(H[Q_BITS], (size_t)n_bits * 4)); HIP_TRY(c, grow_host(H[Q_NFIRST], (size_t)R * 4));
+    HIP_TRY(c, grow_host(H[Q_NLAST], (size_t)R * 4)); HIP_TRY(c, grow_host(H[Q_NTAIL], (size_t)R));
+    *H[Q_MEM_OFF].as<i64>() = 0;
+    if (N > 0) {
+        HIP_TRY(c, grow(c->mem_off, (size_t)(R + 1) * 8));
+        const int rep_grid = (int)std::min<i64>((N + 256) / 256, 4096);
+        HIP_TRY(c, hipEventRecord(c->qev[3], s));
+        hipLaunchKernelGGL(k_nodes, dim3(rep_grid), dim3(256), 0, s, N, D[P_REP_TINT].as<int>(), D[P_TINTS].as<PrepTint>(), c->tints.as<TintDesc>(),
+                           D[P_LEADER].as<int>(), D[P_NODE_ID].as<int>(), D[P_IBITS].as<unsigned>(), D[P_FIRST].as<int>(), D[P_LAST].as<int>(),
+                           D[P_TAIL].as<unsigned char>(), D[P_REP_NODE].as<int>(), D[P_NKEY].as<unsigned>(), D[P_NVAL].as<int>(), D[P_NODE_REP].as<int>(),
+                           c->bits.as<unsigned>(), c->first.as<int>(), c->last.as<int>(), c->tail.as<unsigned char>());
+        size_t tb = D[P_TMP].cap;
+        HIP_TRY(c, rocprim::radix_sort_pairs(D[P_TMP].p, tb, D[P_NKEY].as<unsigned>(), D[P_SNKEY].as<unsigned>(), D[P_NVAL].as<int>(), c->mem.as<int>(), (size_t)N, 0u,
+                                             (unsigned)bits_for(N), s));
+        hipLaunchKernelGGL(k_mem_off, dim3(rep_grid), dim3(256), 0, s, N, R, D[P_SNKEY].as<unsigned>(), c->mem_off.as<i64>());
+        HIP_TRY(c, hipEventRecord(c->qev[4], s));
+        HIP_TRY(c, hipMemcpyAsync(H[Q_IBITS].p, D[P_IBITS].p, (size_t)n_rbits * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipMemcpyAsync(H[Q_CBITS].p, D[P_CBITS].p, (size_t)n_rbits * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipMemcpyAsync(H[Q_FIRST].p, D[P_FIRST].p, (size_t)N * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipMemcpyAsync(H[Q_LAST].p, D[P_LAST].p, (size_t)N * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipMemcpyAsync(H[Q_RFIRST].p, D[P_RFIRST].p, (size_t)N * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipMemcpyAsync(H[Q_RLAST].p, D[P_RLAST].p, (size_t)N * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipMemcpyAsync(H[Q_REP_NODE].p, D[P_REP_NODE].p, (size_t)N * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipMemcpyAsync(H[Q_NODE_REP].p, D[P_NODE_REP].p, (size_t)R * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipMemcpyAsync(H[Q_MEM_OFF].p, c->mem_off.p, (size_t)(R + 1) * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipMemcpyAsync(H[Q_MEM].p, c->mem.p, (size_t)N * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipMemcpyAsync(H[Q_BITS].p, c->bits.p, (size_t)n_bits * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipMemcpyAsync(H[Q_NFIRST].p, c->first.p, (size_t)R * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipMemcpyAsync(H[Q_NLAST].p, c->last.p, (size_t)R * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipMemcpyAsync(H[Q_NTAIL].p, c->tail.p, (size_t)R, hipMemcpyDeviceToHost, s));
+    }
+    fclu_prep &o = c->prep;
+    o.n_tint = T; o.n_reps = N; o.n_rows = R;
+    o.row_off = H[Q_ROW_OFF].as<int64_t>(); o.bits_off = H[Q_BITS_OFF].as<int64_t>(); o.adj_off = H[Q_ADJ_OFF].as<int64_t>();
+    o.rep_bits_off = H[Q_RBITS_OFF].as<int64_t>();
+    o.i_bits = H[Q_IBITS].as<uint32_t>(); o.c_bits = H[Q_CBITS].as<uint32_t>();
+    o.first = H[Q_FIRST].as<int32_t>(); o.last = H[Q_LAST].as<int32_t>(); o.raw_first = H[Q_RFIRST].as<int32_t>(); o.raw_last = H[Q_RLAST].as<int32_t>();
+    o.rep_node = H[Q_REP_NODE].as<int32_t>(); o.node_rep = H[Q_NODE_REP].as<int32_t>();
+    o.mem_off = H[Q_MEM_OFF].as<int64_t>(); o.mem = H[Q_MEM].as<int32_t>();
+    o.bits = H[Q_BITS].as<uint32_t>(); o.node_first = H[Q_NFIRST].as<int32_t>(); o.node_last = H[Q_NLAST].as<int32_t>(); o.node_tail = H[Q_NTAIL].as<uint8_t>();
+    return FCLU_OK;
+}
+
+// the kernels' times of the call that has just synchronised
+void preprocess_times(fclu_ctx *c, i64 n_reps) {
+    if (n_reps <= 0) return;
+    float a = 0.f, b = 0.f;
+    (void)hipEventElapsedTime(&c->rows_ms, c->qev[0], c->qev[1]);
+    (void)hipEventElapsedTime(&a, c->qev[1], c->qev[2]);
+    (void)hipEventElapsedTime(&b, c->qev[3], c->qev[4]);
+    c->dedupe_ms = a + b;
+}
+
 }  // namespace
 
 extern "C" {
+
+int fclu_preprocess(fclu_ctx *c, const fclu_reads *reads) {
+    if (!c) return FCLU_ERR_ARG;
+    Staged st;
+    i64 n_reps = 0;
+    const int rc = preprocess_device(c, reads, 1, st, n_reps);
+    if (rc != FCLU_OK) return rc;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipGetLastError());
+    preprocess_times(c, n_reps);
+    c->have_prep = true;
+    return FCLU_OK;
+}
+
+int fclu_partition_reads(fclu_ctx *c, const fclu_reads *reads, int32_t maximum_ilp_size) {
+    if (!c) return FCLU_ERR_ARG;
+    c->have_parts = false;
+    c->have_prep = false;
+    if (maximum_ilp_size < 1) return fail(c, FCLU_ERR_ARG, "maximum_ilp_size is %d: it must be at least 1", (int)maximum_ilp_size);
+    Staged st;
+    i64 n_reps = 0;
+    int rc = preprocess_device(c, reads, 1, st, n_reps);
+    if (rc != FCLU_OK) return rc;
+    if (!st.empty) rc = compat_run(c, st, 1, nullptr, nullptr);          // (it synchronises: the pinned copies have landed)
+    else HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (rc != FCLU_OK) return rc;
+    preprocess_times(c, n_reps);
+    c->have_prep = true;
+    return partition_device(c, reads->n_tint, st.R, nullptr, nullptr, n_reps, maximum_ilp_size);
+}
+
+int fclu_preprocess_results(fclu_ctx *c, fclu_prep *out) {
+    if (!c || !out) return FCLU_ERR_ARG;
+    if (!c->have_prep) return fail(c, FCLU_ERR_ARG, "fclu_preprocess_results: no result (the last fclu_preprocess / fclu_partition_reads call failed or none was made)");
+    *out = c->prep;
+    return FCLU_OK;
+}
+
+int fclu_preprocess_timing(fclu_ctx *c, float *rows_ms, float *dedupe_ms) {
+    if (!c) return FCLU_ERR_ARG;
+    if (rows_ms) *rows_ms = c->rows_ms;
+    if (dedupe_ms) *dedupe_ms = c->dedupe_ms;
+    return FCLU_OK;
+}
 
 int fclu_partition(fclu_ctx *c, const fclu_batch *b, const int64_t *mem_off, const int32_t *mem, int32_t maximum_ilp_size) {
     if (!c || !b) return FCLU_ERR_ARG;
@@ -1145,7 +1602,7 @@ int fclu_partition(fclu_ctx *c, const fclu_batch *b, const int64_t *mem_off, con
     if (b->n_tint <= 0) return fail(c, FCLU_ERR_ARG, "fclu_partition: empty batch");
     int rc = check_members(c, b->row_off[b->n_tint], mem_off, mem, maximum_ilp_size);
     if (rc == FCLU_OK) rc = compat_device(c, b, 1, nullptr, nullptr);
-    if (rc == FCLU_OK) rc = partition_device(c, b->n_tint, b->row_off[b->n_tint], mem_off, mem, maximum_ilp_size);
+    if (rc == FCLU_OK) rc = partition_device(c, b->n_tint, b->row_off[b->n_tint], mem_off, mem, 0, maximum_ilp_size);
     return rc;
 }
 
@@ -1203,7 +1660,7 @@ int fclu_partition_adj(fclu_ctx *c, int32_t n_tint, const int64_t *row_off, cons
         if (n_adj) HIP_TRY(c, hipMemcpyAsync(c->adj[0].p, adj, (size_t)n_adj * 8, hipMemcpyHostToDevice, s));
         HIP_TRY(c, hipStreamSynchronize(s));              // (the host vectors go out of scope)
     }
-    return partition_device(c, T, R, mem_off, mem, maximum_ilp_size);
+    return partition_device(c, T, R, mem_off, mem, 0, maximum_ilp_size);
 }
 
 int fclu_partition_results(fclu_ctx *c, fclu_parts *out) {

@@ -1,14 +1,19 @@
 /*
  * freddie_cluster.h -- C-ABI of the GPU part of the clustering stage's pre-ILP work.
  *
- * It replaces everything of the reference's partition_reads() (py/freddie_cluster.py:196-274) behind the dedupe:
+ * It replaces the reference's preprocess_ilp() and partition_reads() (py/freddie_cluster.py:277-328, :196-274):
+ *   - per rep, I / C / FL and find_segment_read()      py/freddie_cluster.py:285-310, :175-183   (fclu_preprocess)
+ *   - the dedupe of reps with the same structure       py/freddie_cluster.py:203-215             (fclu_preprocess)
  *   - the pairwise read compatibility test            py/freddie_cluster.py:217-234
  *   - the iterated edge pruning of the compatibility graph   py/freddie_cluster.py:240-255
  *   - connected components, the even split of large components and the incompatible rep pairs of every partition
  *                                                      py/freddie_cluster.py:256-274   (fclu_partition)
- * for a batch of transcriptional intervals ("tints") at once.  The dedupe of reads with the same structure (:207-215)
- * is host code (freddie_amd/cluster_prep.py), as are read_segment() (:119-172) and preprocess_ilp() (:277-328).  The ILP
- * itself (run_ilp, Gurobi) is out of scope.
+ * for a batch of transcriptional intervals ("tints") at once.  fclu_partition_reads() runs all of it in one call, from label
+ * rows at two bits a label to tint['partitions'] as flat arrays: the unique rows and their members go from the dedupe to
+ * the graph on the device.  The entry points behind the dedupe (fclu_compat_graph, fclu_partition) still take unique rows
+ * a caller made on the host (freddie_amd/cluster_prep.py: unique_structures(), pack_structures()).  read_segment()
+ * (:119-172), the poly-tail category of a rep (from the parsed poly_tail dict, :291-300), garbage_cost and the gaps dicts
+ * are host code.  The ILP itself (run_ilp, Gurobi) is out of scope.
  *
  * Data layout (caller-owned host arrays, copied by the call):
  *   tint t owns the unique reads row_off[t] .. row_off[t+1]  (N_t of them; "unique" = py/freddie_cluster.py:207-215)
@@ -98,6 +103,58 @@ int fclu_partition_results(fclu_ctx *c, fclu_parts *out);
 /* Kernel time of the last partition call behind the graph, from HIP events (ms): the components; the pair count + emit
  * (with the members' copy).  The graph's own time is fclu_last_timing()'s. */
 int fclu_partition_timing(fclu_ctx *c, float *components_ms, float *pairs_ms);
+
+/* ---- the front: preprocess_ilp() per rep and the dedupe, from label rows (:277-328, :203-215) ----
+ * Caller-owned host arrays, copied by the call. */
+typedef struct fclu_reads {
+    int32_t n_tint;
+    const int64_t *rep_off;    /* n_tint + 1: tint t owns the reps rep_off[t] .. rep_off[t+1], in read_reps order */
+    const int32_t *n_seg;      /* n_tint: M_t */
+    const int64_t *lab_off;    /* n_tint + 1, in uint32 words; a rep's row is LW_t = max(ceil(M_t / 16), 1) words */
+    const uint32_t *labels;    /* label s of a row at bits 2 * (s & 15) of word s >> 4; code = ASCII & 3 (0, 1, 2); the bits
+                                  beyond M_t are zero */
+    const uint8_t *tail;       /* per rep: 0 'N', 1 'S', 2 'E' -- the category of :293-304, decided by the host from the
+                                  parsed poly_tail dict (exactly one entry, key SA/ST resp. EA/ET, length > 10) */
+} fclu_reads;
+
+/* Per rep: I (label & 1; 2 counts as 0) and C (label 0 inside [max(first, 0), last]) as bit rows of W_t = max(ceil(M_t / 32), 1)
+ * uint32 words, raw_first / raw_last (find_segment_read: (-1, M_t - 1) for a row without a 1), first / last (FL: the raw values,
+ * first = 0 for tail 'S', last = M_t - 1 for tail 'E').  Reps of a tint with equal (I row, first, last, tail) are one unique row
+ * ("node"); nodes are numbered by their smallest rep, a node's members are its reps, ascending.  The hash that buckets the rows
+ * never decides: equality is tested on the whole row.
+ * FCLU_ERR_ARG (fclu_last_error names tint and rep): a label 3, a nonzero bit beyond M_t, a tail above 2, lab_off that is not
+ * reps x LW_t, negative counts, an empty batch.  FCLU_ERR_UNSUPPORTED: more than 9600 segments.  The context stays usable.
+ * FCLU_HASH_BITS=<n> (read at the call; tests): the hash cut to n bits, 0 = one bucket a tint. */
+int fclu_preprocess(fclu_ctx *c, const fclu_reads *reads);
+
+typedef struct fclu_prep {
+    int32_t n_tint;
+    int64_t n_reps, n_rows;                    /* reps and unique rows of the batch */
+    const int64_t *row_off, *bits_off, *adj_off;   /* n_tint + 1 each: the unique rows as a fclu_batch */
+    const int64_t *rep_bits_off;               /* n_tint + 1, uint32 words: rep i of tint t has its I / C row at rep_bits_off[t] + i * W_t */
+    const uint32_t *i_bits, *c_bits;           /* rep_bits_off[n_tint] */
+    const int32_t *first, *last;               /* n_reps: FL */
+    const int32_t *raw_first, *raw_last;       /* n_reps: find_segment_read() */
+    const int32_t *rep_node;                   /* n_reps: the rep's node, local to the tint */
+    const int32_t *node_rep;                   /* n_rows: the node's smallest rep, local to the tint */
+    const int64_t *mem_off;                    /* n_rows + 1 */
+    const int32_t *mem;                        /* n_reps: the nodes' members (rep ids local to the tint), fclu_partition's mem */
+    const uint32_t *bits;                      /* bits_off[n_tint]: the nodes' rows, fclu_batch's bits */
+    const int32_t *node_first, *node_last;     /* n_rows: fclu_batch's first / last */
+    const uint8_t *node_tail;                  /* n_rows: fclu_batch's tail */
+} fclu_prep;
+
+/* Result of the last successful fclu_preprocess() / fclu_partition_reads(): pointers into pinned host buffers the context
+ * owns, valid until the context's next call. */
+int fclu_preprocess_results(fclu_ctx *c, fclu_prep *out);
+
+/* preprocess, dedupe, compatibility graph, pruning and partition in one call; fclu_partition_results() and
+ * fclu_preprocess_results() hold the results.  Refusals: fclu_preprocess()'s and fclu_partition()'s. */
+int fclu_partition_reads(fclu_ctx *c, const fclu_reads *reads, int32_t maximum_ilp_size);
+
+/* Kernel time of the last fclu_preprocess() / fclu_partition_reads() from HIP events (ms): the per-rep rows; the dedupe
+ * (sorts, scans, leaders, nodes and members). */
+int fclu_preprocess_timing(fclu_ctx *c, float *rows_ms, float *dedupe_ms);
 
 #ifdef __cplusplus
 }

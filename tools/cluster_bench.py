@@ -6,6 +6,9 @@ synthetic preprocessed tints through include/freddie_cluster.h.
     python tools/cluster_bench.py [--workload many|big] [--steps K]                          (GPU side only)
     python tools/cluster_bench.py --partitions [--workload many|big] [--steps K] [--host-sample N]
                        (the whole of partition_reads() behind the dedupe on the device against the host tail it replaces)
+    python tools/cluster_bench.py --front [--workload many|big] [--steps K]
+                       (label rows in: the host front preprocess_ilp + unique_structures + pack_structures + pack_members, then
+                        Context.partition, against the one call Context.partition_labels; the new kernels' event times)
 
 One JSON line: read pairs tested per second of the CALL (packed host arrays in -> pruned adjacency in host memory: copies,
 kernels and the pruning loop's host round trips all inside), the kernel times as detail, and the bound of the compatibility
@@ -141,14 +144,86 @@ def run_partitions(workload="many", steps=5, maximum_ilp_size=1000, host_sample=
     }
 
 
+def run_front(workload="many", steps=5, maximum_ilp_size=1000, dup=0.1):
+    """The workload rebuilt as label rows (tests/front_util.labels_from_preprocessed: label = I, a fifth of the zeros written as 2,
+    a share `dup` of the reps copies of earlier reps), then three things timed on the same tints:
+      host front   preprocess_ilp + unique_structures + pack_structures + pack_members, as they stand (pure Python), on deep copies;
+      present path host front + Context.partition;
+      one call     pack_labels + Context.partition_labels (and the call alone, and its kernels' event times).
+    Every timed region ends in a finished device call or is host work; medians over `steps` after one warm-up."""
+    import copy
+    import front_util as fu
+    w = WORKLOADS[workload]
+    base = [cu.random_tint(1000 + t, w["n_reps"], w["n_segs"], n_isoforms=8) for t in range(w["n_tints"])]
+    tints = [fu.labels_from_preprocessed(b, seed=b["id"], twos=0.2, dup=dup) for b in base]
+    del base
+    ctx = cluster_prep.Context(0)
+    settings = dict(recycle_model="constant")
+
+    def host_front():
+        work = copy.deepcopy(tints)
+        t0 = time.perf_counter()
+        for t in work:
+            cluster_prep.preprocess_ilp(t, settings)
+        t1 = time.perf_counter()
+        uniq = [cluster_prep.unique_structures(t) for t in work]
+        t2 = time.perf_counter()
+        packed, members = cluster_prep.pack_structures(uniq), cluster_prep.pack_members(uniq)
+        t3 = time.perf_counter()
+        return (packed, members), dict(preprocess_ilp=t1 - t0, unique_structures=t2 - t1, pack=t3 - t2, total=t3 - t0)
+
+    (packed, members), _ = host_front()
+    labels = cluster_prep.pack_labels(tints)
+    want = ctx.partition(packed, members, maximum_ilp_size)                    # warm-up of both paths, and the results compared
+    prep, got = ctx.partition_labels(labels, maximum_ilp_size)
+    same = all(np.array_equal(want[k], got[k]) for k in want) and np.array_equal(prep["bits"], packed["bits"]) and \
+        np.array_equal(prep["mem"], members["mem"]) and np.array_equal(prep["mem_off"], members["mem_off"])
+    front, part, pack_l, call, rows, dedupe = [], [], [], [], [], []
+    for _ in range(steps):                                                     # the two paths alternate
+        (packed, members), hf = host_front()
+        front.append(hf)
+        t0 = time.perf_counter()
+        ctx.partition(packed, members, maximum_ilp_size)
+        part.append(time.perf_counter() - t0)
+        t0 = time.perf_counter()
+        labels = cluster_prep.pack_labels(tints)
+        t1 = time.perf_counter()
+        ctx.partition_labels(labels, maximum_ilp_size)
+        t2 = time.perf_counter()
+        pack_l.append(t1 - t0); call.append(t2 - t1)
+        tm = ctx.preprocess_timing()
+        rows.append(tm["rows_ms"]); dedupe.append(tm["dedupe_ms"])
+    ctx.close()
+    med = lambda xs: float(np.median(xs)) * 1e3
+    n_reps, n_rows = int(prep["n_reps"]), int(prep["n_rows"])
+    host_ms = {k: med([f[k] for f in front]) for k in front[0]}
+    present, one_call = host_ms["total"] + med(part), med(pack_l) + med(call)
+    return {
+        "metric": "the front of partition_reads(): host front + Context.partition against one Context.partition_labels call", "unit": "ms",
+        "data": "synthetic", "config": {"workload": "cluster-" + workload, **w, "maximum_ilp_size": maximum_ilp_size, "steps": steps,
+                                         "reps": n_reps, "unique_rows": n_rows, "share_of_reps_collapsed": 1.0 - n_rows / max(n_reps, 1),
+                                         "duplicates_drawn": dup, "label_2_share_of_zeros": 0.2},
+        "identical_results": bool(same),
+        "host_front_ms": host_ms, "partition_call_ms": med(part), "present_path_ms": present,
+        "pack_labels_ms": med(pack_l), "partition_labels_call_ms": med(call), "one_call_path_ms": one_call,
+        "kernel_ms": {"rows (k_rows)": float(np.median(rows)), "dedupe (sorts, scans, k_leader, k_nodes, k_mem_off)": float(np.median(dedupe))},
+        "one_call_not_slower": bool(one_call <= present), "call_alone_not_slower": bool(med(call) <= host_ms["total"] + med(part)),
+        "spread_ms": {"present_path": [min(f["total"] + p for f, p in zip(front, part)) * 1e3, max(f["total"] + p for f, p in zip(front, part)) * 1e3],
+                      "one_call_path": [min(a + b for a, b in zip(pack_l, call)) * 1e3, max(a + b for a, b in zip(pack_l, call)) * 1e3]},
+    }
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workload", default="many", choices=sorted(WORKLOADS))
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--partitions", action="store_true", help="measure Context.partition() against the host tail (FCLU_HOST_PARTITIONS=1)")
     ap.add_argument("--host-sample", type=int, default=20, help="--partitions: tints the two partition_reads_batch() runs take")
+    ap.add_argument("--front", action="store_true", help="measure the host front + Context.partition against Context.partition_labels")
     args = ap.parse_args()
-    if args.partitions:
+    if args.front:
+        print(json.dumps(run_front(args.workload, args.steps)))
+    elif args.partitions:
         print(json.dumps(run_partitions(args.workload, args.steps, host_sample=args.host_sample)))
     else:
         print(json.dumps(run(args.workload, args.steps)))
