@@ -12,6 +12,11 @@
 // share a neighbour (:247-251): the columns that share a neighbour with row r are the OR of the rows of r's
 // neighbours, one wave per row; every pass reads the previous pass' matrix only (the reference removes the edges
 // of a pass together, :252) and passes repeat until one removes nothing (:254).
+// The file, in order:  1. the kernels, stage by stage
+//   2. Buf<T> (typed, owning, growing memory) and fclu_ctx, whose buffers free themselves
+//   3. helpers: fail / HIP_TRY, the test knobs (read_knobs, once a call), run_burst, fetch
+//   4. the stages: stage_tints, compat_run; part_* behind partition_device; prep_* behind preprocess_device
+//   5. the C ABI, one extern "C" block
 #include "freddie_cluster.h"
 
 #include <hip/hip_runtime.h>
@@ -783,46 +788,90 @@ __global__ void __launch_bounds__(256) k_mem_off(i64 n_reps, i64 n_rows, const u
 
 }  // namespace
 
-struct GrowBuf {              // device buffer that lives with the context and only ever grows
-    void *p = nullptr;
-    size_t cap = 0;
-    template <typename T> T *as() const { return reinterpret_cast<T *>(p); }
+// ---- buffers and the context -------------------------------------------------------------------------------------------
+// Memory that lives with the context and only ever grows: T *p is used as it is, bytes(n) serves the copies, the destructor frees.
+// kPinned: pinned host memory (HostBuf<T>) instead of device memory.
+template <typename T, bool kPinned = false>
+struct Buf {
+    T *p = nullptr;
+    size_t cap = 0;                                          // bytes
+    Buf() = default;
+    Buf(const Buf &) = delete;
+    ~Buf() { (void)release(); }
+    static size_t bytes(size_t n) { return n * sizeof(T); }
+    hipError_t release() {
+        const hipError_t e = !p ? hipSuccess : kPinned ? hipHostFree(p) : hipFree(p);
+        p = nullptr; cap = 0;
+        return e;
+    }
+    hipError_t alloc(size_t n_bytes) {                       // exactly n_bytes; p is null before it
+        void *q = nullptr;
+        const hipError_t e = kPinned ? hipHostMalloc(&q, n_bytes, hipHostMallocDefault) : hipMalloc(&q, n_bytes);
+        if (e == hipSuccess) { p = static_cast<T *>(q); cap = n_bytes; }
+        return e;
+    }
+    hipError_t grow(size_t n) {                              // never shrinks; room for n elements and a quarter of slack, at least 16 bytes
+        if (p && bytes(n) <= cap) return hipSuccess;
+        const hipError_t e = release();
+        return e != hipSuccess ? e : alloc((n ? bytes(n) : 16) + bytes(n) / 4);
+    }
 };
-struct HostBuf {              // the same in pinned host memory
-    void *p = nullptr;
-    size_t cap = 0;
-    template <typename T> T *as() const { return reinterpret_cast<T *>(p); }
-};
+template <typename T> using HostBuf = Buf<T, true>;
+
+constexpr int kBurst = 4;     // gated passes (pruning, components) enqueued per host round trip
+
 struct fclu_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
     hipEvent_t ev[3] = {};
     std::string err;
     float compat_ms = 0.f, prune_ms = 0.f;
-    GrowBuf tints, tiles, row_tint, bits, first, last, tail, adj[2], deg, changed, word_tint, tint_word0, deg1, pass_any, small_tints, small_rounds;
-    int *h_flags = nullptr;   // pinned: per-pass flags of a burst + per-tint flags
-    size_t h_flags_cap = 0;
+    Buf<TintDesc> tints; Buf<int4> tiles; Buf<int2> word_tint; Buf<i64> tint_word0;
+    Buf<unsigned> bits; Buf<unsigned char> tail; Buf<u64> adj[2], deg1;
+    Buf<int> row_tint, first, last, deg, small_tints, small_rounds;
+    Buf<int> pass_any;        // a burst's flags: kBurst "this pass changed something" words, then (pruning) kBurst x n_tint per-tint words
+    HostBuf<int> h_flags;     // their pinned copy
     // fclu_partition(): the batch the last graph call left on the device, work arrays, results (pinned, context-owned)
     std::vector<TintDesc> h_tints;
     int adj_cur = 0;
     hipEvent_t pev[6] = {};
     float components_ms = 0.f, pairs_ms = 0.f;
-    GrowBuf parent, skey, rows, sval, comp_start, comp_end, chunk_end, head, part_id, smult, rid_pos, cnt, pair_base, d_label, d_nodes,
-            d_tint_part_off, d_part_node_off, d_part_rid_off, d_part_pair_off, mem_off, mem, d_part_rids, d_pairs, tmp;
-    HostBuf h_cc_flags, h_tint_part_off, h_part_node_off, h_part_nodes, h_part_rid_off, h_part_rids, h_part_pair_off, h_pairs, h_label;
+    Buf<int> parent, rows, sval, comp_start, comp_end, chunk_end, d_label, d_nodes, mem, d_part_rids;
+    Buf<i64> head, part_id, smult, rid_pos, cnt, pair_base, d_tint_part_off, d_part_node_off, d_part_rid_off, d_part_pair_off, mem_off;
+    Buf<unsigned> skey; Buf<int2> d_pairs; Buf<char> tmp;
+    HostBuf<i64> h_tot;       // {partitions, pairs}
+    HostBuf<int64_t> h_tint_part_off, h_part_node_off, h_part_rid_off, h_part_pair_off;
+    HostBuf<int32_t> h_part_nodes, h_part_rids, h_label; HostBuf<int2> h_pairs;
     fclu_parts parts = {};
     bool have_parts = false;
-    // fclu_preprocess() / fclu_partition_reads(): device arrays (P_*) and the pinned copies fclu_preprocess_results() hands out (Q_*)
-    GrowBuf pd[32];
-    HostBuf ph[24];
+    // fclu_preprocess() / fclu_partition_reads(): device arrays (pd) and the pinned copies fclu_preprocess_results() hands out (ph)
+    struct {
+        Buf<PrepTint> tints; Buf<unsigned char> tail; Buf<u64> key, skey; Buf<i64> row_off; Buf<char> tmp;
+        Buf<unsigned> labels, ibits, cbits, nkey, snkey;
+        Buf<int> rfirst, rlast, first, last, rep_tint, val, sval, head, bstart, leader, flag, node_id, rep_node, node_rep, nval, err;
+    } pd;
+    struct {
+        HostBuf<int64_t> row_off, bits_off, adj_off, rbits_off, mem_off;
+        HostBuf<uint32_t> ibits, cbits, bits; HostBuf<uint8_t> ntail; HostBuf<int> err;
+        HostBuf<int32_t> first, last, rfirst, rlast, rep_node, node_rep, mem, nfirst, nlast;
+    } ph;
     hipEvent_t qev[6] = {};
     float rows_ms = 0.f, dedupe_ms = 0.f;
     fclu_prep prep = {};
     bool have_prep = false;
+    // (the buffers free themselves behind it, on this device)
+    ~fclu_ctx() {
+        (void)hipSetDevice(device);
+        if (stream) { (void)hipStreamSynchronize(stream); (void)hipStreamDestroy(stream); }
+        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : pev) if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : qev) if (e) (void)hipEventDestroy(e);
+    }
 };
 
 namespace {
 
+// ---- helpers: errors, test knobs, the burst loop -------------------------------------------------------------------------
 std::string g_create_error;
 
 int fail(fclu_ctx *c, int code, const char *fmt, ...) {
@@ -835,34 +884,662 @@ int fail(fclu_ctx *c, int code, const char *fmt, ...) {
     return code;
 }
 
-hipError_t grow(GrowBuf &b, size_t bytes) {
-    if (b.p && bytes <= b.cap) return hipSuccess;
-    if (b.p) { hipError_t e = hipFree(b.p); b.p = nullptr; b.cap = 0; if (e != hipSuccess) return e; }
-    const size_t want = (bytes ? bytes : 16) + bytes / 4;
-    hipError_t e = hipMalloc(&b.p, want);
-    if (e == hipSuccess) b.cap = want;
-    return e;
+#define HIP_TRY(c, expr) \
+    do { hipError_t e__ = (expr); if (e__ != hipSuccess) return fail((c), FCLU_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e__)); } while (0)
+#define RC_TRY(expr) \
+    do { const int rc__ = (expr); if (rc__ != FCLU_OK) return rc__; } while (0)
+
+// Test knobs: environment variables read at the start of every entry point that runs kernels (the tests flip them between calls on
+// one context) and handed down to the stages.
+//   FCLU_PART_LDS=0         part_lds         no tint's components in one workgroup's LDS (k_cc_lds): all take the per-pass kernels
+//   FCLU_PRUNE_LDS=0        prune_lds        the same for the pruning (k_prune_lds)
+//   FCLU_PRUNE_LDS_WORDS=n  prune_lds_words  0 < n < kPruneLdsWords: a lower limit of k_prune_lds, so that small tints take both ways in one batch
+//   FCLU_RANK=0             rank             k_compat keeps the masked sums whatever the rows' length
+//   FCLU_PRUNE_EDGES=0      prune_edges      the pass as OR of rows (k_deg1, k_prune) whatever the shapes
+//   FCLU_HASH_BITS=n        hash_mask        n < 32: the dedupe's hash cut to n bits forces collisions; 0: one bucket a tint
+struct Knobs { bool part_lds, prune_lds, rank, prune_edges; i64 prune_lds_words; unsigned hash_mask; };
+
+Knobs read_knobs() {
+    const auto off = [](const char *name) { const char *e = getenv(name); return e && e[0] == '0'; };
+    Knobs k;
+    k.part_lds = !off("FCLU_PART_LDS"); k.prune_lds = !off("FCLU_PRUNE_LDS"); k.rank = !off("FCLU_RANK"); k.prune_edges = !off("FCLU_PRUNE_EDGES");
+    const char *w = getenv("FCLU_PRUNE_LDS_WORDS");
+    k.prune_lds_words = (w && atoll(w) > 0 && atoll(w) < kPruneLdsWords) ? atoll(w) : kPruneLdsWords;
+    const char *hb = getenv("FCLU_HASH_BITS");
+    k.hash_mask = (hb && hb[0] >= '0' && hb[0] <= '9' && atoi(hb) < 32) ? (1u << atoi(hb)) - 1u : 0xffffffffu;
+    return k;
 }
-constexpr int kBurst = 4;     // pruning passes enqueued per host round trip
 
-// connected components of a tint in one workgroup's LDS: the pruning's criterion; FCLU_PART_LDS=0: never (tests)
-int cc_in_lds(int n, int aw) {
-    const char *e = getenv("FCLU_PART_LDS");
-    return (!(e && e[0] == '0') && n > 0 && (i64)n * aw <= kPruneLdsWords) ? 1 : 0;
+// One burst: kBurst passes enqueued per host round trip, pass q gated on pass q - 1's "changed something" word, so the host reads the
+// flags once per burst and not once per pass.  enqueue(q, any, gate) launches pass q, which sets *any.  The first n_flags words of d_flags
+// (the kBurst pass words in front) are cleared before the passes and copied to h_flags behind them.  ran: the passes that ran, 0 .. the
+// first that changed nothing (inclusive); done: one of them changed nothing.
+template <typename F>
+int run_burst(fclu_ctx *c, Buf<int> &d_flags, HostBuf<int> &h_flags, size_t n_flags, F &&enqueue, int &ran, bool &done) {
+    hipStream_t s = c->stream;
+    HIP_TRY(c, hipMemsetAsync(d_flags.p, 0, d_flags.bytes(n_flags), s));
+    for (int q = 0; q < kBurst; ++q) enqueue(q, d_flags.p + q, q ? d_flags.p + (q - 1) : nullptr);
+    HIP_TRY(c, hipMemcpyAsync(h_flags.p, d_flags.p, d_flags.bytes(n_flags), hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    for (ran = 0, done = false; ran < kBurst && !done; ++ran) done = !h_flags.p[ran];
+    return FCLU_OK;
 }
 
-#define HIP_TRY(c, expr)                                                                                     \
-    do {                                                                                                     \
-        hipError_t e__ = (expr);                                                                             \
-        if (e__ != hipSuccess) return fail((c), FCLU_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e__));      \
-    } while (0)
+// A result array: its pinned buffer grown to n elements, filled from the device (copy; the caller synchronises) and handed out as field.
+template <typename H, typename D>
+int fetch(fclu_ctx *c, HostBuf<H> &h, const D *src, size_t n, bool copy, const H *&field) {
+    static_assert(sizeof(H) == sizeof(D), "one element size on the device and in pinned memory");
+    HIP_TRY(c, h.grow(n));
+    if (copy && n) HIP_TRY(c, hipMemcpyAsync(h.p, src, h.bytes(n), hipMemcpyDeviceToHost, c->stream));
+    field = h.p;
+    return FCLU_OK;
+}
 
-int compat_device(fclu_ctx *c, const fclu_batch *b, int32_t prune, uint64_t *adj_out, int32_t *rounds_out);
-int check_members(fclu_ctx *c, i64 R, const int64_t *mem_off, const int32_t *mem, int32_t maximum_ilp_size);
-int partition_device(fclu_ctx *c, int T, i64 R, const int64_t *mem_off, const int32_t *mem, i64 n_mem_device, int32_t maximum_ilp_size);
+int bits_for(i64 n) { int b = 1; while (b < 32 && (1ll << b) < n) ++b; return b; }
+
+// the *_timing entry points: two times of the last call, each wanted or not
+int two_times(float *a, float va, float *b, float vb) { if (a) *a = va; if (b) *b = vb; return FCLU_OK; }
+
+// ---- staging of a batch ------------------------------------------------------------------------------------------------------
+// What the host derives from a batch's shape (stage_tints) and the graph kernels are launched with (compat_run).
+struct Staged {
+    int T = 0, n_tiles = 0, max_w = 1, max_aw_large = 0;
+    i64 R = 0, n_bits = 0, n_adj = 0;
+    bool any_large = false, empty = false;
+    std::vector<int> small_tints;                        // pruned whole in LDS (k_prune_lds)
+    size_t small_lds = 0;
+    // what the uploads read: alive until the call that staged them has synchronised
+    std::vector<TintDesc> tints;
+    std::vector<int4> tiles;
+    std::vector<int> row_tint;
+    std::vector<int2> word_tint;                         // every adjacency word column of every tint: (tint, word)
+    std::vector<i64> tint_word0;
+};
+
+// Tint t's descriptor from the batch's offsets, with the shape refusals: the kernels index with these and nothing else.  n_seg and
+// bits_off null (fclu_partition_adj: a graph without rows): no segments, one word a row at offset 0.
+int describe_tint(fclu_ctx *c, int t, const Knobs &k, int32_t prune, const int64_t *row_off, const int32_t *n_seg, const int64_t *bits_off,
+                  const int64_t *adj_off, TintDesc &d) {
+    d = TintDesc();
+    d.row0 = row_off[t];
+    const i64 n = row_off[t + 1] - d.row0;
+    if (!n_seg && (n < 0 || n > (1 << 30))) return fail(c, FCLU_ERR_ARG, "tint %d: bad row count", t);
+    if (n_seg && (n < 0 || n > (1 << 30) || n_seg[t] < 0)) return fail(c, FCLU_ERR_ARG, "tint %d: bad row count or segment count", t);
+    d.n = (int)n; d.n_seg = n_seg ? n_seg[t] : 0;
+    d.w = std::max((d.n_seg + 31) / 32, 1);
+    d.aw = (d.n + 63) / 64;
+    d.adj_off = adj_off[t];
+    d.in_lds = (prune && k.prune_lds && d.n > 0 && d.n <= 65535 && (i64)d.n * d.aw <= k.prune_lds_words) ? 1 : 0;
+    d.cc_lds = (k.part_lds && d.n > 0 && (i64)d.n * d.aw <= kPruneLdsWords) ? 1 : 0;      // (the pruning's criterion)
+    if (bits_off) {
+        d.bits_off = bits_off[t];
+        if (bits_off[t + 1] - d.bits_off != (i64)d.n * d.w) return fail(c, FCLU_ERR_ARG, "tint %d: bits_off does not match rows x words", t);
+    }
+    if (adj_off[t + 1] - d.adj_off != (i64)d.n * d.aw) return fail(c, FCLU_ERR_ARG, "tint %d: adj_off does not match rows x words", t);
+    if (d.w > kMaxWords) return fail(c, FCLU_ERR_UNSUPPORTED, "tint %d has %d segments; this build stages at most %d", t, d.n_seg, kMaxWords * 32);
+    return FCLU_OK;
+}
+
+// The caller's rows of tint t: first / last / tail in range and the bits inside [first, last] (first / last ARE a read's first and last
+// covered segment, :175-183): k_compat counts on it.
+int check_rows(fclu_ctx *c, int t, const TintDesc &d, const fclu_batch *b) {
+    for (i64 r = 0; r < d.n; ++r) {
+        const int f = b->first[d.row0 + r], l = b->last[d.row0 + r];
+        if (f < -1 || l >= (d.n_seg > 0 ? d.n_seg : 1) || b->tail[d.row0 + r] > 2) return fail(c, FCLU_ERR_ARG, "tint %d read %lld: first/last/tail out of range", t, r);
+        const uint32_t *rw = b->bits + d.bits_off + r * d.w;
+        for (int w = 0; w < d.w; ++w) {
+            uint32_t allowed = 0;
+            if (f >= 0 && l >= f && w >= (f >> 5) && w <= (l >> 5)) {
+                allowed = 0xffffffffu;
+                if (w == (f >> 5)) allowed &= 0xffffffffu << (f & 31);
+                if (w == (l >> 5)) allowed &= 0xffffffffu >> (31 - (l & 31));
+            }
+            if (rw[w] & ~allowed) return fail(c, FCLU_ERR_ARG, "tint %d read %lld: a covered segment outside [first, last]", t, r);
+        }
+    }
+    return FCLU_OK;
+}
+
+// The caller's matrix of tint t (fclu_partition_adj): symmetric, an empty diagonal, no bit at a column >= N (the kernels index nodes with its bits).
+int check_adj(fclu_ctx *c, int t, const TintDesc &d, const uint64_t *adj) {
+    const uint64_t *A = adj + d.adj_off;
+    for (i64 r = 0; r < d.n; ++r)
+        for (int z = 0; z < d.aw; ++z) {
+            uint64_t word = A[r * d.aw + z];
+            if (z == d.aw - 1 && (d.n & 63) && (word >> (d.n & 63)))
+                return fail(c, FCLU_ERR_ARG, "tint %d row %lld: adjacency bit at a column beyond N = %d", t, r, d.n);
+            while (word) {
+                const i64 col = (i64)z * 64 + __builtin_ctzll(word);
+                word &= word - 1;
+                if (col == r) return fail(c, FCLU_ERR_ARG, "tint %d row %lld: adjacency bit on the diagonal", t, r);
+                if (!((A[col * d.aw + (r >> 6)] >> (r & 63)) & 1ull))
+                    return fail(c, FCLU_ERR_ARG, "tint %d: adjacency not symmetric: (%lld, %lld) set, (%lld, %lld) not", t, r, col, col, r);
+            }
+        }
+    return FCLU_OK;
+}
+
+// the device buffers of a staged batch and of its graph
+int grow_staged(fclu_ctx *c, const Staged &st) {
+    const size_t R = (size_t)st.R, T = (size_t)st.T, n_words = st.word_tint.size();
+    HIP_TRY(c, c->tints.grow(T)); HIP_TRY(c, c->tiles.grow(st.tiles.size())); HIP_TRY(c, c->bits.grow((size_t)st.n_bits)); HIP_TRY(c, c->tail.grow(R));
+    for (Buf<int> *b : {&c->row_tint, &c->first, &c->last, &c->deg}) HIP_TRY(c, b->grow(R));
+    HIP_TRY(c, c->adj[0].grow((size_t)st.n_adj)); HIP_TRY(c, c->adj[1].grow((size_t)st.n_adj));
+    HIP_TRY(c, c->word_tint.grow(n_words)); HIP_TRY(c, c->tint_word0.grow(T + 1)); HIP_TRY(c, c->deg1.grow(n_words));
+    HIP_TRY(c, c->pass_any.grow(kBurst * (T + 1))); HIP_TRY(c, c->h_flags.grow(kBurst * (T + 1)));
+    HIP_TRY(c, c->small_tints.grow(st.small_tints.size() + 1)); HIP_TRY(c, c->small_rounds.grow(T));
+    return FCLU_OK;
+}
+
+// the descriptors, tiles and maps of a staged batch to the device (st outlives the copies)
+int upload_staged(fclu_ctx *c, const Staged &st) {
+    hipStream_t s = c->stream;
+    HIP_TRY(c, hipMemcpyAsync(c->tints.p, st.tints.data(), c->tints.bytes(st.tints.size()), hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(c->tiles.p, st.tiles.data(), c->tiles.bytes(st.tiles.size()), hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(c->row_tint.p, st.row_tint.data(), c->row_tint.bytes(st.row_tint.size()), hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(c->word_tint.p, st.word_tint.data(), c->word_tint.bytes(st.word_tint.size()), hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(c->tint_word0.p, st.tint_word0.data(), c->tint_word0.bytes(st.tint_word0.size()), hipMemcpyHostToDevice, s));
+    return FCLU_OK;
+}
+
+// Host staging of a batch: the tints' descriptors, tiles and row / word maps, the device buffers grown and the maps uploaded.  b: the
+// caller's rows, checked against their tint (fclu_compat_graph, fclu_partition), or null when the rows were made on the device
+// (fclu_partition_reads: first / last / tail in range and bits inside [first, last] by construction).
+int stage_tints(fclu_ctx *c, const Knobs &k, int T, const int64_t *row_off, const int32_t *n_seg, const int64_t *bits_off, const int64_t *adj_off,
+                int32_t prune, const fclu_batch *b, Staged &st) {
+    HIP_TRY(c, hipSetDevice(c->device));
+    st.T = T; st.R = row_off[T]; st.n_bits = bits_off[T]; st.n_adj = adj_off[T];
+    st.tints.assign((size_t)T, TintDesc()); st.row_tint.assign((size_t)st.R, 0); st.tint_word0.assign((size_t)T + 1, 0);
+    for (int t = 0; t < T; ++t) {
+        TintDesc &d = st.tints[(size_t)t];
+        RC_TRY(describe_tint(c, t, k, prune, row_off, n_seg, bits_off, adj_off, d));
+        if (d.in_lds) { st.small_tints.push_back(t); st.small_lds = std::max(st.small_lds, ((size_t)2 * d.n * d.aw + d.aw) * 8 + (size_t)d.n * 2 + 16); }
+        else if (d.n > 0) { st.any_large = true; st.max_aw_large = std::max(st.max_aw_large, d.aw); }
+        st.max_w = std::max(st.max_w, d.w);
+        if (b) RC_TRY(check_rows(c, t, d, b));
+        std::fill_n(st.row_tint.begin() + d.row0, d.n, t);
+        for (int ti = 0; ti < d.aw; ++ti) for (int tj = ti; tj < d.aw; ++tj) st.tiles.push_back(make_int4(t, ti, tj, 0));   // (on and above the diagonal)
+        for (int z = 0; z < d.aw; ++z) st.word_tint.push_back(make_int2(t, z));
+        st.tint_word0[(size_t)t + 1] = (i64)st.word_tint.size();
+    }
+    st.n_tiles = (int)st.tiles.size();
+    c->compat_ms = c->prune_ms = 0.f;
+    c->h_tints = st.tints;
+    c->adj_cur = 0;
+    st.empty = st.n_tiles == 0 || st.R == 0;
+    if (st.empty) return FCLU_OK;
+    RC_TRY(grow_staged(c, st));
+    return upload_staged(c, st);
+}
+
+// ---- the graph: compatibility and pruning ----------------------------------------------------------------------------------
+// The graph of a staged batch whose rows (c->bits / first / last / tail) are on the device: compatibility, then pruning.  The pruned
+// matrix stays on the device in c->adj[c->adj_cur] (with the tints' descriptors in c->tints / c->h_tints and c->row_tint) for
+// partition_device(); adj_out may be null.
+int compat_run(fclu_ctx *c, const Staged &st, const Knobs &k, int32_t prune, uint64_t *adj_out, int32_t *rounds_out) {
+    hipStream_t s = c->stream;
+    const int grid = st.n_tiles < 8192 ? st.n_tiles : 8192;
+    // rows of at most kRankWords words: the rank tables ride along
+    const bool rank = st.max_w <= kRankWords && k.rank;
+    const size_t lds = (size_t)2 * kTile * (st.max_w | 1) * (rank ? 6 : 4);
+    HIP_TRY(c, hipEventRecord(c->ev[0], s));
+    hipLaunchKernelGGL(!rank ? k_compat<false> : k_compat<true>, dim3(grid), dim3(256), lds, s, st.n_tiles, c->tiles.p, c->tints.p, c->bits.p, c->first.p,
+                       c->last.p, c->tail.p, c->adj[0].p);
+    HIP_TRY(c, hipEventRecord(c->ev[1], s));
+    int cur = 0;
+    if (prune && !st.small_tints.empty()) {
+        // (the final matrix of such a tint goes into BOTH copies: whichever the per-pass kernels of the large tints end on holds it)
+        HIP_TRY(c, hipMemcpyAsync(c->small_tints.p, st.small_tints.data(), c->small_tints.bytes(st.small_tints.size()), hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(k_prune_lds, dim3((unsigned)st.small_tints.size()), dim3(256), st.small_lds, s, c->small_tints.p, c->tints.p, c->adj[0].p,
+                           c->adj[1].p, c->small_rounds.p);
+    }
+    if (prune && st.any_large) {
+        // the loop of :240-255 usually ends after two or three passes
+        const i64 R = st.R;
+        const int T = st.T, n_words = (int)st.word_tint.size();
+        const int deg_grid = (int)((R + 3) / 4 < 4096 ? (R + 3) / 4 : 4096);
+        // the pass edge by edge (k_prune_edges) when every tint of the per-pass kernels has rows of at most kEdgeChunks x 64 words
+        const bool edge_walk = st.max_aw_large <= kEdgeChunks * 64 && k.prune_edges;
+        const int edge_chunks = (st.max_aw_large + 63) / 64 > 0 ? (st.max_aw_large + 63) / 64 : 1;
+        int *d_changed = c->pass_any.p + kBurst;             // per pass and tint
+        const int *h_changed = c->h_flags.p + kBurst;
+        const auto pass = [&](int q, int *any, const int *gate) {
+            const int from = cur ^ (q & 1), to = from ^ 1;
+            hipLaunchKernelGGL(k_degree, dim3(deg_grid), dim3(256), 0, s, R, c->row_tint.p, c->tints.p, c->adj[from].p, c->deg.p, gate);
+            if (edge_walk)
+                hipLaunchKernelGGL(k_prune_edges, dim3((int)((R * edge_chunks + 3) / 4 < 65536 ? (R * edge_chunks + 3) / 4 : 65536)), dim3(256), 0, s, R, edge_chunks,
+                                   c->row_tint.p, c->tints.p, c->adj[from].p, c->deg.p, c->adj[to].p, d_changed + (size_t)q * T, any, gate);
+            else {
+                hipLaunchKernelGGL(k_deg1, dim3((n_words + 3) / 4 < 4096 ? (n_words + 3) / 4 : 4096), dim3(256), 0, s, n_words, c->word_tint.p, c->tints.p,
+                                   c->deg.p, c->deg1.p, gate);
+                hipLaunchKernelGGL(k_prune, dim3((int)((R + 3) / 4 < 16384 ? (R + 3) / 4 : 16384)), dim3(256), 0, s, R, c->row_tint.p, c->tints.p, c->tint_word0.p,
+                                   c->adj[from].p, c->deg.p, c->deg1.p, c->adj[to].p, d_changed + (size_t)q * T, any, gate);
+            }
+        };
+        bool done = false;
+        for (int burst = 0; burst < (1 << 18) && !done; ++burst) {
+            int ran = 0;
+            RC_TRY(run_burst(c, c->pass_any, c->h_flags, (size_t)kBurst * (T + 1), pass, ran, done));
+            for (int q = 0; q < ran; ++q)
+                if (rounds_out) for (int t = 0; t < T; ++t) if (h_changed[(size_t)q * T + t]) rounds_out[t] += 1;
+            cur ^= ran & 1;                                  // (each pass that ran wrote the other buffer)
+        }
+    }
+    HIP_TRY(c, hipEventRecord(c->ev[2], s));
+    c->adj_cur = cur;
+    if (adj_out) HIP_TRY(c, hipMemcpyAsync(adj_out, c->adj[cur].p, c->adj[cur].bytes((size_t)st.n_adj), hipMemcpyDeviceToHost, s));
+    std::vector<int> small_rounds;
+    if (prune && rounds_out && !st.small_tints.empty()) {
+        small_rounds.resize((size_t)st.T);
+        HIP_TRY(c, hipMemcpyAsync(small_rounds.data(), c->small_rounds.p, c->small_rounds.bytes((size_t)st.T), hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(c, hipStreamSynchronize(s));
+    if (!small_rounds.empty()) for (int t : st.small_tints) rounds_out[t] = small_rounds[(size_t)t];
+    HIP_TRY(c, hipGetLastError());
+    (void)hipEventElapsedTime(&c->compat_ms, c->ev[0], c->ev[1]);
+    (void)hipEventElapsedTime(&c->prune_ms, c->ev[1], c->ev[2]);
+    return FCLU_OK;
+}
+
+// The graph of a batch of the caller's rows: staging with every check, the rows' upload, the kernels.
+int compat_device(fclu_ctx *c, const Knobs &k, const fclu_batch *b, int32_t prune, uint64_t *adj_out, int32_t *rounds_out) {
+    if (b->n_tint <= 0) return fail(c, FCLU_ERR_ARG, "fclu_compat_graph: empty batch");
+    Staged st;
+    RC_TRY(stage_tints(c, k, b->n_tint, b->row_off, b->n_seg, b->bits_off, b->adj_off, prune, b, st));
+    if (rounds_out) for (int t = 0; t < st.T; ++t) rounds_out[t] = 0;
+    if (st.empty) return FCLU_OK;
+    hipStream_t s = c->stream;
+    HIP_TRY(c, hipMemcpyAsync(c->bits.p, b->bits, c->bits.bytes((size_t)st.n_bits), hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(c->first.p, b->first, c->first.bytes((size_t)st.R), hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(c->last.p, b->last, c->last.bytes((size_t)st.R), hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(c->tail.p, b->tail, c->tail.bytes((size_t)st.R), hipMemcpyHostToDevice, s));
+    return compat_run(c, st, k, prune, adj_out, rounds_out);
+}
+
+// ---- partition_reads() behind the graph (:256-274) ---------------------------------------------------------------
+int check_members(fclu_ctx *c, i64 R, const int64_t *mem_off, const int32_t *mem, int32_t maximum_ilp_size) {
+    if (maximum_ilp_size < 1) return fail(c, FCLU_ERR_ARG, "maximum_ilp_size is %d: it must be at least 1", (int)maximum_ilp_size);
+    if (R < 0 || R >= (1ll << 31)) return fail(c, FCLU_ERR_ARG, "bad row count %lld", R);
+    if (!mem_off) return fail(c, FCLU_ERR_ARG, "mem_off is null");
+    if (mem_off[0] != 0) return fail(c, FCLU_ERR_ARG, "mem_off[0] is %lld, not 0", (i64)mem_off[0]);
+    for (i64 r = 0; r < R; ++r)
+        if (mem_off[r + 1] < mem_off[r]) return fail(c, FCLU_ERR_ARG, "mem_off is not monotone at row %lld (%lld after %lld)", r, (i64)mem_off[r + 1], (i64)mem_off[r]);
+    if (mem_off[R] > 0 && !mem) return fail(c, FCLU_ERR_ARG, "mem is null");
+    return FCLU_OK;
+}
+
+// what the stages of one partition call share
+struct PartRun {
+    int T = 0, max_size = 1, end_bit = 1, row_grid = 1, wave_grid = 1;
+    i64 R = 0, n_mem = 0, P = 0, n_pairs = 0;
+    size_t sort_bytes = 0, scan_bytes = 0;
+};
+
+// The pair list, device and pinned: as large as the graphs make it, so exactly that, and a batch's that does not fit is refused.
+int grow_pairs(fclu_ctx *c, i64 n_pairs) {
+    const size_t need = c->d_pairs.bytes((size_t)n_pairs);
+    if (n_pairs > 2147483647ll)
+        return fail(c, FCLU_ERR_UNSUPPORTED, "%lld incompatible pairs in this batch: more than the 2147483647 a call returns", n_pairs);
+    if (need > c->d_pairs.cap) {
+        HIP_TRY(c, c->d_pairs.release());
+        size_t free_b = 0, total_b = 0;
+        HIP_TRY(c, hipMemGetInfo(&free_b, &total_b));
+        if (need + (64u << 20) > free_b)
+            return fail(c, FCLU_ERR_UNSUPPORTED, "%lld incompatible pairs in this batch (%lld bytes) do not fit the device's free memory (%lld bytes)",
+                        n_pairs, n_pairs * 8, (i64)free_b);
+        if (c->d_pairs.alloc(need) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(c, FCLU_ERR_UNSUPPORTED, "%lld incompatible pairs in this batch: no device memory for %lld bytes", n_pairs, n_pairs * 8);
+        }
+    }
+    if (need > c->h_pairs.cap || !c->h_pairs.p) {
+        HIP_TRY(c, c->h_pairs.release());
+        if (c->h_pairs.alloc(std::max<size_t>(need, 16)) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(c, FCLU_ERR_UNSUPPORTED, "%lld incompatible pairs in this batch: no pinned host memory for %lld bytes", n_pairs, n_pairs * 8);
+        }
+    }
+    return FCLU_OK;
+}
+
+// fclu_parts of the call: the pinned buffers grown, filled from the device (copy; the caller synchronises) and handed out
+int part_results(fclu_ctx *c, const PartRun &p, bool copy) {
+    fclu_parts &o = c->parts;
+    const size_t T1 = (size_t)p.T + 1, P1 = (size_t)p.P + 1, R = (size_t)p.R;
+    RC_TRY(fetch(c, c->h_tint_part_off, c->d_tint_part_off.p, T1, copy, o.tint_part_off));
+    RC_TRY(fetch(c, c->h_part_node_off, c->d_part_node_off.p, P1, copy, o.part_node_off));
+    RC_TRY(fetch(c, c->h_part_rid_off, c->d_part_rid_off.p, P1, copy, o.part_rid_off));
+    RC_TRY(fetch(c, c->h_part_pair_off, c->d_part_pair_off.p, P1, copy, o.part_pair_off));
+    RC_TRY(fetch(c, c->h_part_nodes, c->d_nodes.p, R, copy, o.part_nodes));
+    RC_TRY(fetch(c, c->h_label, c->d_label.p, R, copy, o.label));
+    RC_TRY(fetch(c, c->h_part_rids, c->d_part_rids.p, (size_t)p.n_mem, copy, o.part_rids));
+    if (copy && p.n_pairs) HIP_TRY(c, hipMemcpyAsync(c->h_pairs.p, c->d_pairs.p, c->d_pairs.bytes((size_t)p.n_pairs), hipMemcpyDeviceToHost, c->stream));
+    o.pairs = &c->h_pairs.p->x;                              // (grow_pairs: never null)
+    o.n_tint = p.T; o.n_rows = p.R; o.n_part = p.P; o.n_rids = p.n_mem; o.n_pairs = p.n_pairs;
+    return FCLU_OK;
+}
+
+// nothing but empty tints
+int part_empty(fclu_ctx *c, int T) {
+    PartRun p;
+    p.T = T;
+    RC_TRY(grow_pairs(c, 0));
+    RC_TRY(part_results(c, p, false));
+    memset(c->h_tint_part_off.p, 0, c->h_tint_part_off.bytes((size_t)T + 1));
+    *c->h_part_node_off.p = *c->h_part_rid_off.p = *c->h_part_pair_off.p = 0;
+    return FCLU_OK;
+}
+
+// The work arrays, the members' upload (mem_off null: on the device already) and the connected components: c->parent behind it.
+int part_components(fclu_ctx *c, PartRun &p, const int64_t *mem_off, const int32_t *mem) {
+    hipStream_t s = c->stream;
+    const i64 R = p.R;
+    std::vector<int> small;
+    size_t small_lds = 0;
+    bool any_large = false;
+    for (int t = 0; t < p.T; ++t) {
+        const TintDesc &d = c->h_tints[(size_t)t];
+        if (d.cc_lds) { small.push_back(t); small_lds = std::max(small_lds, (size_t)d.n * d.aw * 8 + (size_t)d.n * 4); }
+        else if (d.n > 0) any_large = true;
+    }
+    const size_t R1 = (size_t)R + 1;
+    for (Buf<int> *b : {&c->parent, &c->rows, &c->sval, &c->comp_start, &c->comp_end, &c->chunk_end, &c->d_label, &c->d_nodes}) HIP_TRY(c, b->grow((size_t)R));
+    for (Buf<i64> *b : {&c->head, &c->part_id, &c->smult, &c->rid_pos, &c->cnt, &c->pair_base, &c->d_part_node_off, &c->d_part_rid_off, &c->d_part_pair_off, &c->mem_off})
+        HIP_TRY(c, b->grow(R1));
+    HIP_TRY(c, c->skey.grow((size_t)R));
+    HIP_TRY(c, c->d_tint_part_off.grow((size_t)p.T + 1));
+    HIP_TRY(c, c->mem.grow((size_t)p.n_mem)); HIP_TRY(c, c->d_part_rids.grow((size_t)p.n_mem));
+    HIP_TRY(c, c->small_tints.grow(small.size() + 1));
+    HIP_TRY(c, c->pass_any.grow(kBurst)); HIP_TRY(c, c->h_flags.grow(kBurst)); HIP_TRY(c, c->h_tot.grow(2));
+    p.end_bit = bits_for(R);
+    unsigned *parent_key = reinterpret_cast<unsigned *>(c->parent.p);            // (the sort's keys: the roots, unsigned)
+    HIP_TRY(c, rocprim::radix_sort_pairs(nullptr, p.sort_bytes, parent_key, c->skey.p, c->rows.p, c->sval.p, (size_t)R, 0u, (unsigned)p.end_bit, s));
+    HIP_TRY(c, rocprim::exclusive_scan(nullptr, p.scan_bytes, c->head.p, c->part_id.p, (i64)0, R1, rocprim::plus<i64>(), s));
+    HIP_TRY(c, c->tmp.grow(std::max(p.sort_bytes, p.scan_bytes)));
+    if (mem_off) {
+        HIP_TRY(c, hipMemcpyAsync(c->mem_off.p, mem_off, c->mem_off.bytes(R1), hipMemcpyHostToDevice, s));
+        if (p.n_mem) HIP_TRY(c, hipMemcpyAsync(c->mem.p, mem, c->mem.bytes((size_t)p.n_mem), hipMemcpyHostToDevice, s));
+    }
+    if (!small.empty()) HIP_TRY(c, hipMemcpyAsync(c->small_tints.p, small.data(), c->small_tints.bytes(small.size()), hipMemcpyHostToDevice, s));
+
+    p.row_grid = (int)std::min<i64>((R + 256) / 256, 4096); p.wave_grid = (int)std::min<i64>((R + 3) / 4, 65536);
+    const u64 *d_adj = c->adj[c->adj_cur].p;
+    HIP_TRY(c, hipEventRecord(c->pev[0], s));
+    hipLaunchKernelGGL(k_cc_init, dim3(p.row_grid), dim3(256), 0, s, R, c->parent.p);
+    hipLaunchKernelGGL(k_cc_init, dim3(p.row_grid), dim3(256), 0, s, R, c->rows.p);     // (the sort's values: the rows themselves)
+    if (!small.empty())
+        hipLaunchKernelGGL(k_cc_lds, dim3((unsigned)small.size()), dim3(256), small_lds, s, c->small_tints.p, c->tints.p, d_adj, c->parent.p);
+    if (any_large) {
+        const auto pass = [&](int, int *any, const int *gate) {
+            hipLaunchKernelGGL(k_cc_hook, dim3(p.wave_grid), dim3(256), 0, s, R, c->row_tint.p, c->tints.p, d_adj, c->parent.p, any, gate);
+            hipLaunchKernelGGL(k_cc_jump, dim3(p.row_grid), dim3(256), 0, s, R, c->row_tint.p, c->tints.p, c->parent.p, any, gate);
+        };
+        bool done = false;
+        for (int burst = 0, ran = 0; !done; ++burst) {
+            if (burst >= (1 << 16)) return fail(c, FCLU_ERR_HIP, "connected components did not converge");
+            RC_TRY(run_burst(c, c->pass_any, c->h_flags, kBurst, pass, ran, done));
+        }
+    }
+    HIP_TRY(c, hipEventRecord(c->pev[1], s));
+    return FCLU_OK;
+}
+
+// The even split, the members' positions and the pair counts: behind it p.P and p.n_pairs, the call's totals.
+int part_split(fclu_ctx *c, PartRun &p) {
+    hipStream_t s = c->stream;
+    const i64 R = p.R;
+    const size_t R1 = (size_t)R + 1;
+    const u64 *d_adj = c->adj[c->adj_cur].p;
+    HIP_TRY(c, rocprim::radix_sort_pairs(c->tmp.p, p.sort_bytes, reinterpret_cast<unsigned *>(c->parent.p), c->skey.p, c->rows.p, c->sval.p, (size_t)R, 0u,
+                                         (unsigned)p.end_bit, s));
+    hipLaunchKernelGGL(k_bounds, dim3(p.row_grid), dim3(256), 0, s, R, c->skey.p, c->comp_start.p, c->comp_end.p);
+    hipLaunchKernelGGL(k_chunk, dim3(p.row_grid), dim3(256), 0, s, R, (i64)p.max_size, c->skey.p, c->sval.p, c->comp_start.p, c->comp_end.p, c->mem_off.p,
+                       c->row_tint.p, c->tints.p, c->parent.p, c->head.p, c->chunk_end.p, c->smult.p, c->d_label.p, c->d_nodes.p);
+    size_t sb = p.scan_bytes;
+    HIP_TRY(c, rocprim::exclusive_scan(c->tmp.p, sb, c->head.p, c->part_id.p, (i64)0, R1, rocprim::plus<i64>(), s));
+    sb = p.scan_bytes;
+    HIP_TRY(c, rocprim::exclusive_scan(c->tmp.p, sb, c->smult.p, c->rid_pos.p, (i64)0, R1, rocprim::plus<i64>(), s));
+    HIP_TRY(c, hipMemsetAsync(c->cnt.p + R, 0, c->cnt.bytes(1), s));
+    HIP_TRY(c, hipEventRecord(c->pev[2], s));
+    hipLaunchKernelGGL(k_pairs<false>, dim3(p.wave_grid), dim3(256), 0, s, R, c->sval.p, c->chunk_end.p, c->smult.p, c->row_tint.p, c->tints.p, d_adj,
+                       c->cnt.p, (const i64 *)nullptr, c->mem_off.p, c->mem.p, (int2 *)nullptr);
+    HIP_TRY(c, hipEventRecord(c->pev[3], s));
+    sb = p.scan_bytes;
+    HIP_TRY(c, rocprim::exclusive_scan(c->tmp.p, sb, c->cnt.p, c->pair_base.p, (i64)0, R1, rocprim::plus<i64>(), s));
+    const i64 RT = std::max<i64>(R, p.T);
+    hipLaunchKernelGGL(k_offsets, dim3((int)std::min<i64>((RT + 256) / 256, 4096)), dim3(256), 0, s, R, p.T, c->tints.p, c->head.p, c->part_id.p, c->rid_pos.p,
+                       c->pair_base.p, c->d_tint_part_off.p, c->d_part_node_off.p, c->d_part_rid_off.p, c->d_part_pair_off.p);
+    HIP_TRY(c, hipMemcpyAsync(c->h_tot.p, c->part_id.p + R, c->h_tot.bytes(1), hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(c->h_tot.p + 1, c->pair_base.p + R, c->h_tot.bytes(1), hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    HIP_TRY(c, hipGetLastError());
+    p.P = c->h_tot.p[0]; p.n_pairs = c->h_tot.p[1];
+    if (p.P < 0 || p.P > R || p.n_pairs < 0) return fail(c, FCLU_ERR_HIP, "partition totals out of range (%lld partitions, %lld pairs)", p.P, p.n_pairs);
+    return FCLU_OK;
+}
+
+// The pairs and the partitions' members, and everything to the host.
+int part_emit(fclu_ctx *c, const PartRun &p) {
+    hipStream_t s = c->stream;
+    RC_TRY(grow_pairs(c, p.n_pairs));
+    HIP_TRY(c, hipEventRecord(c->pev[4], s));
+    if (p.n_pairs)
+        hipLaunchKernelGGL(k_pairs<true>, dim3(p.wave_grid), dim3(256), 0, s, p.R, c->sval.p, c->chunk_end.p, c->smult.p, c->row_tint.p, c->tints.p,
+                           c->adj[c->adj_cur].p, (i64 *)nullptr, c->pair_base.p, c->mem_off.p, c->mem.p, c->d_pairs.p);
+    if (p.n_mem)
+        hipLaunchKernelGGL(k_members, dim3(p.wave_grid), dim3(256), 0, s, p.R, c->sval.p, c->smult.p, c->rid_pos.p, c->mem_off.p, c->mem.p, c->d_part_rids.p);
+    HIP_TRY(c, hipEventRecord(c->pev[5], s));
+    RC_TRY(part_results(c, p, true));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    HIP_TRY(c, hipGetLastError());
+    float a = 0.f, b = 0.f;
+    (void)hipEventElapsedTime(&c->components_ms, c->pev[0], c->pev[1]);
+    (void)hipEventElapsedTime(&a, c->pev[2], c->pev[3]);
+    (void)hipEventElapsedTime(&b, c->pev[4], c->pev[5]);
+    c->pairs_ms = a + b;
+    return FCLU_OK;
+}
+
+// c->tints / c->h_tints / c->row_tint describe the batch and c->adj[c->adj_cur] holds its pruned matrices.  mem_off null: the members
+// are on the device already (c->mem_off, c->mem: n_mem_device rep ids), where the dedupe left them.
+int partition_device(fclu_ctx *c, int T, i64 R, const int64_t *mem_off, const int32_t *mem, i64 n_mem_device, int32_t maximum_ilp_size) {
+    HIP_TRY(c, hipSetDevice(c->device));
+    c->components_ms = c->pairs_ms = 0.f;
+    if (R == 0) RC_TRY(part_empty(c, T));
+    else {
+        PartRun p;
+        p.T = T; p.R = R; p.max_size = maximum_ilp_size; p.n_mem = mem_off ? mem_off[R] : n_mem_device;
+        RC_TRY(part_components(c, p, mem_off, mem));
+        RC_TRY(part_split(c, p));
+        RC_TRY(part_emit(c, p));
+    }
+    c->have_parts = true;
+    return FCLU_OK;
+}
+
+// ---- preprocess_ilp() + the dedupe of a batch of label rows ----------------------------------------------------------
+// what the two halves share
+struct PrepRun {
+    int T = 0;
+    i64 N = 0, n_rbits = 0, R = 0, n_bits = 0;           // reps, words of their I / C rows; unique rows, words of theirs
+    std::vector<PrepTint> pt;
+};
+
+// Rows and dedupe up to the tints' counts of unique rows: only row_off (n_tint + 1 counts) and the three error words come back to the
+// host here, for the refusals and for the unique rows' layout as a batch (c->ph.row_off / bits_off / adj_off).
+int prep_rows(fclu_ctx *c, const Knobs &k, const fclu_reads *rd, PrepRun &p) {
+    if (!rd || rd->n_tint <= 0) return fail(c, FCLU_ERR_ARG, "fclu_preprocess: empty batch");
+    if (!rd->rep_off || !rd->n_seg || !rd->lab_off) return fail(c, FCLU_ERR_ARG, "fclu_preprocess: rep_off, n_seg or lab_off is null");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const int T = p.T = rd->n_tint;
+    if (rd->rep_off[0] != 0 || rd->lab_off[0] != 0) return fail(c, FCLU_ERR_ARG, "fclu_preprocess: rep_off and lab_off start at 0");
+    auto &D = c->pd;
+    auto &H = c->ph;
+    for (HostBuf<int64_t> *h : {&H.row_off, &H.bits_off, &H.adj_off, &H.rbits_off}) HIP_TRY(c, h->grow((size_t)T + 1));
+    HIP_TRY(c, H.err.grow(4));
+    p.pt.assign((size_t)T, PrepTint());
+    i64 n_slots = 0;
+    H.rbits_off.p[0] = 0;
+    for (int t = 0; t < T; ++t) {
+        PrepTint &d = p.pt[(size_t)t];
+        const i64 n = rd->rep_off[t + 1] - rd->rep_off[t];
+        if (n < 0 || n > (1 << 30) || rd->n_seg[t] < 0)
+            return fail(c, FCLU_ERR_ARG, "tint %d: negative or too large rep count (%lld) or segment count (%d)", t, n, (int)rd->n_seg[t]);
+        if (rd->n_seg[t] > kMaxWords * 32)
+            return fail(c, FCLU_ERR_UNSUPPORTED, "tint %d has %d segments; this build stages at most %d", t, (int)rd->n_seg[t], kMaxWords * 32);
+        d.rep0 = rd->rep_off[t]; d.lab_off = rd->lab_off[t]; d.rbits_off = H.rbits_off.p[t]; d.slot0 = n_slots;
+        d.n = (int)n; d.n_seg = rd->n_seg[t];
+        d.lw = std::max((d.n_seg + 15) / 16, 1); d.w = std::max((d.n_seg + 31) / 32, 1);
+        d.g_log2 = 0; while (d.g_log2 < 6 && (1 << d.g_log2) < d.w) ++d.g_log2;
+        if (rd->lab_off[t + 1] - d.lab_off != n * d.lw)
+            return fail(c, FCLU_ERR_ARG, "tint %d: lab_off does not match reps x words (%lld words for %lld reps of %d)", t,
+                        (i64)(rd->lab_off[t + 1] - d.lab_off), n, d.lw);
+        H.rbits_off.p[t + 1] = d.rbits_off + n * d.w;
+        n_slots += ((n << d.g_log2) + 63) / 64 * 64;
+    }
+    const i64 N = p.N = rd->rep_off[T], n_lab = rd->lab_off[T];
+    p.n_rbits = H.rbits_off.p[T];
+    if (N >= 0x7f7f7f7fll) return fail(c, FCLU_ERR_ARG, "fclu_preprocess: %lld reps in one batch", N);
+    if (N > 0 && (!rd->labels || !rd->tail)) return fail(c, FCLU_ERR_ARG, "fclu_preprocess: labels or tail is null");
+    int64_t *h_row_off = H.row_off.p;
+    if (N > 0) {
+        hipStream_t s = c->stream;
+        const size_t N1 = (size_t)N + 1;
+        HIP_TRY(c, D.tints.grow((size_t)T));
+        HIP_TRY(c, D.labels.grow((size_t)n_lab)); HIP_TRY(c, D.tail.grow((size_t)N));
+        HIP_TRY(c, D.ibits.grow((size_t)p.n_rbits)); HIP_TRY(c, D.cbits.grow((size_t)p.n_rbits));
+        for (Buf<int> *b : {&D.rfirst, &D.rlast, &D.first, &D.last, &D.rep_tint, &D.val, &D.sval, &D.head, &D.bstart, &D.leader, &D.rep_node, &D.node_rep, &D.nval, &c->mem})
+            HIP_TRY(c, b->grow((size_t)N));
+        HIP_TRY(c, D.nkey.grow((size_t)N)); HIP_TRY(c, D.snkey.grow((size_t)N));
+        HIP_TRY(c, D.flag.grow(N1)); HIP_TRY(c, D.node_id.grow(N1));
+        HIP_TRY(c, D.key.grow((size_t)N)); HIP_TRY(c, D.skey.grow((size_t)N));
+        HIP_TRY(c, D.row_off.grow((size_t)T + 1)); HIP_TRY(c, D.err.grow(4));
+        const unsigned key_bits = 32u + (unsigned)bits_for(T), node_bits = (unsigned)bits_for(N);
+        size_t sort_a = 0, sort_b = 0, scan_a = 0, scan_b = 0;
+        HIP_TRY(c, rocprim::radix_sort_pairs(nullptr, sort_a, D.key.p, D.skey.p, D.val.p, D.sval.p, (size_t)N, 0u, key_bits, s));
+        HIP_TRY(c, rocprim::radix_sort_pairs(nullptr, sort_b, D.nkey.p, D.snkey.p, D.nval.p, c->mem.p, (size_t)N, 0u, node_bits, s));
+        HIP_TRY(c, rocprim::inclusive_scan(nullptr, scan_a, D.head.p, D.bstart.p, (size_t)N, rocprim::maximum<int>(), s));
+        HIP_TRY(c, rocprim::exclusive_scan(nullptr, scan_b, D.flag.p, D.node_id.p, 0, N1, rocprim::plus<int>(), s));
+        const size_t tmp_bytes = std::max(std::max(sort_a, sort_b), std::max(scan_a, scan_b));
+        HIP_TRY(c, D.tmp.grow(tmp_bytes));
+        HIP_TRY(c, hipMemcpyAsync(D.tints.p, p.pt.data(), D.tints.bytes((size_t)T), hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipMemcpyAsync(D.labels.p, rd->labels, D.labels.bytes((size_t)n_lab), hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipMemcpyAsync(D.tail.p, rd->tail, D.tail.bytes((size_t)N), hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipMemsetAsync(D.err.p, 0x7f, D.err.bytes(4), s));
+        HIP_TRY(c, hipMemsetAsync(D.flag.p + N, 0, D.flag.bytes(1), s));
+        const int rep_grid = (int)std::min<i64>((N + 255) / 256, 4096);
+        HIP_TRY(c, hipEventRecord(c->qev[0], s));
+        hipLaunchKernelGGL(k_rows, dim3((unsigned)std::min<i64>((n_slots + 255) / 256, 65536)), dim3(256), 0, s, T, n_slots, D.tints.p, D.labels.p, D.tail.p,
+                           k.hash_mask, D.ibits.p, D.cbits.p, D.rfirst.p, D.rlast.p, D.first.p, D.last.p, D.rep_tint.p, D.key.p, D.val.p, D.err.p);
+        HIP_TRY(c, hipEventRecord(c->qev[1], s));
+        // refusals first: a tail above 2 or a label 3 has no meaning, and the sort's keys of such a batch are not needed
+        HIP_TRY(c, hipMemcpyAsync(H.err.p, D.err.p, D.err.bytes(4), hipMemcpyDeviceToHost, s));
+        size_t tb = tmp_bytes;
+        HIP_TRY(c, rocprim::radix_sort_pairs(D.tmp.p, tb, D.key.p, D.skey.p, D.val.p, D.sval.p, (size_t)N, 0u, key_bits, s));
+        hipLaunchKernelGGL(k_heads, dim3(rep_grid), dim3(256), 0, s, N, D.skey.p, D.head.p);
+        tb = tmp_bytes;
+        HIP_TRY(c, rocprim::inclusive_scan(D.tmp.p, tb, D.head.p, D.bstart.p, (size_t)N, rocprim::maximum<int>(), s));
+        hipLaunchKernelGGL(k_leader, dim3(rep_grid), dim3(256), 0, s, N, D.skey.p, D.sval.p, D.bstart.p, D.tints.p, D.ibits.p, D.first.p, D.last.p, D.tail.p,
+                           D.leader.p, D.flag.p);
+        tb = tmp_bytes;
+        HIP_TRY(c, rocprim::exclusive_scan(D.tmp.p, tb, D.flag.p, D.node_id.p, 0, N1, rocprim::plus<int>(), s));
+        hipLaunchKernelGGL(k_row_off, dim3((unsigned)(T + 256) / 256), dim3(256), 0, s, T, N, D.tints.p, D.node_id.p, D.row_off.p);
+        HIP_TRY(c, hipEventRecord(c->qev[2], s));
+        HIP_TRY(c, hipMemcpyAsync(h_row_off, D.row_off.p, D.row_off.bytes((size_t)T + 1), hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipStreamSynchronize(s));
+        HIP_TRY(c, hipGetLastError());
+        const int kinds[3] = {2, 0, 1};                      // the tail first: it is the caller's own byte, the labels come from a file
+        for (int kind : kinds) {
+            if (H.err.p[kind] == 0x7f7f7f7f) continue;
+            const i64 rep = H.err.p[kind];
+            int t = 0;
+            while (t + 1 < T && rd->rep_off[t + 1] <= rep) ++t;
+            const i64 r = rep - rd->rep_off[t];
+            if (kind == 2) return fail(c, FCLU_ERR_ARG, "tint %d rep %lld: tail category %d (0 'N', 1 'S', 2 'E')", t, r, (int)rd->tail[rep]);
+            if (kind == 0) return fail(c, FCLU_ERR_ARG, "tint %d rep %lld: a label with code 3 (labels are 0, 1, 2)", t, r);
+            return fail(c, FCLU_ERR_ARG, "tint %d rep %lld: a nonzero bit beyond the tint's %d labels", t, r, (int)rd->n_seg[t]);
+        }
+    } else {
+        memset(h_row_off, 0, H.row_off.bytes((size_t)T + 1));
+    }
+    // ---- the unique rows as a batch
+    H.bits_off.p[0] = H.adj_off.p[0] = 0;
+    for (int t = 0; t < T; ++t) {
+        const i64 n = h_row_off[t + 1] - h_row_off[t];
+        if (n < 0 || n > rd->rep_off[t + 1] - rd->rep_off[t]) return fail(c, FCLU_ERR_HIP, "tint %d: %lld unique rows of %lld reps", t, n, (i64)(rd->rep_off[t + 1] - rd->rep_off[t]));
+        H.bits_off.p[t + 1] = H.bits_off.p[t] + n * p.pt[(size_t)t].w;
+        H.adj_off.p[t + 1] = H.adj_off.p[t] + n * ((n + 63) / 64);
+    }
+    p.R = h_row_off[T]; p.n_bits = H.bits_off.p[T];
+    return FCLU_OK;
+}
+
+// The nodes behind stage_tints(): c->bits / first / last / tail hold them in fclu_batch's layout, c->mem_off / c->mem their members, and
+// the pinned copies of everything fclu_prep names are on their way (the caller synchronises).
+int prep_nodes(fclu_ctx *c, const PrepRun &p) {
+    hipStream_t s = c->stream;
+    auto &D = c->pd;
+    auto &H = c->ph;
+    const i64 N = p.N, R = p.R;
+    const bool copy = N > 0;
+    if (copy) {
+        HIP_TRY(c, c->mem_off.grow((size_t)R + 1));
+        const int rep_grid = (int)std::min<i64>((N + 256) / 256, 4096);
+        HIP_TRY(c, hipEventRecord(c->qev[3], s));
+        hipLaunchKernelGGL(k_nodes, dim3(rep_grid), dim3(256), 0, s, N, D.rep_tint.p, D.tints.p, c->tints.p, D.leader.p, D.node_id.p, D.ibits.p, D.first.p,
+                           D.last.p, D.tail.p, D.rep_node.p, D.nkey.p, D.nval.p, D.node_rep.p, c->bits.p, c->first.p, c->last.p, c->tail.p);
+        size_t tb = D.tmp.cap;
+        HIP_TRY(c, rocprim::radix_sort_pairs(D.tmp.p, tb, D.nkey.p, D.snkey.p, D.nval.p, c->mem.p, (size_t)N, 0u, (unsigned)bits_for(N), s));
+        hipLaunchKernelGGL(k_mem_off, dim3(rep_grid), dim3(256), 0, s, N, R, D.snkey.p, c->mem_off.p);
+        HIP_TRY(c, hipEventRecord(c->qev[4], s));
+    }
+    // the result set: {pinned buffer, device source, element count, fclu_prep's field}
+    fclu_prep &o = c->prep;
+    const size_t nN = (size_t)N, nR = (size_t)R, nW = (size_t)p.n_rbits;
+    RC_TRY(fetch(c, H.ibits, D.ibits.p, nW, copy, o.i_bits));
+    RC_TRY(fetch(c, H.cbits, D.cbits.p, nW, copy, o.c_bits));
+    RC_TRY(fetch(c, H.first, D.first.p, nN, copy, o.first));
+    RC_TRY(fetch(c, H.last, D.last.p, nN, copy, o.last));
+    RC_TRY(fetch(c, H.rfirst, D.rfirst.p, nN, copy, o.raw_first));
+    RC_TRY(fetch(c, H.rlast, D.rlast.p, nN, copy, o.raw_last));
+    RC_TRY(fetch(c, H.rep_node, D.rep_node.p, nN, copy, o.rep_node));
+    RC_TRY(fetch(c, H.node_rep, D.node_rep.p, nR, copy, o.node_rep));
+    RC_TRY(fetch(c, H.mem_off, c->mem_off.p, nR + 1, copy, o.mem_off));
+    RC_TRY(fetch(c, H.mem, c->mem.p, nN, copy, o.mem));
+    RC_TRY(fetch(c, H.bits, c->bits.p, (size_t)p.n_bits, copy, o.bits));
+    RC_TRY(fetch(c, H.nfirst, c->first.p, nR, copy, o.node_first));
+    RC_TRY(fetch(c, H.nlast, c->last.p, nR, copy, o.node_last));
+    RC_TRY(fetch(c, H.ntail, c->tail.p, nR, copy, o.node_tail));
+    if (!copy) *H.mem_off.p = 0;
+    o.n_tint = p.T; o.n_reps = N; o.n_rows = R;
+    o.row_off = H.row_off.p; o.bits_off = H.bits_off.p; o.adj_off = H.adj_off.p; o.rep_bits_off = H.rbits_off.p;
+    return FCLU_OK;
+}
+
+// Rows, dedupe and the staging of the unique rows as a batch: st is what compat_run() needs.
+int preprocess_device(fclu_ctx *c, const Knobs &k, const fclu_reads *rd, int32_t prune, Staged &st, i64 &n_reps_out) {
+    c->have_prep = false;
+    c->rows_ms = c->dedupe_ms = 0.f;
+    PrepRun p;
+    RC_TRY(prep_rows(c, k, rd, p));
+    n_reps_out = p.N;
+    RC_TRY(stage_tints(c, k, p.T, c->ph.row_off.p, rd->n_seg, c->ph.bits_off.p, c->ph.adj_off.p, prune, nullptr, st));
+    return prep_nodes(c, p);
+}
+
+// the kernels' times of the call that has just synchronised
+void preprocess_times(fclu_ctx *c, i64 n_reps) {
+    if (n_reps <= 0) return;
+    float a = 0.f, b = 0.f;
+    (void)hipEventElapsedTime(&c->rows_ms, c->qev[0], c->qev[1]);
+    (void)hipEventElapsedTime(&a, c->qev[1], c->qev[2]);
+    (void)hipEventElapsedTime(&b, c->qev[3], c->qev[4]);
+    c->dedupe_ms = a + b;
+}
 
 }  // namespace
 
+// ---- the C ABI ------------------------------------------------------------------------------------------------------------
 extern "C" {
 
 int fclu_abi_version(void) { return 1; }
@@ -883,16 +1560,12 @@ int fclu_create(int device, fclu_ctx **out) {
     for (int i = 0; e == hipSuccess && i < 3; ++i) e = hipEventCreate(&c->ev[i]);
     for (int i = 0; e == hipSuccess && i < 6; ++i) e = hipEventCreate(&c->pev[i]);
     for (int i = 0; e == hipSuccess && i < 6; ++i) e = hipEventCreate(&c->qev[i]);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_cc_lds), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_compat<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                2 * kTile * (kMaxWords | 1) * 4);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_compat<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                2 * kTile * (kRankWords | 1) * 6);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_prune_lds), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
+    const struct { const void *kernel; int lds; } dyn[] = {                // the most dynamic LDS a launch asks for
+        {reinterpret_cast<const void *>(k_cc_lds), 80 * 1024},
+        {reinterpret_cast<const void *>(k_compat<false>), 2 * kTile * (kMaxWords | 1) * 4},
+        {reinterpret_cast<const void *>(k_compat<true>), 2 * kTile * (kRankWords | 1) * 6},
+        {reinterpret_cast<const void *>(k_prune_lds), 150 * 1024}};
+    for (const auto &d : dyn) if (e == hipSuccess) e = hipFuncSetAttribute(d.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, d.lds);
     if (e != hipSuccess) {
         fail(nullptr, FCLU_ERR_HIP, "context creation failed: %s", hipGetErrorString(e));
         delete c;
@@ -902,708 +1575,24 @@ int fclu_create(int device, fclu_ctx **out) {
     return FCLU_OK;
 }
 
-void fclu_destroy(fclu_ctx *c) {
-    if (!c) return;
-    (void)hipSetDevice(c->device);
-    if (c->stream) { (void)hipStreamSynchronize(c->stream); (void)hipStreamDestroy(c->stream); }
-    for (int i = 0; i < 3; ++i) if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
-    for (int i = 0; i < 6; ++i) if (c->pev[i]) (void)hipEventDestroy(c->pev[i]);
-    for (int i = 0; i < 6; ++i) if (c->qev[i]) (void)hipEventDestroy(c->qev[i]);
-    for (GrowBuf &b : c->pd) if (b.p) (void)hipFree(b.p);
-    for (HostBuf &b : c->ph) if (b.p) (void)hipHostFree(b.p);
-    GrowBuf *bufs[] = {&c->tints, &c->tiles, &c->row_tint, &c->bits, &c->first, &c->last, &c->tail, &c->adj[0], &c->adj[1], &c->deg,
-                       &c->changed, &c->word_tint, &c->tint_word0, &c->deg1, &c->pass_any, &c->small_tints, &c->small_rounds,
-                       &c->parent, &c->skey, &c->rows, &c->sval, &c->comp_start, &c->comp_end, &c->chunk_end, &c->head, &c->part_id, &c->smult,
-                       &c->rid_pos, &c->cnt, &c->pair_base, &c->d_label, &c->d_nodes, &c->d_tint_part_off, &c->d_part_node_off,
-                       &c->d_part_rid_off, &c->d_part_pair_off, &c->mem_off, &c->mem, &c->d_part_rids, &c->d_pairs, &c->tmp};
-    for (GrowBuf *b : bufs) if (b->p) (void)hipFree(b->p);
-    HostBuf *hbufs[] = {&c->h_cc_flags, &c->h_tint_part_off, &c->h_part_node_off, &c->h_part_nodes, &c->h_part_rid_off, &c->h_part_rids,
-                        &c->h_part_pair_off, &c->h_pairs, &c->h_label};
-    for (HostBuf *b : hbufs) if (b->p) (void)hipHostFree(b->p);
-    if (c->h_flags) (void)hipHostFree(c->h_flags);
-    delete c;
-}
+void fclu_destroy(fclu_ctx *c) { delete c; }
 
 const char *fclu_last_error(const fclu_ctx *c) { return c ? c->err.c_str() : g_create_error.c_str(); }
 
 int fclu_compat_graph(fclu_ctx *c, const fclu_batch *b, int32_t prune, uint64_t *adj_out, int32_t *rounds_out) {
     if (!c || !b || !adj_out) return FCLU_ERR_ARG;
-    return compat_device(c, b, prune, adj_out, rounds_out);
+    return compat_device(c, read_knobs(), b, prune, adj_out, rounds_out);
 }
 
-}  // extern "C"
-
-namespace {
-
-// What the host derives from a batch's shape (stage_tints) and the graph kernels are launched with (compat_run).
-struct Staged {
-    int T = 0, n_tiles = 0, max_w = 1, max_aw_large = 0, n_words = 0;
-    i64 R = 0, n_bits = 0, n_adj = 0;
-    bool any_large = false, empty = false;
-    std::vector<int> small_tints;                        // pruned whole in LDS (k_prune_lds); FCLU_PRUNE_LDS=0: none (tests)
-    size_t small_lds = 0;
-    // what the uploads read: alive until the call that staged them has synchronised
-    std::vector<TintDesc> tints;
-    std::vector<int4> tiles;
-    std::vector<int> row_tint;
-    std::vector<int2> word_tint;                         // every adjacency word column of every tint: (tint, word)
-    std::vector<i64> tint_word0;
-};
-
-// Host staging of a batch: the shape checks, the tints' descriptors, tiles and row / word maps, device buffers grown and the maps
-// uploaded.  b: the caller's rows, checked against their tint (fclu_compat_graph, fclu_partition), or null when the rows were made on
-// the device (fclu_partition_reads: first / last / tail in range and bits inside [first, last] by construction).
-int stage_tints(fclu_ctx *c, int T, const int64_t *row_off, const int32_t *n_seg, const int64_t *bits_off, const int64_t *adj_off,
-                int32_t prune, const fclu_batch *b, Staged &st) {
-    HIP_TRY(c, hipSetDevice(c->device));
-    const i64 R = row_off[T];
-    // host-side shape checks: the kernels index with these and nothing else
-    std::vector<TintDesc> &tints = st.tints;
-    std::vector<int4> &tiles = st.tiles;
-    std::vector<int> &row_tint = st.row_tint;
-    std::vector<int2> &word_tint = st.word_tint;
-    std::vector<i64> &tint_word0 = st.tint_word0;
-    std::vector<int> &small_tints = st.small_tints;
-    tints.assign((size_t)T, TintDesc()); row_tint.assign((size_t)R, 0); tint_word0.assign((size_t)T + 1, 0);
-    const char *lds_env = getenv("FCLU_PRUNE_LDS");
-    const bool lds_ok = !(lds_env && lds_env[0] == '0');
-    const char *ldsw_env = getenv("FCLU_PRUNE_LDS_WORDS");                // (tests: a lower limit, so that small tints take both ways in one batch)
-    const i64 lds_words = (ldsw_env && atoll(ldsw_env) > 0 && atoll(ldsw_env) < kPruneLdsWords) ? atoll(ldsw_env) : kPruneLdsWords;
-    size_t small_lds = 0;
-    bool any_large = false;
-    int max_w = 1, max_aw_large = 0;
-    for (int t = 0; t < T; ++t) {
-        TintDesc &d = tints[(size_t)t];
-        d.row0 = row_off[t];
-        const i64 n = row_off[t + 1] - d.row0;
-        if (n < 0 || n > (1 << 30) || n_seg[t] < 0) return fail(c, FCLU_ERR_ARG, "tint %d: bad row count or segment count", t);
-        d.n = (int)n; d.n_seg = n_seg[t];
-        d.w = (d.n_seg + 31) / 32; if (d.w < 1) d.w = 1;
-        d.aw = (d.n + 63) / 64;
-        d.bits_off = bits_off[t]; d.adj_off = adj_off[t];
-        d.in_lds = (prune && lds_ok && d.n > 0 && d.n <= 65535 && (i64)d.n * d.aw <= lds_words) ? 1 : 0;
-        d.cc_lds = cc_in_lds(d.n, d.aw);
-        if (d.in_lds) { small_tints.push_back(t); small_lds = std::max(small_lds, ((size_t)2 * d.n * d.aw + d.aw) * 8 + (size_t)d.n * 2 + 16); }
-        else if (d.n > 0) { any_large = true; max_aw_large = std::max(max_aw_large, d.aw); }
-        if (bits_off[t + 1] - d.bits_off != (i64)d.n * d.w) return fail(c, FCLU_ERR_ARG, "tint %d: bits_off does not match rows x words", t);
-        if (adj_off[t + 1] - d.adj_off != (i64)d.n * d.aw) return fail(c, FCLU_ERR_ARG, "tint %d: adj_off does not match rows x words", t);
-        if (d.w > kMaxWords) return fail(c, FCLU_ERR_UNSUPPORTED, "tint %d has %d segments; this build stages at most %d", t, d.n_seg, kMaxWords * 32);
-        if (d.w > max_w) max_w = d.w;
-        for (i64 r = 0; r < n; ++r) {
-            row_tint[(size_t)(d.row0 + r)] = t;
-            if (!b) continue;
-            const int f = b->first[d.row0 + r], l = b->last[d.row0 + r];
-            if (f < -1 || l >= (d.n_seg > 0 ? d.n_seg : 1) || b->tail[d.row0 + r] > 2) return fail(c, FCLU_ERR_ARG, "tint %d read %lld: first/last/tail out of range", t, r);
-            // a read's bits lie inside [first, last] (first / last ARE its first and last covered segment, :175-183): k_compat counts on it
-            const uint32_t *rw = b->bits + d.bits_off + r * d.w;
-            for (int w = 0; w < d.w; ++w) {
-                uint32_t allowed = 0;
-                if (f >= 0 && l >= f && w >= (f >> 5) && w <= (l >> 5)) {
-                    allowed = 0xffffffffu;
-                    if (w == (f >> 5)) allowed &= 0xffffffffu << (f & 31);
-                    if (w == (l >> 5)) allowed &= 0xffffffffu >> (31 - (l & 31));
-                }
-                if (rw[w] & ~allowed) return fail(c, FCLU_ERR_ARG, "tint %d read %lld: a covered segment outside [first, last]", t, r);
-            }
-        }
-        for (int ti = 0; ti < d.aw; ++ti) for (int tj = ti; tj < d.aw; ++tj) tiles.push_back(make_int4(t, ti, tj, 0));   // (on and above the diagonal)
-        for (int z = 0; z < d.aw; ++z) word_tint.push_back(make_int2(t, z));
-        tint_word0[(size_t)t + 1] = (i64)word_tint.size();
-    }
-    const i64 n_bits = bits_off[T], n_adj = adj_off[T];
-    const int n_tiles = (int)tiles.size();
-    st.T = T; st.R = R; st.n_bits = n_bits; st.n_adj = n_adj; st.n_tiles = n_tiles; st.max_w = max_w; st.max_aw_large = max_aw_large;
-    st.any_large = any_large; st.small_lds = small_lds; st.n_words = (int)word_tint.size();
-    c->compat_ms = c->prune_ms = 0.f;
-    c->h_tints = tints;
-    c->adj_cur = 0;
-    st.empty = n_tiles == 0 || R == 0;
-    if (st.empty) return FCLU_OK;
-
-    GrowBuf &d_tints = c->tints, &d_tiles = c->tiles, &d_row_tint = c->row_tint, &d_bits = c->bits, &d_first = c->first, &d_last = c->last,
-            &d_tail = c->tail, &d_deg = c->deg, &d_changed = c->changed, &d_word_tint = c->word_tint, &d_tint_word0 = c->tint_word0,
-            &d_deg1 = c->deg1, &d_pass_any = c->pass_any;
-    GrowBuf *d_adj = c->adj;
-    HIP_TRY(c, grow(d_tints, tints.size() * sizeof(TintDesc)));
-    HIP_TRY(c, grow(d_tiles, tiles.size() * sizeof(int4)));
-    HIP_TRY(c, grow(d_row_tint, (size_t)R * 4));
-    HIP_TRY(c, grow(d_bits, (size_t)n_bits * 4));
-    HIP_TRY(c, grow(d_first, (size_t)R * 4));
-    HIP_TRY(c, grow(d_last, (size_t)R * 4));
-    HIP_TRY(c, grow(d_tail, (size_t)R));
-    HIP_TRY(c, grow(d_adj[0], (size_t)n_adj * 8));
-    HIP_TRY(c, grow(d_adj[1], (size_t)n_adj * 8));
-    HIP_TRY(c, grow(d_deg, (size_t)R * 4));
-    HIP_TRY(c, grow(d_changed, (size_t)kBurst * T * 4));
-    HIP_TRY(c, grow(d_word_tint, word_tint.size() * sizeof(int2)));
-    HIP_TRY(c, grow(d_tint_word0, tint_word0.size() * 8));
-    HIP_TRY(c, grow(d_deg1, word_tint.size() * 8));
-    HIP_TRY(c, grow(d_pass_any, (size_t)kBurst * 4));
-    HIP_TRY(c, grow(c->small_tints, small_tints.size() * 4 + 4));
-    HIP_TRY(c, grow(c->small_rounds, (size_t)T * 4));
-    {
-        const size_t need = ((size_t)kBurst * T + kBurst) * 4;
-        if (need > c->h_flags_cap) {
-            if (c->h_flags) HIP_TRY(c, hipHostFree(c->h_flags));
-            c->h_flags = nullptr; c->h_flags_cap = 0;
-            HIP_TRY(c, hipHostMalloc((void **)&c->h_flags, need + need / 4, hipHostMallocDefault));
-            c->h_flags_cap = need + need / 4;
-        }
-    }
-    hipStream_t s = c->stream;
-    HIP_TRY(c, hipMemcpyAsync(d_tints.p, tints.data(), tints.size() * sizeof(TintDesc), hipMemcpyHostToDevice, s));
-    HIP_TRY(c, hipMemcpyAsync(d_tiles.p, tiles.data(), tiles.size() * sizeof(int4), hipMemcpyHostToDevice, s));
-    HIP_TRY(c, hipMemcpyAsync(d_row_tint.p, row_tint.data(), (size_t)R * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(c, hipMemcpyAsync(d_word_tint.p, word_tint.data(), word_tint.size() * sizeof(int2), hipMemcpyHostToDevice, s));
-    HIP_TRY(c, hipMemcpyAsync(d_tint_word0.p, tint_word0.data(), tint_word0.size() * 8, hipMemcpyHostToDevice, s));
-    return FCLU_OK;
-}
-
-// The graph of a staged batch whose rows (c->bits / first / last / tail) are on the device: compatibility, then pruning.  The pruned
-// matrix stays on the device in c->adj[c->adj_cur] (with the tints' descriptors in c->tints / c->h_tints and c->row_tint) for
-// partition_device(); adj_out may be null.
-int compat_run(fclu_ctx *c, const Staged &st, int32_t prune, uint64_t *adj_out, int32_t *rounds_out) {
-    const int T = st.T, n_tiles = st.n_tiles, max_w = st.max_w, max_aw_large = st.max_aw_large;
-    const i64 R = st.R, n_adj = st.n_adj;
-    const bool any_large = st.any_large;
-    const std::vector<int> &small_tints = st.small_tints;
-    const size_t small_lds = st.small_lds;
-    GrowBuf &d_tints = c->tints, &d_tiles = c->tiles, &d_row_tint = c->row_tint, &d_bits = c->bits, &d_first = c->first, &d_last = c->last,
-            &d_tail = c->tail, &d_deg = c->deg, &d_changed = c->changed, &d_word_tint = c->word_tint, &d_tint_word0 = c->tint_word0,
-            &d_deg1 = c->deg1, &d_pass_any = c->pass_any;
-    GrowBuf *d_adj = c->adj;
-    hipStream_t s = c->stream;
-
-    const int grid = n_tiles < 8192 ? n_tiles : 8192;
-    // rows of at most kRankWords words: the rank tables ride along (FCLU_RANK=0 keeps the masked sums: tests)
-    const char *rank_env = getenv("FCLU_RANK");
-    const bool rank = max_w <= kRankWords && !(rank_env && rank_env[0] == '0');
-    const size_t lds = (size_t)2 * kTile * (max_w | 1) * (rank ? 6 : 4);
-    HIP_TRY(c, hipEventRecord(c->ev[0], s));
-    if (rank)
-        hipLaunchKernelGGL(k_compat<true>, dim3(grid), dim3(256), lds, s, n_tiles, d_tiles.as<int4>(), d_tints.as<TintDesc>(),
-                           d_bits.as<unsigned>(), d_first.as<int>(), d_last.as<int>(), d_tail.as<unsigned char>(), d_adj[0].as<u64>());
-    else
-        hipLaunchKernelGGL(k_compat<false>, dim3(grid), dim3(256), lds, s, n_tiles, d_tiles.as<int4>(), d_tints.as<TintDesc>(),
-                           d_bits.as<unsigned>(), d_first.as<int>(), d_last.as<int>(), d_tail.as<unsigned char>(), d_adj[0].as<u64>());
-    HIP_TRY(c, hipEventRecord(c->ev[1], s));
-    int cur = 0;
-    if (prune && !small_tints.empty()) {
-        // (the final matrix of such a tint goes into BOTH copies: whichever the per-pass kernels of the large tints end on holds it)
-        HIP_TRY(c, hipMemcpyAsync(c->small_tints.p, small_tints.data(), small_tints.size() * 4, hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(k_prune_lds, dim3((unsigned)small_tints.size()), dim3(256), small_lds, s, c->small_tints.as<int>(), d_tints.as<TintDesc>(),
-                           d_adj[0].as<u64>(), d_adj[1].as<u64>(), c->small_rounds.as<int>());
-    }
-    if (prune && any_large) {
-        // Passes are enqueued kBurst at a time; pass q of a burst is gated on pass q-1's "removed something" word, so the host
-        // reads the flags once per burst instead of once per pass (the loop of :240-255 usually ends after two or three).
-        const int deg_grid = (int)((R + 3) / 4 < 4096 ? (R + 3) / 4 : 4096);
-        // the pass edge by edge (k_prune_edges) when every tint of the per-pass kernels has rows of at most kEdgeChunks x 64 words;
-        // FCLU_PRUNE_EDGES=0: the OR-of-rows form whatever the shapes (tests)
-        const char *edge_env = getenv("FCLU_PRUNE_EDGES");
-        const bool edge_walk = max_aw_large <= kEdgeChunks * 64 && !(edge_env && edge_env[0] == '0');
-        const int edge_chunks = (max_aw_large + 63) / 64 > 0 ? (max_aw_large + 63) / 64 : 1;
-        const int n_words = st.n_words;
-        int *h_any = c->h_flags, *h_changed = c->h_flags + kBurst;
-        bool done = false;
-        for (int burst = 0; burst < (1 << 18) && !done; ++burst) {
-            HIP_TRY(c, hipMemsetAsync(d_changed.p, 0, (size_t)kBurst * T * 4, s));
-            HIP_TRY(c, hipMemsetAsync(d_pass_any.p, 0, (size_t)kBurst * 4, s));
-            for (int q = 0; q < kBurst; ++q) {
-                const int *gate = q ? d_pass_any.as<int>() + (q - 1) : nullptr;
-                const int from = cur ^ (q & 1), to = from ^ 1;
-                hipLaunchKernelGGL(k_degree, dim3(deg_grid), dim3(256), 0, s, R, d_row_tint.as<int>(), d_tints.as<TintDesc>(),
-                                   d_adj[from].as<u64>(), d_deg.as<int>(), gate);
-                if (edge_walk)
-                    hipLaunchKernelGGL(k_prune_edges, dim3((int)((R * edge_chunks + 3) / 4 < 65536 ? (R * edge_chunks + 3) / 4 : 65536)), dim3(256), 0, s, R, edge_chunks,
-                                       d_row_tint.as<int>(), d_tints.as<TintDesc>(), d_adj[from].as<u64>(), d_deg.as<int>(), d_adj[to].as<u64>(),
-                                       d_changed.as<int>() + (size_t)q * T, d_pass_any.as<int>() + q, gate);
-                else {
-                hipLaunchKernelGGL(k_deg1, dim3((n_words + 3) / 4 < 4096 ? (n_words + 3) / 4 : 4096), dim3(256), 0, s, n_words,
-                                   d_word_tint.as<int2>(), d_tints.as<TintDesc>(), d_deg.as<int>(), d_deg1.as<u64>(), gate);
-                hipLaunchKernelGGL(k_prune, dim3((int)((R + 3) / 4 < 16384 ? (R + 3) / 4 : 16384)), dim3(256), 0, s, R, d_row_tint.as<int>(),
-                                   d_tints.as<TintDesc>(), d_tint_word0.as<i64>(), d_adj[from].as<u64>(), d_deg.as<int>(),
-                                   d_deg1.as<u64>(), d_adj[to].as<u64>(), d_changed.as<int>() + (size_t)q * T, d_pass_any.as<int>() + q, gate);
-                }
-            }
-            HIP_TRY(c, hipMemcpyAsync(h_any, d_pass_any.p, (size_t)kBurst * 4, hipMemcpyDeviceToHost, s));
-            HIP_TRY(c, hipMemcpyAsync(h_changed, d_changed.p, (size_t)kBurst * T * 4, hipMemcpyDeviceToHost, s));
-            HIP_TRY(c, hipStreamSynchronize(s));
-            // the passes that ran: 0 .. first pass that removed nothing (inclusive); each of them wrote the other buffer
-            int ran = 0;
-            for (int q = 0; q < kBurst; ++q) { ++ran; if (!h_any[q]) { done = true; break; } }
-            for (int q = 0; q < ran; ++q)
-                if (rounds_out) for (int t = 0; t < T; ++t) if (h_changed[(size_t)q * T + t]) rounds_out[t] += 1;
-            cur ^= ran & 1;
-        }
-    }
-    HIP_TRY(c, hipEventRecord(c->ev[2], s));
-    c->adj_cur = cur;
-    if (adj_out) HIP_TRY(c, hipMemcpyAsync(adj_out, d_adj[cur].p, (size_t)n_adj * 8, hipMemcpyDeviceToHost, s));
-    std::vector<int> small_rounds;
-    if (prune && rounds_out && !small_tints.empty()) {
-        small_rounds.resize((size_t)T);
-        HIP_TRY(c, hipMemcpyAsync(small_rounds.data(), c->small_rounds.p, (size_t)T * 4, hipMemcpyDeviceToHost, s));
-    }
-    HIP_TRY(c, hipStreamSynchronize(s));
-    if (!small_rounds.empty()) for (int t : small_tints) rounds_out[t] = small_rounds[(size_t)t];
-    HIP_TRY(c, hipGetLastError());
-    (void)hipEventElapsedTime(&c->compat_ms, c->ev[0], c->ev[1]);
-    (void)hipEventElapsedTime(&c->prune_ms, c->ev[1], c->ev[2]);
-    return FCLU_OK;
-}
-
-// The graph of a batch of the caller's rows: staging with every check, the rows' upload, the kernels.
-int compat_device(fclu_ctx *c, const fclu_batch *b, int32_t prune, uint64_t *adj_out, int32_t *rounds_out) {
-    if (b->n_tint <= 0) return fail(c, FCLU_ERR_ARG, "fclu_compat_graph: empty batch");
-    Staged st;
-    const int rc = stage_tints(c, b->n_tint, b->row_off, b->n_seg, b->bits_off, b->adj_off, prune, b, st);
-    if (rc != FCLU_OK) return rc;
-    if (rounds_out) for (int t = 0; t < st.T; ++t) rounds_out[t] = 0;
-    if (st.empty) return FCLU_OK;
-    hipStream_t s = c->stream;
-    HIP_TRY(c, hipMemcpyAsync(c->bits.p, b->bits, (size_t)st.n_bits * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(c, hipMemcpyAsync(c->first.p, b->first, (size_t)st.R * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(c, hipMemcpyAsync(c->last.p, b->last, (size_t)st.R * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(c, hipMemcpyAsync(c->tail.p, b->tail, (size_t)st.R, hipMemcpyHostToDevice, s));
-    return compat_run(c, st, prune, adj_out, rounds_out);
-}
-
-
-// ---- partition_reads() behind the graph (:256-274) ---------------------------------------------------------------
-int check_members(fclu_ctx *c, i64 R, const int64_t *mem_off, const int32_t *mem, int32_t maximum_ilp_size) {
-    if (maximum_ilp_size < 1) return fail(c, FCLU_ERR_ARG, "maximum_ilp_size is %d: it must be at least 1", (int)maximum_ilp_size);
-    if (R < 0 || R >= (1ll << 31)) return fail(c, FCLU_ERR_ARG, "bad row count %lld", R);
-    if (!mem_off) return fail(c, FCLU_ERR_ARG, "mem_off is null");
-    if (mem_off[0] != 0) return fail(c, FCLU_ERR_ARG, "mem_off[0] is %lld, not 0", (i64)mem_off[0]);
-    for (i64 r = 0; r < R; ++r)
-        if (mem_off[r + 1] < mem_off[r]) return fail(c, FCLU_ERR_ARG, "mem_off is not monotone at row %lld (%lld after %lld)", r, (i64)mem_off[r + 1], (i64)mem_off[r]);
-    if (mem_off[R] > 0 && !mem) return fail(c, FCLU_ERR_ARG, "mem is null");
-    return FCLU_OK;
-}
-
-hipError_t grow_host(HostBuf &b, size_t bytes) {
-    if (b.p && bytes <= b.cap) return hipSuccess;
-    if (b.p) { hipError_t e = hipHostFree(b.p); b.p = nullptr; b.cap = 0; if (e != hipSuccess) return e; }
-    const size_t want = (bytes ? bytes : 16) + bytes / 4;
-    hipError_t e = hipHostMalloc(&b.p, want, hipHostMallocDefault);
-    if (e == hipSuccess) b.cap = want;
-    return e;
-}
-
-int bits_for(i64 n) { int b = 1; while (b < 32 && (1ll << b) < n) ++b; return b; }
-
-// c->tints / c->h_tints / c->row_tint describe the batch and c->adj[c->adj_cur] holds its pruned matrices.  mem_off null: the members
-// are on the device already (c->mem_off, c->mem: n_mem_device rep ids), where the dedupe left them.
-int partition_device(fclu_ctx *c, int T, i64 R, const int64_t *mem_off, const int32_t *mem, i64 n_mem_device, int32_t maximum_ilp_size) {
-    HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t s = c->stream;
-    c->components_ms = c->pairs_ms = 0.f;
-    fclu_parts &out = c->parts;
-    HIP_TRY(c, grow_host(c->h_tint_part_off, (size_t)(T + 1) * 8));
-    if (R == 0) {                                            // nothing but empty tints
-        HIP_TRY(c, grow_host(c->h_part_node_off, 8)); HIP_TRY(c, grow_host(c->h_part_rid_off, 8)); HIP_TRY(c, grow_host(c->h_part_pair_off, 8));
-        HIP_TRY(c, grow_host(c->h_part_nodes, 0)); HIP_TRY(c, grow_host(c->h_part_rids, 0)); HIP_TRY(c, grow_host(c->h_pairs, 0)); HIP_TRY(c, grow_host(c->h_label, 0));
-        memset(c->h_tint_part_off.p, 0, (size_t)(T + 1) * 8);
-        *c->h_part_node_off.as<i64>() = *c->h_part_rid_off.as<i64>() = *c->h_part_pair_off.as<i64>() = 0;
-        out.n_tint = T; out.n_rows = out.n_part = out.n_rids = out.n_pairs = 0;
-    } else {
-        const u64 *d_adj = c->adj[c->adj_cur].as<u64>();
-        const TintDesc *d_tints = c->tints.as<TintDesc>();
-        const int *d_row_tint = c->row_tint.as<int>();
-        const i64 n_mem = mem_off ? mem_off[R] : n_mem_device;
-        std::vector<int> small;
-        size_t small_lds = 0;
-        bool any_large = false;
-        for (int t = 0; t < T; ++t) {
-            const TintDesc &d = c->h_tints[(size_t)t];
-            if (d.cc_lds) { small.push_back(t); small_lds = std::max(small_lds, (size_t)d.n * d.aw * 8 + (size_t)d.n * 4); }
-            else if (d.n > 0) any_large = true;
-        }
-        const size_t R1 = (size_t)R + 1;
-        HIP_TRY(c, grow(c->parent, (size_t)R * 4)); HIP_TRY(c, grow(c->skey, (size_t)R * 4));
-        HIP_TRY(c, grow(c->rows, (size_t)R * 4)); HIP_TRY(c, grow(c->sval, (size_t)R * 4));
-        HIP_TRY(c, grow(c->comp_start, (size_t)R * 4)); HIP_TRY(c, grow(c->comp_end, (size_t)R * 4)); HIP_TRY(c, grow(c->chunk_end, (size_t)R * 4));
-        HIP_TRY(c, grow(c->head, R1 * 8)); HIP_TRY(c, grow(c->part_id, R1 * 8)); HIP_TRY(c, grow(c->smult, R1 * 8)); HIP_TRY(c, grow(c->rid_pos, R1 * 8));
-        HIP_TRY(c, grow(c->cnt, R1 * 8)); HIP_TRY(c, grow(c->pair_base, R1 * 8));
-        HIP_TRY(c, grow(c->d_label, (size_t)R * 4)); HIP_TRY(c, grow(c->d_nodes, (size_t)R * 4));
-        HIP_TRY(c, grow(c->d_tint_part_off, (size_t)(T + 1) * 8)); HIP_TRY(c, grow(c->d_part_node_off, R1 * 8));
-        HIP_TRY(c, grow(c->d_part_rid_off, R1 * 8)); HIP_TRY(c, grow(c->d_part_pair_off, R1 * 8));
-        HIP_TRY(c, grow(c->mem_off, R1 * 8)); HIP_TRY(c, grow(c->mem, (size_t)n_mem * 4)); HIP_TRY(c, grow(c->d_part_rids, (size_t)n_mem * 4));
-        HIP_TRY(c, grow(c->small_tints, small.size() * 4 + 4));
-        HIP_TRY(c, grow(c->pass_any, (size_t)kBurst * 4));
-        HIP_TRY(c, grow_host(c->h_cc_flags, (size_t)kBurst * 4 + 16));
-        const int end_bit = bits_for(R);
-        size_t sort_bytes = 0, scan_bytes = 0;
-        HIP_TRY(c, rocprim::radix_sort_pairs(nullptr, sort_bytes, c->parent.as<unsigned>(), c->skey.as<unsigned>(), c->rows.as<int>(), c->sval.as<int>(),
-                                             (size_t)R, 0u, (unsigned)end_bit, s));
-        HIP_TRY(c, rocprim::exclusive_scan(nullptr, scan_bytes, c->head.as<i64>(), c->part_id.as<i64>(), (i64)0, R1, rocprim::plus<i64>(), s));
-        const size_t tmp_bytes = std::max(sort_bytes, scan_bytes);
-        HIP_TRY(c, grow(c->tmp, tmp_bytes));
-        if (mem_off) {
-            HIP_TRY(c, hipMemcpyAsync(c->mem_off.p, mem_off, R1 * 8, hipMemcpyHostToDevice, s));
-            if (n_mem) HIP_TRY(c, hipMemcpyAsync(c->mem.p, mem, (size_t)n_mem * 4, hipMemcpyHostToDevice, s));
-        }
-        if (!small.empty()) HIP_TRY(c, hipMemcpyAsync(c->small_tints.p, small.data(), small.size() * 4, hipMemcpyHostToDevice, s));
-
-        const int row_grid = (int)std::min<i64>((R + 256) / 256, 4096), wave_grid = (int)std::min<i64>((R + 3) / 4, 65536);
-        int *d_parent = c->parent.as<int>();
-        // ---- components
-        HIP_TRY(c, hipEventRecord(c->pev[0], s));
-        hipLaunchKernelGGL(k_cc_init, dim3(row_grid), dim3(256), 0, s, R, d_parent);
-        hipLaunchKernelGGL(k_cc_init, dim3(row_grid), dim3(256), 0, s, R, c->rows.as<int>());     // (the sort's values: the rows themselves)
-        if (!small.empty())
-            hipLaunchKernelGGL(k_cc_lds, dim3((unsigned)small.size()), dim3(256), small_lds, s, c->small_tints.as<int>(), d_tints, d_adj, d_parent);
-        if (any_large) {
-            // as in the pruning: kBurst passes per host round trip, pass q gated on pass q - 1's "something changed" word
-            int *h_any = c->h_cc_flags.as<int>(), *d_any = c->pass_any.as<int>();
-            bool done = false;
-            for (int burst = 0; !done; ++burst) {
-                if (burst >= (1 << 16)) return fail(c, FCLU_ERR_HIP, "connected components did not converge");
-                HIP_TRY(c, hipMemsetAsync(d_any, 0, (size_t)kBurst * 4, s));
-                for (int q = 0; q < kBurst; ++q) {
-                    const int *gate = q ? d_any + (q - 1) : nullptr;
-                    hipLaunchKernelGGL(k_cc_hook, dim3(wave_grid), dim3(256), 0, s, R, d_row_tint, d_tints, d_adj, d_parent, d_any + q, gate);
-                    hipLaunchKernelGGL(k_cc_jump, dim3(row_grid), dim3(256), 0, s, R, d_row_tint, d_tints, d_parent, d_any + q, gate);
-                }
-                HIP_TRY(c, hipMemcpyAsync(h_any, d_any, (size_t)kBurst * 4, hipMemcpyDeviceToHost, s));
-                HIP_TRY(c, hipStreamSynchronize(s));
-                for (int q = 0; q < kBurst; ++q) if (!h_any[q]) { done = true; break; }
-            }
-        }
-        HIP_TRY(c, hipEventRecord(c->pev[1], s));
-        // ---- even split, members' positions, pair counts
-        HIP_TRY(c, rocprim::radix_sort_pairs(c->tmp.p, sort_bytes, c->parent.as<unsigned>(), c->skey.as<unsigned>(), c->rows.as<int>(), c->sval.as<int>(),
-                                             (size_t)R, 0u, (unsigned)end_bit, s));
-        hipLaunchKernelGGL(k_bounds, dim3(row_grid), dim3(256), 0, s, R, c->skey.as<unsigned>(), c->comp_start.as<int>(), c->comp_end.as<int>());
-        hipLaunchKernelGGL(k_chunk, dim3(row_grid), dim3(256), 0, s, R, (i64)maximum_ilp_size, c->skey.as<unsigned>(), c->sval.as<int>(), c->comp_start.as<int>(),
-                           c->comp_end.as<int>(), c->mem_off.as<i64>(), d_row_tint, d_tints, d_parent, c->head.as<i64>(), c->chunk_end.as<int>(),
-                           c->smult.as<i64>(), c->d_label.as<int>(), c->d_nodes.as<int>());
-        size_t sb = scan_bytes;
-        HIP_TRY(c, rocprim::exclusive_scan(c->tmp.p, sb, c->head.as<i64>(), c->part_id.as<i64>(), (i64)0, R1, rocprim::plus<i64>(), s));
-        sb = scan_bytes;
-        HIP_TRY(c, rocprim::exclusive_scan(c->tmp.p, sb, c->smult.as<i64>(), c->rid_pos.as<i64>(), (i64)0, R1, rocprim::plus<i64>(), s));
-        HIP_TRY(c, hipMemsetAsync(c->cnt.as<i64>() + R, 0, 8, s));
-        HIP_TRY(c, hipEventRecord(c->pev[2], s));
-        hipLaunchKernelGGL(k_pairs<false>, dim3(wave_grid), dim3(256), 0, s, R, c->sval.as<int>(), c->chunk_end.as<int>(), c->smult.as<i64>(), d_row_tint, d_tints,
-                           d_adj, c->cnt.as<i64>(), (const i64 *)nullptr, c->mem_off.as<i64>(), c->mem.as<int>(), (int2 *)nullptr);
-        HIP_TRY(c, hipEventRecord(c->pev[3], s));
-        sb = scan_bytes;
-        HIP_TRY(c, rocprim::exclusive_scan(c->tmp.p, sb, c->cnt.as<i64>(), c->pair_base.as<i64>(), (i64)0, R1, rocprim::plus<i64>(), s));
-        const i64 RT = std::max<i64>(R, T);
-        hipLaunchKernelGGL(k_offsets, dim3((int)std::min<i64>((RT + 256) / 256, 4096)), dim3(256), 0, s, R, T, d_tints, c->head.as<i64>(), c->part_id.as<i64>(),
-                           c->rid_pos.as<i64>(), c->pair_base.as<i64>(), c->d_tint_part_off.as<i64>(), c->d_part_node_off.as<i64>(),
-                           c->d_part_rid_off.as<i64>(), c->d_part_pair_off.as<i64>());
-        i64 *h_tot = reinterpret_cast<i64 *>(c->h_cc_flags.as<int>() + kBurst);            // {partitions, pairs}
-        HIP_TRY(c, hipMemcpyAsync(h_tot, c->part_id.as<i64>() + R, 8, hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipMemcpyAsync(h_tot + 1, c->pair_base.as<i64>() + R, 8, hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipStreamSynchronize(s));
-        HIP_TRY(c, hipGetLastError());
-        const i64 P = h_tot[0], n_pairs = h_tot[1];
-        if (P < 0 || P > R || n_pairs < 0) return fail(c, FCLU_ERR_HIP, "partition totals out of range (%lld partitions, %lld pairs)", P, n_pairs);
-        // ---- the pair list: as large as the graphs make it
-        if (n_pairs > 2147483647ll)
-            return fail(c, FCLU_ERR_UNSUPPORTED, "%lld incompatible pairs in this batch: more than the 2147483647 a call returns", n_pairs);
-        if ((size_t)n_pairs * 8 > c->d_pairs.cap) {
-            if (c->d_pairs.p) { HIP_TRY(c, hipFree(c->d_pairs.p)); c->d_pairs.p = nullptr; c->d_pairs.cap = 0; }
-            size_t free_b = 0, total_b = 0;
-            HIP_TRY(c, hipMemGetInfo(&free_b, &total_b));
-            if ((size_t)n_pairs * 8 + (64u << 20) > free_b)
-                return fail(c, FCLU_ERR_UNSUPPORTED, "%lld incompatible pairs in this batch (%lld bytes) do not fit the device's free memory (%lld bytes)",
-                            n_pairs, n_pairs * 8, (i64)free_b);
-            if (hipMalloc(&c->d_pairs.p, (size_t)n_pairs * 8) != hipSuccess) {
-                (void)hipGetLastError(); c->d_pairs.p = nullptr;
-                return fail(c, FCLU_ERR_UNSUPPORTED, "%lld incompatible pairs in this batch: no device memory for %lld bytes", n_pairs, n_pairs * 8);
-            }
-            c->d_pairs.cap = (size_t)n_pairs * 8;
-        }
-        if ((size_t)n_pairs * 8 > c->h_pairs.cap || !c->h_pairs.p) {
-            if (c->h_pairs.p) { HIP_TRY(c, hipHostFree(c->h_pairs.p)); c->h_pairs.p = nullptr; c->h_pairs.cap = 0; }
-            const size_t want = std::max<size_t>((size_t)n_pairs * 8, 16);
-            if (hipHostMalloc(&c->h_pairs.p, want, hipHostMallocDefault) != hipSuccess) {
-                (void)hipGetLastError(); c->h_pairs.p = nullptr;
-                return fail(c, FCLU_ERR_UNSUPPORTED, "%lld incompatible pairs in this batch: no pinned host memory for %lld bytes", n_pairs, n_pairs * 8);
-            }
-            c->h_pairs.cap = want;
-        }
-        HIP_TRY(c, grow_host(c->h_part_node_off, (size_t)(P + 1) * 8)); HIP_TRY(c, grow_host(c->h_part_rid_off, (size_t)(P + 1) * 8));
-        HIP_TRY(c, grow_host(c->h_part_pair_off, (size_t)(P + 1) * 8));
-        HIP_TRY(c, grow_host(c->h_part_nodes, (size_t)R * 4)); HIP_TRY(c, grow_host(c->h_label, (size_t)R * 4)); HIP_TRY(c, grow_host(c->h_part_rids, (size_t)n_mem * 4));
-        HIP_TRY(c, hipEventRecord(c->pev[4], s));
-        if (n_pairs)
-            hipLaunchKernelGGL(k_pairs<true>, dim3(wave_grid), dim3(256), 0, s, R, c->sval.as<int>(), c->chunk_end.as<int>(), c->smult.as<i64>(), d_row_tint, d_tints,
-                               d_adj, (i64 *)nullptr, c->pair_base.as<i64>(), c->mem_off.as<i64>(), c->mem.as<int>(), c->d_pairs.as<int2>());
-        if (n_mem)
-            hipLaunchKernelGGL(k_members, dim3(wave_grid), dim3(256), 0, s, R, c->sval.as<int>(), c->smult.as<i64>(), c->rid_pos.as<i64>(), c->mem_off.as<i64>(),
-                               c->mem.as<int>(), c->d_part_rids.as<int>());
-        HIP_TRY(c, hipEventRecord(c->pev[5], s));
-        HIP_TRY(c, hipMemcpyAsync(c->h_tint_part_off.p, c->d_tint_part_off.p, (size_t)(T + 1) * 8, hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipMemcpyAsync(c->h_part_node_off.p, c->d_part_node_off.p, (size_t)(P + 1) * 8, hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipMemcpyAsync(c->h_part_rid_off.p, c->d_part_rid_off.p, (size_t)(P + 1) * 8, hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipMemcpyAsync(c->h_part_pair_off.p, c->d_part_pair_off.p, (size_t)(P + 1) * 8, hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipMemcpyAsync(c->h_part_nodes.p, c->d_nodes.p, (size_t)R * 4, hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipMemcpyAsync(c->h_label.p, c->d_label.p, (size_t)R * 4, hipMemcpyDeviceToHost, s));
-        if (n_mem) HIP_TRY(c, hipMemcpyAsync(c->h_part_rids.p, c->d_part_rids.p, (size_t)n_mem * 4, hipMemcpyDeviceToHost, s));
-        if (n_pairs) HIP_TRY(c, hipMemcpyAsync(c->h_pairs.p, c->d_pairs.p, (size_t)n_pairs * 8, hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipStreamSynchronize(s));
-        HIP_TRY(c, hipGetLastError());
-        float a = 0.f, b = 0.f;
-        (void)hipEventElapsedTime(&c->components_ms, c->pev[0], c->pev[1]);
-        (void)hipEventElapsedTime(&a, c->pev[2], c->pev[3]);
-        (void)hipEventElapsedTime(&b, c->pev[4], c->pev[5]);
-        c->pairs_ms = a + b;
-        out.n_tint = T; out.n_rows = R; out.n_part = P; out.n_rids = n_mem; out.n_pairs = n_pairs;
-    }
-    out.tint_part_off = c->h_tint_part_off.as<int64_t>();
-    out.part_node_off = c->h_part_node_off.as<int64_t>(); out.part_nodes = c->h_part_nodes.as<int32_t>();
-    out.part_rid_off = c->h_part_rid_off.as<int64_t>(); out.part_rids = c->h_part_rids.as<int32_t>();
-    out.part_pair_off = c->h_part_pair_off.as<int64_t>(); out.pairs = c->h_pairs.as<int32_t>();
-    out.label = c->h_label.as<int32_t>();
-    c->have_parts = true;
-    return FCLU_OK;
-}
-
-
-// ---- preprocess_ilp() + the dedupe of a batch of label rows ----------------------------------------------------------
-enum { P_TINTS, P_LABELS, P_TAIL, P_IBITS, P_CBITS, P_RFIRST, P_RLAST, P_FIRST, P_LAST, P_REP_TINT, P_KEY, P_SKEY, P_VAL, P_SVAL, P_HEAD,
-       P_BSTART, P_LEADER, P_FLAG, P_NODE_ID, P_ROW_OFF, P_REP_NODE, P_NODE_REP, P_NKEY, P_SNKEY, P_NVAL, P_ERR, P_TMP };
-enum { Q_ROW_OFF, Q_BITS_OFF, Q_ADJ_OFF, Q_RBITS_OFF, Q_IBITS, Q_CBITS, Q_FIRST, Q_LAST, Q_RFIRST, Q_RLAST, Q_REP_NODE, Q_NODE_REP, Q_MEM_OFF,
-       Q_MEM, Q_BITS, Q_NFIRST, Q_NLAST, Q_NTAIL, Q_ERR };
-
-// Rows, dedupe and the staging of the unique rows as a batch: behind it c->bits / first / last / tail hold the nodes in fclu_batch's
-// layout, c->mem_off / c->mem their members, st what compat_run() needs, and the pinned copies of everything are on their way (the
-// caller synchronises).  Between the two halves only row_off (n_tint + 1 counts) and the three error words come back to the host.
-int preprocess_device(fclu_ctx *c, const fclu_reads *rd, int32_t prune, Staged &st, i64 &n_reps_out) {
-    c->have_prep = false;
-    c->rows_ms = c->dedupe_ms = 0.f;
-    if (!rd || rd->n_tint <= 0) return fail(c, FCLU_ERR_ARG, "fclu_preprocess: empty batch");
-    if (!rd->rep_off || !rd->n_seg || !rd->lab_off) return fail(c, FCLU_ERR_ARG, "fclu_preprocess: rep_off, n_seg or lab_off is null");
-    HIP_TRY(c, hipSetDevice(c->device));
-    const int T = rd->n_tint;
-    if (rd->rep_off[0] != 0 || rd->lab_off[0] != 0) return fail(c, FCLU_ERR_ARG, "fclu_preprocess: rep_off and lab_off start at 0");
-    std::vector<PrepTint> pt((size_t)T);
-    std::vector<int64_t> rbits_off((size_t)T + 1, 0);
-    i64 n_slots = 0;
-    for (int t = 0; t < T; ++t) {
-        PrepTint &d = pt[(size_t)t];
-        const i64 n = rd->rep_off[t + 1] - rd->rep_off[t];
-        if (n < 0 || n > (1 << 30) || rd->n_seg[t] < 0)
-            return fail(c, FCLU_ERR_ARG, "tint %d: negative or too large rep count (%lld) or segment count (%d)", t, n, (int)rd->n_seg[t]);
-        if (rd->n_seg[t] > kMaxWords * 32)
-            return fail(c, FCLU_ERR_UNSUPPORTED, "tint %d has %d segments; this build stages at most %d", t, (int)rd->n_seg[t], kMaxWords * 32);
-        d.rep0 = rd->rep_off[t]; d.lab_off = rd->lab_off[t]; d.rbits_off = rbits_off[(size_t)t]; d.slot0 = n_slots;
-        d.n = (int)n; d.n_seg = rd->n_seg[t];
-        d.lw = std::max((d.n_seg + 15) / 16, 1); d.w = std::max((d.n_seg + 31) / 32, 1);
-        d.g_log2 = 0; while (d.g_log2 < 6 && (1 << d.g_log2) < d.w) ++d.g_log2;
-        if (rd->lab_off[t + 1] - d.lab_off != n * d.lw)
-            return fail(c, FCLU_ERR_ARG, "tint %d: lab_off does not match reps x words (%lld words for %lld reps of %d)", t,
-                        (i64)(rd->lab_off[t + 1] - d.lab_off), n, d.lw);
-        rbits_off[(size_t)t + 1] = d.rbits_off + n * d.w;
-        n_slots += ((n << d.g_log2) + 63) / 64 * 64;
-    }
-    const i64 N = rd->rep_off[T], n_lab = rd->lab_off[T], n_rbits = rbits_off[(size_t)T];
-    if (N >= 0x7f7f7f7fll) return fail(c, FCLU_ERR_ARG, "fclu_preprocess: %lld reps in one batch", N);
-    if (N > 0 && (!rd->labels || !rd->tail)) return fail(c, FCLU_ERR_ARG, "fclu_preprocess: labels or tail is null");
-    n_reps_out = N;
-    const char *hb_env = getenv("FCLU_HASH_BITS");           // (tests: a hash cut to n bits forces collisions; 0: one bucket a tint)
-    unsigned hash_mask = 0xffffffffu;
-    if (hb_env && hb_env[0] >= '0' && hb_env[0] <= '9' && atoi(hb_env) < 32) hash_mask = (1u << atoi(hb_env)) - 1u;
-
-    GrowBuf *D = c->pd;
-    HostBuf *H = c->ph;
-    hipStream_t s = c->stream;
-    const size_t N1 = (size_t)N + 1;
-    HIP_TRY(c, grow_host(H[Q_ROW_OFF], (size_t)(T + 1) * 8)); HIP_TRY(c, grow_host(H[Q_BITS_OFF], (size_t)(T + 1) * 8));
-    HIP_TRY(c, grow_host(H[Q_ADJ_OFF], (size_t)(T + 1) * 8)); HIP_TRY(c, grow_host(H[Q_RBITS_OFF], (size_t)(T + 1) * 8));
-    HIP_TRY(c, grow_host(H[Q_ERR], 16));
-    HIP_TRY(c, grow_host(H[Q_IBITS], (size_t)n_rbits * 4)); HIP_TRY(c, grow_host(H[Q_CBITS], (size_t)n_rbits * 4));
-    for (int q : {Q_FIRST, Q_LAST, Q_RFIRST, Q_RLAST, Q_REP_NODE, Q_MEM}) HIP_TRY(c, grow_host(H[q], (size_t)N * 4));
-    memcpy(H[Q_RBITS_OFF].p, rbits_off.data(), (size_t)(T + 1) * 8);
-    i64 *h_row_off = H[Q_ROW_OFF].as<i64>(), *h_bits_off = H[Q_BITS_OFF].as<i64>(), *h_adj_off = H[Q_ADJ_OFF].as<i64>();
-    int *h_err = H[Q_ERR].as<int>();
-    if (N > 0) {
-        HIP_TRY(c, grow(D[P_TINTS], pt.size() * sizeof(PrepTint)));
-        HIP_TRY(c, grow(D[P_LABELS], (size_t)n_lab * 4)); HIP_TRY(c, grow(D[P_TAIL], (size_t)N));
-        HIP_TRY(c, grow(D[P_IBITS], (size_t)n_rbits * 4)); HIP_TRY(c, grow(D[P_CBITS], (size_t)n_rbits * 4));
-        for (int q : {P_RFIRST, P_RLAST, P_FIRST, P_LAST, P_REP_TINT, P_VAL, P_SVAL, P_HEAD, P_BSTART, P_LEADER, P_REP_NODE, P_NODE_REP, P_NKEY, P_SNKEY, P_NVAL})
-            HIP_TRY(c, grow(D[q], (size_t)N * 4));
-        HIP_TRY(c, grow(D[P_FLAG], N1 * 4)); HIP_TRY(c, grow(D[P_NODE_ID], N1 * 4));
-        HIP_TRY(c, grow(D[P_KEY], (size_t)N * 8)); HIP_TRY(c, grow(D[P_SKEY], (size_t)N * 8));
-        HIP_TRY(c, grow(D[P_ROW_OFF], (size_t)(T + 1) * 8)); HIP_TRY(c, grow(D[P_ERR], 16));
-        HIP_TRY(c, grow(c->mem, (size_t)N * 4));
-        const unsigned key_bits = 32u + (unsigned)bits_for(T), node_bits = (unsigned)bits_for(N);
-        size_t sort_a = 0, sort_b = 0, scan_a = 0, scan_b = 0;
-        HIP_TRY(c, rocprim::radix_sort_pairs(nullptr, sort_a, D[P_KEY].as<u64>(), D[P_SKEY].as<u64>(), D[P_VAL].as<int>(), D[P_SVAL].as<int>(), (size_t)N, 0u, key_bits, s));
-        HIP_TRY(c, rocprim::radix_sort_pairs(nullptr, sort_b, D[P_NKEY].as<unsigned>(), D[P_SNKEY].as<unsigned>(), D[P_NVAL].as<int>(), c->mem.as<int>(), (size_t)N, 0u, node_bits, s));
-        HIP_TRY(c, rocprim::inclusive_scan(nullptr, scan_a, D[P_HEAD].as<int>(), D[P_BSTART].as<int>(), (size_t)N, rocprim::maximum<int>(), s));
-        HIP_TRY(c, rocprim::exclusive_scan(nullptr, scan_b, D[P_FLAG].as<int>(), D[P_NODE_ID].as<int>(), 0, N1, rocprim::plus<int>(), s));
-        const size_t tmp_bytes = std::max(std::max(sort_a, sort_b), std::max(scan_a, scan_b));
-        HIP_TRY(c, grow(D[P_TMP], tmp_bytes));
-        HIP_TRY(c, hipMemcpyAsync(D[P_TINTS].p, pt.data(), pt.size() * sizeof(PrepTint), hipMemcpyHostToDevice, s));
-        HIP_TRY(c, hipMemcpyAsync(D[P_LABELS].p, rd->labels, (size_t)n_lab * 4, hipMemcpyHostToDevice, s));
-        HIP_TRY(c, hipMemcpyAsync(D[P_TAIL].p, rd->tail, (size_t)N, hipMemcpyHostToDevice, s));
-        HIP_TRY(c, hipMemsetAsync(D[P_ERR].p, 0x7f, 16, s));
-        HIP_TRY(c, hipMemsetAsync(D[P_FLAG].as<int>() + N, 0, 4, s));
-        const int rep_grid = (int)std::min<i64>((N + 255) / 256, 4096);
-        const PrepTint *d_pt = D[P_TINTS].as<PrepTint>();
-        HIP_TRY(c, hipEventRecord(c->qev[0], s));
-        hipLaunchKernelGGL(k_rows, dim3((unsigned)std::min<i64>((n_slots + 255) / 256, 65536)), dim3(256), 0, s, T, n_slots, d_pt, D[P_LABELS].as<unsigned>(),
-                           D[P_TAIL].as<unsigned char>(), hash_mask, D[P_IBITS].as<unsigned>(), D[P_CBITS].as<unsigned>(), D[P_RFIRST].as<int>(),
-                           D[P_RLAST].as<int>(), D[P_FIRST].as<int>(), D[P_LAST].as<int>(), D[P_REP_TINT].as<int>(), D[P_KEY].as<u64>(), D[P_VAL].as<int>(),
-                           D[P_ERR].as<int>());
-        HIP_TRY(c, hipEventRecord(c->qev[1], s));
-        // refusals first: a tail above 2 or a label 3 has no meaning, and the sort's keys of such a batch are not needed
-        HIP_TRY(c, hipMemcpyAsync(h_err, D[P_ERR].p, 16, hipMemcpyDeviceToHost, s));
-        size_t tb = tmp_bytes;
-        HIP_TRY(c, rocprim::radix_sort_pairs(D[P_TMP].p, tb, D[P_KEY].as<u64>(), D[P_SKEY].as<u64>(), D[P_VAL].as<int>(), D[P_SVAL].as<int>(), (size_t)N, 0u, key_bits, s));
-        hipLaunchKernelGGL(k_heads, dim3(rep_grid), dim3(256), 0, s, N, D[P_SKEY].as<u64>(), D[P_HEAD].as<int>());
-        tb = tmp_bytes;
-        HIP_TRY(c, rocprim::inclusive_scan(D[P_TMP].p, tb, D[P_HEAD].as<int>(), D[P_BSTART].as<int>(), (size_t)N, rocprim::maximum<int>(), s));
-        hipLaunchKernelGGL(k_leader, dim3(rep_grid), dim3(256), 0, s, N, D[P_SKEY].as<u64>(), D[P_SVAL].as<int>(), D[P_BSTART].as<int>(), d_pt,
-                           D[P_IBITS].as<unsigned>(), D[P_FIRST].as<int>(), D[P_LAST].as<int>(), D[P_TAIL].as<unsigned char>(), D[P_LEADER].as<int>(),
-                           D[P_FLAG].as<int>());
-        tb = tmp_bytes;
-        HIP_TRY(c, rocprim::exclusive_scan(D[P_TMP].p, tb, D[P_FLAG].as<int>(), D[P_NODE_ID].as<int>(), 0, N1, rocprim::plus<int>(), s));
-        hipLaunchKernelGGL(k_row_off, dim3((unsigned)(T + 256) / 256), dim3(256), 0, s, T, N, d_pt, D[P_NODE_ID].as<int>(), D[P_ROW_OFF].as<i64>());
-        HIP_TRY(c, hipEventRecord(c->qev[2], s));
-        HIP_TRY(c, hipMemcpyAsync(h_row_off, D[P_ROW_OFF].p, (size_t)(T + 1) * 8, hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipStreamSynchronize(s));
-        HIP_TRY(c, hipGetLastError());
-        const int kinds[3] = {2, 0, 1};                      // the tail first: it is the caller's own byte, the labels come from a file
-        for (int k : kinds) {
-            if (h_err[k] == 0x7f7f7f7f) continue;
-            const i64 rep = h_err[k];
-            int t = 0;
-            while (t + 1 < T && rd->rep_off[t + 1] <= rep) ++t;
-            const i64 r = rep - rd->rep_off[t];
-            if (k == 2) return fail(c, FCLU_ERR_ARG, "tint %d rep %lld: tail category %d (0 'N', 1 'S', 2 'E')", t, r, (int)rd->tail[rep]);
-            if (k == 0) return fail(c, FCLU_ERR_ARG, "tint %d rep %lld: a label with code 3 (labels are 0, 1, 2)", t, r);
-            return fail(c, FCLU_ERR_ARG, "tint %d rep %lld: a nonzero bit beyond the tint's %d labels", t, r, (int)rd->n_seg[t]);
-        }
-    } else {
-        memset(h_row_off, 0, (size_t)(T + 1) * 8);
-    }
-    // ---- the unique rows as a batch
-    h_bits_off[0] = h_adj_off[0] = 0;
-    for (int t = 0; t < T; ++t) {
-        const i64 n = h_row_off[t + 1] - h_row_off[t];
-        if (n < 0 || n > rd->rep_off[t + 1] - rd->rep_off[t]) return fail(c, FCLU_ERR_HIP, "tint %d: %lld unique rows of %lld reps", t, n, (i64)(rd->rep_off[t + 1] - rd->rep_off[t]));
-        h_bits_off[t + 1] = h_bits_off[t] + n * pt[(size_t)t].w;
-        h_adj_off[t + 1] = h_adj_off[t] + n * ((n + 63) / 64);
-    }
-    const i64 R = h_row_off[T], n_bits = h_bits_off[T];
-    int rc = stage_tints(c, T, H[Q_ROW_OFF].as<int64_t>(), rd->n_seg, H[Q_BITS_OFF].as<int64_t>(), H[Q_ADJ_OFF].as<int64_t>(), prune, nullptr, st);
-    if (rc != FCLU_OK) return rc;
-    HIP_TRY(c, grow_host(H[Q_NODE_REP], (size_t)R * 4)); HIP_TRY(c, grow_host(H[Q_MEM_OFF], (size_t)(R + 1) * 8));
-    HIP_TRY(c, grow_host(H[Q_BITS], (size_t)n_bits * 4)); HIP_TRY(c, grow_host(H[Q_NFIRST], (size_t)R * 4));
-    HIP_TRY(c, grow_host(H[Q_NLAST], (size_t)R * 4)); HIP_TRY(c, grow_host(H[Q_NTAIL], (size_t)R));
-    *H[Q_MEM_OFF].as<i64>() = 0;
-    if (N > 0) {
-        HIP_TRY(c, grow(c->mem_off, (size_t)(R + 1) * 8));
-        const int rep_grid = (int)std::min<i64>((N + 256) / 256, 4096);
-        HIP_TRY(c, hipEventRecord(c->qev[3], s));
-        hipLaunchKernelGGL(k_nodes, dim3(rep_grid), dim3(256), 0, s, N, D[P_REP_TINT].as<int>(), D[P_TINTS].as<PrepTint>(), c->tints.as<TintDesc>(),
-                           D[P_LEADER].as<int>(), D[P_NODE_ID].as<int>(), D[P_IBITS].as<unsigned>(), D[P_FIRST].as<int>(), D[P_LAST].as<int>(),
-                           D[P_TAIL].as<unsigned char>(), D[P_REP_NODE].as<int>(), D[P_NKEY].as<unsigned>(), D[P_NVAL].as<int>(), D[P_NODE_REP].as<int>(),
-                           c->bits.as<unsigned>(), c->first.as<int>(), c->last.as<int>(), c->tail.as<unsigned char>());
-        size_t tb = D[P_TMP].cap;
-        HIP_TRY(c, rocprim::radix_sort_pairs(D[P_TMP].p, tb, D[P_NKEY].as<unsigned>(), D[P_SNKEY].as<unsigned>(), D[P_NVAL].as<int>(), c->mem.as<int>(), (size_t)N, 0u,
-                                             (unsigned)bits_for(N), s));
-        hipLaunchKernelGGL(k_mem_off, dim3(rep_grid), dim3(256), 0, s, N, R, D[P_SNKEY].as<unsigned>(), c->mem_off.as<i64>());
-        HIP_TRY(c, hipEventRecord(c->qev[4], s));
-        HIP_TRY(c, hipMemcpyAsync(H[Q_IBITS].p, D[P_IBITS].p, (size_t)n_rbits * 4, hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipMemcpyAsync(H[Q_CBITS].p, D[P_CBITS].p, (size_t)n_rbits * 4, hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipMemcpyAsync(H[Q_FIRST].p, D[P_FIRST].p, (size_t)N * 4, hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipMemcpyAsync(H[Q_LAST].p, D[P_LAST].p, (size_t)N * 4, hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipMemcpyAsync(H[Q_RFIRST].p, D[P_RFIRST].p, (size_t)N * 4, hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipMemcpyAsync(H[Q_RLAST].p, D[P_RLAST].p, (size_t)N * 4, hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipMemcpyAsync(H[Q_REP_NODE].p, D[P_REP_NODE].p, (size_t)N * 4, hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipMemcpyAsync(H[Q_NODE_REP].p, D[P_NODE_REP].p, (size_t)R * 4, hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipMemcpyAsync(H[Q_MEM_OFF].p, c->mem_off.p, (size_t)(R + 1) * 8, hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipMemcpyAsync(H[Q_MEM].p, c->mem.p, (size_t)N * 4, hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipMemcpyAsync(H[Q_BITS].p, c->bits.p, (size_t)n_bits * 4, hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipMemcpyAsync(H[Q_NFIRST].p, c->first.p, (size_t)R * 4, hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipMemcpyAsync(H[Q_NLAST].p, c->last.p, (size_t)R * 4, hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipMemcpyAsync(H[Q_NTAIL].p, c->tail.p, (size_t)R, hipMemcpyDeviceToHost, s));
-    }
-    fclu_prep &o = c->prep;
-    o.n_tint = T; o.n_reps = N; o.n_rows = R;
-    o.row_off = H[Q_ROW_OFF].as<int64_t>(); o.bits_off = H[Q_BITS_OFF].as<int64_t>(); o.adj_off = H[Q_ADJ_OFF].as<int64_t>();
-    o.rep_bits_off = H[Q_RBITS_OFF].as<int64_t>();
-    o.i_bits = H[Q_IBITS].as<uint32_t>(); o.c_bits = H[Q_CBITS].as<uint32_t>();
-    o.first = H[Q_FIRST].as<int32_t>(); o.last = H[Q_LAST].as<int32_t>(); o.raw_first = H[Q_RFIRST].as<int32_t>(); o.raw_last = H[Q_RLAST].as<int32_t>();
-    o.rep_node = H[Q_REP_NODE].as<int32_t>(); o.node_rep = H[Q_NODE_REP].as<int32_t>();
-    o.mem_off = H[Q_MEM_OFF].as<int64_t>(); o.mem = H[Q_MEM].as<int32_t>();
-    o.bits = H[Q_BITS].as<uint32_t>(); o.node_first = H[Q_NFIRST].as<int32_t>(); o.node_last = H[Q_NLAST].as<int32_t>(); o.node_tail = H[Q_NTAIL].as<uint8_t>();
-    return FCLU_OK;
-}
-
-// the kernels' times of the call that has just synchronised
-void preprocess_times(fclu_ctx *c, i64 n_reps) {
-    if (n_reps <= 0) return;
-    float a = 0.f, b = 0.f;
-    (void)hipEventElapsedTime(&c->rows_ms, c->qev[0], c->qev[1]);
-    (void)hipEventElapsedTime(&a, c->qev[1], c->qev[2]);
-    (void)hipEventElapsedTime(&b, c->qev[3], c->qev[4]);
-    c->dedupe_ms = a + b;
-}
-
-}  // namespace
-
-extern "C" {
-
-int fclu_preprocess(fclu_ctx *c, const fclu_reads *reads) {
-    if (!c) return FCLU_ERR_ARG;
-    Staged st;
-    i64 n_reps = 0;
-    const int rc = preprocess_device(c, reads, 1, st, n_reps);
-    if (rc != FCLU_OK) return rc;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    HIP_TRY(c, hipGetLastError());
-    preprocess_times(c, n_reps);
-    c->have_prep = true;
-    return FCLU_OK;
-}
-
-int fclu_partition_reads(fclu_ctx *c, const fclu_reads *reads, int32_t maximum_ilp_size) {
-    if (!c) return FCLU_ERR_ARG;
-    c->have_parts = false;
-    c->have_prep = false;
-    if (maximum_ilp_size < 1) return fail(c, FCLU_ERR_ARG, "maximum_ilp_size is %d: it must be at least 1", (int)maximum_ilp_size);
-    Staged st;
-    i64 n_reps = 0;
-    int rc = preprocess_device(c, reads, 1, st, n_reps);
-    if (rc != FCLU_OK) return rc;
-    if (!st.empty) rc = compat_run(c, st, 1, nullptr, nullptr);          // (it synchronises: the pinned copies have landed)
-    else HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (rc != FCLU_OK) return rc;
-    preprocess_times(c, n_reps);
-    c->have_prep = true;
-    return partition_device(c, reads->n_tint, st.R, nullptr, nullptr, n_reps, maximum_ilp_size);
-}
-
-int fclu_preprocess_results(fclu_ctx *c, fclu_prep *out) {
-    if (!c || !out) return FCLU_ERR_ARG;
-    if (!c->have_prep) return fail(c, FCLU_ERR_ARG, "fclu_preprocess_results: no result (the last fclu_preprocess / fclu_partition_reads call failed or none was made)");
-    *out = c->prep;
-    return FCLU_OK;
-}
-
-int fclu_preprocess_timing(fclu_ctx *c, float *rows_ms, float *dedupe_ms) {
-    if (!c) return FCLU_ERR_ARG;
-    if (rows_ms) *rows_ms = c->rows_ms;
-    if (dedupe_ms) *dedupe_ms = c->dedupe_ms;
-    return FCLU_OK;
-}
+int fclu_last_timing(fclu_ctx *c, float *compat_ms, float *prune_ms) { return c ? two_times(compat_ms, c->compat_ms, prune_ms, c->prune_ms) : FCLU_ERR_ARG; }
 
 int fclu_partition(fclu_ctx *c, const fclu_batch *b, const int64_t *mem_off, const int32_t *mem, int32_t maximum_ilp_size) {
     if (!c || !b) return FCLU_ERR_ARG;
     c->have_parts = false;
     if (b->n_tint <= 0) return fail(c, FCLU_ERR_ARG, "fclu_partition: empty batch");
-    int rc = check_members(c, b->row_off[b->n_tint], mem_off, mem, maximum_ilp_size);
-    if (rc == FCLU_OK) rc = compat_device(c, b, 1, nullptr, nullptr);
-    if (rc == FCLU_OK) rc = partition_device(c, b->n_tint, b->row_off[b->n_tint], mem_off, mem, 0, maximum_ilp_size);
-    return rc;
+    RC_TRY(check_members(c, b->row_off[b->n_tint], mem_off, mem, maximum_ilp_size));
+    RC_TRY(compat_device(c, read_knobs(), b, 1, nullptr, nullptr));
+    return partition_device(c, b->n_tint, b->row_off[b->n_tint], mem_off, mem, 0, maximum_ilp_size);
 }
 
 int fclu_partition_adj(fclu_ctx *c, int32_t n_tint, const int64_t *row_off, const int64_t *adj_off, const uint64_t *adj,
@@ -1612,6 +1601,7 @@ int fclu_partition_adj(fclu_ctx *c, int32_t n_tint, const int64_t *row_off, cons
     c->have_parts = false;
     if (n_tint <= 0) return fail(c, FCLU_ERR_ARG, "fclu_partition_adj: empty batch");
     HIP_TRY(c, hipSetDevice(c->device));
+    const Knobs k = read_knobs();
     const int T = n_tint;
     const i64 R = row_off[T], n_adj = adj_off[T];
     if (row_off[0] != 0 || adj_off[0] != 0 || R < 0 || R >= (1ll << 31)) return fail(c, FCLU_ERR_ARG, "fclu_partition_adj: bad row_off / adj_off");
@@ -1620,44 +1610,22 @@ int fclu_partition_adj(fclu_ctx *c, int32_t n_tint, const int64_t *row_off, cons
     std::vector<int> row_tint((size_t)R);
     for (int t = 0; t < T; ++t) {
         TintDesc &d = tints[(size_t)t];
-        d = TintDesc();
-        d.row0 = row_off[t];
-        const i64 n = row_off[t + 1] - d.row0;
-        if (n < 0 || n > (1 << 30)) return fail(c, FCLU_ERR_ARG, "tint %d: bad row count", t);
-        d.n = (int)n; d.aw = (d.n + 63) / 64; d.adj_off = adj_off[t]; d.w = 1;
-        d.cc_lds = cc_in_lds(d.n, d.aw);
-        if (adj_off[t + 1] - d.adj_off != (i64)d.n * d.aw) return fail(c, FCLU_ERR_ARG, "tint %d: adj_off does not match rows x words", t);
-        // the matrix is the caller's: symmetric, an empty diagonal, no bit at a column >= N (the kernels index nodes with its bits)
-        const uint64_t *A = adj + d.adj_off;
-        for (i64 r = 0; r < n; ++r) {
-            row_tint[(size_t)(d.row0 + r)] = t;
-            for (int z = 0; z < d.aw; ++z) {
-                uint64_t word = A[r * d.aw + z];
-                if (z == d.aw - 1 && (d.n & 63) && (word >> (d.n & 63)))
-                    return fail(c, FCLU_ERR_ARG, "tint %d row %lld: adjacency bit at a column beyond N = %d", t, r, d.n);
-                while (word) {
-                    const i64 col = (i64)z * 64 + __builtin_ctzll(word);
-                    word &= word - 1;
-                    if (col == r) return fail(c, FCLU_ERR_ARG, "tint %d row %lld: adjacency bit on the diagonal", t, r);
-                    if (!((A[col * d.aw + (r >> 6)] >> (r & 63)) & 1ull))
-                        return fail(c, FCLU_ERR_ARG, "tint %d: adjacency not symmetric: (%lld, %lld) set, (%lld, %lld) not", t, r, col, col, r);
-                }
-            }
-        }
+        RC_TRY(describe_tint(c, t, k, 0, row_off, nullptr, nullptr, adj_off, d));
+        RC_TRY(check_adj(c, t, d, adj));
+        std::fill_n(row_tint.begin() + d.row0, d.n, t);
     }
-    int rc = check_members(c, R, mem_off, mem, maximum_ilp_size);
-    if (rc != FCLU_OK) return rc;
+    RC_TRY(check_members(c, R, mem_off, mem, maximum_ilp_size));
     c->h_tints = tints;
     c->adj_cur = 0;
     c->compat_ms = c->prune_ms = 0.f;
     if (R > 0) {
         hipStream_t s = c->stream;
-        HIP_TRY(c, grow(c->tints, tints.size() * sizeof(TintDesc)));
-        HIP_TRY(c, grow(c->row_tint, (size_t)R * 4));
-        HIP_TRY(c, grow(c->adj[0], (size_t)n_adj * 8));
-        HIP_TRY(c, hipMemcpyAsync(c->tints.p, tints.data(), tints.size() * sizeof(TintDesc), hipMemcpyHostToDevice, s));
-        HIP_TRY(c, hipMemcpyAsync(c->row_tint.p, row_tint.data(), (size_t)R * 4, hipMemcpyHostToDevice, s));
-        if (n_adj) HIP_TRY(c, hipMemcpyAsync(c->adj[0].p, adj, (size_t)n_adj * 8, hipMemcpyHostToDevice, s));
+        HIP_TRY(c, c->tints.grow((size_t)T));
+        HIP_TRY(c, c->row_tint.grow((size_t)R));
+        HIP_TRY(c, c->adj[0].grow((size_t)n_adj));
+        HIP_TRY(c, hipMemcpyAsync(c->tints.p, tints.data(), c->tints.bytes((size_t)T), hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipMemcpyAsync(c->row_tint.p, row_tint.data(), c->row_tint.bytes((size_t)R), hipMemcpyHostToDevice, s));
+        if (n_adj) HIP_TRY(c, hipMemcpyAsync(c->adj[0].p, adj, c->adj[0].bytes((size_t)n_adj), hipMemcpyHostToDevice, s));
         HIP_TRY(c, hipStreamSynchronize(s));              // (the host vectors go out of scope)
     }
     return partition_device(c, T, R, mem_off, mem, 0, maximum_ilp_size);
@@ -1671,18 +1639,45 @@ int fclu_partition_results(fclu_ctx *c, fclu_parts *out) {
 }
 
 int fclu_partition_timing(fclu_ctx *c, float *components_ms, float *pairs_ms) {
+    return c ? two_times(components_ms, c->components_ms, pairs_ms, c->pairs_ms) : FCLU_ERR_ARG;
+}
+
+int fclu_preprocess(fclu_ctx *c, const fclu_reads *reads) {
     if (!c) return FCLU_ERR_ARG;
-    if (components_ms) *components_ms = c->components_ms;
-    if (pairs_ms) *pairs_ms = c->pairs_ms;
+    Staged st;
+    i64 n_reps = 0;
+    RC_TRY(preprocess_device(c, read_knobs(), reads, 1, st, n_reps));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipGetLastError());
+    preprocess_times(c, n_reps);
+    c->have_prep = true;
     return FCLU_OK;
 }
 
-int fclu_last_timing(fclu_ctx *c, float *compat_ms, float *prune_ms) {
+int fclu_partition_reads(fclu_ctx *c, const fclu_reads *reads, int32_t maximum_ilp_size) {
     if (!c) return FCLU_ERR_ARG;
-    if (compat_ms) *compat_ms = c->compat_ms;
-    if (prune_ms) *prune_ms = c->prune_ms;
+    c->have_parts = false;
+    c->have_prep = false;
+    if (maximum_ilp_size < 1) return fail(c, FCLU_ERR_ARG, "maximum_ilp_size is %d: it must be at least 1", (int)maximum_ilp_size);
+    const Knobs k = read_knobs();
+    Staged st;
+    i64 n_reps = 0;
+    RC_TRY(preprocess_device(c, k, reads, 1, st, n_reps));
+    if (!st.empty) RC_TRY(compat_run(c, st, k, 1, nullptr, nullptr));          // (it synchronises: the pinned copies have landed)
+    else HIP_TRY(c, hipStreamSynchronize(c->stream));
+    preprocess_times(c, n_reps);
+    c->have_prep = true;
+    return partition_device(c, reads->n_tint, st.R, nullptr, nullptr, n_reps, maximum_ilp_size);
+}
+
+int fclu_preprocess_results(fclu_ctx *c, fclu_prep *out) {
+    if (!c || !out) return FCLU_ERR_ARG;
+    if (!c->have_prep) return fail(c, FCLU_ERR_ARG, "fclu_preprocess_results: no result (the last fclu_preprocess / fclu_partition_reads call failed or none was made)");
+    *out = c->prep;
     return FCLU_OK;
 }
+
+int fclu_preprocess_timing(fclu_ctx *c, float *rows_ms, float *dedupe_ms) { return c ? two_times(rows_ms, c->rows_ms, dedupe_ms, c->dedupe_ms) : FCLU_ERR_ARG; }
 
 }  // extern "C"
 

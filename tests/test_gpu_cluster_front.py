@@ -266,3 +266,69 @@ def test_refusals_leave_the_context_usable(ctx):
     prep, parts = ctx.partition_labels(good, 10)
     assert_same_arrays(prep, want)
     assert int(parts["tint_part_off"][-1]) >= 3
+
+
+# ---- buffer lifetime: one context through growing, refused, smaller and empty calls ------------------------------------
+def lifetime_batch(shapes, seed):
+    """(label tints packed, the same tints after host preprocess_ilp(), their unique rows packed, the rows' members)."""
+    tints = [fu.labels_from_preprocessed(cu.random_tint(seed + k, n, m), seed=k) if n else dict(fu.label_tint(seed + k, [], [], None), segs=[(0, 1, 1)] * m)
+             for k, (n, m) in enumerate(shapes)]
+    host = copy.deepcopy(tints)
+    for t in host:
+        cluster_prep.preprocess_ilp(t, CONSTANT)
+    uniq = [cluster_prep.unique_structures(t) for t in host]
+    return cluster_prep.pack_labels(tints), host, cluster_prep.pack_structures(uniq), cluster_prep.pack_members(uniq)
+
+
+def lifetime_calls(c, batch, size=50):
+    """Every array a batch gives: the one-call path, then the graph and the partition behind the host's front."""
+    packed, host, structures, _ = batch
+    prep, parts = c.partition_labels(packed, size)
+    adj, rounds = c.compat_graph(structures)
+    return dict(prep=prep, parts=parts, graph=dict(adj=adj, rounds=rounds), batch=cluster_prep.partition_arrays_batch(host, size, c))
+
+
+@pytest.mark.parametrize("per_pass", [False, True], ids=["in-lds", "per-pass"])
+def test_one_context_through_many_calls_equals_fresh_contexts(per_pass, monkeypatch):
+    """Buffers that grew for one call serve the next: three tints across the 64-row tile edge, a refused call, a smaller batch, a batch
+    without a rep and the first batch again on ONE context give, call by call, what a fresh context gives.  per-pass: a lower LDS limit
+    sends the 130-rep tint through the per-pass pruning kernels (and all components through theirs), so the burst loop runs too."""
+    for name, value in (("FCLU_PRUNE_LDS_WORDS", "300"), ("FCLU_PART_LDS", "0")):
+        if per_pass:
+            monkeypatch.setenv(name, value)
+        else:
+            monkeypatch.delenv(name, raising=False)
+    first = lifetime_batch([(130, 64), (65, 33), (1, 5)], 300)
+    small = lifetime_batch([(63, 31)], 310)
+    no_reps = lifetime_batch([(0, 40), (0, 7)], 320)
+    assert first[2]["row_off"][1] > 64 and int(no_reps[0]["rep_off"][-1]) == 0
+
+    def fresh(batch):
+        c = cluster_prep.Context(0)
+        try:
+            return lifetime_calls(c, batch)
+        finally:
+            c.close()
+
+    def same(got, want):
+        assert sorted(got) == sorted(want)
+        for k in got:
+            assert_same_arrays({n: np.asarray(v) for n, v in got[k].items()}, {n: np.asarray(v) for n, v in want[k].items()})
+
+    want = {id(b): fresh(b) for b in (first, small, no_reps)}
+    c = cluster_prep.Context(0)
+    try:
+        same(lifetime_calls(c, first), want[id(first)])
+        bad = dict(first[2]); bad["last"] = first[2]["last"].copy(); bad["last"][0] = 64        # beyond the last segment (0 .. 63)
+        with pytest.raises(cluster_prep.ClusterError, match="out of range"):
+            c.compat_graph(bad)
+        with pytest.raises(cluster_prep.ClusterError, match="out of range"):
+            c.partition(bad, first[3], 50)
+        with pytest.raises(cluster_prep.ClusterError, match="fclu_partition_results: no result"):
+            c._partition_arrays("fclu_partition_results", 0)
+        for b in (small, no_reps, first):
+            same(lifetime_calls(c, b), want[id(b)])
+    finally:
+        c.close()
+    for _ in range(20):
+        cluster_prep.Context(0).close()
