@@ -257,6 +257,14 @@ struct fseg_ctx {
     i64 tiny_from = 256;        // problems above which k_tiny is used (FSEG_TINY_FROM; tests force 0)
     bool trace = false;         // FSEG_TRACE=1: phase timers of upload / run on stderr
     bool force_global_sort = false;   // FSEG_GLOBAL_SORT=1 (tests): the batch-wide radix sort whatever the partition sizes
+    // FSEG_TAP_PATHS (include/freddie_seg.h has the words): what the last enqueue of each stage launched.  A stage's words are reset
+    // where enqueue_run begins the stage; the masks and counts are written in the branches that launch, so they say what ran, not
+    // what the switches asked for (the six decisions of the batch -- small_batch, tiny_on, wave_on, fuse_on, known, plan -- are the
+    // values those branches test, copied where the stage begins); a replayed graph keeps the words of its capture.
+    enum { PATH_SMALL_BATCH, PATH_TINY_ON, PATH_WAVE_ON, PATH_FUSE_ON, PATH_KEY32, PATH_THR_PART, PATH_LABEL_PACKED, PATH_N_SOLVE,
+           PATH_N_WIDE = PATH_N_SOLVE + 3, PATH_N_TINY = PATH_N_WIDE + 3, PATH_N_WORK, PATH_DPW, PATH_WIDE16, PATH_KNOWN, PATH_SOLVE8,
+           PATH_TINY_KERNEL, PATH_SCORE, PATH_ARENA_DP, PATH_PLAN, PATH_N_ARENA_PROB, PATH_N_SCORE, PATH_WORDS = PATH_N_SCORE + 3 };
+    int paths[PATH_WORDS] = {};
 };
 
 namespace {
@@ -603,9 +611,11 @@ int enqueue_run(fseg_ctx *c, unsigned segs, bool sized = false, i64 label_fill_b
     const bool thr_part_fits = c->max_part_pos <= (i64)kThrPartMaxChunks * 8192;
     const bool thr_part = thr_part_fits && (c->thr_part == 1 || (c->thr_part < 0 && n_part >= 64));
     if (thr_part) {
+        c->paths[fseg_ctx::PATH_THR_PART] = 1;
         hipLaunchKernelGGL(k_thr_part, dim3(grid_for(n_part, 1, 4096)), dim3(512), 0, q, n_part, c->d_part_iv_off.as<i64>(), c->d_pos_off.as<i64>(), NPOS,
                            flag_pos_bits, c->d_y.as<double>(), c->d_v.as<double>(), c->P.variance_factor, c->d_mean.as<double>(), c->d_thr.as<double>());
     } else {
+    c->paths[fseg_ctx::PATH_THR_PART] = 0;
     scan_counts(q, bsum_side, flag_pos_bits, &st->n_vals, nullptr);
     hipLaunchKernelGGL(k_scan_emit<kEmitValues>, dim3(scan_grid), dim3(256), 0, q, flag_pos_bits, NPOS,
                        bsum_side, scan_state, &st->n_vals, (i64 *)nullptr, &st->err, c->d_y.as<double>(), c->d_v.as<double>(), K, c->d_pos_off.as<i64>(),
@@ -696,6 +706,13 @@ int enqueue_run(fseg_ctx *c, unsigned segs, bool sized = false, i64 label_fill_b
     if (!score_begun) end(ST_SCORE_PREP);
     }   // do_pre2
     if (do_score && !score_begun) begin(ST_SCORE);
+    int *const census = c->paths;
+    if (do_score) {
+        for (int w = 0; w < fseg_ctx::PATH_WORDS; ++w)
+            if (w != fseg_ctx::PATH_THR_PART && w != fseg_ctx::PATH_LABEL_PACKED && w != fseg_ctx::PATH_ARENA_DP) census[w] = 0;
+        census[fseg_ctx::PATH_SMALL_BATCH] = c->small_batch; census[fseg_ctx::PATH_TINY_ON] = c->tiny_on; census[fseg_ctx::PATH_WAVE_ON] = wave;
+        census[fseg_ctx::PATH_FUSE_ON] = c->use_fuse && c->fuse_on; census[fseg_ctx::PATH_KNOWN] = known; census[fseg_ctx::PATH_PLAN] = plan != nullptr;
+    }
     if (do_score && c->prob_cap > 0) {
         // How the scoring kernels share the chip is a plan (FSEG_SCORE_PLAN, default "gM|W|hB|gST"): streams separated by '|'
         // (the first is the main stream; the segments that have something to launch take the side streams in order); B M S T =
@@ -729,13 +746,14 @@ int enqueue_run(fseg_ctx *c, unsigned segs, bool sized = false, i64 label_fill_b
 #define FSEG_WG_TINY 4096
 #endif
 #define FSEG_LAUNCH_SCORE(Q, NMV, CLS, MAXWG)                                                                           \
+        do { note_score(CLS);                                                                                                  \
         hipLaunchKernelGGL(k_score<NMV>, dim3(work_grid < (MAXWG) ? work_grid : (MAXWG)), dim3(ScoreCfg<NMV>::kThreads),  \
                            score_lds_for((NMV) == kNMax ? c->nm_big : (NMV), (NMV) + 1), Q, st, CLS,                                 \
                            ((NMV) == kNMax ? c->nm_big : (NMV)), pr, c->prob_cap, c->d_cls_items.as<int4>(),              \
                            c->d_prob_desc.as<ProbDesc>(), c->work_cap, c->d_cand_off.as<i64>(),                         \
                            c->d_cand_y.as<int>(), c->d_work_active.as<unsigned char>(), c->d_cov.as<unsigned>(),        \
                            c->cov_cap, c->d_pair_thr.as<int2>(), c->pair_cap, c->d_out.as<unsigned>(), c->tri_cap,      \
-                           c->d_amb.as<unsigned>() FSEG_TARG)
+                           c->d_amb.as<unsigned>() FSEG_TARG); } while (0)
         // (a 16-bit-counter instance of a sized batch goes over its class's WIDE problems only: wide_n of them, through wide_items)
         auto wide_n = [&](int cls, size_t cnt_bytes) -> i64 { return (known && cls >= 0 && cls < 3 && cnt_bytes == 2) ? c->n_wide[cls] : -1; };
 #define FSEG_SOLVE_N(CNT, CLS, N_ITEMS) (wide_n(CLS, sizeof(CNT)) >= 0 ? wide_n(CLS, sizeof(CNT)) : (i64)(N_ITEMS))
@@ -756,28 +774,32 @@ int enqueue_run(fseg_ctx *c, unsigned segs, bool sized = false, i64 label_fill_b
                    c->n_solve[cls] <= kSplitGridCap && cnt_bytes <= c->dpx_cnt[cls] && c->d_dpx.p != nullptr;
         };
 #define FSEG_LAUNCH_SOLVE(Q, NMV, CNT, VT, CLS, N_ITEMS, MAXWG)                                                              \
+            do { note_solve(CLS, sizeof(CNT));                                                                                     \
             hipLaunchKernelGGL((k_solve<NMV, CNT, VT, false>), dim3(grid_for(FSEG_SOLVE_N(CNT, CLS, N_ITEMS), 1, known ? (1 << 20) : (MAXWG))), dim3(SolveCfg<NMV>::kThreads), \
                                solve_lds_for((NMV) == kNMax ? c->nm_big : (NMV), (NMV) + 1, (int)sizeof(CNT)), Q,               \
-                               FSEG_SOLVE_ARGS(NMV, CNT, CLS), (unsigned char *)nullptr, (i64)0, FSEG_SOLVE_WIDE(CNT, CLS) FSEG_TARG)
+                               FSEG_SOLVE_ARGS(NMV, CNT, CLS), (unsigned char *)nullptr, (i64)0, FSEG_SOLVE_WIDE(CNT, CLS) FSEG_TARG); } while (0)
         // every list's problems that see more than kFuseLanes reads, through wide_all: the large class's 16-bit instance, a workgroup each
 #define FSEG_LAUNCH_WIDE_ALL(Q, VT)                                                                                          \
+            do { note_solve(-1, 2);                                                                                                \
             hipLaunchKernelGGL((k_solve<kNMax, unsigned short, VT, false>), dim3((unsigned)n_wide_all), dim3(SolveCfg<kNMax>::kThreads), \
                                solve_lds_for(c->nm_big, kNMax + 1, 2), Q, st, -1, c->nm_big, (i64)0, n_wide_all, pr, c->d_solve_desc.as<ProbDesc>(), \
                                c->prob_cap, c->d_cand_y.as<int>(), c->d_lane_lx.as<int2>(), c->d_lex.as<int2>(),               \
                                c->d_h_table.as<double>(), c->P.h_len, c->P.threshold_rate,               \
                                c->d_thr_tab.as<int2>(), c->P.min_read_support_outside, c->d_chosen.as<unsigned char>(),       \
-                               (unsigned char *)nullptr, (i64)0, c->d_wide_all.as<int>() FSEG_TARG)
+                               (unsigned char *)nullptr, (i64)0, c->d_wide_all.as<int>() FSEG_TARG); } while (0)
 #define FSEG_LAUNCH_DPW(Q, NMV, CNT, VT, CLS, N_ITEMS, TT)                                                                   \
+            do { census[fseg_ctx::PATH_DPW] |= (1 << ((CLS) < 0 ? 0 : (CLS))) | ((TT) == 512 ? 8 : 0);                                 \
             hipLaunchKernelGGL((k_dpw<NMV, CNT, VT, TT>), dim3(grid_for(FSEG_SOLVE_N(CNT, CLS, N_ITEMS), 1, (int)kSplitGridCap)), dim3(TT),      \
                                dpw_lds_for(nm_rt, (int)sizeof(VT), (int)sizeof(CNT)), Q, st, nm_rt, list_lb(CLS),                \
                                FSEG_SOLVE_N(CNT, CLS, list_ln(CLS)), pr,                                                        \
                                c->d_solve_desc.as<ProbDesc>(), dpx0, dstride, \
-                               c->P.min_read_support_outside, c->d_chosen.as<unsigned char>(), FSEG_SOLVE_WIDE(CNT, CLS) FSEG_TARG)
+                               c->P.min_read_support_outside, c->d_chosen.as<unsigned char>(), FSEG_SOLVE_WIDE(CNT, CLS) FSEG_TARG); } while (0)
         // the split path, one instance: k_solve<.., SPLIT> (set-up and rounds) then k_dpw (the DPs) on the same stream
 #define FSEG_LAUNCH_SPLIT(Q, NMV, CNT, VT, CLS, N_ITEMS)                                                                     \
         do { const int nm_rt = (NMV) == kNMax ? c->nm_big : (NMV);                                                            \
             unsigned char *dpx0 = c->d_dpx.as<unsigned char>() + c->dpx_base[(CLS) < 0 ? 0 : (CLS)];                                           \
             const i64 dstride = c->dpx_stride[(CLS) < 0 ? 0 : (CLS)];                                                                       \
+            note_solve(CLS, sizeof(CNT));                                                                                     \
             hipLaunchKernelGGL((k_solve<NMV, CNT, int, true>), dim3(grid_for(FSEG_SOLVE_N(CNT, CLS, N_ITEMS), 1, (int)kSplitGridCap)), dim3(SolveCfg<NMV>::kThreads), \
                                solve_lds_for(nm_rt, (NMV) + 1, (int)sizeof(CNT)), Q, FSEG_SOLVE_ARGS(NMV, CNT, CLS), dpx0, dstride, \
                                FSEG_SOLVE_WIDE(CNT, CLS) FSEG_TARG);                                    \
@@ -804,16 +826,33 @@ int enqueue_run(fseg_ctx *c, unsigned segs, bool sized = false, i64 label_fill_b
         // A batch usually holds only one kind; a class's two launches share a stream.
         // one wave per problem on the exon stream (k_wave): the small class's solve list and k_tiny's list
 #define FSEG_LAUNCH_WAVE_V(Q, NMV, VT, LIST, N_ITEMS)                                                                        \
+            do { note_tiny(1);                                                                                                     \
             hipLaunchKernelGGL((k_wave<NMV, VT>), dim3(grid_for((N_ITEMS), 4, FSEG_WG_TINY)), dim3(256), 0, Q, st,           \
                                c->d_solve_desc.as<ProbDesc>(), c->prob_cap, LIST, pr, c->d_cand_y.as<int>(), c->d_lane_lx.as<int2>(), \
                                c->d_lex.as<int2>(), c->d_h_table.as<double>(), c->P.h_len, c->P.threshold_rate,               \
                                c->d_thr_tab.as<int2>(), c->P.min_read_support_outside, c->d_chosen.as<unsigned char>(),        \
-                               list_lb(LIST), list_ln(LIST) FSEG_TARG)
+                               list_lb(LIST), list_ln(LIST) FSEG_TARG); } while (0)
 #define FSEG_LAUNCH_WAVE(Q, NMV, LIST, N_ITEMS)                                                                              \
             do { if (key32) { FSEG_LAUNCH_WAVE_V(Q, NMV, int, LIST, N_ITEMS); }                              \
                  else { FSEG_LAUNCH_WAVE_V(Q, NMV, i64, LIST, N_ITEMS); } } while (0)
         // the bounds of solve list `l` (0..2 the classes, 3 the tiny problems, < 0 the three classes together) when the host knows them
         const bool key32 = c->max_part_lanes < kKey32Reads && !c->force_key64;     // (FSEG_FORCE_KEY64=1: the 64-bit instances whatever the batch)
+        census[fseg_ctx::PATH_KEY32] = key32;
+        // the census of this stage's launches (cls < 0: one launch over every class)
+        auto note_solve = [&](int cls, size_t cnt_bytes) {
+            census[cnt_bytes == 2 ? fseg_ctx::PATH_WIDE16 : fseg_ctx::PATH_SOLVE8] |= cls < 0 ? 8 : 1 << cls;
+            for (int q = 0; q < 3; ++q) if (cls < 0 || q == cls) {
+                census[fseg_ctx::PATH_N_SOLVE + q] = known ? (int)c->n_solve[q] : -1;
+                if (cnt_bytes == 2) census[fseg_ctx::PATH_N_WIDE + q] = known ? (int)c->n_wide[q] : -1;
+            }
+        };
+        auto note_score = [&](int cls) {
+            census[fseg_ctx::PATH_SCORE] |= cls < 0 ? 8 : 1 << cls;
+            census[fseg_ctx::PATH_N_WORK] = known ? (int)(c->n_cls_work[0] + c->n_cls_work[1] + c->n_cls_work[2] + c->n_cls_work[3]) : -1;
+            census[fseg_ctx::PATH_N_ARENA_PROB] = known ? (int)c->n_arena_prob : -1;
+            for (int q = 0; q < 3; ++q) if (cls < 0 || q == cls) census[fseg_ctx::PATH_N_SCORE + q] = known ? (int)c->n_cls_work[q] : -1;
+        };
+        auto note_tiny = [&](int kernel) { census[fseg_ctx::PATH_TINY_KERNEL] = kernel; census[fseg_ctx::PATH_N_TINY] = known ? (int)c->n_tiny : -1; };
         auto list_lb = [&](int l) -> i64 { return !known ? -1 : (l <= 0 ? 0 : (l == 1 ? c->n_solve[0] : (l == 2 ? c->n_solve[0] + c->n_solve[1] : c->n_solve[0] + c->n_solve[1] + c->n_solve[2]))); };
         auto list_ln = [&](int l) -> i64 { return !known ? -1 : (l < 0 ? c->n_solve[0] + c->n_solve[1] + c->n_solve[2] : (l == 3 ? c->n_tiny : c->n_solve[l])); };
         const bool any_solve = c->use_fuse && c->fuse_on && (!known || c->n_solve[0] + c->n_solve[1] + c->n_solve[2] > 0);
@@ -931,20 +970,22 @@ int enqueue_run(fseg_ctx *c, unsigned segs, bool sized = false, i64 label_fill_b
             // after the classes whose workgroups need half a CU's LDS each); joined at the end of this stage, so the
             // stage's time bracket covers all scoring work
             if (wave) FSEG_LAUNCH_WAVE(qt, kTiny, 3, known ? c->n_tiny : c->prob_cap);
-            else
+            else { note_tiny(2);
             hipLaunchKernelGGL(k_tiny, dim3(grid_for(known ? c->n_tiny : c->prob_cap, 4, FSEG_WG_TINY)), dim3(256), 0, qt, st, c->d_solve_desc.as<ProbDesc>(),
                                c->prob_cap, tiny_max, pr, c->d_cand_y.as<int>(), c->d_lane_ex.as<longlong2>(),
                                c->d_ex_ts.as<int>(), c->d_ex_te.as<int>(), c->d_h_table.as<double>(), c->P.h_len, c->P.threshold_rate,
-                               c->d_thr_tab.as<int2>(), c->P.min_read_support_outside, c->d_chosen.as<unsigned char>(), list_lb(3), list_ln(3) FSEG_TARG);
+                               c->d_thr_tab.as<int2>(), c->P.min_read_support_outside, c->d_chosen.as<unsigned char>(), list_lb(3), list_ln(3) FSEG_TARG); }
         }
 #undef FSEG_LAUNCH_WAVE
 #undef FSEG_LAUNCH_WAVE_V
         if (!c->small_batch && sfork) { join(0); join(1); }
+        if (c->have_huge && any_arena) census[fseg_ctx::PATH_SCORE] |= 16;
         if (c->have_huge && any_arena)
             hipLaunchKernelGGL(k_score_huge, dim3(256), dim3(512), kHugeScoreLds, s, st, c->d_dp_items.as<int>(), pr,
                                c->d_prob_desc.as<ProbDesc>(), c->prob_cap, c->work_cap, c->d_cand_y.as<int>(),
                                c->d_cov.as<unsigned>(), c->cov_cap, c->d_pair_thr.as<int2>(), c->pair_cap,
                                c->d_out.as<unsigned>(), c->tri_cap, c->d_amb.as<unsigned>());
+        if (c->have_huge && c->nm_giant > 0 && any_arena && c->d_giant.p) census[fseg_ctx::PATH_SCORE] |= 32;
         if (c->have_huge && c->nm_giant > 0 && any_arena && c->d_giant.p)
             hipLaunchKernelGGL(k_score_giant, dim3(kGiantWgs), dim3(512), giant_score_lds(c->nm_giant), s, st, c->d_dp_items.as<int>(), pr,
                                c->d_prob_desc.as<ProbDesc>(), c->prob_cap, c->work_cap, c->d_cand_y.as<int>(),
@@ -962,7 +1003,9 @@ int enqueue_run(fseg_ctx *c, unsigned segs, bool sized = false, i64 label_fill_b
     const bool ride_fill = !sized && c->prob_cap > 0 && c->label_cap > 0 && any_arena && !stage_events && !lab_packed;
     if (do_post1) {
     begin(ST_DP);
+    c->paths[fseg_ctx::PATH_ARENA_DP] = 0;
     if (c->prob_cap > 0 && any_arena) {
+        c->paths[fseg_ctx::PATH_ARENA_DP] = c->dp_wide_counts ? 4 : 2;
         int dp_grid = grid_for(c->prob_cap, 1, 1024);
         const int fill_blocks = ride_fill ? grid_for(labels_n16 / 8 + 1, 512, 512) : 0;
 #define FSEG_LAUNCH_DP(NMV, TV, OUTT, NM_RT, DPCLASS, MAXWG)                                                             \
@@ -1043,6 +1086,7 @@ int enqueue_run(fseg_ctx *c, unsigned segs, bool sized = false, i64 label_fill_b
     begin(ST_LABEL);
     if (c->label_cap > 0) {
         c->run_label_packed = lab_packed; c->labels_unpacked = false;
+        c->paths[fseg_ctx::PATH_LABEL_PACKED] = lab_packed;
         if (lab_packed) {
             const i64 n16 = sized ? (label_fill_bytes + 15) / 16 : labels_n16;
             if (n16 > 0)                                            // (one launch: a hipMemsetAsync of 19 MB is two fill kernels here)
@@ -2166,6 +2210,12 @@ int fseg_tap(fseg_ctx *c, int what, void *dst, int64_t cap_bytes, int64_t *n_byt
             bytes = (i64)packed.size() * 4;
             *n_bytes = bytes;
             if (dst && cap_bytes > 0) memcpy(dst, packed.data(), (size_t)(bytes < cap_bytes ? bytes : cap_bytes));
+            return FSEG_OK;
+        }
+        case FSEG_TAP_PATHS: {
+            bytes = (i64)sizeof c->paths;
+            *n_bytes = bytes;
+            if (dst && cap_bytes > 0) memcpy(dst, c->paths, (size_t)(bytes < cap_bytes ? bytes : cap_bytes));
             return FSEG_OK;
         }
         default: return fail(c, FSEG_ERR_ARG, "unknown tap %d", what);

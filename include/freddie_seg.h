@@ -165,7 +165,29 @@ enum {
     /* the scoring stage's device-side fork / join: stages enqueued with waiters so far, whether waiters are still in use
      * (0 after one timed out: events from then on), and the device's words (last problem-list generation, last generation of
      * side streams 0 / 1, workgroup counter) */
-    FSEG_TAP_SYNC = 17         /* int32[6]                                                                             */
+    FSEG_TAP_SYNC = 17,        /* int32[6]                                                                             */
+    /* the launch census of the last run: which kernel instances the host enqueued.  The masks and counts (words 4..16, 18..21, 23..26)
+     * are written in the very branches that launch, not from what the FSEG_* switches asked for; words 0..3, 17 and 22 are the
+     * batch's decisions those branches test, copied where the scoring stage begins.  Counts are the list sizes the host launched
+     * over, -1 where it launched without knowing them (an unsized first run); a replayed hipGraph keeps the words of its capture.
+     * Words:
+     *    0 small_batch (one launch for every size class)      1 tiny_on (problems of <= 8 candidates have a list of their own)
+     *    2 wave_on (k_wave<8> may take that list)             3 fuse_on (problems are solved whole: k_solve / k_wave)
+     *    4 key32 (32-bit DP keys; 0: the 64-bit instances)    5 k_thr_part took the variance threshold
+     *    6 the label arena is packed (two bits per label)
+     *    7..9   n_solve[0..2]: problems of the small / mid / large solve list, for every class with a k_solve launch
+     *   10..12  n_wide[0..2]: of those, the problems the 16-bit-counter instances were launched over
+     *   13 n_tiny: problems k_wave<8> / k_tiny were launched over       14 work items of the arena path (k_score)
+     *   15 k_dpw: bit q = class q's DPs were handed to k_dpw, bit 3 = by the eight-wave k_dpw (large class)
+     *   16 16-bit-counter k_solve launches: bit q = class q's instance, bit 3 = one launch of the large class's over every class
+     *   17 the list sizes were known to the host when it enqueued
+     *   18 8-bit-counter k_solve launches (bits as in 16)     19 tiny list's kernel: 0 none, 1 k_wave<8>, 2 k_tiny
+     *   20 k_score launches: bit q = class q, bit 3 = one launch for every class, bit 4 = k_score_huge, bit 5 = k_score_giant
+     *   21 arena-path DP (k_dp*): 0 not launched, 2 = 16-bit count tables, 4 = 32-bit
+     *   22 a scoring plan (FSEG_SCORE_PLAN) laid the stage out over the side streams
+     *   23 problems of the arena path
+     *   24..26 work items of the small / mid / large class k_score was launched over (a problem is one work item or more) */
+    FSEG_TAP_PATHS = 18        /* int32[27]                                                                            */
 };
 int fseg_tap(fseg_ctx *ctx, int what, void *dst, int64_t cap_bytes, int64_t *n_bytes);
 

@@ -58,4 +58,6 @@ def as_oracle_result(g):
     return dict(error=0, errmsg="", pos_off=pos_off, Y_raw=g["Y_raw"].astype(np.float64), Y=g["Y"],
                 threshold=float(g["threshold"]), cand_off=g["cand_off"], cands=g["cands"], fixed_off=g["fixed_off"],
                 fixed=g["fixed"], finalc_off=g["finalc_off"], finalc=g["finalc"], refine_off=g["refine_off"],
-                refine=g["refine"], final_off=final_off, final_y=final_y, final_pos=final_pos, labels=g["labels"])
+                refine=g["refine"], final_off=final_off, final_y=final_y, final_pos=final_pos, labels=g["labels"],
+                prob_interval=g["problems"][:, 0], prob_start=g["problems"][:, 1], prob_end=g["problems"][:, 2],
+                prob_nchain=g["problems"][:, 3])

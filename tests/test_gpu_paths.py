@@ -80,16 +80,89 @@ SWITCHES = [
 ]
 
 
-@pytest.mark.parametrize("env", SWITCHES, ids=["+".join("%s=%s" % kv for kv in e.items()) for e in SWITCHES])
+# What the launch census (the `paths` tap, include/freddie_seg.h) must say after a SWITCHES line has run, and on which batch.
+# mixed_batch() holds 202 DP problems whose widest sees 930 reads: under the default FSEG_FUSE_LANES all of it takes the arena
+# path, and solved whole (FSEG_FUSE_LANES=1023) it is a small batch -- one launch for every class, no k_dpw, no plan, and with
+# no more than 256 problems no list for k_wave<8> / k_tiny.  A line whose comment names a path of the per-class launches
+# therefore ALSO runs a batch that reaches it: NARROW (solved whole by default, hundreds of problems in every class) or WIDE
+# (problems that see 256-1 023 reads) of tests/test_gpu_scoring_matrix.py.  A value may be a predicate.
+NONZERO = lambda v: v != 0      # noqa: E731
+ARENA = dict(fuse_on=0, solve8=0, wide16=0, dpw=0, arena_dp=2, score=NONZERO, n_work=NONZERO)
+FUSED = dict(small_batch=0, fuse_on=1, solve8=7, score=0, arena_dp=0, tiny_kernel=1)
+CENSUS = {
+    "FSEG_SCAN_SINGLE_MAX=0": ("mixed", ARENA),
+    "FSEG_FORCE_SCAN_STALL=1": ("mixed", ARENA),
+    "FSEG_NO_GRAPH=1": ("mixed", ARENA),
+    "FSEG_NO_FORK=1": ("mixed", dict(ARENA, plan=0)),
+    "FSEG_NO_GRAPH=1+FSEG_NO_FORK=1": ("mixed", dict(ARENA, plan=0)),
+    "FSEG_NO_SIZED=1": ("mixed", ARENA),                                            # (the census of the replay; the unsized first run launched every instance over guessed lists)
+    "FSEG_NO_SIZED=1+FSEG_FORCE_SCAN_STALL=1": ("mixed", ARENA),
+    "FSEG_TINY_FROM=0": ("mixed", dict(ARENA, tiny_on=1, tiny_kernel=1, n_tiny=NONZERO)),
+    "FSEG_NO_FUSE=1": ("NARROW", dict(ARENA, small_batch=0, score=7, n_solve0=0, n_solve1=0, n_solve2=0, tiny_kernel=1)),
+    "FSEG_NO_FUSE=1+FSEG_TINY_FROM=1000000000+FSEG_NO_SIZED=1": ("NARROW", dict(ARENA, small_batch=0, score=7, tiny_on=0, tiny_kernel=0, n_tiny=0)),
+    "FSEG_TINY_FROM=1000000000": ("NARROW", dict(FUSED, tiny_on=0, tiny_kernel=0, n_tiny=0, dpw=15)),
+    "FSEG_NO_WAVE=1": ("NARROW", dict(FUSED, wave_on=0, tiny_kernel=2, n_tiny=NONZERO)),
+    "FSEG_FUSE_LANES=255": ("NARROW", dict(ARENA, small_batch=0, score=7)),         # (NARROW's widest problem sees 500 reads)
+    "FSEG_FUSE_LANES=1023": ("WIDE", dict(FUSED, wide16=NONZERO, dpw=15)),
+    "FSEG_SCORE_PLAN=0": ("NARROW", dict(FUSED, plan=0, dpw=15)),
+    "FSEG_SCORE_PLAN=BM|gTS": ("NARROW", dict(FUSED, plan=1, dpw=15, wide16=7)),    # no W: the 16-bit instances per class
+    "FSEG_SCORE_PLAN=B|M|S|g|T": ("NARROW", dict(FUSED, plan=0, dpw=15)),
+    "FSEG_SCORE_PLAN=gBMTS": ("NARROW", dict(FUSED, plan=1, dpw=15)),
+    "FSEG_SCORE_PLAN=B|gM|gS|gT": ("NARROW", dict(FUSED, plan=1, dpw=15)),
+    "FSEG_FORCE_KEY64=1": ("NARROW", dict(FUSED, key32=0, dpw=15)),
+    "FSEG_FORCE_KEY64=1+FSEG_NO_WAVE=1+FSEG_SCORE_PLAN=0": ("NARROW", dict(FUSED, key32=0, tiny_kernel=2, dpw=15)),
+    "FSEG_GLOBAL_SORT=1": ("mixed", ARENA),
+    "FSEG_NO_SDMA_D2H=1": ("mixed", ARENA),
+    "FSEG_SPLIT_DP=0": ("NARROW", dict(FUSED, dpw=0)),
+    "FSEG_SPLIT_DP=0+FSEG_FORCE_KEY64=1": ("NARROW", dict(FUSED, dpw=0, key32=0)),
+    "FSEG_SPLIT_DP=5+FSEG_SCORE_PLAN=BM|gTS": ("NARROW", dict(FUSED, plan=1, dpw=13)),
+    "FSEG_SPLIT_DP=15": ("NARROW", dict(FUSED, dpw=7)),
+    "FSEG_SPLIT_DP=7+FSEG_FORCE_KEY64=1+FSEG_FUSE_LANES=1023+FSEG_WIDE_BY_SEEN=1": ("WIDE", dict(FUSED, dpw=15, key32=0, wide16=NONZERO)),
+    "FSEG_NO_FORK=1+FSEG_FORCE_KEY64=1+FSEG_FUSE_LANES=1023": ("WIDE", dict(FUSED, plan=0, dpw=15, key32=0, wide16=NONZERO)),
+    "FSEG_FUSE_LANES=1023+FSEG_WIDE_BY_SEEN=1": ("WIDE", dict(FUSED, dpw=15, wide16=NONZERO)),
+    "FSEG_FUSE_LANES=1023+FSEG_WIDE_BY_SEEN=1+FSEG_SPLIT_DP=0": ("WIDE", dict(FUSED, dpw=0, wide16=NONZERO)),
+    "FSEG_FUSE_LANES=1023+FSEG_WIDE_BY_SEEN=1+FSEG_FORCE_KEY64=1": ("WIDE", dict(FUSED, dpw=15, key32=0, wide16=NONZERO)),
+    "FSEG_FUSE_LANES=1023+FSEG_SCORE_PLAN=gM|B|gTS": ("WIDE", dict(FUSED, plan=1, dpw=15, wide16=NONZERO)),
+    "FSEG_THR_PART=1": ("mixed", dict(ARENA, thr_part=1)),
+    "FSEG_THR_PART=0": ("mixed", dict(ARENA, thr_part=0)),
+    "FSEG_THR_PART=1+FSEG_NO_FORK=1+FSEG_NO_GRAPH=1": ("mixed", dict(ARENA, thr_part=1, plan=0)),
+    "FSEG_LABEL_BYTES=1": ("mixed", dict(ARENA, label_packed=0)),
+    "FSEG_DEV_SYNC=0": ("NARROW", dict(FUSED, plan=1, dpw=15)),
+}
+SWITCH_IDS = ["+".join("%s=%s" % kv for kv in e.items()) for e in SWITCHES]
+assert sorted(CENSUS) == sorted(SWITCH_IDS)
+
+
+def assert_census(ctx, want):
+    got = ctx.paths()
+    for k, v in want.items():
+        assert v(got[k]) if callable(v) else got[k] == v, "census word %s = %d (%r)" % (k, got[k], got)
+
+
+@pytest.mark.parametrize("env", SWITCHES, ids=SWITCH_IDS)
 def test_diagnostic_switches_keep_parity(env, monkeypatch):
     for k, v in env.items():
         monkeypatch.setenv(k, v)
+    which, want = CENSUS["+".join("%s=%s" % kv for kv in env.items())]
     parts, oracles = mixed_batch()
     ctx = _lib.Context(0)
     try:
+        if "FSEG_NO_SIZED" in env:                          # guessed arenas: the host enqueues the first run without knowing any list's size ...
+            util.run_gpu(ctx, parts)
+            first = ctx.paths()
+            assert first["known"] == 0 and first["n_work"] == -1 and first["n_arena_prob"] == -1 and first["score"] & 7 == 7, first
+            if "FSEG_NO_FUSE" not in env:                   # ... so every instance of every class goes over the whole problem list
+                assert first["solve8"] == 7 and first["wide16"] == 7 and first["n_solve0"] == first["n_wide2"] == -1, first
+            assert util.compare_partitions(ctx, parts, oracles)["y_identical"]
         check_twice(ctx, parts, oracles)
+        if which == "mixed":
+            assert_census(ctx, dict(dict(label_packed=1, thr_part=0), **want))     # (12 partitions: the chunk kernels unless told otherwise)
         one = [parts[3]]                                    # a one-partition (small) batch on the same context
         check_twice(ctx, one, [oracles[3]])
+        if which != "mixed":                                # the batch on which this line reaches the path its comment names
+            import test_gpu_scoring_matrix as matrix
+            check_twice(ctx, matrix.batch(which), matrix.oracles(which, "defaults"))
+            assert_census(ctx, want)
     finally:
         ctx.close()
 

@@ -1,0 +1,323 @@
+"""The scoring stage's kernel instances crossed with the parameters that change their arithmetic.
+
+test_gpu_paths.py forces every instance through the FSEG_* switches, under util.DEFAULTS only; test_gpu_fuzz.py varies the
+parameters, under the default switches only.  Here every INSTANCE SET below (one context each: the switches are read by
+fseg_create) runs every FLAVOUR, every tap against the CPU oracle on the first (sized) run and on a replay, and every case
+asserts from the launch census (the `paths` tap, include/freddie_seg.h) that the instance its set names did the work: the
+batch is not a small batch, the lists the host launched over hold exactly the oracle's problems of each size class, and the
+named instance handled at least 10 problems in every class the flavour's problem list populates with at least 10.
+
+Batches.  test_gpu_paths.mixed_batch() cannot serve: it holds 202 DP problems (three candidates and more; the oracle's list
+also counts the pairs of adjacent fixed candidates) -- a small batch once it is solved whole -- and its widest problem sees 930
+reads, so under the default switches all of it takes the arena path.  Two batches of its recipe (make_partition, max_span = 0)
+instead:
+  NARROW  16 partitions of 380-500 reads + 12 of 150-249 reads: no problem sees more than 511 reads, so the batch is solved whole
+          by default; about 600 problems, dozens in every class; some keep more than 255 reads (the 16-bit instances run beside
+          the 8-bit ones by the kept-read rule).
+  WIDE    10 partitions of 560-956 reads: all but a handful of problems see 256-1 023 reads; with FSEG_FUSE_LANES=1023 and
+          FSEG_WIDE_BY_SEEN=1 the 16-bit-counter instances take them in every class.
+
+Which classes are reached (problems of 3-8 / 9-16 / 17-32 / 33-60 candidates; "all" = every flavour but the ones listed):
+  set                                    batch   instance                                    classes
+  default                                NARROW  k_wave<8>; 8-bit k_solve + k_dpw (8 waves)  all four, every flavour
+  FSEG_SPLIT_DP=0                        NARROW  8-bit k_solve, the DP its tail              all four, every flavour
+  FSEG_SPLIT_DP=15                       NARROW  8-bit k_solve + one-wave k_dpw              all four, every flavour
+  FSEG_FORCE_KEY64=1 (+ SPLIT_DP=0)      NARROW  the 64-bit-key instances of the above       all four, every flavour
+  FUSE_LANES=1023 + WIDE_BY_SEEN (+ ..)  WIDE    16-bit k_solve (+ k_dpw / tail / 64-bit)    all four; see EMPTIED for the max_problem_size flavours
+  FSEG_NO_FUSE=1                         NARROW  k_wave<8>; k_score + k_dp (arena path)      all four, every flavour
+  FSEG_TINY_FROM=0 + FSEG_NO_WAVE=1      NARROW  k_tiny                                      3-8; the others as default
+  FSEG_TINY_FROM=1000000000              NARROW  k_solve<16> takes the 3-8 class too         all four, every flavour
+EMPTIED states the classes a flavour leaves with fewer than 10 problems (nothing is asked of the instance there); the test
+checks the table against the oracle, so a class cannot go empty unnoticed."""
+import functools
+
+import numpy as np
+import pytest
+
+import util
+from freddie_amd import _lib
+
+pytestmark = pytest.mark.gpu
+
+COMBINED = dict(ignore_ends=False, min_read_support_outside=0, max_problem_size=30, threshold_rate=0.8, sigma=3.0)
+FLAVOURS = [("defaults", {}), ("ends", dict(ignore_ends=False)), ("support0", dict(min_read_support_outside=0)),
+            ("support10", dict(min_read_support_outside=10)), ("support1000", dict(min_read_support_outside=1000)),
+            ("mps10", dict(max_problem_size=10)), ("mps30", dict(max_problem_size=30)), ("rate1", dict(threshold_rate=1.0)),
+            ("rate05", dict(threshold_rate=0.5)), ("rate9999", dict(threshold_rate=0.9999)), ("combined", COMBINED)]
+
+# (batch, flavour) -> the size classes (0: 3-8 candidates, 1: 9-16, 2: 17-32, 3: 33-60) it holds fewer than 10 problems of.
+# max_problem_size = 10 breaks every longer run of candidates at its best peaks: nothing above 32 is left, and little above 16.
+EMPTIED = {("NARROW", "mps10"): {3}, ("WIDE", "mps10"): {2, 3}, ("WIDE", "mps30"): {3}, ("WIDE", "combined"): {3}}
+
+CLASS_BOUNDS = ((3, 8), (9, 16), (17, 32), (33, 60))
+
+
+def _narrow():
+    parts = [util.make_partition(2100 + i, n_reads=380 + 8 * i, n_exons=150 + 12 * i, rp=0.06 + 0.02 * (i % 4), max_span=0) for i in range(16)]
+    parts += [util.make_partition(2200 + i, n_reads=150 + 9 * i, n_exons=120 + 14 * i, rp=0.04 + 0.03 * (i % 4), max_span=0) for i in range(12)]
+    return parts
+
+
+def _wide():
+    return [util.make_partition(2300 + i, n_reads=560 + 44 * i, n_exons=150 + 12 * i, rp=0.06 + 0.02 * (i % 4), max_span=0) for i in range(10)]
+
+
+@functools.lru_cache(maxsize=None)
+def batch(name):
+    return {"NARROW": _narrow, "WIDE": _wide}[name]()
+
+
+@functools.lru_cache(maxsize=None)
+def oracles(name, flavour):
+    """The oracle's results for one batch under one flavour: computed once, shared by every instance set, never changed."""
+    return [util.run_oracle(p, dict(FLAVOURS)[flavour]) for p in batch(name)]
+
+
+def class_counts(results):
+    """DP problems (three candidates and more) of the oracle's problem lists per size class."""
+    n = np.concatenate([o["prob_end"] - o["prob_start"] + 1 for o in results])
+    assert n.max() <= 60, n.max()
+    return np.array([int(((n >= lo) & (n <= hi)).sum()) for lo, hi in CLASS_BOUNDS])
+
+
+def lanes_seen(part, o):
+    """Reads (lanes: every rep rep_weight times) each DP problem of the partition sees -- the rule of k_prob_range on the host -- beside
+    the problem's size: the lanes, ordered by first position, from the first whose running maximum of the last positions reaches
+    the window's first candidate to the first that starts at or after its last."""
+    first, last = part.ex_ts[part.rep_exon_off[:-1]], part.ex_te[part.rep_exon_off[1:] - 1]
+    order = np.lexsort((np.arange(part.n_reps), first))
+    lanes = np.repeat(order, part.rep_weight[order])
+    start, pmax = first[lanes], np.maximum.accumulate(last[lanes])
+    out = []
+    for k, s, e in zip(o["prob_interval"], o["prob_start"], o["prob_end"]):
+        if e - s + 1 >= 3:
+            c = o["cands"][o["cand_off"][k]:o["cand_off"][k + 1]]
+            lo = np.searchsorted(pmax, part.iv_start[k] + c[s], "left")
+            out.append((e - s + 1, int(np.searchsorted(start[lo:], part.iv_start[k] + c[e], "left"))))
+    return np.array(out).reshape(-1, 2)
+
+
+@functools.lru_cache(maxsize=None)
+def narrow_counts(name, flavour):
+    """Per size class, the problems that see at most 255 reads: they cannot keep more, so the 8-bit-counter instances take them."""
+    sn = np.concatenate([lanes_seen(p, o) for p, o in zip(batch(name), oracles(name, flavour))])
+    sn = sn[sn[:, 1] <= 255, 0]
+    return np.array([int(((sn >= lo) & (sn <= hi)).sum()) for lo, hi in CLASS_BOUNDS])
+
+
+def expect_packed(params):
+    p = dict(util.DEFAULTS, **params)
+    return int(p["threshold_rate"] < 1.0 and bool((util.param_tables(p)["h_table"][1:] < 1.0).all()))
+
+
+def dpw_mask(census, split_dp):
+    """The classes whose DP k_dpw must have taken: those FSEG_SPLIT_DP names that have a solve list; bit 3 = eight waves for the large class."""
+    m = sum(1 << q for q in range(3) if (split_dp >> q) & 1 and census["n_solve%d" % q] > 0)
+    return m | (8 if (m & 4) and not split_dp & 8 else 0)
+
+
+# what the census must say for a set: (name, switches, batch, check(census, counts) -> problems the named instance handled per class)
+def _fused(split_dp, key32=1, tiny="wave"):
+    def check(c, cnt, narrow):
+        assert c["fuse_on"] == 1 and c["key32"] == key32 and c["known"] == 1, c
+        assert c["score"] == 0 and c["arena_dp"] == 0 and c["n_work"] == 0, c                   # nothing on the arena path
+        if tiny == "none":
+            assert c["tiny_on"] == 0 and c["tiny_kernel"] == 0 and c["n_tiny"] == 0, c
+            lists = [cnt[0] + cnt[1], cnt[2], cnt[3]]
+        else:
+            assert c["tiny_on"] == 1 and c["tiny_kernel"] == (1 if tiny == "wave" else 2) and c["wave_on"] == (tiny == "wave"), c
+            assert c["n_tiny"] == cnt[0], (c, cnt)
+            lists = [cnt[1], cnt[2], cnt[3]]
+        assert [c["n_solve0"], c["n_solve1"], c["n_solve2"]] == lists, (c, cnt)
+        assert c["solve8"] & 7 == sum(1 << q for q in range(3) if lists[q] > 0), c             # a per-class launch for every list
+        assert c["dpw"] == dpw_mask(c, split_dp), (c, split_dp)
+        by8 = [lists[q] - c["n_wide%d" % q] for q in range(3)]                                  # what the 8-bit instances keep
+        if tiny == "none":          # the small list holds two classes: of each, the 8-bit instance took at least what sees no more than 255 reads
+            assert by8[0] >= narrow[0] + narrow[1], (c, narrow)
+            return [narrow[0], narrow[1], by8[1], by8[2]]
+        return [c["n_tiny"], *by8]
+    return check
+
+
+def _wide16(split_dp, key32=1):
+    def check(c, cnt, narrow):
+        assert c["fuse_on"] == 1 and c["key32"] == key32 and c["known"] == 1, c
+        assert c["score"] == 0 and c["arena_dp"] == 0, c
+        assert c["tiny_on"] == 1 and c["tiny_kernel"] == 1 and c["n_tiny"] == cnt[0], (c, cnt)
+        assert [c["n_solve0"], c["n_solve1"], c["n_solve2"]] == list(cnt[1:]), (c, cnt)
+        assert c["wide16"] != 0, c                                                              # 16-bit-counter launches
+        if c["wide16"] & 7:                                                                     # ... per class: each class that has wide problems
+            assert c["wide16"] & 7 == sum(1 << q for q in range(3) if c["n_wide%d" % q] > 0), c
+        assert c["dpw"] == dpw_mask(c, split_dp), (c, split_dp)
+        return [c["n_tiny"], c["n_wide0"], c["n_wide1"], c["n_wide2"]]                          # (the 3-8 class is k_wave's whatever it sees)
+    return check
+
+
+def _arena(c, cnt, narrow):
+    assert c["fuse_on"] == 0 and c["known"] == 1, c
+    assert c["n_solve0"] == c["n_solve1"] == c["n_solve2"] == 0 and c["solve8"] == 0 and c["wide16"] == 0 and c["dpw"] == 0, c
+    assert c["n_work"] > 0 and c["score"] & 7 == sum(1 << q for q in range(3) if cnt[q + 1] > 0), (c, cnt)
+    assert c["arena_dp"] == 2 and c["n_arena_prob"] == cnt[1:].sum(), (c, cnt)
+    assert c["tiny_kernel"] == 1 and c["n_tiny"] == cnt[0], (c, cnt)
+    work = [c["n_score0"], c["n_score1"], c["n_score2"]]                                        # what k_score<16 | 32 | 60> were launched over
+    assert sum(work) == c["n_work"] and all(work[q] >= cnt[q + 1] for q in range(3)), (c, cnt)  # a work item and more per problem
+    return [c["n_tiny"], *(min(work[q], cnt[q + 1]) for q in range(3))]
+
+
+WIDE_ENV = {"FSEG_FUSE_LANES": "1023", "FSEG_WIDE_BY_SEEN": "1"}
+SETS = [
+    ("default", {}, "NARROW", _fused(7)),
+    ("split0", {"FSEG_SPLIT_DP": "0"}, "NARROW", _fused(0)),
+    ("split15", {"FSEG_SPLIT_DP": "15"}, "NARROW", _fused(15)),
+    ("key64", {"FSEG_FORCE_KEY64": "1"}, "NARROW", _fused(7, key32=0)),
+    ("key64-split0", {"FSEG_FORCE_KEY64": "1", "FSEG_SPLIT_DP": "0"}, "NARROW", _fused(0, key32=0)),
+    ("wide16", dict(WIDE_ENV), "WIDE", _wide16(7)),
+    ("wide16-key64", dict(WIDE_ENV, FSEG_FORCE_KEY64="1"), "WIDE", _wide16(7, key32=0)),
+    ("wide16-split0", dict(WIDE_ENV, FSEG_SPLIT_DP="0"), "WIDE", _wide16(0)),
+    ("no-fuse", {"FSEG_NO_FUSE": "1"}, "NARROW", _arena),
+    ("k_tiny", {"FSEG_TINY_FROM": "0", "FSEG_NO_WAVE": "1"}, "NARROW", _fused(7, tiny="tiny")),
+    ("no-tiny", {"FSEG_TINY_FROM": "1000000000"}, "NARROW", _fused(7, tiny="none")),
+]
+
+
+def check_census(ctx, check, which, flavour, params, results):
+    c = ctx.paths()
+    cnt = class_counts(results)
+    assert c["small_batch"] == 0, c
+    assert c["label_packed"] == expect_packed(params), c
+    handled = check(c, cnt, narrow_counts(which, flavour))
+    emptied = EMPTIED.get((which, flavour), set())
+    assert emptied == {q for q in range(4) if cnt[q] < 10}, (which, flavour, cnt)               # the table in the docstring is the truth
+    for q in range(4):
+        if q not in emptied:
+            assert handled[q] >= 10, "%s / %s: the instance handled %d problems of class %d (%r, oracle %r)" % (which, flavour, handled[q], q, c, cnt)
+
+
+@pytest.mark.parametrize("name,env,which,check", SETS, ids=[s[0] for s in SETS])
+def test_instance_set_under_every_flavour(name, env, which, check, monkeypatch):
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    parts = batch(which)
+    ctx = _lib.Context(0)
+    try:
+        for flavour, params in FLAVOURS:
+            results = oracles(which, flavour)
+            util.run_gpu(ctx, parts, params)                        # the first run under these parameters (sized)
+            check_census(ctx, check, which, flavour, params, results)
+            assert util.compare_partitions(ctx, parts, results)["y_identical"], flavour
+            ctx.run(); ctx.sync()                                   # ... and a replay
+            check_census(ctx, check, which, flavour, params, results)
+            assert util.compare_partitions(ctx, parts, results)["y_identical"], flavour
+    finally:
+        ctx.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Weighted reps: a few reps that stand for hundreds or tens of thousands of reads.  Counter width and the width of the
+# DP's count tables must follow the lanes (reads), not the reps; the oracle costs by reps and takes the weights as they are.
+# (seed, reads generated, exons, weights) -> reps, lanes, what the shape is for
+WEIGHTED = [
+    ((31, 60, 20, 7), 60, 420, "every weight x 7: the lanes cross 255 with 60 reps"),
+    ((32, 60, 20, 40), 60, 2400, "every weight x 40: beyond 1 023 lanes, the arena path"),
+    ((33, 12, 14, tuple(300 if r % 6 == 1 else 1 for r in range(12))), 12, 610, "two reps of 300 reads: a rep alone overflows 8 bits"),
+    ((34, 6, 14, (70000, 1, 1, 1, 1, 1)), 6, 70005, "one rep of 70 000 reads: the 32-bit-count DP with six reps"),
+    ((35, 60, 40, (1 / 3, 5000)), 60, 115037, "23 reps of 5 000 reads, problems of up to 18 candidates"),
+]
+
+
+@functools.lru_cache(maxsize=None)
+def weighted():
+    parts = [util.weighted_partition(*args) for args, _, _, _ in WEIGHTED]
+    for p, (_, reps, lanes, what) in zip(parts, WEIGHTED):
+        assert p.n_reps == reps and int(p.rep_weight.sum()) == lanes, (what, p.n_reps, int(p.rep_weight.sum()))
+    return parts, [util.run_oracle(p) for p in parts]
+
+
+@pytest.mark.parametrize("env", [{}, {"FSEG_FUSE_LANES": "1023"}, {"FSEG_NO_FUSE": "1"}], ids=["default", "fuse-1023", "no-fuse"])
+def test_weighted_reps(env, monkeypatch):
+    """Each shape alone (a small batch) and all of them inside the NARROW batch, every tap against the oracle, first run and
+    replay; the census says which path a shape's lanes sent it down."""
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    parts, results = weighted()
+    fuse_lanes = 0 if "FSEG_NO_FUSE" in env else int(env.get("FSEG_FUSE_LANES", 511))
+    ctx = _lib.Context(0)
+    try:
+        for part, o, (_, _, _, what) in zip(parts, results, WEIGHTED):
+            assert o["error"] == 0, o["errmsg"]
+            seen = int(lanes_seen(part, o)[:, 1].max())
+            n_prob = int((o["prob_end"] - o["prob_start"] + 1 >= 3).sum())
+            assert n_prob > 0, what
+            for rnd in range(2):
+                if rnd == 0:
+                    util.run_gpu(ctx, [part])
+                else:
+                    ctx.run(); ctx.sync()
+                util.compare_partitions(ctx, [part], [o])
+                c, sz = ctx.paths(), ctx.sizes()
+                assert sz["max_problem_reads"] == seen and sz["n_problems"] == n_prob, (what, sz, seen, n_prob)
+                assert c["fuse_on"] == int(seen <= fuse_lanes), (what, c, seen)
+                if seen <= fuse_lanes:                               # solved whole: one launch over every class, 16-bit counters from 256 lanes on
+                    assert c["small_batch"] == 1 and c["solve8"] == 8 and c["score"] == 0 and c["arena_dp"] == 0, (what, c)
+                    assert (c["wide16"] == 8) == (seen > 255), (what, c, seen)
+                else:                                                # the arena path; 32-bit count tables from 65 536 lanes on
+                    assert c["score"] != 0 and c["n_work"] > 0 and c["solve8"] == 0 and c["wide16"] == 0, (what, c)
+                    assert c["arena_dp"] == (4 if seen >= 65536 else 2), (what, c, seen)
+        big, big_results = batch("NARROW") + parts, oracles("NARROW", "defaults") + results
+        util.run_gpu(ctx, big)
+        util.compare_partitions(ctx, big, big_results)
+        c = ctx.paths()
+        assert c["small_batch"] == 0 and c["fuse_on"] == 0 and c["arena_dp"] == 4 and c["n_work"] > 0, c      # 100 000 lanes in one window: all of it on the arena path
+        ctx.run(); ctx.sync()
+        util.compare_partitions(ctx, big, big_results)
+        assert ctx.paths() == c
+    finally:
+        ctx.close()
+
+
+def test_weighted_reps_in_the_per_class_sixteen_bit_instances(monkeypatch):
+    """Counter width follows lanes, not reps, in a batch that is not small: the 420-lane and the 610-lane shape inside the WIDE
+    batch, solved whole (FSEG_FUSE_LANES=1023, wide by the reads seen), no k_wave (so the shapes' problems of a few candidates
+    go to k_solve<16>) and a plan without W (so every class's own 16-bit-counter instance is launched, its DPs handed to
+    k_dpw).  The census must show exactly the problems that see more than 255 lanes in each class's 16-bit instance."""
+    for k, v in {"FSEG_FUSE_LANES": "1023", "FSEG_WIDE_BY_SEEN": "1", "FSEG_TINY_FROM": "1000000000", "FSEG_SCORE_PLAN": "gM|B|gTS"}.items():
+        monkeypatch.setenv(k, v)
+    wparts, wresults = weighted()
+    parts, results = batch("WIDE") + [wparts[0], wparts[2]], oracles("WIDE", "defaults") + [wresults[0], wresults[2]]
+    seen = np.concatenate([lanes_seen(p, o) for p, o in zip(parts, results)])
+    assert seen[:, 1].max() <= 1023
+    of_shapes = np.concatenate([lanes_seen(p, o) for p, o in zip(parts[-2:], results[-2:])])
+    assert (of_shapes[:, 1] > 255).sum() >= 6 and of_shapes[:, 0].max() <= 16, of_shapes       # the shapes' problems: wide, all in the small list
+    lists = [(3, 16), (17, 32), (33, 60)]
+    n_list = [int(((seen[:, 0] >= lo) & (seen[:, 0] <= hi)).sum()) for lo, hi in lists]
+    n_wide = [int(((seen[:, 0] >= lo) & (seen[:, 0] <= hi) & (seen[:, 1] > 255)).sum()) for lo, hi in lists]
+    ctx = _lib.Context(0)
+    try:
+        for rnd in range(2):
+            if rnd == 0:
+                util.run_gpu(ctx, parts)
+            else:
+                ctx.run(); ctx.sync()
+            util.compare_partitions(ctx, parts, results)
+            c = ctx.paths()
+            assert c["small_batch"] == 0 and c["fuse_on"] == 1 and c["tiny_kernel"] == 0 and c["score"] == 0, c
+            assert [c["n_solve0"], c["n_solve1"], c["n_solve2"]] == n_list, (c, n_list)
+            assert c["wide16"] & 7 == 7 and [c["n_wide0"], c["n_wide1"], c["n_wide2"]] == n_wide, (c, n_wide)
+            assert c["dpw"] == 15, c
+    finally:
+        ctx.close()
+
+
+def test_lane_preparation_of_a_rep_of_seventy_thousand_reads(gpu_ctx):
+    """fseg_upload's lanes for six reps of which one stands for 70 000 reads: every rep repeated rep_weight times in
+    the order of the first positions, the running maximum of the last positions beside it (np.repeat on the host)."""
+    parts, _ = weighted()
+    part = parts[3]
+    assert part.n_reps <= 6 and part.rep_weight.sum() > 65535
+    util.run_gpu(gpu_ctx, [part])
+    first, last = part.ex_ts[part.rep_exon_off[:-1]], part.ex_te[part.rep_exon_off[1:] - 1]
+    order = np.lexsort((np.arange(part.n_reps), first))
+    lanes = np.repeat(order, part.rep_weight[order])
+    assert np.array_equal(gpu_ctx.tap("lane_start"), first[lanes])
+    assert np.array_equal(gpu_ctx.tap("lane_pmax"), np.maximum.accumulate(last[lanes]))
+    assert np.array_equal(gpu_ctx.tap("lane_exons"), np.stack([part.rep_exon_off[lanes], part.rep_exon_off[lanes + 1]], axis=1))

@@ -43,8 +43,9 @@ def compare_partitions(ctx, parts, oracles, y_tol=1e-6):
     pos_off = ctx.tap("pos_off"); y_raw = ctx.tap("y_raw"); y = ctx.tap("y"); thr = ctx.tap("threshold")
     cand_off = ctx.tap("cand_off"); cand_y = ctx.tap("cand_y"); fixed = ctx.tap("fixed"); chosen = ctx.tap("chosen")
     final_off = ctx.tap("final_off"); final_y = ctx.tap("final_y")
+    problems = ctx.tap("problems")
     pfo, final_pos, label_off, labels = ctx.download()
-    k0 = 0
+    k0 = q0 = 0
     report = dict(max_y_err=0.0, y_identical=True)
     for p, (part, o) in enumerate(zip(parts, oracles)):
         assert o["error"] == 0, o["errmsg"]
@@ -77,8 +78,39 @@ def compare_partitions(ctx, parts, oracles, y_tol=1e-6):
         S = (f1 - f0) - 1
         lab = labels[label_off[p]:label_off[p + 1]].reshape(part.n_reps, S)
         assert np.array_equal(lab, o["labels"] + ord("0")), "labels p%d" % p
+        # the problem list (k_prob_range / k_prob_scan2 / k_prob_emit): a row per DP problem of at least three candidates -- batch-wide
+        # interval, first candidate inside the interval, candidates, triples on the DP's backtrack -- in the order of the candidates
+        # (a problem's slot is the scan's rank of its last candidate), which is the oracle's: interval by interval, left to right.
+        # The oracle also lists the pairs of adjacent fixed candidates, which have nothing to optimise.
+        n = o["prob_end"] - o["prob_start"] + 1
+        keep = n >= 3
+        want = np.stack([o["prob_interval"][keep] + k0, o["prob_start"][keep], n[keep], o["prob_nchain"][keep]], axis=1)
+        got = problems[q0:q0 + len(want)]
+        assert np.array_equal(got, want), "problems p%d: rows %r differ" % (p, np.flatnonzero((got != want).any(axis=1))[:8] if got.shape == want.shape else (got.shape, want.shape))
+        q0 += len(want)
         k0 += K
+    assert q0 == len(problems), "problems: %d rows on the device, %d in the oracles" % (len(problems), q0)
     return report
+
+
+def weighted_partition(seed, n_reads, n_exons, weights, **gen_kw):
+    """A partition of few reps that stand for many reads: make_partition(..., max_span=0) with rep_weight overwritten (jittered
+    synthetic reads rarely collapse, so no generated batch has a rep of more than a few reads).  `weights`: a factor for every
+    rep's weight, (share, factor) for a seeded random share of the reps, or the weights themselves.  The oracle takes the
+    weights as they are; on the device every rep becomes rep_weight lanes."""
+    part = make_partition(seed, n_reads=n_reads, n_exons=n_exons, max_span=0, **gen_kw)
+    w = part.rep_weight.astype(np.int64)
+    if np.ndim(weights) == 0:
+        w = w * int(weights)
+    elif isinstance(weights, tuple) and len(weights) == 2 and weights[0] < 1:
+        share, factor = weights
+        w = np.where(np.random.default_rng(seed).random(len(w)) < share, w * int(factor), w)
+    else:
+        w = np.asarray(weights, np.int64)
+        assert w.shape == part.rep_weight.shape
+    assert w.min() >= 1 and w.sum() < 2 ** 31
+    part.rep_weight = w.astype(np.int32)
+    return part
 
 
 def pack_labels(labels_ascii):
