@@ -62,6 +62,10 @@ def load():
     for name in ("fhost_listing_contig_of", "fhost_listing_tint", "fhost_listing_size"):
         getattr(L, name).restype = vp
         getattr(L, name).argtypes = [vp]
+    L.fhost_read_segment.restype = ctypes.c_int32                    # (the struct is cluster_prep._HostSegments, passed by reference)
+    L.fhost_read_segment.argtypes = [cpp, ctypes.c_int32, ctypes.c_int32, vp]
+    L.fhost_segments_free.restype = None
+    L.fhost_segments_free.argtypes = [vp]
     L.fhost_touch.restype = ctypes.c_int32
     L.fhost_touch.argtypes = [cpp, ctypes.c_int32, ctypes.c_int32]
     _lib = L

@@ -12,6 +12,9 @@ Reference map (file:line of vpc-ccg/freddie ``py/freddie_cluster.py``):
        :256-257, even split and incompatible pairs :258-274 (GPU: Context.partition, flat arrays)
   preprocess_ilp + partition_reads on tints that are not preprocessed yet -> pack_labels(), preprocess_ilp_batch(),
        cluster_arrays_batch(): I / C / FL, the dedupe and everything behind it in one device call (Context.partition_labels)
+  segment_*.tsv files -> arrays without a Python loop over reads: read_segment_arrays() (the native reader of libfreddie_host.so),
+       Context.group_reads() / Context.partition_segment() (read_reps :154-164 on the GPU, then all of the above),
+       cluster_files_batch(), tints_from_arrays() (back to the dicts, for code that wants them)
 The ILP (run_ilp, Gurobi) and everything after it are out of scope.  There is no CPU implementation of the quadratic
 loops in this package: without the HIP library partition_reads() raises.  FCLU_HOST_PARTITIONS=1 keeps :256-274 on the
 host, behind the GPU's graph (adjacency_matrix + _components + _partitions_from_graph): for A/B runs and timings.
@@ -152,7 +155,8 @@ CLUSTER_SO = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libfreddi
 CLUSTER_SRC = [os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "freddie_cluster.hip")]
 EXPORTS = ["fclu_abi_version", "fclu_create", "fclu_destroy", "fclu_last_error", "fclu_compat_graph", "fclu_last_timing",
            "fclu_partition", "fclu_partition_adj", "fclu_partition_results", "fclu_partition_timing",
-           "fclu_preprocess", "fclu_preprocess_results", "fclu_partition_reads", "fclu_preprocess_timing"]
+           "fclu_preprocess", "fclu_preprocess_results", "fclu_partition_reads", "fclu_preprocess_timing",
+           "fclu_group_reads", "fclu_partition_segment", "fclu_group_results", "fclu_group_timing"]
 ERR_UNSUPPORTED = 3
 _lib = None
 
@@ -188,6 +192,16 @@ class _Prep(ctypes.Structure):
         (name, ctypes.c_void_p) for name in ("row_off", "bits_off", "adj_off", "rep_bits_off", "i_bits", "c_bits", "first", "last",
                                              "raw_first", "raw_last", "rep_node", "node_rep", "mem_off", "mem", "bits",
                                              "node_first", "node_last", "node_tail")]
+
+
+class _Segment(ctypes.Structure):
+    _fields_ = [("n_tint", ctypes.c_int32), ("read_off", ctypes.c_void_p), ("n_seg", ctypes.c_void_p), ("lab_off", ctypes.c_void_p),
+                ("labels", ctypes.c_void_p), ("tok_off", ctypes.c_void_p), ("tok", ctypes.c_void_p), ("tail", ctypes.c_void_p)]
+
+
+class _Groups(ctypes.Structure):
+    _fields_ = [("n_tint", ctypes.c_int32), ("n_reads", ctypes.c_int64), ("n_reps", ctypes.c_int64)] + [
+        (name, ctypes.c_void_p) for name in ("rep_off", "read_rep", "rep_mem_off", "rep_mem", "rep_first")]
 
 
 def build(force=False, verbose=False):
@@ -232,6 +246,14 @@ def load():
     L.fclu_partition_reads.argtypes = [vp, ctypes.POINTER(_Reads), ctypes.c_int32]
     L.fclu_preprocess_timing.restype = ctypes.c_int
     L.fclu_preprocess_timing.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
+    L.fclu_group_reads.restype = ctypes.c_int
+    L.fclu_group_reads.argtypes = [vp, ctypes.POINTER(_Segment)]
+    L.fclu_partition_segment.restype = ctypes.c_int
+    L.fclu_partition_segment.argtypes = [vp, ctypes.POINTER(_Segment), ctypes.c_int32]
+    L.fclu_group_results.restype = ctypes.c_int
+    L.fclu_group_results.argtypes = [vp, ctypes.POINTER(_Groups)]
+    L.fclu_group_timing.restype = ctypes.c_int
+    L.fclu_group_timing.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
     _lib = L
     return L
 
@@ -363,6 +385,56 @@ class Context:
         rc = self._L.fclu_partition_reads(self._h, ctypes.byref(r), int(maximum_ilp_size))
         parts = self._partition_arrays("fclu_partition_reads", rc)
         return self._prep_arrays(), parts
+
+    @staticmethod
+    def _segment(arrays):
+        a = arrays.a if isinstance(arrays, SegmentArrays) else arrays
+        g = _Segment(n_tint=int(a["n_tint"]))
+        keep = []
+        for name, dt in (("read_off", np.int64), ("n_seg", np.int32), ("lab_off", np.int64), ("labels", np.uint32), ("tok_off", np.int64),
+                         ("tok", np.uint32), ("tail", np.uint8)):
+            x = np.ascontiguousarray(a[name], dt)
+            keep.append(x)
+            setattr(g, name, x.ctypes.data if x.size else None)
+        if keep[0].size != g.n_tint + 1 or keep[1].size != g.n_tint or keep[2].size != g.n_tint + 1 or g.n_tint < 0:
+            raise ClusterError("group_reads: read_off / lab_off need n_tint + 1 entries, n_seg n_tint")
+        n = int(keep[0][-1]) if g.n_tint else 0
+        if n > 0 and (keep[4].size != n + 1 or keep[6].size != n or keep[3].size != int(keep[2][-1]) or
+                      keep[5].size != max(int(keep[4][-1]), 0)):
+            raise ClusterError("group_reads: array lengths do not match (tok_off: reads + 1; tail: reads; labels: lab_off[-1]; tok: tok_off[-1])")
+        return g, keep
+
+    def _group_arrays(self):
+        g = _Groups()
+        rc = self._L.fclu_group_results(self._h, ctypes.byref(g))
+        if rc != 0:
+            raise ClusterError("fclu_group_results: " + self._L.fclu_last_error(self._h).decode(), rc)
+        T, N, R = g.n_tint, int(g.n_reads), int(g.n_reps)
+        return dict(n_tint=T, n_reads=N, n_reps=R, rep_off=_copy_out(g.rep_off, T + 1, np.int64), read_rep=_copy_out(g.read_rep, N, np.int32),
+                    rep_mem_off=_copy_out(g.rep_mem_off, R + 1, np.int64), rep_mem=_copy_out(g.rep_mem, N, np.int32),
+                    rep_first=_copy_out(g.rep_first, R, np.int32))
+
+    def group_reads(self, arrays):
+        """read_segment()'s rep grouping of a batch on the device: arrays = read_segment_arrays() (or a dict of the fclu_segment
+        arrays).  Returns numpy arrays named as in include/freddie_cluster.h, fclu_groups."""
+        g, keep = self._segment(arrays)
+        rc = self._L.fclu_group_reads(self._h, ctypes.byref(g))
+        if rc != 0:
+            raise ClusterError("fclu_group_reads: " + self._L.fclu_last_error(self._h).decode(), rc)
+        return self._group_arrays()
+
+    def partition_segment(self, arrays, maximum_ilp_size):
+        """From all reads' rows and token streams to tint['partitions'] of a batch in one device call:
+        (group_reads() arrays, preprocess() arrays of the reps, partition() arrays)."""
+        g, keep = self._segment(arrays)
+        rc = self._L.fclu_partition_segment(self._h, ctypes.byref(g), int(maximum_ilp_size))
+        parts = self._partition_arrays("fclu_partition_segment", rc)
+        return self._group_arrays(), self._prep_arrays(), parts
+
+    def group_timing(self):
+        a, b = ctypes.c_float(), ctypes.c_float()
+        self._L.fclu_group_timing(self._h, ctypes.byref(a), ctypes.byref(b))
+        return dict(keys_ms=a.value, dedupe_ms=b.value)
 
     def preprocess_timing(self):
         a, b = ctypes.c_float(), ctypes.c_float()
@@ -655,3 +727,272 @@ def partition_reads(tint, maximum_ilp_size, ctx=None, verbose=True):
     finally:
         if own:
             ctx.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# segment_*.tsv in, arrays out: the native reader (include/freddie_host.h, fhost_read_segment) and the rep grouping on the device
+# ---------------------------------------------------------------------------------------------------------------
+class _HostSegments(ctypes.Structure):
+    _fields_ = [("owner", ctypes.c_void_p), ("n_file", ctypes.c_int32), ("n_tint", ctypes.c_int32), ("n_read", ctypes.c_int64)] + [
+        (name, ctypes.c_void_p) for name in ("file_declined", "file_line", "file_reason", "file_map", "file_tint_off", "tint_id", "tint_file",
+                                             "tint_chr_off", "tint_chr_len", "n_seg", "pos_off", "pos", "read_off", "lab_off", "rid", "strand",
+                                             "name_off", "name_len", "chr_off", "chr_len", "labels", "tail", "gap_off", "gaps", "clip_off",
+                                             "clips", "poly_off", "polys", "tok_off", "tok")]
+
+
+_CLIP_KEYS = ("SSC", "ESC")
+_POLY_KEYS = ("SA", "ST", "EA", "ET")
+# (name, dtype, what it is counted by, columns): the arrays of a batch; offsets are listed with what they index
+_PER_TINT = (("tint_id", np.int64), ("n_seg", np.int32))
+_PER_READ = (("rid", np.int64), ("strand", np.uint8), ("tail", np.uint8))
+_CSR = (("pos_off", "pos", np.int64, 1, "tint"), ("read_off", None, None, 0, "tint"), ("lab_off", "labels", np.uint32, 1, "tint"),
+        ("gap_off", "gaps", np.int32, 3, "read"), ("clip_off", "clips", np.int32, 2, "read"), ("poly_off", "polys", np.int32, 3, "read"),
+        ("tok_off", "tok", np.uint32, 1, "read"))
+
+
+def _view(ptr, n, dtype):
+    dtype = np.dtype(dtype)
+    if n == 0 or not ptr:
+        return np.zeros(0, dtype)
+    return np.frombuffer((ctypes.c_char * (int(n) * dtype.itemsize)).from_address(ptr), dtype, int(n))
+
+
+def _ints(values, dtype, cols=1):
+    """An integer array of the given dtype; a wider one (in the end Python objects) for the numbers of a file the reader declined."""
+    for dt in (dtype, np.int64, object):
+        try:
+            a = np.array(values, dt)
+            if dt is object or a.size == 0 or (a.astype(object) == np.array(values, object)).all():
+                return a.reshape(-1, cols) if cols > 1 else a.reshape(-1)
+        except OverflowError:
+            pass
+
+
+def _pack_codes(codes):
+    """uint8 label codes [rows, 16 * LW] -> uint32 words, two bits a label (pack_labels()' packing): four labels a byte, the first
+    in the low bits; words little-endian."""
+    q = codes.reshape(codes.shape[0], -1, 4)
+    by = q[:, :, 0] | (q[:, :, 1] << 2) | (q[:, :, 2] << 4) | (q[:, :, 3] << 6)
+    return np.ascontiguousarray(by).view("<u4").astype(np.uint32, copy=False).reshape(-1)
+
+
+def _chunk_from_tints(tints):
+    """The arrays of one file from the mirror's dicts (a file the reader declined).  Its token streams are the mirror's own rep
+    numbers, one token a read: the grouping they give is the mirror's, whatever made the reader decline (a leading zero or a
+    repeated key is in the mirror's rep key as written, not in its dicts)."""
+    a = dict(n_tint=len(tints), tint_chr=[t["chr"] for t in tints], read_name=[], read_chr=[])
+    a["tint_id"] = _ints([t["id"] for t in tints], np.int64)
+    a["n_seg"] = np.array([len(t["segs"]) for t in tints], np.int32)
+    pos, pos_off, read_off, lab_off, labels = [], [0], [0], [0], []
+    rid, strand, tail, gaps, clips, polys, tok = [], [], [], [], [], [], []
+    gap_off, clip_off, poly_off = [0], [0], [0]
+    for t in tints:
+        if t["segs"]:
+            pos.extend([t["segs"][0][0]] + [s[1] for s in t["segs"]])
+        pos_off.append(len(pos))
+        reads, M = t["reads"], len(t["segs"])
+        LW = max((M + 15) // 16, 1)
+        rep_of = {r: i for i, members in enumerate(t["read_reps"]) for r in members}
+        codes = np.zeros((len(reads), LW * 16), np.uint8)
+        for i, r in enumerate(reads):
+            codes[i, :M] = r["data"]
+            rid.append(r["id"]); strand.append(ord(r["strand"]))
+            a["read_name"].append(r["name"]); a["read_chr"].append(r["chr"])
+            pt = r["poly_tail"]
+            cat = 0
+            if len(pt) == 1:
+                (key, (length, _)), = pt.items()
+                if length > 10:
+                    cat = 1 if key in ("SA", "ST") else 2
+            tail.append(cat)
+            gaps.extend([k[0], k[1], v] for k, v in r["gaps"].items()); gap_off.append(len(gaps))
+            clips.extend([_CLIP_KEYS.index(k), v] for k, v in r["softclip"].items()); clip_off.append(len(clips))
+            polys.extend([_POLY_KEYS.index(k), v[0], v[1]] for k, v in pt.items()); poly_off.append(len(polys))
+            tok.append(rep_of[i])
+        labels.append(_pack_codes(codes))
+        read_off.append(len(rid)); lab_off.append(lab_off[-1] + len(reads) * LW)
+    a.update(pos=_ints(pos, np.int64), pos_off=np.array(pos_off, np.int64), read_off=np.array(read_off, np.int64),
+             lab_off=np.array(lab_off, np.int64), labels=np.concatenate(labels) if labels else np.zeros(0, np.uint32),
+             rid=_ints(rid, np.int64), strand=np.array(strand, np.uint8), tail=np.array(tail, np.uint8),
+             gap_off=np.array(gap_off, np.int64), gaps=_ints(gaps, np.int32, 3), clip_off=np.array(clip_off, np.int64),
+             clips=_ints(clips, np.int32, 2), poly_off=np.array(poly_off, np.int64), polys=_ints(polys, np.int32, 3),
+             tok_off=np.arange(len(rid) + 1, dtype=np.int64), tok=np.array(tok, np.uint32))
+    return a
+
+
+def _slice_chunk(a, t0, t1):
+    """Tints t0 .. t1 of a batch's arrays as a batch of their own (copies)."""
+    r0, r1 = int(a["read_off"][t0]), int(a["read_off"][t1])
+    out = dict(n_tint=t1 - t0, tint_chr=a["tint_chr"][t0:t1], read_name=a["read_name"][r0:r1], read_chr=a["read_chr"][r0:r1])
+    for name, _ in _PER_TINT:
+        out[name] = a[name][t0:t1].copy()
+    for name, _ in _PER_READ:
+        out[name] = a[name][r0:r1].copy()
+    for off, data, _, _, by in _CSR:
+        i0, i1 = (t0, t1) if by == "tint" else (r0, r1)
+        o = a[off][i0:i1 + 1]
+        out[off] = o - o[0]
+        if data:
+            out[data] = a[data][int(o[0]):int(o[-1])].copy()
+    return out
+
+
+def _concat_chunks(chunks):
+    out = dict(n_tint=sum(c["n_tint"] for c in chunks))
+    for name in ("tint_chr", "read_name", "read_chr"):
+        out[name] = [x for c in chunks for x in c[name]]
+    for name, dt in _PER_TINT + _PER_READ:
+        out[name] = np.concatenate([c[name] for c in chunks]) if chunks else np.zeros(0, dt)
+    for off, data, dt, cols, _ in _CSR:
+        offs, base = [np.zeros(1, np.int64)], 0
+        for c in chunks:
+            offs.append(c[off][1:] + base)
+            base += int(c[off][-1])
+        out[off] = np.concatenate(offs)
+        if data:
+            empty = np.zeros((0, cols) if cols > 1 else 0, dt)
+            out[data] = np.concatenate([c[data] for c in chunks] or [empty])
+    return out
+
+
+class SegmentArrays:
+    """A batch of segment_*.tsv files as flat arrays (include/freddie_host.h, fhost_segments): ``a`` maps the header's names to numpy
+    arrays -- views of the native result, valid until close(), when no file was declined; copies otherwise, the declined files'
+    parts made from the mirror's read_segment() (mirror=False: left out).  gaps / clips / polys have a row an entry.  file_tint_off: the tints of file f;
+    declined: [(path, line, reason)].  Tint contigs, read names and read contigs (views into the mapped files): strings()."""
+
+    def __init__(self, paths, threads=1, mirror=True):
+        from . import _host
+        self._L = _host.load()
+        self.paths = [str(p) for p in paths]
+        self._s = _HostSegments()
+        self._strings = None
+        self.declined = []
+        if not self.paths:
+            self.a = _concat_chunks([])
+            self.file_tint_off = np.zeros(1, np.int64)
+            return
+        rc = self._L.fhost_read_segment(_host._c_strings(self.paths), len(self.paths), int(threads), ctypes.byref(self._s))
+        if rc != 0:
+            raise ClusterError("fhost_read_segment: out of memory or bad arguments (%d)" % rc)
+        s, F, T, N = self._s, len(self.paths), self._s.n_tint, int(self._s.n_read)
+        a = dict(n_tint=T)
+        for name, dt in _PER_TINT:
+            a[name] = _view(getattr(s, name), T, dt)
+        for name, dt in _PER_READ:
+            a[name] = _view(getattr(s, name), N, dt)
+        for off, data, dt, cols, by in _CSR:
+            a[off] = _view(getattr(s, off), (T if by == "tint" else N) + 1, np.int64)
+            if data:
+                x = _view(getattr(s, data), int(a[off][-1]) * cols, dt)
+                a[data] = x.reshape(-1, cols) if cols > 1 else x
+        self.a = a
+        self.file_tint_off = _view(s.file_tint_off, F + 1, np.int64)
+        declined = _view(s.file_declined, F, np.int32)
+        if declined.any():
+            lines = _view(s.file_line, F, np.int64).tolist()
+            reasons = ctypes.cast(s.file_reason, ctypes.POINTER(ctypes.c_char_p))
+            self.declined = [(self.paths[f], lines[f], reasons[f].decode()) for f in np.flatnonzero(declined).tolist()]
+            if mirror:
+                self._mix_in_the_mirror(declined)
+
+    def _native_strings(self):
+        s, T, N = self._s, self._s.n_tint, int(self._s.n_read)
+        maps = _view(s.file_map, len(self.paths), np.uint64).tolist()
+        tfile = _view(s.tint_file, T, np.int32).tolist()
+        at = ctypes.string_at
+        tint_chr = [at(maps[f] + o, n).decode() for f, o, n in zip(tfile, _view(s.tint_chr_off, T, np.int64).tolist(), _view(s.tint_chr_len, T, np.int32).tolist())]
+        base = np.repeat(np.array([maps[f] for f in tfile], np.uint64), np.diff(_view(s.read_off, T + 1, np.int64))).tolist() if T else []
+        name = [at(b + o, n).decode() for b, o, n in zip(base, _view(s.name_off, N, np.int64).tolist(), _view(s.name_len, N, np.int32).tolist())]
+        chrom = [at(b + o, n).decode() for b, o, n in zip(base, _view(s.chr_off, N, np.int64).tolist(), _view(s.chr_len, N, np.int32).tolist())]
+        return tint_chr, name, chrom
+
+    def _mix_in_the_mirror(self, declined):
+        """The declined files go through read_segment() (which raises what it always raised on a malformed one)."""
+        native = dict(self.a)
+        native["tint_chr"], native["read_name"], native["read_chr"] = self._native_strings()
+        chunks = []
+        for f, path in enumerate(self.paths):
+            if declined[f]:
+                chunks.append(_chunk_from_tints(list(read_segment(path).values())))
+            else:
+                chunks.append(_slice_chunk(native, int(self.file_tint_off[f]), int(self.file_tint_off[f + 1])))
+        self.a = _concat_chunks(chunks)
+        self._strings = (self.a.pop("tint_chr"), self.a.pop("read_name"), self.a.pop("read_chr"))
+        self.file_tint_off = np.concatenate([[0], np.cumsum([c["n_tint"] for c in chunks])]).astype(np.int64)
+        self.close()
+
+    def strings(self):
+        """(tint contigs, read names, read contigs) as lists of str."""
+        if self._strings is None:
+            self._strings = self._native_strings()
+        return self._strings
+
+    def close(self):
+        if getattr(self, "_s", None) is not None and self._s.owner:
+            self._L.fhost_segments_free(ctypes.byref(self._s))
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def read_segment_arrays(paths, threads=1, mirror=True):
+    """segment_*.tsv files as a SegmentArrays: parsed natively on `threads` threads, no per-read Python; a file the reader declines
+    goes through read_segment().  mirror=False: the native result alone -- a declined file has no tints in the arrays and is only
+    listed in .declined (path, line, reason)."""
+    return SegmentArrays(paths, threads, mirror)
+
+
+def cluster_files_batch(paths, maximum_ilp_size, ctx, ilp_settings=None, threads=8):
+    """segment_*.tsv files in, (read_segment_arrays(), Context.group_reads() arrays, Context.preprocess() arrays of the reps,
+    Context.partition() arrays) out: the native reader and one device call.  With ilp_settings the groups carry garbage_cost per rep
+    (the constant model; the reference's other two models raise, :314-316)."""
+    arrays = read_segment_arrays(paths, threads)
+    groups, prep, arr = ctx.partition_segment(arrays, maximum_ilp_size)
+    if ilp_settings is not None:
+        counts = np.diff(groups["rep_mem_off"])
+        if ilp_settings["recycle_model"] == "constant":
+            groups["garbage_cost"] = counts * 3
+        elif ilp_settings["recycle_model"] in ("exons", "introns"):
+            garbage_cost_exons(I=[])                                     # a list: raises like the reference (:314, :316)
+    return arrays, groups, prep, arr
+
+
+def tints_from_arrays(arrays, groups, prep=None, arr=None, ilp_settings=None):
+    """The tint dicts of a batch, in batch order, exactly as read_segment() leaves them; with prep / arr (Context.partition_segment)
+    as preprocess_ilp(tint, ilp_settings) + partition_reads() leave them.  The in-process seam to code that wants dicts."""
+    a = arrays.a
+    tint_chr, read_name, read_chr = arrays.strings()
+    T = a["n_tint"]
+    tid, n_seg, pos, pos_off = a["tint_id"].tolist(), a["n_seg"].tolist(), a["pos"].tolist(), a["pos_off"].tolist()
+    read_off, lab_off = a["read_off"].tolist(), a["lab_off"].tolist()
+    rid, strand = a["rid"].tolist(), a["strand"].tolist()
+    gap_off, clip_off, poly_off = a["gap_off"].tolist(), a["clip_off"].tolist(), a["poly_off"].tolist()
+    gaps, clips, polys = a["gaps"].tolist(), a["clips"].tolist(), a["polys"].tolist()
+    rep_off, mem_off, mem = groups["rep_off"].tolist(), groups["rep_mem_off"].tolist(), groups["rep_mem"].tolist()
+    tints = []
+    for t in range(T):
+        p = pos[pos_off[t]:pos_off[t + 1]]
+        r0, r1, M = read_off[t], read_off[t + 1], n_seg[t]
+        LW = max((M + 15) // 16, 1)
+        words = np.ascontiguousarray(a["labels"][lab_off[t]:lab_off[t + 1]], np.uint32).reshape(r1 - r0, LW)
+        data = ((words[:, :, None] >> (2 * np.arange(16, dtype=np.uint32))[None, None, :]) & 3).reshape(r1 - r0, LW * 16)[:, :M].tolist()
+        reads = []
+        for i, r in enumerate(range(r0, r1)):
+            reads.append(dict(id=rid[r], name=read_name[r], chr=read_chr[r], strand=chr(strand[r]), tint=tid[t], data=data[i],
+                              gaps={(g[0], g[1]): g[2] for g in gaps[gap_off[r]:gap_off[r + 1]]},
+                              softclip={_CLIP_KEYS[c[0]]: c[1] for c in clips[clip_off[r]:clip_off[r + 1]]},
+                              poly_tail={_POLY_KEYS[q[0]]: (q[1], q[2]) for q in polys[poly_off[r]:poly_off[r + 1]]}))
+        read_reps = [mem[mem_off[q]:mem_off[q + 1]] for q in range(rep_off[t], rep_off[t + 1])]
+        tints.append(dict(id=tid[t], chr=tint_chr[t], segs=[(s, e, e - s) for s, e in zip(p[:-1], p[1:])], read_reps=read_reps, reads=reads))
+    if prep is not None:
+        first = groups["rep_first"].astype(np.int64) + np.repeat(a["read_off"][:-1], np.diff(groups["rep_off"]))
+        packed = dict(rep_off=groups["rep_off"], n_seg=a["n_seg"], tail=a["tail"][first])
+        _ilp_data_from_prep(tints, packed, prep, ilp_settings or dict(recycle_model="constant"))
+    if arr is not None:
+        for t, tint in enumerate(tints):
+            tint["partitions"] = _partitions_from_arrays(arr, t, False)
+    return tints

@@ -786,6 +786,145 @@ __global__ void __launch_bounds__(256) k_mem_off(i64 n_reps, i64 n_rows, const u
     }
 }
 
+// ================================================================================================================
+// In front of preprocess_ilp(): read_segment()'s grouping of a tint's reads into reps (py/freddie_cluster.py:154-164), from ALL
+// reads' label rows and key token streams (fclu_segment).  Two reads share a rep exactly when their I rows (2 counts as 0) and
+// their token streams are equal; the dedupe's shape: hash, stable sort by (tint, hash), leaders on whole rows, scan, members.
+// ================================================================================================================
+struct GroupTint {
+    i64 read0, lab_off, slot0;              // first read; first label word; first lane slot of k_gkeys
+    int n, n_seg, lw, g_log2, vec;          // reads, segments, label words a row, log2 of the lanes a read gets, rows are whole 16-byte quads
+};
+
+// the I row of a label word, left where it stands: the low bit of every label that is not 3 (labels are 0, 1, 2 here)
+__device__ __forceinline__ unsigned i_spread(unsigned x) { return x & 0x55555555u & ~(x >> 1); }
+
+// one label word of a read's row for the key: its share of the hash, and the two refusals (a label 3, a bit behind the M labels)
+__device__ __forceinline__ unsigned key_word(unsigned x, int w, int n_seg, int &bad) {
+    int nv = n_seg - 16 * w; nv = nv > 16 ? 16 : (nv < 0 ? 0 : nv);
+    const unsigned vm = nv >= 16 ? 0xffffffffu : ((1u << (2 * nv)) - 1u);
+    if (x & (x >> 1) & 0x55555555u & vm) bad |= 1;
+    if (x & ~vm) bad |= 2;
+    return mix32((i_spread(x) & vm) ^ ((unsigned)w * 0x9e3779b9u + 0x7f4a7c15u));
+}
+
+// ---- per read: the sort key (tint, hash of I row + token stream) ------------------------------------------------------
+// k_rows' lane grouping: a read gets g = 2^g_log2 consecutive lanes (the smallest power of two that holds its label words -- its
+// 16-byte quads where every row of the tint is whole quads, which a lane then loads at once -- 64 at the most, looping beyond), a
+// tint's slots start at a multiple of 64, so a wave works on one tint and the sum below g is xor shuffles.  err[0..2]: the smallest
+// read with a label 3, with a bit behind its M labels, with a tail category above 2.
+__global__ void __launch_bounds__(256) k_gkeys(int n_tint, i64 n_slots, const GroupTint *gt, const unsigned *labels, const i64 *tok_off,
+                                               const unsigned *tok, const unsigned char *tail, unsigned hash_mask, int *read_tint, u64 *key,
+                                               int *val, int *err) {
+    const int lane = lane_id();
+    const i64 wave_g = ((i64)blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = ((i64)gridDim.x * blockDim.x) >> 6;
+    for (i64 s0 = wave_g * 64; s0 < n_slots; s0 += n_waves * 64) {
+        int lo = 0, hi = n_tint - 1;                          // the last tint whose slots start at or before s0 (wave-uniform)
+        while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (gt[mid].slot0 <= s0) lo = mid; else hi = mid - 1; }
+        const int t = __builtin_amdgcn_readfirstlane(lo);
+        const GroupTint d = gt[t];
+        const int g = 1 << d.g_log2, sub = lane & (g - 1);
+        const i64 r = (s0 - d.slot0 + lane) >> d.g_log2;
+        const bool ok = r < d.n;
+        const i64 read = d.read0 + (ok ? r : 0);
+        const unsigned *lab = labels + d.lab_off + (ok ? r : 0) * d.lw;
+        int bad = 0;
+        unsigned h = 0;
+        if (ok) {
+            if (d.vec) {
+                const uint4 *lab4 = reinterpret_cast<const uint4 *>(lab);
+                for (int q = sub; q < (d.lw >> 2); q += g) {
+                    const uint4 v = lab4[q];
+                    h += key_word(v.x, 4 * q, d.n_seg, bad); h += key_word(v.y, 4 * q + 1, d.n_seg, bad);
+                    h += key_word(v.z, 4 * q + 2, d.n_seg, bad); h += key_word(v.w, 4 * q + 3, d.n_seg, bad);
+                }
+            } else
+                for (int w = sub; w < d.lw; w += g) h += key_word(lab[w], w, d.n_seg, bad);
+            const i64 t0 = tok_off[read], nt = tok_off[read + 1] - t0;
+            for (i64 k = sub; k < nt; k += g) h += mix32(tok[t0 + k] ^ ((unsigned)k * 0x85ebca6bu + 0x165667b1u));
+            if (sub == 0) h += mix32((unsigned)nt * 0x27d4eb2fu + 1u);
+        }
+        for (int s = g >> 1; s >= 1; s >>= 1) h += (unsigned)__shfl_xor((int)h, s);
+        if (ok) {
+            if (bad & 1) atomicMin(&err[0], (int)read);
+            if (bad & 2) atomicMin(&err[1], (int)read);
+            if (sub == 0) {
+                if (tail[read] > 2) atomicMin(&err[2], (int)read);
+                read_tint[read] = t;
+                key[read] = ((u64)(unsigned)t << 32) | (u64)(mix32(h) & hash_mask);
+                val[read] = (int)read;
+            }
+        }
+    }
+}
+
+// A read's leader: the FIRST read of its bucket whose WHOLE I row and WHOLE token stream are equal (k_leader's rule; the hash never
+// decides).  The other read's tokens are read through addresses clamped to its own stream (to the array, when it has none), and what
+// they say counts only when the two streams are equally long.
+__global__ void __launch_bounds__(256) k_gleader(i64 n, const u64 *skey, const int *sval, const int *bstart, const GroupTint *gt, const unsigned *labels,
+                                                 const i64 *tok_off, const unsigned *tok, i64 n_tok, int *leader, int *flag) {
+    for (i64 k = (i64)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += (i64)gridDim.x * blockDim.x) {
+        const GroupTint d = gt[(int)(skey[k] >> 32)];
+        const int read = sval[k];
+        const unsigned *a = labels + d.lab_off + (i64)(read - d.read0) * d.lw;
+        const i64 ta = tok_off[read], na = tok_off[read + 1] - ta;
+        int lead = read;
+        for (i64 j = bstart[k]; j < k; ++j) {
+            const int other = sval[j];
+            const unsigned *b = labels + d.lab_off + (i64)(other - d.read0) * d.lw;
+            const i64 tb = tok_off[other], nb = tok_off[other + 1] - tb;
+            bool same = true;
+            for (int w = 0; w < d.lw; ++w) if (i_spread(a[w]) != i_spread(b[w])) { same = false; break; }
+            if (!same) continue;
+            for (i64 x = 0; x < na; ++x) {
+                i64 at = tb + (x < nb ? x : 0);
+                at = at < n_tok ? at : n_tok - 1;
+                if (tok[ta + x] != tok[at]) { same = false; break; }
+            }
+            if (same && na == nb) { lead = other; break; }
+        }
+        leader[read] = lead;
+        flag[read] = lead == read ? 1 : 0;
+    }
+}
+
+// rep_off[t] = the number of leaders in front of tint t's first read (rep_id: the exclusive scan of flag, n_reads + 1 entries)
+__global__ void __launch_bounds__(256) k_grep_off(int n_tint, i64 n_reads, const GroupTint *gt, const int *rep_id, i64 *rep_off) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t <= n_tint) rep_off[t] = rep_id[t < n_tint ? gt[t].read0 : n_reads];
+}
+
+// Reps are numbered by their first read (the leader): the leaders' scan IS the numbering (Python's dict insertion order, :162-164).
+// A read learns its rep; a leader is its rep's first read.  nkey / nval: the second sort's input (rep of the batch, read of the tint).
+__global__ void __launch_bounds__(256) k_greps(i64 n_reads, const int *read_tint, const GroupTint *gt, const int *leader, const int *rep_id,
+                                               int *read_rep, unsigned *nkey, int *nval, int *rep_first) {
+    for (i64 read = (i64)blockIdx.x * blockDim.x + threadIdx.x; read < n_reads; read += (i64)gridDim.x * blockDim.x) {
+        const GroupTint d = gt[read_tint[read]];
+        const int lead = leader[read], rep = rep_id[lead];
+        read_rep[read] = rep - rep_id[d.read0];
+        nkey[read] = (unsigned)rep;
+        nval[read] = (int)(read - d.read0);
+        if (lead == read) rep_first[rep] = (int)(read - d.read0);
+    }
+}
+
+// The reps' rows and tails, where k_rows reads them (fclu_reads' layout): a rep's row is its FIRST read's, with its 2s (:286-289), and
+// so is its tail.  A thread a label word: rep_lab_off[t] = the first word of tint t's reps.
+__global__ void __launch_bounds__(256) k_ggather(int n_tint, i64 n_words, const GroupTint *gt, const i64 *rep_off, const i64 *rep_lab_off,
+                                                 const int *rep_first, const unsigned *labels, const unsigned char *tail, unsigned *rep_labels,
+                                                 unsigned char *rep_tail) {
+    for (i64 x = (i64)blockIdx.x * blockDim.x + threadIdx.x; x < n_words; x += (i64)gridDim.x * blockDim.x) {
+        int lo = 0, hi = n_tint - 1;                          // the last tint whose words start at or before x
+        while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (rep_lab_off[mid] <= x) lo = mid; else hi = mid - 1; }
+        const GroupTint d = gt[lo];
+        const i64 y = x - rep_lab_off[lo], r = y / d.lw;
+        const int w = (int)(y - r * d.lw);
+        const i64 rep = rep_off[lo] + r, first = rep_first[rep];
+        rep_labels[x] = labels[d.lab_off + first * d.lw + w];
+        if (w == 0) rep_tail[rep] = tail[d.read0 + first];
+    }
+}
+
 }  // namespace
 
 // ---- buffers and the context -------------------------------------------------------------------------------------------
@@ -859,6 +998,19 @@ struct fclu_ctx {
     float rows_ms = 0.f, dedupe_ms = 0.f;
     fclu_prep prep = {};
     bool have_prep = false;
+    // fclu_group_reads() / fclu_partition_segment(): device arrays (gd) and the pinned copies fclu_group_results() hands out (gh)
+    struct {
+        Buf<GroupTint> tints; Buf<unsigned char> tail; Buf<u64> key, skey; Buf<i64> tok_off, rep_off, rep_lab_off, mem_off; Buf<char> tmp;
+        Buf<unsigned> labels, tok, nkey, snkey;
+        Buf<int> read_tint, val, sval, head, bstart, leader, flag, rep_id, read_rep, nval, mem, rep_first, err;
+    } gd;
+    struct {
+        HostBuf<int64_t> rep_off, rep_lab_off, mem_off; HostBuf<int32_t> read_rep, mem, rep_first; HostBuf<int> err;
+    } gh;
+    hipEvent_t gev[5] = {};
+    float gkeys_ms = 0.f, gdedupe_ms = 0.f;
+    fclu_groups groups = {};
+    bool have_groups = false;
     // (the buffers free themselves behind it, on this device)
     ~fclu_ctx() {
         (void)hipSetDevice(device);
@@ -866,6 +1018,7 @@ struct fclu_ctx {
         for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
         for (hipEvent_t e : pev) if (e) (void)hipEventDestroy(e);
         for (hipEvent_t e : qev) if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : gev) if (e) (void)hipEventDestroy(e);
     }
 };
 
@@ -1367,7 +1520,8 @@ struct PrepRun {
 
 // Rows and dedupe up to the tints' counts of unique rows: only row_off (n_tint + 1 counts) and the three error words come back to the
 // host here, for the refusals and for the unique rows' layout as a batch (c->ph.row_off / bits_off / adj_off).
-int prep_rows(fclu_ctx *c, const Knobs &k, const fclu_reads *rd, PrepRun &p) {
+// on_device: the rows and tails are in c->pd.labels / c->pd.tail already, where the grouping gathered them (group_device), checked there.
+int prep_rows(fclu_ctx *c, const Knobs &k, const fclu_reads *rd, bool on_device, PrepRun &p) {
     if (!rd || rd->n_tint <= 0) return fail(c, FCLU_ERR_ARG, "fclu_preprocess: empty batch");
     if (!rd->rep_off || !rd->n_seg || !rd->lab_off) return fail(c, FCLU_ERR_ARG, "fclu_preprocess: rep_off, n_seg or lab_off is null");
     HIP_TRY(c, hipSetDevice(c->device));
@@ -1400,7 +1554,7 @@ int prep_rows(fclu_ctx *c, const Knobs &k, const fclu_reads *rd, PrepRun &p) {
     const i64 N = p.N = rd->rep_off[T], n_lab = rd->lab_off[T];
     p.n_rbits = H.rbits_off.p[T];
     if (N >= 0x7f7f7f7fll) return fail(c, FCLU_ERR_ARG, "fclu_preprocess: %lld reps in one batch", N);
-    if (N > 0 && (!rd->labels || !rd->tail)) return fail(c, FCLU_ERR_ARG, "fclu_preprocess: labels or tail is null");
+    if (N > 0 && !on_device && (!rd->labels || !rd->tail)) return fail(c, FCLU_ERR_ARG, "fclu_preprocess: labels or tail is null");
     int64_t *h_row_off = H.row_off.p;
     if (N > 0) {
         hipStream_t s = c->stream;
@@ -1423,8 +1577,10 @@ int prep_rows(fclu_ctx *c, const Knobs &k, const fclu_reads *rd, PrepRun &p) {
         const size_t tmp_bytes = std::max(std::max(sort_a, sort_b), std::max(scan_a, scan_b));
         HIP_TRY(c, D.tmp.grow(tmp_bytes));
         HIP_TRY(c, hipMemcpyAsync(D.tints.p, p.pt.data(), D.tints.bytes((size_t)T), hipMemcpyHostToDevice, s));
-        HIP_TRY(c, hipMemcpyAsync(D.labels.p, rd->labels, D.labels.bytes((size_t)n_lab), hipMemcpyHostToDevice, s));
-        HIP_TRY(c, hipMemcpyAsync(D.tail.p, rd->tail, D.tail.bytes((size_t)N), hipMemcpyHostToDevice, s));
+        if (!on_device) {
+            HIP_TRY(c, hipMemcpyAsync(D.labels.p, rd->labels, D.labels.bytes((size_t)n_lab), hipMemcpyHostToDevice, s));
+            HIP_TRY(c, hipMemcpyAsync(D.tail.p, rd->tail, D.tail.bytes((size_t)N), hipMemcpyHostToDevice, s));
+        }
         HIP_TRY(c, hipMemsetAsync(D.err.p, 0x7f, D.err.bytes(4), s));
         HIP_TRY(c, hipMemsetAsync(D.flag.p + N, 0, D.flag.bytes(1), s));
         const int rep_grid = (int)std::min<i64>((N + 255) / 256, 4096);
@@ -1455,6 +1611,8 @@ int prep_rows(fclu_ctx *c, const Knobs &k, const fclu_reads *rd, PrepRun &p) {
             int t = 0;
             while (t + 1 < T && rd->rep_off[t + 1] <= rep) ++t;
             const i64 r = rep - rd->rep_off[t];
+            // (on_device: the grouping has refused such a tail already, and the byte is not on the host: no number to print)
+            if (kind == 2 && on_device) return fail(c, FCLU_ERR_ARG, "tint %d rep %lld: tail category above 2 (0 'N', 1 'S', 2 'E')", t, r);
             if (kind == 2) return fail(c, FCLU_ERR_ARG, "tint %d rep %lld: tail category %d (0 'N', 1 'S', 2 'E')", t, r, (int)rd->tail[rep]);
             if (kind == 0) return fail(c, FCLU_ERR_ARG, "tint %d rep %lld: a label with code 3 (labels are 0, 1, 2)", t, r);
             return fail(c, FCLU_ERR_ARG, "tint %d rep %lld: a nonzero bit beyond the tint's %d labels", t, r, (int)rd->n_seg[t]);
@@ -1517,11 +1675,11 @@ int prep_nodes(fclu_ctx *c, const PrepRun &p) {
 }
 
 // Rows, dedupe and the staging of the unique rows as a batch: st is what compat_run() needs.
-int preprocess_device(fclu_ctx *c, const Knobs &k, const fclu_reads *rd, int32_t prune, Staged &st, i64 &n_reps_out) {
+int preprocess_device(fclu_ctx *c, const Knobs &k, const fclu_reads *rd, int32_t prune, Staged &st, i64 &n_reps_out, bool on_device = false) {
     c->have_prep = false;
     c->rows_ms = c->dedupe_ms = 0.f;
     PrepRun p;
-    RC_TRY(prep_rows(c, k, rd, p));
+    RC_TRY(prep_rows(c, k, rd, on_device, p));
     n_reps_out = p.N;
     RC_TRY(stage_tints(c, k, p.T, c->ph.row_off.p, rd->n_seg, c->ph.bits_off.p, c->ph.adj_off.p, prune, nullptr, st));
     return prep_nodes(c, p);
@@ -1535,6 +1693,165 @@ void preprocess_times(fclu_ctx *c, i64 n_reps) {
     (void)hipEventElapsedTime(&a, c->qev[1], c->qev[2]);
     (void)hipEventElapsedTime(&b, c->qev[3], c->qev[4]);
     c->dedupe_ms = a + b;
+}
+
+// ---- read_segment()'s rep grouping of a batch of tints (:154-164) ---------------------------------------------------------
+// Keys, the two sorts, leaders and members.  gather (fclu_partition_segment): the reps' rows and tails go into c->pd.labels / c->pd.tail
+// (fclu_reads' layout, at c->gh.rep_off / c->gh.rep_lab_off), where prep_rows() takes them without another upload; the grouping alone
+// leaves the preprocess stage's device arrays as they are.  One synchronisation in the middle: the tints' rep counts size the members'
+// offsets and decide the layout of the gathered rows.  It synchronises at its end.
+int group_device(fclu_ctx *c, const Knobs &k, const fclu_segment *in, bool gather, i64 &n_reps_out) {
+    c->have_groups = false;
+    c->gkeys_ms = c->gdedupe_ms = 0.f;
+    if (!in || in->n_tint <= 0) return fail(c, FCLU_ERR_ARG, "fclu_group_reads: empty batch");
+    if (!in->read_off || !in->n_seg || !in->lab_off) return fail(c, FCLU_ERR_ARG, "fclu_group_reads: read_off, n_seg or lab_off is null");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const int T = in->n_tint;
+    if (in->read_off[0] != 0 || in->lab_off[0] != 0) return fail(c, FCLU_ERR_ARG, "fclu_group_reads: read_off and lab_off start at 0");
+    auto &D = c->gd;
+    auto &H = c->gh;
+    HIP_TRY(c, H.rep_off.grow((size_t)T + 1)); HIP_TRY(c, H.rep_lab_off.grow((size_t)T + 1)); HIP_TRY(c, H.err.grow(4));
+    std::vector<GroupTint> gt((size_t)T);
+    i64 n_slots = 0;
+    for (int t = 0; t < T; ++t) {
+        GroupTint &d = gt[(size_t)t];
+        const i64 n = in->read_off[t + 1] - in->read_off[t];
+        if (n < 0 || n > (1 << 30) || in->n_seg[t] < 0)
+            return fail(c, FCLU_ERR_ARG, "tint %d: negative or too large read count (%lld) or segment count (%d)", t, n, (int)in->n_seg[t]);
+        if (in->n_seg[t] > kMaxWords * 32)
+            return fail(c, FCLU_ERR_UNSUPPORTED, "tint %d has %d segments; this build stages at most %d", t, (int)in->n_seg[t], kMaxWords * 32);
+        d.read0 = in->read_off[t]; d.lab_off = in->lab_off[t]; d.slot0 = n_slots;
+        d.n = (int)n; d.n_seg = in->n_seg[t];
+        d.lw = std::max((d.n_seg + 15) / 16, 1);
+        d.vec = (d.lw % 4 == 0 && d.lab_off % 4 == 0) ? 1 : 0;
+        const int units = d.vec ? d.lw / 4 : d.lw;
+        d.g_log2 = 0; while (d.g_log2 < 6 && (1 << d.g_log2) < units) ++d.g_log2;
+        if (in->lab_off[t + 1] - d.lab_off != n * d.lw)
+            return fail(c, FCLU_ERR_ARG, "tint %d: lab_off does not match reads x words (%lld words for %lld reads of %d)", t,
+                        (i64)(in->lab_off[t + 1] - d.lab_off), n, d.lw);
+        n_slots += ((n << d.g_log2) + 63) / 64 * 64;
+    }
+    const i64 N = in->read_off[T], n_lab = in->lab_off[T];
+    if (N >= 0x7f7f7f7fll) return fail(c, FCLU_ERR_ARG, "fclu_group_reads: %lld reads in one batch", N);
+    if (N > 0 && (!in->labels || !in->tail || !in->tok_off)) return fail(c, FCLU_ERR_ARG, "fclu_group_reads: labels, tail or tok_off is null");
+    i64 n_tok = 0;
+    if (N > 0) {
+        if (in->tok_off[0] != 0) return fail(c, FCLU_ERR_ARG, "fclu_group_reads: tok_off[0] is %lld, not 0", (i64)in->tok_off[0]);
+        int t = 0;
+        for (i64 r = 0; r < N; ++r)
+            if (in->tok_off[r + 1] < in->tok_off[r]) {
+                while (t + 1 < T && in->read_off[t + 1] <= r) ++t;
+                return fail(c, FCLU_ERR_ARG, "tint %d read %lld: tok_off falls (%lld after %lld)", t, r - in->read_off[t], (i64)in->tok_off[r + 1], (i64)in->tok_off[r]);
+            }
+        n_tok = in->tok_off[N];
+        if (n_tok > 0 && !in->tok) return fail(c, FCLU_ERR_ARG, "fclu_group_reads: tok is null");
+    }
+    int64_t *h_rep_off = H.rep_off.p, *h_rep_lab_off = H.rep_lab_off.p;
+    i64 n_reps = 0, n_rep_lab = 0;
+    fclu_groups &o = c->groups;
+    if (N > 0) {
+        hipStream_t s = c->stream;
+        const size_t N1 = (size_t)N + 1;
+        HIP_TRY(c, D.tints.grow((size_t)T)); HIP_TRY(c, D.labels.grow((size_t)n_lab)); HIP_TRY(c, D.tail.grow((size_t)N));
+        HIP_TRY(c, D.tok_off.grow(N1)); HIP_TRY(c, D.tok.grow((size_t)std::max<i64>(n_tok, 1)));
+        for (Buf<int> *b : {&D.read_tint, &D.val, &D.sval, &D.head, &D.bstart, &D.leader, &D.read_rep, &D.nval, &D.mem, &D.rep_first}) HIP_TRY(c, b->grow((size_t)N));
+        HIP_TRY(c, D.nkey.grow((size_t)N)); HIP_TRY(c, D.snkey.grow((size_t)N));
+        HIP_TRY(c, D.flag.grow(N1)); HIP_TRY(c, D.rep_id.grow(N1)); HIP_TRY(c, D.mem_off.grow(N1));
+        HIP_TRY(c, D.key.grow((size_t)N)); HIP_TRY(c, D.skey.grow((size_t)N));
+        HIP_TRY(c, D.rep_off.grow((size_t)T + 1)); HIP_TRY(c, D.rep_lab_off.grow((size_t)T + 1)); HIP_TRY(c, D.err.grow(4));
+        const unsigned key_bits = 32u + (unsigned)bits_for(T), rep_bits = (unsigned)bits_for(N);
+        size_t sort_a = 0, sort_b = 0, scan_a = 0, scan_b = 0;
+        HIP_TRY(c, rocprim::radix_sort_pairs(nullptr, sort_a, D.key.p, D.skey.p, D.val.p, D.sval.p, (size_t)N, 0u, key_bits, s));
+        HIP_TRY(c, rocprim::radix_sort_pairs(nullptr, sort_b, D.nkey.p, D.snkey.p, D.nval.p, D.mem.p, (size_t)N, 0u, rep_bits, s));
+        HIP_TRY(c, rocprim::inclusive_scan(nullptr, scan_a, D.head.p, D.bstart.p, (size_t)N, rocprim::maximum<int>(), s));
+        HIP_TRY(c, rocprim::exclusive_scan(nullptr, scan_b, D.flag.p, D.rep_id.p, 0, N1, rocprim::plus<int>(), s));
+        const size_t tmp_bytes = std::max(std::max(sort_a, sort_b), std::max(scan_a, scan_b));
+        HIP_TRY(c, D.tmp.grow(tmp_bytes));
+        HIP_TRY(c, hipMemcpyAsync(D.tints.p, gt.data(), D.tints.bytes((size_t)T), hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipMemcpyAsync(D.labels.p, in->labels, D.labels.bytes((size_t)n_lab), hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipMemcpyAsync(D.tail.p, in->tail, D.tail.bytes((size_t)N), hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipMemcpyAsync(D.tok_off.p, in->tok_off, D.tok_off.bytes(N1), hipMemcpyHostToDevice, s));
+        if (n_tok) HIP_TRY(c, hipMemcpyAsync(D.tok.p, in->tok, D.tok.bytes((size_t)n_tok), hipMemcpyHostToDevice, s));
+        else HIP_TRY(c, hipMemsetAsync(D.tok.p, 0, D.tok.bytes(1), s));
+        HIP_TRY(c, hipMemsetAsync(D.err.p, 0x7f, D.err.bytes(4), s));
+        HIP_TRY(c, hipMemsetAsync(D.flag.p + N, 0, D.flag.bytes(1), s));
+        const int read_grid = (int)std::min<i64>((N + 255) / 256, 4096);
+        HIP_TRY(c, hipEventRecord(c->gev[0], s));
+        hipLaunchKernelGGL(k_gkeys, dim3((unsigned)std::min<i64>((n_slots + 255) / 256, 65536)), dim3(256), 0, s, T, n_slots, D.tints.p, D.labels.p, D.tok_off.p,
+                           D.tok.p, D.tail.p, k.hash_mask, D.read_tint.p, D.key.p, D.val.p, D.err.p);
+        HIP_TRY(c, hipEventRecord(c->gev[1], s));
+        HIP_TRY(c, hipMemcpyAsync(H.err.p, D.err.p, D.err.bytes(4), hipMemcpyDeviceToHost, s));
+        size_t tb = tmp_bytes;
+        HIP_TRY(c, rocprim::radix_sort_pairs(D.tmp.p, tb, D.key.p, D.skey.p, D.val.p, D.sval.p, (size_t)N, 0u, key_bits, s));
+        hipLaunchKernelGGL(k_heads, dim3(read_grid), dim3(256), 0, s, N, D.skey.p, D.head.p);
+        tb = tmp_bytes;
+        HIP_TRY(c, rocprim::inclusive_scan(D.tmp.p, tb, D.head.p, D.bstart.p, (size_t)N, rocprim::maximum<int>(), s));
+        hipLaunchKernelGGL(k_gleader, dim3(read_grid), dim3(256), 0, s, N, D.skey.p, D.sval.p, D.bstart.p, D.tints.p, D.labels.p, D.tok_off.p, D.tok.p,
+                           std::max<i64>(n_tok, 1), D.leader.p, D.flag.p);
+        tb = tmp_bytes;
+        HIP_TRY(c, rocprim::exclusive_scan(D.tmp.p, tb, D.flag.p, D.rep_id.p, 0, N1, rocprim::plus<int>(), s));
+        hipLaunchKernelGGL(k_grep_off, dim3((unsigned)(T + 256) / 256), dim3(256), 0, s, T, N, D.tints.p, D.rep_id.p, D.rep_off.p);
+        hipLaunchKernelGGL(k_greps, dim3(read_grid), dim3(256), 0, s, N, D.read_tint.p, D.tints.p, D.leader.p, D.rep_id.p, D.read_rep.p, D.nkey.p, D.nval.p,
+                           D.rep_first.p);
+        tb = tmp_bytes;
+        HIP_TRY(c, rocprim::radix_sort_pairs(D.tmp.p, tb, D.nkey.p, D.snkey.p, D.nval.p, D.mem.p, (size_t)N, 0u, rep_bits, s));
+        HIP_TRY(c, hipEventRecord(c->gev[2], s));
+        HIP_TRY(c, hipMemcpyAsync(h_rep_off, D.rep_off.p, D.rep_off.bytes((size_t)T + 1), hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipStreamSynchronize(s));
+        HIP_TRY(c, hipGetLastError());
+        const int kinds[3] = {2, 0, 1};                      // the tail first, as fclu_preprocess does
+        for (int kind : kinds) {
+            if (H.err.p[kind] == 0x7f7f7f7f) continue;
+            const i64 read = H.err.p[kind];
+            int t = 0;
+            while (t + 1 < T && in->read_off[t + 1] <= read) ++t;
+            const i64 r = read - in->read_off[t];
+            if (kind == 2) return fail(c, FCLU_ERR_ARG, "tint %d read %lld: tail category %d (0 'N', 1 'S', 2 'E')", t, r, (int)in->tail[read]);
+            if (kind == 0) return fail(c, FCLU_ERR_ARG, "tint %d read %lld: a label with code 3 (labels are 0, 1, 2)", t, r);
+            return fail(c, FCLU_ERR_ARG, "tint %d read %lld: a nonzero bit beyond the tint's %d labels", t, r, (int)in->n_seg[t]);
+        }
+        // ---- the reps' rows as fclu_reads: their layout from the tints' rep counts
+        h_rep_lab_off[0] = 0;
+        for (int t = 0; t < T; ++t) {
+            const i64 n = h_rep_off[t + 1] - h_rep_off[t];
+            if (n < 0 || n > gt[(size_t)t].n || (n == 0) != (gt[(size_t)t].n == 0))
+                return fail(c, FCLU_ERR_HIP, "tint %d: %lld reps of %d reads", t, n, gt[(size_t)t].n);
+            h_rep_lab_off[t + 1] = h_rep_lab_off[t] + n * gt[(size_t)t].lw;
+        }
+        n_reps = h_rep_off[T]; n_rep_lab = h_rep_lab_off[T];
+        if (gather) {
+            HIP_TRY(c, c->pd.labels.grow((size_t)n_rep_lab)); HIP_TRY(c, c->pd.tail.grow((size_t)n_reps));
+            HIP_TRY(c, hipMemcpyAsync(D.rep_lab_off.p, h_rep_lab_off, D.rep_lab_off.bytes((size_t)T + 1), hipMemcpyHostToDevice, s));
+        }
+        HIP_TRY(c, hipEventRecord(c->gev[3], s));
+        hipLaunchKernelGGL(k_mem_off, dim3(read_grid), dim3(256), 0, s, N, n_reps, D.snkey.p, D.mem_off.p);
+        if (gather)
+            hipLaunchKernelGGL(k_ggather, dim3((unsigned)std::min<i64>((n_rep_lab + 255) / 256, 8192)), dim3(256), 0, s, T, n_rep_lab, D.tints.p, D.rep_off.p,
+                               D.rep_lab_off.p, D.rep_first.p, D.labels.p, D.tail.p, c->pd.labels.p, c->pd.tail.p);
+        HIP_TRY(c, hipEventRecord(c->gev[4], s));
+    } else {
+        memset(h_rep_off, 0, H.rep_off.bytes((size_t)T + 1));
+        memset(h_rep_lab_off, 0, H.rep_lab_off.bytes((size_t)T + 1));
+    }
+    const bool copy = N > 0;
+    RC_TRY(fetch(c, H.read_rep, D.read_rep.p, (size_t)N, copy, o.read_rep));
+    RC_TRY(fetch(c, H.mem_off, D.mem_off.p, (size_t)n_reps + 1, copy, o.rep_mem_off));
+    RC_TRY(fetch(c, H.mem, D.mem.p, (size_t)N, copy, o.rep_mem));
+    RC_TRY(fetch(c, H.rep_first, D.rep_first.p, (size_t)n_reps, copy, o.rep_first));
+    if (!copy) *H.mem_off.p = 0;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipGetLastError());
+    if (copy) {
+        float a = 0.f, b = 0.f;
+        (void)hipEventElapsedTime(&c->gkeys_ms, c->gev[0], c->gev[1]);
+        (void)hipEventElapsedTime(&a, c->gev[1], c->gev[2]);
+        (void)hipEventElapsedTime(&b, c->gev[3], c->gev[4]);
+        c->gdedupe_ms = a + b;
+    }
+    o.n_tint = T; o.n_reads = N; o.n_reps = n_reps; o.rep_off = h_rep_off;
+    n_reps_out = n_reps;
+    c->have_groups = true;
+    return FCLU_OK;
 }
 
 }  // namespace
@@ -1560,6 +1877,7 @@ int fclu_create(int device, fclu_ctx **out) {
     for (int i = 0; e == hipSuccess && i < 3; ++i) e = hipEventCreate(&c->ev[i]);
     for (int i = 0; e == hipSuccess && i < 6; ++i) e = hipEventCreate(&c->pev[i]);
     for (int i = 0; e == hipSuccess && i < 6; ++i) e = hipEventCreate(&c->qev[i]);
+    for (int i = 0; e == hipSuccess && i < 5; ++i) e = hipEventCreate(&c->gev[i]);
     const struct { const void *kernel; int lds; } dyn[] = {                // the most dynamic LDS a launch asks for
         {reinterpret_cast<const void *>(k_cc_lds), 80 * 1024},
         {reinterpret_cast<const void *>(k_compat<false>), 2 * kTile * (kMaxWords | 1) * 4},
@@ -1678,6 +1996,46 @@ int fclu_preprocess_results(fclu_ctx *c, fclu_prep *out) {
 }
 
 int fclu_preprocess_timing(fclu_ctx *c, float *rows_ms, float *dedupe_ms) { return c ? two_times(rows_ms, c->rows_ms, dedupe_ms, c->dedupe_ms) : FCLU_ERR_ARG; }
+
+int fclu_group_reads(fclu_ctx *c, const fclu_segment *in) {
+    if (!c) return FCLU_ERR_ARG;
+    i64 n_reps = 0;
+    return group_device(c, read_knobs(), in, false, n_reps);
+}
+
+int fclu_partition_segment(fclu_ctx *c, const fclu_segment *in, int32_t maximum_ilp_size) {
+    if (!c) return FCLU_ERR_ARG;
+    c->have_parts = false;
+    c->have_prep = false;
+    c->have_groups = false;
+    if (maximum_ilp_size < 1) return fail(c, FCLU_ERR_ARG, "maximum_ilp_size is %d: it must be at least 1", (int)maximum_ilp_size);
+    const Knobs k = read_knobs();
+    i64 n_reps = 0;
+    RC_TRY(group_device(c, k, in, true, n_reps));
+    // the reps as fclu_reads: offsets from the grouping's pinned results, rows and tails on the device already
+    fclu_reads rd = {};
+    rd.n_tint = in->n_tint; rd.rep_off = c->gh.rep_off.p; rd.n_seg = in->n_seg; rd.lab_off = c->gh.rep_lab_off.p;
+    Staged st;
+    const int rc = [&]() {
+        RC_TRY(preprocess_device(c, k, &rd, 1, st, n_reps, true));
+        if (!st.empty) RC_TRY(compat_run(c, st, k, 1, nullptr, nullptr));
+        else HIP_TRY(c, hipStreamSynchronize(c->stream));
+        preprocess_times(c, n_reps);
+        c->have_prep = true;
+        return partition_device(c, in->n_tint, st.R, nullptr, nullptr, n_reps, maximum_ilp_size);
+    }();
+    if (rc != FCLU_OK) c->have_groups = c->have_prep = false;
+    return rc;
+}
+
+int fclu_group_results(fclu_ctx *c, fclu_groups *out) {
+    if (!c || !out) return FCLU_ERR_ARG;
+    if (!c->have_groups) return fail(c, FCLU_ERR_ARG, "fclu_group_results: no result (the last fclu_group_reads / fclu_partition_segment call failed or none was made)");
+    *out = c->groups;
+    return FCLU_OK;
+}
+
+int fclu_group_timing(fclu_ctx *c, float *keys_ms, float *dedupe_ms) { return c ? two_times(keys_ms, c->gkeys_ms, dedupe_ms, c->gdedupe_ms) : FCLU_ERR_ARG; }
 
 }  // extern "C"
 

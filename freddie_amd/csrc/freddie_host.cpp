@@ -1092,6 +1092,267 @@ int32_t fhost_write_packed(fhost_batch *b, const int64_t *part_final_off, const 
 
 }  // extern "C"
 
+// ---- segment_*.tsv reader of the clustering stage (py/freddie_cluster.py:15-34, :119-172) ------------------------------------
+// One pass over the bytes of a mapped file, a file a task.  Whatever the reference's two regexes and its asserts would not take, and
+// whatever this reader's arrays cannot hold, DECLINES the file (line, reason): the Python wrapper then runs the mirror's
+// read_segment() on it, so errors and odd-but-legal files (CRLF line ends, numbers with leading zeros, duplicate dict keys) behave
+// as they always did.
+namespace {
+
+struct SegDecline { const char *why; };
+
+struct SegTint {
+    i64 id = 0, chr_off = 0;
+    int chr_len = 0, n_seg = 0, lw = 1;
+    std::vector<int64_t> pos, rid, name_off, rchr_off;
+    std::vector<int32_t> name_len, rchr_len, gaps, clips, polys;
+    std::vector<uint8_t> strand, tail;
+    std::vector<uint32_t> labels, tok;
+    std::vector<i64> gap_off{0}, clip_off{0}, poly_off{0}, tok_off{0};
+};
+
+struct SegFile {
+    Mapping map;
+    std::vector<SegTint> tints;
+    bool declined = false;
+    i64 line = 0;
+    std::string reason;
+};
+
+constexpr i64 kTokLimit = 1ll << 30;       // numbers of the gaps field: 30 bits of a token, two flag bits above them
+
+// [0-9]+ without a leading zero (the rep key holds the digits as written, :155-157) and below limit
+inline i64 seg_num(const char *&p, const char *e, i64 limit) {
+    const char *b = p;
+    i64 x = 0;
+    while (p < e && (unsigned)(*p - '0') <= 9) { if (p - b < 18) x = x * 10 + (*p - '0'); ++p; }
+    if (p == b) throw SegDecline{"the line does not match the grammar (a number is missing)"};
+    if (p - b > 1 && *b == '0') throw SegDecline{"a number with a leading zero"};
+    if (p - b > 18 || x >= limit) throw SegDecline{"a number that does not fit"};
+    return x;
+}
+inline void seg_expect(const char *&p, const char *e, char c) {
+    if (p >= e || *p != c) throw SegDecline{"the line does not match the grammar"};
+    ++p;
+}
+
+void parse_segment_file(const char *path, SegFile &F) {
+    if (!F.map.open(path, nullptr, nullptr)) throw SegDecline{"cannot read the file"};
+    const char *p = F.map.p, *end = p + F.map.n;
+    std::unordered_map<i64, int> by_id;
+    std::vector<uint32_t> poly_tok;
+    std::vector<i64> keys;
+    const i64 kMax = 1000000000000000000ll;
+    while (p < end) {
+        ++F.line;
+        const char *nl = (const char *)memchr(p, '\n', (size_t)(end - p));
+        if (!nl) throw SegDecline{"a line without a newline"};
+        if (*p == '#') {
+            const char *c0e = find_tab(p + 1, nl);
+            if (c0e >= nl || !chr_ok(p + 1, c0e)) throw SegDecline{"the header does not match the grammar"};
+            const char *q = c0e + 1;
+            SegTint t;
+            t.chr_off = (p + 1) - F.map.p; t.chr_len = (int)(c0e - (p + 1));
+            t.id = seg_num(q, nl, kMax);
+            seg_expect(q, nl, '\t');
+            for (;;) {
+                const i64 v = seg_num(q, nl, kMax);
+                if (!t.pos.empty() && !(t.pos.back() < v)) throw SegDecline{"segment positions that do not rise (:131)"};
+                t.pos.push_back(v);
+                if (q == nl) break;
+                seg_expect(q, nl, ',');
+            }
+            if (t.pos.size() > (size_t)(1 << 30)) throw SegDecline{"too many segments"};
+            t.n_seg = (int)t.pos.size() - 1;
+            t.lw = std::max((t.n_seg + 15) / 16, 1);
+            if (!by_id.emplace(t.id, (int)F.tints.size()).second) throw SegDecline{"a tint id is repeated (:135)"};
+            F.tints.push_back(std::move(t));
+        } else {
+            const char *q = p;
+            const i64 rid = seg_num(q, nl, kMax);
+            seg_expect(q, nl, '\t');
+            const char *name = q, *name_e = find_tab(q, nl);
+            if (name_e >= nl || !name_ok(name, name_e)) throw SegDecline{"the read name does not match the grammar"};
+            const char *chr = name_e + 1, *chr_e = find_tab(chr, nl);
+            if (chr_e >= nl || !chr_ok(chr, chr_e)) throw SegDecline{"the read's contig does not match the grammar"};
+            q = chr_e + 1;
+            if (q >= nl || (*q != '+' && *q != '-')) throw SegDecline{"the strand does not match the grammar"};
+            const char strand = *q++;
+            seg_expect(q, nl, '\t');
+            const i64 cid = seg_num(q, nl, kMax);
+            seg_expect(q, nl, '\t');
+            const auto it = by_id.find(cid);
+            if (it == by_id.end()) throw SegDecline{"a read whose tint has no header yet"};
+            SegTint &t = F.tints[(size_t)it->second];
+            const char *data = q;
+            while (q < nl && (unsigned)(*q - '0') <= 2) ++q;
+            if (q == data) throw SegDecline{"the labels do not match the grammar"};
+            const i64 m = q - data;
+            seg_expect(q, nl, '\t');
+            if (m != t.n_seg) throw SegDecline{"the number of labels is not the number of segments (:165)"};
+            if (t.chr_len != (int)(chr_e - chr) || memcmp(chr, F.map.p + t.chr_off, (size_t)t.chr_len) != 0)
+                throw SegDecline{"the read's contig is not its tint's (:167)"};
+            const size_t l0 = t.labels.size();
+            t.labels.resize(l0 + (size_t)t.lw, 0u);
+            for (i64 s = 0; s < m; ++s) t.labels[l0 + (size_t)(s >> 4)] |= (uint32_t)(data[s] & 3) << (2 * (s & 15));
+            poly_tok.clear(); keys.clear();
+            unsigned poly_seen = 0;
+            int n_poly = 0, tail = 0;
+            while (q < nl) {
+                const char c = *q;
+                if ((unsigned)(c - '0') <= 9) {                          // (\d+)-(\d+):(\d+),
+                    const i64 a = seg_num(q, nl, kTokLimit);
+                    seg_expect(q, nl, '-');
+                    const i64 b = seg_num(q, nl, kTokLimit);
+                    seg_expect(q, nl, ':');
+                    const i64 len = seg_num(q, nl, kTokLimit);
+                    seg_expect(q, nl, ',');
+                    if (!(a < b && b < m)) throw SegDecline{"a gap outside the read's segments (:168)"};
+                    keys.push_back(a * kTokLimit + b);
+                    t.gaps.push_back((int32_t)a); t.gaps.push_back((int32_t)b); t.gaps.push_back((int32_t)len);
+                    t.tok.push_back(len > 10 ? (uint32_t)len : 0u);
+                } else if ((c == 'S' || c == 'E') && nl - q >= 4 && q[1] == 'S' && q[2] == 'C' && q[3] == ':') {     // ([ES]SC):(\d+),
+                    q += 4;
+                    const i64 len = seg_num(q, nl, kTokLimit);
+                    seg_expect(q, nl, ',');
+                    t.clips.push_back(c == 'E' ? 1 : 0); t.clips.push_back((int32_t)len);
+                } else if ((c == 'S' || c == 'E') && nl - q >= 3 && (q[1] == 'A' || q[1] == 'T') && q[2] == '_') {      // ([ES][AT])_(\d+):(\d+),
+                    const int key = (c == 'E' ? 2 : 0) + (q[1] == 'T' ? 1 : 0);
+                    q += 3;
+                    const i64 len = seg_num(q, nl, kTokLimit);
+                    seg_expect(q, nl, ':');
+                    const i64 gap = seg_num(q, nl, kTokLimit);
+                    seg_expect(q, nl, ',');
+                    if (poly_seen & (1u << key)) throw SegDecline{"a poly-tail key twice in one line"};
+                    poly_seen |= 1u << key;
+                    t.polys.push_back(key); t.polys.push_back((int32_t)len); t.polys.push_back((int32_t)gap);
+                    poly_tok.push_back(0x80000000u | (c == 'E' ? 0x40000000u : 0u) | (gap > 10 ? (uint32_t)gap : 0u));
+                    ++n_poly;
+                    tail = len > 10 ? (c == 'S' ? 1 : 2) : 0;             // (counts only when it stays the line's one entry, :293-304)
+                } else
+                    throw SegDecline{"the gaps field does not match the grammar"};
+            }
+            if (keys.size() > 1) {
+                std::sort(keys.begin(), keys.end());
+                if (std::adjacent_find(keys.begin(), keys.end()) != keys.end()) throw SegDecline{"a gap key twice in one line"};
+            }
+            t.tok.insert(t.tok.end(), poly_tok.begin(), poly_tok.end());
+            t.rid.push_back(rid); t.strand.push_back((uint8_t)strand);
+            t.name_off.push_back(name - F.map.p); t.name_len.push_back((int32_t)(name_e - name));
+            t.rchr_off.push_back(chr - F.map.p); t.rchr_len.push_back((int32_t)(chr_e - chr));
+            t.tail.push_back((uint8_t)(n_poly == 1 ? tail : 0));
+            t.gap_off.push_back((i64)t.gaps.size() / 3); t.clip_off.push_back((i64)t.clips.size() / 2);
+            t.poly_off.push_back((i64)t.polys.size() / 3); t.tok_off.push_back((i64)t.tok.size());
+        }
+        p = nl + 1;
+    }
+}
+
+struct SegOwner {
+    std::vector<SegFile> files;
+    std::vector<int32_t> file_declined, tint_file, tint_chr_len, n_seg, name_len, chr_len, gaps, clips, polys;
+    std::vector<int64_t> file_line, file_tint_off, tint_id, tint_chr_off, pos_off, pos, read_off, lab_off, rid, name_off, chr_off, gap_off,
+        clip_off, poly_off, tok_off;
+    std::vector<const char *> file_reason, file_map;
+    std::vector<uint8_t> strand, tail;
+    std::vector<uint32_t> labels, tok;
+};
+
+template <typename T, typename U>
+inline void seg_copy(std::vector<T> &dst, size_t at, const std::vector<U> &src) {
+    static_assert(sizeof(T) == sizeof(U), "one element size");
+    if (!src.empty()) memcpy(&dst[at], src.data(), src.size() * sizeof(T));
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t fhost_read_segment(const char *const *paths, int32_t n, int32_t n_threads, fhost_segments *out) {
+    if (!out) return 1;
+    memset(out, 0, sizeof *out);
+    if (!paths || n <= 0) return 1;
+    SegOwner *o = nullptr;
+    try {
+        o = new SegOwner();
+        o->files = std::vector<SegFile>((size_t)n);
+        parallel_for(n, n_threads, [&](int i) {
+            SegFile &F = o->files[(size_t)i];
+            try { parse_segment_file(paths[i], F); }
+            catch (const SegDecline &d) { F.declined = true; F.reason = d.why; }
+            catch (const std::exception &e) { F.declined = true; F.reason = e.what(); }
+            catch (...) { F.declined = true; F.reason = "internal error while parsing"; }
+            if (F.declined) { F.tints.clear(); F.tints.shrink_to_fit(); F.map.close(); } else F.line = 0;
+        });
+        // the offsets (serial, cheap), then every tint copies its own slices (parallel)
+        struct At { const SegTint *t; int file; size_t read, lab, pos, gap, clip, poly, tok; };
+        std::vector<At> at;
+        o->file_tint_off.assign((size_t)n + 1, 0);
+        size_t n_read = 0, n_lab = 0, n_pos = 0, n_gap = 0, n_clip = 0, n_poly = 0, n_tok = 0;
+        for (int f = 0; f < n; ++f) {
+            const SegFile &F = o->files[(size_t)f];
+            o->file_declined.push_back(F.declined ? 1 : 0); o->file_line.push_back(F.line);
+            o->file_reason.push_back(F.reason.c_str()); o->file_map.push_back(F.map.p);
+            for (const SegTint &t : F.tints) {
+                at.push_back(At{&t, f, n_read, n_lab, n_pos, n_gap, n_clip, n_poly, n_tok});
+                n_read += t.rid.size(); n_lab += t.labels.size(); n_pos += t.pos.size();
+                n_gap += t.gaps.size() / 3; n_clip += t.clips.size() / 2; n_poly += t.polys.size() / 3; n_tok += t.tok.size();
+            }
+            o->file_tint_off[(size_t)f + 1] = (int64_t)at.size();
+        }
+        const size_t T = at.size();
+        if (T >= (size_t)0x7fffffff) throw std::length_error("too many tints");
+        o->tint_id.resize(T); o->tint_file.resize(T); o->tint_chr_off.resize(T); o->tint_chr_len.resize(T); o->n_seg.resize(T);
+        o->pos_off.assign(T + 1, (int64_t)n_pos); o->read_off.assign(T + 1, (int64_t)n_read); o->lab_off.assign(T + 1, (int64_t)n_lab);
+        o->pos.resize(n_pos); o->rid.resize(n_read); o->strand.resize(n_read); o->tail.resize(n_read);
+        o->name_off.resize(n_read); o->name_len.resize(n_read); o->chr_off.resize(n_read); o->chr_len.resize(n_read);
+        o->labels.resize(n_lab); o->tok.resize(n_tok); o->gaps.resize(n_gap * 3); o->clips.resize(n_clip * 2); o->polys.resize(n_poly * 3);
+        o->gap_off.assign(n_read + 1, (int64_t)n_gap); o->clip_off.assign(n_read + 1, (int64_t)n_clip);
+        o->poly_off.assign(n_read + 1, (int64_t)n_poly); o->tok_off.assign(n_read + 1, (int64_t)n_tok);
+        parallel_for((int)T, n_threads, [&](int ti) {
+            const At &a = at[(size_t)ti];
+            const SegTint &t = *a.t;
+            const size_t k = (size_t)ti;
+            o->tint_id[k] = t.id; o->tint_file[k] = a.file; o->tint_chr_off[k] = t.chr_off; o->tint_chr_len[k] = t.chr_len; o->n_seg[k] = t.n_seg;
+            o->pos_off[k] = (int64_t)a.pos; o->read_off[k] = (int64_t)a.read; o->lab_off[k] = (int64_t)a.lab;
+            seg_copy(o->pos, a.pos, t.pos); seg_copy(o->rid, a.read, t.rid); seg_copy(o->strand, a.read, t.strand); seg_copy(o->tail, a.read, t.tail);
+            seg_copy(o->name_off, a.read, t.name_off); seg_copy(o->name_len, a.read, t.name_len);
+            seg_copy(o->chr_off, a.read, t.rchr_off); seg_copy(o->chr_len, a.read, t.rchr_len);
+            seg_copy(o->labels, a.lab, t.labels); seg_copy(o->tok, a.tok, t.tok);
+            seg_copy(o->gaps, a.gap * 3, t.gaps); seg_copy(o->clips, a.clip * 2, t.clips); seg_copy(o->polys, a.poly * 3, t.polys);
+            for (size_t r = 0; r < t.rid.size(); ++r) {
+                o->gap_off[a.read + r] = (int64_t)a.gap + t.gap_off[r]; o->clip_off[a.read + r] = (int64_t)a.clip + t.clip_off[r];
+                o->poly_off[a.read + r] = (int64_t)a.poly + t.poly_off[r]; o->tok_off[a.read + r] = (int64_t)a.tok + t.tok_off[r];
+            }
+        });
+        for (SegFile &F : o->files) { F.tints.clear(); F.tints.shrink_to_fit(); }      // (the mappings stay: names and contigs are views)
+        out->owner = o;
+        out->n_file = n; out->n_tint = (int32_t)T; out->n_read = (int64_t)n_read;
+        out->file_declined = o->file_declined.data(); out->file_line = o->file_line.data(); out->file_reason = o->file_reason.data();
+        out->file_map = o->file_map.data(); out->file_tint_off = o->file_tint_off.data();
+        out->tint_id = o->tint_id.data(); out->tint_file = o->tint_file.data(); out->tint_chr_off = o->tint_chr_off.data();
+        out->tint_chr_len = o->tint_chr_len.data(); out->n_seg = o->n_seg.data(); out->pos_off = o->pos_off.data(); out->pos = o->pos.data();
+        out->read_off = o->read_off.data(); out->lab_off = o->lab_off.data();
+        out->rid = o->rid.data(); out->strand = o->strand.data(); out->name_off = o->name_off.data(); out->name_len = o->name_len.data();
+        out->chr_off = o->chr_off.data(); out->chr_len = o->chr_len.data(); out->labels = o->labels.data(); out->tail = o->tail.data();
+        out->gap_off = o->gap_off.data(); out->gaps = o->gaps.data(); out->clip_off = o->clip_off.data(); out->clips = o->clips.data();
+        out->poly_off = o->poly_off.data(); out->polys = o->polys.data(); out->tok_off = o->tok_off.data(); out->tok = o->tok.data();
+        return 0;
+    } catch (...) {
+        delete o;
+        memset(out, 0, sizeof *out);
+        return 2;
+    }
+}
+
+void fhost_segments_free(fhost_segments *s) {
+    if (!s) return;
+    delete static_cast<SegOwner *>(s->owner);
+    memset(s, 0, sizeof *s);
+}
+
+}  // extern "C"
+
 #ifdef FREDDIE_SOURCE_HASH
 /* what this binary was built from (freddie_amd/build.py looks for the marker in the file) */
 static const char freddie_source_stamp[] __attribute__((used)) = "FREDDIE_SRC_HASH=" FREDDIE_SOURCE_HASH;

@@ -11,9 +11,11 @@
  * for a batch of transcriptional intervals ("tints") at once.  fclu_partition_reads() runs all of it in one call, from label
  * rows at two bits a label to tint['partitions'] as flat arrays: the unique rows and their members go from the dedupe to
  * the graph on the device.  The entry points behind the dedupe (fclu_compat_graph, fclu_partition) still take unique rows
- * a caller made on the host (freddie_amd/cluster_prep.py: unique_structures(), pack_structures()).  read_segment()
- * (:119-172), the poly-tail category of a rep (from the parsed poly_tail dict, :291-300), garbage_cost and the gaps dicts
- * are host code.  The ILP itself (run_ilp, Gurobi) is out of scope.
+ * a caller made on the host (freddie_amd/cluster_prep.py: unique_structures(), pack_structures()).  In front of all of it,
+ * fclu_group_reads() / fclu_partition_segment() take ALL reads of the tints as the native segment_*.tsv reader leaves them
+ * (include/freddie_host.h, fhost_read_segment: label rows, key token streams, tail categories) and group them into reps
+ * (read_segment()'s read_reps, :154-164) on the device.  garbage_cost (from the members' counts) and the gaps dicts are host code.
+ * The ILP itself (run_ilp, Gurobi) is out of scope.
  *
  * Data layout (caller-owned host arrays, copied by the call):
  *   tint t owns the unique reads row_off[t] .. row_off[t+1]  (N_t of them; "unique" = py/freddie_cluster.py:207-215)
@@ -155,6 +157,51 @@ int fclu_partition_reads(fclu_ctx *c, const fclu_reads *reads, int32_t maximum_i
 /* Kernel time of the last fclu_preprocess() / fclu_partition_reads() from HIP events (ms): the per-rep rows; the dedupe
  * (sorts, scans, leaders, nodes and members). */
 int fclu_preprocess_timing(fclu_ctx *c, float *rows_ms, float *dedupe_ms);
+
+/* ---- in front of the front: read_segment()'s grouping of reads into reps (:154-164) ----
+ * ALL reads of every tint, as the native reader leaves them (include/freddie_host.h, fhost_read_segment).  Caller-owned host
+ * arrays, copied by the call. */
+typedef struct fclu_segment {
+    int32_t n_tint;
+    const int64_t *read_off;   /* n_tint + 1: tint t owns the reads read_off[t] .. read_off[t+1], in file order */
+    const int32_t *n_seg;      /* n_tint: M_t */
+    const int64_t *lab_off;    /* n_tint + 1, uint32 words; a read's row is LW_t words, in fclu_reads' layout */
+    const uint32_t *labels;
+    const int64_t *tok_off;    /* reads + 1: a read's key token stream, tok[tok_off[r] .. tok_off[r+1]] */
+    const uint32_t *tok;
+    const uint8_t *tail;       /* per read: 0 'N', 1 'S', 2 'E' */
+} fclu_segment;
+
+/* Two reads of a tint share a rep exactly when their I rows (label & 1; 2 counts as 0) and their token streams are equal.  Reps are
+ * numbered by their first read (Python's dict insertion order), a rep's members are its reads, ascending.  The hash that buckets
+ * the reads never decides (FCLU_HASH_BITS cuts it too).  Refusals as fclu_preprocess's, naming tint and read, and tok_off that
+ * does not start at 0 or falls.  The context stays usable. */
+int fclu_group_reads(fclu_ctx *c, const fclu_segment *in);
+
+/* grouping, preprocess (a rep's row and tail are its FIRST read's), dedupe, graph, pruning and partition in one call: after the
+ * upload everything stays on the device.  fclu_group_results(), fclu_preprocess_results() and fclu_partition_results() hold the
+ * results, the latter two as after fclu_partition_reads() on the reps.  Refusals: fclu_group_reads()'s and fclu_partition()'s. */
+int fclu_partition_segment(fclu_ctx *c, const fclu_segment *in, int32_t maximum_ilp_size);
+
+typedef struct fclu_groups {
+    int32_t n_tint;
+    int64_t n_reads, n_reps;
+    const int64_t *rep_off;        /* n_tint + 1: tint t owns the reps rep_off[t] .. rep_off[t+1] */
+    const int32_t *read_rep;       /* n_reads: the read's rep, local to the tint */
+    const int64_t *rep_mem_off;    /* n_reps + 1 */
+    const int32_t *rep_mem;        /* n_reads: read_reps[i], read indices local to the tint, ascending; len(read_reps[i]) is
+                                      rep_mem_off's difference (garbage_cost) */
+    const int32_t *rep_first;      /* n_reps: read_reps[i][0] */
+} fclu_groups;
+
+/* Result of the last successful fclu_group_reads() / fclu_partition_segment(): pointers into pinned host buffers the context
+ * owns, valid until the context's next call. */
+int fclu_group_results(fclu_ctx *c, fclu_groups *out);
+
+/* Kernel time of the grouping of the last such call from HIP events (ms): the keys; sorts, scans, leaders and members, and in
+ * fclu_partition_segment() the gather of the reps' rows and tails into the preprocess stage's device arrays (fclu_group_reads()
+ * does not gather, and leaves those arrays alone). */
+int fclu_group_timing(fclu_ctx *c, float *keys_ms, float *dedupe_ms);
 
 #ifdef __cplusplus
 }

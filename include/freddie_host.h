@@ -87,6 +87,60 @@ const int64_t *fhost_listing_tint(const fhost_listing *l);                 /* pe
 const int64_t *fhost_listing_size(const fhost_listing *l);                 /* per partition: bytes of its split TSV */
 int32_t fhost_touch(const char *const *paths, int32_t n, int32_t n_threads);   /* 0 on success */
 
+/* ---- segment_<contig>_<tint>.tsv of the clustering stage -----------------------------------
+ * The native form of the reference's read_segment() (py/freddie_cluster.py:119-172, grammar :15-34) up to the rep grouping, which
+ * the GPU does (include/freddie_cluster.h, fclu_group_reads): n files are mapped and parsed on at most n_threads threads into flat
+ * arrays, the tints in file order, then header order inside a file; a tint's reads in file order.
+ * The reader never guesses.  It DECLINES a file (file_declined, with file_line and file_reason) whose lines the grammar does not
+ * match, on which an assert of :131-136 or :165-169 would fire, or that holds a read whose tint has no header yet, a number with
+ * a leading zero, a number that does not fit (18 digits; 2^30 in the gaps field), a gap key (j1, j2) or a poly-tail key twice
+ * in one line, or a line without a newline.  A declined file has no tints in the arrays: the caller runs the Python mirror on it.
+ * Names and contigs are views: offset and length into the file's mapping file_map[tint_file[t]], alive until the free call.
+ * The key token stream of a read (what besides the I row decides its rep, :155-158): its internal gaps' len > 10 ? len : 0 in
+ * line order, then per poly entry 0x80000000 | (key E.: 0x40000000) | (gap > 10 ? gap : 0) in line order. */
+typedef struct fhost_segments {
+    void *owner;
+    int32_t n_file, n_tint;
+    int64_t n_read;
+    /* per file */
+    const int32_t *file_declined;       /* 1: declined */
+    const int64_t *file_line;           /* the line (from 1) that declined it, else 0 */
+    const char *const *file_reason;     /* "" or why */
+    const char *const *file_map;        /* the mapping (NULL: empty or declined) */
+    const int64_t *file_tint_off;       /* n_file + 1 */
+    /* per tint */
+    const int64_t *tint_id;
+    const int32_t *tint_file;
+    const int64_t *tint_chr_off;
+    const int32_t *tint_chr_len;
+    const int32_t *n_seg;               /* M_t = positions - 1 */
+    const int64_t *pos_off;             /* n_tint + 1 */
+    const int64_t *pos;                 /* the segment positions */
+    const int64_t *read_off;            /* n_tint + 1 */
+    const int64_t *lab_off;             /* n_tint + 1, uint32 words: read r of tint t has its row at lab_off[t] + r * LW_t */
+    /* per read */
+    const int64_t *rid;
+    const uint8_t *strand;              /* '+' or '-' */
+    const int64_t *name_off;
+    const int32_t *name_len;
+    const int64_t *chr_off;
+    const int32_t *chr_len;
+    const uint32_t *labels;             /* fclu_reads' layout: two bits a label (ASCII & 3), LW_t = max(ceil(M_t / 16), 1) words a row */
+    const uint8_t *tail;                /* 0 'N', 1 'S', 2 'E' (:293-304): exactly one poly entry, SA/ST resp. EA/ET, length > 10 */
+    const int64_t *gap_off;             /* n_read + 1 */
+    const int32_t *gaps;                /* (j1, j2, len) */
+    const int64_t *clip_off;            /* n_read + 1 */
+    const int32_t *clips;               /* (0 SSC / 1 ESC, len) */
+    const int64_t *poly_off;            /* n_read + 1 */
+    const int32_t *polys;               /* (0 SA / 1 ST / 2 EA / 3 ET, len, gap) */
+    const int64_t *tok_off;             /* n_read + 1 */
+    const uint32_t *tok;
+} fhost_segments;
+
+/* 0 on success (declined files included); out is zeroed otherwise. */
+int32_t fhost_read_segment(const char *const *paths, int32_t n, int32_t n_threads, fhost_segments *out);
+void fhost_segments_free(fhost_segments *s);
+
 #ifdef __cplusplus
 }
 #endif

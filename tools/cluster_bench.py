@@ -9,6 +9,9 @@ synthetic preprocessed tints through include/freddie_cluster.h.
     python tools/cluster_bench.py --front [--workload many|big] [--steps K]
                        (label rows in: the host front preprocess_ilp + unique_structures + pack_structures + pack_members, then
                         Context.partition, against the one call Context.partition_labels; the new kernels' event times)
+    python tools/cluster_bench.py --files [--workload many|big] [--steps K] [--baseline-steps K] [--threads N]
+                       (segment_*.tsv files in: the native reader, the rep grouping and the whole cluster_files_batch, against
+                        read_segment + pack_labels + Context.partition_labels on the same files)
 
 One JSON line: read pairs tested per second of the CALL (packed host arrays in -> pruned adjacency in host memory: copies,
 kernels and the pruning loop's host round trips all inside), the kernel times as detail, and the bound of the compatibility
@@ -213,6 +216,99 @@ def run_front(workload="many", steps=5, maximum_ilp_size=1000, dup=0.1):
     }
 
 
+def write_segment_files(workload, directory, seed=7):
+    """The workload as segment_<contig>_<tint>.tsv files, a tint a file: rows are noisy sub-ranges of a few isoform patterns (as
+    cluster_util.random_tint draws them), a fifth of the zeros written as 2, every structure written as one to three reads whose 2s
+    and small gaps differ (so they share a rep), one internal gap a read and a poly tail on a quarter of them."""
+    w = WORKLOADS[workload]
+    M, n = w["n_segs"], w["n_reps"]
+    rng = np.random.default_rng(seed)
+    header_pos = ",".join(str(100 + 50 * j) for j in range(M + 1))
+    paths, n_reads = [], 0
+    for t in range(w["n_tints"]):
+        iso = rng.random((8, M)) < 0.6
+        a = rng.integers(0, M, n); b = rng.integers(a, M)
+        col = np.arange(M)[None, :]
+        rows = (iso[rng.integers(0, 8, n)] ^ (rng.random((n, M)) < 0.03)) & (col >= a[:, None]) & (col <= b[:, None])
+        copies = rng.integers(1, 4, n)
+        g1 = rng.integers(0, M - 1, n); l1 = rng.choice([4, 9, 15, 60], n)
+        poly = rng.integers(0, 16, n)
+        lines = ["#ctg%d\t%d\t%s\n" % (t % 7, t, header_pos)]
+        rid = 0
+        for c in range(3):
+            idx = np.flatnonzero(copies > c)
+            text = np.where(rows[idx], 49, np.where(rng.random((len(idx), M)) < 0.2, 50, 48)).astype(np.uint8)
+            small = rng.integers(0, 11, len(idx))
+            for k, i in enumerate(idx.tolist()):
+                gaps = "%d-%d:%d," % (g1[i], g1[i] + 1, l1[i] if l1[i] > 10 else small[k])
+                if poly[i] < 4:
+                    gaps += "%s_%d:%d," % (("SA", "ST", "EA", "ET")[poly[i]], 8 + 3 * (i % 5), (i % 3) * 9)
+                lines.append("%d\tread%d_%d\tctg%d\t%s\t%d\t%s\t%s\n" % (rid, i, c, t % 7, "+-"[i & 1], t, text[k].tobytes().decode(), gaps))
+                rid += 1
+        n_reads += rid
+        path = os.path.join(directory, "segment_ctg%d_%d.tsv" % (t % 7, t))
+        with open(path, "w") as f:
+            f.write("".join(lines))
+        paths.append(path)
+    return paths, n_reads
+
+
+def run_files(workload="many", steps=5, baseline_steps=1, maximum_ilp_size=1000, threads=16):
+    """segment_*.tsv files of the workload in a temporary directory, then on the same files, medians after one warm-up:
+      native read   read_segment_arrays;  group  Context.group_reads (with fclu_group_timing's kernel times);
+      whole         cluster_files_batch: reader + one device call, arrays out;
+      baseline      the path without them: read_segment + pack_labels (with tail_categories) + Context.partition_labels."""
+    import tempfile
+    with tempfile.TemporaryDirectory() as d:
+        paths, n_reads = write_segment_files(workload, d)
+        n_bytes = sum(os.path.getsize(p) for p in paths)
+        ctx = cluster_prep.Context(0)
+        arrays, groups, prep, arr = cluster_prep.cluster_files_batch(paths, maximum_ilp_size, ctx, threads=threads)      # warm-up
+        read, group, whole, keys, dedupe = [], [], [], [], []
+        for _ in range(steps):
+            t0 = time.perf_counter()
+            a = cluster_prep.read_segment_arrays(paths, threads)
+            t1 = time.perf_counter()
+            ctx.group_reads(a)
+            t2 = time.perf_counter()
+            tm = ctx.group_timing()
+            a.close()
+            t3 = time.perf_counter()
+            cluster_prep.cluster_files_batch(paths, maximum_ilp_size, ctx, threads=threads)[0].close()
+            t4 = time.perf_counter()
+            read.append(t1 - t0); group.append(t2 - t1); whole.append(t4 - t3); keys.append(tm["keys_ms"]); dedupe.append(tm["dedupe_ms"])
+        base, same = [], True
+        for _ in range(baseline_steps):
+            t0 = time.perf_counter()
+            tints = [t for p in paths for t in cluster_prep.read_segment(p).values()]
+            t1 = time.perf_counter()
+            packed = cluster_prep.pack_labels(tints)
+            t2 = time.perf_counter()
+            prep0, arr0 = ctx.partition_labels(packed, maximum_ilp_size)
+            t3 = time.perf_counter()
+            base.append(dict(read_segment=t1 - t0, pack_labels=t2 - t1, partition_labels=t3 - t2, total=t3 - t0))
+            same = same and all(np.array_equal(prep0[k], prep[k]) for k in prep0) and all(np.array_equal(arr0[k], arr[k]) for k in arr0)
+            del tints
+        ctx.close()
+        declined = len(arrays.declined)
+        arrays.close()
+    med = lambda xs: float(np.median(xs)) * 1e3
+    base_ms = {k: med([b[k] for b in base]) for k in base[0]} if base else None
+    return {
+        "metric": "segment TSVs in, partitions out: native reader + one device call against read_segment + pack_labels + partition_labels",
+        "unit": "ms", "data": "synthetic",
+        "config": {"workload": "cluster-" + workload, **WORKLOADS[workload], "files": len(paths), "bytes": n_bytes, "reads": n_reads,
+                   "reps": int(groups["n_reps"]), "unique_rows": int(prep["n_rows"]), "maximum_ilp_size": maximum_ilp_size, "steps": steps,
+                   "baseline_steps": baseline_steps, "threads": threads, "files_declined": declined},
+        "native_read_ms": med(read), "group_reads_call_ms": med(group),
+        "kernel_ms": {"keys (k_gkeys)": float(np.median(keys)), "dedupe (sorts, scans, k_gleader, k_greps, k_mem_off)": float(np.median(dedupe))},
+        "cluster_files_batch_ms": med(whole), "baseline_ms": base_ms,
+        "identical_results": bool(same) if base else None,
+        "whole_path_faster_than_baseline": bool(med(whole) < base_ms["total"]) if base else None,
+        "spread_ms": {"native_read": [min(read) * 1e3, max(read) * 1e3], "cluster_files_batch": [min(whole) * 1e3, max(whole) * 1e3]},
+    }
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workload", default="many", choices=sorted(WORKLOADS))
@@ -220,8 +316,13 @@ def main():
     ap.add_argument("--partitions", action="store_true", help="measure Context.partition() against the host tail (FCLU_HOST_PARTITIONS=1)")
     ap.add_argument("--host-sample", type=int, default=20, help="--partitions: tints the two partition_reads_batch() runs take")
     ap.add_argument("--front", action="store_true", help="measure the host front + Context.partition against Context.partition_labels")
+    ap.add_argument("--files", action="store_true", help="measure the native segment TSV reader + Context.partition_segment against read_segment + partition_labels")
+    ap.add_argument("--baseline-steps", type=int, default=1, help="--files: runs of the Python baseline (it takes seconds a run)")
+    ap.add_argument("--threads", type=int, default=16, help="--files: threads of the native reader")
     args = ap.parse_args()
-    if args.front:
+    if args.files:
+        print(json.dumps(run_files(args.workload, args.steps, args.baseline_steps, threads=args.threads)))
+    elif args.front:
         print(json.dumps(run_front(args.workload, args.steps)))
     elif args.partitions:
         print(json.dumps(run_partitions(args.workload, args.steps, host_sample=args.host_sample)))
