@@ -1,0 +1,265 @@
+"""The clustering stage from segment_*.tsv to cluster_*.tsv: the reference's cluster_tint() (py/freddie_cluster.py:694-780) restated
+with its loop turned inside out.  The reference runs the rounds of one partition after the other; rounds of different partitions do
+not depend on each other, so here round r of EVERY active partition of every tint of a batch is one device call
+(cluster_prep.Context.round_models: informative segments, support, correction terms, pairs, gap groups) followed by the solves
+(cluster_solve.solve_round: HiGHS; a process pool when asked for), and the results are put back in the reference's order.
+
+  cluster_tint :716-773   -> cluster_tints()        min_isoform_size, max_rounds, the breaks and garbage_rids as there
+  run_ilp's read-out :601-635 -> read_out()         isoform exons = e on informative segments, the first remaining rep's I elsewhere;
+                                                     corrections = the rep's first read's data, '-' where uninformative, 'X' where C, x and e
+  output_isoforms :639-691 -> output_isoforms()
+The solve is HiGHS, not Gurobi: where a round's optimum is not unique the tie may be broken differently."""
+import os
+
+from . import cluster_prep, cluster_solve
+
+MAX_WORKERS = 16
+FILES_PER_BATCH = 256
+
+
+def ilp_settings(recycle_model="constant", epsilon=0.2, offset=20, timeout=1, max_rounds=30, min_isoform_size=3, max_ilp=1000):
+    return dict(recycle_model=recycle_model, K=2, epsilon=epsilon, offset=offset, timeout=timeout, max_rounds=max_rounds, threads=1,
+                min_isoform_size=min_isoform_size, max_ilp=max_ilp)
+
+
+def garbage_costs(tint, recycle_model):
+    """Per rep, the three garbage costs as the reference's formulas read (:186-194, :314-322); its own preprocess_ilp() hands the
+    exons / introns formulas a list where they want a dict and raises, so only their evident meaning can be restated."""
+    I, C = tint["ilp_data"]["I"], tint["ilp_data"]["C"]
+    out = {}
+    for i, members in enumerate(tint["read_reps"]):
+        if recycle_model == "exons":
+            out[i] = len(members) * max(sum(I[i]) - 0.5, 1)
+        elif recycle_model == "introns":
+            out[i] = len(members) * max(sum(C[i]) - 0.5, 1)
+        else:
+            out[i] = len(members) * 3
+    return out
+
+
+def read_out(tint, remaining, model, x, e):
+    """The round's isoform as run_ilp() returns it (:601-635): dict(exons, rid_to_corrections)."""
+    M = len(tint["segs"])
+    I, C = tint["ilp_data"]["I"], tint["ilp_data"]["C"]
+    e_of = dict(zip(model["inf_seg"], e))
+    exons = [e_of[j] if j in e_of else I[remaining[0]][j] for j in range(M)]
+    rid_to_corrections = dict()
+    for c, i in enumerate(remaining):
+        if not x[c]:
+            continue
+        data = tint["reads"][tint["read_reps"][i][0]]["data"]
+        corrections = [str(data[j]) for j in range(M)]
+        for j in range(M):
+            if j not in e_of:
+                corrections[j] = "-"
+            elif C[i][j] == 1 and e_of[j]:
+                corrections[j] = "X"
+        rid_to_corrections[i] = corrections
+    return dict(exons=exons, rid_to_corrections=rid_to_corrections)
+
+
+def _read_line(read, isoform, labels):
+    out = [str(read["id"]), read["name"], read["chr"], read["strand"], str(read["tint"]), str(read["partition"]),
+           str(read["poly_tail_category"]), isoform, "".join(map(str, labels))]
+    exon_strs = [str(v) for v in labels]
+    for (j1, _), l in read["gaps"].items():
+        exon_strs[j1] += "({})".format(l)                    # (j1 = -1, a start tail's pseudo-gap, lands on the last segment, as there)
+    out.extend(exon_strs)
+    out.extend("{}:{}".format(k, v) for k, v in sorted(read["poly_tail"].items()))
+    return "\t".join(out) + "\n"
+
+
+def output_isoforms(tint, out_file):
+    """cluster_*.tsv of one tint (:639-691)."""
+    reads, read_reps = tint["reads"], tint["read_reps"]
+    out_file.write("#{}\t{}\t{}\n".format(tint["chr"], tint["id"], ",".join([str(s[0]) for s in tint["segs"]] + [str(tint["segs"][-1][1])])))
+    for iid, isoform in enumerate(tint["isoforms"]):
+        out_file.write("isoform_{}\t{}\t{}\n".format(iid, tint["id"], "".join(map(str, isoform["exons"]))))
+        for i, corrections in isoform["rid_to_corrections"].items():
+            for ridx in read_reps[i]:
+                out_file.write(_read_line(reads[ridx], str(iid), corrections))
+    for i in tint["garbage_rids"]:
+        for ridx in read_reps[i]:
+            out_file.write(_read_line(reads[ridx], "*", reads[ridx]["data"]))
+
+
+def _solve_job(job):
+    solve, model, settings = job
+    return solve(model, settings)
+
+
+def cluster_tints(tints, part0, ctx, settings, solve=cluster_solve.solve_round, pool=None, on_round=None):
+    """The rounds of every partition of preprocessed, partitioned tints whose rows the context holds (Context.partition_segment() /
+    partition_labels() and round_setup()); part0[t] = the batch's number of tint t's first partition.  Leaves tint['isoforms'],
+    tint['garbage_rids'] and the reads' 'partition' as cluster_tint() does, and returns per tint the timeout.log lines
+    [(status, tint id, partition, round, remaining reps)].  on_round: called with a dict per solved round (tests, profiles)."""
+    cluster_solve.check_settings(settings)
+    min_size, max_rounds = settings["min_isoform_size"], settings["max_rounds"]
+    state = []                                               # a partition: its tint, number, remaining reps, isoforms; active or not
+    for t, tint in enumerate(tints):
+        tint["garbage_cost"] = garbage_costs(tint, settings["recycle_model"])
+        tint["max_lg"] = sum(s[2] for s in tint["segs"])
+        for q, (rids, incomp) in enumerate(tint["partitions"]):
+            for rid in rids:
+                for ridx in tint["read_reps"][rid]:
+                    tint["reads"][ridx]["partition"] = q
+            state.append(dict(t=t, q=q, remaining=list(rids), incomp=incomp, isoforms=[], active=True))
+    logs = [[] for _ in tints]
+    for round_num in range(max_rounds):
+        todo = []
+        for s in state:
+            if s["active"] and sum(len(tints[s["t"]]["read_reps"][i]) for i in s["remaining"]) < min_size:
+                s["active"] = False                          # (:729-730)
+            if s["active"]:
+                todo.append(s)
+        if not todo:
+            break
+        arr = ctx.round_models([part0[s["t"]] + s["q"] for s in todo], [s["remaining"] for s in todo])
+        jobs = []
+        for p, s in enumerate(todo):
+            tint = tints[s["t"]]
+            model = cluster_prep.round_model(arr, p)
+            if model is None:
+                raise cluster_prep.ClusterError("tint %s partition %d round %d: a gap of column %d (rep %d) ends on an uninformative segment "
+                                                "(the reference's assert, py/freddie_cluster.py:467-468)" %
+                                                (tint["id"], s["q"], round_num, int(arr["refused"][p]), s["remaining"][int(arr["refused"][p])]))
+            model["garbage"] = [tint["garbage_cost"][i] for i in s["remaining"]]
+            model["max_lg"] = tint["max_lg"]
+            model["key"] = (tint["id"], s["q"], round_num)        # (for a solver that logs, or replays: tests)
+            jobs.append((solve, model, settings))
+        results = pool.map(_solve_job, jobs, chunksize=1) if pool is not None else [_solve_job(j) for j in jobs]
+        for s, (_, model, _), (status, x, e) in zip(todo, jobs, results):
+            tint = tints[s["t"]]
+            logs[s["t"]].append((status, tint["id"], s["q"], round_num, len(s["remaining"])))
+            if on_round is not None:
+                on_round(dict(tint=tint, partition=s["q"], round=round_num, remaining=list(s["remaining"]), incomp=s["incomp"], status=status,
+                              cost=cluster_solve.round_cost(model, x, e) if status == cluster_solve.OPTIMAL else None, x=x, e=e))
+            if status != cluster_solve.OPTIMAL:
+                s["active"] = False                          # (:750-751)
+                continue
+            isoform = read_out(tint, s["remaining"], model, x, e)
+            size = sum(len(tint["read_reps"][rid]) for rid in isoform["rid_to_corrections"])
+            if size < min_size:
+                s["active"] = False                          # (:755-756; with one isoform a round, :758-759 is the same test)
+                continue
+            s["isoforms"].append(isoform)
+            for rid in isoform["rid_to_corrections"]:
+                s["remaining"].remove(rid)
+    for t, tint in enumerate(tints):
+        tint["isoforms"], tint["garbage_rids"] = [], []
+    for s in state:                                          # the reference's order: partition by partition, a partition's rounds in order
+        tint = tints[s["t"]]
+        for isoform in s["isoforms"]:
+            tint["isoforms"].append(isoform)
+            for rid, corrections in isoform["rid_to_corrections"].items():
+                for ridx in tint["read_reps"][rid]:
+                    tint["reads"][ridx]["corrections"] = corrections
+                    tint["reads"][ridx]["isoform"] = len(tint["isoforms"]) - 1
+        tint["garbage_rids"].extend(sorted(s["remaining"]))
+    return [sorted(lines, key=lambda l: (l[2], l[3])) for lines in logs]
+
+
+def stage_files(paths, settings, ctx, threads=8):
+    """segment_*.tsv files -> (tints as preprocess_ilp() + partition_reads() leave them, part0), rows and pair lists on the context."""
+    arrays = cluster_prep.read_segment_arrays(paths, threads)
+    groups, prep, arr = ctx.partition_segment(arrays, settings["max_ilp"])
+    tints = cluster_prep.tints_from_arrays(arrays, groups, prep, arr, dict(recycle_model="constant"))
+    ctx.round_setup(*cluster_prep.round_gaps(tints))
+    return tints, arr["tint_part_off"].tolist(), arrays.file_tint_off.tolist()
+
+
+def cluster_files(paths, settings, ctx, solve=cluster_solve.solve_round, pool=None, on_round=None, threads=8):
+    """Yields (tints of the file, their timeout.log lines) per path, in order, a batch of FILES_PER_BATCH files at a time as it finishes
+    (a caller that writes as it goes keeps one batch in memory and loses nothing finished to a late failure); a batch whose pair list
+    the library refuses as too large for one call is halved."""
+    for b0 in range(0, len(paths), FILES_PER_BATCH):
+        pending = [list(paths[b0:b0 + FILES_PER_BATCH])]
+        while pending:
+            batch = pending.pop(0)
+            try:
+                tints, part0, file_off = stage_files(batch, settings, ctx, threads)
+            except cluster_prep.ClusterError as err:
+                if err.code != cluster_prep.ERR_UNSUPPORTED or len(batch) < 2:
+                    raise
+                pending[:0] = [batch[:len(batch) // 2], batch[len(batch) // 2:]]
+                continue
+            logs = cluster_tints(tints, part0, ctx, settings, solve, pool, on_round)
+            for f in range(len(batch)):
+                yield tints[file_off[f]:file_off[f + 1]], logs[file_off[f]:file_off[f + 1]]
+
+
+# ---- the command line (py/freddie_cluster.py :37-110, :783-827) ---------------------------------------------------------------
+def parse_args(argv=None):
+    import argparse
+    parser = argparse.ArgumentParser(
+        description="Cluster aligned reads into isoforms.  The rounds' models are built on the GPU; the solve is HiGHS (scipy.optimize.milp), "
+                    "not Gurobi: optimal ties may be broken differently from Gurobi's.  The .lp, .glog and .sol files are Gurobi's and are not "
+                    "written; --logs-dir holds the timeout.log files, with this program's status (OPTIMAL / NO_SOLUTION) in the first column.")
+    recycle_models = ["constant", "exons", "introns", "relative"]
+    parser.add_argument("-s", "--segment-dir", type=str, required=True, help="Path to Freddie segment directory of the reads")
+    parser.add_argument("-rm", "--recycle-model", type=str, default="constant",
+                        help="Model type: {}. Default: {}.  relative is refused: it needs E2I_min".format(", ".join(recycle_models), "constant"))
+    parser.add_argument("-go", "--gap-offset", type=int, default=20, help="Slack +- value for exons and the unaligned gaps. Default: 20")
+    parser.add_argument("-e", "--epsilon", type=float, default=0.2, help="Epsilon percent value for how much can unaligned gaps can cover. Default: 0.2")
+    parser.add_argument("-mr", "--max-rounds", type=int, default=30, help="Maximum number of ILP rounds. Default 30")
+    parser.add_argument("-is", "--min-isoform-size", type=int, default=3, help="Minimum isoform size in terms of number supporting reads. Default 3")
+    parser.add_argument("-mi", "--max-ilp", type=int, default=1000,
+                        help="Maximum number of unique reads allowed for an ILP instance. ILP instances with more reads will have their input "
+                             "broken into evenly sized problems, each with less than the max. Default 1000")
+    parser.add_argument("-to", "--timeout", type=int, default=1, help="Solver time-out in minutes. Default: 1")
+    parser.add_argument("-t", "--threads", type=int, default=1, help="Number of processes that solve (at most {})".format(MAX_WORKERS))
+    parser.add_argument("-l", "--logs-dir", type=str, default=None, help="Directory path where logs will be outputted. Default: No log")
+    parser.add_argument("-o", "--outdir", type=str, default="freddie_cluster/", help="Path to output directory. Default: freddie_cluster/")
+    args = parser.parse_args(argv)
+    assert args.recycle_model in recycle_models
+    assert args.gap_offset >= 0
+    assert args.epsilon >= 0
+    assert args.timeout > 0
+    assert args.threads > 0
+    assert args.min_isoform_size >= 0
+    assert args.max_rounds >= 0
+    return args
+
+
+def main(argv=None, make_context=None):
+    """make_context: what opens the device context, cluster_prep.Context by default (a stand-in runs the command line without a GPU)."""
+    import glob
+    args = parse_args(argv)
+    args.segment_dir = args.segment_dir.rstrip("/")
+    settings = ilp_settings(args.recycle_model, args.epsilon, args.gap_offset, args.timeout, args.max_rounds, args.min_isoform_size, args.max_ilp)
+    cluster_solve.check_settings(settings)
+    jobs = []
+    for contig in os.listdir(args.segment_dir):
+        if not os.path.isdir("{}/{}".format(args.segment_dir, contig)):
+            continue
+        os.makedirs("{}/{}".format(args.outdir, contig), exist_ok=False)
+        if args.logs_dir is not None:
+            os.makedirs("{}/{}".format(args.logs_dir, contig), exist_ok=False)
+        for path in glob.iglob("{}/{}/segment_*.tsv".format(args.segment_dir, contig)):
+            jobs.append((contig, int(path[:-4].split("/")[-1].split("_")[-1]), path))
+    pool = None
+    if args.threads > 1:                                     # before the GPU is opened: the workers are forked without it and never touch it
+        from multiprocessing import Pool
+        pool = Pool(min(args.threads, MAX_WORKERS))
+    try:
+        ctx = (make_context or cluster_prep.Context)(0)
+        try:
+            results = cluster_files([j[2] for j in jobs], settings, ctx, pool=pool, threads=min(args.threads, MAX_WORKERS))
+            for idx, ((contig, tint_id, _), (tints, logs)) in enumerate(zip(jobs, results)):       # written as the batches finish
+                assert len(tints) == 1
+                tint = tints[0]
+                if args.logs_dir is not None:
+                    os.makedirs("{}/{}/{}".format(args.logs_dir, contig, tint["id"]), exist_ok=True)
+                    with open("{}/{}/{}/timeout.log".format(args.logs_dir, contig, tint["id"]), "w+") as log:
+                        for line in logs[0]:
+                            print("\t".join(map(str, line)), file=log)
+                with open("{}/{}/cluster_{}_{}.tsv".format(args.outdir, contig, contig, tint_id), "w+") as out_file:
+                    output_isoforms(tint, out_file)
+                print("[freddie_cluster] Done with {}/{} tints ({:.1%})".format(idx + 1, len(jobs), (idx + 1) / len(jobs)))
+        finally:
+            ctx.close()
+    finally:
+        if pool is not None:
+            pool.close()
+            pool.join()
+    return 0

@@ -15,7 +15,9 @@ Reference map (file:line of vpc-ccg/freddie ``py/freddie_cluster.py``):
   segment_*.tsv files -> arrays without a Python loop over reads: read_segment_arrays() (the native reader of libfreddie_host.so),
        Context.group_reads() / Context.partition_segment() (read_reps :154-164 on the GPU, then all of the above),
        cluster_files_batch(), tints_from_arrays() (back to the dicts, for code that wants them)
-The ILP (run_ilp, Gurobi) and everything after it are out of scope.  There is no CPU implementation of the quadratic
+  informative_segs :331-344 and the model run_ilp builds :397-535 -> Context.round_setup() / Context.round_models() (GPU: one call per
+       round of many partitions), round_gaps(), round_model(); the solve is freddie_amd/cluster_solve.py, the loop freddie_amd/cluster.py
+There is no CPU implementation of the quadratic
 loops in this package: without the HIP library partition_reads() raises.  FCLU_HOST_PARTITIONS=1 keeps :256-274 on the
 host, behind the GPU's graph (adjacency_matrix + _components + _partitions_from_graph): for A/B runs and timings.
 """
@@ -156,7 +158,8 @@ CLUSTER_SRC = [os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", 
 EXPORTS = ["fclu_abi_version", "fclu_create", "fclu_destroy", "fclu_last_error", "fclu_compat_graph", "fclu_last_timing",
            "fclu_partition", "fclu_partition_adj", "fclu_partition_results", "fclu_partition_timing",
            "fclu_preprocess", "fclu_preprocess_results", "fclu_partition_reads", "fclu_preprocess_timing",
-           "fclu_group_reads", "fclu_partition_segment", "fclu_group_results", "fclu_group_timing"]
+           "fclu_group_reads", "fclu_partition_segment", "fclu_group_results", "fclu_group_timing",
+           "fclu_round_setup", "fclu_round_models", "fclu_round_results", "fclu_round_timing"]
 ERR_UNSUPPORTED = 3
 _lib = None
 
@@ -202,6 +205,19 @@ class _Segment(ctypes.Structure):
 class _Groups(ctypes.Structure):
     _fields_ = [("n_tint", ctypes.c_int32), ("n_reads", ctypes.c_int64), ("n_reps", ctypes.c_int64)] + [
         (name, ctypes.c_void_p) for name in ("rep_off", "read_rep", "rep_mem_off", "rep_mem", "rep_first")]
+
+
+class _RoundBatch(ctypes.Structure):
+    _fields_ = [("n_prob", ctypes.c_int32), ("part", ctypes.c_void_p), ("rid_off", ctypes.c_void_p), ("rids", ctypes.c_void_p)]
+
+
+_ROUND_COUNTS = ("n_cols", "n_inf", "n_sup", "n_corr", "n_pairs", "n_grp", "n_grp_seg", "n_gap_rows")
+_ROUND_ARRAYS = ("refused", "inf_bits_off", "inf_bits", "inf_off", "inf_seg", "sup_off", "sup_cols", "col_off", "corr_off", "corr_seg", "pair_off",
+                 "pairs", "grp_off", "grp", "grp_seg_off", "grp_seg", "grp_len", "row_off", "rows")
+
+
+class _Rounds(ctypes.Structure):
+    _fields_ = [("n_prob", ctypes.c_int32)] + [(n, ctypes.c_int64) for n in _ROUND_COUNTS] + [(n, ctypes.c_void_p) for n in _ROUND_ARRAYS]
 
 
 def build(force=False, verbose=False):
@@ -254,6 +270,14 @@ def load():
     L.fclu_group_results.argtypes = [vp, ctypes.POINTER(_Groups)]
     L.fclu_group_timing.restype = ctypes.c_int
     L.fclu_group_timing.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
+    L.fclu_round_setup.restype = ctypes.c_int
+    L.fclu_round_setup.argtypes = [vp, vp, vp, vp, vp]
+    L.fclu_round_models.restype = ctypes.c_int
+    L.fclu_round_models.argtypes = [vp, ctypes.POINTER(_RoundBatch)]
+    L.fclu_round_results.restype = ctypes.c_int
+    L.fclu_round_results.argtypes = [vp, ctypes.POINTER(_Rounds)]
+    L.fclu_round_timing.restype = ctypes.c_int
+    L.fclu_round_timing.argtypes = [vp] + [ctypes.POINTER(ctypes.c_float)] * 3
     _lib = L
     return L
 
@@ -431,6 +455,61 @@ class Context:
         parts = self._partition_arrays("fclu_partition_segment", rc)
         return self._group_arrays(), self._prep_arrays(), parts
 
+    def round_setup(self, gap_off, gaps, seg_off, seg_len):
+        """Once per batch, behind partition_labels() / partition_segment() on this context: the reps' gap triples (j1, j2, l) (CSR by the
+        batch's reps, round_gaps()) and the segments' lengths (CSR by tint)."""
+        gap_off = np.ascontiguousarray(gap_off, np.int64)
+        gaps = np.ascontiguousarray(gaps, np.int32).reshape(-1)
+        seg_off = np.ascontiguousarray(seg_off, np.int64)
+        seg_len = np.ascontiguousarray(seg_len, np.int32)
+        if gap_off.size == 0 or seg_off.size == 0 or gaps.size != 3 * int(gap_off[-1]) or seg_len.size != int(seg_off[-1]):
+            raise ClusterError("round_setup: array lengths do not match (gaps: 3 x gap_off[-1]; seg_len: seg_off[-1])")
+        rc = self._L.fclu_round_setup(self._h, gap_off.ctypes.data, gaps.ctypes.data if gaps.size else None, seg_off.ctypes.data,
+                                      seg_len.ctypes.data if seg_len.size else None)
+        if rc != 0:
+            raise ClusterError("fclu_round_setup: " + self._L.fclu_last_error(self._h).decode(), rc)
+
+    def round_models(self, parts, remaining):
+        """The ILP models of one round of many partitions, one device call (include/freddie_cluster.h, fclu_rounds): parts = partition
+        ids numbered through the batch, remaining = per problem the remaining rep ids (local to the tint) in the caller's order.
+        Returns the flat numpy arrays, pairs as [n, 2], grp as [n, 2], rows as [n, 3] (column, group, l); round_model() cuts one
+        problem out.  refused[p] >= 0: the reference raises on problem p (a gap with an uninformative endpoint, :467-468), the value is
+        the smallest offending column and the problem has no model."""
+        part = np.ascontiguousarray(parts, np.int64)
+        if len(remaining) != part.size:
+            raise ClusterError("round_models: %d partitions, %d remaining lists" % (part.size, len(remaining)))
+        rid_off = np.zeros(part.size + 1, np.int64)
+        np.cumsum([len(r) for r in remaining], out=rid_off[1:])
+        rids = np.fromiter((i for r in remaining for i in r), np.int32, int(rid_off[-1]))
+        b = _RoundBatch(n_prob=part.size, part=part.ctypes.data if part.size else None, rid_off=rid_off.ctypes.data,
+                        rids=rids.ctypes.data if rids.size else None)
+        rc = self._L.fclu_round_models(self._h, ctypes.byref(b))
+        if rc != 0:
+            raise ClusterError("fclu_round_models: " + self._L.fclu_last_error(self._h).decode(), rc)
+        r = _Rounds()
+        rc = self._L.fclu_round_results(self._h, ctypes.byref(r))
+        if rc != 0:
+            raise ClusterError("fclu_round_results: " + self._L.fclu_last_error(self._h).decode(), rc)
+        P = r.n_prob
+        out = dict(n_prob=P)
+        for n in _ROUND_COUNTS:
+            out[n] = int(getattr(r, n))
+        for n in ("inf_bits_off", "inf_off", "col_off", "pair_off", "grp_off", "row_off"):
+            out[n] = _copy_out(getattr(r, n), P + 1, np.int64)
+        for n, cnt, dt in (("refused", P, np.int32), ("inf_bits", int(out["inf_bits_off"][-1]), np.uint32), ("inf_seg", out["n_inf"], np.int32),
+                           ("sup_off", out["n_inf"] + 1, np.int64), ("sup_cols", out["n_sup"], np.int32), ("corr_off", out["n_cols"] + 1, np.int64),
+                           ("corr_seg", out["n_corr"], np.int32), ("pairs", 2 * out["n_pairs"], np.int32), ("grp", 2 * out["n_grp"], np.int32),
+                           ("grp_seg_off", out["n_grp"] + 1, np.int64), ("grp_seg", out["n_grp_seg"], np.int32),
+                           ("grp_len", out["n_grp_seg"], np.int32), ("rows", 3 * out["n_gap_rows"], np.int32)):
+            out[n] = _copy_out(getattr(r, n), cnt, dt)
+        out["pairs"] = out["pairs"].reshape(-1, 2); out["grp"] = out["grp"].reshape(-1, 2); out["rows"] = out["rows"].reshape(-1, 3)
+        return out
+
+    def round_timing(self):
+        a, b, f = ctypes.c_float(), ctypes.c_float(), ctypes.c_float()
+        self._L.fclu_round_timing(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(f))
+        return dict(count_ms=a.value, gaps_ms=b.value, fill_ms=f.value)
+
     def group_timing(self):
         a, b = ctypes.c_float(), ctypes.c_float()
         self._L.fclu_group_timing(self._h, ctypes.byref(a), ctypes.byref(b))
@@ -461,6 +540,43 @@ class Context:
             self.close()
         except Exception:
             pass
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# a round's models (run_ilp :347-535 up to the solver): the inputs of Context.round_setup() and one problem of Context.round_models()
+# ---------------------------------------------------------------------------------------------------------------
+def round_gaps(tints):
+    """(gap_off, gaps [n, 3], seg_off, seg_len) of preprocessed tints for Context.round_setup(): per rep the (j1, j2, l) of its first
+    read's gaps dict, pseudo-gaps included, in the dict's order."""
+    gap_off, gaps, seg_off, seg_len = [0], [], [0], []
+    for tint in tints:
+        for members in tint["read_reps"]:
+            gaps.extend((j1, j2, l) for (j1, j2), l in tint["reads"][members[0]]["gaps"].items())
+            gap_off.append(len(gaps))
+        seg_len.extend(s[2] for s in tint["segs"])
+        seg_off.append(len(seg_len))
+    return (np.array(gap_off, np.int64), np.array(gaps, np.int32).reshape(-1, 3), np.array(seg_off, np.int64), np.array(seg_len, np.int32))
+
+
+def round_model(arr, p):
+    """Problem p of Context.round_models() as plain lists, or None when it was refused: informative (bit row as a list of 0 / 1 is the
+    caller's, from inf_bits), inf_seg, support (per informative segment its columns), corrections (per column its segments), pairs,
+    groups [(j1, j2)], group_segs (per group [(j, length)]), gap_rows [(column, group, l)]."""
+    if arr["refused"][p] >= 0:
+        return None
+    i0, i1 = int(arr["inf_off"][p]), int(arr["inf_off"][p + 1])
+    c0, c1 = int(arr["col_off"][p]), int(arr["col_off"][p + 1])
+    g0, g1 = int(arr["grp_off"][p]), int(arr["grp_off"][p + 1])
+    so, co, go = arr["sup_off"].tolist(), arr["corr_off"], arr["grp_seg_off"]
+    sup, corr, gs, gl = arr["sup_cols"], arr["corr_seg"], arr["grp_seg"], arr["grp_len"]
+    return dict(n_cols=c1 - c0, words=arr["inf_bits"][int(arr["inf_bits_off"][p]):int(arr["inf_bits_off"][p + 1])].tolist(),
+                inf_seg=arr["inf_seg"][i0:i1].tolist(),
+                support=[sup[so[k]:so[k + 1]].tolist() for k in range(i0, i1)],
+                corrections=[corr[int(co[c]):int(co[c + 1])].tolist() for c in range(c0, c1)],
+                pairs=[tuple(x) for x in arr["pairs"][int(arr["pair_off"][p]):int(arr["pair_off"][p + 1])].tolist()],
+                groups=[tuple(x) for x in arr["grp"][g0:g1].tolist()],
+                group_segs=[list(zip(gs[int(go[g]):int(go[g + 1])].tolist(), gl[int(go[g]):int(go[g + 1])].tolist())) for g in range(g0, g1)],
+                gap_rows=[tuple(x) for x in arr["rows"][int(arr["row_off"][p]):int(arr["row_off"][p + 1])].tolist()])
 
 
 # ---------------------------------------------------------------------------------------------------------------

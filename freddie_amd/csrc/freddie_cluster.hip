@@ -925,6 +925,272 @@ __global__ void __launch_bounds__(256) k_ggather(int n_tint, i64 n_words, const 
     }
 }
 
+// ================================================================================================================
+// A round's ILP models as arrays (fclu_round_models): what run_ilp() builds its model from (py/freddie_cluster.py:359, :397-535), for
+// round r of many partitions at once.  A problem = a partition and its remaining reps ("columns", in the caller's order).
+// ================================================================================================================
+struct RoundProb {
+    i64 col0, rbits_off, rep0, pair0, pair1, inf_off, seg0;   // first column (in rids); the tint's first I / C word, first rep and first
+                                                              // segment length; the partition's pairs; the informative row's first word
+    int n, n_seg, w, pad;                                     // columns, segments, words per row
+};
+
+constexpr int kRoundCounts = 4;                  // per problem: informative segments, support entries, correction terms, pairs
+constexpr int kRoundLdsBytes = 96 * 1024;        // I and C rows of a problem staged in LDS up to this (beside about 5 KB of static arrays: one such
+                                                 // workgroup a CU; two from about 75 KB down)
+constexpr int kRoundTinyBytes = 16 * 1024;       // problems up to this are launched apart, with their own LDS size: a batch's one large problem
+                                                 // does not cost hundreds of small ones their occupancy
+
+// exclusive prefix sum of v over the workgroup's 256 threads (total: the sum); s_wave: 4 words of LDS; synchronises before it returns
+__device__ __forceinline__ i64 block_scan(i64 v, i64 &total, i64 *s_wave) {
+    const int lane = lane_id(), wave = threadIdx.x >> 6;
+    i64 inc = v;
+    for (int s = 1; s < 64; s <<= 1) { const i64 o = __shfl_up(inc, s); if (lane >= s) inc += o; }
+    if (lane == 63) s_wave[wave] = inc;
+    __syncthreads();
+    i64 before = 0;
+    total = 0;
+    for (int x = 0; x < 4; ++x) { const i64 t = s_wave[x]; if (x < wave) before += t; total += t; }
+    __syncthreads();
+    return before + inc - v;
+}
+
+// a[0 .. n) (counts, written by this workgroup) -> base + their exclusive prefix sums, in place
+__device__ __forceinline__ void block_scan_inplace(i64 *a, int n, i64 base, i64 *s_wave) {
+    __syncthreads();
+    i64 carry = base;
+    for (int i0 = 0; i0 < n; i0 += 256) {
+        const int i = i0 + (int)threadIdx.x;
+        const i64 v = i < n ? a[i] : 0;
+        i64 total;
+        const i64 ex = block_scan(v, total, s_wave);
+        if (i < n) a[i] = carry + ex;
+        carry += total;
+    }
+    __syncthreads();
+}
+
+// A workgroup per problem.  LDS: the I and C rows of the remaining reps are staged (row stride W | 1 words, so that a lane per column
+// does not hit one bank); !LDS: they are read where preprocess left them.
+// EMIT = false, the counts: the AND and the OR of the columns' I words (a stripe of columns per lane, met in LDS atomics -- AND and OR do
+// not depend on the order), the informative row (informative_segs(), :331-344: segment j is dropped when the columns j - 1, j, j + 1 hold
+// one value each and the same one; "column holds only 0" = ~OR, "only 1" = AND, the neighbours by shifts with the carries of the words
+// next door; bits behind M count as "holds both", which keeps segment M - 1, and bit 0 has no left neighbour, which keeps segment 0),
+// col_of (the membership mask of :500-502) and the problem's four totals.
+// EMIT = true, behind the scan of the totals: the informative segments; support (per informative j its columns, a wave per segment, a
+// ballot per 64 columns); the correction terms (per column its informative j with C = 1); the pairs with both ends remaining, in the
+// partition's order (a prefix sum over the workgroup per 256 pairs).  Nothing depends on the order atomics arrive in.
+template <bool LDS, bool EMIT>
+__global__ void __launch_bounds__(256) k_round(const int *list, int P, const RoundProb *probs, const unsigned *ibits, const unsigned *cbits,
+                                               const int *rids, int *col_of, const int2 *part_pairs, unsigned *inf_bits, i64 *cnt,
+                                               const i64 *scan, int *inf_seg, i64 *sup_off, int *sup_cols, i64 *corr_off, int *corr_seg,
+                                               int2 *out_pairs) {
+    extern __shared__ unsigned s_rows[];
+    __shared__ unsigned s_and[kMaxWords], s_or[kMaxWords], s_inf[kMaxWords];
+    __shared__ int s_rank[kMaxWords];
+    __shared__ i64 s_wave[4];
+    __shared__ int s_tot[kRoundCounts];
+    const int tid = threadIdx.x, lane = lane_id(), wave = tid >> 6;
+    const int p = list[blockIdx.x];
+    const RoundProb d = probs[p];
+    const int R = d.n, W = d.w, M = d.n_seg, S = W | 1;
+    const int *prids = rids + d.col0;
+    if (LDS) {
+        for (int x = tid; x < R * W; x += 256) {
+            const int c = x / W, w = x - c * W;
+            const i64 src = d.rbits_off + (i64)prids[c] * W + w;
+            s_rows[c * S + w] = ibits[src];
+            s_rows[(R + c) * S + w] = cbits[src];
+        }
+    }
+    const auto row_i = [&](int c, int w) { return LDS ? s_rows[c * S + w] : ibits[d.rbits_off + (i64)prids[c] * W + w]; };
+    const auto row_c = [&](int c, int w) { return LDS ? s_rows[(R + c) * S + w] : cbits[d.rbits_off + (i64)prids[c] * W + w]; };
+    if (!EMIT) {
+        for (int c = tid; c < R; c += 256) col_of[d.rep0 + prids[c]] = c;
+        for (int w = tid; w < W; w += 256) { s_and[w] = 0xffffffffu; s_or[w] = 0u; }
+        if (tid < kRoundCounts) s_tot[tid] = 0;
+        __syncthreads();
+        const int stripes = W >= 256 ? 1 : 256 / W;
+        for (int x = tid; x < stripes * W; x += 256) {
+            const int st = x / W, w = x - st * W;
+            unsigned a = 0xffffffffu, o = 0u;
+            for (int c = st; c < R; c += stripes) { const unsigned v = row_i(c, w); a &= v; o |= v; }
+            atomicAnd(&s_and[w], a); atomicOr(&s_or[w], o);
+        }
+        __syncthreads();
+        int n_inf = 0;
+        for (int w = tid; w < W; w += 256) {
+            const int rest = M - w * 32;                       // the row's bits in this word: all of them valid, or the low `rest`
+            const unsigned valid = rest >= 32 ? 0xffffffffu : rest <= 0 ? 0u : (1u << rest) - 1u;
+            unsigned inf = valid;
+            if (R > 0) {
+                const int wl = max(w - 1, 0), wr = min(w + 1, W - 1);                 // (clamped; the carry is dropped where there is no word)
+                const int rest_r = M - wr * 32;
+                const unsigned valid_r = rest_r >= 32 ? 0xffffffffu : rest_r <= 0 ? 0u : (1u << rest_r) - 1u;
+                const unsigned z = ~s_or[w] & valid, zl = w > 0 ? ~s_or[wl] : 0u, zr = w + 1 < W ? ~s_or[wr] & valid_r : 0u;
+                const unsigned a = s_and[w] & valid, al = w > 0 ? s_and[wl] : 0u, ar = w + 1 < W ? s_and[wr] & valid_r : 0u;
+                const unsigned u0 = z & ((z << 1) | (zl >> 31)) & ((z >> 1) | (zr << 31));
+                const unsigned u1 = a & ((a << 1) | (al >> 31)) & ((a >> 1) | (ar << 31));
+                inf = valid & ~(u0 | u1);
+            }
+            s_inf[w] = inf;
+            inf_bits[d.inf_off + w] = inf;
+            n_inf += __popc(inf);
+        }
+        __syncthreads();
+        int n_sup = 0, n_corr = 0, n_pair = 0;
+        for (int x = tid; x < R * W; x += 256) {
+            const int c = x / W, w = x - c * W;
+            n_sup += __popc(row_i(c, w) & s_inf[w]);
+            n_corr += __popc(row_c(c, w) & s_inf[w]);
+        }
+        for (i64 i = d.pair0 + tid; i < d.pair1; i += 256) {
+            const int2 pr = part_pairs[i];
+            n_pair += (col_of[d.rep0 + pr.x] >= 0 && col_of[d.rep0 + pr.y] >= 0) ? 1 : 0;
+        }
+        int v[kRoundCounts] = {n_inf, n_sup, n_corr, n_pair};
+        for (int k = 0; k < kRoundCounts; ++k) {
+            for (int s = 32; s > 0; s >>= 1) v[k] += __shfl_xor(v[k], s);
+            if (lane == 0) atomicAdd(&s_tot[k], v[k]);
+        }
+        __syncthreads();
+        if (tid < kRoundCounts) cnt[(i64)tid * (P + 1) + p] = s_tot[tid];
+        return;
+    }
+    // ---- EMIT
+    const i64 inf_base = scan[p], sup_base = scan[(i64)(P + 1) + p] - scan[(i64)(P + 1)];
+    const i64 corr_base = scan[2ll * (P + 1) + p] - scan[2ll * (P + 1)], pair_base = scan[3ll * (P + 1) + p] - scan[3ll * (P + 1)];
+    for (int w = tid; w < W; w += 256) s_inf[w] = inf_bits[d.inf_off + w];
+    __syncthreads();
+    i64 carry = 0;
+    for (int w0 = 0; w0 < W; w0 += 256) {                        // the informative segments in front of every word, and the segments themselves
+        const int w = w0 + tid;
+        unsigned m = w < W ? s_inf[w] : 0u;
+        i64 total;
+        const i64 ex = block_scan(__popc(m), total, s_wave);
+        if (w < W) s_rank[w] = (int)(carry + ex);
+        i64 x = inf_base + carry + ex;
+        while (m) { inf_seg[x++] = w * 32 + __ffs((int)m) - 1; m &= m - 1; }
+        carry += total;
+    }
+    __syncthreads();
+    const int n_inf = (int)carry;
+    i64 *my_sup = sup_off + inf_base;
+    for (int pass = 0; pass < 2; ++pass) {                        // support: the counts, their prefix sums in place, the columns
+        for (int j = wave; j < M; j += 4) {
+            const unsigned m = s_inf[j >> 5];
+            if (!((m >> (j & 31)) & 1u)) continue;
+            const int k = s_rank[j >> 5] + __popc(m & ((1u << (j & 31)) - 1u));
+            const i64 base = pass ? my_sup[k] : 0;
+            int run = 0;
+            for (int c0 = 0; c0 < R; c0 += 64) {
+                const int c = min(c0 + lane, R - 1);
+                const bool on = c0 + lane < R && ((row_i(c, j >> 5) >> (j & 31)) & 1u);
+                const u64 b = __ballot(on);
+                if (pass && on) sup_cols[base + run + __popcll(b & ((1ull << lane) - 1ull))] = c;
+                run += __popcll(b);
+            }
+            if (!pass && lane == 0) my_sup[k] = run;
+        }
+        if (!pass) block_scan_inplace(my_sup, n_inf, sup_base, s_wave);
+    }
+    i64 *my_corr = corr_off + d.col0;                            // the correction terms: the same three steps, a lane per column
+    for (int c = tid; c < R; c += 256) {
+        int n = 0;
+        for (int w = 0; w < W; ++w) n += __popc(row_c(c, w) & s_inf[w]);
+        my_corr[c] = n;
+    }
+    block_scan_inplace(my_corr, R, corr_base, s_wave);
+    for (int c = tid; c < R; c += 256) {
+        i64 x = my_corr[c];
+        for (int w = 0; w < W; ++w) {
+            unsigned m = row_c(c, w) & s_inf[w];
+            while (m) { corr_seg[x++] = w * 32 + __ffs((int)m) - 1; m &= m - 1; }
+        }
+    }
+    i64 run = pair_base;                                         // the pairs
+    for (i64 i0 = d.pair0; i0 < d.pair1; i0 += 256) {
+        const i64 i = i0 + tid;
+        const int2 pr = part_pairs[min(i, d.pair1 - 1)];
+        const int a = col_of[d.rep0 + pr.x], b = col_of[d.rep0 + pr.y];
+        const bool keep = i < d.pair1 && a >= 0 && b >= 0;
+        i64 total;
+        const i64 ex = block_scan(keep ? 1 : 0, total, s_wave);
+        if (keep) out_pairs[run + ex] = make_int2(a, b);
+        run += total;
+    }
+}
+
+// ---- gap groups (:462-497) -------------------------------------------------------------------------------------------
+// A row = (column, gap of its rep), in column order then the rep's own order: row_off per column comes from the host, which holds the
+// reps' gap counts.  A row's key = (problem, (j1 + 1) * (M + 2) + j2 + 1) (a rep without a 1 and an 'S' tail has the pseudo-gap (-1, -1)): sorted, the runs of one key are the problems' distinct (j1, j2),
+// ascending -- the groups, numbered through the batch.
+__global__ void __launch_bounds__(256) k_gap_keys(i64 n_cols, const int *col_prob, const RoundProb *probs, const int *rids, const i64 *gap_off,
+                                                  const int *gaps, const i64 *row_off, u64 *key, int *val, int *rows) {
+    for (i64 cg = (i64)blockIdx.x * blockDim.x + threadIdx.x; cg < n_cols; cg += (i64)gridDim.x * blockDim.x) {
+        const int p = col_prob[cg];
+        const RoundProb d = probs[p];
+        const i64 g0 = gap_off[d.rep0 + rids[cg]], n = gap_off[d.rep0 + rids[cg] + 1] - g0, r0 = row_off[cg];
+        for (i64 g = 0; g < n; ++g) {
+            const int j1 = gaps[3 * (g0 + g)], j2 = gaps[3 * (g0 + g) + 1];
+            key[r0 + g] = ((u64)(unsigned)p << 32) | (u64)((i64)(j1 + 1) * (d.n_seg + 2) + (j2 + 1));
+            val[r0 + g] = (int)(r0 + g);
+            rows[3 * (r0 + g)] = (int)(cg - d.col0);
+            rows[3 * (r0 + g) + 2] = gaps[3 * (g0 + g) + 2];
+        }
+    }
+}
+
+__global__ void __launch_bounds__(256) k_gap_heads(i64 n, const u64 *skey, i64 *head) {
+    for (i64 k = (i64)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += (i64)gridDim.x * blockDim.x)
+        head[k] = (k > 0 && skey[k - 1] == skey[k]) ? 0 : 1;
+}
+
+__device__ __forceinline__ int inf_bit(const unsigned *row, int j) { return (row[j >> 5] >> (j & 31)) & 1u; }
+
+// gid = the inclusive scan of head: sorted row k belongs to group gid[k] - 1.  Per sorted row: its group, local to the problem, and the
+// refusal of :467-468 (the smallest column of a problem whose gap has an uninformative endpoint; Python's j % M: -1 is M - 1, M is 0; a rep without a 1 has first = -1, so j2 = -1 occurs).
+// Per head: the group's (j1, j2), its problem and its count of informative segments strictly between.  Per problem: grp_off.
+__global__ void __launch_bounds__(256) k_gap_groups(i64 n, int P, const u64 *skey, const int *sval, const i64 *gid, const i64 *prob_row_off,
+                                                    const RoundProb *probs, const unsigned *inf_bits, int *rows, int *grp, int *grp_prob,
+                                                    i64 *grp_cnt, i64 *grp_off, int *refused) {
+    const i64 last = n > P ? n : P;
+    for (i64 k = (i64)blockIdx.x * blockDim.x + threadIdx.x; k <= last; k += (i64)gridDim.x * blockDim.x) {
+        if (k <= P) { const i64 r = prob_row_off[k]; grp_off[k] = r < n ? gid[r] - 1 : gid[n - 1]; }
+        if (k >= n) continue;
+        const int p = (int)(skey[k] >> 32);
+        const RoundProb d = probs[p];
+        const i64 kk = (i64)(skey[k] & 0xffffffffull), g = gid[k] - 1;
+        const int j1 = (int)(kk / (d.n_seg + 2)) - 1, j2 = (int)(kk % (d.n_seg + 2)) - 1;
+        const unsigned *inf = inf_bits + d.inf_off;
+        const int r = sval[k];
+        rows[3 * (i64)r + 1] = (int)(g - (gid[prob_row_off[p]] - 1));
+        if (!inf_bit(inf, j1 < 0 ? d.n_seg - 1 : j1) || !inf_bit(inf, j2 < 0 ? d.n_seg - 1 : j2 >= d.n_seg ? 0 : j2)) atomicMin(&refused[p], rows[3 * (i64)r]);
+        if (k == 0 || skey[k - 1] != skey[k]) {
+            grp[2 * g] = j1; grp[2 * g + 1] = j2; grp_prob[g] = p;
+            int n_between = 0;
+            for (int w = (j1 + 1) >> 5; w <= (j2 - 1) >> 5 && j1 + 1 <= j2 - 1; ++w) n_between += __popc(inf[w] & span_mask(j1 + 1, j2 - 1, w));
+            grp_cnt[g] = n_between;
+        }
+    }
+}
+
+// a group's informative segments strictly between j1 and j2, with their lengths (GAPI_C1, :474-481), behind the scan of the counts
+__global__ void __launch_bounds__(256) k_gap_fill(const i64 *gid, i64 n_rows, const int *grp, const int *grp_prob, const i64 *grp_seg_off,
+                                                  const RoundProb *probs, const unsigned *inf_bits, const int *seg_len, int *grp_seg, int *grp_len) {
+    const i64 n_grp = gid[n_rows - 1];
+    for (i64 g = (i64)blockIdx.x * blockDim.x + threadIdx.x; g < n_grp; g += (i64)gridDim.x * blockDim.x) {
+        const RoundProb d = probs[grp_prob[g]];
+        const unsigned *inf = inf_bits + d.inf_off;
+        const int j1 = grp[2 * g], j2 = grp[2 * g + 1];
+        i64 x = grp_seg_off[g];
+        for (int w = (j1 + 1) >> 5; w <= (j2 - 1) >> 5 && j1 + 1 <= j2 - 1; ++w) {
+            unsigned m = inf[w] & span_mask(j1 + 1, j2 - 1, w);
+            while (m) { const int j = w * 32 + __ffs((int)m) - 1; grp_seg[x] = j; grp_len[x] = seg_len[d.seg0 + j]; ++x; m &= m - 1; }
+        }
+    }
+}
+
 }  // namespace
 
 // ---- buffers and the context -------------------------------------------------------------------------------------------
@@ -1011,6 +1277,27 @@ struct fclu_ctx {
     float gkeys_ms = 0.f, gdedupe_ms = 0.f;
     fclu_groups groups = {};
     bool have_groups = false;
+    // fclu_round_setup() / fclu_round_models(): what the last fclu_partition_reads() / fclu_partition_segment() left on the device is the
+    // source (pd.ibits / pd.cbits, d_pairs); device arrays (rd), the pinned copies fclu_round_results() hands out (rh), and what the host
+    // keeps of the batch to check and lay out a round's problems
+    struct {
+        Buf<RoundProb> probs; Buf<u64> key, skey; Buf<unsigned> inf_bits; Buf<int2> pairs; Buf<char> tmp;
+        Buf<i64> gap_off, col_row_off, prob_row_off, cnt, scan, head, gid, grp_cnt, grp_seg_off, grp_off, sup_off, corr_off;
+        Buf<int> gaps, seg_len, col_of, rids, col_prob, list, val, sval, rows, grp, grp_prob, refused, inf_seg, sup_cols, corr_seg, grp_seg, grp_len;
+    } rd;
+    struct {
+        HostBuf<int64_t> scan, inf_bits_off, inf_off, sup_off, col_off, corr_off, pair_off, grp_off, grp_seg_off, row_off;
+        HostBuf<uint32_t> inf_bits; HostBuf<int2> pairs;
+        HostBuf<int32_t> refused, inf_seg, sup_cols, corr_seg, grp, grp_seg, grp_len, rows;
+    } rh;
+    std::vector<int64_t> r_rep_off, r_gap_off, r_seg_off, r_rep_part;
+    std::vector<int32_t> r_n_seg, r_part_tint, r_rep_stamp, r_part_stamp;
+    int r_epoch = 0;
+    bool round_src_ok = false, round_ready = false;
+    hipEvent_t rev[5] = {};
+    float rcount_ms = 0.f, rgaps_ms = 0.f, rfill_ms = 0.f;
+    fclu_rounds rounds = {};
+    bool have_rounds = false;
     // (the buffers free themselves behind it, on this device)
     ~fclu_ctx() {
         (void)hipSetDevice(device);
@@ -1019,6 +1306,7 @@ struct fclu_ctx {
         for (hipEvent_t e : pev) if (e) (void)hipEventDestroy(e);
         for (hipEvent_t e : qev) if (e) (void)hipEventDestroy(e);
         for (hipEvent_t e : gev) if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : rev) if (e) (void)hipEventDestroy(e);
     }
 };
 
@@ -1050,7 +1338,9 @@ int fail(fclu_ctx *c, int code, const char *fmt, ...) {
 //   FCLU_RANK=0             rank             k_compat keeps the masked sums whatever the rows' length
 //   FCLU_PRUNE_EDGES=0      prune_edges      the pass as OR of rows (k_deg1, k_prune) whatever the shapes
 //   FCLU_HASH_BITS=n        hash_mask        n < 32: the dedupe's hash cut to n bits forces collisions; 0: one bucket a tint
-struct Knobs { bool part_lds, prune_lds, rank, prune_edges; i64 prune_lds_words; unsigned hash_mask; };
+//   FCLU_ROUND_LDS=0        round_lds        no problem's rows in LDS (k_round<true, .>): all read them from device memory
+//   FCLU_ROUND_LDS_BYTES=n  round_lds_bytes  0 < n < kRoundLdsBytes: a lower limit of the LDS path, so that small problems take both ways in one batch
+struct Knobs { bool part_lds, prune_lds, rank, prune_edges, round_lds; i64 prune_lds_words, round_lds_bytes; unsigned hash_mask; };
 
 Knobs read_knobs() {
     const auto off = [](const char *name) { const char *e = getenv(name); return e && e[0] == '0'; };
@@ -1058,6 +1348,9 @@ Knobs read_knobs() {
     k.part_lds = !off("FCLU_PART_LDS"); k.prune_lds = !off("FCLU_PRUNE_LDS"); k.rank = !off("FCLU_RANK"); k.prune_edges = !off("FCLU_PRUNE_EDGES");
     const char *w = getenv("FCLU_PRUNE_LDS_WORDS");
     k.prune_lds_words = (w && atoll(w) > 0 && atoll(w) < kPruneLdsWords) ? atoll(w) : kPruneLdsWords;
+    k.round_lds = !off("FCLU_ROUND_LDS");
+    const char *rb = getenv("FCLU_ROUND_LDS_BYTES");
+    k.round_lds_bytes = (rb && atoll(rb) > 0 && atoll(rb) < kRoundLdsBytes) ? atoll(rb) : kRoundLdsBytes;
     const char *hb = getenv("FCLU_HASH_BITS");
     k.hash_mask = (hb && hb[0] >= '0' && hb[0] <= '9' && atoi(hb) < 32) ? (1u << atoi(hb)) - 1u : 0xffffffffu;
     return k;
@@ -1677,6 +1970,7 @@ int prep_nodes(fclu_ctx *c, const PrepRun &p) {
 // Rows, dedupe and the staging of the unique rows as a batch: st is what compat_run() needs.
 int preprocess_device(fclu_ctx *c, const Knobs &k, const fclu_reads *rd, int32_t prune, Staged &st, i64 &n_reps_out, bool on_device = false) {
     c->have_prep = false;
+    c->round_src_ok = c->round_ready = c->have_rounds = false;
     c->rows_ms = c->dedupe_ms = 0.f;
     PrepRun p;
     RC_TRY(prep_rows(c, k, rd, on_device, p));
@@ -1702,6 +1996,7 @@ void preprocess_times(fclu_ctx *c, i64 n_reps) {
 // offsets and decide the layout of the gathered rows.  It synchronises at its end.
 int group_device(fclu_ctx *c, const Knobs &k, const fclu_segment *in, bool gather, i64 &n_reps_out) {
     c->have_groups = false;
+    c->round_src_ok = c->round_ready = c->have_rounds = false;
     c->gkeys_ms = c->gdedupe_ms = 0.f;
     if (!in || in->n_tint <= 0) return fail(c, FCLU_ERR_ARG, "fclu_group_reads: empty batch");
     if (!in->read_off || !in->n_seg || !in->lab_off) return fail(c, FCLU_ERR_ARG, "fclu_group_reads: read_off, n_seg or lab_off is null");
@@ -1854,6 +2149,271 @@ int group_device(fclu_ctx *c, const Knobs &k, const fclu_segment *in, bool gathe
     return FCLU_OK;
 }
 
+// ---- a round's models (fclu_round_setup, fclu_round_models) ----------------------------------------------------------------
+// The I / C rows (c->pd.ibits / cbits), the pair lists (c->d_pairs) and the partitions (c->parts, pinned) of the call that has just
+// succeeded are the rounds' source: the host keeps the batch's shape.
+void round_source(fclu_ctx *c, const fclu_reads *rd) {
+    c->r_rep_off.assign(rd->rep_off, rd->rep_off + rd->n_tint + 1);
+    c->r_n_seg.assign(rd->n_seg, rd->n_seg + rd->n_tint);
+    c->round_src_ok = true;
+}
+
+int round_setup(fclu_ctx *c, const int64_t *gap_off, const int32_t *gaps, const int64_t *seg_off, const int32_t *seg_len) {
+    c->round_ready = c->have_rounds = false;
+    if (!c->round_src_ok || !c->have_parts)
+        return fail(c, FCLU_ERR_ARG, "fclu_round_setup: the context holds no fclu_partition_reads() / fclu_partition_segment() result");
+    if (!gap_off || !seg_off) return fail(c, FCLU_ERR_ARG, "fclu_round_setup: gap_off or seg_off is null");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const int T = (int)c->r_n_seg.size();
+    const i64 N = c->r_rep_off[(size_t)T];
+    if (gap_off[0] != 0 || seg_off[0] != 0) return fail(c, FCLU_ERR_ARG, "fclu_round_setup: gap_off and seg_off start at 0");
+    for (int t = 0; t < T; ++t) {
+        const int M = c->r_n_seg[(size_t)t];
+        if (seg_off[t + 1] - seg_off[t] != M)
+            return fail(c, FCLU_ERR_ARG, "tint %d: %lld segment lengths for %d segments", t, (i64)(seg_off[t + 1] - seg_off[t]), M);
+        for (i64 r = c->r_rep_off[(size_t)t]; r < c->r_rep_off[(size_t)t + 1]; ++r) {
+            if (gap_off[r + 1] < gap_off[r] || gap_off[r + 1] > 2147483647ll) return fail(c, FCLU_ERR_ARG, "fclu_round_setup: gap_off falls or is too large at rep %lld", r);
+            for (i64 g = gap_off[r]; g < gap_off[r + 1]; ++g) {
+                if (!gaps) return fail(c, FCLU_ERR_ARG, "fclu_round_setup: gaps is null");
+                const int j1 = gaps[3 * g], j2 = gaps[3 * g + 1];
+                if (M < 1 || j1 < -1 || j1 > j2 || j2 > M || j1 > M - 1)
+                    return fail(c, FCLU_ERR_ARG, "tint %d rep %lld: gap (%d, %d) outside -1 <= j1 <= j2 <= %d", t, r - c->r_rep_off[(size_t)t], j1, j2, M);
+            }
+        }
+    }
+    const i64 n_gaps = gap_off[N], n_seg_total = seg_off[T];
+    if (n_seg_total > 0 && !seg_len) return fail(c, FCLU_ERR_ARG, "fclu_round_setup: seg_len is null");
+    // rep -> partition, partition -> tint, from the partition call's pinned results
+    const fclu_parts &pp = c->parts;
+    c->r_rep_part.assign((size_t)N, -1);
+    c->r_part_tint.assign((size_t)pp.n_part, 0);
+    for (int t = 0; t < T; ++t)
+        for (i64 q = pp.tint_part_off[t]; q < pp.tint_part_off[t + 1]; ++q) {
+            c->r_part_tint[(size_t)q] = t;
+            for (i64 x = pp.part_rid_off[q]; x < pp.part_rid_off[q + 1]; ++x) c->r_rep_part[(size_t)(c->r_rep_off[(size_t)t] + pp.part_rids[x])] = q;
+        }
+    c->r_rep_stamp.assign((size_t)N, 0); c->r_part_stamp.assign((size_t)pp.n_part, 0);
+    c->r_epoch = 0;
+    c->r_gap_off.assign(gap_off, gap_off + N + 1);
+    c->r_seg_off.assign(seg_off, seg_off + T + 1);
+    auto &D = c->rd;
+    hipStream_t s = c->stream;
+    HIP_TRY(c, D.gap_off.grow((size_t)N + 1)); HIP_TRY(c, D.gaps.grow((size_t)n_gaps * 3)); HIP_TRY(c, D.seg_len.grow((size_t)n_seg_total));
+    HIP_TRY(c, D.col_of.grow((size_t)N));
+    HIP_TRY(c, hipMemcpyAsync(D.gap_off.p, gap_off, D.gap_off.bytes((size_t)N + 1), hipMemcpyHostToDevice, s));
+    if (n_gaps) HIP_TRY(c, hipMemcpyAsync(D.gaps.p, gaps, D.gaps.bytes((size_t)n_gaps * 3), hipMemcpyHostToDevice, s));
+    if (n_seg_total) HIP_TRY(c, hipMemcpyAsync(D.seg_len.p, seg_len, D.seg_len.bytes((size_t)n_seg_total), hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    c->round_ready = true;
+    return FCLU_OK;
+}
+
+// what the host derives from a round's problems
+struct RoundRun {
+    int P = 0;
+    i64 C = 0, G = 0, n_inf_bits = 0;                      // columns, gap rows, words of the informative rows
+    std::vector<RoundProb> probs;
+    std::vector<int> col_prob, tiny, small, large;          // problems by path: LDS up to kRoundTinyBytes, LDS, device memory
+    std::vector<i64> col_row_off, prob_row_off, inf_bits_off;
+    size_t tiny_lds = 0, small_lds = 0;
+};
+
+// The problems checked (every refusal names problem and column) and laid out.
+int round_stage(fclu_ctx *c, const Knobs &k, const fclu_round_batch *b, RoundRun &r) {
+    const int P = r.P = b->n_prob;
+    const fclu_parts &pp = c->parts;
+    if (b->rid_off[0] != 0) return fail(c, FCLU_ERR_ARG, "fclu_round_models: rid_off starts at 0");
+    const i64 C = r.C = b->rid_off[P];
+    if (C < 0 || C > 2147483647ll) return fail(c, FCLU_ERR_ARG, "fclu_round_models: %lld columns in one batch", C);
+    if (C > 0 && !b->rids) return fail(c, FCLU_ERR_ARG, "fclu_round_models: rids is null");
+    r.probs.assign((size_t)P, RoundProb());
+    r.col_prob.resize((size_t)C); r.col_row_off.resize((size_t)C + 1); r.prob_row_off.resize((size_t)P + 1); r.inf_bits_off.resize((size_t)P + 1);
+    const int epoch = ++c->r_epoch;
+    i64 G = 0, n_inf_bits = 0;
+    for (int p = 0; p < P; ++p) {
+        const i64 q = b->part[p], c0 = b->rid_off[p], n = b->rid_off[p + 1] - c0;
+        if (q < 0 || q >= pp.n_part) return fail(c, FCLU_ERR_ARG, "problem %d: partition %lld of %lld", p, q, (i64)pp.n_part);
+        if (n < 0 || b->rid_off[p + 1] > C) return fail(c, FCLU_ERR_ARG, "problem %d: rid_off falls", p);
+        if (c->r_part_stamp[(size_t)q] == epoch) return fail(c, FCLU_ERR_ARG, "problem %d: partition %lld is in this batch twice", p, q);
+        c->r_part_stamp[(size_t)q] = epoch;
+        const int t = c->r_part_tint[(size_t)q];
+        RoundProb &d = r.probs[(size_t)p];
+        d.col0 = c0; d.rbits_off = c->ph.rbits_off.p[t]; d.rep0 = c->r_rep_off[(size_t)t]; d.pair0 = pp.part_pair_off[q]; d.pair1 = pp.part_pair_off[q + 1];
+        d.inf_off = n_inf_bits; d.seg0 = c->r_seg_off[(size_t)t];
+        d.n = (int)n; d.n_seg = c->r_n_seg[(size_t)t]; d.w = std::max((d.n_seg + 31) / 32, 1);
+        const i64 n_t = c->r_rep_off[(size_t)t + 1] - d.rep0;
+        r.inf_bits_off[(size_t)p] = n_inf_bits; r.prob_row_off[(size_t)p] = G;
+        n_inf_bits += d.w;
+        for (i64 x = 0; x < n; ++x) {
+            const i64 rid = b->rids[c0 + x];
+            if (rid < 0 || rid >= n_t) return fail(c, FCLU_ERR_ARG, "problem %d column %lld: rep %lld of %lld", p, x, rid, n_t);
+            const size_t rep = (size_t)(d.rep0 + rid);
+            if (c->r_rep_part[rep] != q) return fail(c, FCLU_ERR_ARG, "problem %d column %lld: rep %lld is not in partition %lld", p, x, rid, q);
+            if (c->r_rep_stamp[rep] == epoch) return fail(c, FCLU_ERR_ARG, "problem %d column %lld: rep %lld is in the problem twice", p, x, rid);
+            c->r_rep_stamp[rep] = epoch;
+            r.col_prob[(size_t)(c0 + x)] = p; r.col_row_off[(size_t)(c0 + x)] = G;
+            G += c->r_gap_off[rep + 1] - c->r_gap_off[rep];
+        }
+        const size_t lds = 2 * (size_t)n * (size_t)(d.w | 1) * 4;
+        if ((i64)n * d.w > 2147483647ll) return fail(c, FCLU_ERR_UNSUPPORTED, "problem %d: %lld columns of %d words are more than one workgroup indexes", p, n, d.w);
+        if (k.round_lds && lds <= (size_t)std::min<i64>(k.round_lds_bytes, kRoundTinyBytes)) { r.tiny.push_back(p); r.tiny_lds = std::max(r.tiny_lds, lds); }
+        else if (k.round_lds && lds <= (size_t)k.round_lds_bytes) { r.small.push_back(p); r.small_lds = std::max(r.small_lds, lds); }
+        else r.large.push_back(p);
+    }
+    r.col_row_off[(size_t)C] = r.prob_row_off[(size_t)P] = G; r.inf_bits_off[(size_t)P] = n_inf_bits;
+    if (G > 2147483647ll) return fail(c, FCLU_ERR_UNSUPPORTED, "fclu_round_models: %lld gap rows in one batch", G);
+    r.G = G; r.n_inf_bits = n_inf_bits;
+    return FCLU_OK;
+}
+
+template <bool EMIT>
+void round_launch(fclu_ctx *c, const RoundRun &r) {
+    auto &D = c->rd;
+    const int nT = (int)r.tiny.size(), nS = (int)r.small.size(), nL = (int)r.large.size();
+    const auto lds_launch = [&](int n, int first, size_t lds) {
+        if (n)
+            hipLaunchKernelGGL((k_round<true, EMIT>), dim3((unsigned)n), dim3(256), lds, c->stream, D.list.p + first, r.P, D.probs.p, c->pd.ibits.p, c->pd.cbits.p,
+                               D.rids.p, D.col_of.p, c->d_pairs.p, D.inf_bits.p, D.cnt.p, D.scan.p, D.inf_seg.p, D.sup_off.p, D.sup_cols.p, D.corr_off.p, D.corr_seg.p, D.pairs.p);
+    };
+    lds_launch(nT, 0, r.tiny_lds);
+    lds_launch(nS, nT, r.small_lds);
+    if (nL)
+        hipLaunchKernelGGL((k_round<false, EMIT>), dim3((unsigned)nL), dim3(256), 0, c->stream, D.list.p + nT + nS, r.P, D.probs.p, c->pd.ibits.p, c->pd.cbits.p,
+                           D.rids.p, D.col_of.p, c->d_pairs.p, D.inf_bits.p, D.cnt.p, D.scan.p, D.inf_seg.p, D.sup_off.p, D.sup_cols.p, D.corr_off.p, D.corr_seg.p, D.pairs.p);
+}
+
+int round_device(fclu_ctx *c, const Knobs &k, const fclu_round_batch *b) {
+    c->have_rounds = false;
+    c->rcount_ms = c->rgaps_ms = c->rfill_ms = 0.f;
+    if (!c->round_ready || !c->round_src_ok || !c->have_parts)
+        return fail(c, FCLU_ERR_ARG, "fclu_round_models: no fclu_round_setup() behind the context's last partition call");
+    if (!b || b->n_prob <= 0 || !b->part || !b->rid_off) return fail(c, FCLU_ERR_ARG, "fclu_round_models: empty batch or null arrays");
+    HIP_TRY(c, hipSetDevice(c->device));
+    RoundRun r;
+    RC_TRY(round_stage(c, k, b, r));
+    auto &D = c->rd;
+    auto &H = c->rh;
+    hipStream_t s = c->stream;
+    const int P = r.P;
+    const i64 C = r.C, G = r.G;
+    const size_t P1 = (size_t)P + 1, nCnt = (size_t)kRoundCounts * P1, nC = (size_t)C, nG = (size_t)G;
+    const i64 N = c->r_rep_off.back();
+    HIP_TRY(c, D.probs.grow((size_t)P)); HIP_TRY(c, D.list.grow((size_t)P)); HIP_TRY(c, D.rids.grow(nC)); HIP_TRY(c, D.col_prob.grow(nC));
+    HIP_TRY(c, D.col_row_off.grow(nC + 1)); HIP_TRY(c, D.prob_row_off.grow(P1)); HIP_TRY(c, D.cnt.grow(nCnt)); HIP_TRY(c, D.scan.grow(nCnt));
+    HIP_TRY(c, D.inf_bits.grow((size_t)r.n_inf_bits)); HIP_TRY(c, D.refused.grow((size_t)P)); HIP_TRY(c, D.corr_off.grow(nC + 1)); HIP_TRY(c, D.grp_off.grow(P1));
+    HIP_TRY(c, D.key.grow(nG)); HIP_TRY(c, D.skey.grow(nG)); HIP_TRY(c, D.val.grow(nG)); HIP_TRY(c, D.sval.grow(nG)); HIP_TRY(c, D.rows.grow(3 * nG));
+    HIP_TRY(c, D.head.grow(nG)); HIP_TRY(c, D.gid.grow(nG)); HIP_TRY(c, D.grp.grow(2 * nG)); HIP_TRY(c, D.grp_prob.grow(nG));
+    HIP_TRY(c, D.grp_cnt.grow(nG + 1)); HIP_TRY(c, D.grp_seg_off.grow(nG + 1));
+    HIP_TRY(c, H.scan.grow(nCnt)); HIP_TRY(c, c->h_tot.grow(2));
+    const unsigned key_bits = 32u + (unsigned)bits_for(P);
+    size_t tmp_a = 0, tmp_b = 0, tmp_c = 0, tmp_d = 0;
+    HIP_TRY(c, rocprim::exclusive_scan(nullptr, tmp_a, D.cnt.p, D.scan.p, (i64)0, nCnt, rocprim::plus<i64>(), s));
+    if (G) {
+        HIP_TRY(c, rocprim::radix_sort_pairs(nullptr, tmp_b, D.key.p, D.skey.p, D.val.p, D.sval.p, nG, 0u, key_bits, s));
+        HIP_TRY(c, rocprim::inclusive_scan(nullptr, tmp_c, D.head.p, D.gid.p, nG, rocprim::plus<i64>(), s));
+        HIP_TRY(c, rocprim::exclusive_scan(nullptr, tmp_d, D.grp_cnt.p, D.grp_seg_off.p, (i64)0, nG + 1, rocprim::plus<i64>(), s));
+    }
+    const size_t tmp_bytes = std::max(std::max(tmp_a, tmp_b), std::max(tmp_c, tmp_d));
+    HIP_TRY(c, D.tmp.grow(tmp_bytes));
+    std::vector<int> list(r.tiny);
+    list.insert(list.end(), r.small.begin(), r.small.end());
+    list.insert(list.end(), r.large.begin(), r.large.end());
+    HIP_TRY(c, hipMemcpyAsync(D.probs.p, r.probs.data(), D.probs.bytes((size_t)P), hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(D.list.p, list.data(), D.list.bytes((size_t)P), hipMemcpyHostToDevice, s));
+    if (C) {
+        HIP_TRY(c, hipMemcpyAsync(D.rids.p, b->rids, D.rids.bytes(nC), hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipMemcpyAsync(D.col_prob.p, r.col_prob.data(), D.col_prob.bytes(nC), hipMemcpyHostToDevice, s));
+    }
+    HIP_TRY(c, hipMemcpyAsync(D.col_row_off.p, r.col_row_off.data(), D.col_row_off.bytes(nC + 1), hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(D.prob_row_off.p, r.prob_row_off.data(), D.prob_row_off.bytes(P1), hipMemcpyHostToDevice, s));
+    if (N) HIP_TRY(c, hipMemsetAsync(D.col_of.p, 0xff, D.col_of.bytes((size_t)N), s));
+    HIP_TRY(c, hipMemsetAsync(D.cnt.p, 0, D.cnt.bytes(nCnt), s));
+    HIP_TRY(c, hipMemsetAsync(D.refused.p, 0x7f, D.refused.bytes((size_t)P), s));
+    HIP_TRY(c, hipMemsetAsync(D.grp_off.p, 0, D.grp_off.bytes(P1), s));
+    // ---- the counts: column reduction, informative rows, totals
+    HIP_TRY(c, hipEventRecord(c->rev[0], s));
+    round_launch<false>(c, r);
+    size_t tb = tmp_bytes;
+    HIP_TRY(c, rocprim::exclusive_scan(D.tmp.p, tb, D.cnt.p, D.scan.p, (i64)0, nCnt, rocprim::plus<i64>(), s));
+    HIP_TRY(c, hipEventRecord(c->rev[1], s));
+    // ---- the gap groups
+    const int row_grid = (int)std::min<i64>((std::max<i64>(G, P) + 256) / 256, 4096);
+    if (G) {
+        hipLaunchKernelGGL(k_gap_keys, dim3((unsigned)std::min<i64>((C + 255) / 256, 4096)), dim3(256), 0, s, C, D.col_prob.p, D.probs.p, D.rids.p, D.gap_off.p,
+                           D.gaps.p, D.col_row_off.p, D.key.p, D.val.p, D.rows.p);
+        tb = tmp_bytes;
+        HIP_TRY(c, rocprim::radix_sort_pairs(D.tmp.p, tb, D.key.p, D.skey.p, D.val.p, D.sval.p, nG, 0u, key_bits, s));
+        hipLaunchKernelGGL(k_gap_heads, dim3(row_grid), dim3(256), 0, s, G, D.skey.p, D.head.p);
+        tb = tmp_bytes;
+        HIP_TRY(c, rocprim::inclusive_scan(D.tmp.p, tb, D.head.p, D.gid.p, nG, rocprim::plus<i64>(), s));
+        HIP_TRY(c, hipMemsetAsync(D.grp_cnt.p, 0, D.grp_cnt.bytes(nG + 1), s));
+        hipLaunchKernelGGL(k_gap_groups, dim3(row_grid), dim3(256), 0, s, G, P, D.skey.p, D.sval.p, D.gid.p, D.prob_row_off.p, D.probs.p, D.inf_bits.p, D.rows.p,
+                           D.grp.p, D.grp_prob.p, D.grp_cnt.p, D.grp_off.p, D.refused.p);
+        tb = tmp_bytes;
+        HIP_TRY(c, rocprim::exclusive_scan(D.tmp.p, tb, D.grp_cnt.p, D.grp_seg_off.p, (i64)0, nG + 1, rocprim::plus<i64>(), s));
+        HIP_TRY(c, hipMemcpyAsync(c->h_tot.p, D.gid.p + (G - 1), c->h_tot.bytes(1), hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipMemcpyAsync(c->h_tot.p + 1, D.grp_seg_off.p + G, c->h_tot.bytes(1), hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(c, hipEventRecord(c->rev[2], s));
+    HIP_TRY(c, hipMemcpyAsync(H.scan.p, D.scan.p, D.scan.bytes(nCnt), hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    HIP_TRY(c, hipGetLastError());
+    i64 tot[kRoundCounts];
+    for (int x = 0; x < kRoundCounts; ++x) tot[x] = H.scan.p[(size_t)x * P1 + P] - H.scan.p[(size_t)x * P1];
+    const i64 n_inf = tot[0], n_sup = tot[1], n_corr = tot[2], n_pairs = tot[3], n_grp = G ? c->h_tot.p[0] : 0, n_grp_seg = G ? c->h_tot.p[1] : 0;
+    if (n_inf < 0 || n_inf > r.n_inf_bits * 32 || n_sup < 0 || n_corr < 0 || n_pairs < 0 || n_pairs > c->parts.n_pairs || n_grp < 0 || n_grp > G || n_grp_seg < 0)
+        return fail(c, FCLU_ERR_HIP, "round totals out of range (%lld informative, %lld support, %lld corrections, %lld pairs, %lld groups)", n_inf, n_sup, n_corr, n_pairs, n_grp);
+    // ---- the fills
+    HIP_TRY(c, D.inf_seg.grow((size_t)n_inf)); HIP_TRY(c, D.sup_off.grow((size_t)n_inf + 1)); HIP_TRY(c, D.sup_cols.grow((size_t)n_sup));
+    HIP_TRY(c, D.corr_seg.grow((size_t)n_corr)); HIP_TRY(c, D.pairs.grow((size_t)n_pairs));
+    HIP_TRY(c, D.grp_seg.grow((size_t)n_grp_seg)); HIP_TRY(c, D.grp_len.grow((size_t)n_grp_seg));
+    HIP_TRY(c, hipEventRecord(c->rev[3], s));
+    round_launch<true>(c, r);
+    if (n_grp)
+        hipLaunchKernelGGL(k_gap_fill, dim3((unsigned)std::min<i64>((n_grp + 255) / 256, 4096)), dim3(256), 0, s, D.gid.p, G, D.grp.p, D.grp_prob.p, D.grp_seg_off.p,
+                           D.probs.p, D.inf_bits.p, D.seg_len.p, D.grp_seg.p, D.grp_len.p);
+    HIP_TRY(c, hipEventRecord(c->rev[4], s));
+    fclu_rounds &o = c->rounds;
+    // (the three CSR offset arrays close with their total, which the host writes: room for it before the copies are enqueued)
+    HIP_TRY(c, H.sup_off.grow((size_t)n_inf + 1)); HIP_TRY(c, H.corr_off.grow(nC + 1)); HIP_TRY(c, H.grp_seg_off.grow((size_t)n_grp + 1));
+    const int2 *h_pairs = nullptr;
+    RC_TRY(fetch(c, H.refused, D.refused.p, (size_t)P, true, o.refused));
+    RC_TRY(fetch(c, H.inf_bits, D.inf_bits.p, (size_t)r.n_inf_bits, true, o.inf_bits));
+    RC_TRY(fetch(c, H.inf_seg, D.inf_seg.p, (size_t)n_inf, true, o.inf_seg));
+    RC_TRY(fetch(c, H.sup_off, D.sup_off.p, (size_t)n_inf, true, o.sup_off));
+    RC_TRY(fetch(c, H.sup_cols, D.sup_cols.p, (size_t)n_sup, true, o.sup_cols));
+    RC_TRY(fetch(c, H.corr_off, D.corr_off.p, nC, true, o.corr_off));
+    RC_TRY(fetch(c, H.corr_seg, D.corr_seg.p, (size_t)n_corr, true, o.corr_seg));
+    RC_TRY(fetch(c, H.pairs, D.pairs.p, (size_t)n_pairs, true, h_pairs));
+    o.pairs = &h_pairs->x;
+    RC_TRY(fetch(c, H.grp_off, D.grp_off.p, P1, true, o.grp_off));
+    RC_TRY(fetch(c, H.grp, D.grp.p, 2 * (size_t)n_grp, true, o.grp));
+    RC_TRY(fetch(c, H.grp_seg_off, D.grp_seg_off.p, (size_t)n_grp, true, o.grp_seg_off));
+    RC_TRY(fetch(c, H.grp_seg, D.grp_seg.p, (size_t)n_grp_seg, true, o.grp_seg));
+    RC_TRY(fetch(c, H.grp_len, D.grp_len.p, (size_t)n_grp_seg, true, o.grp_len));
+    RC_TRY(fetch(c, H.rows, D.rows.p, 3 * nG, true, o.rows));
+    for (HostBuf<int64_t> *h : {&H.inf_bits_off, &H.inf_off, &H.col_off, &H.pair_off, &H.row_off}) HIP_TRY(c, h->grow(P1));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    HIP_TRY(c, hipGetLastError());
+    H.sup_off.p[n_inf] = n_sup; H.corr_off.p[C] = n_corr; H.grp_seg_off.p[n_grp] = n_grp_seg;
+    for (int p = 0; p <= P; ++p) {
+        H.inf_bits_off.p[p] = r.inf_bits_off[(size_t)p];
+        H.inf_off.p[p] = H.scan.p[p] - H.scan.p[0];
+        H.pair_off.p[p] = H.scan.p[3 * P1 + p] - H.scan.p[3 * P1];
+        H.col_off.p[p] = b->rid_off[p];
+        H.row_off.p[p] = r.prob_row_off[(size_t)p];
+    }
+    for (int p = 0; p < P; ++p) if (H.refused.p[p] == 0x7f7f7f7f) H.refused.p[p] = -1;
+    o.inf_bits_off = H.inf_bits_off.p; o.inf_off = H.inf_off.p; o.col_off = H.col_off.p; o.pair_off = H.pair_off.p; o.row_off = H.row_off.p;
+    o.n_prob = P; o.n_cols = C; o.n_inf = n_inf; o.n_sup = n_sup; o.n_corr = n_corr; o.n_pairs = n_pairs; o.n_grp = n_grp; o.n_grp_seg = n_grp_seg;
+    o.n_gap_rows = G;
+    (void)hipEventElapsedTime(&c->rcount_ms, c->rev[0], c->rev[1]);
+    (void)hipEventElapsedTime(&c->rgaps_ms, c->rev[1], c->rev[2]);
+    (void)hipEventElapsedTime(&c->rfill_ms, c->rev[3], c->rev[4]);
+    c->have_rounds = true;
+    return FCLU_OK;
+}
+
 }  // namespace
 
 // ---- the C ABI ------------------------------------------------------------------------------------------------------------
@@ -1878,11 +2438,14 @@ int fclu_create(int device, fclu_ctx **out) {
     for (int i = 0; e == hipSuccess && i < 6; ++i) e = hipEventCreate(&c->pev[i]);
     for (int i = 0; e == hipSuccess && i < 6; ++i) e = hipEventCreate(&c->qev[i]);
     for (int i = 0; e == hipSuccess && i < 5; ++i) e = hipEventCreate(&c->gev[i]);
+    for (int i = 0; e == hipSuccess && i < 5; ++i) e = hipEventCreate(&c->rev[i]);
     const struct { const void *kernel; int lds; } dyn[] = {                // the most dynamic LDS a launch asks for
         {reinterpret_cast<const void *>(k_cc_lds), 80 * 1024},
         {reinterpret_cast<const void *>(k_compat<false>), 2 * kTile * (kMaxWords | 1) * 4},
         {reinterpret_cast<const void *>(k_compat<true>), 2 * kTile * (kRankWords | 1) * 6},
-        {reinterpret_cast<const void *>(k_prune_lds), 150 * 1024}};
+        {reinterpret_cast<const void *>(k_prune_lds), 150 * 1024},
+        {reinterpret_cast<const void *>(k_round<true, false>), kRoundLdsBytes},
+        {reinterpret_cast<const void *>(k_round<true, true>), kRoundLdsBytes}};
     for (const auto &d : dyn) if (e == hipSuccess) e = hipFuncSetAttribute(d.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, d.lds);
     if (e != hipSuccess) {
         fail(nullptr, FCLU_ERR_HIP, "context creation failed: %s", hipGetErrorString(e));
@@ -1907,6 +2470,7 @@ int fclu_last_timing(fclu_ctx *c, float *compat_ms, float *prune_ms) { return c 
 int fclu_partition(fclu_ctx *c, const fclu_batch *b, const int64_t *mem_off, const int32_t *mem, int32_t maximum_ilp_size) {
     if (!c || !b) return FCLU_ERR_ARG;
     c->have_parts = false;
+    c->round_src_ok = c->round_ready = c->have_rounds = false;
     if (b->n_tint <= 0) return fail(c, FCLU_ERR_ARG, "fclu_partition: empty batch");
     RC_TRY(check_members(c, b->row_off[b->n_tint], mem_off, mem, maximum_ilp_size));
     RC_TRY(compat_device(c, read_knobs(), b, 1, nullptr, nullptr));
@@ -1917,6 +2481,7 @@ int fclu_partition_adj(fclu_ctx *c, int32_t n_tint, const int64_t *row_off, cons
                        const int64_t *mem_off, const int32_t *mem, int32_t maximum_ilp_size) {
     if (!c || !row_off || !adj_off) return FCLU_ERR_ARG;
     c->have_parts = false;
+    c->round_src_ok = c->round_ready = c->have_rounds = false;
     if (n_tint <= 0) return fail(c, FCLU_ERR_ARG, "fclu_partition_adj: empty batch");
     HIP_TRY(c, hipSetDevice(c->device));
     const Knobs k = read_knobs();
@@ -1985,7 +2550,9 @@ int fclu_partition_reads(fclu_ctx *c, const fclu_reads *reads, int32_t maximum_i
     else HIP_TRY(c, hipStreamSynchronize(c->stream));
     preprocess_times(c, n_reps);
     c->have_prep = true;
-    return partition_device(c, reads->n_tint, st.R, nullptr, nullptr, n_reps, maximum_ilp_size);
+    RC_TRY(partition_device(c, reads->n_tint, st.R, nullptr, nullptr, n_reps, maximum_ilp_size));
+    round_source(c, reads);
+    return FCLU_OK;
 }
 
 int fclu_preprocess_results(fclu_ctx *c, fclu_prep *out) {
@@ -2025,6 +2592,7 @@ int fclu_partition_segment(fclu_ctx *c, const fclu_segment *in, int32_t maximum_
         return partition_device(c, in->n_tint, st.R, nullptr, nullptr, n_reps, maximum_ilp_size);
     }();
     if (rc != FCLU_OK) c->have_groups = c->have_prep = false;
+    else round_source(c, &rd);
     return rc;
 }
 
@@ -2036,6 +2604,25 @@ int fclu_group_results(fclu_ctx *c, fclu_groups *out) {
 }
 
 int fclu_group_timing(fclu_ctx *c, float *keys_ms, float *dedupe_ms) { return c ? two_times(keys_ms, c->gkeys_ms, dedupe_ms, c->gdedupe_ms) : FCLU_ERR_ARG; }
+
+int fclu_round_setup(fclu_ctx *c, const int64_t *gap_off, const int32_t *gaps, const int64_t *seg_off, const int32_t *seg_len) {
+    return c ? round_setup(c, gap_off, gaps, seg_off, seg_len) : FCLU_ERR_ARG;
+}
+
+int fclu_round_models(fclu_ctx *c, const fclu_round_batch *b) { return c ? round_device(c, read_knobs(), b) : FCLU_ERR_ARG; }
+
+int fclu_round_results(fclu_ctx *c, fclu_rounds *out) {
+    if (!c || !out) return FCLU_ERR_ARG;
+    if (!c->have_rounds) return fail(c, FCLU_ERR_ARG, "fclu_round_results: no result (the last fclu_round_models call failed or none was made)");
+    *out = c->rounds;
+    return FCLU_OK;
+}
+
+int fclu_round_timing(fclu_ctx *c, float *count_ms, float *gaps_ms, float *fill_ms) {
+    if (!c) return FCLU_ERR_ARG;
+    if (fill_ms) *fill_ms = c->rfill_ms;
+    return two_times(count_ms, c->rcount_ms, gaps_ms, c->rgaps_ms);
+}
 
 }  // extern "C"
 

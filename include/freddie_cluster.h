@@ -15,7 +15,8 @@
  * fclu_group_reads() / fclu_partition_segment() take ALL reads of the tints as the native segment_*.tsv reader leaves them
  * (include/freddie_host.h, fhost_read_segment: label rows, key token streams, tail categories) and group them into reps
  * (read_segment()'s read_reps, :154-164) on the device.  garbage_cost (from the members' counts) and the gaps dicts are host code.
- * The ILP itself (run_ilp, Gurobi) is out of scope.
+ * The ILP's solve is not here; what run_ilp() builds its model from is: fclu_round_models() (at the end of this header) gives round r of
+ * many partitions as flat arrays, from the rows and pair lists the calls above left on the device.
  *
  * Data layout (caller-owned host arrays, copied by the call):
  *   tint t owns the unique reads row_off[t] .. row_off[t+1]  (N_t of them; "unique" = py/freddie_cluster.py:207-215)
@@ -202,6 +203,62 @@ int fclu_group_results(fclu_ctx *c, fclu_groups *out);
  * fclu_partition_segment() the gather of the reps' rows and tails into the preprocess stage's device arrays (fclu_group_reads()
  * does not gather, and leaves those arrays alone). */
 int fclu_group_timing(fclu_ctx *c, float *keys_ms, float *dedupe_ms);
+
+/* ---- a round's ILP models as arrays: informative_segs() (:331-344) and what run_ilp() builds from (:397-535), K = 2 ----
+ * The source is what the context's last fclu_partition_reads() / fclu_partition_segment() left on the device (the reps' I and C rows,
+ * the partitions' pair lists); a call that overwrites them in between (fclu_preprocess, fclu_partition, fclu_partition_adj,
+ * fclu_group_reads) ends that, and fclu_round_setup() then refuses; fclu_compat_graph() leaves them alone.
+ * fclu_round_setup(), once per batch of tints: rep r of the batch (rep_off[t] + i) has the gaps gaps[3 * gap_off[r] .. 3 * gap_off[r + 1]),
+ * triples (j1, j2, l) in the order of the rep's first read's gaps dict as preprocess_ilp() leaves it, the pseudo-gaps (-1, first) /
+ * (last, M) of :299 / :303 included (-1 <= j1 <= j2 <= M_t, j1 < M_t, M_t >= 1: FCLU_ERR_ARG otherwise; a rep without a 1 has first = -1); segment j of tint t is seg_len[seg_off[t] + j]
+ * long.  Caller-owned host arrays, copied by the call. */
+int fclu_round_setup(fclu_ctx *c, const int64_t *gap_off, const int32_t *gaps, const int64_t *seg_off, const int32_t *seg_len);
+
+/* A batch of problems: problem p is partition part[p] (numbered through the batch, as in fclu_parts) with the remaining reps
+ * rids[rid_off[p] .. rid_off[p + 1]) (local to the tint) in the caller's order; "column" = a rep's position in that list.
+ * FCLU_ERR_ARG, naming problem and column: a partition twice in the batch, a rep outside its tint, outside the partition or twice in
+ * the problem.  The context stays usable. */
+typedef struct fclu_round_batch {
+    int32_t n_prob;
+    const int64_t *part;       /* n_prob */
+    const int64_t *rid_off;    /* n_prob + 1 */
+    const int32_t *rids;
+} fclu_round_batch;
+
+int fclu_round_models(fclu_ctx *c, const fclu_round_batch *b);
+
+/* Every order is fixed.  Integers only: (1 +- epsilon), the offset and MAX_ISOFORM_LG are the host's. */
+typedef struct fclu_rounds {
+    int32_t n_prob;
+    int64_t n_cols, n_inf, n_sup, n_corr, n_pairs, n_grp, n_grp_seg, n_gap_rows;
+    const int32_t *refused;        /* n_prob: -1, or the smallest column with a gap (j1, j2) whose informative[j1 % M] or informative[j2 % M]
+                                      is false -- the reference's asserts :467-468; the arrays of such a problem are not a model */
+    const int64_t *inf_bits_off;   /* n_prob + 1, uint32 words: problem p's informative row, W_t words, bit j = informative[j] */
+    const uint32_t *inf_bits;
+    const int64_t *inf_off;        /* n_prob + 1: problem p's informative segments inf_seg[inf_off[p] .. inf_off[p + 1]), ascending */
+    const int32_t *inf_seg;        /* n_inf */
+    const int64_t *sup_off;        /* n_inf + 1: beside inf_seg; the columns with I = 1 at that segment, ascending */
+    const int32_t *sup_cols;       /* n_sup */
+    const int64_t *col_off;        /* n_prob + 1: = rid_off */
+    const int64_t *corr_off;       /* n_cols + 1: per column the informative j with C = 1, ascending (OBJ[i][j][1], :522-535) */
+    const int32_t *corr_seg;       /* n_corr */
+    const int64_t *pair_off;       /* n_prob + 1, in pairs */
+    const int32_t *pairs;          /* 2 * n_pairs: the partition's pairs with both ends remaining, as columns, in the partition's order */
+    const int64_t *grp_off;        /* n_prob + 1: the problem's gap groups, the distinct (j1, j2) of its columns' gaps, ascending */
+    const int32_t *grp;            /* 2 * n_grp: j1, j2 */
+    const int64_t *grp_seg_off;    /* n_grp + 1: the group's informative segments strictly between j1 and j2, ascending (GAPI_C1) */
+    const int32_t *grp_seg, *grp_len;   /* n_grp_seg: segment, its length */
+    const int64_t *row_off;        /* n_prob + 1: the problem's (column, gap) rows, in column order then the rep's own gap order */
+    const int32_t *rows;           /* 3 * n_gap_rows: column, group (local to the problem), l (GAPR_C1 / GAPR_C2) */
+} fclu_rounds;
+
+/* Result of the last successful fclu_round_models(): pointers into pinned host buffers the context owns, valid until the context's
+ * next call.  The partition and preprocess results stay valid behind a round call. */
+int fclu_round_results(fclu_ctx *c, fclu_rounds *out);
+
+/* Kernel time of the last fclu_round_models() from HIP events (ms): column reduction, informative rows and counts with their scan; the
+ * gap groups (keys, sort, groups); the fills. */
+int fclu_round_timing(fclu_ctx *c, float *count_ms, float *gaps_ms, float *fill_ms);
 
 #ifdef __cplusplus
 }

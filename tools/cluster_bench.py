@@ -12,6 +12,10 @@ synthetic preprocessed tints through include/freddie_cluster.h.
     python tools/cluster_bench.py --files [--workload many|big] [--steps K] [--baseline-steps K] [--threads N]
                        (segment_*.tsv files in: the native reader, the rep grouping and the whole cluster_files_batch, against
                         read_segment + pack_labels + Context.partition_labels on the same files)
+    python tools/cluster_bench.py --rounds [--workload many|big] [--steps K] [--host-sample N] [--solve-budget S] [--out FILE]
+                       (the first round of every partition: Context.round_models against the plain-Python build of the same arrays as
+                        the reference does it, the kernels' event times, and -- apart -- what HiGHS takes on the same round; the
+                        result also goes to profiles/cluster_rounds.txt)
 
 One JSON line: read pairs tested per second of the CALL (packed host arrays in -> pruned adjacency in host memory: copies,
 kernels and the pruning loop's host round trips all inside), the kernel times as detail, and the bound of the compatibility
@@ -309,6 +313,107 @@ def run_files(workload="many", steps=5, baseline_steps=1, maximum_ilp_size=1000,
     }
 
 
+def python_round(tint, remaining_rids, incomp_rids):
+    """The arrays of one problem in plain Python, as the reference gets at them inside run_ilp(): informative_segs() (:331-344, with its
+    early break), the transposes the model loops walk (:429-439, :519-535), the pair filter with `in` on the LIST remaining_rids
+    (:500-502), the gap keys and their segments (:462-481)."""
+    M = len(tint["segs"])
+    I, C = tint["ilp_data"]["I"], tint["ilp_data"]["C"]
+    seg_content = [set() for _ in range(M)]
+    informative = [True for _ in range(M)]
+    for j in range(M):
+        for i in remaining_rids:
+            seg_content[j].add(I[i][j])
+            if seg_content[j] == {0, 1}:
+                break
+    for j in range(1, M - 1):
+        if len(seg_content[j]) == 1 and (seg_content[j - 1] == seg_content[j] == seg_content[j + 1]):
+            informative[j] = False
+    support = [[c for c, i in enumerate(remaining_rids) if I[i][j] == 1] for j in range(M) if informative[j]]
+    corrections = [[j for j in range(M) if informative[j] and C[i][j] > 0] for i in remaining_rids]
+    pairs = [(i1, i2) for (i1, i2) in incomp_rids if i1 in remaining_rids and i2 in remaining_rids]
+    groups = dict()
+    for i in remaining_rids:
+        for (j1, j2), l in tint["reads"][tint["read_reps"][i][0]]["gaps"].items():
+            if (j1, j2) not in groups:
+                groups[(j1, j2)] = [(j, tint["segs"][j][2]) for j in range(j1 + 1, j2) if informative[j]]
+    return informative, support, corrections, pairs, groups
+
+
+def run_rounds(workload="many", steps=5, host_sample=4, solve_budget=120.0, maximum_ilp_size=1000, threads=16):
+    """The workload's segment_*.tsv files staged as the stage does (cluster.stage_files), then the FIRST round, every partition active:
+      device    Context.round_models on all problems (medians over `steps` after a warm-up; fclu_round_timing's kernel split), and on
+                the problems of the first `host_sample` tints alone;
+      baseline  python_round() on those same `host_sample` tints' problems (the pair filter is quadratic: a sample, not the batch);
+      solve     apart from both: cluster_solve.solve_round (HiGHS) on the sample's problems, smallest first, until `solve_budget`
+                seconds are spent -- the model build is not the solve."""
+    import tempfile
+    from freddie_amd import cluster, cluster_solve
+    with tempfile.TemporaryDirectory() as d:
+        paths, n_reads = write_segment_files(workload, d)
+        ctx = cluster_prep.Context(0)
+        settings = cluster.ilp_settings(max_ilp=maximum_ilp_size)
+        t0 = time.perf_counter()
+        tints, part0, _ = cluster.stage_files(paths, settings, ctx, threads)
+        stage_s = time.perf_counter() - t0
+    problems = [(t, q, list(rids)) for t, tint in enumerate(tints) for q, (rids, _) in enumerate(tint["partitions"])]
+    sample = [p for p in problems if p[0] < host_sample]
+    call = lambda ps: ctx.round_models([part0[t] + q for t, q, _ in ps], [rem for _, _, rem in ps])
+    arr = call(problems)                                                          # warm-up
+    all_s, kern, sample_s = [], [], []
+    for _ in range(steps):
+        t0 = time.perf_counter(); arr = call(problems); all_s.append(time.perf_counter() - t0)
+        kern.append(ctx.round_timing())
+        t0 = time.perf_counter(); sarr = call(sample); sample_s.append(time.perf_counter() - t0)
+    t0 = time.perf_counter()
+    py = [python_round(tints[t], rem, tints[t]["partitions"][q][1]) for t, q, rem in sample]
+    python_s = time.perf_counter() - t0
+    same = True
+    for p, (informative, support, corrections, pairs, groups) in enumerate(py):
+        m = cluster_prep.round_model(sarr, p)
+        if m is None:                                                             # (a problem the reference asserts on, :467-468: no model)
+            continue
+        col = {rid: c for c, rid in enumerate(sample[p][2])}
+        same = same and m["inf_seg"] == [j for j, v in enumerate(informative) if v] and m["support"] == support and \
+            m["corrections"] == corrections and m["pairs"] == [(col[a], col[b]) for a, b in pairs] and m["groups"] == sorted(groups) and \
+            m["group_segs"] == [groups[k] for k in sorted(groups)]
+    solved, spent, statuses = [], 0.0, {}
+    order = sorted(range(len(sample)), key=lambda p: len(sample[p][2]))
+    for p in order:
+        if spent >= solve_budget:
+            break
+        t, q, rem = sample[p]
+        model = cluster_prep.round_model(sarr, p)
+        if model is None:
+            continue
+        costs = cluster.garbage_costs(tints[t], "constant")
+        model["garbage"] = [costs[i] for i in rem]; model["max_lg"] = sum(s[2] for s in tints[t]["segs"])
+        t0 = time.perf_counter()
+        status = cluster_solve.solve_round(model, settings)[0]
+        dt = time.perf_counter() - t0
+        spent += dt
+        solved.append((len(rem), dt)); statuses[status] = statuses.get(status, 0) + 1
+        print("solved %d reps in %.2f s: %s" % (len(rem), dt, status), file=sys.stderr, flush=True)
+    ctx.close()
+    med = lambda xs: float(np.median(xs)) * 1e3
+    return {
+        "metric": "first round of every partition: Context.round_models against the plain-Python build of the same arrays", "unit": "ms",
+        "data": "synthetic",
+        "config": {"workload": "cluster-" + workload, **WORKLOADS[workload], "reads": n_reads, "reps": sum(len(t["read_reps"]) for t in tints),
+                   "problems": len(problems), "columns": int(arr["n_cols"]), "pairs_kept": int(arr["n_pairs"]), "support_entries": int(arr["n_sup"]),
+                   "correction_terms": int(arr["n_corr"]), "gap_rows": int(arr["n_gap_rows"]), "gap_groups": int(arr["n_grp"]),
+                   "refused_problems": int((arr["refused"] >= 0).sum()), "maximum_ilp_size": maximum_ilp_size, "steps": steps,
+                   "host_sample_tints": host_sample, "sample_problems": len(sample), "sample_refused": int((sarr["refused"] >= 0).sum()), "sample_columns": int(sarr["n_cols"])},
+        "stage_files_s": stage_s,
+        "round_models_call_ms": med(all_s), "kernel_ms": {k: float(np.median([x[k] for x in kern])) for k in kern[0]},
+        "sample_round_models_call_ms": med(sample_s), "sample_python_ms": python_s * 1e3, "identical_results": bool(same),
+        "sample_python_over_device": python_s / max(float(np.median(sample_s)), 1e-9),
+        "highs": {"problems_solved": len(solved), "of_sample_problems": len(sample), "seconds": spent, "statuses": statuses,
+                  "largest_solved_reps": max([n for n, _ in solved] or [0]), "slowest_s": max([x for _, x in solved] or [0.0])},
+        "spread_ms": {"round_models_call": [min(all_s) * 1e3, max(all_s) * 1e3]},
+    }
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workload", default="many", choices=sorted(WORKLOADS))
@@ -319,8 +424,18 @@ def main():
     ap.add_argument("--files", action="store_true", help="measure the native segment TSV reader + Context.partition_segment against read_segment + partition_labels")
     ap.add_argument("--baseline-steps", type=int, default=1, help="--files: runs of the Python baseline (it takes seconds a run)")
     ap.add_argument("--threads", type=int, default=16, help="--files: threads of the native reader")
+    ap.add_argument("--rounds", action="store_true", help="measure Context.round_models on the first round against the plain-Python build; HiGHS apart")
+    ap.add_argument("--solve-budget", type=float, default=120.0, help="--rounds: seconds of HiGHS solves on the sample's problems")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "cluster_rounds.txt"), help="--rounds: where the result is written too")
     args = ap.parse_args()
-    if args.files:
+    if args.rounds:
+        res = run_rounds(args.workload, args.steps, host_sample=min(args.host_sample, 4) if args.host_sample == 20 else args.host_sample,
+                         solve_budget=args.solve_budget, threads=args.threads)
+        with open(args.out, "w") as f:
+            f.write("tools/cluster_bench.py --rounds --workload %s --steps %d\n" % (args.workload, args.steps))
+            f.write(json.dumps(res, indent=1) + "\n")
+        print(json.dumps(res))
+    elif args.files:
         print(json.dumps(run_files(args.workload, args.steps, args.baseline_steps, threads=args.threads)))
     elif args.front:
         print(json.dumps(run_front(args.workload, args.steps)))
