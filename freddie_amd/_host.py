@@ -13,6 +13,28 @@ class HostError(RuntimeError):
     pass
 
 
+class _Reads(ctypes.Structure):
+    """fhost_reads: fseg_reads' fields (what _lib.Context.annotate passes on by reference), then the read ids."""
+    _fields_ = [("n_read", ctypes.c_int64)] + [(k, ctypes.c_void_p) for k in (
+        "read_part", "read_rep", "strand", "seq_len", "seq_off", "read_q_off", "qs", "qe", "cig_off", "cig_op", "cig_len",
+        "seq_classes", "read_id")]
+
+
+class _Names(ctypes.Structure):
+    _fields_ = [("n_part", ctypes.c_int32), ("n_read", ctypes.c_int64)] + [(k, ctypes.c_void_p) for k in (
+        "part_id", "part_chr", "part_chr_len", "name", "name_len", "chr", "chr_len")]
+
+
+class _Annot(ctypes.Structure):
+    """fhost_annot = fseg_annot."""
+    _fields_ = [("n_read", ctypes.c_int64)] + [(k, ctypes.c_void_p) for k in (
+        "gap_off", "gaps", "clip_off", "clips", "poly_off", "polys", "tail", "tok_off", "tok")]
+
+
+ANNOT_DTYPES = dict(gap_off=np.int64, gaps=np.int32, clip_off=np.int64, clips=np.int32, poly_off=np.int64, polys=np.int32,
+                    tail=np.uint8, tok_off=np.int64, tok=np.uint32)
+
+
 def load():
     global _lib
     if _lib is not None:
@@ -47,6 +69,12 @@ def load():
     for name in ("fhost_write", "fhost_write_packed"):
         getattr(L, name).restype = ctypes.c_int32
         getattr(L, name).argtypes = [vp, vp, vp, vp, vp, cpp, ctypes.c_int32]
+    L.fhost_write_annotated.restype = ctypes.c_int32
+    L.fhost_write_annotated.argtypes = [vp, vp, vp, vp, vp, ctypes.POINTER(_Annot), cpp, ctypes.c_int32]
+    L.fhost_read_arrays.restype = ctypes.c_int32
+    L.fhost_read_arrays.argtypes = [vp, ctypes.c_int32, ctypes.POINTER(_Reads)]
+    L.fhost_read_names.restype = ctypes.c_int32
+    L.fhost_read_names.argtypes = [vp, ctypes.POINTER(_Names)]
     L.fhost_discover.restype = vp
     L.fhost_discover.argtypes = [ctypes.c_char_p, ctypes.c_int32]
     L.fhost_listing_free.restype = None
@@ -164,6 +192,50 @@ class HostBatch:
              np.ascontiguousarray(label_off, np.int64), np.ascontiguousarray(labels, np.uint8)]
         rc = (self._L.fhost_write_packed if packed else self._L.fhost_write)(self._h, a[0].ctypes.data, a[1].ctypes.data, a[2].ctypes.data,
                                  a[3].ctypes.data if a[3].size else None, _c_strings(out_paths), int(n_threads))
+        if rc != 0:
+            raise HostError(self._L.fhost_error(self._h).decode())
+
+    def read_arrays(self, n_threads=1):
+        """The per-read arrays in fseg_reads' layout (include/freddie_seg.h) as numpy views valid until close(), plus ``read_id``:
+        what Context.annotate() takes.  Partitions in batch order, a partition's reads in file order."""
+        s = _Reads()
+        if self._L.fhost_read_arrays(self._h, int(n_threads), ctypes.byref(s)) != 0:
+            raise HostError(self._L.fhost_error(self._h).decode())
+        n = int(s.n_read)
+        seq_off = _view(s.seq_off, n + 1, np.int64)
+        read_q_off = _view(s.read_q_off, n + 1, np.int64)
+        nq = int(read_q_off[-1]) if n else 0
+        cig_off = _view(s.cig_off, nq + 1, np.int64)
+        nc = int(cig_off[-1]) if nq else 0
+        return dict(read_part=_view(s.read_part, n, np.int32), read_rep=_view(s.read_rep, n, np.int32), strand=_view(s.strand, n, np.uint8),
+                    seq_len=_view(s.seq_len, n, np.int32), seq_off=seq_off, read_q_off=read_q_off, qs=_view(s.qs, nq, np.int32),
+                    qe=_view(s.qe, nq, np.int32), cig_off=cig_off, cig_op=_view(s.cig_op, nc, np.uint8), cig_len=_view(s.cig_len, nc, np.int32),
+                    seq_classes=_view(s.seq_classes, (int(seq_off[-1]) + 15) // 16 if n else 0, np.uint32), read_id=_view(s.read_id, n, np.int64))
+
+    def names(self):
+        """(tint ids int64[n_part], tint contigs, read names, read contigs) of the batch, the reads in read_arrays()' order."""
+        s = _Names()
+        if self._L.fhost_read_names(self._h, ctypes.byref(s)) != 0:
+            raise HostError(self._L.fhost_error(self._h).decode())
+        at = ctypes.string_at
+
+        def strings(ptrs, lens, n):
+            return [at(p, m).decode() for p, m in zip(_view(ptrs, n, np.uint64).tolist(), _view(lens, n, np.int32).tolist())]
+        return (_view(s.part_id, s.n_part, np.int64).copy(), strings(s.part_chr, s.part_chr_len, s.n_part),
+                strings(s.name, s.name_len, s.n_read), strings(s.chr, s.chr_len, s.n_read))
+
+    def write_annotated(self, part_final_off, final_pos, label_off, labels2, annotation, out_paths, n_threads=1):
+        """write(..., packed=True) with the annotation given (a dict of fseg_annot's arrays: Context.annotate()) instead of computed."""
+        a = [np.ascontiguousarray(part_final_off, np.int64), np.ascontiguousarray(final_pos, np.int32),
+             np.ascontiguousarray(label_off, np.int64), np.ascontiguousarray(labels2, np.uint8)]
+        keep = {k: np.ascontiguousarray(annotation[k], dt) for k, dt in ANNOT_DTYPES.items()}
+        n = len(keep["gap_off"]) - 1
+        if any(len(keep[k]) != n + 1 for k in ("clip_off", "poly_off")) or keep["gaps"].size < 3 * int(keep["gap_off"][-1]) \
+                or keep["clips"].size < 2 * int(keep["clip_off"][-1]) or keep["polys"].size < 3 * int(keep["poly_off"][-1]):
+            raise HostError("write_annotated: array lengths do not match the offsets")
+        s = _Annot(n, *[keep[k].ctypes.data if keep[k].size else None for k, _ in _Annot._fields_[1:]])
+        rc = self._L.fhost_write_annotated(self._h, a[0].ctypes.data, a[1].ctypes.data, a[2].ctypes.data,
+                                           a[3].ctypes.data if a[3].size else None, ctypes.byref(s), _c_strings(out_paths), int(n_threads))
         if rc != 0:
             raise HostError(self._L.fhost_error(self._h).decode())
 

@@ -50,7 +50,21 @@ class _Sizes(ctypes.Structure):
                 ("max_problem_reads", ctypes.c_int64)]
 
 
-EXPORTS = ["fseg_abi_version", "fseg_source_hash", "fseg_results", "fseg_results_packed", "fseg_create", "fseg_destroy", "fseg_last_error", "fseg_set_params", "fseg_upload",
+class _Reads(ctypes.Structure):
+    _fields_ = [("n_read", ctypes.c_int64)] + [(k, ctypes.c_void_p) for k in (
+        "read_part", "read_rep", "strand", "seq_len", "seq_off", "read_q_off", "qs", "qe", "cig_off", "cig_op", "cig_len", "seq_classes")]
+
+
+READS_DTYPES = dict(read_part=np.int32, read_rep=np.int32, strand=np.uint8, seq_len=np.int32, seq_off=np.int64, read_q_off=np.int64,
+                    qs=np.int32, qe=np.int32, cig_off=np.int64, cig_op=np.uint8, cig_len=np.int32, seq_classes=np.uint32)
+
+
+class _Annot(ctypes.Structure):
+    _fields_ = [("n_read", ctypes.c_int64)] + [(k, ctypes.c_void_p) for k in (
+        "gap_off", "gaps", "clip_off", "clips", "poly_off", "polys", "tail", "tok_off", "tok")]
+
+
+EXPORTS = ["fseg_annotate", "fseg_annotation", "fseg_abi_version", "fseg_source_hash", "fseg_results", "fseg_results_packed", "fseg_create", "fseg_destroy", "fseg_last_error", "fseg_set_params", "fseg_upload",
            "fseg_run", "fseg_sync", "fseg_get_sizes", "fseg_download", "fseg_tap", "fseg_set_profiling",
            "fseg_n_stages", "fseg_stage_name", "fseg_stage_ms", "fseg_scoring_algorithmic_bytes"]
 
@@ -103,6 +117,10 @@ def load():
     L.fseg_results.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp)]
     L.fseg_results_packed.restype = ctypes.c_int
     L.fseg_results_packed.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp)]
+    L.fseg_annotate.restype = ctypes.c_int32
+    L.fseg_annotate.argtypes = [vp, ctypes.POINTER(_Reads), vp, vp, vp, vp]
+    L.fseg_annotation.restype = ctypes.c_int32
+    L.fseg_annotation.argtypes = [vp, ctypes.POINTER(_Annot)]
     L.fseg_source_hash.restype = ctypes.c_char_p
     L.fseg_tap.restype = ctypes.c_int
     L.fseg_tap.argtypes = [vp, ctypes.c_int, vp, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]
@@ -221,6 +239,44 @@ class Context:
             return np.frombuffer(buf, dtype=dtype)
         return (view(p[0], self.n_part + 1, np.int64), view(p[1], sz["n_final"], np.int32),
                 view(p[2], self.n_part + 1, np.int64), view(p[3], (sz["label_bytes"] + 3) // 4 if packed else sz["label_bytes"], np.uint8))
+
+    def annotate(self, reads, labels=None):
+        """Per-read unaligned gaps, clips and poly tails on the device (fseg_annotate).  ``reads``: the arrays of fseg_reads by name
+        (HostBatch.read_arrays()).  ``labels``: None -- the context's last run -- or (part_final_off, final_pos, label_off, labels2)
+        in results(packed=True)'s layout, annotated instead.  Returns fseg_annot's arrays by name: numpy views of the context's
+        pinned buffers, valid until the next annotate() on this context."""
+        a = {k: np.ascontiguousarray(reads[k], dt) for k, dt in READS_DTYPES.items()}
+        n = len(a["read_part"])
+        if any(len(a[k]) != n for k in ("read_rep", "strand", "seq_len")) or len(a["seq_off"]) != n + 1 or len(a["read_q_off"]) != n + 1:
+            raise SegError("annotate: per-read arrays of different lengths")
+        nq = len(a["qs"])
+        if len(a["qe"]) != nq or len(a["cig_off"]) != nq + 1 or (n and int(a["read_q_off"].max()) > nq) or len(a["cig_op"]) != len(a["cig_len"]) \
+                or (nq and int(a["cig_off"].max()) > len(a["cig_len"])) or (n and (int(a["seq_off"].max()) + 15) // 16 > len(a["seq_classes"])):
+            raise SegError("annotate: array lengths do not match the offsets")
+        s = _Reads(n, *[a[k].ctypes.data if a[k].size else None for k, _ in _Reads._fields_[1:]])
+        extra = [None] * 4
+        if labels is not None:
+            pfo, fp, lo, l2 = (np.ascontiguousarray(labels[0], np.int64), np.ascontiguousarray(labels[1], np.int32),
+                               np.ascontiguousarray(labels[2], np.int64), np.ascontiguousarray(labels[3], np.uint8))
+            if len(pfo) != self.n_part + 1 or len(lo) != self.n_part + 1 or len(fp) < int(pfo[-1]) or len(l2) < (int(lo[-1]) + 3) // 4:
+                raise SegError("annotate: the labels' arrays do not match the resident batch")
+            a["_labels"] = (pfo, fp, lo, l2)
+            extra = [lo.ctypes.data, l2.ctypes.data if l2.size else None, pfo.ctypes.data, fp.ctypes.data]
+        self._check(self._L.fseg_annotate(self._h, ctypes.byref(s), *extra), "fseg_annotate")
+        out = _Annot()
+        self._check(self._L.fseg_annotation(self._h, ctypes.byref(out)), "fseg_annotation")
+
+        def view(ptr, m, dtype):
+            if m == 0 or not ptr:
+                return np.empty(0, dtype)
+            return np.frombuffer((ctypes.c_char * (int(m) * np.dtype(dtype).itemsize)).from_address(ptr), dtype=dtype)
+        res = {k: view(getattr(out, k), n + 1, np.int64) for k in ("gap_off", "clip_off", "poly_off", "tok_off")}
+        res["gaps"] = view(out.gaps, 3 * int(res["gap_off"][-1]), np.int32).reshape(-1, 3)
+        res["clips"] = view(out.clips, 2 * int(res["clip_off"][-1]), np.int32).reshape(-1, 2)
+        res["polys"] = view(out.polys, 3 * int(res["poly_off"][-1]), np.int32).reshape(-1, 3)
+        res["tail"] = view(out.tail, n, np.uint8)
+        res["tok"] = view(out.tok, int(res["tok_off"][-1]), np.uint32)
+        return res
 
     def tap(self, name):
         what, dtype = TAPS[name]

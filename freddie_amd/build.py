@@ -26,7 +26,7 @@ CSRC = os.path.join(_HERE, "csrc")
 # and the radix-sort unit; what they share is in two headers of csrc/ plus the ABI header.  The units are compiled side by side
 # (k_solve's three size classes are a unit each: the kernel is most of the build time -- 71 s as one file, ~25 s now on 8 cores).
 SEG_UNITS = ["freddie_seg", "seg_front", "seg_problems", "seg_score_arena", "seg_score_fused", "seg_solve16", "seg_solve32", "seg_solve60",
-             "seg_tail", "seg_upload", "freddie_seg_sort"]
+             "seg_tail", "seg_upload", "seg_annotate", "freddie_seg_sort"]
 SEG_HEADERS = [os.path.join(CSRC, "seg_common.h"), os.path.join(CSRC, "seg_kernels.h"), os.path.join(CSRC, "seg_solve.h")]
 SEG_SRC = [os.path.join(CSRC, u + ".hip") for u in SEG_UNITS] + SEG_HEADERS
 SEG_OBJ_DIR = os.path.join(CSRC, ".obj")

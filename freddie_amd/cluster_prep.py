@@ -1062,6 +1062,50 @@ def read_segment_arrays(paths, threads=1, mirror=True):
     return SegmentArrays(paths, threads, mirror)
 
 
+def arrays_from_segmentation(host_batch, results, annotation):
+    """The SegmentArrays read_segment_arrays() would make of the segment TSVs of a batch, built in memory from the segmentation
+    stage: host_batch = the loaded _host.HostBatch, results = (part_final_off, final_pos, label_off, labels2) of
+    Context.results(packed=True), annotation = the arrays of _lib.Context.annotate().  Context.partition_segment, tints_from_arrays,
+    round_gaps and cluster.cluster_tints take it unchanged.
+    A read's gaps come in ascending j1 (a TSV line has them in string order).  Nothing downstream depends on that order: the rep
+    grouping compares the key tokens of reads with equal label rows, and equal rows have equal j1 lists in either order."""
+    pfo, fp, lo, l2 = (np.asarray(results[0], np.int64), np.asarray(results[1], np.int32), np.asarray(results[2], np.int64),
+                       np.asarray(results[3], np.uint8))
+    ra = host_batch.read_arrays()
+    tint_id, tint_chr, read_name, read_chr = host_batch.names()
+    T, N = len(pfo) - 1, len(ra["read_part"])
+    read_off = np.zeros(T + 1, np.int64)
+    np.cumsum(np.bincount(ra["read_part"], minlength=T), out=read_off[1:])
+    n_seg = np.maximum(np.diff(pfo) - 1, 0).astype(np.int32)
+    lab_off, labels = np.zeros(T + 1, np.int64), []
+    for t in range(T):
+        M, n_r = int(n_seg[t]), int(read_off[t + 1] - read_off[t])
+        LW = max((M + 15) // 16, 1)
+        g = np.arange(int(lo[t]), int(lo[t + 1]), dtype=np.int64)
+        rows = ((l2[g >> 2] >> (2 * (g & 3)).astype(np.uint8)) & 3).reshape(-1, M) if M else np.zeros((0, 0), np.uint8)
+        codes = np.zeros((n_r, LW * 16), np.uint8)
+        if M and n_r:
+            codes[:, :M] = rows[ra["read_rep"][read_off[t]:read_off[t + 1]]]
+        labels.append(_pack_codes(codes))
+        lab_off[t + 1] = lab_off[t] + n_r * LW
+    a = dict(n_tint=T, tint_id=tint_id, n_seg=n_seg, pos_off=pfo.copy(), pos=fp[:int(pfo[-1])].astype(np.int64), read_off=read_off,
+             lab_off=lab_off, labels=np.concatenate(labels) if labels else np.zeros(0, np.uint32), rid=ra["read_id"].copy(),
+             strand=ra["strand"].copy(), tail=np.array(annotation["tail"], np.uint8))
+    for off, data, dt, cols in (("gap_off", "gaps", np.int32, 3), ("clip_off", "clips", np.int32, 2), ("poly_off", "polys", np.int32, 3),
+                                ("tok_off", "tok", np.uint32, 1)):
+        a[off] = np.array(annotation[off], np.int64)
+        x = np.array(annotation[data], dt)
+        a[data] = x.reshape(-1, cols) if cols > 1 else x.reshape(-1)
+    if len(a["tail"]) != N or len(a["gap_off"]) != N + 1:
+        raise ClusterError("arrays_from_segmentation: the annotation is not of this batch's reads")
+    out = SegmentArrays.__new__(SegmentArrays)
+    out._L, out._s, out.paths, out.declined = None, None, [], []
+    out.a = a
+    out.file_tint_off = np.arange(T + 1, dtype=np.int64)          # (a partition is what a segment TSV holds)
+    out._strings = (tint_chr, read_name, read_chr)
+    return out
+
+
 def cluster_files_batch(paths, maximum_ilp_size, ctx, ilp_settings=None, threads=8):
     """segment_*.tsv files in, (read_segment_arrays(), Context.group_reads() arrays, Context.preprocess() arrays of the reps,
     Context.partition() arrays) out: the native reader and one device call.  With ilp_settings the groups carry garbage_cost per rep

@@ -494,6 +494,21 @@ inline char *put_i(char *p, i64 v) {
 }
 inline char *put_s(char *p, const char *s) { while (*s) *p++ = *s++; return p; }
 
+// read['gaps'] = sorted(set(...)) on strings (:472), for tokens that come as [gap tokens in j1 order][E / S tokens].  No two tokens are
+// equal (the gap tokens differ in their first number, the others in their first letters), and a digit sorts before 'E' before 'S': the
+// gap tokens, sorted among themselves, go first, then the (at most three each) E and S tokens -- two short sorts instead of one sort of
+// 48-byte records.
+void sort_tokens(std::vector<Tok> &toks, size_t n_gaps) {
+    const auto less = [](const Tok &a, const Tok &b2) { return strcmp(a.s, b2.s) < 0; };
+    if (n_gaps > 1) {
+        // "last1-first2:size" with last1 ascending: already sorted unless the first numbers differ in their digit counts
+        bool sorted = true;
+        for (size_t k = 1; k < n_gaps && sorted; ++k) sorted = less(toks[k - 1], toks[k]);
+        if (!sorted) std::sort(toks.begin(), toks.begin() + (std::ptrdiff_t)n_gaps, less);
+    }
+    std::sort(toks.begin() + (std::ptrdiff_t)n_gaps, toks.end(), less);
+}
+
 // gaps: the tokens of read['gaps'] = sorted(set(...)) (:472), in `toks` (sorted, unique); empty when the read has no '1'
 void annotate_read(const Partition &P, const Read &r, const unsigned char *data, i64 S, const int *fp,
                    std::vector<Tok> &toks, std::vector<std::pair<i64, i64>> &runs, std::vector<char> &scratch) {
@@ -541,19 +556,28 @@ void annotate_read(const Partition &P, const Read &r, const unsigned char *data,
         if (!(0 <= size && size < length && last1 < first2)) throw Fail{"unaligned gap size out of range (:466-468)"};
         char *t = tok(); t = put_i(t, last1); *t++ = '-'; t = put_i(t, first2); *t++ = ':'; t = put_i(t, size); *t = 0;
     }
-    // read['gaps'] = sorted(set(...)) on strings (:472).  No two tokens are equal (the gap tokens differ in their first number, the
-    // others in their first letters), and a digit sorts before 'E' before 'S': the gap tokens, sorted among themselves, go first,
-    // then the (at most three each) E and S tokens -- a rotation and two short sorts instead of one sort of 48-byte records.
     std::rotate(toks.begin(), toks.begin() + (std::ptrdiff_t)n_ends, toks.end());
-    const auto less = [](const Tok &a, const Tok &b2) { return strcmp(a.s, b2.s) < 0; };
-    const size_t n_gaps = toks.size() - n_ends;
-    if (n_gaps > 1) {
-        // "last1-first2:size" with last1 ascending: already sorted unless the first numbers differ in their digit counts
-        bool sorted = true;
-        for (size_t k = 1; k < n_gaps && sorted; ++k) sorted = less(toks[k - 1], toks[k]);
-        if (!sorted) std::sort(toks.begin(), toks.begin() + (std::ptrdiff_t)n_gaps, less);
+    sort_tokens(toks, toks.size() - n_ends);
+}
+
+// the same tokens from an annotation that was computed elsewhere (fhost_write_annotated): read `g` of the batch in `an`
+void tokens_from_annotation(const fhost_annot &an, i64 g, std::vector<Tok> &toks) {
+    toks.clear();
+    auto tok = [&]() -> char * { toks.emplace_back(); return toks.back().s; };
+    const i64 g0 = an.gap_off[g], g1 = an.gap_off[g + 1];
+    for (i64 k = g0; k < g1; ++k) {
+        char *t = tok(); t = put_i(t, an.gaps[3 * k]); *t++ = '-'; t = put_i(t, an.gaps[3 * k + 1]); *t++ = ':'; t = put_i(t, an.gaps[3 * k + 2]); *t = 0;
     }
-    std::sort(toks.begin() + (std::ptrdiff_t)n_gaps, toks.end(), less);
+    for (i64 k = an.clip_off[g]; k < an.clip_off[g + 1]; ++k) {
+        char *t = tok(); t = put_s(t, an.clips[2 * k] ? "ESC:" : "SSC:"); t = put_i(t, an.clips[2 * k + 1]); *t = 0;
+    }
+    for (i64 k = an.poly_off[g]; k < an.poly_off[g + 1]; ++k) {
+        const int key = an.polys[3 * k];
+        if (key < 0 || key > 3) throw Fail{"fhost_write_annotated: a poly key outside 0..3"};
+        char *t = tok(); *t++ = key & 2 ? 'E' : 'S'; *t++ = key & 1 ? 'T' : 'A'; *t++ = '_'; t = put_i(t, an.polys[3 * k + 1]); *t++ = ':';
+        t = put_i(t, an.polys[3 * k + 2]); *t = 0;
+    }
+    sort_tokens(toks, (size_t)(g1 - g0 > 0 ? g1 - g0 : 0));
 }
 
 // ---- binary side-car of a partition ------------------------------------------
@@ -806,6 +830,16 @@ void parallel_for(int n, int n_threads, F fn) {
 struct fhost_batch {
     std::vector<Partition> parts;
     std::string err;
+    // fhost_read_arrays: the per-read arrays in fseg_reads' layout (built on the first call)
+    bool have_reads = false;
+    std::vector<int32_t> rd_part, rd_rep, rd_seq_len, rd_qs, rd_qe, rd_cig_len;
+    std::vector<uint8_t> rd_strand, rd_cig_op;
+    std::vector<int64_t> rd_seq_off, rd_q_off, rd_cig_off, rd_id;
+    std::vector<uint32_t> rd_cls;
+    // fhost_read_names: views into the split TSVs / side-cars the batch keeps mapped
+    std::vector<const char *> nm_name, nm_chr, nm_part_chr;
+    std::vector<int32_t> nm_name_len, nm_chr_len, nm_part_chr_len;
+    std::vector<int64_t> nm_part_id;
     std::vector<int64_t> part_iv_off, part_rep_off, rep_exon_off;
     std::vector<int32_t> iv_start, iv_end, rep_weight, ex_ts, ex_te;
     int64_t n_reads = 0;
@@ -999,8 +1033,14 @@ const int32_t *fhost_ex_ts(const fhost_batch *b) { return b->ex_ts.data(); }
 const int32_t *fhost_ex_te(const fhost_batch *b) { return b->ex_te.data(); }
 
 static int32_t write_impl(fhost_batch *b, const int64_t *part_final_off, const int32_t *final_pos, const int64_t *label_off,
-                          const uint8_t *labels, const char *const *out_paths, int32_t n_threads, bool packed) {
+                          const uint8_t *labels, const char *const *out_paths, int32_t n_threads, bool packed, const fhost_annot *an = nullptr) {
     if (!b || !b->err.empty()) return 1;
+    std::vector<i64> read_base;                             // (annotation given: where each partition's reads start in it)
+    if (an) {
+        if (an->n_read != b->n_reads) { b->err = "fhost_write_annotated: the annotation is not of this batch's reads"; return 2; }
+        read_base.assign(b->parts.size() + 1, 0);
+        for (size_t p = 0; p < b->parts.size(); ++p) read_base[p + 1] = read_base[p] + (i64)b->parts[p].reads.size();
+    }
     // packed labels: two bits each, label byte g of the arena at bits 2(g & 3).. of packed byte g >> 2 (fseg_results_packed);
     // a packed byte becomes four ASCII digits through a table
     static char DIGITS4[256][4];
@@ -1028,6 +1068,7 @@ static int32_t write_impl(fhost_batch *b, const int64_t *part_final_off, const i
             w = put_i(w, P.id); *w++ = '\t';
             for (i64 i = 0; i < F; ++i) { if (i) *w++ = ','; w = put_i(w, fp[i]); }
             *w++ = '\n';
+            i64 rg = an ? read_base[(size_t)p] : 0;
             for (const Read &r : P.reads) {
                 {   // room for the line up to and including its label field (the gap tokens are accounted for below)
                     const size_t used = (size_t)(w - out.data()), line_max = (size_t)Sc + r.name.n + r.chr.n + 64;
@@ -1049,7 +1090,8 @@ static int32_t write_impl(fhost_batch *b, const int64_t *part_final_off, const i
                     for (; i < Sc; ++i, ++g) row[i] = (char)('0' + ((labels[g >> 2] >> ((g & 3) * 2)) & 3));
                 }
                 w += Sc;
-                annotate_read(P, r, reinterpret_cast<const unsigned char *>(row), S, fp, toks, runs, scratch);
+                if (an) tokens_from_annotation(*an, rg++, toks);
+                else annotate_read(P, r, reinterpret_cast<const unsigned char *>(row), S, fp, toks, runs, scratch);
                 {   // a read with many label runs has many gap tokens: make room before writing them
                     const size_t used = (size_t)(w - out.data()), rest_max = 8 + toks.size() * 48;
                     if (used + rest_max > out.size()) { out.resize((used + rest_max) * 2); w = out.data() + used; }
@@ -1088,6 +1130,101 @@ int32_t fhost_write(fhost_batch *b, const int64_t *part_final_off, const int32_t
 int32_t fhost_write_packed(fhost_batch *b, const int64_t *part_final_off, const int32_t *final_pos, const int64_t *label_off,
                            const uint8_t *labels2, const char *const *out_paths, int32_t n_threads) {
     return write_impl(b, part_final_off, final_pos, label_off, labels2, out_paths, n_threads, true);
+}
+
+int32_t fhost_write_annotated(fhost_batch *b, const int64_t *part_final_off, const int32_t *final_pos, const int64_t *label_off,
+                              const uint8_t *labels2, const fhost_annot *annotation, const char *const *out_paths, int32_t n_threads) {
+    if (!annotation) return 1;
+    return write_impl(b, part_final_off, final_pos, label_off, labels2, out_paths, n_threads, true, annotation);
+}
+
+// The per-read arrays of a loaded batch in the layout fseg_annotate() takes: partitions in batch order, a partition's reads in file
+// order.  Every read's letters start on a word of the class codes (seq_off is a multiple of 16), so the partitions are built side
+// by side without two threads sharing a word.
+int32_t fhost_read_arrays(fhost_batch *b, int32_t n_threads, fhost_reads *out) {
+    if (!b || !out || !b->err.empty()) return 1;
+    try {
+        if (!b->have_reads) {
+            const size_t np = b->parts.size();
+            std::vector<i64> r0(np + 1, 0), q0(np + 1, 0), c0(np + 1, 0), w0(np + 1, 0);
+            for (size_t p = 0; p < np; ++p) {
+                const Partition &P = b->parts[p];
+                i64 words = 0;
+                for (const Read &r : P.reads) words += ((i64)r.seq.n + 15) / 16;
+                r0[p + 1] = r0[p] + (i64)P.reads.size(); q0[p + 1] = q0[p] + (i64)P.qs.size(); c0[p + 1] = c0[p] + (i64)P.cig_len.size();
+                w0[p + 1] = w0[p] + words;
+            }
+            const size_t n = (size_t)r0[np];
+            b->rd_part.resize(n); b->rd_rep.resize(n); b->rd_seq_len.resize(n); b->rd_strand.resize(n); b->rd_id.resize(n);
+            b->rd_seq_off.assign(n + 1, 0); b->rd_q_off.assign(n + 1, 0);
+            b->rd_qs.resize((size_t)q0[np]); b->rd_qe.resize((size_t)q0[np]); b->rd_cig_off.assign((size_t)q0[np] + 1, 0);
+            b->rd_cig_op.resize((size_t)c0[np]); b->rd_cig_len.resize((size_t)c0[np]);
+            b->rd_cls.assign((size_t)w0[np], 0u);
+            b->rd_seq_off[n] = w0[np] * 16; b->rd_q_off[n] = q0[np]; b->rd_cig_off[(size_t)q0[np]] = c0[np];
+            parallel_for((int)np, n_threads, [&](int pi) {
+                const Partition &P = b->parts[(size_t)pi];
+                const size_t nq = P.qs.size(), nc = P.cig_len.size();
+                if (nq) { memcpy(&b->rd_qs[(size_t)q0[(size_t)pi]], P.qs.data(), nq * 4); memcpy(&b->rd_qe[(size_t)q0[(size_t)pi]], P.qe.data(), nq * 4); }
+                for (size_t x = 0; x < nq; ++x) b->rd_cig_off[(size_t)q0[(size_t)pi] + x] = c0[(size_t)pi] + P.cig_off[x];
+                if (nc) { memcpy(&b->rd_cig_op[(size_t)c0[(size_t)pi]], P.cig_op.data(), nc); memcpy(&b->rd_cig_len[(size_t)c0[(size_t)pi]], P.cig_len.data(), nc * 4); }
+                i64 w = w0[(size_t)pi];
+                size_t g = (size_t)r0[(size_t)pi];
+                for (const Read &r : P.reads) {
+                    b->rd_part[g] = pi; b->rd_rep[g] = r.rep; b->rd_seq_len[g] = (int32_t)r.seq.n; b->rd_strand[g] = (uint8_t)r.strand; b->rd_id[g] = r.id;
+                    b->rd_seq_off[g] = w * 16; b->rd_q_off[g] = q0[(size_t)pi] + r.ex0;
+                    uint32_t *cls = b->rd_cls.data() + w;
+                    const size_t m = r.seq.n;
+                    if (r.seq.p) {                             // TSV letters
+                        for (size_t t = 0; t < m; ++t) { const char ch = r.seq.p[t]; cls[t >> 4] |= (uint32_t)(ch == 'A' ? 0 : ch == 'T' ? 1 : 2) << (2 * (t & 15)); }
+                    } else {                                   // the side-car's packed letters (A C G T = 0 1 2 3) and its exception list
+                        for (size_t t = 0; t < m; ++t) {
+                            const uint64_t q = r.seq_g0 + t;
+                            const unsigned code = (P.packed[(size_t)(q >> 2)] >> ((q & 3) * 2)) & 3;
+                            cls[t >> 4] |= (uint32_t)(code == 0 ? 0 : code == 3 ? 1 : 2) << (2 * (t & 15));
+                        }
+                        if (P.n_exc) {                         // a byte other than upper-case ACGT is neither 'A' nor 'T'
+                            const uint64_t *e = std::lower_bound(P.exc_pos, P.exc_pos + P.n_exc, r.seq_g0);
+                            for (; e < P.exc_pos + P.n_exc && *e < r.seq_g0 + m; ++e) {
+                                const size_t t = (size_t)(*e - r.seq_g0);
+                                cls[t >> 4] = (cls[t >> 4] & ~(3u << (2 * (t & 15)))) | (2u << (2 * (t & 15)));
+                            }
+                        }
+                    }
+                    w += ((i64)m + 15) / 16;
+                    ++g;
+                }
+            });
+            b->have_reads = true;
+        }
+        out->n_read = (int64_t)b->rd_part.size();
+        out->read_part = b->rd_part.data(); out->read_rep = b->rd_rep.data(); out->strand = b->rd_strand.data(); out->seq_len = b->rd_seq_len.data();
+        out->seq_off = b->rd_seq_off.data(); out->read_q_off = b->rd_q_off.data(); out->qs = b->rd_qs.data(); out->qe = b->rd_qe.data();
+        out->cig_off = b->rd_cig_off.data(); out->cig_op = b->rd_cig_op.data(); out->cig_len = b->rd_cig_len.data(); out->seq_classes = b->rd_cls.data();
+        out->read_id = b->rd_id.data();
+    } catch (const std::exception &e) { b->err = std::string("fhost_read_arrays: ") + e.what(); return 2; }
+    catch (...) { b->err = "fhost_read_arrays: internal error"; return 2; }
+    return 0;
+}
+
+int32_t fhost_read_names(fhost_batch *b, fhost_names *out) {
+    if (!b || !out || !b->err.empty()) return 1;
+    try {
+        if (b->nm_part_id.size() != b->parts.size()) {
+            b->nm_name.clear(); b->nm_chr.clear(); b->nm_name_len.clear(); b->nm_chr_len.clear();
+            b->nm_part_chr.clear(); b->nm_part_chr_len.clear(); b->nm_part_id.clear();
+            for (const Partition &P : b->parts) {
+                b->nm_part_id.push_back(P.id); b->nm_part_chr.push_back(P.chr.data()); b->nm_part_chr_len.push_back((int32_t)P.chr.size());
+                for (const Read &r : P.reads) {
+                    b->nm_name.push_back(r.name.p); b->nm_name_len.push_back((int32_t)r.name.n);
+                    b->nm_chr.push_back(r.chr.p); b->nm_chr_len.push_back((int32_t)r.chr.n);
+                }
+            }
+        }
+        out->n_part = (int32_t)b->parts.size(); out->n_read = (int64_t)b->nm_name.size();
+        out->part_id = b->nm_part_id.data(); out->part_chr = b->nm_part_chr.data(); out->part_chr_len = b->nm_part_chr_len.data();
+        out->name = b->nm_name.data(); out->name_len = b->nm_name_len.data(); out->chr = b->nm_chr.data(); out->chr_len = b->nm_chr_len.data();
+    } catch (...) { b->err = "fhost_read_names: out of memory"; return 2; }
+    return 0;
 }
 
 }  // extern "C"

@@ -265,6 +265,12 @@ struct fseg_ctx {
            PATH_N_WIDE = PATH_N_SOLVE + 3, PATH_N_TINY = PATH_N_WIDE + 3, PATH_N_WORK, PATH_DPW, PATH_WIDE16, PATH_KNOWN, PATH_SOLVE8,
            PATH_TINY_KERNEL, PATH_SCORE, PATH_ARENA_DP, PATH_PLAN, PATH_N_ARENA_PROB, PATH_N_SCORE, PATH_WORDS = PATH_N_SCORE + 3 };
     int paths[PATH_WORDS] = {};
+    // fseg_annotate: the uploaded reads (one allocation, mirrored by a pinned image), per-read work arrays, the emitted lists, and
+    // the pinned buffers fseg_annotation() points into (own allocations: nothing of a run or of fseg_results* touches them)
+    DevBuf d_an_in, d_an_work, d_an_out;
+    HostBuf h_an_in, h_an;
+    bool have_annot = false;
+    fseg_annot annot{};
 };
 
 namespace {
@@ -1560,10 +1566,12 @@ void fseg_destroy(fseg_ctx *c) {
     drop_graph(c);
     Slab *slabs[] = {&c->slab_in, &c->slab_pos, &c->slab_arena};
     for (Slab *s : slabs) if (s->p) (void)hipFree(s->p);
-    DevBuf *bufs[] = {&c->d_labels, &c->d_packed, &c->d_sort_tmp, &c->d_w_main, &c->d_w_refine, &c->d_h_table, &c->d_thr_tab, &c->d_status, &c->d_prep, &c->d_tacc, &c->d_sync, &c->d_giant};
+    DevBuf *bufs[] = {&c->d_labels, &c->d_packed, &c->d_sort_tmp, &c->d_w_main, &c->d_w_refine, &c->d_h_table, &c->d_thr_tab, &c->d_status, &c->d_prep, &c->d_tacc, &c->d_sync, &c->d_giant, &c->d_an_in, &c->d_an_work, &c->d_an_out};
     for (DevBuf *b : bufs) if (b->p) (void)hipFree(b->p);
     if (c->h_stage.p) (void)hipHostFree(c->h_stage.p);
     if (c->h_res.p) (void)hipHostFree(c->h_res.p);
+    if (c->h_an_in.p) (void)hipHostFree(c->h_an_in.p);
+    if (c->h_an.p) (void)hipHostFree(c->h_an.p);
     if (c->h_status) (void)hipHostFree(c->h_status);
     if (c->h_prep) (void)hipHostFree(c->h_prep);
     for (int i = 0; i < ST_COUNT; ++i) { if (c->ev_b[i]) (void)hipEventDestroy(c->ev_b[i]); if (c->ev_e[i]) (void)hipEventDestroy(c->ev_e[i]); }
@@ -2159,6 +2167,200 @@ int fseg_download(fseg_ctx *c, int64_t *part_final_off, int32_t *final_pos, int6
         HIP_TRY(c, hipMemcpyAsync(labels, c->d_labels.p, (size_t)c->h_status->label_bytes, hipMemcpyDeviceToHost, s));
     }
     HIP_TRY(c, hipStreamSynchronize(s));
+    return FSEG_OK;
+}
+
+// ---- per-read annotation (seg_annotate.hip) --------------------------------------------------------------------------------
+// the reference asserts a read can fire, in the order of the kAn* codes (seg_kernels.h); the texts are the host writer's
+static const char *const kAnMessages[kAnCodes] = {
+    "", "forward_thread_cigar: t_pos > t_goal (:290)", "forward_thread_cigar: CIGAR exhausted before the goal (:293)",
+    "get_interval_start: slack / query position out of range (:323-324)", "get_interval_start: no exon at or after the position (:326)",
+    "get_interval_end: slack / query position out of range (:346-347)", "get_interval_end: no exon at or before the position (:349)",
+    "find_longest_poly: sequence index out of range (:355)", "soft-clip positions out of order (:389)",
+    "start poly tail out of range (:405,:410)", "end poly tail out of range (:435,:441,:450)",
+    "unaligned gap positions out of order (:462)", "unaligned gap size out of range (:466-468)"};
+
+static int annotate_impl(fseg_ctx *c, const fseg_reads *rd, const int64_t *label_off, const uint8_t *labels2,
+                         const int64_t *part_final_off, const int32_t *final_pos) {
+    if (!c || !rd) return FSEG_ERR_ARG;
+    c->have_annot = false;
+    const bool given = label_off || labels2 || part_final_off || final_pos;
+    if (given && !(label_off && part_final_off && final_pos))
+        return fail(c, FSEG_ERR_ARG, "fseg_annotate: give label_off, part_final_off and final_pos together (labels2 may be null only when there are no labels)");
+    if (!c->have_batch) return fail(c, FSEG_ERR_ARG, "fseg_annotate: upload a batch first");
+    HIP_TRY(c, hipSetDevice(c->device));
+    TRY(fseg_sync(c));
+    if (!given && !c->ran) return fail(c, FSEG_ERR_ARG, "fseg_annotate: no completed run");
+    const i64 n = rd->n_read;
+    if (n < 0 || n >= 0x7fffffffLL) return fail(c, FSEG_ERR_ARG, "fseg_annotate: bad n_read");
+    if (n > 0 && (!rd->read_part || !rd->read_rep || !rd->strand || !rd->seq_len || !rd->seq_off || !rd->read_q_off || !rd->qs || !rd->qe ||
+                  !rd->cig_off || !rd->cig_op || !rd->cig_len))
+        return fail(c, FSEG_ERR_ARG, "fseg_annotate: null array");
+    const int np = c->n_part;
+    // ---- argument checks: everything a kernel indexes with is bounded here
+    const i64 *h_rep_exon_off = reinterpret_cast<const i64 *>(c->h_stage.as<char>() + (static_cast<char *>(c->d_rep_exon_off.p) - static_cast<char *>(c->slab_in.p)));
+    if (n > 0 && (rd->seq_off[0] != 0 || rd->read_q_off[0] != 0)) return fail(c, FSEG_ERR_ARG, "fseg_annotate: read 0: offsets must start at 0");
+    for (i64 r = 0; r < n; ++r) {
+        const int p = rd->read_part[r], rep = rd->read_rep[r];
+        if (p < 0 || p >= np) return fail(c, FSEG_ERR_ARG, "fseg_annotate: read %lld: partition %d is outside the batch (%d partitions)", (long long)r, p, np);
+        const i64 n_rep = c->part_rep_off[(size_t)p + 1] - c->part_rep_off[(size_t)p];
+        if (rep < 0 || rep >= n_rep) return fail(c, FSEG_ERR_ARG, "fseg_annotate: read %lld: rep %d is beyond the %lld reps of partition %d", (long long)r, rep, (long long)n_rep, p);
+        if (rd->seq_off[r + 1] < rd->seq_off[r]) return fail(c, FSEG_ERR_ARG, "fseg_annotate: read %lld: seq_off does not ascend", (long long)r);
+        if (rd->seq_len[r] < 0 || rd->seq_len[r] > rd->seq_off[r + 1] - rd->seq_off[r])
+            return fail(c, FSEG_ERR_ARG, "fseg_annotate: read %lld: seq_len is not inside its seq_off span", (long long)r);
+        if (rd->read_q_off[r + 1] < rd->read_q_off[r]) return fail(c, FSEG_ERR_ARG, "fseg_annotate: read %lld: read_q_off does not ascend", (long long)r);
+        const i64 g = c->part_rep_off[(size_t)p] + rep, m = h_rep_exon_off[g + 1] - h_rep_exon_off[g];
+        if (rd->read_q_off[r + 1] - rd->read_q_off[r] != m)
+            return fail(c, FSEG_ERR_ARG, "fseg_annotate: read %lld: read_q_off spans %lld exons, its rep has %lld", (long long)r,
+                        (long long)(rd->read_q_off[r + 1] - rd->read_q_off[r]), (long long)m);
+        if (rd->strand[r] != '+' && rd->strand[r] != '-') return fail(c, FSEG_ERR_ARG, "fseg_annotate: read %lld: strand is neither '+' nor '-'", (long long)r);
+        for (i64 x = rd->read_q_off[r]; x < rd->read_q_off[r + 1]; ++x)
+            if (rd->cig_off[x + 1] < rd->cig_off[x] || rd->cig_off[x] < 0) return fail(c, FSEG_ERR_ARG, "fseg_annotate: read %lld: cig_off does not ascend", (long long)r);
+    }
+    const i64 NQ = n ? rd->read_q_off[n] : 0, NC = NQ ? rd->cig_off[NQ] : 0, NL = n ? rd->seq_off[n] : 0;
+    if (NL > 0 && !rd->seq_classes) return fail(c, FSEG_ERR_ARG, "fseg_annotate: null array");
+    i64 n_final = 0, n_label = 0;
+    if (given) {
+        if (part_final_off[0] != 0 || label_off[0] != 0) return fail(c, FSEG_ERR_ARG, "fseg_annotate: partition 0: offsets must start at 0");
+        for (int p = 0; p < np; ++p) {
+            const i64 F = part_final_off[p + 1] - part_final_off[p], n_rep = c->part_rep_off[(size_t)p + 1] - c->part_rep_off[(size_t)p];
+            if (F < 0) return fail(c, FSEG_ERR_ARG, "fseg_annotate: partition %d: part_final_off does not ascend", p);
+            if (label_off[p + 1] - label_off[p] != n_rep * (F > 0 ? F - 1 : 0))
+                return fail(c, FSEG_ERR_ARG, "fseg_annotate: partition %d: label_off does not span reps x (final positions - 1) labels", p);
+        }
+        n_final = part_final_off[np]; n_label = label_off[np];
+        if (n_label > 0 && !labels2) return fail(c, FSEG_ERR_ARG, "fseg_annotate: labels2 is null");
+    }
+    hipStream_t s = c->stream;
+    // ---- the inputs: one pinned image, one copy
+    DevBuf i_part, i_rep, i_strand, i_slen, i_soff, i_qoff, i_qs, i_qe, i_coff, i_cop, i_clen, i_cls, i_pfo, i_fp, i_loff, i_lab;
+    Carve in;
+    const size_t cls_words = (size_t)((NL + 15) / 16), lab_bytes = (size_t)((n_label + 3) / 4), lab_words = (size_t)((n_label + 15) / 16);
+    in.add(i_part, (size_t)n * 4); in.add(i_rep, (size_t)n * 4); in.add(i_strand, (size_t)n); in.add(i_slen, (size_t)n * 4);
+    in.add(i_soff, ((size_t)n + 1) * 8); in.add(i_qoff, ((size_t)n + 1) * 8); in.add(i_qs, (size_t)NQ * 4); in.add(i_qe, (size_t)NQ * 4);
+    in.add(i_coff, ((size_t)NQ + 1) * 8); in.add(i_cop, (size_t)NC); in.add(i_clen, (size_t)NC * 4); in.add(i_cls, cls_words * 4);
+    in.add(i_pfo, ((size_t)np + 1) * 8);
+    if (given) { in.add(i_fp, (size_t)n_final * 4); in.add(i_loff, ((size_t)np + 1) * 8); in.add(i_lab, lab_words * 4); }
+    TRY(ensure(c, c->d_an_in, in.total + 256));
+    TRY(reserve_host(c, c->h_an_in, in.total + 256));
+    { Slab sl; sl.p = c->d_an_in.p; sl.cap = c->d_an_in.cap; in.bind(sl); }
+    char *hin = c->h_an_in.as<char>();
+    auto put = [&](const DevBuf &d, const void *src, size_t bytes) {
+        if (bytes) memcpy(hin + (static_cast<char *>(d.p) - static_cast<char *>(c->d_an_in.p)), src, bytes);
+    };
+    put(i_part, rd->read_part, (size_t)n * 4); put(i_rep, rd->read_rep, (size_t)n * 4); put(i_strand, rd->strand, (size_t)n);
+    put(i_slen, rd->seq_len, (size_t)n * 4);
+    const i64 zero = 0;
+    put(i_soff, n ? (const void *)rd->seq_off : &zero, ((size_t)n + 1) * 8); put(i_qoff, n ? (const void *)rd->read_q_off : &zero, ((size_t)n + 1) * 8);
+    put(i_qs, rd->qs, (size_t)NQ * 4); put(i_qe, rd->qe, (size_t)NQ * 4);
+    put(i_coff, NQ ? (const void *)rd->cig_off : &zero, ((size_t)NQ + 1) * 8); put(i_cop, rd->cig_op, (size_t)NC); put(i_clen, rd->cig_len, (size_t)NC * 4);
+    put(i_cls, rd->seq_classes, cls_words * 4);
+    if (given) {
+        put(i_pfo, part_final_off, ((size_t)np + 1) * 8); put(i_fp, final_pos, (size_t)n_final * 4); put(i_loff, label_off, ((size_t)np + 1) * 8);
+        if (lab_words) memset(hin + (static_cast<char *>(i_lab.p) - static_cast<char *>(c->d_an_in.p)), 0, lab_words * 4);     // the caller's array ends with its last byte
+        put(i_lab, labels2, lab_bytes);
+    }
+    HIP_TRY(c, hipMemcpyAsync(c->d_an_in.p, hin, in.total, hipMemcpyHostToDevice, s));
+    // ---- work arrays
+    const i64 nb = (n + kAnScanItemsPerBlock - 1) / kAnScanItemsPerBlock;
+    DevBuf w_cnt, w_ends, w_poly, w_off, w_tok_off, w_tail, w_status, w_bad, w_bsum;
+    Carve wk;
+    wk.add(w_cnt, (size_t)n * 8); wk.add(w_ends, (size_t)n * 16); wk.add(w_poly, (size_t)n * 32); wk.add(w_off, ((size_t)n + 1) * 24);
+    wk.add(w_tok_off, ((size_t)n + 1) * 8); wk.add(w_tail, (size_t)n); wk.add(w_status, (size_t)n * 4); wk.add(w_bad, 8); wk.add(w_bsum, (size_t)nb * 24 + 8);
+    TRY(ensure(c, c->d_an_work, wk.total + 256));
+    { Slab sl; sl.p = c->d_an_work.p; sl.cap = c->d_an_work.cap; wk.bind(sl); }
+    AnnotIn a{};
+    a.n_read = n;
+    a.read_part = i_part.as<int>(); a.read_rep = i_rep.as<int>(); a.strand = i_strand.as<unsigned char>(); a.seq_len = i_slen.as<int>();
+    a.seq_off = i_soff.as<i64>(); a.read_q_off = i_qoff.as<i64>(); a.qs = i_qs.as<int>(); a.qe = i_qe.as<int>(); a.cig_off = i_coff.as<i64>();
+    a.cig_op = i_cop.as<unsigned char>(); a.cig_len = i_clen.as<int>(); a.seq_cls = i_cls.as<unsigned>();
+    a.part_rep_off = c->d_part_rep_off.as<i64>(); a.rep_exon_off = c->d_rep_exon_off.as<i64>(); a.ex_ts = c->d_ex_ts.as<int>(); a.ex_te = c->d_ex_te.as<int>();
+    a.pfo = i_pfo.as<i64>();
+    if (given) { a.final_pos = i_fp.as<int>(); a.label_off = i_loff.as<i64>(); a.lab2 = i_lab.as<unsigned>(); a.lab1 = nullptr; }
+    else {
+        hipLaunchKernelGGL(k_an_pfo, dim3(grid_for(np + 1, 256, 65536)), dim3(256), 0, s, np, c->d_part_iv_off.as<i64>(), c->d_final_off.as<i64>(), i_pfo.as<i64>());
+        a.final_pos = c->d_final_pos.as<int>(); a.label_off = c->d_label_off.as<i64>();
+        a.lab2 = c->run_label_packed ? c->d_packed.as<unsigned>() : nullptr;
+        a.lab1 = c->run_label_packed ? nullptr : c->d_labels.as<unsigned char>();
+    }
+    AnnotOut o{};
+    o.cnt = w_cnt.as<int>(); o.ends = w_ends.as<int4>(); o.poly = w_poly.as<int4>(); o.off = w_off.as<i64>(); o.tok_off = w_tok_off.as<i64>();
+    o.tail = w_tail.as<unsigned char>(); o.status = w_status.as<int>(); o.first_bad = w_bad.as<unsigned long long>();
+    // pinned results: offsets and the per-read bytes first (their sizes are known), the lists behind them
+    size_t hoff[9], htotal = 0;
+    auto take = [&](int i, size_t bytes) { hoff[i] = htotal; htotal = (htotal + bytes + 255) & ~(size_t)255; };
+    take(0, ((size_t)n + 1) * 8); take(1, ((size_t)n + 1) * 8); take(2, ((size_t)n + 1) * 8); take(3, ((size_t)n + 1) * 8); take(4, (size_t)n + 8);
+    const size_t head = htotal;
+    TRY(reserve_host(c, c->h_an, head + 4096));
+    i64 *totals = reinterpret_cast<i64 *>(c->h_an.as<char>());       // (scratch until the results land)
+    totals[0] = totals[1] = totals[2] = 0;
+    unsigned long long *h_bad = reinterpret_cast<unsigned long long *>(c->h_an.as<char>() + 64);
+    *h_bad = ~0ull;
+    if (n > 0) {
+        HIP_TRY(c, hipMemsetAsync(w_bad.p, 0xff, 8, s));
+        const int g = grid_for(n, 256, 65536);
+        hipLaunchKernelGGL(k_an_count, dim3(g), dim3(256), 0, s, a, o);
+        hipLaunchKernelGGL(k_an_poly, dim3(grid_for(2 * n, 256, 65536)), dim3(256), 0, s, a, o);
+        hipLaunchKernelGGL(k_an_scan1, dim3((unsigned)nb, 3), dim3(256), 0, s, o.cnt, o.poly, n, nb, w_bsum.as<i64>());
+        hipLaunchKernelGGL(k_an_scan2, dim3(3), dim3(256), 0, s, nb, w_bsum.as<i64>());
+        hipLaunchKernelGGL(k_an_scan3, dim3((unsigned)nb, 3), dim3(256), 0, s, o.cnt, o.poly, n, nb, w_bsum.as<i64>(), o.off);
+        for (int k = 0; k < 3; ++k) HIP_TRY(c, hipMemcpyAsync(&totals[k], o.off + (size_t)k * ((size_t)n + 1) + (size_t)n, 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipStreamSynchronize(s));
+    }
+    const i64 G = totals[0], C = totals[1], Pn = totals[2];
+    DevBuf o_gaps, o_clips, o_polys, o_tok;
+    Carve ov;
+    ov.add(o_gaps, (size_t)G * 12); ov.add(o_clips, (size_t)C * 8); ov.add(o_polys, (size_t)Pn * 12); ov.add(o_tok, (size_t)(G + Pn) * 4);
+    TRY(ensure(c, c->d_an_out, ov.total + 256));
+    { Slab sl; sl.p = c->d_an_out.p; sl.cap = c->d_an_out.cap; ov.bind(sl); }
+    o.gaps = o_gaps.as<int>(); o.clips = o_clips.as<int>(); o.polys = o_polys.as<int>(); o.tok = o_tok.as<unsigned>();
+    take(5, (size_t)G * 12); take(6, (size_t)C * 8); take(7, (size_t)Pn * 12); take(8, (size_t)(G + Pn) * 4);
+    TRY(reserve_host(c, c->h_an, htotal + 4096));
+    char *h = c->h_an.as<char>();
+    if (n > 0) {
+        hipLaunchKernelGGL(k_an_emit, dim3(grid_for(n, 256, 65536)), dim3(256), 0, s, a, o);
+        HIP_TRY(c, hipGetLastError());
+        unsigned long long *bad = reinterpret_cast<unsigned long long *>(h + htotal);
+        HIP_TRY(c, hipMemcpyAsync(bad, w_bad.p, 8, hipMemcpyDeviceToHost, s));
+        for (int k = 0; k < 3; ++k) HIP_TRY(c, hipMemcpyAsync(h + hoff[k], o.off + (size_t)k * ((size_t)n + 1), ((size_t)n + 1) * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipMemcpyAsync(h + hoff[3], o.tok_off, ((size_t)n + 1) * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipMemcpyAsync(h + hoff[4], o.tail, (size_t)n, hipMemcpyDeviceToHost, s));
+        if (G) HIP_TRY(c, hipMemcpyAsync(h + hoff[5], o.gaps, (size_t)G * 12, hipMemcpyDeviceToHost, s));
+        if (C) HIP_TRY(c, hipMemcpyAsync(h + hoff[6], o.clips, (size_t)C * 8, hipMemcpyDeviceToHost, s));
+        if (Pn) HIP_TRY(c, hipMemcpyAsync(h + hoff[7], o.polys, (size_t)Pn * 12, hipMemcpyDeviceToHost, s));
+        if (G + Pn) HIP_TRY(c, hipMemcpyAsync(h + hoff[8], o.tok, (size_t)(G + Pn) * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipStreamSynchronize(s));
+        if (*bad != ~0ull) {
+            const i64 r = (i64)*bad;
+            int code = 0;
+            HIP_TRY(c, copy_sync(c, &code, o.status + r, 4, hipMemcpyDeviceToHost));
+            return fail(c, FSEG_ERR_INPUT, "fseg_annotate: partition %d, read %lld: %s (reference: py/freddie_segment.py)", rd->read_part[r], (long long)r,
+                        code > 0 && code < kAnCodes ? kAnMessages[code] : "unknown status");
+        }
+    } else {
+        for (int k = 0; k < 4; ++k) *reinterpret_cast<i64 *>(h + hoff[k]) = 0;
+    }
+    fseg_annot &A = c->annot;
+    A.n_read = n;
+    A.gap_off = reinterpret_cast<const int64_t *>(h + hoff[0]); A.clip_off = reinterpret_cast<const int64_t *>(h + hoff[1]);
+    A.poly_off = reinterpret_cast<const int64_t *>(h + hoff[2]); A.tok_off = reinterpret_cast<const int64_t *>(h + hoff[3]);
+    A.tail = reinterpret_cast<const uint8_t *>(h + hoff[4]);
+    A.gaps = reinterpret_cast<const int32_t *>(h + hoff[5]); A.clips = reinterpret_cast<const int32_t *>(h + hoff[6]);
+    A.polys = reinterpret_cast<const int32_t *>(h + hoff[7]); A.tok = reinterpret_cast<const uint32_t *>(h + hoff[8]);
+    c->have_annot = true;
+    return FSEG_OK;
+}
+
+int32_t fseg_annotate(fseg_ctx *c, const fseg_reads *reads, const int64_t *label_off, const uint8_t *labels2,
+                      const int64_t *part_final_off, const int32_t *final_pos) {
+    return annotate_impl(c, reads, label_off, labels2, part_final_off, final_pos);
+}
+
+int32_t fseg_annotation(fseg_ctx *c, fseg_annot *out) {
+    if (!c || !out) return FSEG_ERR_ARG;
+    if (!c->have_annot) return fail(c, FSEG_ERR_ARG, "fseg_annotation: no completed fseg_annotate");
+    *out = c->annot;
     return FSEG_OK;
 }
 

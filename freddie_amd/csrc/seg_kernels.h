@@ -271,4 +271,48 @@ __global__ void __launch_bounds__(256) k_hist_ranges(int n_chunks, const int *hc
                                                      const i64 *part_lane_off, const int *lane_start, const int *lane_pmax,
                                                      i64 *hc_llo, i64 *hc_lhi);
 
+// seg_annotate.hip: per-read gaps, clips and poly tails (fseg_annotate).  Per-read status codes: the reference assert a read
+// would have fired (kAnMessages, freddie_seg.hip, in the same order)
+enum : int { kAnOk = 0, kAnThreadOrder, kAnCigarShort, kAnStartRange, kAnStartNone, kAnEndRange, kAnEndNone, kAnPolyIndex, kAnClipOrder,
+             kAnStartPoly, kAnEndPoly, kAnGapOrder, kAnGapSize, kAnCodes };
+struct AnnotIn {          // device pointers
+    i64 n_read;
+    const int *read_part, *read_rep;         // per read: partition, rep inside the partition
+    const unsigned char *strand;
+    const int *seq_len;
+    const i64 *seq_off, *read_q_off;         // letters into seq_cls; into qs / qe / cig_off
+    const int *qs, *qe;
+    const i64 *cig_off;
+    const unsigned char *cig_op;
+    const int *cig_len;
+    const unsigned *seq_cls;                 // 16 class codes a word: 0 'A', 1 'T', 2 anything else
+    const i64 *part_rep_off, *rep_exon_off;  // the resident batch
+    const int *ex_ts, *ex_te;
+    const i64 *pfo;                          // part_final_off
+    const int *final_pos;
+    const i64 *label_off;
+    const unsigned *lab2;                    // the label arena at two bits a label, or null and ...
+    const unsigned char *lab1;               // ... a byte a label
+};
+struct AnnotOut {
+    int *cnt;                                // [2][n]: gaps, clips of a read
+    int4 *ends;                              // per read: (has a label 1, status of the ends, q_ssc, q_esc)
+    int4 *poly;                              // per window (2 r: start, 2 r + 1: end): (0 none / 1 A / 2 T, first, len, status)
+    i64 *off;                                // [3][n + 1]: gap_off, clip_off, poly_off
+    i64 *tok_off;
+    int *gaps, *clips, *polys;
+    unsigned *tok;
+    unsigned char *tail;
+    int *status;
+    unsigned long long *first_bad;           // smallest read with a status (atomicMin)
+};
+constexpr int kAnScanItemsPerBlock = 1024;
+__global__ void __launch_bounds__(256) k_an_pfo(int n_part, const i64 *part_iv_off, const i64 *final_off, i64 *pfo);
+__global__ void __launch_bounds__(256) k_an_count(AnnotIn a, AnnotOut o);
+__global__ void __launch_bounds__(256) k_an_poly(AnnotIn a, AnnotOut o);
+__global__ void __launch_bounds__(256) k_an_scan1(const int *cnt, const int4 *poly, i64 n, i64 nb, i64 *bsum);
+__global__ void __launch_bounds__(256) k_an_scan2(i64 nb, i64 *bsum);
+__global__ void __launch_bounds__(256) k_an_scan3(const int *cnt, const int4 *poly, i64 n, i64 nb, const i64 *bsum, i64 *off);
+__global__ void __launch_bounds__(256) k_an_emit(AnnotIn a, AnnotOut o);
+
 }  // namespace fseg

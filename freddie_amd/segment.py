@@ -65,6 +65,9 @@ def parse_args(argv=None):
     ap.add_argument("--devices", type=str, default=None,
                     help="Comma-separated GPU ordinals, one worker per entry (overrides --gpus; e.g. 0,1,2,3)")
     ap.add_argument("--batch-reads", type=int, default=250000, help="Reads per device batch")
+    ap.add_argument("--annotate", choices=("host", "gpu"), default="host",
+                    help="Where the unaligned gaps and poly tails of the reads are computed: by the native writer's threads (host), or "
+                         "on the device behind the segmentation (gpu: fseg_annotate; the writer then only formats). The outputs are the same")
     ap.add_argument("--sidecar", choices=("auto", "off", "write"), default="auto",
                     help="Binary side-cars (split_*.fsc) of the split TSVs: auto = use the fresh ones that exist; "
                          "write = also emit them for partitions that had to be parsed; off = always parse the TSVs")
@@ -333,6 +336,47 @@ def pack_tint(tint):
                                 np.ascontiguousarray(flat[:, 0]), np.ascontiguousarray(flat[:, 1]), read_rep)
 
 
+def class_codes(seq):
+    """The two-bit class codes of a sequence, 16 to a uint32 word: 0 'A', 1 'T', 2 any other byte (include/freddie_seg.h, fseg_reads)."""
+    b = np.frombuffer(seq.encode("latin-1"), np.uint8)
+    c = np.where(b == 65, 0, np.where(b == 84, 1, 2)).astype(np.uint32)
+    c = np.concatenate([c, np.zeros(-len(c) % 16, np.uint32)]).reshape(-1, 16)
+    return (c << (2 * np.arange(16, dtype=np.uint32))).sum(axis=1, dtype=np.uint32)
+
+
+def read_arrays_from_tints(tints, parts):
+    """fseg_reads' arrays (include/freddie_seg.h) from tint dicts: what HostBatch.read_arrays() hands over for a native batch."""
+    read_part, read_rep, strand, seq_len, seq_off, read_q_off = [], [], [], [], [0], [0]
+    qs, qe, cig_off, cig_op, cig_len, cls = [], [], [0], [], [], []
+    for p, (tint, part) in enumerate(zip(tints, parts)):
+        for ridx, read in enumerate(tint["reads"]):
+            read_part.append(p); read_rep.append(int(part.read_rep[ridx])); strand.append(ord(read["strand"])); seq_len.append(len(read["seq"]))
+            w = class_codes(read["seq"])
+            cls.append(w)
+            seq_off.append(seq_off[-1] + 16 * len(w))
+            for _, _, q0, q1, cigar in read["intervals"]:
+                qs.append(q0); qe.append(q1)
+                for ln, op in cigar:
+                    cig_len.append(ln); cig_op.append(ord(op))
+                cig_off.append(len(cig_len))
+            read_q_off.append(len(qs))
+    return dict(read_part=np.array(read_part, np.int32), read_rep=np.array(read_rep, np.int32), strand=np.array(strand, np.uint8),
+                seq_len=np.array(seq_len, np.int32), seq_off=np.array(seq_off, np.int64), read_q_off=np.array(read_q_off, np.int64),
+                qs=np.array(qs, np.int32), qe=np.array(qe, np.int32), cig_off=np.array(cig_off, np.int64), cig_op=np.array(cig_op, np.uint8),
+                cig_len=np.array(cig_len, np.int32), seq_classes=np.concatenate(cls) if cls else np.empty(0, np.uint32))
+
+
+_POLY_KEYS = ("SA", "ST", "EA", "ET")
+
+
+def annotation_tokens(ann, r):
+    """read['gaps'] of read r from fseg_annot's arrays (Context.annotate()): the token strings of :409-471, sorted (:472)."""
+    toks = ["%d-%d:%d" % tuple(g) for g in ann["gaps"][ann["gap_off"][r]:ann["gap_off"][r + 1]].tolist()]
+    toks += ["%s:%d" % ("ESC" if k else "SSC", v) for k, v in ann["clips"][ann["clip_off"][r]:ann["clip_off"][r + 1]].tolist()]
+    toks += ["%s_%d:%d" % (_POLY_KEYS[k], ln, gap) for k, ln, gap in ann["polys"][ann["poly_off"][r]:ann["poly_off"][r + 1]].tolist()]
+    return sorted(toks)
+
+
 _default_ctx = {}
 
 
@@ -346,7 +390,9 @@ def default_context(device=0):
 def segment_batch(tints, sigma, smoothed_threshold, threshold_rate, variance_factor, max_problem_size,
                   min_read_support_outside, ignore_ends, ctx=None, gaps=True):
     """segment() over a batch of tints in one device pass.  Mutates every tint like the reference's segment():
-    tint['final_positions'], tint['segs'], read['data'], read['gaps']."""
+    tint['final_positions'], tint['segs'], read['data'], read['gaps'].
+    gaps: True -- the Python mirror of get_unaligned_gaps_and_polyA(); "gpu" -- the device's annotation of the run (Context.annotate),
+    formatted into the same token strings; False -- none."""
     ctx = ctx or default_context()
     parts = [pack_tint(t) for t in tints]
     ctx.set_params(sigma, threshold_rate, variance_factor, max_problem_size, min_read_support_outside, ignore_ends,
@@ -355,6 +401,8 @@ def segment_batch(tints, sigma, smoothed_threshold, threshold_rate, variance_fac
     ctx.upload(**pack.concat_batch(parts))
     ctx.run()
     part_final_off, final_pos, label_off, labels = ctx.download()
+    ann = ctx.annotate(read_arrays_from_tints(tints, parts)) if gaps == "gpu" else None
+    g = 0
     for p, (tint, part) in enumerate(zip(tints, parts)):
         fp = final_pos[part_final_off[p]:part_final_off[p + 1]]
         tint["final_positions"] = fp.tolist()
@@ -365,7 +413,11 @@ def segment_batch(tints, sigma, smoothed_threshold, threshold_rate, variance_fac
         for ri, (_, ridxs) in enumerate(tint["read_reps"]):
             for ridx in ridxs:
                 tint["reads"][ridx]["data"] = list(rows[ri])
-        if gaps:
+        if ann is not None:
+            for read in tint["reads"]:
+                read["gaps"] = annotation_tokens(ann, g) if 1 in read["data"] else set()
+                g += 1
+        elif gaps:
             for read in tint["reads"]:
                 unaligned_gaps_and_polyA(read, tint["segs"])
     return [t["id"] for t in tints]
@@ -473,13 +525,15 @@ def batch_too_large(exc):
     return (code == 4 and "split it" in msg) or (code == 2 and "memory" in msg)
 
 
-def run_batches(batches, params, ctxs, threads, on_done, sidecar="off"):
+def run_batches(batches, params, ctxs, threads, on_done, sidecar="off", annotate="host"):
     """Pipelined driver of one GPU.  ``ctxs``: one or two contexts on the same device (a single Context is accepted).
     Batch i+1 (and i+2) are being parsed by the native loader while batch i is on the device and batch i-1 is annotated
     and written; with two contexts consecutive batches alternate between them, so one batch's upload and the other's
     download overlap the kernels of the batch in between (each context has its own stream, pinned staging and pinned
     results, and the writer reads the results in place).  FREDDIE_TIMING=1 prints one line per batch to stderr (load /
-    device / write seconds, partitions taken from side-cars)."""
+    device / write seconds, partitions taken from side-cars).
+    annotate="gpu": the reads' gaps and poly tails come from the device (Context.annotate, behind the run and after the wait for the
+    writer that still reads this context's previous annotation); the writer formats them (HostBatch.write_annotated)."""
     import threading
     import time
     from collections import deque
@@ -500,10 +554,13 @@ def run_batches(batches, params, ctxs, threads, on_done, sidecar="off"):
             marks.append(("load", i, t0 - t_pipe, t1 - t_pipe))      # (i = the batch's index; -1: a half of a batch that was too large)
         return hb, t1 - t0
 
-    def write(hb, res, jobs, t_load, t_dev, i):
+    def write(hb, res, jobs, t_load, t_dev, i, ann=None):
         t0 = time.perf_counter()
         try:
-            hb.write(*res, [_job_paths(j)[2] for j in jobs], n_threads=threads, packed=True)
+            if ann is not None:
+                hb.write_annotated(*res, ann, [_job_paths(j)[2] for j in jobs], n_threads=threads)
+            else:
+                hb.write(*res, [_job_paths(j)[2] for j in jobs], n_threads=threads, packed=True)
         finally:
             n_sc, n_reads = hb.n_from_sidecar, hb.n_reads
             hb.close()
@@ -552,6 +609,7 @@ def run_batches(batches, params, ctxs, threads, on_done, sidecar="off"):
                     last_write[k].result()   # its results live in this context's pinned buffers until it has finished
                 t2 = time.perf_counter()
                 res = ctx.results(packed=True)    # two bits per label across PCIe; the writer unpacks rows into the TSV
+                ann = ctx.annotate(hb.read_arrays(n_threads=threads)) if annotate == "gpu" else None
             except BaseException as exc:
                 hb.close()
                 if len(jobs) > 1 and batch_too_large(exc):
@@ -566,7 +624,7 @@ def run_batches(batches, params, ctxs, threads, on_done, sidecar="off"):
             t_dev = (t1 - t0) + (time.perf_counter() - t2)       # without the wait for the writer
             if timing:
                 marks.append(("device", i, t0 - t_pipe, time.perf_counter() - t_pipe))
-            last_write[k] = write_pool.submit(write, hb, res, jobs, t_load, t_dev, i)
+            last_write[k] = write_pool.submit(write, hb, res, jobs, t_load, t_dev, i, ann)
 
         dev_futs = [None] * n_ctx
         try:
@@ -665,7 +723,7 @@ def open_contexts(device, n=2):
     return ctxs
 
 
-def _gpu_worker(device, n_workers, jobs_with_cost, params, batch_bytes, threads, queue, sidecar="off", worker=None):
+def _gpu_worker(device, n_workers, jobs_with_cost, params, batch_bytes, threads, queue, sidecar="off", worker=None, annotate="host"):
     """jobs_with_cost: the worker's jobs, or the receiving end of a pipe they arrive through (main() starts its workers before
     it has looked at the split directory: interpreter start-up, imports and the GPU's contexts -- 0.3-0.5 s -- run beside the
     parent's discovery and scatter instead of behind them)."""
@@ -683,7 +741,7 @@ def _gpu_worker(device, n_workers, jobs_with_cost, params, batch_bytes, threads,
                     jobs_with_cost = _expand_jobs(conn.recv())
                 finally:
                     conn.close()
-            run_batches(make_batches(jobs_with_cost, batch_bytes), params, ctx_future, threads, queue.put, sidecar)
+            run_batches(make_batches(jobs_with_cost, batch_bytes), params, ctx_future, threads, queue.put, sidecar, annotate)
             ok = True
         finally:
             try:
@@ -764,7 +822,7 @@ def main(argv=None, leave_contexts=False):
         queue = mp.Queue()
         for w, dev in enumerate(device_list):
             recv_end, send_end = mp.Pipe(duplex=False)
-            pr = mp.Process(target=_gpu_worker, args=(dev, n_gpus, recv_end, params, batch_bytes, args.threads, queue, args.sidecar, w))
+            pr = mp.Process(target=_gpu_worker, args=(dev, n_gpus, recv_end, params, batch_bytes, args.threads, queue, args.sidecar, w, args.annotate))
             pr.start()
             recv_end.close()
             procs.append(pr)
@@ -806,7 +864,7 @@ def main(argv=None, leave_contexts=False):
         with boot:
             ok = False
             try:
-                run_batches(make_batches(jobs, batch_bytes), params, ctx_future, args.threads, report, args.sidecar)
+                run_batches(make_batches(jobs, batch_bytes), params, ctx_future, args.threads, report, args.sidecar, args.annotate)
                 ok = True
             finally:
                 t_run = time.perf_counter()

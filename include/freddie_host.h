@@ -54,6 +54,65 @@ int32_t fhost_write(fhost_batch *b, const int64_t *part_final_off, const int32_t
 int32_t fhost_write_packed(fhost_batch *b, const int64_t *part_final_off, const int32_t *final_pos, const int64_t *label_off,
                            const uint8_t *labels2, const char *const *out_paths, int32_t n_threads);
 
+/* ---- the annotation computed elsewhere (include/freddie_seg.h, fseg_annotate) ------------------------------------------------
+ * fhost_reads begins with the fields of fseg_reads, in its order and with its meaning, so that a pointer to it is a pointer to an
+ * fseg_reads: the per-read arrays of a loaded batch, partitions in batch order and a partition's reads in file order; every read's
+ * letters start on a word of seq_classes.  The class codes (0 'A', 1 'T', 2 any other byte) are built from the TSV letters or from
+ * the side-car's packed letters and exception list, on n_threads.  Pointers stay valid until fhost_free(). */
+typedef struct {
+    int64_t n_read;
+    const int32_t *read_part;
+    const int32_t *read_rep;
+    const uint8_t *strand;
+    const int32_t *seq_len;
+    const int64_t *seq_off;
+    const int64_t *read_q_off;
+    const int32_t *qs;
+    const int32_t *qe;
+    const int64_t *cig_off;
+    const uint8_t *cig_op;
+    const int32_t *cig_len;
+    const uint32_t *seq_classes;
+    const int64_t *read_id;        /* (beyond fseg_reads: the read ids of the split TSVs) */
+} fhost_reads;
+int32_t fhost_read_arrays(fhost_batch *b, int32_t n_threads, fhost_reads *out);   /* 0 on success */
+
+/* The tint ids and contigs of the batch's partitions and the names and contigs of its reads (fhost_reads' order): views, not
+ * NUL-terminated, into the split TSVs or side-cars the batch keeps mapped until fhost_free(). */
+typedef struct {
+    int32_t n_part;
+    int64_t n_read;
+    const int64_t *part_id;
+    const char *const *part_chr;
+    const int32_t *part_chr_len;
+    const char *const *name;
+    const int32_t *name_len;
+    const char *const *chr;
+    const int32_t *chr_len;
+} fhost_names;
+int32_t fhost_read_names(fhost_batch *b, fhost_names *out);   /* 0 on success */
+
+/* fseg_annot, field for field (and so the gap / clip / poly lists and tail of fhost_segments below), for the batch's reads in
+ * fhost_reads' order. */
+typedef struct {
+    int64_t n_read;
+    const int64_t *gap_off;
+    const int32_t *gaps;
+    const int64_t *clip_off;
+    const int32_t *clips;
+    const int64_t *poly_off;
+    const int32_t *polys;
+    const uint8_t *tail;
+    const int64_t *tok_off;
+    const uint32_t *tok;
+} fhost_annot;
+
+/* fhost_write_packed with the annotation GIVEN instead of computed: formats its tokens and puts them in the line order of
+ * sorted(set(...)) (py/freddie_segment.py:472); the order of a read's gaps in `annotation` does not matter.  tail, tok_off and tok
+ * are not read.  The bytes equal fhost_write_packed's when the annotation equals what it computes. */
+int32_t fhost_write_annotated(fhost_batch *b, const int64_t *part_final_off, const int32_t *final_pos, const int64_t *label_off,
+                              const uint8_t *labels2, const fhost_annot *annotation, const char *const *out_paths, int32_t n_threads);
+
 /* ---- binary side-car ------------------------------------------------------------
  * split_<contig>_<tint>.fsc, written next to the TSVs that py/freddie_split.py:445-481 produces, holds the parsed
  * form of both files (flat exon / CIGAR arrays, the read_reps grouping of py/freddie_segment.py:165-170, sequences

@@ -141,7 +141,62 @@ int fseg_results_packed(fseg_ctx *ctx, const int64_t **part_final_off, const int
  * n_part+1 entries.  Any pointer may be NULL to skip that array. */
 int fseg_download(fseg_ctx *ctx, int64_t *part_final_off, int32_t *final_pos, int64_t *label_off, uint8_t *labels);
 
-/* Debug taps: intermediates of the last run, for parity tests.  `what` selects the array;
+/* ---- per-read annotation on the device: unaligned gaps, soft clips and poly tails --------------------------------------
+ * get_unaligned_gaps_and_polyA() and helpers (py/freddie_segment.py:289-472) for every READ of the resident batch.  The reads of
+ * a rep share its (ts, te) exons and its label row; what differs per read is given here (all host pointers):
+ *   read r belongs to partition read_part[r] and to rep read_rep[r] (index INSIDE the partition), has strand[r] ('+' / '-') and a
+ *   sequence of seq_len[r] letters at letters seq_off[r] .. of seq_classes (seq_off has n_read + 1 ascending entries, seq_off[0] = 0);
+ *   its exons' query coordinates and interval CIGARs are qs / qe / cig_off[x] .. cig_off[x + 1] for x in read_q_off[r] ..
+ *   read_q_off[r + 1]: one entry per exon of the read's rep, in the rep's order (read_q_off: n_read + 1 entries from 0; cig_off: one
+ *   more entry than qs); CIGAR op k is cig_len[k] times the letter cig_op[k];
+ *   seq_classes holds two-bit class codes, 16 to a 32-bit word (letter g = bits 2(g & 15).. of word g >> 4): 0 'A', 1 'T', 2 any
+ *   other byte -- the poly search only ever asks "is it A" / "is it T" (:355-360). */
+typedef struct {
+    int64_t n_read;
+    const int32_t *read_part;
+    const int32_t *read_rep;
+    const uint8_t *strand;
+    const int32_t *seq_len;
+    const int64_t *seq_off;
+    const int64_t *read_q_off;
+    const int32_t *qs;
+    const int32_t *qe;
+    const int64_t *cig_off;
+    const uint8_t *cig_op;
+    const int32_t *cig_len;
+    const uint32_t *seq_classes;
+} fseg_reads;
+
+/* The annotation, per read, in the layouts of fhost_segments (include/freddie_host.h) field for field: CSR offsets have
+ * n_read + 1 entries.  A read's gaps ascend by j1 and its key tokens follow them, then its poly entries (E keys before S keys);
+ * its clips are ESC, then SSC -- the order of a segment TSV line, except that a line has its gap tokens in string order.
+ * A read without a label 1 has no entries at all (:372-373). */
+typedef struct {
+    int64_t n_read;
+    const int64_t *gap_off;
+    const int32_t *gaps;       /* (j1, j2, len) */
+    const int64_t *clip_off;
+    const int32_t *clips;      /* (0 SSC | 1 ESC, len) */
+    const int64_t *poly_off;
+    const int32_t *polys;      /* (0 SA | 1 ST | 2 EA | 3 ET, len, gap) */
+    const uint8_t *tail;       /* 0 N | 1 S | 2 E */
+    const int64_t *tok_off;
+    const uint32_t *tok;
+} fseg_annot;
+
+/* Annotate the reads.  With the four trailing pointers NULL: against the final positions and labels of the context's last
+ * fseg_run.  With them given (fseg_results_packed's layout: label g = bits 2(g & 3).. of labels2[g >> 2]): against those, for the
+ * resident batch's reps -- a caller that kept only the packed results, or a test that drives label rows no segmentation makes.
+ * Runs on the context's own stream and waits for it; the pinned buffers of fseg_results* are not touched.
+ * FSEG_ERR_ARG names the read whose arrays are inconsistent (offsets that do not ascend, a rep beyond its partition, a
+ * read_q_off span that is not the rep's exon count, a strand other than '+' / '-').  A read on which the reference would assert
+ * is FSEG_ERR_INPUT: the message names the smallest such read, its partition and the reference line; the context stays usable. */
+int32_t fseg_annotate(fseg_ctx *ctx, const fseg_reads *reads, const int64_t *label_off, const uint8_t *labels2,
+                      const int64_t *part_final_off, const int32_t *final_pos);
+/* Pointers into pinned buffers of the context, valid until its next fseg_annotate / fseg_destroy. */
+int32_t fseg_annotation(fseg_ctx *ctx, fseg_annot *out);
+
+/* Debug taps: intermediates of the last run, for parity tests. `what` selects the array;
  * dst receives up to cap_bytes; *n_bytes is set to the full size in bytes. */
 enum {
     FSEG_TAP_POS_OFF = 1,     /* int64[K+1]   offsets of each interval's positions                         */
