@@ -15,7 +15,8 @@
 // The file, in order:  1. the kernels, stage by stage
 //   2. Buf<T> (typed, owning, growing memory) and fclu_ctx, whose buffers free themselves
 //   3. helpers: fail / HIP_TRY, the test knobs (read_knobs, once a call), run_burst, fetch
-//   4. the stages: stage_tints, compat_run; part_* behind partition_device; prep_* behind preprocess_device
+//   4. the stages: stage_tints, compat_run; part_* behind partition_device; the dedupe, once (describe_rows, dedupe_classes,
+//      dedupe_members, report_row_errors) for prep_* behind preprocess_device and for group_device; round_* behind round_device
 //   5. the C ABI, one extern "C" block
 #include "freddie_cluster.h"
 
@@ -627,7 +628,7 @@ __global__ void __launch_bounds__(256) k_offsets(i64 n_rows_total, int n_tint, c
 // with the same structure (:203-215), from label rows at two bits a label (fclu_reads).
 // ================================================================================================================
 struct PrepTint {
-    i64 rep0, lab_off, rbits_off, slot0;   // first rep; first label word; first word of the reps' I / C rows; first lane slot of k_rows
+    i64 item0, lab_off, rbits_off, slot0;  // first rep; first label word; first word of the reps' I / C rows; first lane slot of k_rows
     int n, n_seg, lw, w, g_log2;            // reps, segments, label words and bit words per row, log2 of the lanes a rep gets
 };
 
@@ -672,7 +673,7 @@ __global__ void __launch_bounds__(256) k_rows(int n_tint, i64 n_slots, const Pre
         const int g = 1 << d.g_log2, sub = lane & (g - 1);
         const i64 r = (s0 - d.slot0 + lane) >> d.g_log2;
         const bool ok = r < d.n;
-        const i64 rep = d.rep0 + (ok ? r : 0);
+        const i64 rep = d.item0 + (ok ? r : 0);
         const unsigned *lab = labels + d.lab_off + (ok ? r : 0) * d.lw;
         unsigned *ib = ibits + d.rbits_off + (ok ? r : 0) * d.w, *cb = cbits + d.rbits_off + (ok ? r : 0) * d.w;
         int fmin = 0x7fffffff, lmax = -1, bad = 0;
@@ -732,13 +733,13 @@ __global__ void __launch_bounds__(256) k_leader(i64 n, const u64 *skey, const in
     for (i64 k = (i64)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += (i64)gridDim.x * blockDim.x) {
         const PrepTint d = pt[(int)(skey[k] >> 32)];
         const int rep = sval[k];
-        const unsigned *a = ibits + d.rbits_off + (i64)(rep - d.rep0) * d.w;
+        const unsigned *a = ibits + d.rbits_off + (i64)(rep - d.item0) * d.w;
         const int fa = first[rep], la = last[rep], ta = tail[rep];
         int lead = rep;
         for (i64 j = bstart[k]; j < k; ++j) {
             const int other = sval[j];
             if (first[other] != fa || last[other] != la || tail[other] != ta) continue;
-            const unsigned *b = ibits + d.rbits_off + (i64)(other - d.rep0) * d.w;
+            const unsigned *b = ibits + d.rbits_off + (i64)(other - d.item0) * d.w;
             bool same = true;
             for (int w = 0; w < d.w; ++w) if (a[w] != b[w]) { same = false; break; }
             if (same) { lead = other; break; }
@@ -748,10 +749,12 @@ __global__ void __launch_bounds__(256) k_leader(i64 n, const u64 *skey, const in
     }
 }
 
-// row_off[t] = the number of leaders in front of tint t's first rep (node_id: the exclusive scan of flag, n_reps + 1 entries)
-__global__ void __launch_bounds__(256) k_row_off(int n_tint, i64 n_reps, const PrepTint *pt, const int *node_id, i64 *row_off) {
+// off[t] = the number of leaders in front of tint t's first item (id: the exclusive scan of flag, n_items + 1 entries): the tints' row_off
+// behind the reps' dedupe (D = PrepTint), their rep_off behind the reads' grouping (D = GroupTint)
+template <typename D>
+__global__ void __launch_bounds__(256) k_class_off(int n_tint, i64 n_items, const D *tints, const int *id, i64 *off) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t <= n_tint) row_off[t] = node_id[t < n_tint ? pt[t].rep0 : n_reps];
+    if (t <= n_tint) off[t] = id[t < n_tint ? tints[t].item0 : n_items];
 }
 
 // Nodes are numbered by their smallest rep (the leader): the leaders' scan IS the numbering.  A rep learns its node; a leader hands
@@ -767,11 +770,11 @@ __global__ void __launch_bounds__(256) k_nodes(i64 n_reps, const int *rep_tint, 
         const int lead = leader[rep], node = node_id[lead];
         rep_node[rep] = node - (int)d.row0;
         nkey[rep] = (unsigned)node;
-        nval[rep] = (int)(rep - p.rep0);
+        nval[rep] = (int)(rep - p.item0);
         if (lead == rep) {
-            node_rep[node] = (int)(rep - p.rep0);
+            node_rep[node] = (int)(rep - p.item0);
             nfirst[node] = first[rep]; nlast[node] = last[rep]; ntail[node] = tail[rep];
-            const unsigned *src = ibits + p.rbits_off + (rep - p.rep0) * p.w;
+            const unsigned *src = ibits + p.rbits_off + (rep - p.item0) * p.w;
             unsigned *dst = bits + d.bits_off + (i64)(node - d.row0) * d.w;
             for (int w = 0; w < p.w; ++w) dst[w] = src[w];
         }
@@ -792,7 +795,7 @@ __global__ void __launch_bounds__(256) k_mem_off(i64 n_reps, i64 n_rows, const u
 // their token streams are equal; the dedupe's shape: hash, stable sort by (tint, hash), leaders on whole rows, scan, members.
 // ================================================================================================================
 struct GroupTint {
-    i64 read0, lab_off, slot0;              // first read; first label word; first lane slot of k_gkeys
+    i64 item0, lab_off, slot0;              // first read; first label word; first lane slot of k_gkeys
     int n, n_seg, lw, g_log2, vec;          // reads, segments, label words a row, log2 of the lanes a read gets, rows are whole 16-byte quads
 };
 
@@ -826,7 +829,7 @@ __global__ void __launch_bounds__(256) k_gkeys(int n_tint, i64 n_slots, const Gr
         const int g = 1 << d.g_log2, sub = lane & (g - 1);
         const i64 r = (s0 - d.slot0 + lane) >> d.g_log2;
         const bool ok = r < d.n;
-        const i64 read = d.read0 + (ok ? r : 0);
+        const i64 read = d.item0 + (ok ? r : 0);
         const unsigned *lab = labels + d.lab_off + (ok ? r : 0) * d.lw;
         int bad = 0;
         unsigned h = 0;
@@ -866,12 +869,12 @@ __global__ void __launch_bounds__(256) k_gleader(i64 n, const u64 *skey, const i
     for (i64 k = (i64)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += (i64)gridDim.x * blockDim.x) {
         const GroupTint d = gt[(int)(skey[k] >> 32)];
         const int read = sval[k];
-        const unsigned *a = labels + d.lab_off + (i64)(read - d.read0) * d.lw;
+        const unsigned *a = labels + d.lab_off + (i64)(read - d.item0) * d.lw;
         const i64 ta = tok_off[read], na = tok_off[read + 1] - ta;
         int lead = read;
         for (i64 j = bstart[k]; j < k; ++j) {
             const int other = sval[j];
-            const unsigned *b = labels + d.lab_off + (i64)(other - d.read0) * d.lw;
+            const unsigned *b = labels + d.lab_off + (i64)(other - d.item0) * d.lw;
             const i64 tb = tok_off[other], nb = tok_off[other + 1] - tb;
             bool same = true;
             for (int w = 0; w < d.lw; ++w) if (i_spread(a[w]) != i_spread(b[w])) { same = false; break; }
@@ -888,12 +891,6 @@ __global__ void __launch_bounds__(256) k_gleader(i64 n, const u64 *skey, const i
     }
 }
 
-// rep_off[t] = the number of leaders in front of tint t's first read (rep_id: the exclusive scan of flag, n_reads + 1 entries)
-__global__ void __launch_bounds__(256) k_grep_off(int n_tint, i64 n_reads, const GroupTint *gt, const int *rep_id, i64 *rep_off) {
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t <= n_tint) rep_off[t] = rep_id[t < n_tint ? gt[t].read0 : n_reads];
-}
-
 // Reps are numbered by their first read (the leader): the leaders' scan IS the numbering (Python's dict insertion order, :162-164).
 // A read learns its rep; a leader is its rep's first read.  nkey / nval: the second sort's input (rep of the batch, read of the tint).
 __global__ void __launch_bounds__(256) k_greps(i64 n_reads, const int *read_tint, const GroupTint *gt, const int *leader, const int *rep_id,
@@ -901,10 +898,10 @@ __global__ void __launch_bounds__(256) k_greps(i64 n_reads, const int *read_tint
     for (i64 read = (i64)blockIdx.x * blockDim.x + threadIdx.x; read < n_reads; read += (i64)gridDim.x * blockDim.x) {
         const GroupTint d = gt[read_tint[read]];
         const int lead = leader[read], rep = rep_id[lead];
-        read_rep[read] = rep - rep_id[d.read0];
+        read_rep[read] = rep - rep_id[d.item0];
         nkey[read] = (unsigned)rep;
-        nval[read] = (int)(read - d.read0);
-        if (lead == read) rep_first[rep] = (int)(read - d.read0);
+        nval[read] = (int)(read - d.item0);
+        if (lead == read) rep_first[rep] = (int)(read - d.item0);
     }
 }
 
@@ -921,7 +918,7 @@ __global__ void __launch_bounds__(256) k_ggather(int n_tint, i64 n_words, const 
         const int w = (int)(y - r * d.lw);
         const i64 rep = rep_off[lo] + r, first = rep_first[rep];
         rep_labels[x] = labels[d.lab_off + first * d.lw + w];
-        if (w == 0) rep_tail[rep] = tail[d.read0 + first];
+        if (w == 0) rep_tail[rep] = tail[d.item0 + first];
     }
 }
 
@@ -1228,7 +1225,9 @@ constexpr int kBurst = 4;     // gated passes (pruning, components) enqueued per
 struct fclu_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
-    hipEvent_t ev[3] = {};
+    // every event, one list to create and destroy; by stage: the graph (ev), fclu_partition (pev), _preprocess (qev), _group_reads (gev), _round_models (rev)
+    hipEvent_t events[3 + 6 + 6 + 5 + 5] = {};
+    hipEvent_t *const ev = events, *const pev = ev + 3, *const qev = pev + 6, *const gev = qev + 6, *const rev = gev + 5;
     std::string err;
     float compat_ms = 0.f, prune_ms = 0.f;
     Buf<TintDesc> tints; Buf<int4> tiles; Buf<int2> word_tint; Buf<i64> tint_word0;
@@ -1239,7 +1238,6 @@ struct fclu_ctx {
     // fclu_partition(): the batch the last graph call left on the device, work arrays, results (pinned, context-owned)
     std::vector<TintDesc> h_tints;
     int adj_cur = 0;
-    hipEvent_t pev[6] = {};
     float components_ms = 0.f, pairs_ms = 0.f;
     Buf<int> parent, rows, sval, comp_start, comp_end, chunk_end, d_label, d_nodes, mem, d_part_rids;
     Buf<i64> head, part_id, smult, rid_pos, cnt, pair_base, d_tint_part_off, d_part_node_off, d_part_rid_off, d_part_pair_off, mem_off;
@@ -1249,31 +1247,39 @@ struct fclu_ctx {
     HostBuf<int32_t> h_part_nodes, h_part_rids, h_label; HostBuf<int2> h_pairs;
     fclu_parts parts = {};
     bool have_parts = false;
+    // The dedupe's scratch, one set for both of its users (the reps' dedupe of fclu_preprocess, the reads' grouping of fclu_group_reads):
+    // the keys and their sort, the buckets' heads and starts, the leaders, their scan (id: the class numbering, n + 1 entries), the second
+    // sort's input, rocPRIM's temporary storage, and the three refusal words with their pinned copy.  What makes the sharing sound: a
+    // stage's use of it ends before that stage returns (dedupe_classes .. dedupe_members, on the one stream), and nothing in it is a result
+    // or a round's source -- those are the stages' own (pd / gd, c->mem / c->mem_off; pd.ibits, pd.cbits and d_pairs feed the rounds).
+    struct Dedupe {
+        Buf<u64> key, skey; Buf<unsigned> nkey, snkey; Buf<char> tmp;
+        Buf<int> val, sval, head, bstart, leader, flag, id, nval, err;
+        HostBuf<int> h_err;
+    } dd;
     // fclu_preprocess() / fclu_partition_reads(): device arrays (pd) and the pinned copies fclu_preprocess_results() hands out (ph)
     struct {
-        Buf<PrepTint> tints; Buf<unsigned char> tail; Buf<u64> key, skey; Buf<i64> row_off; Buf<char> tmp;
-        Buf<unsigned> labels, ibits, cbits, nkey, snkey;
-        Buf<int> rfirst, rlast, first, last, rep_tint, val, sval, head, bstart, leader, flag, node_id, rep_node, node_rep, nval, err;
+        Buf<PrepTint> tints; Buf<unsigned char> tail; Buf<i64> row_off;
+        Buf<unsigned> labels, ibits, cbits;
+        Buf<int> rfirst, rlast, first, last, rep_tint, rep_node, node_rep;
     } pd;
     struct {
         HostBuf<int64_t> row_off, bits_off, adj_off, rbits_off, mem_off;
-        HostBuf<uint32_t> ibits, cbits, bits; HostBuf<uint8_t> ntail; HostBuf<int> err;
+        HostBuf<uint32_t> ibits, cbits, bits; HostBuf<uint8_t> ntail;
         HostBuf<int32_t> first, last, rfirst, rlast, rep_node, node_rep, mem, nfirst, nlast;
     } ph;
-    hipEvent_t qev[6] = {};
     float rows_ms = 0.f, dedupe_ms = 0.f;
     fclu_prep prep = {};
     bool have_prep = false;
     // fclu_group_reads() / fclu_partition_segment(): device arrays (gd) and the pinned copies fclu_group_results() hands out (gh)
     struct {
-        Buf<GroupTint> tints; Buf<unsigned char> tail; Buf<u64> key, skey; Buf<i64> tok_off, rep_off, rep_lab_off, mem_off; Buf<char> tmp;
-        Buf<unsigned> labels, tok, nkey, snkey;
-        Buf<int> read_tint, val, sval, head, bstart, leader, flag, rep_id, read_rep, nval, mem, rep_first, err;
+        Buf<GroupTint> tints; Buf<unsigned char> tail; Buf<i64> tok_off, rep_off, rep_lab_off, mem_off;
+        Buf<unsigned> labels, tok;
+        Buf<int> read_tint, read_rep, mem, rep_first;
     } gd;
     struct {
-        HostBuf<int64_t> rep_off, rep_lab_off, mem_off; HostBuf<int32_t> read_rep, mem, rep_first; HostBuf<int> err;
+        HostBuf<int64_t> rep_off, rep_lab_off, mem_off; HostBuf<int32_t> read_rep, mem, rep_first;
     } gh;
-    hipEvent_t gev[5] = {};
     float gkeys_ms = 0.f, gdedupe_ms = 0.f;
     fclu_groups groups = {};
     bool have_groups = false;
@@ -1294,7 +1300,6 @@ struct fclu_ctx {
     std::vector<int32_t> r_n_seg, r_part_tint, r_rep_stamp, r_part_stamp;
     int r_epoch = 0;
     bool round_src_ok = false, round_ready = false;
-    hipEvent_t rev[5] = {};
     float rcount_ms = 0.f, rgaps_ms = 0.f, rfill_ms = 0.f;
     fclu_rounds rounds = {};
     bool have_rounds = false;
@@ -1302,11 +1307,7 @@ struct fclu_ctx {
     ~fclu_ctx() {
         (void)hipSetDevice(device);
         if (stream) { (void)hipStreamSynchronize(stream); (void)hipStreamDestroy(stream); }
-        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-        for (hipEvent_t e : pev) if (e) (void)hipEventDestroy(e);
-        for (hipEvent_t e : qev) if (e) (void)hipEventDestroy(e);
-        for (hipEvent_t e : gev) if (e) (void)hipEventDestroy(e);
-        for (hipEvent_t e : rev) if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : events) if (e) (void)hipEventDestroy(e);
     }
 };
 
@@ -1803,6 +1804,127 @@ int partition_device(fclu_ctx *c, int T, i64 R, const int64_t *mem_off, const in
     return FCLU_OK;
 }
 
+// ---- the dedupe, once for its two users: reps -> nodes (prep_rows, prep_nodes) and reads -> reps (group_device) ----------------
+// An item is a rep there and a read here, a class a node and a rep.  The scratch is c->dd (see fclu_ctx).
+int item_grid(i64 n) { return (int)std::min<i64>((n + 255) / 256, 4096); }
+
+// rocPRIM's stable sort of (key, value) pairs by the keys' low bits, tmp its temporary storage; need: no sort, only what it takes of tmp
+template <typename K>
+int sort_pairs(fclu_ctx *c, Buf<char> &tmp, size_t *need, K *key, K *skey, int *val, int *sval, size_t n, unsigned bits) {
+    size_t tb = tmp.cap;
+    HIP_TRY(c, rocprim::radix_sort_pairs(need ? nullptr : (void *)tmp.p, need ? *need : tb, key, skey, val, sval, n, 0u, bits, c->stream));
+    return FCLU_OK;
+}
+
+// the two times of a stage from its five events: the key kernel; the dedupe in front of and behind the stage's synchronisation
+void stage_times(hipEvent_t *e, float &keys_ms, float &dedupe_ms) {
+    float a = 0.f, b = 0.f;
+    (void)hipEventElapsedTime(&keys_ms, e[0], e[1]);
+    (void)hipEventElapsedTime(&a, e[1], e[2]);
+    (void)hipEventElapsedTime(&b, e[3], e[4]);
+    dedupe_ms = a + b;
+}
+
+// The tints' descriptors from the batch's offsets, with the offsets' and the shapes' refusals: what PrepTint and GroupTint share.  lane_units(d): the caller's
+// own fields of d, and the number of units a row's lanes share out (g_log2: the smallest power of two that holds them, 64 at the most).
+// n_slots: the lane slots of the key kernel, every tint's starting at a multiple of 64.
+template <typename D, typename U>
+int describe_rows(fclu_ctx *c, const char *entry, const char *noun, int T, const int64_t *item_off, const int32_t *n_seg, const int64_t *lab_off,
+                  U &&lane_units, std::vector<D> &tints, i64 &n_slots) {
+    if (!item_off || !n_seg || !lab_off) return fail(c, FCLU_ERR_ARG, "%s: %s_off, n_seg or lab_off is null", entry, noun);
+    if (item_off[0] != 0 || lab_off[0] != 0) return fail(c, FCLU_ERR_ARG, "%s: %s_off and lab_off start at 0", entry, noun);
+    tints.assign((size_t)T, D());
+    n_slots = 0;
+    for (int t = 0; t < T; ++t) {
+        D &d = tints[(size_t)t];
+        const i64 n = item_off[t + 1] - item_off[t];
+        if (n < 0 || n > (1 << 30) || n_seg[t] < 0)
+            return fail(c, FCLU_ERR_ARG, "tint %d: negative or too large %s count (%lld) or segment count (%d)", t, noun, n, (int)n_seg[t]);
+        if (n_seg[t] > kMaxWords * 32)
+            return fail(c, FCLU_ERR_UNSUPPORTED, "tint %d has %d segments; this build stages at most %d", t, (int)n_seg[t], kMaxWords * 32);
+        d.item0 = item_off[t]; d.lab_off = lab_off[t]; d.slot0 = n_slots;
+        d.n = (int)n; d.n_seg = n_seg[t]; d.lw = std::max((d.n_seg + 15) / 16, 1);
+        const int units = lane_units(d);
+        d.g_log2 = 0; while (d.g_log2 < 6 && (1 << d.g_log2) < units) ++d.g_log2;
+        if (lab_off[t + 1] - d.lab_off != n * d.lw)
+            return fail(c, FCLU_ERR_ARG, "tint %d: lab_off does not match %ss x words (%lld words for %lld %ss of %d)", t, noun,
+                        (i64)(lab_off[t + 1] - d.lab_off), n, noun, d.lw);
+        n_slots += ((n << d.g_log2) + 63) / 64 * 64;
+    }
+    if (item_off[T] >= 0x7f7f7f7fll) return fail(c, FCLU_ERR_ARG, "%s: %lld %ss in one batch", entry, (i64)item_off[T], noun);
+    return FCLU_OK;
+}
+
+// From the key kernel to the tints' class counts, with the stage's one synchronisation at its end.  The callables launch the caller's
+// kernels (as run_burst's does): launch_keys fills dd.key (tint, hash), dd.val (the item) and dd.err[0..2] (the smallest refused item);
+// launch_leader dd.leader and dd.flag; launch_offsets runs k_class_off into d_off (T + 1 entries, h_off on the host) and whatever else of
+// the caller's needs no count from the host.  ev[0], ev[1]: around the key kernel; ev[2]: behind launch_offsets.  dd.id = the exclusive
+// scan of flag is the classes' numbering (N + 1 entries); behind the call, report_row_errors() says what dd.h_err holds.
+template <typename K, typename L, typename O>
+int dedupe_classes(fclu_ctx *c, int T, i64 N, hipEvent_t *ev, K &&launch_keys, L &&launch_leader, O &&launch_offsets, const i64 *d_off, int64_t *h_off) {
+    hipStream_t s = c->stream;
+    auto &D = c->dd;
+    const size_t n = (size_t)N, N1 = n + 1;
+    for (Buf<int> *b : {&D.val, &D.sval, &D.head, &D.bstart, &D.leader, &D.nval}) HIP_TRY(c, b->grow(n));
+    HIP_TRY(c, D.key.grow(n)); HIP_TRY(c, D.skey.grow(n)); HIP_TRY(c, D.nkey.grow(n)); HIP_TRY(c, D.snkey.grow(n));
+    HIP_TRY(c, D.flag.grow(N1)); HIP_TRY(c, D.id.grow(N1)); HIP_TRY(c, D.err.grow(4)); HIP_TRY(c, D.h_err.grow(4));
+    const unsigned key_bits = 32u + (unsigned)bits_for(T);
+    size_t sort_a = 0, sort_b = 0, scan_a = 0, scan_b = 0;                 // (sort_b: dedupe_members' sort, whose values go to the caller's array)
+    RC_TRY(sort_pairs(c, D.tmp, &sort_a, D.key.p, D.skey.p, D.val.p, D.sval.p, n, key_bits));
+    RC_TRY(sort_pairs(c, D.tmp, &sort_b, D.nkey.p, D.snkey.p, D.nval.p, D.sval.p, n, (unsigned)bits_for(N)));
+    HIP_TRY(c, rocprim::inclusive_scan(nullptr, scan_a, D.head.p, D.bstart.p, n, rocprim::maximum<int>(), s));
+    HIP_TRY(c, rocprim::exclusive_scan(nullptr, scan_b, D.flag.p, D.id.p, 0, N1, rocprim::plus<int>(), s));
+    HIP_TRY(c, D.tmp.grow(std::max(std::max(sort_a, sort_b), std::max(scan_a, scan_b))));
+    HIP_TRY(c, hipMemsetAsync(D.err.p, 0x7f, D.err.bytes(4), s));
+    HIP_TRY(c, hipMemsetAsync(D.flag.p + N, 0, D.flag.bytes(1), s));
+    HIP_TRY(c, hipEventRecord(ev[0], s));
+    launch_keys();
+    HIP_TRY(c, hipEventRecord(ev[1], s));
+    // refusals first: a tail above 2 or a label 3 has no meaning, and the sort's keys of such a batch are not needed
+    HIP_TRY(c, hipMemcpyAsync(D.h_err.p, D.err.p, D.err.bytes(4), hipMemcpyDeviceToHost, s));
+    RC_TRY(sort_pairs(c, D.tmp, nullptr, D.key.p, D.skey.p, D.val.p, D.sval.p, n, key_bits));
+    hipLaunchKernelGGL(k_heads, dim3(item_grid(N)), dim3(256), 0, s, N, D.skey.p, D.head.p);
+    size_t tb = D.tmp.cap;
+    HIP_TRY(c, rocprim::inclusive_scan(D.tmp.p, tb, D.head.p, D.bstart.p, n, rocprim::maximum<int>(), s));
+    launch_leader();
+    tb = D.tmp.cap;
+    HIP_TRY(c, rocprim::exclusive_scan(D.tmp.p, tb, D.flag.p, D.id.p, 0, N1, rocprim::plus<int>(), s));
+    launch_offsets();
+    HIP_TRY(c, hipEventRecord(ev[2], s));
+    HIP_TRY(c, hipMemcpyAsync(h_off, d_off, sizeof(i64) * ((size_t)T + 1), hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    HIP_TRY(c, hipGetLastError());
+    return FCLU_OK;
+}
+
+// The classes' member lists, behind the caller's numbering kernel (dd.nkey: an item's class, dd.nval: the item within its tint): the items
+// sorted (stable) by class are the lists end to end, each ascending (mem); class q's starts where its key first stands (mem_off).
+int dedupe_members(fclu_ctx *c, i64 N, i64 n_classes, int *mem, i64 *mem_off) {
+    auto &D = c->dd;
+    RC_TRY(sort_pairs(c, D.tmp, nullptr, D.nkey.p, D.snkey.p, D.nval.p, mem, (size_t)N, (unsigned)bits_for(N)));
+    hipLaunchKernelGGL(k_mem_off, dim3(item_grid(N + 1)), dim3(256), 0, c->stream, N, n_classes, D.snkey.p, mem_off);      // (k <= N)
+    return FCLU_OK;
+}
+
+// What the key kernel refused (dd.h_err, behind dedupe_classes): the smallest item with a tail category above 2, with a label 3, with a
+// bit behind its tint's labels.  tail: the caller's bytes, or null when they are not on the host (the grouping has refused such a tail
+// already; no number to print).
+int report_row_errors(fclu_ctx *c, const char *noun, int T, const int64_t *item_off, const int32_t *n_seg, const uint8_t *tail) {
+    const int kinds[3] = {2, 0, 1};                          // the tail first: it is the caller's own byte, the labels come from a file
+    for (int kind : kinds) {
+        const i64 item = c->dd.h_err.p[kind];
+        if (item == 0x7f7f7f7f) continue;
+        int t = 0;
+        while (t + 1 < T && item_off[t + 1] <= item) ++t;
+        const i64 r = item - item_off[t];
+        if (kind == 2 && !tail) return fail(c, FCLU_ERR_ARG, "tint %d %s %lld: tail category above 2 (0 'N', 1 'S', 2 'E')", t, noun, r);
+        if (kind == 2) return fail(c, FCLU_ERR_ARG, "tint %d %s %lld: tail category %d (0 'N', 1 'S', 2 'E')", t, noun, r, (int)tail[item]);
+        if (kind == 0) return fail(c, FCLU_ERR_ARG, "tint %d %s %lld: a label with code 3 (labels are 0, 1, 2)", t, noun, r);
+        return fail(c, FCLU_ERR_ARG, "tint %d %s %lld: a nonzero bit beyond the tint's %d labels", t, noun, r, (int)n_seg[t]);
+    }
+    return FCLU_OK;
+}
+
 // ---- preprocess_ilp() + the dedupe of a batch of label rows ----------------------------------------------------------
 // what the two halves share
 struct PrepRun {
@@ -1816,100 +1938,45 @@ struct PrepRun {
 // on_device: the rows and tails are in c->pd.labels / c->pd.tail already, where the grouping gathered them (group_device), checked there.
 int prep_rows(fclu_ctx *c, const Knobs &k, const fclu_reads *rd, bool on_device, PrepRun &p) {
     if (!rd || rd->n_tint <= 0) return fail(c, FCLU_ERR_ARG, "fclu_preprocess: empty batch");
-    if (!rd->rep_off || !rd->n_seg || !rd->lab_off) return fail(c, FCLU_ERR_ARG, "fclu_preprocess: rep_off, n_seg or lab_off is null");
     HIP_TRY(c, hipSetDevice(c->device));
     const int T = p.T = rd->n_tint;
-    if (rd->rep_off[0] != 0 || rd->lab_off[0] != 0) return fail(c, FCLU_ERR_ARG, "fclu_preprocess: rep_off and lab_off start at 0");
     auto &D = c->pd;
     auto &H = c->ph;
     for (HostBuf<int64_t> *h : {&H.row_off, &H.bits_off, &H.adj_off, &H.rbits_off}) HIP_TRY(c, h->grow((size_t)T + 1));
-    HIP_TRY(c, H.err.grow(4));
-    p.pt.assign((size_t)T, PrepTint());
     i64 n_slots = 0;
-    H.rbits_off.p[0] = 0;
-    for (int t = 0; t < T; ++t) {
-        PrepTint &d = p.pt[(size_t)t];
-        const i64 n = rd->rep_off[t + 1] - rd->rep_off[t];
-        if (n < 0 || n > (1 << 30) || rd->n_seg[t] < 0)
-            return fail(c, FCLU_ERR_ARG, "tint %d: negative or too large rep count (%lld) or segment count (%d)", t, n, (int)rd->n_seg[t]);
-        if (rd->n_seg[t] > kMaxWords * 32)
-            return fail(c, FCLU_ERR_UNSUPPORTED, "tint %d has %d segments; this build stages at most %d", t, (int)rd->n_seg[t], kMaxWords * 32);
-        d.rep0 = rd->rep_off[t]; d.lab_off = rd->lab_off[t]; d.rbits_off = H.rbits_off.p[t]; d.slot0 = n_slots;
-        d.n = (int)n; d.n_seg = rd->n_seg[t];
-        d.lw = std::max((d.n_seg + 15) / 16, 1); d.w = std::max((d.n_seg + 31) / 32, 1);
-        d.g_log2 = 0; while (d.g_log2 < 6 && (1 << d.g_log2) < d.w) ++d.g_log2;
-        if (rd->lab_off[t + 1] - d.lab_off != n * d.lw)
-            return fail(c, FCLU_ERR_ARG, "tint %d: lab_off does not match reps x words (%lld words for %lld reps of %d)", t,
-                        (i64)(rd->lab_off[t + 1] - d.lab_off), n, d.lw);
-        H.rbits_off.p[t + 1] = d.rbits_off + n * d.w;
-        n_slots += ((n << d.g_log2) + 63) / 64 * 64;
-    }
+    const auto words = [](PrepTint &d) { return d.w = std::max((d.n_seg + 31) / 32, 1); };                // a lane a bit word
+    RC_TRY(describe_rows(c, "fclu_preprocess", "rep", T, rd->rep_off, rd->n_seg, rd->lab_off, words, p.pt, n_slots));
+    H.rbits_off.p[0] = 0;                                    // the reps' I / C rows end to end
+    for (int t = 0; t < T; ++t) { PrepTint &d = p.pt[(size_t)t]; d.rbits_off = H.rbits_off.p[t]; H.rbits_off.p[t + 1] = d.rbits_off + (i64)d.n * d.w; }
     const i64 N = p.N = rd->rep_off[T], n_lab = rd->lab_off[T];
     p.n_rbits = H.rbits_off.p[T];
-    if (N >= 0x7f7f7f7fll) return fail(c, FCLU_ERR_ARG, "fclu_preprocess: %lld reps in one batch", N);
     if (N > 0 && !on_device && (!rd->labels || !rd->tail)) return fail(c, FCLU_ERR_ARG, "fclu_preprocess: labels or tail is null");
     int64_t *h_row_off = H.row_off.p;
     if (N > 0) {
         hipStream_t s = c->stream;
-        const size_t N1 = (size_t)N + 1;
-        HIP_TRY(c, D.tints.grow((size_t)T));
+        auto &S = c->dd;
+        HIP_TRY(c, D.tints.grow((size_t)T)); HIP_TRY(c, D.row_off.grow((size_t)T + 1));
         HIP_TRY(c, D.labels.grow((size_t)n_lab)); HIP_TRY(c, D.tail.grow((size_t)N));
         HIP_TRY(c, D.ibits.grow((size_t)p.n_rbits)); HIP_TRY(c, D.cbits.grow((size_t)p.n_rbits));
-        for (Buf<int> *b : {&D.rfirst, &D.rlast, &D.first, &D.last, &D.rep_tint, &D.val, &D.sval, &D.head, &D.bstart, &D.leader, &D.rep_node, &D.node_rep, &D.nval, &c->mem})
-            HIP_TRY(c, b->grow((size_t)N));
-        HIP_TRY(c, D.nkey.grow((size_t)N)); HIP_TRY(c, D.snkey.grow((size_t)N));
-        HIP_TRY(c, D.flag.grow(N1)); HIP_TRY(c, D.node_id.grow(N1));
-        HIP_TRY(c, D.key.grow((size_t)N)); HIP_TRY(c, D.skey.grow((size_t)N));
-        HIP_TRY(c, D.row_off.grow((size_t)T + 1)); HIP_TRY(c, D.err.grow(4));
-        const unsigned key_bits = 32u + (unsigned)bits_for(T), node_bits = (unsigned)bits_for(N);
-        size_t sort_a = 0, sort_b = 0, scan_a = 0, scan_b = 0;
-        HIP_TRY(c, rocprim::radix_sort_pairs(nullptr, sort_a, D.key.p, D.skey.p, D.val.p, D.sval.p, (size_t)N, 0u, key_bits, s));
-        HIP_TRY(c, rocprim::radix_sort_pairs(nullptr, sort_b, D.nkey.p, D.snkey.p, D.nval.p, c->mem.p, (size_t)N, 0u, node_bits, s));
-        HIP_TRY(c, rocprim::inclusive_scan(nullptr, scan_a, D.head.p, D.bstart.p, (size_t)N, rocprim::maximum<int>(), s));
-        HIP_TRY(c, rocprim::exclusive_scan(nullptr, scan_b, D.flag.p, D.node_id.p, 0, N1, rocprim::plus<int>(), s));
-        const size_t tmp_bytes = std::max(std::max(sort_a, sort_b), std::max(scan_a, scan_b));
-        HIP_TRY(c, D.tmp.grow(tmp_bytes));
+        for (Buf<int> *b : {&D.rfirst, &D.rlast, &D.first, &D.last, &D.rep_tint, &D.rep_node, &D.node_rep, &c->mem}) HIP_TRY(c, b->grow((size_t)N));
         HIP_TRY(c, hipMemcpyAsync(D.tints.p, p.pt.data(), D.tints.bytes((size_t)T), hipMemcpyHostToDevice, s));
         if (!on_device) {
             HIP_TRY(c, hipMemcpyAsync(D.labels.p, rd->labels, D.labels.bytes((size_t)n_lab), hipMemcpyHostToDevice, s));
             HIP_TRY(c, hipMemcpyAsync(D.tail.p, rd->tail, D.tail.bytes((size_t)N), hipMemcpyHostToDevice, s));
         }
-        HIP_TRY(c, hipMemsetAsync(D.err.p, 0x7f, D.err.bytes(4), s));
-        HIP_TRY(c, hipMemsetAsync(D.flag.p + N, 0, D.flag.bytes(1), s));
-        const int rep_grid = (int)std::min<i64>((N + 255) / 256, 4096);
-        HIP_TRY(c, hipEventRecord(c->qev[0], s));
-        hipLaunchKernelGGL(k_rows, dim3((unsigned)std::min<i64>((n_slots + 255) / 256, 65536)), dim3(256), 0, s, T, n_slots, D.tints.p, D.labels.p, D.tail.p,
-                           k.hash_mask, D.ibits.p, D.cbits.p, D.rfirst.p, D.rlast.p, D.first.p, D.last.p, D.rep_tint.p, D.key.p, D.val.p, D.err.p);
-        HIP_TRY(c, hipEventRecord(c->qev[1], s));
-        // refusals first: a tail above 2 or a label 3 has no meaning, and the sort's keys of such a batch are not needed
-        HIP_TRY(c, hipMemcpyAsync(H.err.p, D.err.p, D.err.bytes(4), hipMemcpyDeviceToHost, s));
-        size_t tb = tmp_bytes;
-        HIP_TRY(c, rocprim::radix_sort_pairs(D.tmp.p, tb, D.key.p, D.skey.p, D.val.p, D.sval.p, (size_t)N, 0u, key_bits, s));
-        hipLaunchKernelGGL(k_heads, dim3(rep_grid), dim3(256), 0, s, N, D.skey.p, D.head.p);
-        tb = tmp_bytes;
-        HIP_TRY(c, rocprim::inclusive_scan(D.tmp.p, tb, D.head.p, D.bstart.p, (size_t)N, rocprim::maximum<int>(), s));
-        hipLaunchKernelGGL(k_leader, dim3(rep_grid), dim3(256), 0, s, N, D.skey.p, D.sval.p, D.bstart.p, D.tints.p, D.ibits.p, D.first.p, D.last.p, D.tail.p,
-                           D.leader.p, D.flag.p);
-        tb = tmp_bytes;
-        HIP_TRY(c, rocprim::exclusive_scan(D.tmp.p, tb, D.flag.p, D.node_id.p, 0, N1, rocprim::plus<int>(), s));
-        hipLaunchKernelGGL(k_row_off, dim3((unsigned)(T + 256) / 256), dim3(256), 0, s, T, N, D.tints.p, D.node_id.p, D.row_off.p);
-        HIP_TRY(c, hipEventRecord(c->qev[2], s));
-        HIP_TRY(c, hipMemcpyAsync(h_row_off, D.row_off.p, D.row_off.bytes((size_t)T + 1), hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipStreamSynchronize(s));
-        HIP_TRY(c, hipGetLastError());
-        const int kinds[3] = {2, 0, 1};                      // the tail first: it is the caller's own byte, the labels come from a file
-        for (int kind : kinds) {
-            if (H.err.p[kind] == 0x7f7f7f7f) continue;
-            const i64 rep = H.err.p[kind];
-            int t = 0;
-            while (t + 1 < T && rd->rep_off[t + 1] <= rep) ++t;
-            const i64 r = rep - rd->rep_off[t];
-            // (on_device: the grouping has refused such a tail already, and the byte is not on the host: no number to print)
-            if (kind == 2 && on_device) return fail(c, FCLU_ERR_ARG, "tint %d rep %lld: tail category above 2 (0 'N', 1 'S', 2 'E')", t, r);
-            if (kind == 2) return fail(c, FCLU_ERR_ARG, "tint %d rep %lld: tail category %d (0 'N', 1 'S', 2 'E')", t, r, (int)rd->tail[rep]);
-            if (kind == 0) return fail(c, FCLU_ERR_ARG, "tint %d rep %lld: a label with code 3 (labels are 0, 1, 2)", t, r);
-            return fail(c, FCLU_ERR_ARG, "tint %d rep %lld: a nonzero bit beyond the tint's %d labels", t, r, (int)rd->n_seg[t]);
-        }
+        const auto keys = [&]() {
+            hipLaunchKernelGGL(k_rows, dim3((unsigned)std::min<i64>((n_slots + 255) / 256, 65536)), dim3(256), 0, s, T, n_slots, D.tints.p, D.labels.p, D.tail.p,
+                               k.hash_mask, D.ibits.p, D.cbits.p, D.rfirst.p, D.rlast.p, D.first.p, D.last.p, D.rep_tint.p, S.key.p, S.val.p, S.err.p);
+        };
+        const auto leader = [&]() {
+            hipLaunchKernelGGL(k_leader, dim3(item_grid(N)), dim3(256), 0, s, N, S.skey.p, S.sval.p, S.bstart.p, D.tints.p, D.ibits.p, D.first.p, D.last.p,
+                               D.tail.p, S.leader.p, S.flag.p);
+        };
+        const auto offsets = [&]() {
+            hipLaunchKernelGGL(k_class_off<PrepTint>, dim3((unsigned)(T + 256) / 256), dim3(256), 0, s, T, N, D.tints.p, S.id.p, D.row_off.p);
+        };
+        RC_TRY(dedupe_classes(c, T, N, c->qev, keys, leader, offsets, D.row_off.p, h_row_off));
+        RC_TRY(report_row_errors(c, "rep", T, rd->rep_off, rd->n_seg, on_device ? nullptr : rd->tail));
     } else {
         memset(h_row_off, 0, H.row_off.bytes((size_t)T + 1));
     }
@@ -1934,14 +2001,12 @@ int prep_nodes(fclu_ctx *c, const PrepRun &p) {
     const i64 N = p.N, R = p.R;
     const bool copy = N > 0;
     if (copy) {
+        auto &S = c->dd;
         HIP_TRY(c, c->mem_off.grow((size_t)R + 1));
-        const int rep_grid = (int)std::min<i64>((N + 256) / 256, 4096);
         HIP_TRY(c, hipEventRecord(c->qev[3], s));
-        hipLaunchKernelGGL(k_nodes, dim3(rep_grid), dim3(256), 0, s, N, D.rep_tint.p, D.tints.p, c->tints.p, D.leader.p, D.node_id.p, D.ibits.p, D.first.p,
-                           D.last.p, D.tail.p, D.rep_node.p, D.nkey.p, D.nval.p, D.node_rep.p, c->bits.p, c->first.p, c->last.p, c->tail.p);
-        size_t tb = D.tmp.cap;
-        HIP_TRY(c, rocprim::radix_sort_pairs(D.tmp.p, tb, D.nkey.p, D.snkey.p, D.nval.p, c->mem.p, (size_t)N, 0u, (unsigned)bits_for(N), s));
-        hipLaunchKernelGGL(k_mem_off, dim3(rep_grid), dim3(256), 0, s, N, R, D.snkey.p, c->mem_off.p);
+        hipLaunchKernelGGL(k_nodes, dim3(item_grid(N + 1)), dim3(256), 0, s, N, D.rep_tint.p, D.tints.p, c->tints.p, S.leader.p, S.id.p, D.ibits.p, D.first.p,
+                           D.last.p, D.tail.p, D.rep_node.p, S.nkey.p, S.nval.p, D.node_rep.p, c->bits.p, c->first.p, c->last.p, c->tail.p);
+        RC_TRY(dedupe_members(c, N, R, c->mem.p, c->mem_off.p));
         HIP_TRY(c, hipEventRecord(c->qev[4], s));
     }
     // the result set: {pinned buffer, device source, element count, fclu_prep's field}
@@ -1980,54 +2045,29 @@ int preprocess_device(fclu_ctx *c, const Knobs &k, const fclu_reads *rd, int32_t
 }
 
 // the kernels' times of the call that has just synchronised
-void preprocess_times(fclu_ctx *c, i64 n_reps) {
-    if (n_reps <= 0) return;
-    float a = 0.f, b = 0.f;
-    (void)hipEventElapsedTime(&c->rows_ms, c->qev[0], c->qev[1]);
-    (void)hipEventElapsedTime(&a, c->qev[1], c->qev[2]);
-    (void)hipEventElapsedTime(&b, c->qev[3], c->qev[4]);
-    c->dedupe_ms = a + b;
-}
+void preprocess_times(fclu_ctx *c, i64 n_reps) { if (n_reps > 0) stage_times(c->qev, c->rows_ms, c->dedupe_ms); }
 
 // ---- read_segment()'s rep grouping of a batch of tints (:154-164) ---------------------------------------------------------
-// Keys, the two sorts, leaders and members.  gather (fclu_partition_segment): the reps' rows and tails go into c->pd.labels / c->pd.tail
-// (fclu_reads' layout, at c->gh.rep_off / c->gh.rep_lab_off), where prep_rows() takes them without another upload; the grouping alone
-// leaves the preprocess stage's device arrays as they are.  One synchronisation in the middle: the tints' rep counts size the members'
-// offsets and decide the layout of the gathered rows.  It synchronises at its end.
+// Keys, the dedupe, the reps' numbering and members.  gather (fclu_partition_segment): the reps' rows and tails go into c->pd.labels /
+// c->pd.tail (fclu_reads' layout, at c->gh.rep_off / c->gh.rep_lab_off), where prep_rows() takes them without another upload; the grouping
+// alone leaves the preprocess stage's device arrays as they are.  One synchronisation in the middle (dedupe_classes): the tints' rep
+// counts size the members' offsets and decide the layout of the gathered rows.  It synchronises at its end: the scratch is free again.
 int group_device(fclu_ctx *c, const Knobs &k, const fclu_segment *in, bool gather, i64 &n_reps_out) {
     c->have_groups = false;
     c->round_src_ok = c->round_ready = c->have_rounds = false;
     c->gkeys_ms = c->gdedupe_ms = 0.f;
     if (!in || in->n_tint <= 0) return fail(c, FCLU_ERR_ARG, "fclu_group_reads: empty batch");
-    if (!in->read_off || !in->n_seg || !in->lab_off) return fail(c, FCLU_ERR_ARG, "fclu_group_reads: read_off, n_seg or lab_off is null");
     HIP_TRY(c, hipSetDevice(c->device));
     const int T = in->n_tint;
-    if (in->read_off[0] != 0 || in->lab_off[0] != 0) return fail(c, FCLU_ERR_ARG, "fclu_group_reads: read_off and lab_off start at 0");
     auto &D = c->gd;
     auto &H = c->gh;
-    HIP_TRY(c, H.rep_off.grow((size_t)T + 1)); HIP_TRY(c, H.rep_lab_off.grow((size_t)T + 1)); HIP_TRY(c, H.err.grow(4));
-    std::vector<GroupTint> gt((size_t)T);
+    HIP_TRY(c, H.rep_off.grow((size_t)T + 1)); HIP_TRY(c, H.rep_lab_off.grow((size_t)T + 1));
+    std::vector<GroupTint> gt;
     i64 n_slots = 0;
-    for (int t = 0; t < T; ++t) {
-        GroupTint &d = gt[(size_t)t];
-        const i64 n = in->read_off[t + 1] - in->read_off[t];
-        if (n < 0 || n > (1 << 30) || in->n_seg[t] < 0)
-            return fail(c, FCLU_ERR_ARG, "tint %d: negative or too large read count (%lld) or segment count (%d)", t, n, (int)in->n_seg[t]);
-        if (in->n_seg[t] > kMaxWords * 32)
-            return fail(c, FCLU_ERR_UNSUPPORTED, "tint %d has %d segments; this build stages at most %d", t, (int)in->n_seg[t], kMaxWords * 32);
-        d.read0 = in->read_off[t]; d.lab_off = in->lab_off[t]; d.slot0 = n_slots;
-        d.n = (int)n; d.n_seg = in->n_seg[t];
-        d.lw = std::max((d.n_seg + 15) / 16, 1);
-        d.vec = (d.lw % 4 == 0 && d.lab_off % 4 == 0) ? 1 : 0;
-        const int units = d.vec ? d.lw / 4 : d.lw;
-        d.g_log2 = 0; while (d.g_log2 < 6 && (1 << d.g_log2) < units) ++d.g_log2;
-        if (in->lab_off[t + 1] - d.lab_off != n * d.lw)
-            return fail(c, FCLU_ERR_ARG, "tint %d: lab_off does not match reads x words (%lld words for %lld reads of %d)", t,
-                        (i64)(in->lab_off[t + 1] - d.lab_off), n, d.lw);
-        n_slots += ((n << d.g_log2) + 63) / 64 * 64;
-    }
+    // a lane a 16-byte quad where every row of the tint is whole quads, else a label word
+    const auto quads = [](GroupTint &d) { d.vec = (d.lw % 4 == 0 && d.lab_off % 4 == 0) ? 1 : 0; return d.vec ? d.lw / 4 : d.lw; };
+    RC_TRY(describe_rows(c, "fclu_group_reads", "read", T, in->read_off, in->n_seg, in->lab_off, quads, gt, n_slots));
     const i64 N = in->read_off[T], n_lab = in->lab_off[T];
-    if (N >= 0x7f7f7f7fll) return fail(c, FCLU_ERR_ARG, "fclu_group_reads: %lld reads in one batch", N);
     if (N > 0 && (!in->labels || !in->tail || !in->tok_off)) return fail(c, FCLU_ERR_ARG, "fclu_group_reads: labels, tail or tok_off is null");
     i64 n_tok = 0;
     if (N > 0) {
@@ -2046,65 +2086,33 @@ int group_device(fclu_ctx *c, const Knobs &k, const fclu_segment *in, bool gathe
     fclu_groups &o = c->groups;
     if (N > 0) {
         hipStream_t s = c->stream;
+        auto &S = c->dd;
         const size_t N1 = (size_t)N + 1;
         HIP_TRY(c, D.tints.grow((size_t)T)); HIP_TRY(c, D.labels.grow((size_t)n_lab)); HIP_TRY(c, D.tail.grow((size_t)N));
         HIP_TRY(c, D.tok_off.grow(N1)); HIP_TRY(c, D.tok.grow((size_t)std::max<i64>(n_tok, 1)));
-        for (Buf<int> *b : {&D.read_tint, &D.val, &D.sval, &D.head, &D.bstart, &D.leader, &D.read_rep, &D.nval, &D.mem, &D.rep_first}) HIP_TRY(c, b->grow((size_t)N));
-        HIP_TRY(c, D.nkey.grow((size_t)N)); HIP_TRY(c, D.snkey.grow((size_t)N));
-        HIP_TRY(c, D.flag.grow(N1)); HIP_TRY(c, D.rep_id.grow(N1)); HIP_TRY(c, D.mem_off.grow(N1));
-        HIP_TRY(c, D.key.grow((size_t)N)); HIP_TRY(c, D.skey.grow((size_t)N));
-        HIP_TRY(c, D.rep_off.grow((size_t)T + 1)); HIP_TRY(c, D.rep_lab_off.grow((size_t)T + 1)); HIP_TRY(c, D.err.grow(4));
-        const unsigned key_bits = 32u + (unsigned)bits_for(T), rep_bits = (unsigned)bits_for(N);
-        size_t sort_a = 0, sort_b = 0, scan_a = 0, scan_b = 0;
-        HIP_TRY(c, rocprim::radix_sort_pairs(nullptr, sort_a, D.key.p, D.skey.p, D.val.p, D.sval.p, (size_t)N, 0u, key_bits, s));
-        HIP_TRY(c, rocprim::radix_sort_pairs(nullptr, sort_b, D.nkey.p, D.snkey.p, D.nval.p, D.mem.p, (size_t)N, 0u, rep_bits, s));
-        HIP_TRY(c, rocprim::inclusive_scan(nullptr, scan_a, D.head.p, D.bstart.p, (size_t)N, rocprim::maximum<int>(), s));
-        HIP_TRY(c, rocprim::exclusive_scan(nullptr, scan_b, D.flag.p, D.rep_id.p, 0, N1, rocprim::plus<int>(), s));
-        const size_t tmp_bytes = std::max(std::max(sort_a, sort_b), std::max(scan_a, scan_b));
-        HIP_TRY(c, D.tmp.grow(tmp_bytes));
+        for (Buf<int> *b : {&D.read_tint, &D.read_rep, &D.mem, &D.rep_first}) HIP_TRY(c, b->grow((size_t)N));
+        HIP_TRY(c, D.mem_off.grow(N1)); HIP_TRY(c, D.rep_off.grow((size_t)T + 1)); HIP_TRY(c, D.rep_lab_off.grow((size_t)T + 1));
         HIP_TRY(c, hipMemcpyAsync(D.tints.p, gt.data(), D.tints.bytes((size_t)T), hipMemcpyHostToDevice, s));
         HIP_TRY(c, hipMemcpyAsync(D.labels.p, in->labels, D.labels.bytes((size_t)n_lab), hipMemcpyHostToDevice, s));
         HIP_TRY(c, hipMemcpyAsync(D.tail.p, in->tail, D.tail.bytes((size_t)N), hipMemcpyHostToDevice, s));
         HIP_TRY(c, hipMemcpyAsync(D.tok_off.p, in->tok_off, D.tok_off.bytes(N1), hipMemcpyHostToDevice, s));
         if (n_tok) HIP_TRY(c, hipMemcpyAsync(D.tok.p, in->tok, D.tok.bytes((size_t)n_tok), hipMemcpyHostToDevice, s));
         else HIP_TRY(c, hipMemsetAsync(D.tok.p, 0, D.tok.bytes(1), s));
-        HIP_TRY(c, hipMemsetAsync(D.err.p, 0x7f, D.err.bytes(4), s));
-        HIP_TRY(c, hipMemsetAsync(D.flag.p + N, 0, D.flag.bytes(1), s));
-        const int read_grid = (int)std::min<i64>((N + 255) / 256, 4096);
-        HIP_TRY(c, hipEventRecord(c->gev[0], s));
-        hipLaunchKernelGGL(k_gkeys, dim3((unsigned)std::min<i64>((n_slots + 255) / 256, 65536)), dim3(256), 0, s, T, n_slots, D.tints.p, D.labels.p, D.tok_off.p,
-                           D.tok.p, D.tail.p, k.hash_mask, D.read_tint.p, D.key.p, D.val.p, D.err.p);
-        HIP_TRY(c, hipEventRecord(c->gev[1], s));
-        HIP_TRY(c, hipMemcpyAsync(H.err.p, D.err.p, D.err.bytes(4), hipMemcpyDeviceToHost, s));
-        size_t tb = tmp_bytes;
-        HIP_TRY(c, rocprim::radix_sort_pairs(D.tmp.p, tb, D.key.p, D.skey.p, D.val.p, D.sval.p, (size_t)N, 0u, key_bits, s));
-        hipLaunchKernelGGL(k_heads, dim3(read_grid), dim3(256), 0, s, N, D.skey.p, D.head.p);
-        tb = tmp_bytes;
-        HIP_TRY(c, rocprim::inclusive_scan(D.tmp.p, tb, D.head.p, D.bstart.p, (size_t)N, rocprim::maximum<int>(), s));
-        hipLaunchKernelGGL(k_gleader, dim3(read_grid), dim3(256), 0, s, N, D.skey.p, D.sval.p, D.bstart.p, D.tints.p, D.labels.p, D.tok_off.p, D.tok.p,
-                           std::max<i64>(n_tok, 1), D.leader.p, D.flag.p);
-        tb = tmp_bytes;
-        HIP_TRY(c, rocprim::exclusive_scan(D.tmp.p, tb, D.flag.p, D.rep_id.p, 0, N1, rocprim::plus<int>(), s));
-        hipLaunchKernelGGL(k_grep_off, dim3((unsigned)(T + 256) / 256), dim3(256), 0, s, T, N, D.tints.p, D.rep_id.p, D.rep_off.p);
-        hipLaunchKernelGGL(k_greps, dim3(read_grid), dim3(256), 0, s, N, D.read_tint.p, D.tints.p, D.leader.p, D.rep_id.p, D.read_rep.p, D.nkey.p, D.nval.p,
-                           D.rep_first.p);
-        tb = tmp_bytes;
-        HIP_TRY(c, rocprim::radix_sort_pairs(D.tmp.p, tb, D.nkey.p, D.snkey.p, D.nval.p, D.mem.p, (size_t)N, 0u, rep_bits, s));
-        HIP_TRY(c, hipEventRecord(c->gev[2], s));
-        HIP_TRY(c, hipMemcpyAsync(h_rep_off, D.rep_off.p, D.rep_off.bytes((size_t)T + 1), hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipStreamSynchronize(s));
-        HIP_TRY(c, hipGetLastError());
-        const int kinds[3] = {2, 0, 1};                      // the tail first, as fclu_preprocess does
-        for (int kind : kinds) {
-            if (H.err.p[kind] == 0x7f7f7f7f) continue;
-            const i64 read = H.err.p[kind];
-            int t = 0;
-            while (t + 1 < T && in->read_off[t + 1] <= read) ++t;
-            const i64 r = read - in->read_off[t];
-            if (kind == 2) return fail(c, FCLU_ERR_ARG, "tint %d read %lld: tail category %d (0 'N', 1 'S', 2 'E')", t, r, (int)in->tail[read]);
-            if (kind == 0) return fail(c, FCLU_ERR_ARG, "tint %d read %lld: a label with code 3 (labels are 0, 1, 2)", t, r);
-            return fail(c, FCLU_ERR_ARG, "tint %d read %lld: a nonzero bit beyond the tint's %d labels", t, r, (int)in->n_seg[t]);
-        }
+        const auto keys = [&]() {
+            hipLaunchKernelGGL(k_gkeys, dim3((unsigned)std::min<i64>((n_slots + 255) / 256, 65536)), dim3(256), 0, s, T, n_slots, D.tints.p, D.labels.p, D.tok_off.p,
+                               D.tok.p, D.tail.p, k.hash_mask, D.read_tint.p, S.key.p, S.val.p, S.err.p);
+        };
+        const auto leader = [&]() {
+            hipLaunchKernelGGL(k_gleader, dim3(item_grid(N)), dim3(256), 0, s, N, S.skey.p, S.sval.p, S.bstart.p, D.tints.p, D.labels.p, D.tok_off.p, D.tok.p,
+                               std::max<i64>(n_tok, 1), S.leader.p, S.flag.p);
+        };
+        const auto offsets = [&]() {                         // (the numbering needs no count from the host: in front of the synchronisation)
+            hipLaunchKernelGGL(k_class_off<GroupTint>, dim3((unsigned)(T + 256) / 256), dim3(256), 0, s, T, N, D.tints.p, S.id.p, D.rep_off.p);
+            hipLaunchKernelGGL(k_greps, dim3(item_grid(N)), dim3(256), 0, s, N, D.read_tint.p, D.tints.p, S.leader.p, S.id.p, D.read_rep.p, S.nkey.p, S.nval.p,
+                               D.rep_first.p);
+        };
+        RC_TRY(dedupe_classes(c, T, N, c->gev, keys, leader, offsets, D.rep_off.p, h_rep_off));
+        RC_TRY(report_row_errors(c, "read", T, in->read_off, in->n_seg, in->tail));
         // ---- the reps' rows as fclu_reads: their layout from the tints' rep counts
         h_rep_lab_off[0] = 0;
         for (int t = 0; t < T; ++t) {
@@ -2119,7 +2127,7 @@ int group_device(fclu_ctx *c, const Knobs &k, const fclu_segment *in, bool gathe
             HIP_TRY(c, hipMemcpyAsync(D.rep_lab_off.p, h_rep_lab_off, D.rep_lab_off.bytes((size_t)T + 1), hipMemcpyHostToDevice, s));
         }
         HIP_TRY(c, hipEventRecord(c->gev[3], s));
-        hipLaunchKernelGGL(k_mem_off, dim3(read_grid), dim3(256), 0, s, N, n_reps, D.snkey.p, D.mem_off.p);
+        RC_TRY(dedupe_members(c, N, n_reps, D.mem.p, D.mem_off.p));
         if (gather)
             hipLaunchKernelGGL(k_ggather, dim3((unsigned)std::min<i64>((n_rep_lab + 255) / 256, 8192)), dim3(256), 0, s, T, n_rep_lab, D.tints.p, D.rep_off.p,
                                D.rep_lab_off.p, D.rep_first.p, D.labels.p, D.tail.p, c->pd.labels.p, c->pd.tail.p);
@@ -2136,13 +2144,7 @@ int group_device(fclu_ctx *c, const Knobs &k, const fclu_segment *in, bool gathe
     if (!copy) *H.mem_off.p = 0;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     HIP_TRY(c, hipGetLastError());
-    if (copy) {
-        float a = 0.f, b = 0.f;
-        (void)hipEventElapsedTime(&c->gkeys_ms, c->gev[0], c->gev[1]);
-        (void)hipEventElapsedTime(&a, c->gev[1], c->gev[2]);
-        (void)hipEventElapsedTime(&b, c->gev[3], c->gev[4]);
-        c->gdedupe_ms = a + b;
-    }
+    if (copy) stage_times(c->gev, c->gkeys_ms, c->gdedupe_ms);
     o.n_tint = T; o.n_reads = N; o.n_reps = n_reps; o.rep_off = h_rep_off;
     n_reps_out = n_reps;
     c->have_groups = true;
@@ -2309,7 +2311,7 @@ int round_device(fclu_ctx *c, const Knobs &k, const fclu_round_batch *b) {
     size_t tmp_a = 0, tmp_b = 0, tmp_c = 0, tmp_d = 0;
     HIP_TRY(c, rocprim::exclusive_scan(nullptr, tmp_a, D.cnt.p, D.scan.p, (i64)0, nCnt, rocprim::plus<i64>(), s));
     if (G) {
-        HIP_TRY(c, rocprim::radix_sort_pairs(nullptr, tmp_b, D.key.p, D.skey.p, D.val.p, D.sval.p, nG, 0u, key_bits, s));
+        RC_TRY(sort_pairs(c, D.tmp, &tmp_b, D.key.p, D.skey.p, D.val.p, D.sval.p, nG, key_bits));
         HIP_TRY(c, rocprim::inclusive_scan(nullptr, tmp_c, D.head.p, D.gid.p, nG, rocprim::plus<i64>(), s));
         HIP_TRY(c, rocprim::exclusive_scan(nullptr, tmp_d, D.grp_cnt.p, D.grp_seg_off.p, (i64)0, nG + 1, rocprim::plus<i64>(), s));
     }
@@ -2341,8 +2343,7 @@ int round_device(fclu_ctx *c, const Knobs &k, const fclu_round_batch *b) {
     if (G) {
         hipLaunchKernelGGL(k_gap_keys, dim3((unsigned)std::min<i64>((C + 255) / 256, 4096)), dim3(256), 0, s, C, D.col_prob.p, D.probs.p, D.rids.p, D.gap_off.p,
                            D.gaps.p, D.col_row_off.p, D.key.p, D.val.p, D.rows.p);
-        tb = tmp_bytes;
-        HIP_TRY(c, rocprim::radix_sort_pairs(D.tmp.p, tb, D.key.p, D.skey.p, D.val.p, D.sval.p, nG, 0u, key_bits, s));
+        RC_TRY(sort_pairs(c, D.tmp, nullptr, D.key.p, D.skey.p, D.val.p, D.sval.p, nG, key_bits));
         hipLaunchKernelGGL(k_gap_heads, dim3(row_grid), dim3(256), 0, s, G, D.skey.p, D.head.p);
         tb = tmp_bytes;
         HIP_TRY(c, rocprim::inclusive_scan(D.tmp.p, tb, D.head.p, D.gid.p, nG, rocprim::plus<i64>(), s));
@@ -2434,11 +2435,7 @@ int fclu_create(int device, fclu_ctx **out) {
     c->device = device;
     e = hipSetDevice(device);
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
-    for (int i = 0; e == hipSuccess && i < 3; ++i) e = hipEventCreate(&c->ev[i]);
-    for (int i = 0; e == hipSuccess && i < 6; ++i) e = hipEventCreate(&c->pev[i]);
-    for (int i = 0; e == hipSuccess && i < 6; ++i) e = hipEventCreate(&c->qev[i]);
-    for (int i = 0; e == hipSuccess && i < 5; ++i) e = hipEventCreate(&c->gev[i]);
-    for (int i = 0; e == hipSuccess && i < 5; ++i) e = hipEventCreate(&c->rev[i]);
+    for (hipEvent_t &ev : c->events) if (e == hipSuccess) e = hipEventCreate(&ev);
     const struct { const void *kernel; int lds; } dyn[] = {                // the most dynamic LDS a launch asks for
         {reinterpret_cast<const void *>(k_cc_lds), 80 * 1024},
         {reinterpret_cast<const void *>(k_compat<false>), 2 * kTile * (kMaxWords | 1) * 4},

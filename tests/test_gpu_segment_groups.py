@@ -249,6 +249,72 @@ def test_replay_on_one_context(batches):
         c.close()
 
 
+def label_batch(shapes, seed):
+    """pack_labels() of random tints of (reps, segments): the tints of test_gpu_cluster_front.lifetime_batch()."""
+    return cluster_prep.pack_labels([fu.labels_from_preprocessed(cu.random_tint(seed + k, n, m), seed=k) for k, (n, m) in enumerate(shapes)])
+
+
+def round_zero(c, b, result):
+    """round_setup() + round_models() of every partition's first round, behind partition_segment(b) = result on c.  The inputs are made
+    once, from the first result: the caller asserts that every later one equals it."""
+    if not hasattr(b, "round_inputs"):
+        tints = cluster_prep.tints_from_arrays(b.arrays, *result, CONSTANT)
+        b.round_inputs = (cluster_prep.round_gaps(tints), [list(p[0]) for t in tints for p in t["partitions"]])
+    gaps, rem = b.round_inputs
+    c.round_setup(*gaps)
+    return c.round_models(list(range(len(rem))), rem)
+
+
+@pytest.mark.parametrize("hash_bits", [None, "0"], ids=["default-hash", "one-bucket"])
+def test_one_scratch_under_both_dedupes_equals_fresh_contexts(batches, monkeypatch, hash_bits):
+    """The grouping and the reps' dedupe share one scratch set, re-grown between them: ONE context through label batches with more reps
+    than the segment batch before them had reads, 5 000 reads that grow the scratch under the grouping with 216 reps that reuse it under
+    the dedupe, the round models behind that, a refusal in the last read of the last tint and the first batch again gives, call by
+    call, every array (and the refusal's text) a fresh context gives for that call alone."""
+    if hash_bits is None:
+        monkeypatch.delenv("FCLU_HASH_BITS", raising=False)
+    else:
+        monkeypatch.setenv("FCLU_HASH_BITS", hash_bits)
+    small, many, big = batches["small"].arrays, batches["many"].arrays, batches["big"].arrays
+    L = label_batch([(130, 64), (65, 33), (1, 5)], 300)
+    assert int(L["rep_off"][-1]) > int(small.a["read_off"][-1]) and int(big.a["read_off"][-1]) == 5700
+    bad = dict(many.a)
+    assert int(bad["read_off"][-1]) > int(bad["read_off"][-2])
+    bad["labels"] = np.array(bad["labels"], np.uint32)
+    bad["labels"][int(bad["lab_off"][-1]) - max((int(bad["n_seg"][-1]) + 15) // 16, 1)] |= 3       # the last read's first label
+
+    def big_and_round_zero(c):
+        result = c.partition_segment(big, SIZE)
+        return result + (round_zero(c, batches["big"], result),)
+
+    def refused(c):
+        with pytest.raises(cluster_prep.ClusterError) as e:
+            c.group_reads(bad)
+        return (dict(code=e.value.code, message=str(e.value)),)
+
+    calls = [lambda c: c.partition_segment(small, SIZE), lambda c: c.partition_labels(L, SIZE), lambda c: (c.group_reads(many),),
+             lambda c: (c.preprocess(L),), big_and_round_zero, refused, lambda c: c.partition_segment(small, SIZE)]
+
+    def fresh(call):
+        c = cluster_prep.Context(0)
+        try:
+            return call(c)
+        finally:
+            c.close()
+
+    want = [fresh(call) for call in calls]
+    assert "tint 64 read %d: a label with code 3" % (int(np.diff(bad["read_off"])[-1]) - 1) in want[5][0]["message"]
+    assert int(want[4][1]["n_reps"]) == 216 and want[4][3]["n_prob"] > 0
+    c = cluster_prep.Context(0)
+    try:
+        for call, w in zip(calls, want):
+            got = call(c)
+            assert len(got) == len(w)
+            assert_same(got, w)
+    finally:
+        c.close()
+
+
 def test_files_batch_entry(ctx, batches):
     b = batches["many"]
     arrays, groups, prep, arr = cluster_prep.cluster_files_batch(b.paths, SIZE, ctx, CONSTANT, threads=2)
