@@ -98,6 +98,8 @@ struct fseg_ctx {
     i64 K = 0, R = 0, I = 0, NPOS = 0, LANES = 0;
     i64 max_part_pos = 0;      // positions of the batch's largest partition (k_thr_part takes partitions of up to kThrPartMaxChunks * 8192)
     int thr_part = -1;         // FSEG_THR_PART=0 / 1: the threshold per partition by one workgroup (k_thr_part) never / whenever possible; -1: batches of many partitions
+    int hist16 = -1;           // FSEG_HIST16=0 / 1: S1 with 32-bit LDS counters always / with packed 16-bit ones wherever no count can overflow; -1: the same as 1
+    bool hist_packed = false;  // the resident batch's chunks were planned for k_hist<16> (kHistChunk16 positions, every count <= 65 535)
     i64 max_part_lanes = 0;    // reads of the batch's largest partition (what bounds a DP sum: 32-bit keys below 2^18)
     int n_tiles = 0;
     bool expanded = false;
@@ -263,7 +265,7 @@ struct fseg_ctx {
     // values those branches test, copied where the stage begins); a replayed graph keeps the words of its capture.
     enum { PATH_SMALL_BATCH, PATH_TINY_ON, PATH_WAVE_ON, PATH_FUSE_ON, PATH_KEY32, PATH_THR_PART, PATH_LABEL_PACKED, PATH_N_SOLVE,
            PATH_N_WIDE = PATH_N_SOLVE + 3, PATH_N_TINY = PATH_N_WIDE + 3, PATH_N_WORK, PATH_DPW, PATH_WIDE16, PATH_KNOWN, PATH_SOLVE8,
-           PATH_TINY_KERNEL, PATH_SCORE, PATH_ARENA_DP, PATH_PLAN, PATH_N_ARENA_PROB, PATH_N_SCORE, PATH_WORDS = PATH_N_SCORE + 3 };
+           PATH_TINY_KERNEL, PATH_SCORE, PATH_ARENA_DP, PATH_PLAN, PATH_N_ARENA_PROB, PATH_N_SCORE, PATH_HIST16 = PATH_N_SCORE + 3, PATH_WORDS };
     int paths[PATH_WORDS] = {};
     // fseg_annotate: the uploaded reads (one allocation, mirrored by a pinned image), per-read work arrays, the emitted lists, and
     // the pinned buffers fseg_annotation() points into (own allocations: nothing of a run or of fseg_results* touches them)
@@ -584,13 +586,19 @@ int enqueue_run(fseg_ctx *c, unsigned segs, bool sized = false, i64 label_fill_b
     }
     begin(ST_HIST);
     // S1
-    hipLaunchKernelGGL(k_hist, dim3(grid_for(c->n_hist_chunks, 1, 16384)), dim3(512), 0, s, c->n_hist_chunks,
-                       c->d_hc_part.as<int>(), c->d_hc_p0.as<i64>(), c->d_hc_n.as<int>(), c->d_hc_glo.as<int>(),
-                       c->d_hc_ghi.as<int>(), c->d_hc_llo.as<i64>(), c->d_hc_lhi.as<i64>(), c->d_part_iv_off.as<i64>(), c->d_iv_start.as<int>(), c->d_iv_end.as<int>(),
-                       c->d_pos_off.as<i64>(), c->d_part_lane_off.as<i64>(), c->d_lane_lx.as<int2>(),
-                       c->d_lane_start.as<int>(), c->d_lane_pmax.as<int>(),
-                       c->d_lex.as<int2>(), c->P.ignore_ends, c->d_y_raw.as<int>(), st,
-                       scan_state, scan_single ? scan_nb * 3 : 0);
+    // (the chunks were laid out on upload for one counter width: one instance per launch)
+#define FSEG_LAUNCH_HIST(BITS)                                                                                         \
+    hipLaunchKernelGGL(k_hist<BITS>, dim3(grid_for(c->n_hist_chunks, 1, 16384)), dim3(512), 0, s, c->n_hist_chunks,   \
+                       c->d_hc_part.as<int>(), c->d_hc_p0.as<i64>(), c->d_hc_n.as<int>(), c->d_hc_glo.as<int>(),       \
+                       c->d_hc_ghi.as<int>(), c->d_hc_llo.as<i64>(), c->d_hc_lhi.as<i64>(), c->d_part_iv_off.as<i64>(), c->d_iv_start.as<int>(), c->d_iv_end.as<int>(), \
+                       c->d_pos_off.as<i64>(), c->d_part_lane_off.as<i64>(), c->d_lane_lx.as<int2>(),                  \
+                       c->d_lane_start.as<int>(), c->d_lane_pmax.as<int>(),                                            \
+                       c->d_lex.as<int2>(), c->P.ignore_ends, c->d_y_raw.as<int>(), st,                                \
+                       scan_state, scan_single ? scan_nb * 3 : 0)
+    c->paths[fseg_ctx::PATH_HIST16] = c->hist_packed;
+    if (c->hist_packed) { FSEG_LAUNCH_HIST(16); }
+    else { FSEG_LAUNCH_HIST(32); }
+#undef FSEG_LAUNCH_HIST
     end(ST_HIST); begin(ST_SMOOTH);
     // S2
 #define FSEG_LAUNCH_SMOOTH(RV)                                                                                         \
@@ -715,7 +723,7 @@ int enqueue_run(fseg_ctx *c, unsigned segs, bool sized = false, i64 label_fill_b
     int *const census = c->paths;
     if (do_score) {
         for (int w = 0; w < fseg_ctx::PATH_WORDS; ++w)
-            if (w != fseg_ctx::PATH_THR_PART && w != fseg_ctx::PATH_LABEL_PACKED && w != fseg_ctx::PATH_ARENA_DP) census[w] = 0;
+            if (w != fseg_ctx::PATH_THR_PART && w != fseg_ctx::PATH_LABEL_PACKED && w != fseg_ctx::PATH_ARENA_DP && w != fseg_ctx::PATH_HIST16) census[w] = 0;
         census[fseg_ctx::PATH_SMALL_BATCH] = c->small_batch; census[fseg_ctx::PATH_TINY_ON] = c->tiny_on; census[fseg_ctx::PATH_WAVE_ON] = wave;
         census[fseg_ctx::PATH_FUSE_ON] = c->use_fuse && c->fuse_on; census[fseg_ctx::PATH_KNOWN] = known; census[fseg_ctx::PATH_PLAN] = plan != nullptr;
     }
@@ -1527,6 +1535,7 @@ int fseg_create(int device, fseg_ctx **out) {
     { const char *v = getenv("FSEG_DEV_SYNC"); if (v && v[0] == '0') c->dev_sync = false; }
     if (flag("FSEG_LABEL_BYTES")) c->label_packed_ok = false;
     { const char *v = getenv("FSEG_THR_PART"); if (v && (v[0] == '0' || v[0] == '1')) c->thr_part = v[0] - '0'; }
+    { const char *v = getenv("FSEG_HIST16"); if (v && (v[0] == '0' || v[0] == '1')) c->hist16 = v[0] - '0'; }
     { const char *v = getenv("FSEG_SYNC_TICKS"); if (v && v[0] && atoll(v) > 0) c->sync_ticks = (unsigned)atoll(v); }
     if (flag("FSEG_NO_GRAPH")) c->use_graph = false;
     if (flag("FSEG_NO_FORK")) c->use_fork = false;
@@ -1674,9 +1683,33 @@ static int upload_impl(fseg_ctx *c, const fseg_batch *b) {
         if (b->rep_exon_off[r + 1] - b->rep_exon_off[r] > max_rep_exons) max_rep_exons = b->rep_exon_off[r + 1] - b->rep_exon_off[r];
     }
     if (lanes >= 0x7fffffffLL) return fail(c, FSEG_ERR_UNSUPPORTED, "batch has %lld reads; split it (limit 2^31-1 per upload)", (long long)lanes);
+    // S1's counter width.  The packed instance (two 16-bit counters per LDS word, chunks of twice the positions) is taken where no
+    // position's count can exceed 65 535.  A read hits a position at most twice (an exon may end where the next begins), so a
+    // partition of up to 32 767 lanes cannot get there -- every partition of an ordinary batch.  A larger one is counted here:
+    // its reps' exon ends, sorted, each with its weight (ignore_ends only takes hits away).  One width per batch.
+    bool hist_packed = c->hist16 != 0;
+    for (int p = 0; p < np && hist_packed; ++p) {
+        const i64 r0 = b->part_rep_off[p], r1 = b->part_rep_off[p + 1];
+        i64 part_lanes = 0;
+        for (i64 r = r0; r < r1; ++r) part_lanes += b->rep_weight[r];
+        if (2 * part_lanes <= kHistCountMax16) continue;
+        std::vector<std::pair<int, int>> ends;
+        ends.reserve((size_t)(2 * (b->rep_exon_off[r1] - b->rep_exon_off[r0])));
+        for (i64 r = r0; r < r1; ++r)
+            for (i64 e = b->rep_exon_off[r]; e < b->rep_exon_off[r + 1]; ++e) {
+                ends.emplace_back(b->ex_ts[e], b->rep_weight[r]);
+                ends.emplace_back(b->ex_te[e], b->rep_weight[r]);
+            }
+        std::sort(ends.begin(), ends.end());
+        i64 count = 0;
+        for (size_t i = 0; i < ends.size() && hist_packed; ++i) {
+            count = (i > 0 && ends[i].first == ends[i - 1].first ? count : 0) + ends[i].second;
+            if (count > kHistCountMax16) hist_packed = false;
+        }
+    }
     // histogram chunks: consecutive positions of one partition; as large as possible (fewer reads are visited twice)
     // while still giving >= 512 workgroups
-    int hist_chunk = kHistChunk;
+    int hist_chunk = hist_packed ? kHistChunk16 : kHistChunk;
     while (hist_chunk > 1024 && NPOS / hist_chunk < 512) hist_chunk >>= 1;
     i64 n_chunks = 0;
     {
@@ -1797,7 +1830,7 @@ static int upload_impl(fseg_ctx *c, const fseg_batch *b) {
     const double t_copy = tk.ms();
     c->n_part = np; c->K = K; c->R = R; c->I = I; c->NPOS = NPOS; c->LANES = lanes; c->expanded = expanded;
     if (c->max_part_lanes > lanes) c->max_part_lanes = lanes;
-    c->n_tiles = (int)n_tiles; c->n_hist_chunks = (int)n_chunks; c->n_rep_blocks = (int)n_rep_blocks; c->max_rep_exons = max_rep_exons;
+    c->n_tiles = (int)n_tiles; c->n_hist_chunks = (int)n_chunks; c->hist_packed = hist_packed; c->n_rep_blocks = (int)n_rep_blocks; c->max_rep_exons = max_rep_exons;
     c->part_iv_off.assign(b->part_iv_off, b->part_iv_off + np + 1);
     c->part_rep_off.assign(b->part_rep_off, b->part_rep_off + np + 1);
     hipStream_t s = c->stream;

@@ -240,8 +240,18 @@ __device__ __forceinline__ void label_thresholds_tab(i64 L, const int2 *tab, con
 // A lane is one read (reps are repeated rep_weight times in the lane list), so every hit adds 1.
 // ---------------------------------------------------------------------------------------------
 constexpr int kHistChunk = 8192;
+// The same 32 KB of LDS as two 16-bit counters per word (k_hist<16>: position i of the chunk is half i & 1 of word i >> 1) hold twice
+// the positions: half the chunks, so half the visits of a read that spans its partition, half the table stagings and barriers.
+// A low half never carries into its neighbour because the host takes this instance only for batches in which no position's
+// count can exceed 65 535 (upload_impl: hist_packed).
+#ifndef FSEG_HIST_CHUNK16
+#define FSEG_HIST_CHUNK16 16384
+#endif
+constexpr int kHistChunk16 = FSEG_HIST_CHUNK16;
+static_assert(kHistChunk16 % 8 == 0, "the packed counters are zeroed sixteen bytes at a time");
+constexpr int kHistCountMax16 = 65535;
 
-constexpr int kHistIv = 1024;      // intervals of a partition cached in LDS by k_hist
+constexpr int kHistIv = 1024;     // intervals of a partition cached in LDS by k_hist
 
 
 // ---------------------------------------------------------------------------------------------

@@ -15,6 +15,9 @@ __global__ void __launch_bounds__(256) k_thr_table(const double *h_table, int h_
     }
 }
 
+// BITS: the width of a counter in LDS.  32: kHistChunk positions, a word each.  16: kHistChunk16 positions, two to a word (a batch
+// in which no count can exceed 65 535; the host decides, one instance per launch).  The walk is the same.
+template <int BITS>
 __global__ void __launch_bounds__(512) k_hist(int n_chunks, const int *chunk_part, const i64 *chunk_p0, const int *chunk_n,
                                               const int *chunk_glo, const int *chunk_ghi, const i64 *chunk_lane_lo,
                                               const i64 *chunk_lane_hi, const i64 *part_iv_off,
@@ -22,7 +25,10 @@ __global__ void __launch_bounds__(512) k_hist(int n_chunks, const int *chunk_par
                                               const i64 *part_lane_off, const int2 *__restrict__ lane_lx, const int *lane_start,
                                               const int *lane_pmax, const int2 *__restrict__ lex,
                                               int ignore_ends, int *y_raw, Status *st, u64 *zero_ptr, i64 zero_n) {
-    __shared__ int hist[kHistChunk];
+    static_assert(BITS == 32 || BITS == 16, "a counter is a word or half a word");
+    using Word = std::conditional_t<BITS == 16, unsigned, int>;
+    constexpr int kWords = BITS == 16 ? kHistChunk16 / 2 : kHistChunk;
+    __shared__ __attribute__((aligned(16))) Word hist[kWords];
     __shared__ int ivs_s[kHistIv], ive_s[kHistIv], base_s[kHistIv];
     // first kernel of the run: also clears the look-back words of the three compactions (saves a memset node)
     for (i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x; i < zero_n; i += (i64)gridDim.x * blockDim.x) zero_ptr[i] = 0;
@@ -33,7 +39,12 @@ __global__ void __launch_bounds__(512) k_hist(int n_chunks, const int *chunk_par
         const int g_lo = chunk_glo[ch], g_hi = chunk_ghi[ch];          // genomic position of the first / last position
         const i64 k0 = part_iv_off[part], k1 = part_iv_off[part + 1];
         __syncthreads();
-        for (int i = threadIdx.x; i < np; i += blockDim.x) hist[i] = 0;
+        if constexpr (BITS == 16) {
+            // (np + 1) / 2 words, sixteen bytes per write (kWords is a multiple of four: the last write stays inside the array)
+            for (int i = threadIdx.x; i < (np + 7) >> 3; i += blockDim.x) reinterpret_cast<uint4 *>(hist)[i] = make_uint4(0u, 0u, 0u, 0u);
+        } else {
+            for (int i = threadIdx.x; i < np; i += blockDim.x) hist[i] = 0;
+        }
         // lanes whose [first, last] position range meets [g_lo, g_hi]: found on upload (the chunks and the sorted
         // lanes are both fixed then), two dependent 16-step searches less per workgroup
         const i64 lo = chunk_lane_lo[ch], hi = chunk_lane_hi[ch];
@@ -53,6 +64,10 @@ __global__ void __launch_bounds__(512) k_hist(int n_chunks, const int *chunk_par
         // lanes' pieces (from the rep-ordered ex_ts / ex_te: two lines per read, anywhere)
         const int sub = threadIdx.x & 7;
         const int G8 = blockDim.x >> 3;
+        auto hit = [&](int i) {       // i: chunk-local index of the position
+            if constexpr (BITS == 16) atomicAdd(&hist[i >> 1], 1u << (16 * (i & 1)));
+            else atomicAdd(&hist[i], 1);
+        };
         auto count_exon = [&](i64 e, i64 e0, i64 e1, int ts, int te) {
             if (te < g_lo || ts > g_hi) return;
             // the interval that holds ts must hold te as well (:666-668; also validated on upload)
@@ -72,8 +87,8 @@ __global__ void __launch_bounds__(512) k_hist(int n_chunks, const int *chunk_par
                 base = (int)(pos_off[k] - p0) - iv_start[k];
             }
             if (!ok) { atomicOr(&st->err, kErrExonInterval); return; }
-            if (!(ignore_ends && e == e0) && ts >= g_lo && ts <= g_hi) atomicAdd(&hist[base + ts], 1);       // :670-671
-            if (!(ignore_ends && e == e1 - 1) && te >= g_lo && te <= g_hi) atomicAdd(&hist[base + te], 1);   // :672-673
+            if (!(ignore_ends && e == e0) && ts >= g_lo && ts <= g_hi) hit(base + ts);       // :670-671
+            if (!(ignore_ends && e == e1 - 1) && te >= g_lo && te <= g_hi) hit(base + te);   // :672-673
         };
         for (i64 l0 = lo + (threadIdx.x >> 3); l0 < hi; l0 += 4 * (i64)G8) {
             int2 ex[4], x0[4];
@@ -93,7 +108,21 @@ __global__ void __launch_bounds__(512) k_hist(int n_chunks, const int *chunk_par
             }
         }
         __syncthreads();
-        for (int i = threadIdx.x; i < np; i += blockDim.x) y_raw[p0 + i] = hist[i];
+        if constexpr (BITS == 16) {
+            // y_raw stays int32, a position per element.  A thread takes the two positions i0, i0 + 1 with p0 + i0 even -- one
+            // aligned 8-byte store, a wave's stores one contiguous run -- whichever halves of whichever words they are (p0 is odd
+            // where the partitions before it hold an odd number of positions: then i0 = -1 first, and a pair straddles two words).
+            const int odd = (int)(p0 & 1);
+            auto count_at = [&](int i) { return (int)((hist[i >> 1] >> (16 * (i & 1))) & 0xffffu); };
+            for (int i0 = 2 * (int)threadIdx.x - odd; i0 < np; i0 += 2 * (int)blockDim.x) {
+                const int i1 = i0 + 1;
+                if (i0 >= 0 && i1 < np) *reinterpret_cast<int2 *>(y_raw + p0 + i0) = make_int2(count_at(i0), count_at(i1));
+                else if (i0 >= 0) y_raw[p0 + i0] = count_at(i0);
+                else y_raw[p0 + i1] = count_at(i1);              // (a chunk has at least one position)
+            }
+        } else {
+            for (int i = threadIdx.x; i < np; i += blockDim.x) y_raw[p0 + i] = hist[i];
+        }
     }
 }
 
@@ -728,6 +757,8 @@ __global__ void __launch_bounds__(256) k_peaks_edges(int n_tiles, const TileDesc
 // the instances the host launches (freddie_seg.hip sees the declarations only: taking an instance's address here is what
 // instantiates it -- host stub and device code -- in this translation unit)
 __attribute__((used)) static const void *const kInstances[] = {
+    reinterpret_cast<const void *>(&k_hist<32>),
+    reinterpret_cast<const void *>(&k_hist<16>),
     reinterpret_cast<const void *>(&k_smooth<20>),
     reinterpret_cast<const void *>(&k_smooth<12>),
     reinterpret_cast<const void *>(&k_smooth<0>),

@@ -9,6 +9,7 @@ namespace fseg {
 __global__ void __launch_bounds__(256) k_thr_table(const double *h_table, int h_len, double tau, int2 *tab);
 
 // seg_front.hip
+template <int BITS>
 __global__ void __launch_bounds__(512) k_hist(int n_chunks, const int *chunk_part, const i64 *chunk_p0, const int *chunk_n,
                                               const int *chunk_glo, const int *chunk_ghi, const i64 *chunk_lane_lo,
                                               const i64 *chunk_lane_hi, const i64 *part_iv_off,

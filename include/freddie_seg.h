@@ -241,8 +241,9 @@ enum {
      *   21 arena-path DP (k_dp*): 0 not launched, 2 = 16-bit count tables, 4 = 32-bit
      *   22 a scoring plan (FSEG_SCORE_PLAN) laid the stage out over the side streams
      *   23 problems of the arena path
-     *   24..26 work items of the small / mid / large class k_score was launched over (a problem is one work item or more) */
-    FSEG_TAP_PATHS = 18        /* int32[27]                                                                            */
+     *   24..26 work items of the small / mid / large class k_score was launched over (a problem is one work item or more)
+     *   27 the histogram ran with packed 16-bit LDS counters (k_hist<16>; 0: the 32-bit instance) */
+    FSEG_TAP_PATHS = 18        /* int32[28]                                                                            */
 };
 int fseg_tap(fseg_ctx *ctx, int what, void *dst, int64_t cap_bytes, int64_t *n_bytes);
 
