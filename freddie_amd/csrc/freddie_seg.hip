@@ -265,7 +265,8 @@ struct fseg_ctx {
     // values those branches test, copied where the stage begins); a replayed graph keeps the words of its capture.
     enum { PATH_SMALL_BATCH, PATH_TINY_ON, PATH_WAVE_ON, PATH_FUSE_ON, PATH_KEY32, PATH_THR_PART, PATH_LABEL_PACKED, PATH_N_SOLVE,
            PATH_N_WIDE = PATH_N_SOLVE + 3, PATH_N_TINY = PATH_N_WIDE + 3, PATH_N_WORK, PATH_DPW, PATH_WIDE16, PATH_KNOWN, PATH_SOLVE8,
-           PATH_TINY_KERNEL, PATH_SCORE, PATH_ARENA_DP, PATH_PLAN, PATH_N_ARENA_PROB, PATH_N_SCORE, PATH_HIST16 = PATH_N_SCORE + 3, PATH_WORDS };
+           PATH_TINY_KERNEL, PATH_SCORE, PATH_ARENA_DP, PATH_PLAN, PATH_N_ARENA_PROB, PATH_N_SCORE, PATH_HIST16 = PATH_N_SCORE + 3, PATH_IV_THREADS,
+           PATH_SMOOTH_R, PATH_WORDS };
     int paths[PATH_WORDS] = {};
     // fseg_annotate: the uploaded reads (one allocation, mirrored by a pinned image), per-read work arrays, the emitted lists, and
     // the pinned buffers fseg_annotation() points into (own allocations: nothing of a run or of fseg_results* touches them)
@@ -607,9 +608,9 @@ int enqueue_run(fseg_ctx *c, unsigned segs, bool sized = false, i64 label_fill_b
                        c->P.radius_main, c->d_y.as<double>(), flag_pos_bits,                           \
                        flag_cand_bits, c->d_blk_pre.as<int>(), c->d_tile_tot.as<int>(), c->d_tile_defer.as<int>())
     // sigma = 5 (default) and sigma = 3 (config 5) have their own unrolled instances; any other radius runs the loop
-    if (c->P.radius_main == 20) { FSEG_LAUNCH_SMOOTH(20); }
-    else if (c->P.radius_main == 12) { FSEG_LAUNCH_SMOOTH(12); }
-    else { FSEG_LAUNCH_SMOOTH(0); }
+    if (c->P.radius_main == 20) { c->paths[fseg_ctx::PATH_SMOOTH_R] = 20; FSEG_LAUNCH_SMOOTH(20); }
+    else if (c->P.radius_main == 12) { c->paths[fseg_ctx::PATH_SMOOTH_R] = 12; FSEG_LAUNCH_SMOOTH(12); }
+    else { c->paths[fseg_ctx::PATH_SMOOTH_R] = 0; FSEG_LAUNCH_SMOOTH(0); }
 #undef FSEG_LAUNCH_SMOOTH
     end(ST_SMOOTH);
     // S3a threshold: needs only the smoothed signal, like the candidates (S3b) -- the two chains run side by side
@@ -665,6 +666,7 @@ int enqueue_run(fseg_ctx *c, unsigned segs, bool sized = false, i64 label_fill_b
     early_fork();
     begin(ST_FIX);
     // S4
+    c->paths[fseg_ctx::PATH_IV_THREADS] = iv_threads;              // (k_segments, S6, is launched with the same block)
     hipLaunchKernelGGL(k_fix, dim3(grid_for(K, 1, 8192)), dim3(iv_threads), 0, s, K, c->d_pos_off.as<i64>(),
                        c->d_iv_part.as<int>(), c->d_cand_off.as<i64>(), c->d_cand_y.as<int>(), c->d_y.as<double>(),
                        c->d_thr.as<double>(), c->P.max_problem_size, c->d_fixed0.as<unsigned char>(),
@@ -723,7 +725,8 @@ int enqueue_run(fseg_ctx *c, unsigned segs, bool sized = false, i64 label_fill_b
     int *const census = c->paths;
     if (do_score) {
         for (int w = 0; w < fseg_ctx::PATH_WORDS; ++w)
-            if (w != fseg_ctx::PATH_THR_PART && w != fseg_ctx::PATH_LABEL_PACKED && w != fseg_ctx::PATH_ARENA_DP && w != fseg_ctx::PATH_HIST16) census[w] = 0;
+            if (w != fseg_ctx::PATH_THR_PART && w != fseg_ctx::PATH_LABEL_PACKED && w != fseg_ctx::PATH_ARENA_DP && w != fseg_ctx::PATH_HIST16 &&
+                w != fseg_ctx::PATH_IV_THREADS && w != fseg_ctx::PATH_SMOOTH_R) census[w] = 0;
         census[fseg_ctx::PATH_SMALL_BATCH] = c->small_batch; census[fseg_ctx::PATH_TINY_ON] = c->tiny_on; census[fseg_ctx::PATH_WAVE_ON] = wave;
         census[fseg_ctx::PATH_FUSE_ON] = c->use_fuse && c->fuse_on; census[fseg_ctx::PATH_KNOWN] = known; census[fseg_ctx::PATH_PLAN] = plan != nullptr;
     }

@@ -11,26 +11,13 @@ import numpy as np
 import pytest
 
 import util
-from freddie_amd import _lib, pack
+from freddie_amd import _lib
 
 pytestmark = pytest.mark.gpu
 
 K16 = 16384            # kHistChunk16 (csrc/seg_common.h)
 ENDS = dict(ignore_ends=False)
-
-
-def hand(ivs, reads, weights=None):
-    """A partition written out by hand: intervals [(start, end)], reads [[(ts, te), ...]], a rep per read (no dedupe)."""
-    off = np.cumsum([0] + [len(r) for r in reads])
-    ex = np.array([x for r in reads for x in r], np.int32).reshape(-1, 2)
-    part = pack.pack_partition([s for s, _ in ivs], [e for _, e in ivs], off, ex[:, 0], ex[:, 1], dedupe=False)
-    if weights is not None:
-        part.rep_weight = np.asarray(weights, np.int32)
-    return part
-
-
-def shifted(reads, d):
-    return [[(ts + d, te + d) for ts, te in r] for r in reads]
+hand, shifted = util.hand, util.shifted
 
 
 # three exons a read: under ignore_ends the first exon's start and the last exon's end do not count, the four ends between do

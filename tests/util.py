@@ -93,6 +93,38 @@ def compare_partitions(ctx, parts, oracles, y_tol=1e-6):
     return report
 
 
+def hand(ivs, reads, weights=None):
+    """A partition written out by hand: intervals [(start, end)], reads [[(ts, te), ...]], a rep per read (no dedupe)."""
+    off = np.cumsum([0] + [len(r) for r in reads])
+    ex = np.array([x for r in reads for x in r], np.int32).reshape(-1, 2)
+    part = pack.pack_partition([s for s, _ in ivs], [e for _, e in ivs], off, ex[:, 0], ex[:, 1], dedupe=False)
+    if weights is not None:
+        part.rep_weight = np.asarray(weights, np.int32)
+    return part
+
+
+def shifted(reads, d):
+    return [[(ts + d, te + d) for ts, te in r] for r in reads]
+
+
+def junction_reads(iv, positions, weights, sink):
+    """Counts placed by hand: a two-exon rep per position q of interval `iv` = (start, end), [(start, start + q), (sink start + 50,
+    sink end)].  Under ignore_ends a rep's first start and last end count nothing, so rep i puts exactly weights[i] counts on position
+    positions[i] of `iv` and as many on position 50 of `sink`, which keeps whatever else there is: a short interval behind `iv`, or
+    a stretch of `iv` itself behind every position (the batch then holds the one interval).  Returns (reads, weights) for hand()."""
+    (s, e), (ss, se) = iv, sink
+    assert se - ss > 50 and (ss > e or se <= e) and all(0 < q <= e - s and s + q < ss for q in positions)
+    assert len(positions) == len(weights)
+    return [[(s, s + int(q)), (ss + 50, se)] for q in positions], [int(w) for w in weights]
+
+
+def flat_top(a, W, weight=30):
+    """(positions, weights) of one junction of `weight` on every position of [a, a + W): under a filter of radius r <= (W - 1) / 2
+    the smoothed signal is bit-identical over [a + r, a + W - r) (every output there is the same sum of the same products) and
+    strictly lower on both sides -- a plateau whose midpoint, (a + r + a + W - r - 1) // 2, is the candidate."""
+    return list(range(a, a + W)), [weight] * W
+
+
 def weighted_partition(seed, n_reads, n_exons, weights, **gen_kw):
     """A partition of few reps that stand for many reads: make_partition(..., max_span=0) with rep_weight overwritten (jittered
     synthetic reads rarely collapse, so no generated batch has a rep of more than a few reads).  `weights`: a factor for every
