@@ -332,10 +332,10 @@ __global__ void __launch_bounds__(256) k_votes(int n_iso, const i64 *iso_read_of
         const i64 q0 = read_b_off[r0], q1 = read_b_off[r1];                // the member reads' boundaries are contiguous
         const int *ib = iso_bound + b0;
         for (i64 q = q0 + threadIdx.x; q < q1; q += blockDim.x) {
-            const int v = read_bound[q];
+            const i64 v = read_bound[q];                                   // 64-bit: v +- window leaves int32 at the ends of the range
             i64 lo = 0, hi = nb;
-            while (lo < hi) { i64 mid = (lo + hi) >> 1; if (ib[mid] < v - window) lo = mid + 1; else hi = mid; }
-            for (i64 k = lo; k < nb && ib[k] <= v + window; ++k)
+            while (lo < hi) { i64 mid = (lo + hi) >> 1; if ((i64)ib[mid] < v - window) lo = mid + 1; else hi = mid; }
+            for (i64 k = lo; k < nb && (i64)ib[k] <= v + window; ++k)
                 atomicAdd(&votes[(b0 + k) * (2 * window + 1) + (v - ib[k] + window)], 1);
         }
     }

@@ -1,8 +1,11 @@
-"""Helpers of the isoform-consensus tests: fixtures (reference GTFs) and a random stage input."""
+"""Helpers of the isoform-consensus tests: fixtures (reference GTFs), a random stage input, and plain numpy references of
+the two device calls (consensus counts, boundary votes)."""
 import gzip
 import json
 import os
 import random
+
+import numpy as np
 
 import goldens
 
@@ -66,3 +69,39 @@ def random_job(seed, n_iso, reads_per_iso, n_segs, tail_p=0.3):
             isoforms[key]["rids"].add(rid)
             rid += 1
     return isoforms, segments, reads
+
+
+def plain_counts(iro, n_seg, off, lab, tail):
+    """cons / cov / tails of isoforms_cons (:203-232) with numpy, an isoform at a time; a read's row is lab[off[r]:off[r] + M],
+    wherever that lies."""
+    cons, cov, tails = [], [], []
+    for i in range(len(n_seg)):
+        M, r0, r1 = int(n_seg[i]), int(iro[i]), int(iro[i + 1])
+        rows = np.stack([lab[int(off[r]):int(off[r]) + M] for r in range(r0, r1)]) if r1 > r0 and M else np.zeros((r1 - r0, M), np.uint8)
+        one = rows == ord("1")
+        has = one.any(1) if M else np.zeros(r1 - r0, bool)
+        first = np.where(has, one.argmax(1), M) if M else np.zeros(r1 - r0, int)
+        last = np.where(has, M - 1 - one[:, ::-1].argmax(1), -1) if M else np.zeros(r1 - r0, int) - 1
+        tl = tail[r0:r1]
+        first = np.where(has & (tl == 1), 0, first); last = np.where(has & (tl == 1), M - 1, last)
+        j = np.arange(M)[None, :]
+        inside = (j >= first[:, None]) & (j <= last[:, None])
+        cons.append((inside & one).sum(0)); cov.append(inside.sum(0))
+        tails.append([int((has & (tl == k)).sum()) for k in range(3)])
+    return np.concatenate(cons).astype(np.int32), np.concatenate(cov).astype(np.int32), np.asarray(tails, np.int32)
+
+
+def plain_votes(iso_read_off, iso_b_off, iso_bound, read_b_off, read_bound, w):
+    """votes of correct_boundaries (:129-137) as a (B, 2w + 1) int32 array: row = isoform boundary, column x + w = the
+    member reads' boundaries at distance x from it.  Differences in int64, every x of the window counted: no search, no sort."""
+    iso_bound = np.asarray(iso_bound, np.int64); read_bound = np.asarray(read_bound, np.int64)
+    xs = np.arange(-w, w + 1, dtype=np.int64)
+    out = np.zeros((int(iso_b_off[-1]), 2 * w + 1), np.int32)
+    for i in range(len(iso_b_off) - 1):
+        b0, b1 = int(iso_b_off[i]), int(iso_b_off[i + 1])
+        q0, q1 = int(read_b_off[int(iso_read_off[i])]), int(read_b_off[int(iso_read_off[i + 1])])
+        if b0 == b1 or q0 == q1:
+            continue
+        d = read_bound[None, q0:q1] - iso_bound[b0:b1, None]
+        out[b0:b1] = (d[:, :, None] == xs[None, None, :]).sum(1)
+    return out

@@ -136,25 +136,6 @@ def test_counts_are_plain_sums(ctx):
     assert np.array_equal(votes[i * nb:(i + 1) * nb], want)
 
 
-def _plain_counts(iro, n_seg, off, lab, tail):
-    """cons / cov / tails of isoforms_cons (:203-232) with numpy, an isoform at a time."""
-    cons, cov, tails = [], [], []
-    for i in range(len(n_seg)):
-        M, r0, r1 = int(n_seg[i]), int(iro[i]), int(iro[i + 1])
-        rows = np.stack([lab[int(off[r]):int(off[r]) + M] for r in range(r0, r1)]) if r1 > r0 and M else np.zeros((r1 - r0, M), np.uint8)
-        one = rows == ord("1")
-        has = one.any(1) if M else np.zeros(r1 - r0, bool)
-        first = np.where(has, one.argmax(1), M) if M else np.zeros(r1 - r0, int)
-        last = np.where(has, M - 1 - one[:, ::-1].argmax(1), -1) if M else np.zeros(r1 - r0, int) - 1
-        tl = tail[r0:r1]
-        first = np.where(has & (tl == 1), 0, first); last = np.where(has & (tl == 1), M - 1, last)
-        j = np.arange(M)[None, :]
-        inside = (j >= first[:, None]) & (j <= last[:, None])
-        cons.append((inside & one).sum(0)); cov.append(inside.sum(0))
-        tails.append([int((has & (tl == k)).sum()) for k in range(3)])
-    return np.concatenate(cons).astype(np.int32), np.concatenate(cov).astype(np.int32), np.asarray(tails, np.int32)
-
-
 @pytest.mark.parametrize("rows_switch", ["1", "0"])
 def test_row_lengths_and_read_counts_of_every_shape(ctx, rows_switch, monkeypatch):
     """The one-pass kernel (rows of at most 1 024 labels: a read's row is one load instruction of a group of lanes) and the
@@ -180,7 +161,7 @@ def test_row_lengths_and_read_counts_of_every_shape(ctx, rows_switch, monkeypatc
         lab = np.concatenate(rows)
         off = np.concatenate([[0], np.cumsum(np.repeat(n_seg, per))])[:-1]
         tail = rng.integers(0, 3, R).astype(np.uint8)
-        want = _plain_counts(iro, n_seg, off, lab, tail)
+        want = iu.plain_counts(iro, n_seg, off, lab, tail)
         for packed in (False, True):
             _, cons, cov, tails = ctx.consensus(iro, n_seg, off, isoforms.pack_labels(lab) if packed else lab, tail, packed=packed)
             assert np.array_equal(cons, want[0]), (longer, packed)
