@@ -136,7 +136,7 @@ struct fseg_ctx {
     DevBuf d_w_main, d_w_refine, d_h_table, d_thr_tab;     // parameter tables (own allocations)
     // device buffers: position-sized (slab_pos)
     DevBuf d_bits;               // the three flag masks (Y > 0, candidate, final position), a bit per position each, cleared per run
-    DevBuf d_y_raw, d_y, d_v, d_scan_state, d_bsum, d_bsum_side, d_g, d_pk, d_pf, d_kp;
+    DevBuf d_y_raw, d_y, d_v, d_scan_state, d_bsum, d_gsum, d_bsum_side, d_g, d_pk, d_pf, d_kp;
     int n_hist_chunks = 0;
     DevBuf d_voff, d_chunk_off, d_csum, d_mean, d_thr, d_label_off, d_part_has2;
     int n_rep_blocks = 0;
@@ -564,8 +564,19 @@ int enqueue_run(fseg_ctx *c, unsigned segs, bool sized = false, i64 label_fill_b
     u64 *scan_state = c->d_scan_state.as<u64>();
     // single-pass look-back scan while the chain of blocks is short; block sums + one scanning workgroup beyond that
     const bool scan_single = scan_nb <= c->scan_single_max;
-    int *bsum = scan_single ? nullptr : c->d_bsum.as<int>();
-    int *bsum_side = scan_single ? nullptr : c->d_bsum_side.as<int>();     // block sums of the scan that runs on a side stream
+    int *bsum_side = scan_single ? nullptr : c->d_bsum_side.as<int>();     // block sums of the scan that runs on a side stream (values)
+    // the two position compactions: blocks of kPosBlock positions (a quarter of the words of look-back state, same layout).  The
+    // look-back chain keeps its limit in POSITIONS (FSEG_SCAN_SINGLE_MAX blocks of kScanBlock, as it was measured): beyond it
+    // block sums + group sums that the emitting workgroups add up themselves (k_pos_count), no scanning workgroup between
+    const i64 pos_nb = pos_blocks(NPOS);
+    const int pos_grid = pos_nb > 0 ? (int)pos_nb : 1;          // exactly one workgroup per block
+    const bool pos_single = scan_single;
+    int *bsum = pos_single ? nullptr : c->d_bsum.as<int>();
+    int *gsum = pos_single ? nullptr : c->d_gsum.as<int>();
+    auto pos_counts = [&](hipStream_t q, const unsigned *flags) {
+        if (pos_single) return;
+        hipLaunchKernelGGL(k_pos_count, dim3(grid_for(pos_groups(NPOS), 1, 4096)), dim3(kPosCountThreads), 0, q, flags, NPOS, bsum, gsum);
+    };
     auto scan_counts = [&](hipStream_t q, int *bs, const unsigned *flags, u64 *total_dev, i64 *off_last) {
         if (scan_single) return;
         hipLaunchKernelGGL(k_scan1, dim3(grid_for(scan_nb, 1, 4096)), dim3(256), 0, q, flags, NPOS, bs);
@@ -633,7 +644,7 @@ int enqueue_run(fseg_ctx *c, unsigned segs, bool sized = false, i64 label_fill_b
     c->paths[fseg_ctx::PATH_THR_PART] = 0;
     scan_counts(q, bsum_side, flag_pos_bits, &st->n_vals, nullptr);
     hipLaunchKernelGGL(k_scan_emit<kEmitValues>, dim3(scan_grid), dim3(256), 0, q, flag_pos_bits, NPOS,
-                       bsum_side, scan_state, &st->n_vals, (i64 *)nullptr, &st->err, c->d_y.as<double>(), c->d_v.as<double>(), K, c->d_pos_off.as<i64>(),
+                       bsum_side, (const int *)nullptr, scan_state, &st->n_vals, (i64 *)nullptr, &st->err, c->d_y.as<double>(), c->d_v.as<double>(), K, c->d_pos_off.as<i64>(),
                        c->d_iv_start.as<int>(), c->d_blk_iv0.as<int>(), (int *)nullptr, (int *)nullptr, (i64 *)nullptr,
                        c->force_scan_stall ? 1 : 0, (int *)nullptr);
     hipLaunchKernelGGL(k_voff, dim3(grid_for(n_part + 1, 1, 2048)), dim3(64), 0, q, n_part, c->d_part_iv_off.as<i64>(),
@@ -656,9 +667,9 @@ int enqueue_run(fseg_ctx *c, unsigned segs, bool sized = false, i64 label_fill_b
     // S3b candidates
     hipLaunchKernelGGL(k_peaks_edges, dim3(grid_for(c->n_tiles, 256, 4096)), dim3(256), 0, s, c->n_tiles, c->d_tile_desc.as<TileDesc>(),
                        c->d_tile_defer.as<int>(), c->d_y.as<double>(), flag_cand_bits, c->d_part_has2.as<int>(), n_part);
-    scan_counts(s, bsum, flag_cand_bits, &st->n_cand, c->d_cand_off.as<i64>() + K);
-    hipLaunchKernelGGL(k_scan_emit<kEmitPositions>, dim3(scan_grid), dim3(256), 0, s, flag_cand_bits, NPOS,
-                       bsum, scan_state + scan_nb, &st->n_cand, c->d_cand_off.as<i64>() + K, &st->err, (const double *)nullptr, (double *)nullptr, K, c->d_pos_off.as<i64>(),
+    pos_counts(s, flag_cand_bits);
+    hipLaunchKernelGGL(k_scan_emit<kEmitPositions>, dim3(pos_grid), dim3(256), 0, s, flag_cand_bits, NPOS,
+                       bsum, gsum, scan_state + scan_nb, &st->n_cand, c->d_cand_off.as<i64>() + K, &st->err, (const double *)nullptr, (double *)nullptr, K, c->d_pos_off.as<i64>(),
                        c->d_iv_start.as<int>(), c->d_blk_iv0.as<int>(), c->d_cand_y.as<int>(), (int *)nullptr,
                        c->d_cand_off.as<i64>(), 0, (int *)nullptr);
     end(ST_CANDIDATES);
@@ -1086,9 +1097,9 @@ int enqueue_run(fseg_ctx *c, unsigned segs, bool sized = false, i64 label_fill_b
                        c->d_w_refine.as<double>(), c->P.radius_refine, c->P.sigma, c->d_g.as<double>(), c->d_pk.as<int>(),
                        c->d_pf.as<unsigned char>(), c->d_kp.as<unsigned char>(), flag_final_bits);
     end(ST_REFINE); begin(ST_FINAL);
-    scan_counts(s, bsum, flag_final_bits, &st->n_final, c->d_final_off.as<i64>() + K);
-    hipLaunchKernelGGL(k_scan_emit<kEmitPositions>, dim3(scan_grid), dim3(256), 0, s, flag_final_bits,
-                       NPOS, bsum, scan_state + 2 * scan_nb, &st->n_final, c->d_final_off.as<i64>() + K, &st->err, (const double *)nullptr, (double *)nullptr, K, c->d_pos_off.as<i64>(),
+    pos_counts(s, flag_final_bits);
+    hipLaunchKernelGGL(k_scan_emit<kEmitPositions>, dim3(pos_grid), dim3(256), 0, s, flag_final_bits,
+                       NPOS, bsum, gsum, scan_state + 2 * scan_nb, &st->n_final, c->d_final_off.as<i64>() + K, &st->err, (const double *)nullptr, (double *)nullptr, K, c->d_pos_off.as<i64>(),
                        c->d_iv_start.as<int>(), c->d_blk_iv0.as<int>(), c->d_final_y.as<int>(), c->d_final_pos.as<int>(),
                        c->d_final_off.as<i64>(), 0, c->d_final_iv.as<int>());
     // S7, first half: per-column thresholds and the label arena's plan
@@ -1725,7 +1736,7 @@ static int upload_impl(fseg_ctx *c, const fseg_batch *b) {
         }
         (void)pos;
     }
-    const i64 nb = scan_blocks(NPOS);
+    const i64 nb = scan_blocks(NPOS), nbp = pos_blocks(NPOS);
     if (n_tiles >= 0x7fffffffLL || n_chunks >= 0x7fffffffLL) return fail(c, FSEG_ERR_UNSUPPORTED, "batch too large");
     // ---- the input slab: [uploaded part, mirrored by the pinned staging image][device-derived part]
     Carve in;
@@ -1738,7 +1749,7 @@ static int upload_impl(fseg_ctx *c, const fseg_batch *b) {
     in.add(c->d_iv_part, (size_t)K * 4);
     in.add(c->d_iv_tile0, (size_t)K * 4);
     in.add(c->d_tile_desc, (size_t)n_tiles * sizeof(TileDesc));
-    in.add(c->d_blk_iv0, ((size_t)nb + 1) * 4);
+    in.add(c->d_blk_iv0, ((size_t)nbp + 1) * 4);
     in.add(c->d_rb_part, (size_t)n_rep_blocks * 4);
     in.add(c->d_rb_r0, (size_t)n_rep_blocks * 4);
     in.add(c->d_hc_part, (size_t)n_chunks * 4);
@@ -1795,8 +1806,8 @@ static int upload_impl(fseg_ctx *c, const fseg_batch *b) {
                 h_pos_off[k + 1] = h_pos_off[k] + len;
                 h_iv_tile0[k] = (int)t;
                 for (i64 y = 0; y < len; y += kSmoothTile) h_tile[t++] = TileDesc{h_pos_off[k], (int)y, (int)len};
-                // interval of the first position of every scan block
-                for (; bq < nb && bq * kScanBlock < h_pos_off[k + 1]; ++bq) h_blk[bq] = (int)k;
+                // interval of the first position of every block of the position compactions
+                for (; bq < nbp && bq * kPosBlock < h_pos_off[k + 1]; ++bq) h_blk[bq] = (int)k;
             }
             for (i64 r = b->part_rep_off[p]; r < b->part_rep_off[p + 1]; r += 256) { h_rb_part[rb] = p; h_rb_r0[rb] = (int)r; ++rb; }
             for (i64 r = b->part_rep_off[p]; r < b->part_rep_off[p + 1]; ++r) l += b->rep_weight[r];
@@ -1818,7 +1829,7 @@ static int upload_impl(fseg_ctx *c, const fseg_batch *b) {
                 ++ch;
             }
         }
-        h_blk[nb] = (int)(K - 1);
+        h_blk[nbp] = (int)(K - 1);
     }
     const double t_tables = tk.ms();
     // ---- the caller's arrays
@@ -1900,7 +1911,8 @@ static int upload_impl(fseg_ctx *c, const fseg_batch *b) {
         cv.add(c->d_y_raw, np8 * 4); cv.add(c->d_y, np8 * 8); cv.add(c->d_bits, 3 * flag_words(np8) * 4);
         cv.add(c->d_v, np8 * 8);
         cv.add(c->d_scan_state, ((size_t)nb * 3 + 1) * 8);
-        cv.add(c->d_bsum, ((size_t)nb + 2) * 4);
+        cv.add(c->d_bsum, ((size_t)nbp + 2) * 4);
+        cv.add(c->d_gsum, ((size_t)pos_groups(NPOS) + 2) * 4);
         cv.add(c->d_bsum_side, ((size_t)nb + 2) * 4);
         cv.add(c->d_g, np8 * 8); cv.add(c->d_pk, np8 * 4); cv.add(c->d_pf, np8); cv.add(c->d_kp, np8);
         cv.add(c->d_part_has2, ((size_t)np + 1) * 4);

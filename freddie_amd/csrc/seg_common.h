@@ -44,7 +44,19 @@ static_assert(kSmoothTile / kSumBlock <= 64 && kSumBlock == 16, "a tile's block 
 
 constexpr int kMaxRadius = 200;        // sigma <= 50, truncate 4.0 (py/freddie_segment.py:106,:755)
 
-constexpr int kScanBlock = 8192;       // elements per scan workgroup (256 threads x one 32-bit word of flags)
+constexpr int kScanBlock = 8192;       // elements per scan workgroup (256 threads x one 32-bit word of flags): the Y > 0 values (k_scan_emit<kEmitValues>, k_voff)
+
+// The two position compactions (candidates, final positions) flag about one position in two hundred: their workgroup takes four flag
+// words a thread (one 16-byte load), a quarter of the workgroups and of their chains of dependent loads.  The block sums are kept
+// raw, with the sum of every group of kPosGroup blocks beside them (k_pos_count): an emitting workgroup adds the groups before its
+// own and the blocks before it inside the group in one round of loads, so no single workgroup scans the sums between the two.
+constexpr int kPosBlock = 32768;       // positions per workgroup of a position compaction (256 threads x four words)
+constexpr int kPosGroup = 64;          // blocks per group of the two-level sums: a wave of k_pos_count each four blocks
+constexpr int kPosCountThreads = 1024; // k_pos_count: a workgroup per group
+static_assert(kPosBlock % (64 * 128) == 0 && kPosGroup % (kPosCountThreads / 64) == 0 && kPosGroup <= 64,
+              "k_pos_count: a wave takes whole blocks, 64 lanes x 16 bytes a round; k_scan_emit: a wave adds a group's block sums in one round");
+inline i64 pos_blocks(i64 n) { return (n + kPosBlock - 1) / kPosBlock; }
+inline i64 pos_groups(i64 n) { return (pos_blocks(n) + kPosGroup - 1) / kPosGroup; }
 
 inline size_t flag_words(i64 n_pos) { return ((size_t)n_pos + 31) / 32 + 64; }      // words of one flag mask (+ room for a tile's last word and the scans' last block)
 
@@ -350,6 +362,21 @@ __device__ __forceinline__ Flags32 load_flags32(const unsigned *flags, i64 i0, i
 }
 
 __device__ __forceinline__ int count_flags32(Flags32 f) { return __popc(f); }
+
+// The four words of positions i0 .. i0 + 127 (i0 a multiple of 128, i0 < n) as one 16-byte load, masked like load_flags32(); a plane
+// holds 64 words beyond its last position (flag_words()), and starts on a word, not on sixteen bytes.
+__device__ __forceinline__ void load_flags128(const unsigned *flags, i64 i0, i64 n, Flags32 w[4]) {
+    const int4u v = *reinterpret_cast<const int4u *>(flags + (i0 >> 5));
+    w[0] = (unsigned)v.x; w[1] = (unsigned)v.y; w[2] = (unsigned)v.z; w[3] = (unsigned)v.w;
+    if (i0 + 128 > n) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const i64 left = n - (i0 + 32 * j);
+            if (left < 32) w[j] &= left > 0 ? ((1u << (int)left) - 1u) : 0u;
+        }
+    }
+}
+__device__ __forceinline__ int count_flags128(const Flags32 w[4]) { return __popc(w[0]) + __popc(w[1]) + __popc(w[2]) + __popc(w[3]); }
 
 __device__ __forceinline__ void set_flag(unsigned *flags, i64 p) { atomicOr(&flags[p >> 5], 1u << (int)(p & 31)); }
 
@@ -746,6 +773,7 @@ __device__ __forceinline__ void window_exons(const int2 *__restrict__ lex, int2 
 // instances located every such problem and counted its kept reads, the 16-bit ones to drop nearly all of them again --
 // launches of 12-70 us in front of the classes behind them on config3 / config5.)
 constexpr int kRangeThreads = 1024;    // = kProbBlock: a workgroup of k_prob_range is a block of the problem scan
+constexpr int kRangeStage = 4096;      // lanes of a workgroup's partitions that k_prob_range bisects in LDS (32 KB: start and largest end of each)
 
 
 // Problem list by a prefix sum over the candidates: problem slot, pair / triple / coverage arena offsets and

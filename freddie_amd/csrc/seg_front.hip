@@ -419,15 +419,56 @@ __global__ void __launch_bounds__(kScan2Threads) k_scan2(int *bsum, i64 nb, u64 
     if (threadIdx.x == 0) { *total_out = (u64)carry_s; if (off_last) *off_last = (i64)carry_s; }
 }
 
+// Block sums of a position compaction (blocks of kPosBlock positions) and the sums of every kPosGroup blocks: a workgroup per
+// group of kPosGroup, a wave per four of its blocks, the sixteen 16-byte loads of a lane issued together -- a reduction per block, no scan,
+// and nothing for a single workgroup to scan afterwards (k_scan_emit<kEmitPositions> adds what lies before its block itself).
+__global__ void __launch_bounds__(kPosCountThreads) k_pos_count(const unsigned *flags, i64 n, int *bsum, int *gsum) {
+    __shared__ int wsum[kPosCountThreads / 64];
+    constexpr int kPer = kPosGroup / (kPosCountThreads / 64);        // blocks per wave
+    const int lane = lane_id(), wave = threadIdx.x >> 6;
+    const i64 nb = (n + kPosBlock - 1) / kPosBlock;
+    for (i64 g = blockIdx.x; g * kPosGroup < nb; g += gridDim.x) {   // (workgroup-uniform)
+        int cnt[kPer];
+#pragma unroll
+        for (int j = 0; j < kPer; ++j) {
+            const i64 b = g * kPosGroup + wave * kPer + j;
+            int s = 0;
+#pragma unroll
+            for (int r = 0; r < kPosBlock / (64 * 128); ++r) {
+                const i64 i0 = b * kPosBlock + (i64)(r * 64 + lane) * 128;
+                if (i0 < n) { Flags32 f[4]; load_flags128(flags, i0, n, f); s += count_flags128(f); }
+            }
+            cnt[j] = s;
+        }
+        int tot = 0;
+#pragma unroll
+        for (int j = 0; j < kPer; ++j) {
+            int x = cnt[j];
+            for (int d = 32; d >= 1; d >>= 1) x += __shfl_xor(x, d);
+            const i64 b = g * kPosGroup + wave * kPer + j;
+            if (lane == 0 && b < nb) bsum[b] = x;
+            tot += x;
+        }
+        if (lane == 0) wsum[wave] = tot;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            int t = 0;
+            for (int w = 0; w < kPosCountThreads / 64; ++w) t += wsum[w];
+            gsum[g] = t;
+        }
+        __syncthreads();
+    }
+}
+
 template <int MODE>
 __global__ void __launch_bounds__(256) k_scan_emit(const unsigned *flags, i64 n, const int *bsum /* or null */,
-                                                   u64 *state, u64 *total_out, i64 *off_last /* may be null */,
+                                                   const int *gsum /* positions, with bsum: sums of kPosGroup raw block sums; else null */, u64 *state, u64 *total_out, i64 *off_last /* may be null */,
                                                    unsigned *err, const double *y,
                                                    double *v, i64 K, const i64 *pos_off, const int *iv_start,
                                                    const int *blk_iv0, int *out_y, int *out_pos, i64 *out_off,
                                                    int force_stall /* tests: report a look-back stall */, int *out_iv /* may be null */) {
     if (force_stall && !bsum && blockIdx.x == 0 && threadIdx.x == 0) atomicOr(err, kErrScanStall);
-    // A block is 4 waves x 2048 consecutive positions.  Each wave first counts its flags (16-byte loads), the wave
+    // (values) A block is 4 waves x 2048 consecutive positions.  Each wave first counts its flags, the wave
     // offsets come from LDS, then the wave walks its positions in rows of 64: ballot -> rank, so the loads of y and
     // the stores of the compacted output are coalesced.
     __shared__ int wave_cnt[4];
@@ -435,17 +476,19 @@ __global__ void __launch_bounds__(256) k_scan_emit(const unsigned *flags, i64 n,
     __shared__ i64 bcast;
     const int lane = lane_id(), wave = threadIdx.x >> 6;
     const u64 lt_mask = (1ULL << lane) - 1ULL;
-    i64 nb = (n + kScanBlock - 1) / kScanBlock;
     if (MODE == kEmitPositions) {
-        // sparse flags (about one position in a hundred): every thread owns 32 consecutive positions and only the
-        // threads that hold a flag do any work.  The intervals the block's positions lie in (first interval of this block ..
-        // first interval of the next) are staged in LDS with one coalesced load: a flagged thread's interval search and its
-        // three look-ups would otherwise be a chain of five or six dependent global loads, which is what this kernel ran at.
+        // sparse flags (about one position in two hundred): every thread owns the 128 consecutive positions of four flag words (one
+        // 16-byte load) and only the threads that hold a flag do any work.  The intervals the block's positions lie in (first
+        // interval of this block .. first interval of the next) are staged in LDS with one coalesced load: a flagged thread's
+        // interval search and its three look-ups would otherwise be a chain of five or six dependent global loads, which is what
+        // this kernel ran at.
         constexpr int kIvStage = 768;
         __shared__ i64 po_s[kIvStage + 1];
         __shared__ int is_s[kIvStage];
+        __shared__ int pre_s;
         {
-            const i64 b = blockIdx.x;                                // grid == nb
+            const i64 b = blockIdx.x;                                // grid == nbp
+            const i64 nbp = (n + kPosBlock - 1) / kPosBlock;
             const i64 ka0 = blk_iv0[b], kb0 = (i64)blk_iv0[b + 1] + 1;      // intervals [ka0, kb0) (kb0 <= K)
             const int niv = (int)(kb0 - ka0);
             const bool staged = niv <= kIvStage;
@@ -453,22 +496,40 @@ __global__ void __launch_bounds__(256) k_scan_emit(const unsigned *flags, i64 n,
                 for (int x = threadIdx.x; x <= niv; x += blockDim.x) po_s[x] = pos_off[ka0 + x];
                 for (int x = threadIdx.x; x < niv; x += blockDim.x) is_s[x] = iv_start[ka0 + x];
             }
-            i64 i0 = b * kScanBlock + (i64)threadIdx.x * 32;
-            Flags32 f = 0;
+            if (bsum && wave == 0) {
+                // the flags before this block: the groups before this block's (nbp / kPosGroup values at most, 64 a round of
+                // independent loads) and the blocks before it inside its group -- one wave, nobody waited for
+                int p = 0;
+                const i64 g = b / kPosGroup;
+                for (i64 j = lane; j < g; j += 64) p += gsum[j];
+                for (i64 j = g * kPosGroup + lane; j < b; j += 64) p += bsum[j];
+                for (int d = 32; d >= 1; d >>= 1) p += __shfl_xor(p, d);
+                if (lane == 0) pre_s = p;
+            }
+            const i64 i0 = b * kPosBlock + (i64)threadIdx.x * 128;
+            Flags32 f[4] = {0u, 0u, 0u, 0u};
             int s = 0;
-            if (i0 < n) { f = load_flags32(flags, i0, n); s = count_flags32(f); }
+            if (i0 < n) { load_flags128(flags, i0, n, f); s = count_flags128(f); }
             int tot;
-            int ex = wg_exclusive_scan<4>(s, lds, &tot);             // (its barriers also publish the staged table)
-            ex += bsum ? bsum[b] : (int)scan_lookback(state, b, nb, tot, &bcast, total_out, off_last, err);
+            int ex = wg_exclusive_scan<4>(s, lds, &tot);             // (its barriers also publish the staged table and pre_s)
+            if (bsum) {
+                const int pre = pre_s;
+                ex += pre;
+                if (b == nbp - 1 && threadIdx.x == 0) {              // (the totals that k_scan2 writes on the values path)
+                    *total_out = (u64)((i64)pre + tot);
+                    if (off_last) *off_last = (i64)pre + tot;
+                }
+            } else ex += (int)scan_lookback(state, b, nbp, tot, &bcast, total_out, off_last, err);
             if (s) {
                 i64 k = -1, k_end = 0, k_base = 0;
                 int k_start = 0;
-                {
-                    unsigned w = f;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    unsigned w = f[j];
                     while (w) {
                         int e = __ffs(w) - 1;
                         w &= w - 1;
-                        i64 i = i0 + e;
+                        i64 i = i0 + 32 * j + e;
                         if (k < 0 || i >= k_end) {
                             // the interval of position i lies between the first intervals of this and the next block
                             const i64 ka = k < 0 ? ka0 : k + 1;
@@ -494,7 +555,7 @@ __global__ void __launch_bounds__(256) k_scan_emit(const unsigned *flags, i64 n,
         return;
     }
     {
-        const i64 b = blockIdx.x;                                    // grid == nb
+        const i64 b = blockIdx.x, nb = (n + kScanBlock - 1) / kScanBlock;      // grid == nb
         const i64 w0 = b * kScanBlock + (i64)wave * 2048;            // first position of this wave
         int s = 0;
         unsigned fm = 0;                                             // bit j = flag of position w0 + lane * 32 + j
@@ -516,7 +577,6 @@ __global__ void __launch_bounds__(256) k_scan_emit(const unsigned *flags, i64 n,
             // stores are coalesced.  Row q's 64 flags are the masks of lanes 2q and 2q+1 (two readlanes, no memory),
             // and the values of eight rows are loaded together from clamped addresses before any of them is used: a
             // load under a condition would be a branch with its own wait, one memory round trip per row.
-            i64 k = -1, k_end = 0, k_base = 0;
             // the rows that hold a flag at all (bit q of `rows`): the values Y > 0 come in runs of 2 * radius + 1 around the
             // splice sites, so six rows in ten of a typical batch hold none and their values are not loaded
             u64 rows = 0;
@@ -532,39 +592,23 @@ __global__ void __launch_bounds__(256) k_scan_emit(const unsigned *flags, i64 n,
             while (rows) {
                 u64 m[8];
                 double yv[8];
-                int qs[8];
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {                            // the next eight rows that hold flags
                     const int q = rows ? (int)__builtin_ctzll(rows) : -1;
-                    qs[e] = q;
                     rows = rows ? rows & (rows - 1) : 0;
                     const int qq = q < 0 ? 0 : q;
                     const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)fm, 2 * qq);
                     const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)fm, 2 * qq + 1);
                     m[e] = q < 0 ? 0 : ((u64)lo | ((u64)hi << 32));
                     const i64 i = w0 + qq * 64 + lane;
-                    if (MODE == kEmitValues) yv[e] = y[i < n ? i : n - 1];
+                    yv[e] = y[i < n ? i : n - 1];
                 }
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
                     if (!m[e]) continue;
-                    const i64 i = w0 + qs[e] * 64 + lane;
                     if ((m[e] >> lane) & 1ULL) {
                         const int d = ex + __popcll(m[e] & lt_mask);
-                        if (MODE == kEmitValues) v[d] = yv[e];
-                        else {
-                            if (k < 0 || i >= k_end) {
-                                // the interval of position i lies between the first intervals of this and the next block
-                                const i64 ka = k < 0 ? blk_iv0[b] : k, kb = (i64)blk_iv0[b + 1] + 1;
-                                k = ka + last_le(pos_off + ka, kb - ka, i);
-                                k_base = pos_off[k]; k_end = pos_off[k + 1];
-                            }
-                            int yy = (int)(i - k_base);
-                            out_y[d] = yy;
-                            if (out_pos) out_pos[d] = iv_start[k] + yy;
-                            if (out_iv) out_iv[d] = (int)k;
-                            if (yy == 0) out_off[k] = d;
-                        }
+                        v[d] = yv[e];
                     }
                     ex += __popcll(m[e]);
                 }

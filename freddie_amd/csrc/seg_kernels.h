@@ -38,9 +38,12 @@ __global__ void __launch_bounds__(256) k_scan1(const unsigned *flags, i64 n, int
 __global__ void __launch_bounds__(kScan2Threads) k_scan2(int *bsum, i64 nb, u64 *total_out, i64 *off_last /* may be null */);
 
 // seg_front.hip
+__global__ void __launch_bounds__(kPosCountThreads) k_pos_count(const unsigned *flags, i64 n, int *bsum, int *gsum);
+
+// seg_front.hip
 template <int MODE>
 __global__ void __launch_bounds__(256) k_scan_emit(const unsigned *flags, i64 n, const int *bsum /* or null */,
-                                                   u64 *state, u64 *total_out, i64 *off_last /* may be null */,
+                                                   const int *gsum /* or null */, u64 *state, u64 *total_out, i64 *off_last /* may be null */,
                                                    unsigned *err, const double *y,
                                                    double *v, i64 K, const i64 *pos_off, const int *iv_start,
                                                    const int *blk_iv0, int *out_y, int *out_pos, i64 *out_off,

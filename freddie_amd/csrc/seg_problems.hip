@@ -102,24 +102,56 @@ __global__ void __launch_bounds__(kRangeThreads) k_prob_range(Status *st, const 
     __shared__ int l_wide[kRangeThreads], l_n, l_red[kRangeThreads / 64];
     __shared__ i64 scan_lds[4 * kProbCols];
     __shared__ int l_mx[8];
+    // The workgroup's consecutive candidates lie in consecutive intervals, so in consecutive partitions, so their reads are ONE
+    // contiguous range of the lane list: [part_lane_off[first partition], part_lane_off[last partition + 1]).  While it fits the
+    // stage it is loaded once, coalesced, and both bisections of every problem run in LDS; a larger range (a config2 partition
+    // has 50 000 lanes) keeps the bisections in device memory, up to 18 dependent loads each.
+    __shared__ int s_pmax[kRangeStage], s_start[kRangeStage];
+    __shared__ i64 l_lane_a, l_lane_b;
     const i64 n_cand = (i64)st->n_cand;
     for (i64 c0 = (i64)blockIdx.x * blockDim.x; c0 < n_cand; c0 += (i64)gridDim.x * blockDim.x) {    // (workgroup-uniform)
         const i64 c = c0 + threadIdx.x;
         if (threadIdx.x == 0) l_n = 0;
-        __syncthreads();
+        // what every candidate's chain needs, asked for whether it is the right end of a problem or not (a load under `if (n > 0)`
+        // waits for n first): candidate -> interval -> partition -> lanes of the partition
+        int n = 0, g0 = 0, g1 = 0;
+        i64 pa = 0, pb = 0;
         if (c < n_cand) {
-            int n = cand_pn[c];
+            n = cand_pn[c];
+            const int k = cand_iv[c], y1 = cand_y[c];
+            const int part = iv_part[k], is = iv_start[k];
+            const int y0 = cand_y[n > 0 ? c - (n - 1) : c];
+            pa = part_lane_off[part]; pb = part_lane_off[part + 1];
+            g0 = is + y0; g1 = is + y1;
+            if (threadIdx.x == 0) l_lane_a = pa;
+            if (c == n_cand - 1 || threadIdx.x == kRangeThreads - 1) l_lane_b = pb;
+        }
+        __syncthreads();
+        const i64 A = l_lane_a;
+        const int n_stage = (int)(l_lane_b - A < (i64)kRangeStage + 1 ? l_lane_b - A : (i64)kRangeStage + 1);
+        const bool staged = n_stage <= kRangeStage;
+        if (staged) {
+            for (int x = threadIdx.x; x < n_stage; x += kRangeThreads) { s_pmax[x] = lane_pmax[A + x]; s_start[x] = lane_start[A + x]; }
+            __syncthreads();
+        }
+        if (c < n_cand) {
             int lo_lane = 0, n_lanes = 0;
             if (n > 0) {
-                int k = cand_iv[c];
-                int part = iv_part[k];
-                int g0 = iv_start[k] + cand_y[c - (n - 1)], g1 = iv_start[k] + cand_y[c];
-                i64 a = part_lane_off[part], L1 = part_lane_off[part + 1], b = L1;
-                while (a < b) { i64 m = (a + b) >> 1; if (lane_pmax[m] < g0) a = m + 1; else b = m; }
-                i64 lo = a;
-                b = L1;
-                while (a < b) { i64 m = (a + b) >> 1; if (lane_start[m] < g1) a = m + 1; else b = m; }
-                lo_lane = (int)lo; n_lanes = (int)(a - lo);
+                i64 a = pa, L1 = pb, b = L1;
+                if (staged) {
+                    int x = (int)(a - A), xe = (int)(L1 - A), y = xe;
+                    while (x < y) { const int m = (x + y) >> 1; if (s_pmax[m] < g0) x = m + 1; else y = m; }
+                    const int lo = x;
+                    y = xe;
+                    while (x < y) { const int m = (x + y) >> 1; if (s_start[m] < g1) x = m + 1; else y = m; }
+                    lo_lane = (int)(A + lo); n_lanes = x - lo;
+                } else {
+                    while (a < b) { i64 m = (a + b) >> 1; if (lane_pmax[m] < g0) a = m + 1; else b = m; }
+                    i64 lo = a;
+                    b = L1;
+                    while (a < b) { i64 m = (a + b) >> 1; if (lane_start[m] < g1) a = m + 1; else b = m; }
+                    lo_lane = (int)lo; n_lanes = (int)(a - lo);
+                }
             }
             cand_ll[c] = lo_lane; cand_ln[c] = n_lanes;
             // (fuse_lanes: what a problem may see to be solved whole, -1 in a batch that is not -- there nobody asks, and a
