@@ -379,7 +379,8 @@ def test_scoring_stage_fork_and_join(env, waiters, still_on, monkeypatch):
 def test_threshold_paths_on_the_goldens_and_big_partitions(mode, monkeypatch):
     """The variance threshold (:757-759, numpy's summation order) both ways -- a workgroup per partition (k_thr_part) and the
     batch-wide compaction with a workgroup per chunk -- on every golden of the reference (NaN threshold, sigma 50, ...), on a
-    partition with dozens of 8192-value chunks, and on a many-partition batch; bit-identical thresholds either way."""
+    partition with dozens of 8192-value chunks, and on a many-partition batch; bit-identical thresholds either way.
+    (The edges of both paths, count by count and word by word: tests/test_gpu_threshold_edges.py.)"""
     import goldens
     monkeypatch.setenv("FSEG_THR_PART", mode)
     ctx = _lib.Context(0)
