@@ -8,7 +8,9 @@ not depend on each other, so here round r of EVERY active partition of every tin
   run_ilp's read-out :601-635 -> read_out()         isoform exons = e on informative segments, the first remaining rep's I elsewhere;
                                                      corrections = the rep's first read's data, '-' where uninformative, 'X' where C, x and e
   output_isoforms :639-691 -> output_isoforms()
-The solve is HiGHS, not Gurobi: where a round's optimum is not unique the tie may be broken differently."""
+The solve is HiGHS, not Gurobi: where a round's optimum is not unique the tie may be broken differently.  Under
+settings["incumbent"] = "cutoff" / "fallback" a round is one more device call (Context.round_incumbents: a greedy feasible isoform per
+problem), which bounds the solves and, under "fallback", answers for a solve that ends without a proven optimum."""
 import os
 
 from . import cluster_prep, cluster_solve
@@ -17,9 +19,11 @@ MAX_WORKERS = 16
 FILES_PER_BATCH = 256
 
 
-def ilp_settings(recycle_model="constant", epsilon=0.2, offset=20, timeout=1, max_rounds=30, min_isoform_size=3, max_ilp=1000):
+def ilp_settings(recycle_model="constant", epsilon=0.2, offset=20, timeout=1, max_rounds=30, min_isoform_size=3, max_ilp=1000, incumbent="off"):
+    """incumbent: "off"; "cutoff": every round's greedy incumbents (Context.round_incumbents, one device call a round) bound the solves'
+    objective; "fallback": and stand in for a solve that ends without a proven optimum (status INCUMBENT)."""
     return dict(recycle_model=recycle_model, K=2, epsilon=epsilon, offset=offset, timeout=timeout, max_rounds=max_rounds, threads=1,
-                min_isoform_size=min_isoform_size, max_ilp=max_ilp)
+                min_isoform_size=min_isoform_size, max_ilp=max_ilp, incumbent=incumbent)
 
 
 def garbage_costs(tint, recycle_model):
@@ -115,6 +119,10 @@ def cluster_tints(tints, part0, ctx, settings, solve=cluster_solve.solve_round, 
         if not todo:
             break
         arr = ctx.round_models([part0[s["t"]] + s["q"] for s in todo], [s["remaining"] for s in todo])
+        inc = None
+        if settings.get("incumbent", "off") != "off":        # one more device call behind the models; a refused problem raises below
+            inc = ctx.round_incumbents([g for s in todo for g in (tints[s["t"]]["garbage_cost"][i] for i in s["remaining"])],
+                                       settings["epsilon"], settings["offset"])
         jobs = []
         for p, s in enumerate(todo):
             tint = tints[s["t"]]
@@ -126,6 +134,8 @@ def cluster_tints(tints, part0, ctx, settings, solve=cluster_solve.solve_round, 
             model["garbage"] = [tint["garbage_cost"][i] for i in s["remaining"]]
             model["max_lg"] = tint["max_lg"]
             model["key"] = (tint["id"], s["q"], round_num)        # (for a solver that logs, or replays: tests)
+            if inc is not None:
+                model["incumbent"] = cluster_prep.round_incumbent(inc, p)
             jobs.append((solve, model, settings))
         results = pool.map(_solve_job, jobs, chunksize=1) if pool is not None else [_solve_job(j) for j in jobs]
         for s, (_, model, _), (status, x, e) in zip(todo, jobs, results):
@@ -133,8 +143,9 @@ def cluster_tints(tints, part0, ctx, settings, solve=cluster_solve.solve_round, 
             logs[s["t"]].append((status, tint["id"], s["q"], round_num, len(s["remaining"])))
             if on_round is not None:
                 on_round(dict(tint=tint, partition=s["q"], round=round_num, remaining=list(s["remaining"]), incomp=s["incomp"], status=status,
-                              cost=cluster_solve.round_cost(model, x, e) if status == cluster_solve.OPTIMAL else None, x=x, e=e))
-            if status != cluster_solve.OPTIMAL:
+                              cost=cluster_solve.round_cost(model, x, e) if status in (cluster_solve.OPTIMAL, cluster_solve.INCUMBENT) else None,
+                              x=x, e=e))
+            if status not in (cluster_solve.OPTIMAL, cluster_solve.INCUMBENT):
                 s["active"] = False                          # (:750-751)
                 continue
             isoform = read_out(tint, s["remaining"], model, x, e)
@@ -194,7 +205,8 @@ def parse_args(argv=None):
     parser = argparse.ArgumentParser(
         description="Cluster aligned reads into isoforms.  The rounds' models are built on the GPU; the solve is HiGHS (scipy.optimize.milp), "
                     "not Gurobi: optimal ties may be broken differently from Gurobi's.  The .lp, .glog and .sol files are Gurobi's and are not "
-                    "written; --logs-dir holds the timeout.log files, with this program's status (OPTIMAL / NO_SOLUTION) in the first column.")
+                    "written; --logs-dir holds the timeout.log files, with this program's status (OPTIMAL / NO_SOLUTION, INCUMBENT under "
+                    "--incumbent fallback) in the first column.")
     recycle_models = ["constant", "exons", "introns", "relative"]
     parser.add_argument("-s", "--segment-dir", type=str, required=True, help="Path to Freddie segment directory of the reads")
     parser.add_argument("-rm", "--recycle-model", type=str, default="constant",
@@ -207,6 +219,10 @@ def parse_args(argv=None):
                         help="Maximum number of unique reads allowed for an ILP instance. ILP instances with more reads will have their input "
                              "broken into evenly sized problems, each with less than the max. Default 1000")
     parser.add_argument("-to", "--timeout", type=int, default=1, help="Solver time-out in minutes. Default: 1")
+    parser.add_argument("--incumbent", type=str, default="off", choices=list(cluster_solve.INCUMBENT_MODES),
+                        help="Greedy incumbents of every round's problems, computed on the GPU: cutoff = an objective bound for the solves; "
+                             "fallback = also the round's isoform when a solve ends without a proven optimum (status INCUMBENT).  Default: off "
+                             "(nothing changes)")
     parser.add_argument("-t", "--threads", type=int, default=1, help="Number of processes that solve (at most {})".format(MAX_WORKERS))
     parser.add_argument("-l", "--logs-dir", type=str, default=None, help="Directory path where logs will be outputted. Default: No log")
     parser.add_argument("-o", "--outdir", type=str, default="freddie_cluster/", help="Path to output directory. Default: freddie_cluster/")
@@ -226,7 +242,8 @@ def main(argv=None, make_context=None):
     import glob
     args = parse_args(argv)
     args.segment_dir = args.segment_dir.rstrip("/")
-    settings = ilp_settings(args.recycle_model, args.epsilon, args.gap_offset, args.timeout, args.max_rounds, args.min_isoform_size, args.max_ilp)
+    settings = ilp_settings(args.recycle_model, args.epsilon, args.gap_offset, args.timeout, args.max_rounds, args.min_isoform_size, args.max_ilp,
+                            args.incumbent)
     cluster_solve.check_settings(settings)
     jobs = []
     for contig in os.listdir(args.segment_dir):

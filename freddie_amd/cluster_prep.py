@@ -155,11 +155,13 @@ def split_list_evenly(l, m):
 # ---------------------------------------------------------------------------------------------------------------
 CLUSTER_SO = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libfreddie_cluster.so")
 CLUSTER_SRC = [os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "freddie_cluster.hip")]
+CLUSTER_HEADERS = [os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "clu_incumbent.h")]
 EXPORTS = ["fclu_abi_version", "fclu_create", "fclu_destroy", "fclu_last_error", "fclu_compat_graph", "fclu_last_timing",
            "fclu_partition", "fclu_partition_adj", "fclu_partition_results", "fclu_partition_timing",
            "fclu_preprocess", "fclu_preprocess_results", "fclu_partition_reads", "fclu_preprocess_timing",
            "fclu_group_reads", "fclu_partition_segment", "fclu_group_results", "fclu_group_timing",
-           "fclu_round_setup", "fclu_round_models", "fclu_round_results", "fclu_round_timing"]
+           "fclu_round_setup", "fclu_round_models", "fclu_round_results", "fclu_round_timing",
+           "fclu_round_incumbents", "fclu_round_incumbent_results", "fclu_round_incumbent_timing"]
 ERR_UNSUPPORTED = 3
 _lib = None
 
@@ -220,10 +222,15 @@ class _Rounds(ctypes.Structure):
     _fields_ = [("n_prob", ctypes.c_int32)] + [(n, ctypes.c_int64) for n in _ROUND_COUNTS] + [(n, ctypes.c_void_p) for n in _ROUND_ARRAYS]
 
 
+class _Incumbents(ctypes.Structure):
+    _fields_ = [("n_prob", ctypes.c_int32), ("n_mem", ctypes.c_int64)] + [
+        (n, ctypes.c_void_p) for n in ("cost2", "start", "grow_steps", "repair_steps", "mem_off", "mem")]
+
+
 def build(force=False, verbose=False):
     """hipcc -> libfreddie_cluster.so (in-tree; cross-compiles without a GPU)."""
     cmd = ["hipcc", "-O3", "--offload-arch=gfx950", "-shared", "-fPIC", "-I", _build.INCLUDE, "-o", CLUSTER_SO] + CLUSTER_SRC
-    _build.build_stamped(CLUSTER_SO, cmd, CLUSTER_SRC + [os.path.join(_build.INCLUDE, "freddie_cluster.h")], force, verbose)
+    _build.build_stamped(CLUSTER_SO, cmd, CLUSTER_SRC + CLUSTER_HEADERS + [os.path.join(_build.INCLUDE, "freddie_cluster.h")], force, verbose)
     return CLUSTER_SO
 
 
@@ -278,6 +285,12 @@ def load():
     L.fclu_round_results.argtypes = [vp, ctypes.POINTER(_Rounds)]
     L.fclu_round_timing.restype = ctypes.c_int
     L.fclu_round_timing.argtypes = [vp] + [ctypes.POINTER(ctypes.c_float)] * 3
+    L.fclu_round_incumbents.restype = ctypes.c_int
+    L.fclu_round_incumbents.argtypes = [vp, vp, ctypes.c_double, ctypes.c_double, ctypes.c_int32, ctypes.c_int32]
+    L.fclu_round_incumbent_results.restype = ctypes.c_int
+    L.fclu_round_incumbent_results.argtypes = [vp, ctypes.POINTER(_Incumbents)]
+    L.fclu_round_incumbent_timing.restype = ctypes.c_int
+    L.fclu_round_incumbent_timing.argtypes = [vp] + [ctypes.POINTER(ctypes.c_float)] * 3
     _lib = L
     return L
 
@@ -505,6 +518,43 @@ class Context:
         out["pairs"] = out["pairs"].reshape(-1, 2); out["grp"] = out["grp"].reshape(-1, 2); out["rows"] = out["rows"].reshape(-1, 3)
         return out
 
+    def round_incumbents(self, garbage, epsilon, offset, max_seeds=64):
+        """Greedy incumbents of the problems of the last round_models() call, one device call (include/freddie_cluster.h,
+        fclu_incumbents; the definition is cluster_solve.greedy_incumbent()): garbage = the garbage cost of every column of that batch,
+        problem by problem (multiples of 0.5).  Returns numpy arrays: cost2 (twice the cost; -1 for a refused problem), start,
+        grow_steps, repair_steps per problem, mem_off / mem (the members, as columns, ascending) and col_off; round_incumbent() cuts
+        one problem out."""
+        g = np.asarray(garbage, np.float64).reshape(-1)
+        g2 = np.rint(2.0 * g)
+        if g.size and not (np.isfinite(g).all() and (g2 == 2.0 * g).all() and (g2 >= 0).all() and (g2 < 2.0 ** 31).all()):
+            bad = int(np.flatnonzero(~(np.isfinite(g) & (g2 == 2.0 * g) & (g2 >= 0) & (g2 < 2.0 ** 31)))[0])
+            raise ClusterError("round_incumbents: garbage cost %r of column %d is not a multiple of 0.5 in [0, 2^30)" % (float(g[bad]), bad))
+        r = _Rounds()
+        rc = self._L.fclu_round_results(self._h, ctypes.byref(r))
+        if rc != 0:
+            raise ClusterError("round_incumbents: " + self._L.fclu_last_error(self._h).decode(), rc)
+        if g.size != int(r.n_cols):
+            raise ClusterError("round_incumbents: %d garbage costs for the %d columns of the last round_models() call" % (g.size, int(r.n_cols)))
+        col_off = _copy_out(r.col_off, r.n_prob + 1, np.int64)
+        g2 = np.ascontiguousarray(g2, np.int32)
+        rc = self._L.fclu_round_incumbents(self._h, g2.ctypes.data if g2.size else None, 1.0 - float(epsilon), 1.0 + float(epsilon), int(offset),
+                                           int(max_seeds))
+        if rc != 0:
+            raise ClusterError("fclu_round_incumbents: " + self._L.fclu_last_error(self._h).decode(), rc)
+        i = _Incumbents()
+        rc = self._L.fclu_round_incumbent_results(self._h, ctypes.byref(i))
+        if rc != 0:
+            raise ClusterError("fclu_round_incumbent_results: " + self._L.fclu_last_error(self._h).decode(), rc)
+        P = i.n_prob
+        return dict(n_prob=P, col_off=col_off, cost2=_copy_out(i.cost2, P, np.int64), start=_copy_out(i.start, P, np.int32),
+                    grow_steps=_copy_out(i.grow_steps, P, np.int32), repair_steps=_copy_out(i.repair_steps, P, np.int32),
+                    mem_off=_copy_out(i.mem_off, P + 1, np.int64), mem=_copy_out(i.mem, int(i.n_mem), np.int32))
+
+    def round_incumbent_timing(self):
+        a, b, f = ctypes.c_float(), ctypes.c_float(), ctypes.c_float()
+        self._L.fclu_round_incumbent_timing(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(f))
+        return dict(conflict_ms=a.value, starts_ms=b.value, pick_ms=f.value)
+
     def round_timing(self):
         a, b, f = ctypes.c_float(), ctypes.c_float(), ctypes.c_float()
         self._L.fclu_round_timing(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(f))
@@ -577,6 +627,16 @@ def round_model(arr, p):
                 groups=[tuple(x) for x in arr["grp"][g0:g1].tolist()],
                 group_segs=[list(zip(gs[int(go[g]):int(go[g + 1])].tolist(), gl[int(go[g]):int(go[g + 1])].tolist())) for g in range(g0, g1)],
                 gap_rows=[tuple(x) for x in arr["rows"][int(arr["row_off"][p]):int(arr["row_off"][p + 1])].tolist()])
+
+
+def round_incumbent(arr, p):
+    """Problem p of Context.round_incumbents(): (cost, x) -- the cost and a 0 / 1 per column -- or None when the problem was refused."""
+    if arr["cost2"][p] < 0:
+        return None
+    x = [0] * int(arr["col_off"][p + 1] - arr["col_off"][p])
+    for c in arr["mem"][int(arr["mem_off"][p]):int(arr["mem_off"][p + 1])].tolist():
+        x[c] = 1
+    return int(arr["cost2"][p]) / 2.0, x
 
 
 # ---------------------------------------------------------------------------------------------------------------

@@ -14,17 +14,26 @@ and the informative segments:
                     (1 + epsilon) G_g + offset + (1 - x_i) MAX_LG >= l   (:490-497)
   x_a + x_b <= 1 per incompatible pair (:505-511);  the garbage cost on 1 - x_i (:544).
 ``model`` = cluster_prep.round_model() of the problem plus ``garbage`` (a cost per column) and ``max_lg`` (the tint's summed segment
-lengths).  The relative recycle model needs E2I_min and the reference's preprocess_ilp() sets no garbage cost for it: refused."""
+lengths).  The relative recycle model needs E2I_min and the reference's preprocess_ilp() sets no garbage cost for it: refused.
+
+With K = 2 the model is a function of the chosen column set S alone: e = the OR of the chosen reps' I rows on the informative segments,
+cost = sum over S of popcount(C_c & e) + the others' garbage costs, S without an incompatible pair, every gap row of a member holding.
+greedy_incumbent() is a seeded greedy over exactly that (the definition the GPU's fclu_round_incumbents reproduces bit for bit); an
+incumbent in ``model["incumbent"]`` = (cost, x) gives solve_round() an objective cutoff and, under settings["incumbent"] == "fallback",
+the answer when the solve ends without a proven optimum (status INCUMBENT)."""
 import numpy as np
 
-OPTIMAL, NO_SOLUTION = "OPTIMAL", "NO_SOLUTION"
+OPTIMAL, NO_SOLUTION, INCUMBENT = "OPTIMAL", "NO_SOLUTION", "INCUMBENT"
 RECYCLE_MODELS = ("constant", "exons", "introns")
+INCUMBENT_MODES = ("off", "cutoff", "fallback")
 
 
 def check_settings(settings):
     if settings["recycle_model"] not in RECYCLE_MODELS:
         raise ValueError("recycle model %r: the solve supports %s (relative needs E2I_min and has no garbage cost in the reference either)"
                          % (settings["recycle_model"], ", ".join(RECYCLE_MODELS)))
+    if settings.get("incumbent", "off") not in INCUMBENT_MODES:
+        raise ValueError("incumbent mode %r: one of %s" % (settings["incumbent"], ", ".join(INCUMBENT_MODES)))
 
 
 def build_rows(model, settings):
@@ -66,10 +75,125 @@ def build_rows(model, settings):
     return cost, (data, rows, cols), np.array(lo), np.array(hi), ub, float(sum(model["garbage"]))
 
 
+def garbage2(garbage):
+    """Twice the garbage costs as ints; costs are multiples of 0.5 (and not negative), anything else is refused."""
+    out = []
+    for c, g in enumerate(garbage):
+        g2 = int(round(2 * g))
+        if g2 != 2 * g or g2 < 0 or g2 > 0x7fffffff:
+            raise ValueError("garbage cost %r of column %d is not a multiple of 0.5 in [0, 2^30)" % (g, c))
+        out.append(g2)
+    return out
+
+
+def _bits(x):
+    while x:
+        b = x & -x
+        yield b.bit_length() - 1
+        x ^= b
+
+
+def greedy_incumbent(model, settings, max_seeds=64):
+    """The seeded greedy incumbent of one round_model() dict (with ``garbage`` and ``max_lg``): dict(cost2, cost, start, members, x, e,
+    grow_steps, repair_steps), or None when no start ends feasible.  Rows are Python ints over the segment numbers (only informative
+    segments ever carry a bit).
+
+    Starts: n = min(R, max_seeds); start k < n is {k * R // n}, start n is the empty set.
+    Grow: with E = the OR of the members' I rows and cnt[j] = the members with C = 1 at j, every column outside S that conflicts with no
+        member has N = I_c & ~E and delta2 = 2 * (popcount(C_c & (E | N)) + sum of cnt[j] over N) - g2_c; the smallest delta2 (then the
+        smallest column) is added while it is negative.
+    Repair: G_g = the group's lengths summed over the segments in E; a member's row (g, l) is violated when lo_f * G_g - offset > l or
+        hi_f * G_g + offset < l (doubles, one rounded multiply and one rounded add; no tolerance, so whatever passes here passes the
+        model's rows); while a member has a violated row the one with the most (then the smallest column) leaves and E is recomputed.
+    Score: cost2 = the non-members' g2 + 2 * the members' popcount(C_c & E); the smallest cost2 wins, then the earliest start.  The
+        model gives the rows of a column OUTSIDE the set a slack of max_lg and no more, so a gap longer than the tint can still need
+        segments in E: a start with such a row violated -- the same test with offset + max_lg (one exact integer) for offset -- is
+        not feasible and has no cost2.  (The empty set is feasible unless a gap is longer than offset + max_lg.)"""
+    if max_seeds < 1:
+        raise ValueError("max_seeds is %r: at least 1" % (max_seeds,))
+    R = model["n_cols"]
+    g2 = garbage2(model["garbage"])
+    if len(g2) != R:
+        raise ValueError("%d garbage costs for %d columns" % (len(g2), R))
+    rows_i, rows_c, conf = [0] * R, [0] * R, [0] * R
+    for j, support in zip(model["inf_seg"], model["support"]):
+        for c in support:
+            rows_i[c] |= 1 << j
+    for c, segs in enumerate(model["corrections"]):
+        for j in segs:
+            rows_c[c] |= 1 << j
+    for a, b in model["pairs"]:
+        conf[a] |= 1 << b
+        conf[b] |= 1 << a
+    col_rows = [[] for _ in range(R)]
+    for c, g, l in model["gap_rows"]:
+        col_rows[c].append((g, l))
+    lo_f, hi_f, offset = 1.0 - settings["epsilon"], 1.0 + settings["epsilon"], settings["offset"]
+    out_offset = offset + int(model["max_lg"])
+    n = min(R, max_seeds)
+    best = None
+    for k in range(n + 1):
+        members, E, blocked, cnt, grow_steps, repair_steps = 0, 0, 0, {}, 0, 0
+
+        def add(c):
+            nonlocal members, E, blocked
+            members |= 1 << c
+            blocked |= conf[c]
+            E |= rows_i[c]
+            for j in _bits(rows_c[c]):
+                cnt[j] = cnt.get(j, 0) + 1
+
+        if k < n:
+            add(k * R // n)
+        for _ in range(R):
+            pick = None
+            for c in range(R):
+                if (members | blocked) >> c & 1:
+                    continue
+                N = rows_i[c] & ~E
+                d2 = 2 * (bin(rows_c[c] & (E | N)).count("1") + sum(cnt.get(j, 0) for j in _bits(N))) - g2[c]
+                if pick is None or d2 < pick[0]:
+                    pick = (d2, c)
+            if pick is None or pick[0] >= 0:
+                break
+            add(pick[1])
+            grow_steps += 1
+        def violated(c, off):
+            bad = 0
+            for g, l in col_rows[c]:
+                G = sum(ln for j, ln in model["group_segs"][g] if E >> j & 1)
+                if lo_f * G - off > l or hi_f * G + off < l:
+                    bad += 1
+            return bad
+
+        while members:
+            worst = None
+            for c in _bits(members):
+                bad = violated(c, offset)
+                if bad and (worst is None or bad > worst[0]):
+                    worst = (bad, c)
+            if worst is None:
+                break
+            members ^= 1 << worst[1]
+            repair_steps += 1
+            E = 0
+            for c in _bits(members):
+                E |= rows_i[c]
+        if any(violated(c, out_offset) for c in range(R) if not members >> c & 1):
+            continue
+        cost2 = sum(g2[c] for c in range(R) if not members >> c & 1) + 2 * sum(bin(rows_c[c] & E).count("1") for c in _bits(members))
+        if best is None or cost2 < best["cost2"]:
+            best = dict(cost2=cost2, cost=cost2 / 2.0, start=k, members=list(_bits(members)), grow_steps=grow_steps, repair_steps=repair_steps,
+                        x=[members >> c & 1 for c in range(R)], e=[E >> j & 1 for j in model["inf_seg"]])
+    return best
+
+
 def solve_round(model, settings):
     """(status, x, e): status OPTIMAL only for a proven optimum within timeout minutes (anything else is NO_SOLUTION, as :591-592),
     x a 0 / 1 per column, e a 0 / 1 per informative segment (beside model['inf_seg']).  The relative gap is 0: costs are multiples of
-    0.5 and a relative gap would accept a worse isoform."""
+    0.5 and a relative gap would accept a worse isoform.  model["incumbent"] = (cost, x) of a feasible column set, when there is one,
+    adds the row objective <= cost + 0.25 (the incumbent and every optimum stay feasible); under settings["incumbent"] == "fallback" a
+    solve without a proven optimum returns (INCUMBENT, the incumbent's x, its e = the OR of the members' support)."""
     from scipy.optimize import Bounds, LinearConstraint, milp
     from scipy.sparse import csr_matrix
     check_settings(settings)
@@ -81,9 +205,15 @@ def solve_round(model, settings):
     integrality = np.zeros(n)
     integrality[:R + E] = 1
     constraints = [LinearConstraint(csr_matrix((data, (rows, cols)), shape=(lo.size, n)), lo, hi)] if lo.size else []
+    incumbent = model.get("incumbent")
+    if incumbent is not None:                                # cost . v + sum(garbage) <= the incumbent's cost + 0.25
+        constraints.append(LinearConstraint(csr_matrix(cost.reshape(1, n)), -np.inf, incumbent[0] + 0.25 - float(sum(model["garbage"]))))
     res = milp(cost, integrality=integrality, bounds=Bounds(np.zeros(n), ub), constraints=constraints,
                options=dict(time_limit=settings["timeout"] * 60, mip_rel_gap=0.0, disp=False))
     if res.status != 0 or res.x is None:
+        if incumbent is not None and settings.get("incumbent", "off") == "fallback":
+            x = [int(v) for v in incumbent[1]]
+            return INCUMBENT, x, [int(any(x[c] for c in support)) for support in model["support"]]
         return NO_SOLUTION, None, None
     return OPTIMAL, [int(v > 0.5) for v in res.x[:R]], [int(v > 0.5) for v in res.x[R:R + E]]
 

@@ -21,6 +21,8 @@
 #include "freddie_cluster.h"
 
 #include <hip/hip_runtime.h>
+
+#include "clu_incumbent.h"   // (behind the runtime: its functions are __host__ __device__)
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 
@@ -929,7 +931,7 @@ __global__ void __launch_bounds__(256) k_ggather(int n_tint, i64 n_words, const 
 struct RoundProb {
     i64 col0, rbits_off, rep0, pair0, pair1, inf_off, seg0;   // first column (in rids); the tint's first I / C word, first rep and first
                                                               // segment length; the partition's pairs; the informative row's first word
-    int n, n_seg, w, pad;                                     // columns, segments, words per row
+    int n, n_seg, w, tint;                                    // columns, segments, words per row; the tint (the host's own note)
 };
 
 constexpr int kRoundCounts = 4;                  // per problem: informative segments, support entries, correction terms, pairs
@@ -1188,6 +1190,198 @@ __global__ void __launch_bounds__(256) k_gap_fill(const i64 *gid, i64 n_rows, co
     }
 }
 
+// ================================================================================================================
+// Greedy round incumbents (fclu_round_incumbents): with K = 2 a round's model is a function of the chosen column set S alone (e = the OR
+// of the members' I rows on the informative segments, cost = the members' popcount(C & e) + the others' garbage costs, no incompatible
+// pair in S, every gap row of a member holding), so a feasible S of low cost is bit-row arithmetic on what fclu_round_models has just
+// left on the device.  The definition is cluster_solve.greedy_incumbent()'s docstring; what one thread computes is clu_incumbent.h.
+// ================================================================================================================
+struct IncProb {
+    i64 col0, rbits_off, inf_off;     // RoundProb's: first column; the tint's first I / C word; the informative row
+    i64 conf_off, pair0, pair1;       // the problem's R x cw conflict matrix (uint32 words); its pairs, as columns, in the round's pair list
+    i64 grp0;                         // its first gap group, numbered through the batch
+    i64 slot0, mrow_off;              // its starts' first result slot; their member rows' first word (cw words a start)
+    i64 max_lg;                       // MAX_ISOFORM_LG: the tint's summed segment lengths, the slack of the gap rows of a column outside the set
+    int n, n_seg, w, cw, n_starts, n_seeds;   // columns, segments, words per row, words per column set; starts = n_seeds + 1 (the last is empty)
+};
+
+constexpr i64 kIncNoCost = 0x7fffffffffffffffll;   // cost2 of a start that is not feasible
+constexpr int kIncMaxCols = 32768;    // columns of one problem: delta2 stays inside 32 bits (2 x 9600 x 32769 < 2^31) and a start is blockIdx.y
+
+// the smallest of the workgroup's 256 keys, in every thread; s_key: 4 words of LDS; synchronises before it returns
+__device__ __forceinline__ u64 block_min_key(u64 v, u64 *s_key) {
+    for (int s = 32; s > 0; s >>= 1) { const u64 o = __shfl_xor(v, s); v = o < v ? o : v; }
+    if (lane_id() == 0) s_key[threadIdx.x >> 6] = v;
+    __syncthreads();
+    u64 r = s_key[0];
+    for (int x = 1; x < 4; ++x) r = s_key[x] < r ? s_key[x] : r;
+    __syncthreads();
+    return r;
+}
+
+// Each problem's remaining pairs as a symmetric R x R bit matrix (zeroed before the launch).  A workgroup per problem; OR does not depend
+// on the order the atomics arrive in.  A pair with an end outside the problem's columns cannot come from k_round, and sets nothing.
+__global__ void __launch_bounds__(256) k_inc_conflict(const int *list, const IncProb *probs, const int2 *pairs, unsigned *conf) {
+    const IncProb d = probs[list[blockIdx.x]];
+    for (i64 i = d.pair0 + threadIdx.x; i < d.pair1; i += 256) {
+        const int2 pr = pairs[i];
+        const bool ok = (unsigned)pr.x < (unsigned)d.n && (unsigned)pr.y < (unsigned)d.n;
+        const int a = inc_clamp(pr.x, 0, d.n - 1), b = inc_clamp(pr.y, 0, d.n - 1);
+        if (ok) {
+            atomicOr(&conf[d.conf_off + (i64)a * d.cw + (b >> 5)], 1u << (b & 31));
+            atomicOr(&conf[d.conf_off + (i64)b * d.cw + (a >> 5)], 1u << (a & 31));
+        }
+    }
+}
+
+// dynamic LDS of k_inc_start for one problem: cnt (a counter per bit of a row), the member and the blocked bit rows, and (LDS) the I and
+// C rows at k_round's stride
+inline size_t inc_lds_bytes(int R, int W, int CW, bool rows) { return 4 * ((size_t)W * 32 + 2 * (size_t)CW + (rows ? 2 * (size_t)R * (size_t)(W | 1) : 0)); }
+
+// A workgroup per (problem, start): blockIdx.x = the problem (through list), blockIdx.y = the start.  Grow, repair and score of that one
+// start, whole, with every loop bounded by R; the candidates (grow) and the members (repair) are spread over the threads and a step's
+// choice is ONE packed key reduced over the workgroup (smaller delta2, then smaller column; more violated rows, then smaller column).
+// LDS: the rows (ANDed with the informative row) are staged as in k_round; !LDS: read where preprocess left them and ANDed on the way.
+// Results per start: cost2, the two step counts and the member bit row; k_inc_pick chooses.  No workgroup reads another's.
+template <bool LDS>
+__global__ void __launch_bounds__(256) k_inc_start(const int *list, const IncProb *probs, const unsigned *ibits, const unsigned *cbits, const int *rids,
+                                                   const unsigned *inf_bits, const unsigned *conf, const int *g2, const i64 *col_row_off, i64 n_rows,
+                                                   const int *rows, const i64 *grp_seg_off, const int *grp_seg, const int *grp_len, i64 n_grp,
+                                                   i64 n_grp_seg, double lo_f, double hi_f, int offset, i64 *cost2, int *steps, unsigned *mrows) {
+    extern __shared__ unsigned s_dyn[];
+    __shared__ unsigned s_E[kMaxWords], s_inf[kMaxWords];
+    __shared__ u64 s_key[4];
+    __shared__ i64 s_sum[4];
+    __shared__ int s_bad[4];
+    const IncProb d = probs[list[blockIdx.x]];
+    const int k = blockIdx.y;
+    if (k >= d.n_starts) return;                              // (the grid's height is the batch's largest count of starts)
+    const int tid = threadIdx.x, lane = lane_id(), wave = tid >> 6;
+    const int R = d.n, W = d.w, M = d.n_seg, CW = d.cw, S = W | 1;
+    int *s_cnt = reinterpret_cast<int *>(s_dyn);
+    unsigned *s_mem = s_dyn + W * 32, *s_blk = s_mem + CW, *s_rows = s_blk + CW;
+    const int *prids = rids + d.col0;
+    const int *pg2 = g2 + d.col0;
+    for (int x = tid; x < W * 32; x += 256) s_cnt[x] = 0;
+    for (int x = tid; x < 2 * CW; x += 256) s_mem[x] = 0u;   // (member and blocked rows lie side by side)
+    for (int w = tid; w < W; w += 256) { s_E[w] = 0u; s_inf[w] = inf_bits[d.inf_off + w]; }
+    __syncthreads();
+    if (LDS) {
+        for (int x = tid; x < R * W; x += 256) {
+            const int c = x / W, w = x - c * W;
+            const i64 src = d.rbits_off + (i64)prids[c] * W + w;
+            s_rows[c * S + w] = ibits[src] & s_inf[w];
+            s_rows[(R + c) * S + w] = cbits[src] & s_inf[w];
+        }
+        __syncthreads();
+    }
+    const unsigned *inf = LDS ? nullptr : s_inf;             // (the staged rows carry the informative row already)
+    const auto row_i = [&](int c) { return LDS ? s_rows + c * S : ibits + d.rbits_off + (i64)prids[c] * W; };
+    const auto row_c = [&](int c) { return LDS ? s_rows + (R + c) * S : cbits + d.rbits_off + (i64)prids[c] * W; };
+    const auto add = [&](int c) {                             // c is the workgroup's: E, cnt, blocked and the member row take column c
+        const unsigned *ri = row_i(c), *rc = row_c(c);
+        for (int w = tid; w < W; w += 256) inc_add_word(ri[w] & s_inf[w], rc[w] & s_inf[w], w, s_E, s_cnt);
+        for (int w = tid; w < CW; w += 256) s_blk[w] |= conf[d.conf_off + (i64)c * CW + w];
+        if (tid == 0) s_mem[c >> 5] |= 1u << (c & 31);
+        __syncthreads();
+    };
+    const int seed = inc_start_col(k, d.n_seeds, R);
+    if (seed >= 0 && seed < R) add(seed);
+    int grow = 0, repair = 0;
+    for (int step = 0; step < R; ++step) {                    // ---- grow
+        u64 key = kIncKeyNone;
+        for (int c = tid; c < R; c += 256) {
+            if (inc_bit(s_mem, c) || inc_bit(s_blk, c)) continue;
+            const u64 kk = inc_grow_key(inc_delta2(row_i(c), row_c(c), inf, W, s_E, s_cnt, pg2[c]), c);
+            key = kk < key ? kk : key;
+        }
+        key = block_min_key(key, s_key);
+        if (key == kIncKeyNone || inc_key_delta2(key) >= 0) break;
+        add(inc_clamp(inc_key_col(key), 0, R - 1));
+        ++grow;
+    }
+    for (int step = 0; step < R; ++step) {                    // ---- repair: at most one member leaves a step
+        u64 key = kIncKeyNone;
+        for (int c = tid; c < R; c += 256) {
+            if (!inc_bit(s_mem, c)) continue;
+            i64 r0 = col_row_off[d.col0 + c], r1 = col_row_off[d.col0 + c + 1];
+            r0 = r0 < 0 ? 0 : r0 > n_rows ? n_rows : r0;
+            r1 = r1 < r0 ? r0 : r1 > n_rows ? n_rows : r1;
+            const int bad = inc_violations(r0, r1, rows, d.grp0, n_grp, grp_seg_off, n_grp_seg, grp_seg, grp_len, M, s_E, lo_f, hi_f, (i64)offset);
+            if (bad) { const u64 kk = inc_repair_key(bad, c); key = kk < key ? kk : key; }
+        }
+        key = block_min_key(key, s_key);
+        if (key == kIncKeyNone) break;
+        const int out = inc_clamp(inc_key_col(key), 0, R - 1);
+        if (tid == 0) s_mem[out >> 5] &= ~(1u << (out & 31));
+        for (int w = tid; w < W; w += 256) s_E[w] = 0u;
+        __syncthreads();
+        const int stripes = W >= 256 ? 1 : 256 / W;           // E again from the members that are left (OR: any order)
+        for (int x = tid; x < stripes * W; x += 256) {
+            const int st = x / W, w = x - st * W;
+            unsigned o = 0u;
+            for (int c = st; c < R; c += stripes) if (inc_bit(s_mem, c)) o |= row_i(c)[w] & s_inf[w];
+            if (o) atomicOr(&s_E[w], o);
+        }
+        __syncthreads();
+        ++repair;
+    }
+    i64 sum = 0;                                              // ---- score, from scratch; a violated row of a column outside the set (its
+    int bad_out = 0;                                          //      slack is MAX_ISOFORM_LG, no more) leaves the start without a cost
+    for (int c = tid; c < R; c += 256) {
+        const bool in = inc_bit(s_mem, c);
+        sum += inc_score_col(in, row_c(c), inf, W, s_E, pg2[c]);
+        if (!in) {
+            i64 r0 = col_row_off[d.col0 + c], r1 = col_row_off[d.col0 + c + 1];
+            r0 = r0 < 0 ? 0 : r0 > n_rows ? n_rows : r0;
+            r1 = r1 < r0 ? r0 : r1 > n_rows ? n_rows : r1;
+            bad_out += inc_violations(r0, r1, rows, d.grp0, n_grp, grp_seg_off, n_grp_seg, grp_seg, grp_len, M, s_E, lo_f, hi_f, (i64)offset + d.max_lg);
+        }
+    }
+    for (int s = 32; s > 0; s >>= 1) { sum += __shfl_xor(sum, s); bad_out += __shfl_xor(bad_out, s); }
+    if (lane == 0) { s_sum[wave] = sum; s_bad[wave] = bad_out; }
+    __syncthreads();
+    if (tid == 0) {
+        cost2[d.slot0 + k] = s_bad[0] + s_bad[1] + s_bad[2] + s_bad[3] ? kIncNoCost : s_sum[0] + s_sum[1] + s_sum[2] + s_sum[3];
+        steps[2 * (d.slot0 + k)] = grow; steps[2 * (d.slot0 + k) + 1] = repair;
+    }
+    for (int w = tid; w < CW; w += 256) mrows[d.mrow_off + (i64)k * CW + w] = s_mem[w];
+}
+
+// A workgroup per problem: the feasible start with the smallest cost2, at equal cost2 the earliest; its cost2, number and step counts, and its
+// members, ascending, at the front of the problem's own columns of mem_cols (mem_cnt of them; the host lays them end to end).
+__global__ void __launch_bounds__(256) k_inc_pick(const int *list, const IncProb *probs, const i64 *cost2, const int *steps, const unsigned *mrows,
+                                                  i64 *out_cost2, int *out_start, int *out_grow, int *out_repair, int *mem_cols, int *mem_cnt) {
+    __shared__ i64 s_cost[256];
+    __shared__ int s_start[256];
+    __shared__ i64 s_wave[4];
+    const int p = list[blockIdx.x], tid = threadIdx.x;
+    const IncProb d = probs[p];
+    i64 best = kIncNoCost;
+    int at = 0x7fffffff;
+    for (int k = tid; k < d.n_starts; k += 256) {            // (k ascends: a thread keeps its earliest)
+        const i64 v = cost2[d.slot0 + k];
+        if (v < best) { best = v; at = k; }
+    }
+    s_cost[tid] = best; s_start[tid] = at;
+    __syncthreads();
+    for (int x = 0; x < 256; ++x)
+        if (s_cost[x] < best || (s_cost[x] == best && s_start[x] < at)) { best = s_cost[x]; at = s_start[x]; }
+    if (best == kIncNoCost) return;                           // no feasible start: the problem keeps cost2 = -1, start = -1 and no member
+    at = inc_clamp(at, 0, d.n_starts - 1);
+    if (tid == 0) { out_cost2[p] = best; out_start[p] = at; out_grow[p] = steps[2 * (d.slot0 + at)]; out_repair[p] = steps[2 * (d.slot0 + at) + 1]; }
+    i64 carry = 0;
+    for (int w0 = 0; w0 < d.cw; w0 += 256) {
+        const int w = w0 + tid;
+        unsigned m = w < d.cw ? mrows[d.mrow_off + (i64)at * d.cw + w] : 0u;
+        i64 total;
+        i64 x = carry + block_scan(__popc(m), total, s_wave);
+        while (m) { if (x < d.n) mem_cols[d.col0 + x] = w * 32 + __ffs((int)m) - 1; ++x; m &= m - 1; }
+        carry += total;
+    }
+    if (tid == 0) mem_cnt[p] = (int)(carry < d.n ? carry : d.n);
+}
+
 }  // namespace
 
 // ---- buffers and the context -------------------------------------------------------------------------------------------
@@ -1225,9 +1419,10 @@ constexpr int kBurst = 4;     // gated passes (pruning, components) enqueued per
 struct fclu_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
-    // every event, one list to create and destroy; by stage: the graph (ev), fclu_partition (pev), _preprocess (qev), _group_reads (gev), _round_models (rev)
-    hipEvent_t events[3 + 6 + 6 + 5 + 5] = {};
-    hipEvent_t *const ev = events, *const pev = ev + 3, *const qev = pev + 6, *const gev = qev + 6, *const rev = gev + 5;
+    // every event, one list to create and destroy; by stage: the graph (ev), fclu_partition (pev), _preprocess (qev), _group_reads (gev), _round_models (rev),
+    // _round_incumbents (iev)
+    hipEvent_t events[3 + 6 + 6 + 5 + 5 + 4] = {};
+    hipEvent_t *const ev = events, *const pev = ev + 3, *const qev = pev + 6, *const gev = qev + 6, *const rev = gev + 5, *const iev = rev + 5;
     std::string err;
     float compat_ms = 0.f, prune_ms = 0.f;
     Buf<TintDesc> tints; Buf<int4> tiles; Buf<int2> word_tint; Buf<i64> tint_word0;
@@ -1296,13 +1491,28 @@ struct fclu_ctx {
         HostBuf<uint32_t> inf_bits; HostBuf<int2> pairs;
         HostBuf<int32_t> refused, inf_seg, sup_cols, corr_seg, grp, grp_seg, grp_len, rows;
     } rh;
-    std::vector<int64_t> r_rep_off, r_gap_off, r_seg_off, r_rep_part;
+    std::vector<int64_t> r_rep_off, r_gap_off, r_seg_off, r_rep_part, r_max_lg;
     std::vector<int32_t> r_n_seg, r_part_tint, r_rep_stamp, r_part_stamp;
     int r_epoch = 0;
     bool round_src_ok = false, round_ready = false;
     float rcount_ms = 0.f, rgaps_ms = 0.f, rfill_ms = 0.f;
     fclu_rounds rounds = {};
     bool have_rounds = false;
+    // fclu_round_incumbents(): the last fclu_round_models() call's device arrays (rd) are the input and r_probs is what the host kept of its
+    // problems; device arrays (id: the conflict matrices, per start cost2 / step counts / member rows, per problem the choice) and the pinned
+    // copies fclu_round_incumbent_results() hands out (ih; mem_cols / mem_cnt are the members as the device leaves them, a problem's at its
+    // own columns, which the host lays end to end into mem)
+    std::vector<RoundProb> r_probs;
+    struct {
+        Buf<IncProb> probs; Buf<unsigned> conf, mrows; Buf<i64> start_cost2, cost2;
+        Buf<int> list, g2, steps, start, grow, repair, mem_cols, mem_cnt;
+    } id;
+    struct {
+        HostBuf<int64_t> cost2, mem_off; HostBuf<int32_t> start, grow, repair, mem, mem_cols, mem_cnt;
+    } ih;
+    float iconf_ms = 0.f, istart_ms = 0.f, ipick_ms = 0.f;
+    fclu_incumbents incs = {};
+    bool have_incs = false;
     // (the buffers free themselves behind it, on this device)
     ~fclu_ctx() {
         (void)hipSetDevice(device);
@@ -2198,6 +2408,8 @@ int round_setup(fclu_ctx *c, const int64_t *gap_off, const int32_t *gaps, const 
     c->r_epoch = 0;
     c->r_gap_off.assign(gap_off, gap_off + N + 1);
     c->r_seg_off.assign(seg_off, seg_off + T + 1);
+    c->r_max_lg.assign((size_t)T, 0);
+    for (int t = 0; t < T; ++t) for (i64 j = seg_off[t]; j < seg_off[t + 1]; ++j) c->r_max_lg[(size_t)t] += seg_len[j];
     auto &D = c->rd;
     hipStream_t s = c->stream;
     HIP_TRY(c, D.gap_off.grow((size_t)N + 1)); HIP_TRY(c, D.gaps.grow((size_t)n_gaps * 3)); HIP_TRY(c, D.seg_len.grow((size_t)n_seg_total));
@@ -2242,7 +2454,7 @@ int round_stage(fclu_ctx *c, const Knobs &k, const fclu_round_batch *b, RoundRun
         RoundProb &d = r.probs[(size_t)p];
         d.col0 = c0; d.rbits_off = c->ph.rbits_off.p[t]; d.rep0 = c->r_rep_off[(size_t)t]; d.pair0 = pp.part_pair_off[q]; d.pair1 = pp.part_pair_off[q + 1];
         d.inf_off = n_inf_bits; d.seg0 = c->r_seg_off[(size_t)t];
-        d.n = (int)n; d.n_seg = c->r_n_seg[(size_t)t]; d.w = std::max((d.n_seg + 31) / 32, 1);
+        d.n = (int)n; d.n_seg = c->r_n_seg[(size_t)t]; d.w = std::max((d.n_seg + 31) / 32, 1); d.tint = t;
         const i64 n_t = c->r_rep_off[(size_t)t + 1] - d.rep0;
         r.inf_bits_off[(size_t)p] = n_inf_bits; r.prob_row_off[(size_t)p] = G;
         n_inf_bits += d.w;
@@ -2285,7 +2497,7 @@ void round_launch(fclu_ctx *c, const RoundRun &r) {
 }
 
 int round_device(fclu_ctx *c, const Knobs &k, const fclu_round_batch *b) {
-    c->have_rounds = false;
+    c->have_rounds = c->have_incs = false;
     c->rcount_ms = c->rgaps_ms = c->rfill_ms = 0.f;
     if (!c->round_ready || !c->round_src_ok || !c->have_parts)
         return fail(c, FCLU_ERR_ARG, "fclu_round_models: no fclu_round_setup() behind the context's last partition call");
@@ -2411,7 +2623,126 @@ int round_device(fclu_ctx *c, const Knobs &k, const fclu_round_batch *b) {
     (void)hipEventElapsedTime(&c->rcount_ms, c->rev[0], c->rev[1]);
     (void)hipEventElapsedTime(&c->rgaps_ms, c->rev[1], c->rev[2]);
     (void)hipEventElapsedTime(&c->rfill_ms, c->rev[3], c->rev[4]);
+    c->r_probs = r.probs;
     c->have_rounds = true;
+    return FCLU_OK;
+}
+
+// ---- greedy incumbents of the last round's problems (fclu_round_incumbents) ---------------------------------------------------
+int incumbents_device(fclu_ctx *c, const Knobs &k, const int32_t *g2, double lo_f, double hi_f, int32_t offset, int32_t max_seeds) {
+    c->have_incs = false;
+    c->iconf_ms = c->istart_ms = c->ipick_ms = 0.f;
+    if (!c->have_rounds || !c->round_ready || !c->round_src_ok || !c->have_parts)
+        return fail(c, FCLU_ERR_ARG, "fclu_round_incumbents: no successful fclu_round_models() stands behind the call (none was made, it failed, or a later "
+                                     "call ended the rounds' source)");
+    const fclu_rounds &o = c->rounds;
+    const int P = o.n_prob;
+    const i64 C = o.n_cols, G = o.n_gap_rows;
+    if (max_seeds < 1) return fail(c, FCLU_ERR_ARG, "fclu_round_incumbents: max_seeds is %d, it must be at least 1", (int)max_seeds);
+    if (offset < 0 || !(lo_f == lo_f) || !(hi_f == hi_f) || lo_f - lo_f != 0.0 || hi_f - hi_f != 0.0)
+        return fail(c, FCLU_ERR_ARG, "fclu_round_incumbents: offset is negative or a factor is not finite");
+    if (C > 0 && !g2) return fail(c, FCLU_ERR_ARG, "fclu_round_incumbents: g2 is null");
+    for (i64 x = 0; x < C; ++x) if (g2[x] < 0) return fail(c, FCLU_ERR_ARG, "fclu_round_incumbents: g2[%lld] is negative", x);
+    if ((int)c->r_probs.size() != P) return fail(c, FCLU_ERR_ARG, "fclu_round_incumbents: the round's problems are gone");
+    HIP_TRY(c, hipSetDevice(c->device));
+    auto &D = c->id;
+    auto &H = c->ih;
+    auto &RD = c->rd;
+    hipStream_t s = c->stream;
+    std::vector<IncProb> probs((size_t)P);
+    std::vector<int> groups[3];                              // by path, as the models': rows in LDS (tiny, small), rows in device memory
+    size_t lds[3] = {0, 0, 0};
+    int height[3] = {0, 0, 0};
+    i64 n_conf = 0, n_slots = 0, n_mrow = 0;
+    for (int p = 0; p < P; ++p) {
+        const RoundProb &rp = c->r_probs[(size_t)p];
+        IncProb &d = probs[(size_t)p];
+        d.col0 = rp.col0; d.rbits_off = rp.rbits_off; d.inf_off = rp.inf_off;
+        d.n = rp.n; d.n_seg = rp.n_seg; d.w = rp.w; d.cw = std::max((rp.n + 31) / 32, 1);
+        d.n_seeds = std::min(rp.n, (int)max_seeds); d.n_starts = d.n_seeds + 1;
+        d.conf_off = n_conf; d.pair0 = o.pair_off[p]; d.pair1 = o.pair_off[p + 1]; d.grp0 = o.grp_off[p];
+        d.slot0 = n_slots; d.mrow_off = n_mrow; d.max_lg = c->r_max_lg[(size_t)rp.tint];
+        if (o.refused[p] >= 0) continue;                     // no model: cost2 -1, skipped
+        if (d.n > kIncMaxCols) return fail(c, FCLU_ERR_UNSUPPORTED, "problem %d: %d columns, fclu_round_incumbents takes %d at the most", p, d.n, kIncMaxCols);
+        if (d.pair0 < 0 || d.pair1 < d.pair0 || d.pair1 > o.n_pairs || d.grp0 < 0 || d.grp0 > o.n_grp)
+            return fail(c, FCLU_ERR_HIP, "problem %d: the round's offsets are out of range", p);
+        n_conf += (i64)d.n * d.cw; n_slots += d.n_starts; n_mrow += (i64)d.n_starts * d.cw;
+        const size_t row_bytes = 2 * (size_t)d.n * (size_t)(d.w | 1) * 4;
+        const int path = !k.round_lds || row_bytes > (size_t)k.round_lds_bytes ? 2 : row_bytes <= (size_t)std::min<i64>(k.round_lds_bytes, kRoundTinyBytes) ? 0 : 1;
+        groups[path].push_back(p);
+        lds[path] = std::max(lds[path], inc_lds_bytes(d.n, d.w, d.cw, path < 2));
+        height[path] = std::max(height[path], d.n_starts);
+    }
+    const size_t need = D.conf.bytes((size_t)n_conf);
+    if (need > D.conf.cap) {                                 // sized from the sum of R^2: a batch's that does not fit is refused
+        HIP_TRY(c, D.conf.release());
+        size_t free_b = 0, total_b = 0;
+        HIP_TRY(c, hipMemGetInfo(&free_b, &total_b));
+        if (need + need / 4 + (64u << 20) > free_b)
+            return fail(c, FCLU_ERR_UNSUPPORTED, "the conflict matrices of this round (%lld bytes) do not fit the device's free memory (%lld bytes)", (i64)need, (i64)free_b);
+    }
+    std::vector<int> list;
+    for (const auto &g : groups) list.insert(list.end(), g.begin(), g.end());
+    const size_t nL = list.size(), nP = (size_t)P, nC = (size_t)C;
+    HIP_TRY(c, D.conf.grow((size_t)n_conf)); HIP_TRY(c, D.probs.grow(nP)); HIP_TRY(c, D.list.grow(nL)); HIP_TRY(c, D.g2.grow(nC));
+    HIP_TRY(c, D.start_cost2.grow((size_t)n_slots)); HIP_TRY(c, D.steps.grow(2 * (size_t)n_slots)); HIP_TRY(c, D.mrows.grow((size_t)n_mrow));
+    HIP_TRY(c, D.cost2.grow(nP)); HIP_TRY(c, D.start.grow(nP)); HIP_TRY(c, D.grow.grow(nP)); HIP_TRY(c, D.repair.grow(nP));
+    HIP_TRY(c, D.mem_cols.grow(nC)); HIP_TRY(c, D.mem_cnt.grow(nP));
+    HIP_TRY(c, H.cost2.grow(nP)); HIP_TRY(c, H.start.grow(nP)); HIP_TRY(c, H.grow.grow(nP)); HIP_TRY(c, H.repair.grow(nP));
+    HIP_TRY(c, H.mem_cols.grow(nC)); HIP_TRY(c, H.mem_cnt.grow(nP)); HIP_TRY(c, H.mem.grow(nC)); HIP_TRY(c, H.mem_off.grow(nP + 1));
+    HIP_TRY(c, hipMemcpyAsync(D.probs.p, probs.data(), D.probs.bytes(nP), hipMemcpyHostToDevice, s));
+    if (nL) HIP_TRY(c, hipMemcpyAsync(D.list.p, list.data(), D.list.bytes(nL), hipMemcpyHostToDevice, s));
+    if (C) HIP_TRY(c, hipMemcpyAsync(D.g2.p, g2, D.g2.bytes(nC), hipMemcpyHostToDevice, s));
+    if (n_conf) HIP_TRY(c, hipMemsetAsync(D.conf.p, 0, D.conf.bytes((size_t)n_conf), s));
+    HIP_TRY(c, hipMemsetAsync(D.cost2.p, 0xff, D.cost2.bytes(nP), s));          // -1: what a refused problem keeps
+    HIP_TRY(c, hipMemsetAsync(D.start.p, 0xff, D.start.bytes(nP), s));
+    HIP_TRY(c, hipMemsetAsync(D.grow.p, 0, D.grow.bytes(nP), s));
+    HIP_TRY(c, hipMemsetAsync(D.repair.p, 0, D.repair.bytes(nP), s));
+    HIP_TRY(c, hipMemsetAsync(D.mem_cnt.p, 0, D.mem_cnt.bytes(nP), s));
+    HIP_TRY(c, hipEventRecord(c->iev[0], s));
+    if (nL) hipLaunchKernelGGL(k_inc_conflict, dim3((unsigned)nL), dim3(256), 0, s, D.list.p, D.probs.p, RD.pairs.p, D.conf.p);
+    HIP_TRY(c, hipEventRecord(c->iev[1], s));
+    size_t first = 0;
+    for (int path = 0; path < 3; ++path) {
+        const size_t n = groups[path].size();
+        if (n) {
+            const auto kernel = path < 2 ? k_inc_start<true> : k_inc_start<false>;
+            hipLaunchKernelGGL(kernel, dim3((unsigned)n, (unsigned)height[path]), dim3(256), lds[path], s, D.list.p + first, D.probs.p, c->pd.ibits.p, c->pd.cbits.p,
+                               RD.rids.p, RD.inf_bits.p, D.conf.p, D.g2.p, RD.col_row_off.p, G, RD.rows.p, RD.grp_seg_off.p, RD.grp_seg.p, RD.grp_len.p, (i64)o.n_grp,
+                               (i64)o.n_grp_seg, lo_f, hi_f, (int)offset, D.start_cost2.p, D.steps.p, D.mrows.p);
+        }
+        first += n;
+    }
+    HIP_TRY(c, hipEventRecord(c->iev[2], s));
+    if (nL)
+        hipLaunchKernelGGL(k_inc_pick, dim3((unsigned)nL), dim3(256), 0, s, D.list.p, D.probs.p, D.start_cost2.p, D.steps.p, D.mrows.p, D.cost2.p, D.start.p, D.grow.p,
+                           D.repair.p, D.mem_cols.p, D.mem_cnt.p);
+    HIP_TRY(c, hipEventRecord(c->iev[3], s));
+    HIP_TRY(c, hipMemcpyAsync(H.cost2.p, D.cost2.p, D.cost2.bytes(nP), hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(H.start.p, D.start.p, D.start.bytes(nP), hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(H.grow.p, D.grow.p, D.grow.bytes(nP), hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(H.repair.p, D.repair.p, D.repair.bytes(nP), hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(H.mem_cnt.p, D.mem_cnt.p, D.mem_cnt.bytes(nP), hipMemcpyDeviceToHost, s));
+    if (C) HIP_TRY(c, hipMemcpyAsync(H.mem_cols.p, D.mem_cols.p, D.mem_cols.bytes(nC), hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    HIP_TRY(c, hipGetLastError());
+    i64 n_mem = 0;
+    for (int p = 0; p < P; ++p) {                            // the members end to end
+        const IncProb &d = probs[(size_t)p];
+        const int cnt = H.mem_cnt.p[p];
+        if (cnt < 0 || cnt > d.n) return fail(c, FCLU_ERR_HIP, "problem %d: %d members for %d columns", p, cnt, d.n);
+        H.mem_off.p[p] = n_mem;
+        for (int x = 0; x < cnt; ++x) H.mem.p[n_mem + x] = H.mem_cols.p[d.col0 + x];
+        n_mem += cnt;
+    }
+    H.mem_off.p[P] = n_mem;
+    fclu_incumbents &r = c->incs;
+    r.n_prob = P; r.n_mem = n_mem; r.cost2 = H.cost2.p; r.start = H.start.p; r.grow_steps = H.grow.p; r.repair_steps = H.repair.p;
+    r.mem_off = H.mem_off.p; r.mem = H.mem.p;
+    (void)hipEventElapsedTime(&c->iconf_ms, c->iev[0], c->iev[1]);
+    (void)hipEventElapsedTime(&c->istart_ms, c->iev[1], c->iev[2]);
+    (void)hipEventElapsedTime(&c->ipick_ms, c->iev[2], c->iev[3]);
+    c->have_incs = true;
     return FCLU_OK;
 }
 
@@ -2442,7 +2773,9 @@ int fclu_create(int device, fclu_ctx **out) {
         {reinterpret_cast<const void *>(k_compat<true>), 2 * kTile * (kRankWords | 1) * 6},
         {reinterpret_cast<const void *>(k_prune_lds), 150 * 1024},
         {reinterpret_cast<const void *>(k_round<true, false>), kRoundLdsBytes},
-        {reinterpret_cast<const void *>(k_round<true, true>), kRoundLdsBytes}};
+        {reinterpret_cast<const void *>(k_round<true, true>), kRoundLdsBytes},
+        {reinterpret_cast<const void *>(k_inc_start<true>), (int)inc_lds_bytes(0, kMaxWords, (kIncMaxCols + 31) / 32, false) + kRoundLdsBytes},
+        {reinterpret_cast<const void *>(k_inc_start<false>), (int)inc_lds_bytes(0, kMaxWords, (kIncMaxCols + 31) / 32, false)}};
     for (const auto &d : dyn) if (e == hipSuccess) e = hipFuncSetAttribute(d.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, d.lds);
     if (e != hipSuccess) {
         fail(nullptr, FCLU_ERR_HIP, "context creation failed: %s", hipGetErrorString(e));
@@ -2619,6 +2952,24 @@ int fclu_round_timing(fclu_ctx *c, float *count_ms, float *gaps_ms, float *fill_
     if (!c) return FCLU_ERR_ARG;
     if (fill_ms) *fill_ms = c->rfill_ms;
     return two_times(count_ms, c->rcount_ms, gaps_ms, c->rgaps_ms);
+}
+
+int fclu_round_incumbents(fclu_ctx *c, const int32_t *g2, double lo_f, double hi_f, int32_t offset, int32_t max_seeds) {
+    return c ? incumbents_device(c, read_knobs(), g2, lo_f, hi_f, offset, max_seeds) : FCLU_ERR_ARG;
+}
+
+int fclu_round_incumbent_results(fclu_ctx *c, fclu_incumbents *out) {
+    if (!c || !out) return FCLU_ERR_ARG;
+    if (!c->have_incs || !c->have_rounds)
+        return fail(c, FCLU_ERR_ARG, "fclu_round_incumbent_results: no result (the last fclu_round_incumbents call failed, none was made, or a later call ended it)");
+    *out = c->incs;
+    return FCLU_OK;
+}
+
+int fclu_round_incumbent_timing(fclu_ctx *c, float *conflict_ms, float *starts_ms, float *pick_ms) {
+    if (!c) return FCLU_ERR_ARG;
+    if (pick_ms) *pick_ms = c->ipick_ms;
+    return two_times(conflict_ms, c->iconf_ms, starts_ms, c->istart_ms);
 }
 
 }  // extern "C"

@@ -260,6 +260,42 @@ int fclu_round_results(fclu_ctx *c, fclu_rounds *out);
  * gap groups (keys, sort, groups); the fills. */
 int fclu_round_timing(fclu_ctx *c, float *count_ms, float *gaps_ms, float *fill_ms);
 
+/* ---- greedy incumbents of a round's problems: a feasible column set per problem, as cutoff and fallback of the solve ----
+ * With K = 2 a round's model is a function of the chosen column set S alone: e = the OR of the members' I rows on the informative
+ * segments, cost = sum over S of popcount(C_c & e) + the others' garbage costs, no incompatible pair inside S, every gap row of a member
+ * holding.  Per problem, min(R, max_seeds) seeded starts (start k = {floor(k R / n)}) and the empty start are grown greedily (the column
+ * with the smallest delta2, then the smallest column, while delta2 < 0), repaired (while a member has a violated gap row, the member with
+ * the most, then the smallest column, leaves) and scored; the smallest cost2, then the earliest start, is the incumbent.  A start that
+ * leaves a gap row of a column OUTSIDE the set violated (the model gives such a row MAX_ISOFORM_LG -- the tint's summed segment lengths,
+ * from fclu_round_setup's seg_len -- of slack and no more: the same test with offset + MAX_ISOFORM_LG for offset) is not feasible and is
+ * left out; a problem without a feasible start has no incumbent.  The definition, every tie included, is freddie_amd/cluster_solve.py
+ * greedy_incumbent(), which the device reproduces exactly.
+ * The batch is that of the context's last successful fclu_round_models(), whose device arrays are the input; g2[n_cols] = twice each
+ * column's garbage cost (>= 0); a member's row (g, l) is violated when lo_f * G_g - offset > l or hi_f * G_g + offset < l in doubles (one
+ * rounded multiply, one rounded add, no fused multiply-add), lo_f = 1 - epsilon and hi_f = 1 + epsilon being the host's; max_seeds >= 1.
+ * FCLU_ERR_ARG: no such fclu_round_models() behind the call, the rounds' source ended by a later call (see above), a bad argument.
+ * FCLU_ERR_UNSUPPORTED: a problem of more than 32768 columns; conflict matrices (the sum of R^2 bits) beyond the device's free memory
+ * (fclu_last_error names the total).  The context stays usable.  FCLU_ROUND_LDS / FCLU_ROUND_LDS_BYTES split the problems as they do
+ * for fclu_round_models(). */
+int fclu_round_incumbents(fclu_ctx *c, const int32_t *g2, double lo_f, double hi_f, int32_t offset, int32_t max_seeds);
+
+typedef struct fclu_incumbents {
+    int32_t n_prob;
+    int64_t n_mem;
+    const int64_t *cost2;          /* n_prob: twice the incumbent's cost; -1 for a refused problem (no model: skipped) and for one without a feasible start */
+    const int32_t *start;          /* n_prob: the chosen start (min(R, max_seeds) = the empty one); -1 where cost2 is */
+    const int32_t *grow_steps, *repair_steps;   /* n_prob: columns the chosen start added / members it lost */
+    const int64_t *mem_off;        /* n_prob + 1 */
+    const int32_t *mem;            /* n_mem: the members (columns), ascending */
+} fclu_incumbents;
+
+/* Result of the last successful fclu_round_incumbents(): pointers into pinned host buffers the context owns, valid until the context's
+ * next call.  The round results stay valid behind it. */
+int fclu_round_incumbent_results(fclu_ctx *c, fclu_incumbents *out);
+
+/* Kernel time of the last fclu_round_incumbents() from HIP events (ms): the conflict matrices; the starts (grow, repair, score); the choice. */
+int fclu_round_incumbent_timing(fclu_ctx *c, float *conflict_ms, float *starts_ms, float *pick_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,6 +12,7 @@ synthetic preprocessed tints through include/freddie_cluster.h.
     python tools/cluster_bench.py --files [--workload many|big] [--steps K] [--baseline-steps K] [--threads N]
                        (segment_*.tsv files in: the native reader, the rep grouping and the whole cluster_files_batch, against
                         read_segment + pack_labels + Context.partition_labels on the same files)
+    python tools/cluster_bench.py --incumbents [--workload many|big] [--steps K] [--host-sample N] [--solve-budget S] [--max-seeds N] [--out FILE]
     python tools/cluster_bench.py --rounds [--workload many|big] [--steps K] [--host-sample N] [--solve-budget S] [--out FILE]
                        (the first round of every partition: Context.round_models against the plain-Python build of the same arrays as
                         the reference does it, the kernels' event times, and -- apart -- what HiGHS takes on the same round; the
@@ -414,6 +415,91 @@ def run_rounds(workload="many", steps=5, host_sample=4, solve_budget=120.0, maxi
     }
 
 
+def run_incumbents(workload="many", steps=5, host_sample=2, solve_budget=300.0, maximum_ilp_size=1000, threads=16, max_seeds=64):
+    """The workload staged as run_rounds() stages it, then the FIRST round, every partition active:
+      device   Context.round_models then Context.round_incumbents on all problems (medians over `steps` after a warm-up; the kernel
+               splits of fclu_round_timing and fclu_round_incumbent_timing side by side), and the share of problems with a model whose
+               incumbent is not empty;
+      solve    on the solvable problems of the first `host_sample` tints (run_rounds()' sample), smallest first, until `solve_budget`
+               seconds are spent: HiGHS without and with the incumbent as a cutoff, and incumbent cost / HiGHS optimum.
+    What was not taken is None."""
+    import tempfile
+    from freddie_amd import cluster, cluster_solve
+    with tempfile.TemporaryDirectory() as d:
+        paths, n_reads = write_segment_files(workload, d)
+        ctx = cluster_prep.Context(0)
+        settings = cluster.ilp_settings(max_ilp=maximum_ilp_size)
+        tints, part0, _ = cluster.stage_files(paths, settings, ctx, threads)
+    costs = [cluster.garbage_costs(t, "constant") for t in tints]
+    problems = [(t, q, list(rids)) for t, tint in enumerate(tints) for q, (rids, _) in enumerate(tint["partitions"])]
+    sample = [p for p in problems if p[0] < host_sample]
+
+    def call(ps):
+        t0 = time.perf_counter()
+        arr = ctx.round_models([part0[t] + q for t, q, _ in ps], [rem for _, _, rem in ps])
+        t1 = time.perf_counter()
+        inc = ctx.round_incumbents([costs[t][i] for t, _, rem in ps for i in rem], settings["epsilon"], settings["offset"], max_seeds)
+        return arr, inc, t1 - t0, time.perf_counter() - t1
+
+    call(problems)                                                                # warm-up
+    models_s, inc_s, kern_models, kern_inc = [], [], [], []
+    for _ in range(steps):
+        arr, inc, a, b = call(problems)
+        models_s.append(a); inc_s.append(b)
+        kern_models.append(ctx.round_timing()); kern_inc.append(ctx.round_incumbent_timing())
+    with_model = int((arr["refused"] < 0).sum())
+    no_start = int(((inc["cost2"] < 0) & (arr["refused"] < 0)).sum())
+    sizes = np.diff(inc["mem_off"])
+    nonempty = int((sizes > 0).sum())
+    sarr, sinc, _, _ = call(sample)
+    rows, spent = [], 0.0
+    for p in sorted(range(len(sample)), key=lambda p: len(sample[p][2])):
+        t, q, rem = sample[p]
+        model = cluster_prep.round_model(sarr, p)
+        if model is None or spent >= solve_budget:
+            continue
+        model["garbage"] = [costs[t][i] for i in rem]; model["max_lg"] = sum(s[2] for s in tints[t]["segs"])
+        incumbent = cluster_prep.round_incumbent(sinc, p)
+        row = {"reps": len(rem), "incumbent_cost": incumbent[0] if incumbent else None, "incumbent_members": int(sum(incumbent[1])) if incumbent else None}
+        for name, with_cutoff in (("plain", False), ("cutoff", True)):
+            m = dict(model)
+            if with_cutoff and incumbent is not None:
+                m["incumbent"] = incumbent
+            t0 = time.perf_counter()
+            status, x, e = cluster_solve.solve_round(m, settings)
+            dt = time.perf_counter() - t0
+            spent += dt
+            row[name + "_s"], row[name + "_status"] = dt, status
+            row[name + "_cost"] = cluster_solve.round_cost(model, x, e) if status == cluster_solve.OPTIMAL else None
+            print("%s: %d reps in %.2f s: %s" % (name, len(rem), dt, status), file=sys.stderr, flush=True)
+        row["incumbent_over_optimum"] = incumbent[0] / row["plain_cost"] if incumbent and row["plain_cost"] else None
+        rows.append(row)
+    ctx.close()
+    med = lambda xs: float(np.median(xs)) * 1e3
+    kmed = lambda ks: {k: float(np.median([x[k] for x in ks])) for k in ks[0]}
+    return {
+        "metric": "first round of every partition: Context.round_incumbents behind Context.round_models; HiGHS with and without the cutoff on the sample",
+        "unit": "ms", "data": "synthetic", "source_hash": _build_hash(),
+        "config": {"workload": "cluster-" + workload, **WORKLOADS[workload], "reads": n_reads, "problems": len(problems), "columns": int(arr["n_cols"]),
+                   "pairs_kept": int(arr["n_pairs"]), "gap_rows": int(arr["n_gap_rows"]), "refused_problems": len(problems) - with_model,
+                   "max_seeds": max_seeds, "steps": steps, "host_sample_tints": host_sample, "sample_problems": len(sample), "solve_budget_s": solve_budget},
+        "round_models_call_ms": med(models_s), "round_models_kernel_ms": kmed(kern_models),
+        "round_incumbents_call_ms": med(inc_s), "round_incumbents_kernel_ms": kmed(kern_inc),
+        "round_incumbents_kernel_ms_total": float(np.median([sum(k.values()) for k in kern_inc])),
+        "round_models_kernel_ms_total": float(np.median([sum(k.values()) for k in kern_models])),
+        "problems_with_a_model": with_model, "without_a_feasible_start": no_start, "incumbent_not_empty": nonempty,
+        "share_not_empty": nonempty / with_model if with_model else None,
+        "mean_members_over_columns": float(sizes.sum()) / max(int(np.diff(arr["col_off"])[arr["refused"] < 0].sum()), 1),
+        "sample": rows or None, "sample_solve_seconds": spent,
+        "spread_ms": {"round_incumbents_call": [min(inc_s) * 1e3, max(inc_s) * 1e3]},
+    }
+
+
+def _build_hash():
+    from freddie_amd import build as _b
+    return _b.embedded_hash(cluster_prep.CLUSTER_SO)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workload", default="many", choices=sorted(WORKLOADS))
@@ -426,12 +512,21 @@ def main():
     ap.add_argument("--threads", type=int, default=16, help="--files: threads of the native reader")
     ap.add_argument("--rounds", action="store_true", help="measure Context.round_models on the first round against the plain-Python build; HiGHS apart")
     ap.add_argument("--solve-budget", type=float, default=120.0, help="--rounds: seconds of HiGHS solves on the sample's problems")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "cluster_rounds.txt"), help="--rounds: where the result is written too")
+    ap.add_argument("--incumbents", action="store_true", help="measure Context.round_incumbents on the first round; HiGHS with and without the cutoff on the --rounds sample")
+    ap.add_argument("--max-seeds", type=int, default=64, help="--incumbents: seeded starts a problem")
+    ap.add_argument("--out", default=None, help="--rounds / --incumbents: where the result is written too (profiles/cluster_rounds.txt, profiles/cluster_incumbents.txt)")
     args = ap.parse_args()
-    if args.rounds:
+    if args.incumbents:
+        res = run_incumbents(args.workload, args.steps, host_sample=2 if args.host_sample == 20 else args.host_sample,
+                             solve_budget=args.solve_budget if args.solve_budget != 120.0 else 300.0, threads=args.threads, max_seeds=args.max_seeds)
+        with open(args.out or os.path.join(ROOT, "profiles", "cluster_incumbents.txt"), "w") as f:
+            f.write("tools/cluster_bench.py --incumbents --workload %s --steps %d  (libfreddie_cluster.so source hash %s)\n" % (args.workload, args.steps, res["source_hash"]))
+            f.write(json.dumps(res, indent=1) + "\n")
+        print(json.dumps(res))
+    elif args.rounds:
         res = run_rounds(args.workload, args.steps, host_sample=min(args.host_sample, 4) if args.host_sample == 20 else args.host_sample,
                          solve_budget=args.solve_budget, threads=args.threads)
-        with open(args.out, "w") as f:
+        with open(args.out or os.path.join(ROOT, "profiles", "cluster_rounds.txt"), "w") as f:
             f.write("tools/cluster_bench.py --rounds --workload %s --steps %d\n" % (args.workload, args.steps))
             f.write(json.dumps(res, indent=1) + "\n")
         print(json.dumps(res))
