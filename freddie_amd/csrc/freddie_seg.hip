@@ -100,6 +100,8 @@ struct fseg_ctx {
     int thr_part = -1;         // FSEG_THR_PART=0 / 1: the threshold per partition by one workgroup (k_thr_part) never / whenever possible; -1: batches of many partitions
     int hist16 = -1;           // FSEG_HIST16=0 / 1: S1 with 32-bit LDS counters always / with packed 16-bit ones wherever no count can overflow; -1: the same as 1
     bool hist_packed = false;  // the resident batch's chunks were planned for k_hist<16> (kHistChunk16 positions, every count <= 65 535)
+    int yraw16 = -1;           // FSEG_YRAW16=0 / 1: the histogram in device memory int32 always / uint16 wherever S1 runs packed; -1: the same as 1
+    bool yraw_narrow = false;  // the resident batch's d_y_raw holds uint16 (hist_packed and the switch): S1's output, S2's and S6's input
     i64 max_part_lanes = 0;    // reads of the batch's largest partition (what bounds a DP sum: 32-bit keys below 2^18)
     int n_tiles = 0;
     bool expanded = false;
@@ -266,7 +268,7 @@ struct fseg_ctx {
     enum { PATH_SMALL_BATCH, PATH_TINY_ON, PATH_WAVE_ON, PATH_FUSE_ON, PATH_KEY32, PATH_THR_PART, PATH_LABEL_PACKED, PATH_N_SOLVE,
            PATH_N_WIDE = PATH_N_SOLVE + 3, PATH_N_TINY = PATH_N_WIDE + 3, PATH_N_WORK, PATH_DPW, PATH_WIDE16, PATH_KNOWN, PATH_SOLVE8,
            PATH_TINY_KERNEL, PATH_SCORE, PATH_ARENA_DP, PATH_PLAN, PATH_N_ARENA_PROB, PATH_N_SCORE, PATH_HIST16 = PATH_N_SCORE + 3, PATH_IV_THREADS,
-           PATH_SMOOTH_R, PATH_WORDS };
+           PATH_SMOOTH_R, PATH_YRAW16, PATH_WORDS };
     int paths[PATH_WORDS] = {};
     // fseg_annotate: the uploaded reads (one allocation, mirrored by a pinned image), per-read work arrays, the emitted lists, and
     // the pinned buffers fseg_annotation() points into (own allocations: nothing of a run or of fseg_results* touches them)
@@ -599,30 +601,34 @@ int enqueue_run(fseg_ctx *c, unsigned segs, bool sized = false, i64 label_fill_b
     begin(ST_HIST);
     // S1
     // (the chunks were laid out on upload for one counter width: one instance per launch)
-#define FSEG_LAUNCH_HIST(BITS)                                                                                         \
-    hipLaunchKernelGGL(k_hist<BITS>, dim3(grid_for(c->n_hist_chunks, 1, 16384)), dim3(512), 0, s, c->n_hist_chunks,   \
+#define FSEG_LAUNCH_HIST(BITS, OUT)                                                                                    \
+    hipLaunchKernelGGL((k_hist<BITS, OUT>), dim3(grid_for(c->n_hist_chunks, 1, 16384)), dim3(512), 0, s, c->n_hist_chunks,   \
                        c->d_hc_part.as<int>(), c->d_hc_p0.as<i64>(), c->d_hc_n.as<int>(), c->d_hc_glo.as<int>(),       \
                        c->d_hc_ghi.as<int>(), c->d_hc_llo.as<i64>(), c->d_hc_lhi.as<i64>(), c->d_part_iv_off.as<i64>(), c->d_iv_start.as<int>(), c->d_iv_end.as<int>(), \
                        c->d_pos_off.as<i64>(), c->d_part_lane_off.as<i64>(), c->d_lane_lx.as<int2>(),                  \
                        c->d_lane_start.as<int>(), c->d_lane_pmax.as<int>(),                                            \
-                       c->d_lex.as<int2>(), c->P.ignore_ends, c->d_y_raw.as<int>(), st,                                \
+                       c->d_lex.as<int2>(), c->P.ignore_ends, c->d_y_raw.as<OUT>(), st,                                \
                        scan_state, scan_single ? scan_nb * 3 : 0)
     c->paths[fseg_ctx::PATH_HIST16] = c->hist_packed;
-    if (c->hist_packed) { FSEG_LAUNCH_HIST(16); }
-    else { FSEG_LAUNCH_HIST(32); }
+    c->paths[fseg_ctx::PATH_YRAW16] = c->yraw_narrow;
+    if (c->yraw_narrow) { FSEG_LAUNCH_HIST(16, uint16_t); }
+    else if (c->hist_packed) { FSEG_LAUNCH_HIST(16, int); }
+    else { FSEG_LAUNCH_HIST(32, int); }
 #undef FSEG_LAUNCH_HIST
     end(ST_HIST); begin(ST_SMOOTH);
     // S2
-#define FSEG_LAUNCH_SMOOTH(RV)                                                                                         \
-    hipLaunchKernelGGL(k_smooth<RV>, dim3(tile_grid), dim3(kSmoothThreads), 0, s, c->n_tiles, c->d_tile_desc.as<TileDesc>(),      \
-                       c->d_y_raw.as<int>(), c->d_w_main.as<double>(),                                                 \
+#define FSEG_LAUNCH_SMOOTH_AS(RV, COUNT)                                                                               \
+    hipLaunchKernelGGL((k_smooth<RV, COUNT>), dim3(tile_grid), dim3(kSmoothThreads), 0, s, c->n_tiles, c->d_tile_desc.as<TileDesc>(),      \
+                       c->d_y_raw.as<COUNT>(), c->d_w_main.as<double>(),                                               \
                        c->P.radius_main, c->d_y.as<double>(), flag_pos_bits,                           \
                        flag_cand_bits, c->d_blk_pre.as<int>(), c->d_tile_tot.as<int>(), c->d_tile_defer.as<int>())
+#define FSEG_LAUNCH_SMOOTH(RV) do { if (c->yraw_narrow) { FSEG_LAUNCH_SMOOTH_AS(RV, uint16_t); } else { FSEG_LAUNCH_SMOOTH_AS(RV, int); } } while (0)
     // sigma = 5 (default) and sigma = 3 (config 5) have their own unrolled instances; any other radius runs the loop
     if (c->P.radius_main == 20) { c->paths[fseg_ctx::PATH_SMOOTH_R] = 20; FSEG_LAUNCH_SMOOTH(20); }
     else if (c->P.radius_main == 12) { c->paths[fseg_ctx::PATH_SMOOTH_R] = 12; FSEG_LAUNCH_SMOOTH(12); }
     else { c->paths[fseg_ctx::PATH_SMOOTH_R] = 0; FSEG_LAUNCH_SMOOTH(0); }
 #undef FSEG_LAUNCH_SMOOTH
+#undef FSEG_LAUNCH_SMOOTH_AS
     end(ST_SMOOTH);
     // S3a threshold: needs only the smoothed signal, like the candidates (S3b) -- the two chains run side by side
     {
@@ -737,7 +743,7 @@ int enqueue_run(fseg_ctx *c, unsigned segs, bool sized = false, i64 label_fill_b
     if (do_score) {
         for (int w = 0; w < fseg_ctx::PATH_WORDS; ++w)
             if (w != fseg_ctx::PATH_THR_PART && w != fseg_ctx::PATH_LABEL_PACKED && w != fseg_ctx::PATH_ARENA_DP && w != fseg_ctx::PATH_HIST16 &&
-                w != fseg_ctx::PATH_IV_THREADS && w != fseg_ctx::PATH_SMOOTH_R) census[w] = 0;
+                w != fseg_ctx::PATH_IV_THREADS && w != fseg_ctx::PATH_SMOOTH_R && w != fseg_ctx::PATH_YRAW16) census[w] = 0;
         census[fseg_ctx::PATH_SMALL_BATCH] = c->small_batch; census[fseg_ctx::PATH_TINY_ON] = c->tiny_on; census[fseg_ctx::PATH_WAVE_ON] = wave;
         census[fseg_ctx::PATH_FUSE_ON] = c->use_fuse && c->fuse_on; census[fseg_ctx::PATH_KNOWN] = known; census[fseg_ctx::PATH_PLAN] = plan != nullptr;
     }
@@ -1087,15 +1093,19 @@ int enqueue_run(fseg_ctx *c, unsigned segs, bool sized = false, i64 label_fill_b
                                c->d_giant.as<unsigned char>(), (i64)giant_scratch_bytes(c->nm_giant));
     }
     end(ST_DP); begin(ST_REFINE);
-    // S6
-    hipLaunchKernelGGL(k_segments, dim3(grid_for(K, 1, 8192)), dim3(iv_threads), 0, s, K, c->d_pos_off.as<i64>(),
-                       c->d_cand_off.as<i64>(), c->d_cand_y.as<int>(), c->d_y_raw.as<int>(), c->d_blk_pre.as<int>(), c->d_tile_tot.as<int>(), c->d_iv_tile0.as<int>(),
-                       c->d_chosen.as<unsigned char>(), flag_final_bits, c->d_rseg_c.as<int>(),
-                       c->d_seg_prev.as<int>(), st);
-    hipLaunchKernelGGL(k_refine, dim3(2048), dim3(64), 0, s, st, c->d_seg_iv.as<int>(), c->d_rseg_c.as<int>(),
-                       c->d_seg_prev.as<int>(), c->d_cand_y.as<int>(), c->d_pos_off.as<i64>(), c->d_y_raw.as<int>(),
-                       c->d_w_refine.as<double>(), c->P.radius_refine, c->P.sigma, c->d_g.as<double>(), c->d_pk.as<int>(),
-                       c->d_pf.as<unsigned char>(), c->d_kp.as<unsigned char>(), flag_final_bits);
+    // S6 (the histogram as S1 left it: uint16 where it ran packed)
+#define FSEG_LAUNCH_REFINE(COUNT)                                                                                      \
+    hipLaunchKernelGGL(k_segments<COUNT>, dim3(grid_for(K, 1, 8192)), dim3(iv_threads), 0, s, K, c->d_pos_off.as<i64>(),                       \
+                       c->d_cand_off.as<i64>(), c->d_cand_y.as<int>(), c->d_y_raw.as<COUNT>(), c->d_blk_pre.as<int>(), c->d_tile_tot.as<int>(), c->d_iv_tile0.as<int>(), \
+                       c->d_chosen.as<unsigned char>(), flag_final_bits, c->d_rseg_c.as<int>(),                        \
+                       c->d_seg_prev.as<int>(), st);                                                                   \
+    hipLaunchKernelGGL(k_refine<COUNT>, dim3(2048), dim3(64), 0, s, st, c->d_seg_iv.as<int>(), c->d_rseg_c.as<int>(), \
+                       c->d_seg_prev.as<int>(), c->d_cand_y.as<int>(), c->d_pos_off.as<i64>(), c->d_y_raw.as<COUNT>(), \
+                       c->d_w_refine.as<double>(), c->P.radius_refine, c->P.sigma, c->d_g.as<double>(), c->d_pk.as<int>(), \
+                       c->d_pf.as<unsigned char>(), c->d_kp.as<unsigned char>(), flag_final_bits)
+    if (c->yraw_narrow) { FSEG_LAUNCH_REFINE(uint16_t); }
+    else { FSEG_LAUNCH_REFINE(int); }
+#undef FSEG_LAUNCH_REFINE
     end(ST_REFINE); begin(ST_FINAL);
     pos_counts(s, flag_final_bits);
     hipLaunchKernelGGL(k_scan_emit<kEmitPositions>, dim3(pos_grid), dim3(256), 0, s, flag_final_bits,
@@ -1550,6 +1560,7 @@ int fseg_create(int device, fseg_ctx **out) {
     if (flag("FSEG_LABEL_BYTES")) c->label_packed_ok = false;
     { const char *v = getenv("FSEG_THR_PART"); if (v && (v[0] == '0' || v[0] == '1')) c->thr_part = v[0] - '0'; }
     { const char *v = getenv("FSEG_HIST16"); if (v && (v[0] == '0' || v[0] == '1')) c->hist16 = v[0] - '0'; }
+    { const char *v = getenv("FSEG_YRAW16"); if (v && (v[0] == '0' || v[0] == '1')) c->yraw16 = v[0] - '0'; }
     { const char *v = getenv("FSEG_SYNC_TICKS"); if (v && v[0] && atoll(v) > 0) c->sync_ticks = (unsigned)atoll(v); }
     if (flag("FSEG_NO_GRAPH")) c->use_graph = false;
     if (flag("FSEG_NO_FORK")) c->use_fork = false;
@@ -1721,6 +1732,9 @@ static int upload_impl(fseg_ctx *c, const fseg_batch *b) {
             if (count > kHistCountMax16) hist_packed = false;
         }
     }
+    // The histogram's element in device memory follows: uint16 where the counters are (one width per batch, decided before the
+    // position slab is carved below), unless FSEG_YRAW16=0 keeps it int32.
+    const bool yraw_narrow = hist_packed && c->yraw16 != 0;
     // histogram chunks: consecutive positions of one partition; as large as possible (fewer reads are visited twice)
     // while still giving >= 512 workgroups
     int hist_chunk = hist_packed ? kHistChunk16 : kHistChunk;
@@ -1844,7 +1858,7 @@ static int upload_impl(fseg_ctx *c, const fseg_batch *b) {
     const double t_copy = tk.ms();
     c->n_part = np; c->K = K; c->R = R; c->I = I; c->NPOS = NPOS; c->LANES = lanes; c->expanded = expanded;
     if (c->max_part_lanes > lanes) c->max_part_lanes = lanes;
-    c->n_tiles = (int)n_tiles; c->n_hist_chunks = (int)n_chunks; c->hist_packed = hist_packed; c->n_rep_blocks = (int)n_rep_blocks; c->max_rep_exons = max_rep_exons;
+    c->n_tiles = (int)n_tiles; c->n_hist_chunks = (int)n_chunks; c->hist_packed = hist_packed; c->yraw_narrow = yraw_narrow; c->n_rep_blocks = (int)n_rep_blocks; c->max_rep_exons = max_rep_exons;
     c->part_iv_off.assign(b->part_iv_off, b->part_iv_off + np + 1);
     c->part_rep_off.assign(b->part_rep_off, b->part_rep_off + np + 1);
     hipStream_t s = c->stream;
@@ -1908,7 +1922,8 @@ static int upload_impl(fseg_ctx *c, const fseg_batch *b) {
         auto atleast = [](i64 &cap, i64 v) { if (cap < v) cap = v; };
         atleast(c->chunk_cap, NPOS / 8192 + np + 8);              // an upper bound, not a guess
         Carve cv;
-        cv.add(c->d_y_raw, np8 * 4); cv.add(c->d_y, np8 * 8); cv.add(c->d_bits, 3 * flag_words(np8) * 4);
+        cv.add(c->d_y_raw, np8 * (yraw_narrow ? 2 : 4)); cv.add(c->d_y, np8 * 8);      // (an array starts on a multiple of 256 bytes whatever the one before it holds)
+        cv.add(c->d_bits, 3 * flag_words(np8) * 4);
         cv.add(c->d_v, np8 * 8);
         cv.add(c->d_scan_state, ((size_t)nb * 3 + 1) * 8);
         cv.add(c->d_bsum, ((size_t)nbp + 2) * 4);
@@ -2422,7 +2437,18 @@ int fseg_tap(fseg_ctx *c, int what, void *dst, int64_t cap_bytes, int64_t *n_byt
     std::vector<int> packed;
     switch (what) {
         case FSEG_TAP_POS_OFF: src = c->d_pos_off.p; bytes = (c->K + 1) * 8; break;
-        case FSEG_TAP_Y_RAW: src = c->d_y_raw.p; bytes = c->NPOS * 4; break;
+        case FSEG_TAP_Y_RAW: {                                             // int32 whatever the device holds: uint16 is widened here
+            bytes = c->NPOS * 4;
+            if (!c->yraw_narrow) { src = c->d_y_raw.p; break; }
+            *n_bytes = bytes;
+            if (dst && cap_bytes > 0 && bytes > 0) {
+                std::vector<uint16_t> narrow((size_t)c->NPOS);
+                HIP_TRY(c, copy_sync(c, narrow.data(), c->d_y_raw.p, narrow.size() * 2, hipMemcpyDeviceToHost));
+                const i64 n = (bytes < cap_bytes ? bytes : cap_bytes) / 4;
+                for (i64 i = 0; i < n; ++i) static_cast<int32_t *>(dst)[i] = (int32_t)narrow[(size_t)i];
+            }
+            return FSEG_OK;
+        }
         case FSEG_TAP_Y: src = c->d_y.p; bytes = c->NPOS * 8; break;
         case FSEG_TAP_THRESHOLD: src = c->d_thr.p; bytes = (i64)c->n_part * 8; break;
         case FSEG_TAP_CAND_OFF: src = c->d_cand_off.p; bytes = (c->K + 1) * 8; break;

@@ -256,6 +256,10 @@ constexpr int kHistChunk = 8192;
 // the positions: half the chunks, so half the visits of a read that spans its partition, half the table stagings and barriers.
 // A low half never carries into its neighbour because the host takes this instance only for batches in which no position's
 // count can exceed 65 535 (upload_impl: hist_packed).
+// Such a batch's histogram is uint16 in device memory as well (FSEG_YRAW16, default on): the write-out is then a copy of the LDS
+// words.  For that the chunk's counters start at half-word p0 & 7 of the LDS array (p0: the chunk's first position in the batch), so
+// 16-byte group j of the array is 16-byte group (p0 >> 3) + j of the histogram -- aligned on both sides -- and the array is one group
+// longer.  Only a chunk's first and last group can hold a neighbouring chunk's positions: those leave as 2-byte stores.
 #ifndef FSEG_HIST_CHUNK16
 #define FSEG_HIST_CHUNK16 16384
 #endif
@@ -322,6 +326,11 @@ constexpr int kSmoothStage = (kSmoothTile + 2 * kMaxRadius + kSmoothThreads - 1)
 
 
 typedef int int4u __attribute__((ext_vector_type(4), aligned(4)));      // (16 bytes from a dword-aligned address)
+
+// 16 bytes from an address aligned to a uint16 count.  This counts on unaligned access to global memory, which gfx950 under HSA has and
+// the compiler knows of: the load is ONE global_load_dwordx4.  A toolchain that split it into 2-byte loads would still be right, and
+// k_segments would quietly lose what it gained (profiles/yraw16.txt; `hipcc -S` of seg_tail.hip shows which).
+typedef unsigned uint4u __attribute__((ext_vector_type(4), aligned(2)));
 
 
 // ---------------------------------------------------------------------------------------------

@@ -17,17 +17,21 @@ __global__ void __launch_bounds__(256) k_thr_table(const double *h_table, int h_
 
 // BITS: the width of a counter in LDS.  32: kHistChunk positions, a word each.  16: kHistChunk16 positions, two to a word (a batch
 // in which no count can exceed 65 535; the host decides, one instance per launch).  The walk is the same.
-template <int BITS>
+// Out: the histogram's element in device memory.  int: a position per 32-bit element.  uint16_t (BITS == 16 only): the LDS words
+// leave as they lie (seg_common.h, above kHistChunk16).
+template <int BITS, typename Out>
 __global__ void __launch_bounds__(512) k_hist(int n_chunks, const int *chunk_part, const i64 *chunk_p0, const int *chunk_n,
                                               const int *chunk_glo, const int *chunk_ghi, const i64 *chunk_lane_lo,
                                               const i64 *chunk_lane_hi, const i64 *part_iv_off,
                                               const int *iv_start, const int *iv_end, const i64 *pos_off,
                                               const i64 *part_lane_off, const int2 *__restrict__ lane_lx, const int *lane_start,
                                               const int *lane_pmax, const int2 *__restrict__ lex,
-                                              int ignore_ends, int *y_raw, Status *st, u64 *zero_ptr, i64 zero_n) {
+                                              int ignore_ends, Out *y_raw, Status *st, u64 *zero_ptr, i64 zero_n) {
     static_assert(BITS == 32 || BITS == 16, "a counter is a word or half a word");
+    constexpr bool kNarrow = std::is_same<Out, uint16_t>::value;
+    static_assert(kNarrow ? BITS == 16 : std::is_same<Out, int>::value, "uint16 counts in memory are the packed counters' words");
     using Word = std::conditional_t<BITS == 16, unsigned, int>;
-    constexpr int kWords = BITS == 16 ? kHistChunk16 / 2 : kHistChunk;
+    constexpr int kWords = BITS == 16 ? kHistChunk16 / 2 + (kNarrow ? 4 : 0) : kHistChunk;
     __shared__ __attribute__((aligned(16))) Word hist[kWords];
     __shared__ int ivs_s[kHistIv], ive_s[kHistIv], base_s[kHistIv];
     // first kernel of the run: also clears the look-back words of the three compactions (saves a memset node)
@@ -38,10 +42,12 @@ __global__ void __launch_bounds__(512) k_hist(int n_chunks, const int *chunk_par
         const int np = chunk_n[ch];
         const int g_lo = chunk_glo[ch], g_hi = chunk_ghi[ch];          // genomic position of the first / last position
         const i64 k0 = part_iv_off[part], k1 = part_iv_off[part + 1];
+        // uint16 in memory: the chunk's first counter is half-word sh of the array, its sixteen-byte groups those of the histogram
+        const int sh = kNarrow ? (int)(p0 & 7) : 0;
         __syncthreads();
         if constexpr (BITS == 16) {
-            // (np + 1) / 2 words, sixteen bytes per write (kWords is a multiple of four: the last write stays inside the array)
-            for (int i = threadIdx.x; i < (np + 7) >> 3; i += blockDim.x) reinterpret_cast<uint4 *>(hist)[i] = make_uint4(0u, 0u, 0u, 0u);
+            // (sh + np + 1) / 2 words, sixteen bytes per write (kWords is a multiple of four: the last write stays inside the array)
+            for (int i = threadIdx.x; i < (sh + np + 7) >> 3; i += blockDim.x) reinterpret_cast<uint4 *>(hist)[i] = make_uint4(0u, 0u, 0u, 0u);
         } else {
             for (int i = threadIdx.x; i < np; i += blockDim.x) hist[i] = 0;
         }
@@ -54,7 +60,7 @@ __global__ void __launch_bounds__(512) k_hist(int n_chunks, const int *chunk_par
         if (cached)
             for (int i = threadIdx.x; i < nk; i += blockDim.x) {
                 ivs_s[i] = iv_start[k0 + i]; ive_s[i] = iv_end[k0 + i];
-                base_s[i] = (int)(pos_off[k0 + i] - p0) - iv_start[k0 + i];   // chunk-local index = base + genomic position
+                base_s[i] = (int)(pos_off[k0 + i] - p0) - iv_start[k0 + i] + sh;   // counter's index = base + genomic position
             }
         __syncthreads();
         // 8 threads share a read: thread q of the group takes the read's exons q, q+8, ...  The walk is a chain of
@@ -64,7 +70,7 @@ __global__ void __launch_bounds__(512) k_hist(int n_chunks, const int *chunk_par
         // lanes' pieces (from the rep-ordered ex_ts / ex_te: two lines per read, anywhere)
         const int sub = threadIdx.x & 7;
         const int G8 = blockDim.x >> 3;
-        auto hit = [&](int i) {       // i: chunk-local index of the position
+        auto hit = [&](int i) {       // i: index of the position's counter (chunk-local index + sh)
             if constexpr (BITS == 16) atomicAdd(&hist[i >> 1], 1u << (16 * (i & 1)));
             else atomicAdd(&hist[i], 1);
         };
@@ -84,7 +90,7 @@ __global__ void __launch_bounds__(512) k_hist(int n_chunks, const int *chunk_par
                 ok = ts >= iv_start[k0];
                 i64 k = k0;
                 if (ok) { k = k0 + last_le(iv_start + k0, k1 - k0, ts); ok = ts <= iv_end[k] && te <= iv_end[k]; }
-                base = (int)(pos_off[k] - p0) - iv_start[k];
+                base = (int)(pos_off[k] - p0) - iv_start[k] + sh;
             }
             if (!ok) { atomicOr(&st->err, kErrExonInterval); return; }
             if (!(ignore_ends && e == e0) && ts >= g_lo && ts <= g_hi) hit(base + ts);       // :670-671
@@ -108,8 +114,25 @@ __global__ void __launch_bounds__(512) k_hist(int n_chunks, const int *chunk_par
             }
         }
         __syncthreads();
-        if constexpr (BITS == 16) {
-            // y_raw stays int32, a position per element.  A thread takes the two positions i0, i0 + 1 with p0 + i0 even -- one
+        if constexpr (kNarrow) {
+            // Group g of the array is group (p0 >> 3) + g of the histogram: sixteen bytes read, sixteen bytes stored, a wave's stores
+            // one contiguous run.  The first and the last group may hold positions of the chunks before and after (sh half-words in
+            // front; what follows half-word sh + np) -- other workgroups', other partitions', written there at any time: such a group's
+            // own counts leave as 2-byte stores, one per position, never a word that another chunk has a half of.
+            uint4 *dst = reinterpret_cast<uint4 *>(y_raw + (p0 - sh));              // (p0 - sh is a multiple of 8, y_raw 256-byte aligned)
+            const int end = sh + np, ng = (end + 7) >> 3;
+            for (int g = threadIdx.x; g < ng; g += blockDim.x) {
+                const uint4 w = reinterpret_cast<const uint4 *>(hist)[g];
+                if (8 * g >= sh && 8 * g + 8 <= end) { dst[g] = w; continue; }
+                const unsigned ww[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    const int h = 8 * g + e;
+                    if (h >= sh && h < end) y_raw[p0 - sh + h] = (uint16_t)(ww[e >> 1] >> (16 * (e & 1)));
+                }
+            }
+        } else if constexpr (BITS == 16) {
+            // y_raw is int32, a position per element.  A thread takes the two positions i0, i0 + 1 with p0 + i0 even -- one
             // aligned 8-byte store, a wave's stores one contiguous run -- whichever halves of whichever words they are (p0 is odd
             // where the partitions before it hold an odd number of positions: then i0 = -1 first, and a pair straddles two words).
             const int odd = (int)(p0 & 1);
@@ -126,12 +149,17 @@ __global__ void __launch_bounds__(512) k_hist(int n_chunks, const int *chunk_par
     }
 }
 
-template <int R>
+// Count: the histogram's element (int, or uint16_t where S1 ran packed); a count is zero-extended into the int it is staged as, and
+// nothing after load_counts knows the difference.  uint16 counts are loaded one a lane like int32 ones (2-byte loads): k_smooth is
+// 4-5 % slower from them than from int32 counts, and two variants with ONE 4-byte load of two neighbouring counts a lane on the
+// no-reflection path (three staged registers instead of five, split when they enter LDS) were slower still, +10 % and more
+// (profiles/yraw16.txt, section 1a).
+template <int R, typename Count>
 #ifndef FSEG_SMOOTH_OCC
 #define FSEG_SMOOTH_OCC 6
 #endif
 __global__ void __launch_bounds__(kSmoothThreads, FSEG_SMOOTH_OCC) k_smooth(int n_tiles, const TileDesc *__restrict__ tiles,
-                                                const int *__restrict__ y_raw, const double *__restrict__ w_g, int radius_rt,
+                                                const Count *__restrict__ y_raw, const double *__restrict__ w_g, int radius_rt,
                                                 double *y_out, unsigned *flag_pos, unsigned *flag_cand, int *blk_pre, int *tile_tot,
                                                 int *tile_defer) {
     __shared__ int xs[kSmoothTile + 2 * kMaxRadius];
@@ -158,7 +186,7 @@ __global__ void __launch_bounds__(kSmoothThreads, FSEG_SMOOTH_OCC) k_smooth(int 
         // (the record is the same in every lane: in scalar registers the tests below are branches of the whole wave)
         const int len_d = __builtin_amdgcn_readfirstlane(d.len), y0_d = __builtin_amdgcn_readfirstlane(d.y0);
         const int yb = y0_d - radius + (int)threadIdx.x;
-        const int *src = y_raw + (((i64)__builtin_amdgcn_readfirstlane((int)(d.base >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)d.base));
+        const Count *src = y_raw + (((i64)__builtin_amdgcn_readfirstlane((int)(d.base >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)d.base));
         if (R > 0 && y0_d + kSmoothTile + radius <= len_d) {
             // nothing of the window lies beyond the interval's end (two tiles in three): only the first radius positions of the
             // interval's first tile reflect, and they are all in the first staged element (R <= kSmoothThreads)
@@ -801,11 +829,15 @@ __global__ void __launch_bounds__(256) k_peaks_edges(int n_tiles, const TileDesc
 // the instances the host launches (freddie_seg.hip sees the declarations only: taking an instance's address here is what
 // instantiates it -- host stub and device code -- in this translation unit)
 __attribute__((used)) static const void *const kInstances[] = {
-    reinterpret_cast<const void *>(&k_hist<32>),
-    reinterpret_cast<const void *>(&k_hist<16>),
-    reinterpret_cast<const void *>(&k_smooth<20>),
-    reinterpret_cast<const void *>(&k_smooth<12>),
-    reinterpret_cast<const void *>(&k_smooth<0>),
+    reinterpret_cast<const void *>(&k_hist<32, int>),
+    reinterpret_cast<const void *>(&k_hist<16, int>),
+    reinterpret_cast<const void *>(&k_hist<16, uint16_t>),
+    reinterpret_cast<const void *>(&k_smooth<20, int>),
+    reinterpret_cast<const void *>(&k_smooth<12, int>),
+    reinterpret_cast<const void *>(&k_smooth<0, int>),
+    reinterpret_cast<const void *>(&k_smooth<20, uint16_t>),
+    reinterpret_cast<const void *>(&k_smooth<12, uint16_t>),
+    reinterpret_cast<const void *>(&k_smooth<0, uint16_t>),
     reinterpret_cast<const void *>(&k_scan_emit<kEmitValues>),
     reinterpret_cast<const void *>(&k_scan_emit<kEmitPositions>),
 };

@@ -9,22 +9,22 @@ namespace fseg {
 __global__ void __launch_bounds__(256) k_thr_table(const double *h_table, int h_len, double tau, int2 *tab);
 
 // seg_front.hip
-template <int BITS>
+template <int BITS, typename Out>
 __global__ void __launch_bounds__(512) k_hist(int n_chunks, const int *chunk_part, const i64 *chunk_p0, const int *chunk_n,
                                               const int *chunk_glo, const int *chunk_ghi, const i64 *chunk_lane_lo,
                                               const i64 *chunk_lane_hi, const i64 *part_iv_off,
                                               const int *iv_start, const int *iv_end, const i64 *pos_off,
                                               const i64 *part_lane_off, const int2 *__restrict__ lane_lx, const int *lane_start,
                                               const int *lane_pmax, const int2 *__restrict__ lex,
-                                              int ignore_ends, int *y_raw, Status *st, u64 *zero_ptr, i64 zero_n);
+                                              int ignore_ends, Out *y_raw, Status *st, u64 *zero_ptr, i64 zero_n);
 
 // seg_front.hip
-template <int R>
+template <int R, typename Count>
 #ifndef FSEG_SMOOTH_OCC
 #define FSEG_SMOOTH_OCC 6
 #endif
 __global__ void __launch_bounds__(kSmoothThreads, FSEG_SMOOTH_OCC) k_smooth(int n_tiles, const TileDesc *__restrict__ tiles,
-                                                const int *__restrict__ y_raw, const double *__restrict__ w_g, int radius_rt,
+                                                const Count *__restrict__ y_raw, const double *__restrict__ w_g, int radius_rt,
                                                 double *y_out, unsigned *flag_pos, unsigned *flag_cand, int *blk_pre, int *tile_tot,
                                                 int *tile_defer);
 
@@ -206,14 +206,16 @@ __global__ void __launch_bounds__(512) k_dp_giant(Status *st, const int *dp_item
                                                   unsigned char *chosen, int nm, unsigned char *scratch, i64 scratch_stride);
 
 // seg_tail.hip
-__global__ void k_segments(i64 K, const i64 *pos_off, const i64 *cand_off, const int *cand_y, const int *__restrict__ y_raw,
+template <typename Count>
+__global__ void k_segments(i64 K, const i64 *pos_off, const i64 *cand_off, const int *cand_y, const Count *__restrict__ y_raw,
                            const int *__restrict__ blk_pre, const int *tile_tot, const int *iv_tile0, const unsigned char *chosen, unsigned *final_flag, int *rseg_c, int *rseg_prev,
                            Status *st);
 
 // seg_tail.hip
+template <typename Count>
 __global__ void __launch_bounds__(64) k_refine(const Status *st, const int *cand_iv, const int *rseg_c,
                                                const int *rseg_prev, const int *cand_y, const i64 *pos_off,
-                                               const int *y_raw, const double *w_g, int radius, double sigma,
+                                               const Count *y_raw, const double *w_g, int radius, double sigma,
                                                double *g_scr, int *pk_scr, unsigned char *flag_scr,
                                                unsigned char *keep_scr, unsigned *final_flag);
 

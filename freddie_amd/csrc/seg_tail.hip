@@ -4,7 +4,43 @@
 
 namespace fseg {
 
-__global__ void k_segments(i64 K, const i64 *pos_off, const i64 *cand_off, const int *cand_y, const int *__restrict__ y_raw,
+// What k_segments' inner sum takes from the histogram itself: the counts of b's block of kSumBlock positions (from b0) up to b
+// (inclusive) less those of a's block (from a0) up to a (exclusive).  The two blocks as 16-byte loads; a block of b's may reach beyond
+// the interval's last position -- into the next interval's counts or the slab's padding: masked.
+// int32 counts: from dword-aligned addresses.
+__device__ __forceinline__ int end_blocks(const int *yr, int a0, int a, int b0, int b) {
+    int4u va[kSumBlock / 4], vb[kSumBlock / 4];
+#pragma unroll
+    for (int e = 0; e < kSumBlock / 4; ++e) { va[e] = *reinterpret_cast<const int4u *>(yr + a0 + 4 * e); vb[e] = *reinterpret_cast<const int4u *>(yr + b0 + 4 * e); }
+    int tot = 0;
+#pragma unroll
+    for (int e = 0; e < kSumBlock / 4; ++e) {
+        const int pa = a0 + 4 * e, pb = b0 + 4 * e;
+        tot += (pb <= b ? vb[e].x : 0) + (pb + 1 <= b ? vb[e].y : 0) + (pb + 2 <= b ? vb[e].z : 0) + (pb + 3 <= b ? vb[e].w : 0);
+        tot -= (pa < a ? va[e].x : 0) + (pa + 1 < a ? va[e].y : 0) + (pa + 2 < a ? va[e].z : 0) + (pa + 3 < a ? va[e].w : 0);
+    }
+    return tot;
+}
+// uint16 counts (S1 ran packed): a block is 32 bytes at an address aligned to a count, two counts a word.  Of the block's first n
+// counts word d holds both (n >= 2d + 2), its low one (n == 2d + 1) or none; the halves are unsigned, 65 535 stays 65 535.
+__device__ __forceinline__ int end_blocks(const uint16_t *yr, int a0, int a, int b0, int b) {
+    uint4u va[kSumBlock / 8], vb[kSumBlock / 8];
+#pragma unroll
+    for (int e = 0; e < kSumBlock / 8; ++e) { va[e] = *reinterpret_cast<const uint4u *>(yr + a0 + 8 * e); vb[e] = *reinterpret_cast<const uint4u *>(yr + b0 + 8 * e); }
+    const int na = a - a0, nb = b - b0 + 1;                           // counts of each block that lie in front of a / up to b
+    auto first = [](unsigned w, int n) { return n >= 2 ? (w & 0xffffu) + (w >> 16) : (n == 1 ? w & 0xffffu : 0u); };   // n counts of word w
+    unsigned tot_a = 0, tot_b = 0;
+#pragma unroll
+    for (int e = 0; e < kSumBlock / 8; ++e) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) { tot_a += first(va[e][q], na - 8 * e - 2 * q); tot_b += first(vb[e][q], nb - 8 * e - 2 * q); }
+    }
+    return (int)tot_b - (int)tot_a;
+}
+
+// Count: the histogram's element (int, or uint16_t where S1 ran packed), here and in k_refine
+template <typename Count>
+__global__ void k_segments(i64 K, const i64 *pos_off, const i64 *cand_off, const int *cand_y, const Count *__restrict__ y_raw,
                            const int *__restrict__ blk_pre, const int *tile_tot, const int *iv_tile0, const unsigned char *chosen, unsigned *final_flag, int *rseg_c, int *rseg_prev,
                            Status *st) {
     __shared__ int lds[16];
@@ -22,21 +58,11 @@ __global__ void k_segments(i64 K, const i64 *pos_off, const i64 *cand_off, const
         if (tb - ta > 64) return true;                            // (very long segments: k_refine sums them itself)
         constexpr int kBlocks = kSmoothTile / kSumBlock;
         const int *tt = tile_tot + tile0;
-        const int *yr = y_raw + base;
+        const Count *yr = y_raw + base;
         const int a0 = a & ~(kSumBlock - 1), b0 = b & ~(kSumBlock - 1);
         i64 tot = (i64)blk_pre[(i64)(tile0 + tb) * kBlocks + ((b & (kSmoothTile - 1)) >> kSumShift)]
                 - (i64)blk_pre[(i64)(tile0 + ta) * kBlocks + ((a & (kSmoothTile - 1)) >> kSumShift)];
-        // (the two blocks as 16-byte loads from dword-aligned addresses; a block of b's may reach beyond the interval's
-        // last position -- into the next interval's counts or the slab's padding: masked)
-        int4u va[kSumBlock / 4], vb[kSumBlock / 4];
-#pragma unroll
-        for (int e = 0; e < kSumBlock / 4; ++e) { va[e] = *reinterpret_cast<const int4u *>(yr + a0 + 4 * e); vb[e] = *reinterpret_cast<const int4u *>(yr + b0 + 4 * e); }
-#pragma unroll
-        for (int e = 0; e < kSumBlock / 4; ++e) {
-            const int pa = a0 + 4 * e, pb = b0 + 4 * e;
-            tot += (pb <= b ? vb[e].x : 0) + (pb + 1 <= b ? vb[e].y : 0) + (pb + 2 <= b ? vb[e].z : 0) + (pb + 3 <= b ? vb[e].w : 0);
-            tot -= (pa < a ? va[e].x : 0) + (pa + 1 < a ? va[e].y : 0) + (pa + 2 < a ? va[e].z : 0) + (pa + 3 < a ? va[e].w : 0);
-        }
+        tot += end_blocks(yr, a0, a, b0, b);
         for (int q = ta; q < tb; ++q) tot += tt[q];
         return tot >= 20;
     };
@@ -128,9 +154,10 @@ __global__ void k_segments(i64 K, const i64 *pos_off, const i64 *cand_off, const
 // from speculative loads of the four candidates below it, one slot atomic per workgroup: 2 300 waves instead of 61 000 and 20-21 us
 // either way.  With the pieces taken out: 11 us without the final flags and the inner sums, the sums 8, the flags 2 -- the kernel is four
 // or five levels of dependent L2 round trips and a drain whatever its shape.)
+template <typename Count>
 __global__ void __launch_bounds__(64) k_refine(const Status *st, const int *cand_iv, const int *rseg_c,
                                                const int *rseg_prev, const int *cand_y, const i64 *pos_off,
-                                               const int *y_raw, const double *w_g, int radius, double sigma,
+                                               const Count *y_raw, const double *w_g, int radius, double sigma,
                                                double *g_scr, int *pk_scr, unsigned char *flag_scr,
                                                unsigned char *keep_scr, unsigned *final_flag) {
     __shared__ double ws[kMaxRadius + 1];
@@ -149,7 +176,7 @@ __global__ void __launch_bounds__(64) k_refine(const Status *st, const int *cand
         int e = cand_y[sg];
         int len = e - s;
         i64 base = pos_off[cand_iv[sg]] + s;
-        const int *xr = y_raw + base;
+        const Count *xr = y_raw + base;
         if (len <= kRefCap) {
             // ---- the segment fits in LDS (nearly all do): its counts are fetched once, four coalesced rows at a time
             // from clamped addresses (a load under a condition is a branch with its own wait -- and the filter below
@@ -519,5 +546,13 @@ __global__ void __launch_bounds__(256) k_pack_labels(const uint4 *__restrict__ l
         packed[i] = out;
     }
 }
+
+// the instances the host launches (as in seg_front.hip)
+__attribute__((used)) static const void *const kInstances[] = {
+    reinterpret_cast<const void *>(&k_segments<int>),
+    reinterpret_cast<const void *>(&k_segments<uint16_t>),
+    reinterpret_cast<const void *>(&k_refine<int>),
+    reinterpret_cast<const void *>(&k_refine<uint16_t>),
+};
 
 }  // namespace fseg

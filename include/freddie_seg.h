@@ -244,8 +244,9 @@ enum {
      *   24..26 work items of the small / mid / large class k_score was launched over (a problem is one work item or more)
      *   27 the histogram ran with packed 16-bit LDS counters (k_hist<16>; 0: the 32-bit instance)
      *   28 the block size k_fix and k_segments were launched with (64, 256 or 1024, by the batch's average interval length)
-     *   29 the k_smooth instance: 20 or 12 (the unrolled radii), 0 (any other radius, the loop) */
-    FSEG_TAP_PATHS = 18        /* int32[30]                                                                            */
+     *   29 the k_smooth instance: 20 or 12 (the unrolled radii), 0 (any other radius, the loop)
+     *   30 the histogram is uint16 in device memory (FSEG_YRAW16, where word 27 is 1; 0: int32) */
+    FSEG_TAP_PATHS = 18        /* int32[31]                                                                            */
 };
 int fseg_tap(fseg_ctx *ctx, int what, void *dst, int64_t cap_bytes, int64_t *n_bytes);
 
