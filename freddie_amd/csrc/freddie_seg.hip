@@ -26,39 +26,55 @@ namespace {
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-// A DevBuf is a view into one of the context's slabs (or, for the few buffers with a life of their own, an allocation):
-// the buffers of a batch are carved out of three device allocations -- inputs (one host-to-device copy fills it),
-// position-sized work arrays, data-dependent arenas -- so a new batch costs no allocator call unless it is larger than
-// every batch before it.
-struct DevBuf {
+// A DevBuf<T> is a VIEW of device memory that holds T: into one of the context's slabs (the buffers of a batch are carved out
+// of three device allocations -- inputs (one host-to-device copy fills it), position-sized work arrays, data-dependent arenas --
+// so a new batch costs no allocator call unless it is larger than every batch before it), or, as the base of an OwnDev<T>, of an
+// allocation with a life of its own.  T is what the kernels take: the carve-up, the launches and every copy get their sizes from it
+// (bytes(n)).  DevBuf<void> holds different types per batch or region: its sizes are bytes, its readers name the type (as<T>()).
+template <typename T> struct DevBuf {
+    T *p = nullptr;
+    size_t cap = 0;      // bytes
+    static size_t bytes(size_t n) { return n * sizeof(T); }
+};
+template <> struct DevBuf<void> {
     void *p = nullptr;
     size_t cap = 0;
-    template <typename T> T *as() const { return reinterpret_cast<T *>(p); }
+    static size_t bytes(size_t n) { return n; }
+    template <typename U> U *as() const { return static_cast<U *>(p); }
 };
-struct Slab {
-    void *p = nullptr;
+template <typename T> size_t bytes_of(const DevBuf<T> &, size_t n) { return DevBuf<T>::bytes(n); }   // n elements of this buffer
+// The owners: each frees what it holds when it goes, none can be copied.
+struct NoCopy { NoCopy() = default; NoCopy(const NoCopy &) = delete; NoCopy &operator=(const NoCopy &) = delete; };
+template <typename T> struct OwnDev : DevBuf<T>, NoCopy {   // a device allocation of its own (ensure() grows it)
+    ~OwnDev() { if (this->p) (void)hipFree(this->p); }
+    hipError_t alloc(size_t bytes) { this->cap = bytes; return hipMalloc(&this->p, bytes); }   // exactly these bytes
+};
+struct Slab : OwnDev<void> {};                        // ... that buffers are carved out of (reserve() grows it)
+template <typename T> struct Pinned : NoCopy {        // pinned host memory (reserve_host() grows it; alloc(): exactly one T)
+    T *p = nullptr;
     size_t cap = 0;
+    ~Pinned() { if (p) (void)hipHostFree(p); }
+    hipError_t alloc() { cap = sizeof(T); return hipHostMalloc(&p, sizeof(T), hipHostMallocDefault); }
+    T *operator->() const { return p; }
+    T &operator*() const { return *p; }
 };
-struct HostBuf {     // pinned host memory
-    void *p = nullptr;
-    size_t cap = 0;
-    template <typename T> T *as() const { return reinterpret_cast<T *>(p); }
-};
-// offsets of consecutive 256-byte-aligned buffers inside a slab: add() them all, reserve the slab, then bind()
+// offsets of consecutive 256-byte-aligned buffers inside a slab: add() them all (n elements each, plus padding bytes where a
+// kernel reads past the end), reserve the slab, then bind()
 struct Carve {
-    struct Item { DevBuf *b; size_t off, bytes; };
+    struct Item { void *buf; void (*set)(void *buf, char *p, size_t cap); size_t off, bytes; };
     std::vector<Item> items;
     size_t total = 0;
-    size_t add(DevBuf &b, size_t bytes) {
-        const size_t off = total;
-        items.push_back(Item{&b, off, bytes});
+    template <typename T> void add(DevBuf<T> &b, size_t n, size_t pad_bytes = 0) {
+        const size_t off = total, bytes = DevBuf<T>::bytes(n) + pad_bytes;
+        items.push_back(Item{&b, [](void *buf, char *p, size_t cap) { auto *d = static_cast<DevBuf<T> *>(buf); d->p = static_cast<T *>(static_cast<void *>(p)); d->cap = cap; }, off, bytes});
         total = (off + bytes + 255) & ~(size_t)255;
-        return off;
     }
-    void bind(const Slab &s) const {
-        for (const Item &it : items) { it.b->p = static_cast<char *>(s.p) + it.off; it.b->cap = it.bytes; }
-    }
+    void bind(void *base) const { for (const Item &it : items) it.set(it.buf, static_cast<char *>(base) + it.off, it.bytes); }
 };
+// where a buffer carved out of the allocation at dev_base lies in the host image of that allocation
+template <typename T> T *mirror_of(char *host_base, const void *dev_base, const DevBuf<T> &d) {
+    return static_cast<T *>(static_cast<void *>(host_base + (reinterpret_cast<const char *>(d.p) - static_cast<const char *>(dev_base))));
+}
 
 enum Stage { ST_HIST, ST_SMOOTH, ST_THRESHOLD, ST_CANDIDATES, ST_FIX, ST_SCORE_PREP, ST_SCORE, ST_DP, ST_REFINE, ST_FINAL, ST_LABEL, ST_COUNT,
              ST_GRAPH_PRE = ST_COUNT, ST_GRAPH_POST, ST_REPORTED };
@@ -106,14 +122,18 @@ struct fseg_ctx {
     int n_tiles = 0;
     bool expanded = false;
     std::vector<i64> part_iv_off, part_rep_off;
-    // the three slabs and the buffers that live outside them
+    // The three slabs and the buffers that live outside them.  Every DevBuf<T> below is a view into a slab, every OwnDev<T> /
+    // Slab / Pinned<T> an owner that frees itself when the context goes (~fseg_ctx has the order).  Untyped (DevBuf<void> /
+    // OwnDev<void>, read through as<T>()) are the buffers whose element is not one type: d_y_raw (int32 or uint16 per batch),
+    // d_labels (bytes, cleared and packed as uint4), d_sort_tmp and d_giant (scratch that a sort / a kernel carves up itself),
+    // and the annotate arenas d_an_in / d_an_work / d_an_out (carved into typed local views per call).
     Slab slab_in, slab_pos, slab_arena;
-    HostBuf h_stage;             // pinned image of the input slab's uploaded part
-    HostBuf h_res;               // pinned results: final offsets | final positions | label offsets | labels
+    Pinned<char> h_stage;        // pinned image of the input slab's uploaded part
+    Pinned<char> h_res;          // pinned results: final offsets | final positions | label offsets | labels
     size_t res_off[4] = {0, 0, 0, 0};
     std::vector<i64> res_pfo;    // part_final_off gathered from the per-interval offsets
-    DevBuf d_labels;             // label arena (sized after the final positions are known)
-    DevBuf d_packed;             // the same at two bits per label, for the trip to the host
+    OwnDev<void> d_labels;       // label arena (sized after the final positions are known)
+    OwnDev<unsigned> d_packed;   // the same at two bits per label, for the trip to the host
     int fetched_packed = -1;     // what the pinned result buffer holds: -1 nothing, 0 label bytes, 1 packed labels
     // Round 5: the labels are WRITTEN at two bits each (k_label_reads ORs the codes of a rep's non-'0' labels into d_packed, a word
     // at a time) whenever no column's default can be '2' (threshold_rate < 1: a read without coverage is never ambiguous) -- the
@@ -126,44 +146,57 @@ struct fseg_ctx {
     bool label_has2 = false;         // some segment length has h >= 1 (lo < 0): a read without coverage is '2' there -> byte arena
     bool run_label_packed = false;   // the resident run's labels live in d_packed
     bool labels_unpacked = false;    // ... and d_labels holds their byte form (made on demand)
-    DevBuf d_sort_tmp;
+    OwnDev<void> d_sort_tmp;
     // device buffers: inputs (slab_in, uploaded)
-    DevBuf d_part_iv_off, d_part_rep_off, d_part_lane_off, d_iv_start, d_iv_end, d_pos_off, d_iv_part,
-        d_rep_exon_off, d_rep_weight, d_ex_ts, d_ex_te, d_tile_desc, d_iv_tile0, d_blk_iv0, d_rb_part, d_rb_r0, d_rb_sum, d_rb_base, d_rb_max, d_rb_cmax,
-        d_hc_part, d_hc_p0, d_hc_n, d_hc_glo, d_hc_ghi;
+    DevBuf<i64> d_part_iv_off, d_part_rep_off, d_part_lane_off, d_pos_off, d_rep_exon_off, d_hc_p0, d_rb_sum, d_rb_base;
+    DevBuf<int> d_iv_start, d_iv_end, d_iv_part, d_rep_weight, d_ex_ts, d_ex_te, d_iv_tile0, d_blk_iv0, d_rb_part, d_rb_r0, d_rb_max, d_rb_cmax,
+        d_hc_part, d_hc_n, d_hc_glo, d_hc_ghi;
+    DevBuf<TileDesc> d_tile_desc;
     // slab_in, derived on the device by the upload
-    DevBuf d_lane_ex, d_lane_start, d_lane_pmax, d_hc_llo, d_hc_lhi, d_key_a, d_key_b, d_val_a, d_val_b, d_rep_last;
-    DevBuf d_lane_lx, d_lex, d_rb_esum, d_rb_ebase;   // the exons again as one (ts, te) stream in lane order, and every lane's range in it
+    DevBuf<longlong2> d_lane_ex;
+    DevBuf<int> d_lane_start, d_lane_pmax, d_val_a, d_val_b, d_rep_last;
+    DevBuf<i64> d_hc_llo, d_hc_lhi, d_rb_esum, d_rb_ebase;
+    DevBuf<u64> d_key_a, d_key_b;
+    DevBuf<int2> d_lane_lx, d_lex;      // the exons again as one (ts, te) stream in lane order, and every lane's range in it
     i64 max_rep_exons = 0;       // most exons of one rep in the resident batch
-    DevBuf d_w_main, d_w_refine, d_h_table, d_thr_tab;     // parameter tables (own allocations)
+    OwnDev<double> d_w_main, d_w_refine, d_h_table;        // parameter tables (own allocations)
+    OwnDev<int2> d_thr_tab;
     // device buffers: position-sized (slab_pos)
-    DevBuf d_bits;               // the three flag masks (Y > 0, candidate, final position), a bit per position each, cleared per run
-    DevBuf d_y_raw, d_y, d_v, d_scan_state, d_bsum, d_gsum, d_bsum_side, d_g, d_pk, d_pf, d_kp;
-    int n_hist_chunks = 0;
-    DevBuf d_voff, d_chunk_off, d_csum, d_mean, d_thr, d_label_off, d_part_has2;
-    int n_rep_blocks = 0;
+    DevBuf<unsigned> d_bits;     // the three flag masks (Y > 0, candidate, final position), a bit per position each, cleared per run
+    DevBuf<void> d_y_raw;        // S1's histogram: int32, or uint16 where the batch's counters are (yraw_narrow)
+    DevBuf<double> d_y, d_v, d_g, d_csum, d_mean, d_thr;
+    DevBuf<u64> d_scan_state;
+    DevBuf<int> d_bsum, d_gsum, d_bsum_side, d_pk, d_part_has2;
+    DevBuf<unsigned char> d_pf, d_kp;
+    DevBuf<i64> d_voff, d_chunk_off, d_label_off;
+    int n_hist_chunks = 0, n_rep_blocks = 0;
     // candidate-sized (slab_pos)
-    DevBuf d_cand_off, d_cand_y, d_fixed0, d_added, d_fixed, d_chosen, d_final_off, d_final_y, d_final_pos, d_final_iv, d_col_thr,
-        d_col_zero;
-    DevBuf d_tile_defer;        // per smoothing tile: start of the plateau that reaches the tile's end (-1: none)
-    DevBuf d_blk_pre, d_tile_tot, d_seg_iv, d_seg_prev, d_rseg_c, d_cand_pn, d_cand_ll, d_cand_ln, d_cand_wide, d_prob_bs;
+    DevBuf<i64> d_cand_off, d_final_off, d_prob_bs;
+    DevBuf<int> d_cand_y, d_final_y, d_final_pos, d_final_iv, d_blk_pre, d_tile_tot, d_seg_iv, d_seg_prev, d_rseg_c, d_cand_pn, d_cand_ll, d_cand_ln;
+    DevBuf<int> d_tile_defer;   // per smoothing tile: start of the plateau that reaches the tile's end (-1: none)
+    DevBuf<unsigned char> d_fixed0, d_added, d_fixed, d_chosen, d_col_zero, d_cand_wide;
+    DevBuf<int2> d_col_thr;
     // problems / arenas (slab_arena)
-    DevBuf d_prob_iv, d_prob_start, d_prob_n, d_prob_pair_off, d_prob_tri_off, d_prob_flags, d_prob_chain,
-        d_prob_cov_off, d_prob_lane_lo, d_prob_lane_n;
-    DevBuf d_dp_items, d_solve_items, d_solve_desc, d_prob_desc, d_work_pc, d_cls_items, d_work_active, d_pair_thr, d_amb, d_out, d_cov;
+    DevBuf<int> d_prob_iv, d_prob_start, d_prob_n, d_prob_flags, d_prob_chain, d_prob_lane_lo, d_prob_lane_n, d_dp_items, d_solve_items;
+    DevBuf<i64> d_prob_pair_off, d_prob_tri_off, d_prob_cov_off;
+    DevBuf<ProbDesc> d_solve_desc, d_prob_desc;
+    DevBuf<int2> d_work_pc, d_pair_thr;
+    DevBuf<int4> d_cls_items;
+    DevBuf<unsigned char> d_work_active;
+    DevBuf<unsigned> d_amb, d_out, d_cov;
     // hand-over arena between k_solve<.., SPLIT> and k_dpw (dpx_slot_bytes per problem of the three solve lists), laid out by
     // alloc_arenas() for the counts it knew: a launch takes the split path only for a list that fits what was laid out
-    DevBuf d_wide_items;         // per solve list: the list positions of the problems that see more than kFuseLanes reads (k_prob_emit)
-    DevBuf d_wide_all;           // ... of the three lists together (positions from the first list's start)
-    DevBuf d_dpx;
+    DevBuf<int> d_wide_items;    // per solve list: the list positions of the problems that see more than kFuseLanes reads (k_prob_emit)
+    DevBuf<int> d_wide_all;      // ... of the three lists together (positions from the first list's start)
+    DevBuf<unsigned char> d_dpx;
     i64 dpx_base[3] = {0, 0, 0}, dpx_stride[3] = {0, 0, 0}, dpx_n[3] = {0, 0, 0};
     int dpx_nm = 0, dpx_cnt[3] = {1, 1, 1};
     static constexpr i64 kWideOneMax = 256;   // plan 'W' takes a batch's wide problems in one launch when there are at most this many
     int split_dp = 7;           // FSEG_SPLIT_DP: bit 0 / 1 / 2 = the small / mid / large class hands its DPs to k_dpw (0: the DP stays the tail of k_solve's workgroups);
                                 // bit 3 = the large class's k_dpw by one wave a problem (as the other classes') instead of eight
     i64 prob_cap = 0, work_cap = 0, pair_cap = 0, tri_cap = 0, label_cap = 0, chunk_cap = 0, cov_cap = 0;
-    DevBuf d_status, d_prep, d_tacc;
-    DevBuf d_sync;               // SyncWords: the scoring stage's device-side fork / join (k_wait_word)
+    OwnDev<Status> d_status; OwnDev<PrepStatus> d_prep; OwnDev<unsigned long long> d_tacc;
+    OwnDev<SyncWords> d_sync;    // the scoring stage's device-side fork / join (k_wait_word)
     unsigned sync_gen = 0;       // generation of the last stage enqueued with device-side waiters
     // What a waiter waits at most, in ticks of the 100 MHz clock, per 2^18 reads of the batch: 10 ms, at most 20 (FSEG_SYNC_TICKS; tests
     // force a time-out with 1).  Round 5's 20 ms DID run out, four times in one 8-context trace -- for two reasons, both removed in
@@ -180,8 +213,7 @@ struct fseg_ctx {
     unsigned forked_runs = 0;    // runs of this context that owned the device (side streams in use); FSEG_TAP_SYNC[7]
     bool run_events_only = false;   // this run: no device-side waiters (it is the rerun after a timeout)
     bool dev_sync = true;        // FSEG_DEV_SYNC=0: the stage's side streams are forked and joined with events only (also after a waiter timed out)
-    Status *h_status = nullptr;   // pinned
-    PrepStatus *h_prep = nullptr; // pinned
+    Pinned<Status> h_status; Pinned<PrepStatus> h_prep;
     bool prep_checked = false;   // the upload's device-side validation has been read back
     bool counted_in_flight = false, counted_live = false;
     // Which side streams may carry a device-side waiter: those whose hardware queue is NOT the main stream's (probe_side_queues).
@@ -201,7 +233,7 @@ struct fseg_ctx {
     bool profile_all = true;    // false (fseg_set_profiling(ctx, 2)): only the interval-scoring stage is bracketed by events
     bool have_huge = false;      // the batch has a problem with more than kNMax candidates: launch the huge kernels
     int nm_giant = 0;            // ... with more than kNHuge: its size (rounded up: the LDS carve-up and scratch piece of the giant kernels); 0: none
-    DevBuf d_giant;              // their scratch: kGiantWgs pieces of giant_scratch_bytes(nm_giant) (own allocation)
+    OwnDev<void> d_giant;        // their scratch: kGiantWgs pieces of giant_scratch_bytes(nm_giant) (own allocation)
     bool dp_wide_counts = false; // some problem sees >= 65536 reads: DP stages 32-bit counts
     int nm_big = kNMax;         // LDS carve-up of the big-problem kernels: largest problem of the batch, rounded up
     bool small_batch = false;
@@ -272,10 +304,11 @@ struct fseg_ctx {
     int paths[PATH_WORDS] = {};
     // fseg_annotate: the uploaded reads (one allocation, mirrored by a pinned image), per-read work arrays, the emitted lists, and
     // the pinned buffers fseg_annotation() points into (own allocations: nothing of a run or of fseg_results* touches them)
-    DevBuf d_an_in, d_an_work, d_an_out;
-    HostBuf h_an_in, h_an;
+    OwnDev<void> d_an_in, d_an_work, d_an_out;
+    Pinned<char> h_an_in, h_an;
     bool have_annot = false;
     fseg_annot annot{};
+    ~fseg_ctx();                // streams drained, graphs, HSA signal, events, streams -- then the owners above free themselves, as members
 };
 
 namespace {
@@ -327,7 +360,8 @@ struct Tick {
 };
 
 // own allocation (parameter tables, label arena, sort scratch): grows, never shrinks
-int ensure(fseg_ctx *c, DevBuf &b, size_t bytes) {
+template <typename T>
+int ensure(fseg_ctx *c, OwnDev<T> &b, size_t bytes) {
     if (bytes <= b.cap && b.p) return FSEG_OK;
     if (b.p) HIP_TRY(c, hipFree(b.p));
     b.p = nullptr; b.cap = 0;
@@ -350,7 +384,7 @@ int reserve(fseg_ctx *c, Slab &s, size_t bytes, bool keep = false) {
     s.p = np; s.cap = want;
     return FSEG_OK;
 }
-int reserve_host(fseg_ctx *c, HostBuf &h, size_t bytes) {
+int reserve_host(fseg_ctx *c, Pinned<char> &h, size_t bytes) {
     if (bytes <= h.cap && h.p) return FSEG_OK;
     if (h.p) HIP_TRY(c, hipHostFree(h.p));
     h.p = nullptr; h.cap = 0;
@@ -360,12 +394,14 @@ int reserve_host(fseg_ctx *c, HostBuf &h, size_t bytes) {
     return FSEG_OK;
 }
 template <typename T>
-int upload_vec(fseg_ctx *c, DevBuf &b, const T *src, size_t n) {
-    int rc = ensure(c, b, n * sizeof(T));
+int upload_vec(fseg_ctx *c, OwnDev<T> &b, const T *src, size_t n) {
+    int rc = ensure(c, b, bytes_of(b, n));
     if (rc) return rc;
-    if (n) HIP_TRY(c, hipMemcpyAsync(b.p, src, n * sizeof(T), hipMemcpyHostToDevice, c->stream));
+    if (n) HIP_TRY(c, hipMemcpyAsync(b.p, src, bytes_of(b, n), hipMemcpyHostToDevice, c->stream));
     return FSEG_OK;
 }
+// where a buffer of the input slab lies in the slab's pinned staging image (its uploaded part only)
+template <typename T> T *host_of(const fseg_ctx *c, const DevBuf<T> &d) { return mirror_of(c->h_stage.p, c->slab_in.p, d); }
 
 // A blocking copy on the context's OWN stream.  (Never hipMemcpy: it runs on the legacy stream, which must not be touched while another
 // thread of the process -- another context -- is capturing a graph: "operation would make the legacy stream depend on a capturing blocking
@@ -404,35 +440,21 @@ void drop_graph(fseg_ctx *c) {
 // the label arena for label_cap labels: two bits each (d_packed) when this context's parameters allow it, else bytes (d_labels)
 bool labels_packed(const fseg_ctx *c) { return c->label_packed_ok && c->have_params && !c->label_has2; }
 int ensure_label_arena(fseg_ctx *c) {
-    if (labels_packed(c)) return ensure(c, c->d_packed, (size_t)((c->label_cap + 15) / 16) * 4 + 16);
+    if (labels_packed(c)) return ensure(c, c->d_packed, bytes_of(c->d_packed, (size_t)((c->label_cap + 15) / 16)) + 16);
     return ensure(c, c->d_labels, (size_t)c->label_cap + 16);
 }
 int alloc_arenas(fseg_ctx *c) {
     drop_graph(c);
     Carve cv;
-    cv.add(c->d_prob_iv, (size_t)c->prob_cap * 4);
-    cv.add(c->d_prob_start, (size_t)c->prob_cap * 4);
-    cv.add(c->d_prob_n, (size_t)c->prob_cap * 4);
-    cv.add(c->d_prob_pair_off, (size_t)c->prob_cap * 8);
-    cv.add(c->d_prob_tri_off, (size_t)c->prob_cap * 8);
-    cv.add(c->d_prob_flags, (size_t)c->prob_cap * 4);
-    cv.add(c->d_prob_chain, (size_t)c->prob_cap * 4);
-    cv.add(c->d_dp_items, (size_t)c->prob_cap * 4);
-    cv.add(c->d_solve_items, (size_t)c->prob_cap * 4);
-    cv.add(c->d_wide_items, (size_t)c->prob_cap * 4);
-    cv.add(c->d_wide_all, (size_t)c->prob_cap * 4);
-    cv.add(c->d_solve_desc, (size_t)c->prob_cap * sizeof(ProbDesc));
-    cv.add(c->d_prob_cov_off, (size_t)c->prob_cap * 8);
-    cv.add(c->d_prob_lane_lo, (size_t)c->prob_cap * 4);
-    cv.add(c->d_prob_lane_n, (size_t)c->prob_cap * 4);
-    cv.add(c->d_prob_desc, (size_t)c->prob_cap * sizeof(ProbDesc));
-    cv.add(c->d_work_pc, (size_t)c->work_cap * 8);
-    cv.add(c->d_cls_items, (size_t)c->work_cap * 16);
-    cv.add(c->d_work_active, (size_t)c->work_cap);
-    cv.add(c->d_cov, (size_t)c->cov_cap * 4);
-    cv.add(c->d_pair_thr, (size_t)c->pair_cap * 8);
-    cv.add(c->d_amb, (size_t)c->pair_cap * 4);
-    cv.add(c->d_out, (size_t)c->tri_cap * 4);
+    const size_t n_prob = (size_t)c->prob_cap, nw = (size_t)c->work_cap;
+    cv.add(c->d_prob_iv, n_prob); cv.add(c->d_prob_start, n_prob); cv.add(c->d_prob_n, n_prob); cv.add(c->d_prob_pair_off, n_prob); cv.add(c->d_prob_tri_off, n_prob);
+    cv.add(c->d_prob_flags, n_prob); cv.add(c->d_prob_chain, n_prob); cv.add(c->d_dp_items, n_prob); cv.add(c->d_solve_items, n_prob);
+    cv.add(c->d_wide_items, n_prob); cv.add(c->d_wide_all, n_prob); cv.add(c->d_solve_desc, n_prob);
+    cv.add(c->d_prob_cov_off, n_prob); cv.add(c->d_prob_lane_lo, n_prob); cv.add(c->d_prob_lane_n, n_prob); cv.add(c->d_prob_desc, n_prob);
+    cv.add(c->d_work_pc, nw); cv.add(c->d_cls_items, nw); cv.add(c->d_work_active, nw);
+    cv.add(c->d_cov, (size_t)c->cov_cap);
+    cv.add(c->d_pair_thr, (size_t)c->pair_cap); cv.add(c->d_amb, (size_t)c->pair_cap);
+    cv.add(c->d_out, (size_t)c->tri_cap);
     {
         size_t bytes = 0;
         const int nms[3] = {kClsSmall, kClsMid, c->nm_big};
@@ -448,7 +470,7 @@ int alloc_arenas(fseg_ctx *c) {
         cv.add(c->d_dpx, bytes);
     }
     TRY(reserve(c, c->slab_arena, cv.total));
-    cv.bind(c->slab_arena);
+    cv.bind(c->slab_arena.p);
     TRY(ensure_label_arena(c));
     return FSEG_OK;
 }
@@ -476,9 +498,9 @@ int enqueue_run(fseg_ctx *c, unsigned segs, bool sized = false, i64 label_fill_b
     const bool stage_events = c->profiling && (sized || c->run_plain);
     const int n_part = c->n_part;
     const i64 K = c->K, NPOS = c->NPOS;
-    Status *st = c->d_status.as<Status>();
+    Status *st = c->d_status.p;
     // the flag masks: Y > 0 | candidate | final position, flag_words(NPOS) words each
-    unsigned *flag_pos_bits = c->d_bits.as<unsigned>(), *flag_cand_bits = flag_pos_bits + flag_words(NPOS), *flag_final_bits = flag_cand_bits + flag_words(NPOS);
+    unsigned *flag_pos_bits = c->d_bits.p, *flag_cand_bits = flag_pos_bits + flag_words(NPOS), *flag_final_bits = flag_cand_bits + flag_words(NPOS);
     auto begin = [&](int i) { if (stage_events && (c->profile_all || i == ST_SCORE)) (void)hipEventRecord(c->ev_b[i], s); };
     auto end = [&](int i) { if (stage_events && (c->profile_all || i == ST_SCORE)) (void)hipEventRecord(c->ev_e[i], s); };
     // fork(k): side stream k continues from here; join(k): the main stream waits for it.  Every fork is joined before
@@ -537,7 +559,7 @@ int enqueue_run(fseg_ctx *c, unsigned segs, bool sized = false, i64 label_fill_b
     // k_prob_emit, whose last workgroup is what the side streams wait for; only on side streams whose hardware queue is not the
     // main stream's (side_ok, probed once: a waiter there would sit in front of the kernel it waits for)
     const bool dev_sync = plan && c->dev_sync && !c->run_events_only && do_pre2 && (sized || c->run_plain) && c->d_sync.p != nullptr;
-    SyncWords *sw = c->d_sync.as<SyncWords>();
+    SyncWords *sw = c->d_sync.p;
     const unsigned sync_gen = dev_sync ? ++c->sync_gen : 0;
     // (a context's first stages with waiters also load the stage's code objects and make the runtime allocate scratch for the side
     // streams' queues -- hundreds of microseconds, once: tools/waiter_probe.py)
@@ -563,18 +585,18 @@ int enqueue_run(fseg_ctx *c, unsigned segs, bool sized = false, i64 label_fill_b
     int tile_grid = grid_for(c->n_tiles, 1, 16384);
     const i64 scan_nb = scan_blocks(NPOS);
     const int scan_grid = scan_nb > 0 ? (int)scan_nb : 1;       // exactly one workgroup per scan block (look-back)
-    u64 *scan_state = c->d_scan_state.as<u64>();
+    u64 *scan_state = c->d_scan_state.p;
     // single-pass look-back scan while the chain of blocks is short; block sums + one scanning workgroup beyond that
     const bool scan_single = scan_nb <= c->scan_single_max;
-    int *bsum_side = scan_single ? nullptr : c->d_bsum_side.as<int>();     // block sums of the scan that runs on a side stream (values)
+    int *bsum_side = scan_single ? nullptr : c->d_bsum_side.p;     // block sums of the scan that runs on a side stream (values)
     // the two position compactions: blocks of kPosBlock positions (a quarter of the words of look-back state, same layout).  The
     // look-back chain keeps its limit in POSITIONS (FSEG_SCAN_SINGLE_MAX blocks of kScanBlock, as it was measured): beyond it
     // block sums + group sums that the emitting workgroups add up themselves (k_pos_count), no scanning workgroup between
     const i64 pos_nb = pos_blocks(NPOS);
     const int pos_grid = pos_nb > 0 ? (int)pos_nb : 1;          // exactly one workgroup per block
     const bool pos_single = scan_single;
-    int *bsum = pos_single ? nullptr : c->d_bsum.as<int>();
-    int *gsum = pos_single ? nullptr : c->d_gsum.as<int>();
+    int *bsum = pos_single ? nullptr : c->d_bsum.p;
+    int *gsum = pos_single ? nullptr : c->d_gsum.p;
     auto pos_counts = [&](hipStream_t q, const unsigned *flags) {
         if (pos_single) return;
         hipLaunchKernelGGL(k_pos_count, dim3(grid_for(pos_groups(NPOS), 1, 4096)), dim3(kPosCountThreads), 0, q, flags, NPOS, bsum, gsum);
@@ -585,29 +607,29 @@ int enqueue_run(fseg_ctx *c, unsigned segs, bool sized = false, i64 label_fill_b
         hipLaunchKernelGGL(k_scan2, dim3(1), dim3(kScan2Threads), 0, q, bs, scan_nb, total_dev, off_last);
     };
     int work_grid = grid_for(c->work_cap, 1, 4096);
-    ProblemArrays pr{c->d_prob_iv.as<int>(), c->d_prob_start.as<int>(), c->d_prob_n.as<int>(),
-                     c->d_prob_pair_off.as<i64>(), c->d_prob_tri_off.as<i64>(), c->d_prob_flags.as<int>(),
-                     c->d_prob_chain.as<int>(), c->d_prob_cov_off.as<i64>(), c->d_prob_lane_lo.as<int>(),
-                     c->d_prob_lane_n.as<int>()};
+    ProblemArrays pr{c->d_prob_iv.p, c->d_prob_start.p, c->d_prob_n.p,
+                     c->d_prob_pair_off.p, c->d_prob_tri_off.p, c->d_prob_flags.p,
+                     c->d_prob_chain.p, c->d_prob_cov_off.p, c->d_prob_lane_lo.p,
+                     c->d_prob_lane_n.p};
     const int pg = grid_for(NPOS / 8 / kProbBlock + 1, 1, 1024);
     // few candidates: the emit kernel scans by itself, one launch instead of three (never in a sized run: there the
     // host reads the scan's totals before the emit kernel is launched)
-    i64 *prob_bs = (c->prob_self_scan && !sized) ? nullptr : c->d_prob_bs.as<i64>();
+    i64 *prob_bs = (c->prob_self_scan && !sized) ? nullptr : c->d_prob_bs.p;
     if (do_pre1) {
     {   // Status and the flag planes (OR-ed into: k_smooth, k_peaks_edges, k_segments, k_refine) by one launch (two memsets were three fill kernels)
         const i64 nw = 3 * (i64)flag_words(NPOS);
-        hipLaunchKernelGGL(k_clear, dim3(grid_for(nw / 4 + 1, 256, 2048)), dim3(256), 0, s, st, c->d_bits.as<unsigned>(), nw);
+        hipLaunchKernelGGL(k_clear, dim3(grid_for(nw / 4 + 1, 256, 2048)), dim3(256), 0, s, st, c->d_bits.p, nw);
     }
     begin(ST_HIST);
     // S1
     // (the chunks were laid out on upload for one counter width: one instance per launch)
 #define FSEG_LAUNCH_HIST(BITS, OUT)                                                                                    \
     hipLaunchKernelGGL((k_hist<BITS, OUT>), dim3(grid_for(c->n_hist_chunks, 1, 16384)), dim3(512), 0, s, c->n_hist_chunks,   \
-                       c->d_hc_part.as<int>(), c->d_hc_p0.as<i64>(), c->d_hc_n.as<int>(), c->d_hc_glo.as<int>(),       \
-                       c->d_hc_ghi.as<int>(), c->d_hc_llo.as<i64>(), c->d_hc_lhi.as<i64>(), c->d_part_iv_off.as<i64>(), c->d_iv_start.as<int>(), c->d_iv_end.as<int>(), \
-                       c->d_pos_off.as<i64>(), c->d_part_lane_off.as<i64>(), c->d_lane_lx.as<int2>(),                  \
-                       c->d_lane_start.as<int>(), c->d_lane_pmax.as<int>(),                                            \
-                       c->d_lex.as<int2>(), c->P.ignore_ends, c->d_y_raw.as<OUT>(), st,                                \
+                       c->d_hc_part.p, c->d_hc_p0.p, c->d_hc_n.p, c->d_hc_glo.p,       \
+                       c->d_hc_ghi.p, c->d_hc_llo.p, c->d_hc_lhi.p, c->d_part_iv_off.p, c->d_iv_start.p, c->d_iv_end.p, \
+                       c->d_pos_off.p, c->d_part_lane_off.p, c->d_lane_lx.p,                  \
+                       c->d_lane_start.p, c->d_lane_pmax.p,                                            \
+                       c->d_lex.p, c->P.ignore_ends, c->d_y_raw.as<OUT>(), st,                                \
                        scan_state, scan_single ? scan_nb * 3 : 0)
     c->paths[fseg_ctx::PATH_HIST16] = c->hist_packed;
     c->paths[fseg_ctx::PATH_YRAW16] = c->yraw_narrow;
@@ -618,10 +640,10 @@ int enqueue_run(fseg_ctx *c, unsigned segs, bool sized = false, i64 label_fill_b
     end(ST_HIST); begin(ST_SMOOTH);
     // S2
 #define FSEG_LAUNCH_SMOOTH_AS(RV, COUNT)                                                                               \
-    hipLaunchKernelGGL((k_smooth<RV, COUNT>), dim3(tile_grid), dim3(kSmoothThreads), 0, s, c->n_tiles, c->d_tile_desc.as<TileDesc>(),      \
-                       c->d_y_raw.as<COUNT>(), c->d_w_main.as<double>(),                                               \
-                       c->P.radius_main, c->d_y.as<double>(), flag_pos_bits,                           \
-                       flag_cand_bits, c->d_blk_pre.as<int>(), c->d_tile_tot.as<int>(), c->d_tile_defer.as<int>())
+    hipLaunchKernelGGL((k_smooth<RV, COUNT>), dim3(tile_grid), dim3(kSmoothThreads), 0, s, c->n_tiles, c->d_tile_desc.p,      \
+                       c->d_y_raw.as<COUNT>(), c->d_w_main.p,                                               \
+                       c->P.radius_main, c->d_y.p, flag_pos_bits,                           \
+                       flag_cand_bits, c->d_blk_pre.p, c->d_tile_tot.p, c->d_tile_defer.p)
 #define FSEG_LAUNCH_SMOOTH(RV) do { if (c->yraw_narrow) { FSEG_LAUNCH_SMOOTH_AS(RV, uint16_t); } else { FSEG_LAUNCH_SMOOTH_AS(RV, int); } } while (0)
     // sigma = 5 (default) and sigma = 3 (config 5) have their own unrolled instances; any other radius runs the loop
     if (c->P.radius_main == 20) { c->paths[fseg_ctx::PATH_SMOOTH_R] = 20; FSEG_LAUNCH_SMOOTH(20); }
@@ -644,61 +666,61 @@ int enqueue_run(fseg_ctx *c, unsigned segs, bool sized = false, i64 label_fill_b
     const bool thr_part = thr_part_fits && (c->thr_part == 1 || (c->thr_part < 0 && n_part >= 64));
     if (thr_part) {
         c->paths[fseg_ctx::PATH_THR_PART] = 1;
-        hipLaunchKernelGGL(k_thr_part, dim3(grid_for(n_part, 1, 4096)), dim3(512), 0, q, n_part, c->d_part_iv_off.as<i64>(), c->d_pos_off.as<i64>(), NPOS,
-                           flag_pos_bits, c->d_y.as<double>(), c->d_v.as<double>(), c->P.variance_factor, c->d_mean.as<double>(), c->d_thr.as<double>());
+        hipLaunchKernelGGL(k_thr_part, dim3(grid_for(n_part, 1, 4096)), dim3(512), 0, q, n_part, c->d_part_iv_off.p, c->d_pos_off.p, NPOS,
+                           flag_pos_bits, c->d_y.p, c->d_v.p, c->P.variance_factor, c->d_mean.p, c->d_thr.p);
     } else {
     c->paths[fseg_ctx::PATH_THR_PART] = 0;
     scan_counts(q, bsum_side, flag_pos_bits, &st->n_vals, nullptr);
     hipLaunchKernelGGL(k_scan_emit<kEmitValues>, dim3(scan_grid), dim3(256), 0, q, flag_pos_bits, NPOS,
-                       bsum_side, (const int *)nullptr, scan_state, &st->n_vals, (i64 *)nullptr, &st->err, c->d_y.as<double>(), c->d_v.as<double>(), K, c->d_pos_off.as<i64>(),
-                       c->d_iv_start.as<int>(), c->d_blk_iv0.as<int>(), (int *)nullptr, (int *)nullptr, (i64 *)nullptr,
+                       bsum_side, (const int *)nullptr, scan_state, &st->n_vals, (i64 *)nullptr, &st->err, c->d_y.p, c->d_v.p, K, c->d_pos_off.p,
+                       c->d_iv_start.p, c->d_blk_iv0.p, (int *)nullptr, (int *)nullptr, (i64 *)nullptr,
                        c->force_scan_stall ? 1 : 0, (int *)nullptr);
-    hipLaunchKernelGGL(k_voff, dim3(grid_for(n_part + 1, 1, 2048)), dim3(64), 0, q, n_part, c->d_part_iv_off.as<i64>(),
-                       c->d_pos_off.as<i64>(), NPOS, flag_pos_bits, bsum_side, scan_state, &st->n_vals,
-                       c->d_voff.as<i64>());
-    hipLaunchKernelGGL(k_vplan, dim3(1), dim3(256), 0, q, n_part, c->d_part_iv_off.as<i64>(), c->d_pos_off.as<i64>(), NPOS,
-                       c->d_voff.as<i64>(), c->d_chunk_off.as<i64>(), st, c->chunk_cap);
+    hipLaunchKernelGGL(k_voff, dim3(grid_for(n_part + 1, 1, 2048)), dim3(64), 0, q, n_part, c->d_part_iv_off.p,
+                       c->d_pos_off.p, NPOS, flag_pos_bits, bsum_side, scan_state, &st->n_vals,
+                       c->d_voff.p);
+    hipLaunchKernelGGL(k_vplan, dim3(1), dim3(256), 0, q, n_part, c->d_part_iv_off.p, c->d_pos_off.p, NPOS,
+                       c->d_voff.p, c->d_chunk_off.p, st, c->chunk_cap);
     int chunk_grid = grid_for(c->chunk_cap, 1, 4096);
-    double *csum0 = c->d_csum.as<double>(), *csum1 = csum0 + c->chunk_cap;
+    double *csum0 = c->d_csum.p, *csum1 = csum0 + c->chunk_cap;
     for (int pass = 0; pass < 2; ++pass)
-        hipLaunchKernelGGL(k_vsum_chunks, dim3(chunk_grid), dim3(512), 0, q, n_part, c->d_voff.as<i64>(),
-                           c->d_chunk_off.as<i64>(), c->d_v.as<double>(), csum0, pass, pass ? csum1 : csum0, c->chunk_cap);
-    hipLaunchKernelGGL(k_vsum_part, dim3(grid_for(n_part, 64, 1024)), dim3(64), 0, q, n_part, c->d_voff.as<i64>(),
-                       c->d_chunk_off.as<i64>(), csum0, csum1, c->P.variance_factor, c->d_mean.as<double>(),
-                       c->d_thr.as<double>(), c->chunk_cap);
+        hipLaunchKernelGGL(k_vsum_chunks, dim3(chunk_grid), dim3(512), 0, q, n_part, c->d_voff.p,
+                           c->d_chunk_off.p, c->d_v.p, csum0, pass, pass ? csum1 : csum0, c->chunk_cap);
+    hipLaunchKernelGGL(k_vsum_part, dim3(grid_for(n_part, 64, 1024)), dim3(64), 0, q, n_part, c->d_voff.p,
+                       c->d_chunk_off.p, csum0, csum1, c->P.variance_factor, c->d_mean.p,
+                       c->d_thr.p, c->chunk_cap);
     }
     if (stage_events && c->profile_all) (void)hipEventRecord(c->ev_e[ST_THRESHOLD], q);
     }
     begin(ST_CANDIDATES);
     // S3b candidates
-    hipLaunchKernelGGL(k_peaks_edges, dim3(grid_for(c->n_tiles, 256, 4096)), dim3(256), 0, s, c->n_tiles, c->d_tile_desc.as<TileDesc>(),
-                       c->d_tile_defer.as<int>(), c->d_y.as<double>(), flag_cand_bits, c->d_part_has2.as<int>(), n_part);
+    hipLaunchKernelGGL(k_peaks_edges, dim3(grid_for(c->n_tiles, 256, 4096)), dim3(256), 0, s, c->n_tiles, c->d_tile_desc.p,
+                       c->d_tile_defer.p, c->d_y.p, flag_cand_bits, c->d_part_has2.p, n_part);
     pos_counts(s, flag_cand_bits);
     hipLaunchKernelGGL(k_scan_emit<kEmitPositions>, dim3(pos_grid), dim3(256), 0, s, flag_cand_bits, NPOS,
-                       bsum, gsum, scan_state + scan_nb, &st->n_cand, c->d_cand_off.as<i64>() + K, &st->err, (const double *)nullptr, (double *)nullptr, K, c->d_pos_off.as<i64>(),
-                       c->d_iv_start.as<int>(), c->d_blk_iv0.as<int>(), c->d_cand_y.as<int>(), (int *)nullptr,
-                       c->d_cand_off.as<i64>(), 0, (int *)nullptr);
+                       bsum, gsum, scan_state + scan_nb, &st->n_cand, c->d_cand_off.p + K, &st->err, (const double *)nullptr, (double *)nullptr, K, c->d_pos_off.p,
+                       c->d_iv_start.p, c->d_blk_iv0.p, c->d_cand_y.p, (int *)nullptr,
+                       c->d_cand_off.p, 0, (int *)nullptr);
     end(ST_CANDIDATES);
     join(0);
     early_fork();
     begin(ST_FIX);
     // S4
     c->paths[fseg_ctx::PATH_IV_THREADS] = iv_threads;              // (k_segments, S6, is launched with the same block)
-    hipLaunchKernelGGL(k_fix, dim3(grid_for(K, 1, 8192)), dim3(iv_threads), 0, s, K, c->d_pos_off.as<i64>(),
-                       c->d_iv_part.as<int>(), c->d_cand_off.as<i64>(), c->d_cand_y.as<int>(), c->d_y.as<double>(),
-                       c->d_thr.as<double>(), c->P.max_problem_size, c->d_fixed0.as<unsigned char>(),
-                       c->d_added.as<unsigned char>(), c->d_fixed.as<unsigned char>(), c->d_chosen.as<unsigned char>(),
-                       c->d_cand_pn.as<int>(), c->d_seg_iv.as<int>(), st);
+    hipLaunchKernelGGL(k_fix, dim3(grid_for(K, 1, 8192)), dim3(iv_threads), 0, s, K, c->d_pos_off.p,
+                       c->d_iv_part.p, c->d_cand_off.p, c->d_cand_y.p, c->d_y.p,
+                       c->d_thr.p, c->P.max_problem_size, c->d_fixed0.p,
+                       c->d_added.p, c->d_fixed.p, c->d_chosen.p,
+                       c->d_cand_pn.p, c->d_seg_iv.p, st);
     // (with the block sums of the problem scan when the scan is a launch of its own: k_prob_scan1 is the rescan's only)
     i64 *range_bs = prob_bs;
-    hipLaunchKernelGGL(k_prob_range, dim3(pg), dim3(kRangeThreads), 0, s, st, c->d_cand_pn.as<int>(),
-                       c->d_seg_iv.as<int>(), c->d_cand_y.as<int>(), c->d_iv_part.as<int>(), c->d_iv_start.as<int>(),
-                       c->d_part_lane_off.as<i64>(), c->d_lane_start.as<int>(), c->d_lane_pmax.as<int>(),
-                       c->d_cand_ll.as<int>(), c->d_cand_ln.as<int>(), c->d_cand_wide.as<unsigned char>(), c->d_lane_lx.as<int2>(),
-                       c->d_lex.as<int2>(), c->wide_by_seen ? 1 : 0, split.fuse_lanes, range_bs, split);
+    hipLaunchKernelGGL(k_prob_range, dim3(pg), dim3(kRangeThreads), 0, s, st, c->d_cand_pn.p,
+                       c->d_seg_iv.p, c->d_cand_y.p, c->d_iv_part.p, c->d_iv_start.p,
+                       c->d_part_lane_off.p, c->d_lane_start.p, c->d_lane_pmax.p,
+                       c->d_cand_ll.p, c->d_cand_ln.p, c->d_cand_wide.p, c->d_lane_lx.p,
+                       c->d_lex.p, c->wide_by_seen ? 1 : 0, split.fuse_lanes, range_bs, split);
     if (prob_bs) {
         if (!range_bs)
-            hipLaunchKernelGGL(k_prob_scan1, dim3(pg), dim3(256), 0, s, st, c->d_cand_pn.as<int>(), c->d_cand_ln.as<int>(), c->d_cand_wide.as<unsigned char>(), prob_bs, split);
+            hipLaunchKernelGGL(k_prob_scan1, dim3(pg), dim3(256), 0, s, st, c->d_cand_pn.p, c->d_cand_ln.p, c->d_cand_wide.p, prob_bs, split);
         hipLaunchKernelGGL(k_prob_scan2, dim3(1), dim3(256), 0, s, st, prob_bs);
     }
     end(ST_FIX);
@@ -707,12 +729,12 @@ int enqueue_run(fseg_ctx *c, unsigned segs, bool sized = false, i64 label_fill_b
     if (do_pre2) {
     if (!do_pre1) early_fork();
     begin(ST_SCORE_PREP);
-    hipLaunchKernelGGL(k_prob_emit, dim3(pg), dim3(256), 0, s, st, c->d_cand_pn.as<int>(), c->d_cand_ll.as<int>(),
-                       c->d_cand_ln.as<int>(), c->d_seg_iv.as<int>(), c->d_cand_off.as<i64>(), prob_bs,
-                       pr, c->prob_cap, c->d_work_pc.as<int2>(), c->d_cls_items.as<int4>(),
-                       c->work_cap, c->d_dp_items.as<int>(), c->d_prob_desc.as<ProbDesc>(), c->d_iv_start.as<int>(),
-                       c->d_iv_part.as<int>(), c->d_part_lane_off.as<i64>(), split, c->d_solve_items.as<int>(), c->d_solve_desc.as<ProbDesc>(),
-                       c->d_wide_items.as<int>(), c->d_wide_all.as<int>(), c->d_cand_wide.as<unsigned char>(),
+    hipLaunchKernelGGL(k_prob_emit, dim3(pg), dim3(256), 0, s, st, c->d_cand_pn.p, c->d_cand_ll.p,
+                       c->d_cand_ln.p, c->d_seg_iv.p, c->d_cand_off.p, prob_bs,
+                       pr, c->prob_cap, c->d_work_pc.p, c->d_cls_items.p,
+                       c->work_cap, c->d_dp_items.p, c->d_prob_desc.p, c->d_iv_start.p,
+                       c->d_iv_part.p, c->d_part_lane_off.p, split, c->d_solve_items.p, c->d_solve_desc.p,
+                       c->d_wide_items.p, c->d_wide_all.p, c->d_cand_wide.p,
                        dev_sync ? sw : (SyncWords *)nullptr, sync_gen);
     launch_fork_waiters();
     // S5.  The arena path's window coverage (and pair thresholds) are launches of their own in front of k_score: they are
@@ -724,17 +746,17 @@ int enqueue_run(fseg_ctx *c, unsigned segs, bool sized = false, i64 label_fill_b
         const int pt_blocks = c->small_batch ? grid_for(c->prob_cap, 1, 512) : 0;       // fused only for small batches
         if (!pt_blocks)
             hipLaunchKernelGGL(k_pair_thresholds, dim3(grid_for(c->prob_cap, 1, 2048)), dim3(256), 0, s, st, pr,
-                               c->d_prob_desc.as<ProbDesc>(), c->prob_cap, c->d_cand_off.as<i64>(), c->d_cand_y.as<int>(),
-                               c->d_h_table.as<double>(), c->P.h_len,
-                               c->P.threshold_rate, c->d_pair_thr.as<int2>(), c->pair_cap, c->d_amb.as<unsigned>(),
-                               c->d_out.as<unsigned>(), c->tri_cap);
+                               c->d_prob_desc.p, c->prob_cap, c->d_cand_off.p, c->d_cand_y.p,
+                               c->d_h_table.p, c->P.h_len,
+                               c->P.threshold_rate, c->d_pair_thr.p, c->pair_cap, c->d_amb.p,
+                               c->d_out.p, c->tri_cap);
         hipLaunchKernelGGL(k_cov, dim3(cov_blocks + pt_blocks), dim3(kLaneChunk), 0, s, st,
-                           c->d_prob_desc.as<ProbDesc>(), c->prob_cap, c->d_work_pc.as<int2>(), c->work_cap, c->d_cand_off.as<i64>(),
-                           c->d_cand_y.as<int>(), c->d_iv_start.as<int>(), c->d_lane_lx.as<int2>(),
-                           c->d_lex.as<int2>(),
-                           c->d_cov.as<unsigned>(), c->cov_cap, c->d_work_active.as<unsigned char>(),
-                           cov_blocks, pr, c->d_h_table.as<double>(), c->P.h_len, c->P.threshold_rate, c->d_pair_thr.as<int2>(),
-                           c->pair_cap, c->d_amb.as<unsigned>(), c->d_out.as<unsigned>(), c->tri_cap);
+                           c->d_prob_desc.p, c->prob_cap, c->d_work_pc.p, c->work_cap, c->d_cand_off.p,
+                           c->d_cand_y.p, c->d_iv_start.p, c->d_lane_lx.p,
+                           c->d_lex.p,
+                           c->d_cov.p, c->cov_cap, c->d_work_active.p,
+                           cov_blocks, pr, c->d_h_table.p, c->P.h_len, c->P.threshold_rate, c->d_pair_thr.p,
+                           c->pair_cap, c->d_amb.p, c->d_out.p, c->tri_cap);
     }
     if (!score_begun) end(ST_SCORE_PREP);
     }   // do_pre2
@@ -766,7 +788,7 @@ int enqueue_run(fseg_ctx *c, unsigned segs, bool sized = false, i64 label_fill_b
         const bool sfork = any_arena;                               // (the arena path's work-item kernels keep their streams)
         hipStream_t qt = (tiny_max > 0 && sfork) ? fork(2) : s;     // (forked here: a side stream continues from where it was forked)
 #ifdef FSEG_SCORE_TIMING
-#define FSEG_TARG , c->d_tacc.as<unsigned long long>()
+#define FSEG_TARG , c->d_tacc.p
 #else
 #define FSEG_TARG
 #endif
@@ -783,21 +805,21 @@ int enqueue_run(fseg_ctx *c, unsigned segs, bool sized = false, i64 label_fill_b
         do { note_score(CLS);                                                                                                  \
         hipLaunchKernelGGL(k_score<NMV>, dim3(work_grid < (MAXWG) ? work_grid : (MAXWG)), dim3(ScoreCfg<NMV>::kThreads),  \
                            score_lds_for((NMV) == kNMax ? c->nm_big : (NMV), (NMV) + 1), Q, st, CLS,                                 \
-                           ((NMV) == kNMax ? c->nm_big : (NMV)), pr, c->prob_cap, c->d_cls_items.as<int4>(),              \
-                           c->d_prob_desc.as<ProbDesc>(), c->work_cap, c->d_cand_off.as<i64>(),                         \
-                           c->d_cand_y.as<int>(), c->d_work_active.as<unsigned char>(), c->d_cov.as<unsigned>(),        \
-                           c->cov_cap, c->d_pair_thr.as<int2>(), c->pair_cap, c->d_out.as<unsigned>(), c->tri_cap,      \
-                           c->d_amb.as<unsigned>() FSEG_TARG); } while (0)
+                           ((NMV) == kNMax ? c->nm_big : (NMV)), pr, c->prob_cap, c->d_cls_items.p,              \
+                           c->d_prob_desc.p, c->work_cap, c->d_cand_off.p,                         \
+                           c->d_cand_y.p, c->d_work_active.p, c->d_cov.p,        \
+                           c->cov_cap, c->d_pair_thr.p, c->pair_cap, c->d_out.p, c->tri_cap,      \
+                           c->d_amb.p FSEG_TARG); } while (0)
         // (a 16-bit-counter instance of a sized batch goes over its class's WIDE problems only: wide_n of them, through wide_items)
         auto wide_n = [&](int cls, size_t cnt_bytes) -> i64 { return (known && cls >= 0 && cls < 3 && cnt_bytes == 2) ? c->n_wide[cls] : -1; };
 #define FSEG_SOLVE_N(CNT, CLS, N_ITEMS) (wide_n(CLS, sizeof(CNT)) >= 0 ? wide_n(CLS, sizeof(CNT)) : (i64)(N_ITEMS))
-#define FSEG_SOLVE_WIDE(CNT, CLS) (wide_n(CLS, sizeof(CNT)) >= 0 ? c->d_wide_items.as<int>() : (const int *)nullptr)
+#define FSEG_SOLVE_WIDE(CNT, CLS) (wide_n(CLS, sizeof(CNT)) >= 0 ? c->d_wide_items.p : (const int *)nullptr)
 #define FSEG_SOLVE_ARGS(NMV, CNT, CLS)                                                                                      \
                                st, CLS, ((NMV) == kNMax ? c->nm_big : (NMV)), list_lb(CLS),                                    \
-                               (wide_n(CLS, sizeof(CNT)) >= 0 ? wide_n(CLS, sizeof(CNT)) : list_ln(CLS)), pr, c->d_solve_desc.as<ProbDesc>(), \
-                               c->prob_cap, c->d_cand_y.as<int>(), c->d_lane_lx.as<int2>(), c->d_lex.as<int2>(),               \
-                               c->d_h_table.as<double>(), c->P.h_len, c->P.threshold_rate,               \
-                               c->d_thr_tab.as<int2>(), c->P.min_read_support_outside, c->d_chosen.as<unsigned char>()
+                               (wide_n(CLS, sizeof(CNT)) >= 0 ? wide_n(CLS, sizeof(CNT)) : list_ln(CLS)), pr, c->d_solve_desc.p, \
+                               c->prob_cap, c->d_cand_y.p, c->d_lane_lx.p, c->d_lex.p,               \
+                               c->d_h_table.p, c->P.h_len, c->P.threshold_rate,               \
+                               c->d_thr_tab.p, c->P.min_read_support_outside, c->d_chosen.p
         // the split path (k_solve<.., SPLIT> then k_dpw on the same stream) for a list that fits the hand-over arena as laid out.
         // (Until round 5 only where the context has the device to itself: host memory -> host memory, eight contexts, the two were
         // within the noise -- 383 against 388 M reads/s; over resident batches the split is 1.8 % faster; FSEG_SPLIT_ALWAYS=0.)
@@ -816,22 +838,22 @@ int enqueue_run(fseg_ctx *c, unsigned segs, bool sized = false, i64 label_fill_b
 #define FSEG_LAUNCH_WIDE_ALL(Q, VT)                                                                                          \
             do { note_solve(-1, 2);                                                                                                \
             hipLaunchKernelGGL((k_solve<kNMax, unsigned short, VT, false>), dim3((unsigned)n_wide_all), dim3(SolveCfg<kNMax>::kThreads), \
-                               solve_lds_for(c->nm_big, kNMax + 1, 2), Q, st, -1, c->nm_big, (i64)0, n_wide_all, pr, c->d_solve_desc.as<ProbDesc>(), \
-                               c->prob_cap, c->d_cand_y.as<int>(), c->d_lane_lx.as<int2>(), c->d_lex.as<int2>(),               \
-                               c->d_h_table.as<double>(), c->P.h_len, c->P.threshold_rate,               \
-                               c->d_thr_tab.as<int2>(), c->P.min_read_support_outside, c->d_chosen.as<unsigned char>(),       \
-                               (unsigned char *)nullptr, (i64)0, c->d_wide_all.as<int>() FSEG_TARG); } while (0)
+                               solve_lds_for(c->nm_big, kNMax + 1, 2), Q, st, -1, c->nm_big, (i64)0, n_wide_all, pr, c->d_solve_desc.p, \
+                               c->prob_cap, c->d_cand_y.p, c->d_lane_lx.p, c->d_lex.p,               \
+                               c->d_h_table.p, c->P.h_len, c->P.threshold_rate,               \
+                               c->d_thr_tab.p, c->P.min_read_support_outside, c->d_chosen.p,       \
+                               (unsigned char *)nullptr, (i64)0, c->d_wide_all.p FSEG_TARG); } while (0)
 #define FSEG_LAUNCH_DPW(Q, NMV, CNT, VT, CLS, N_ITEMS, TT)                                                                   \
             do { census[fseg_ctx::PATH_DPW] |= (1 << ((CLS) < 0 ? 0 : (CLS))) | ((TT) == 512 ? 8 : 0);                                 \
             hipLaunchKernelGGL((k_dpw<NMV, CNT, VT, TT>), dim3(grid_for(FSEG_SOLVE_N(CNT, CLS, N_ITEMS), 1, (int)kSplitGridCap)), dim3(TT),      \
                                dpw_lds_for(nm_rt, (int)sizeof(VT), (int)sizeof(CNT)), Q, st, nm_rt, list_lb(CLS),                \
                                FSEG_SOLVE_N(CNT, CLS, list_ln(CLS)), pr,                                                        \
-                               c->d_solve_desc.as<ProbDesc>(), dpx0, dstride, \
-                               c->P.min_read_support_outside, c->d_chosen.as<unsigned char>(), FSEG_SOLVE_WIDE(CNT, CLS) FSEG_TARG); } while (0)
+                               c->d_solve_desc.p, dpx0, dstride, \
+                               c->P.min_read_support_outside, c->d_chosen.p, FSEG_SOLVE_WIDE(CNT, CLS) FSEG_TARG); } while (0)
         // the split path, one instance: k_solve<.., SPLIT> (set-up and rounds) then k_dpw (the DPs) on the same stream
 #define FSEG_LAUNCH_SPLIT(Q, NMV, CNT, VT, CLS, N_ITEMS)                                                                     \
         do { const int nm_rt = (NMV) == kNMax ? c->nm_big : (NMV);                                                            \
-            unsigned char *dpx0 = c->d_dpx.as<unsigned char>() + c->dpx_base[(CLS) < 0 ? 0 : (CLS)];                                           \
+            unsigned char *dpx0 = c->d_dpx.p + c->dpx_base[(CLS) < 0 ? 0 : (CLS)];                                           \
             const i64 dstride = c->dpx_stride[(CLS) < 0 ? 0 : (CLS)];                                                                       \
             note_solve(CLS, sizeof(CNT));                                                                                     \
             hipLaunchKernelGGL((k_solve<NMV, CNT, int, true>), dim3(grid_for(FSEG_SOLVE_N(CNT, CLS, N_ITEMS), 1, (int)kSplitGridCap)), dim3(SolveCfg<NMV>::kThreads), \
@@ -862,9 +884,9 @@ int enqueue_run(fseg_ctx *c, unsigned segs, bool sized = false, i64 label_fill_b
 #define FSEG_LAUNCH_WAVE_V(Q, NMV, VT, LIST, N_ITEMS)                                                                        \
             do { note_tiny(1);                                                                                                     \
             hipLaunchKernelGGL((k_wave<NMV, VT>), dim3(grid_for((N_ITEMS), 4, FSEG_WG_TINY)), dim3(256), 0, Q, st,           \
-                               c->d_solve_desc.as<ProbDesc>(), c->prob_cap, LIST, pr, c->d_cand_y.as<int>(), c->d_lane_lx.as<int2>(), \
-                               c->d_lex.as<int2>(), c->d_h_table.as<double>(), c->P.h_len, c->P.threshold_rate,               \
-                               c->d_thr_tab.as<int2>(), c->P.min_read_support_outside, c->d_chosen.as<unsigned char>(),        \
+                               c->d_solve_desc.p, c->prob_cap, LIST, pr, c->d_cand_y.p, c->d_lane_lx.p, \
+                               c->d_lex.p, c->d_h_table.p, c->P.h_len, c->P.threshold_rate,               \
+                               c->d_thr_tab.p, c->P.min_read_support_outside, c->d_chosen.p,        \
                                list_lb(LIST), list_ln(LIST) FSEG_TARG); } while (0)
 #define FSEG_LAUNCH_WAVE(Q, NMV, LIST, N_ITEMS)                                                                              \
             do { if (key32) { FSEG_LAUNCH_WAVE_V(Q, NMV, int, LIST, N_ITEMS); }                              \
@@ -1005,26 +1027,26 @@ int enqueue_run(fseg_ctx *c, unsigned segs, bool sized = false, i64 label_fill_b
             // stage's time bracket covers all scoring work
             if (wave) FSEG_LAUNCH_WAVE(qt, kTiny, 3, known ? c->n_tiny : c->prob_cap);
             else { note_tiny(2);
-            hipLaunchKernelGGL(k_tiny, dim3(grid_for(known ? c->n_tiny : c->prob_cap, 4, FSEG_WG_TINY)), dim3(256), 0, qt, st, c->d_solve_desc.as<ProbDesc>(),
-                               c->prob_cap, tiny_max, pr, c->d_cand_y.as<int>(), c->d_lane_ex.as<longlong2>(),
-                               c->d_ex_ts.as<int>(), c->d_ex_te.as<int>(), c->d_h_table.as<double>(), c->P.h_len, c->P.threshold_rate,
-                               c->d_thr_tab.as<int2>(), c->P.min_read_support_outside, c->d_chosen.as<unsigned char>(), list_lb(3), list_ln(3) FSEG_TARG); }
+            hipLaunchKernelGGL(k_tiny, dim3(grid_for(known ? c->n_tiny : c->prob_cap, 4, FSEG_WG_TINY)), dim3(256), 0, qt, st, c->d_solve_desc.p,
+                               c->prob_cap, tiny_max, pr, c->d_cand_y.p, c->d_lane_ex.p,
+                               c->d_ex_ts.p, c->d_ex_te.p, c->d_h_table.p, c->P.h_len, c->P.threshold_rate,
+                               c->d_thr_tab.p, c->P.min_read_support_outside, c->d_chosen.p, list_lb(3), list_ln(3) FSEG_TARG); }
         }
 #undef FSEG_LAUNCH_WAVE
 #undef FSEG_LAUNCH_WAVE_V
         if (!c->small_batch && sfork) { join(0); join(1); }
         if (c->have_huge && any_arena) census[fseg_ctx::PATH_SCORE] |= 16;
         if (c->have_huge && any_arena)
-            hipLaunchKernelGGL(k_score_huge, dim3(256), dim3(512), kHugeScoreLds, s, st, c->d_dp_items.as<int>(), pr,
-                               c->d_prob_desc.as<ProbDesc>(), c->prob_cap, c->work_cap, c->d_cand_y.as<int>(),
-                               c->d_cov.as<unsigned>(), c->cov_cap, c->d_pair_thr.as<int2>(), c->pair_cap,
-                               c->d_out.as<unsigned>(), c->tri_cap, c->d_amb.as<unsigned>());
+            hipLaunchKernelGGL(k_score_huge, dim3(256), dim3(512), kHugeScoreLds, s, st, c->d_dp_items.p, pr,
+                               c->d_prob_desc.p, c->prob_cap, c->work_cap, c->d_cand_y.p,
+                               c->d_cov.p, c->cov_cap, c->d_pair_thr.p, c->pair_cap,
+                               c->d_out.p, c->tri_cap, c->d_amb.p);
         if (c->have_huge && c->nm_giant > 0 && any_arena && c->d_giant.p) census[fseg_ctx::PATH_SCORE] |= 32;
         if (c->have_huge && c->nm_giant > 0 && any_arena && c->d_giant.p)
-            hipLaunchKernelGGL(k_score_giant, dim3(kGiantWgs), dim3(512), giant_score_lds(c->nm_giant), s, st, c->d_dp_items.as<int>(), pr,
-                               c->d_prob_desc.as<ProbDesc>(), c->prob_cap, c->work_cap, c->d_cand_y.as<int>(),
-                               c->d_cov.as<unsigned>(), c->cov_cap, c->d_pair_thr.as<int2>(), c->pair_cap,
-                               c->d_out.as<unsigned>(), c->tri_cap, c->d_amb.as<unsigned>(), c->nm_giant,
+            hipLaunchKernelGGL(k_score_giant, dim3(kGiantWgs), dim3(512), giant_score_lds(c->nm_giant), s, st, c->d_dp_items.p, pr,
+                               c->d_prob_desc.p, c->prob_cap, c->work_cap, c->d_cand_y.p,
+                               c->d_cov.p, c->cov_cap, c->d_pair_thr.p, c->pair_cap,
+                               c->d_out.p, c->tri_cap, c->d_amb.p, c->nm_giant,
                                c->d_giant.as<unsigned char>(), (i64)giant_scratch_bytes(c->nm_giant));
         if (tiny_max > 0 && sfork) join(2);    // k_tiny is interval scoring too: inside the stage's time bracket
     }
@@ -1044,25 +1066,25 @@ int enqueue_run(fseg_ctx *c, unsigned segs, bool sized = false, i64 label_fill_b
         const int fill_blocks = ride_fill ? grid_for(labels_n16 / 8 + 1, 512, 512) : 0;
 #define FSEG_LAUNCH_DP(NMV, TV, OUTT, NM_RT, DPCLASS, MAXWG)                                                             \
         hipLaunchKernelGGL((k_dp<NMV, TV, OUTT>), dim3((dp_grid < (MAXWG) ? dp_grid : (MAXWG)) + fill_blocks), dim3(TV),     \
-                           dp_lds_for(NM_RT, (int)sizeof(OUTT)), ((NMV) == kDpSmall ? q_small : s), st, DPCLASS, NM_RT, c->d_dp_items.as<int>(), pr,          \
-                           c->d_prob_desc.as<ProbDesc>(), c->prob_cap, c->d_cand_off.as<i64>(), c->d_cand_y.as<int>(), c->d_iv_part.as<int>(),               \
-                           c->d_part_lane_off.as<i64>(), c->d_out.as<unsigned>(), c->tri_cap, c->d_amb.as<unsigned>(),        \
-                           c->d_pair_thr.as<int2>(), c->pair_cap, c->P.min_read_support_outside,                              \
-                           c->d_chosen.as<unsigned char>(), tiny_max, (dp_grid < (MAXWG) ? dp_grid : (MAXWG)),                \
+                           dp_lds_for(NM_RT, (int)sizeof(OUTT)), ((NMV) == kDpSmall ? q_small : s), st, DPCLASS, NM_RT, c->d_dp_items.p, pr,          \
+                           c->d_prob_desc.p, c->prob_cap, c->d_cand_off.p, c->d_cand_y.p, c->d_iv_part.p,               \
+                           c->d_part_lane_off.p, c->d_out.p, c->tri_cap, c->d_amb.p,        \
+                           c->d_pair_thr.p, c->pair_cap, c->P.min_read_support_outside,                              \
+                           c->d_chosen.p, tiny_max, (dp_grid < (MAXWG) ? dp_grid : (MAXWG)),                \
                            c->d_labels.as<uint4>(), labels_n16 FSEG_TARG)
 #define FSEG_LAUNCH_DP_WAVES(OUTT)                                                                                        \
         hipLaunchKernelGGL((k_dp_waves<OUTT>), dim3(grid_for(c->prob_cap, 4, 2048)), dim3(256),                                \
                            dp_lds_for(kDpSmall, (int)sizeof(OUTT)) > 4 * dp_wave_bytes<OUTT>() ? dp_lds_for(kDpSmall, (int)sizeof(OUTT)) : 4 * dp_wave_bytes<OUTT>(), \
-                           q_small, st, c->d_dp_items.as<int>(), pr, c->d_prob_desc.as<ProbDesc>(), c->prob_cap,                \
-                           c->d_cand_y.as<int>(), c->d_out.as<unsigned>(), c->tri_cap, c->d_amb.as<unsigned>(),                \
-                           c->d_pair_thr.as<int2>(), c->pair_cap, c->P.min_read_support_outside, c->d_chosen.as<unsigned char>(), 0); \
+                           q_small, st, c->d_dp_items.p, pr, c->d_prob_desc.p, c->prob_cap,                \
+                           c->d_cand_y.p, c->d_out.p, c->tri_cap, c->d_amb.p,                \
+                           c->d_pair_thr.p, c->pair_cap, c->P.min_read_support_outside, c->d_chosen.p, 0); \
         /* the problems of the list with 17 .. 32 candidates: one workgroup each, so that none waits behind another */      \
         hipLaunchKernelGGL((k_dp<kDpSmall, 256, OUTT>), dim3(grid_for(c->prob_cap, 1, 8192)), dim3(256),                       \
-                           dp_lds_for(kDpSmall, (int)sizeof(OUTT)), q_mid, st, 0, kDpSmall, c->d_dp_items.as<int>(), pr,       \
-                           c->d_prob_desc.as<ProbDesc>(), c->prob_cap, c->d_cand_off.as<i64>(), c->d_cand_y.as<int>(), c->d_iv_part.as<int>(), \
-                           c->d_part_lane_off.as<i64>(), c->d_out.as<unsigned>(), c->tri_cap, c->d_amb.as<unsigned>(),        \
-                           c->d_pair_thr.as<int2>(), c->pair_cap, c->P.min_read_support_outside,                              \
-                           c->d_chosen.as<unsigned char>(), kDpWave, grid_for(c->prob_cap, 1, 8192), (uint4 *)nullptr, (i64)0 FSEG_TARG)
+                           dp_lds_for(kDpSmall, (int)sizeof(OUTT)), q_mid, st, 0, kDpSmall, c->d_dp_items.p, pr,       \
+                           c->d_prob_desc.p, c->prob_cap, c->d_cand_off.p, c->d_cand_y.p, c->d_iv_part.p, \
+                           c->d_part_lane_off.p, c->d_out.p, c->tri_cap, c->d_amb.p,        \
+                           c->d_pair_thr.p, c->pair_cap, c->P.min_read_support_outside,                              \
+                           c->d_chosen.p, kDpWave, grid_for(c->prob_cap, 1, 8192), (uint4 *)nullptr, (i64)0 FSEG_TARG)
         // 16-bit count tables unless some problem sees >= 65536 reads;
         // 512 threads (8 waves share the c2 loop) when the tables of the largest problem leave room for their scratch.
         // small_batch: one launch over every problem; otherwise one launch per DP class list.
@@ -1081,43 +1103,43 @@ int enqueue_run(fseg_ctx *c, unsigned segs, bool sized = false, i64 label_fill_b
 #undef FSEG_LAUNCH_DP_WAVES
         if (!c->small_batch) { join(0); join(1); }
         if (c->have_huge)
-            hipLaunchKernelGGL(k_dp_huge, dim3(dp_grid < 256 ? dp_grid : 256), dim3(512), kHugeDpLds, s, st, c->d_dp_items.as<int>(),
-                               pr, c->d_prob_desc.as<ProbDesc>(), c->prob_cap, c->d_cand_y.as<int>(), c->d_out.as<unsigned>(),
-                               c->tri_cap, c->d_amb.as<unsigned>(), c->d_pair_thr.as<int2>(), c->pair_cap,
-                               c->P.min_read_support_outside, c->d_chosen.as<unsigned char>());
+            hipLaunchKernelGGL(k_dp_huge, dim3(dp_grid < 256 ? dp_grid : 256), dim3(512), kHugeDpLds, s, st, c->d_dp_items.p,
+                               pr, c->d_prob_desc.p, c->prob_cap, c->d_cand_y.p, c->d_out.p,
+                               c->tri_cap, c->d_amb.p, c->d_pair_thr.p, c->pair_cap,
+                               c->P.min_read_support_outside, c->d_chosen.p);
         if (c->have_huge && c->nm_giant > 0 && c->d_giant.p)
-            hipLaunchKernelGGL(k_dp_giant, dim3(kGiantWgs), dim3(512), giant_dp_lds(c->nm_giant), s, st, c->d_dp_items.as<int>(),
-                               pr, c->d_prob_desc.as<ProbDesc>(), c->prob_cap, c->d_cand_y.as<int>(), c->d_out.as<unsigned>(),
-                               c->tri_cap, c->d_amb.as<unsigned>(), c->d_pair_thr.as<int2>(), c->pair_cap,
-                               c->P.min_read_support_outside, c->d_chosen.as<unsigned char>(), c->nm_giant,
+            hipLaunchKernelGGL(k_dp_giant, dim3(kGiantWgs), dim3(512), giant_dp_lds(c->nm_giant), s, st, c->d_dp_items.p,
+                               pr, c->d_prob_desc.p, c->prob_cap, c->d_cand_y.p, c->d_out.p,
+                               c->tri_cap, c->d_amb.p, c->d_pair_thr.p, c->pair_cap,
+                               c->P.min_read_support_outside, c->d_chosen.p, c->nm_giant,
                                c->d_giant.as<unsigned char>(), (i64)giant_scratch_bytes(c->nm_giant));
     }
     end(ST_DP); begin(ST_REFINE);
     // S6 (the histogram as S1 left it: uint16 where it ran packed)
 #define FSEG_LAUNCH_REFINE(COUNT)                                                                                      \
-    hipLaunchKernelGGL(k_segments<COUNT>, dim3(grid_for(K, 1, 8192)), dim3(iv_threads), 0, s, K, c->d_pos_off.as<i64>(),                       \
-                       c->d_cand_off.as<i64>(), c->d_cand_y.as<int>(), c->d_y_raw.as<COUNT>(), c->d_blk_pre.as<int>(), c->d_tile_tot.as<int>(), c->d_iv_tile0.as<int>(), \
-                       c->d_chosen.as<unsigned char>(), flag_final_bits, c->d_rseg_c.as<int>(),                        \
-                       c->d_seg_prev.as<int>(), st);                                                                   \
-    hipLaunchKernelGGL(k_refine<COUNT>, dim3(2048), dim3(64), 0, s, st, c->d_seg_iv.as<int>(), c->d_rseg_c.as<int>(), \
-                       c->d_seg_prev.as<int>(), c->d_cand_y.as<int>(), c->d_pos_off.as<i64>(), c->d_y_raw.as<COUNT>(), \
-                       c->d_w_refine.as<double>(), c->P.radius_refine, c->P.sigma, c->d_g.as<double>(), c->d_pk.as<int>(), \
-                       c->d_pf.as<unsigned char>(), c->d_kp.as<unsigned char>(), flag_final_bits)
+    hipLaunchKernelGGL(k_segments<COUNT>, dim3(grid_for(K, 1, 8192)), dim3(iv_threads), 0, s, K, c->d_pos_off.p,                       \
+                       c->d_cand_off.p, c->d_cand_y.p, c->d_y_raw.as<COUNT>(), c->d_blk_pre.p, c->d_tile_tot.p, c->d_iv_tile0.p, \
+                       c->d_chosen.p, flag_final_bits, c->d_rseg_c.p,                        \
+                       c->d_seg_prev.p, st);                                                                   \
+    hipLaunchKernelGGL(k_refine<COUNT>, dim3(2048), dim3(64), 0, s, st, c->d_seg_iv.p, c->d_rseg_c.p, \
+                       c->d_seg_prev.p, c->d_cand_y.p, c->d_pos_off.p, c->d_y_raw.as<COUNT>(), \
+                       c->d_w_refine.p, c->P.radius_refine, c->P.sigma, c->d_g.p, c->d_pk.p, \
+                       c->d_pf.p, c->d_kp.p, flag_final_bits)
     if (c->yraw_narrow) { FSEG_LAUNCH_REFINE(uint16_t); }
     else { FSEG_LAUNCH_REFINE(int); }
 #undef FSEG_LAUNCH_REFINE
     end(ST_REFINE); begin(ST_FINAL);
     pos_counts(s, flag_final_bits);
     hipLaunchKernelGGL(k_scan_emit<kEmitPositions>, dim3(pos_grid), dim3(256), 0, s, flag_final_bits,
-                       NPOS, bsum, gsum, scan_state + 2 * scan_nb, &st->n_final, c->d_final_off.as<i64>() + K, &st->err, (const double *)nullptr, (double *)nullptr, K, c->d_pos_off.as<i64>(),
-                       c->d_iv_start.as<int>(), c->d_blk_iv0.as<int>(), c->d_final_y.as<int>(), c->d_final_pos.as<int>(),
-                       c->d_final_off.as<i64>(), 0, c->d_final_iv.as<int>());
+                       NPOS, bsum, gsum, scan_state + 2 * scan_nb, &st->n_final, c->d_final_off.p + K, &st->err, (const double *)nullptr, (double *)nullptr, K, c->d_pos_off.p,
+                       c->d_iv_start.p, c->d_blk_iv0.p, c->d_final_y.p, c->d_final_pos.p,
+                       c->d_final_off.p, 0, c->d_final_iv.p);
     // S7, first half: per-column thresholds and the label arena's plan
-    hipLaunchKernelGGL(k_label_cols, dim3(grid_for(NPOS / 8 + 1, 256, 2048)), dim3(256), 0, s, K, c->d_final_off.as<i64>(),
-                       c->d_final_y.as<int>(), c->d_final_iv.as<int>(), c->d_iv_part.as<int>(), c->d_h_table.as<double>(), c->P.h_len,
-                       c->P.threshold_rate, c->d_thr_tab.as<int2>(), c->d_col_thr.as<int2>(), c->d_col_zero.as<unsigned char>(),
-                       c->d_part_has2.as<int>(), n_part, c->d_part_iv_off.as<i64>(), c->d_part_rep_off.as<i64>(),
-                       c->d_label_off.as<i64>(), st, c->label_cap);
+    hipLaunchKernelGGL(k_label_cols, dim3(grid_for(NPOS / 8 + 1, 256, 2048)), dim3(256), 0, s, K, c->d_final_off.p,
+                       c->d_final_y.p, c->d_final_iv.p, c->d_iv_part.p, c->d_h_table.p, c->P.h_len,
+                       c->P.threshold_rate, c->d_thr_tab.p, c->d_col_thr.p, c->d_col_zero.p,
+                       c->d_part_has2.p, n_part, c->d_part_iv_off.p, c->d_part_rep_off.p,
+                       c->d_label_off.p, st, c->label_cap);
     end(ST_FINAL);
     }   // do_post1
     if (do_post2) {
@@ -1128,22 +1150,22 @@ int enqueue_run(fseg_ctx *c, unsigned segs, bool sized = false, i64 label_fill_b
         if (lab_packed) {
             const i64 n16 = sized ? (label_fill_bytes + 15) / 16 : labels_n16;
             if (n16 > 0)                                            // (one launch: a hipMemsetAsync of 19 MB is two fill kernels here)
-                hipLaunchKernelGGL(k_clear, dim3(grid_for(n16 / 4 + 1, 256, 4096)), dim3(256), 0, s, (Status *)nullptr, c->d_packed.as<unsigned>(), n16);
+                hipLaunchKernelGGL(k_clear, dim3(grid_for(n16 / 4 + 1, 256, 4096)), dim3(256), 0, s, (Status *)nullptr, c->d_packed.p, n16);
         } else if (!ride_fill) {                                    // no DP launch carried the fill
             const i64 n16 = sized ? (label_fill_bytes + 15) / 16 : labels_n16;
             if (n16 > 0)
                 hipLaunchKernelGGL(k_label_zero, dim3(grid_for(n16 / 8 + 1, 256, 4096)), dim3(256), 0, s, c->d_labels.as<uint4>(), n16);
         }
         hipLaunchKernelGGL(k_label_reads, dim3(grid_for((i64)c->n_rep_blocks * kLabelSplit, 1, 65536)), dim3(256), 0, s, c->n_rep_blocks,
-                           c->d_rb_part.as<int>(), c->d_rb_r0.as<int>(), c->d_label_off.as<i64>(), c->label_cap, n_part,
-                           c->d_part_iv_off.as<i64>(), c->d_part_rep_off.as<i64>(), c->d_final_off.as<i64>(),
-                           c->d_final_pos.as<int>(), c->d_col_thr.as<int2>(), c->d_rep_exon_off.as<i64>(),
-                           c->d_ex_ts.as<int>(), c->d_ex_te.as<int>(), c->d_col_zero.as<unsigned char>(),
-                           c->d_part_has2.as<int>(), c->d_labels.as<unsigned char>(), lab_packed ? c->d_packed.as<unsigned>() : (unsigned *)nullptr);
+                           c->d_rb_part.p, c->d_rb_r0.p, c->d_label_off.p, c->label_cap, n_part,
+                           c->d_part_iv_off.p, c->d_part_rep_off.p, c->d_final_off.p,
+                           c->d_final_pos.p, c->d_col_thr.p, c->d_rep_exon_off.p,
+                           c->d_ex_ts.p, c->d_ex_te.p, c->d_col_zero.p,
+                           c->d_part_has2.p, c->d_labels.as<unsigned char>(), lab_packed ? c->d_packed.p : (unsigned *)nullptr);
     }
     end(ST_LABEL);
     }   // do_post2
-    if (segs & SEG_STATUS) HIP_TRY(c, hipMemcpyAsync(c->h_status, st, sizeof(Status), hipMemcpyDeviceToHost, s));
+    if (segs & SEG_STATUS) HIP_TRY(c, hipMemcpyAsync(c->h_status.p, st, sizeof(Status), hipMemcpyDeviceToHost, s));
     HIP_TRY(c, fj_err);
     HIP_TRY(c, hipGetLastError());
     return FSEG_OK;
@@ -1350,7 +1372,7 @@ static int finish_run_impl(fseg_ctx *c) {
 int probe_side_queues(fseg_ctx *c) {
     if (c->side_probed || !c->side[0] || !c->d_sync.p) return FSEG_OK;
     c->side_probed = true;
-    SyncWords *sw = c->d_sync.as<SyncWords>();
+    SyncWords *sw = c->d_sync.p;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     for (int k = 0; k < fseg_ctx::kSide; ++k) {
         const unsigned gen = ++c->probe_gen;
@@ -1393,19 +1415,19 @@ int run_sized(fseg_ctx *c) {
                 const bool fuse_turned_on = fuse && !c->fuse_on;
                 c->tiny_on = tiny; c->fuse_on = fuse;
                 const int pg = grid_for(c->NPOS / 8 / kProbBlock + 1, 1, 1024);
-                Status *st = c->d_status.as<Status>();
+                Status *st = c->d_status.p;
                 if (fuse_turned_on)     // the first pass did not count the reads the wide problems keep: nobody was going to ask
-                    hipLaunchKernelGGL(k_prob_range, dim3(pg), dim3(kRangeThreads), 0, c->stream, st, c->d_cand_pn.as<int>(),
-                                       c->d_seg_iv.as<int>(), c->d_cand_y.as<int>(), c->d_iv_part.as<int>(), c->d_iv_start.as<int>(),
-                                       c->d_part_lane_off.as<i64>(), c->d_lane_start.as<int>(), c->d_lane_pmax.as<int>(),
-                                       c->d_cand_ll.as<int>(), c->d_cand_ln.as<int>(), c->d_cand_wide.as<unsigned char>(), c->d_lane_lx.as<int2>(),
-                                       c->d_lex.as<int2>(), c->wide_by_seen ? 1 : 0, split_of(c, tiny, fuse).fuse_lanes, (i64 *)nullptr, split_of(c, tiny, fuse));
+                    hipLaunchKernelGGL(k_prob_range, dim3(pg), dim3(kRangeThreads), 0, c->stream, st, c->d_cand_pn.p,
+                                       c->d_seg_iv.p, c->d_cand_y.p, c->d_iv_part.p, c->d_iv_start.p,
+                                       c->d_part_lane_off.p, c->d_lane_start.p, c->d_lane_pmax.p,
+                                       c->d_cand_ll.p, c->d_cand_ln.p, c->d_cand_wide.p, c->d_lane_lx.p,
+                                       c->d_lex.p, c->wide_by_seen ? 1 : 0, split_of(c, tiny, fuse).fuse_lanes, (i64 *)nullptr, split_of(c, tiny, fuse));
                 // (the scan ADDS to the per-class counts of wide problems: the first scan's must not stay in them)
                 HIP_TRY(c, hipMemsetAsync(reinterpret_cast<char *>(st) + offsetof(Status, wide_cls), 0, sizeof(st->wide_cls), c->stream));
-                hipLaunchKernelGGL(k_prob_scan1, dim3(pg), dim3(256), 0, c->stream, st, c->d_cand_pn.as<int>(), c->d_cand_ln.as<int>(), c->d_cand_wide.as<unsigned char>(),
-                                   c->d_prob_bs.as<i64>(), split_of(c, tiny, fuse));
-                hipLaunchKernelGGL(k_prob_scan2, dim3(1), dim3(256), 0, c->stream, st, c->d_prob_bs.as<i64>());
-                HIP_TRY(c, hipMemcpyAsync(c->h_status, st, sizeof(Status), hipMemcpyDeviceToHost, c->stream));
+                hipLaunchKernelGGL(k_prob_scan1, dim3(pg), dim3(256), 0, c->stream, st, c->d_cand_pn.p, c->d_cand_ln.p, c->d_cand_wide.p,
+                                   c->d_prob_bs.p, split_of(c, tiny, fuse));
+                hipLaunchKernelGGL(k_prob_scan2, dim3(1), dim3(256), 0, c->stream, st, c->d_prob_bs.p);
+                HIP_TRY(c, hipMemcpyAsync(c->h_status.p, st, sizeof(Status), hipMemcpyDeviceToHost, c->stream));
                 HIP_TRY(c, wait_stream(c));
                 s = *c->h_status;
             }
@@ -1463,7 +1485,111 @@ int run_sized(fseg_ctx *c) {
     return fail(c, FSEG_ERR_HIP, "the compaction scans stalled repeatedly");
 }
 
+// fseg_create, first half: what a context allocates and creates up front (on failure the caller deletes the context: that releases it)
+struct LdsAttr { const void *fn; size_t bytes; template <typename F> LdsAttr(F *f, size_t b) : fn(reinterpret_cast<const void *>(f)), bytes(b) {} };
+hipError_t init_resources(fseg_ctx *c, bool first_on_device) {
+#define CREATE_TRY(expr) do { const hipError_t e__ = (expr); if (e__ != hipSuccess) return e__; } while (0)
+    CREATE_TRY(hipSetDevice(c->device));
+    CREATE_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+    CREATE_TRY(c->h_status.alloc()); CREATE_TRY(c->h_prep.alloc());
+    CREATE_TRY(c->d_status.alloc(sizeof(Status))); CREATE_TRY(c->d_prep.alloc(sizeof(PrepStatus)));
+    CREATE_TRY(c->d_tacc.alloc(kTaccBytes));
+    CREATE_TRY(hipMemsetAsync(c->d_tacc.p, 0, kTaccBytes, c->stream));
+    CREATE_TRY(c->d_sync.alloc(sizeof(SyncWords)));
+    CREATE_TRY(hipMemsetAsync(c->d_sync.p, 0, sizeof(SyncWords), c->stream));
+    for (int i = 0; i < ST_COUNT; ++i) { CREATE_TRY(hipEventCreate(&c->ev_b[i])); CREATE_TRY(hipEventCreate(&c->ev_e[i])); }
+    for (int i = 0; i < 4; ++i) CREATE_TRY(hipEventCreate(&c->ev_g[i]));
+    // The side streams: at once for the first context of a device (the usual single-context user gets its four streams on
+    // four hardware queues), otherwise by the first run that forks: the runtime spreads a process's streams over its few
+    // hardware queues in creation order, and contexts that take turns on a device use their main streams only -- created
+    // back to back, those land on different queues.
+    if (first_on_device)
+        for (int i = 0; i < fseg_ctx::kSide; ++i) CREATE_TRY(hipStreamCreateWithFlags(&c->side[i], hipStreamNonBlocking));
+    for (int i = 0; i < fseg_ctx::kForkEvents; ++i) CREATE_TRY(hipEventCreateWithFlags(&c->fj[i], hipEventDisableTiming));
+    // the kernels that are launched with more dynamic LDS than the default limit, and the most each may ask for
+    const LdsAttr lds_attrs[] = {
+        {k_score<kNMax>, ScoreCfg<kNMax>::kLds},
+        {k_dp<kNMax, 256, unsigned>, dp_lds_for(kNMax, 4)},
+        {k_dp<kNMax, 512, unsigned>, kLdsPerWg - 8 * 1024},
+        {k_dp<kNMax, 512, unsigned short>, dp_lds_for(kNMax, 2)},
+        {k_score_huge, kHugeScoreLds},
+        {k_solve<kNMax, unsigned char, int, false>, solve_lds_for(kNMax, kNMax + 1, 1)},
+        {k_solve<kNMax, unsigned char, i64, false>, solve_lds_for(kNMax, kNMax + 1, 1)},
+        {k_solve<kNMax, unsigned short, int, false>, solve_lds_for(kNMax, kNMax + 1, 2)},
+        {k_solve<kNMax, unsigned short, i64, false>, solve_lds_for(kNMax, kNMax + 1, 2)},
+        {k_solve<kNMax, unsigned char, int, true>, solve_lds_for(kNMax, kNMax + 1, 1)},
+        {k_solve<kNMax, unsigned short, int, true>, solve_lds_for(kNMax, kNMax + 1, 2)},
+        {k_dpw<kNMax, unsigned char, int, 64>, dpw_lds_for(kNMax, 4, 1)},
+        {k_dpw<kNMax, unsigned short, int, 64>, dpw_lds_for(kNMax, 4, 2)},
+        {k_dpw<kNMax, unsigned char, i64, 64>, dpw_lds_for(kNMax, 8, 1)},
+        {k_dpw<kNMax, unsigned short, i64, 64>, dpw_lds_for(kNMax, 8, 2)},
+        {k_dpw<kNMax, unsigned char, int, 512>, dpw_lds_for(kNMax, 4, 1)},
+        {k_dpw<kNMax, unsigned short, int, 512>, dpw_lds_for(kNMax, 4, 2)},
+        {k_dpw<kNMax, unsigned char, i64, 512>, dpw_lds_for(kNMax, 8, 1)},
+        {k_dpw<kNMax, unsigned short, i64, 512>, dpw_lds_for(kNMax, 8, 2)},
+        {k_dp_huge, kHugeDpLds},
+    };
+    for (const auto &a : lds_attrs) CREATE_TRY(hipFuncSetAttribute(a.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)a.bytes));
+#undef CREATE_TRY
+    return hipSuccess;
+}
+
+// The FSEG_* switches, read once per context: a flag is on where the value begins with '1'; an off-flag turns its default off where it
+// begins with '0'; a tri-state takes '0' or '1', else "decide per batch" stays; an integer is taken where the value is not empty.
+bool env_flag(const char *name) { const char *v = getenv(name); return v && v[0] == '1'; }
+bool env_off(const char *name) { const char *v = getenv(name); return v && v[0] == '0'; }
+void env_tri(const char *name, int &out) { const char *v = getenv(name); if (v && (v[0] == '0' || v[0] == '1')) out = v[0] - '0'; }
+bool env_int(const char *name, i64 &out) { const char *v = getenv(name); if (!v || !v[0]) return false; out = atoll(v); return true; }
+const char *env_str(const char *name) { return getenv(name); }
+
+void read_switches(fseg_ctx *c) {
+    i64 v = 0;
+    if (env_off("FSEG_DEV_SYNC")) c->dev_sync = false;
+    if (env_flag("FSEG_LABEL_BYTES")) c->label_packed_ok = false;
+    env_tri("FSEG_THR_PART", c->thr_part);
+    env_tri("FSEG_HIST16", c->hist16);
+    env_tri("FSEG_YRAW16", c->yraw16);
+    if (env_int("FSEG_SYNC_TICKS", v) && v > 0) c->sync_ticks = (unsigned)v;
+    if (env_flag("FSEG_NO_GRAPH")) c->use_graph = false;
+    if (env_flag("FSEG_NO_FORK")) c->use_fork = false;
+    if (env_flag("FSEG_NO_FUSE")) c->use_fuse = false;
+    if (env_flag("FSEG_NO_WAVE")) c->use_wave = false;
+    if (env_flag("FSEG_FORCE_KEY64")) c->force_key64 = true;
+    if (env_flag("FSEG_WIDE_BY_SEEN")) c->wide_by_seen = true;
+    if (const char *s = env_str("FSEG_SPLIT_DP")) c->split_dp = atoi(s) & 15;       // (set but empty counts: 0, no class hands its DPs over)
+    if (const char *s = env_str("FSEG_SCORE_PLAN")) snprintf(c->score_plan, sizeof c->score_plan, "%s", s);
+    {
+        int seen[4] = {0, 0, 0, 0};
+        static const char kinds[] = "BMST";
+        for (const char *q = c->score_plan; *q; ++q) { const char *at = strchr(kinds, *q); if (at) ++seen[at - kinds]; }
+        int bars = 0;
+        for (const char *q = c->score_plan; *q; ++q) bars += *q == '|';
+        if (seen[0] != 1 || seen[1] != 1 || seen[2] != 1 || seen[3] != 1 || bars > fseg_ctx::kSide) c->score_plan[0] = 0;   // (a stream per segment)
+    }
+    if (env_int("FSEG_FUSE_LANES", v) && v > 0 && v <= kFuseLanesWide) c->fuse_lanes = (int)v;
+    if (env_flag("FSEG_NO_SIZED")) c->use_sized = false;
+    if (env_flag("FSEG_TRACE")) c->trace = true;
+    if (env_flag("FSEG_GLOBAL_SORT")) c->force_global_sort = true;
+    if (env_flag("FSEG_FORCE_SCAN_STALL")) c->force_scan_stall = true;
+    if (env_int("FSEG_TINY_FROM", v)) c->tiny_from = v;
+    if (env_int("FSEG_SCAN_SINGLE_MAX", v)) c->scan_single_max = v;
+}
+
 }  // namespace
+
+fseg_ctx::~fseg_ctx() {
+    (void)hipSetDevice(device);
+    if (stream) (void)hipStreamSynchronize(stream);
+    for (hipStream_t q : side) if (q) (void)hipStreamSynchronize(q);
+    drop_graph(this);
+    if (hsa_agent >= 0) (void)hsa_signal_destroy(hsa_sig);
+    for (hipEvent_t e : ev_b) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : ev_e) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : ev_g) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : fj) if (e) (void)hipEventDestroy(e);
+    for (hipStream_t q : side) if (q) (void)hipStreamDestroy(q);
+    if (stream) (void)hipStreamDestroy(stream);
+}
 
 // ---------------------------------------------------------------------------------------------
 // C-ABI
@@ -1493,98 +1619,16 @@ int fseg_create(int device, fseg_ctx **out) {
     if (device < 0 || device >= n) { g_create_error = "device ordinal out of range"; return FSEG_ERR_ARG; }
     fseg_ctx *c = new fseg_ctx();
     c->device = device;
-    e = hipSetDevice(device);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipHostMalloc((void **)&c->h_status, sizeof(Status), hipHostMallocDefault);
-    if (e == hipSuccess) e = hipHostMalloc((void **)&c->h_prep, sizeof(PrepStatus), hipHostMallocDefault);
-    if (e == hipSuccess) e = hipMalloc(&c->d_status.p, sizeof(Status));
-    if (e == hipSuccess) e = hipMalloc(&c->d_prep.p, sizeof(PrepStatus));
-    if (e == hipSuccess) e = hipMalloc(&c->d_tacc.p, kTaccBytes);
-    if (e == hipSuccess) e = hipMemsetAsync(c->d_tacc.p, 0, kTaccBytes, c->stream);
-    if (e == hipSuccess) e = hipMalloc(&c->d_sync.p, sizeof(SyncWords));
-    if (e == hipSuccess) e = hipMemsetAsync(c->d_sync.p, 0, sizeof(SyncWords), c->stream);
-    for (int i = 0; e == hipSuccess && i < ST_COUNT; ++i) { e = hipEventCreate(&c->ev_b[i]); if (e == hipSuccess) e = hipEventCreate(&c->ev_e[i]); }
-    for (int i = 0; e == hipSuccess && i < 4; ++i) e = hipEventCreate(&c->ev_g[i]);
-    // The side streams: at once for the first context of a device (the usual single-context user gets its four streams on
-    // four hardware queues), otherwise by the first run that forks: the runtime spreads a process's streams over its few
-    // hardware queues in creation order, and contexts that take turns on a device use their main streams only -- created
-    // back to back, those land on different queues.
     c->counted_live = device >= 0 && device < 64;
-    if (c->counted_live && g_live[device].fetch_add(1) == 0)
-        for (int i = 0; e == hipSuccess && i < fseg_ctx::kSide; ++i) e = hipStreamCreateWithFlags(&c->side[i], hipStreamNonBlocking);
-    for (int i = 0; e == hipSuccess && i < fseg_ctx::kForkEvents; ++i) e = hipEventCreateWithFlags(&c->fj[i], hipEventDisableTiming);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_score<kNMax>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)ScoreCfg<kNMax>::kLds);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_dp<kNMax, 256, unsigned>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)dp_lds_for(kNMax, 4));
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_dp<kNMax, 512, unsigned>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kLdsPerWg - 8 * 1024));
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_dp<kNMax, 512, unsigned short>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)dp_lds_for(kNMax, 2));
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_score_huge), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)kHugeScoreLds);
-    {
-        auto lds_attr = [&](const void *f, size_t bytes) { if (e == hipSuccess) e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes); };
-        lds_attr(reinterpret_cast<const void *>(k_solve<kNMax, unsigned char, int, false>), solve_lds_for(kNMax, kNMax + 1, 1));
-        lds_attr(reinterpret_cast<const void *>(k_solve<kNMax, unsigned char, i64, false>), solve_lds_for(kNMax, kNMax + 1, 1));
-        lds_attr(reinterpret_cast<const void *>(k_solve<kNMax, unsigned short, int, false>), solve_lds_for(kNMax, kNMax + 1, 2));
-        lds_attr(reinterpret_cast<const void *>(k_solve<kNMax, unsigned short, i64, false>), solve_lds_for(kNMax, kNMax + 1, 2));
-        lds_attr(reinterpret_cast<const void *>(k_solve<kNMax, unsigned char, int, true>), solve_lds_for(kNMax, kNMax + 1, 1));
-        lds_attr(reinterpret_cast<const void *>(k_solve<kNMax, unsigned short, int, true>), solve_lds_for(kNMax, kNMax + 1, 2));
-        lds_attr(reinterpret_cast<const void *>(k_dpw<kNMax, unsigned char, int, 64>), dpw_lds_for(kNMax, 4, 1));
-        lds_attr(reinterpret_cast<const void *>(k_dpw<kNMax, unsigned short, int, 64>), dpw_lds_for(kNMax, 4, 2));
-        lds_attr(reinterpret_cast<const void *>(k_dpw<kNMax, unsigned char, i64, 64>), dpw_lds_for(kNMax, 8, 1));
-        lds_attr(reinterpret_cast<const void *>(k_dpw<kNMax, unsigned short, i64, 64>), dpw_lds_for(kNMax, 8, 2));
-        lds_attr(reinterpret_cast<const void *>(k_dpw<kNMax, unsigned char, int, 512>), dpw_lds_for(kNMax, 4, 1));
-        lds_attr(reinterpret_cast<const void *>(k_dpw<kNMax, unsigned short, int, 512>), dpw_lds_for(kNMax, 4, 2));
-        lds_attr(reinterpret_cast<const void *>(k_dpw<kNMax, unsigned char, i64, 512>), dpw_lds_for(kNMax, 8, 1));
-        lds_attr(reinterpret_cast<const void *>(k_dpw<kNMax, unsigned short, i64, 512>), dpw_lds_for(kNMax, 8, 2));
-    }
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_dp_huge), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)kHugeDpLds);
-    if (e != hipSuccess) {
+    const bool first_on_device = c->counted_live && g_live[device].fetch_add(1) == 0;
+    e = init_resources(c, first_on_device);
+    if (e != hipSuccess) {           // (whatever had been made by then goes with the context)
         g_create_error = std::string("context creation failed: ") + hipGetErrorString(e);
         if (c->counted_live) g_live[device].fetch_sub(1);
         delete c;
         return FSEG_ERR_HIP;
     }
-    c->d_status.cap = sizeof(Status); c->d_prep.cap = sizeof(PrepStatus); c->d_tacc.cap = kTaccBytes; c->d_sync.cap = sizeof(SyncWords);
-    auto flag = [](const char *name) { const char *v = getenv(name); return v && v[0] == '1'; };
-    { const char *v = getenv("FSEG_DEV_SYNC"); if (v && v[0] == '0') c->dev_sync = false; }
-    if (flag("FSEG_LABEL_BYTES")) c->label_packed_ok = false;
-    { const char *v = getenv("FSEG_THR_PART"); if (v && (v[0] == '0' || v[0] == '1')) c->thr_part = v[0] - '0'; }
-    { const char *v = getenv("FSEG_HIST16"); if (v && (v[0] == '0' || v[0] == '1')) c->hist16 = v[0] - '0'; }
-    { const char *v = getenv("FSEG_YRAW16"); if (v && (v[0] == '0' || v[0] == '1')) c->yraw16 = v[0] - '0'; }
-    { const char *v = getenv("FSEG_SYNC_TICKS"); if (v && v[0] && atoll(v) > 0) c->sync_ticks = (unsigned)atoll(v); }
-    if (flag("FSEG_NO_GRAPH")) c->use_graph = false;
-    if (flag("FSEG_NO_FORK")) c->use_fork = false;
-    if (flag("FSEG_NO_FUSE")) c->use_fuse = false;
-    if (flag("FSEG_NO_WAVE")) c->use_wave = false;
-    if (flag("FSEG_FORCE_KEY64")) c->force_key64 = true;
-    if (flag("FSEG_WIDE_BY_SEEN")) c->wide_by_seen = true;
-    if (const char *e = getenv("FSEG_SPLIT_DP")) c->split_dp = atoi(e) & 15;
-    if (const char *e = getenv("FSEG_SCORE_PLAN")) snprintf(c->score_plan, sizeof c->score_plan, "%s", e);
-    {
-        int seen[4] = {0, 0, 0, 0};
-        static const char kinds[] = "BMST";
-        for (const char *q = c->score_plan; *q; ++q) { const char *at = strchr(kinds, *q); if (at) ++seen[at - kinds]; }
-        int bars = 0;
-        for (const char *q = c->score_plan; *q; ++q) bars += *q == '|';
-        if (seen[0] != 1 || seen[1] != 1 || seen[2] != 1 || seen[3] != 1 || bars > fseg_ctx::kSide) c->score_plan[0] = 0;   // (a stream per segment)
-    }
-    { const char *v = getenv("FSEG_FUSE_LANES"); if (v && v[0] && atoi(v) > 0 && atoi(v) <= kFuseLanesWide) c->fuse_lanes = atoi(v); }
-    if (flag("FSEG_NO_SIZED")) c->use_sized = false;
-    if (flag("FSEG_TRACE")) c->trace = true;
-    if (flag("FSEG_GLOBAL_SORT")) c->force_global_sort = true;
-    if (flag("FSEG_FORCE_SCAN_STALL")) c->force_scan_stall = true;
-    { const char *tf = getenv("FSEG_TINY_FROM"); if (tf && tf[0]) c->tiny_from = atoll(tf); }
-    { const char *sm = getenv("FSEG_SCAN_SINGLE_MAX"); if (sm && sm[0]) c->scan_single_max = atoll(sm); }
+    read_switches(c);
     *out = c;
     return FSEG_OK;
 }
@@ -1594,25 +1638,6 @@ void fseg_destroy(fseg_ctx *c) {
     set_in_flight(c, false);
     release_device(c);
     if (c->counted_live) { g_live[c->device].fetch_sub(1); c->counted_live = false; }
-    if (c->hsa_agent >= 0) { (void)hsa_signal_destroy(c->hsa_sig); c->hsa_agent = -2; }
-    (void)hipSetDevice(c->device);
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
-    drop_graph(c);
-    Slab *slabs[] = {&c->slab_in, &c->slab_pos, &c->slab_arena};
-    for (Slab *s : slabs) if (s->p) (void)hipFree(s->p);
-    DevBuf *bufs[] = {&c->d_labels, &c->d_packed, &c->d_sort_tmp, &c->d_w_main, &c->d_w_refine, &c->d_h_table, &c->d_thr_tab, &c->d_status, &c->d_prep, &c->d_tacc, &c->d_sync, &c->d_giant, &c->d_an_in, &c->d_an_work, &c->d_an_out};
-    for (DevBuf *b : bufs) if (b->p) (void)hipFree(b->p);
-    if (c->h_stage.p) (void)hipHostFree(c->h_stage.p);
-    if (c->h_res.p) (void)hipHostFree(c->h_res.p);
-    if (c->h_an_in.p) (void)hipHostFree(c->h_an_in.p);
-    if (c->h_an.p) (void)hipHostFree(c->h_an.p);
-    if (c->h_status) (void)hipHostFree(c->h_status);
-    if (c->h_prep) (void)hipHostFree(c->h_prep);
-    for (int i = 0; i < ST_COUNT; ++i) { if (c->ev_b[i]) (void)hipEventDestroy(c->ev_b[i]); if (c->ev_e[i]) (void)hipEventDestroy(c->ev_e[i]); }
-    for (int i = 0; i < 4; ++i) if (c->ev_g[i]) (void)hipEventDestroy(c->ev_g[i]);
-    for (int i = 0; i < fseg_ctx::kSide; ++i) if (c->side[i]) { (void)hipStreamSynchronize(c->side[i]); (void)hipStreamDestroy(c->side[i]); }
-    for (int i = 0; i < fseg_ctx::kForkEvents; ++i) if (c->fj[i]) (void)hipEventDestroy(c->fj[i]);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
 
@@ -1639,8 +1664,8 @@ int fseg_set_params(fseg_ctx *c, const fseg_params *p) {
     TRY(upload_vec(c, c->d_w_refine, c->w_refine.data(), c->w_refine.size()));
     TRY(upload_vec(c, c->d_h_table, c->h_table.data(), c->h_table.size()));
     TRY(ensure(c, c->d_thr_tab, (size_t)kThrTab * sizeof(int2)));
-    hipLaunchKernelGGL(k_thr_table, dim3(kThrTab / 256), dim3(256), 0, c->stream, c->d_h_table.as<double>(), c->P.h_len,
-                       c->P.threshold_rate, c->d_thr_tab.as<int2>());
+    hipLaunchKernelGGL(k_thr_table, dim3(kThrTab / 256), dim3(256), 0, c->stream, c->d_h_table.p, c->P.h_len,
+                       c->P.threshold_rate, c->d_thr_tab.p);
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     // lo < 0 (label_thresholds: no v >= 0 with v / L < 1 - h) exactly where h >= 1: the rate itself, or an entry of the table that
     // round(y, 2) took to 1.0 (segment lengths start at 1)
@@ -1754,62 +1779,32 @@ static int upload_impl(fseg_ctx *c, const fseg_batch *b) {
     if (n_tiles >= 0x7fffffffLL || n_chunks >= 0x7fffffffLL) return fail(c, FSEG_ERR_UNSUPPORTED, "batch too large");
     // ---- the input slab: [uploaded part, mirrored by the pinned staging image][device-derived part]
     Carve in;
-    in.add(c->d_part_iv_off, ((size_t)np + 1) * 8);
-    in.add(c->d_part_rep_off, ((size_t)np + 1) * 8);
-    in.add(c->d_part_lane_off, ((size_t)np + 1) * 8);
-    in.add(c->d_iv_start, (size_t)K * 4);
-    in.add(c->d_iv_end, (size_t)K * 4);
-    in.add(c->d_pos_off, ((size_t)K + 1) * 8);
-    in.add(c->d_iv_part, (size_t)K * 4);
-    in.add(c->d_iv_tile0, (size_t)K * 4);
-    in.add(c->d_tile_desc, (size_t)n_tiles * sizeof(TileDesc));
-    in.add(c->d_blk_iv0, ((size_t)nbp + 1) * 4);
-    in.add(c->d_rb_part, (size_t)n_rep_blocks * 4);
-    in.add(c->d_rb_r0, (size_t)n_rep_blocks * 4);
-    in.add(c->d_hc_part, (size_t)n_chunks * 4);
-    in.add(c->d_hc_p0, (size_t)n_chunks * 8);
-    in.add(c->d_hc_n, (size_t)n_chunks * 4);
-    in.add(c->d_hc_glo, (size_t)n_chunks * 4);
-    in.add(c->d_hc_ghi, (size_t)n_chunks * 4);
-    in.add(c->d_rep_exon_off, ((size_t)R + 1) * 8);
-    in.add(c->d_rep_weight, (size_t)R * 4);
-    in.add(c->d_ex_ts, (size_t)I * 4 + kExonPad);
-    in.add(c->d_ex_te, (size_t)I * 4 + kExonPad);
+    in.add(c->d_part_iv_off, np + 1); in.add(c->d_part_rep_off, np + 1); in.add(c->d_part_lane_off, np + 1);
+    in.add(c->d_iv_start, K); in.add(c->d_iv_end, K); in.add(c->d_pos_off, K + 1); in.add(c->d_iv_part, K); in.add(c->d_iv_tile0, K);
+    in.add(c->d_tile_desc, n_tiles);
+    in.add(c->d_blk_iv0, nbp + 1);
+    in.add(c->d_rb_part, n_rep_blocks); in.add(c->d_rb_r0, n_rep_blocks);
+    in.add(c->d_hc_part, n_chunks); in.add(c->d_hc_p0, n_chunks); in.add(c->d_hc_n, n_chunks); in.add(c->d_hc_glo, n_chunks); in.add(c->d_hc_ghi, n_chunks);
+    in.add(c->d_rep_exon_off, R + 1); in.add(c->d_rep_weight, R);
+    in.add(c->d_ex_ts, I, kExonPad); in.add(c->d_ex_te, I, kExonPad);
     const size_t up_bytes = in.total;
-    in.add(c->d_lane_ex, (size_t)lanes * 16);
-    in.add(c->d_lane_start, (size_t)lanes * 4);
-    in.add(c->d_lane_pmax, (size_t)lanes * 4);
-    in.add(c->d_hc_llo, (size_t)n_chunks * 8);
-    in.add(c->d_hc_lhi, (size_t)n_chunks * 8);
-    in.add(c->d_key_a, (size_t)R * 8);
-    in.add(c->d_key_b, (size_t)R * 8);
-    in.add(c->d_val_a, (size_t)R * 4);
-    in.add(c->d_val_b, (size_t)R * 4);
-    in.add(c->d_rep_last, (size_t)R * 4);
-    in.add(c->d_rb_sum, (size_t)n_rep_blocks * 8);
-    in.add(c->d_rb_base, (size_t)n_rep_blocks * 8);
-    in.add(c->d_rb_max, (size_t)n_rep_blocks * 4);
-    in.add(c->d_rb_cmax, (size_t)n_rep_blocks * 4);
-    in.add(c->d_rb_esum, (size_t)n_rep_blocks * 8);
-    in.add(c->d_rb_ebase, (size_t)n_rep_blocks * 8);
-    in.add(c->d_lane_lx, (size_t)lanes * 8 + 64);
-    in.add(c->d_lex, (size_t)I * 8 + kLexPad);
+    in.add(c->d_lane_ex, lanes); in.add(c->d_lane_start, lanes); in.add(c->d_lane_pmax, lanes);
+    in.add(c->d_hc_llo, n_chunks); in.add(c->d_hc_lhi, n_chunks);
+    in.add(c->d_key_a, R); in.add(c->d_key_b, R); in.add(c->d_val_a, R); in.add(c->d_val_b, R); in.add(c->d_rep_last, R);
+    in.add(c->d_rb_sum, n_rep_blocks); in.add(c->d_rb_base, n_rep_blocks); in.add(c->d_rb_max, n_rep_blocks); in.add(c->d_rb_cmax, n_rep_blocks);
+    in.add(c->d_rb_esum, n_rep_blocks); in.add(c->d_rb_ebase, n_rep_blocks);
+    in.add(c->d_lane_lx, lanes, 64); in.add(c->d_lex, I, kLexPad);
     TRY(reserve(c, c->slab_in, in.total));
-    in.bind(c->slab_in);
+    in.bind(c->slab_in.p);
     TRY(reserve_host(c, c->h_stage, up_bytes));
-    char *stage = c->h_stage.as<char>();
-    auto host_of = [&](const DevBuf &d) { return stage + (static_cast<char *>(d.p) - static_cast<char *>(c->slab_in.p)); };
     const double t_plan = tk.ms();
     // ---- host pass 2: the small derived tables, written straight into the staging image
     {
-        i64 *h_pos_off = reinterpret_cast<i64 *>(host_of(c->d_pos_off)), *h_lane_off = reinterpret_cast<i64 *>(host_of(c->d_part_lane_off));
-        int *h_iv_part = reinterpret_cast<int *>(host_of(c->d_iv_part)), *h_iv_tile0 = reinterpret_cast<int *>(host_of(c->d_iv_tile0));
-        TileDesc *h_tile = reinterpret_cast<TileDesc *>(host_of(c->d_tile_desc));
-        int *h_blk = reinterpret_cast<int *>(host_of(c->d_blk_iv0));
-        int *h_rb_part = reinterpret_cast<int *>(host_of(c->d_rb_part)), *h_rb_r0 = reinterpret_cast<int *>(host_of(c->d_rb_r0));
-        int *h_hc_part = reinterpret_cast<int *>(host_of(c->d_hc_part)), *h_hc_n = reinterpret_cast<int *>(host_of(c->d_hc_n));
-        int *h_hc_glo = reinterpret_cast<int *>(host_of(c->d_hc_glo)), *h_hc_ghi = reinterpret_cast<int *>(host_of(c->d_hc_ghi));
-        i64 *h_hc_p0 = reinterpret_cast<i64 *>(host_of(c->d_hc_p0));
+        i64 *h_pos_off = host_of(c, c->d_pos_off), *h_lane_off = host_of(c, c->d_part_lane_off), *h_hc_p0 = host_of(c, c->d_hc_p0);
+        int *h_iv_part = host_of(c, c->d_iv_part), *h_iv_tile0 = host_of(c, c->d_iv_tile0), *h_blk = host_of(c, c->d_blk_iv0);
+        TileDesc *h_tile = host_of(c, c->d_tile_desc);
+        int *h_rb_part = host_of(c, c->d_rb_part), *h_rb_r0 = host_of(c, c->d_rb_r0);
+        int *h_hc_part = host_of(c, c->d_hc_part), *h_hc_n = host_of(c, c->d_hc_n), *h_hc_glo = host_of(c, c->d_hc_glo), *h_hc_ghi = host_of(c, c->d_hc_ghi);
         h_pos_off[0] = 0; h_lane_off[0] = 0; c->max_part_lanes = 0; c->max_part_pos = 0;
         i64 t = 0, rb = 0, ch = 0, l = 0, bq = 0;
         for (int p = 0; p < np; ++p) {
@@ -1847,14 +1842,14 @@ static int upload_impl(fseg_ctx *c, const fseg_batch *b) {
     }
     const double t_tables = tk.ms();
     // ---- the caller's arrays
-    memcpy(host_of(c->d_part_iv_off), b->part_iv_off, ((size_t)np + 1) * 8);
-    memcpy(host_of(c->d_part_rep_off), b->part_rep_off, ((size_t)np + 1) * 8);
-    memcpy(host_of(c->d_iv_start), b->iv_start, (size_t)K * 4);
-    memcpy(host_of(c->d_iv_end), b->iv_end, (size_t)K * 4);
-    memcpy(host_of(c->d_rep_exon_off), b->rep_exon_off, ((size_t)R + 1) * 8);
-    memcpy(host_of(c->d_rep_weight), b->rep_weight, (size_t)R * 4);
-    memcpy(host_of(c->d_ex_ts), b->ex_ts, (size_t)I * 4);
-    memcpy(host_of(c->d_ex_te), b->ex_te, (size_t)I * 4);
+    auto stage_in = [&](const auto &d, const auto *src, size_t n) {
+        static_assert(sizeof(*src) == sizeof(*d.p), "the caller's array and the buffer hold the same element");
+        memcpy(host_of(c, d), src, d.bytes(n));
+    };
+    stage_in(c->d_part_iv_off, b->part_iv_off, (size_t)np + 1); stage_in(c->d_part_rep_off, b->part_rep_off, (size_t)np + 1);
+    stage_in(c->d_iv_start, b->iv_start, (size_t)K); stage_in(c->d_iv_end, b->iv_end, (size_t)K);
+    stage_in(c->d_rep_exon_off, b->rep_exon_off, (size_t)R + 1); stage_in(c->d_rep_weight, b->rep_weight, (size_t)R);
+    stage_in(c->d_ex_ts, b->ex_ts, (size_t)I); stage_in(c->d_ex_te, b->ex_te, (size_t)I);
     const double t_copy = tk.ms();
     c->n_part = np; c->K = K; c->R = R; c->I = I; c->NPOS = NPOS; c->LANES = lanes; c->expanded = expanded;
     if (c->max_part_lanes > lanes) c->max_part_lanes = lanes;
@@ -1862,21 +1857,21 @@ static int upload_impl(fseg_ctx *c, const fseg_batch *b) {
     c->part_iv_off.assign(b->part_iv_off, b->part_iv_off + np + 1);
     c->part_rep_off.assign(b->part_rep_off, b->part_rep_off + np + 1);
     hipStream_t s = c->stream;
-    HIP_TRY(c, hipMemcpyAsync(c->slab_in.p, stage, up_bytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(c->slab_in.p, c->h_stage.p, up_bytes, hipMemcpyHostToDevice, s));
     // ---- device-side preparation
     {
         PrepStatus init;
         init.err = 0; init.pad = 0;
         for (int q = 0; q < 4; ++q) init.bad_rep[q] = 0x7fffffffffffffffLL;
         *c->h_prep = init;
-        HIP_TRY(c, hipMemcpyAsync(c->d_prep.p, c->h_prep, sizeof(PrepStatus), hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipMemcpyAsync(c->d_prep.p, c->h_prep.p, sizeof(PrepStatus), hipMemcpyHostToDevice, s));
         c->prep_checked = false;
     }
     if (R > 0) {
-        hipLaunchKernelGGL(k_prep_reps, dim3(grid_for(n_rep_blocks, 1, 65536)), dim3(256), 0, s, (int)n_rep_blocks, c->d_rb_part.as<int>(),
-                           c->d_rb_r0.as<int>(), c->d_part_rep_off.as<i64>(), c->d_part_iv_off.as<i64>(), c->d_iv_start.as<int>(),
-                           c->d_iv_end.as<int>(), c->d_rep_exon_off.as<i64>(), c->d_ex_ts.as<int>(), c->d_ex_te.as<int>(),
-                           c->d_key_a.as<u64>(), c->d_val_a.as<int>(), c->d_rep_last.as<int>(), c->d_prep.as<PrepStatus>());
+        hipLaunchKernelGGL(k_prep_reps, dim3(grid_for(n_rep_blocks, 1, 65536)), dim3(256), 0, s, (int)n_rep_blocks, c->d_rb_part.p,
+                           c->d_rb_r0.p, c->d_part_rep_off.p, c->d_part_iv_off.p, c->d_iv_start.p,
+                           c->d_iv_end.p, c->d_rep_exon_off.p, c->d_ex_ts.p, c->d_ex_te.p,
+                           c->d_key_a.p, c->d_val_a.p, c->d_rep_last.p, c->d_prep.p);
         // small partitions (the usual case) sort themselves inside k_lanes; a batch with a large one goes through the
         // batch-wide radix sort (FSEG_GLOBAL_SORT=1 forces it: tests)
         const bool sort_here = max_part_reps <= kLaneSortMax && !c->force_global_sort;
@@ -1884,37 +1879,37 @@ static int upload_impl(fseg_ctx *c, const fseg_batch *b) {
             unsigned end_bit = 33;
             while (end_bit < 64 && ((u64)np >> (end_bit - 32)) != 0) ++end_bit;
             size_t tmp_bytes = 0;
-            HIP_TRY(c, fseg_sort_pairs(nullptr, &tmp_bytes, c->d_key_a.as<u64>(), c->d_key_b.as<u64>(), c->d_val_a.as<int>(), c->d_val_b.as<int>(),
+            HIP_TRY(c, fseg_sort_pairs(nullptr, &tmp_bytes, c->d_key_a.p, c->d_key_b.p, c->d_val_a.p, c->d_val_b.p,
                                        (size_t)R, end_bit, s));
             TRY(ensure(c, c->d_sort_tmp, tmp_bytes));
-            HIP_TRY(c, fseg_sort_pairs(c->d_sort_tmp.p, &tmp_bytes, c->d_key_a.as<u64>(), c->d_key_b.as<u64>(), c->d_val_a.as<int>(),
-                                       c->d_val_b.as<int>(), (size_t)R, end_bit, s));
+            HIP_TRY(c, fseg_sort_pairs(c->d_sort_tmp.p, &tmp_bytes, c->d_key_a.p, c->d_key_b.p, c->d_val_a.p,
+                                       c->d_val_b.p, (size_t)R, end_bit, s));
         }
         if (sort_here) {
-            hipLaunchKernelGGL(k_lanes, dim3(grid_for(np, 1, 65536)), dim3(256), 0, s, np, c->d_part_rep_off.as<i64>(), c->d_part_lane_off.as<i64>(),
-                               c->d_key_b.as<u64>(), c->d_val_b.as<int>(), c->d_rep_weight.as<int>(), c->d_rep_last.as<int>(),
-                               c->d_rep_exon_off.as<i64>(), c->d_lane_ex.as<longlong2>(), c->d_lane_start.as<int>(), c->d_lane_pmax.as<int>(),
-                               1, c->d_key_a.as<u64>(), c->d_ex_ts.as<int>(), c->d_ex_te.as<int>(), c->d_lane_lx.as<int2>(), c->d_lex.as<int2>());
+            hipLaunchKernelGGL(k_lanes, dim3(grid_for(np, 1, 65536)), dim3(256), 0, s, np, c->d_part_rep_off.p, c->d_part_lane_off.p,
+                               c->d_key_b.p, c->d_val_b.p, c->d_rep_weight.p, c->d_rep_last.p,
+                               c->d_rep_exon_off.p, c->d_lane_ex.p, c->d_lane_start.p, c->d_lane_pmax.p,
+                               1, c->d_key_a.p, c->d_ex_ts.p, c->d_ex_te.p, c->d_lane_lx.p, c->d_lex.p);
         } else {
             const int rbg = grid_for(n_rep_blocks, 1, 65536);
-            hipLaunchKernelGGL(k_lane_blocks, dim3(rbg), dim3(256), 0, s, (int)n_rep_blocks, c->d_rb_part.as<int>(), c->d_rb_r0.as<int>(),
-                               c->d_part_rep_off.as<i64>(), c->d_val_b.as<int>(), c->d_rep_weight.as<int>(), c->d_rep_last.as<int>(),
-                               c->d_rb_sum.as<i64>(), c->d_rb_max.as<int>(), c->d_rep_exon_off.as<i64>(), c->d_rb_esum.as<i64>());
-            hipLaunchKernelGGL(k_lane_block_scan, dim3(grid_for(np, 4, 4096)), dim3(256), 0, s, np, (int)n_rep_blocks, c->d_rb_part.as<int>(),
-                               c->d_part_lane_off.as<i64>(), c->d_rb_sum.as<i64>(), c->d_rb_max.as<int>(), c->d_rb_base.as<i64>(),
-                               c->d_rb_cmax.as<int>(), c->d_part_rep_off.as<i64>(), c->d_rep_exon_off.as<i64>(), c->d_rb_esum.as<i64>(),
-                               c->d_rb_ebase.as<i64>());
-            hipLaunchKernelGGL(k_lane_emit, dim3(rbg), dim3(256), 0, s, (int)n_rep_blocks, c->d_rb_part.as<int>(), c->d_rb_r0.as<int>(),
-                               c->d_part_rep_off.as<i64>(), c->d_key_b.as<u64>(), c->d_val_b.as<int>(), c->d_rep_weight.as<int>(),
-                               c->d_rep_last.as<int>(), c->d_rep_exon_off.as<i64>(), c->d_rb_base.as<i64>(), c->d_rb_cmax.as<int>(),
-                               c->d_lane_ex.as<longlong2>(), c->d_lane_start.as<int>(), c->d_lane_pmax.as<int>(), c->d_rb_ebase.as<i64>(),
-                               c->d_ex_ts.as<int>(), c->d_ex_te.as<int>(), c->d_lane_lx.as<int2>(), c->d_lex.as<int2>());
+            hipLaunchKernelGGL(k_lane_blocks, dim3(rbg), dim3(256), 0, s, (int)n_rep_blocks, c->d_rb_part.p, c->d_rb_r0.p,
+                               c->d_part_rep_off.p, c->d_val_b.p, c->d_rep_weight.p, c->d_rep_last.p,
+                               c->d_rb_sum.p, c->d_rb_max.p, c->d_rep_exon_off.p, c->d_rb_esum.p);
+            hipLaunchKernelGGL(k_lane_block_scan, dim3(grid_for(np, 4, 4096)), dim3(256), 0, s, np, (int)n_rep_blocks, c->d_rb_part.p,
+                               c->d_part_lane_off.p, c->d_rb_sum.p, c->d_rb_max.p, c->d_rb_base.p,
+                               c->d_rb_cmax.p, c->d_part_rep_off.p, c->d_rep_exon_off.p, c->d_rb_esum.p,
+                               c->d_rb_ebase.p);
+            hipLaunchKernelGGL(k_lane_emit, dim3(rbg), dim3(256), 0, s, (int)n_rep_blocks, c->d_rb_part.p, c->d_rb_r0.p,
+                               c->d_part_rep_off.p, c->d_key_b.p, c->d_val_b.p, c->d_rep_weight.p,
+                               c->d_rep_last.p, c->d_rep_exon_off.p, c->d_rb_base.p, c->d_rb_cmax.p,
+                               c->d_lane_ex.p, c->d_lane_start.p, c->d_lane_pmax.p, c->d_rb_ebase.p,
+                               c->d_ex_ts.p, c->d_ex_te.p, c->d_lane_lx.p, c->d_lex.p);
         }
     }
-    hipLaunchKernelGGL(k_hist_ranges, dim3(grid_for(n_chunks, 256, 4096)), dim3(256), 0, s, (int)n_chunks, c->d_hc_part.as<int>(),
-                       c->d_hc_glo.as<int>(), c->d_hc_ghi.as<int>(), c->d_part_lane_off.as<i64>(), c->d_lane_start.as<int>(),
-                       c->d_lane_pmax.as<int>(), c->d_hc_llo.as<i64>(), c->d_hc_lhi.as<i64>());
-    HIP_TRY(c, hipMemcpyAsync(c->h_prep, c->d_prep.p, sizeof(PrepStatus), hipMemcpyDeviceToHost, s));
+    hipLaunchKernelGGL(k_hist_ranges, dim3(grid_for(n_chunks, 256, 4096)), dim3(256), 0, s, (int)n_chunks, c->d_hc_part.p,
+                       c->d_hc_glo.p, c->d_hc_ghi.p, c->d_part_lane_off.p, c->d_lane_start.p,
+                       c->d_lane_pmax.p, c->d_hc_llo.p, c->d_hc_lhi.p);
+    HIP_TRY(c, hipMemcpyAsync(c->h_prep.p, c->d_prep.p, sizeof(PrepStatus), hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipGetLastError());
     // ---- position- and candidate-sized work buffers (candidates and finals are distinct positions, so NPOS bounds them)
     {
@@ -1922,31 +1917,31 @@ static int upload_impl(fseg_ctx *c, const fseg_batch *b) {
         auto atleast = [](i64 &cap, i64 v) { if (cap < v) cap = v; };
         atleast(c->chunk_cap, NPOS / 8192 + np + 8);              // an upper bound, not a guess
         Carve cv;
-        cv.add(c->d_y_raw, np8 * (yraw_narrow ? 2 : 4)); cv.add(c->d_y, np8 * 8);      // (an array starts on a multiple of 256 bytes whatever the one before it holds)
-        cv.add(c->d_bits, 3 * flag_words(np8) * 4);
-        cv.add(c->d_v, np8 * 8);
-        cv.add(c->d_scan_state, ((size_t)nb * 3 + 1) * 8);
-        cv.add(c->d_bsum, ((size_t)nbp + 2) * 4);
-        cv.add(c->d_gsum, ((size_t)pos_groups(NPOS) + 2) * 4);
-        cv.add(c->d_bsum_side, ((size_t)nb + 2) * 4);
-        cv.add(c->d_g, np8 * 8); cv.add(c->d_pk, np8 * 4); cv.add(c->d_pf, np8); cv.add(c->d_kp, np8);
-        cv.add(c->d_part_has2, ((size_t)np + 1) * 4);
-        cv.add(c->d_tile_tot, ((size_t)n_tiles + 1) * 4);
-        cv.add(c->d_blk_pre, ((size_t)n_tiles + 1) * (kSmoothTile / kSumBlock) * 4);
-        cv.add(c->d_tile_defer, ((size_t)n_tiles + 1) * 4);
-        cv.add(c->d_voff, ((size_t)np + 2) * 8); cv.add(c->d_chunk_off, ((size_t)np + 2) * 8);
-        cv.add(c->d_mean, ((size_t)np + 1) * 8); cv.add(c->d_thr, ((size_t)np + 1) * 8);
-        cv.add(c->d_label_off, ((size_t)np + 2) * 8);
-        cv.add(c->d_csum, (size_t)c->chunk_cap * 16);     // chunk sums of both passes
-        cv.add(c->d_cand_off, ((size_t)K + 2) * 8); cv.add(c->d_final_off, ((size_t)K + 2) * 8);
-        cv.add(c->d_cand_y, np8 * 4); cv.add(c->d_fixed0, np8); cv.add(c->d_added, np8);
+        cv.add(c->d_y_raw, np8 * (yraw_narrow ? sizeof(uint16_t) : sizeof(int))); cv.add(c->d_y, np8);      // (an array starts on a multiple of 256 bytes whatever the one before it holds)
+        cv.add(c->d_bits, 3 * flag_words(np8));
+        cv.add(c->d_v, np8);
+        cv.add(c->d_scan_state, ((size_t)nb * 3 + 1));
+        cv.add(c->d_bsum, ((size_t)nbp + 2));
+        cv.add(c->d_gsum, ((size_t)pos_groups(NPOS) + 2));
+        cv.add(c->d_bsum_side, ((size_t)nb + 2));
+        cv.add(c->d_g, np8); cv.add(c->d_pk, np8); cv.add(c->d_pf, np8); cv.add(c->d_kp, np8);
+        cv.add(c->d_part_has2, ((size_t)np + 1));
+        cv.add(c->d_tile_tot, ((size_t)n_tiles + 1));
+        cv.add(c->d_blk_pre, ((size_t)n_tiles + 1) * (kSmoothTile / kSumBlock));
+        cv.add(c->d_tile_defer, ((size_t)n_tiles + 1));
+        cv.add(c->d_voff, ((size_t)np + 2)); cv.add(c->d_chunk_off, ((size_t)np + 2));
+        cv.add(c->d_mean, ((size_t)np + 1)); cv.add(c->d_thr, ((size_t)np + 1));
+        cv.add(c->d_label_off, ((size_t)np + 2));
+        cv.add(c->d_csum, (size_t)c->chunk_cap * 2);     // chunk sums of both passes
+        cv.add(c->d_cand_off, ((size_t)K + 2)); cv.add(c->d_final_off, ((size_t)K + 2));
+        cv.add(c->d_cand_y, np8); cv.add(c->d_fixed0, np8); cv.add(c->d_added, np8);
         cv.add(c->d_fixed, np8); cv.add(c->d_chosen, np8);
-        cv.add(c->d_final_y, np8 * 4); cv.add(c->d_final_pos, np8 * 4); cv.add(c->d_final_iv, np8 * 4); cv.add(c->d_col_thr, np8 * 8); cv.add(c->d_col_zero, np8);
-        cv.add(c->d_seg_iv, np8 * 4); cv.add(c->d_seg_prev, np8 * 4); cv.add(c->d_rseg_c, np8 * 4);
-        cv.add(c->d_cand_pn, np8 * 4); cv.add(c->d_cand_ll, np8 * 4); cv.add(c->d_cand_ln, np8 * 4); cv.add(c->d_cand_wide, np8);
-        cv.add(c->d_prob_bs, ((size_t)NPOS / kProbBlock + 2) * kProbCols * 8);
+        cv.add(c->d_final_y, np8); cv.add(c->d_final_pos, np8); cv.add(c->d_final_iv, np8); cv.add(c->d_col_thr, np8); cv.add(c->d_col_zero, np8);
+        cv.add(c->d_seg_iv, np8); cv.add(c->d_seg_prev, np8); cv.add(c->d_rseg_c, np8);
+        cv.add(c->d_cand_pn, np8); cv.add(c->d_cand_ll, np8); cv.add(c->d_cand_ln, np8); cv.add(c->d_cand_wide, np8);
+        cv.add(c->d_prob_bs, ((size_t)NPOS / kProbBlock + 2) * kProbCols);
         TRY(reserve(c, c->slab_pos, cv.total));
-        cv.bind(c->slab_pos);
+        cv.bind(c->slab_pos.p);
         // arena capacities: a sized first run makes them exact; without it (FSEG_NO_SIZED) these are first guesses that
         // finish_run() grows
         atleast(c->prob_cap, 1024); atleast(c->work_cap, 1024); atleast(c->pair_cap, 1 << 16); atleast(c->tri_cap, 1 << 18);
@@ -2142,7 +2137,7 @@ static int unpack_labels(fseg_ctx *c, size_t lb) {
     if (!c->run_label_packed || c->labels_unpacked || lb == 0) return FSEG_OK;
     TRY(ensure(c, c->d_labels, lb + 32));
     const i64 n16 = (i64)((lb + 15) / 16);
-    hipLaunchKernelGGL(k_unpack_labels, dim3(grid_for(n16, 256 * 4, 2048)), dim3(256), 0, c->stream, c->d_packed.as<unsigned>(), c->d_labels.as<uint4>(), n16);
+    hipLaunchKernelGGL(k_unpack_labels, dim3(grid_for(n16, 256 * 4, 2048)), dim3(256), 0, c->stream, c->d_packed.p, c->d_labels.as<uint4>(), n16);
     c->labels_unpacked = true;
     return FSEG_OK;
 }
@@ -2160,12 +2155,13 @@ static int results_impl(fseg_ctx *c, const int64_t **part_final_off, const int32
         const size_t nf = (size_t)c->h_status->n_final, lb = (size_t)c->h_status->label_bytes;
         size_t off = 0;
         auto take = [&](int i, size_t bytes) { c->res_off[i] = off; off = (off + bytes + 255) & ~(size_t)255; };
-        take(0, ((size_t)c->K + 1) * 8); take(1, nf * 4); take(2, ((size_t)c->n_part + 1) * 8); take(3, packed ? (lb + 15) / 16 * 4 : lb);
+        take(0, bytes_of(c->d_final_off, (size_t)c->K + 1)); take(1, bytes_of(c->d_final_pos, nf)); take(2, bytes_of(c->d_label_off, (size_t)c->n_part + 1));
+        take(3, packed ? bytes_of(c->d_packed, (lb + 15) / 16) : lb);
         TRY(reserve_host(c, c->h_res, off));
-        char *h = c->h_res.as<char>();
-        HIP_TRY(c, hipMemcpyAsync(h + c->res_off[0], c->d_final_off.p, ((size_t)c->K + 1) * 8, hipMemcpyDeviceToHost, s));
-        if (nf) HIP_TRY(c, hipMemcpyAsync(h + c->res_off[1], c->d_final_pos.p, nf * 4, hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipMemcpyAsync(h + c->res_off[2], c->d_label_off.p, ((size_t)c->n_part + 1) * 8, hipMemcpyDeviceToHost, s));
+        char *h = c->h_res.p;
+        HIP_TRY(c, hipMemcpyAsync(h + c->res_off[0], c->d_final_off.p, bytes_of(c->d_final_off, (size_t)c->K + 1), hipMemcpyDeviceToHost, s));
+        if (nf) HIP_TRY(c, hipMemcpyAsync(h + c->res_off[1], c->d_final_pos.p, bytes_of(c->d_final_pos, nf), hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipMemcpyAsync(h + c->res_off[2], c->d_label_off.p, bytes_of(c->d_label_off, (size_t)c->n_part + 1), hipMemcpyDeviceToHost, s));
         const void *big_src = nullptr;                       // the label matrix: on SDMA when it is large (see sdma_d2h)
         size_t big_bytes = 0;
         if (lb && !packed) { TRY(unpack_labels(c, lb)); big_src = c->d_labels.p; big_bytes = lb; }
@@ -2173,11 +2169,11 @@ static int results_impl(fseg_ctx *c, const int64_t **part_final_off, const int32
             // (the label arena is allocated with 16 spare bytes: the last, partial group of 16 labels is read whole)
             const i64 n16 = (i64)((lb + 15) / 16);
             if (!c->run_label_packed) {                      // the run wrote bytes (threshold_rate = 1, FSEG_LABEL_BYTES=1): pack them
-                TRY(ensure(c, c->d_packed, (size_t)n16 * 4));
+                TRY(ensure(c, c->d_packed, bytes_of(c->d_packed, (size_t)n16)));
                 hipLaunchKernelGGL(k_pack_labels, dim3(grid_for(n16, 256 * 4, 2048)), dim3(256), 0, s, c->d_labels.as<uint4>(),
-                                   c->d_packed.as<unsigned>(), n16);
+                                   c->d_packed.p, n16);
             }
-            big_src = c->d_packed.p; big_bytes = (size_t)n16 * 4;
+            big_src = c->d_packed.p; big_bytes = bytes_of(c->d_packed, (size_t)n16);
         }
         if (big_bytes >= (1u << 20) && hsa_agents().ok && c->hsa_agent != -2) {
             if (c->pending) TRY(finish_run(c));
@@ -2195,7 +2191,7 @@ static int results_impl(fseg_ctx *c, const int64_t **part_final_off, const int32
         c->fetched = true;
         c->fetched_packed = packed ? 1 : 0;
     }
-    const char *h = c->h_res.as<char>();
+    const char *h = c->h_res.p;
     if (part_final_off) *part_final_off = reinterpret_cast<const int64_t *>(c->res_pfo.data());
     if (final_pos) *final_pos = reinterpret_cast<const int32_t *>(h + c->res_off[1]);
     if (label_off) *label_off = reinterpret_cast<const int64_t *>(h + c->res_off[2]);
@@ -2219,12 +2215,12 @@ int fseg_download(fseg_ctx *c, int64_t *part_final_off, int32_t *final_pos, int6
     hipStream_t s = c->stream;
     if (part_final_off) {
         std::vector<i64> fo((size_t)c->K + 1);
-        HIP_TRY(c, hipMemcpyAsync(fo.data(), c->d_final_off.p, fo.size() * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipMemcpyAsync(fo.data(), c->d_final_off.p, bytes_of(c->d_final_off, fo.size()), hipMemcpyDeviceToHost, s));
         HIP_TRY(c, hipStreamSynchronize(s));
         for (int p = 0; p <= c->n_part; ++p) part_final_off[p] = fo[(size_t)c->part_iv_off[p]];
     }
-    if (final_pos) HIP_TRY(c, hipMemcpyAsync(final_pos, c->d_final_pos.p, (size_t)c->h_status->n_final * 4, hipMemcpyDeviceToHost, s));
-    if (label_off) HIP_TRY(c, hipMemcpyAsync(label_off, c->d_label_off.p, ((size_t)c->n_part + 1) * 8, hipMemcpyDeviceToHost, s));
+    if (final_pos) HIP_TRY(c, hipMemcpyAsync(final_pos, c->d_final_pos.p, bytes_of(c->d_final_pos, (size_t)c->h_status->n_final), hipMemcpyDeviceToHost, s));
+    if (label_off) HIP_TRY(c, hipMemcpyAsync(label_off, c->d_label_off.p, bytes_of(c->d_label_off, (size_t)c->n_part + 1), hipMemcpyDeviceToHost, s));
     if (labels && c->h_status->label_bytes) {
         TRY(unpack_labels(c, (size_t)c->h_status->label_bytes));
         HIP_TRY(c, hipMemcpyAsync(labels, c->d_labels.p, (size_t)c->h_status->label_bytes, hipMemcpyDeviceToHost, s));
@@ -2261,7 +2257,7 @@ static int annotate_impl(fseg_ctx *c, const fseg_reads *rd, const int64_t *label
         return fail(c, FSEG_ERR_ARG, "fseg_annotate: null array");
     const int np = c->n_part;
     // ---- argument checks: everything a kernel indexes with is bounded here
-    const i64 *h_rep_exon_off = reinterpret_cast<const i64 *>(c->h_stage.as<char>() + (static_cast<char *>(c->d_rep_exon_off.p) - static_cast<char *>(c->slab_in.p)));
+    const i64 *h_rep_exon_off = host_of(c, c->d_rep_exon_off);
     if (n > 0 && (rd->seq_off[0] != 0 || rd->read_q_off[0] != 0)) return fail(c, FSEG_ERR_ARG, "fseg_annotate: read 0: offsets must start at 0");
     for (i64 r = 0; r < n; ++r) {
         const int p = rd->read_part[r], rep = rd->read_rep[r];
@@ -2296,103 +2292,115 @@ static int annotate_impl(fseg_ctx *c, const fseg_reads *rd, const int64_t *label
     }
     hipStream_t s = c->stream;
     // ---- the inputs: one pinned image, one copy
-    DevBuf i_part, i_rep, i_strand, i_slen, i_soff, i_qoff, i_qs, i_qe, i_coff, i_cop, i_clen, i_cls, i_pfo, i_fp, i_loff, i_lab;
+    DevBuf<int> i_part, i_rep, i_slen, i_qs, i_qe, i_clen, i_fp;
+    DevBuf<unsigned char> i_strand, i_cop;
+    DevBuf<i64> i_soff, i_qoff, i_coff, i_pfo, i_loff;
+    DevBuf<unsigned> i_cls, i_lab;           // 16 sequence classes / 16 labels a word
     Carve in;
     const size_t cls_words = (size_t)((NL + 15) / 16), lab_bytes = (size_t)((n_label + 3) / 4), lab_words = (size_t)((n_label + 15) / 16);
-    in.add(i_part, (size_t)n * 4); in.add(i_rep, (size_t)n * 4); in.add(i_strand, (size_t)n); in.add(i_slen, (size_t)n * 4);
-    in.add(i_soff, ((size_t)n + 1) * 8); in.add(i_qoff, ((size_t)n + 1) * 8); in.add(i_qs, (size_t)NQ * 4); in.add(i_qe, (size_t)NQ * 4);
-    in.add(i_coff, ((size_t)NQ + 1) * 8); in.add(i_cop, (size_t)NC); in.add(i_clen, (size_t)NC * 4); in.add(i_cls, cls_words * 4);
-    in.add(i_pfo, ((size_t)np + 1) * 8);
-    if (given) { in.add(i_fp, (size_t)n_final * 4); in.add(i_loff, ((size_t)np + 1) * 8); in.add(i_lab, lab_words * 4); }
+    in.add(i_part, (size_t)n); in.add(i_rep, (size_t)n); in.add(i_strand, (size_t)n); in.add(i_slen, (size_t)n);
+    in.add(i_soff, (size_t)n + 1); in.add(i_qoff, (size_t)n + 1); in.add(i_qs, (size_t)NQ); in.add(i_qe, (size_t)NQ);
+    in.add(i_coff, (size_t)NQ + 1); in.add(i_cop, (size_t)NC); in.add(i_clen, (size_t)NC); in.add(i_cls, cls_words);
+    in.add(i_pfo, (size_t)np + 1);
+    if (given) { in.add(i_fp, (size_t)n_final); in.add(i_loff, (size_t)np + 1); in.add(i_lab, lab_words); }
     TRY(ensure(c, c->d_an_in, in.total + 256));
     TRY(reserve_host(c, c->h_an_in, in.total + 256));
-    { Slab sl; sl.p = c->d_an_in.p; sl.cap = c->d_an_in.cap; in.bind(sl); }
-    char *hin = c->h_an_in.as<char>();
-    auto put = [&](const DevBuf &d, const void *src, size_t bytes) {
-        if (bytes) memcpy(hin + (static_cast<char *>(d.p) - static_cast<char *>(c->d_an_in.p)), src, bytes);
+    in.bind(c->d_an_in.p);
+    char *hin = c->h_an_in.p;
+    auto put = [&](const auto &d, const void *src, size_t n_el) {
+        if (n_el) memcpy(mirror_of(hin, c->d_an_in.p, d), src, d.bytes(n_el));
     };
-    put(i_part, rd->read_part, (size_t)n * 4); put(i_rep, rd->read_rep, (size_t)n * 4); put(i_strand, rd->strand, (size_t)n);
-    put(i_slen, rd->seq_len, (size_t)n * 4);
+    put(i_part, rd->read_part, (size_t)n); put(i_rep, rd->read_rep, (size_t)n); put(i_strand, rd->strand, (size_t)n);
+    put(i_slen, rd->seq_len, (size_t)n);
     const i64 zero = 0;
-    put(i_soff, n ? (const void *)rd->seq_off : &zero, ((size_t)n + 1) * 8); put(i_qoff, n ? (const void *)rd->read_q_off : &zero, ((size_t)n + 1) * 8);
-    put(i_qs, rd->qs, (size_t)NQ * 4); put(i_qe, rd->qe, (size_t)NQ * 4);
-    put(i_coff, NQ ? (const void *)rd->cig_off : &zero, ((size_t)NQ + 1) * 8); put(i_cop, rd->cig_op, (size_t)NC); put(i_clen, rd->cig_len, (size_t)NC * 4);
-    put(i_cls, rd->seq_classes, cls_words * 4);
+    put(i_soff, n ? (const void *)rd->seq_off : &zero, (size_t)n + 1); put(i_qoff, n ? (const void *)rd->read_q_off : &zero, (size_t)n + 1);
+    put(i_qs, rd->qs, (size_t)NQ); put(i_qe, rd->qe, (size_t)NQ);
+    put(i_coff, NQ ? (const void *)rd->cig_off : &zero, (size_t)NQ + 1); put(i_cop, rd->cig_op, (size_t)NC); put(i_clen, rd->cig_len, (size_t)NC);
+    put(i_cls, rd->seq_classes, cls_words);
     if (given) {
-        put(i_pfo, part_final_off, ((size_t)np + 1) * 8); put(i_fp, final_pos, (size_t)n_final * 4); put(i_loff, label_off, ((size_t)np + 1) * 8);
-        if (lab_words) memset(hin + (static_cast<char *>(i_lab.p) - static_cast<char *>(c->d_an_in.p)), 0, lab_words * 4);     // the caller's array ends with its last byte
-        put(i_lab, labels2, lab_bytes);
+        put(i_pfo, part_final_off, (size_t)np + 1); put(i_fp, final_pos, (size_t)n_final); put(i_loff, label_off, (size_t)np + 1);
+        if (lab_words) {                     // the caller's array ends with its last byte, the image with a whole word
+            unsigned *h_lab = mirror_of(hin, c->d_an_in.p, i_lab);
+            memset(h_lab, 0, i_lab.bytes(lab_words));
+            memcpy(h_lab, labels2, lab_bytes);
+        }
     }
     HIP_TRY(c, hipMemcpyAsync(c->d_an_in.p, hin, in.total, hipMemcpyHostToDevice, s));
     // ---- work arrays
     const i64 nb = (n + kAnScanItemsPerBlock - 1) / kAnScanItemsPerBlock;
-    DevBuf w_cnt, w_ends, w_poly, w_off, w_tok_off, w_tail, w_status, w_bad, w_bsum;
+    DevBuf<int> w_cnt, w_status;
+    DevBuf<int4> w_ends, w_poly;
+    DevBuf<i64> w_off, w_tok_off, w_bsum;
+    DevBuf<unsigned char> w_tail;
+    DevBuf<unsigned long long> w_bad;
     Carve wk;
-    wk.add(w_cnt, (size_t)n * 8); wk.add(w_ends, (size_t)n * 16); wk.add(w_poly, (size_t)n * 32); wk.add(w_off, ((size_t)n + 1) * 24);
-    wk.add(w_tok_off, ((size_t)n + 1) * 8); wk.add(w_tail, (size_t)n); wk.add(w_status, (size_t)n * 4); wk.add(w_bad, 8); wk.add(w_bsum, (size_t)nb * 24 + 8);
+    wk.add(w_cnt, (size_t)n * 2); wk.add(w_ends, (size_t)n); wk.add(w_poly, (size_t)n * 2); wk.add(w_off, ((size_t)n + 1) * 3);
+    wk.add(w_tok_off, (size_t)n + 1); wk.add(w_tail, (size_t)n); wk.add(w_status, (size_t)n); wk.add(w_bad, 1); wk.add(w_bsum, (size_t)nb * 3 + 1);
     TRY(ensure(c, c->d_an_work, wk.total + 256));
-    { Slab sl; sl.p = c->d_an_work.p; sl.cap = c->d_an_work.cap; wk.bind(sl); }
+    wk.bind(c->d_an_work.p);
     AnnotIn a{};
     a.n_read = n;
-    a.read_part = i_part.as<int>(); a.read_rep = i_rep.as<int>(); a.strand = i_strand.as<unsigned char>(); a.seq_len = i_slen.as<int>();
-    a.seq_off = i_soff.as<i64>(); a.read_q_off = i_qoff.as<i64>(); a.qs = i_qs.as<int>(); a.qe = i_qe.as<int>(); a.cig_off = i_coff.as<i64>();
-    a.cig_op = i_cop.as<unsigned char>(); a.cig_len = i_clen.as<int>(); a.seq_cls = i_cls.as<unsigned>();
-    a.part_rep_off = c->d_part_rep_off.as<i64>(); a.rep_exon_off = c->d_rep_exon_off.as<i64>(); a.ex_ts = c->d_ex_ts.as<int>(); a.ex_te = c->d_ex_te.as<int>();
-    a.pfo = i_pfo.as<i64>();
-    if (given) { a.final_pos = i_fp.as<int>(); a.label_off = i_loff.as<i64>(); a.lab2 = i_lab.as<unsigned>(); a.lab1 = nullptr; }
+    a.read_part = i_part.p; a.read_rep = i_rep.p; a.strand = i_strand.p; a.seq_len = i_slen.p;
+    a.seq_off = i_soff.p; a.read_q_off = i_qoff.p; a.qs = i_qs.p; a.qe = i_qe.p; a.cig_off = i_coff.p;
+    a.cig_op = i_cop.p; a.cig_len = i_clen.p; a.seq_cls = i_cls.p;
+    a.part_rep_off = c->d_part_rep_off.p; a.rep_exon_off = c->d_rep_exon_off.p; a.ex_ts = c->d_ex_ts.p; a.ex_te = c->d_ex_te.p;
+    a.pfo = i_pfo.p;
+    if (given) { a.final_pos = i_fp.p; a.label_off = i_loff.p; a.lab2 = i_lab.p; a.lab1 = nullptr; }
     else {
-        hipLaunchKernelGGL(k_an_pfo, dim3(grid_for(np + 1, 256, 65536)), dim3(256), 0, s, np, c->d_part_iv_off.as<i64>(), c->d_final_off.as<i64>(), i_pfo.as<i64>());
-        a.final_pos = c->d_final_pos.as<int>(); a.label_off = c->d_label_off.as<i64>();
-        a.lab2 = c->run_label_packed ? c->d_packed.as<unsigned>() : nullptr;
+        hipLaunchKernelGGL(k_an_pfo, dim3(grid_for(np + 1, 256, 65536)), dim3(256), 0, s, np, c->d_part_iv_off.p, c->d_final_off.p, i_pfo.p);
+        a.final_pos = c->d_final_pos.p; a.label_off = c->d_label_off.p;
+        a.lab2 = c->run_label_packed ? c->d_packed.p : nullptr;
         a.lab1 = c->run_label_packed ? nullptr : c->d_labels.as<unsigned char>();
     }
     AnnotOut o{};
-    o.cnt = w_cnt.as<int>(); o.ends = w_ends.as<int4>(); o.poly = w_poly.as<int4>(); o.off = w_off.as<i64>(); o.tok_off = w_tok_off.as<i64>();
-    o.tail = w_tail.as<unsigned char>(); o.status = w_status.as<int>(); o.first_bad = w_bad.as<unsigned long long>();
+    o.cnt = w_cnt.p; o.ends = w_ends.p; o.poly = w_poly.p; o.off = w_off.p; o.tok_off = w_tok_off.p;
+    o.tail = w_tail.p; o.status = w_status.p; o.first_bad = w_bad.p;
     // pinned results: offsets and the per-read bytes first (their sizes are known), the lists behind them
     size_t hoff[9], htotal = 0;
     auto take = [&](int i, size_t bytes) { hoff[i] = htotal; htotal = (htotal + bytes + 255) & ~(size_t)255; };
-    take(0, ((size_t)n + 1) * 8); take(1, ((size_t)n + 1) * 8); take(2, ((size_t)n + 1) * 8); take(3, ((size_t)n + 1) * 8); take(4, (size_t)n + 8);
+    const size_t off_bytes = bytes_of(w_tok_off, (size_t)n + 1);     // one list of offsets: those of w_off and w_tok_off
+    take(0, off_bytes); take(1, off_bytes); take(2, off_bytes); take(3, off_bytes); take(4, (size_t)n + 8);
     const size_t head = htotal;
     TRY(reserve_host(c, c->h_an, head + 4096));
-    i64 *totals = reinterpret_cast<i64 *>(c->h_an.as<char>());       // (scratch until the results land)
+    i64 *totals = reinterpret_cast<i64 *>(c->h_an.p);       // (scratch until the results land)
     totals[0] = totals[1] = totals[2] = 0;
-    unsigned long long *h_bad = reinterpret_cast<unsigned long long *>(c->h_an.as<char>() + 64);
+    unsigned long long *h_bad = reinterpret_cast<unsigned long long *>(c->h_an.p + 64);
     *h_bad = ~0ull;
     if (n > 0) {
         HIP_TRY(c, hipMemsetAsync(w_bad.p, 0xff, 8, s));
         const int g = grid_for(n, 256, 65536);
         hipLaunchKernelGGL(k_an_count, dim3(g), dim3(256), 0, s, a, o);
         hipLaunchKernelGGL(k_an_poly, dim3(grid_for(2 * n, 256, 65536)), dim3(256), 0, s, a, o);
-        hipLaunchKernelGGL(k_an_scan1, dim3((unsigned)nb, 3), dim3(256), 0, s, o.cnt, o.poly, n, nb, w_bsum.as<i64>());
-        hipLaunchKernelGGL(k_an_scan2, dim3(3), dim3(256), 0, s, nb, w_bsum.as<i64>());
-        hipLaunchKernelGGL(k_an_scan3, dim3((unsigned)nb, 3), dim3(256), 0, s, o.cnt, o.poly, n, nb, w_bsum.as<i64>(), o.off);
-        for (int k = 0; k < 3; ++k) HIP_TRY(c, hipMemcpyAsync(&totals[k], o.off + (size_t)k * ((size_t)n + 1) + (size_t)n, 8, hipMemcpyDeviceToHost, s));
+        hipLaunchKernelGGL(k_an_scan1, dim3((unsigned)nb, 3), dim3(256), 0, s, o.cnt, o.poly, n, nb, w_bsum.p);
+        hipLaunchKernelGGL(k_an_scan2, dim3(3), dim3(256), 0, s, nb, w_bsum.p);
+        hipLaunchKernelGGL(k_an_scan3, dim3((unsigned)nb, 3), dim3(256), 0, s, o.cnt, o.poly, n, nb, w_bsum.p, o.off);
+        for (int k = 0; k < 3; ++k) HIP_TRY(c, hipMemcpyAsync(&totals[k], o.off + (size_t)k * ((size_t)n + 1) + (size_t)n, sizeof(i64), hipMemcpyDeviceToHost, s));
         HIP_TRY(c, hipGetLastError());
         HIP_TRY(c, hipStreamSynchronize(s));
     }
     const i64 G = totals[0], C = totals[1], Pn = totals[2];
-    DevBuf o_gaps, o_clips, o_polys, o_tok;
+    DevBuf<int> o_gaps, o_clips, o_polys;
+    DevBuf<unsigned> o_tok;
     Carve ov;
-    ov.add(o_gaps, (size_t)G * 12); ov.add(o_clips, (size_t)C * 8); ov.add(o_polys, (size_t)Pn * 12); ov.add(o_tok, (size_t)(G + Pn) * 4);
+    ov.add(o_gaps, (size_t)G * 3); ov.add(o_clips, (size_t)C * 2); ov.add(o_polys, (size_t)Pn * 3); ov.add(o_tok, (size_t)(G + Pn));
     TRY(ensure(c, c->d_an_out, ov.total + 256));
-    { Slab sl; sl.p = c->d_an_out.p; sl.cap = c->d_an_out.cap; ov.bind(sl); }
-    o.gaps = o_gaps.as<int>(); o.clips = o_clips.as<int>(); o.polys = o_polys.as<int>(); o.tok = o_tok.as<unsigned>();
-    take(5, (size_t)G * 12); take(6, (size_t)C * 8); take(7, (size_t)Pn * 12); take(8, (size_t)(G + Pn) * 4);
+    ov.bind(c->d_an_out.p);
+    o.gaps = o_gaps.p; o.clips = o_clips.p; o.polys = o_polys.p; o.tok = o_tok.p;
+    take(5, o_gaps.cap); take(6, o_clips.cap); take(7, o_polys.cap); take(8, o_tok.cap);
     TRY(reserve_host(c, c->h_an, htotal + 4096));
-    char *h = c->h_an.as<char>();
+    char *h = c->h_an.p;
     if (n > 0) {
         hipLaunchKernelGGL(k_an_emit, dim3(grid_for(n, 256, 65536)), dim3(256), 0, s, a, o);
         HIP_TRY(c, hipGetLastError());
         unsigned long long *bad = reinterpret_cast<unsigned long long *>(h + htotal);
         HIP_TRY(c, hipMemcpyAsync(bad, w_bad.p, 8, hipMemcpyDeviceToHost, s));
-        for (int k = 0; k < 3; ++k) HIP_TRY(c, hipMemcpyAsync(h + hoff[k], o.off + (size_t)k * ((size_t)n + 1), ((size_t)n + 1) * 8, hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipMemcpyAsync(h + hoff[3], o.tok_off, ((size_t)n + 1) * 8, hipMemcpyDeviceToHost, s));
+        for (int k = 0; k < 3; ++k) HIP_TRY(c, hipMemcpyAsync(h + hoff[k], o.off + (size_t)k * ((size_t)n + 1), off_bytes, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipMemcpyAsync(h + hoff[3], o.tok_off, off_bytes, hipMemcpyDeviceToHost, s));
         HIP_TRY(c, hipMemcpyAsync(h + hoff[4], o.tail, (size_t)n, hipMemcpyDeviceToHost, s));
-        if (G) HIP_TRY(c, hipMemcpyAsync(h + hoff[5], o.gaps, (size_t)G * 12, hipMemcpyDeviceToHost, s));
-        if (C) HIP_TRY(c, hipMemcpyAsync(h + hoff[6], o.clips, (size_t)C * 8, hipMemcpyDeviceToHost, s));
-        if (Pn) HIP_TRY(c, hipMemcpyAsync(h + hoff[7], o.polys, (size_t)Pn * 12, hipMemcpyDeviceToHost, s));
-        if (G + Pn) HIP_TRY(c, hipMemcpyAsync(h + hoff[8], o.tok, (size_t)(G + Pn) * 4, hipMemcpyDeviceToHost, s));
+        if (G) HIP_TRY(c, hipMemcpyAsync(h + hoff[5], o.gaps, o_gaps.cap, hipMemcpyDeviceToHost, s));
+        if (C) HIP_TRY(c, hipMemcpyAsync(h + hoff[6], o.clips, o_clips.cap, hipMemcpyDeviceToHost, s));
+        if (Pn) HIP_TRY(c, hipMemcpyAsync(h + hoff[7], o.polys, o_polys.cap, hipMemcpyDeviceToHost, s));
+        if (G + Pn) HIP_TRY(c, hipMemcpyAsync(h + hoff[8], o.tok, o_tok.cap, hipMemcpyDeviceToHost, s));
         HIP_TRY(c, hipStreamSynchronize(s));
         if (*bad != ~0ull) {
             const i64 r = (i64)*bad;
@@ -2432,74 +2440,64 @@ int fseg_tap(fseg_ctx *c, int what, void *dst, int64_t cap_bytes, int64_t *n_byt
     TRY(fseg_sync(c));
     if (!c->ran) return fail(c, FSEG_ERR_ARG, "no completed run");
     const Status &st = *c->h_status;
-    const void *src = nullptr;
-    i64 bytes = 0;
-    std::vector<int> packed;
+    auto from_dev = [&](const auto &buf, i64 n) -> int {     // n elements of a device buffer
+        const i64 bytes = (i64)buf.bytes((size_t)n);
+        *n_bytes = bytes;
+        if (dst && cap_bytes > 0 && bytes > 0) HIP_TRY(c, copy_sync(c, dst, buf.p, (size_t)(bytes < cap_bytes ? bytes : cap_bytes), hipMemcpyDeviceToHost));
+        return FSEG_OK;
+    };
+    auto from_host = [&](const void *words, size_t bytes) {  // a tap that the host puts together
+        *n_bytes = (i64)bytes;
+        if (dst && cap_bytes > 0) memcpy(dst, words, bytes < (size_t)cap_bytes ? bytes : (size_t)cap_bytes);
+        return FSEG_OK;
+    };
     switch (what) {
-        case FSEG_TAP_POS_OFF: src = c->d_pos_off.p; bytes = (c->K + 1) * 8; break;
+        case FSEG_TAP_POS_OFF: return from_dev(c->d_pos_off, c->K + 1);
         case FSEG_TAP_Y_RAW: {                                             // int32 whatever the device holds: uint16 is widened here
-            bytes = c->NPOS * 4;
-            if (!c->yraw_narrow) { src = c->d_y_raw.p; break; }
+            if (!c->yraw_narrow) return from_dev(DevBuf<int32_t>{c->d_y_raw.as<int32_t>()}, c->NPOS);
+            const i64 bytes = (i64)DevBuf<int32_t>::bytes((size_t)c->NPOS);
             *n_bytes = bytes;
             if (dst && cap_bytes > 0 && bytes > 0) {
                 std::vector<uint16_t> narrow((size_t)c->NPOS);
-                HIP_TRY(c, copy_sync(c, narrow.data(), c->d_y_raw.p, narrow.size() * 2, hipMemcpyDeviceToHost));
-                const i64 n = (bytes < cap_bytes ? bytes : cap_bytes) / 4;
+                HIP_TRY(c, copy_sync(c, narrow.data(), c->d_y_raw.p, narrow.size() * sizeof(uint16_t), hipMemcpyDeviceToHost));
+                const i64 n = (bytes < cap_bytes ? bytes : cap_bytes) / (i64)sizeof(int32_t);
                 for (i64 i = 0; i < n; ++i) static_cast<int32_t *>(dst)[i] = (int32_t)narrow[(size_t)i];
             }
             return FSEG_OK;
         }
-        case FSEG_TAP_Y: src = c->d_y.p; bytes = c->NPOS * 8; break;
-        case FSEG_TAP_THRESHOLD: src = c->d_thr.p; bytes = (i64)c->n_part * 8; break;
-        case FSEG_TAP_CAND_OFF: src = c->d_cand_off.p; bytes = (c->K + 1) * 8; break;
-        case FSEG_TAP_CAND_Y: src = c->d_cand_y.p; bytes = (i64)st.n_cand * 4; break;
-        case FSEG_TAP_FIXED: src = c->d_fixed.p; bytes = (i64)st.n_cand; break;
-        case FSEG_TAP_CHOSEN: src = c->d_chosen.p; bytes = (i64)st.n_cand; break;
-        case FSEG_TAP_FINAL_OFF: src = c->d_final_off.p; bytes = (c->K + 1) * 8; break;
-        case FSEG_TAP_FINAL_Y: src = c->d_final_y.p; bytes = (i64)st.n_final * 4; break;
-        case FSEG_TAP_PROBLEMS: {
-            size_t n = (size_t)st.n_prob;
-            std::vector<int> iv(n), sa(n), nn(n), ch(n);
-            if (n) {
-                HIP_TRY(c, copy_sync(c, iv.data(), c->d_prob_iv.p, n * 4, hipMemcpyDeviceToHost));
-                HIP_TRY(c, copy_sync(c, sa.data(), c->d_prob_start.p, n * 4, hipMemcpyDeviceToHost));
-                HIP_TRY(c, copy_sync(c, nn.data(), c->d_prob_n.p, n * 4, hipMemcpyDeviceToHost));
-                HIP_TRY(c, copy_sync(c, ch.data(), c->d_prob_chain.p, n * 4, hipMemcpyDeviceToHost));
+        case FSEG_TAP_Y: return from_dev(c->d_y, c->NPOS);
+        case FSEG_TAP_THRESHOLD: return from_dev(c->d_thr, c->n_part);
+        case FSEG_TAP_CAND_OFF: return from_dev(c->d_cand_off, c->K + 1);
+        case FSEG_TAP_CAND_Y: return from_dev(c->d_cand_y, (i64)st.n_cand);
+        case FSEG_TAP_FIXED: return from_dev(c->d_fixed, (i64)st.n_cand);
+        case FSEG_TAP_CHOSEN: return from_dev(c->d_chosen, (i64)st.n_cand);
+        case FSEG_TAP_FINAL_OFF: return from_dev(c->d_final_off, c->K + 1);
+        case FSEG_TAP_FINAL_Y: return from_dev(c->d_final_y, (i64)st.n_final);
+        case FSEG_TAP_PROBLEMS: {                                          // a row per problem: interval, first candidate, candidates, chain
+            const size_t n = (size_t)st.n_prob;
+            const DevBuf<int> *cols[4] = {&c->d_prob_iv, &c->d_prob_start, &c->d_prob_n, &c->d_prob_chain};
+            std::vector<int> col(n), rows(n * 4);
+            for (int k = 0; k < 4 && n; ++k) {
+                HIP_TRY(c, copy_sync(c, col.data(), cols[k]->p, bytes_of(*cols[k], n), hipMemcpyDeviceToHost));
+                for (size_t i = 0; i < n; ++i) rows[4 * i + k] = col[i];
             }
-            packed.resize(n * 4);
-            for (size_t i = 0; i < n; ++i) { packed[4 * i] = iv[i]; packed[4 * i + 1] = sa[i]; packed[4 * i + 2] = nn[i]; packed[4 * i + 3] = ch[i]; }
-            bytes = (i64)n * 16;
-            *n_bytes = bytes;
-            if (dst && cap_bytes > 0) memcpy(dst, packed.data(), (size_t)(bytes < cap_bytes ? bytes : cap_bytes));
-            return FSEG_OK;
+            return from_host(rows.data(), rows.size() * sizeof(int));
         }
-        case FSEG_TAP_LANE_START: src = c->d_lane_start.p; bytes = c->LANES * 4; break;
-        case FSEG_TAP_LANE_PMAX: src = c->d_lane_pmax.p; bytes = c->LANES * 4; break;
-        case FSEG_TAP_LANE_EXONS: src = c->d_lane_ex.p; bytes = c->LANES * 16; break;
-        case FSEG_TAP_LANE_STREAM: src = c->d_lane_lx.p; bytes = c->LANES * 8; break;
-        case FSEG_TAP_EXON_STREAM: src = c->d_lex.p; bytes = c->I * 8; break;
+        case FSEG_TAP_LANE_START: return from_dev(c->d_lane_start, c->LANES);
+        case FSEG_TAP_LANE_PMAX: return from_dev(c->d_lane_pmax, c->LANES);
+        case FSEG_TAP_LANE_EXONS: return from_dev(c->d_lane_ex, c->LANES);
+        case FSEG_TAP_LANE_STREAM: return from_dev(c->d_lane_lx, c->LANES);
+        case FSEG_TAP_EXON_STREAM: return from_dev(c->d_lex, c->I);
         case FSEG_TAP_SYNC: {
             SyncWords w{};
             HIP_TRY(c, copy_sync(c, &w, c->d_sync.p, sizeof w, hipMemcpyDeviceToHost));
-            packed = {(int)c->sync_gen, c->dev_sync ? 1 : 0, (int)w.emit_gen, (int)w.side_gen[0], (int)w.side_gen[1], (int)w.emit_ctr,
-                      (int)c->sync_timeouts, (int)c->forked_runs, (c->side_probed ? 8 : 0) | (c->side_ok[0] ? 1 : 0) | (c->side_ok[1] ? 2 : 0) | (c->side_ok[2] ? 4 : 0)};
-            bytes = (i64)packed.size() * 4;
-            *n_bytes = bytes;
-            if (dst && cap_bytes > 0) memcpy(dst, packed.data(), (size_t)(bytes < cap_bytes ? bytes : cap_bytes));
-            return FSEG_OK;
+            const int words[] = {(int)c->sync_gen, c->dev_sync ? 1 : 0, (int)w.emit_gen, (int)w.side_gen[0], (int)w.side_gen[1], (int)w.emit_ctr,
+                                 (int)c->sync_timeouts, (int)c->forked_runs, (c->side_probed ? 8 : 0) | (c->side_ok[0] ? 1 : 0) | (c->side_ok[1] ? 2 : 0) | (c->side_ok[2] ? 4 : 0)};
+            return from_host(words, sizeof words);
         }
-        case FSEG_TAP_PATHS: {
-            bytes = (i64)sizeof c->paths;
-            *n_bytes = bytes;
-            if (dst && cap_bytes > 0) memcpy(dst, c->paths, (size_t)(bytes < cap_bytes ? bytes : cap_bytes));
-            return FSEG_OK;
-        }
+        case FSEG_TAP_PATHS: return from_host(c->paths, sizeof c->paths);
         default: return fail(c, FSEG_ERR_ARG, "unknown tap %d", what);
     }
-    *n_bytes = bytes;
-    if (dst && cap_bytes > 0 && bytes > 0)
-        HIP_TRY(c, copy_sync(c, dst, src, (size_t)(bytes < cap_bytes ? bytes : cap_bytes), hipMemcpyDeviceToHost));
-    return FSEG_OK;
 }
 
 int fseg_set_profiling(fseg_ctx *c, int on) {
@@ -2528,17 +2526,17 @@ int fseg_debug_score_timing(fseg_ctx *c, unsigned long long *out8) {
 }
 int fseg_debug_prob_ticks(fseg_ctx *c, unsigned long long *out4, long long n_prob) {     /* 4 values per problem */
     if (!c || !out4 || n_prob < 0 || (size_t)n_prob > kTaccProbs) return FSEG_ERR_ARG;
-    if (copy_sync(c, out4, static_cast<char *>(c->d_tacc.p) + 128, (size_t)n_prob * 32, hipMemcpyDeviceToHost) != hipSuccess) return FSEG_ERR_HIP;
+    if (copy_sync(c, out4, reinterpret_cast<char *>(c->d_tacc.p) + 128, (size_t)n_prob * 32, hipMemcpyDeviceToHost) != hipSuccess) return FSEG_ERR_HIP;
     return FSEG_OK;
 }
 int fseg_debug_dp_ticks(fseg_ctx *c, unsigned long long *out4, long long n_prob) {       /* k_dpw's records: (ticks, -, -, start tick) */
     if (!c || !out4 || n_prob < 0 || (size_t)n_prob > kTaccProbs) return FSEG_ERR_ARG;
-    if (copy_sync(c, out4, static_cast<char *>(c->d_tacc.p) + 128 + kTaccProbs * 32, (size_t)n_prob * 32, hipMemcpyDeviceToHost) != hipSuccess) return FSEG_ERR_HIP;
+    if (copy_sync(c, out4, reinterpret_cast<char *>(c->d_tacc.p) + 128 + kTaccProbs * 32, (size_t)n_prob * 32, hipMemcpyDeviceToHost) != hipSuccess) return FSEG_ERR_HIP;
     return FSEG_OK;
 }
 int fseg_debug_timed_class(fseg_ctx *c, int cls) {
     unsigned long long v = (unsigned long long)(long long)cls;
-    if (!c || copy_sync(c, static_cast<char *>(c->d_tacc.p) + 120, &v, 8, hipMemcpyHostToDevice) != hipSuccess) return FSEG_ERR_HIP;
+    if (!c || copy_sync(c, reinterpret_cast<char *>(c->d_tacc.p) + 120, &v, 8, hipMemcpyHostToDevice) != hipSuccess) return FSEG_ERR_HIP;
     return FSEG_OK;
 }
 #endif
@@ -2547,7 +2545,7 @@ int64_t fseg_scoring_algorithmic_bytes(fseg_ctx *c) {
     if (!c || !c->ran) return -1;
     // per partition 4*(N_p + K_p)*R_p + 4*R_p, R_p = read reps
     std::vector<i64> co((size_t)c->K + 1);
-    if (copy_sync(c, co.data(), c->d_cand_off.p, co.size() * 8, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    if (copy_sync(c, co.data(), c->d_cand_off.p, bytes_of(c->d_cand_off, co.size()), hipMemcpyDeviceToHost) != hipSuccess) return -1;
     i64 total = 0;
     for (int p = 0; p < c->n_part; ++p) {
         i64 Np = co[(size_t)c->part_iv_off[p + 1]] - co[(size_t)c->part_iv_off[p]];
