@@ -116,6 +116,7 @@ struct fseg_ctx {
     int thr_part = -1;         // FSEG_THR_PART=0 / 1: the threshold per partition by one workgroup (k_thr_part) never / whenever possible; -1: batches of many partitions
     int hist16 = -1;           // FSEG_HIST16=0 / 1: S1 with 32-bit LDS counters always / with packed 16-bit ones wherever no count can overflow; -1: the same as 1
     bool hist_packed = false;  // the resident batch's chunks were planned for k_hist<16> (kHistChunk16 positions, every count <= 65 535)
+    int thr_chain = -1;        // FSEG_THR_CHAIN=0 / 1: k_thr_part as it was / k_thr_part_chain (the same additions, a shorter chain per partition); -1: the same as 1
     int yraw16 = -1;           // FSEG_YRAW16=0 / 1: the histogram in device memory int32 always / uint16 wherever S1 runs packed; -1: the same as 1
     bool yraw_narrow = false;  // the resident batch's d_y_raw holds uint16 (hist_packed and the switch): S1's output, S2's and S6's input
     i64 max_part_lanes = 0;    // reads of the batch's largest partition (what bounds a DP sum: 32-bit keys below 2^18)
@@ -300,7 +301,7 @@ struct fseg_ctx {
     enum { PATH_SMALL_BATCH, PATH_TINY_ON, PATH_WAVE_ON, PATH_FUSE_ON, PATH_KEY32, PATH_THR_PART, PATH_LABEL_PACKED, PATH_N_SOLVE,
            PATH_N_WIDE = PATH_N_SOLVE + 3, PATH_N_TINY = PATH_N_WIDE + 3, PATH_N_WORK, PATH_DPW, PATH_WIDE16, PATH_KNOWN, PATH_SOLVE8,
            PATH_TINY_KERNEL, PATH_SCORE, PATH_ARENA_DP, PATH_PLAN, PATH_N_ARENA_PROB, PATH_N_SCORE, PATH_HIST16 = PATH_N_SCORE + 3, PATH_IV_THREADS,
-           PATH_SMOOTH_R, PATH_YRAW16, PATH_WORDS };
+           PATH_SMOOTH_R, PATH_YRAW16, PATH_THR_CHAIN, PATH_WORDS };
     int paths[PATH_WORDS] = {};
     // fseg_annotate: the uploaded reads (one allocation, mirrored by a pinned image), per-read work arrays, the emitted lists, and
     // the pinned buffers fseg_annotation() points into (own allocations: nothing of a run or of fseg_results* touches them)
@@ -666,10 +667,16 @@ int enqueue_run(fseg_ctx *c, unsigned segs, bool sized = false, i64 label_fill_b
     const bool thr_part = thr_part_fits && (c->thr_part == 1 || (c->thr_part < 0 && n_part >= 64));
     if (thr_part) {
         c->paths[fseg_ctx::PATH_THR_PART] = 1;
+        c->paths[fseg_ctx::PATH_THR_CHAIN] = c->thr_chain != 0;
+        if (c->thr_chain != 0)
+            hipLaunchKernelGGL(k_thr_part_chain<kThrChainLevel>, dim3(grid_for(n_part, 1, 4096)), dim3(512), 0, q, n_part, c->d_part_iv_off.p,
+                               c->d_pos_off.p, NPOS, flag_pos_bits, c->d_y.p, c->d_v.p, c->P.variance_factor, c->d_mean.p, c->d_thr.p);
+        else
         hipLaunchKernelGGL(k_thr_part, dim3(grid_for(n_part, 1, 4096)), dim3(512), 0, q, n_part, c->d_part_iv_off.p, c->d_pos_off.p, NPOS,
                            flag_pos_bits, c->d_y.p, c->d_v.p, c->P.variance_factor, c->d_mean.p, c->d_thr.p);
     } else {
     c->paths[fseg_ctx::PATH_THR_PART] = 0;
+    c->paths[fseg_ctx::PATH_THR_CHAIN] = 0;
     scan_counts(q, bsum_side, flag_pos_bits, &st->n_vals, nullptr);
     hipLaunchKernelGGL(k_scan_emit<kEmitValues>, dim3(scan_grid), dim3(256), 0, q, flag_pos_bits, NPOS,
                        bsum_side, (const int *)nullptr, scan_state, &st->n_vals, (i64 *)nullptr, &st->err, c->d_y.p, c->d_v.p, K, c->d_pos_off.p,
@@ -765,7 +772,7 @@ int enqueue_run(fseg_ctx *c, unsigned segs, bool sized = false, i64 label_fill_b
     if (do_score) {
         for (int w = 0; w < fseg_ctx::PATH_WORDS; ++w)
             if (w != fseg_ctx::PATH_THR_PART && w != fseg_ctx::PATH_LABEL_PACKED && w != fseg_ctx::PATH_ARENA_DP && w != fseg_ctx::PATH_HIST16 &&
-                w != fseg_ctx::PATH_IV_THREADS && w != fseg_ctx::PATH_SMOOTH_R && w != fseg_ctx::PATH_YRAW16) census[w] = 0;
+                w != fseg_ctx::PATH_IV_THREADS && w != fseg_ctx::PATH_SMOOTH_R && w != fseg_ctx::PATH_YRAW16 && w != fseg_ctx::PATH_THR_CHAIN) census[w] = 0;
         census[fseg_ctx::PATH_SMALL_BATCH] = c->small_batch; census[fseg_ctx::PATH_TINY_ON] = c->tiny_on; census[fseg_ctx::PATH_WAVE_ON] = wave;
         census[fseg_ctx::PATH_FUSE_ON] = c->use_fuse && c->fuse_on; census[fseg_ctx::PATH_KNOWN] = known; census[fseg_ctx::PATH_PLAN] = plan != nullptr;
     }
@@ -1547,6 +1554,7 @@ void read_switches(fseg_ctx *c) {
     if (env_off("FSEG_DEV_SYNC")) c->dev_sync = false;
     if (env_flag("FSEG_LABEL_BYTES")) c->label_packed_ok = false;
     env_tri("FSEG_THR_PART", c->thr_part);
+    env_tri("FSEG_THR_CHAIN", c->thr_chain);
     env_tri("FSEG_HIST16", c->hist16);
     env_tri("FSEG_YRAW16", c->yraw16);
     if (env_int("FSEG_SYNC_TICKS", v) && v > 0) c->sync_ticks = (unsigned)v;

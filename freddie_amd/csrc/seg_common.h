@@ -516,7 +516,11 @@ __device__ __forceinline__ double vsum_chunk(const double *a, int m, int pass, d
                 int body = len - (len % 8);
                 double x[16];
 #pragma unroll
+#ifdef FSEG_LAB_NOREREAD                                         // (timing experiment: the second pass loads nothing)
+                for (int i = 0; i < 16; ++i) x[i] = (8 * i + q < body) ? (pass ? __hiloint2double(0x40300000 + i, (int)threadIdx.x) : b[8 * i + q]) : 0.0;
+#else
                 for (int i = 0; i < 16; ++i) x[i] = (8 * i + q < body) ? b[8 * i + q] : 0.0;
+#endif
                 double r = FSEG_VAL(x[0]);
 #pragma unroll
                 for (int i = 1; i < 16; ++i) if (8 * i + q < body) r = __dadd_rn(r, FSEG_VAL(x[i]));
@@ -562,7 +566,17 @@ constexpr int kThrPartMaxChunks = 128;     // chunk sums a workgroup keeps in LD
 // into v[ex ..) and returns their number.  Rows of 64 positions (lane = column), so the loads of y and the stores are coalesced;
 // a row's 64 flags are the words of lanes 2q and 2q + 1 (two readlanes); rows without a flag are skipped (the values Y > 0 come
 // in runs of 2 * radius + 1 around the splice sites) and the values of eight rows are loaded together from clamped addresses.
-__device__ __forceinline__ int wave_emit_values(i64 w0, i64 n_pos, unsigned fm, i64 ex, const double *__restrict__ y, double *v) {
+// kLds (k_thr_part_chain): the first kThrLdsVals values of the partition go to the LDS array lv instead (thr_lds_slot), ex counting
+// from the partition's first value.
+constexpr int kThrLdsVals = 8192;          // one full chunk: a leaf of the pairwise recursion lies in LDS whole or not at all
+// eight doubles of padding per 128: the eight leaves a wave reads together (128 values apart in a full chunk) start on eight
+// different 16-bank groups of the 64-bank LDS instead of on one
+__device__ __forceinline__ int thr_lds_slot(int i) { return i + ((i >> 7) << 3); }
+constexpr int kThrLdsSlots = kThrLdsVals + (kThrLdsVals >> 7) * 8;
+
+template <bool kLds = false>
+__device__ __forceinline__ int wave_emit_values(i64 w0, i64 n_pos, unsigned fm, i64 ex, const double *__restrict__ y, double *v,
+                                                double *lv = nullptr) {
     const int lane = lane_id();
     const u64 lt_mask = (1ULL << lane) - 1ULL;
     u64 rows;
@@ -593,11 +607,143 @@ __device__ __forceinline__ int wave_emit_values(i64 w0, i64 n_pos, unsigned fm, 
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
             if (!m[e]) continue;
-            if ((m[e] >> lane) & 1ULL) v[ex + cnt + __popcll(m[e] & lt_mask)] = yv[e];
+#ifdef FSEG_LAB_NOSTORE                                          // (timing experiment: the loads stay, no value is stored)
+            if (((m[e] >> lane) & 1ULL) && yv[e] == -12345.678) v[ex + cnt + __popcll(m[e] & lt_mask)] = yv[e];
+#else
+            if ((m[e] >> lane) & 1ULL) {
+                const i64 idx = ex + cnt + __popcll(m[e] & lt_mask);
+                if (kLds && idx < kThrLdsVals) lv[thr_lds_slot((int)idx)] = yv[e];
+                else v[idx] = yv[e];
+            }
+#endif
             cnt += __popcll(m[e]);
         }
     }
     return cnt;
+}
+
+// ---- k_thr_part_chain: vsum_chunk's additions in vsum_chunk's order, with fewer barriers and round trips between them ----------
+#ifndef FSEG_LAB_CHAIN_LEVEL
+#define FSEG_LAB_CHAIN_LEVEL 5
+#endif
+constexpr int kThrChainLevel = FSEG_LAB_CHAIN_LEVEL;      // the k_thr_part_chain instance the product launches (seg_front.hip)
+constexpr int kThrKeepGroups = 8;          // flag words a lane keeps from the count loop for the emit loop (its wave's first groups)
+constexpr int kThrSweepChunks = 4;         // chunks whose leaves are summed in one sweep (their leaf sums are in LDS together)
+
+struct ThrChainLds {
+    // the partition's partial chunk (its last, m < 8192 values): leaves left to right and the tree in heap order, as in VsumLds;
+    // built once per partition (thr_leaf_table), used by both passes
+    int leaf_off[128], leaf_len[128], leaf_heap[128];
+    double node_val[256];
+    unsigned char node_kind[256];
+    int n_leaf;
+    double full_val[kThrSweepChunks][64];  // leaf sums of the sweep's full chunks (64 leaves of 128 each)
+};
+
+// LDS written by some lanes of a wave and read by others of the same wave: program order and a compiler fence
+__device__ __forceinline__ void wave_lds_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// The leaf table of a chunk of 0 < m < 8192 values, by ONE wave (all 64 lanes) and without a workgroup barrier: vsum_chunk's
+// walk, lane l taking x = 64 l and x = 64 (l + 64).
+__device__ __forceinline__ void thr_leaf_table(int m, ThrChainLds &L) {
+    const int lane = lane_id();
+    reinterpret_cast<unsigned *>(L.node_kind)[lane] = 0u;
+    wave_lds_sync();
+    int off[2], len[2], h[2];
+    bool own[2];
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const int x = (lane + 64 * k) * 64;
+        off[k] = 0; len[k] = m; h[k] = 1; own[k] = false;
+        if (x < m) {
+            while (len[k] > 128) {
+                int n2 = len[k] / 2; n2 -= n2 % 8;
+                if (x < off[k] + n2) { len[k] = n2; h[k] = 2 * h[k]; } else { off[k] += n2; len[k] -= n2; h[k] = 2 * h[k] + 1; }
+            }
+            own[k] = x - off[k] < 64;
+        }
+    }
+    const u64 mk0 = __ballot(own[0]), mk1 = __ballot(own[1]);
+    const u64 lt = (1ULL << lane) - 1ULL;
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        if (!own[k]) continue;
+        const int rank = k ? __popcll(mk0) + __popcll(mk1 & lt) : __popcll(mk0 & lt);
+        L.leaf_off[rank] = off[k]; L.leaf_len[rank] = len[k]; L.leaf_heap[rank] = h[k];
+        L.node_kind[h[k]] = 1;
+        for (int anc = h[k] >> 1; anc >= 1; anc >>= 1) L.node_kind[anc] = 2;
+    }
+    if (lane == 0) L.n_leaf = __popcll(mk0) + __popcll(mk1);
+}
+
+// one leaf (len <= 128 values, value k = ld(k)) by its eight threads q = 0 .. 7: vsum_chunk's leaf, the same operations
+template <class Load>
+__device__ __forceinline__ double thr_leaf_sum(int len, int q, int pass, double mu, Load ld) {
+#define FSEG_VAL(x) (pass ? __dmul_rn(__dsub_rn((x), mu), __dsub_rn((x), mu)) : (x))
+    double res = 0.0;
+    if (len < 8) {
+        for (int i = 0; i < len; ++i) res = __dadd_rn(res, FSEG_VAL(ld(i)));               // from 0.0, left to right
+    } else {
+        const int body = len - (len % 8);
+        double x[16];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) x[i] = (8 * i + q < body) ? ld(8 * i + q) : 0.0;
+        double r = FSEG_VAL(x[0]);
+#pragma unroll
+        for (int i = 1; i < 16; ++i) if (8 * i + q < body) r = __dadd_rn(r, FSEG_VAL(x[i]));
+        r = __dadd_rn(r, __shfl_xor(r, 1));
+        r = __dadd_rn(r, __shfl_xor(r, 2));
+        r = __dadd_rn(r, __shfl_xor(r, 4));
+        res = r;
+        for (int i = body; i < len; ++i) res = __dadd_rn(res, FSEG_VAL(ld(i)));
+    }
+#undef FSEG_VAL
+    return res;
+}
+
+// The sums of the partition's chunks c0 .. c0 + nsw - 1 (nsw <= kThrSweepChunks) into cs[c0 ..): the first nfull of them are full,
+// a further one is the partition's partial chunk (m_last values, table in L).  Leaves of different chunks are independent, so they
+// share the rounds of 64 leaf slots; then wave j folds chunk c0 + j -- a full chunk's 64 leaf sums by the xor butterfly, the
+// partial chunk's heap bottom-up with wave-level synchronisation (level 7 holds leaves only).  The caller has a barrier before
+// (values visible, full_val / node_val free) and after (cs visible).
+template <bool kLds>
+__device__ __forceinline__ void thr_sweep(const double *vp, const double *lv, int c0, int nsw, int nfull, int pass, double mu,
+                                          ThrChainLds &L, double *cs) {
+    const int lane = lane_id(), wave = threadIdx.x >> 6, q = threadIdx.x & 7;
+    const int nlf = 64 * nfull, nl = nlf + (nsw > nfull ? L.n_leaf : 0);
+    for (int t0 = 0; t0 < nl; t0 += 64) {
+        const int t = t0 + (threadIdx.x >> 3);
+        if (t >= nl) continue;
+        int off, len;
+        double *dst;
+        if (t < nlf) { off = c0 * 8192 + t * 128; len = 128; dst = &L.full_val[t >> 6][t & 63]; }
+        else { const int r = t - nlf; off = (c0 + nfull) * 8192 + L.leaf_off[r]; len = L.leaf_len[r]; dst = &L.node_val[L.leaf_heap[r]]; }
+        double res;
+        if (kLds && off < kThrLdsVals) res = thr_leaf_sum(len, q, pass, mu, [&](int k) { return lv[thr_lds_slot(off + k)]; });
+        else res = thr_leaf_sum(len, q, pass, mu, [&](int k) { return vp[off + k]; });
+        if (q == 0) *dst = res;
+    }
+    __syncthreads();
+    if (wave < nsw) {
+        double out;
+        if (wave < nfull) {
+            double x = L.full_val[wave][lane];
+            for (int d = 1; d < 64; d <<= 1) x = __dadd_rn(x, __shfl_xor(x, d));
+            out = x;
+        } else {
+            for (int lvl = 6; lvl >= 0; --lvl) {
+                const int i = (1 << lvl) + lane;
+                if (lane < (1 << lvl) && L.node_kind[i] == 2) L.node_val[i] = __dadd_rn(L.node_val[2 * i], L.node_val[2 * i + 1]);
+                wave_lds_sync();
+            }
+            out = L.node_val[1];
+        }
+        if (lane == 0) cs[c0 + wave] = out;
+    }
 }
 
 

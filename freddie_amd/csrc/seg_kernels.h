@@ -64,6 +64,9 @@ __global__ void __launch_bounds__(512) k_vsum_chunks(int n_part, const i64 *voff
 // seg_front.hip
 __global__ void __launch_bounds__(512) k_thr_part(int n_part, const i64 *part_iv_off, const i64 *pos_off, i64 n_pos, const unsigned *flags,
                                                   const double *__restrict__ y, double *v, double vf, double *mean, double *thr);
+template <int kLevel>
+__global__ void __launch_bounds__(512) k_thr_part_chain(int n_part, const i64 *part_iv_off, const i64 *pos_off, i64 n_pos, const unsigned *flags,
+                                                        const double *__restrict__ y, double *v, double vf, double *mean, double *thr);
 
 // seg_front.hip
 __global__ void k_vsum_part(int n_part, const i64 *voff, const i64 *chunk_off, const double *csum0, const double *csum1,

@@ -245,8 +245,9 @@ enum {
      *   27 the histogram ran with packed 16-bit LDS counters (k_hist<16>; 0: the 32-bit instance)
      *   28 the block size k_fix and k_segments were launched with (64, 256 or 1024, by the batch's average interval length)
      *   29 the k_smooth instance: 20 or 12 (the unrolled radii), 0 (any other radius, the loop)
-     *   30 the histogram is uint16 in device memory (FSEG_YRAW16, where word 27 is 1; 0: int32) */
-    FSEG_TAP_PATHS = 18        /* int32[31]                                                                            */
+     *   30 the histogram is uint16 in device memory (FSEG_YRAW16, where word 27 is 1; 0: int32)
+     *   31 k_thr_part_chain took the variance threshold (FSEG_THR_CHAIN, where word 5 is 1; 0: k_thr_part) */
+    FSEG_TAP_PATHS = 18        /* int32[32]                                                                            */
 };
 int fseg_tap(fseg_ctx *ctx, int what, void *dst, int64_t cap_bytes, int64_t *n_bytes);
 
