@@ -157,6 +157,7 @@ CLUSTER_SO = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libfreddi
 CLUSTER_SRC = [os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "freddie_cluster.hip")]
 CLUSTER_HEADERS = [os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "clu_incumbent.h")]
 EXPORTS = ["fclu_abi_version", "fclu_create", "fclu_destroy", "fclu_last_error", "fclu_compat_graph", "fclu_last_timing",
+           "fclu_last_paths",
            "fclu_partition", "fclu_partition_adj", "fclu_partition_results", "fclu_partition_timing",
            "fclu_preprocess", "fclu_preprocess_results", "fclu_partition_reads", "fclu_preprocess_timing",
            "fclu_group_reads", "fclu_partition_segment", "fclu_group_results", "fclu_group_timing",
@@ -222,6 +223,9 @@ class _Rounds(ctypes.Structure):
     _fields_ = [("n_prob", ctypes.c_int32)] + [(n, ctypes.c_int64) for n in _ROUND_COUNTS] + [(n, ctypes.c_void_p) for n in _ROUND_ARRAYS]
 
 
+_PATHS = ("compat_form", "tiles", "lds_tints", "pass_kernel", "edge_chunks", "passes_enqueued", "passes_ran")     # FCLU_PATH_*
+
+
 class _Incumbents(ctypes.Structure):
     _fields_ = [("n_prob", ctypes.c_int32), ("n_mem", ctypes.c_int64)] + [
         (n, ctypes.c_void_p) for n in ("cost2", "start", "grow_steps", "repair_steps", "mem_off", "mem")]
@@ -253,6 +257,8 @@ def load():
     L.fclu_compat_graph.argtypes = [vp, ctypes.POINTER(_Batch), ctypes.c_int32, vp, vp]
     L.fclu_last_timing.restype = ctypes.c_int
     L.fclu_last_timing.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
+    L.fclu_last_paths.restype = ctypes.c_int
+    L.fclu_last_paths.argtypes = [vp, vp, ctypes.c_int32]
     L.fclu_partition.restype = ctypes.c_int
     L.fclu_partition.argtypes = [vp, ctypes.POINTER(_Batch), vp, vp, ctypes.c_int32]
     L.fclu_partition_adj.restype = ctypes.c_int
@@ -579,6 +585,18 @@ class Context:
         a, b = ctypes.c_float(), ctypes.c_float()
         self._L.fclu_last_timing(self._h, ctypes.byref(a), ctypes.byref(b))
         return dict(compat_ms=a.value, prune_ms=b.value)
+
+    def last_paths(self):
+        """The launch census of the last call that built a graph (include/freddie_cluster.h, fclu_last_paths): compat_form "rank" /
+        "masked", tiles, lds_tints, pass_kernel None / "edge_walk" / "or_of_rows", edge_chunks, passes_enqueued, passes_ran."""
+        v = np.zeros(len(_PATHS), np.int32)
+        rc = self._L.fclu_last_paths(self._h, v.ctypes.data, v.size)
+        if rc != 0:
+            raise ClusterError("fclu_last_paths: bad arguments", rc)
+        out = dict(zip(_PATHS, v.tolist()))
+        out["compat_form"] = (None, "rank", "masked")[out["compat_form"]]
+        out["pass_kernel"] = (None, "edge_walk", "or_of_rows")[out["pass_kernel"]]
+        return out
 
     def close(self):
         if getattr(self, "_h", None):

@@ -1425,6 +1425,7 @@ struct fclu_ctx {
     hipEvent_t *const ev = events, *const pev = ev + 3, *const qev = pev + 6, *const gev = qev + 6, *const rev = gev + 5, *const iev = rev + 5;
     std::string err;
     float compat_ms = 0.f, prune_ms = 0.f;
+    int32_t paths[FCLU_N_PATHS] = {};     // the last graph call's launch census (fclu_last_paths)
     Buf<TintDesc> tints; Buf<int4> tiles; Buf<int2> word_tint; Buf<i64> tint_word0;
     Buf<unsigned> bits; Buf<unsigned char> tail; Buf<u64> adj[2], deg1;
     Buf<int> row_tint, first, last, deg, small_tints, small_rounds;
@@ -1721,6 +1722,7 @@ int stage_tints(fclu_ctx *c, const Knobs &k, int T, const int64_t *row_off, cons
     }
     st.n_tiles = (int)st.tiles.size();
     c->compat_ms = c->prune_ms = 0.f;
+    std::fill_n(c->paths, FCLU_N_PATHS, 0);
     c->h_tints = st.tints;
     c->adj_cur = 0;
     st.empty = st.n_tiles == 0 || st.R == 0;
@@ -1742,6 +1744,8 @@ int compat_run(fclu_ctx *c, const Staged &st, const Knobs &k, int32_t prune, uin
     HIP_TRY(c, hipEventRecord(c->ev[0], s));
     hipLaunchKernelGGL(!rank ? k_compat<false> : k_compat<true>, dim3(grid), dim3(256), lds, s, st.n_tiles, c->tiles.p, c->tints.p, c->bits.p, c->first.p,
                        c->last.p, c->tail.p, c->adj[0].p);
+    c->paths[FCLU_PATH_COMPAT_FORM] = rank ? FCLU_FORM_RANK : FCLU_FORM_MASKED;
+    c->paths[FCLU_PATH_TILES] = st.n_tiles;
     HIP_TRY(c, hipEventRecord(c->ev[1], s));
     int cur = 0;
     if (prune && !st.small_tints.empty()) {
@@ -1749,6 +1753,7 @@ int compat_run(fclu_ctx *c, const Staged &st, const Knobs &k, int32_t prune, uin
         HIP_TRY(c, hipMemcpyAsync(c->small_tints.p, st.small_tints.data(), c->small_tints.bytes(st.small_tints.size()), hipMemcpyHostToDevice, s));
         hipLaunchKernelGGL(k_prune_lds, dim3((unsigned)st.small_tints.size()), dim3(256), st.small_lds, s, c->small_tints.p, c->tints.p, c->adj[0].p,
                            c->adj[1].p, c->small_rounds.p);
+        c->paths[FCLU_PATH_LDS_TINTS] = (int32_t)st.small_tints.size();
     }
     if (prune && st.any_large) {
         // the loop of :240-255 usually ends after two or three passes
@@ -1758,6 +1763,8 @@ int compat_run(fclu_ctx *c, const Staged &st, const Knobs &k, int32_t prune, uin
         // the pass edge by edge (k_prune_edges) when every tint of the per-pass kernels has rows of at most kEdgeChunks x 64 words
         const bool edge_walk = st.max_aw_large <= kEdgeChunks * 64 && k.prune_edges;
         const int edge_chunks = (st.max_aw_large + 63) / 64 > 0 ? (st.max_aw_large + 63) / 64 : 1;
+        c->paths[FCLU_PATH_PASS_KERNEL] = edge_walk ? FCLU_PASS_EDGE_WALK : FCLU_PASS_OR_OF_ROWS;
+        c->paths[FCLU_PATH_EDGE_CHUNKS] = edge_walk ? edge_chunks : 0;
         int *d_changed = c->pass_any.p + kBurst;             // per pass and tint
         const int *h_changed = c->h_flags.p + kBurst;
         const auto pass = [&](int q, int *any, const int *gate) {
@@ -1780,6 +1787,8 @@ int compat_run(fclu_ctx *c, const Staged &st, const Knobs &k, int32_t prune, uin
             for (int q = 0; q < ran; ++q)
                 if (rounds_out) for (int t = 0; t < T; ++t) if (h_changed[(size_t)q * T + t]) rounds_out[t] += 1;
             cur ^= ran & 1;                                  // (each pass that ran wrote the other buffer)
+            c->paths[FCLU_PATH_PASSES_ENQUEUED] += kBurst;
+            c->paths[FCLU_PATH_PASSES_RAN] += ran;
         }
     }
     HIP_TRY(c, hipEventRecord(c->ev[2], s));
@@ -2797,6 +2806,12 @@ int fclu_compat_graph(fclu_ctx *c, const fclu_batch *b, int32_t prune, uint64_t 
 
 int fclu_last_timing(fclu_ctx *c, float *compat_ms, float *prune_ms) { return c ? two_times(compat_ms, c->compat_ms, prune_ms, c->prune_ms) : FCLU_ERR_ARG; }
 
+int fclu_last_paths(fclu_ctx *c, int32_t *out, int32_t n) {
+    if (!c || !out || n < 0) return FCLU_ERR_ARG;
+    std::copy_n(c->paths, std::min<int32_t>(n, FCLU_N_PATHS), out);
+    return FCLU_OK;
+}
+
 int fclu_partition(fclu_ctx *c, const fclu_batch *b, const int64_t *mem_off, const int32_t *mem, int32_t maximum_ilp_size) {
     if (!c || !b) return FCLU_ERR_ARG;
     c->have_parts = false;
@@ -2831,6 +2846,7 @@ int fclu_partition_adj(fclu_ctx *c, int32_t n_tint, const int64_t *row_off, cons
     c->h_tints = tints;
     c->adj_cur = 0;
     c->compat_ms = c->prune_ms = 0.f;
+    std::fill_n(c->paths, FCLU_N_PATHS, 0);
     if (R > 0) {
         hipStream_t s = c->stream;
         HIP_TRY(c, c->tints.grow((size_t)T));

@@ -74,6 +74,24 @@ int fclu_compat_graph(fclu_ctx *c, const fclu_batch *b, int32_t prune, uint64_t 
 /* Duration of the kernels of the last fclu_compat_graph() call, from HIP events on the library's stream (ms). */
 int fclu_last_timing(fclu_ctx *c, float *compat_ms, float *prune_ms);
 
+/* Launch census of the graph stage: which kernels the last call that built a graph (fclu_compat_graph, fclu_partition,
+ * fclu_partition_reads, fclu_partition_segment) launched, as the host decided it.  All zero behind a call that built none
+ * (an empty batch, fclu_partition_adj).  The first min(n, FCLU_N_PATHS) values go to out. */
+enum {
+    FCLU_PATH_COMPAT_FORM = 0,      /* k_compat: FCLU_FORM_RANK (rank tables) or FCLU_FORM_MASKED (a range mask per word) */
+    FCLU_PATH_TILES = 1,            /* 64 x 64 tiles on and above the diagonals, all tints */
+    FCLU_PATH_LDS_TINTS = 2,        /* tints pruned whole by one workgroup (k_prune_lds); 0 without pruning */
+    FCLU_PATH_PASS_KERNEL = 3,      /* the per-pass kernels: 0 not launched, FCLU_PASS_EDGE_WALK (k_prune_edges) or
+                                       FCLU_PASS_OR_OF_ROWS (k_deg1 + k_prune) */
+    FCLU_PATH_EDGE_CHUNKS = 4,      /* k_prune_edges: 64-word chunks of the longest adjacency row it takes; 0 otherwise */
+    FCLU_PATH_PASSES_ENQUEUED = 5,  /* per-pass launches enqueued (whole bursts) */
+    FCLU_PATH_PASSES_RAN = 6,       /* of those, the passes that ran: up to and with the first that removed nothing */
+    FCLU_N_PATHS = 7
+};
+enum { FCLU_FORM_RANK = 1, FCLU_FORM_MASKED = 2 };
+enum { FCLU_PASS_EDGE_WALK = 1, FCLU_PASS_OR_OF_ROWS = 2 };
+int fclu_last_paths(fclu_ctx *c, int32_t *out, int32_t n);
+
 /* ---- the rest of partition_reads(): components, even split, members and incompatible pairs (:256-274) ----
  * mem_off: int64[row_off[n_tint] + 1], starts at 0 and never falls; mem[mem_off[r] .. mem_off[r+1]] = the rep ids of
  * unique read r (unique_data[r][1]).  maximum_ilp_size >= 1.
