@@ -71,13 +71,15 @@ EXPORTS = ["fseg_annotate", "fseg_annotation", "fseg_abi_version", "fseg_source_
 # the words of the `paths` tap (include/freddie_seg.h, FSEG_TAP_PATHS)
 PATHS = ("small_batch", "tiny_on", "wave_on", "fuse_on", "key32", "thr_part", "label_packed", "n_solve0", "n_solve1", "n_solve2",
          "n_wide0", "n_wide1", "n_wide2", "n_tiny", "n_work", "dpw", "wide16", "known", "solve8", "tiny_kernel", "score", "arena_dp",
-         "plan", "n_arena_prob", "n_score0", "n_score1", "n_score2", "hist16", "iv_threads", "smooth_r", "yraw16", "thr_chain")
+         "plan", "n_arena_prob", "n_score0", "n_score1", "n_score2", "hist16", "iv_threads", "smooth_r", "yraw16", "thr_chain",
+         "lane_sort")
 
 TAPS = dict(pos_off=(1, np.int64), y_raw=(2, np.int32), y=(3, np.float64), threshold=(4, np.float64),
             cand_off=(5, np.int64), cand_y=(6, np.int32), fixed=(7, np.uint8), chosen=(8, np.uint8),
             final_off=(9, np.int64), final_y=(10, np.int32), problems=(11, np.int32),
             lane_start=(12, np.int32), lane_pmax=(13, np.int32), lane_exons=(14, np.int64),
-            lane_stream=(15, np.int32), exon_stream=(16, np.int32), sync=(17, np.int32), paths=(18, np.int32))
+            lane_stream=(15, np.int32), exon_stream=(16, np.int32), sync=(17, np.int32), paths=(18, np.int32),
+            hist_ranges=(19, np.int64))
 
 
 def lib_path():
@@ -285,7 +287,7 @@ class Context:
         out = np.empty(n.value // np.dtype(dtype).itemsize, dtype)
         if n.value:
             self._check(self._L.fseg_tap(self._h, what, out.ctypes.data, n.value, ctypes.byref(n)), "fseg_tap")
-        return out.reshape(-1, 4) if name == "problems" else (out.reshape(-1, 2) if name in ("lane_exons", "lane_stream", "exon_stream") else out)
+        return out.reshape(-1, 4) if name in ("problems", "hist_ranges") else (out.reshape(-1, 2) if name in ("lane_exons", "lane_stream", "exon_stream") else out)
 
     def paths(self):
         """The launch census of the last run (the `paths` tap) as a dict: which kernel instances the host enqueued."""

@@ -301,7 +301,7 @@ struct fseg_ctx {
     enum { PATH_SMALL_BATCH, PATH_TINY_ON, PATH_WAVE_ON, PATH_FUSE_ON, PATH_KEY32, PATH_THR_PART, PATH_LABEL_PACKED, PATH_N_SOLVE,
            PATH_N_WIDE = PATH_N_SOLVE + 3, PATH_N_TINY = PATH_N_WIDE + 3, PATH_N_WORK, PATH_DPW, PATH_WIDE16, PATH_KNOWN, PATH_SOLVE8,
            PATH_TINY_KERNEL, PATH_SCORE, PATH_ARENA_DP, PATH_PLAN, PATH_N_ARENA_PROB, PATH_N_SCORE, PATH_HIST16 = PATH_N_SCORE + 3, PATH_IV_THREADS,
-           PATH_SMOOTH_R, PATH_YRAW16, PATH_THR_CHAIN, PATH_WORDS };
+           PATH_SMOOTH_R, PATH_YRAW16, PATH_THR_CHAIN, PATH_LANE_SORT, PATH_WORDS };
     int paths[PATH_WORDS] = {};
     // fseg_annotate: the uploaded reads (one allocation, mirrored by a pinned image), per-read work arrays, the emitted lists, and
     // the pinned buffers fseg_annotation() points into (own allocations: nothing of a run or of fseg_results* touches them)
@@ -772,7 +772,7 @@ int enqueue_run(fseg_ctx *c, unsigned segs, bool sized = false, i64 label_fill_b
     if (do_score) {
         for (int w = 0; w < fseg_ctx::PATH_WORDS; ++w)
             if (w != fseg_ctx::PATH_THR_PART && w != fseg_ctx::PATH_LABEL_PACKED && w != fseg_ctx::PATH_ARENA_DP && w != fseg_ctx::PATH_HIST16 &&
-                w != fseg_ctx::PATH_IV_THREADS && w != fseg_ctx::PATH_SMOOTH_R && w != fseg_ctx::PATH_YRAW16 && w != fseg_ctx::PATH_THR_CHAIN) census[w] = 0;
+                w != fseg_ctx::PATH_IV_THREADS && w != fseg_ctx::PATH_SMOOTH_R && w != fseg_ctx::PATH_YRAW16 && w != fseg_ctx::PATH_THR_CHAIN && w != fseg_ctx::PATH_LANE_SORT) census[w] = 0;
         census[fseg_ctx::PATH_SMALL_BATCH] = c->small_batch; census[fseg_ctx::PATH_TINY_ON] = c->tiny_on; census[fseg_ctx::PATH_WAVE_ON] = wave;
         census[fseg_ctx::PATH_FUSE_ON] = c->use_fuse && c->fuse_on; census[fseg_ctx::PATH_KNOWN] = known; census[fseg_ctx::PATH_PLAN] = plan != nullptr;
     }
@@ -1894,12 +1894,14 @@ static int upload_impl(fseg_ctx *c, const fseg_batch *b) {
                                        c->d_val_b.p, (size_t)R, end_bit, s));
         }
         if (sort_here) {
+            c->paths[fseg_ctx::PATH_LANE_SORT] = 0;
             hipLaunchKernelGGL(k_lanes, dim3(grid_for(np, 1, 65536)), dim3(256), 0, s, np, c->d_part_rep_off.p, c->d_part_lane_off.p,
                                c->d_key_b.p, c->d_val_b.p, c->d_rep_weight.p, c->d_rep_last.p,
                                c->d_rep_exon_off.p, c->d_lane_ex.p, c->d_lane_start.p, c->d_lane_pmax.p,
                                1, c->d_key_a.p, c->d_ex_ts.p, c->d_ex_te.p, c->d_lane_lx.p, c->d_lex.p);
         } else {
             const int rbg = grid_for(n_rep_blocks, 1, 65536);
+            c->paths[fseg_ctx::PATH_LANE_SORT] = 1;
             hipLaunchKernelGGL(k_lane_blocks, dim3(rbg), dim3(256), 0, s, (int)n_rep_blocks, c->d_rb_part.p, c->d_rb_r0.p,
                                c->d_part_rep_off.p, c->d_val_b.p, c->d_rep_weight.p, c->d_rep_last.p,
                                c->d_rb_sum.p, c->d_rb_max.p, c->d_rep_exon_off.p, c->d_rb_esum.p);
@@ -2504,6 +2506,19 @@ int fseg_tap(fseg_ctx *c, int what, void *dst, int64_t cap_bytes, int64_t *n_byt
             return from_host(words, sizeof words);
         }
         case FSEG_TAP_PATHS: return from_host(c->paths, sizeof c->paths);
+        case FSEG_TAP_HIST_RANGES: {                                       // a row per histogram chunk: first position, positions, lane range
+            const size_t n = (size_t)c->n_hist_chunks;
+            std::vector<i64> col(n), rows(n * 4);
+            std::vector<int> cnt(n);
+            const DevBuf<i64> *cols[3] = {&c->d_hc_p0, &c->d_hc_llo, &c->d_hc_lhi};
+            for (int k = 0; k < 3 && n; ++k) {
+                HIP_TRY(c, copy_sync(c, col.data(), cols[k]->p, bytes_of(*cols[k], n), hipMemcpyDeviceToHost));
+                for (size_t i = 0; i < n; ++i) rows[4 * i + (k ? k + 1 : 0)] = col[i];
+            }
+            if (n) HIP_TRY(c, copy_sync(c, cnt.data(), c->d_hc_n.p, bytes_of(c->d_hc_n, n), hipMemcpyDeviceToHost));
+            for (size_t i = 0; i < n; ++i) rows[4 * i + 1] = cnt[i];
+            return from_host(rows.data(), rows.size() * sizeof(i64));
+        }
         default: return fail(c, FSEG_ERR_ARG, "unknown tap %d", what);
     }
 }

@@ -246,8 +246,14 @@ enum {
      *   28 the block size k_fix and k_segments were launched with (64, 256 or 1024, by the batch's average interval length)
      *   29 the k_smooth instance: 20 or 12 (the unrolled radii), 0 (any other radius, the loop)
      *   30 the histogram is uint16 in device memory (FSEG_YRAW16, where word 27 is 1; 0: int32)
-     *   31 k_thr_part_chain took the variance threshold (FSEG_THR_CHAIN, where word 5 is 1; 0: k_thr_part) */
-    FSEG_TAP_PATHS = 18        /* int32[32]                                                                            */
+     *   31 k_thr_part_chain took the variance threshold (FSEG_THR_CHAIN, where word 5 is 1; 0: k_thr_part)
+     *   32 lane_sort: how the last upload ordered the reps -- 0 k_lanes sorted every partition in LDS, 1 the batch-wide radix sort
+     *      and k_lane_blocks / k_lane_block_scan / k_lane_emit (a partition of more than 2 048 reps, or FSEG_GLOBAL_SORT=1);
+     *      written by fseg_upload, kept by every run and replay of the batch */
+    FSEG_TAP_PATHS = 18,       /* int32[33]                                                                            */
+    /* the histogram chunks of the last upload, a row each: (p0, n, llo, lhi) -- the chunk's first batch position, its position
+     * count, and the lanes [llo, lhi) of its partition that k_hist_ranges found able to reach it */
+    FSEG_TAP_HIST_RANGES = 19  /* int64[n_hist_chunks][4]                                                              */
 };
 int fseg_tap(fseg_ctx *ctx, int what, void *dst, int64_t cap_bytes, int64_t *n_bytes);
 

@@ -6,6 +6,7 @@ the bench workloads (reference: optimize :475-568, get_cumulative_coverage's uin
 import numpy as np
 import pytest
 
+import lane_cases
 import util
 from freddie_amd import _lib, synth
 
@@ -417,26 +418,21 @@ def test_lane_preparation_on_the_device(big, gpu_ctx):
     lstream, estream = gpu_ctx.tap("lane_stream"), gpu_ctx.tap("exon_stream")
     l0 = e0 = 0
     for p in parts:
-        first = p.ex_ts[p.rep_exon_off[:-1]]
-        last = p.ex_te[p.rep_exon_off[1:] - 1]
-        order = np.lexsort((np.arange(p.n_reps), first))
-        lanes = np.repeat(order, p.rep_weight[order])
-        n = len(lanes)
+        # the model (tests/lane_cases.py): order = lexsort((arange, first)), lanes = repeat(order, weight), the running maximum of the
+        # last positions, and the exon stream: the partition's exons once more as (ts, te) pairs, rep after rep in lane order; a
+        # lane's range in it holds exactly its rep's exons (the copies of a weighted rep share one range)
+        m = lane_cases.model_partition(p)
+        n = len(m["start"])
         assert n == p.rep_weight.sum()
-        assert np.array_equal(start[l0:l0 + n], first[lanes])
-        assert np.array_equal(pmax[l0:l0 + n], np.maximum.accumulate(last[lanes]))
-        assert np.array_equal(exons[l0:l0 + n, 0], p.rep_exon_off[lanes] + e0)
-        assert np.array_equal(exons[l0:l0 + n, 1], p.rep_exon_off[lanes + 1] + e0)
-        # the exon stream: the partition's exons once more as (ts, te) pairs, rep after rep in lane order; a lane's range
-        # in it holds exactly its rep's exons (the copies of a weighted rep share one range)
-        n_ex = np.diff(p.rep_exon_off)[order]
-        off = np.concatenate([[0], np.cumsum(n_ex)]) + e0
-        rep_pos = np.repeat(np.arange(p.n_reps), p.rep_weight[order])
-        assert np.array_equal(lstream[l0:l0 + n, 0], off[rep_pos])
-        assert np.array_equal(lstream[l0:l0 + n, 1], off[rep_pos + 1])
-        idx = np.concatenate([np.arange(p.rep_exon_off[r], p.rep_exon_off[r + 1]) for r in order])
-        assert np.array_equal(estream[e0:e0 + len(idx), 0], p.ex_ts[idx])
-        assert np.array_equal(estream[e0:e0 + len(idx), 1], p.ex_te[idx])
+        assert np.array_equal(start[l0:l0 + n], m["start"])
+        assert np.array_equal(pmax[l0:l0 + n], m["pmax"])
+        assert np.array_equal(exons[l0:l0 + n, 0], m["exons"][:, 0] + e0)
+        assert np.array_equal(exons[l0:l0 + n, 1], m["exons"][:, 1] + e0)
+        assert np.array_equal(lstream[l0:l0 + n, 0], m["stream"][:, 0] + e0)
+        assert np.array_equal(lstream[l0:l0 + n, 1], m["stream"][:, 1] + e0)
+        n_ex = len(p.ex_ts)
+        assert np.array_equal(estream[e0:e0 + n_ex, 0], m["estream"][:, 0])
+        assert np.array_equal(estream[e0:e0 + n_ex, 1], m["estream"][:, 1])
         l0 += n; e0 += len(p.ex_ts)
     assert l0 == len(start)
 
