@@ -1779,6 +1779,15 @@ constexpr int kLabelStage = FSEG_LABEL_STAGE;
 
 constexpr int kLabelSplit = 4;
 
+// k_label_reads_lds (FSEG_LABEL_LDS, the default): the exons of a workgroup's 64 reps are one contiguous run of ex_ts / ex_te; a run
+// of up to kLabelExons is staged in LDS beside the column table (a longer one is read from global memory, as k_label_reads does).
+// 960: 4 100 + 8 192 B of columns, 260 B of rep offsets and 7 680 B of exons are 20 232 B, eight workgroups a CU (20 480 B each) as before.
+constexpr int kLabelReps = 256 / kLabelSplit;
+#ifndef FSEG_LABEL_EXONS
+#define FSEG_LABEL_EXONS 960
+#endif
+constexpr int kLabelExons = FSEG_LABEL_EXONS;
+
 
 // ---------------------------------------------------------------------------------------------
 // upload-time preparation, once per batch, on the device (the inputs arrive in one copy; what used to be a host pass

@@ -448,7 +448,19 @@ __global__ void __launch_bounds__(256) k_label_reads(int n_blocks, const int *rb
         i64 acc_w = -1;
         i64 e = rep_exon_off[r], e1 = rep_exon_off[r + 1];
         if (e >= e1) continue;
-        int first_ts = ex_ts[e], last_te = ex_te[e1 - 1];
+#ifdef FSEG_LAB_NOEXON
+        // diagnostic build (wrong results): exon k of a rep is computed from the rep and the partition's average column width w --
+        // [3 w k', 3 w k' + 2 w] from the partition's first position, k' = k + 3 (r mod 64): every exon read below is arithmetic,
+        // the spans and the exons per column stay about what a config4 batch has (some 20 columns, a third of them uncovered)
+        const int fk_w = max(1, (fp[S] - fp[0]) / (int)S), fk_0 = fp[0] + 9 * fk_w * (int)(r & 63);
+        const i64 fk_e = e;
+#define LAB_TS(i) (fk_0 + 3 * fk_w * (int)((i) - fk_e))
+#define LAB_TE(i) (LAB_TS(i) + 2 * fk_w)
+#else
+#define LAB_TS(i) ex_ts[i]
+#define LAB_TE(i) ex_te[i]
+#endif
+        int first_ts = LAB_TS(e), last_te = LAB_TE(e1 - 1);
         // first column whose segment [fp[c], fp[c+1]) ends after first_ts
         int lo = 0, hi = (int)S;
         while (lo < hi) { int mid = (lo + hi) >> 1; if (fp[mid + 1] <= first_ts) lo = mid + 1; else hi = mid; }
@@ -465,23 +477,23 @@ __global__ void __launch_bounds__(256) k_label_reads(int n_blocks, const int *rb
         if (q) {                                             // first exon that reaches the first column of the share
             const int g = fp[c_a];
             i64 a = e, b = e1;
-            while (a < b) { i64 mid = (a + b) >> 1; if (ex_te[mid] < g) a = mid + 1; else b = mid; }
+            while (a < b) { i64 mid = (a + b) >> 1; if (LAB_TE(mid) < g) a = mid + 1; else b = mid; }
             e = a;
         }
         int ts = 0, te = 0;
-        if (e < e1) { ts = ex_ts[e]; te = ex_te[e]; }
+        if (e < e1) { ts = LAB_TS(e); te = LAB_TE(e); }
         for (int c = c_a; c < c_b; ++c) {
             int2 t2 = th[c];
             if (t2.x == 0x7fffffff) continue;                 // sentinel column between two intervals
             int g0 = fp[c], g1 = fp[c + 1];
-            while (e < e1 && te < g0) { ++e; if (e < e1) { ts = ex_ts[e]; te = ex_te[e]; } }   // exons before the segment
+            while (e < e1 && te < g0) { ++e; if (e < e1) { ts = LAB_TS(e); te = LAB_TE(e); } }   // exons before the segment
             int cov = 0;
             if (e < e1 && ts < g1) {
                 int a = ts > g0 ? ts : g0, b2 = te + 1 < g1 ? te + 1 : g1;
                 if (b2 > a) cov += b2 - a;
-                for (i64 x = e + 1; x < e1 && ex_ts[x] < g1; ++x) {
-                    int a3 = ex_ts[x] > g0 ? ex_ts[x] : g0;
-                    int b3 = ex_te[x] + 1 < g1 ? ex_te[x] + 1 : g1;
+                for (i64 x = e + 1; x < e1 && LAB_TS(x) < g1; ++x) {
+                    int a3 = LAB_TS(x) > g0 ? LAB_TS(x) : g0;
+                    int b3 = LAB_TE(x) + 1 < g1 ? LAB_TE(x) + 1 : g1;
                     if (b3 > a3) cov += b3 - a3;
                 }
             }
@@ -501,6 +513,8 @@ __global__ void __launch_bounds__(256) k_label_reads(int n_blocks, const int *rb
         }
         if (acc) atomicOr(&packed[acc_w], acc);
     }
+#undef LAB_TS
+#undef LAB_TE
 }
 
 
@@ -509,6 +523,154 @@ __global__ void __launch_bounds__(256) k_label_reads(int n_blocks, const int *rb
 // 78 us against 73: finding a pair's rep, walking its exons from the first and the cross-lane OR cost more per pair than the
 // balance saves.  Of k_label_reads' 73 us 41 are the column loop, 13 its stores, 9 the bisections, 10 the workgroup's staging
 // (tools/probes/label_ablate.sh with the FSEG_LAB_NO* builds).)
+
+
+// k_label_reads with its operands in LDS (FSEG_LABEL_LDS, the default; profiles/label_lds.txt).  The same comparisons, the same
+// cov sums and the same store rule; what changes is where fp / th / the exons are read from:
+//   COLS_LDS   the column table is indexed as the LDS array it is.  (k_label_reads selects `fp = fp_s` at run time, which makes fp a
+//              generic pointer: both bisections and the column loop are FLAT loads there, never a ds_read.)
+//   EXONS_LDS  the exons of the unit's 64 reps -- one contiguous run of ex_ts / ex_te -- are staged with coalesced loads beside the
+//              column table, as (ts, te) pairs, and every exon read is a ds_read at a unit-local int index.
+// Both flags are uniform over the workgroup; a unit takes one of the four instances of label_rep.
+
+// what a unit stages of its reps: the reps [r0, r0 + n_rep), their exon offsets relative to e_base, the exon run [e_base, e_base + n_ex).
+// r0 < r_end <= R (the caller's test), so rep_exon_off[r0 + n_rep] is an entry of the R + 1 there are and e_base + n_ex <= I.
+struct LabelUnit { int n_rep; i64 e_base, n_ex; };
+__device__ __forceinline__ LabelUnit label_unit(i64 r0, i64 r_end, const i64 *rep_exon_off) {
+    LabelUnit u;
+    u.n_rep = (int)(r_end - r0 < kLabelReps ? r_end - r0 : kLabelReps);     // (a partition's last unit may hold fewer)
+    u.e_base = rep_exon_off[r0];
+    u.n_ex = rep_exon_off[r0 + u.n_rep] - u.e_base;
+    return u;
+}
+// reo_s[0 .. n_rep] and, where the run fits, ex_s[0 .. n_ex): the only new addressing of the kernel.  Returns whether the exons were
+// staged (uniform over the workgroup): the one place that decides it.
+__device__ __forceinline__ bool label_stage_exons(const LabelUnit &u, i64 r0, const i64 *rep_exon_off, const int *ex_ts, const int *ex_te,
+                                                  int *reo_s, int2 *ex_s) {
+    for (int x = threadIdx.x; x <= u.n_rep; x += blockDim.x) reo_s[x] = (int)(rep_exon_off[r0 + x] - u.e_base);
+    if (u.n_ex > kLabelExons) return false;
+    for (int x = threadIdx.x; x < (int)u.n_ex; x += blockDim.x) ex_s[x] = make_int2(ex_ts[u.e_base + x], ex_te[u.e_base + x]);
+    return true;
+}
+
+// one thread's share of one rep: exons [e, e1) as unit-local indices (into ex_s, or into ts_g / te_g = ex_ts / ex_te + e_base)
+template <bool COLS_LDS, bool EXONS_LDS>
+__device__ __forceinline__ void label_rep(const int *fp_g, const int2 *th_g, const int *fp_s, const int2 *th_s, const int2 *ex_s,
+                                          const int *ts_g, const int *te_g, int e, const int e1, const int S, const int q,
+                                          const i64 row_g0, unsigned char *row, unsigned *packed) {
+    auto FP = [&](int i) -> int { if constexpr (COLS_LDS) return fp_s[i]; else return fp_g[i]; };
+    auto TH = [&](int i) -> int2 { if constexpr (COLS_LDS) return th_s[i]; else return th_g[i]; };
+    auto TS = [&](int i) -> int { if constexpr (EXONS_LDS) return ex_s[i].x; else return ts_g[i]; };
+    auto TE = [&](int i) -> int { if constexpr (EXONS_LDS) return ex_s[i].y; else return te_g[i]; };
+    unsigned acc = 0;
+    i64 acc_w = -1;
+    const int first_ts = TS(e), last_te = TE(e1 - 1);
+    // first column whose segment [fp[c], fp[c+1]) ends after first_ts
+    int lo = 0, hi = S;
+    while (lo < hi) { int mid = (lo + hi) >> 1; if (FP(mid + 1) <= first_ts) lo = mid + 1; else hi = mid; }
+    // first column that starts after last_te
+    int c_hi = lo; hi = S;
+    while (c_hi < hi) { int mid = (c_hi + hi) >> 1; if (FP(mid) <= last_te) c_hi = mid + 1; else hi = mid; }
+    // this thread's share of [lo, c_hi)
+    const int span = c_hi - lo;
+    const int c_a = lo + (int)((i64)span * q / kLabelSplit), c_b = lo + (int)((i64)span * (q + 1) / kLabelSplit);
+    if (c_a >= c_b) return;
+    if (q) {                                                 // first exon that reaches the first column of the share
+        const int g = FP(c_a);
+        int a = e, b = e1;
+        while (a < b) { int mid = (a + b) >> 1; if (TE(mid) < g) a = mid + 1; else b = mid; }
+        e = a;
+    }
+    int ts = 0, te = 0;
+    if (e < e1) { ts = TS(e); te = TE(e); }
+    for (int c = c_a; c < c_b; ++c) {
+        const int2 t2 = TH(c);
+        if (t2.x == 0x7fffffff) continue;                     // sentinel column between two intervals
+        const int g0 = FP(c), g1 = FP(c + 1);
+        while (e < e1 && te < g0) { ++e; if (e < e1) { ts = TS(e); te = TE(e); } }   // exons before the segment
+        int cov = 0;
+        if (e < e1 && ts < g1) {
+            int a = ts > g0 ? ts : g0, b2 = te + 1 < g1 ? te + 1 : g1;
+            if (b2 > a) cov += b2 - a;
+            for (int x = e + 1; x < e1; ++x) {
+                const int xs = TS(x);
+                if (!(xs < g1)) break;
+                const int xe = TE(x);
+                int a3 = xs > g0 ? xs : g0;
+                int b3 = xe + 1 < g1 ? xe + 1 : g1;
+                if (b3 > a3) cov += b3 - a3;
+            }
+        }
+        // the arena already holds the zero-coverage label of the column ('0', or '2' when lo < 0): store only what differs
+        const unsigned char lab = cov >= t2.x ? '1' : (cov <= t2.y ? '0' : '2');
+        if (lab != (t2.y < 0 ? '2' : '0')) {
+            if (packed) {
+                const i64 g = row_g0 + c, w = g >> 4;
+                if (w != acc_w) { if (acc) atomicOr(&packed[acc_w], acc); acc_w = w; acc = 0; }
+                acc |= (unsigned)(lab - '0') << (2 * (int)(g & 15));
+            } else row[c] = lab;
+        }
+    }
+    if (acc) atomicOr(&packed[acc_w], acc);
+}
+
+__global__ void __launch_bounds__(256) k_label_reads_lds(int n_blocks, const int *rb_part, const int *rb_r0,
+                                                         const i64 *label_off, i64 label_cap, int n_part,
+                                                         const i64 *part_iv_off, const i64 *part_rep_off,
+                                                         const i64 *final_off, const int *final_pos, const int2 *col_thr,
+                                                         const i64 *rep_exon_off, const int *ex_ts, const int *ex_te,
+                                                         const unsigned char *col_zero, const int *part_has2,
+                                                         unsigned char *labels, unsigned *packed) {
+    __shared__ int fp_s[kLabelCols + 1];
+    __shared__ int2 th_s[kLabelCols];
+    __shared__ int2 ex_s[kLabelExons];
+    __shared__ int reo_s[kLabelReps + 1];
+    if (label_off[n_part] > label_cap) return;
+    for (i64 unit = blockIdx.x; unit < (i64)n_blocks * kLabelSplit; unit += gridDim.x) {
+        const int blk = (int)(unit / kLabelSplit), sub = (int)(unit % kLabelSplit);
+        const int p = rb_part[blk];
+        const i64 f0 = final_off[part_iv_off[p]];
+        const i64 S = final_off[part_iv_off[p + 1]] - f0 - 1;
+        if (S <= 0) continue;
+        const i64 r0 = (i64)rb_r0[blk] + sub * kLabelReps, r_end = part_rep_off[p + 1];
+        if (r0 >= r_end) continue;
+        const int *fp = final_pos + f0;                      // ascending over the whole partition
+        const int2 *th = col_thr + f0;
+        const LabelUnit u = label_unit(r0, r_end, rep_exon_off);
+        const bool cols_lds = S <= kLabelStage;
+        __syncthreads();                                     // the previous unit of this workgroup has read what it staged
+        if (cols_lds) {
+            for (int x = threadIdx.x; x <= S; x += blockDim.x) fp_s[x] = fp[x];
+            for (int x = threadIdx.x; x < S; x += blockDim.x) th_s[x] = th[x];
+        }
+        const bool exons_lds = label_stage_exons(u, r0, rep_exon_off, ex_ts, ex_te, reo_s, ex_s);
+        __syncthreads();
+        const i64 r = r0 + (threadIdx.x / kLabelSplit);
+        const int q = threadIdx.x % kLabelSplit;
+        if (!packed && part_has2[p]) {                       // uniform over the workgroup: the rows' defaults are not all '0'
+            if (r < r_end) {
+                unsigned char *row0 = labels + label_off[p] + (r - part_rep_off[p]) * S;
+                const unsigned char *cz = col_zero + f0;
+                for (i64 x = S * q / kLabelSplit; x < S * (q + 1) / kLabelSplit; ++x) row0[x] = cz[x];
+            }
+            __threadfence_block();
+            __syncthreads();                                 // the label stores below may hit bytes another thread just wrote
+        }
+        if (r >= r_end) continue;
+        const int e = reo_s[threadIdx.x / kLabelSplit], e1 = reo_s[threadIdx.x / kLabelSplit + 1];
+        if (e >= e1) continue;
+        const i64 row_g0 = label_off[p] + (r - part_rep_off[p]) * S;
+        unsigned char *row = labels + row_g0;
+        const int *ts_g = ex_ts + u.e_base, *te_g = ex_te + u.e_base;
+        if (cols_lds) {
+            if (exons_lds) label_rep<true, true>(fp, th, fp_s, th_s, ex_s, ts_g, te_g, e, e1, (int)S, q, row_g0, row, packed);
+            else label_rep<true, false>(fp, th, fp_s, th_s, ex_s, ts_g, te_g, e, e1, (int)S, q, row_g0, row, packed);
+        } else {
+            if (exons_lds) label_rep<false, true>(fp, th, fp_s, th_s, ex_s, ts_g, te_g, e, e1, (int)S, q, row_g0, row, packed);
+            else label_rep<false, false>(fp, th, fp_s, th_s, ex_s, ts_g, te_g, e, e1, (int)S, q, row_g0, row, packed);
+        }
+    }
+}
 
 
 // ---------------------------------------------------------------------------------------------

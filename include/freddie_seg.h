@@ -249,8 +249,9 @@ enum {
      *   31 k_thr_part_chain took the variance threshold (FSEG_THR_CHAIN, where word 5 is 1; 0: k_thr_part)
      *   32 lane_sort: how the last upload ordered the reps -- 0 k_lanes sorted every partition in LDS, 1 the batch-wide radix sort
      *      and k_lane_blocks / k_lane_block_scan / k_lane_emit (a partition of more than 2 048 reps, or FSEG_GLOBAL_SORT=1);
-     *      written by fseg_upload, kept by every run and replay of the batch */
-    FSEG_TAP_PATHS = 18,       /* int32[33]                                                                            */
+     *      written by fseg_upload, kept by every run and replay of the batch
+     *   33 label_lds: k_label_reads_lds wrote the labels (FSEG_LABEL_LDS; 0: k_label_reads) */
+    FSEG_TAP_PATHS = 18,       /* int32[34]                                                                            */
     /* the histogram chunks of the last upload, a row each: (p0, n, llo, lhi) -- the chunk's first batch position, its position
      * count, and the lanes [llo, lhi) of its partition that k_hist_ranges found able to reach it */
     FSEG_TAP_HIST_RANGES = 19  /* int64[n_hist_chunks][4]                                                              */
