@@ -116,8 +116,6 @@ struct fseg_ctx {
     int thr_part = -1;         // FSEG_THR_PART=0 / 1: the threshold per partition by one workgroup (k_thr_part) never / whenever possible; -1: batches of many partitions
     int hist16 = -1;           // FSEG_HIST16=0 / 1: S1 with 32-bit LDS counters always / with packed 16-bit ones wherever no count can overflow; -1: the same as 1
     bool hist_packed = false;  // the resident batch's chunks were planned for k_hist<16> (kHistChunk16 positions, every count <= 65 535)
-    int thr_chain = -1;        // FSEG_THR_CHAIN=0 / 1: k_thr_part as it was / k_thr_part_chain (the same additions, a shorter chain per partition); -1: the same as 1
-    int label_lds = -1;        // FSEG_LABEL_LDS=0 / 1: k_label_reads as it was / k_label_reads_lds (column table and the unit's exons read from LDS); -1: the same as 1
     i64 label_grid = 0;        // FSEG_LABEL_GRID=<n> (tests): the label launch takes at most n workgroups, so that one walks several units; 0: 65 536
     int yraw16 = -1;           // FSEG_YRAW16=0 / 1: the histogram in device memory int32 always / uint16 wherever S1 runs packed; -1: the same as 1
     bool yraw_narrow = false;  // the resident batch's d_y_raw holds uint16 (hist_packed and the switch): S1's output, S2's and S6's input
@@ -303,7 +301,7 @@ struct fseg_ctx {
     enum { PATH_SMALL_BATCH, PATH_TINY_ON, PATH_WAVE_ON, PATH_FUSE_ON, PATH_KEY32, PATH_THR_PART, PATH_LABEL_PACKED, PATH_N_SOLVE,
            PATH_N_WIDE = PATH_N_SOLVE + 3, PATH_N_TINY = PATH_N_WIDE + 3, PATH_N_WORK, PATH_DPW, PATH_WIDE16, PATH_KNOWN, PATH_SOLVE8,
            PATH_TINY_KERNEL, PATH_SCORE, PATH_ARENA_DP, PATH_PLAN, PATH_N_ARENA_PROB, PATH_N_SCORE, PATH_HIST16 = PATH_N_SCORE + 3, PATH_IV_THREADS,
-           PATH_SMOOTH_R, PATH_YRAW16, PATH_THR_CHAIN, PATH_LANE_SORT, PATH_LABEL_LDS, PATH_WORDS };
+           PATH_SMOOTH_R, PATH_YRAW16, PATH_LANE_SORT, PATH_WORDS };
     int paths[PATH_WORDS] = {};
     // fseg_annotate: the uploaded reads (one allocation, mirrored by a pinned image), per-read work arrays, the emitted lists, and
     // the pinned buffers fseg_annotation() points into (own allocations: nothing of a run or of fseg_results* touches them)
@@ -669,16 +667,10 @@ int enqueue_run(fseg_ctx *c, unsigned segs, bool sized = false, i64 label_fill_b
     const bool thr_part = thr_part_fits && (c->thr_part == 1 || (c->thr_part < 0 && n_part >= 64));
     if (thr_part) {
         c->paths[fseg_ctx::PATH_THR_PART] = 1;
-        c->paths[fseg_ctx::PATH_THR_CHAIN] = c->thr_chain != 0;
-        if (c->thr_chain != 0)
-            hipLaunchKernelGGL(k_thr_part_chain<kThrChainLevel>, dim3(grid_for(n_part, 1, 4096)), dim3(512), 0, q, n_part, c->d_part_iv_off.p,
-                               c->d_pos_off.p, NPOS, flag_pos_bits, c->d_y.p, c->d_v.p, c->P.variance_factor, c->d_mean.p, c->d_thr.p);
-        else
         hipLaunchKernelGGL(k_thr_part, dim3(grid_for(n_part, 1, 4096)), dim3(512), 0, q, n_part, c->d_part_iv_off.p, c->d_pos_off.p, NPOS,
                            flag_pos_bits, c->d_y.p, c->d_v.p, c->P.variance_factor, c->d_mean.p, c->d_thr.p);
     } else {
     c->paths[fseg_ctx::PATH_THR_PART] = 0;
-    c->paths[fseg_ctx::PATH_THR_CHAIN] = 0;
     scan_counts(q, bsum_side, flag_pos_bits, &st->n_vals, nullptr);
     hipLaunchKernelGGL(k_scan_emit<kEmitValues>, dim3(scan_grid), dim3(256), 0, q, flag_pos_bits, NPOS,
                        bsum_side, (const int *)nullptr, scan_state, &st->n_vals, (i64 *)nullptr, &st->err, c->d_y.p, c->d_v.p, K, c->d_pos_off.p,
@@ -774,7 +766,7 @@ int enqueue_run(fseg_ctx *c, unsigned segs, bool sized = false, i64 label_fill_b
     if (do_score) {
         for (int w = 0; w < fseg_ctx::PATH_WORDS; ++w)
             if (w != fseg_ctx::PATH_THR_PART && w != fseg_ctx::PATH_LABEL_PACKED && w != fseg_ctx::PATH_ARENA_DP && w != fseg_ctx::PATH_HIST16 &&
-                w != fseg_ctx::PATH_IV_THREADS && w != fseg_ctx::PATH_SMOOTH_R && w != fseg_ctx::PATH_YRAW16 && w != fseg_ctx::PATH_THR_CHAIN && w != fseg_ctx::PATH_LANE_SORT && w != fseg_ctx::PATH_LABEL_LDS) census[w] = 0;
+                w != fseg_ctx::PATH_IV_THREADS && w != fseg_ctx::PATH_SMOOTH_R && w != fseg_ctx::PATH_YRAW16 && w != fseg_ctx::PATH_LANE_SORT) census[w] = 0;
         census[fseg_ctx::PATH_SMALL_BATCH] = c->small_batch; census[fseg_ctx::PATH_TINY_ON] = c->tiny_on; census[fseg_ctx::PATH_WAVE_ON] = wave;
         census[fseg_ctx::PATH_FUSE_ON] = c->use_fuse && c->fuse_on; census[fseg_ctx::PATH_KNOWN] = known; census[fseg_ctx::PATH_PLAN] = plan != nullptr;
     }
@@ -1166,17 +1158,12 @@ int enqueue_run(fseg_ctx *c, unsigned segs, bool sized = false, i64 label_fill_b
                 hipLaunchKernelGGL(k_label_zero, dim3(grid_for(n16 / 8 + 1, 256, 4096)), dim3(256), 0, s, c->d_labels.as<uint4>(), n16);
         }
         const int lab_grid = grid_for((i64)c->n_rep_blocks * kLabelSplit, 1, c->label_grid > 0 && c->label_grid < 65536 ? c->label_grid : 65536);
-        c->paths[fseg_ctx::PATH_LABEL_LDS] = c->label_lds != 0;
-#define FSEG_LAUNCH_LABEL(KERNEL)                                                                                       \
-        hipLaunchKernelGGL(KERNEL, dim3(lab_grid), dim3(256), 0, s, c->n_rep_blocks,                                    \
-                           c->d_rb_part.p, c->d_rb_r0.p, c->d_label_off.p, c->label_cap, n_part,                        \
-                           c->d_part_iv_off.p, c->d_part_rep_off.p, c->d_final_off.p,                                   \
-                           c->d_final_pos.p, c->d_col_thr.p, c->d_rep_exon_off.p,                                       \
-                           c->d_ex_ts.p, c->d_ex_te.p, c->d_col_zero.p,                                                 \
-                           c->d_part_has2.p, c->d_labels.as<unsigned char>(), lab_packed ? c->d_packed.p : (unsigned *)nullptr)
-        if (c->label_lds != 0) { FSEG_LAUNCH_LABEL(k_label_reads_lds); }
-        else { FSEG_LAUNCH_LABEL(k_label_reads); }
-#undef FSEG_LAUNCH_LABEL
+        hipLaunchKernelGGL(k_label_reads, dim3(lab_grid), dim3(256), 0, s, c->n_rep_blocks,
+                           c->d_rb_part.p, c->d_rb_r0.p, c->d_label_off.p, c->label_cap, n_part,
+                           c->d_part_iv_off.p, c->d_part_rep_off.p, c->d_final_off.p,
+                           c->d_final_pos.p, c->d_col_thr.p, c->d_rep_exon_off.p,
+                           c->d_ex_ts.p, c->d_ex_te.p, c->d_col_zero.p,
+                           c->d_part_has2.p, c->d_labels.as<unsigned char>(), lab_packed ? c->d_packed.p : (unsigned *)nullptr);
     }
     end(ST_LABEL);
     }   // do_post2
@@ -1562,10 +1549,8 @@ void read_switches(fseg_ctx *c) {
     if (env_off("FSEG_DEV_SYNC")) c->dev_sync = false;
     if (env_flag("FSEG_LABEL_BYTES")) c->label_packed_ok = false;
     env_tri("FSEG_THR_PART", c->thr_part);
-    env_tri("FSEG_THR_CHAIN", c->thr_chain);
     env_tri("FSEG_HIST16", c->hist16);
     env_tri("FSEG_YRAW16", c->yraw16);
-    env_tri("FSEG_LABEL_LDS", c->label_lds);
     if (env_int("FSEG_LABEL_GRID", v) && v > 0) c->label_grid = v;
     if (env_int("FSEG_SYNC_TICKS", v) && v > 0) c->sync_ticks = (unsigned)v;
     if (env_flag("FSEG_NO_GRAPH")) c->use_graph = false;

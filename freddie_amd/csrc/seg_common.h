@@ -516,11 +516,7 @@ __device__ __forceinline__ double vsum_chunk(const double *a, int m, int pass, d
                 int body = len - (len % 8);
                 double x[16];
 #pragma unroll
-#ifdef FSEG_LAB_NOREREAD                                         // (timing experiment: the second pass loads nothing)
-                for (int i = 0; i < 16; ++i) x[i] = (8 * i + q < body) ? (pass ? __hiloint2double(0x40300000 + i, (int)threadIdx.x) : b[8 * i + q]) : 0.0;
-#else
                 for (int i = 0; i < 16; ++i) x[i] = (8 * i + q < body) ? b[8 * i + q] : 0.0;
-#endif
                 double r = FSEG_VAL(x[0]);
 #pragma unroll
                 for (int i = 1; i < 16; ++i) if (8 * i + q < body) r = __dadd_rn(r, FSEG_VAL(x[i]));
@@ -557,7 +553,7 @@ __device__ __forceinline__ double vsum_chunk(const double *a, int m, int pass, d
 
 // The whole threshold of a partition by ONE 512-thread workgroup (round 5; batches of many partitions of moderate size): the
 // partition's Y > 0 values are compacted into its own piece of v (it starts where the partition's positions start: no batch-wide
-// scan, no offsets), summed chunk by chunk in numpy's order (vsum_chunk, the same function the chunk kernel uses), the mean,
+// scan, no offsets), summed chunk by chunk in numpy's order (the additions of vsum_chunk, which the chunk kernel uses), the mean,
 // the squared deviations likewise, the threshold.  One launch instead of seven to nine (k_scan1 / k_scan2 / k_scan_emit<values>,
 // k_voff, k_vplan, k_vsum_chunks twice, k_vsum_part): 0.106 ms of launch-latency-sized pieces per 250 k-read batch.
 constexpr int kThrPartMaxChunks = 128;     // chunk sums a workgroup keeps in LDS: partitions of up to 2^20 positions
@@ -566,17 +562,16 @@ constexpr int kThrPartMaxChunks = 128;     // chunk sums a workgroup keeps in LD
 // into v[ex ..) and returns their number.  Rows of 64 positions (lane = column), so the loads of y and the stores are coalesced;
 // a row's 64 flags are the words of lanes 2q and 2q + 1 (two readlanes); rows without a flag are skipped (the values Y > 0 come
 // in runs of 2 * radius + 1 around the splice sites) and the values of eight rows are loaded together from clamped addresses.
-// kLds (k_thr_part_chain): the first kThrLdsVals values of the partition go to the LDS array lv instead (thr_lds_slot), ex counting
-// from the partition's first value.
+// The first kThrLdsVals values of the partition go to the LDS array lv instead (thr_lds_slot), ex counting from the partition's
+// first value.
 constexpr int kThrLdsVals = 8192;          // one full chunk: a leaf of the pairwise recursion lies in LDS whole or not at all
 // eight doubles of padding per 128: the eight leaves a wave reads together (128 values apart in a full chunk) start on eight
 // different 16-bank groups of the 64-bank LDS instead of on one
 __device__ __forceinline__ int thr_lds_slot(int i) { return i + ((i >> 7) << 3); }
 constexpr int kThrLdsSlots = kThrLdsVals + (kThrLdsVals >> 7) * 8;
 
-template <bool kLds = false>
 __device__ __forceinline__ int wave_emit_values(i64 w0, i64 n_pos, unsigned fm, i64 ex, const double *__restrict__ y, double *v,
-                                                double *lv = nullptr) {
+                                                double *lv) {
     const int lane = lane_id();
     const u64 lt_mask = (1ULL << lane) - 1ULL;
     u64 rows;
@@ -607,26 +602,18 @@ __device__ __forceinline__ int wave_emit_values(i64 w0, i64 n_pos, unsigned fm, 
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
             if (!m[e]) continue;
-#ifdef FSEG_LAB_NOSTORE                                          // (timing experiment: the loads stay, no value is stored)
-            if (((m[e] >> lane) & 1ULL) && yv[e] == -12345.678) v[ex + cnt + __popcll(m[e] & lt_mask)] = yv[e];
-#else
             if ((m[e] >> lane) & 1ULL) {
                 const i64 idx = ex + cnt + __popcll(m[e] & lt_mask);
-                if (kLds && idx < kThrLdsVals) lv[thr_lds_slot((int)idx)] = yv[e];
+                if (idx < kThrLdsVals) lv[thr_lds_slot((int)idx)] = yv[e];
                 else v[idx] = yv[e];
             }
-#endif
             cnt += __popcll(m[e]);
         }
     }
     return cnt;
 }
 
-// ---- k_thr_part_chain: vsum_chunk's additions in vsum_chunk's order, with fewer barriers and round trips between them ----------
-#ifndef FSEG_LAB_CHAIN_LEVEL
-#define FSEG_LAB_CHAIN_LEVEL 5
-#endif
-constexpr int kThrChainLevel = FSEG_LAB_CHAIN_LEVEL;      // the k_thr_part_chain instance the product launches (seg_front.hip)
+// ---- k_thr_part: vsum_chunk's additions in vsum_chunk's order, with fewer barriers and round trips between them ----------------
 constexpr int kThrKeepGroups = 8;          // flag words a lane keeps from the count loop for the emit loop (its wave's first groups)
 constexpr int kThrSweepChunks = 4;         // chunks whose leaves are summed in one sweep (their leaf sums are in LDS together)
 
@@ -710,7 +697,6 @@ __device__ __forceinline__ double thr_leaf_sum(int len, int q, int pass, double 
 // share the rounds of 64 leaf slots; then wave j folds chunk c0 + j -- a full chunk's 64 leaf sums by the xor butterfly, the
 // partial chunk's heap bottom-up with wave-level synchronisation (level 7 holds leaves only).  The caller has a barrier before
 // (values visible, full_val / node_val free) and after (cs visible).
-template <bool kLds>
 __device__ __forceinline__ void thr_sweep(const double *vp, const double *lv, int c0, int nsw, int nfull, int pass, double mu,
                                           ThrChainLds &L, double *cs) {
     const int lane = lane_id(), wave = threadIdx.x >> 6, q = threadIdx.x & 7;
@@ -723,7 +709,7 @@ __device__ __forceinline__ void thr_sweep(const double *vp, const double *lv, in
         if (t < nlf) { off = c0 * 8192 + t * 128; len = 128; dst = &L.full_val[t >> 6][t & 63]; }
         else { const int r = t - nlf; off = (c0 + nfull) * 8192 + L.leaf_off[r]; len = L.leaf_len[r]; dst = &L.node_val[L.leaf_heap[r]]; }
         double res;
-        if (kLds && off < kThrLdsVals) res = thr_leaf_sum(len, q, pass, mu, [&](int k) { return lv[thr_lds_slot(off + k)]; });
+        if (off < kThrLdsVals) res = thr_leaf_sum(len, q, pass, mu, [&](int k) { return lv[thr_lds_slot(off + k)]; });
         else res = thr_leaf_sum(len, q, pass, mu, [&](int k) { return vp[off + k]; });
         if (q == 0) *dst = res;
     }
@@ -1779,8 +1765,8 @@ constexpr int kLabelStage = FSEG_LABEL_STAGE;
 
 constexpr int kLabelSplit = 4;
 
-// k_label_reads_lds (FSEG_LABEL_LDS, the default): the exons of a workgroup's 64 reps are one contiguous run of ex_ts / ex_te; a run
-// of up to kLabelExons is staged in LDS beside the column table (a longer one is read from global memory, as k_label_reads does).
+// k_label_reads: the exons of a workgroup's 64 reps are one contiguous run of ex_ts / ex_te; a run of up to kLabelExons is staged
+// in LDS beside the column table (a longer one is read from global memory).
 // 960: 4 100 + 8 192 B of columns, 260 B of rep offsets and 7 680 B of exons are 20 232 B, eight workgroups a CU (20 480 B each) as before.
 constexpr int kLabelReps = 256 / kLabelSplit;
 #ifndef FSEG_LABEL_EXONS

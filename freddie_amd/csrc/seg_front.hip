@@ -734,86 +734,19 @@ __global__ void __launch_bounds__(512) k_vsum_chunks(int n_part, const i64 *voff
     }
 }
 
+// The whole threshold of a partition by one workgroup (seg_common.h), vsum_chunk's IEEE operations in vsum_chunk's order, so
+// thresholds and means have the chunk path's bits; what keeps the chain per partition short (profiles/thr_chain.txt):
+//   * a wave keeps the flag words of its first kThrKeepGroups groups from the count loop for the emit loop
+//   * the partial chunk's leaf table is built once per partition, by wave 7 beside the compaction; the leaves of up to
+//     kThrSweepChunks chunks are summed in one sweep and a wave folds each chunk (thr_sweep); every thread adds the chunk sums
+//     itself, so no mean is handed round: six workgroup barriers a partition of up to four chunks
+//   * the partition's first kThrLdsVals values stay in LDS (70 KB: two workgroups a CU) and never see v
 __global__ void __launch_bounds__(512) k_thr_part(int n_part, const i64 *part_iv_off, const i64 *pos_off, i64 n_pos, const unsigned *flags,
                                                   const double *__restrict__ y, double *v, double vf, double *mean, double *thr) {
-    __shared__ VsumLds L;
+    __shared__ ThrChainLds L;
+    __shared__ double lv[kThrLdsSlots];
     __shared__ int wave_cnt[8];
     __shared__ double cs[kThrPartMaxChunks];
-    __shared__ double mu_s;
-    const int lane = lane_id(), wave = threadIdx.x >> 6;
-    for (int p = blockIdx.x; p < n_part; p += gridDim.x) {
-        const i64 pos0 = pos_off[part_iv_off[p]], pos1 = pos_off[part_iv_off[p + 1]];
-        double *vp = v + pos0;
-        // compaction: the partition's flag words in groups of 64 (2048 positions), every wave an eighth of the groups
-        const i64 wbeg = pos0 >> 5, wend = (pos1 + 31) >> 5;
-        const i64 groups = (wend - wbeg + 63) / 64, gpw = (groups + 7) / 8;
-        const i64 g0 = (i64)wave * gpw, g1 = g0 + gpw < groups ? g0 + gpw : groups;
-        auto flag_word = [&](i64 wd) -> unsigned {
-            if (wd >= wend) return 0u;
-            unsigned f = flags[wd];
-            const i64 i0 = wd << 5;
-            if (i0 < pos0) f &= ~0u << (int)(pos0 - i0);
-            if (i0 + 32 > pos1) f &= (1u << (int)(pos1 - i0)) - 1u;
-            return f;
-        };
-        int cnt = 0;
-        for (i64 g = g0; g < g1; ++g) cnt += __popc(flag_word(wbeg + g * 64 + lane));
-        for (int d = 32; d >= 1; d >>= 1) cnt += __shfl_xor(cnt, d);
-        if (lane == 0) wave_cnt[wave] = cnt;
-        __syncthreads();
-        i64 ex = 0;
-        int nv = 0;
-        for (int w = 0; w < 8; ++w) { if (w < wave) ex += wave_cnt[w]; nv += wave_cnt[w]; }
-        for (i64 g = g0; g < g1; ++g) ex += wave_emit_values((wbeg + g * 64) << 5, n_pos, flag_word(wbeg + g * 64 + lane), ex, y, vp);
-        __builtin_amdgcn_s_waitcnt(0);                  // the values are read back by other waves of this workgroup
-        __syncthreads();
-#ifdef FSEG_LAB_NOSUMS                                           // (timing experiment: the compaction alone)
-        const int nch = 0;
-#else
-        const int nch = (nv + 8191) / 8192;
-#endif
-        double s_acc[2] = {0.0, 0.0};
-        for (int pass = 0; pass < 2; ++pass) {
-            const double mu = pass ? mu_s : 0.0;
-            for (int c = 0; c < nch; ++c) {
-                const int m = nv - c * 8192 < 8192 ? nv - c * 8192 : 8192;
-                const double x = vsum_chunk(vp + (i64)c * 8192, m, pass, mu, L);
-                if (threadIdx.x == 0) cs[c] = x;
-            }
-            if (threadIdx.x == 0) {
-                double sacc = 0.0;
-                for (int c = 0; c < nch; ++c) sacc = c == 0 ? cs[0] : __dadd_rn(sacc, cs[c]);     // numpy adds its chunks left to right
-                s_acc[pass] = sacc;
-                if (pass == 0) mu_s = sacc / (double)nv;                                         // empty -> 0/0 = NaN like numpy
-            }
-            __syncthreads();
-        }
-        if (threadIdx.x == 0) {
-            const double mu = mu_s;
-            mean[p] = mu;
-            thr[p] = __dadd_rn(mu, __dmul_rn(vf, __dsqrt_rn(s_acc[1] / (double)nv)));             // :758-759
-        }
-        __syncthreads();
-    }
-}
-
-// k_thr_part with a shorter chain per partition (FSEG_THR_CHAIN, the default; profiles/thr_chain.txt): the same IEEE operations in
-// the same order, so thresholds and means have k_thr_part's bits.
-//   kLevel >= 1  a wave keeps the flag words of its first kThrKeepGroups groups from the count loop for the emit loop
-//   kLevel >= 4  the partial chunk's leaf table is built once per partition, by one wave beside the compaction; the leaves of up to
-//                kThrSweepChunks chunks are summed in one sweep and a wave folds each chunk (thr_sweep); every thread adds the chunk
-//                sums itself, so no mean is handed round: six workgroup barriers a partition of up to four chunks, it was about 36
-//   kLevel >= 5  the partition's first kThrLdsVals values stay in LDS (70 KB: two workgroups a CU as before) and never see v
-// The product launches kThrChainLevel; the lower levels are what the steps were timed with (-DFSEG_LAB_CHAIN_LEVEL).
-template <int kLevel>
-__global__ void __launch_bounds__(512) k_thr_part_chain(int n_part, const i64 *part_iv_off, const i64 *pos_off, i64 n_pos, const unsigned *flags,
-                                                        const double *__restrict__ y, double *v, double vf, double *mean, double *thr) {
-    constexpr bool kSweep = kLevel >= 4, kLds = kLevel >= 5;
-    __shared__ std::conditional_t<kSweep, ThrChainLds, VsumLds> L;
-    __shared__ double lv[kLds ? kThrLdsSlots : 1];
-    __shared__ int wave_cnt[8];
-    __shared__ double cs[kThrPartMaxChunks];
-    __shared__ double mu_s;
     const int lane = lane_id(), wave = threadIdx.x >> 6;
     for (int p = blockIdx.x; p < n_part; p += gridDim.x) {
         const i64 pos0 = pos_off[part_iv_off[p]], pos1 = pos_off[part_iv_off[p + 1]];
@@ -845,64 +778,39 @@ __global__ void __launch_bounds__(512) k_thr_part_chain(int n_part, const i64 *p
         for (int w = 0; w < 8; ++w) { if (w < wave) ex += wave_cnt[w]; nv += wave_cnt[w]; }
         const int nch = (nv + 8191) / 8192, nfull = nv / 8192;
         // (the last wave has the fewest groups where they do not divide by eight)
-        if constexpr (kSweep) if (wave == 7 && nch > nfull) thr_leaf_table(nv - nfull * 8192, L);
+        if (wave == 7 && nch > nfull) thr_leaf_table(nv - nfull * 8192, L);
 #pragma nounroll
         for (int j = 0; j < kThrKeepGroups && g0 + j < g1; ++j) {
             unsigned f = fk[0];
 #pragma unroll
             for (int k = 1; k < kThrKeepGroups; ++k) f = j == k ? fk[k] : f;
-            ex += wave_emit_values<kLds>((wbeg + (g0 + j) * 64) << 5, n_pos, f, ex, y, vp, lv);
+            ex += wave_emit_values((wbeg + (g0 + j) * 64) << 5, n_pos, f, ex, y, vp, lv);
         }
         for (i64 g = g0 + kThrKeepGroups; g < g1; ++g)
-            ex += wave_emit_values<kLds>((wbeg + g * 64) << 5, n_pos, flag_word(wbeg + g * 64 + lane), ex, y, vp, lv);
+            ex += wave_emit_values((wbeg + g * 64) << 5, n_pos, flag_word(wbeg + g * 64 + lane), ex, y, vp, lv);
         __builtin_amdgcn_s_waitcnt(0);                  // the values are read back by other waves of this workgroup
         __syncthreads();
-        if constexpr (kSweep) {
-            double mu = 0.0, s1 = 0.0;
-            for (int pass = 0; pass < 2; ++pass) {
-                for (int c0 = 0; c0 < nch; c0 += kThrSweepChunks) {
-                    if (c0) __syncthreads();            // the folds of the sweep before are done with full_val
-                    const int nsw = nch - c0 < kThrSweepChunks ? nch - c0 : kThrSweepChunks;
-                    const int nf = nfull - c0 < nsw ? nfull - c0 : nsw;
-                    thr_sweep<kLds>(vp, lv, c0, nsw, nf, pass, mu, L, cs);
-                }
-                __syncthreads();
-                double sacc = 0.0;                      // every thread for itself: the same additions, nothing to hand round
-                for (int c = 0; c < nch; ++c) sacc = c == 0 ? cs[0] : __dadd_rn(sacc, cs[c]);     // numpy adds its chunks left to right
-                if (pass == 0) mu = sacc / (double)nv;                                           // empty -> 0/0 = NaN like numpy
-                else s1 = sacc;
-            }
-            if (threadIdx.x == 0) {
-                mean[p] = mu;
-                thr[p] = __dadd_rn(mu, __dmul_rn(vf, __dsqrt_rn(s1 / (double)nv)));               // :758-759
-            }
-            // (no barrier here: between this partition's last read of an LDS word and the next partition's write to it lies a
-            //  barrier every wave takes -- wave_cnt is read before the compaction, the table, lv, full_val and node_val before
-            //  pass 1's last barrier, and cs, read behind that barrier, is next written behind the next partition's third)
-        } else {
-            double s_acc[2] = {0.0, 0.0};
-            for (int pass = 0; pass < 2; ++pass) {
-                const double mu = pass ? mu_s : 0.0;
-                for (int c = 0; c < nch; ++c) {
-                    const int m = nv - c * 8192 < 8192 ? nv - c * 8192 : 8192;
-                    const double x = vsum_chunk(vp + (i64)c * 8192, m, pass, mu, L);
-                    if (threadIdx.x == 0) cs[c] = x;
-                }
-                if (threadIdx.x == 0) {
-                    double sacc = 0.0;
-                    for (int c = 0; c < nch; ++c) sacc = c == 0 ? cs[0] : __dadd_rn(sacc, cs[c]);
-                    s_acc[pass] = sacc;
-                    if (pass == 0) mu_s = sacc / (double)nv;
-                }
-                __syncthreads();
-            }
-            if (threadIdx.x == 0) {
-                const double mu = mu_s;
-                mean[p] = mu;
-                thr[p] = __dadd_rn(mu, __dmul_rn(vf, __dsqrt_rn(s_acc[1] / (double)nv)));
+        double mu = 0.0, s1 = 0.0;
+        for (int pass = 0; pass < 2; ++pass) {
+            for (int c0 = 0; c0 < nch; c0 += kThrSweepChunks) {
+                if (c0) __syncthreads();            // the folds of the sweep before are done with full_val
+                const int nsw = nch - c0 < kThrSweepChunks ? nch - c0 : kThrSweepChunks;
+                const int nf = nfull - c0 < nsw ? nfull - c0 : nsw;
+                thr_sweep(vp, lv, c0, nsw, nf, pass, mu, L, cs);
             }
             __syncthreads();
+            double sacc = 0.0;                      // every thread for itself: the same additions, nothing to hand round
+            for (int c = 0; c < nch; ++c) sacc = c == 0 ? cs[0] : __dadd_rn(sacc, cs[c]);     // numpy adds its chunks left to right
+            if (pass == 0) mu = sacc / (double)nv;                                           // empty -> 0/0 = NaN like numpy
+            else s1 = sacc;
         }
+        if (threadIdx.x == 0) {
+            mean[p] = mu;
+            thr[p] = __dadd_rn(mu, __dmul_rn(vf, __dsqrt_rn(s1 / (double)nv)));               // :758-759
+        }
+        // (no barrier here: between this partition's last read of an LDS word and the next partition's write to it lies a
+        //  barrier every wave takes -- wave_cnt is read before the compaction, the table, lv, full_val and node_val before
+        //  pass 1's last barrier, and cs, read behind that barrier, is next written behind the next partition's third)
     }
 }
 
@@ -953,7 +861,6 @@ __attribute__((used)) static const void *const kInstances[] = {
     reinterpret_cast<const void *>(&k_smooth<0, uint16_t>),
     reinterpret_cast<const void *>(&k_scan_emit<kEmitValues>),
     reinterpret_cast<const void *>(&k_scan_emit<kEmitPositions>),
-    reinterpret_cast<const void *>(&k_thr_part_chain<kThrChainLevel>),
 };
 
 }  // namespace fseg

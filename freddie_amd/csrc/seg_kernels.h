@@ -64,9 +64,6 @@ __global__ void __launch_bounds__(512) k_vsum_chunks(int n_part, const i64 *voff
 // seg_front.hip
 __global__ void __launch_bounds__(512) k_thr_part(int n_part, const i64 *part_iv_off, const i64 *pos_off, i64 n_pos, const unsigned *flags,
                                                   const double *__restrict__ y, double *v, double vf, double *mean, double *thr);
-template <int kLevel>
-__global__ void __launch_bounds__(512) k_thr_part_chain(int n_part, const i64 *part_iv_off, const i64 *pos_off, i64 n_pos, const unsigned *flags,
-                                                        const double *__restrict__ y, double *v, double vf, double *mean, double *thr);
 
 // seg_front.hip
 __global__ void k_vsum_part(int n_part, const i64 *voff, const i64 *chunk_off, const double *csum0, const double *csum1,
@@ -240,13 +237,6 @@ __global__ void __launch_bounds__(256) k_label_reads(int n_blocks, const int *rb
                                                      const i64 *rep_exon_off, const int *ex_ts, const int *ex_te,
                                                      const unsigned char *col_zero, const int *part_has2,
                                                      unsigned char *labels, unsigned *packed);
-__global__ void __launch_bounds__(256) k_label_reads_lds(int n_blocks, const int *rb_part, const int *rb_r0,
-                                                         const i64 *label_off, i64 label_cap, int n_part,
-                                                         const i64 *part_iv_off, const i64 *part_rep_off,
-                                                         const i64 *final_off, const int *final_pos, const int2 *col_thr,
-                                                         const i64 *rep_exon_off, const int *ex_ts, const int *ex_te,
-                                                         const unsigned char *col_zero, const int *part_has2,
-                                                         unsigned char *labels, unsigned *packed);
 __global__ void __launch_bounds__(256) k_unpack_labels(const unsigned *__restrict__ packed, uint4 *__restrict__ labels16, i64 n16);
 
 // seg_tail.hip

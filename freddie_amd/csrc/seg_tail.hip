@@ -395,142 +395,23 @@ __global__ void __launch_bounds__(256) k_label_zero(uint4 *labels16, i64 n16) {
     fill_labels(labels16, n16, (i64)blockIdx.x * blockDim.x + threadIdx.x, (i64)gridDim.x * blockDim.x);
 }
 
-__global__ void __launch_bounds__(256) k_label_reads(int n_blocks, const int *rb_part, const int *rb_r0,
-                                                     const i64 *label_off, i64 label_cap, int n_part,
-                                                     const i64 *part_iv_off, const i64 *part_rep_off,
-                                                     const i64 *final_off, const int *final_pos, const int2 *col_thr,
-                                                     const i64 *rep_exon_off, const int *ex_ts, const int *ex_te,
-                                                     const unsigned char *col_zero, const int *part_has2,
-                                                     unsigned char *labels, unsigned *packed) {
-    // packed != nullptr: the labels are written at two bits each into a cleared arena (label g at bits 2 (g & 15) .. of word g >> 4,
-    // the layout fseg_results_packed delivers): a thread walks consecutive columns of its rep's row, collects the codes of a word
-    // in a register and ORs the word in when it moves on.  Only where no column's default is '2' (the host: no table entry and no rate >= 1, label_has2).
-    __shared__ int fp_s[kLabelCols + 1];
-    __shared__ int2 th_s[kLabelCols];
-    if (label_off[n_part] > label_cap) return;
-    for (i64 unit = blockIdx.x; unit < (i64)n_blocks * kLabelSplit; unit += gridDim.x) {
-        const int blk = (int)(unit / kLabelSplit), sub = (int)(unit % kLabelSplit);
-        int p = rb_part[blk];
-        i64 f0 = final_off[part_iv_off[p]];
-        i64 F = final_off[part_iv_off[p + 1]] - f0;
-        i64 S = F - 1;
-        if (S <= 0) continue;
-        if ((i64)rb_r0[blk] + sub * (256 / kLabelSplit) >= part_rep_off[p + 1]) continue;
-        const int *fp = final_pos + f0;                      // ascending over the whole partition
-        const int2 *th = col_thr + f0;
-        __syncthreads();
-        // short column tables are staged in LDS; a long table stays in global memory (a read only visits the few
-        // columns around its exons, and staging the whole table per workgroup would cost more than it saves)
-        if (S <= kLabelStage) {
-            for (int x = threadIdx.x; x <= S; x += blockDim.x) fp_s[x] = fp[x];
-            for (int x = threadIdx.x; x < S; x += blockDim.x) th_s[x] = th[x];
-            fp = fp_s; th = th_s;
-        }
-        __syncthreads();
-        i64 r = (i64)rb_r0[blk] + sub * (256 / kLabelSplit) + (threadIdx.x / kLabelSplit);
-        const int q = threadIdx.x % kLabelSplit;
-#ifdef FSEG_LAB_NOSEARCH
-        if (fp[0] != -12345) continue;                       // diagnostic build (wrong results): the workgroup's staging only
-#endif
-        if (!packed && part_has2[p]) {                       // uniform over the workgroup: the rows' defaults are not all '0'
-            if (r < part_rep_off[p + 1]) {
-                unsigned char *row0 = labels + label_off[p] + (r - part_rep_off[p]) * S;
-                const unsigned char *cz = col_zero + f0;
-                for (i64 x = S * q / kLabelSplit; x < S * (q + 1) / kLabelSplit; ++x) row0[x] = cz[x];
-            }
-            __threadfence_block();
-            __syncthreads();                                 // the label stores below may hit bytes another thread just wrote
-        }
-        if (r >= part_rep_off[p + 1]) continue;
-        const i64 row_g0 = label_off[p] + (r - part_rep_off[p]) * S;
-        unsigned char *row = labels + row_g0;
-        unsigned acc = 0;
-        i64 acc_w = -1;
-        i64 e = rep_exon_off[r], e1 = rep_exon_off[r + 1];
-        if (e >= e1) continue;
-#ifdef FSEG_LAB_NOEXON
-        // diagnostic build (wrong results): exon k of a rep is computed from the rep and the partition's average column width w --
-        // [3 w k', 3 w k' + 2 w] from the partition's first position, k' = k + 3 (r mod 64): every exon read below is arithmetic,
-        // the spans and the exons per column stay about what a config4 batch has (some 20 columns, a third of them uncovered)
-        const int fk_w = max(1, (fp[S] - fp[0]) / (int)S), fk_0 = fp[0] + 9 * fk_w * (int)(r & 63);
-        const i64 fk_e = e;
-#define LAB_TS(i) (fk_0 + 3 * fk_w * (int)((i) - fk_e))
-#define LAB_TE(i) (LAB_TS(i) + 2 * fk_w)
-#else
-#define LAB_TS(i) ex_ts[i]
-#define LAB_TE(i) ex_te[i]
-#endif
-        int first_ts = LAB_TS(e), last_te = LAB_TE(e1 - 1);
-        // first column whose segment [fp[c], fp[c+1]) ends after first_ts
-        int lo = 0, hi = (int)S;
-        while (lo < hi) { int mid = (lo + hi) >> 1; if (fp[mid + 1] <= first_ts) lo = mid + 1; else hi = mid; }
-        // first column that starts after last_te
-        int c_hi = lo; hi = (int)S;
-        while (c_hi < hi) { int mid = (c_hi + hi) >> 1; if (fp[mid] <= last_te) c_hi = mid + 1; else hi = mid; }
-        // this thread's share of [lo, c_hi)
-        const int span = c_hi - lo;
-        const int c_a = lo + (int)((i64)span * q / kLabelSplit), c_b = lo + (int)((i64)span * (q + 1) / kLabelSplit);
-        if (c_a >= c_b) continue;
-#ifdef FSEG_LAB_NOLOOP
-        if (c_a != -12345) { if (c_b == 0x7ffffff0) atomicOr(&packed[0], 1u); continue; }    // diagnostic build (wrong results): no column loop
-#endif
-        if (q) {                                             // first exon that reaches the first column of the share
-            const int g = fp[c_a];
-            i64 a = e, b = e1;
-            while (a < b) { i64 mid = (a + b) >> 1; if (LAB_TE(mid) < g) a = mid + 1; else b = mid; }
-            e = a;
-        }
-        int ts = 0, te = 0;
-        if (e < e1) { ts = LAB_TS(e); te = LAB_TE(e); }
-        for (int c = c_a; c < c_b; ++c) {
-            int2 t2 = th[c];
-            if (t2.x == 0x7fffffff) continue;                 // sentinel column between two intervals
-            int g0 = fp[c], g1 = fp[c + 1];
-            while (e < e1 && te < g0) { ++e; if (e < e1) { ts = LAB_TS(e); te = LAB_TE(e); } }   // exons before the segment
-            int cov = 0;
-            if (e < e1 && ts < g1) {
-                int a = ts > g0 ? ts : g0, b2 = te + 1 < g1 ? te + 1 : g1;
-                if (b2 > a) cov += b2 - a;
-                for (i64 x = e + 1; x < e1 && LAB_TS(x) < g1; ++x) {
-                    int a3 = LAB_TS(x) > g0 ? LAB_TS(x) : g0;
-                    int b3 = LAB_TE(x) + 1 < g1 ? LAB_TE(x) + 1 : g1;
-                    if (b3 > a3) cov += b3 - a3;
-                }
-            }
-            // the arena already holds the zero-coverage label of the column ('0', or '2' when lo < 0): store only what differs
-            const unsigned char lab = cov >= t2.x ? '1' : (cov <= t2.y ? '0' : '2');
-            if (lab != (t2.y < 0 ? '2' : '0')) {
-                if (packed) {
-                    const i64 g = row_g0 + c, w = g >> 4;
-#ifdef FSEG_LAB_NOSTORE
-                    if (w != acc_w) { acc_w = w; }           // diagnostic build (wrong results): one store per thread
-#else
-                    if (w != acc_w) { if (acc) atomicOr(&packed[acc_w], acc); acc_w = w; acc = 0; }
-#endif
-                    acc |= (unsigned)(lab - '0') << (2 * (int)(g & 15));
-                } else row[c] = lab;
-            }
-        }
-        if (acc) atomicOr(&packed[acc_w], acc);
-    }
-#undef LAB_TS
-#undef LAB_TE
-}
-
-
 // (Round 5, measured and not kept: the (rep, column) pairs of a workgroup's 64 reps as ONE list walked by its 256 threads -- every
 // thread the same number of pairs, the reps' exons in LDS, a word's codes OR-ed across lanes before one atomic -- parity-green,
 // 78 us against 73: finding a pair's rep, walking its exons from the first and the cross-lane OR cost more per pair than the
-// balance saves.  Of k_label_reads' 73 us 41 are the column loop, 13 its stores, 9 the bisections, 10 the workgroup's staging
-// (tools/probes/label_ablate.sh with the FSEG_LAB_NO* builds).)
+// balance saves.  Of the 73 us of k_label_reads as it was then, 41 were the column loop, 13 its stores, 9 the bisections, 10 the
+// workgroup's staging (HISTORY.md, round 5).)
 
 
-// k_label_reads with its operands in LDS (FSEG_LABEL_LDS, the default; profiles/label_lds.txt).  The same comparisons, the same
-// cov sums and the same store rule; what changes is where fp / th / the exons are read from:
-//   COLS_LDS   the column table is indexed as the LDS array it is.  (k_label_reads selects `fp = fp_s` at run time, which makes fp a
-//              generic pointer: both bisections and the column loop are FLAT loads there, never a ds_read.)
-//   EXONS_LDS  the exons of the unit's 64 reps -- one contiguous run of ex_ts / ex_te -- are staged with coalesced loads beside the
-//              column table, as (ts, te) pairs, and every exon read is a ds_read at a unit-local int index.
+// k_label_reads: a workgroup takes units of 64 reps of one partition, four threads a rep; a thread bisects its rep's exons for the
+// columns they can reach, takes a quarter of those columns and merges exons and columns into coverage sums and labels.  Where they
+// fit, the operands are read from LDS (profiles/label_lds.txt):
+//   COLS_LDS   a column table of up to kLabelStage columns is staged and indexed as the LDS array it is.  (Selecting `fp = fp_s` or
+//              the global table at run time was slow: it makes fp a generic pointer, so both bisections and the column loop are
+//              FLAT loads, never a ds_read.)  A long table stays in global memory: a read only visits the few columns around its
+//              exons, and staging the whole table per workgroup would cost more than it saves.
+//   EXONS_LDS  the exons of the unit's 64 reps -- one contiguous run of ex_ts / ex_te, of up to kLabelExons -- are staged with
+//              coalesced loads beside the column table, as (ts, te) pairs, and every exon read is a ds_read at a unit-local int
+//              index.  A longer run is read from global memory.
 // Both flags are uniform over the workgroup; a unit takes one of the four instances of label_rep.
 
 // what a unit stages of its reps: the reps [r0, r0 + n_rep), their exon offsets relative to e_base, the exon run [e_base, e_base + n_ex).
@@ -543,7 +424,7 @@ __device__ __forceinline__ LabelUnit label_unit(i64 r0, i64 r_end, const i64 *re
     u.n_ex = rep_exon_off[r0 + u.n_rep] - u.e_base;
     return u;
 }
-// reo_s[0 .. n_rep] and, where the run fits, ex_s[0 .. n_ex): the only new addressing of the kernel.  Returns whether the exons were
+// reo_s[0 .. n_rep] and, where the run fits, ex_s[0 .. n_ex).  Returns whether the exons were
 // staged (uniform over the workgroup): the one place that decides it.
 __device__ __forceinline__ bool label_stage_exons(const LabelUnit &u, i64 r0, const i64 *rep_exon_off, const int *ex_ts, const int *ex_te,
                                                   int *reo_s, int2 *ex_s) {
@@ -614,13 +495,16 @@ __device__ __forceinline__ void label_rep(const int *fp_g, const int2 *th_g, con
     if (acc) atomicOr(&packed[acc_w], acc);
 }
 
-__global__ void __launch_bounds__(256) k_label_reads_lds(int n_blocks, const int *rb_part, const int *rb_r0,
-                                                         const i64 *label_off, i64 label_cap, int n_part,
-                                                         const i64 *part_iv_off, const i64 *part_rep_off,
-                                                         const i64 *final_off, const int *final_pos, const int2 *col_thr,
-                                                         const i64 *rep_exon_off, const int *ex_ts, const int *ex_te,
-                                                         const unsigned char *col_zero, const int *part_has2,
-                                                         unsigned char *labels, unsigned *packed) {
+__global__ void __launch_bounds__(256) k_label_reads(int n_blocks, const int *rb_part, const int *rb_r0,
+                                                     const i64 *label_off, i64 label_cap, int n_part,
+                                                     const i64 *part_iv_off, const i64 *part_rep_off,
+                                                     const i64 *final_off, const int *final_pos, const int2 *col_thr,
+                                                     const i64 *rep_exon_off, const int *ex_ts, const int *ex_te,
+                                                     const unsigned char *col_zero, const int *part_has2,
+                                                     unsigned char *labels, unsigned *packed) {
+    // packed != nullptr: the labels are written at two bits each into a cleared arena (label g at bits 2 (g & 15) .. of word g >> 4,
+    // the layout fseg_results_packed delivers): a thread walks consecutive columns of its rep's row, collects the codes of a word
+    // in a register and ORs the word in when it moves on.  Only where no column's default is '2' (the host: no table entry and no rate >= 1, label_has2).
     __shared__ int fp_s[kLabelCols + 1];
     __shared__ int2 th_s[kLabelCols];
     __shared__ int2 ex_s[kLabelExons];

@@ -221,10 +221,11 @@ enum {
      * (0 after one timed out: events from then on), and the device's words (last problem-list generation, last generation of
      * side streams 0 / 1, workgroup counter) */
     FSEG_TAP_SYNC = 17,        /* int32[6]                                                                             */
-    /* the launch census of the last run: which kernel instances the host enqueued.  The masks and counts (words 4..16, 18..21, 23..26)
+    /* the launch census of the last run: which kernel instances the host enqueued.  The masks and counts (words 4..16, 18..21, 23..30)
      * are written in the very branches that launch, not from what the FSEG_* switches asked for; words 0..3, 17 and 22 are the
-     * batch's decisions those branches test, copied where the scoring stage begins.  Counts are the list sizes the host launched
-     * over, -1 where it launched without knowing them (an unsized first run); a replayed hipGraph keeps the words of its capture.
+     * batch's decisions those branches test, copied where the scoring stage begins; word 31 is written by fseg_upload.  Counts are
+     * the list sizes the host launched over, -1 where it launched without knowing them (an unsized first run); a replayed hipGraph
+     * keeps the words of its capture.
      * Words:
      *    0 small_batch (one launch for every size class)      1 tiny_on (problems of <= 8 candidates have a list of their own)
      *    2 wave_on (k_wave<8> may take that list)             3 fuse_on (problems are solved whole: k_solve / k_wave)
@@ -246,12 +247,10 @@ enum {
      *   28 the block size k_fix and k_segments were launched with (64, 256 or 1024, by the batch's average interval length)
      *   29 the k_smooth instance: 20 or 12 (the unrolled radii), 0 (any other radius, the loop)
      *   30 the histogram is uint16 in device memory (FSEG_YRAW16, where word 27 is 1; 0: int32)
-     *   31 k_thr_part_chain took the variance threshold (FSEG_THR_CHAIN, where word 5 is 1; 0: k_thr_part)
-     *   32 lane_sort: how the last upload ordered the reps -- 0 k_lanes sorted every partition in LDS, 1 the batch-wide radix sort
+     *   31 lane_sort: how the last upload ordered the reps -- 0 k_lanes sorted every partition in LDS, 1 the batch-wide radix sort
      *      and k_lane_blocks / k_lane_block_scan / k_lane_emit (a partition of more than 2 048 reps, or FSEG_GLOBAL_SORT=1);
-     *      written by fseg_upload, kept by every run and replay of the batch
-     *   33 label_lds: k_label_reads_lds wrote the labels (FSEG_LABEL_LDS; 0: k_label_reads) */
-    FSEG_TAP_PATHS = 18,       /* int32[34]                                                                            */
+     *      written by fseg_upload, kept by every run and replay of the batch */
+    FSEG_TAP_PATHS = 18,       /* int32[32]                                                                            */
     /* the histogram chunks of the last upload, a row each: (p0, n, llo, lhi) -- the chunk's first batch position, its position
      * count, and the lanes [llo, lhi) of its partition that k_hist_ranges found able to reach it */
     FSEG_TAP_HIST_RANGES = 19  /* int64[n_hist_chunks][4]                                                              */

@@ -1,4 +1,4 @@
-"""Hand-built batches for k_label_reads_lds (csrc/seg_tail.hip) at the edges of what it stages: reps per partition on the unit
+"""Hand-built batches for k_label_reads (csrc/seg_tail.hip) at the edges of what it stages: reps per partition on the unit
 (64 reps) and block (256 reps) edges, the exons of a unit one below, on and one above kLabelExons, column tables of 1, kLabelStage
 and kLabelStage + 1 columns crossed with those, a unit's first exon at every residue mod 4 of the exon arrays, and the geometry the
 merge has to get right.  tests/test_label_cases_host.py shows on the CPU that every batch reaches its edge;

@@ -1,7 +1,7 @@
-"""k_label_reads_lds on the device: the batches of tests/label_cases.py, every tap against the CPU oracle on the first run and on the
-replay -- under the default (the column table and the units' exons read from LDS), under FSEG_LABEL_LDS=0 (k_label_reads as it was),
-and with the label launch capped at one and at three workgroups (FSEG_LABEL_GRID), so that one workgroup walks units of different
-partitions and shapes in turn over what the unit before it staged.  The census word label_lds says which kernel ran."""
+"""k_label_reads on the device: the batches of tests/label_cases.py, every tap against the CPU oracle on the first run and on the
+replay -- under the default (the column table and the units' exons read from LDS where they fit) and with the label launch capped at
+one and at three workgroups (FSEG_LABEL_GRID), so that one workgroup walks units of different partitions and shapes in turn over
+what the unit before it staged.  The census word label_packed says which arena the kernel wrote."""
 import numpy as np
 import pytest
 
@@ -11,12 +11,9 @@ import util
 pytestmark = pytest.mark.gpu
 
 SWITCHES = {
-    "default": ({}, 1),
-    "lds-1": ({"FSEG_LABEL_LDS": "1"}, 1),
-    "lds-0": ({"FSEG_LABEL_LDS": "0"}, 0),
-    "grid-1": ({"FSEG_LABEL_GRID": "1"}, 1),
-    "grid-3": ({"FSEG_LABEL_GRID": "3"}, 1),
-    "grid-3-lds-0": ({"FSEG_LABEL_GRID": "3", "FSEG_LABEL_LDS": "0"}, 0),
+    "default": {},
+    "grid-1": {"FSEG_LABEL_GRID": "1"},
+    "grid-3": {"FSEG_LABEL_GRID": "3"},
 }
 
 
@@ -24,8 +21,8 @@ SWITCHES = {
 @pytest.mark.parametrize("name", list(lc.BATCHES))
 def test_labels_against_the_oracle(name, switch, monkeypatch):
     from freddie_amd import _lib
-    env, label_lds = SWITCHES[switch]
-    for k in ("FSEG_LABEL_LDS", "FSEG_LABEL_GRID", "FSEG_LABEL_BYTES"):
+    env = SWITCHES[switch]
+    for k in ("FSEG_LABEL_GRID", "FSEG_LABEL_BYTES"):
         monkeypatch.delenv(k, raising=False)
     for k, v in env.items():
         monkeypatch.setenv(k, v)
@@ -40,7 +37,7 @@ def test_labels_against_the_oracle(name, switch, monkeypatch):
             else:
                 ctx.run(); ctx.sync()
             census = ctx.paths()
-            assert census["label_lds"] == label_lds and census["label_packed"] == int(packed), (run, census)
+            assert census["label_packed"] == int(packed), (run, census)
             try:
                 util.compare_partitions(ctx, parts, want)
             except AssertionError as e:

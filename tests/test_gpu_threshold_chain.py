@@ -1,8 +1,7 @@
-"""What k_thr_part_chain (FSEG_THR_CHAIN, the default) carries from step to step, on the device: the batches of
+"""What k_thr_part carries from step to step, on the device: the batches of
 tests/threshold_chain_cases.py -- a workgroup walks two partitions of different shape one after the other (counts 0, 2, 7, 8, 9, 128,
 129, 8 191 / 8 192 / 8 193 = the values kept in LDS less one, exactly and one more, 16 384, 16 385, one chunk more than a sweep holds,
-and 140 000 = more flag groups a wave than it keeps words of), under the default, under FSEG_THR_CHAIN=0 (k_thr_part as it was) and
-under FSEG_THR_PART=0 (the chunk kernels).  tests/test_threshold_chain_host.py proves on the CPU that a stale leaf table, stale values
+and 140 000 = more flag groups a wave than it keeps words of), under the default and under FSEG_THR_PART=0 (the chunk kernels).  tests/test_threshold_chain_host.py proves on the CPU that a stale leaf table, stale values
 or a dropped last LDS value would change the bits compared here.
 
 Thresholds bit-identical with the CPU oracle (NaN with NaN) on the first run and on the replay, every other tap equal, the smoothed
@@ -17,10 +16,8 @@ from freddie_amd import _lib
 pytestmark = pytest.mark.gpu
 
 SETTINGS = {
-    "default": ({}, dict(thr_part=1, thr_chain=1)),
-    "chain-1": ({"FSEG_THR_CHAIN": "1", "FSEG_THR_PART": "1"}, dict(thr_part=1, thr_chain=1)),
-    "chain-0": ({"FSEG_THR_CHAIN": "0"}, dict(thr_part=1, thr_chain=0)),
-    "chunks": ({"FSEG_THR_PART": "0"}, dict(thr_part=0, thr_chain=0)),
+    "default": ({}, dict(thr_part=1)),
+    "chunks": ({"FSEG_THR_PART": "0"}, dict(thr_part=0)),
 }
 RUNS = [(kind, s) for kind in cc.KINDS for s in SETTINGS]
 
@@ -34,7 +31,7 @@ def wrong_thresholds(ctx, names, want):
 
 @pytest.mark.parametrize("kind,setting", RUNS, ids=["%s-%s" % r for r in RUNS])
 def test_threshold_chain(kind, setting, monkeypatch):
-    for name in ("FSEG_THR_PART", "FSEG_THR_CHAIN", "FSEG_SCAN_SINGLE_MAX"):
+    for name in ("FSEG_THR_PART", "FSEG_SCAN_SINGLE_MAX"):
         monkeypatch.delenv(name, raising=False)
     env, census = SETTINGS[setting]
     for name, v in env.items():

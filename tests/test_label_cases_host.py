@@ -1,6 +1,6 @@
 """tests/label_cases.py on the CPU: every batch reaches the edge it is named after, shown with the oracle alone -- the reps of every
 partition against the unit and the block, the exons of a unit against kLabelExons, the column tables against kLabelStage, which of
-k_label_reads_lds' four instances a batch's units take, where a unit's first exon sits in the exon arrays, and the geometry of exons
+k_label_reads' four label_rep instances a batch's units take, where a unit's first exon sits in the exon arrays, and the geometry of exons
 against columns that the merge has to get right."""
 import numpy as np
 import pytest

@@ -1,4 +1,4 @@
-"""Hand-built batches for what k_thr_part_chain (FSEG_THR_CHAIN) carries from one step to the next: the partial chunk's leaf table
+"""Hand-built batches for what k_thr_part carries from one step to the next: the partial chunk's leaf table
 across the two passes and from one partition of a workgroup to its next, the first LDS_VALS values of V in LDS, the flag words a
 wave keeps in registers, and the chunk sums of more chunks than one sweep holds.  Built on tests/threshold_cases.py (filled(): every
 position of a partition is flagged, so |V| is the partition's length).
