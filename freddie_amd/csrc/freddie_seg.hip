@@ -18,6 +18,7 @@
 //
 // No CPU fallback exists in this library: without a GPU fseg_create() fails.
 #include "seg_kernels.h"
+#include "seg_score_plan.h"
 
 using namespace fseg;
 
@@ -271,7 +272,7 @@ struct fseg_ctx {
     bool use_fork = true;
     bool force_key64 = false;
     bool wide_by_seen = false;  // FSEG_WIDE_BY_SEEN=1 (tests)
-    char score_plan[32] = "gM|W|hB|gST";   // FSEG_SCORE_PLAN (see enqueue_run; anything that does not name each class once = one stream)
+    char score_plan[kScorePlanChars + 1] = "gM|W|hB|gST";   // FSEG_SCORE_PLAN (see seg_score_plan.h; anything that does not name each class once = one stream)
     bool use_wave = true;       // FSEG_NO_WAVE=1: k_tiny / k_solve<16> instead of the wave kernels (k_wave)
     bool use_fuse = true;       // FSEG_NO_FUSE=1: no problem goes to k_solve (everything that is not tiny takes the arena path)
     // Reads the widest problem of a batch may see for the batch's problems to be solved whole (k_solve / k_wave) instead of going
@@ -345,7 +346,6 @@ thread_local std::string g_create_error;      // fseg_create has no context to p
 // forks only after it has CLAIMED the device: one compare-and-swap on the device's owner word, taken by fseg_run when nobody
 // else is in flight, given back when the run has completed (finish_run).  Losers, and whoever arrives while the word is held,
 // keep to one stream.  With one forking context per device a waiter can only sit in front of kernels that do not feed it.
-static bool g_ablate_dp = false;     // (diagnostic build FSEG_ABLATE_STAGE only: the k_dpw launches are left out)
 static std::atomic<int> g_in_flight[64];
 static std::atomic<int> g_live[64];
 static std::atomic<const fseg_ctx *> g_owner[64];
@@ -483,9 +483,100 @@ inline i64 scan_blocks(i64 n) { return (n + kScanBlock - 1) / kScanBlock; }
 // k_tiny / k_solve for its small problems
 bool wave_on(const fseg_ctx *c) { return c->use_wave && c->max_rep_exons <= kWaveRepExons; }
 ProbSplit split_of(const fseg_ctx *c, bool tiny, bool fuse) {
-    const bool wave = wave_on(c);
-    (void)wave;
     return ProbSplit{tiny ? kTiny : 0, (c->use_fuse && fuse) ? c->fuse_lanes : -1};
+}
+
+// The scoring stage's launches (enqueue_run walks the list of seg_score_plan.h): a function per kernel family, the family's
+// argument list written once, and the dispatchers that map an op to the instance -- only instances the kernels' units instantiate
+// (kInstances in seg_solve16 / 32 / 60 .hip, seg_score_fused.hip, seg_score_arena.hip).
+static_assert(kScoreSide == fseg_ctx::kSide, "a plan's segments beyond the first take a side stream each");
+#ifdef FSEG_SCORE_TIMING
+#define FSEG_TARG , c->d_tacc.p
+#else
+#define FSEG_TARG
+#endif
+#ifndef FSEG_WG_SMALL
+#define FSEG_WG_SMALL 4096
+#endif
+#ifndef FSEG_WG_MID
+#define FSEG_WG_MID 2048
+#endif
+#ifndef FSEG_WG_TINY
+#define FSEG_WG_TINY 4096
+#endif
+// the candidates a kernel of size class NM lays its LDS out for: the large class's follow the batch's largest problem
+template <int NM> int nm_of(const fseg_ctx *c) { return NM == kNMax ? c->nm_big : NM; }
+// a 16-bit instance over one class of a sized batch walks the class's wide problems through wide_items, the one launch over
+// every class's through wide_all
+const int *wide_list(const fseg_ctx *c, const ScoreFacts &f, const ScoreOp &op) {
+    return op.kind == ScoreKind::WideAll ? c->d_wide_all.p : (wide_n(f, op.cls, op.cnt_bytes) >= 0 ? c->d_wide_items.p : nullptr);
+}
+template <int NM>
+void launch_score(fseg_ctx *c, hipStream_t q, const ScoreOp &op, const ProblemArrays &pr) {
+    constexpr int max_wg = NM == kNMax ? 512 : (NM == kClsMid ? 1280 : 2048);
+    const int work_grid = grid_for(c->work_cap, 1, 4096);
+    hipLaunchKernelGGL(k_score<NM>, dim3(work_grid < max_wg ? work_grid : max_wg), dim3(ScoreCfg<NM>::kThreads),
+                       score_lds_for(nm_of<NM>(c), NM + 1), q, c->d_status.p, op.cls, nm_of<NM>(c), pr, c->prob_cap, c->d_cls_items.p,
+                       c->d_prob_desc.p, c->work_cap, c->d_cand_off.p, c->d_cand_y.p, c->d_work_active.p, c->d_cov.p,
+                       c->cov_cap, c->d_pair_thr.p, c->pair_cap, c->d_out.p, c->tri_cap, c->d_amb.p FSEG_TARG);
+}
+// (an unsized batch: grid-stride workgroups up to the class's cap over prob_cap; sized: a workgroup per problem of the list)
+template <int NM, typename CntT, typename V, bool SPLIT>
+void launch_solve(fseg_ctx *c, hipStream_t q, const ScoreOp &op, const ScoreFacts &f, const ProblemArrays &pr) {
+    constexpr int max_wg = NM == kNMax ? 512 : (NM == kClsMid ? FSEG_WG_MID : FSEG_WG_SMALL);
+    hipLaunchKernelGGL((k_solve<NM, CntT, V, SPLIT>), dim3(grid_for(op.n, 1, f.known ? (1 << 20) : max_wg)), dim3(SolveCfg<NM>::kThreads),
+                       solve_lds_for(nm_of<NM>(c), NM + 1, (int)sizeof(CntT)), q, c->d_status.p, op.cls, nm_of<NM>(c), list_lb(f, op.cls),
+                       f.known ? op.n : (i64)-1, pr, c->d_solve_desc.p, c->prob_cap, c->d_cand_y.p, c->d_lane_lx.p, c->d_lex.p,
+                       c->d_h_table.p, c->P.h_len, c->P.threshold_rate, c->d_thr_tab.p, c->P.min_read_support_outside, c->d_chosen.p,
+                       SPLIT ? c->d_dpx.p + c->dpx_base[op.cls] : (unsigned char *)nullptr, SPLIT ? c->dpx_stride[op.cls] : (i64)0,
+                       wide_list(c, f, op) FSEG_TARG);
+}
+template <int NM, typename CntT, typename V, int T>
+void launch_dpw(fseg_ctx *c, hipStream_t q, const ScoreOp &op, const ScoreFacts &f, const ProblemArrays &pr) {
+    c->paths[fseg_ctx::PATH_DPW] |= (1 << op.cls) | (T == 512 ? 8 : 0);
+    hipLaunchKernelGGL((k_dpw<NM, CntT, V, T>), dim3(grid_for(op.n, 1, (int)kSplitGridCap)), dim3(T),
+                       dpw_lds_for(nm_of<NM>(c), (int)sizeof(V), (int)sizeof(CntT)), q, c->d_status.p, nm_of<NM>(c), list_lb(f, op.cls), op.n, pr,
+                       c->d_solve_desc.p, c->d_dpx.p + c->dpx_base[op.cls], c->dpx_stride[op.cls],
+                       c->P.min_read_support_outside, c->d_chosen.p, wide_list(c, f, op) FSEG_TARG);
+}
+// one wave per problem on the exon stream: the list op.cls names (3: the tiny problems')
+template <int NM, typename V>
+void launch_wave(fseg_ctx *c, hipStream_t q, const ScoreOp &op, const ScoreFacts &f, const ProblemArrays &pr) {
+    hipLaunchKernelGGL((k_wave<NM, V>), dim3(grid_for(op.n, 4, FSEG_WG_TINY)), dim3(256), 0, q, c->d_status.p,
+                       c->d_solve_desc.p, c->prob_cap, op.cls, pr, c->d_cand_y.p, c->d_lane_lx.p,
+                       c->d_lex.p, c->d_h_table.p, c->P.h_len, c->P.threshold_rate,
+                       c->d_thr_tab.p, c->P.min_read_support_outside, c->d_chosen.p,
+                       list_lb(f, op.cls), list_ln(f, op.cls) FSEG_TARG);
+}
+// A k_solve op's instance: the size class (one launch over every class is the large class's), the counter width, 32-bit DP keys
+// when the batch allows them.  The split path is k_solve<.., int, SPLIT> (its rounds need no keys) then k_dpw (the DPs, keyed as
+// the fused instance would be; `with_dpw` false: a diagnostic build leaves them out); eight waves a workgroup exist for the
+// large class only.
+template <int NM, typename CntT>
+void launch_solve_as(fseg_ctx *c, hipStream_t q, const ScoreOp &op, const ScoreFacts &f, const ProblemArrays &pr, bool with_dpw) {
+    if (op.kind != ScoreKind::SolveSplit) {
+        if (f.key32) launch_solve<NM, CntT, int, false>(c, q, op, f, pr); else launch_solve<NM, CntT, i64, false>(c, q, op, f, pr);
+        return;
+    }
+    launch_solve<NM, CntT, int, true>(c, q, op, f, pr);
+    if (!with_dpw) return;
+    if constexpr (NM == kNMax) if (op.dpw_threads == 512) {
+        if (f.key32) launch_dpw<NM, CntT, int, 512>(c, q, op, f, pr); else launch_dpw<NM, CntT, i64, 512>(c, q, op, f, pr);
+        return;
+    }
+    if (f.key32) launch_dpw<NM, CntT, int, 64>(c, q, op, f, pr); else launch_dpw<NM, CntT, i64, 64>(c, q, op, f, pr);
+}
+template <int NM>
+void launch_class(fseg_ctx *c, hipStream_t q, const ScoreOp &op, const ScoreFacts &f, const ProblemArrays &pr, bool with_dpw) {
+    if (op.kind == ScoreKind::Score) launch_score<NM>(c, q, op, pr);
+    else if (op.cnt_bytes == 2) launch_solve_as<NM, unsigned short>(c, q, op, f, pr, with_dpw);
+    else launch_solve_as<NM, unsigned char>(c, q, op, f, pr, with_dpw);
+}
+// k_score / k_solve ops
+void launch_class_op(fseg_ctx *c, hipStream_t q, const ScoreOp &op, const ScoreFacts &f, const ProblemArrays &pr, bool with_dpw) {
+    if (op.cls == 0) launch_class<kClsSmall>(c, q, op, f, pr, with_dpw);
+    else if (op.cls == 1) launch_class<kClsMid>(c, q, op, f, pr, with_dpw);
+    else launch_class<kNMax>(c, q, op, f, pr, with_dpw);
 }
 
 // Enqueue the segments `segs` of one run on the context's stream.
@@ -533,33 +624,27 @@ int enqueue_run(fseg_ctx *c, unsigned segs, bool sized = false, i64 label_fill_b
         if (r == hipSuccess) r = hipStreamWaitEvent(s, e, 0);
         if (r != hipSuccess) fj_err = r;
     };
-    // The scoring plan of this enqueue (FSEG_SCORE_PLAN, see the scoring stage below) is decided HERE: with the device-side
-    // fork (k_wait_word) its side streams are forked in front of the stage's predecessors, so that the events' latency
-    // (10-15 us each) is over when k_prob_emit ends.
-    const bool any_solve_plan = c->use_fuse && c->fuse_on;
-    const char *plan = (do_score && c->prob_cap > 0 && known && !any_arena && !c->small_batch && forking && c->n_solve[2] > 0 && any_solve_plan && wave && c->score_plan[0]) ? c->score_plan : nullptr;
-    struct PlanSegs { int n_seg = 1; bool used[4] = {true, false, false, false}; int side_of[4] = {-1, -1, -1, -1}; i64 n_wide_all = 0; bool wide_one = false; } ps;
-    if (plan) {
-        // W: the problems of every class that see more than kFuseLanes reads -- a handful per batch, most of which keep fewer
-        // and are only looked at -- in ONE launch of the large class's 16-bit instance, a workgroup each (as a launch per
-        // class on the tiny class's stream they held it back 46-60 us on config3 / config5: tools/run_gaps.py); batches
-        // with many such problems keep the per-class instances (in a row on W's stream)
-        ps.n_wide_all = c->n_wide[0] + c->n_wide[1] + c->n_wide[2];
-        ps.wide_one = ps.n_wide_all <= fseg_ctx::kWideOneMax && strchr(plan, 'W') != nullptr;
-        for (const char *p = plan; *p; ++p) {
-            if (*p == '|') { ++ps.n_seg; continue; }
-            if (ps.n_seg > 4) continue;
-            if (*p == 'W') { if (c->wide_solve && ps.n_wide_all > 0) ps.used[ps.n_seg - 1] = true; }
-            else ps.used[ps.n_seg - 1] = true;
-        }
-        if (ps.n_seg > 4) ps.n_seg = 4;
-        // (the segments that have something to launch take the side streams in order: the first ones start first)
-        for (int k = 1, nx = 0; k < ps.n_seg; ++k) if (ps.used[k]) ps.side_of[k] = nx++;
-    }
+    // What the scoring stage of this enqueue launches -- which instance over which list on which stream, in which host order:
+    // seg_score_plan.h has the rules and what was measured for them -- is decided HERE, the plan (FSEG_SCORE_PLAN) with it: with the
+    // device-side fork (k_wait_word) a plan's side streams are forked in front of the stage's predecessors, so that the events'
+    // latency (10-15 us each) is over when k_prob_emit ends.
+    ScoreFacts facts;
+    facts.known = known; facts.small_batch = c->small_batch; facts.any_arena = any_arena; facts.fuse = c->use_fuse && c->fuse_on;
+    facts.tiny_on = c->tiny_on; facts.wave = wave; facts.forking = forking; facts.wide_solve = c->wide_solve;
+    // 32-bit DP keys (dp_solve_push) when no sum of a chain can reach 2^24: at most 32 links times the reads of the largest partition
+    facts.key32 = c->max_part_lanes < kKey32Reads && !c->force_key64;     // (FSEG_FORCE_KEY64=1: the 64-bit instances whatever the batch)
+    for (int q = 0; q < 3; ++q) { facts.n_solve[q] = c->n_solve[q]; facts.n_wide[q] = c->n_wide[q]; facts.dpx_n[q] = c->dpx_n[q]; facts.dpx_cnt[q] = c->dpx_cnt[q]; }
+    for (int q = 0; q < 4; ++q) facts.n_cls_work[q] = c->n_cls_work[q];
+    facts.n_tiny = c->n_tiny; facts.prob_cap = c->prob_cap; facts.split_dp = c->split_dp;
+    facts.dpx_nm_fits = c->dpx_nm == c->nm_big; facts.dpx_arena = c->d_dpx.p != nullptr;
+    facts.split_grid_cap = kSplitGridCap; facts.wide_one_max = fseg_ctx::kWideOneMax;
+    const ScorePlan ps = parse_score_plan(facts, c->score_plan, do_score);
+    ScoreOps ops;
+    if (do_score) plan_score_ops(facts, ps, ops);
     // device-side fork / join (k_wait_word): plain launches only (never inside a capture), and only when this enqueue holds
     // k_prob_emit, whose last workgroup is what the side streams wait for; only on side streams whose hardware queue is not the
     // main stream's (side_ok, probed once: a waiter there would sit in front of the kernel it waits for)
-    const bool dev_sync = plan && c->dev_sync && !c->run_events_only && do_pre2 && (sized || c->run_plain) && c->d_sync.p != nullptr;
+    const bool dev_sync = ps.on && c->dev_sync && !c->run_events_only && do_pre2 && (sized || c->run_plain) && c->d_sync.p != nullptr;
     SyncWords *sw = c->d_sync.p;
     const unsigned sync_gen = dev_sync ? ++c->sync_gen : 0;
     // (a context's first stages with waiters also load the stage's code objects and make the runtime allocate scratch for the side
@@ -768,135 +853,32 @@ int enqueue_run(fseg_ctx *c, unsigned segs, bool sized = false, i64 label_fill_b
             if (w != fseg_ctx::PATH_THR_PART && w != fseg_ctx::PATH_LABEL_PACKED && w != fseg_ctx::PATH_ARENA_DP && w != fseg_ctx::PATH_HIST16 &&
                 w != fseg_ctx::PATH_IV_THREADS && w != fseg_ctx::PATH_SMOOTH_R && w != fseg_ctx::PATH_YRAW16 && w != fseg_ctx::PATH_LANE_SORT) census[w] = 0;
         census[fseg_ctx::PATH_SMALL_BATCH] = c->small_batch; census[fseg_ctx::PATH_TINY_ON] = c->tiny_on; census[fseg_ctx::PATH_WAVE_ON] = wave;
-        census[fseg_ctx::PATH_FUSE_ON] = c->use_fuse && c->fuse_on; census[fseg_ctx::PATH_KNOWN] = known; census[fseg_ctx::PATH_PLAN] = plan != nullptr;
+        census[fseg_ctx::PATH_FUSE_ON] = c->use_fuse && c->fuse_on; census[fseg_ctx::PATH_KNOWN] = known; census[fseg_ctx::PATH_PLAN] = ps.on;
     }
     if (do_score && c->prob_cap > 0) {
-        // How the scoring kernels share the chip is a plan (FSEG_SCORE_PLAN, default "gM|W|hB|gST"): streams separated by '|'
-        // (the first is the main stream; the segments that have something to launch take the side streams in order); B M S T =
-        // the large / mid / small / tiny class -- a class on the split path is k_solve (rounds) followed by k_dpw (its DPs) --,
-        // b m s = the classes' 16-bit-counter instances (launched over their classes' wide problems), g = k_gate (wait until the
-        // large class's workgroups, both instances', are placed), h = wait until the 16-bit instance's are, e = wait for the large
-        // class to end.  Measured on config4 (250 k-read batch, stage alone, tools/r4_plans.sh):
-        //   * everything on the main stream 0.19-0.21 ms; a stream each without a gate 0.21 (the dispatcher runs them in the
-        //     reverse of their launch order: a large-class workgroup needs eight wave slots and half a CU's LDS at once);
-        //   * round 3's "BM|gTS" 0.161-0.165: the tiny class in the large class's shadow, then small beside mid;
-        //   * a cross-stream dependency costs ~9 us (fork or join), so the chain that ends LAST belongs on the main stream,
-        //     where the stage's end needs no join: the mid class (gate, rounds, DPs) on main, the large class on a side stream
-        //     of its own, tiny + small on a third: 0.144-0.149 with the split path ("B|gM|gTS", the same chains with the large
-        //     class on main: 0.154-0.167; per-problem clocks, tools/r4_ticks.sh: 133 us from first start to last end either way);
-        //   * the 16-bit instances first (batches of 1 000-read partitions): see the passes below.
-        // Anything that does not name each class once, batches with arena-path problems and small batches: one stream.
+        // What the stage launches is the list `ops` (seg_score_plan.h: which instance over which list on which stream, and why),
+        // made at the top of this function.  Here the side streams are forked, the list is walked -- its order is the host's
+        // launch order -- and the streams are joined.
         const bool sfork = any_arena;                               // (the arena path's work-item kernels keep their streams)
-        hipStream_t qt = (tiny_max > 0 && sfork) ? fork(2) : s;     // (forked here: a side stream continues from where it was forked)
-#ifdef FSEG_SCORE_TIMING
-#define FSEG_TARG , c->d_tacc.p
-#else
-#define FSEG_TARG
-#endif
-#ifndef FSEG_WG_SMALL
-#define FSEG_WG_SMALL 4096
-#endif
-#ifndef FSEG_WG_MID
-#define FSEG_WG_MID 2048
-#endif
-#ifndef FSEG_WG_TINY
-#define FSEG_WG_TINY 4096
-#endif
-#define FSEG_LAUNCH_SCORE(Q, NMV, CLS, MAXWG)                                                                           \
-        do { note_score(CLS);                                                                                                  \
-        hipLaunchKernelGGL(k_score<NMV>, dim3(work_grid < (MAXWG) ? work_grid : (MAXWG)), dim3(ScoreCfg<NMV>::kThreads),  \
-                           score_lds_for((NMV) == kNMax ? c->nm_big : (NMV), (NMV) + 1), Q, st, CLS,                                 \
-                           ((NMV) == kNMax ? c->nm_big : (NMV)), pr, c->prob_cap, c->d_cls_items.p,              \
-                           c->d_prob_desc.p, c->work_cap, c->d_cand_off.p,                         \
-                           c->d_cand_y.p, c->d_work_active.p, c->d_cov.p,        \
-                           c->cov_cap, c->d_pair_thr.p, c->pair_cap, c->d_out.p, c->tri_cap,      \
-                           c->d_amb.p FSEG_TARG); } while (0)
-        // (a 16-bit-counter instance of a sized batch goes over its class's WIDE problems only: wide_n of them, through wide_items)
-        auto wide_n = [&](int cls, size_t cnt_bytes) -> i64 { return (known && cls >= 0 && cls < 3 && cnt_bytes == 2) ? c->n_wide[cls] : -1; };
-#define FSEG_SOLVE_N(CNT, CLS, N_ITEMS) (wide_n(CLS, sizeof(CNT)) >= 0 ? wide_n(CLS, sizeof(CNT)) : (i64)(N_ITEMS))
-#define FSEG_SOLVE_WIDE(CNT, CLS) (wide_n(CLS, sizeof(CNT)) >= 0 ? c->d_wide_items.p : (const int *)nullptr)
-#define FSEG_SOLVE_ARGS(NMV, CNT, CLS)                                                                                      \
-                               st, CLS, ((NMV) == kNMax ? c->nm_big : (NMV)), list_lb(CLS),                                    \
-                               (wide_n(CLS, sizeof(CNT)) >= 0 ? wide_n(CLS, sizeof(CNT)) : list_ln(CLS)), pr, c->d_solve_desc.p, \
-                               c->prob_cap, c->d_cand_y.p, c->d_lane_lx.p, c->d_lex.p,               \
-                               c->d_h_table.p, c->P.h_len, c->P.threshold_rate,               \
-                               c->d_thr_tab.p, c->P.min_read_support_outside, c->d_chosen.p
-        // the split path (k_solve<.., SPLIT> then k_dpw on the same stream) for a list that fits the hand-over arena as laid out.
-        // (Until round 5 only where the context has the device to itself: host memory -> host memory, eight contexts, the two were
-        // within the noise -- 383 against 388 M reads/s; over resident batches the split is 1.8 % faster; FSEG_SPLIT_ALWAYS=0.)
-        auto split_ok = [&](int cls, int cnt_bytes) {
-            // (k_dpw takes the problem its workgroup index names -- no grid stride --, so a list longer than the grid cap of the
-            // two launches keeps the DP as k_solve's tail)
-            return known && cls >= 0 && cls < 3 && ((c->split_dp >> cls) & 1) && c->dpx_n[cls] > 0 && c->n_solve[cls] <= c->dpx_n[cls] && c->dpx_nm == c->nm_big &&
-                   c->n_solve[cls] <= kSplitGridCap && cnt_bytes <= c->dpx_cnt[cls] && c->d_dpx.p != nullptr;
-        };
-#define FSEG_LAUNCH_SOLVE(Q, NMV, CNT, VT, CLS, N_ITEMS, MAXWG)                                                              \
-            do { note_solve(CLS, sizeof(CNT));                                                                                     \
-            hipLaunchKernelGGL((k_solve<NMV, CNT, VT, false>), dim3(grid_for(FSEG_SOLVE_N(CNT, CLS, N_ITEMS), 1, known ? (1 << 20) : (MAXWG))), dim3(SolveCfg<NMV>::kThreads), \
-                               solve_lds_for((NMV) == kNMax ? c->nm_big : (NMV), (NMV) + 1, (int)sizeof(CNT)), Q,               \
-                               FSEG_SOLVE_ARGS(NMV, CNT, CLS), (unsigned char *)nullptr, (i64)0, FSEG_SOLVE_WIDE(CNT, CLS) FSEG_TARG); } while (0)
-        // every list's problems that see more than kFuseLanes reads, through wide_all: the large class's 16-bit instance, a workgroup each
-#define FSEG_LAUNCH_WIDE_ALL(Q, VT)                                                                                          \
-            do { note_solve(-1, 2);                                                                                                \
-            hipLaunchKernelGGL((k_solve<kNMax, unsigned short, VT, false>), dim3((unsigned)n_wide_all), dim3(SolveCfg<kNMax>::kThreads), \
-                               solve_lds_for(c->nm_big, kNMax + 1, 2), Q, st, -1, c->nm_big, (i64)0, n_wide_all, pr, c->d_solve_desc.p, \
-                               c->prob_cap, c->d_cand_y.p, c->d_lane_lx.p, c->d_lex.p,               \
-                               c->d_h_table.p, c->P.h_len, c->P.threshold_rate,               \
-                               c->d_thr_tab.p, c->P.min_read_support_outside, c->d_chosen.p,       \
-                               (unsigned char *)nullptr, (i64)0, c->d_wide_all.p FSEG_TARG); } while (0)
-#define FSEG_LAUNCH_DPW(Q, NMV, CNT, VT, CLS, N_ITEMS, TT)                                                                   \
-            do { census[fseg_ctx::PATH_DPW] |= (1 << ((CLS) < 0 ? 0 : (CLS))) | ((TT) == 512 ? 8 : 0);                                 \
-            hipLaunchKernelGGL((k_dpw<NMV, CNT, VT, TT>), dim3(grid_for(FSEG_SOLVE_N(CNT, CLS, N_ITEMS), 1, (int)kSplitGridCap)), dim3(TT),      \
-                               dpw_lds_for(nm_rt, (int)sizeof(VT), (int)sizeof(CNT)), Q, st, nm_rt, list_lb(CLS),                \
-                               FSEG_SOLVE_N(CNT, CLS, list_ln(CLS)), pr,                                                        \
-                               c->d_solve_desc.p, dpx0, dstride, \
-                               c->P.min_read_support_outside, c->d_chosen.p, FSEG_SOLVE_WIDE(CNT, CLS) FSEG_TARG); } while (0)
-        // the split path, one instance: k_solve<.., SPLIT> (set-up and rounds) then k_dpw (the DPs) on the same stream
-#define FSEG_LAUNCH_SPLIT(Q, NMV, CNT, VT, CLS, N_ITEMS)                                                                     \
-        do { const int nm_rt = (NMV) == kNMax ? c->nm_big : (NMV);                                                            \
-            unsigned char *dpx0 = c->d_dpx.p + c->dpx_base[(CLS) < 0 ? 0 : (CLS)];                                           \
-            const i64 dstride = c->dpx_stride[(CLS) < 0 ? 0 : (CLS)];                                                                       \
-            note_solve(CLS, sizeof(CNT));                                                                                     \
-            hipLaunchKernelGGL((k_solve<NMV, CNT, int, true>), dim3(grid_for(FSEG_SOLVE_N(CNT, CLS, N_ITEMS), 1, (int)kSplitGridCap)), dim3(SolveCfg<NMV>::kThreads), \
-                               solve_lds_for(nm_rt, (NMV) + 1, (int)sizeof(CNT)), Q, FSEG_SOLVE_ARGS(NMV, CNT, CLS), dpx0, dstride, \
-                               FSEG_SOLVE_WIDE(CNT, CLS) FSEG_TARG);                                    \
-            if (g_ablate_dp) break;                                                                                               \
-            /* the large class's DPs by workgroups of eight waves (k_dpw<.., 512>: 27 us alone instead of 38; FSEG_SPLIT_DP bit 3: by one) */ \
-            if constexpr ((NMV) == kNMax) { if (!(c->split_dp & 8)) { FSEG_LAUNCH_DPW(Q, NMV, CNT, VT, CLS, N_ITEMS, 512); break; } }      \
-            FSEG_LAUNCH_DPW(Q, NMV, CNT, VT, CLS, N_ITEMS, 64); } while (0)
-        // 32-bit DP keys (dp_solve_push) when no sum of a chain can reach 2^24: at most 32 links times the reads of the largest partition
-        // (WHICH: 1 = the instance with 8-bit counters, 2 = the one with 16-bit counters if the class has problems for it, 3 = both)
-#define FSEG_LAUNCH_SPLIT_K(Q, NMV, CNT, CLS, N_ITEMS)                                                                        \
-            do { if (key32) FSEG_LAUNCH_SPLIT(Q, NMV, CNT, int, CLS, N_ITEMS); else FSEG_LAUNCH_SPLIT(Q, NMV, CNT, i64, CLS, N_ITEMS); } while (0)
-#define FSEG_LAUNCH_SOLVE_X(Q, NMV, CLS, N_ITEMS, MAXWG, WHICH)                                                              \
-            do { if (split_ok(CLS, FSEG_WIDE_NEEDED(CLS) ? 2 : 1)) {                                                            \
-                         if ((WHICH) & 1) FSEG_LAUNCH_SPLIT_K(Q, NMV, unsigned char, CLS, N_ITEMS);                              \
-                         if (((WHICH) & 2) && FSEG_WIDE_NEEDED(CLS)) FSEG_LAUNCH_SPLIT_K(Q, NMV, unsigned short, CLS, N_ITEMS);   \
-                 } else if (key32) { if ((WHICH) & 1) FSEG_LAUNCH_SOLVE(Q, NMV, unsigned char, int, CLS, N_ITEMS, MAXWG);              \
-                              if (((WHICH) & 2) && FSEG_WIDE_NEEDED(CLS)) FSEG_LAUNCH_SOLVE(Q, NMV, unsigned short, int, CLS, N_ITEMS, MAXWG); } \
-                 else { if ((WHICH) & 1) FSEG_LAUNCH_SOLVE(Q, NMV, unsigned char, i64, CLS, N_ITEMS, MAXWG);                    \
-                        if (((WHICH) & 2) && FSEG_WIDE_NEEDED(CLS)) FSEG_LAUNCH_SOLVE(Q, NMV, unsigned short, i64, CLS, N_ITEMS, MAXWG); } } while (0)
-#define FSEG_LAUNCH_SOLVE_W(Q, NMV, CLS, N_ITEMS, MAXWG) FSEG_LAUNCH_SOLVE_X(Q, NMV, CLS, N_ITEMS, MAXWG, 3)
-#define FSEG_WIDE_NEEDED(CLS) (!known || (c->wide_solve && ((CLS) < 0 || c->n_wide[(CLS)] > 0)))
-        // Two ways a problem is scored (prob_kind): the arena path's work items (k_score per size class) and the problems that
-        // see few reads (at most 255: 8-bit counters), whole, one workgroup each (k_solve per size class).
-        // A batch usually holds only one kind; a class's two launches share a stream.
-        // one wave per problem on the exon stream (k_wave): the small class's solve list and k_tiny's list
-#define FSEG_LAUNCH_WAVE_V(Q, NMV, VT, LIST, N_ITEMS)                                                                        \
-            do { note_tiny(1);                                                                                                     \
-            hipLaunchKernelGGL((k_wave<NMV, VT>), dim3(grid_for((N_ITEMS), 4, FSEG_WG_TINY)), dim3(256), 0, Q, st,           \
-                               c->d_solve_desc.p, c->prob_cap, LIST, pr, c->d_cand_y.p, c->d_lane_lx.p, \
-                               c->d_lex.p, c->d_h_table.p, c->P.h_len, c->P.threshold_rate,               \
-                               c->d_thr_tab.p, c->P.min_read_support_outside, c->d_chosen.p,        \
-                               list_lb(LIST), list_ln(LIST) FSEG_TARG); } while (0)
-#define FSEG_LAUNCH_WAVE(Q, NMV, LIST, N_ITEMS)                                                                              \
-            do { if (key32) { FSEG_LAUNCH_WAVE_V(Q, NMV, int, LIST, N_ITEMS); }                              \
-                 else { FSEG_LAUNCH_WAVE_V(Q, NMV, i64, LIST, N_ITEMS); } } while (0)
-        // the bounds of solve list `l` (0..2 the classes, 3 the tiny problems, < 0 the three classes together) when the host knows them
-        const bool key32 = c->max_part_lanes < kKey32Reads && !c->force_key64;     // (FSEG_FORCE_KEY64=1: the 64-bit instances whatever the batch)
-        census[fseg_ctx::PATH_KEY32] = key32;
+        // (forked here: a side stream continues from where it was forked)
+        if (tiny_max > 0 && sfork) (void)fork(2);
+        if (!c->small_batch && sfork) { (void)fork(0); (void)fork(1); }
+        if (ps.on) {
+            // every side stream continues from HERE (the stage's begin event, when it is being recorded, is the first side
+            // stream's fork: one marker packet less in front of everything -- each is ~5 us on its queue)
+            // (every side stream on that one event: 0.135 -> 0.137-0.149 ms -- the records stagger the streams' starts)
+            bool shared = !(stage_events && forking);
+            for (int k = 1; k < ps.n_seg; ++k) if (ps.used[k]) {
+                if (dev_side(k)) continue;           // forked early; its waiter (k_wait_word) is what the stream runs first
+                if (!shared) {
+                    shared = true;
+                    if (hipError_t r = hipStreamWaitEvent(c->side[ps.side_of[k]], c->ev_b[ST_SCORE], 0); r != hipSuccess) fj_err = r;
+                } else (void)fork(ps.side_of[k]);
+            }
+        }
+        census[fseg_ctx::PATH_KEY32] = facts.key32;
         // the census of this stage's launches (cls < 0: one launch over every class)
-        auto note_solve = [&](int cls, size_t cnt_bytes) {
+        auto note_solve = [&](int cls, int cnt_bytes) {
             census[cnt_bytes == 2 ? fseg_ctx::PATH_WIDE16 : fseg_ctx::PATH_SOLVE8] |= cls < 0 ? 8 : 1 << cls;
             for (int q = 0; q < 3; ++q) if (cls < 0 || q == cls) {
                 census[fseg_ctx::PATH_N_SOLVE + q] = known ? (int)c->n_solve[q] : -1;
@@ -910,131 +892,57 @@ int enqueue_run(fseg_ctx *c, unsigned segs, bool sized = false, i64 label_fill_b
             for (int q = 0; q < 3; ++q) if (cls < 0 || q == cls) census[fseg_ctx::PATH_N_SCORE + q] = known ? (int)c->n_cls_work[q] : -1;
         };
         auto note_tiny = [&](int kernel) { census[fseg_ctx::PATH_TINY_KERNEL] = kernel; census[fseg_ctx::PATH_N_TINY] = known ? (int)c->n_tiny : -1; };
-        auto list_lb = [&](int l) -> i64 { return !known ? -1 : (l <= 0 ? 0 : (l == 1 ? c->n_solve[0] : (l == 2 ? c->n_solve[0] + c->n_solve[1] : c->n_solve[0] + c->n_solve[1] + c->n_solve[2]))); };
-        auto list_ln = [&](int l) -> i64 { return !known ? -1 : (l < 0 ? c->n_solve[0] + c->n_solve[1] + c->n_solve[2] : (l == 3 ? c->n_tiny : c->n_solve[l])); };
-        const bool any_solve = c->use_fuse && c->fuse_on && (!known || c->n_solve[0] + c->n_solve[1] + c->n_solve[2] > 0);
-        const i64 cap = c->prob_cap;
-        if (c->small_batch) {
-            if (any_arena) FSEG_LAUNCH_SCORE(s, kNMax, -1, 512);    // few work items: one launch for every size class
-            if (any_solve) FSEG_LAUNCH_SOLVE_W(s, kNMax, -1, known ? c->n_solve[0] + c->n_solve[1] + c->n_solve[2] : cap, 512);
-        } else {                                     // the size classes own disjoint problems: three concurrent chains
-            hipStream_t q1 = sfork ? fork(0) : s, q0 = sfork ? fork(1) : s;
-            if (plan) {
-                // (which segments have something to launch and the side streams they take: decided at the top, `ps`)
-                const int n_seg = ps.n_seg;
-                const bool *used = ps.used;              // a stream whose kernels have nothing to do is left alone
-                const int *side_of = ps.side_of;
-                const i64 n_wide_all = ps.n_wide_all;
-                const bool wide_one = ps.wide_one;
-                // every side stream continues from HERE (the stage's begin event, when it is being recorded, is the first side
-                // stream's fork: one marker packet less in front of everything -- each is ~5 us on its queue)
-                // (every side stream on that one event: 0.135 -> 0.137-0.149 ms -- the records stagger the streams' starts)
-                bool shared = !(stage_events && forking);
-                for (int k = 1; k < n_seg; ++k) if (used[k]) {
-                    if (dev_side(k)) continue;           // forked early; its waiter (k_wait_word) is what the stream runs first
-                    if (!shared) {
-                        shared = true;
-                        if (hipError_t r = hipStreamWaitEvent(c->side[side_of[k]], c->ev_b[ST_SCORE], 0); r != hipSuccess) fj_err = r;
-                    } else (void)fork(side_of[k]);
-                }
-                int seg = 0;
-                // (a plan with W: B M S launch their 8-bit instances only; without: both instances, one after the other)
-                const int wb = strchr(plan, 'W') ? 1 : 3, wm = wb, ws = wb;
-                // the large class's workgroups a start gate waits for: the 8-bit instance's and the 16-bit instance's (one per wide
-                // problem) -- the latter need 90 KB of LDS each and find no room once the other classes are in
-                const i64 wide_wgs = wide_one ? (c->wide_solve ? n_wide_all : 0) : (FSEG_WIDE_NEEDED(2) ? c->n_wide[2] : 0);
-                const i64 big_wgs = c->n_solve[2] + wide_wgs;
-                // Three passes over the plan: the large class's launches that open their stream go out FIRST -- the 16-bit instance
-                // (W), then the 8-bit one (B, behind `h` = a gate on W's workgroups having started) --, everything else follows in
-                // plan order (a stream's own order is kept).  Why: a workgroup of the 16-bit instance holds up to 120 KB of LDS (n
-                // <= 60: planes 28 + coverage 16 + 16-bit counters 68 KB) and fits no CU that has one of the 8-bit instance's
-                // (81 KB); enqueued behind it, config3's one real wide problem was placed 135-150 us into the stage, when the 8-bit
-                // instance and the classes behind the gate had drained, and the stage took 0.29 ms (tools/stage_timeline.py).  A
-                // class has a handful of wide problems: placed first they take a few CUs and the 8-bit instance the rest.
-                for (int pass = 0; pass < 3; ++pass) {                       // 0: W   1: h, B   2: the rest
-                seg = 0;
-                bool opens = true;
-                for (const char *p = plan; *p && seg < n_seg; ++p) {
-                    if (*p == '|') { ++seg; opens = true; continue; }
-                    const int when = !opens ? 2 : (*p == 'W' ? 0 : ((*p == 'B' || *p == 'h') ? 1 : 2));
-                    if (*p != 'h') opens = false;
-                    if (!used[seg] || when != pass) continue;
-                    hipStream_t q = seg == 0 ? s : c->side[side_of[seg]];
-                    // (the side streams' waiters are released by k_prob_emit's last workgroup: emit_done)
+        bool with_dpw = true;
 #ifdef FSEG_ABLATE_STAGE
-                    // diagnostic build (wrong results, honest timing): FSEG_ABLATE = bit mask of what the stage leaves out --
-                    // 1 the DP launches (k_dpw), 2 the large class, 4 the gates, 8 the mid class, 16 the small class, 32 the tiny class
-                    {
-                        static const int abl = getenv("FSEG_ABLATE") ? atoi(getenv("FSEG_ABLATE")) : 0;
-                        g_ablate_dp = (abl & 1) != 0;
-                        if (((abl & 2) && (*p == 'B' || *p == 'W')) || ((abl & 4) && (*p == 'g' || *p == 'h')) || ((abl & 8) && *p == 'M') ||
-                            ((abl & 16) && *p == 'S') || ((abl & 32) && *p == 'T')) continue;
-                    }
+        // diagnostic build (wrong results, honest timing): FSEG_ABLATE = bit mask of what a planned stage leaves out --
+        // 1 the DP launches (k_dpw), 2 the large class (B and what W launches), 4 the gates, 8 the mid class, 16 the small class, 32 the tiny class
+        static const int abl = getenv("FSEG_ABLATE") ? atoi(getenv("FSEG_ABLATE")) : 0;
+        with_dpw = !(ps.on && (abl & 1));
+        auto ablated = [&](const ScoreOp &op) {
+            const bool gate = op.kind == ScoreKind::GateG || op.kind == ScoreKind::GateH;
+            const bool of_w = op.kind == ScoreKind::WideAll || (ps.has_w && op.cnt_bytes == 2);
+            const int cls = (gate || op.kind == ScoreKind::Wave) ? -1 : (of_w ? 2 : op.cls);
+            return ps.on && (((abl & 2) && cls == 2) || ((abl & 4) && gate) || ((abl & 8) && cls == 1) || ((abl & 16) && cls == 0) ||
+                             ((abl & 32) && op.kind == ScoreKind::Wave));
+        };
 #endif
-                    switch (*p) {
-                    case 'B': FSEG_LAUNCH_SOLVE_X(q, kNMax, 2, c->n_solve[2], 512, wb); break;
-                    case 'M': if (c->n_solve[1] > 0) FSEG_LAUNCH_SOLVE_X(q, kClsMid, 1, c->n_solve[1], FSEG_WG_MID, wm); break;
-                    case 'S': if (c->n_solve[0] > 0) FSEG_LAUNCH_SOLVE_X(q, kClsSmall, 0, c->n_solve[0], FSEG_WG_SMALL, ws); break;
-                    case 'W':
-                        if (!c->wide_solve || n_wide_all == 0) break;
-                        if (wide_one) {                          // (the DP stays the workgroup's tail: nothing to hand over, no second placement)
-                            if (key32) FSEG_LAUNCH_WIDE_ALL(q, int); else FSEG_LAUNCH_WIDE_ALL(q, i64);
-                        } else {
-                            FSEG_LAUNCH_SOLVE_X(q, kNMax, 2, c->n_solve[2], 512, 2);
-                            if (c->n_solve[1] > 0) FSEG_LAUNCH_SOLVE_X(q, kClsMid, 1, c->n_solve[1], FSEG_WG_MID, 2);
-                            if (c->n_solve[0] > 0) FSEG_LAUNCH_SOLVE_X(q, kClsSmall, 0, c->n_solve[0], FSEG_WG_SMALL, 2);
-                        }
-                        break;
-                    case 'T': if (c->n_tiny > 0) FSEG_LAUNCH_WAVE(q, kTiny, 3, c->n_tiny); break;
-                    case 'g': hipLaunchKernelGGL(k_gate, dim3(1), dim3(64), 0, q, st, 0, (unsigned)(big_wgs < 512 ? big_wgs : 512), 3000u); break;
-                    case 'h': if (wide_wgs > 0)       // the 16-bit instance's workgroups (up to 120 KB of LDS each) take their CUs first
-                                  hipLaunchKernelGGL(k_gate, dim3(1), dim3(64), 0, q, st, 2, (unsigned)(wide_wgs < 256 ? wide_wgs : 256), 1500u);
-                              break;
-                    default: break;
-                    }
-                }
-                }
-                // join: a side chain with a device-side fork ends with k_signal and the main stream waits for the words (one wave in
-                // front of k_segments) instead of two marker + barrier packets per side stream
-                unsigned dev_mask = 0;
-                for (int k = 1; k < n_seg; ++k) if (used[k]) {
-                    if (dev_side(k)) { hipLaunchKernelGGL(k_signal, dim3(1), dim3(64), 0, c->side[side_of[k]], &sw->side_gen[side_of[k]], sync_gen); dev_mask |= 1u << side_of[k]; }
-                    else join(side_of[k]);
-                }
-                if (dev_mask) hipLaunchKernelGGL(k_wait_word, dim3(1), dim3(64), 0, s, st, sw->side_gen, dev_mask, sync_gen, kSyncTicks);
-            } else {
-            if (any_arena && (!known || c->n_cls_work[2] > 0)) FSEG_LAUNCH_SCORE(s, kNMax, 2, 512);     // big problems: they are the long poles
-            if (any_solve && (!known || c->n_solve[2] > 0)) FSEG_LAUNCH_SOLVE_W(s, kNMax, 2, known ? c->n_solve[2] : cap, 512);
-            if (any_arena && (!known || c->n_cls_work[1] > 0)) FSEG_LAUNCH_SCORE(q1, kClsMid, 1, 1280);
-            if (any_solve && (!known || c->n_solve[1] > 0)) FSEG_LAUNCH_SOLVE_W(q1, kClsMid, 1, known ? c->n_solve[1] : cap, FSEG_WG_MID);
-            if (any_arena && (!known || c->n_cls_work[0] > 0)) FSEG_LAUNCH_SCORE(q0, kClsSmall, 0, 2048);
-            if (any_solve && (!known || c->n_solve[0] > 0)) FSEG_LAUNCH_SOLVE_W(q0, kClsSmall, 0, known ? c->n_solve[0] : cap, FSEG_WG_SMALL);
+        for (int i = 0; i < ops.n; ++i) {
+            const ScoreOp &op = ops.op[i];
+            hipStream_t q = op.lane < 0 ? s : c->side[op.lane];
+            // (a plan's side streams' waiters are released by k_prob_emit's last workgroup: emit_done)
+#ifdef FSEG_ABLATE_STAGE
+            if (ablated(op)) continue;
+#endif
+            switch (op.kind) {
+            case ScoreKind::Score: note_score(op.cls); launch_class_op(c, q, op, facts, pr, with_dpw); break;
+            case ScoreKind::SolveFused: case ScoreKind::SolveSplit: case ScoreKind::WideAll:
+                note_solve(op.cls, op.cnt_bytes); launch_class_op(c, q, op, facts, pr, with_dpw); break;
+            case ScoreKind::Wave:
+                note_tiny(1);
+                if (facts.key32) launch_wave<kTiny, int>(c, q, op, facts, pr); else launch_wave<kTiny, i64>(c, q, op, facts, pr);
+                break;
+            case ScoreKind::Tiny:
+                note_tiny(2);
+                hipLaunchKernelGGL(k_tiny, dim3(grid_for(op.n, 4, FSEG_WG_TINY)), dim3(256), 0, q, st, c->d_solve_desc.p,
+                                   c->prob_cap, tiny_max, pr, c->d_cand_y.p, c->d_lane_ex.p,
+                                   c->d_ex_ts.p, c->d_ex_te.p, c->d_h_table.p, c->P.h_len, c->P.threshold_rate,
+                                   c->d_thr_tab.p, c->P.min_read_support_outside, c->d_chosen.p, list_lb(facts, 3), list_ln(facts, 3) FSEG_TARG);
+                break;
+            case ScoreKind::GateG: hipLaunchKernelGGL(k_gate, dim3(1), dim3(64), 0, q, st, 0, (unsigned)op.n, 3000u); break;
+            case ScoreKind::GateH: hipLaunchKernelGGL(k_gate, dim3(1), dim3(64), 0, q, st, 2, (unsigned)op.n, 1500u); break;
             }
         }
-#undef FSEG_LAUNCH_SOLVE_W
-#undef FSEG_LAUNCH_SOLVE_X
-#undef FSEG_LAUNCH_SPLIT_K
-#undef FSEG_LAUNCH_DPW
-#undef FSEG_LAUNCH_WIDE_ALL
-#undef FSEG_LAUNCH_SPLIT
-#undef FSEG_LAUNCH_SOLVE
-#undef FSEG_SOLVE_ARGS
-#undef FSEG_SOLVE_WIDE
-#undef FSEG_SOLVE_N
-#undef FSEG_LAUNCH_SCORE
-        if (tiny_max > 0 && !plan) {
-            // the problems with a handful of candidates, whole (coverage, labels, counts, DP), beside the others (launched
-            // after the classes whose workgroups need half a CU's LDS each); joined at the end of this stage, so the
-            // stage's time bracket covers all scoring work
-            if (wave) FSEG_LAUNCH_WAVE(qt, kTiny, 3, known ? c->n_tiny : c->prob_cap);
-            else { note_tiny(2);
-            hipLaunchKernelGGL(k_tiny, dim3(grid_for(known ? c->n_tiny : c->prob_cap, 4, FSEG_WG_TINY)), dim3(256), 0, qt, st, c->d_solve_desc.p,
-                               c->prob_cap, tiny_max, pr, c->d_cand_y.p, c->d_lane_ex.p,
-                               c->d_ex_ts.p, c->d_ex_te.p, c->d_h_table.p, c->P.h_len, c->P.threshold_rate,
-                               c->d_thr_tab.p, c->P.min_read_support_outside, c->d_chosen.p, list_lb(3), list_ln(3) FSEG_TARG); }
+        if (ps.on) {
+            // join: a side chain with a device-side fork ends with k_signal and the main stream waits for the words (one wave in
+            // front of k_segments) instead of two marker + barrier packets per side stream
+            unsigned dev_mask = 0;
+            for (int k = 1; k < ps.n_seg; ++k) if (ps.used[k]) {
+                if (dev_side(k)) { hipLaunchKernelGGL(k_signal, dim3(1), dim3(64), 0, c->side[ps.side_of[k]], &sw->side_gen[ps.side_of[k]], sync_gen); dev_mask |= 1u << ps.side_of[k]; }
+                else join(ps.side_of[k]);
+            }
+            if (dev_mask) hipLaunchKernelGGL(k_wait_word, dim3(1), dim3(64), 0, s, st, sw->side_gen, dev_mask, sync_gen, kSyncTicks);
         }
-#undef FSEG_LAUNCH_WAVE
-#undef FSEG_LAUNCH_WAVE_V
+        // (the tiny problems' kernel is joined at the end of this stage, so the stage's time bracket covers all scoring work)
         if (!c->small_batch && sfork) { join(0); join(1); }
         if (c->have_huge && any_arena) census[fseg_ctx::PATH_SCORE] |= 16;
         if (c->have_huge && any_arena)
@@ -1561,14 +1469,7 @@ void read_switches(fseg_ctx *c) {
     if (env_flag("FSEG_WIDE_BY_SEEN")) c->wide_by_seen = true;
     if (const char *s = env_str("FSEG_SPLIT_DP")) c->split_dp = atoi(s) & 15;       // (set but empty counts: 0, no class hands its DPs over)
     if (const char *s = env_str("FSEG_SCORE_PLAN")) snprintf(c->score_plan, sizeof c->score_plan, "%s", s);
-    {
-        int seen[4] = {0, 0, 0, 0};
-        static const char kinds[] = "BMST";
-        for (const char *q = c->score_plan; *q; ++q) { const char *at = strchr(kinds, *q); if (at) ++seen[at - kinds]; }
-        int bars = 0;
-        for (const char *q = c->score_plan; *q; ++q) bars += *q == '|';
-        if (seen[0] != 1 || seen[1] != 1 || seen[2] != 1 || seen[3] != 1 || bars > fseg_ctx::kSide) c->score_plan[0] = 0;   // (a stream per segment)
-    }
+    if (!score_plan_valid(c->score_plan)) c->score_plan[0] = 0;
     if (env_int("FSEG_FUSE_LANES", v) && v > 0 && v <= kFuseLanesWide) c->fuse_lanes = (int)v;
     if (env_flag("FSEG_NO_SIZED")) c->use_sized = false;
     if (env_flag("FSEG_TRACE")) c->trace = true;
