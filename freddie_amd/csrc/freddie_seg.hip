@@ -1,6 +1,9 @@
 // freddie_seg.hip -- the HOST side of libfreddie_seg.so, the gfx950 (MI355X) library of the canonical-segmentation path: contexts,
-// slabs and arenas, the launch sequence of a run (enqueue_run), the sized first run, uploads, results, and the C-ABI of
-// include/freddie_seg.h.  The kernels live in the stage families' translation units (seg_front / seg_problems /
+// slabs and arenas, the launch sequence of a run, the sized first run, uploads, results, and the C-ABI of include/freddie_seg.h.
+// The launch sequence is enqueue_run: it builds a Run (what the call computes once: streams, geometry, the scoring stage's launch
+// list, the fork / join state) and calls a function per segment of the pipeline -- seg_pre1, seg_pre2, seg_score, seg_post1,
+// seg_post2 --, each a list of launches; a kernel family with several instances or callers has its argument list once, in a
+// launch_* function.  This unit defines no kernel: they live in the stage families' translation units (seg_front / seg_problems /
 // seg_score_arena / seg_score_fused + seg_solve16|32|60 / seg_tail / seg_upload .hip; shared definitions seg_common.h,
 // declarations seg_kernels.h); freddie_amd/build.py compiles the units side by side.
 //
@@ -296,7 +299,7 @@ struct fseg_ctx {
     bool trace = false;         // FSEG_TRACE=1: phase timers of upload / run on stderr
     bool force_global_sort = false;   // FSEG_GLOBAL_SORT=1 (tests): the batch-wide radix sort whatever the partition sizes
     // FSEG_TAP_PATHS (include/freddie_seg.h has the words): what the last enqueue of each stage launched.  A stage's words are reset
-    // where enqueue_run begins the stage; the masks and counts are written in the branches that launch, so they say what ran, not
+    // where the stage's segment of enqueue_run begins (the scoring stage's: kScoreCensus); the masks and counts are written in the branches that launch, so they say what ran, not
     // what the switches asked for (the six decisions of the batch -- small_batch, tiny_on, wave_on, fuse_on, known, plan -- are the
     // values those branches test, copied where the stage begins); a replayed graph keeps the words of its capture.
     enum { PATH_SMALL_BATCH, PATH_TINY_ON, PATH_WAVE_ON, PATH_FUSE_ON, PATH_KEY32, PATH_THR_PART, PATH_LABEL_PACKED, PATH_N_SOLVE,
@@ -486,7 +489,7 @@ ProbSplit split_of(const fseg_ctx *c, bool tiny, bool fuse) {
     return ProbSplit{tiny ? kTiny : 0, (c->use_fuse && fuse) ? c->fuse_lanes : -1};
 }
 
-// The scoring stage's launches (enqueue_run walks the list of seg_score_plan.h): a function per kernel family, the family's
+// The scoring stage's launches (seg_score walks the list of seg_score_plan.h): a function per kernel family, the family's
 // argument list written once, and the dispatchers that map an op to the instance -- only instances the kernels' units instantiate
 // (kInstances in seg_solve16 / 32 / 60 .hip, seg_score_fused.hip, seg_score_arena.hip).
 static_assert(kScoreSide == fseg_ctx::kSide, "a plan's segments beyond the first take a side stream each");
@@ -579,169 +582,248 @@ void launch_class_op(fseg_ctx *c, hipStream_t q, const ScoreOp &op, const ScoreF
     else launch_class<kNMax>(c, q, op, f, pr, with_dpw);
 }
 
-// Enqueue the segments `segs` of one run on the context's stream.
-//   sized: the run is being launched piecewise with the host reading the sizes in between (first run of a batch):
-//          the problem scan always runs as its own kernels (their totals are what the host waits for) and the label
-//          arena is filled by its own kernel over exactly label_fill_bytes.
-int enqueue_run(fseg_ctx *c, unsigned segs, bool sized = false, i64 label_fill_bytes = 0) {
+// the problem kernels' grid (k_prob_range, k_prob_scan1, k_prob_emit)
+int prob_grid(const fseg_ctx *c) { return grid_for(c->NPOS / 8 / kProbBlock + 1, 1, 1024); }
+// what the scoring stage's decisions read (seg_score_plan.h), from the context
+ScoreFacts score_facts(const fseg_ctx *c, bool forking) {
+    ScoreFacts f;
+    // list sizes known (the batch has been sized or has run): launches over an empty list are left out
+    f.known = c->counts_known; f.small_batch = c->small_batch; f.any_arena = !f.known || c->n_arena_prob > 0; f.fuse = c->use_fuse && c->fuse_on;
+    f.tiny_on = c->tiny_on; f.wave = wave_on(c); f.forking = forking; f.wide_solve = c->wide_solve;
+    // 32-bit DP keys (dp_solve_push) when no sum of a chain can reach 2^24: at most 32 links times the reads of the largest partition
+    f.key32 = c->max_part_lanes < kKey32Reads && !c->force_key64;     // (FSEG_FORCE_KEY64=1: the 64-bit instances whatever the batch)
+    for (int q = 0; q < 3; ++q) { f.n_solve[q] = c->n_solve[q]; f.n_wide[q] = c->n_wide[q]; f.dpx_n[q] = c->dpx_n[q]; f.dpx_cnt[q] = c->dpx_cnt[q]; }
+    for (int q = 0; q < 4; ++q) f.n_cls_work[q] = c->n_cls_work[q];
+    f.n_tiny = c->n_tiny; f.prob_cap = c->prob_cap; f.split_dp = c->split_dp;
+    f.dpx_nm_fits = c->dpx_nm == c->nm_big; f.dpx_arena = c->d_dpx.p != nullptr;
+    f.split_grid_cap = kSplitGridCap; f.wide_one_max = fseg_ctx::kWideOneMax;
+    return f;
+}
+
+// What one call of enqueue_run computes once and every segment of the call reads (the members' initialisers, in this order), the
+// call's fork / join state, and what a segment leaves for a later one of the same call.  Built on the stack per call; the
+// segments' functions (seg_pre1 .. seg_post2) take it.
+struct Run {
+    fseg_ctx *c;
+    unsigned segs;              // the segments this call enqueues
+    bool sized;                 // the first run of a batch, launched piecewise (see enqueue_run)
     hipStream_t s = c->stream;
-    const bool do_pre1 = segs & SEG_PRE1, do_pre2 = segs & SEG_PRE2, do_score = segs & SEG_SCORE, do_post1 = segs & SEG_POST1,
-               do_post2 = segs & SEG_POST2;
-    const bool stage_events = c->profiling && (sized || c->run_plain);
-    const int n_part = c->n_part;
-    const i64 K = c->K, NPOS = c->NPOS;
     Status *st = c->d_status.p;
     // the flag masks: Y > 0 | candidate | final position, flag_words(NPOS) words each
-    unsigned *flag_pos_bits = c->d_bits.p, *flag_cand_bits = flag_pos_bits + flag_words(NPOS), *flag_final_bits = flag_cand_bits + flag_words(NPOS);
-    auto begin = [&](int i) { if (stage_events && (c->profile_all || i == ST_SCORE)) (void)hipEventRecord(c->ev_b[i], s); };
-    auto end = [&](int i) { if (stage_events && (c->profile_all || i == ST_SCORE)) (void)hipEventRecord(c->ev_e[i], s); };
-    // fork(k): side stream k continues from here; join(k): the main stream waits for it.  Every fork is joined before
-    // the function returns, so a capture of the main stream ends with all branches merged.
+    unsigned *flag_pos_bits = c->d_bits.p, *flag_cand_bits = flag_pos_bits + flag_words(c->NPOS), *flag_final_bits = flag_cand_bits + flag_words(c->NPOS);
+    bool stage_events = c->profiling && (sized || c->run_plain);   // the stages are bracketed by events (begin / end)
     // Small batches (one partition, few problems) are chains of launch-latency-sized kernels: branches only add
     // cross-stream dependencies there (measured: config2 +4 %), so they stay on the one stream.
-    const bool forking = would_fork(c) && !c->run_linear;
-    const int tiny_max = c->tiny_on ? kTiny : 0;
-    const bool wave = wave_on(c);
-    const ProbSplit split = split_of(c, c->tiny_on, c->fuse_on);
-    // list sizes known (the batch has been sized or has run): launches over an empty list are left out
-    const bool known = c->counts_known;
-    const bool any_arena = !known || c->n_arena_prob > 0;
+    bool forking = would_fork(c) && !c->run_linear;
+    // look-back state of the three compactions (values, candidates, final positions): scan_nb words each of d_scan_state
+    i64 scan_nb = scan_blocks(c->NPOS);
+    int scan_grid = scan_nb > 0 ? (int)scan_nb : 1;       // exactly one workgroup per scan block (look-back)
+    // single-pass look-back scan while the chain of blocks is short; block sums + one scanning workgroup beyond that
+    bool scan_single = scan_nb <= c->scan_single_max;
+    int *bsum_side = scan_single ? nullptr : c->d_bsum_side.p;     // block sums of the scan that runs on a side stream (values)
+    // the two position compactions: blocks of kPosBlock positions (a quarter of the words of look-back state, same layout).  The
+    // look-back chain keeps its limit in POSITIONS (FSEG_SCAN_SINGLE_MAX blocks of kScanBlock, as it was measured): beyond it
+    // block sums + group sums that the emitting workgroups add up themselves (k_pos_count), no scanning workgroup between
+    int pos_grid = (int)std::max<i64>(pos_blocks(c->NPOS), 1);     // exactly one workgroup per block
+    int *bsum = scan_single ? nullptr : c->d_bsum.p;
+    int *gsum = scan_single ? nullptr : c->d_gsum.p;
+    i64 avg_len = c->NPOS / (c->K > 0 ? c->K : 1);        // positions per interval
+    int iv_threads = avg_len > 65536 ? 1024 : (avg_len > 16384 ? 256 : 64);    // the block of k_fix and k_segments
+    int pg = prob_grid(c);
+    // few candidates: the emit kernel scans by itself, one launch instead of three (never in a sized run: there the
+    // host reads the scan's totals before the emit kernel is launched)
+    i64 *prob_bs = (c->prob_self_scan && !sized) ? nullptr : c->d_prob_bs.p;
+    ProblemArrays pr{c->d_prob_iv.p, c->d_prob_start.p, c->d_prob_n.p,
+                     c->d_prob_pair_off.p, c->d_prob_tri_off.p, c->d_prob_flags.p,
+                     c->d_prob_chain.p, c->d_prob_cov_off.p, c->d_prob_lane_lo.p,
+                     c->d_prob_lane_n.p};
+    ProbSplit split = split_of(c, c->tiny_on, c->fuse_on);
+    // What the scoring stage of this enqueue launches -- which instance over which list on which stream, in which host order:
+    // seg_score_plan.h has the rules and what was measured for them -- is decided HERE, the plan (FSEG_SCORE_PLAN) with it: with the
+    // device-side fork (k_wait_word) a plan's side streams are forked in front of the stage's predecessors, so that the events'
+    // latency (10-15 us each) is over when k_prob_emit ends.
+    ScoreFacts facts = score_facts(c, forking);
+    ScorePlan ps = parse_score_plan(facts, c->score_plan, segs & SEG_SCORE);
+    ScoreOps ops;               // (filled in by the constructor when the call holds the scoring stage)
+    // device-side fork / join (k_wait_word): plain launches only (never inside a capture), and only when this enqueue holds
+    // k_prob_emit, whose last workgroup is what the side streams wait for; only on side streams whose hardware queue is not the
+    // main stream's (side_ok, probed once: a waiter there would sit in front of the kernel it waits for)
+    bool dev_sync = ps.on && c->dev_sync && !c->run_events_only && (segs & SEG_PRE2) && (sized || c->run_plain) && c->d_sync.p != nullptr;
+    SyncWords *sw = c->d_sync.p;
+    unsigned sync_gen = dev_sync ? ++c->sync_gen : 0;
+    // (a context's first stages with waiters also load the stage's code objects and make the runtime allocate scratch for the side
+    // streams' queues -- hundreds of microseconds, once: tools/waiter_probe.py)
+    unsigned sync_ticks = (unsigned)std::min<i64>((i64)c->sync_ticks * std::max<i64>(1, c->LANES >> 18), 2000000);
+    i64 labels_n16 = (c->label_cap + 15) / 16;            // the arena is allocated in multiples of 16 bytes
+    bool lab_packed = labels_packed(c);                   // (two-bit labels: the arena is cleared by a memset, nothing rides)
+    // the label arena's '0' fill rides the big-problem DP launch as extra workgroups -- unless the run is being sized
+    // (the arena's size is not known yet) or there is no DP launch
+    // (not where the stages are bracketed by events: the fill is the labels stage's work, and a DP bracket that holds it says nothing about the DP)
+    bool ride_fill = !sized && c->prob_cap > 0 && c->label_cap > 0 && facts.any_arena && !stage_events && !lab_packed;
+    // What a segment leaves for a later one of the same call: SEG_PRE2 opens the scoring stage's bracket in front of the arena
+    // path's coverage launches (they are interval scoring), so SEG_SCORE must not open it again.
+    bool score_begun = false;
     int fj_next = 0;
     hipError_t fj_err = hipSuccess;
-    auto fj_event = [&]() { hipEvent_t e = c->fj[fj_next % fseg_ctx::kForkEvents]; ++fj_next; return e; };
-    auto fork = [&](int k) -> hipStream_t {
+
+    Run(fseg_ctx *ctx, unsigned segs_, bool sized_) : c(ctx), segs(segs_), sized(sized_) { if (segs & SEG_SCORE) plan_score_ops(facts, ps, ops); }
+    void begin(int i) const { if (stage_events && (c->profile_all || i == ST_SCORE)) (void)hipEventRecord(c->ev_b[i], s); }
+    void end(int i) const { if (stage_events && (c->profile_all || i == ST_SCORE)) (void)hipEventRecord(c->ev_e[i], s); }
+    // fork(k): side stream k continues from here; join(k): the main stream waits for it.  Every fork is joined before
+    // enqueue_run returns, so a capture of the main stream ends with all branches merged.
+    hipEvent_t fj_event() { hipEvent_t e = c->fj[fj_next % fseg_ctx::kForkEvents]; ++fj_next; return e; }
+    hipStream_t fork(int k) {
         if (!forking) return s;
         hipEvent_t e = fj_event();
         hipError_t r = hipEventRecord(e, s);
         if (r == hipSuccess) r = hipStreamWaitEvent(c->side[k], e, 0);
         if (r != hipSuccess) fj_err = r;
         return c->side[k];
-    };
-    auto join = [&](int k) {
+    }
+    void join(int k) {
         if (!forking) return;
         hipEvent_t e = fj_event();
         hipError_t r = hipEventRecord(e, c->side[k]);
         if (r == hipSuccess) r = hipStreamWaitEvent(s, e, 0);
         if (r != hipSuccess) fj_err = r;
-    };
-    // What the scoring stage of this enqueue launches -- which instance over which list on which stream, in which host order:
-    // seg_score_plan.h has the rules and what was measured for them -- is decided HERE, the plan (FSEG_SCORE_PLAN) with it: with the
-    // device-side fork (k_wait_word) a plan's side streams are forked in front of the stage's predecessors, so that the events'
-    // latency (10-15 us each) is over when k_prob_emit ends.
-    ScoreFacts facts;
-    facts.known = known; facts.small_batch = c->small_batch; facts.any_arena = any_arena; facts.fuse = c->use_fuse && c->fuse_on;
-    facts.tiny_on = c->tiny_on; facts.wave = wave; facts.forking = forking; facts.wide_solve = c->wide_solve;
-    // 32-bit DP keys (dp_solve_push) when no sum of a chain can reach 2^24: at most 32 links times the reads of the largest partition
-    facts.key32 = c->max_part_lanes < kKey32Reads && !c->force_key64;     // (FSEG_FORCE_KEY64=1: the 64-bit instances whatever the batch)
-    for (int q = 0; q < 3; ++q) { facts.n_solve[q] = c->n_solve[q]; facts.n_wide[q] = c->n_wide[q]; facts.dpx_n[q] = c->dpx_n[q]; facts.dpx_cnt[q] = c->dpx_cnt[q]; }
-    for (int q = 0; q < 4; ++q) facts.n_cls_work[q] = c->n_cls_work[q];
-    facts.n_tiny = c->n_tiny; facts.prob_cap = c->prob_cap; facts.split_dp = c->split_dp;
-    facts.dpx_nm_fits = c->dpx_nm == c->nm_big; facts.dpx_arena = c->d_dpx.p != nullptr;
-    facts.split_grid_cap = kSplitGridCap; facts.wide_one_max = fseg_ctx::kWideOneMax;
-    const ScorePlan ps = parse_score_plan(facts, c->score_plan, do_score);
-    ScoreOps ops;
-    if (do_score) plan_score_ops(facts, ps, ops);
-    // device-side fork / join (k_wait_word): plain launches only (never inside a capture), and only when this enqueue holds
-    // k_prob_emit, whose last workgroup is what the side streams wait for; only on side streams whose hardware queue is not the
-    // main stream's (side_ok, probed once: a waiter there would sit in front of the kernel it waits for)
-    const bool dev_sync = ps.on && c->dev_sync && !c->run_events_only && do_pre2 && (sized || c->run_plain) && c->d_sync.p != nullptr;
-    SyncWords *sw = c->d_sync.p;
-    const unsigned sync_gen = dev_sync ? ++c->sync_gen : 0;
-    // (a context's first stages with waiters also load the stage's code objects and make the runtime allocate scratch for the side
-    // streams' queues -- hundreds of microseconds, once: tools/waiter_probe.py)
-    const i64 sync_scale = std::max<i64>(1, c->LANES >> 18);
-    const unsigned kSyncTicks = (unsigned)std::min<i64>((i64)c->sync_ticks * sync_scale, 2000000);
-    auto dev_side = [&](int k) { return dev_sync && k >= 1 && k < ps.n_seg && ps.used[k] && ps.side_of[k] >= 0 && ps.side_of[k] < fseg_ctx::kSide && c->side_ok[ps.side_of[k]]; };
+    }
+    // segment k of the plan runs on a side stream behind a device-side waiter
+    bool dev_side(int k) const { return dev_sync && k >= 1 && k < ps.n_seg && ps.used[k] && ps.side_of[k] >= 0 && ps.side_of[k] < fseg_ctx::kSide && c->side_ok[ps.side_of[k]]; }
     // The fork is EARLY (the event in front of k_fix: its latency hides behind the stage's predecessors), the waiters' launches come
     // LATE on the host -- behind k_prob_emit's --: a waiter then never spins on the device while the host has not yet enqueued the
     // kernel it waits for (a host thread that is descheduled, or held up in the runtime beside another context's large pageable copy,
     // between the two was one way to a time-out: tests/test_gpu_contexts_stress.py); on the device nothing moves -- the host is four
     // launches (~20 us) ahead of the event either way.
-    auto early_fork = [&]() {
+    void early_fork() {
         if (!dev_sync) return;
         for (int k = 1; k < ps.n_seg; ++k) if (dev_side(k)) (void)fork(ps.side_of[k]);
-    };
-    auto launch_fork_waiters = [&]() {
+    }
+    void launch_fork_waiters() const {
         if (!dev_sync) return;
         for (int k = 1; k < ps.n_seg; ++k) if (dev_side(k))
-            hipLaunchKernelGGL(k_wait_word, dim3(1), dim3(64), 0, c->side[ps.side_of[k]], st, &sw->emit_gen, 1u, sync_gen, kSyncTicks);
-    };
-    const i64 avg_len = NPOS / (K > 0 ? K : 1);
-    const int iv_threads = avg_len > 65536 ? 1024 : (avg_len > 16384 ? 256 : 64);
-    int tile_grid = grid_for(c->n_tiles, 1, 16384);
-    const i64 scan_nb = scan_blocks(NPOS);
-    const int scan_grid = scan_nb > 0 ? (int)scan_nb : 1;       // exactly one workgroup per scan block (look-back)
-    u64 *scan_state = c->d_scan_state.p;
-    // single-pass look-back scan while the chain of blocks is short; block sums + one scanning workgroup beyond that
-    const bool scan_single = scan_nb <= c->scan_single_max;
-    int *bsum_side = scan_single ? nullptr : c->d_bsum_side.p;     // block sums of the scan that runs on a side stream (values)
-    // the two position compactions: blocks of kPosBlock positions (a quarter of the words of look-back state, same layout).  The
-    // look-back chain keeps its limit in POSITIONS (FSEG_SCAN_SINGLE_MAX blocks of kScanBlock, as it was measured): beyond it
-    // block sums + group sums that the emitting workgroups add up themselves (k_pos_count), no scanning workgroup between
-    const i64 pos_nb = pos_blocks(NPOS);
-    const int pos_grid = pos_nb > 0 ? (int)pos_nb : 1;          // exactly one workgroup per block
-    const bool pos_single = scan_single;
-    int *bsum = pos_single ? nullptr : c->d_bsum.p;
-    int *gsum = pos_single ? nullptr : c->d_gsum.p;
-    auto pos_counts = [&](hipStream_t q, const unsigned *flags) {
-        if (pos_single) return;
-        hipLaunchKernelGGL(k_pos_count, dim3(grid_for(pos_groups(NPOS), 1, 4096)), dim3(kPosCountThreads), 0, q, flags, NPOS, bsum, gsum);
-    };
-    auto scan_counts = [&](hipStream_t q, int *bs, const unsigned *flags, u64 *total_dev, i64 *off_last) {
-        if (scan_single) return;
-        hipLaunchKernelGGL(k_scan1, dim3(grid_for(scan_nb, 1, 4096)), dim3(256), 0, q, flags, NPOS, bs);
-        hipLaunchKernelGGL(k_scan2, dim3(1), dim3(kScan2Threads), 0, q, bs, scan_nb, total_dev, off_last);
-    };
-    int work_grid = grid_for(c->work_cap, 1, 4096);
-    ProblemArrays pr{c->d_prob_iv.p, c->d_prob_start.p, c->d_prob_n.p,
-                     c->d_prob_pair_off.p, c->d_prob_tri_off.p, c->d_prob_flags.p,
-                     c->d_prob_chain.p, c->d_prob_cov_off.p, c->d_prob_lane_lo.p,
-                     c->d_prob_lane_n.p};
-    const int pg = grid_for(NPOS / 8 / kProbBlock + 1, 1, 1024);
-    // few candidates: the emit kernel scans by itself, one launch instead of three (never in a sized run: there the
-    // host reads the scan's totals before the emit kernel is launched)
-    i64 *prob_bs = (c->prob_self_scan && !sized) ? nullptr : c->d_prob_bs.p;
-    if (do_pre1) {
+            hipLaunchKernelGGL(k_wait_word, dim3(1), dim3(64), 0, c->side[ps.side_of[k]], st, &sw->emit_gen, 1u, sync_gen, sync_ticks);
+    }
+};
+
+// The launches of the other stages whose argument list is needed more than once (an instance per counter type, a second caller):
+// the list written once, as the scoring stage's above.  A kernel with one launch site is launched where its stage's function has it.
+// S1 (the chunks were laid out on upload for one counter width: one instance per launch)
+template <int BITS, typename OUT>
+void launch_hist(const Run &r) {
+    fseg_ctx *c = r.c;
+    hipLaunchKernelGGL((k_hist<BITS, OUT>), dim3(grid_for(c->n_hist_chunks, 1, 16384)), dim3(512), 0, r.s, c->n_hist_chunks,
+                       c->d_hc_part.p, c->d_hc_p0.p, c->d_hc_n.p, c->d_hc_glo.p,
+                       c->d_hc_ghi.p, c->d_hc_llo.p, c->d_hc_lhi.p, c->d_part_iv_off.p, c->d_iv_start.p, c->d_iv_end.p,
+                       c->d_pos_off.p, c->d_part_lane_off.p, c->d_lane_lx.p,
+                       c->d_lane_start.p, c->d_lane_pmax.p,
+                       c->d_lex.p, c->P.ignore_ends, c->d_y_raw.as<OUT>(), r.st,
+                       c->d_scan_state.p, r.scan_single ? r.scan_nb * 3 : 0);
+}
+// S2, radius RV (0: the loop) over the histogram as S1 left it
+template <int RV, typename COUNT>
+void launch_smooth(const Run &r) {
+    fseg_ctx *c = r.c;
+    hipLaunchKernelGGL((k_smooth<RV, COUNT>), dim3(grid_for(c->n_tiles, 1, 16384)), dim3(kSmoothThreads), 0, r.s, c->n_tiles, c->d_tile_desc.p,
+                       c->d_y_raw.as<COUNT>(), c->d_w_main.p,
+                       c->P.radius_main, c->d_y.p, r.flag_pos_bits,
+                       r.flag_cand_bits, c->d_blk_pre.p, c->d_tile_tot.p, c->d_tile_defer.p);
+}
+template <int RV>
+void launch_smooth_as(const Run &r) {
+    if (r.c->yraw_narrow) launch_smooth<RV, uint16_t>(r); else launch_smooth<RV, int>(r);
+}
+// A position compaction (`plane` 1: the candidates, 2: the final positions) on the main stream: the flagged positions' values,
+// positions and intervals into the lists, every interval's offset into off[0 .. K]
+void launch_positions(const Run &r, const unsigned *flags, int plane, u64 *total, i64 *off, int *out_y, int *out_pos, int *out_iv) {
+    fseg_ctx *c = r.c;
+    if (!r.scan_single)
+        hipLaunchKernelGGL(k_pos_count, dim3(grid_for(pos_groups(c->NPOS), 1, 4096)), dim3(kPosCountThreads), 0, r.s, flags, c->NPOS, r.bsum, r.gsum);
+    hipLaunchKernelGGL(k_scan_emit<kEmitPositions>, dim3(r.pos_grid), dim3(256), 0, r.s, flags, c->NPOS,
+                       r.bsum, r.gsum, c->d_scan_state.p + plane * r.scan_nb, total, off + c->K, &r.st->err, (const double *)nullptr, (double *)nullptr, c->K, c->d_pos_off.p,
+                       c->d_iv_start.p, c->d_blk_iv0.p, out_y, out_pos,
+                       off, 0, out_iv);
+}
+// The problem ranges under `split`, with the block sums of the problem scan (bs) or without (null), and the scan as launches of
+// its own (blocks: k_prob_scan1 makes the block sums): S4, and the sized first run's rescan under another split
+void launch_prob_range(fseg_ctx *c, ProbSplit split, i64 *bs) {
+    hipLaunchKernelGGL(k_prob_range, dim3(prob_grid(c)), dim3(kRangeThreads), 0, c->stream, c->d_status.p, c->d_cand_pn.p,
+                       c->d_seg_iv.p, c->d_cand_y.p, c->d_iv_part.p, c->d_iv_start.p,
+                       c->d_part_lane_off.p, c->d_lane_start.p, c->d_lane_pmax.p,
+                       c->d_cand_ll.p, c->d_cand_ln.p, c->d_cand_wide.p, c->d_lane_lx.p,
+                       c->d_lex.p, c->wide_by_seen ? 1 : 0, split.fuse_lanes, bs, split);
+}
+void launch_prob_scan(fseg_ctx *c, ProbSplit split, i64 *bs, bool blocks) {
+    if (blocks)
+        hipLaunchKernelGGL(k_prob_scan1, dim3(prob_grid(c)), dim3(256), 0, c->stream, c->d_status.p, c->d_cand_pn.p, c->d_cand_ln.p, c->d_cand_wide.p, bs, split);
+    hipLaunchKernelGGL(k_prob_scan2, dim3(1), dim3(256), 0, c->stream, c->d_status.p, bs);
+}
+// The arena path's DP: the list of `dp_class` (-1: every class in one launch) by dp_blocks workgroups, the problems of more than
+// n_lo candidates.  The large class's launch carries the label arena, and fill_blocks more workgroups that fill it (Run::ride_fill).
+template <int NM, int T, typename OUTT>
+void launch_dp(const Run &r, hipStream_t q, int dp_class, int n_lo, int dp_blocks, int fill_blocks) {
+    fseg_ctx *c = r.c;
+    hipLaunchKernelGGL((k_dp<NM, T, OUTT>), dim3(dp_blocks + fill_blocks), dim3(T),
+                       dp_lds_for(nm_of<NM>(c), (int)sizeof(OUTT)), q, r.st, dp_class, nm_of<NM>(c), c->d_dp_items.p, r.pr,
+                       c->d_prob_desc.p, c->prob_cap, c->d_cand_off.p, c->d_cand_y.p, c->d_iv_part.p,
+                       c->d_part_lane_off.p, c->d_out.p, c->tri_cap, c->d_amb.p,
+                       c->d_pair_thr.p, c->pair_cap, c->P.min_read_support_outside,
+                       c->d_chosen.p, n_lo, dp_blocks,
+                       NM == kNMax ? c->d_labels.as<uint4>() : (uint4 *)nullptr, NM == kNMax ? r.labels_n16 : (i64)0 FSEG_TARG);
+}
+// the small DP class's list: a wave per problem of up to kDpWave candidates (q_small), and beside them (q_mid) ...
+template <typename OUTT>
+void launch_dp_waves(const Run &r, hipStream_t q_small, hipStream_t q_mid) {
+    fseg_ctx *c = r.c;
+    hipLaunchKernelGGL((k_dp_waves<OUTT>), dim3(grid_for(c->prob_cap, 4, 2048)), dim3(256),
+                       dp_lds_for(kDpSmall, (int)sizeof(OUTT)) > 4 * dp_wave_bytes<OUTT>() ? dp_lds_for(kDpSmall, (int)sizeof(OUTT)) : 4 * dp_wave_bytes<OUTT>(),
+                       q_small, r.st, c->d_dp_items.p, r.pr, c->d_prob_desc.p, c->prob_cap,
+                       c->d_cand_y.p, c->d_out.p, c->tri_cap, c->d_amb.p,
+                       c->d_pair_thr.p, c->pair_cap, c->P.min_read_support_outside, c->d_chosen.p, 0);
+    // ... the problems of the list with 17 .. 32 candidates: one workgroup each, so that none waits behind another
+    launch_dp<kDpSmall, 256, OUTT>(r, q_mid, 0, kDpWave, grid_for(c->prob_cap, 1, 8192), 0);
+}
+// S6 (the histogram as S1 left it: uint16 where it ran packed)
+template <typename COUNT>
+void launch_refine(const Run &r) {
+    fseg_ctx *c = r.c;
+    hipLaunchKernelGGL(k_segments<COUNT>, dim3(grid_for(c->K, 1, 8192)), dim3(r.iv_threads), 0, r.s, c->K, c->d_pos_off.p,
+                       c->d_cand_off.p, c->d_cand_y.p, c->d_y_raw.as<COUNT>(), c->d_blk_pre.p, c->d_tile_tot.p, c->d_iv_tile0.p,
+                       c->d_chosen.p, r.flag_final_bits, c->d_rseg_c.p,
+                       c->d_seg_prev.p, r.st);
+    hipLaunchKernelGGL(k_refine<COUNT>, dim3(2048), dim3(64), 0, r.s, r.st, c->d_seg_iv.p, c->d_rseg_c.p,
+                       c->d_seg_prev.p, c->d_cand_y.p, c->d_pos_off.p, c->d_y_raw.as<COUNT>(),
+                       c->d_w_refine.p, c->P.radius_refine, c->P.sigma, c->d_g.p, c->d_pk.p,
+                       c->d_pf.p, c->d_kp.p, r.flag_final_bits);
+}
+
+// SEG_PRE1: status reset, histogram .. problem ranges and the problem scan
+void seg_pre1(Run &r) {
+    fseg_ctx *c = r.c;
+    hipStream_t s = r.s;
+    Status *st = r.st;
+    const int n_part = c->n_part;
+    const i64 K = c->K, NPOS = c->NPOS;
     {   // Status and the flag planes (OR-ed into: k_smooth, k_peaks_edges, k_segments, k_refine) by one launch (two memsets were three fill kernels)
         const i64 nw = 3 * (i64)flag_words(NPOS);
         hipLaunchKernelGGL(k_clear, dim3(grid_for(nw / 4 + 1, 256, 2048)), dim3(256), 0, s, st, c->d_bits.p, nw);
     }
-    begin(ST_HIST);
+    r.begin(ST_HIST);
     // S1
-    // (the chunks were laid out on upload for one counter width: one instance per launch)
-#define FSEG_LAUNCH_HIST(BITS, OUT)                                                                                    \
-    hipLaunchKernelGGL((k_hist<BITS, OUT>), dim3(grid_for(c->n_hist_chunks, 1, 16384)), dim3(512), 0, s, c->n_hist_chunks,   \
-                       c->d_hc_part.p, c->d_hc_p0.p, c->d_hc_n.p, c->d_hc_glo.p,       \
-                       c->d_hc_ghi.p, c->d_hc_llo.p, c->d_hc_lhi.p, c->d_part_iv_off.p, c->d_iv_start.p, c->d_iv_end.p, \
-                       c->d_pos_off.p, c->d_part_lane_off.p, c->d_lane_lx.p,                  \
-                       c->d_lane_start.p, c->d_lane_pmax.p,                                            \
-                       c->d_lex.p, c->P.ignore_ends, c->d_y_raw.as<OUT>(), st,                                \
-                       scan_state, scan_single ? scan_nb * 3 : 0)
     c->paths[fseg_ctx::PATH_HIST16] = c->hist_packed;
     c->paths[fseg_ctx::PATH_YRAW16] = c->yraw_narrow;
-    if (c->yraw_narrow) { FSEG_LAUNCH_HIST(16, uint16_t); }
-    else if (c->hist_packed) { FSEG_LAUNCH_HIST(16, int); }
-    else { FSEG_LAUNCH_HIST(32, int); }
-#undef FSEG_LAUNCH_HIST
-    end(ST_HIST); begin(ST_SMOOTH);
+    if (c->yraw_narrow) launch_hist<16, uint16_t>(r);
+    else if (c->hist_packed) launch_hist<16, int>(r);
+    else launch_hist<32, int>(r);
+    r.end(ST_HIST); r.begin(ST_SMOOTH);
     // S2
-#define FSEG_LAUNCH_SMOOTH_AS(RV, COUNT)                                                                               \
-    hipLaunchKernelGGL((k_smooth<RV, COUNT>), dim3(tile_grid), dim3(kSmoothThreads), 0, s, c->n_tiles, c->d_tile_desc.p,      \
-                       c->d_y_raw.as<COUNT>(), c->d_w_main.p,                                               \
-                       c->P.radius_main, c->d_y.p, flag_pos_bits,                           \
-                       flag_cand_bits, c->d_blk_pre.p, c->d_tile_tot.p, c->d_tile_defer.p)
-#define FSEG_LAUNCH_SMOOTH(RV) do { if (c->yraw_narrow) { FSEG_LAUNCH_SMOOTH_AS(RV, uint16_t); } else { FSEG_LAUNCH_SMOOTH_AS(RV, int); } } while (0)
     // sigma = 5 (default) and sigma = 3 (config 5) have their own unrolled instances; any other radius runs the loop
-    if (c->P.radius_main == 20) { c->paths[fseg_ctx::PATH_SMOOTH_R] = 20; FSEG_LAUNCH_SMOOTH(20); }
-    else if (c->P.radius_main == 12) { c->paths[fseg_ctx::PATH_SMOOTH_R] = 12; FSEG_LAUNCH_SMOOTH(12); }
-    else { c->paths[fseg_ctx::PATH_SMOOTH_R] = 0; FSEG_LAUNCH_SMOOTH(0); }
-#undef FSEG_LAUNCH_SMOOTH
-#undef FSEG_LAUNCH_SMOOTH_AS
-    end(ST_SMOOTH);
+    if (c->P.radius_main == 20) { c->paths[fseg_ctx::PATH_SMOOTH_R] = 20; launch_smooth_as<20>(r); }
+    else if (c->P.radius_main == 12) { c->paths[fseg_ctx::PATH_SMOOTH_R] = 12; launch_smooth_as<12>(r); }
+    else { c->paths[fseg_ctx::PATH_SMOOTH_R] = 0; launch_smooth_as<0>(r); }
+    r.end(ST_SMOOTH);
     // S3a threshold: needs only the smoothed signal, like the candidates (S3b) -- the two chains run side by side
-    {
-    hipStream_t q = fork(0);
-    if (stage_events && c->profile_all) (void)hipEventRecord(c->ev_b[ST_THRESHOLD], q);
+    hipStream_t q = r.fork(0);
+    if (r.stage_events && c->profile_all) (void)hipEventRecord(c->ev_b[ST_THRESHOLD], q);
     // batches of many partitions of moderate size: a workgroup per partition does the whole threshold (k_thr_part); a batch of a
     // few large partitions (config 2: one) keeps the batch-wide compaction and a workgroup per 8192-value chunk
     // (Until the end of round 5 a context that shares the device kept the chunk kernels: host memory -> host memory, eight contexts, the job
@@ -753,81 +835,77 @@ int enqueue_run(fseg_ctx *c, unsigned segs, bool sized = false, i64 label_fill_b
     if (thr_part) {
         c->paths[fseg_ctx::PATH_THR_PART] = 1;
         hipLaunchKernelGGL(k_thr_part, dim3(grid_for(n_part, 1, 4096)), dim3(512), 0, q, n_part, c->d_part_iv_off.p, c->d_pos_off.p, NPOS,
-                           flag_pos_bits, c->d_y.p, c->d_v.p, c->P.variance_factor, c->d_mean.p, c->d_thr.p);
+                           r.flag_pos_bits, c->d_y.p, c->d_v.p, c->P.variance_factor, c->d_mean.p, c->d_thr.p);
     } else {
-    c->paths[fseg_ctx::PATH_THR_PART] = 0;
-    scan_counts(q, bsum_side, flag_pos_bits, &st->n_vals, nullptr);
-    hipLaunchKernelGGL(k_scan_emit<kEmitValues>, dim3(scan_grid), dim3(256), 0, q, flag_pos_bits, NPOS,
-                       bsum_side, (const int *)nullptr, scan_state, &st->n_vals, (i64 *)nullptr, &st->err, c->d_y.p, c->d_v.p, K, c->d_pos_off.p,
-                       c->d_iv_start.p, c->d_blk_iv0.p, (int *)nullptr, (int *)nullptr, (i64 *)nullptr,
-                       c->force_scan_stall ? 1 : 0, (int *)nullptr);
-    hipLaunchKernelGGL(k_voff, dim3(grid_for(n_part + 1, 1, 2048)), dim3(64), 0, q, n_part, c->d_part_iv_off.p,
-                       c->d_pos_off.p, NPOS, flag_pos_bits, bsum_side, scan_state, &st->n_vals,
-                       c->d_voff.p);
-    hipLaunchKernelGGL(k_vplan, dim3(1), dim3(256), 0, q, n_part, c->d_part_iv_off.p, c->d_pos_off.p, NPOS,
-                       c->d_voff.p, c->d_chunk_off.p, st, c->chunk_cap);
-    int chunk_grid = grid_for(c->chunk_cap, 1, 4096);
-    double *csum0 = c->d_csum.p, *csum1 = csum0 + c->chunk_cap;
-    for (int pass = 0; pass < 2; ++pass)
-        hipLaunchKernelGGL(k_vsum_chunks, dim3(chunk_grid), dim3(512), 0, q, n_part, c->d_voff.p,
-                           c->d_chunk_off.p, c->d_v.p, csum0, pass, pass ? csum1 : csum0, c->chunk_cap);
-    hipLaunchKernelGGL(k_vsum_part, dim3(grid_for(n_part, 64, 1024)), dim3(64), 0, q, n_part, c->d_voff.p,
-                       c->d_chunk_off.p, csum0, csum1, c->P.variance_factor, c->d_mean.p,
-                       c->d_thr.p, c->chunk_cap);
+        c->paths[fseg_ctx::PATH_THR_PART] = 0;
+        u64 *scan_state = c->d_scan_state.p;
+        if (!r.scan_single) {
+            hipLaunchKernelGGL(k_scan1, dim3(grid_for(r.scan_nb, 1, 4096)), dim3(256), 0, q, r.flag_pos_bits, NPOS, r.bsum_side);
+            hipLaunchKernelGGL(k_scan2, dim3(1), dim3(kScan2Threads), 0, q, r.bsum_side, r.scan_nb, &st->n_vals, (i64 *)nullptr);
+        }
+        hipLaunchKernelGGL(k_scan_emit<kEmitValues>, dim3(r.scan_grid), dim3(256), 0, q, r.flag_pos_bits, NPOS,
+                           r.bsum_side, (const int *)nullptr, scan_state, &st->n_vals, (i64 *)nullptr, &st->err, c->d_y.p, c->d_v.p, K, c->d_pos_off.p,
+                           c->d_iv_start.p, c->d_blk_iv0.p, (int *)nullptr, (int *)nullptr, (i64 *)nullptr,
+                           c->force_scan_stall ? 1 : 0, (int *)nullptr);
+        hipLaunchKernelGGL(k_voff, dim3(grid_for(n_part + 1, 1, 2048)), dim3(64), 0, q, n_part, c->d_part_iv_off.p,
+                           c->d_pos_off.p, NPOS, r.flag_pos_bits, r.bsum_side, scan_state, &st->n_vals,
+                           c->d_voff.p);
+        hipLaunchKernelGGL(k_vplan, dim3(1), dim3(256), 0, q, n_part, c->d_part_iv_off.p, c->d_pos_off.p, NPOS,
+                           c->d_voff.p, c->d_chunk_off.p, st, c->chunk_cap);
+        int chunk_grid = grid_for(c->chunk_cap, 1, 4096);
+        double *csum0 = c->d_csum.p, *csum1 = csum0 + c->chunk_cap;
+        for (int pass = 0; pass < 2; ++pass)
+            hipLaunchKernelGGL(k_vsum_chunks, dim3(chunk_grid), dim3(512), 0, q, n_part, c->d_voff.p,
+                               c->d_chunk_off.p, c->d_v.p, csum0, pass, pass ? csum1 : csum0, c->chunk_cap);
+        hipLaunchKernelGGL(k_vsum_part, dim3(grid_for(n_part, 64, 1024)), dim3(64), 0, q, n_part, c->d_voff.p,
+                           c->d_chunk_off.p, csum0, csum1, c->P.variance_factor, c->d_mean.p,
+                           c->d_thr.p, c->chunk_cap);
     }
-    if (stage_events && c->profile_all) (void)hipEventRecord(c->ev_e[ST_THRESHOLD], q);
-    }
-    begin(ST_CANDIDATES);
+    if (r.stage_events && c->profile_all) (void)hipEventRecord(c->ev_e[ST_THRESHOLD], q);
+    r.begin(ST_CANDIDATES);
     // S3b candidates
     hipLaunchKernelGGL(k_peaks_edges, dim3(grid_for(c->n_tiles, 256, 4096)), dim3(256), 0, s, c->n_tiles, c->d_tile_desc.p,
-                       c->d_tile_defer.p, c->d_y.p, flag_cand_bits, c->d_part_has2.p, n_part);
-    pos_counts(s, flag_cand_bits);
-    hipLaunchKernelGGL(k_scan_emit<kEmitPositions>, dim3(pos_grid), dim3(256), 0, s, flag_cand_bits, NPOS,
-                       bsum, gsum, scan_state + scan_nb, &st->n_cand, c->d_cand_off.p + K, &st->err, (const double *)nullptr, (double *)nullptr, K, c->d_pos_off.p,
-                       c->d_iv_start.p, c->d_blk_iv0.p, c->d_cand_y.p, (int *)nullptr,
-                       c->d_cand_off.p, 0, (int *)nullptr);
-    end(ST_CANDIDATES);
-    join(0);
-    early_fork();
-    begin(ST_FIX);
+                       c->d_tile_defer.p, c->d_y.p, r.flag_cand_bits, c->d_part_has2.p, n_part);
+    launch_positions(r, r.flag_cand_bits, 1, &st->n_cand, c->d_cand_off.p, c->d_cand_y.p, nullptr, nullptr);
+    r.end(ST_CANDIDATES);
+    r.join(0);
+    r.early_fork();
+    r.begin(ST_FIX);
     // S4
-    c->paths[fseg_ctx::PATH_IV_THREADS] = iv_threads;              // (k_segments, S6, is launched with the same block)
-    hipLaunchKernelGGL(k_fix, dim3(grid_for(K, 1, 8192)), dim3(iv_threads), 0, s, K, c->d_pos_off.p,
+    c->paths[fseg_ctx::PATH_IV_THREADS] = r.iv_threads;              // (k_segments, S6, is launched with the same block)
+    hipLaunchKernelGGL(k_fix, dim3(grid_for(K, 1, 8192)), dim3(r.iv_threads), 0, s, K, c->d_pos_off.p,
                        c->d_iv_part.p, c->d_cand_off.p, c->d_cand_y.p, c->d_y.p,
                        c->d_thr.p, c->P.max_problem_size, c->d_fixed0.p,
                        c->d_added.p, c->d_fixed.p, c->d_chosen.p,
                        c->d_cand_pn.p, c->d_seg_iv.p, st);
     // (with the block sums of the problem scan when the scan is a launch of its own: k_prob_scan1 is the rescan's only)
-    i64 *range_bs = prob_bs;
-    hipLaunchKernelGGL(k_prob_range, dim3(pg), dim3(kRangeThreads), 0, s, st, c->d_cand_pn.p,
-                       c->d_seg_iv.p, c->d_cand_y.p, c->d_iv_part.p, c->d_iv_start.p,
-                       c->d_part_lane_off.p, c->d_lane_start.p, c->d_lane_pmax.p,
-                       c->d_cand_ll.p, c->d_cand_ln.p, c->d_cand_wide.p, c->d_lane_lx.p,
-                       c->d_lex.p, c->wide_by_seen ? 1 : 0, split.fuse_lanes, range_bs, split);
-    if (prob_bs) {
-        if (!range_bs)
-            hipLaunchKernelGGL(k_prob_scan1, dim3(pg), dim3(256), 0, s, st, c->d_cand_pn.p, c->d_cand_ln.p, c->d_cand_wide.p, prob_bs, split);
-        hipLaunchKernelGGL(k_prob_scan2, dim3(1), dim3(256), 0, s, st, prob_bs);
-    }
-    end(ST_FIX);
-    }   // do_pre1
-    bool score_begun = false;
-    if (do_pre2) {
-    if (!do_pre1) early_fork();
-    begin(ST_SCORE_PREP);
-    hipLaunchKernelGGL(k_prob_emit, dim3(pg), dim3(256), 0, s, st, c->d_cand_pn.p, c->d_cand_ll.p,
-                       c->d_cand_ln.p, c->d_seg_iv.p, c->d_cand_off.p, prob_bs,
+    launch_prob_range(c, r.split, r.prob_bs);
+    if (r.prob_bs) launch_prob_scan(c, r.split, r.prob_bs, false);
+    r.end(ST_FIX);
+}
+
+// SEG_PRE2: problem list, pair thresholds, window coverage
+void seg_pre2(Run &r) {
+    fseg_ctx *c = r.c;
+    hipStream_t s = r.s;
+    Status *st = r.st;
+    const ProblemArrays &pr = r.pr;
+    if (!(r.segs & SEG_PRE1)) r.early_fork();
+    r.begin(ST_SCORE_PREP);
+    hipLaunchKernelGGL(k_prob_emit, dim3(r.pg), dim3(256), 0, s, st, c->d_cand_pn.p, c->d_cand_ll.p,
+                       c->d_cand_ln.p, c->d_seg_iv.p, c->d_cand_off.p, r.prob_bs,
                        pr, c->prob_cap, c->d_work_pc.p, c->d_cls_items.p,
                        c->work_cap, c->d_dp_items.p, c->d_prob_desc.p, c->d_iv_start.p,
-                       c->d_iv_part.p, c->d_part_lane_off.p, split, c->d_solve_items.p, c->d_solve_desc.p,
+                       c->d_iv_part.p, c->d_part_lane_off.p, r.split, c->d_solve_items.p, c->d_solve_desc.p,
                        c->d_wide_items.p, c->d_wide_all.p, c->d_cand_wide.p,
-                       dev_sync ? sw : (SyncWords *)nullptr, sync_gen);
-    launch_fork_waiters();
+                       r.dev_sync ? r.sw : (SyncWords *)nullptr, r.sync_gen);
+    r.launch_fork_waiters();
     // S5.  The arena path's window coverage (and pair thresholds) are launches of their own in front of k_score: they are
     // interval scoring (get_cumulative_coverage :188-246 -- the solve-list kernels do the same inside their workgroups), so
     // where the stages are bracketed by events the scoring stage's bracket opens here
-    if (c->prob_cap > 0 && any_arena) {
-        if (stage_events && do_score) { end(ST_SCORE_PREP); begin(ST_SCORE); score_begun = true; }
+    if (c->prob_cap > 0 && r.facts.any_arena) {
+        if (r.stage_events && (r.segs & SEG_SCORE)) { r.end(ST_SCORE_PREP); r.begin(ST_SCORE); r.score_begun = true; }
+        const int work_grid = grid_for(c->work_cap, 1, 4096);
         const int cov_blocks = work_grid < 2048 ? work_grid : 2048;
         const int pt_blocks = c->small_batch ? grid_for(c->prob_cap, 1, 512) : 0;       // fused only for small batches
         if (!pt_blocks)
@@ -844,36 +922,62 @@ int enqueue_run(fseg_ctx *c, unsigned segs, bool sized = false, i64 label_fill_b
                            cov_blocks, pr, c->d_h_table.p, c->P.h_len, c->P.threshold_rate, c->d_pair_thr.p,
                            c->pair_cap, c->d_amb.p, c->d_out.p, c->tri_cap);
     }
-    if (!score_begun) end(ST_SCORE_PREP);
-    }   // do_pre2
-    if (do_score && !score_begun) begin(ST_SCORE);
+    if (!r.score_begun) r.end(ST_SCORE_PREP);
+}
+
+// The census words (fseg_ctx::paths) by who writes them: the scoring stage resets ITS words where it begins, the others are
+// written by their own stages (PATH_LANE_SORT by the upload).  A new word joins one of the two lists, or this does not compile.
+constexpr int kScoreCensus[] = {
+    fseg_ctx::PATH_SMALL_BATCH, fseg_ctx::PATH_TINY_ON, fseg_ctx::PATH_WAVE_ON, fseg_ctx::PATH_FUSE_ON, fseg_ctx::PATH_KEY32,
+    fseg_ctx::PATH_N_SOLVE, fseg_ctx::PATH_N_SOLVE + 1, fseg_ctx::PATH_N_SOLVE + 2, fseg_ctx::PATH_N_WIDE, fseg_ctx::PATH_N_WIDE + 1,
+    fseg_ctx::PATH_N_WIDE + 2, fseg_ctx::PATH_N_TINY, fseg_ctx::PATH_N_WORK, fseg_ctx::PATH_DPW, fseg_ctx::PATH_WIDE16, fseg_ctx::PATH_KNOWN,
+    fseg_ctx::PATH_SOLVE8, fseg_ctx::PATH_TINY_KERNEL, fseg_ctx::PATH_SCORE, fseg_ctx::PATH_PLAN, fseg_ctx::PATH_N_ARENA_PROB,
+    fseg_ctx::PATH_N_SCORE, fseg_ctx::PATH_N_SCORE + 1, fseg_ctx::PATH_N_SCORE + 2};
+constexpr int kOtherCensus[] = {fseg_ctx::PATH_THR_PART, fseg_ctx::PATH_LABEL_PACKED, fseg_ctx::PATH_ARENA_DP, fseg_ctx::PATH_HIST16,
+                                fseg_ctx::PATH_IV_THREADS, fseg_ctx::PATH_SMOOTH_R, fseg_ctx::PATH_YRAW16, fseg_ctx::PATH_LANE_SORT};
+constexpr bool census_covered() {
+    int seen[fseg_ctx::PATH_WORDS] = {};
+    for (int w : kScoreCensus) ++seen[w];
+    for (int w : kOtherCensus) ++seen[w];
+    for (int n : seen) if (n != 1) return false;
+    return true;
+}
+static_assert(census_covered(), "every census word is the scoring stage's or another stage's, none both");
+
+// SEG_SCORE: the interval-scoring kernels
+void seg_score(Run &r) {
+    fseg_ctx *c = r.c;
+    hipStream_t s = r.s;
+    Status *st = r.st;
+    const ProblemArrays &pr = r.pr;
+    const ScoreFacts &facts = r.facts;
+    const ScorePlan &ps = r.ps;
+    const bool known = facts.known, any_arena = facts.any_arena;
+    const int tiny_max = c->tiny_on ? kTiny : 0;
+    if (!r.score_begun) r.begin(ST_SCORE);
     int *const census = c->paths;
-    if (do_score) {
-        for (int w = 0; w < fseg_ctx::PATH_WORDS; ++w)
-            if (w != fseg_ctx::PATH_THR_PART && w != fseg_ctx::PATH_LABEL_PACKED && w != fseg_ctx::PATH_ARENA_DP && w != fseg_ctx::PATH_HIST16 &&
-                w != fseg_ctx::PATH_IV_THREADS && w != fseg_ctx::PATH_SMOOTH_R && w != fseg_ctx::PATH_YRAW16 && w != fseg_ctx::PATH_LANE_SORT) census[w] = 0;
-        census[fseg_ctx::PATH_SMALL_BATCH] = c->small_batch; census[fseg_ctx::PATH_TINY_ON] = c->tiny_on; census[fseg_ctx::PATH_WAVE_ON] = wave;
-        census[fseg_ctx::PATH_FUSE_ON] = c->use_fuse && c->fuse_on; census[fseg_ctx::PATH_KNOWN] = known; census[fseg_ctx::PATH_PLAN] = ps.on;
-    }
-    if (do_score && c->prob_cap > 0) {
-        // What the stage launches is the list `ops` (seg_score_plan.h: which instance over which list on which stream, and why),
-        // made at the top of this function.  Here the side streams are forked, the list is walked -- its order is the host's
+    for (int w : kScoreCensus) census[w] = 0;
+    census[fseg_ctx::PATH_SMALL_BATCH] = c->small_batch; census[fseg_ctx::PATH_TINY_ON] = c->tiny_on; census[fseg_ctx::PATH_WAVE_ON] = facts.wave;
+    census[fseg_ctx::PATH_FUSE_ON] = c->use_fuse && c->fuse_on; census[fseg_ctx::PATH_KNOWN] = known; census[fseg_ctx::PATH_PLAN] = ps.on;
+    if (c->prob_cap > 0) {
+        // What the stage launches is the list r.ops (seg_score_plan.h: which instance over which list on which stream, and why),
+        // made where the Run is built.  Here the side streams are forked, the list is walked -- its order is the host's
         // launch order -- and the streams are joined.
         const bool sfork = any_arena;                               // (the arena path's work-item kernels keep their streams)
         // (forked here: a side stream continues from where it was forked)
-        if (tiny_max > 0 && sfork) (void)fork(2);
-        if (!c->small_batch && sfork) { (void)fork(0); (void)fork(1); }
+        if (tiny_max > 0 && sfork) (void)r.fork(2);
+        if (!c->small_batch && sfork) { (void)r.fork(0); (void)r.fork(1); }
         if (ps.on) {
             // every side stream continues from HERE (the stage's begin event, when it is being recorded, is the first side
             // stream's fork: one marker packet less in front of everything -- each is ~5 us on its queue)
             // (every side stream on that one event: 0.135 -> 0.137-0.149 ms -- the records stagger the streams' starts)
-            bool shared = !(stage_events && forking);
+            bool shared = !(r.stage_events && r.forking);
             for (int k = 1; k < ps.n_seg; ++k) if (ps.used[k]) {
-                if (dev_side(k)) continue;           // forked early; its waiter (k_wait_word) is what the stream runs first
+                if (r.dev_side(k)) continue;         // forked early; its waiter (k_wait_word) is what the stream runs first
                 if (!shared) {
                     shared = true;
-                    if (hipError_t r = hipStreamWaitEvent(c->side[ps.side_of[k]], c->ev_b[ST_SCORE], 0); r != hipSuccess) fj_err = r;
-                } else (void)fork(ps.side_of[k]);
+                    if (hipError_t e = hipStreamWaitEvent(c->side[ps.side_of[k]], c->ev_b[ST_SCORE], 0); e != hipSuccess) r.fj_err = e;
+                } else (void)r.fork(ps.side_of[k]);
             }
         }
         census[fseg_ctx::PATH_KEY32] = facts.key32;
@@ -906,8 +1010,8 @@ int enqueue_run(fseg_ctx *c, unsigned segs, bool sized = false, i64 label_fill_b
                              ((abl & 32) && op.kind == ScoreKind::Wave));
         };
 #endif
-        for (int i = 0; i < ops.n; ++i) {
-            const ScoreOp &op = ops.op[i];
+        for (int i = 0; i < r.ops.n; ++i) {
+            const ScoreOp &op = r.ops.op[i];
             hipStream_t q = op.lane < 0 ? s : c->side[op.lane];
             // (a plan's side streams' waiters are released by k_prob_emit's last workgroup: emit_done)
 #ifdef FSEG_ABLATE_STAGE
@@ -937,80 +1041,63 @@ int enqueue_run(fseg_ctx *c, unsigned segs, bool sized = false, i64 label_fill_b
             // front of k_segments) instead of two marker + barrier packets per side stream
             unsigned dev_mask = 0;
             for (int k = 1; k < ps.n_seg; ++k) if (ps.used[k]) {
-                if (dev_side(k)) { hipLaunchKernelGGL(k_signal, dim3(1), dim3(64), 0, c->side[ps.side_of[k]], &sw->side_gen[ps.side_of[k]], sync_gen); dev_mask |= 1u << ps.side_of[k]; }
-                else join(ps.side_of[k]);
+                if (r.dev_side(k)) { hipLaunchKernelGGL(k_signal, dim3(1), dim3(64), 0, c->side[ps.side_of[k]], &r.sw->side_gen[ps.side_of[k]], r.sync_gen); dev_mask |= 1u << ps.side_of[k]; }
+                else r.join(ps.side_of[k]);
             }
-            if (dev_mask) hipLaunchKernelGGL(k_wait_word, dim3(1), dim3(64), 0, s, st, sw->side_gen, dev_mask, sync_gen, kSyncTicks);
+            if (dev_mask) hipLaunchKernelGGL(k_wait_word, dim3(1), dim3(64), 0, s, st, r.sw->side_gen, dev_mask, r.sync_gen, r.sync_ticks);
         }
         // (the tiny problems' kernel is joined at the end of this stage, so the stage's time bracket covers all scoring work)
-        if (!c->small_batch && sfork) { join(0); join(1); }
-        if (c->have_huge && any_arena) census[fseg_ctx::PATH_SCORE] |= 16;
-        if (c->have_huge && any_arena)
+        if (!c->small_batch && sfork) { r.join(0); r.join(1); }
+        if (c->have_huge && any_arena) {
+            census[fseg_ctx::PATH_SCORE] |= 16;
             hipLaunchKernelGGL(k_score_huge, dim3(256), dim3(512), kHugeScoreLds, s, st, c->d_dp_items.p, pr,
                                c->d_prob_desc.p, c->prob_cap, c->work_cap, c->d_cand_y.p,
                                c->d_cov.p, c->cov_cap, c->d_pair_thr.p, c->pair_cap,
                                c->d_out.p, c->tri_cap, c->d_amb.p);
-        if (c->have_huge && c->nm_giant > 0 && any_arena && c->d_giant.p) census[fseg_ctx::PATH_SCORE] |= 32;
-        if (c->have_huge && c->nm_giant > 0 && any_arena && c->d_giant.p)
+        }
+        if (c->have_huge && c->nm_giant > 0 && any_arena && c->d_giant.p) {
+            census[fseg_ctx::PATH_SCORE] |= 32;
             hipLaunchKernelGGL(k_score_giant, dim3(kGiantWgs), dim3(512), giant_score_lds(c->nm_giant), s, st, c->d_dp_items.p, pr,
                                c->d_prob_desc.p, c->prob_cap, c->work_cap, c->d_cand_y.p,
                                c->d_cov.p, c->cov_cap, c->d_pair_thr.p, c->pair_cap,
                                c->d_out.p, c->tri_cap, c->d_amb.p, c->nm_giant,
                                c->d_giant.as<unsigned char>(), (i64)giant_scratch_bytes(c->nm_giant));
-        if (tiny_max > 0 && sfork) join(2);    // k_tiny is interval scoring too: inside the stage's time bracket
+        }
+        if (tiny_max > 0 && sfork) r.join(2);    // k_tiny is interval scoring too: inside the stage's time bracket
     }
-    if (do_score) end(ST_SCORE);
-    const i64 labels_n16 = (c->label_cap + 15) / 16;            // the arena is allocated in multiples of 16 bytes
-    // the label arena's '0' fill rides the big-problem DP launch as extra workgroups -- unless the run is being sized
-    // (the arena's size is not known yet) or there is no DP launch
-    // (not where the stages are bracketed by events: the fill is the labels stage's work, and a DP bracket that holds it says nothing about the DP)
-    const bool lab_packed = labels_packed(c);                   // (two-bit labels: the arena is cleared by a memset, nothing rides)
-    const bool ride_fill = !sized && c->prob_cap > 0 && c->label_cap > 0 && any_arena && !stage_events && !lab_packed;
-    if (do_post1) {
-    begin(ST_DP);
+    r.end(ST_SCORE);
+}
+
+// SEG_POST1: DP, refinement, final positions, label columns
+void seg_post1(Run &r) {
+    fseg_ctx *c = r.c;
+    hipStream_t s = r.s;
+    Status *st = r.st;
+    const ProblemArrays &pr = r.pr;
+    const int tiny_max = c->tiny_on ? kTiny : 0;
+    r.begin(ST_DP);
     c->paths[fseg_ctx::PATH_ARENA_DP] = 0;
-    if (c->prob_cap > 0 && any_arena) {
+    if (c->prob_cap > 0 && r.facts.any_arena) {
         c->paths[fseg_ctx::PATH_ARENA_DP] = c->dp_wide_counts ? 4 : 2;
         int dp_grid = grid_for(c->prob_cap, 1, 1024);
-        const int fill_blocks = ride_fill ? grid_for(labels_n16 / 8 + 1, 512, 512) : 0;
-#define FSEG_LAUNCH_DP(NMV, TV, OUTT, NM_RT, DPCLASS, MAXWG)                                                             \
-        hipLaunchKernelGGL((k_dp<NMV, TV, OUTT>), dim3((dp_grid < (MAXWG) ? dp_grid : (MAXWG)) + fill_blocks), dim3(TV),     \
-                           dp_lds_for(NM_RT, (int)sizeof(OUTT)), ((NMV) == kDpSmall ? q_small : s), st, DPCLASS, NM_RT, c->d_dp_items.p, pr,          \
-                           c->d_prob_desc.p, c->prob_cap, c->d_cand_off.p, c->d_cand_y.p, c->d_iv_part.p,               \
-                           c->d_part_lane_off.p, c->d_out.p, c->tri_cap, c->d_amb.p,        \
-                           c->d_pair_thr.p, c->pair_cap, c->P.min_read_support_outside,                              \
-                           c->d_chosen.p, tiny_max, (dp_grid < (MAXWG) ? dp_grid : (MAXWG)),                \
-                           c->d_labels.as<uint4>(), labels_n16 FSEG_TARG)
-#define FSEG_LAUNCH_DP_WAVES(OUTT)                                                                                        \
-        hipLaunchKernelGGL((k_dp_waves<OUTT>), dim3(grid_for(c->prob_cap, 4, 2048)), dim3(256),                                \
-                           dp_lds_for(kDpSmall, (int)sizeof(OUTT)) > 4 * dp_wave_bytes<OUTT>() ? dp_lds_for(kDpSmall, (int)sizeof(OUTT)) : 4 * dp_wave_bytes<OUTT>(), \
-                           q_small, st, c->d_dp_items.p, pr, c->d_prob_desc.p, c->prob_cap,                \
-                           c->d_cand_y.p, c->d_out.p, c->tri_cap, c->d_amb.p,                \
-                           c->d_pair_thr.p, c->pair_cap, c->P.min_read_support_outside, c->d_chosen.p, 0); \
-        /* the problems of the list with 17 .. 32 candidates: one workgroup each, so that none waits behind another */      \
-        hipLaunchKernelGGL((k_dp<kDpSmall, 256, OUTT>), dim3(grid_for(c->prob_cap, 1, 8192)), dim3(256),                       \
-                           dp_lds_for(kDpSmall, (int)sizeof(OUTT)), q_mid, st, 0, kDpSmall, c->d_dp_items.p, pr,       \
-                           c->d_prob_desc.p, c->prob_cap, c->d_cand_off.p, c->d_cand_y.p, c->d_iv_part.p, \
-                           c->d_part_lane_off.p, c->d_out.p, c->tri_cap, c->d_amb.p,        \
-                           c->d_pair_thr.p, c->pair_cap, c->P.min_read_support_outside,                              \
-                           c->d_chosen.p, kDpWave, grid_for(c->prob_cap, 1, 8192), (uint4 *)nullptr, (i64)0 FSEG_TARG)
+        const int fill_blocks = r.ride_fill ? grid_for(r.labels_n16 / 8 + 1, 512, 512) : 0;
         // 16-bit count tables unless some problem sees >= 65536 reads;
         // 512 threads (8 waves share the c2 loop) when the tables of the largest problem leave room for their scratch.
         // small_batch: one launch over every problem; otherwise one launch per DP class list.
-        hipStream_t q_small = c->small_batch ? s : fork(0);      // the DP classes own disjoint problems
-        hipStream_t q_mid = c->small_batch ? s : fork(1);
+        hipStream_t q_small = c->small_batch ? s : r.fork(0);    // the DP classes own disjoint problems
+        hipStream_t q_mid = c->small_batch ? s : r.fork(1);
+        const int big_class = c->small_batch ? -1 : 1;
         if (c->dp_wide_counts) {
             const bool wide_wg = dp_lds_for(c->nm_big, 4) + 8 * 1024 <= kLdsPerWg;
-            if (!c->small_batch) { FSEG_LAUNCH_DP_WAVES(unsigned); }
-            if (wide_wg) { FSEG_LAUNCH_DP(kNMax, 512, unsigned, c->nm_big, c->small_batch ? -1 : 1, 256); }
-            else { FSEG_LAUNCH_DP(kNMax, 256, unsigned, c->nm_big, c->small_batch ? -1 : 1, 256); }
+            const int dp_blocks = dp_grid < 256 ? dp_grid : 256;
+            if (!c->small_batch) launch_dp_waves<unsigned>(r, q_small, q_mid);
+            if (wide_wg) launch_dp<kNMax, 512, unsigned>(r, s, big_class, tiny_max, dp_blocks, fill_blocks);
+            else launch_dp<kNMax, 256, unsigned>(r, s, big_class, tiny_max, dp_blocks, fill_blocks);
         } else {
-            if (!c->small_batch) { FSEG_LAUNCH_DP_WAVES(unsigned short); }
-            FSEG_LAUNCH_DP(kNMax, 512, unsigned short, c->nm_big, c->small_batch ? -1 : 1, 512);
+            if (!c->small_batch) launch_dp_waves<unsigned short>(r, q_small, q_mid);
+            launch_dp<kNMax, 512, unsigned short>(r, s, big_class, tiny_max, dp_grid < 512 ? dp_grid : 512, fill_blocks);
         }
-#undef FSEG_LAUNCH_DP
-#undef FSEG_LAUNCH_DP_WAVES
-        if (!c->small_batch) { join(0); join(1); }
+        if (!c->small_batch) { r.join(0); r.join(1); }
         if (c->have_huge)
             hipLaunchKernelGGL(k_dp_huge, dim3(dp_grid < 256 ? dp_grid : 256), dim3(512), kHugeDpLds, s, st, c->d_dp_items.p,
                                pr, c->d_prob_desc.p, c->prob_cap, c->d_cand_y.p, c->d_out.p,
@@ -1023,60 +1110,64 @@ int enqueue_run(fseg_ctx *c, unsigned segs, bool sized = false, i64 label_fill_b
                                c->P.min_read_support_outside, c->d_chosen.p, c->nm_giant,
                                c->d_giant.as<unsigned char>(), (i64)giant_scratch_bytes(c->nm_giant));
     }
-    end(ST_DP); begin(ST_REFINE);
-    // S6 (the histogram as S1 left it: uint16 where it ran packed)
-#define FSEG_LAUNCH_REFINE(COUNT)                                                                                      \
-    hipLaunchKernelGGL(k_segments<COUNT>, dim3(grid_for(K, 1, 8192)), dim3(iv_threads), 0, s, K, c->d_pos_off.p,                       \
-                       c->d_cand_off.p, c->d_cand_y.p, c->d_y_raw.as<COUNT>(), c->d_blk_pre.p, c->d_tile_tot.p, c->d_iv_tile0.p, \
-                       c->d_chosen.p, flag_final_bits, c->d_rseg_c.p,                        \
-                       c->d_seg_prev.p, st);                                                                   \
-    hipLaunchKernelGGL(k_refine<COUNT>, dim3(2048), dim3(64), 0, s, st, c->d_seg_iv.p, c->d_rseg_c.p, \
-                       c->d_seg_prev.p, c->d_cand_y.p, c->d_pos_off.p, c->d_y_raw.as<COUNT>(), \
-                       c->d_w_refine.p, c->P.radius_refine, c->P.sigma, c->d_g.p, c->d_pk.p, \
-                       c->d_pf.p, c->d_kp.p, flag_final_bits)
-    if (c->yraw_narrow) { FSEG_LAUNCH_REFINE(uint16_t); }
-    else { FSEG_LAUNCH_REFINE(int); }
-#undef FSEG_LAUNCH_REFINE
-    end(ST_REFINE); begin(ST_FINAL);
-    pos_counts(s, flag_final_bits);
-    hipLaunchKernelGGL(k_scan_emit<kEmitPositions>, dim3(pos_grid), dim3(256), 0, s, flag_final_bits,
-                       NPOS, bsum, gsum, scan_state + 2 * scan_nb, &st->n_final, c->d_final_off.p + K, &st->err, (const double *)nullptr, (double *)nullptr, K, c->d_pos_off.p,
-                       c->d_iv_start.p, c->d_blk_iv0.p, c->d_final_y.p, c->d_final_pos.p,
-                       c->d_final_off.p, 0, c->d_final_iv.p);
+    r.end(ST_DP); r.begin(ST_REFINE);
+    // S6
+    if (c->yraw_narrow) launch_refine<uint16_t>(r);
+    else launch_refine<int>(r);
+    r.end(ST_REFINE); r.begin(ST_FINAL);
+    launch_positions(r, r.flag_final_bits, 2, &st->n_final, c->d_final_off.p, c->d_final_y.p, c->d_final_pos.p, c->d_final_iv.p);
     // S7, first half: per-column thresholds and the label arena's plan
-    hipLaunchKernelGGL(k_label_cols, dim3(grid_for(NPOS / 8 + 1, 256, 2048)), dim3(256), 0, s, K, c->d_final_off.p,
+    hipLaunchKernelGGL(k_label_cols, dim3(grid_for(c->NPOS / 8 + 1, 256, 2048)), dim3(256), 0, s, c->K, c->d_final_off.p,
                        c->d_final_y.p, c->d_final_iv.p, c->d_iv_part.p, c->d_h_table.p, c->P.h_len,
                        c->P.threshold_rate, c->d_thr_tab.p, c->d_col_thr.p, c->d_col_zero.p,
-                       c->d_part_has2.p, n_part, c->d_part_iv_off.p, c->d_part_rep_off.p,
+                       c->d_part_has2.p, c->n_part, c->d_part_iv_off.p, c->d_part_rep_off.p,
                        c->d_label_off.p, st, c->label_cap);
-    end(ST_FINAL);
-    }   // do_post1
-    if (do_post2) {
-    begin(ST_LABEL);
+    r.end(ST_FINAL);
+}
+
+// SEG_POST2: label arena fill + per-read labels; a sized run fills exactly label_fill_bytes with a kernel of its own
+void seg_post2(Run &r, i64 label_fill_bytes) {
+    fseg_ctx *c = r.c;
+    hipStream_t s = r.s;
+    const bool lab_packed = r.lab_packed;
+    r.begin(ST_LABEL);
     if (c->label_cap > 0) {
         c->run_label_packed = lab_packed; c->labels_unpacked = false;
         c->paths[fseg_ctx::PATH_LABEL_PACKED] = lab_packed;
+        const i64 n16 = r.sized ? (label_fill_bytes + 15) / 16 : r.labels_n16;
         if (lab_packed) {
-            const i64 n16 = sized ? (label_fill_bytes + 15) / 16 : labels_n16;
             if (n16 > 0)                                            // (one launch: a hipMemsetAsync of 19 MB is two fill kernels here)
                 hipLaunchKernelGGL(k_clear, dim3(grid_for(n16 / 4 + 1, 256, 4096)), dim3(256), 0, s, (Status *)nullptr, c->d_packed.p, n16);
-        } else if (!ride_fill) {                                    // no DP launch carried the fill
-            const i64 n16 = sized ? (label_fill_bytes + 15) / 16 : labels_n16;
+        } else if (!r.ride_fill) {                                  // no DP launch carried the fill
             if (n16 > 0)
                 hipLaunchKernelGGL(k_label_zero, dim3(grid_for(n16 / 8 + 1, 256, 4096)), dim3(256), 0, s, c->d_labels.as<uint4>(), n16);
         }
         const int lab_grid = grid_for((i64)c->n_rep_blocks * kLabelSplit, 1, c->label_grid > 0 && c->label_grid < 65536 ? c->label_grid : 65536);
         hipLaunchKernelGGL(k_label_reads, dim3(lab_grid), dim3(256), 0, s, c->n_rep_blocks,
-                           c->d_rb_part.p, c->d_rb_r0.p, c->d_label_off.p, c->label_cap, n_part,
+                           c->d_rb_part.p, c->d_rb_r0.p, c->d_label_off.p, c->label_cap, c->n_part,
                            c->d_part_iv_off.p, c->d_part_rep_off.p, c->d_final_off.p,
                            c->d_final_pos.p, c->d_col_thr.p, c->d_rep_exon_off.p,
                            c->d_ex_ts.p, c->d_ex_te.p, c->d_col_zero.p,
                            c->d_part_has2.p, c->d_labels.as<unsigned char>(), lab_packed ? c->d_packed.p : (unsigned *)nullptr);
     }
-    end(ST_LABEL);
-    }   // do_post2
-    if (segs & SEG_STATUS) HIP_TRY(c, hipMemcpyAsync(c->h_status.p, st, sizeof(Status), hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, fj_err);
+    r.end(ST_LABEL);
+}
+
+// Enqueue the segments `segs` of one run on the context's stream: the launch sequence of the pipeline, a function per segment.
+// A call holds any subset: everything (a replay as plain launches, a capture), the sized first run's three pieces, the halves
+// of a profiled replay's two graphs and the scoring stage between them.
+//   sized: the run is being launched piecewise with the host reading the sizes in between (first run of a batch):
+//          the problem scan always runs as its own kernels (their totals are what the host waits for) and the label
+//          arena is filled by its own kernel over exactly label_fill_bytes.
+int enqueue_run(fseg_ctx *c, unsigned segs, bool sized = false, i64 label_fill_bytes = 0) {
+    Run r(c, segs, sized);
+    if (segs & SEG_PRE1) seg_pre1(r);
+    if (segs & SEG_PRE2) seg_pre2(r);
+    if (segs & SEG_SCORE) seg_score(r);
+    if (segs & SEG_POST1) seg_post1(r);
+    if (segs & SEG_POST2) seg_post2(r, label_fill_bytes);
+    if (segs & SEG_STATUS) HIP_TRY(c, hipMemcpyAsync(c->h_status.p, r.st, sizeof(Status), hipMemcpyDeviceToHost, r.s));
+    HIP_TRY(c, r.fj_err);
     HIP_TRY(c, hipGetLastError());
     return FSEG_OK;
 }
@@ -1217,7 +1308,7 @@ static bool others_in_flight(const fseg_ctx *c) {
     if (c->device < 0 || c->device >= 64) return false;
     return g_in_flight[c->device].load(std::memory_order_acquire) - (c->counted_in_flight ? 1 : 0) > 0;
 }
-// the run owns the device and is worth branching (see enqueue_run)
+// the run owns the device and is worth branching (see Run::forking)
 static bool would_fork(const fseg_ctx *c) { return c->use_fork && !c->small_batch && c->owns_device && c->side[0] != nullptr; }
 static int finish_run_impl(fseg_ctx *c);
 int finish_run(fseg_ctx *c) {
@@ -1324,19 +1415,12 @@ int run_sized(fseg_ctx *c) {
                                       (int)c->tiny_on, (int)tiny, (int)c->fuse_on, (int)fuse, (unsigned long long)s.n_prob, s.max_ln);
                 const bool fuse_turned_on = fuse && !c->fuse_on;
                 c->tiny_on = tiny; c->fuse_on = fuse;
-                const int pg = grid_for(c->NPOS / 8 / kProbBlock + 1, 1, 1024);
+                const ProbSplit split = split_of(c, tiny, fuse);
                 Status *st = c->d_status.p;
-                if (fuse_turned_on)     // the first pass did not count the reads the wide problems keep: nobody was going to ask
-                    hipLaunchKernelGGL(k_prob_range, dim3(pg), dim3(kRangeThreads), 0, c->stream, st, c->d_cand_pn.p,
-                                       c->d_seg_iv.p, c->d_cand_y.p, c->d_iv_part.p, c->d_iv_start.p,
-                                       c->d_part_lane_off.p, c->d_lane_start.p, c->d_lane_pmax.p,
-                                       c->d_cand_ll.p, c->d_cand_ln.p, c->d_cand_wide.p, c->d_lane_lx.p,
-                                       c->d_lex.p, c->wide_by_seen ? 1 : 0, split_of(c, tiny, fuse).fuse_lanes, (i64 *)nullptr, split_of(c, tiny, fuse));
+                if (fuse_turned_on) launch_prob_range(c, split, nullptr);   // the first pass did not count the reads the wide problems keep: nobody was going to ask
                 // (the scan ADDS to the per-class counts of wide problems: the first scan's must not stay in them)
                 HIP_TRY(c, hipMemsetAsync(reinterpret_cast<char *>(st) + offsetof(Status, wide_cls), 0, sizeof(st->wide_cls), c->stream));
-                hipLaunchKernelGGL(k_prob_scan1, dim3(pg), dim3(256), 0, c->stream, st, c->d_cand_pn.p, c->d_cand_ln.p, c->d_cand_wide.p,
-                                   c->d_prob_bs.p, split_of(c, tiny, fuse));
-                hipLaunchKernelGGL(k_prob_scan2, dim3(1), dim3(256), 0, c->stream, st, c->d_prob_bs.p);
+                launch_prob_scan(c, split, c->d_prob_bs.p, true);
                 HIP_TRY(c, hipMemcpyAsync(c->h_status.p, st, sizeof(Status), hipMemcpyDeviceToHost, c->stream));
                 HIP_TRY(c, wait_stream(c));
                 s = *c->h_status;
