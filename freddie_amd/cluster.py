@@ -10,7 +10,9 @@ not depend on each other, so here round r of EVERY active partition of every tin
   output_isoforms :639-691 -> output_isoforms()
 The solve is HiGHS, not Gurobi: where a round's optimum is not unique the tie may be broken differently.  Under
 settings["incumbent"] = "cutoff" / "fallback" a round is one more device call (Context.round_incumbents: a greedy feasible isoform per
-problem), which bounds the solves and, under "fallback", answers for a solve that ends without a proven optimum."""
+problem), which bounds the solves and, under "fallback", answers for a solve that ends without a proven optimum.  Under
+settings["exact_cols"] = N > 0 a round is one more device call (Context.round_exact): every problem of at most N columns that fits the
+mask budget is solved there by enumeration, a proven optimum, and only the others go to the solver."""
 import os
 
 from . import cluster_prep, cluster_solve
@@ -19,11 +21,26 @@ MAX_WORKERS = 16
 FILES_PER_BATCH = 256
 
 
-def ilp_settings(recycle_model="constant", epsilon=0.2, offset=20, timeout=1, max_rounds=30, min_isoform_size=3, max_ilp=1000, incumbent="off"):
+EXACT_MASKS = 1 << 29     # the default mask budget of a round's exact call: what keeps the call at 24 columns under a round_models call on the
+                          # cluster-many workload (profiles/cluster_exact.txt)
+
+
+def ilp_settings(recycle_model="constant", epsilon=0.2, offset=20, timeout=1, max_rounds=30, min_isoform_size=3, max_ilp=1000, incumbent="off",
+                 exact_cols=0, exact_masks=EXACT_MASKS):
     """incumbent: "off"; "cutoff": every round's greedy incumbents (Context.round_incumbents, one device call a round) bound the solves'
-    objective; "fallback": and stand in for a solve that ends without a proven optimum (status INCUMBENT)."""
+    objective; "fallback": and stand in for a solve that ends without a proven optimum (status INCUMBENT).
+    exact_cols: 0, or the largest number of columns (<= 24) of a problem the GPU solves exactly by enumeration (Context.round_exact, one
+    device call a round) instead of the solver; exact_masks: that call's budget, the sum of 2^columns over the problems it takes."""
     return dict(recycle_model=recycle_model, K=2, epsilon=epsilon, offset=offset, timeout=timeout, max_rounds=max_rounds, threads=1,
-                min_isoform_size=min_isoform_size, max_ilp=max_ilp, incumbent=incumbent)
+                min_isoform_size=min_isoform_size, max_ilp=max_ilp, incumbent=incumbent, exact_cols=exact_cols, exact_masks=exact_masks)
+
+
+def check_exact(settings):
+    cols, masks = settings.get("exact_cols", 0), settings.get("exact_masks", EXACT_MASKS)
+    if not 0 <= cols <= cluster_solve.EXACT_MAX_COLS:
+        raise ValueError("exact_cols is %r: 0 .. %d" % (cols, cluster_solve.EXACT_MAX_COLS))
+    if cols and masks < 1:
+        raise ValueError("exact_masks is %r: at least 1" % (masks,))
 
 
 def garbage_costs(tint, recycle_model):
@@ -98,6 +115,7 @@ def cluster_tints(tints, part0, ctx, settings, solve=cluster_solve.solve_round, 
     tint['garbage_rids'] and the reads' 'partition' as cluster_tint() does, and returns per tint the timeout.log lines
     [(status, tint id, partition, round, remaining reps)].  on_round: called with a dict per solved round (tests, profiles)."""
     cluster_solve.check_settings(settings)
+    check_exact(settings)
     min_size, max_rounds = settings["min_isoform_size"], settings["max_rounds"]
     state = []                                               # a partition: its tint, number, remaining reps, isoforms; active or not
     for t, tint in enumerate(tints):
@@ -123,7 +141,11 @@ def cluster_tints(tints, part0, ctx, settings, solve=cluster_solve.solve_round, 
         if settings.get("incumbent", "off") != "off":        # one more device call behind the models; a refused problem raises below
             inc = ctx.round_incumbents([g for s in todo for g in (tints[s["t"]]["garbage_cost"][i] for i in s["remaining"])],
                                        settings["epsilon"], settings["offset"])
-        jobs = []
+        exact = None
+        if settings.get("exact_cols", 0) > 0:                # one more device call: the small problems' proven optima, no solve job for them
+            exact = ctx.round_exact([g for s in todo for g in (tints[s["t"]]["garbage_cost"][i] for i in s["remaining"])],
+                                    settings["epsilon"], settings["offset"], settings["exact_cols"], settings.get("exact_masks", EXACT_MASKS))
+        jobs, models, answers = [], [], []
         for p, s in enumerate(todo):
             tint = tints[s["t"]]
             model = cluster_prep.round_model(arr, p)
@@ -136,9 +158,19 @@ def cluster_tints(tints, part0, ctx, settings, solve=cluster_solve.solve_round, 
             model["key"] = (tint["id"], s["q"], round_num)        # (for a solver that logs, or replays: tests)
             if inc is not None:
                 model["incumbent"] = cluster_prep.round_incumbent(inc, p)
-            jobs.append((solve, model, settings))
+            models.append(model)
+            found = cluster_prep.round_exact_solution(exact, p) if exact is not None else None
+            if found is None:
+                answers.append(len(jobs))                    # the solver's: its place among the jobs
+                jobs.append((solve, model, settings))
+            elif found == "infeasible":
+                answers.append((cluster_solve.NO_SOLUTION, None, None))
+            else:
+                x = found[1]
+                answers.append((cluster_solve.OPTIMAL, x, [int(any(x[c] for c in support)) for support in model["support"]]))
         results = pool.map(_solve_job, jobs, chunksize=1) if pool is not None else [_solve_job(j) for j in jobs]
-        for s, (_, model, _), (status, x, e) in zip(todo, jobs, results):
+        for s, model, answer in zip(todo, models, answers):
+            status, x, e = results[answer] if isinstance(answer, int) else answer
             tint = tints[s["t"]]
             logs[s["t"]].append((status, tint["id"], s["q"], round_num, len(s["remaining"])))
             if on_round is not None:
@@ -199,6 +231,10 @@ def cluster_files(paths, settings, ctx, solve=cluster_solve.solve_round, pool=No
                 yield tints[file_off[f]:file_off[f + 1]], logs[file_off[f]:file_off[f + 1]]
 
 
+EXACT_HELP = ("Recommended where small problems dominate: 24 -- measured on an MI355X (profiles/cluster_exact.txt), the enumeration beats HiGHS at every "
+              "size up to 24 columns; the budget, not N, bounds a call.")
+
+
 # ---- the command line (py/freddie_cluster.py :37-110, :783-827) ---------------------------------------------------------------
 def parse_args(argv=None):
     import argparse
@@ -223,6 +259,13 @@ def parse_args(argv=None):
                         help="Greedy incumbents of every round's problems, computed on the GPU: cutoff = an objective bound for the solves; "
                              "fallback = also the round's isoform when a solve ends without a proven optimum (status INCUMBENT).  Default: off "
                              "(nothing changes)")
+    parser.add_argument("--exact-small", type=int, default=0, choices=range(0, cluster_solve.EXACT_MAX_COLS + 1), metavar="N",
+                        help="Problems of at most N columns (0 .. {}) are solved on the GPU by enumerating every column set: a proven optimum, the "
+                             "smallest set at equal cost, and no solver call.  Default: 0 (nothing changes, no extra call).  {}".format(
+                                 cluster_solve.EXACT_MAX_COLS, EXACT_HELP))
+    parser.add_argument("--exact-masks", type=int, default=EXACT_MASKS, metavar="M",
+                        help="Budget of a round's exact call: the sum of 2^columns over the problems it takes, smallest first; the rest go to the "
+                             "solver.  Default: {}".format(EXACT_MASKS))
     parser.add_argument("-t", "--threads", type=int, default=1, help="Number of processes that solve (at most {})".format(MAX_WORKERS))
     parser.add_argument("-l", "--logs-dir", type=str, default=None, help="Directory path where logs will be outputted. Default: No log")
     parser.add_argument("-o", "--outdir", type=str, default="freddie_cluster/", help="Path to output directory. Default: freddie_cluster/")
@@ -234,6 +277,8 @@ def parse_args(argv=None):
     assert args.threads > 0
     assert args.min_isoform_size >= 0
     assert args.max_rounds >= 0
+    if args.exact_masks < 1:
+        parser.error("--exact-masks must be at least 1")
     return args
 
 
@@ -243,7 +288,7 @@ def main(argv=None, make_context=None):
     args = parse_args(argv)
     args.segment_dir = args.segment_dir.rstrip("/")
     settings = ilp_settings(args.recycle_model, args.epsilon, args.gap_offset, args.timeout, args.max_rounds, args.min_isoform_size, args.max_ilp,
-                            args.incumbent)
+                            args.incumbent, args.exact_small, args.exact_masks)
     cluster_solve.check_settings(settings)
     jobs = []
     for contig in os.listdir(args.segment_dir):

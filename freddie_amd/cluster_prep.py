@@ -155,14 +155,15 @@ def split_list_evenly(l, m):
 # ---------------------------------------------------------------------------------------------------------------
 CLUSTER_SO = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libfreddie_cluster.so")
 CLUSTER_SRC = [os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "freddie_cluster.hip")]
-CLUSTER_HEADERS = [os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "clu_incumbent.h")]
+CLUSTER_HEADERS = [os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", n) for n in ("clu_incumbent.h", "clu_exact.h")]
 EXPORTS = ["fclu_abi_version", "fclu_create", "fclu_destroy", "fclu_last_error", "fclu_compat_graph", "fclu_last_timing",
            "fclu_last_paths",
            "fclu_partition", "fclu_partition_adj", "fclu_partition_results", "fclu_partition_timing",
            "fclu_preprocess", "fclu_preprocess_results", "fclu_partition_reads", "fclu_preprocess_timing",
            "fclu_group_reads", "fclu_partition_segment", "fclu_group_results", "fclu_group_timing",
            "fclu_round_setup", "fclu_round_models", "fclu_round_results", "fclu_round_timing",
-           "fclu_round_incumbents", "fclu_round_incumbent_results", "fclu_round_incumbent_timing"]
+           "fclu_round_incumbents", "fclu_round_incumbent_results", "fclu_round_incumbent_timing",
+           "fclu_round_exact", "fclu_round_exact_results", "fclu_round_exact_timing"]
 ERR_UNSUPPORTED = 3
 _lib = None
 
@@ -231,6 +232,11 @@ class _Incumbents(ctypes.Structure):
         (n, ctypes.c_void_p) for n in ("cost2", "start", "grow_steps", "repair_steps", "mem_off", "mem")]
 
 
+class _Exact(ctypes.Structure):
+    _fields_ = [("n_prob", ctypes.c_int32), ("cost2", ctypes.c_void_p), ("mask", ctypes.c_void_p), ("n_taken", ctypes.c_int64),
+                ("n_masks", ctypes.c_int64), ("n_launches", ctypes.c_int64)]
+
+
 def build(force=False, verbose=False):
     """hipcc -> libfreddie_cluster.so (in-tree; cross-compiles without a GPU)."""
     cmd = ["hipcc", "-O3", "--offload-arch=gfx950", "-shared", "-fPIC", "-I", _build.INCLUDE, "-o", CLUSTER_SO] + CLUSTER_SRC
@@ -297,6 +303,12 @@ def load():
     L.fclu_round_incumbent_results.argtypes = [vp, ctypes.POINTER(_Incumbents)]
     L.fclu_round_incumbent_timing.restype = ctypes.c_int
     L.fclu_round_incumbent_timing.argtypes = [vp] + [ctypes.POINTER(ctypes.c_float)] * 3
+    L.fclu_round_exact.restype = ctypes.c_int
+    L.fclu_round_exact.argtypes = [vp, vp, ctypes.c_double, ctypes.c_double, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64]
+    L.fclu_round_exact_results.restype = ctypes.c_int
+    L.fclu_round_exact_results.argtypes = [vp, ctypes.POINTER(_Exact)]
+    L.fclu_round_exact_timing.restype = ctypes.c_int
+    L.fclu_round_exact_timing.argtypes = [vp] + [ctypes.POINTER(ctypes.c_float)] * 3
     _lib = L
     return L
 
@@ -524,25 +536,29 @@ class Context:
         out["pairs"] = out["pairs"].reshape(-1, 2); out["grp"] = out["grp"].reshape(-1, 2); out["rows"] = out["rows"].reshape(-1, 3)
         return out
 
+    def _garbage2(self, what, garbage):
+        """Twice the garbage costs of the last round_models() call's columns as int32 (multiples of 0.5, as cluster_solve.garbage2()),
+        and that call's col_off."""
+        g = np.asarray(garbage, np.float64).reshape(-1)
+        g2 = np.rint(2.0 * g)
+        if g.size and not (np.isfinite(g).all() and (g2 == 2.0 * g).all() and (g2 >= 0).all() and (g2 < 2.0 ** 31).all()):
+            bad = int(np.flatnonzero(~(np.isfinite(g) & (g2 == 2.0 * g) & (g2 >= 0) & (g2 < 2.0 ** 31)))[0])
+            raise ClusterError("%s: garbage cost %r of column %d is not a multiple of 0.5 in [0, 2^30)" % (what, float(g[bad]), bad))
+        r = _Rounds()
+        rc = self._L.fclu_round_results(self._h, ctypes.byref(r))
+        if rc != 0:
+            raise ClusterError("%s: " % what + self._L.fclu_last_error(self._h).decode(), rc)
+        if g.size != int(r.n_cols):
+            raise ClusterError("%s: %d garbage costs for the %d columns of the last round_models() call" % (what, g.size, int(r.n_cols)))
+        return np.ascontiguousarray(g2, np.int32), _copy_out(r.col_off, r.n_prob + 1, np.int64)
+
     def round_incumbents(self, garbage, epsilon, offset, max_seeds=64):
         """Greedy incumbents of the problems of the last round_models() call, one device call (include/freddie_cluster.h,
         fclu_incumbents; the definition is cluster_solve.greedy_incumbent()): garbage = the garbage cost of every column of that batch,
         problem by problem (multiples of 0.5).  Returns numpy arrays: cost2 (twice the cost; -1 for a refused problem), start,
         grow_steps, repair_steps per problem, mem_off / mem (the members, as columns, ascending) and col_off; round_incumbent() cuts
         one problem out."""
-        g = np.asarray(garbage, np.float64).reshape(-1)
-        g2 = np.rint(2.0 * g)
-        if g.size and not (np.isfinite(g).all() and (g2 == 2.0 * g).all() and (g2 >= 0).all() and (g2 < 2.0 ** 31).all()):
-            bad = int(np.flatnonzero(~(np.isfinite(g) & (g2 == 2.0 * g) & (g2 >= 0) & (g2 < 2.0 ** 31)))[0])
-            raise ClusterError("round_incumbents: garbage cost %r of column %d is not a multiple of 0.5 in [0, 2^30)" % (float(g[bad]), bad))
-        r = _Rounds()
-        rc = self._L.fclu_round_results(self._h, ctypes.byref(r))
-        if rc != 0:
-            raise ClusterError("round_incumbents: " + self._L.fclu_last_error(self._h).decode(), rc)
-        if g.size != int(r.n_cols):
-            raise ClusterError("round_incumbents: %d garbage costs for the %d columns of the last round_models() call" % (g.size, int(r.n_cols)))
-        col_off = _copy_out(r.col_off, r.n_prob + 1, np.int64)
-        g2 = np.ascontiguousarray(g2, np.int32)
+        g2, col_off = self._garbage2("round_incumbents", garbage)
         rc = self._L.fclu_round_incumbents(self._h, g2.ctypes.data if g2.size else None, 1.0 - float(epsilon), 1.0 + float(epsilon), int(offset),
                                            int(max_seeds))
         if rc != 0:
@@ -560,6 +576,30 @@ class Context:
         a, b, f = ctypes.c_float(), ctypes.c_float(), ctypes.c_float()
         self._L.fclu_round_incumbent_timing(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(f))
         return dict(conflict_ms=a.value, starts_ms=b.value, pick_ms=f.value)
+
+    def round_exact(self, garbage, epsilon, offset, max_cols, max_masks):
+        """The proven optimum of every small problem of the last round_models() call by enumeration, one device call
+        (include/freddie_cluster.h, fclu_exact; the definition is cluster_solve.exact_small()): garbage as round_incumbents'; a problem
+        is taken when it has a model, at most max_cols (<= 24) columns and 2^columns fits what is left of max_masks, in ascending
+        (columns, problem).  Returns numpy arrays cost2 (twice the cost; -1: no feasible subset; -2: not taken or refused) and mask (bit c
+        = column c) per problem, col_off, and n_taken, n_masks, n_launches; round_exact_solution() cuts one problem out."""
+        g2, col_off = self._garbage2("round_exact", garbage)
+        rc = self._L.fclu_round_exact(self._h, g2.ctypes.data if g2.size else None, 1.0 - float(epsilon), 1.0 + float(epsilon), int(offset),
+                                      int(max_cols), int(max_masks))
+        if rc != 0:
+            raise ClusterError("fclu_round_exact: " + self._L.fclu_last_error(self._h).decode(), rc)
+        x = _Exact()
+        rc = self._L.fclu_round_exact_results(self._h, ctypes.byref(x))
+        if rc != 0:
+            raise ClusterError("fclu_round_exact_results: " + self._L.fclu_last_error(self._h).decode(), rc)
+        P = x.n_prob
+        return dict(n_prob=P, col_off=col_off, cost2=_copy_out(x.cost2, P, np.int64), mask=_copy_out(x.mask, P, np.uint32),
+                    n_taken=int(x.n_taken), n_masks=int(x.n_masks), n_launches=int(x.n_launches))
+
+    def round_exact_timing(self):
+        a, b, f = ctypes.c_float(), ctypes.c_float(), ctypes.c_float()
+        self._L.fclu_round_exact_timing(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(f))
+        return dict(prep_ms=a.value, search_ms=b.value, longest_launch_ms=f.value)
 
     def round_timing(self):
         a, b, f = ctypes.c_float(), ctypes.c_float(), ctypes.c_float()
@@ -655,6 +695,18 @@ def round_incumbent(arr, p):
     for c in arr["mem"][int(arr["mem_off"][p]):int(arr["mem_off"][p + 1])].tolist():
         x[c] = 1
     return int(arr["cost2"][p]) / 2.0, x
+
+
+def round_exact_solution(arr, p):
+    """Problem p of Context.round_exact(): (cost, x) -- the proven optimum's cost and a 0 / 1 per column --, "infeasible" when no subset
+    of the columns is feasible, or None when the problem was not taken."""
+    cost2 = int(arr["cost2"][p])
+    if cost2 == -1:
+        return "infeasible"
+    if cost2 < 0:
+        return None
+    mask = int(arr["mask"][p])
+    return cost2 / 2.0, [mask >> c & 1 for c in range(int(arr["col_off"][p + 1] - arr["col_off"][p]))]
 
 
 # ---------------------------------------------------------------------------------------------------------------

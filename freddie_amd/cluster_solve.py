@@ -20,7 +20,8 @@ With K = 2 the model is a function of the chosen column set S alone: e = the OR 
 cost = sum over S of popcount(C_c & e) + the others' garbage costs, S without an incompatible pair, every gap row of a member holding.
 greedy_incumbent() is a seeded greedy over exactly that (the definition the GPU's fclu_round_incumbents reproduces bit for bit); an
 incumbent in ``model["incumbent"]`` = (cost, x) gives solve_round() an objective cutoff and, under settings["incumbent"] == "fallback",
-the answer when the solve ends without a proven optimum (status INCUMBENT)."""
+the answer when the solve ends without a proven optimum (status INCUMBENT).  exact_small() enumerates all 2^R column sets of a problem
+of at most 24 columns (the definition the GPU's fclu_round_exact reproduces bit for bit): a proven optimum with no matrix and no solver."""
 import numpy as np
 
 OPTIMAL, NO_SOLUTION, INCUMBENT = "OPTIMAL", "NO_SOLUTION", "INCUMBENT"
@@ -186,6 +187,99 @@ def greedy_incumbent(model, settings, max_seeds=64):
             best = dict(cost2=cost2, cost=cost2 / 2.0, start=k, members=list(_bits(members)), grow_steps=grow_steps, repair_steps=repair_steps,
                         x=[members >> c & 1 for c in range(R)], e=[E >> j & 1 for j in model["inf_seg"]])
     return best
+
+
+EXACT_MAX_COLS = 24
+_POPC16 = None
+
+
+def _popcounts(v):
+    """popcount of every element of an int64 array of values below 2^32."""
+    global _POPC16
+    if _POPC16 is None:
+        t = np.zeros(1 << 16, np.int64)
+        for b in range(16):
+            t += (np.arange(1 << 16) >> b) & 1
+        _POPC16 = t
+    return _POPC16[v & 0xffff] + _POPC16[v >> 16]
+
+
+def exact_small(model, settings, chunk=1 << 16):
+    """The proven optimum of one round_model() dict (with ``garbage`` and ``max_lg``) of at most 24 columns by enumeration -- the
+    definition the GPU's fclu_round_exact reproduces bit for bit: dict(cost2, cost, mask, members, x, e), or None when no subset is
+    feasible.  e = the OR of the members' support (as solve_round()'s fallback computes it).
+
+    Search: all subsets S of the R columns as masks 0 .. 2^R - 1, bit c = column c, over the transposed model: per informative segment
+        the mask of its support and the mask of the columns with C = 1 there, per column the mask of the columns it conflicts with.
+    Feasible (the yardstick's test, tests/round_util.py subset_cost): no pair of model["pairs"] inside S, and every gap row (c, g, l)
+        holds: with G = the summed lengths of group g's segments whose support meets S and slack = 0 when c is in S, else max_lg, the row
+        is violated when (1.0 - eps) * G - offset - slack > l + 1e-9 or (1.0 + eps) * G + offset + slack < l - 1e-9, in doubles, these
+        operations in this order, none fused.  greedy_incumbent()'s test has no tolerance, because an incumbent must be feasible for
+        everybody; a proven optimum must not exclude what the model admits: eps 0.15, offset 20, G = 200, l = 250 holds with equality
+        in rationals, and in doubles 1.15 * 200 + 20 is below 250.
+    Cost: cost2 = the g2 of the columns outside S + 2 * the sum over S of popcount(C_c & e).  The smallest cost2 wins, then the smallest
+        mask as an integer.
+    The masks are evaluated ``chunk`` at a time as numpy arrays (R = 12 is one chunk and takes milliseconds)."""
+    R = model["n_cols"]
+    if R > EXACT_MAX_COLS:
+        raise ValueError("%d columns: exact_small takes %d at the most" % (R, EXACT_MAX_COLS))
+    g2 = garbage2(model["garbage"])
+    if len(g2) != R:
+        raise ValueError("%d garbage costs for %d columns" % (len(g2), R))
+    sup_of = {}
+    sup, corr, conf = [], [0] * len(model["inf_seg"]), [0] * R
+    for j, support in zip(model["inf_seg"], model["support"]):
+        sup.append(sum(1 << c for c in support))
+        sup_of[j] = sup[-1]
+    place = {j: k for k, j in enumerate(model["inf_seg"])}
+    for c, segs in enumerate(model["corrections"]):
+        for j in segs:
+            corr[place[j]] |= 1 << c
+    for a, b in model["pairs"]:
+        conf[a] |= 1 << b
+        conf[b] |= 1 << a
+    lo_f, hi_f, offset, max_lg = 1.0 - settings["epsilon"], 1.0 + settings["epsilon"], float(settings["offset"]), float(int(model["max_lg"]))
+    used = sorted(set(g for _, g, _ in model["gap_rows"]))
+    best = None
+    for m0 in range(0, 1 << R, chunk):
+        S = np.arange(m0, min(m0 + chunk, 1 << R), dtype=np.int64)
+        ok = np.ones(S.size, bool)
+        for c in range(R):
+            if conf[c]:
+                ok &= ~(((S >> c) & 1).astype(bool) & ((S & conf[c]) != 0))
+        G = {}
+        for g in used:
+            total = np.zeros(S.size, np.int64)
+            for j, ln in model["group_segs"][g]:
+                total += np.where((S & sup_of.get(j, 0)) != 0, ln, 0)
+            G[g] = total.astype(np.float64)
+        for c, g, l in model["gap_rows"]:
+            slack = np.where((S >> c) & 1, 0.0, max_lg)
+            a = lo_f * G[g]
+            a = a - offset
+            a = a - slack
+            b = hi_f * G[g]
+            b = b + offset
+            b = b + slack
+            ok &= ~((a > float(l) + 1e-9) | (b < float(l) - 1e-9))
+        if not ok.any():
+            continue
+        cost2 = np.zeros(S.size, np.int64)
+        for c in range(R):
+            cost2 += np.where((S >> c) & 1, 0, g2[c])
+        for s_mask, c_mask in zip(sup, corr):
+            if c_mask:
+                cost2 += 2 * np.where((S & s_mask) != 0, _popcounts(S & c_mask), 0)
+        key = np.where(ok, (cost2 << EXACT_MAX_COLS) | S, np.int64(1) << 62)
+        k = int(key.min())
+        if best is None or k < best:
+            best = k
+    if best is None:
+        return None
+    cost2, mask = best >> EXACT_MAX_COLS, best & ((1 << EXACT_MAX_COLS) - 1)
+    x = [mask >> c & 1 for c in range(R)]
+    return dict(cost2=cost2, cost=cost2 / 2.0, mask=mask, members=list(_bits(mask)), x=x,
+                e=[int(any(x[c] for c in support)) for support in model["support"]])
 
 
 def solve_round(model, settings):

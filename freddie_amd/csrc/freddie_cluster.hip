@@ -23,6 +23,7 @@
 #include <hip/hip_runtime.h>
 
 #include "clu_incumbent.h"   // (behind the runtime: its functions are __host__ __device__)
+#include "clu_exact.h"
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 
@@ -1382,6 +1383,94 @@ __global__ void __launch_bounds__(256) k_inc_pick(const int *list, const IncProb
     if (tid == 0) mem_cnt[p] = (int)(carry < d.n ? carry : d.n);
 }
 
+// ================================================================================================================
+// The exact solve of a round's small problems (fclu_round_exact): a problem of R <= 24 columns has 2^R column sets, each a few bit
+// operations on the transposed model (per informative segment the mask of its support and of the columns with C = 1; per column the mask
+// of its conflicts; per gap-group segment its support mask beside its length).  Every set is evaluated and the smallest
+// (cost2, mask) is the proven optimum.  The definition is cluster_solve.exact_small()'s docstring; what one thread computes is clu_exact.h.
+// ================================================================================================================
+struct ExactProb {
+    i64 col0, inf0;                   // first column (its conflict word and g2); first informative segment, numbered through the batch (table: 2 words each)
+    i64 pair0, pair1;                 // its pairs, as columns, in the round's pair list
+    i64 grp0, grp1, row0, row1;       // its gap groups and gap rows, numbered through the batch
+    i64 max_lg;                       // MAX_ISOFORM_LG: the slack of the gap rows of a column outside the set
+    int n, n_inf;                     // columns (<= 24), informative segments (<= 32 kMaxWords)
+};
+
+constexpr int kExactWgMasks = 4096;           // masks one workgroup evaluates (16 a thread): staging the table is a small share of it
+constexpr i64 kExactLaunchMasks = 1ll << 24;  // masks one launch evaluates (profiles/cluster_exact.txt: the longest launch stays far under 50 ms)
+constexpr int kExactMaxLaunches = 4096;       // launches of one call (an event each)
+constexpr int kExactLdsBytes = 80 * 1024;     // the reduction's 4 keys, 2 x 9600 table words, 2 x 24 words of conflicts and g2
+
+// the support word of informative segment k (numbered through the batch); sup_off closes with n_sup, which the device array does not hold
+__device__ __forceinline__ unsigned exact_sup_word(i64 k, const i64 *sup_off, i64 n_inf, const int *sup_cols, i64 n_sup, int R) {
+    const i64 a = ex_clamp(sup_off[k], 0, n_sup), b = ex_clamp(k + 1 < n_inf ? sup_off[k + 1] : n_sup, a, n_sup);
+    unsigned m = 0u;
+    for (i64 s = a; s < b; ++s) { const int c = sup_cols[s]; if ((unsigned)c < (unsigned)R) m |= 1u << c; }
+    return m;
+}
+
+// A workgroup per taken problem: its transposed table (zeroed before the launch: the support words are stored, the correction words and the
+// conflict words are ORed in, which does not depend on the order the atomics arrive in) and its groups' support words.
+__global__ void __launch_bounds__(256) k_exact_prep(const int *list, const ExactProb *probs, const int *inf_seg, const i64 *sup_off, i64 n_inf, const int *sup_cols,
+                                                    i64 n_sup, const i64 *corr_off, i64 n_cols, const int *corr_seg, i64 n_corr, const int2 *pairs,
+                                                    const i64 *grp_seg_off, const int *grp_seg, i64 n_grp_seg, unsigned *tab, unsigned *conf, unsigned *gsup) {
+    const ExactProb d = probs[list[blockIdx.x]];
+    const int R = d.n, E = d.n_inf, tid = threadIdx.x;
+    const int *inf = inf_seg + d.inf0;
+    for (int k = tid; k < E; k += 256) tab[2 * (d.inf0 + k)] = exact_sup_word(d.inf0 + k, sup_off, n_inf, sup_cols, n_sup, R);
+    for (int c = 0; c < R; ++c) {
+        const i64 a = ex_clamp(corr_off[d.col0 + c], 0, n_corr), b = ex_clamp(d.col0 + c + 1 < n_cols ? corr_off[d.col0 + c + 1] : n_corr, a, n_corr);
+        for (i64 x = a + tid; x < b; x += 256) {
+            const int k = ex_find_seg(inf, E, corr_seg[x]);
+            if (k >= 0) atomicOr(&tab[2 * (d.inf0 + k) + 1], 1u << c);
+        }
+    }
+    for (i64 i = d.pair0 + tid; i < d.pair1; i += 256) {
+        const int2 pr = pairs[i];
+        if ((unsigned)pr.x < (unsigned)R && (unsigned)pr.y < (unsigned)R) {
+            atomicOr(&conf[d.col0 + pr.x], 1u << pr.y);
+            atomicOr(&conf[d.col0 + pr.y], 1u << pr.x);
+        }
+    }
+    if (d.grp1 > d.grp0) {
+        const i64 s0 = ex_clamp(grp_seg_off[d.grp0], 0, n_grp_seg), s1 = ex_clamp(grp_seg_off[d.grp1], s0, n_grp_seg);
+        for (i64 s = s0 + tid; s < s1; s += 256) {
+            const int k = ex_find_seg(inf, E, grp_seg[s]);
+            gsup[s] = k >= 0 ? exact_sup_word(d.inf0 + k, sup_off, n_inf, sup_cols, n_sup, R) : 0u;
+        }
+    }
+}
+
+// A workgroup per item = (problem, first mask, masks): the problem's table, conflict words and g2 are staged in LDS (every lane reads the
+// same word: a broadcast), a lane takes every 256th mask of the slice, and the slice's smallest key reaches the problem's word by one
+// atomic minimum, whose result does not depend on the order the slices arrive in.  No workgroup waits for another; every loop is bounded
+// by the slice and the table sizes.
+__global__ void __launch_bounds__(256) k_exact_search(const int4 *items, const ExactProb *probs, const unsigned *tab, const unsigned *conf, const int *g2,
+                                                      const int *rows, i64 n_rows, const i64 *grp_seg_off, i64 n_grp, i64 n_grp_seg, const unsigned *gsup,
+                                                      const int *grp_len, double lo_f, double hi_f, int offset, u64 *best) {
+    extern __shared__ __attribute__((aligned(16))) unsigned s_exact[];
+    const int4 it = items[blockIdx.x];
+    const ExactProb d = probs[it.x];
+    const int R = d.n, E = d.n_inf, tid = threadIdx.x;
+    u64 *s_key = reinterpret_cast<u64 *>(s_exact);
+    unsigned *s_tab = s_exact + 8, *s_conf = s_tab + 2 * E;
+    int *s_g2 = reinterpret_cast<int *>(s_conf + R);
+    for (int x = tid; x < 2 * E; x += 256) s_tab[x] = tab[2 * d.inf0 + x];
+    if (tid < R) { s_conf[tid] = conf[d.col0 + tid]; s_g2[tid] = g2[d.col0 + tid]; }
+    __syncthreads();
+    const i64 r0 = ex_clamp(d.row0, 0, n_rows), r1 = ex_clamp(d.row1, r0, n_rows);
+    const unsigned lo = (unsigned)it.y, n = (unsigned)it.z;
+    u64 key = kExactKeyNone;
+    for (unsigned i = tid; i < n; i += 256) {
+        const u64 kk = ex_mask_key(lo + i, s_tab, E, s_conf, s_g2, R, r0, r1, rows, d.grp0, n_grp, grp_seg_off, n_grp_seg, gsup, grp_len, lo_f, hi_f, offset,
+                                   d.max_lg);
+        key = kk < key ? kk : key;
+    }
+    key = block_min_key(key, s_key);
+    if (tid == 0 && key != kExactKeyNone) atomicMin(&best[it.x], key);
+}
+
 }  // namespace
 
 // ---- buffers and the context -------------------------------------------------------------------------------------------
@@ -1420,9 +1509,10 @@ struct fclu_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
     // every event, one list to create and destroy; by stage: the graph (ev), fclu_partition (pev), _preprocess (qev), _group_reads (gev), _round_models (rev),
-    // _round_incumbents (iev)
-    hipEvent_t events[3 + 6 + 6 + 5 + 5 + 4] = {};
-    hipEvent_t *const ev = events, *const pev = ev + 3, *const qev = pev + 6, *const gev = qev + 6, *const rev = gev + 5, *const iev = rev + 5;
+    // _round_incumbents (iev), _round_exact's prep (xev; its search launches have an event each in xl_ev, created as a call needs them)
+    hipEvent_t events[3 + 6 + 6 + 5 + 5 + 4 + 2] = {};
+    hipEvent_t *const ev = events, *const pev = ev + 3, *const qev = pev + 6, *const gev = qev + 6, *const rev = gev + 5, *const iev = rev + 5, *const xev = iev + 4;
+    std::vector<hipEvent_t> xl_ev;
     std::string err;
     float compat_ms = 0.f, prune_ms = 0.f;
     int32_t paths[FCLU_N_PATHS] = {};     // the last graph call's launch census (fclu_last_paths)
@@ -1514,11 +1604,24 @@ struct fclu_ctx {
     float iconf_ms = 0.f, istart_ms = 0.f, ipick_ms = 0.f;
     fclu_incumbents incs = {};
     bool have_incs = false;
+    // fclu_round_exact(): the same input; device arrays (xd: the problems, the taken ones' list, the work items, the transposed tables, the
+    // conflict words, the groups' support words, g2, a key per problem) and the pinned copies fclu_round_exact_results() hands out (xh)
+    struct {
+        Buf<ExactProb> probs; Buf<int4> items; Buf<unsigned> tab, conf, gsup; Buf<u64> best;
+        Buf<int> list, g2;
+    } xd;
+    struct {
+        HostBuf<u64> best; HostBuf<int64_t> cost2; HostBuf<uint32_t> mask;
+    } xh;
+    float xprep_ms = 0.f, xsearch_ms = 0.f, xlongest_ms = 0.f;
+    fclu_exact exact = {};
+    bool have_exact = false;
     // (the buffers free themselves behind it, on this device)
     ~fclu_ctx() {
         (void)hipSetDevice(device);
         if (stream) { (void)hipStreamSynchronize(stream); (void)hipStreamDestroy(stream); }
         for (hipEvent_t e : events) if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : xl_ev) if (e) (void)hipEventDestroy(e);
     }
 };
 
@@ -1552,7 +1655,9 @@ int fail(fclu_ctx *c, int code, const char *fmt, ...) {
 //   FCLU_HASH_BITS=n        hash_mask        n < 32: the dedupe's hash cut to n bits forces collisions; 0: one bucket a tint
 //   FCLU_ROUND_LDS=0        round_lds        no problem's rows in LDS (k_round<true, .>): all read them from device memory
 //   FCLU_ROUND_LDS_BYTES=n  round_lds_bytes  0 < n < kRoundLdsBytes: a lower limit of the LDS path, so that small problems take both ways in one batch
-struct Knobs { bool part_lds, prune_lds, rank, prune_edges, round_lds; i64 prune_lds_words, round_lds_bytes; unsigned hash_mask; };
+//   FCLU_EXACT_SLICE=n      exact_slice      0 < n < kExactWgMasks: fclu_round_exact gives a workgroup n masks and a launch 16 n, so that a small problem crosses
+//                                            many slices and several launches
+struct Knobs { bool part_lds, prune_lds, rank, prune_edges, round_lds; i64 prune_lds_words, round_lds_bytes, exact_slice; unsigned hash_mask; };
 
 Knobs read_knobs() {
     const auto off = [](const char *name) { const char *e = getenv(name); return e && e[0] == '0'; };
@@ -1563,6 +1668,8 @@ Knobs read_knobs() {
     k.round_lds = !off("FCLU_ROUND_LDS");
     const char *rb = getenv("FCLU_ROUND_LDS_BYTES");
     k.round_lds_bytes = (rb && atoll(rb) > 0 && atoll(rb) < kRoundLdsBytes) ? atoll(rb) : kRoundLdsBytes;
+    const char *xs = getenv("FCLU_EXACT_SLICE");
+    k.exact_slice = (xs && atoll(xs) > 0 && atoll(xs) < kExactWgMasks) ? atoll(xs) : 0;
     const char *hb = getenv("FCLU_HASH_BITS");
     k.hash_mask = (hb && hb[0] >= '0' && hb[0] <= '9' && atoi(hb) < 32) ? (1u << atoi(hb)) - 1u : 0xffffffffu;
     return k;
@@ -2506,7 +2613,7 @@ void round_launch(fclu_ctx *c, const RoundRun &r) {
 }
 
 int round_device(fclu_ctx *c, const Knobs &k, const fclu_round_batch *b) {
-    c->have_rounds = c->have_incs = false;
+    c->have_rounds = c->have_incs = c->have_exact = false;
     c->rcount_ms = c->rgaps_ms = c->rfill_ms = 0.f;
     if (!c->round_ready || !c->round_src_ok || !c->have_parts)
         return fail(c, FCLU_ERR_ARG, "fclu_round_models: no fclu_round_setup() behind the context's last partition call");
@@ -2755,6 +2862,122 @@ int incumbents_device(fclu_ctx *c, const Knobs &k, const int32_t *g2, double lo_
     return FCLU_OK;
 }
 
+// ---- the exact solve of the last round's small problems (fclu_round_exact) ------------------------------------------------------
+int exact_device(fclu_ctx *c, const Knobs &k, const int32_t *g2, double lo_f, double hi_f, int32_t offset, int32_t max_cols, int64_t max_masks) {
+    c->have_exact = false;
+    c->xprep_ms = c->xsearch_ms = c->xlongest_ms = 0.f;
+    if (!c->have_rounds || !c->round_ready || !c->round_src_ok || !c->have_parts)
+        return fail(c, FCLU_ERR_ARG, "fclu_round_exact: no successful fclu_round_models() stands behind the call (none was made, it failed, or a later "
+                                     "call ended the rounds' source)");
+    const fclu_rounds &o = c->rounds;
+    const int P = o.n_prob;
+    const i64 C = o.n_cols, G = o.n_gap_rows;
+    if (max_cols < 0 || max_cols > kExactMaxCols) return fail(c, FCLU_ERR_ARG, "fclu_round_exact: max_cols is %d, it must lie in [0, %d]", (int)max_cols, kExactMaxCols);
+    if (max_masks < 1) return fail(c, FCLU_ERR_ARG, "fclu_round_exact: max_masks is %lld, it must be at least 1", (i64)max_masks);
+    if (offset < 0 || !(lo_f == lo_f) || !(hi_f == hi_f) || lo_f - lo_f != 0.0 || hi_f - hi_f != 0.0)
+        return fail(c, FCLU_ERR_ARG, "fclu_round_exact: offset is negative or a factor is not finite");
+    if (C > 0 && !g2) return fail(c, FCLU_ERR_ARG, "fclu_round_exact: g2 is null");
+    for (i64 x = 0; x < C; ++x) if (g2[x] < 0) return fail(c, FCLU_ERR_ARG, "fclu_round_exact: g2[%lld] is negative", x);
+    if ((int)c->r_probs.size() != P) return fail(c, FCLU_ERR_ARG, "fclu_round_exact: the round's problems are gone");
+    HIP_TRY(c, hipSetDevice(c->device));
+    auto &D = c->xd;
+    auto &H = c->xh;
+    auto &RD = c->rd;
+    hipStream_t s = c->stream;
+    // ---- which problems are taken: ascending (R, problem) while the running total of 2^R stays inside the budget
+    std::vector<ExactProb> probs((size_t)P);
+    std::vector<std::pair<int, int>> order;
+    for (int p = 0; p < P; ++p) {
+        const RoundProb &rp = c->r_probs[(size_t)p];
+        ExactProb &d = probs[(size_t)p];
+        d.col0 = rp.col0; d.inf0 = o.inf_off[p]; d.pair0 = o.pair_off[p]; d.pair1 = o.pair_off[p + 1];
+        d.grp0 = o.grp_off[p]; d.grp1 = o.grp_off[p + 1]; d.row0 = o.row_off[p]; d.row1 = o.row_off[p + 1];
+        d.max_lg = c->r_max_lg[(size_t)rp.tint];
+        d.n = rp.n; d.n_inf = (int)(o.inf_off[p + 1] - o.inf_off[p]);
+        if (o.refused[p] >= 0 || d.n > max_cols) continue;   // no model, or too many columns: cost2 -2
+        if (d.inf0 < 0 || o.inf_off[p + 1] < d.inf0 || o.inf_off[p + 1] > o.n_inf || d.n_inf > kMaxWords * 32 || d.pair0 < 0 || d.pair1 < d.pair0 ||
+            d.pair1 > o.n_pairs || d.grp0 < 0 || d.grp1 < d.grp0 || d.grp1 > o.n_grp || d.row0 < 0 || d.row1 < d.row0 || d.row1 > G || d.col0 < 0 || d.col0 + d.n > C)
+            return fail(c, FCLU_ERR_HIP, "problem %d: the round's offsets are out of range", p);
+        if (o.n_grp == 0) d.row0 = d.row1 = 0;               // (a row has a group: nothing to index without one)
+        order.emplace_back(d.n, p);
+    }
+    std::sort(order.begin(), order.end());
+    const int wg_masks = k.exact_slice ? (int)k.exact_slice : kExactWgMasks;
+    const i64 launch_masks = k.exact_slice ? 16 * k.exact_slice : kExactLaunchMasks;
+    std::vector<int> list;
+    std::vector<int4> items;
+    std::vector<size_t> launch_first;                        // a launch's first item; closed by the number of items
+    std::vector<size_t> launch_lds;
+    i64 n_masks = 0, in_launch = 0;
+    for (const auto &rp : order) {
+        const ExactProb &d = probs[(size_t)rp.second];
+        const i64 total = 1ll << d.n;
+        if (n_masks + total > max_masks) break;              // (ascending R: nothing behind it fits either)
+        n_masks += total;
+        list.push_back(rp.second);
+        const size_t lds = (size_t)(32 + 4 * (2 * d.n_inf + 2 * d.n) + 15) & ~(size_t)15;
+        for (i64 lo = 0; lo < total; lo += wg_masks) {
+            const i64 n = std::min<i64>(wg_masks, total - lo);
+            if (launch_first.empty() || in_launch + n > launch_masks) { launch_first.push_back(items.size()); launch_lds.push_back(0); in_launch = 0; }
+            items.push_back(make_int4(rp.second, (int)lo, (int)n, 0));
+            launch_lds.back() = std::max(launch_lds.back(), lds);
+            in_launch += n;
+        }
+    }
+    const size_t nL = list.size(), nI = items.size(), n_launch = launch_first.size(), nP = (size_t)P, nC = (size_t)C;
+    launch_first.push_back(nI);
+    if (n_launch > (size_t)kExactMaxLaunches)
+        return fail(c, FCLU_ERR_UNSUPPORTED, "fclu_round_exact: %lld masks need %lld launches, a call issues %d at the most: lower max_masks", n_masks, (i64)n_launch,
+                    kExactMaxLaunches);
+    while (c->xl_ev.size() < n_launch + 1) {
+        hipEvent_t e = nullptr;
+        HIP_TRY(c, hipEventCreate(&e));
+        c->xl_ev.push_back(e);
+    }
+    HIP_TRY(c, D.probs.grow(nP)); HIP_TRY(c, D.list.grow(nL)); HIP_TRY(c, D.items.grow(nI)); HIP_TRY(c, D.tab.grow(2 * (size_t)o.n_inf));
+    HIP_TRY(c, D.conf.grow(nC)); HIP_TRY(c, D.gsup.grow((size_t)o.n_grp_seg)); HIP_TRY(c, D.g2.grow(nC)); HIP_TRY(c, D.best.grow(nP));
+    HIP_TRY(c, H.best.grow(nP)); HIP_TRY(c, H.cost2.grow(nP)); HIP_TRY(c, H.mask.grow(nP));
+    HIP_TRY(c, hipMemcpyAsync(D.probs.p, probs.data(), D.probs.bytes(nP), hipMemcpyHostToDevice, s));
+    if (nL) HIP_TRY(c, hipMemcpyAsync(D.list.p, list.data(), D.list.bytes(nL), hipMemcpyHostToDevice, s));
+    if (nI) HIP_TRY(c, hipMemcpyAsync(D.items.p, items.data(), D.items.bytes(nI), hipMemcpyHostToDevice, s));
+    if (C) HIP_TRY(c, hipMemcpyAsync(D.g2.p, g2, D.g2.bytes(nC), hipMemcpyHostToDevice, s));
+    if (o.n_inf) HIP_TRY(c, hipMemsetAsync(D.tab.p, 0, D.tab.bytes(2 * (size_t)o.n_inf), s));
+    if (C) HIP_TRY(c, hipMemsetAsync(D.conf.p, 0, D.conf.bytes(nC), s));
+    HIP_TRY(c, hipMemsetAsync(D.best.p, 0xff, D.best.bytes(nP), s));            // kExactKeyNone
+    HIP_TRY(c, hipEventRecord(c->xev[0], s));
+    if (nL)
+        hipLaunchKernelGGL(k_exact_prep, dim3((unsigned)nL), dim3(256), 0, s, D.list.p, D.probs.p, RD.inf_seg.p, RD.sup_off.p, (i64)o.n_inf, RD.sup_cols.p, (i64)o.n_sup,
+                           RD.corr_off.p, C, RD.corr_seg.p, (i64)o.n_corr, RD.pairs.p, RD.grp_seg_off.p, RD.grp_seg.p, (i64)o.n_grp_seg, D.tab.p, D.conf.p, D.gsup.p);
+    HIP_TRY(c, hipEventRecord(c->xev[1], s));
+    HIP_TRY(c, hipEventRecord(c->xl_ev[0], s));
+    for (size_t l = 0; l < n_launch; ++l) {
+        hipLaunchKernelGGL(k_exact_search, dim3((unsigned)(launch_first[l + 1] - launch_first[l])), dim3(256), launch_lds[l], s, D.items.p + launch_first[l], D.probs.p,
+                           D.tab.p, D.conf.p, D.g2.p, RD.rows.p, G, RD.grp_seg_off.p, (i64)o.n_grp, (i64)o.n_grp_seg, D.gsup.p, RD.grp_len.p, lo_f, hi_f, (int)offset,
+                           D.best.p);
+        HIP_TRY(c, hipEventRecord(c->xl_ev[l + 1], s));
+    }
+    HIP_TRY(c, hipMemcpyAsync(H.best.p, D.best.p, D.best.bytes(nP), hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    HIP_TRY(c, hipGetLastError());
+    for (int p = 0; p < P; ++p) { H.cost2.p[p] = -2; H.mask.p[p] = 0u; }
+    for (const int p : list) {
+        const u64 key = H.best.p[p];
+        H.cost2.p[p] = key == kExactKeyNone ? -1 : ex_key_cost2(key);
+        H.mask.p[p] = key == kExactKeyNone ? 0u : ex_key_mask(key);
+    }
+    fclu_exact &r = c->exact;
+    r.n_prob = P; r.cost2 = H.cost2.p; r.mask = H.mask.p; r.n_taken = (int64_t)nL; r.n_masks = n_masks; r.n_launches = (int64_t)n_launch;
+    (void)hipEventElapsedTime(&c->xprep_ms, c->xev[0], c->xev[1]);
+    if (n_launch) (void)hipEventElapsedTime(&c->xsearch_ms, c->xl_ev[0], c->xl_ev[n_launch]);
+    for (size_t l = 0; l < n_launch; ++l) {
+        float ms = 0.f;
+        (void)hipEventElapsedTime(&ms, c->xl_ev[l], c->xl_ev[l + 1]);
+        c->xlongest_ms = std::max(c->xlongest_ms, ms);
+    }
+    c->have_exact = true;
+    return FCLU_OK;
+}
+
 }  // namespace
 
 // ---- the C ABI ------------------------------------------------------------------------------------------------------------
@@ -2784,7 +3007,8 @@ int fclu_create(int device, fclu_ctx **out) {
         {reinterpret_cast<const void *>(k_round<true, false>), kRoundLdsBytes},
         {reinterpret_cast<const void *>(k_round<true, true>), kRoundLdsBytes},
         {reinterpret_cast<const void *>(k_inc_start<true>), (int)inc_lds_bytes(0, kMaxWords, (kIncMaxCols + 31) / 32, false) + kRoundLdsBytes},
-        {reinterpret_cast<const void *>(k_inc_start<false>), (int)inc_lds_bytes(0, kMaxWords, (kIncMaxCols + 31) / 32, false)}};
+        {reinterpret_cast<const void *>(k_inc_start<false>), (int)inc_lds_bytes(0, kMaxWords, (kIncMaxCols + 31) / 32, false)},
+        {reinterpret_cast<const void *>(k_exact_search), kExactLdsBytes}};
     for (const auto &d : dyn) if (e == hipSuccess) e = hipFuncSetAttribute(d.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, d.lds);
     if (e != hipSuccess) {
         fail(nullptr, FCLU_ERR_HIP, "context creation failed: %s", hipGetErrorString(e));
@@ -2986,6 +3210,24 @@ int fclu_round_incumbent_timing(fclu_ctx *c, float *conflict_ms, float *starts_m
     if (!c) return FCLU_ERR_ARG;
     if (pick_ms) *pick_ms = c->ipick_ms;
     return two_times(conflict_ms, c->iconf_ms, starts_ms, c->istart_ms);
+}
+
+int fclu_round_exact(fclu_ctx *c, const int32_t *g2, double lo_f, double hi_f, int32_t offset, int32_t max_cols, int64_t max_masks) {
+    return c ? exact_device(c, read_knobs(), g2, lo_f, hi_f, offset, max_cols, max_masks) : FCLU_ERR_ARG;
+}
+
+int fclu_round_exact_results(fclu_ctx *c, fclu_exact *out) {
+    if (!c || !out) return FCLU_ERR_ARG;
+    if (!c->have_exact || !c->have_rounds)
+        return fail(c, FCLU_ERR_ARG, "fclu_round_exact_results: no result (the last fclu_round_exact call failed, none was made, or a later call ended it)");
+    *out = c->exact;
+    return FCLU_OK;
+}
+
+int fclu_round_exact_timing(fclu_ctx *c, float *prep_ms, float *search_ms, float *longest_launch_ms) {
+    if (!c) return FCLU_ERR_ARG;
+    if (longest_launch_ms) *longest_launch_ms = c->xlongest_ms;
+    return two_times(prep_ms, c->xprep_ms, search_ms, c->xsearch_ms);
 }
 
 }  // extern "C"

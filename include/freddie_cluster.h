@@ -16,7 +16,8 @@
  * (include/freddie_host.h, fhost_read_segment: label rows, key token streams, tail categories) and group them into reps
  * (read_segment()'s read_reps, :154-164) on the device.  garbage_cost (from the members' counts) and the gaps dicts are host code.
  * The ILP's solve is not here; what run_ilp() builds its model from is: fclu_round_models() (at the end of this header) gives round r of
- * many partitions as flat arrays, from the rows and pair lists the calls above left on the device.
+ * many partitions as flat arrays, from the rows and pair lists the calls above left on the device.  Problems of at most 24 columns need no
+ * ILP: fclu_round_exact() (the last section) enumerates their column sets and returns the proven optimum.
  *
  * Data layout (caller-owned host arrays, copied by the call):
  *   tint t owns the unique reads row_off[t] .. row_off[t+1]  (N_t of them; "unique" = py/freddie_cluster.py:207-215)
@@ -313,6 +314,41 @@ int fclu_round_incumbent_results(fclu_ctx *c, fclu_incumbents *out);
 
 /* Kernel time of the last fclu_round_incumbents() from HIP events (ms): the conflict matrices; the starts (grow, repair, score); the choice. */
 int fclu_round_incumbent_timing(fclu_ctx *c, float *conflict_ms, float *starts_ms, float *pick_ms);
+
+/* ---- the exact solve of a round's small problems: a proven optimum per problem by enumeration, with no matrix and no solver ----
+ * The model is the one above (a function of the chosen column set S alone); a problem of R columns has 2^R sets, masks 0 .. 2^R - 1 with
+ * bit c = column c.  S is feasible when no incompatible pair lies inside it and every gap row (c, g, l) of the problem holds: with G_g = the
+ * summed lengths of group g's segments whose support meets S and slack = 0 when c is in S, else MAX_ISOFORM_LG, the row is violated when
+ *   lo_f * G_g - offset - slack > l + 1e-9   or   hi_f * G_g + offset + slack < l - 1e-9
+ * in doubles, every operation rounded on its own, in this order, none fused.  The tolerance is the model's (a proven optimum must not
+ * exclude what the rows admit: with epsilon 0.15, offset 20, G = 200 the row l = 250 holds with equality, and 1.15 * 200 + 20 < 250 in
+ * doubles); the incumbents above have none, because an incumbent must be feasible for everybody.  cost2 = the g2 of the columns outside S +
+ * twice the members' corrections on the segments some member covers; the smallest cost2 wins, then the smallest mask.  The definition is
+ * freddie_amd/cluster_solve.py exact_small(), which the device reproduces exactly.
+ * Input as fclu_round_incumbents': the device arrays of the context's last successful fclu_round_models(), g2[n_cols] >= 0 (below 2^31; a
+ * problem's cost2 stays below 2^36), lo_f, hi_f, offset.  A problem is taken when it has a model (is not refused), has at most max_cols
+ * columns and fits the budget: the problems are taken in ascending (columns, problem index) while the running total of 2^R stays
+ * <= max_masks, a choice the host makes.  The call is cut into launches of a bounded number of masks, so that no single launch runs long.
+ * FCLU_ERR_ARG: fclu_round_incumbents' cases; max_cols outside [0, 24]; max_masks < 1.  FCLU_ERR_UNSUPPORTED: a budget that needs more
+ * than 4096 launches.  The context stays usable.  FCLU_EXACT_SLICE=<masks> (read at the call; tests): fewer masks a workgroup and a
+ * launch, so that a 12-column problem crosses many slices and several launches. */
+int fclu_round_exact(fclu_ctx *c, const int32_t *g2, double lo_f, double hi_f, int32_t offset, int32_t max_cols, int64_t max_masks);
+
+typedef struct fclu_exact {
+    int32_t n_prob;
+    const int64_t *cost2;          /* n_prob: twice the optimum's cost; -1 when no column set is feasible; -2 when the problem was not taken or is refused */
+    const uint32_t *mask;          /* n_prob: the optimal column set, bit c = column c; 0 where cost2 < 0 */
+    int64_t n_taken;               /* problems taken */
+    int64_t n_masks;               /* masks evaluated: the sum of 2^R over the taken problems */
+    int64_t n_launches;            /* search launches issued (the one launch that transposes the models is not counted) */
+} fclu_exact;
+
+/* Result of the last successful fclu_round_exact(): pointers into pinned host buffers the context owns, valid until the context's next
+ * call.  The round results and the incumbents' results stay valid behind it. */
+int fclu_round_exact_results(fclu_ctx *c, fclu_exact *out);
+
+/* Kernel time of the last fclu_round_exact() from HIP events (ms): the transposed tables; all search launches; the longest of them. */
+int fclu_round_exact_timing(fclu_ctx *c, float *prep_ms, float *search_ms, float *longest_launch_ms);
 
 #ifdef __cplusplus
 }

@@ -13,6 +13,9 @@ synthetic preprocessed tints through include/freddie_cluster.h.
                        (segment_*.tsv files in: the native reader, the rep grouping and the whole cluster_files_batch, against
                         read_segment + pack_labels + Context.partition_labels on the same files)
     python tools/cluster_bench.py --incumbents [--workload many|big] [--steps K] [--host-sample N] [--solve-budget S] [--max-seeds N] [--out FILE]
+    python tools/cluster_bench.py --exact [--max-ilp K] [--exact-small N] [--exact-masks M] [--steps K] [--host-sample N] [--solve-budget S] [--out FILE]
+                       (per problem size N = 8, 12, 16, 20, 24: Context.round_exact on every partition's first N reps -- the call, the kernels,
+                        the longest launch, masks per second -- against HiGHS on a sample of the same problems; profiles/cluster_exact.txt)
     python tools/cluster_bench.py --rounds [--workload many|big] [--steps K] [--host-sample N] [--solve-budget S] [--out FILE]
                        (the first round of every partition: Context.round_models against the plain-Python build of the same arrays as
                         the reference does it, the kernels' event times, and -- apart -- what HiGHS takes on the same round; the
@@ -495,6 +498,90 @@ def run_incumbents(workload="many", steps=5, host_sample=2, solve_budget=300.0, 
     }
 
 
+EXACT_LAUNCH_MASKS = 1 << 24     # kExactLaunchMasks of freddie_amd/csrc/freddie_cluster.hip: the masks one search launch evaluates at the most
+
+
+def run_exact(workload="many", steps=3, maximum_ilp_size=24, sizes=(8, 12, 16, 20, 24), max_masks=1 << 30, host_sample=24, solve_budget=120.0, threads=16):
+    """The workload staged with a small maximum_ilp_size (thousands of small partitions with incompatible pairs), then per N of `sizes`
+    the round whose problems are every partition's first N reps (a later round's shape: at most N columns, most of them exactly N):
+      models   Context.round_models on these problems (median call time: what a round costs today on the device);
+      exact    Context.round_exact with max_cols = N and the budget max_masks (medians over `steps` after a warm-up): the call, the
+               kernels from fclu_round_exact_timing (prep, all search launches, the longest launch), problems taken, masks, launches,
+               masks per second of the call and of the search kernels;
+      HiGHS    cluster_solve.solve_round on `host_sample` of the taken problems, evenly spread, within solve_budget / len(sizes) seconds:
+               the mean per problem, extrapolated to the taken problems, and whether the costs agree with the exact ones.
+    What was not taken is None."""
+    import tempfile
+    from freddie_amd import cluster, cluster_solve
+    with tempfile.TemporaryDirectory() as d:
+        paths, n_reads = write_segment_files(workload, d)
+        ctx = cluster_prep.Context(0)
+        settings = cluster.ilp_settings(max_ilp=maximum_ilp_size)
+        tints, part0, _ = cluster.stage_files(paths, settings, ctx, threads)
+    costs = [cluster.garbage_costs(t, "constant") for t in tints]
+    med = lambda xs: float(np.median(xs))
+    rows = []
+    for N in sizes:
+        problems = [(t, q, list(rids)[:N]) for t, tint in enumerate(tints) for q, (rids, _) in enumerate(tint["partitions"])]
+        garbage = [costs[t][i] for t, _, rem in problems for i in rem]
+        models_s = []
+        for _ in range(steps + 1):
+            t0 = time.perf_counter()
+            arr = ctx.round_models([part0[t] + q for t, q, _ in problems], [rem for _, _, rem in problems])
+            models_s.append(time.perf_counter() - t0)
+        models_kernel_ms = sum(ctx.round_timing().values())
+        got = ctx.round_exact(garbage, settings["epsilon"], settings["offset"], N, max_masks)      # warm-up
+        call_s, kern = [], []
+        for _ in range(steps):
+            t0 = time.perf_counter()
+            got = ctx.round_exact(garbage, settings["epsilon"], settings["offset"], N, max_masks)
+            call_s.append(time.perf_counter() - t0)
+            kern.append(ctx.round_exact_timing())
+        taken = np.flatnonzero(got["cost2"] != -2)
+        row = {"N": N, "problems": len(problems), "with_a_model": int((arr["refused"] < 0).sum()), "columns": int(arr["n_cols"]), "pairs_kept": int(arr["n_pairs"]),
+               "gap_rows": int(arr["n_gap_rows"]), "informative_segments": int(arr["n_inf"]),
+               "round_models_call_ms": med(models_s[1:]) * 1e3, "round_models_kernel_ms": models_kernel_ms,
+               "taken": got["n_taken"], "masks": got["n_masks"], "launches": got["n_launches"], "infeasible": int((got["cost2"] == -1).sum()),
+               "round_exact_call_ms": med(call_s) * 1e3, "round_exact_call_spread_ms": [min(call_s) * 1e3, max(call_s) * 1e3],
+               "kernel_ms": {k: med([x[k] for x in kern]) for k in kern[0]},
+               "masks_per_s_call": got["n_masks"] / med(call_s),
+               "masks_per_s_search_kernels": got["n_masks"] / max(med([x["search_ms"] for x in kern]) * 1e-3, 1e-9)}
+        sample = taken[np.linspace(0, len(taken) - 1, min(host_sample, len(taken))).astype(int)].tolist() if len(taken) else []
+        spent, solved, agree = 0.0, [], 0
+        for p in sample:
+            if spent >= solve_budget / len(sizes):
+                break
+            t, q, rem = problems[p]
+            model = cluster_prep.round_model(arr, p)
+            model["garbage"] = [costs[t][i] for i in rem]; model["max_lg"] = sum(s[2] for s in tints[t]["segs"])
+            t0 = time.perf_counter()
+            status, x, e = cluster_solve.solve_round(model, settings)
+            dt = time.perf_counter() - t0
+            spent += dt
+            solved.append(dt)
+            exact = cluster_prep.round_exact_solution(got, p)
+            agree += (status != cluster_solve.OPTIMAL and exact == "infeasible") or \
+                (status == cluster_solve.OPTIMAL and exact != "infeasible" and abs(cluster_solve.round_cost(model, x, e) - exact[0]) < 0.25)
+        mean_s = float(np.mean(solved)) if solved else None
+        row["highs"] = {"problems_solved": len(solved), "seconds": spent, "mean_s": mean_s, "slowest_s": max(solved or [0.0]), "costs_agree": int(agree),
+                        "extrapolated_to_taken_s": mean_s * got["n_taken"] if solved else None,
+                        "extrapolated_over_16_workers_s": mean_s * got["n_taken"] / 16 if solved else None}
+        row["exact_call_faster_than_highs_on_the_taken"] = bool(med(call_s) < mean_s * got["n_taken"] / 16) if solved else None
+        print("N = %d: %d taken, %d masks, call %.2f ms, longest launch %.2f ms; HiGHS mean %s s" %
+              (N, got["n_taken"], got["n_masks"], row["round_exact_call_ms"], row["kernel_ms"]["longest_launch_ms"], mean_s), file=sys.stderr, flush=True)
+        rows.append(row)
+    ctx.close()
+    return {
+        "metric": "a round's small problems: Context.round_exact (enumeration on the device) against HiGHS (cluster_solve.solve_round) on a sample of the same problems",
+        "unit": "ms", "data": "synthetic", "source_hash": _build_hash(),
+        "config": {"workload": "cluster-" + workload, **WORKLOADS[workload], "reads": n_reads, "maximum_ilp_size": maximum_ilp_size, "max_masks": max_masks,
+                   "steps": steps, "host_sample": host_sample, "solve_budget_s": solve_budget, "launch_bound_masks": EXACT_LAUNCH_MASKS,
+                   "problems_of_N": "every partition's first N reps"},
+        "longest_launch_ms": max(r["kernel_ms"]["longest_launch_ms"] for r in rows),
+        "sizes": rows,
+    }
+
+
 def _build_hash():
     from freddie_amd import build as _b
     return _b.embedded_hash(cluster_prep.CLUSTER_SO)
@@ -515,8 +602,20 @@ def main():
     ap.add_argument("--incumbents", action="store_true", help="measure Context.round_incumbents on the first round; HiGHS with and without the cutoff on the --rounds sample")
     ap.add_argument("--max-seeds", type=int, default=64, help="--incumbents: seeded starts a problem")
     ap.add_argument("--out", default=None, help="--rounds / --incumbents: where the result is written too (profiles/cluster_rounds.txt, profiles/cluster_incumbents.txt)")
+    ap.add_argument("--exact", action="store_true", help="measure Context.round_exact per problem size against HiGHS on a sample of the same problems")
+    ap.add_argument("--max-ilp", type=int, default=24, help="--exact: maximum_ilp_size the workload is staged with")
+    ap.add_argument("--exact-small", type=int, default=None, help="--exact: one N instead of 8, 12, 16, 20, 24")
+    ap.add_argument("--exact-masks", type=int, default=1 << 30, help="--exact: the mask budget of a call")
     args = ap.parse_args()
-    if args.incumbents:
+    if args.exact:
+        res = run_exact(args.workload, args.steps, args.max_ilp, (args.exact_small,) if args.exact_small is not None else (8, 12, 16, 20, 24), args.exact_masks,
+                        host_sample=24 if args.host_sample == 20 else args.host_sample, solve_budget=args.solve_budget, threads=args.threads)
+        with open(args.out or os.path.join(ROOT, "profiles", "cluster_exact.txt"), "w") as f:
+            f.write("tools/cluster_bench.py --exact --workload %s --steps %d --max-ilp %d --exact-masks %d  (libfreddie_cluster.so source hash %s)\n" %
+                    (args.workload, args.steps, args.max_ilp, args.exact_masks, res["source_hash"]))
+            f.write(json.dumps(res, indent=1) + "\n")
+        print(json.dumps(res))
+    elif args.incumbents:
         res = run_incumbents(args.workload, args.steps, host_sample=2 if args.host_sample == 20 else args.host_sample,
                              solve_budget=args.solve_budget if args.solve_budget != 120.0 else 300.0, threads=args.threads, max_seeds=args.max_seeds)
         with open(args.out or os.path.join(ROOT, "profiles", "cluster_incumbents.txt"), "w") as f:
