@@ -12,7 +12,10 @@ The solve is HiGHS, not Gurobi: where a round's optimum is not unique the tie ma
 settings["incumbent"] = "cutoff" / "fallback" a round is one more device call (Context.round_incumbents: a greedy feasible isoform per
 problem), which bounds the solves and, under "fallback", answers for a solve that ends without a proven optimum.  Under
 settings["exact_cols"] = N > 0 a round is one more device call (Context.round_exact): every problem of at most N columns that fits the
-mask budget is solved there by enumeration, a proven optimum, and only the others go to the solver."""
+mask budget is solved there by enumeration, a proven optimum, and only the others go to the solver.  Under settings["bnb_cols"] = N >
+exact_cols the problems of exact_cols + 1 .. N (<= 64) columns that fit the node budget are searched by a branch and bound on the device
+(Context.round_bnb, behind a round_incumbents call whose costs bound it): a search that finishes is a proven optimum under the
+enumeration's rule and makes no solve job; one that does not hands the solver its best set as an incumbent."""
 import os
 
 from . import cluster_prep, cluster_solve
@@ -25,14 +28,23 @@ EXACT_MASKS = 1 << 29     # the default mask budget of a round's exact call: wha
                           # cluster-many workload (profiles/cluster_exact.txt)
 
 
+BNB_NODES = 1 << 30       # the default node budget of a round's branch and bound: 16 384 problems at BNB_DEPTH and BNB_NODE_CAP (2^6 tasks x 1024
+                          # nodes each), 64 launches -- ten times the 1 672 problems of 25 to 64 columns of the cluster-many workload's first round
+                          # (profiles/cluster_bnb.txt)
+
+
 def ilp_settings(recycle_model="constant", epsilon=0.2, offset=20, timeout=1, max_rounds=30, min_isoform_size=3, max_ilp=1000, incumbent="off",
-                 exact_cols=0, exact_masks=EXACT_MASKS):
+                 exact_cols=0, exact_masks=EXACT_MASKS, bnb_cols=0, bnb_nodes=BNB_NODES):
     """incumbent: "off"; "cutoff": every round's greedy incumbents (Context.round_incumbents, one device call a round) bound the solves'
     objective; "fallback": and stand in for a solve that ends without a proven optimum (status INCUMBENT).
     exact_cols: 0, or the largest number of columns (<= 24) of a problem the GPU solves exactly by enumeration (Context.round_exact, one
-    device call a round) instead of the solver; exact_masks: that call's budget, the sum of 2^columns over the problems it takes."""
+    device call a round) instead of the solver; exact_masks: that call's budget, the sum of 2^columns over the problems it takes.
+    bnb_cols: 0, or the largest number of columns (<= 64) of a problem the GPU searches by branch and bound (Context.round_bnb: the problems
+    of exact_cols + 1 .. bnb_cols columns; one more device call a round, two where the incumbents are not computed anyway); bnb_nodes: that
+    call's budget, the sum of tasks x node cap over the problems it takes."""
     return dict(recycle_model=recycle_model, K=2, epsilon=epsilon, offset=offset, timeout=timeout, max_rounds=max_rounds, threads=1,
-                min_isoform_size=min_isoform_size, max_ilp=max_ilp, incumbent=incumbent, exact_cols=exact_cols, exact_masks=exact_masks)
+                min_isoform_size=min_isoform_size, max_ilp=max_ilp, incumbent=incumbent, exact_cols=exact_cols, exact_masks=exact_masks,
+                bnb_cols=bnb_cols, bnb_nodes=bnb_nodes)
 
 
 def check_exact(settings):
@@ -41,6 +53,14 @@ def check_exact(settings):
         raise ValueError("exact_cols is %r: 0 .. %d" % (cols, cluster_solve.EXACT_MAX_COLS))
     if cols and masks < 1:
         raise ValueError("exact_masks is %r: at least 1" % (masks,))
+
+
+def check_bnb(settings):
+    cols, nodes = settings.get("bnb_cols", 0), settings.get("bnb_nodes", BNB_NODES)
+    if not 0 <= cols <= cluster_solve.BNB_MAX_COLS:
+        raise ValueError("bnb_cols is %r: 0 .. %d" % (cols, cluster_solve.BNB_MAX_COLS))
+    if cols and nodes < 1:
+        raise ValueError("bnb_nodes is %r: at least 1" % (nodes,))
 
 
 def garbage_costs(tint, recycle_model):
@@ -116,6 +136,7 @@ def cluster_tints(tints, part0, ctx, settings, solve=cluster_solve.solve_round, 
     [(status, tint id, partition, round, remaining reps)].  on_round: called with a dict per solved round (tests, profiles)."""
     cluster_solve.check_settings(settings)
     check_exact(settings)
+    check_bnb(settings)
     min_size, max_rounds = settings["min_isoform_size"], settings["max_rounds"]
     state = []                                               # a partition: its tint, number, remaining reps, isoforms; active or not
     for t, tint in enumerate(tints):
@@ -145,6 +166,12 @@ def cluster_tints(tints, part0, ctx, settings, solve=cluster_solve.solve_round, 
         if settings.get("exact_cols", 0) > 0:                # one more device call: the small problems' proven optima, no solve job for them
             exact = ctx.round_exact([g for s in todo for g in (tints[s["t"]]["garbage_cost"][i] for i in s["remaining"])],
                                     settings["epsilon"], settings["offset"], settings["exact_cols"], settings.get("exact_masks", EXACT_MASKS))
+        bnb = None
+        if settings.get("bnb_cols", 0) > settings.get("exact_cols", 0):     # the larger problems' search, bounded by the greedy incumbents' costs
+            garbage = [g for s in todo for g in (tints[s["t"]]["garbage_cost"][i] for i in s["remaining"])]
+            greedy = inc if inc is not None else ctx.round_incumbents(garbage, settings["epsilon"], settings["offset"])
+            bnb = ctx.round_bnb(garbage, greedy["cost2"], settings["epsilon"], settings["offset"], settings.get("exact_cols", 0) + 1, settings["bnb_cols"],
+                                settings.get("bnb_nodes", BNB_NODES))
         jobs, models, answers = [], [], []
         for p, s in enumerate(todo):
             tint = tints[s["t"]]
@@ -160,6 +187,13 @@ def cluster_tints(tints, part0, ctx, settings, solve=cluster_solve.solve_round, 
                 model["incumbent"] = cluster_prep.round_incumbent(inc, p)
             models.append(model)
             found = cluster_prep.round_exact_solution(exact, p) if exact is not None else None
+            if found is None and bnb is not None:
+                found = cluster_prep.round_bnb_solution(bnb, p)
+                if found is not None and found[0] == "unproven":       # the solver's; where the search found a set, with the better of
+                    if found[1] is not None:                           # that and the greedy's as its incumbent
+                        best = cluster_prep.round_incumbent(greedy, p)
+                        model["incumbent"] = tuple(found[1:]) if best is None or found[1] < best[0] else best
+                    found = None
             if found is None:
                 answers.append(len(jobs))                    # the solver's: its place among the jobs
                 jobs.append((solve, model, settings))
@@ -235,6 +269,10 @@ EXACT_HELP = ("Recommended where small problems dominate: 24 -- measured on an M
               "size up to 24 columns; the budget, not N, bounds a call.")
 
 
+BNB_HELP = ("Recommended: 64 -- measured on an MI355X (profiles/cluster_bnb.txt), a call proves 1 652 of the cluster-many workload's 1 672 problems of 25 "
+            "to 64 columns in 0.28 s, where sixteen HiGHS workers take about 21 s.")
+
+
 # ---- the command line (py/freddie_cluster.py :37-110, :783-827) ---------------------------------------------------------------
 def parse_args(argv=None):
     import argparse
@@ -266,6 +304,14 @@ def parse_args(argv=None):
     parser.add_argument("--exact-masks", type=int, default=EXACT_MASKS, metavar="M",
                         help="Budget of a round's exact call: the sum of 2^columns over the problems it takes, smallest first; the rest go to the "
                              "solver.  Default: {}".format(EXACT_MASKS))
+    parser.add_argument("--exact-bnb", type=int, default=0, choices=range(0, cluster_solve.BNB_MAX_COLS + 1), metavar="N",
+                        help="Problems of more columns than --exact-small and at most N (0 .. {}) are searched on the GPU by branch and bound, "
+                             "bounded by the greedy incumbents: a search that finishes is a proven optimum and no solver call; one that does "
+                             "not hands the solver its best set as an incumbent.  Default: 0 (nothing changes, no extra call).  {}".format(
+                                 cluster_solve.BNB_MAX_COLS, BNB_HELP))
+    parser.add_argument("--bnb-nodes", type=int, default=BNB_NODES, metavar="M",
+                        help="Budget of a round's branch and bound: the sum of tasks x node cap over the problems it takes, smallest first; the "
+                             "rest go to the solver.  Default: {}".format(BNB_NODES))
     parser.add_argument("-t", "--threads", type=int, default=1, help="Number of processes that solve (at most {})".format(MAX_WORKERS))
     parser.add_argument("-l", "--logs-dir", type=str, default=None, help="Directory path where logs will be outputted. Default: No log")
     parser.add_argument("-o", "--outdir", type=str, default="freddie_cluster/", help="Path to output directory. Default: freddie_cluster/")
@@ -279,6 +325,8 @@ def parse_args(argv=None):
     assert args.max_rounds >= 0
     if args.exact_masks < 1:
         parser.error("--exact-masks must be at least 1")
+    if args.bnb_nodes < 1:
+        parser.error("--bnb-nodes must be at least 1")
     return args
 
 
@@ -288,7 +336,7 @@ def main(argv=None, make_context=None):
     args = parse_args(argv)
     args.segment_dir = args.segment_dir.rstrip("/")
     settings = ilp_settings(args.recycle_model, args.epsilon, args.gap_offset, args.timeout, args.max_rounds, args.min_isoform_size, args.max_ilp,
-                            args.incumbent, args.exact_small, args.exact_masks)
+                            args.incumbent, args.exact_small, args.exact_masks, args.exact_bnb, args.bnb_nodes)
     cluster_solve.check_settings(settings)
     jobs = []
     for contig in os.listdir(args.segment_dir):

@@ -29,6 +29,7 @@ from math import ceil
 import numpy as np
 
 from . import build as _build
+from . import cluster_solve
 
 # ---------------------------------------------------------------------------------------------------------------
 # segment_*.tsv -> tint dict   (read_segment :119-172)
@@ -155,7 +156,7 @@ def split_list_evenly(l, m):
 # ---------------------------------------------------------------------------------------------------------------
 CLUSTER_SO = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libfreddie_cluster.so")
 CLUSTER_SRC = [os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "freddie_cluster.hip")]
-CLUSTER_HEADERS = [os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", n) for n in ("clu_incumbent.h", "clu_exact.h")]
+CLUSTER_HEADERS = [os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", n) for n in ("clu_incumbent.h", "clu_exact.h", "clu_bnb.h")]
 EXPORTS = ["fclu_abi_version", "fclu_create", "fclu_destroy", "fclu_last_error", "fclu_compat_graph", "fclu_last_timing",
            "fclu_last_paths",
            "fclu_partition", "fclu_partition_adj", "fclu_partition_results", "fclu_partition_timing",
@@ -163,7 +164,8 @@ EXPORTS = ["fclu_abi_version", "fclu_create", "fclu_destroy", "fclu_last_error",
            "fclu_group_reads", "fclu_partition_segment", "fclu_group_results", "fclu_group_timing",
            "fclu_round_setup", "fclu_round_models", "fclu_round_results", "fclu_round_timing",
            "fclu_round_incumbents", "fclu_round_incumbent_results", "fclu_round_incumbent_timing",
-           "fclu_round_exact", "fclu_round_exact_results", "fclu_round_exact_timing"]
+           "fclu_round_exact", "fclu_round_exact_results", "fclu_round_exact_timing",
+           "fclu_round_bnb", "fclu_round_bnb_results", "fclu_round_bnb_timing"]
 ERR_UNSUPPORTED = 3
 _lib = None
 
@@ -235,6 +237,14 @@ class _Incumbents(ctypes.Structure):
 class _Exact(ctypes.Structure):
     _fields_ = [("n_prob", ctypes.c_int32), ("cost2", ctypes.c_void_p), ("mask", ctypes.c_void_p), ("n_taken", ctypes.c_int64),
                 ("n_masks", ctypes.c_int64), ("n_launches", ctypes.c_int64)]
+
+
+class _Bnb(ctypes.Structure):
+    _fields_ = [("n_prob", ctypes.c_int32)] + [(n, ctypes.c_void_p) for n in ("status", "cost2", "mask", "nodes", "capped")] + [
+        (n, ctypes.c_int64) for n in ("n_taken", "n_launches", "nodes_total")]
+
+
+BNB_STATUS = {0: "optimal", 1: "infeasible", 2: "unproven", -2: None}     # FCLU_BNB_*
 
 
 def build(force=False, verbose=False):
@@ -309,6 +319,12 @@ def load():
     L.fclu_round_exact_results.argtypes = [vp, ctypes.POINTER(_Exact)]
     L.fclu_round_exact_timing.restype = ctypes.c_int
     L.fclu_round_exact_timing.argtypes = [vp] + [ctypes.POINTER(ctypes.c_float)] * 3
+    L.fclu_round_bnb.restype = ctypes.c_int
+    L.fclu_round_bnb.argtypes = [vp, vp, vp, ctypes.c_double, ctypes.c_double] + [ctypes.c_int32] * 5 + [ctypes.c_int64]
+    L.fclu_round_bnb_results.restype = ctypes.c_int
+    L.fclu_round_bnb_results.argtypes = [vp, ctypes.POINTER(_Bnb)]
+    L.fclu_round_bnb_timing.restype = ctypes.c_int
+    L.fclu_round_bnb_timing.argtypes = [vp] + [ctypes.POINTER(ctypes.c_float)] * 3
     _lib = L
     return L
 
@@ -601,6 +617,35 @@ class Context:
         self._L.fclu_round_exact_timing(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(f))
         return dict(prep_ms=a.value, search_ms=b.value, longest_launch_ms=f.value)
 
+    def round_bnb(self, garbage, ub2, epsilon, offset, min_cols, max_cols, max_nodes, depth=cluster_solve.BNB_DEPTH, node_cap=cluster_solve.BNB_NODE_CAP):
+        """A branch and bound over every problem of min_cols .. max_cols (<= 64) columns of the last round_models() call, one device call
+        (include/freddie_cluster.h, fclu_bnb; the definition is cluster_solve.exact_bnb()): garbage as round_incumbents'; ub2 = per problem
+        twice the cost of a known feasible set, or a negative number (e.g. round_incumbents()' cost2); a problem is taken in ascending
+        (columns, problem) while 2^min(columns, depth) * node_cap fits what is left of max_nodes.  Returns numpy arrays status (0 optimal,
+        1 infeasible, 2 unproven, -2 not taken or refused), cost2 (-1: no set found), mask (uint64, bit c = column c), nodes and capped per
+        problem, col_off, and n_taken, n_launches, nodes_total; round_bnb_solution() cuts one problem out."""
+        g2, col_off = self._garbage2("round_bnb", garbage)
+        ub = np.ascontiguousarray(np.asarray(ub2, np.int64).reshape(-1))
+        if ub.size != col_off.size - 1:
+            raise ClusterError("round_bnb: %d bounds for the %d problems of the last round_models() call" % (ub.size, col_off.size - 1))
+        rc = self._L.fclu_round_bnb(self._h, g2.ctypes.data if g2.size else None, ub.ctypes.data if ub.size else None, 1.0 - float(epsilon),
+                                    1.0 + float(epsilon), int(offset), int(min_cols), int(max_cols), int(depth), int(node_cap), int(max_nodes))
+        if rc != 0:
+            raise ClusterError("fclu_round_bnb: " + self._L.fclu_last_error(self._h).decode(), rc)
+        b = _Bnb()
+        rc = self._L.fclu_round_bnb_results(self._h, ctypes.byref(b))
+        if rc != 0:
+            raise ClusterError("fclu_round_bnb_results: " + self._L.fclu_last_error(self._h).decode(), rc)
+        P = b.n_prob
+        return dict(n_prob=P, col_off=col_off, status=_copy_out(b.status, P, np.int32), cost2=_copy_out(b.cost2, P, np.int64),
+                    mask=_copy_out(b.mask, P, np.uint64), nodes=_copy_out(b.nodes, P, np.int64), capped=_copy_out(b.capped, P, np.int32),
+                    n_taken=int(b.n_taken), n_launches=int(b.n_launches), nodes_total=int(b.nodes_total))
+
+    def round_bnb_timing(self):
+        a, b, f = ctypes.c_float(), ctypes.c_float(), ctypes.c_float()
+        self._L.fclu_round_bnb_timing(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(f))
+        return dict(prep_ms=a.value, search_ms=b.value, longest_launch_ms=f.value)
+
     def round_timing(self):
         a, b, f = ctypes.c_float(), ctypes.c_float(), ctypes.c_float()
         self._L.fclu_round_timing(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(f))
@@ -707,6 +752,18 @@ def round_exact_solution(arr, p):
         return None
     mask = int(arr["mask"][p])
     return cost2 / 2.0, [mask >> c & 1 for c in range(int(arr["col_off"][p + 1] - arr["col_off"][p]))]
+
+
+def round_bnb_solution(arr, p):
+    """Problem p of Context.round_bnb(): (cost, x) -- a proven optimum's cost and a 0 / 1 per column --, "infeasible" when no subset of
+    the columns is feasible, ("unproven", cost, x) -- the best set the search found before a task ran into its node cap --,
+    ("unproven", None, None) when it found none, or None when the problem was not taken."""
+    status = BNB_STATUS[int(arr["status"][p])]
+    if status is None or status == "infeasible":
+        return status
+    cost2, mask = int(arr["cost2"][p]), int(arr["mask"][p])
+    found = (cost2 / 2.0, [mask >> c & 1 for c in range(int(arr["col_off"][p + 1] - arr["col_off"][p]))]) if cost2 >= 0 else (None, None)
+    return found if status == "optimal" else ("unproven",) + found
 
 
 # ---------------------------------------------------------------------------------------------------------------

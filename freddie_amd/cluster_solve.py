@@ -282,6 +282,189 @@ def exact_small(model, settings, chunk=1 << 16):
                 e=[int(any(x[c] for c in support)) for support in model["support"]])
 
 
+BNB_MAX_COLS = 64
+BNB_DEPTH = 6             # columns fixed by the task number: 64 tasks a problem.  On the cluster-many workload nearly every prefix is dropped at once
+                          # (a problem of 60 columns counts a few hundred nodes), so 12 columns only add 4 096 one-node tasks a problem
+BNB_NODE_CAP = 1024       # nodes a task may count: what keeps the longest launch under 50 ms at 64 columns while 98 % of the problems are still
+                          # proved (profiles/cluster_bnb.txt; 4 096 proves them all but a launch takes longer than 50 ms)
+_BNB_NONE = 1 << 62       # "no bound": no cost2 reaches it
+
+
+def _popc(x):
+    return bin(x).count("1")
+
+
+def bnb_tables(model, settings):
+    """The transposed tables of exact_small() as Python ints of up to 64 bits (bit c = column c): sup[k] and corr[k] per informative
+    segment, conf[c] and g2[c] per column; the gap rows (column, group, l) and per group its segments as (support mask, length)."""
+    R = model["n_cols"]
+    if R > BNB_MAX_COLS:
+        raise ValueError("%d columns: exact_bnb takes %d at the most" % (R, BNB_MAX_COLS))
+    g2 = garbage2(model["garbage"])
+    if len(g2) != R:
+        raise ValueError("%d garbage costs for %d columns" % (len(g2), R))
+    sup, corr, conf = [], [0] * len(model["inf_seg"]), [0] * R
+    for support in model["support"]:
+        sup.append(sum(1 << c for c in support))
+    place = {j: k for k, j in enumerate(model["inf_seg"])}
+    for c, segs in enumerate(model["corrections"]):
+        for j in segs:
+            if j in place:
+                corr[place[j]] |= 1 << c
+    for a, b in model["pairs"]:
+        conf[a] |= 1 << b
+        conf[b] |= 1 << a
+    ccol = [sum(1 << k for k in range(len(sup)) if corr[k] >> c & 1) for c in range(R)]       # the same tables by column: bit k = segment k
+    icol = [sum(1 << k for k in range(len(sup)) if sup[k] >> c & 1) for c in range(R)]
+    gsegs = [[(sup[place[j]] if j in place else 0, ln) for j, ln in segs] for segs in model["group_segs"]]
+    return dict(R=R, g2=g2, sup=sup, corr=corr, conf=conf, ccol=ccol, icol=icol, rows=list(model["gap_rows"]), gsegs=gsegs,
+                lo_f=1.0 - settings["epsilon"], hi_f=1.0 + settings["epsilon"], offset=float(settings["offset"]), max_lg=float(int(model["max_lg"])))
+
+
+def _bnb_pruned(tb, S, d, best2, weak):
+    """A node (columns 0 .. d - 1 fixed, S of them in) is dropped: its lower bound exceeds best2, or a member's row is violated from below."""
+    g2, ccol = tb["g2"], tb["ccol"]
+    e_in = blocked = 0
+    for c in _bits(S):
+        e_in |= tb["icol"][c]
+        blocked |= tb["conf"][c]
+    lb = 0
+    for c in range(d):
+        lb += 2 * _popc(ccol[c] & e_in) if S >> c & 1 else g2[c]
+    if not weak:
+        for c in range(d, tb["R"]):
+            lb += g2[c] if blocked >> c & 1 else min(g2[c], 2 * _popc(ccol[c] & e_in))
+    if lb > best2:
+        return True
+    for c, g, l in tb["rows"]:
+        if S >> c & 1:
+            G = sum(ln for m, ln in tb["gsegs"][g] if m & S)
+            a = tb["lo_f"] * G
+            a = a - tb["offset"]
+            if a > float(l) + 1e-9:
+                return True
+    return False
+
+
+def _bnb_leaf(tb, S):
+    """cost2 of the full column set S, or None when it is not feasible: exact_small()'s test and cost."""
+    for c in _bits(S):
+        if tb["conf"][c] & S:
+            return None
+    for c, g, l in tb["rows"]:
+        G = float(sum(ln for m, ln in tb["gsegs"][g] if m & S))
+        slack = 0.0 if S >> c & 1 else tb["max_lg"]
+        a = tb["lo_f"] * G
+        a = a - tb["offset"]
+        a = a - slack
+        b = tb["hi_f"] * G
+        b = b + tb["offset"]
+        b = b + slack
+        if a > float(l) + 1e-9 or b < float(l) - 1e-9:
+            return None
+    cost2 = sum(tb["g2"][c] for c in range(tb["R"]) if not S >> c & 1)
+    for s_mask, c_mask in zip(tb["sup"], tb["corr"]):
+        if s_mask & S:
+            cost2 += 2 * _popc(c_mask & S)
+    return cost2
+
+
+def bnb_task(tb, t, D, ub2=None, node_cap=BNB_NODE_CAP, weak=False):
+    """Task t of a problem's 2^D (exact_bnb()'s docstring): (cost2, mask, nodes, capped); cost2 -1 and mask 0 when it found no leaf."""
+    R, conf = tb["R"], tb["conf"]
+    best2, mask, have, nodes = (_BNB_NONE if ub2 is None else ub2), 0, False, 1
+    S = t
+
+    def leaf(S):
+        nonlocal best2, mask, have
+        cost2 = _bnb_leaf(tb, S)
+        if cost2 is not None and (cost2 < best2 or (cost2 == best2 and (not have or S < mask))):
+            best2, mask, have = cost2, S, True
+
+    dead = any(conf[c] & S for c in _bits(S))
+    if not dead and D == R:
+        leaf(S)
+    capped = False
+    if not dead and D < R and not _bnb_pruned(tb, S, D, best2, weak):
+        d, tried_in, tried_out = D, 0, 0                     # the stack: frame d is S's low d bits and two bits of progress
+        while True:
+            bit = 1 << d
+            Sd = S & (bit - 1)
+            if tried_out & bit:                              # both children done: pop
+                if d == D:
+                    break
+                d -= 1
+                continue
+            if not tried_in & bit:
+                tried_in |= bit
+                if conf[d] & Sd:
+                    continue
+                child = Sd | bit
+            else:
+                tried_out |= bit
+                child = Sd
+            if nodes >= node_cap:
+                capped = True
+                break
+            nodes += 1
+            if d + 1 == R:
+                leaf(child)
+            elif not _bnb_pruned(tb, child, d + 1, best2, weak):
+                S, d = child, d + 1
+                tried_in &= ~(1 << d)
+                tried_out &= ~(1 << d)
+    return (best2 if have else -1), (mask if have else 0), nodes, capped
+
+
+def exact_bnb(model, settings, ub2=None, depth=BNB_DEPTH, node_cap=BNB_NODE_CAP, weak=False):
+    """A depth-first branch and bound over the column sets of one round_model() dict (with ``garbage`` and ``max_lg``) of at most 64
+    columns -- the definition the GPU's fclu_round_bnb reproduces exactly, node counts included: dict(status, cost2, cost, mask, members,
+    x, e, nodes, capped).  Where it ends "optimal" the (cost2, mask) is exact_small()'s: the smallest cost2, then the smallest mask.
+
+    Tables: bnb_tables(), those of exact_small() as 64-bit masks (bit c = column c): sup[k], corr[k] per informative segment, conf[c], g2[c].
+    Node: columns 0 .. d - 1 are fixed and S is the set of those fixed in.  With e_in = the segments whose support meets S and blocked = the
+        OR of conf[c] over S,
+            LB2 = the g2 of the columns fixed out + 2 * the sum over S of |C_c & e_in|
+                  + over the columns c >= d: g2_c when c is blocked, else min(g2_c, 2 * |C_c & e_in|).
+        (e only grows, so a member's corrections only grow; a blocked column ends outside S; a free one ends outside, g2_c, or inside with
+        at least its corrections on e_in.)  ``weak`` leaves the last line out (profiles only; the device has the full bound).
+    Pruned: LB2 > best2 (strict: every set of optimal cost is still reached, so the tie rule holds; best2 starts at ub2 when one is given
+        and falls with the task's own leaves), or a row (c, g, l) of a member c of S is violated from below already -- with G = the summed
+        lengths of group g's segments whose support meets S, lo_f * G - offset > l + 1e-9 in doubles, one rounded multiply, one rounded
+        subtraction and one rounded addition, none fused (G only grows).
+    Leaf: a node at depth R; exact_small()'s whole test (pairs, every row, the slack of the columns outside, the tolerance) and its cost2.
+        A leaf replaces the task's best when its cost2 is smaller, or equal and the task has none yet or a larger mask.
+    Tasks: D = min(R, depth); task t of 2^D fixes columns 0 .. D - 1, bit c of t = column c is in.  A task with a pair inside its prefix
+        counts one node and is dead.  Otherwise the prefix counts one node: at D = R it is a leaf; else it is tested by the pruning rules
+        and searched depth first over the columns D .. R - 1 with an explicit stack of at most R - D frames.  At column d the include child
+        comes first, when conf[d] & S == 0 (else there is none and nothing is counted), then the exclude child.  Before a child is
+        evaluated the task's count is compared with node_cap: where it has reached it the task stops and is capped (its best leaf so far
+        still counts); else the child counts one node.  Tasks share nothing, so a task depends on (model, ub2, t, node_cap) alone.
+    Result: "optimal" -- no task capped and a leaf exists (at cost2 <= ub2 when one is given): the lexicographic minimum of (cost2, mask)
+        over the tasks; "infeasible" -- no task capped, no leaf, no ub2; "unproven" -- a task was capped (cost2 and mask the best found,
+        or None), or a ub2 was given and no leaf is at or under it.  nodes = the tasks' counts summed, capped = the capped tasks."""
+    tb = bnb_tables(model, settings)
+    R = tb["R"]
+    if depth < 0 or node_cap < 1:
+        raise ValueError("depth %r, node_cap %r: at least 0 and 1" % (depth, node_cap))
+    D = min(R, depth)
+    best, nodes, capped = None, 0, 0
+    for t in range(1 << D):
+        cost2, mask, n, cap = bnb_task(tb, t, D, ub2, node_cap, weak)
+        nodes += n
+        capped += cap
+        if cost2 >= 0 and (best is None or (cost2, mask) < best):
+            best = (cost2, mask)
+    status = "unproven" if capped or (best is None and ub2 is not None) else "optimal" if best is not None else "infeasible"
+    out = dict(status=status, cost2=None, cost=None, mask=None, members=None, x=None, e=None, nodes=nodes, capped=capped)
+    if best is not None:
+        cost2, mask = best
+        x = [mask >> c & 1 for c in range(R)]
+        out.update(cost2=cost2, cost=cost2 / 2.0, mask=mask, members=list(_bits(mask)), x=x,
+                   e=[int(any(x[c] for c in support)) for support in model["support"]])
+    return out
+
+
 def solve_round(model, settings):
     """(status, x, e): status OPTIMAL only for a proven optimum within timeout minutes (anything else is NO_SOLUTION, as :591-592),
     x a 0 / 1 per column, e a 0 / 1 per informative segment (beside model['inf_seg']).  The relative gap is 0: costs are multiples of

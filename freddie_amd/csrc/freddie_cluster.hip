@@ -24,6 +24,7 @@
 
 #include "clu_incumbent.h"   // (behind the runtime: its functions are __host__ __device__)
 #include "clu_exact.h"
+#include "clu_bnb.h"
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 
@@ -1471,6 +1472,120 @@ __global__ void __launch_bounds__(256) k_exact_search(const int4 *items, const E
     if (tid == 0 && key != kExactKeyNone) atomicMin(&best[it.x], key);
 }
 
+// ================================================================================================================
+// The branch and bound over a round's problems of up to 64 columns (fclu_round_bnb): a problem's first D = min(R, depth) columns are
+// fixed by a task number, a lane runs one task depth first with the bound, the row test and the leaf test of clu_bnb.h, and the
+// smallest (cost2, mask) over a problem's tasks is its proven optimum when no task ran into node_cap.  The definition is
+// cluster_solve.exact_bnb()'s docstring.  The tables are k_exact_prep's with 64-bit words; the problems' descriptor is ExactProb.
+// ================================================================================================================
+constexpr int kBnbWgTasks = 256;               // tasks one workgroup runs: one a lane
+constexpr i64 kBnbLaunchNodes = 1ll << 24;     // task-nodes of budget (tasks x node_cap) one launch holds (profiles/cluster_bnb.txt)
+constexpr int kBnbMaxLaunches = 4096;          // launches of one call (an event each)
+constexpr int kBnbMaxDepth = 20;               // 2^20 tasks a problem at the most
+constexpr int kBnbLdsBytes = 160 * 1024;       // a workgroup's LDS on this part: 16 bytes an informative segment, 12 a column
+constexpr int kBnbMaxInf = (kBnbLdsBytes - 12 * kBnbMaxCols) / 16;      // 10 192 informative segments (a row holds 32 kMaxWords = 9 600: every model fits)
+static_assert(kBnbMaxInf < (1 << kBnbPlanes), "bnb_lb2 counts a column's corrections in kBnbPlanes bits");
+
+__device__ __forceinline__ u64 bnb_sup_word(i64 k, const i64 *sup_off, i64 n_inf, const int *sup_cols, i64 n_sup, int R) {
+    const i64 a = ex_clamp(sup_off[k], 0, n_sup), b = ex_clamp(k + 1 < n_inf ? sup_off[k + 1] : n_sup, a, n_sup);
+    u64 m = 0ull;
+    for (i64 s = a; s < b; ++s) { const int c = sup_cols[s]; if ((unsigned)c < (unsigned)R) m |= 1ull << c; }
+    return m;
+}
+
+// k_exact_prep with 64-bit words: a workgroup per taken problem; tab and conf are zeroed before the launch and ORed into.
+__global__ void __launch_bounds__(256) k_bnb_prep(const int *list, const ExactProb *probs, const int *inf_seg, const i64 *sup_off, i64 n_inf, const int *sup_cols,
+                                                  i64 n_sup, const i64 *corr_off, i64 n_cols, const int *corr_seg, i64 n_corr, const int2 *pairs,
+                                                  const i64 *grp_seg_off, const int *grp_seg, i64 n_grp_seg, u64 *tab, u64 *conf, u64 *gsup) {
+    const ExactProb d = probs[list[blockIdx.x]];
+    const int R = d.n, E = d.n_inf, tid = threadIdx.x;
+    const int *inf = inf_seg + d.inf0;
+    for (int k = tid; k < E; k += 256) tab[2 * (d.inf0 + k)] = bnb_sup_word(d.inf0 + k, sup_off, n_inf, sup_cols, n_sup, R);
+    for (int c = 0; c < R; ++c) {
+        const i64 a = ex_clamp(corr_off[d.col0 + c], 0, n_corr), b = ex_clamp(d.col0 + c + 1 < n_cols ? corr_off[d.col0 + c + 1] : n_corr, a, n_corr);
+        for (i64 x = a + tid; x < b; x += 256) {
+            const int k = ex_find_seg(inf, E, corr_seg[x]);
+            if (k >= 0) atomicOr(&tab[2 * (d.inf0 + k) + 1], 1ull << c);
+        }
+    }
+    for (i64 i = d.pair0 + tid; i < d.pair1; i += 256) {
+        const int2 pr = pairs[i];
+        if ((unsigned)pr.x < (unsigned)R && (unsigned)pr.y < (unsigned)R) {
+            atomicOr(&conf[d.col0 + pr.x], 1ull << pr.y);
+            atomicOr(&conf[d.col0 + pr.y], 1ull << pr.x);
+        }
+    }
+    if (d.grp1 > d.grp0) {
+        const i64 s0 = ex_clamp(grp_seg_off[d.grp0], 0, n_grp_seg), s1 = ex_clamp(grp_seg_off[d.grp1], s0, n_grp_seg);
+        for (i64 s = s0 + tid; s < s1; s += 256) {
+            const int k = ex_find_seg(inf, E, grp_seg[s]);
+            gsup[s] = k >= 0 ? bnb_sup_word(d.inf0 + k, sup_off, n_inf, sup_cols, n_sup, R) : 0ull;
+        }
+    }
+}
+
+struct BnbTask { i64 cost2; u64 mask; int nodes, capped; };      // a task's result (BnbResult of clu_bnb.h)
+
+// A workgroup per item = (problem, first task, tasks <= 256, -): the problem's table, conflict words and g2 are staged in LDS, lane i runs
+// task first + i and writes its result to the problem's place task_off[problem] + task of the per-task array.  Tasks share nothing and no
+// workgroup waits for another; every loop is bounded by R, the table sizes or node_cap.
+__global__ void __launch_bounds__(256) k_bnb_search(const int4 *items, const ExactProb *probs, const u64 *tab, const u64 *conf, const int *g2, const i64 *ub2,
+                                                    const int *rows, i64 n_rows, const i64 *grp_seg_off, i64 n_grp, i64 n_grp_seg, const u64 *gsup,
+                                                    const int *grp_len, double lo_f, double hi_f, int offset, int depth, int node_cap, const i64 *task_off,
+                                                    BnbTask *tasks) {
+    extern __shared__ __attribute__((aligned(16))) u64 s_bnb[];
+    const int4 it = items[blockIdx.x];
+    const ExactProb d = probs[it.x];
+    const int R = d.n, E = d.n_inf, tid = threadIdx.x;
+    u64 *s_tab = s_bnb, *s_conf = s_tab + 2 * E;
+    int *s_g2 = reinterpret_cast<int *>(s_conf + R);
+    for (int x = tid; x < 2 * E; x += 256) s_tab[x] = tab[2 * d.inf0 + x];
+    if (tid < R) { s_conf[tid] = conf[d.col0 + tid]; s_g2[tid] = g2[d.col0 + tid]; }
+    __syncthreads();
+    if (tid >= it.z) return;
+    BnbView v;
+    v.tab = s_tab; v.conf = s_conf; v.g2 = s_g2; v.E = E; v.R = R;
+    v.r0 = ex_clamp(d.row0, 0, n_rows); v.r1 = ex_clamp(d.row1, v.r0, n_rows); v.rows = rows;
+    v.grp0 = d.grp0; v.n_grp = n_grp; v.grp_seg_off = grp_seg_off; v.n_grp_seg = n_grp_seg; v.gsup = gsup; v.grp_len = grp_len;
+    v.lo_f = lo_f; v.hi_f = hi_f; v.offset = offset; v.max_lg = d.max_lg;
+    const int D = R < depth ? R : depth;
+    const u64 t = (u64)(unsigned)it.y + (u64)tid;
+    if (t >> D) return;                                      // (no such task: the host cuts the items inside 2^D)
+    const BnbResult r = bnb_task(v, t, D, ub2[it.x], node_cap);
+    BnbTask out;
+    out.cost2 = r.cost2; out.mask = r.mask; out.nodes = r.nodes; out.capped = r.capped;
+    tasks[task_off[it.x] + (i64)t] = out;
+}
+
+struct BnbOut { i64 cost2; u64 mask; i64 nodes; i64 capped; };   // a problem's result: cost2 -1 and mask 0 when no task found a leaf
+
+// A workgroup per taken problem: the smallest (cost2, mask) of its n_tasks tasks, their nodes summed, the capped ones counted.  A lane
+// folds every 256th task and a tree in LDS folds the 256 partial results; a minimum and two sums, so nothing depends on an order.
+__global__ void __launch_bounds__(256) k_bnb_reduce(const int *list, const i64 *task_off, const i64 *n_tasks, const BnbTask *tasks, BnbOut *out) {
+    __shared__ BnbOut s_part[256];
+    const int p = list[blockIdx.x], tid = threadIdx.x;
+    const i64 t0 = task_off[p], n = n_tasks[p];
+    BnbOut acc = {-1, 0ull, 0, 0};
+    for (i64 t = tid; t < n; t += 256) {
+        const BnbTask r = tasks[t0 + t];
+        if (bnb_better(r.cost2, r.mask, acc.cost2, acc.mask)) { acc.cost2 = r.cost2; acc.mask = r.mask; }
+        acc.nodes += r.nodes; acc.capped += r.capped ? 1 : 0;
+    }
+    s_part[tid] = acc;
+    __syncthreads();
+    for (int step = 128; step > 0; step >>= 1) {
+        if (tid < step) {
+            BnbOut a = s_part[tid];
+            const BnbOut b = s_part[tid + step];
+            if (bnb_better(b.cost2, b.mask, a.cost2, a.mask)) { a.cost2 = b.cost2; a.mask = b.mask; }
+            a.nodes += b.nodes; a.capped += b.capped;
+            s_part[tid] = a;
+        }
+        __syncthreads();
+    }
+    if (tid == 0) out[p] = s_part[0];
+}
+
 }  // namespace
 
 // ---- buffers and the context -------------------------------------------------------------------------------------------
@@ -1509,10 +1624,10 @@ struct fclu_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
     // every event, one list to create and destroy; by stage: the graph (ev), fclu_partition (pev), _preprocess (qev), _group_reads (gev), _round_models (rev),
-    // _round_incumbents (iev), _round_exact's prep (xev; its search launches have an event each in xl_ev, created as a call needs them)
-    hipEvent_t events[3 + 6 + 6 + 5 + 5 + 4 + 2] = {};
-    hipEvent_t *const ev = events, *const pev = ev + 3, *const qev = pev + 6, *const gev = qev + 6, *const rev = gev + 5, *const iev = rev + 5, *const xev = iev + 4;
-    std::vector<hipEvent_t> xl_ev;
+    // _round_incumbents (iev), _round_exact's prep (xev; its search launches have an event each in xl_ev, created as a call needs them), _round_bnb's prep and reduction (bev; bl_ev likewise)
+    hipEvent_t events[3 + 6 + 6 + 5 + 5 + 4 + 2 + 3] = {};
+    hipEvent_t *const ev = events, *const pev = ev + 3, *const qev = pev + 6, *const gev = qev + 6, *const rev = gev + 5, *const iev = rev + 5, *const xev = iev + 4, *const bev = xev + 2;
+    std::vector<hipEvent_t> xl_ev, bl_ev;
     std::string err;
     float compat_ms = 0.f, prune_ms = 0.f;
     int32_t paths[FCLU_N_PATHS] = {};     // the last graph call's launch census (fclu_last_paths)
@@ -1616,12 +1731,26 @@ struct fclu_ctx {
     float xprep_ms = 0.f, xsearch_ms = 0.f, xlongest_ms = 0.f;
     fclu_exact exact = {};
     bool have_exact = false;
+    // fclu_round_bnb(): the same input; device arrays (bd: the problems, the taken ones' list, the work items, the 64-bit tables, conflict
+    // words and groups' support words, g2, the bounds, per problem its first task and task count, a result per task and per problem) and
+    // the pinned copies fclu_round_bnb_results() hands out (bh)
+    struct {
+        Buf<ExactProb> probs; Buf<int4> items; Buf<u64> tab, conf, gsup; Buf<i64> ub2, task_off, n_tasks; Buf<BnbTask> tasks; Buf<BnbOut> out;
+        Buf<int> list, g2;
+    } bd;
+    struct {
+        HostBuf<BnbOut> out; HostBuf<int64_t> cost2, nodes; HostBuf<uint64_t> mask; HostBuf<int32_t> status, capped;
+    } bh;
+    float bprep_ms = 0.f, bsearch_ms = 0.f, blongest_ms = 0.f;
+    fclu_bnb bnb = {};
+    bool have_bnb = false;
     // (the buffers free themselves behind it, on this device)
     ~fclu_ctx() {
         (void)hipSetDevice(device);
         if (stream) { (void)hipStreamSynchronize(stream); (void)hipStreamDestroy(stream); }
         for (hipEvent_t e : events) if (e) (void)hipEventDestroy(e);
         for (hipEvent_t e : xl_ev) if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : bl_ev) if (e) (void)hipEventDestroy(e);
     }
 };
 
@@ -1657,7 +1786,8 @@ int fail(fclu_ctx *c, int code, const char *fmt, ...) {
 //   FCLU_ROUND_LDS_BYTES=n  round_lds_bytes  0 < n < kRoundLdsBytes: a lower limit of the LDS path, so that small problems take both ways in one batch
 //   FCLU_EXACT_SLICE=n      exact_slice      0 < n < kExactWgMasks: fclu_round_exact gives a workgroup n masks and a launch 16 n, so that a small problem crosses
 //                                            many slices and several launches
-struct Knobs { bool part_lds, prune_lds, rank, prune_edges, round_lds; i64 prune_lds_words, round_lds_bytes, exact_slice; unsigned hash_mask; };
+//   FCLU_BNB_SLICE=n        bnb_slice        n > 0: fclu_round_bnb gives a launch n tasks (and a workgroup min(n, 256)), so that a problem crosses several launches
+struct Knobs { bool part_lds, prune_lds, rank, prune_edges, round_lds; i64 prune_lds_words, round_lds_bytes, exact_slice, bnb_slice; unsigned hash_mask; };
 
 Knobs read_knobs() {
     const auto off = [](const char *name) { const char *e = getenv(name); return e && e[0] == '0'; };
@@ -1670,6 +1800,8 @@ Knobs read_knobs() {
     k.round_lds_bytes = (rb && atoll(rb) > 0 && atoll(rb) < kRoundLdsBytes) ? atoll(rb) : kRoundLdsBytes;
     const char *xs = getenv("FCLU_EXACT_SLICE");
     k.exact_slice = (xs && atoll(xs) > 0 && atoll(xs) < kExactWgMasks) ? atoll(xs) : 0;
+    const char *bs = getenv("FCLU_BNB_SLICE");
+    k.bnb_slice = (bs && atoll(bs) > 0 && atoll(bs) < (1ll << 30)) ? atoll(bs) : 0;
     const char *hb = getenv("FCLU_HASH_BITS");
     k.hash_mask = (hb && hb[0] >= '0' && hb[0] <= '9' && atoi(hb) < 32) ? (1u << atoi(hb)) - 1u : 0xffffffffu;
     return k;
@@ -2613,7 +2745,7 @@ void round_launch(fclu_ctx *c, const RoundRun &r) {
 }
 
 int round_device(fclu_ctx *c, const Knobs &k, const fclu_round_batch *b) {
-    c->have_rounds = c->have_incs = c->have_exact = false;
+    c->have_rounds = c->have_incs = c->have_exact = c->have_bnb = false;
     c->rcount_ms = c->rgaps_ms = c->rfill_ms = 0.f;
     if (!c->round_ready || !c->round_src_ok || !c->have_parts)
         return fail(c, FCLU_ERR_ARG, "fclu_round_models: no fclu_round_setup() behind the context's last partition call");
@@ -2863,6 +2995,24 @@ int incumbents_device(fclu_ctx *c, const Knobs &k, const int32_t *g2, double lo_
 }
 
 // ---- the exact solve of the last round's small problems (fclu_round_exact) ------------------------------------------------------
+// Problem p of the last round as fclu_round_exact and fclu_round_bnb describe it to their kernels, and whether its offsets lie inside
+// the round's arrays (asked only of a problem that is taken).
+void fill_exact_prob(const fclu_ctx *c, int p, ExactProb &d) {
+    const fclu_rounds &o = c->rounds;
+    const RoundProb &rp = c->r_probs[(size_t)p];
+    d.col0 = rp.col0; d.inf0 = o.inf_off[p]; d.pair0 = o.pair_off[p]; d.pair1 = o.pair_off[p + 1];
+    d.grp0 = o.grp_off[p]; d.grp1 = o.grp_off[p + 1]; d.row0 = o.row_off[p]; d.row1 = o.row_off[p + 1];
+    d.max_lg = c->r_max_lg[(size_t)rp.tint];
+    d.n = rp.n; d.n_inf = (int)(o.inf_off[p + 1] - o.inf_off[p]);
+}
+
+bool exact_prob_in_range(const fclu_ctx *c, int p, const ExactProb &d) {
+    const fclu_rounds &o = c->rounds;
+    return !(d.inf0 < 0 || o.inf_off[p + 1] < d.inf0 || o.inf_off[p + 1] > o.n_inf || d.n_inf > kMaxWords * 32 || d.pair0 < 0 || d.pair1 < d.pair0 ||
+             d.pair1 > o.n_pairs || d.grp0 < 0 || d.grp1 < d.grp0 || d.grp1 > o.n_grp || d.row0 < 0 || d.row1 < d.row0 || d.row1 > o.n_gap_rows || d.col0 < 0 ||
+             d.col0 + d.n > o.n_cols);
+}
+
 int exact_device(fclu_ctx *c, const Knobs &k, const int32_t *g2, double lo_f, double hi_f, int32_t offset, int32_t max_cols, int64_t max_masks) {
     c->have_exact = false;
     c->xprep_ms = c->xsearch_ms = c->xlongest_ms = 0.f;
@@ -2888,16 +3038,10 @@ int exact_device(fclu_ctx *c, const Knobs &k, const int32_t *g2, double lo_f, do
     std::vector<ExactProb> probs((size_t)P);
     std::vector<std::pair<int, int>> order;
     for (int p = 0; p < P; ++p) {
-        const RoundProb &rp = c->r_probs[(size_t)p];
         ExactProb &d = probs[(size_t)p];
-        d.col0 = rp.col0; d.inf0 = o.inf_off[p]; d.pair0 = o.pair_off[p]; d.pair1 = o.pair_off[p + 1];
-        d.grp0 = o.grp_off[p]; d.grp1 = o.grp_off[p + 1]; d.row0 = o.row_off[p]; d.row1 = o.row_off[p + 1];
-        d.max_lg = c->r_max_lg[(size_t)rp.tint];
-        d.n = rp.n; d.n_inf = (int)(o.inf_off[p + 1] - o.inf_off[p]);
+        fill_exact_prob(c, p, d);
         if (o.refused[p] >= 0 || d.n > max_cols) continue;   // no model, or too many columns: cost2 -2
-        if (d.inf0 < 0 || o.inf_off[p + 1] < d.inf0 || o.inf_off[p + 1] > o.n_inf || d.n_inf > kMaxWords * 32 || d.pair0 < 0 || d.pair1 < d.pair0 ||
-            d.pair1 > o.n_pairs || d.grp0 < 0 || d.grp1 < d.grp0 || d.grp1 > o.n_grp || d.row0 < 0 || d.row1 < d.row0 || d.row1 > G || d.col0 < 0 || d.col0 + d.n > C)
-            return fail(c, FCLU_ERR_HIP, "problem %d: the round's offsets are out of range", p);
+        if (!exact_prob_in_range(c, p, d)) return fail(c, FCLU_ERR_HIP, "problem %d: the round's offsets are out of range", p);
         if (o.n_grp == 0) d.row0 = d.row1 = 0;               // (a row has a group: nothing to index without one)
         order.emplace_back(d.n, p);
     }
@@ -2978,6 +3122,138 @@ int exact_device(fclu_ctx *c, const Knobs &k, const int32_t *g2, double lo_f, do
     return FCLU_OK;
 }
 
+// ---- the branch and bound over the last round's larger problems (fclu_round_bnb) ------------------------------------------------
+int bnb_device(fclu_ctx *c, const Knobs &k, const int32_t *g2, const int64_t *ub2, double lo_f, double hi_f, int32_t offset, int32_t min_cols, int32_t max_cols,
+               int32_t depth, int32_t node_cap, int64_t max_nodes) {
+    c->have_bnb = false;
+    c->bprep_ms = c->bsearch_ms = c->blongest_ms = 0.f;
+    if (!c->have_rounds || !c->round_ready || !c->round_src_ok || !c->have_parts)
+        return fail(c, FCLU_ERR_ARG, "fclu_round_bnb: no successful fclu_round_models() stands behind the call (none was made, it failed, or a later "
+                                     "call ended the rounds' source)");
+    const fclu_rounds &o = c->rounds;
+    const int P = o.n_prob;
+    const i64 C = o.n_cols, G = o.n_gap_rows;
+    if (min_cols < 0 || max_cols < min_cols || max_cols > kBnbMaxCols)
+        return fail(c, FCLU_ERR_ARG, "fclu_round_bnb: min_cols is %d and max_cols %d, they must be 0 <= min_cols <= max_cols <= %d", (int)min_cols, (int)max_cols,
+                    kBnbMaxCols);
+    if (depth < 0 || depth > kBnbMaxDepth) return fail(c, FCLU_ERR_ARG, "fclu_round_bnb: depth is %d, it must lie in [0, %d]", (int)depth, kBnbMaxDepth);
+    if (node_cap < 1) return fail(c, FCLU_ERR_ARG, "fclu_round_bnb: node_cap is %d, it must be at least 1", (int)node_cap);
+    if (max_nodes < 1) return fail(c, FCLU_ERR_ARG, "fclu_round_bnb: max_nodes is %lld, it must be at least 1", (i64)max_nodes);
+    if (offset < 0 || !(lo_f == lo_f) || !(hi_f == hi_f) || lo_f - lo_f != 0.0 || hi_f - hi_f != 0.0)
+        return fail(c, FCLU_ERR_ARG, "fclu_round_bnb: offset is negative or a factor is not finite");
+    if (C > 0 && !g2) return fail(c, FCLU_ERR_ARG, "fclu_round_bnb: g2 is null");
+    if (P > 0 && !ub2) return fail(c, FCLU_ERR_ARG, "fclu_round_bnb: ub2 is null");
+    for (i64 x = 0; x < C; ++x) if (g2[x] < 0) return fail(c, FCLU_ERR_ARG, "fclu_round_bnb: g2[%lld] is negative", x);
+    if ((int)c->r_probs.size() != P) return fail(c, FCLU_ERR_ARG, "fclu_round_bnb: the round's problems are gone");
+    HIP_TRY(c, hipSetDevice(c->device));
+    auto &D = c->bd;
+    auto &H = c->bh;
+    auto &RD = c->rd;
+    hipStream_t s = c->stream;
+    // ---- which problems are taken: ascending (R, problem) while the running total of 2^D x node_cap stays inside the budget
+    std::vector<ExactProb> probs((size_t)P);
+    std::vector<std::pair<int, int>> order;
+    for (int p = 0; p < P; ++p) {
+        ExactProb &d = probs[(size_t)p];
+        fill_exact_prob(c, p, d);
+        if (o.refused[p] >= 0 || d.n < min_cols || d.n > max_cols || d.n_inf > kBnbMaxInf) continue;      // no model, outside the sizes, or tables beyond LDS
+        if (!exact_prob_in_range(c, p, d)) return fail(c, FCLU_ERR_HIP, "problem %d: the round's offsets are out of range", p);
+        if (o.n_grp == 0) d.row0 = d.row1 = 0;               // (a row has a group: nothing to index without one)
+        order.emplace_back(d.n, p);
+    }
+    std::sort(order.begin(), order.end());
+    const i64 launch_tasks = k.bnb_slice ? k.bnb_slice : std::max<i64>(kBnbLaunchNodes / node_cap, 1);
+    const i64 wg_tasks = std::min<i64>(kBnbWgTasks, launch_tasks);
+    std::vector<int> list;
+    std::vector<int4> items;
+    std::vector<size_t> launch_first;                        // a launch's first item; closed by the number of items
+    std::vector<size_t> launch_lds;
+    std::vector<i64> task_off((size_t)P, 0), n_tasks((size_t)P, 0);
+    i64 budget = 0, total_tasks = 0, in_launch = 0;
+    for (const auto &rp : order) {
+        const ExactProb &d = probs[(size_t)rp.second];
+        const i64 tasks = 1ll << std::min<int>(d.n, depth);
+        if (tasks > (max_nodes - budget) / node_cap) break;  // (ascending R: nothing behind it fits either; no product that could overflow)
+        budget += tasks * node_cap;
+        list.push_back(rp.second);
+        task_off[(size_t)rp.second] = total_tasks; n_tasks[(size_t)rp.second] = tasks;
+        total_tasks += tasks;
+        const size_t lds = (size_t)(16 * d.n_inf + 12 * d.n + 15) & ~(size_t)15;
+        for (i64 lo = 0; lo < tasks; lo += wg_tasks) {
+            const i64 n = std::min<i64>(wg_tasks, tasks - lo);
+            if (launch_first.empty() || in_launch + n > launch_tasks) { launch_first.push_back(items.size()); launch_lds.push_back(0); in_launch = 0; }
+            items.push_back(make_int4(rp.second, (int)lo, (int)n, 0));
+            launch_lds.back() = std::max(launch_lds.back(), lds);
+            in_launch += n;
+        }
+    }
+    const size_t nL = list.size(), nI = items.size(), n_launch = launch_first.size(), nP = (size_t)P, nC = (size_t)C, nT = (size_t)total_tasks;
+    launch_first.push_back(nI);
+    if (n_launch > (size_t)kBnbMaxLaunches)
+        return fail(c, FCLU_ERR_UNSUPPORTED, "fclu_round_bnb: %lld tasks need %lld launches, a call issues %d at the most: lower max_nodes", total_tasks, (i64)n_launch,
+                    kBnbMaxLaunches);
+    while (c->bl_ev.size() < n_launch + 1) {
+        hipEvent_t e = nullptr;
+        HIP_TRY(c, hipEventCreate(&e));
+        c->bl_ev.push_back(e);
+    }
+    HIP_TRY(c, D.probs.grow(nP)); HIP_TRY(c, D.list.grow(nL)); HIP_TRY(c, D.items.grow(nI)); HIP_TRY(c, D.tab.grow(2 * (size_t)o.n_inf));
+    HIP_TRY(c, D.conf.grow(nC)); HIP_TRY(c, D.gsup.grow((size_t)o.n_grp_seg)); HIP_TRY(c, D.g2.grow(nC)); HIP_TRY(c, D.ub2.grow(nP));
+    HIP_TRY(c, D.task_off.grow(nP)); HIP_TRY(c, D.n_tasks.grow(nP)); HIP_TRY(c, D.tasks.grow(nT)); HIP_TRY(c, D.out.grow(nP));
+    HIP_TRY(c, H.out.grow(nP)); HIP_TRY(c, H.cost2.grow(nP)); HIP_TRY(c, H.mask.grow(nP)); HIP_TRY(c, H.nodes.grow(nP)); HIP_TRY(c, H.status.grow(nP));
+    HIP_TRY(c, H.capped.grow(nP));
+    if (nP) {
+        HIP_TRY(c, hipMemcpyAsync(D.probs.p, probs.data(), D.probs.bytes(nP), hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipMemcpyAsync(D.ub2.p, ub2, D.ub2.bytes(nP), hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipMemcpyAsync(D.task_off.p, task_off.data(), D.task_off.bytes(nP), hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipMemcpyAsync(D.n_tasks.p, n_tasks.data(), D.n_tasks.bytes(nP), hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipMemsetAsync(D.out.p, 0, D.out.bytes(nP), s));
+    }
+    if (nL) HIP_TRY(c, hipMemcpyAsync(D.list.p, list.data(), D.list.bytes(nL), hipMemcpyHostToDevice, s));
+    if (nI) HIP_TRY(c, hipMemcpyAsync(D.items.p, items.data(), D.items.bytes(nI), hipMemcpyHostToDevice, s));
+    if (C) HIP_TRY(c, hipMemcpyAsync(D.g2.p, g2, D.g2.bytes(nC), hipMemcpyHostToDevice, s));
+    if (o.n_inf) HIP_TRY(c, hipMemsetAsync(D.tab.p, 0, D.tab.bytes(2 * (size_t)o.n_inf), s));
+    if (C) HIP_TRY(c, hipMemsetAsync(D.conf.p, 0, D.conf.bytes(nC), s));
+    HIP_TRY(c, hipEventRecord(c->bev[0], s));
+    if (nL)
+        hipLaunchKernelGGL(k_bnb_prep, dim3((unsigned)nL), dim3(256), 0, s, D.list.p, D.probs.p, RD.inf_seg.p, RD.sup_off.p, (i64)o.n_inf, RD.sup_cols.p, (i64)o.n_sup,
+                           RD.corr_off.p, C, RD.corr_seg.p, (i64)o.n_corr, RD.pairs.p, RD.grp_seg_off.p, RD.grp_seg.p, (i64)o.n_grp_seg, D.tab.p, D.conf.p, D.gsup.p);
+    HIP_TRY(c, hipEventRecord(c->bev[1], s));
+    HIP_TRY(c, hipEventRecord(c->bl_ev[0], s));
+    for (size_t l = 0; l < n_launch; ++l) {
+        hipLaunchKernelGGL(k_bnb_search, dim3((unsigned)(launch_first[l + 1] - launch_first[l])), dim3(256), launch_lds[l], s, D.items.p + launch_first[l], D.probs.p,
+                           D.tab.p, D.conf.p, D.g2.p, D.ub2.p, RD.rows.p, G, RD.grp_seg_off.p, (i64)o.n_grp, (i64)o.n_grp_seg, D.gsup.p, RD.grp_len.p, lo_f, hi_f,
+                           (int)offset, (int)depth, (int)node_cap, D.task_off.p, D.tasks.p);
+        HIP_TRY(c, hipEventRecord(c->bl_ev[l + 1], s));
+    }
+    if (nL) hipLaunchKernelGGL(k_bnb_reduce, dim3((unsigned)nL), dim3(256), 0, s, D.list.p, D.task_off.p, D.n_tasks.p, D.tasks.p, D.out.p);
+    HIP_TRY(c, hipEventRecord(c->bev[2], s));
+    if (nP) HIP_TRY(c, hipMemcpyAsync(H.out.p, D.out.p, D.out.bytes(nP), hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    HIP_TRY(c, hipGetLastError());
+    for (int p = 0; p < P; ++p) { H.status.p[p] = FCLU_BNB_NOT_TAKEN; H.cost2.p[p] = -1; H.mask.p[p] = 0ull; H.nodes.p[p] = 0; H.capped.p[p] = 0; }
+    i64 nodes_total = 0;
+    for (const int p : list) {
+        const BnbOut &r = H.out.p[p];
+        const bool found = r.cost2 >= 0;
+        H.cost2.p[p] = found ? r.cost2 : -1; H.mask.p[p] = found ? r.mask : 0ull; H.nodes.p[p] = r.nodes; H.capped.p[p] = (int32_t)r.capped;
+        H.status.p[p] = r.capped > 0 ? FCLU_BNB_UNPROVEN : found ? FCLU_BNB_OPTIMAL : ub2[p] < 0 ? FCLU_BNB_INFEASIBLE : FCLU_BNB_UNPROVEN;
+        nodes_total += r.nodes;
+    }
+    fclu_bnb &r = c->bnb;
+    r.n_prob = P; r.status = H.status.p; r.cost2 = H.cost2.p; r.mask = H.mask.p; r.nodes = H.nodes.p; r.capped = H.capped.p;
+    r.n_taken = (int64_t)nL; r.n_launches = (int64_t)n_launch; r.nodes_total = nodes_total;
+    (void)hipEventElapsedTime(&c->bprep_ms, c->bev[0], c->bev[1]);
+    if (n_launch) (void)hipEventElapsedTime(&c->bsearch_ms, c->bl_ev[0], c->bl_ev[n_launch]);
+    for (size_t l = 0; l < n_launch; ++l) {
+        float ms = 0.f;
+        (void)hipEventElapsedTime(&ms, c->bl_ev[l], c->bl_ev[l + 1]);
+        c->blongest_ms = std::max(c->blongest_ms, ms);
+    }
+    c->have_bnb = true;
+    return FCLU_OK;
+}
+
 }  // namespace
 
 // ---- the C ABI ------------------------------------------------------------------------------------------------------------
@@ -3008,7 +3284,8 @@ int fclu_create(int device, fclu_ctx **out) {
         {reinterpret_cast<const void *>(k_round<true, true>), kRoundLdsBytes},
         {reinterpret_cast<const void *>(k_inc_start<true>), (int)inc_lds_bytes(0, kMaxWords, (kIncMaxCols + 31) / 32, false) + kRoundLdsBytes},
         {reinterpret_cast<const void *>(k_inc_start<false>), (int)inc_lds_bytes(0, kMaxWords, (kIncMaxCols + 31) / 32, false)},
-        {reinterpret_cast<const void *>(k_exact_search), kExactLdsBytes}};
+        {reinterpret_cast<const void *>(k_exact_search), kExactLdsBytes},
+        {reinterpret_cast<const void *>(k_bnb_search), kBnbLdsBytes}};
     for (const auto &d : dyn) if (e == hipSuccess) e = hipFuncSetAttribute(d.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, d.lds);
     if (e != hipSuccess) {
         fail(nullptr, FCLU_ERR_HIP, "context creation failed: %s", hipGetErrorString(e));
@@ -3228,6 +3505,25 @@ int fclu_round_exact_timing(fclu_ctx *c, float *prep_ms, float *search_ms, float
     if (!c) return FCLU_ERR_ARG;
     if (longest_launch_ms) *longest_launch_ms = c->xlongest_ms;
     return two_times(prep_ms, c->xprep_ms, search_ms, c->xsearch_ms);
+}
+
+int fclu_round_bnb(fclu_ctx *c, const int32_t *g2, const int64_t *ub2, double lo_f, double hi_f, int32_t offset, int32_t min_cols, int32_t max_cols,
+                   int32_t depth, int32_t node_cap, int64_t max_nodes) {
+    return c ? bnb_device(c, read_knobs(), g2, ub2, lo_f, hi_f, offset, min_cols, max_cols, depth, node_cap, max_nodes) : FCLU_ERR_ARG;
+}
+
+int fclu_round_bnb_results(fclu_ctx *c, fclu_bnb *out) {
+    if (!c || !out) return FCLU_ERR_ARG;
+    if (!c->have_bnb || !c->have_rounds)
+        return fail(c, FCLU_ERR_ARG, "fclu_round_bnb_results: no result (the last fclu_round_bnb call failed, none was made, or a later call ended it)");
+    *out = c->bnb;
+    return FCLU_OK;
+}
+
+int fclu_round_bnb_timing(fclu_ctx *c, float *prep_ms, float *search_ms, float *longest_launch_ms) {
+    if (!c) return FCLU_ERR_ARG;
+    if (longest_launch_ms) *longest_launch_ms = c->blongest_ms;
+    return two_times(prep_ms, c->bprep_ms, search_ms, c->bsearch_ms);
 }
 
 }  // extern "C"

@@ -17,7 +17,8 @@
  * (read_segment()'s read_reps, :154-164) on the device.  garbage_cost (from the members' counts) and the gaps dicts are host code.
  * The ILP's solve is not here; what run_ilp() builds its model from is: fclu_round_models() (at the end of this header) gives round r of
  * many partitions as flat arrays, from the rows and pair lists the calls above left on the device.  Problems of at most 24 columns need no
- * ILP: fclu_round_exact() (the last section) enumerates their column sets and returns the proven optimum.
+ * ILP: fclu_round_exact() enumerates their column sets and returns the proven optimum, and fclu_round_bnb() (the last section) searches
+ * problems of up to 64 columns by branch and bound.
  *
  * Data layout (caller-owned host arrays, copied by the call):
  *   tint t owns the unique reads row_off[t] .. row_off[t+1]  (N_t of them; "unique" = py/freddie_cluster.py:207-215)
@@ -349,6 +350,54 @@ int fclu_round_exact_results(fclu_ctx *c, fclu_exact *out);
 
 /* Kernel time of the last fclu_round_exact() from HIP events (ms): the transposed tables; all search launches; the longest of them. */
 int fclu_round_exact_timing(fclu_ctx *c, float *prep_ms, float *search_ms, float *longest_launch_ms);
+
+/* ---- branch and bound over a round's larger problems: a proven optimum of a problem of up to 64 columns where the search finishes ----
+ * The model and the rule of the result are fclu_round_exact's: S feasible by the same test, the smallest cost2, then the smallest mask
+ * (64 bits, bit c = column c).  D = min(R, depth); task t of a problem's 2^D fixes columns 0 .. D - 1 (bit c of t = column c is in) and is
+ * searched depth first over the columns D .. R - 1, the include child first where the column conflicts with no member, then the exclude
+ * child.  A node (columns 0 .. d - 1 fixed, S of them in) is dropped when its lower bound exceeds the task's best cost2 so far --
+ *   LB2 = the g2 of the columns fixed out + 2 * the members' corrections on the segments some member covers (e_in)
+ *         + over the columns c >= d: g2_c when c conflicts with a member, else min(g2_c, 2 * c's corrections on e_in),
+ * strictly, so that every set of optimal cost is reached -- or when a member's row is violated from below already
+ * (lo_f * G - offset > l + 1e-9, the doubles of the row test above; G only grows).  A leaf (d = R) is tested by the whole test above.  A
+ * task's best starts at ub2[p] (>= 0: a bound, e.g. the incumbent's cost2, which a leaf may equal; < 0: none).  Every child evaluated
+ * counts one node, the prefix one; a task whose count has reached node_cap when it wants another child stops and is capped, and its best
+ * leaf still counts.  Tasks share nothing, so the result, node counts included, is a function of the arguments.  The definition is
+ * freddie_amd/cluster_solve.py exact_bnb(), which the device reproduces exactly; what a lane computes is freddie_amd/csrc/clu_bnb.h.
+ * Input as fclu_round_exact's, and ub2[n_prob].  A problem is taken when it has a model, min_cols <= R <= max_cols <= 64, its tables fit
+ * one workgroup's LDS (160 KiB: 16 bytes an informative segment and 12 a column, 10 192 informative segments; a row holds 9 600 at the
+ * most, so every model fits) and it fits the budget: ascending (columns, problem index) while the running total of 2^D * node_cap stays
+ * <= max_nodes, a choice the host makes.  A launch holds at most 2^24 task-nodes of budget (tasks * node_cap; at least one task).
+ * FCLU_ERR_ARG: fclu_round_exact's cases; ub2 null with problems; min_cols < 0, max_cols < min_cols or > 64; depth outside [0, 20];
+ * node_cap < 1; max_nodes < 1.  FCLU_ERR_UNSUPPORTED: a budget that needs more than 4096 launches.  The context stays usable.
+ * FCLU_BNB_SLICE=<tasks> (read at the call; tests): a launch holds that many tasks. */
+int fclu_round_bnb(fclu_ctx *c, const int32_t *g2, const int64_t *ub2, double lo_f, double hi_f, int32_t offset, int32_t min_cols, int32_t max_cols,
+                   int32_t depth, int32_t node_cap, int64_t max_nodes);
+
+#define FCLU_BNB_OPTIMAL 0
+#define FCLU_BNB_INFEASIBLE 1
+#define FCLU_BNB_UNPROVEN 2
+#define FCLU_BNB_NOT_TAKEN (-2)
+
+typedef struct fclu_bnb {
+    int32_t n_prob;
+    const int32_t *status;         /* n_prob: 0 optimal (no task capped, a leaf at or under the bound); 1 infeasible (no task capped, no leaf, no bound);
+                                      2 unproven (a task capped, or a bound and no leaf under it); -2 not taken or refused */
+    const int64_t *cost2;          /* n_prob: twice the cost of the best set found; -1 where there is none */
+    const uint64_t *mask;          /* n_prob: that set, bit c = column c; 0 where cost2 < 0 */
+    const int64_t *nodes;          /* n_prob: nodes counted over the problem's tasks; 0 where it was not taken */
+    const int32_t *capped;         /* n_prob: tasks that stopped at node_cap */
+    int64_t n_taken;               /* problems taken */
+    int64_t n_launches;            /* search launches issued */
+    int64_t nodes_total;           /* the taken problems' nodes summed */
+} fclu_bnb;
+
+/* Result of the last successful fclu_round_bnb(): pointers into pinned host buffers the context owns, valid until the context's next
+ * call.  The round's, the incumbents' and the exact call's results stay valid behind it. */
+int fclu_round_bnb_results(fclu_ctx *c, fclu_bnb *out);
+
+/* Kernel time of the last fclu_round_bnb() from HIP events (ms): the tables; all search launches; the longest of them. */
+int fclu_round_bnb_timing(fclu_ctx *c, float *prep_ms, float *search_ms, float *longest_launch_ms);
 
 #ifdef __cplusplus
 }

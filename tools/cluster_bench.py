@@ -16,6 +16,10 @@ synthetic preprocessed tints through include/freddie_cluster.h.
     python tools/cluster_bench.py --exact [--max-ilp K] [--exact-small N] [--exact-masks M] [--steps K] [--host-sample N] [--solve-budget S] [--out FILE]
                        (per problem size N = 8, 12, 16, 20, 24: Context.round_exact on every partition's first N reps -- the call, the kernels,
                         the longest launch, masks per second -- against HiGHS on a sample of the same problems; profiles/cluster_exact.txt)
+    python tools/cluster_bench.py --bnb [--exact-bnb N] [--bnb-nodes M] [--bnb-depth D] [--bnb-node-cap C] [--steps K] [--host-sample N] [--solve-budget S] [--out FILE]
+                       (per maximum_ilp_size N = 32, 48, 64: Context.round_bnb on the first round's problems of 25 .. N columns -- taken, proved,
+                        capped, nodes, the call, the longest launch, nodes per second -- against HiGHS with 1 and 16 workers on a sample of
+                        the same problems, and the weak bound's node count from the mirror; profiles/cluster_bnb.txt)
     python tools/cluster_bench.py --rounds [--workload many|big] [--steps K] [--host-sample N] [--solve-budget S] [--out FILE]
                        (the first round of every partition: Context.round_models against the plain-Python build of the same arrays as
                         the reference does it, the kernels' event times, and -- apart -- what HiGHS takes on the same round; the
@@ -582,6 +586,158 @@ def run_exact(workload="many", steps=3, maximum_ilp_size=24, sizes=(8, 12, 16, 2
     }
 
 
+BNB_LAUNCH_NODES = 1 << 24       # kBnbLaunchNodes of freddie_amd/csrc/freddie_cluster.hip: the task-nodes of budget one search launch holds
+
+
+def _solve_timed(job):
+    from freddie_amd import cluster_solve
+    model, settings = job
+    t0 = time.perf_counter()
+    status, x, e = cluster_solve.solve_round(model, settings)
+    return status, (cluster_solve.round_cost(model, x, e) if status == cluster_solve.OPTIMAL else None), time.perf_counter() - t0
+
+
+def run_bnb(workload="many", steps=3, sizes=(32, 48, 64), min_cols=25, max_nodes=None, depth=None, node_cap=None, host_sample=16, solve_budget=240.0,
+            weak_budget=90.0, threads=16):
+    """Per N of `sizes` the workload is staged with maximum_ilp_size = N and the FIRST round of every partition is the batch:
+      device   Context.round_models, Context.round_incumbents (the bounds) and Context.round_bnb with min_cols .. N columns (medians over
+               `steps` after a warm-up): problems taken, proved (optimal or infeasible), unproven with and without a set, capped tasks,
+               nodes, the call, the kernels of fclu_round_bnb_timing (tables, all search launches, the longest launch), nodes per second;
+      sample   `host_sample` of the taken problems, evenly spread, as a round of their own: the three device calls timed together, then
+               HiGHS (cluster_solve.solve_round) on the same problems with 1 worker, one after the other until solve_budget / len(sizes)
+               seconds are spent, and on those it got through with 16 workers (wall time of a pool); the feature's path on them = the
+               device calls + HiGHS with 16 workers on the unproven ones, each with the incumbent cluster_tints() would hand it;
+      weak     the mirror (cluster_solve.bnb_task) with the weak bound on the sample's first problems, task by task, until weak_budget /
+               len(sizes) seconds are spent: its nodes and capped tasks beside the device's on the same tasks.
+    What was not taken is None."""
+    import tempfile
+    from multiprocessing import Pool
+    from freddie_amd import cluster, cluster_solve
+    depth = cluster_solve.BNB_DEPTH if depth is None else depth
+    node_cap = cluster_solve.BNB_NODE_CAP if node_cap is None else node_cap
+    max_nodes = cluster.BNB_NODES if max_nodes is None else max_nodes
+    pool = Pool(16)                                              # before the device is opened: the workers never touch it
+    med = lambda xs: float(np.median(xs))
+    rows = []
+    ctx = cluster_prep.Context(0)
+    for N in sizes:
+        with tempfile.TemporaryDirectory() as d:
+            paths, n_reads = write_segment_files(workload, d)
+            settings = cluster.ilp_settings(max_ilp=N)
+            tints, part0, _ = cluster.stage_files(paths, settings, ctx, threads)
+        costs = [cluster.garbage_costs(t, "constant") for t in tints]
+        problems = [(t, q, list(rids)) for t, tint in enumerate(tints) for q, (rids, _) in enumerate(tint["partitions"])]
+
+        def device(ps):
+            t0 = time.perf_counter()
+            arr = ctx.round_models([part0[t] + q for t, q, _ in ps], [rem for _, _, rem in ps])
+            garbage = [costs[t][i] for t, _, rem in ps for i in rem]
+            inc = ctx.round_incumbents(garbage, settings["epsilon"], settings["offset"])
+            t1 = time.perf_counter()
+            got = ctx.round_bnb(garbage, inc["cost2"], settings["epsilon"], settings["offset"], min_cols, N, max_nodes, depth, node_cap)
+            return arr, inc, got, t1 - t0, time.perf_counter() - t1
+
+        device(problems)                                                          # warm-up
+        call_s, kern = [], []
+        for _ in range(steps):
+            arr, inc, got, _, b = device(problems)
+            call_s.append(b)
+            kern.append(ctx.round_bnb_timing())
+        status = got["status"]
+        taken = np.flatnonzero(status != -2)
+        cols = np.diff(got["col_off"])
+        row = {"N": N, "problems": len(problems), "with_a_model": int((arr["refused"] < 0).sum()), "of_min_cols_to_N_columns": int(((cols >= min_cols) & (cols <= N)).sum()),
+               "informative_segments": int(arr["n_inf"]), "gap_rows": int(arr["n_gap_rows"]), "pairs_kept": int(arr["n_pairs"]),
+               "taken": got["n_taken"], "taken_columns": [int(cols[taken].min()), int(cols[taken].max())] if len(taken) else None,
+               "proved": int(((status == 0) | (status == 1)).sum()), "infeasible": int((status == 1).sum()),
+               "unproven_with_a_set": int(((status == 2) & (got["cost2"] >= 0)).sum()), "unproven_without_a_set": int(((status == 2) & (got["cost2"] < 0)).sum()),
+               "capped_tasks": int(got["capped"].sum()), "nodes": got["nodes_total"], "launches": got["n_launches"],
+               "round_bnb_call_ms": med(call_s) * 1e3, "round_bnb_call_spread_ms": [min(call_s) * 1e3, max(call_s) * 1e3],
+               "kernel_ms": {k: med([x[k] for x in kern]) for k in kern[0]},
+               "nodes_per_s_call": got["nodes_total"] / med(call_s),
+               "nodes_per_s_search_kernels": got["nodes_total"] / max(med([x["search_ms"] for x in kern]) * 1e-3, 1e-9)}
+        pick = taken[np.linspace(0, len(taken) - 1, min(host_sample, len(taken))).astype(int)].tolist() if len(taken) else []
+        sample = [problems[p] for p in pick]
+        if sample:
+            device(sample)
+            sarr, sinc, sgot, a, b = device(sample)
+            jobs, spent = [], 0.0
+            for p, (t, q, rem) in enumerate(sample):
+                model = cluster_prep.round_model(sarr, p)
+                model["garbage"] = [costs[t][i] for i in rem]; model["max_lg"] = sum(s[2] for s in tints[t]["segs"])
+                jobs.append(model)
+            serial = []
+            for model in jobs:                                                    # 1 worker
+                if spent >= solve_budget / len(sizes):
+                    break
+                serial.append(_solve_timed((model, settings)))
+                spent += serial[-1][2]
+            done = len(serial)
+            t0 = time.perf_counter()
+            pool.map(_solve_timed, [(m, settings) for m in jobs[:done]], chunksize=1)
+            pool16_s = time.perf_counter() - t0
+            later, agree = [], 0
+            for p in range(done):
+                found = cluster_prep.round_bnb_solution(sgot, p)
+                if found is not None and found != "infeasible" and found[0] != "unproven":
+                    agree += serial[p][0] == cluster_solve.OPTIMAL and abs(serial[p][1] - found[0]) < 0.25
+                elif found == "infeasible":
+                    agree += serial[p][0] != cluster_solve.OPTIMAL
+                else:
+                    m = dict(jobs[p])
+                    greedy = cluster_prep.round_incumbent(sinc, p)
+                    if found is not None and found[1] is not None:
+                        m["incumbent"] = tuple(found[1:]) if greedy is None or found[1] < greedy[0] else greedy
+                    later.append((m, settings))
+            t0 = time.perf_counter()
+            if later:
+                pool.map(_solve_timed, later, chunksize=1)
+            later_s = time.perf_counter() - t0
+            sstat = sgot["status"][:done]
+            row["sample"] = {"problems": len(sample), "solved_by_highs": done, "columns": [len(rem) for _, _, rem in sample[:done]],
+                             "models_and_incumbents_call_ms": a * 1e3, "round_bnb_call_ms": b * 1e3, "proved": int(((sstat == 0) | (sstat == 1)).sum()),
+                             "unproven": int((sstat == 2).sum()), "nodes": int(sgot["nodes"][:done].sum()),
+                             "highs_1_worker_s": spent, "highs_1_worker_slowest_s": max([x[2] for x in serial] or [0.0]), "highs_16_workers_s": pool16_s,
+                             "highs_statuses": {s: sum(1 for x in serial if x[0] == s) for s in set(x[0] for x in serial)},
+                             "proved_costs_agree_with_highs": int(agree), "later_solves_16_workers_s": later_s,
+                             "bnb_path_s": b + later_s, "bnb_path_faster_than_16_workers": bool(b + later_s < pool16_s)}
+            weak_nodes = weak_capped = strong_nodes = strong_capped = tasks = 0
+            t0 = time.perf_counter()
+            complete, out_of_time = 0, False
+            for p in range(done):
+                tb = cluster_solve.bnb_tables(jobs[p], settings)
+                D = min(tb["R"], depth)
+                ub2 = None if sinc["cost2"][p] < 0 else int(sinc["cost2"][p])
+                for t in range(1 << D):
+                    if time.perf_counter() - t0 > weak_budget / len(sizes):
+                        out_of_time = True
+                        break
+                    w = cluster_solve.bnb_task(tb, t, D, ub2, node_cap, weak=True)
+                    s = cluster_solve.bnb_task(tb, t, D, ub2, node_cap)
+                    weak_nodes += w[2]; weak_capped += w[3]; strong_nodes += s[2]; strong_capped += s[3]; tasks += 1
+                if out_of_time:
+                    break
+                complete += 1
+            row["weak_bound_mirror"] = {"problems_complete": complete, "tasks": tasks, "weak_nodes": weak_nodes, "weak_capped_tasks": weak_capped,
+                                        "full_bound_nodes_same_tasks": strong_nodes, "full_bound_capped_tasks": strong_capped}
+        print("N = %d: %d taken, %d proved, %d nodes, call %.2f ms, longest launch %.2f ms; sample %s" %
+              (N, got["n_taken"], row["proved"], got["nodes_total"], row["round_bnb_call_ms"], row["kernel_ms"]["longest_launch_ms"], row.get("sample")),
+              file=sys.stderr, flush=True)
+        rows.append(row)
+    ctx.close()
+    pool.close()
+    pool.join()
+    return {
+        "metric": "a round's problems of 25 to N columns: Context.round_bnb (branch and bound on the device) against HiGHS (cluster_solve.solve_round) on a sample of the same problems",
+        "unit": "ms", "data": "synthetic", "source_hash": _build_hash(),
+        "config": {"workload": "cluster-" + workload, **WORKLOADS[workload], "min_cols": min_cols, "max_nodes": max_nodes, "depth": depth, "node_cap": node_cap,
+                   "steps": steps, "host_sample": host_sample, "solve_budget_s": solve_budget, "weak_budget_s": weak_budget, "launch_bound_task_nodes": BNB_LAUNCH_NODES,
+                   "problems_of_N": "every partition's first round under maximum_ilp_size N"},
+        "longest_launch_ms": max(r["kernel_ms"]["longest_launch_ms"] for r in rows),
+        "sizes": rows,
+    }
+
+
 def _build_hash():
     from freddie_amd import build as _b
     return _b.embedded_hash(cluster_prep.CLUSTER_SO)
@@ -606,8 +762,22 @@ def main():
     ap.add_argument("--max-ilp", type=int, default=24, help="--exact: maximum_ilp_size the workload is staged with")
     ap.add_argument("--exact-small", type=int, default=None, help="--exact: one N instead of 8, 12, 16, 20, 24")
     ap.add_argument("--exact-masks", type=int, default=1 << 30, help="--exact: the mask budget of a call")
+    ap.add_argument("--bnb", action="store_true", help="measure Context.round_bnb under maximum_ilp_size 32, 48 and 64 against HiGHS on a sample of the same problems")
+    ap.add_argument("--exact-bnb", type=int, default=None, help="--bnb: one N instead of 32, 48, 64")
+    ap.add_argument("--bnb-nodes", type=int, default=None, help="--bnb: the node budget of a call (default: cluster.BNB_NODES)")
+    ap.add_argument("--bnb-depth", type=int, default=None, help="--bnb: columns the task number fixes (default: cluster_solve.BNB_DEPTH)")
+    ap.add_argument("--bnb-node-cap", type=int, default=None, help="--bnb: nodes a task may count (default: cluster_solve.BNB_NODE_CAP)")
+    ap.add_argument("--weak-budget", type=float, default=90.0, help="--bnb: seconds of the weak-bound mirror on the sample")
     args = ap.parse_args()
-    if args.exact:
+    if args.bnb:
+        res = run_bnb(args.workload, args.steps, (args.exact_bnb,) if args.exact_bnb is not None else (32, 48, 64), max_nodes=args.bnb_nodes, depth=args.bnb_depth,
+                      node_cap=args.bnb_node_cap, host_sample=16 if args.host_sample == 20 else args.host_sample,
+                      solve_budget=args.solve_budget if args.solve_budget != 120.0 else 240.0, weak_budget=args.weak_budget, threads=args.threads)
+        with open(args.out or os.path.join(ROOT, "profiles", "cluster_bnb.txt"), "w") as f:
+            f.write("tools/cluster_bench.py --bnb --workload %s --steps %d  (libfreddie_cluster.so source hash %s)\n" % (args.workload, args.steps, res["source_hash"]))
+            f.write(json.dumps(res, indent=1) + "\n")
+        print(json.dumps(res))
+    elif args.exact:
         res = run_exact(args.workload, args.steps, args.max_ilp, (args.exact_small,) if args.exact_small is not None else (8, 12, 16, 20, 24), args.exact_masks,
                         host_sample=24 if args.host_sample == 20 else args.host_sample, solve_budget=args.solve_budget, threads=args.threads)
         with open(args.out or os.path.join(ROOT, "profiles", "cluster_exact.txt"), "w") as f:
