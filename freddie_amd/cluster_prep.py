@@ -17,6 +17,9 @@ Reference map (file:line of vpc-ccg/freddie ``py/freddie_cluster.py``):
        cluster_files_batch(), tints_from_arrays() (back to the dicts, for code that wants them)
   informative_segs :331-344 and the model run_ilp builds :397-535 -> Context.round_setup() / Context.round_models() (GPU: one call per
        round of many partitions), round_gaps(), round_model(); the solve is freddie_amd/cluster_solve.py, the loop freddie_amd/cluster.py
+  run_ilp's read-out :601-635 -> Context.round_readout() (GPU: the isoforms of a round's accepted column sets, behind round_models() in
+       either form; fetch=False leaves the models on the device), readout_isoform(), and readout_mirror() / readout_words(), the numpy
+       restatement of the kernels' word arithmetic (tests, tools/readout_host_check.py)
 There is no CPU implementation of the quadratic
 loops in this package: without the HIP library partition_reads() raises.  FCLU_HOST_PARTITIONS=1 keeps :256-274 on the
 host, behind the GPU's graph (adjacency_matrix + _components + _partitions_from_graph): for A/B runs and timings.
@@ -156,7 +159,7 @@ def split_list_evenly(l, m):
 # ---------------------------------------------------------------------------------------------------------------
 CLUSTER_SO = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libfreddie_cluster.so")
 CLUSTER_SRC = [os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "freddie_cluster.hip")]
-CLUSTER_HEADERS = [os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", n) for n in ("clu_incumbent.h", "clu_exact.h", "clu_bnb.h")]
+CLUSTER_HEADERS = [os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", n) for n in ("clu_incumbent.h", "clu_exact.h", "clu_bnb.h", "clu_readout.h")]
 EXPORTS = ["fclu_abi_version", "fclu_create", "fclu_destroy", "fclu_last_error", "fclu_compat_graph", "fclu_last_timing",
            "fclu_last_paths",
            "fclu_partition", "fclu_partition_adj", "fclu_partition_results", "fclu_partition_timing",
@@ -165,7 +168,8 @@ EXPORTS = ["fclu_abi_version", "fclu_create", "fclu_destroy", "fclu_last_error",
            "fclu_round_setup", "fclu_round_models", "fclu_round_results", "fclu_round_timing",
            "fclu_round_incumbents", "fclu_round_incumbent_results", "fclu_round_incumbent_timing",
            "fclu_round_exact", "fclu_round_exact_results", "fclu_round_exact_timing",
-           "fclu_round_bnb", "fclu_round_bnb_results", "fclu_round_bnb_timing"]
+           "fclu_round_bnb", "fclu_round_bnb_results", "fclu_round_bnb_timing",
+           "fclu_round_models_resident", "fclu_round_readout", "fclu_round_readout_results", "fclu_round_readout_timing"]
 ERR_UNSUPPORTED = 3
 _lib = None
 
@@ -242,6 +246,15 @@ class _Exact(ctypes.Structure):
 class _Bnb(ctypes.Structure):
     _fields_ = [("n_prob", ctypes.c_int32)] + [(n, ctypes.c_void_p) for n in ("status", "cost2", "mask", "nodes", "capped")] + [
         (n, ctypes.c_int64) for n in ("n_taken", "n_launches", "nodes_total")]
+
+
+class _Readout(ctypes.Structure):
+    _fields_ = [("n_prob", ctypes.c_int32)] + [(n, ctypes.c_int64) for n in ("n_sets", "n_mem", "n_exon_bytes", "n_corr_bytes", "n_e")] + [
+        (n, ctypes.c_void_p) for n in ("exon_off", "exons", "mem_off", "corr_off", "corr", "e_off", "e")]
+
+
+_READOUT_PATHS = ("sets", "members", "stores")     # FCLU_PATH_READOUT_*, behind the graph's words
+STORE_WIDE, STORE_BYTES = 1, 2                     # FCLU_STORE_*
 
 
 BNB_STATUS = {0: "optimal", 1: "infeasible", 2: "unproven", -2: None}     # FCLU_BNB_*
@@ -325,6 +338,14 @@ def load():
     L.fclu_round_bnb_results.argtypes = [vp, ctypes.POINTER(_Bnb)]
     L.fclu_round_bnb_timing.restype = ctypes.c_int
     L.fclu_round_bnb_timing.argtypes = [vp] + [ctypes.POINTER(ctypes.c_float)] * 3
+    L.fclu_round_models_resident.restype = ctypes.c_int
+    L.fclu_round_models_resident.argtypes = [vp, ctypes.POINTER(_RoundBatch)]
+    L.fclu_round_readout.restype = ctypes.c_int
+    L.fclu_round_readout.argtypes = [vp, vp, vp]
+    L.fclu_round_readout_results.restype = ctypes.c_int
+    L.fclu_round_readout_results.argtypes = [vp, ctypes.POINTER(_Readout)]
+    L.fclu_round_readout_timing.restype = ctypes.c_int
+    L.fclu_round_readout_timing.argtypes = [vp] + [ctypes.POINTER(ctypes.c_float)] * 2
     _lib = L
     return L
 
@@ -516,12 +537,15 @@ class Context:
         if rc != 0:
             raise ClusterError("fclu_round_setup: " + self._L.fclu_last_error(self._h).decode(), rc)
 
-    def round_models(self, parts, remaining):
+    def round_models(self, parts, remaining, fetch=True):
         """The ILP models of one round of many partitions, one device call (include/freddie_cluster.h, fclu_rounds): parts = partition
         ids numbered through the batch, remaining = per problem the remaining rep ids (local to the tint) in the caller's order.
         Returns the flat numpy arrays, pairs as [n, 2], grp as [n, 2], rows as [n, 3] (column, group, l); round_model() cuts one
         problem out.  refused[p] >= 0: the reference raises on problem p (a gap with an uninformative endpoint, :467-468), the value is
-        the smallest offending column and the problem has no model."""
+        the smallest offending column and the problem has no model.
+        fetch=False (fclu_round_models_resident): the models stay on the device, where round_incumbents(), round_exact(), round_bnb() and
+        round_readout() find them; only n_prob, the counts, refused, col_off, inf_bits_off and inf_bits come back, under resident=True,
+        and round_model() refuses such a result."""
         part = np.ascontiguousarray(parts, np.int64)
         if len(remaining) != part.size:
             raise ClusterError("round_models: %d partitions, %d remaining lists" % (part.size, len(remaining)))
@@ -530,7 +554,7 @@ class Context:
         rids = np.fromiter((i for r in remaining for i in r), np.int32, int(rid_off[-1]))
         b = _RoundBatch(n_prob=part.size, part=part.ctypes.data if part.size else None, rid_off=rid_off.ctypes.data,
                         rids=rids.ctypes.data if rids.size else None)
-        rc = self._L.fclu_round_models(self._h, ctypes.byref(b))
+        rc = (self._L.fclu_round_models if fetch else self._L.fclu_round_models_resident)(self._h, ctypes.byref(b))
         if rc != 0:
             raise ClusterError("fclu_round_models: " + self._L.fclu_last_error(self._h).decode(), rc)
         r = _Rounds()
@@ -541,6 +565,11 @@ class Context:
         out = dict(n_prob=P)
         for n in _ROUND_COUNTS:
             out[n] = int(getattr(r, n))
+        if not fetch:
+            out["resident"] = True
+            out["inf_bits_off"], out["col_off"] = _copy_out(r.inf_bits_off, P + 1, np.int64), _copy_out(r.col_off, P + 1, np.int64)
+            out["refused"], out["inf_bits"] = _copy_out(r.refused, P, np.int32), _copy_out(r.inf_bits, int(out["inf_bits_off"][-1]), np.uint32)
+            return out
         for n in ("inf_bits_off", "inf_off", "col_off", "pair_off", "grp_off", "row_off"):
             out[n] = _copy_out(getattr(r, n), P + 1, np.int64)
         for n, cnt, dt in (("refused", P, np.int32), ("inf_bits", int(out["inf_bits_off"][-1]), np.uint32), ("inf_seg", out["n_inf"], np.int32),
@@ -646,6 +675,52 @@ class Context:
         self._L.fclu_round_bnb_timing(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(f))
         return dict(prep_ms=a.value, search_ms=b.value, longest_launch_ms=f.value)
 
+    def round_readout(self, sets):
+        """The isoforms of the last round_models() call's problems (either form) from their accepted column sets, one device call
+        (include/freddie_cluster.h, fclu_readout; the definition is cluster.read_out()): sets = per problem the accepted columns, ascending,
+        or an empty list for "no isoform this round".  Returns numpy arrays: exons (uint8 0 / 1, M_t a problem with a set) under exon_off;
+        corr (ASCII bytes, M_t a member, in set order; member k of problem p starts at corr_off[p] + k * M_t); e (the exon values at the
+        informative segments) under e_off; mem_off; and n_sets, n_mem.  readout_isoform() cuts one problem out."""
+        r = _Rounds()
+        rc = self._L.fclu_round_results(self._h, ctypes.byref(r))
+        if rc != 0:
+            raise ClusterError("round_readout: " + self._L.fclu_last_error(self._h).decode(), rc)
+        if len(sets) != r.n_prob:
+            raise ClusterError("round_readout: %d sets for the %d problems of the last round_models() call" % (len(sets), r.n_prob))
+        sel_off = np.zeros(len(sets) + 1, np.int64)
+        np.cumsum([len(x) for x in sets], out=sel_off[1:])
+        sel = np.fromiter((c for x in sets for c in x), np.int32, int(sel_off[-1]))
+        rc = self._L.fclu_round_readout(self._h, sel_off.ctypes.data, sel.ctypes.data if sel.size else None)
+        if rc != 0:
+            raise ClusterError("fclu_round_readout: " + self._L.fclu_last_error(self._h).decode(), rc)
+        o = _Readout()
+        rc = self._L.fclu_round_readout_results(self._h, ctypes.byref(o))
+        if rc != 0:
+            raise ClusterError("fclu_round_readout_results: " + self._L.fclu_last_error(self._h).decode(), rc)
+        P = o.n_prob
+        if P != len(sets):
+            raise ClusterError("round_readout: %d sets for the %d problems of the last round_models() call" % (len(sets), P))
+        return dict(n_prob=P, n_sets=int(o.n_sets), n_mem=int(o.n_mem), exon_off=_copy_out(o.exon_off, P + 1, np.int64),
+                    exons=_copy_out(o.exons, int(o.n_exon_bytes), np.uint8), mem_off=_copy_out(o.mem_off, P + 1, np.int64),
+                    corr_off=_copy_out(o.corr_off, P + 1, np.int64), corr=_copy_out(o.corr, int(o.n_corr_bytes), np.uint8),
+                    e_off=_copy_out(o.e_off, P + 1, np.int64), e=_copy_out(o.e, int(o.n_e), np.uint8), sel=sel)
+
+    def round_readout_timing(self):
+        a, b = ctypes.c_float(), ctypes.c_float()
+        self._L.fclu_round_readout_timing(self._h, ctypes.byref(a), ctypes.byref(b))
+        return dict(exons_ms=a.value, corr_ms=b.value)
+
+    def readout_paths(self):
+        """The launch census of the last round_readout() call (include/freddie_cluster.h, FCLU_PATH_READOUT_*): sets (problems with a
+        set), members, wide_stores / byte_stores (some lane stores 16 bytes at once / some byte is stored alone, as the host predicts
+        it from the rows' addresses; the kernel reports nothing)."""
+        v = np.zeros(len(_PATHS) + len(_READOUT_PATHS), np.int32)
+        rc = self._L.fclu_last_paths(self._h, v.ctypes.data, v.size)
+        if rc != 0:
+            raise ClusterError("fclu_last_paths: bad arguments", rc)
+        sets, members, stores = v[len(_PATHS):].tolist()
+        return dict(sets=sets, members=members, wide_stores=bool(stores & STORE_WIDE), byte_stores=bool(stores & STORE_BYTES))
+
     def round_timing(self):
         a, b, f = ctypes.c_float(), ctypes.c_float(), ctypes.c_float()
         self._L.fclu_round_timing(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(f))
@@ -715,6 +790,8 @@ def round_model(arr, p):
     """Problem p of Context.round_models() as plain lists, or None when it was refused: informative (bit row as a list of 0 / 1 is the
     caller's, from inf_bits), inf_seg, support (per informative segment its columns), corrections (per column its segments), pairs,
     groups [(j1, j2)], group_segs (per group [(j, length)]), gap_rows [(column, group, l)]."""
+    if isinstance(arr, dict) and arr.get("resident"):
+        raise ClusterError("round_model: the models of this round_models(fetch=False) call stayed on the device; problem %d has none on the host" % p)
     if arr["refused"][p] >= 0:
         return None
     i0, i1 = int(arr["inf_off"][p]), int(arr["inf_off"][p + 1])
@@ -730,6 +807,103 @@ def round_model(arr, p):
                 groups=[tuple(x) for x in arr["grp"][g0:g1].tolist()],
                 group_segs=[list(zip(gs[int(go[g]):int(go[g + 1])].tolist(), gl[int(go[g]):int(go[g + 1])].tolist())) for g in range(g0, g1)],
                 gap_rows=[tuple(x) for x in arr["rows"][int(arr["row_off"][p]):int(arr["row_off"][p + 1])].tolist()])
+
+
+def readout_isoform(out, p, remaining):
+    """Problem p of Context.round_readout() as cluster.read_out() returns it and the solver's e: (dict(exons, rid_to_corrections), e), or
+    None when the problem had no set.  remaining: the problem's rep ids in its column order."""
+    a, b = int(out["exon_off"][p]), int(out["exon_off"][p + 1])
+    m0, m1 = int(out["mem_off"][p]), int(out["mem_off"][p + 1])
+    if m0 == m1:
+        return None
+    M, c0 = b - a, int(out["corr_off"][p])
+    text = out["corr"][c0:c0 + (m1 - m0) * M].tobytes().decode("ascii")
+    members = out["sel"][m0:m1].tolist()
+    return (dict(exons=out["exons"][a:b].tolist(), rid_to_corrections={remaining[c]: list(text[k * M:(k + 1) * M]) for k, c in enumerate(members)}),
+            out["e"][int(out["e_off"][p]):int(out["e_off"][p + 1])].tolist())
+
+
+def readout_words(I, C, labels, inf, members, M, rule=None):
+    """One problem: I, C = uint32 [R, W] bit rows of its columns, labels = uint32 [R, LW] label rows (two bits a label), inf = uint32 [W],
+    members = the accepted columns.  Returns (exon words uint32 [W], corrections uint8 [len(members), M]).  rule names the one step left
+    out (the tests' mutations): "first_member" (the uninformative value from the first member instead of column 0), "x_without_exon"
+    ('X' wherever C is 1), "no_dash" ('-' dropped), "label2_as_0", "no_tail_mask" (the last word's bits behind M kept)."""
+    W = I.shape[1]
+    valid = np.full(W, 0xffffffff, np.uint32)
+    for w in range(W):                                       # ro_valid
+        n = min(max(M - 32 * w, 0), 32)
+        valid[w] = 0xffffffff if n >= 32 else (1 << n) - 1
+    if rule == "no_tail_mask":
+        valid[:] = 0xffffffff
+    member_or = np.bitwise_or.reduce(I[members], axis=0) if len(members) else np.zeros(W, np.uint32)
+    base = I[members[0]] if rule == "first_member" else I[0]
+    inf = inf & valid
+    ex = ((member_or & inf) | (base & ~inf)) & valid         # ro_exon_word
+    j = np.arange(M)
+    bit = lambda words: (words[..., j >> 5] >> (j & 31).astype(np.uint32)) & 1
+    corr = np.zeros((len(members), M), np.uint8)
+    for k, c in enumerate(members):                          # ro_corr_byte
+        code = (labels[c][j >> 4] >> (2 * (j & 15)).astype(np.uint32)) & 3
+        if rule == "label2_as_0":
+            code = np.where(code == 2, 0, code)
+        row = (ord("0") + code).astype(np.uint8)
+        x = (bit(C[c]) & (1 if rule == "x_without_exon" else bit(ex))) == 1
+        on = bit(inf) == 1
+        if rule == "no_dash":
+            row[x] = ord("X")
+        else:
+            row[x & on] = ord("X")
+            row[~on] = ord("-")
+        corr[k] = row
+    return ex, corr
+
+
+def _pack_bits(rows, M):
+    W = max((M + 31) // 32, 1)
+    a = np.zeros((len(rows), W * 32), np.uint8)
+    if M and len(rows):
+        a[:, :M] = np.asarray(rows, np.uint8).reshape(len(rows), M)
+    return np.packbits(a, axis=1, bitorder="little").view(np.uint32).reshape(len(rows), W)
+
+
+def readout_rows(tint, remaining):
+    """(I, C, labels) of a problem's columns as readout_words() wants them, from a preprocessed tint dict."""
+    M = len(tint["segs"])
+    I, C = tint["ilp_data"]["I"], tint["ilp_data"]["C"]
+    LW = max((M + 15) // 16, 1)
+    labels = np.zeros((len(remaining), LW), np.uint32)
+    for c, i in enumerate(remaining):
+        data = tint["reads"][tint["read_reps"][i][0]]["data"]
+        for j in range(M):
+            labels[c, j >> 4] |= np.uint32((data[j] & 3) << (2 * (j & 15)))
+    return _pack_bits([I[i] for i in remaining], M), _pack_bits([C[i] for i in remaining], M), labels
+
+
+def readout_mirror(tints, problems, sets, informative, rule=None):
+    """What Context.round_readout() returns, in numpy: the word arithmetic of freddie_amd/csrc/clu_readout.h on packed rows, so that the
+    kernels' code and this agree word by word (tools/readout_host_check.py) and this and cluster.read_out() agree on every case the tests
+    name.  problems = [(tint index, remaining rep ids)], sets = per problem the accepted columns, informative = per problem the 0 / 1
+    list of its segments (inf_bits unpacked).  rule: one step of readout_words() left out (tests)."""
+    exons, corr, e, exon_off, corr_off, e_off, mem_off, sel = [], [], [], [0], [0], [0], [0], []
+    for (t, remaining), members, inf in zip(problems, sets, informative):
+        members = list(members)
+        if members:
+            M = len(tints[t]["segs"])
+            I, C, labels = readout_rows(tints[t], remaining)
+            inf_w = _pack_bits([inf], M)[0]
+            ex, rows = readout_words(I, C, labels, inf_w, members, M, rule)
+            j = np.arange(M)
+            row = ((ex[j >> 5] >> (j & 31).astype(np.uint32)) & 1).astype(np.uint8)
+            exons.append(row); corr.append(rows.reshape(-1)); e.append(row[np.flatnonzero(np.asarray(inf[:M]))])
+            sel.extend(members)
+        exon_off.append(exon_off[-1] + (len(exons[-1]) if members else 0))
+        corr_off.append(corr_off[-1] + (len(corr[-1]) if members else 0))
+        e_off.append(e_off[-1] + (len(e[-1]) if members else 0))
+        mem_off.append(len(sel))
+    cat = lambda parts: np.concatenate(parts) if parts else np.zeros(0, np.uint8)
+    return dict(n_prob=len(problems), n_sets=len(exons), n_mem=len(sel), exon_off=np.array(exon_off, np.int64), exons=cat(exons),
+                mem_off=np.array(mem_off, np.int64), corr_off=np.array(corr_off, np.int64), corr=cat(corr), e_off=np.array(e_off, np.int64),
+                e=cat(e), sel=np.array(sel, np.int32))
 
 
 def round_incumbent(arr, p):

@@ -25,6 +25,7 @@
 #include "clu_incumbent.h"   // (behind the runtime: its functions are __host__ __device__)
 #include "clu_exact.h"
 #include "clu_bnb.h"
+#include "clu_readout.h"
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 
@@ -1586,6 +1587,101 @@ __global__ void __launch_bounds__(256) k_bnb_reduce(const int *list, const i64 *
     if (tid == 0) out[p] = s_part[0];
 }
 
+// ================================================================================================================
+// The read-out of a round (fclu_round_readout): run_ilp()'s isoform (py/freddie_cluster.py:601-635; cluster.read_out) of every problem
+// with an accepted column set, from the rows the context holds -- the reps' I, C and label rows, the round's informative rows and rids.
+// What a lane computes per word is clu_readout.h.
+// ================================================================================================================
+struct ReadoutProb {
+    i64 col0, rbits_off, lab_off, inf_off, sel0, exon0, corr0, e0, slot0;   // first column (in rids); the tint's first I / C word and first label word; the
+                                                                             // informative (and exon) row's first word; the set's first member (in sel); the
+                                                                             // first byte of the exon row, of the members' rows and of e; first lane slot
+    int n, n_sel, n_seg, w, lw, n_reps, n_e, g_log2;                         // columns, members, segments, bit and label words per row, the tint's reps, the
+                                                                             // informative segments, log2 of the lanes a member gets
+};
+
+// the rep (local to the tint) of column c, column and rep clamped
+__device__ __forceinline__ i64 readout_rep(const ReadoutProb &d, const int *rids, int c) {
+    return ro_clamp(rids[d.col0 + ro_clamp(c, 0, d.n - 1)], 0, d.n_reps - 1);
+}
+
+// A workgroup per problem with a set: lanes across the words, a loop over the members for the OR of their I words; with the informative
+// word and column 0's the exon word (kept in ex_bits, laid out as inf_bits, for k_readout_corr), then the row as bytes 0 / 1 and e, the exon
+// bits at the informative segments in ascending order (a prefix sum of the words' counts).
+__global__ void __launch_bounds__(256) k_readout_exons(const ReadoutProb *probs, const int *rids, const int *sel, const unsigned *ibits, const unsigned *inf_bits,
+                                                       unsigned *ex_bits, unsigned char *exons, unsigned char *e) {
+    __shared__ unsigned s_ex[kMaxWords], s_inf[kMaxWords];
+    __shared__ i64 s_wave[4];
+    const int tid = threadIdx.x;
+    const ReadoutProb d = probs[blockIdx.x];
+    if (d.n <= 0 || d.n_reps <= 0) return;                       // (the host gives no such problem a set)
+    const int W = min(max(d.w, 1), kMaxWords), M = min(max(d.n_seg, 0), 32 * W);
+    const i64 row0 = d.rbits_off + readout_rep(d, rids, 0) * d.w;
+    for (int w = tid; w < W; w += 256) {
+        unsigned acc = 0u;
+        for (int m = 0; m < d.n_sel; ++m) acc |= ibits[d.rbits_off + readout_rep(d, rids, sel[d.sel0 + m]) * d.w + w];
+        const unsigned valid = ro_valid(M, w), inf = inf_bits[d.inf_off + w] & valid;
+        const unsigned ex = ro_exon_word(acc, ibits[row0 + w], inf, valid);
+        s_ex[w] = ex; s_inf[w] = inf;
+        ex_bits[d.inf_off + w] = ex;
+    }
+    __syncthreads();
+    for (int k = tid; 4 * k < M; k += 256) {                     // four segments a lane: one store where the row starts at a multiple of 4
+        const unsigned v = ro_exon_bytes4(s_ex[k >> 3], k & 7);
+        unsigned char *out = exons + d.exon0 + 4 * k;
+        if (!(d.exon0 & 3) && 4 * k + 3 < M) *reinterpret_cast<unsigned *>(out) = v;
+        else for (int b = 0; b < 4 && 4 * k + b < M; ++b) out[b] = (unsigned char)(v >> (8 * b));
+    }
+    i64 carry = 0;
+    for (int w0 = 0; w0 < W; w0 += 256) {
+        const int w = w0 + tid;
+        unsigned m = w < W ? s_inf[w] : 0u;
+        const unsigned ex = w < W ? s_ex[w] : 0u;
+        i64 total;
+        i64 x = carry + block_scan(__popc(m), total, s_wave);
+        for (; m; m &= m - 1, ++x)
+            if (x < d.n_e) e[d.e0 + x] = (unsigned char)((ex >> (__ffs((int)m) - 1)) & 1u);
+        carry += total;
+    }
+}
+
+// A lane per (member, bit word), k_rows' grouping: a member gets g = 2^g_log2 lanes (the smallest power of two that holds its W words, 64
+// at the most) and a problem's slots start at a multiple of 64, so a wave works on one problem and one-word rows do not cost a wave each.
+// A lane reads its two label words, its C word, the informative and the exon word and writes its up to 32 characters: 16 at a time where
+// the address is a multiple of 16, alone at the ragged ends and in rows that start elsewhere (ro_store_halves).  No lane writes a byte of
+// another's.
+__global__ void __launch_bounds__(256) k_readout_corr(int n_set, i64 n_slots, const ReadoutProb *probs, const int *rids, const int *sel, const unsigned *labels,
+                                                      const unsigned *cbits, const unsigned *inf_bits, const unsigned *ex_bits, unsigned char *corr) {
+    const int lane = lane_id();
+    const i64 wave_g = ((i64)blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = ((i64)gridDim.x * blockDim.x) >> 6;
+    for (i64 s0 = wave_g * 64; s0 < n_slots; s0 += n_waves * 64) {
+        int lo = 0, hi = n_set - 1;                               // the last problem whose slots start at or before s0 (wave-uniform)
+        while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (probs[mid].slot0 <= s0) lo = mid; else hi = mid - 1; }
+        const ReadoutProb d = probs[__builtin_amdgcn_readfirstlane(lo)];
+        const int g_log2 = min(max(d.g_log2, 0), 6), g = 1 << g_log2, sub = lane & (g - 1);
+        const i64 m = (s0 - d.slot0 + lane) >> g_log2;
+        if (m < 0 || m >= d.n_sel || d.n <= 0 || d.n_reps <= 0) continue;
+        const int W = min(max(d.w, 1), kMaxWords), M = min(max(d.n_seg, 0), 32 * W), LW = max(d.lw, 1);
+        const i64 rep = readout_rep(d, rids, sel[d.sel0 + m]);
+        const unsigned *lab = labels + d.lab_off + rep * LW, *cb = cbits + d.rbits_off + rep * d.w;
+        const i64 row = d.corr0 + m * (i64)M;
+        for (int w = sub; w < W; w += g) {
+            const int nv = ro_word_segs(M, w);
+            const u64 x = (u64)lab[min(2 * w, LW - 1)] | (2 * w + 1 < LW ? (u64)lab[2 * w + 1] << 32 : 0ull);
+            const unsigned cw = cb[w], inf = inf_bits[d.inf_off + w] & ro_valid(M, w), ex = ex_bits[d.inf_off + w];
+            unsigned char *out = corr + row + 32 * w;
+            const int halves = ro_store_halves((u64)(row + 32 * w), nv);
+            if (halves & 1)
+                *reinterpret_cast<uint4 *>(out) = make_uint4(ro_corr_bytes4(x, cw, inf, ex, 0), ro_corr_bytes4(x, cw, inf, ex, 1), ro_corr_bytes4(x, cw, inf, ex, 2),
+                                                             ro_corr_bytes4(x, cw, inf, ex, 3));
+            if (halves & 2)
+                *reinterpret_cast<uint4 *>(out + 16) = make_uint4(ro_corr_bytes4(x, cw, inf, ex, 4), ro_corr_bytes4(x, cw, inf, ex, 5), ro_corr_bytes4(x, cw, inf, ex, 6),
+                                                                  ro_corr_bytes4(x, cw, inf, ex, 7));
+            for (int b = (halves & 2) ? 32 : (halves & 1) ? 16 : 0; b < nv; ++b) out[b] = (unsigned char)ro_corr_byte(x, cw, inf, ex, b);
+        }
+    }
+}
+
 }  // namespace
 
 // ---- buffers and the context -------------------------------------------------------------------------------------------
@@ -1624,13 +1720,14 @@ struct fclu_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
     // every event, one list to create and destroy; by stage: the graph (ev), fclu_partition (pev), _preprocess (qev), _group_reads (gev), _round_models (rev),
-    // _round_incumbents (iev), _round_exact's prep (xev; its search launches have an event each in xl_ev, created as a call needs them), _round_bnb's prep and reduction (bev; bl_ev likewise)
-    hipEvent_t events[3 + 6 + 6 + 5 + 5 + 4 + 2 + 3] = {};
-    hipEvent_t *const ev = events, *const pev = ev + 3, *const qev = pev + 6, *const gev = qev + 6, *const rev = gev + 5, *const iev = rev + 5, *const xev = iev + 4, *const bev = xev + 2;
+    // _round_incumbents (iev), _round_exact's prep (xev; its search launches have an event each in xl_ev, created as a call needs them), _round_bnb's prep and reduction (bev; bl_ev likewise),
+    // _round_readout (oev)
+    hipEvent_t events[3 + 6 + 6 + 5 + 5 + 4 + 2 + 3 + 3] = {};
+    hipEvent_t *const ev = events, *const pev = ev + 3, *const qev = pev + 6, *const gev = qev + 6, *const rev = gev + 5, *const iev = rev + 5, *const xev = iev + 4, *const bev = xev + 2, *const oev = bev + 3;
     std::vector<hipEvent_t> xl_ev, bl_ev;
     std::string err;
     float compat_ms = 0.f, prune_ms = 0.f;
-    int32_t paths[FCLU_N_PATHS] = {};     // the last graph call's launch census (fclu_last_paths)
+    int32_t paths[FCLU_N_PATHS] = {};     // the last graph call's launch census and the last read-out's (fclu_last_paths)
     Buf<TintDesc> tints; Buf<int4> tiles; Buf<int2> word_tint; Buf<i64> tint_word0;
     Buf<unsigned> bits; Buf<unsigned char> tail; Buf<u64> adj[2], deg1;
     Buf<int> row_tint, first, last, deg, small_tints, small_rounds;
@@ -1698,9 +1795,11 @@ struct fclu_ctx {
         HostBuf<int32_t> refused, inf_seg, sup_cols, corr_seg, grp, grp_seg, grp_len, rows;
     } rh;
     std::vector<int64_t> r_rep_off, r_gap_off, r_seg_off, r_rep_part, r_max_lg;
+    std::vector<int64_t> r_lab_off;           // per tint the first label word of its reps' rows in pd.labels (the read-out's)
     std::vector<int32_t> r_n_seg, r_part_tint, r_rep_stamp, r_part_stamp;
     int r_epoch = 0;
     bool round_src_ok = false, round_ready = false;
+    bool rounds_resident = false;             // the last fclu_round_models call was fclu_round_models_resident: c->rounds names the small arrays only
     float rcount_ms = 0.f, rgaps_ms = 0.f, rfill_ms = 0.f;
     fclu_rounds rounds = {};
     bool have_rounds = false;
@@ -1744,6 +1843,17 @@ struct fclu_ctx {
     float bprep_ms = 0.f, bsearch_ms = 0.f, blongest_ms = 0.f;
     fclu_bnb bnb = {};
     bool have_bnb = false;
+    // fclu_round_readout(): the same input and the reps' rows (pd.ibits / cbits / labels); device arrays (od: the problems with a set, the
+    // sets, the exon words, the three outputs) and the pinned copies fclu_round_readout_results() hands out (oh)
+    struct {
+        Buf<ReadoutProb> probs; Buf<int> sel; Buf<unsigned> ex_bits; Buf<unsigned char> exons, corr, e;
+    } od;
+    struct {
+        HostBuf<int64_t> exon_off, mem_off, corr_off, e_off; HostBuf<uint8_t> exons, corr, e;
+    } oh;
+    float oexon_ms = 0.f, ocorr_ms = 0.f;
+    fclu_readout readout = {};
+    bool have_readout = false;
     // (the buffers free themselves behind it, on this device)
     ~fclu_ctx() {
         (void)hipSetDevice(device);
@@ -2615,6 +2725,7 @@ int group_device(fclu_ctx *c, const Knobs &k, const fclu_segment *in, bool gathe
 void round_source(fclu_ctx *c, const fclu_reads *rd) {
     c->r_rep_off.assign(rd->rep_off, rd->rep_off + rd->n_tint + 1);
     c->r_n_seg.assign(rd->n_seg, rd->n_seg + rd->n_tint);
+    c->r_lab_off.assign(rd->lab_off, rd->lab_off + rd->n_tint + 1);
     c->round_src_ok = true;
 }
 
@@ -2744,8 +2855,10 @@ void round_launch(fclu_ctx *c, const RoundRun &r) {
                            D.rids.p, D.col_of.p, c->d_pairs.p, D.inf_bits.p, D.cnt.p, D.scan.p, D.inf_seg.p, D.sup_off.p, D.sup_cols.p, D.corr_off.p, D.corr_seg.p, D.pairs.p);
 }
 
-int round_device(fclu_ctx *c, const Knobs &k, const fclu_round_batch *b) {
-    c->have_rounds = c->have_incs = c->have_exact = c->have_bnb = false;
+// resident (fclu_round_models_resident): the same kernels and device arrays; of the results only the small per-problem arrays come to the
+// host -- what the later round calls and the read-out need of them -- and the model's own arrays stay where they are.
+int round_device(fclu_ctx *c, const Knobs &k, const fclu_round_batch *b, bool resident) {
+    c->have_rounds = c->have_incs = c->have_exact = c->have_bnb = c->have_readout = false;
     c->rcount_ms = c->rgaps_ms = c->rfill_ms = 0.f;
     if (!c->round_ready || !c->round_src_ok || !c->have_parts)
         return fail(c, FCLU_ERR_ARG, "fclu_round_models: no fclu_round_setup() behind the context's last partition call");
@@ -2836,27 +2949,30 @@ int round_device(fclu_ctx *c, const Knobs &k, const fclu_round_batch *b) {
     HIP_TRY(c, hipEventRecord(c->rev[4], s));
     fclu_rounds &o = c->rounds;
     // (the three CSR offset arrays close with their total, which the host writes: room for it before the copies are enqueued)
-    HIP_TRY(c, H.sup_off.grow((size_t)n_inf + 1)); HIP_TRY(c, H.corr_off.grow(nC + 1)); HIP_TRY(c, H.grp_seg_off.grow((size_t)n_grp + 1));
-    const int2 *h_pairs = nullptr;
+    if (!resident) { HIP_TRY(c, H.sup_off.grow((size_t)n_inf + 1)); HIP_TRY(c, H.corr_off.grow(nC + 1)); HIP_TRY(c, H.grp_seg_off.grow((size_t)n_grp + 1)); }
+    o = fclu_rounds();
     RC_TRY(fetch(c, H.refused, D.refused.p, (size_t)P, true, o.refused));
     RC_TRY(fetch(c, H.inf_bits, D.inf_bits.p, (size_t)r.n_inf_bits, true, o.inf_bits));
-    RC_TRY(fetch(c, H.inf_seg, D.inf_seg.p, (size_t)n_inf, true, o.inf_seg));
-    RC_TRY(fetch(c, H.sup_off, D.sup_off.p, (size_t)n_inf, true, o.sup_off));
-    RC_TRY(fetch(c, H.sup_cols, D.sup_cols.p, (size_t)n_sup, true, o.sup_cols));
-    RC_TRY(fetch(c, H.corr_off, D.corr_off.p, nC, true, o.corr_off));
-    RC_TRY(fetch(c, H.corr_seg, D.corr_seg.p, (size_t)n_corr, true, o.corr_seg));
-    RC_TRY(fetch(c, H.pairs, D.pairs.p, (size_t)n_pairs, true, h_pairs));
-    o.pairs = &h_pairs->x;
     RC_TRY(fetch(c, H.grp_off, D.grp_off.p, P1, true, o.grp_off));
-    RC_TRY(fetch(c, H.grp, D.grp.p, 2 * (size_t)n_grp, true, o.grp));
-    RC_TRY(fetch(c, H.grp_seg_off, D.grp_seg_off.p, (size_t)n_grp, true, o.grp_seg_off));
-    RC_TRY(fetch(c, H.grp_seg, D.grp_seg.p, (size_t)n_grp_seg, true, o.grp_seg));
-    RC_TRY(fetch(c, H.grp_len, D.grp_len.p, (size_t)n_grp_seg, true, o.grp_len));
-    RC_TRY(fetch(c, H.rows, D.rows.p, 3 * nG, true, o.rows));
+    if (!resident) {
+        const int2 *h_pairs = nullptr;
+        RC_TRY(fetch(c, H.inf_seg, D.inf_seg.p, (size_t)n_inf, true, o.inf_seg));
+        RC_TRY(fetch(c, H.sup_off, D.sup_off.p, (size_t)n_inf, true, o.sup_off));
+        RC_TRY(fetch(c, H.sup_cols, D.sup_cols.p, (size_t)n_sup, true, o.sup_cols));
+        RC_TRY(fetch(c, H.corr_off, D.corr_off.p, nC, true, o.corr_off));
+        RC_TRY(fetch(c, H.corr_seg, D.corr_seg.p, (size_t)n_corr, true, o.corr_seg));
+        RC_TRY(fetch(c, H.pairs, D.pairs.p, (size_t)n_pairs, true, h_pairs));
+        o.pairs = &h_pairs->x;
+        RC_TRY(fetch(c, H.grp, D.grp.p, 2 * (size_t)n_grp, true, o.grp));
+        RC_TRY(fetch(c, H.grp_seg_off, D.grp_seg_off.p, (size_t)n_grp, true, o.grp_seg_off));
+        RC_TRY(fetch(c, H.grp_seg, D.grp_seg.p, (size_t)n_grp_seg, true, o.grp_seg));
+        RC_TRY(fetch(c, H.grp_len, D.grp_len.p, (size_t)n_grp_seg, true, o.grp_len));
+        RC_TRY(fetch(c, H.rows, D.rows.p, 3 * nG, true, o.rows));
+    }
     for (HostBuf<int64_t> *h : {&H.inf_bits_off, &H.inf_off, &H.col_off, &H.pair_off, &H.row_off}) HIP_TRY(c, h->grow(P1));
     HIP_TRY(c, hipStreamSynchronize(s));
     HIP_TRY(c, hipGetLastError());
-    H.sup_off.p[n_inf] = n_sup; H.corr_off.p[C] = n_corr; H.grp_seg_off.p[n_grp] = n_grp_seg;
+    if (!resident) { H.sup_off.p[n_inf] = n_sup; H.corr_off.p[C] = n_corr; H.grp_seg_off.p[n_grp] = n_grp_seg; }
     for (int p = 0; p <= P; ++p) {
         H.inf_bits_off.p[p] = r.inf_bits_off[(size_t)p];
         H.inf_off.p[p] = H.scan.p[p] - H.scan.p[0];
@@ -2872,6 +2988,7 @@ int round_device(fclu_ctx *c, const Knobs &k, const fclu_round_batch *b) {
     (void)hipEventElapsedTime(&c->rgaps_ms, c->rev[1], c->rev[2]);
     (void)hipEventElapsedTime(&c->rfill_ms, c->rev[3], c->rev[4]);
     c->r_probs = r.probs;
+    c->rounds_resident = resident;
     c->have_rounds = true;
     return FCLU_OK;
 }
@@ -3254,6 +3371,99 @@ int bnb_device(fclu_ctx *c, const Knobs &k, const int32_t *g2, const int64_t *ub
     return FCLU_OK;
 }
 
+// ---- the read-out of the last round's accepted sets (fclu_round_readout) --------------------------------------------------------
+// Every refusal is the host's, before any launch: the kernels get sets that are inside their problems, and clamp what they read all the same.
+int readout_device(fclu_ctx *c, const int64_t *sel_off, const int32_t *sel) {
+    c->have_readout = false;
+    c->oexon_ms = c->ocorr_ms = 0.f;
+    c->paths[FCLU_PATH_READOUT_SETS] = c->paths[FCLU_PATH_READOUT_MEMBERS] = c->paths[FCLU_PATH_READOUT_STORES] = 0;
+    if (!c->have_rounds || !c->round_ready || !c->round_src_ok || !c->have_parts)
+        return fail(c, FCLU_ERR_ARG, "fclu_round_readout: no successful fclu_round_models() stands behind the call (none was made, it failed, or a later "
+                                     "call ended the rounds' source)");
+    const fclu_rounds &o = c->rounds;
+    const int P = o.n_prob;
+    if ((int)c->r_probs.size() != P || c->r_lab_off.size() != c->r_n_seg.size() + 1) return fail(c, FCLU_ERR_ARG, "fclu_round_readout: the round's problems are gone");
+    if (!sel_off) return fail(c, FCLU_ERR_ARG, "fclu_round_readout: sel_off is null");
+    if (sel_off[0] != 0) return fail(c, FCLU_ERR_ARG, "fclu_round_readout: sel_off starts at 0");
+    auto &D = c->od;
+    auto &H = c->oh;
+    const size_t P1 = (size_t)P + 1;
+    for (HostBuf<int64_t> *h : {&H.exon_off, &H.mem_off, &H.corr_off, &H.e_off}) HIP_TRY(c, h->grow(P1));
+    std::vector<ReadoutProb> probs;
+    i64 n_exon = 0, n_corr = 0, n_e = 0, n_slots = 0;
+    bool wide = false, narrow = false;
+    for (int p = 0; p < P; ++p) {
+        const i64 m0 = sel_off[p], n = sel_off[p + 1] - m0;
+        H.exon_off.p[p] = n_exon; H.mem_off.p[p] = m0; H.corr_off.p[p] = n_corr; H.e_off.p[p] = n_e;
+        if (n < 0 || sel_off[p + 1] > 2147483647ll) return fail(c, FCLU_ERR_ARG, "problem %d: sel_off falls or is too large", p);
+        if (n == 0) continue;
+        if (!sel) return fail(c, FCLU_ERR_ARG, "fclu_round_readout: sel is null");
+        const RoundProb &rp = c->r_probs[(size_t)p];
+        if (o.refused[p] >= 0)
+            return fail(c, FCLU_ERR_ARG, "problem %d: a set for a refused problem (column %d has a gap that ends on an uninformative segment: no model)", p, (int)o.refused[p]);
+        int prev = -1;
+        for (i64 x = 0; x < n; ++x) {
+            const int col = sel[m0 + x];
+            if (col < 0 || col >= rp.n) return fail(c, FCLU_ERR_ARG, "problem %d: column %d is outside the problem's %d columns", p, col, rp.n);
+            if (col <= prev) return fail(c, FCLU_ERR_ARG, "problem %d: column %d follows column %d; a set is strictly ascending", p, col, prev);
+            prev = col;
+        }
+        const i64 n_inf = o.inf_off[p + 1] - o.inf_off[p];
+        if (n_inf < 0 || n_inf > rp.n_seg || rp.w > kMaxWords) return fail(c, FCLU_ERR_HIP, "problem %d: the round's offsets are out of range", p);
+        ReadoutProb d;
+        d.col0 = rp.col0; d.rbits_off = rp.rbits_off; d.lab_off = c->r_lab_off[(size_t)rp.tint]; d.inf_off = rp.inf_off; d.sel0 = m0;
+        d.exon0 = n_exon; d.corr0 = n_corr; d.e0 = n_e; d.slot0 = n_slots;
+        d.n = rp.n; d.n_sel = (int)n; d.n_seg = rp.n_seg; d.w = rp.w; d.lw = std::max((rp.n_seg + 15) / 16, 1);
+        d.n_reps = (int)(c->r_rep_off[(size_t)rp.tint + 1] - c->r_rep_off[(size_t)rp.tint]); d.n_e = (int)n_inf;
+        d.g_log2 = 0; while (d.g_log2 < 6 && (1 << d.g_log2) < d.w) ++d.g_log2;
+        probs.push_back(d);
+        // The census' store word is the host's prediction from the rows' addresses, not a report of the kernel's: ro_store_halves' rule
+        // restated (a word's address is its row's plus a multiple of 32, so a row is aligned or not as a whole).
+        for (i64 x = 0; x < n; ++x) {
+            const bool aligned = ((n_corr + x * rp.n_seg) & 15) == 0;
+            wide = wide || (aligned && rp.n_seg >= 16);
+            narrow = narrow || (rp.n_seg > 0 && (!aligned || (rp.n_seg & 15)));
+        }
+        n_exon += rp.n_seg; n_corr += n * (i64)rp.n_seg; n_e += n_inf;
+        n_slots += ((n << d.g_log2) + 63) / 64 * 64;
+    }
+    const i64 n_mem = sel_off[P];
+    H.exon_off.p[P] = n_exon; H.mem_off.p[P] = n_mem; H.corr_off.p[P] = n_corr; H.e_off.p[P] = n_e;
+    const size_t nS = probs.size();
+    HIP_TRY(c, H.exons.grow((size_t)n_exon)); HIP_TRY(c, H.corr.grow((size_t)n_corr)); HIP_TRY(c, H.e.grow((size_t)n_e));
+    if (nS) {
+        HIP_TRY(c, hipSetDevice(c->device));
+        hipStream_t s = c->stream;
+        const i64 n_words = o.inf_bits_off[P];
+        HIP_TRY(c, D.probs.grow(nS)); HIP_TRY(c, D.sel.grow((size_t)n_mem)); HIP_TRY(c, D.ex_bits.grow((size_t)n_words));
+        HIP_TRY(c, D.exons.grow((size_t)n_exon)); HIP_TRY(c, D.corr.grow((size_t)n_corr)); HIP_TRY(c, D.e.grow((size_t)n_e));
+        HIP_TRY(c, hipMemcpyAsync(D.probs.p, probs.data(), D.probs.bytes(nS), hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipMemcpyAsync(D.sel.p, sel, D.sel.bytes((size_t)n_mem), hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipEventRecord(c->oev[0], s));
+        hipLaunchKernelGGL(k_readout_exons, dim3((unsigned)nS), dim3(256), 0, s, D.probs.p, c->rd.rids.p, D.sel.p, c->pd.ibits.p, c->rd.inf_bits.p, D.ex_bits.p, D.exons.p,
+                           D.e.p);
+        HIP_TRY(c, hipEventRecord(c->oev[1], s));
+        hipLaunchKernelGGL(k_readout_corr, dim3((unsigned)std::min<i64>((n_slots + 255) / 256, 65536)), dim3(256), 0, s, (int)nS, n_slots, D.probs.p, c->rd.rids.p, D.sel.p,
+                           c->pd.labels.p, c->pd.cbits.p, c->rd.inf_bits.p, D.ex_bits.p, D.corr.p);
+        HIP_TRY(c, hipEventRecord(c->oev[2], s));
+        if (n_exon) HIP_TRY(c, hipMemcpyAsync(H.exons.p, D.exons.p, (size_t)n_exon, hipMemcpyDeviceToHost, s));
+        if (n_corr) HIP_TRY(c, hipMemcpyAsync(H.corr.p, D.corr.p, (size_t)n_corr, hipMemcpyDeviceToHost, s));
+        if (n_e) HIP_TRY(c, hipMemcpyAsync(H.e.p, D.e.p, (size_t)n_e, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipStreamSynchronize(s));
+        HIP_TRY(c, hipGetLastError());
+        (void)hipEventElapsedTime(&c->oexon_ms, c->oev[0], c->oev[1]);
+        (void)hipEventElapsedTime(&c->ocorr_ms, c->oev[1], c->oev[2]);
+    }
+    fclu_readout &r = c->readout;
+    r.n_prob = P; r.n_sets = (int64_t)nS; r.n_mem = n_mem; r.n_exon_bytes = n_exon; r.n_corr_bytes = n_corr; r.n_e = n_e;
+    r.exon_off = H.exon_off.p; r.mem_off = H.mem_off.p; r.corr_off = H.corr_off.p; r.e_off = H.e_off.p;
+    r.exons = H.exons.p; r.corr = H.corr.p; r.e = H.e.p;
+    c->paths[FCLU_PATH_READOUT_SETS] = (int32_t)nS; c->paths[FCLU_PATH_READOUT_MEMBERS] = (int32_t)n_mem;
+    c->paths[FCLU_PATH_READOUT_STORES] = (wide ? FCLU_STORE_WIDE : 0) | (narrow ? FCLU_STORE_BYTES : 0);
+    c->have_readout = true;
+    return FCLU_OK;
+}
+
 }  // namespace
 
 // ---- the C ABI ------------------------------------------------------------------------------------------------------------
@@ -3456,12 +3666,16 @@ int fclu_round_setup(fclu_ctx *c, const int64_t *gap_off, const int32_t *gaps, c
     return c ? round_setup(c, gap_off, gaps, seg_off, seg_len) : FCLU_ERR_ARG;
 }
 
-int fclu_round_models(fclu_ctx *c, const fclu_round_batch *b) { return c ? round_device(c, read_knobs(), b) : FCLU_ERR_ARG; }
+int fclu_round_models(fclu_ctx *c, const fclu_round_batch *b) { return c ? round_device(c, read_knobs(), b, false) : FCLU_ERR_ARG; }
+
+int fclu_round_models_resident(fclu_ctx *c, const fclu_round_batch *b) { return c ? round_device(c, read_knobs(), b, true) : FCLU_ERR_ARG; }
 
 int fclu_round_results(fclu_ctx *c, fclu_rounds *out) {
     if (!c || !out) return FCLU_ERR_ARG;
     if (!c->have_rounds) return fail(c, FCLU_ERR_ARG, "fclu_round_results: no result (the last fclu_round_models call failed or none was made)");
     *out = c->rounds;
+    if (c->rounds_resident)                                  // (the library keeps these four for its own later calls; the model they index is not here)
+        out->inf_off = out->pair_off = out->grp_off = out->row_off = nullptr;
     return FCLU_OK;
 }
 
@@ -3525,6 +3739,18 @@ int fclu_round_bnb_timing(fclu_ctx *c, float *prep_ms, float *search_ms, float *
     if (longest_launch_ms) *longest_launch_ms = c->blongest_ms;
     return two_times(prep_ms, c->bprep_ms, search_ms, c->bsearch_ms);
 }
+
+int fclu_round_readout(fclu_ctx *c, const int64_t *sel_off, const int32_t *sel) { return c ? readout_device(c, sel_off, sel) : FCLU_ERR_ARG; }
+
+int fclu_round_readout_results(fclu_ctx *c, fclu_readout *out) {
+    if (!c || !out) return FCLU_ERR_ARG;
+    if (!c->have_readout || !c->have_rounds)
+        return fail(c, FCLU_ERR_ARG, "fclu_round_readout_results: no result (the last fclu_round_readout call failed, none was made, or a later call ended it)");
+    *out = c->readout;
+    return FCLU_OK;
+}
+
+int fclu_round_readout_timing(fclu_ctx *c, float *exons_ms, float *corr_ms) { return c ? two_times(exons_ms, c->oexon_ms, corr_ms, c->ocorr_ms) : FCLU_ERR_ARG; }
 
 }  // extern "C"
 

@@ -17,8 +17,10 @@
  * (read_segment()'s read_reps, :154-164) on the device.  garbage_cost (from the members' counts) and the gaps dicts are host code.
  * The ILP's solve is not here; what run_ilp() builds its model from is: fclu_round_models() (at the end of this header) gives round r of
  * many partitions as flat arrays, from the rows and pair lists the calls above left on the device.  Problems of at most 24 columns need no
- * ILP: fclu_round_exact() enumerates their column sets and returns the proven optimum, and fclu_round_bnb() (the last section) searches
- * problems of up to 64 columns by branch and bound.
+ * ILP: fclu_round_exact() enumerates their column sets and returns the proven optimum, and fclu_round_bnb() searches problems of up to 64
+ * columns by branch and bound.  A round whose problems are answered there needs no model on the host: fclu_round_models_resident() leaves
+ * the models on the device, and fclu_round_readout() (the last section) turns the accepted column sets into the round's isoforms -- exon
+ * rows and the members' correction strings -- from the rows the context holds.
  *
  * Data layout (caller-owned host arrays, copied by the call):
  *   tint t owns the unique reads row_off[t] .. row_off[t+1]  (N_t of them; "unique" = py/freddie_cluster.py:207-215)
@@ -88,10 +90,17 @@ enum {
     FCLU_PATH_EDGE_CHUNKS = 4,      /* k_prune_edges: 64-word chunks of the longest adjacency row it takes; 0 otherwise */
     FCLU_PATH_PASSES_ENQUEUED = 5,  /* per-pass launches enqueued (whole bursts) */
     FCLU_PATH_PASSES_RAN = 6,       /* of those, the passes that ran: up to and with the first that removed nothing */
-    FCLU_N_PATHS = 7
+    /* the read-out's words: those of the last fclu_round_readout() call (zero behind a refused one, and behind a later graph call) */
+    FCLU_PATH_READOUT_SETS = 7,     /* problems with a set: the workgroups of k_readout_exons */
+    FCLU_PATH_READOUT_MEMBERS = 8,  /* members over all sets: the rows k_readout_corr wrote */
+    FCLU_PATH_READOUT_STORES = 9,   /* FCLU_STORE_WIDE: some lane stores 16 bytes at once; FCLU_STORE_BYTES: some byte is stored alone -- as the host
+                                       predicts it from the rows' addresses by the kernel's rule (clu_readout.h, ro_store_halves); the kernel reports
+                                       nothing, so the word says which paths the batch calls for, not that they ran */
+    FCLU_N_PATHS = 10
 };
 enum { FCLU_FORM_RANK = 1, FCLU_FORM_MASKED = 2 };
 enum { FCLU_PASS_EDGE_WALK = 1, FCLU_PASS_OR_OF_ROWS = 2 };
+enum { FCLU_STORE_WIDE = 1, FCLU_STORE_BYTES = 2 };
 int fclu_last_paths(fclu_ctx *c, int32_t *out, int32_t n);
 
 /* ---- the rest of partition_reads(): components, even split, members and incompatible pairs (:256-274) ----
@@ -276,6 +285,12 @@ typedef struct fclu_rounds {
  * next call.  The partition and preprocess results stay valid behind a round call. */
 int fclu_round_results(fclu_ctx *c, fclu_rounds *out);
 
+/* The same call with the models left on the device: the same kernels and the same device arrays, so that fclu_round_incumbents(),
+ * fclu_round_exact(), fclu_round_bnb() and fclu_round_readout() run behind it unchanged, and only the small per-problem arrays come to the
+ * host.  fclu_round_results() behind it fills n_prob, the counts, refused, col_off, inf_bits_off and inf_bits and leaves every other pointer
+ * null.  Refusals as fclu_round_models'. */
+int fclu_round_models_resident(fclu_ctx *c, const fclu_round_batch *b);
+
 /* Kernel time of the last fclu_round_models() from HIP events (ms): column reduction, informative rows and counts with their scan; the
  * gap groups (keys, sort, groups); the fills. */
 int fclu_round_timing(fclu_ctx *c, float *count_ms, float *gaps_ms, float *fill_ms);
@@ -398,6 +413,41 @@ int fclu_round_bnb_results(fclu_ctx *c, fclu_bnb *out);
 
 /* Kernel time of the last fclu_round_bnb() from HIP events (ms): the tables; all search launches; the longest of them. */
 int fclu_round_bnb_timing(fclu_ctx *c, float *prep_ms, float *search_ms, float *longest_launch_ms);
+
+/* ---- the read-out of a round: run_ilp()'s isoform (:601-635) of every problem with an accepted column set, on the device ----
+ * The batch is that of the context's last successful fclu_round_models() / fclu_round_models_resident().  Problem p's accepted columns are
+ * sel[sel_off[p] .. sel_off[p + 1]), ascending; an empty range means "no isoform this round" and gives empty outputs.  Any number of
+ * columns: the sets are lists, so a solver's answer goes through the same call as a mask of fclu_round_exact / fclu_round_bnb.
+ * Per problem with a set, M_t = the tint's segments:
+ *   exons  M_t bytes 0 / 1: on an informative segment the OR of the members' I bits, elsewhere the I bit of column 0 of the problem (the
+ *          first remaining rep, member or not)
+ *   corr   M_t ASCII bytes per member, in set order: '-' on an uninformative segment, 'X' where the member's C bit and the exon bit are 1,
+ *          otherwise the label '0', '1' or '2' of the rep's row (its first read's)
+ *   e      the exon values at the problem's informative segments, ascending (what a solver returns beside x)
+ * The definition is freddie_amd/cluster.py read_out(); what a lane computes is freddie_amd/csrc/clu_readout.h.
+ * FCLU_ERR_ARG, naming problem and column: a column outside the problem, a set that is not strictly ascending, a set for a refused problem,
+ * sel_off that does not start at 0 or falls, no such round behind the call.  Every refusal is made before a kernel is launched; the context
+ * stays usable, and the round's results stay valid behind the call. */
+int fclu_round_readout(fclu_ctx *c, const int64_t *sel_off, const int32_t *sel);
+
+typedef struct fclu_readout {
+    int32_t n_prob;
+    int64_t n_sets, n_mem, n_exon_bytes, n_corr_bytes, n_e;   /* problems with a set, members, lengths of exons, corr and e */
+    const int64_t *exon_off;       /* n_prob + 1, bytes: problem p's exon row (M_t bytes, or none) */
+    const uint8_t *exons;
+    const int64_t *mem_off;        /* n_prob + 1: = sel_off */
+    const int64_t *corr_off;       /* n_prob + 1, bytes: member k of problem p has its row at corr_off[p] + k * M_t */
+    const uint8_t *corr;
+    const int64_t *e_off;          /* n_prob + 1 */
+    const uint8_t *e;
+} fclu_readout;
+
+/* Result of the last successful fclu_round_readout(): pointers into pinned host buffers the context owns, valid until the context's next
+ * call. */
+int fclu_round_readout_results(fclu_ctx *c, fclu_readout *out);
+
+/* Kernel time of the last fclu_round_readout() from HIP events (ms): the exon rows with e; the corrections. */
+int fclu_round_readout_timing(fclu_ctx *c, float *exons_ms, float *corr_ms);
 
 #ifdef __cplusplus
 }

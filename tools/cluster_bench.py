@@ -25,6 +25,12 @@ synthetic preprocessed tints through include/freddie_cluster.h.
                         the reference does it, the kernels' event times, and -- apart -- what HiGHS takes on the same round; the
                         result also goes to profiles/cluster_rounds.txt)
 
+    python tools/cluster_bench.py --device-rounds [--sizes 24,64,1000] [--runs K] [--threads N] [--max-rounds R] [--tints N] [--out FILE] [--append]
+                       (per maximum_ilp_size: the whole cluster_tints loop under --exact-small 24 --exact-bnb 64 with N solver workers, with
+                        device_rounds off and on in turn, K runs each: wall time in total and per round, bytes copied to numpy, round_model()
+                        builds, solver jobs, the read-out's kernel time, and whether both settings left the same tints;
+                        profiles/cluster_device_rounds.txt)
+
 One JSON line: read pairs tested per second of the CALL (packed host arrays in -> pruned adjacency in host memory: copies,
 kernels and the pruning loop's host round trips all inside), the kernel times as detail, and the bound of the compatibility
 kernel.  That kernel works on bit rows staged in LDS, so bytes do not describe it (a byte roofline credited it with more
@@ -228,10 +234,12 @@ def run_front(workload="many", steps=5, maximum_ilp_size=1000, dup=0.1):
     }
 
 
-def write_segment_files(workload, directory, seed=7):
+def write_segment_files(workload, directory, seed=7, gaps=True):
     """The workload as segment_<contig>_<tint>.tsv files, a tint a file: rows are noisy sub-ranges of a few isoform patterns (as
     cluster_util.random_tint draws them), a fifth of the zeros written as 2, every structure written as one to three reads whose 2s
-    and small gaps differ (so they share a rep), one internal gap a read and a poly tail on a quarter of them."""
+    and small gaps differ (so they share a rep), one internal gap a read and a poly tail on a quarter of them.  gaps=False: the same
+    reads without gaps and tails (the random draws are the same), for a loop that must reach its end: with them some first-round problem
+    has a gap that ends on an uninformative segment, where the reference asserts and the loop raises."""
     w = WORKLOADS[workload]
     M, n = w["n_segs"], w["n_reps"]
     rng = np.random.default_rng(seed)
@@ -252,10 +260,10 @@ def write_segment_files(workload, directory, seed=7):
             text = np.where(rows[idx], 49, np.where(rng.random((len(idx), M)) < 0.2, 50, 48)).astype(np.uint8)
             small = rng.integers(0, 11, len(idx))
             for k, i in enumerate(idx.tolist()):
-                gaps = "%d-%d:%d," % (g1[i], g1[i] + 1, l1[i] if l1[i] > 10 else small[k])
+                gap_text = "%d-%d:%d," % (g1[i], g1[i] + 1, l1[i] if l1[i] > 10 else small[k])
                 if poly[i] < 4:
-                    gaps += "%s_%d:%d," % (("SA", "ST", "EA", "ET")[poly[i]], 8 + 3 * (i % 5), (i % 3) * 9)
-                lines.append("%d\tread%d_%d\tctg%d\t%s\t%d\t%s\t%s\n" % (rid, i, c, t % 7, "+-"[i & 1], t, text[k].tobytes().decode(), gaps))
+                    gap_text += "%s_%d:%d," % (("SA", "ST", "EA", "ET")[poly[i]], 8 + 3 * (i % 5), (i % 3) * 9)
+                lines.append("%d\tread%d_%d\tctg%d\t%s\t%d\t%s\t%s\n" % (rid, i, c, t % 7, "+-"[i & 1], t, text[k].tobytes().decode(), gap_text if gaps else ""))
                 rid += 1
         n_reads += rid
         path = os.path.join(directory, "segment_ctg%d_%d.tsv" % (t % 7, t))
@@ -738,6 +746,117 @@ def run_bnb(workload="many", steps=3, sizes=(32, 48, 64), min_cols=25, max_nodes
     }
 
 
+class _RoundClock:
+    """A context that notes when each round starts (its first round_models call) and what the read-out's kernels took."""
+
+    def __init__(self, ctx, device):
+        self.ctx, self.device, self.marks, self.readout_ms, self.calls, self.bytes = ctx, device, [], [], dict(models=0, readout=0), 0
+
+    def __getattr__(self, name):
+        return getattr(self.ctx, name)
+
+    def round_models(self, parts, remaining, fetch=True):
+        if not (self.device and fetch):
+            self.marks.append(time.perf_counter())
+            print("  round %d: %d problems" % (len(self.marks) - 1, len(parts)), file=sys.stderr, flush=True)
+        self.calls["models"] += 1
+        return self._count(self.ctx.round_models(parts, remaining, fetch) if self.device else self.ctx.round_models(parts, remaining))
+
+    def _count(self, arrays):
+        self.bytes += sum(a.nbytes for a in arrays.values() if isinstance(a, np.ndarray))
+        return arrays
+
+    def round_incumbents(self, *args, **kw):
+        return self._count(self.ctx.round_incumbents(*args, **kw))
+
+    def round_exact(self, *args, **kw):
+        return self._count(self.ctx.round_exact(*args, **kw))
+
+    def round_bnb(self, *args, **kw):
+        return self._count(self.ctx.round_bnb(*args, **kw))
+
+    def round_readout(self, sets):
+        out = self._count(self.ctx.round_readout(sets))
+        self.calls["readout"] += 1
+        self.readout_ms.append(sum(self.ctx.round_readout_timing().values()))
+        return out
+
+
+def run_device_rounds(workload="many", sizes=(24, 64, 1000), runs=3, threads=16, max_rounds=30, exact_cols=24, bnb_cols=64, n_tints=None):
+    """The workload's segment_*.tsv files staged afresh for every run (cluster.stage_files, timed apart), then the whole cluster_tints()
+    loop to its end under exact_cols / bnb_cols with `threads` solver workers, device_rounds off and on in turn, `runs` times each.  The
+    yardstick is the flag-off run: the same binary on the path the flag leaves alone.  n_tints: the workload's first so many files only."""
+    import hashlib
+    import tempfile
+    from multiprocessing import Pool
+    from freddie_amd import cluster
+    pool = Pool(threads)                                      # before the GPU is opened: the workers never touch it
+    rows = []
+    try:
+        with tempfile.TemporaryDirectory() as d:
+            paths, n_reads = write_segment_files(workload, d, gaps=False)
+            paths = paths[:n_tints] if n_tints else paths
+            ctx = cluster_prep.Context(0)
+            for size in sizes:
+                per = {False: [], True: []}
+                for run_no in range(runs):
+                    for flag in (False, True):
+                        settings = cluster.ilp_settings(max_ilp=size, max_rounds=max_rounds, exact_cols=exact_cols, bnb_cols=bnb_cols, device_rounds=flag)
+                        t0 = time.perf_counter()
+                        tints, part0, _ = cluster.stage_files(paths, settings, ctx, threads)
+                        stage_s = time.perf_counter() - t0
+                        clock, built, jobs = _RoundClock(ctx, flag), [0], [0]
+
+                        def counting(arr, p):
+                            built[0] += 1
+                            return cluster_prep.round_model(arr, p)
+
+                        class CountingPool:
+                            def map(self, fn, items, chunksize=1):
+                                jobs[0] += len(items)
+                                return pool.map(fn, items, chunksize=chunksize)
+
+                        t0 = time.perf_counter()
+                        logs = cluster.cluster_tints(tints, part0, clock, settings, pool=CountingPool(), round_model=counting)
+                        t1 = time.perf_counter()
+                        marks = clock.marks + [t1]
+                        digest = hashlib.sha256(repr([(t["id"], t["isoforms"], t["garbage_rids"]) for t in tints]).encode() + repr(logs).encode()).hexdigest()[:16]
+                        per[flag].append(dict(total_s=t1 - t0, stage_files_s=stage_s, rounds=len(clock.marks), round_s=[b - a for a, b in zip(marks[:-1], marks[1:])],
+                                              round_models_calls=clock.calls["models"], round_readout_calls=clock.calls["readout"],
+                                              bytes_copied=clock.bytes, round_model_builds=built[0], solver_jobs=jobs[0],
+                                              problem_rounds=sum(len(l) for l in logs), isoforms=sum(len(t["isoforms"]) for t in tints),
+                                              readout_kernel_ms=float(sum(clock.readout_ms)), readout_kernel_ms_longest=max(clock.readout_ms or [0.0]),
+                                              digest=digest))
+                        print("max_ilp %d run %d device_rounds=%s: %.2f s, %d rounds, %d builds, %d solver jobs" %
+                              (size, run_no, flag, t1 - t0, len(clock.marks), built[0], jobs[0]), file=sys.stderr, flush=True)
+                        del tints
+                summary = {}
+                for flag in (False, True):
+                    tot = [r["total_s"] for r in per[flag]]
+                    summary["on" if flag else "off"] = dict(
+                        total_s_median=float(np.median(tot)), total_s_range=[min(tot), max(tot)], runs=per[flag],
+                        round_s_median=[float(np.median(x)) for x in zip(*[r["round_s"] for r in per[flag]])] if len(set(r["rounds"] for r in per[flag])) == 1 else None,
+                        bytes_copied_per_round=float(np.median([r["bytes_copied"] / max(r["rounds"], 1) for r in per[flag]])))
+                off, on = summary["off"], summary["on"]
+                spread = max(off["total_s_range"][1] - off["total_s_range"][0], on["total_s_range"][1] - on["total_s_range"][0])
+                rows.append(dict(maximum_ilp_size=size, off=off, on=on, saved_s=off["total_s_median"] - on["total_s_median"], run_to_run_range_s=spread,
+                                 faster_by_more_than_the_range=bool(off["total_s_median"] - on["total_s_median"] > spread),
+                                 same_tints_and_logs=bool(len(set(r["digest"] for f in (False, True) for r in per[f])) == 1)))
+            ctx.close()
+    finally:
+        pool.close()
+        pool.join()
+    return {
+        "metric": "the whole cluster_tints loop with device_rounds off (the yardstick: the unchanged path of the same binary) and on", "unit": "s",
+        "data": "synthetic", "source_hash": _build_hash(),
+        "config": {"workload": "cluster-" + workload, **WORKLOADS[workload], "files_taken": len(paths), "reads_written": n_reads, "exact_cols": exact_cols, "bnb_cols": bnb_cols, "solver_workers": threads,
+                   "max_rounds": max_rounds, "runs": runs,
+                   "gaps": "left out (write_segment_files(gaps=False)): with them the first round holds problems the reference asserts on, and the loop raises",
+                   "order": "off, on, off, on, ...: every run stages the files afresh; the first run of a size grows the buffers"},
+        "sizes": rows,
+    }
+
+
 def _build_hash():
     from freddie_amd import build as _b
     return _b.embedded_hash(cluster_prep.CLUSTER_SO)
@@ -768,8 +887,24 @@ def main():
     ap.add_argument("--bnb-depth", type=int, default=None, help="--bnb: columns the task number fixes (default: cluster_solve.BNB_DEPTH)")
     ap.add_argument("--bnb-node-cap", type=int, default=None, help="--bnb: nodes a task may count (default: cluster_solve.BNB_NODE_CAP)")
     ap.add_argument("--weak-budget", type=float, default=90.0, help="--bnb: seconds of the weak-bound mirror on the sample")
+    ap.add_argument("--device-rounds", action="store_true", help="measure the whole cluster_tints loop with device_rounds off and on (profiles/cluster_device_rounds.txt)")
+    ap.add_argument("--sizes", default="24,64,1000", help="--device-rounds: the maximum_ilp_size values")
+    ap.add_argument("--runs", type=int, default=3, help="--device-rounds: runs of each setting")
+    ap.add_argument("--max-rounds", type=int, default=30, help="--device-rounds: the loop's max_rounds")
+    ap.add_argument("--tints", type=int, default=None, help="--device-rounds: the workload's first N files only (default: all)")
+    ap.add_argument("--append", action="store_true", help="--device-rounds: add the result to --out instead of replacing it (a size a call, each under its own time limit)")
     args = ap.parse_args()
-    if args.bnb:
+    if args.device_rounds:
+        sizes = tuple(int(v) for v in args.sizes.split(","))
+        res = run_device_rounds(args.workload, sizes, args.runs, args.threads, args.max_rounds, n_tints=args.tints)
+        with open(args.out or os.path.join(ROOT, "profiles", "cluster_device_rounds.txt"), "a" if args.append else "w") as f:
+            f.write("tools/cluster_bench.py --device-rounds --workload %s --sizes %s --runs %d --threads %d --max-rounds %d%s  (libfreddie_cluster.so source hash %s)\n" %
+                    (args.workload, args.sizes, args.runs, args.threads, args.max_rounds, " --tints %d" % args.tints if args.tints else "", res["source_hash"]))
+            f.write(json.dumps(res, indent=1) + "\n")
+        print(json.dumps({k: v for k, v in res.items() if k != "sizes"}))
+        for row in res["sizes"]:
+            print(json.dumps({k: (v if not isinstance(v, dict) else {a: b for a, b in v.items() if a != "runs"}) for k, v in row.items()}))
+    elif args.bnb:
         res = run_bnb(args.workload, args.steps, (args.exact_bnb,) if args.exact_bnb is not None else (32, 48, 64), max_nodes=args.bnb_nodes, depth=args.bnb_depth,
                       node_cap=args.bnb_node_cap, host_sample=16 if args.host_sample == 20 else args.host_sample,
                       solve_budget=args.solve_budget if args.solve_budget != 120.0 else 240.0, weak_budget=args.weak_budget, threads=args.threads)
