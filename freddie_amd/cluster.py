@@ -16,9 +16,11 @@ mask budget is solved there by enumeration, a proven optimum, and only the other
 exact_cols the problems of exact_cols + 1 .. N (<= 64) columns that fit the node budget are searched by a branch and bound on the device
 (Context.round_bnb, behind a round_incumbents call whose costs bound it): a search that finishes is a proven optimum under the
 enumeration's rule and makes no solve job; one that does not hands the solver its best set as an incumbent.  Under
-settings["device_rounds"] (with exact_cols or bnb_cols) the models of a round stay on the device (round_models(fetch=False)); the problems
+settings["device_rounds"] (with exact_cols, bnb_cols or wide_cols) the models of a round stay on the device (round_models(fetch=False)); the problems
 the GPU has answered get their isoforms from one more device call (Context.round_readout) and no model, list or loop of theirs is built
-on the host, and only the other problems are modelled again, alone, for the solver."""
+on the host, and only the other problems are modelled again, alone, for the solver.  Under settings["wide_cols"] = N > max(exact_cols,
+bnb_cols) the problems of more columns than those and at most N (<= 1024) whose tables fit are searched by the same branch and bound on
+sets of several words (Context.round_bnb_wide), and answered exactly as round_bnb's are."""
 import os
 
 import numpy as np
@@ -38,8 +40,12 @@ BNB_NODES = 1 << 30       # the default node budget of a round's branch and boun
                           # (profiles/cluster_bnb.txt)
 
 
+WIDE_NODES = 1 << 30      # the default node budget of a round's wide branch and bound: the sum of tasks x node cap over the problems it takes
+                          # (profiles/cluster_bnb_wide.txt)
+
+
 def ilp_settings(recycle_model="constant", epsilon=0.2, offset=20, timeout=1, max_rounds=30, min_isoform_size=3, max_ilp=1000, incumbent="off",
-                 exact_cols=0, exact_masks=EXACT_MASKS, bnb_cols=0, bnb_nodes=BNB_NODES, device_rounds=False):
+                 exact_cols=0, exact_masks=EXACT_MASKS, bnb_cols=0, bnb_nodes=BNB_NODES, device_rounds=False, wide_cols=0, wide_nodes=WIDE_NODES):
     """incumbent: "off"; "cutoff": every round's greedy incumbents (Context.round_incumbents, one device call a round) bound the solves'
     objective; "fallback": and stand in for a solve that ends without a proven optimum (status INCUMBENT).
     exact_cols: 0, or the largest number of columns (<= 24) of a problem the GPU solves exactly by enumeration (Context.round_exact, one
@@ -48,12 +54,15 @@ def ilp_settings(recycle_model="constant", epsilon=0.2, offset=20, timeout=1, ma
     of exact_cols + 1 .. bnb_cols columns; one more device call a round, two where the incumbents are not computed anyway); bnb_nodes: that
     call's budget, the sum of tasks x node cap over the problems it takes.
     device_rounds: the round's models stay on the device and the problems the GPU has answered are read out there (Context.round_readout);
-    it needs exact_cols or bnb_cols, the calls that answer problems."""
-    if device_rounds and not (exact_cols > 0 or bnb_cols > 0):
-        raise ValueError("device_rounds needs exact_cols or bnb_cols: without them no problem is answered on the device")
+    it needs exact_cols, bnb_cols or wide_cols, the calls that answer problems.
+    wide_cols: 0, or the largest number of columns (<= 1024) of a problem the GPU searches by the branch and bound on sets of several words
+    (Context.round_bnb_wide: the problems of max(exact_cols, bnb_cols) + 1 .. wide_cols columns whose tables fit); wide_nodes: that call's
+    budget, as bnb_nodes."""
+    if device_rounds and not (exact_cols > 0 or bnb_cols > 0 or wide_cols > 0):
+        raise ValueError("device_rounds needs exact_cols, bnb_cols or wide_cols: without them no problem is answered on the device")
     return dict(recycle_model=recycle_model, K=2, epsilon=epsilon, offset=offset, timeout=timeout, max_rounds=max_rounds, threads=1,
                 min_isoform_size=min_isoform_size, max_ilp=max_ilp, incumbent=incumbent, exact_cols=exact_cols, exact_masks=exact_masks,
-                bnb_cols=bnb_cols, bnb_nodes=bnb_nodes, device_rounds=bool(device_rounds))
+                bnb_cols=bnb_cols, bnb_nodes=bnb_nodes, device_rounds=bool(device_rounds), wide_cols=wide_cols, wide_nodes=wide_nodes)
 
 
 def check_exact(settings):
@@ -72,9 +81,17 @@ def check_bnb(settings):
         raise ValueError("bnb_nodes is %r: at least 1" % (nodes,))
 
 
+def check_wide(settings):
+    cols, nodes = settings.get("wide_cols", 0), settings.get("wide_nodes", WIDE_NODES)
+    if not 0 <= cols <= cluster_solve.BNB_WIDE_MAX_COLS:
+        raise ValueError("wide_cols is %r: 0 .. %d" % (cols, cluster_solve.BNB_WIDE_MAX_COLS))
+    if cols and nodes < 1:
+        raise ValueError("wide_nodes is %r: at least 1" % (nodes,))
+
+
 def check_device_rounds(settings):
-    if settings.get("device_rounds", False) and not (settings.get("exact_cols", 0) > 0 or settings.get("bnb_cols", 0) > 0):
-        raise ValueError("device_rounds needs exact_cols or bnb_cols: without them no problem is answered on the device")
+    if settings.get("device_rounds", False) and not (settings.get("exact_cols", 0) > 0 or settings.get("bnb_cols", 0) > 0 or settings.get("wide_cols", 0) > 0):
+        raise ValueError("device_rounds needs exact_cols, bnb_cols or wide_cols: without them no problem is answered on the device")
 
 
 def garbage_costs(tint, recycle_model):
@@ -148,18 +165,20 @@ def _refused_error(tint, s, round_num, column):
                                      "(the reference's assert, py/freddie_cluster.py:467-468)" % (tint["id"], s["q"], round_num, column, s["remaining"][column]))
 
 
-def _gpu_answer(exact, bnb, greedy, p):
+def _gpu_answer(exact, bnb, greedy, p, wide=None):
     """(found, incumbent) of problem p from the round's exact and branch-and-bound calls: found = (cost, x), "infeasible" or None (the
     solver's); incumbent = what an unproven search hands the solver, the better of its best set and the greedy's, or None."""
     found = cluster_prep.round_exact_solution(exact, p) if exact is not None else None
     incumbent = None
     if found is None and bnb is not None:
         found = cluster_prep.round_bnb_solution(bnb, p)
-        if found is not None and found[0] == "unproven":
-            if found[1] is not None:
-                best = cluster_prep.round_incumbent(greedy, p)
-                incumbent = tuple(found[1:]) if best is None or found[1] < best[0] else best
-            found = None
+    if found is None and wide is not None:                   # (a problem is taken by one search at the most: the sizes do not overlap)
+        found = cluster_prep.round_bnb_wide_solution(wide, p)
+    if found is not None and found[0] == "unproven":
+        if found[1] is not None:
+            best = cluster_prep.round_incumbent(greedy, p)
+            incumbent = tuple(found[1:]) if best is None or found[1] < best[0] else best
+        found = None
     return found, incumbent
 
 
@@ -207,6 +226,7 @@ def cluster_tints(tints, part0, ctx, settings, solve=cluster_solve.solve_round, 
     cluster_solve.check_settings(settings)
     check_exact(settings)
     check_bnb(settings)
+    check_wide(settings)
     check_device_rounds(settings)
     device = bool(settings.get("device_rounds", False))
     build_model = round_model if round_model is not None else (lambda arr, p: cluster_prep.round_model(arr, p))
@@ -248,8 +268,16 @@ def cluster_tints(tints, part0, ctx, settings, solve=cluster_solve.solve_round, 
             greedy = inc if inc is not None else ctx.round_incumbents(garbage, settings["epsilon"], settings["offset"])
             bnb = ctx.round_bnb(garbage, greedy["cost2"], settings["epsilon"], settings["offset"], settings.get("exact_cols", 0) + 1, settings["bnb_cols"],
                                 settings.get("bnb_nodes", BNB_NODES))
+        wide = None
+        narrow_cols = max(settings.get("exact_cols", 0), settings.get("bnb_cols", 0))
+        if settings.get("wide_cols", 0) > narrow_cols:       # the same search on sets of several words, for the problems beyond both
+            garbage = [g for s in todo for g in (tints[s["t"]]["garbage_cost"][i] for i in s["remaining"])]
+            if greedy is None:
+                greedy = inc if inc is not None else ctx.round_incumbents(garbage, settings["epsilon"], settings["offset"])
+            wide = ctx.round_bnb_wide(garbage, greedy["cost2"], settings["epsilon"], settings["offset"], narrow_cols + 1, settings["wide_cols"],
+                                      settings.get("wide_nodes", WIDE_NODES))
         # ---- every problem's answer from the device, once; under device rounds the answered ones get no model
-        found = [_gpu_answer(exact, bnb, greedy, p) for p in range(len(todo))]
+        found = [_gpu_answer(exact, bnb, greedy, p, wide) for p in range(len(todo))]
         direct, host, out, source = {}, list(range(len(todo))), None, arr
         if device:
             direct, host, out, source = _device_round(ctx, tints, todo, parts, arr, found, min_size, round_num)
@@ -358,6 +386,14 @@ BNB_HELP = ("Recommended: 64 -- measured on an MI355X (profiles/cluster_bnb.txt)
             "to 64 columns in 0.28 s, where sixteen HiGHS workers take about 21 s.")
 
 
+WIDE_HELP = ("Recommended: 128 -- measured on an MI355X (profiles/cluster_bnb_wide.txt; the first round of the first 40 files of the cluster-many "
+             "workload, written without gaps), a call proves all 160 problems of 120 to 124 columns under -mi 128 in 12 ms, where sixteen HiGHS "
+             "workers take 5.2 s for 16 of them.  Not recommended above 128: under -mi 256 a call proves 4 of 80 problems of about 245 columns "
+             "within 50 ms a launch (64 of 80 with 16 384 nodes a task, 69 ms a launch), and under -mi 1000 none of 40 problems of about 490 "
+             "columns; the best sets found still reach the solver as incumbents.  A task's node cap follows the largest problem of a round "
+             "that N admits (4 096 up to 128 columns, 8 192 up to 256, 4 096 beyond), so a larger N changes the cap of the smaller problems too.")
+
+
 DEVICE_ROUNDS_HELP = ("Recommended together with --exact-small 24 --exact-bnb 64 at small maximum ILP sizes: measured on an MI355X "
                       "(profiles/cluster_device_rounds.txt; the first 40 of the cluster-many workload's 400 files, written without gaps, sixteen "
                       "workers, medians of three runs) the whole loop takes 10.3 s against 26.7 s under -mi 24 and 2.8 s against 18.1 s under "
@@ -405,10 +441,17 @@ def parse_args(argv=None):
     parser.add_argument("--bnb-nodes", type=int, default=BNB_NODES, metavar="M",
                         help="Budget of a round's branch and bound: the sum of tasks x node cap over the problems it takes, smallest first; the "
                              "rest go to the solver.  Default: {}".format(BNB_NODES))
+    parser.add_argument("--exact-wide", type=int, default=0, choices=range(0, cluster_solve.BNB_WIDE_MAX_COLS + 1), metavar="N",
+                        help="Problems of more columns than --exact-small and --exact-bnb and at most N (0 .. {}) whose tables fit the GPU's "
+                             "on-chip memory are searched by the same branch and bound on column sets of several words, a wave a task; answers "
+                             "are handled as --exact-bnb's.  Default: 0 (nothing changes, no extra call).  {}".format(
+                                 cluster_solve.BNB_WIDE_MAX_COLS, WIDE_HELP))
+    parser.add_argument("--wide-nodes", type=int, default=WIDE_NODES, metavar="M",
+                        help="Budget of a round's wide branch and bound, as --bnb-nodes.  Default: {}".format(WIDE_NODES))
     parser.add_argument("--device-rounds", action="store_true",
-                        help="Keep every round's models on the GPU and read the isoforms of the problems --exact-small / --exact-bnb have "
-                             "answered out there; only the other problems are modelled on the host, for the solver.  Needs --exact-small or "
-                             "--exact-bnb.  Default: off (nothing changes).  {}".format(DEVICE_ROUNDS_HELP))
+                        help="Keep every round's models on the GPU and read the isoforms of the problems --exact-small / --exact-bnb / "
+                             "--exact-wide have answered out there; only the other problems are modelled on the host, for the solver.  Needs "
+                             "--exact-small, --exact-bnb or --exact-wide.  Default: off (nothing changes).  {}".format(DEVICE_ROUNDS_HELP))
     parser.add_argument("-t", "--threads", type=int, default=1, help="Number of processes that solve (at most {})".format(MAX_WORKERS))
     parser.add_argument("-l", "--logs-dir", type=str, default=None, help="Directory path where logs will be outputted. Default: No log")
     parser.add_argument("-o", "--outdir", type=str, default="freddie_cluster/", help="Path to output directory. Default: freddie_cluster/")
@@ -424,8 +467,10 @@ def parse_args(argv=None):
         parser.error("--exact-masks must be at least 1")
     if args.bnb_nodes < 1:
         parser.error("--bnb-nodes must be at least 1")
-    if args.device_rounds and not (args.exact_small > 0 or args.exact_bnb > 0):
-        parser.error("--device-rounds needs --exact-small or --exact-bnb: without them no problem is answered on the GPU")
+    if args.wide_nodes < 1:
+        parser.error("--wide-nodes must be at least 1")
+    if args.device_rounds and not (args.exact_small > 0 or args.exact_bnb > 0 or args.exact_wide > 0):
+        parser.error("--device-rounds needs --exact-small, --exact-bnb or --exact-wide: without them no problem is answered on the GPU")
     return args
 
 
@@ -435,7 +480,7 @@ def main(argv=None, make_context=None):
     args = parse_args(argv)
     args.segment_dir = args.segment_dir.rstrip("/")
     settings = ilp_settings(args.recycle_model, args.epsilon, args.gap_offset, args.timeout, args.max_rounds, args.min_isoform_size, args.max_ilp,
-                            args.incumbent, args.exact_small, args.exact_masks, args.exact_bnb, args.bnb_nodes, args.device_rounds)
+                            args.incumbent, args.exact_small, args.exact_masks, args.exact_bnb, args.bnb_nodes, args.device_rounds, args.exact_wide, args.wide_nodes)
     cluster_solve.check_settings(settings)
     jobs = []
     for contig in os.listdir(args.segment_dir):

@@ -159,7 +159,7 @@ def split_list_evenly(l, m):
 # ---------------------------------------------------------------------------------------------------------------
 CLUSTER_SO = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libfreddie_cluster.so")
 CLUSTER_SRC = [os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "freddie_cluster.hip")]
-CLUSTER_HEADERS = [os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", n) for n in ("clu_incumbent.h", "clu_exact.h", "clu_bnb.h", "clu_readout.h")]
+CLUSTER_HEADERS = [os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", n) for n in ("clu_incumbent.h", "clu_exact.h", "clu_bnb.h", "clu_bnb_wide.h", "clu_readout.h")]
 EXPORTS = ["fclu_abi_version", "fclu_create", "fclu_destroy", "fclu_last_error", "fclu_compat_graph", "fclu_last_timing",
            "fclu_last_paths",
            "fclu_partition", "fclu_partition_adj", "fclu_partition_results", "fclu_partition_timing",
@@ -169,6 +169,7 @@ EXPORTS = ["fclu_abi_version", "fclu_create", "fclu_destroy", "fclu_last_error",
            "fclu_round_incumbents", "fclu_round_incumbent_results", "fclu_round_incumbent_timing",
            "fclu_round_exact", "fclu_round_exact_results", "fclu_round_exact_timing",
            "fclu_round_bnb", "fclu_round_bnb_results", "fclu_round_bnb_timing",
+           "fclu_round_bnb_wide", "fclu_round_bnb_wide_results", "fclu_round_bnb_wide_timing",
            "fclu_round_models_resident", "fclu_round_readout", "fclu_round_readout_results", "fclu_round_readout_timing"]
 ERR_UNSUPPORTED = 3
 _lib = None
@@ -338,6 +339,12 @@ def load():
     L.fclu_round_bnb_results.argtypes = [vp, ctypes.POINTER(_Bnb)]
     L.fclu_round_bnb_timing.restype = ctypes.c_int
     L.fclu_round_bnb_timing.argtypes = [vp] + [ctypes.POINTER(ctypes.c_float)] * 3
+    L.fclu_round_bnb_wide.restype = ctypes.c_int
+    L.fclu_round_bnb_wide.argtypes = [vp, vp, vp, ctypes.c_double, ctypes.c_double] + [ctypes.c_int32] * 5 + [ctypes.c_int64]
+    L.fclu_round_bnb_wide_results.restype = ctypes.c_int
+    L.fclu_round_bnb_wide_results.argtypes = [vp, ctypes.POINTER(_Bnb)]
+    L.fclu_round_bnb_wide_timing.restype = ctypes.c_int
+    L.fclu_round_bnb_wide_timing.argtypes = [vp] + [ctypes.POINTER(ctypes.c_float)] * 3
     L.fclu_round_models_resident.restype = ctypes.c_int
     L.fclu_round_models_resident.argtypes = [vp, ctypes.POINTER(_RoundBatch)]
     L.fclu_round_readout.restype = ctypes.c_int
@@ -675,6 +682,40 @@ class Context:
         self._L.fclu_round_bnb_timing(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(f))
         return dict(prep_ms=a.value, search_ms=b.value, longest_launch_ms=f.value)
 
+    def round_bnb_wide(self, garbage, ub2, epsilon, offset, min_cols, max_cols, max_nodes, depth=None, node_cap=None):
+        """round_bnb() for the problems of min_cols .. max_cols (<= 1024) columns whose tables fit (bnb_wide_lds_bytes), one device call
+        (include/freddie_cluster.h, fclu_bnb_wide; the definition is cluster_solve.exact_bnb_wide()).  depth None = cluster_solve.BNB_DEPTH;
+        node_cap None = cluster_solve.bnb_wide_node_cap(R) of the round's largest problem of min_cols .. max_cols columns (a call has one
+        cap: the measured defaults are per size, and the largest problem is the one that decides a launch's time).  Returns round_bnb()'s dict with mask as a (problems, 16) uint64 array,
+        low word first, and the depth and node_cap used; round_bnb_wide_solution() cuts one problem out."""
+        depth = cluster_solve.BNB_DEPTH if depth is None else depth
+        g2, col_off = self._garbage2("round_bnb_wide", garbage)
+        if node_cap is None:
+            cols = np.diff(col_off)
+            cols = cols[(cols >= int(min_cols)) & (cols <= int(max_cols))]
+            node_cap = cluster_solve.bnb_wide_node_cap(int(cols.max()) if cols.size else int(max_cols))
+        ub = np.ascontiguousarray(np.asarray(ub2, np.int64).reshape(-1))
+        if ub.size != col_off.size - 1:
+            raise ClusterError("round_bnb_wide: %d bounds for the %d problems of the last round_models() call" % (ub.size, col_off.size - 1))
+        rc = self._L.fclu_round_bnb_wide(self._h, g2.ctypes.data if g2.size else None, ub.ctypes.data if ub.size else None, 1.0 - float(epsilon),
+                                         1.0 + float(epsilon), int(offset), int(min_cols), int(max_cols), int(depth), int(node_cap), int(max_nodes))
+        if rc != 0:
+            raise ClusterError("fclu_round_bnb_wide: " + self._L.fclu_last_error(self._h).decode(), rc)
+        b = _Bnb()                                           # (fclu_bnb_wide has fclu_bnb's layout; its mask holds 16 words a problem)
+        rc = self._L.fclu_round_bnb_wide_results(self._h, ctypes.byref(b))
+        if rc != 0:
+            raise ClusterError("fclu_round_bnb_wide_results: " + self._L.fclu_last_error(self._h).decode(), rc)
+        P = b.n_prob
+        return dict(n_prob=P, col_off=col_off, status=_copy_out(b.status, P, np.int32), cost2=_copy_out(b.cost2, P, np.int64),
+                    mask=_copy_out(b.mask, P * BNB_WIDE_WORDS, np.uint64).reshape(P, BNB_WIDE_WORDS), nodes=_copy_out(b.nodes, P, np.int64),
+                    capped=_copy_out(b.capped, P, np.int32), n_taken=int(b.n_taken), n_launches=int(b.n_launches), nodes_total=int(b.nodes_total),
+                    depth=int(depth), node_cap=int(node_cap))
+
+    def round_bnb_wide_timing(self):
+        a, b, f = ctypes.c_float(), ctypes.c_float(), ctypes.c_float()
+        self._L.fclu_round_bnb_wide_timing(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(f))
+        return dict(prep_ms=a.value, search_ms=b.value, longest_launch_ms=f.value)
+
     def round_readout(self, sets):
         """The isoforms of the last round_models() call's problems (either form) from their accepted column sets, one device call
         (include/freddie_cluster.h, fclu_readout; the definition is cluster.read_out()): sets = per problem the accepted columns, ascending,
@@ -936,6 +977,33 @@ def round_bnb_solution(arr, p):
     if status is None or status == "infeasible":
         return status
     cost2, mask = int(arr["cost2"][p]), int(arr["mask"][p])
+    found = (cost2 / 2.0, [mask >> c & 1 for c in range(int(arr["col_off"][p + 1] - arr["col_off"][p]))]) if cost2 >= 0 else (None, None)
+    return found if status == "optimal" else ("unproven",) + found
+
+
+BNB_WIDE_WORDS = 16           # words of a set of Context.round_bnb_wide() (FCLU_BNB_WIDE_WORDS)
+BNB_WIDE_LDS_BYTES = 160 * 1024
+BNB_WIDE_WAVES = 8
+
+
+def bnb_wide_lds_bytes(R, E):
+    """The LDS fclu_round_bnb_wide needs for a problem of R columns and E informative segments (bw_lds_bytes of csrc/clu_bnb_wide.h, the
+    same formula): it is taken only when this is at most BNB_WIDE_LDS_BYTES."""
+    W, EW = max(1, (R + 63) // 64), (E + 63) // 64
+    return (8 * 2 * R * EW + 4 * R + 8 * BNB_WIDE_WAVES * (9 * W + 2 * EW) + 15) & ~15
+
+
+def wide_mask(words):
+    """A set of Context.round_bnb_wide() (16 words, low word first) as one Python integer, bit c = column c."""
+    return sum(int(w) << (64 * i) for i, w in enumerate(words))
+
+
+def round_bnb_wide_solution(arr, p):
+    """Problem p of Context.round_bnb_wide(), by round_bnb_solution()'s convention; x is a list of R zeros and ones."""
+    status = BNB_STATUS[int(arr["status"][p])]
+    if status is None or status == "infeasible":
+        return status
+    cost2, mask = int(arr["cost2"][p]), wide_mask(arr["mask"][p])
     found = (cost2 / 2.0, [mask >> c & 1 for c in range(int(arr["col_off"][p + 1] - arr["col_off"][p]))]) if cost2 >= 0 else (None, None)
     return found if status == "optimal" else ("unproven",) + found
 

@@ -287,6 +287,7 @@ BNB_DEPTH = 6             # columns fixed by the task number: 64 tasks a problem
                           # (a problem of 60 columns counts a few hundred nodes), so 12 columns only add 4 096 one-node tasks a problem
 BNB_NODE_CAP = 1024       # nodes a task may count: what keeps the longest launch under 50 ms at 64 columns while 98 % of the problems are still
                           # proved (profiles/cluster_bnb.txt; 4 096 proves them all but a launch takes longer than 50 ms)
+BNB_WIDE_MAX_COLS = 1024  # exact_bnb_wide(): column sets of up to 16 words of 64 bits
 _BNB_NONE = 1 << 62       # "no bound": no cost2 reaches it
 
 
@@ -294,12 +295,12 @@ def _popc(x):
     return bin(x).count("1")
 
 
-def bnb_tables(model, settings):
-    """The transposed tables of exact_small() as Python ints of up to 64 bits (bit c = column c): sup[k] and corr[k] per informative
+def bnb_tables(model, settings, max_cols=BNB_MAX_COLS, who="exact_bnb"):
+    """The transposed tables of exact_small() as Python ints of up to max_cols bits (bit c = column c): sup[k] and corr[k] per informative
     segment, conf[c] and g2[c] per column; the gap rows (column, group, l) and per group its segments as (support mask, length)."""
     R = model["n_cols"]
-    if R > BNB_MAX_COLS:
-        raise ValueError("%d columns: exact_bnb takes %d at the most" % (R, BNB_MAX_COLS))
+    if R > max_cols:
+        raise ValueError("%d columns: %s takes %d at the most" % (R, who, max_cols))
     g2 = garbage2(model["garbage"])
     if len(g2) != R:
         raise ValueError("%d garbage costs for %d columns" % (len(g2), R))
@@ -443,7 +444,11 @@ def exact_bnb(model, settings, ub2=None, depth=BNB_DEPTH, node_cap=BNB_NODE_CAP,
     Result: "optimal" -- no task capped and a leaf exists (at cost2 <= ub2 when one is given): the lexicographic minimum of (cost2, mask)
         over the tasks; "infeasible" -- no task capped, no leaf, no ub2; "unproven" -- a task was capped (cost2 and mask the best found,
         or None), or a ub2 was given and no leaf is at or under it.  nodes = the tasks' counts summed, capped = the capped tasks."""
-    tb = bnb_tables(model, settings)
+    return _bnb_search(bnb_tables(model, settings), model, ub2, depth, node_cap, weak)
+
+
+def _bnb_search(tb, model, ub2, depth, node_cap, weak):
+    """exact_bnb()'s body on the tables tb: every task, and the result rule."""
     R = tb["R"]
     if depth < 0 or node_cap < 1:
         raise ValueError("depth %r, node_cap %r: at least 0 and 1" % (depth, node_cap))
@@ -463,6 +468,26 @@ def exact_bnb(model, settings, ub2=None, depth=BNB_DEPTH, node_cap=BNB_NODE_CAP,
         out.update(cost2=cost2, cost=cost2 / 2.0, mask=mask, members=list(_bits(mask)), x=x,
                    e=[int(any(x[c] for c in support)) for support in model["support"]])
     return out
+
+
+def bnb_wide_node_cap(R):
+    """The default node_cap of exact_bnb_wide() and Context.round_bnb_wide() at R columns, from profiles/cluster_bnb_wide.txt (DESIGN.md
+    section 8).  A task cannot reach a leaf in fewer than R - D nodes and one task of a problem walks nearly all of its nodes, so the cap
+    has to grow with R; a lone task's nodes run one after the other, about 2.6 us each at 123 columns, 4.3 at 245 and 6.8 at 490, so the
+    cap is also what the longest launch takes.  Up to 64 columns BNB_NODE_CAP, so that the two searches agree; up to 128 columns 4 096,
+    which proves every problem of the workload (10 ms); up to 256 columns 8 192, the largest power of two under 50 ms there (35 ms; it
+    proves 4 of 80, 16 384 proves 64 and takes 69 ms); beyond 256 columns 4 096 again: nothing was proven at 8 192 or 16 384 nodes, and
+    8 192 take 56 ms at 490 columns."""
+    return BNB_NODE_CAP if R <= BNB_MAX_COLS else 8192 if 128 < R <= 256 else 4096
+
+
+def exact_bnb_wide(model, settings, ub2=None, depth=BNB_DEPTH, node_cap=None):
+    """exact_bnb() for a model of at most BNB_WIDE_MAX_COLS = 1024 columns -- the definition the GPU's fclu_round_bnb_wide reproduces
+    exactly, node counts included.  exact_bnb()'s docstring holds word for word (tables, node, bound LB2, lower-side row test, leaf, tasks,
+    cap, result rule, node counts); a mask is a Python integer of up to 1024 bits and the smallest mask is the smaller integer.  On a
+    model of at most 64 columns the two return equal dicts.  node_cap None = bnb_wide_node_cap(R)."""
+    tb = bnb_tables(model, settings, BNB_WIDE_MAX_COLS, "exact_bnb_wide")
+    return _bnb_search(tb, model, ub2, depth, bnb_wide_node_cap(tb["R"]) if node_cap is None else node_cap, False)
 
 
 def solve_round(model, settings):

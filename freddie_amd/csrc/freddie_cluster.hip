@@ -25,6 +25,7 @@
 #include "clu_incumbent.h"   // (behind the runtime: its functions are __host__ __device__)
 #include "clu_exact.h"
 #include "clu_bnb.h"
+#include "clu_bnb_wide.h"
 #include "clu_readout.h"
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
@@ -1588,6 +1589,151 @@ __global__ void __launch_bounds__(256) k_bnb_reduce(const int *list, const i64 *
 }
 
 // ================================================================================================================
+// The same search for problems of up to 1024 columns (fclu_round_bnb_wide): a column set is W = ceil(R / 64) words, a wave runs one
+// task -- the walk of clu_bnb_wide.h, bw_task, whose control flow is the same in all its lanes -- and the lanes share a node's work:
+// e_in and the blocked columns a word a lane, the columns' pieces of LB2 and the gap rows one a lane, a wave reduction for the sum and
+// the verdict.  The definition is cluster_solve.exact_bnb_wide()'s docstring.
+// ================================================================================================================
+constexpr i64 kBwLaunchNodes = 1ll << 26;      // task-nodes of budget (tasks x node_cap) one launch holds (profiles/cluster_bnb_wide.txt)
+constexpr int kBwMaxLaunches = 4096;           // launches of one call (an event each)
+constexpr int kBwThreads = kBwWaves * kBwLanes;
+
+struct BwProb {
+    ExactProb b;
+    i64 tab0, conf0;                  // its first table word (icol, R x EW words, then ccol, EW x R words) and first conflict word (R x W words)
+    int W, EW;
+};
+
+// A workgroup per taken problem: its tables by column, its conflict rows (all zeroed before the launch and ORed into, which does not depend
+// on the order the atomics arrive in) and its groups' segments' places among the informative segments.
+__global__ void __launch_bounds__(256) k_bw_prep(const int *list, const BwProb *probs, const int *inf_seg, const i64 *sup_off, i64 n_inf, const int *sup_cols, i64 n_sup,
+                                                 const i64 *corr_off, i64 n_cols, const int *corr_seg, i64 n_corr, const int2 *pairs, const i64 *grp_seg_off,
+                                                 const int *grp_seg, i64 n_grp_seg, u64 *tab, u64 *conf, int *gk) {
+    const BwProb q = probs[list[blockIdx.x]];
+    const ExactProb d = q.b;
+    const int R = d.n, E = d.n_inf, W = q.W, EW = q.EW, tid = threadIdx.x;
+    const int *inf = inf_seg + d.inf0;
+    u64 *icol = tab + q.tab0, *ccol = icol + (i64)R * EW, *cf = conf + q.conf0;
+    for (int k = tid; k < E; k += 256) {
+        const i64 a = ex_clamp(sup_off[d.inf0 + k], 0, n_sup), b = ex_clamp(d.inf0 + k + 1 < n_inf ? sup_off[d.inf0 + k + 1] : n_sup, a, n_sup);
+        for (i64 s = a; s < b; ++s) {
+            const int c = sup_cols[s];
+            if ((unsigned)c < (unsigned)R) atomicOr(&icol[(i64)c * EW + (k >> 6)], 1ull << (k & 63));
+        }
+    }
+    for (int c = 0; c < R; ++c) {
+        const i64 a = ex_clamp(corr_off[d.col0 + c], 0, n_corr), b = ex_clamp(d.col0 + c + 1 < n_cols ? corr_off[d.col0 + c + 1] : n_corr, a, n_corr);
+        for (i64 x = a + tid; x < b; x += 256) {
+            const int k = ex_find_seg(inf, E, corr_seg[x]);
+            if (k >= 0) atomicOr(&ccol[(i64)(k >> 6) * R + c], 1ull << (k & 63));
+        }
+    }
+    for (i64 i = d.pair0 + tid; i < d.pair1; i += 256) {
+        const int2 pr = pairs[i];
+        if ((unsigned)pr.x < (unsigned)R && (unsigned)pr.y < (unsigned)R) {
+            atomicOr(&cf[(i64)pr.x * W + (pr.y >> 6)], 1ull << (pr.y & 63));
+            atomicOr(&cf[(i64)pr.y * W + (pr.x >> 6)], 1ull << (pr.x & 63));
+        }
+    }
+    if (d.grp1 > d.grp0) {
+        const i64 s0 = ex_clamp(grp_seg_off[d.grp0], 0, n_grp_seg), s1 = ex_clamp(grp_seg_off[d.grp1], s0, n_grp_seg);
+        for (i64 s = s0 + tid; s < s1; s += 256) gk[s] = ex_find_seg(inf, E, grp_seg[s]);
+    }
+}
+
+// The lanes of a wave on the device (BwHostWave of clu_bnb_wide.h on the host).  sync: what a lane wrote to the wave's LDS state is
+// there for the other lanes of the wave (they run in step; the fence keeps the compiler and the LDS counter in line).
+struct BwDevWave {
+    int lane;
+    template <class F> __device__ __forceinline__ i64 sum(F f) {
+        i64 x = f(lane);
+        for (int s = 32; s > 0; s >>= 1) x += __shfl_xor(x, s);
+        return x;
+    }
+    template <class F> __device__ __forceinline__ bool any(F f) { return __any(f(lane) ? 1 : 0) != 0; }
+    template <class F> __device__ __forceinline__ void each(F f) { f(lane); }
+    __device__ __forceinline__ void sync() {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    }
+};
+
+struct BwTask { i64 cost2; int nodes, capped; u64 mask[kBwMaxWords]; };  // a task's result: cost2 -1 and an empty mask when it found no leaf
+
+// A workgroup per item = (problem, first task, tasks <= 8, -): the problem's tables by column and g2 are staged in LDS, wave i runs
+// task first + i on its own state words behind them and its first lane writes the result to the problem's place task_off[problem] +
+// task of the per-task array.  Tasks share nothing and no workgroup waits for another; every loop is bounded by R, the table sizes or
+// node_cap.  The items, the descriptors and their offsets (it.x, tab0, conf0, task_off) are the host's own, built and checked in
+// bnb_wide_device before the launch, and are used as they are, as in k_bnb_search; what comes from the round's arrays is clamped.
+__global__ void __launch_bounds__(kBwThreads) k_bw_search(const int4 *items, const BwProb *probs, const u64 *tab, const u64 *conf, const int *g2, const i64 *ub2,
+                                                          const int *rows, i64 n_rows, const i64 *grp_seg_off, i64 n_grp, i64 n_grp_seg, const int *gk,
+                                                          const int *grp_len, double lo_f, double hi_f, int offset, int depth, int node_cap, const i64 *task_off,
+                                                          BwTask *tasks) {
+    extern __shared__ __attribute__((aligned(16))) u64 s_bw[];
+    const int4 it = items[blockIdx.x];
+    const BwProb q = probs[it.x];
+    const ExactProb d = q.b;
+    const int R = d.n, E = d.n_inf, W = q.W, EW = q.EW, tid = threadIdx.x, wave = tid / kBwLanes;
+    const i64 n_tab = 2ll * R * EW;
+    const int n_st = bw_state_words(W, EW);
+    u64 *s_state = s_bw + n_tab;
+    int *s_g2 = reinterpret_cast<int *>(s_state + (i64)kBwWaves * n_st);
+    for (i64 x = tid; x < n_tab; x += kBwThreads) s_bw[x] = tab[q.tab0 + x];
+    for (int c = tid; c < R; c += kBwThreads) s_g2[c] = g2[d.col0 + c];
+    __syncthreads();
+    const int D = R < depth ? R : depth;
+    const u64 t = (u64)(unsigned)it.y + (u64)wave;
+    if (wave >= it.z || (t >> D)) return;                    // (no such task: the host cuts the items inside 2^D)
+    BwView v;
+    v.icol = s_bw; v.ccol = s_bw + (i64)R * EW; v.conf = conf + q.conf0; v.g2 = s_g2; v.E = E; v.R = R; v.W = W; v.EW = EW;
+    v.r0 = ex_clamp(d.row0, 0, n_rows); v.r1 = ex_clamp(d.row1, v.r0, n_rows); v.rows = rows;
+    v.grp0 = d.grp0; v.n_grp = n_grp; v.grp_seg_off = grp_seg_off; v.n_grp_seg = n_grp_seg; v.gk = gk; v.grp_len = grp_len;
+    v.lo_f = lo_f; v.hi_f = hi_f; v.offset = offset; v.max_lg = d.max_lg;
+    v.st = s_state + (i64)wave * n_st;
+    BwDevWave wv = {tid % kBwLanes};
+    const BwResult r = bw_task(v, wv, t, D, ub2[it.x], node_cap);
+    wv.sync();
+    BwTask *out = tasks + task_off[it.x] + (i64)t;
+    if (wv.lane == 0) { out->cost2 = r.cost2; out->nodes = r.nodes; out->capped = r.capped; }
+    if (wv.lane < kBwMaxWords) out->mask[wv.lane] = r.cost2 >= 0 && wv.lane < W ? v.st[4 * W + wv.lane] : 0ull;
+}
+
+struct BwOut { i64 cost2, task, nodes, capped; };             // a problem's result: cost2 -1 when no task found a leaf; task: the one whose set it is
+
+// A workgroup per taken problem: the smallest (cost2, mask) of its n_tasks tasks as that task's number, their nodes summed, the capped
+// ones counted; then the set's 16 words.  A lane folds every 256th task and a tree in LDS folds the 256 partial results; a minimum and
+// two sums, so nothing depends on an order (two tasks never hold the same set).
+__global__ void __launch_bounds__(256) k_bw_reduce(const int *list, const BwProb *probs, const i64 *task_off, const i64 *n_tasks, const BwTask *tasks, BwOut *out,
+                                                   u64 *out_mask) {
+    __shared__ BwOut s_part[256];
+    const int p = list[blockIdx.x], tid = threadIdx.x, W = probs[p].W;
+    const i64 n = n_tasks[p];
+    const BwTask *mine = tasks + task_off[p];
+    BwOut acc = {-1, 0, 0, 0};
+    for (i64 t = tid; t < n; t += 256) {
+        const BwTask &r = mine[t];
+        if (bw_better(r.cost2, r.mask, acc.cost2, mine[acc.task].mask, W)) { acc.cost2 = r.cost2; acc.task = t; }
+        acc.nodes += r.nodes; acc.capped += r.capped ? 1 : 0;
+    }
+    s_part[tid] = acc;
+    __syncthreads();
+    for (int step = 128; step > 0; step >>= 1) {
+        if (tid < step) {
+            BwOut a = s_part[tid];
+            const BwOut b = s_part[tid + step];
+            if (bw_better(b.cost2, mine[b.task].mask, a.cost2, mine[a.task].mask, W)) { a.cost2 = b.cost2; a.task = b.task; }
+            a.nodes += b.nodes; a.capped += b.capped;
+            s_part[tid] = a;
+        }
+        __syncthreads();
+    }
+    const BwOut r = s_part[0];
+    if (tid == 0) out[p] = r;
+    if (tid < kBwMaxWords) out_mask[(i64)p * kBwMaxWords + tid] = r.cost2 >= 0 ? mine[r.task].mask[tid] : 0ull;
+}
+
+// ================================================================================================================
 // The read-out of a round (fclu_round_readout): run_ilp()'s isoform (py/freddie_cluster.py:601-635; cluster.read_out) of every problem
 // with an accepted column set, from the rows the context holds -- the reps' I, C and label rows, the round's informative rows and rids.
 // What a lane computes per word is clu_readout.h.
@@ -1721,10 +1867,10 @@ struct fclu_ctx {
     hipStream_t stream = nullptr;
     // every event, one list to create and destroy; by stage: the graph (ev), fclu_partition (pev), _preprocess (qev), _group_reads (gev), _round_models (rev),
     // _round_incumbents (iev), _round_exact's prep (xev; its search launches have an event each in xl_ev, created as a call needs them), _round_bnb's prep and reduction (bev; bl_ev likewise),
-    // _round_readout (oev)
-    hipEvent_t events[3 + 6 + 6 + 5 + 5 + 4 + 2 + 3 + 3] = {};
-    hipEvent_t *const ev = events, *const pev = ev + 3, *const qev = pev + 6, *const gev = qev + 6, *const rev = gev + 5, *const iev = rev + 5, *const xev = iev + 4, *const bev = xev + 2, *const oev = bev + 3;
-    std::vector<hipEvent_t> xl_ev, bl_ev;
+    // _round_readout (oev), _round_bnb_wide's prep and reduction (wev; wl_ev as bl_ev)
+    hipEvent_t events[3 + 6 + 6 + 5 + 5 + 4 + 2 + 3 + 3 + 3] = {};
+    hipEvent_t *const ev = events, *const pev = ev + 3, *const qev = pev + 6, *const gev = qev + 6, *const rev = gev + 5, *const iev = rev + 5, *const xev = iev + 4, *const bev = xev + 2, *const oev = bev + 3, *const wev = oev + 3;
+    std::vector<hipEvent_t> xl_ev, bl_ev, wl_ev;
     std::string err;
     float compat_ms = 0.f, prune_ms = 0.f;
     int32_t paths[FCLU_N_PATHS] = {};     // the last graph call's launch census and the last read-out's (fclu_last_paths)
@@ -1843,6 +1989,19 @@ struct fclu_ctx {
     float bprep_ms = 0.f, bsearch_ms = 0.f, blongest_ms = 0.f;
     fclu_bnb bnb = {};
     bool have_bnb = false;
+    // fclu_round_bnb_wide(): the same input; device arrays (wd: the problems, the taken ones' list, the work items, the tables by column,
+    // the conflict rows, the group segments' places, g2, the bounds, per problem its first task and task count, a result per task and per
+    // problem with its 16 mask words) and the pinned copies fclu_round_bnb_wide_results() hands out (wh)
+    struct {
+        Buf<BwProb> probs; Buf<int4> items; Buf<u64> tab, conf, out_mask; Buf<i64> ub2, task_off, n_tasks; Buf<BwTask> tasks; Buf<BwOut> out;
+        Buf<int> list, g2, gk;
+    } wd;
+    struct {
+        HostBuf<BwOut> out; HostBuf<int64_t> cost2, nodes; HostBuf<uint64_t> mask; HostBuf<int32_t> status, capped;
+    } wh;
+    float wprep_ms = 0.f, wsearch_ms = 0.f, wlongest_ms = 0.f;
+    fclu_bnb_wide wide = {};
+    bool have_wide = false;
     // fclu_round_readout(): the same input and the reps' rows (pd.ibits / cbits / labels); device arrays (od: the problems with a set, the
     // sets, the exon words, the three outputs) and the pinned copies fclu_round_readout_results() hands out (oh)
     struct {
@@ -1861,6 +2020,7 @@ struct fclu_ctx {
         for (hipEvent_t e : events) if (e) (void)hipEventDestroy(e);
         for (hipEvent_t e : xl_ev) if (e) (void)hipEventDestroy(e);
         for (hipEvent_t e : bl_ev) if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : wl_ev) if (e) (void)hipEventDestroy(e);
     }
 };
 
@@ -1897,7 +2057,8 @@ int fail(fclu_ctx *c, int code, const char *fmt, ...) {
 //   FCLU_EXACT_SLICE=n      exact_slice      0 < n < kExactWgMasks: fclu_round_exact gives a workgroup n masks and a launch 16 n, so that a small problem crosses
 //                                            many slices and several launches
 //   FCLU_BNB_SLICE=n        bnb_slice        n > 0: fclu_round_bnb gives a launch n tasks (and a workgroup min(n, 256)), so that a problem crosses several launches
-struct Knobs { bool part_lds, prune_lds, rank, prune_edges, round_lds; i64 prune_lds_words, round_lds_bytes, exact_slice, bnb_slice; unsigned hash_mask; };
+//   FCLU_BNB_WIDE_SLICE=n   bnb_wide_slice   n > 0: fclu_round_bnb_wide gives a launch n tasks (and a workgroup min(n, 8)), so that a problem crosses several launches
+struct Knobs { bool part_lds, prune_lds, rank, prune_edges, round_lds; i64 prune_lds_words, round_lds_bytes, exact_slice, bnb_slice, bnb_wide_slice; unsigned hash_mask; };
 
 Knobs read_knobs() {
     const auto off = [](const char *name) { const char *e = getenv(name); return e && e[0] == '0'; };
@@ -1912,6 +2073,8 @@ Knobs read_knobs() {
     k.exact_slice = (xs && atoll(xs) > 0 && atoll(xs) < kExactWgMasks) ? atoll(xs) : 0;
     const char *bs = getenv("FCLU_BNB_SLICE");
     k.bnb_slice = (bs && atoll(bs) > 0 && atoll(bs) < (1ll << 30)) ? atoll(bs) : 0;
+    const char *ws = getenv("FCLU_BNB_WIDE_SLICE");
+    k.bnb_wide_slice = (ws && atoll(ws) > 0 && atoll(ws) < (1ll << 30)) ? atoll(ws) : 0;
     const char *hb = getenv("FCLU_HASH_BITS");
     k.hash_mask = (hb && hb[0] >= '0' && hb[0] <= '9' && atoi(hb) < 32) ? (1u << atoi(hb)) - 1u : 0xffffffffu;
     return k;
@@ -2858,7 +3021,7 @@ void round_launch(fclu_ctx *c, const RoundRun &r) {
 // resident (fclu_round_models_resident): the same kernels and device arrays; of the results only the small per-problem arrays come to the
 // host -- what the later round calls and the read-out need of them -- and the model's own arrays stay where they are.
 int round_device(fclu_ctx *c, const Knobs &k, const fclu_round_batch *b, bool resident) {
-    c->have_rounds = c->have_incs = c->have_exact = c->have_bnb = c->have_readout = false;
+    c->have_rounds = c->have_incs = c->have_exact = c->have_bnb = c->have_wide = c->have_readout = false;
     c->rcount_ms = c->rgaps_ms = c->rfill_ms = 0.f;
     if (!c->round_ready || !c->round_src_ok || !c->have_parts)
         return fail(c, FCLU_ERR_ARG, "fclu_round_models: no fclu_round_setup() behind the context's last partition call");
@@ -3371,6 +3534,148 @@ int bnb_device(fclu_ctx *c, const Knobs &k, const int32_t *g2, const int64_t *ub
     return FCLU_OK;
 }
 
+// ---- the same search over the last round's problems of up to 1024 columns (fclu_round_bnb_wide) ---------------------------------
+int bnb_wide_device(fclu_ctx *c, const Knobs &k, const int32_t *g2, const int64_t *ub2, double lo_f, double hi_f, int32_t offset, int32_t min_cols,
+                    int32_t max_cols, int32_t depth, int32_t node_cap, int64_t max_nodes) {
+    c->have_wide = false;
+    c->wprep_ms = c->wsearch_ms = c->wlongest_ms = 0.f;
+    if (!c->have_rounds || !c->round_ready || !c->round_src_ok || !c->have_parts)
+        return fail(c, FCLU_ERR_ARG, "fclu_round_bnb_wide: no successful fclu_round_models() stands behind the call (none was made, it failed, or a later "
+                                     "call ended the rounds' source)");
+    const fclu_rounds &o = c->rounds;
+    const int P = o.n_prob;
+    const i64 C = o.n_cols, G = o.n_gap_rows;
+    if (min_cols < 0 || max_cols < min_cols || max_cols > kBwMaxCols)
+        return fail(c, FCLU_ERR_ARG, "fclu_round_bnb_wide: min_cols is %d and max_cols %d, they must be 0 <= min_cols <= max_cols <= %d", (int)min_cols,
+                    (int)max_cols, kBwMaxCols);
+    if (depth < 0 || depth > kBnbMaxDepth) return fail(c, FCLU_ERR_ARG, "fclu_round_bnb_wide: depth is %d, it must lie in [0, %d]", (int)depth, kBnbMaxDepth);
+    if (node_cap < 1) return fail(c, FCLU_ERR_ARG, "fclu_round_bnb_wide: node_cap is %d, it must be at least 1", (int)node_cap);
+    if (max_nodes < 1) return fail(c, FCLU_ERR_ARG, "fclu_round_bnb_wide: max_nodes is %lld, it must be at least 1", (i64)max_nodes);
+    if (offset < 0 || !(lo_f == lo_f) || !(hi_f == hi_f) || lo_f - lo_f != 0.0 || hi_f - hi_f != 0.0)
+        return fail(c, FCLU_ERR_ARG, "fclu_round_bnb_wide: offset is negative or a factor is not finite");
+    if (C > 0 && !g2) return fail(c, FCLU_ERR_ARG, "fclu_round_bnb_wide: g2 is null");
+    if (P > 0 && !ub2) return fail(c, FCLU_ERR_ARG, "fclu_round_bnb_wide: ub2 is null");
+    for (i64 x = 0; x < C; ++x) if (g2[x] < 0) return fail(c, FCLU_ERR_ARG, "fclu_round_bnb_wide: g2[%lld] is negative", x);
+    if ((int)c->r_probs.size() != P) return fail(c, FCLU_ERR_ARG, "fclu_round_bnb_wide: the round's problems are gone");
+    HIP_TRY(c, hipSetDevice(c->device));
+    auto &D = c->wd;
+    auto &H = c->wh;
+    auto &RD = c->rd;
+    hipStream_t s = c->stream;
+    // ---- which problems are taken: ascending (R, problem) while the running total of 2^D x node_cap stays inside the budget
+    std::vector<BwProb> probs((size_t)P);
+    std::vector<std::pair<int, int>> order;
+    for (int p = 0; p < P; ++p) {
+        BwProb &q = probs[(size_t)p];
+        ExactProb &d = q.b;
+        fill_exact_prob(c, p, d);
+        q.tab0 = q.conf0 = 0; q.W = bw_words(d.n); q.EW = bw_ewords(d.n_inf);
+        if (o.refused[p] >= 0 || d.n < min_cols || d.n > max_cols || d.n_inf < 0 || bw_lds_bytes(d.n, d.n_inf) > kBwLdsBytes) continue;   // no model, outside the sizes, or tables beyond LDS
+        if (!exact_prob_in_range(c, p, d)) return fail(c, FCLU_ERR_HIP, "problem %d: the round's offsets are out of range", p);
+        if (o.n_grp == 0) d.row0 = d.row1 = 0;               // (a row has a group: nothing to index without one)
+        order.emplace_back(d.n, p);
+    }
+    std::sort(order.begin(), order.end());
+    const i64 launch_tasks = k.bnb_wide_slice ? k.bnb_wide_slice : std::max<i64>(kBwLaunchNodes / node_cap, 1);
+    const i64 wg_tasks = std::min<i64>(kBwWaves, launch_tasks);
+    std::vector<int> list;
+    std::vector<int4> items;
+    std::vector<size_t> launch_first;                        // a launch's first item; closed by the number of items
+    std::vector<size_t> launch_lds;
+    std::vector<i64> task_off((size_t)P, 0), n_tasks((size_t)P, 0);
+    i64 budget = 0, total_tasks = 0, in_launch = 0, n_tab = 0, n_conf = 0;
+    for (const auto &rp : order) {
+        BwProb &q = probs[(size_t)rp.second];
+        const ExactProb &d = q.b;
+        const i64 tasks = 1ll << std::min<int>(d.n, depth);
+        if (tasks > (max_nodes - budget) / node_cap) break;  // (ascending R: nothing behind it fits either; no product that could overflow)
+        budget += tasks * node_cap;
+        list.push_back(rp.second);
+        task_off[(size_t)rp.second] = total_tasks; n_tasks[(size_t)rp.second] = tasks;
+        total_tasks += tasks;
+        q.tab0 = n_tab; q.conf0 = n_conf;
+        n_tab += bw_table_words(d.n, d.n_inf); n_conf += (i64)d.n * q.W;
+        const size_t lds = (size_t)bw_lds_bytes(d.n, d.n_inf);
+        for (i64 lo = 0; lo < tasks; lo += wg_tasks) {
+            const i64 n = std::min<i64>(wg_tasks, tasks - lo);
+            if (launch_first.empty() || in_launch + n > launch_tasks) { launch_first.push_back(items.size()); launch_lds.push_back(0); in_launch = 0; }
+            items.push_back(make_int4(rp.second, (int)lo, (int)n, 0));
+            launch_lds.back() = std::max(launch_lds.back(), lds);
+            in_launch += n;
+        }
+    }
+    const size_t nL = list.size(), nI = items.size(), n_launch = launch_first.size(), nP = (size_t)P, nC = (size_t)C, nT = (size_t)total_tasks;
+    launch_first.push_back(nI);
+    if (n_launch > (size_t)kBwMaxLaunches)
+        return fail(c, FCLU_ERR_UNSUPPORTED, "fclu_round_bnb_wide: %lld tasks need %lld launches, a call issues %d at the most: lower max_nodes", total_tasks,
+                    (i64)n_launch, kBwMaxLaunches);
+    while (c->wl_ev.size() < n_launch + 1) {
+        hipEvent_t e = nullptr;
+        HIP_TRY(c, hipEventCreate(&e));
+        c->wl_ev.push_back(e);
+    }
+    HIP_TRY(c, D.probs.grow(nP)); HIP_TRY(c, D.list.grow(nL)); HIP_TRY(c, D.items.grow(nI)); HIP_TRY(c, D.tab.grow((size_t)n_tab));
+    HIP_TRY(c, D.conf.grow((size_t)n_conf)); HIP_TRY(c, D.gk.grow((size_t)o.n_grp_seg)); HIP_TRY(c, D.g2.grow(nC)); HIP_TRY(c, D.ub2.grow(nP));
+    HIP_TRY(c, D.task_off.grow(nP)); HIP_TRY(c, D.n_tasks.grow(nP)); HIP_TRY(c, D.tasks.grow(nT)); HIP_TRY(c, D.out.grow(nP));
+    HIP_TRY(c, D.out_mask.grow(nP * kBwMaxWords));
+    HIP_TRY(c, H.out.grow(nP)); HIP_TRY(c, H.cost2.grow(nP)); HIP_TRY(c, H.mask.grow(nP * kBwMaxWords)); HIP_TRY(c, H.nodes.grow(nP)); HIP_TRY(c, H.status.grow(nP));
+    HIP_TRY(c, H.capped.grow(nP));
+    if (nP) {
+        HIP_TRY(c, hipMemcpyAsync(D.probs.p, probs.data(), D.probs.bytes(nP), hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipMemcpyAsync(D.ub2.p, ub2, D.ub2.bytes(nP), hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipMemcpyAsync(D.task_off.p, task_off.data(), D.task_off.bytes(nP), hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipMemcpyAsync(D.n_tasks.p, n_tasks.data(), D.n_tasks.bytes(nP), hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipMemsetAsync(D.out.p, 0, D.out.bytes(nP), s));
+        HIP_TRY(c, hipMemsetAsync(D.out_mask.p, 0, D.out_mask.bytes(nP * kBwMaxWords), s));
+    }
+    if (nL) HIP_TRY(c, hipMemcpyAsync(D.list.p, list.data(), D.list.bytes(nL), hipMemcpyHostToDevice, s));
+    if (nI) HIP_TRY(c, hipMemcpyAsync(D.items.p, items.data(), D.items.bytes(nI), hipMemcpyHostToDevice, s));
+    if (C) HIP_TRY(c, hipMemcpyAsync(D.g2.p, g2, D.g2.bytes(nC), hipMemcpyHostToDevice, s));
+    if (n_tab) HIP_TRY(c, hipMemsetAsync(D.tab.p, 0, D.tab.bytes((size_t)n_tab), s));
+    if (n_conf) HIP_TRY(c, hipMemsetAsync(D.conf.p, 0, D.conf.bytes((size_t)n_conf), s));
+    HIP_TRY(c, hipEventRecord(c->wev[0], s));
+    if (nL)
+        hipLaunchKernelGGL(k_bw_prep, dim3((unsigned)nL), dim3(256), 0, s, D.list.p, D.probs.p, RD.inf_seg.p, RD.sup_off.p, (i64)o.n_inf, RD.sup_cols.p, (i64)o.n_sup,
+                           RD.corr_off.p, C, RD.corr_seg.p, (i64)o.n_corr, RD.pairs.p, RD.grp_seg_off.p, RD.grp_seg.p, (i64)o.n_grp_seg, D.tab.p, D.conf.p, D.gk.p);
+    HIP_TRY(c, hipEventRecord(c->wev[1], s));
+    HIP_TRY(c, hipEventRecord(c->wl_ev[0], s));
+    for (size_t l = 0; l < n_launch; ++l) {
+        hipLaunchKernelGGL(k_bw_search, dim3((unsigned)(launch_first[l + 1] - launch_first[l])), dim3(kBwThreads), launch_lds[l], s, D.items.p + launch_first[l],
+                           D.probs.p, D.tab.p, D.conf.p, D.g2.p, D.ub2.p, RD.rows.p, G, RD.grp_seg_off.p, (i64)o.n_grp, (i64)o.n_grp_seg, D.gk.p, RD.grp_len.p, lo_f,
+                           hi_f, (int)offset, (int)depth, (int)node_cap, D.task_off.p, D.tasks.p);
+        HIP_TRY(c, hipEventRecord(c->wl_ev[l + 1], s));
+    }
+    if (nL) hipLaunchKernelGGL(k_bw_reduce, dim3((unsigned)nL), dim3(256), 0, s, D.list.p, D.probs.p, D.task_off.p, D.n_tasks.p, D.tasks.p, D.out.p, D.out_mask.p);
+    HIP_TRY(c, hipEventRecord(c->wev[2], s));
+    if (nP) {
+        HIP_TRY(c, hipMemcpyAsync(H.out.p, D.out.p, D.out.bytes(nP), hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipMemcpyAsync(H.mask.p, D.out_mask.p, D.out_mask.bytes(nP * kBwMaxWords), hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(c, hipStreamSynchronize(s));
+    HIP_TRY(c, hipGetLastError());
+    for (int p = 0; p < P; ++p) { H.status.p[p] = FCLU_BNB_NOT_TAKEN; H.cost2.p[p] = -1; H.nodes.p[p] = 0; H.capped.p[p] = 0; }
+    i64 nodes_total = 0;
+    for (const int p : list) {
+        const BwOut &r = H.out.p[p];
+        const bool found = r.cost2 >= 0;
+        H.cost2.p[p] = found ? r.cost2 : -1; H.nodes.p[p] = r.nodes; H.capped.p[p] = (int32_t)r.capped;
+        H.status.p[p] = r.capped > 0 ? FCLU_BNB_UNPROVEN : found ? FCLU_BNB_OPTIMAL : ub2[p] < 0 ? FCLU_BNB_INFEASIBLE : FCLU_BNB_UNPROVEN;
+        nodes_total += r.nodes;
+    }
+    fclu_bnb_wide &r = c->wide;
+    r.n_prob = P; r.status = H.status.p; r.cost2 = H.cost2.p; r.mask = H.mask.p; r.nodes = H.nodes.p; r.capped = H.capped.p;
+    r.n_taken = (int64_t)nL; r.n_launches = (int64_t)n_launch; r.nodes_total = nodes_total;
+    (void)hipEventElapsedTime(&c->wprep_ms, c->wev[0], c->wev[1]);
+    if (n_launch) (void)hipEventElapsedTime(&c->wsearch_ms, c->wl_ev[0], c->wl_ev[n_launch]);
+    for (size_t l = 0; l < n_launch; ++l) {
+        float ms = 0.f;
+        (void)hipEventElapsedTime(&ms, c->wl_ev[l], c->wl_ev[l + 1]);
+        c->wlongest_ms = std::max(c->wlongest_ms, ms);
+    }
+    c->have_wide = true;
+    return FCLU_OK;
+}
+
 // ---- the read-out of the last round's accepted sets (fclu_round_readout) --------------------------------------------------------
 // Every refusal is the host's, before any launch: the kernels get sets that are inside their problems, and clamp what they read all the same.
 int readout_device(fclu_ctx *c, const int64_t *sel_off, const int32_t *sel) {
@@ -3495,7 +3800,8 @@ int fclu_create(int device, fclu_ctx **out) {
         {reinterpret_cast<const void *>(k_inc_start<true>), (int)inc_lds_bytes(0, kMaxWords, (kIncMaxCols + 31) / 32, false) + kRoundLdsBytes},
         {reinterpret_cast<const void *>(k_inc_start<false>), (int)inc_lds_bytes(0, kMaxWords, (kIncMaxCols + 31) / 32, false)},
         {reinterpret_cast<const void *>(k_exact_search), kExactLdsBytes},
-        {reinterpret_cast<const void *>(k_bnb_search), kBnbLdsBytes}};
+        {reinterpret_cast<const void *>(k_bnb_search), kBnbLdsBytes},
+        {reinterpret_cast<const void *>(k_bw_search), kBwLdsBytes}};
     for (const auto &d : dyn) if (e == hipSuccess) e = hipFuncSetAttribute(d.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, d.lds);
     if (e != hipSuccess) {
         fail(nullptr, FCLU_ERR_HIP, "context creation failed: %s", hipGetErrorString(e));
@@ -3738,6 +4044,25 @@ int fclu_round_bnb_timing(fclu_ctx *c, float *prep_ms, float *search_ms, float *
     if (!c) return FCLU_ERR_ARG;
     if (longest_launch_ms) *longest_launch_ms = c->blongest_ms;
     return two_times(prep_ms, c->bprep_ms, search_ms, c->bsearch_ms);
+}
+
+int fclu_round_bnb_wide(fclu_ctx *c, const int32_t *g2, const int64_t *ub2, double lo_f, double hi_f, int32_t offset, int32_t min_cols, int32_t max_cols,
+                        int32_t depth, int32_t node_cap, int64_t max_nodes) {
+    return c ? bnb_wide_device(c, read_knobs(), g2, ub2, lo_f, hi_f, offset, min_cols, max_cols, depth, node_cap, max_nodes) : FCLU_ERR_ARG;
+}
+
+int fclu_round_bnb_wide_results(fclu_ctx *c, fclu_bnb_wide *out) {
+    if (!c || !out) return FCLU_ERR_ARG;
+    if (!c->have_wide || !c->have_rounds)
+        return fail(c, FCLU_ERR_ARG, "fclu_round_bnb_wide_results: no result (the last fclu_round_bnb_wide call failed, none was made, or a later call ended it)");
+    *out = c->wide;
+    return FCLU_OK;
+}
+
+int fclu_round_bnb_wide_timing(fclu_ctx *c, float *prep_ms, float *search_ms, float *longest_launch_ms) {
+    if (!c) return FCLU_ERR_ARG;
+    if (longest_launch_ms) *longest_launch_ms = c->wlongest_ms;
+    return two_times(prep_ms, c->wprep_ms, search_ms, c->wsearch_ms);
 }
 
 int fclu_round_readout(fclu_ctx *c, const int64_t *sel_off, const int32_t *sel) { return c ? readout_device(c, sel_off, sel) : FCLU_ERR_ARG; }

@@ -18,7 +18,7 @@
  * The ILP's solve is not here; what run_ilp() builds its model from is: fclu_round_models() (at the end of this header) gives round r of
  * many partitions as flat arrays, from the rows and pair lists the calls above left on the device.  Problems of at most 24 columns need no
  * ILP: fclu_round_exact() enumerates their column sets and returns the proven optimum, and fclu_round_bnb() searches problems of up to 64
- * columns by branch and bound.  A round whose problems are answered there needs no model on the host: fclu_round_models_resident() leaves
+ * columns by branch and bound (fclu_round_bnb_wide(): up to 1024, a wave a task).  A round whose problems are answered there needs no model on the host: fclu_round_models_resident() leaves
  * the models on the device, and fclu_round_readout() (the last section) turns the accepted column sets into the round's isoforms -- exon
  * rows and the members' correction strings -- from the rows the context holds.
  *
@@ -413,6 +413,40 @@ int fclu_round_bnb_results(fclu_ctx *c, fclu_bnb *out);
 
 /* Kernel time of the last fclu_round_bnb() from HIP events (ms): the tables; all search launches; the longest of them. */
 int fclu_round_bnb_timing(fclu_ctx *c, float *prep_ms, float *search_ms, float *longest_launch_ms);
+
+/* ---- the same search for problems of up to 1024 columns ----
+ * fclu_round_bnb()'s search, word for word (the definition is freddie_amd/cluster_solve.py exact_bnb_wide(), which the device reproduces
+ * exactly, node counts included), on column sets of W = ceil(R / 64) words: a wave runs one task and its 64 lanes share the work inside
+ * a node (freddie_amd/csrc/clu_bnb_wide.h).  Input as fclu_round_bnb's.  A problem is taken when it has a model, min_cols <= R <=
+ * max_cols <= 1024, its tables fit one workgroup's LDS -- bw_lds_bytes(R, E) of clu_bnb_wide.h, 16 R ceil(E / 64) + 4 R + 64 (9 W + 2
+ * ceil(E / 64)) bytes rounded up to 16, at most 160 KiB -- and it fits the budget: ascending (columns, problem index) while the running
+ * total of 2^D * node_cap stays <= max_nodes.  A launch holds at most 2^26 task-nodes of budget (tasks * node_cap; at least one task).
+ * FCLU_ERR_ARG: fclu_round_bnb's cases with 1024 for 64, all refused on the host before any launch.  FCLU_ERR_UNSUPPORTED: a budget that
+ * needs more than 4096 launches.  The context stays usable.  FCLU_BNB_WIDE_SLICE=<tasks> (read at the call; tests): a launch holds that
+ * many tasks. */
+int fclu_round_bnb_wide(fclu_ctx *c, const int32_t *g2, const int64_t *ub2, double lo_f, double hi_f, int32_t offset, int32_t min_cols, int32_t max_cols,
+                        int32_t depth, int32_t node_cap, int64_t max_nodes);
+
+#define FCLU_BNB_WIDE_WORDS 16
+
+typedef struct fclu_bnb_wide {
+    int32_t n_prob;
+    const int32_t *status;         /* n_prob: as fclu_bnb's */
+    const int64_t *cost2;          /* n_prob: twice the cost of the best set found; -1 where there is none */
+    const uint64_t *mask;          /* 16 n_prob: that set, 16 words a problem, low word first, bit c & 63 of word c >> 6 = column c; 0 where cost2 < 0 */
+    const int64_t *nodes;          /* n_prob: nodes counted over the problem's tasks; 0 where it was not taken */
+    const int32_t *capped;         /* n_prob: tasks that stopped at node_cap */
+    int64_t n_taken;               /* problems taken */
+    int64_t n_launches;            /* search launches issued */
+    int64_t nodes_total;           /* the taken problems' nodes summed */
+} fclu_bnb_wide;
+
+/* Result of the last successful fclu_round_bnb_wide(): pointers into pinned host buffers the context owns, valid until the context's
+ * next call.  The round's, the incumbents', the exact call's and fclu_round_bnb's results stay valid behind it. */
+int fclu_round_bnb_wide_results(fclu_ctx *c, fclu_bnb_wide *out);
+
+/* Kernel time of the last fclu_round_bnb_wide() from HIP events (ms): the tables; all search launches; the longest of them. */
+int fclu_round_bnb_wide_timing(fclu_ctx *c, float *prep_ms, float *search_ms, float *longest_launch_ms);
 
 /* ---- the read-out of a round: run_ilp()'s isoform (:601-635) of every problem with an accepted column set, on the device ----
  * The batch is that of the context's last successful fclu_round_models() / fclu_round_models_resident().  Problem p's accepted columns are

@@ -57,13 +57,14 @@ def boundary_model(l):
                 group_segs=[[(1, 200)]], gap_rows=[(0, 0, l)], garbage=[50.0, 50.0], max_lg=400)
 
 
-def family_tint(tid, R, n_low):
+def family_tint(tid, R, n_low, gaps=None, weight=None):
     """Two families of reps and two reps that tie them into one component: family A, reps 0 .. n_low - 1, is all ones with one 0 at a
     place of the rep's own (rep 0: none); family B, reps n_low .. R - 1, has three 0s in common and one of the rep's own (rep n_low:
     none).  Two reps of a family differ in at most 2 segments and are compatible, two of different families in at least 3 and are not.
     Reps R (one of B's 0s) and R + 1 (two of them) are compatible with each other, with A resp. B and with rep 0, so the partition is
     one; a problem leaves them out: remaining = range(R), with every cross pair in its pair list.  A rep of B stands for n_low + 1
     reads, so B as a whole is the optimum -- cost (R - n_low - 1) + 3 n_low under the constant model -- at the columns from n_low on.
+    gaps: make_tint()'s, {rep: {(j1, j2): l}}; weight: the reads a rep of B stands for, n_low + 1 by default.
     Returns (tint as read_segment() leaves it, the cross pairs)."""
     n_high = R - n_low
     assert n_low >= 1 and n_high >= 1
@@ -83,7 +84,7 @@ def family_tint(tid, R, n_low):
         for j in zeros:
             row[j] = 0
         rows.append(row)
-    tint = ru.make_tint(tid, rows, members={i: n_low + 1 for i in range(n_low, R)})
+    tint = ru.make_tint(tid, rows, gaps, members={i: n_low + 1 if weight is None else weight for i in range(n_low, R)})
     return tint, [(a, b) for a in range(n_low) for b in range(n_low, R)]
 
 

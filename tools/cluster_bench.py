@@ -16,6 +16,10 @@ synthetic preprocessed tints through include/freddie_cluster.h.
     python tools/cluster_bench.py --exact [--max-ilp K] [--exact-small N] [--exact-masks M] [--steps K] [--host-sample N] [--solve-budget S] [--out FILE]
                        (per problem size N = 8, 12, 16, 20, 24: Context.round_exact on every partition's first N reps -- the call, the kernels,
                         the longest launch, masks per second -- against HiGHS on a sample of the same problems; profiles/cluster_exact.txt)
+    python tools/cluster_bench.py --wide [--sizes 128,256,1000] [--tints 40] [--wide-node-caps A,B] [--loop-runs R] [--steps K] [--host-sample N] [--out FILE] [--append]
+                       (per maximum_ilp_size: Context.round_bnb_wide on the first round's problems of 65 .. min(N, 1024) columns by column class --
+                        taken, proven, unproven, nodes, ms a call, the longest launch --, HiGHS on a sample of the same problems, and optionally
+                        the whole loop with and without --exact-wide; profiles/cluster_bnb_wide.txt)
     python tools/cluster_bench.py --bnb [--exact-bnb N] [--bnb-nodes M] [--bnb-depth D] [--bnb-node-cap C] [--steps K] [--host-sample N] [--solve-budget S] [--out FILE]
                        (per maximum_ilp_size N = 32, 48, 64: Context.round_bnb on the first round's problems of 25 .. N columns -- taken, proved,
                         capped, nodes, the call, the longest launch, nodes per second -- against HiGHS with 1 and 16 workers on a sample of
@@ -746,6 +750,160 @@ def run_bnb(workload="many", steps=3, sizes=(32, 48, 64), min_cols=25, max_nodes
     }
 
 
+def _compare_rounds(base, wide):
+    """Two loops' on_round records, keyed (tint, partition, round) -> (status, cost, remaining, x), partition by partition up to the first
+    round in which they differ (behind it the remaining reps differ and the rounds are other problems): how many partitions agree to the
+    end, and what the first difference is -- the same status and cost with another set (an optimum that is not unique), another cost, or
+    another status -- with up to five examples of each of the last two."""
+    parts = sorted(set(k[:2] for k in base) | set(k[:2] for k in wide))
+    out = {"partitions": len(parts), "same_to_the_end": 0, "rounds_compared_equal": 0, "first_difference": {"same_cost_other_set": 0, "other_cost": 0, "other_status": 0,
+                                                                                                             "one_loop_has_no_such_round": 0}, "examples": []}
+    for part in parts:
+        r = 0
+        while True:
+            a, b = base.get(part + (r,)), wide.get(part + (r,))
+            if a is None and b is None:
+                out["same_to_the_end"] += 1
+                break
+            if a is None or b is None:
+                kind = "one_loop_has_no_such_round"
+            elif a == b:
+                out["rounds_compared_equal"] += 1
+                r += 1
+                continue
+            elif a[0] != b[0]:
+                kind = "other_status"
+            elif a[1] != b[1]:
+                kind = "other_cost"
+            else:
+                kind = "same_cost_other_set"
+            out["first_difference"][kind] += 1
+            if kind != "same_cost_other_set" and len(out["examples"]) < 10:
+                out["examples"].append({"tint": part[0], "partition": part[1], "round": r, "columns": None if a is None else len(a[2]),
+                                        "without": None if a is None else list(a[:2]), "with": None if b is None else list(b[:2])})
+            break
+    return out
+
+
+WIDE_CLASSES = ((65, 128), (129, 256), (257, 512), (513, 1024))
+
+
+def run_wide(workload="many", steps=3, sizes=(128, 256, 1000), n_tints=40, max_nodes=None, depth=None, node_caps=None, host_sample=32, threads=16,
+             loop_runs=0, exact_cols=24, bnb_cols=64):
+    """Per N of `sizes` the workload's first n_tints files, written without gaps, are staged with maximum_ilp_size = N and the FIRST round
+    of every partition is the batch:
+      device   Context.round_models, Context.round_incumbents (the bounds) and Context.round_bnb_wide with 65 .. min(N, 1024) columns, once
+               per node cap of `node_caps` (default: cluster_solve.bnb_wide_node_cap(N); medians over `steps` after a warm-up): per column
+               class 65-128, 129-256, 257-512, 513-1024 the problems of that size, those whose tables do not fit, taken, proven and unproven;
+               nodes, capped tasks, the call, the kernels of fclu_round_bnb_wide_timing (tables, all search launches, the longest launch);
+      solver   HiGHS (cluster_solve.solve_round) with `threads` workers on `host_sample` of the taken problems, evenly spread: wall time of
+               the pool, and the share of them the search proved at the default cap;
+      loop     loop_runs > 0: the whole cluster_tints() loop under exact_cols / bnb_cols with and without wide_cols = min(N, 1024), in turn,
+               loop_runs times each: seconds, solver jobs, and whether tints and logs are the same."""
+    import hashlib
+    import tempfile
+    from multiprocessing import Pool
+    from freddie_amd import cluster, cluster_solve
+    depth = cluster_solve.BNB_DEPTH if depth is None else depth
+    max_nodes = cluster.WIDE_NODES if max_nodes is None else max_nodes
+    pool = Pool(threads)                                         # before the device is opened: the workers never touch it
+    med = lambda xs: float(np.median(xs))
+    rows = []
+    ctx = cluster_prep.Context(0)
+    with tempfile.TemporaryDirectory() as d:
+        paths, n_reads = write_segment_files(workload, d, gaps=False)
+        paths = paths[:n_tints] if n_tints else paths
+        for N in sizes:
+            top = min(N, cluster_solve.BNB_WIDE_MAX_COLS)
+            settings = cluster.ilp_settings(max_ilp=N)
+            tints, part0, _ = cluster.stage_files(paths, settings, ctx, threads)
+            costs = [cluster.garbage_costs(t, "constant") for t in tints]
+            problems = [(t, q, list(rids)) for t, tint in enumerate(tints) for q, (rids, _) in enumerate(tint["partitions"])]
+            row = {"N": N, "problems": len(problems), "caps": []}
+            for node_cap in (node_caps or (cluster_solve.bnb_wide_node_cap(top),)):
+                def device(ps):
+                    arr = ctx.round_models([part0[t] + q for t, q, _ in ps], [rem for _, _, rem in ps])
+                    garbage = [costs[t][i] for t, _, rem in ps for i in rem]
+                    inc = ctx.round_incumbents(garbage, settings["epsilon"], settings["offset"])
+                    t1 = time.perf_counter()
+                    got = ctx.round_bnb_wide(garbage, inc["cost2"], settings["epsilon"], settings["offset"], 65, top, max_nodes, depth, node_cap)
+                    return arr, inc, got, time.perf_counter() - t1
+
+                device(problems)                                                  # warm-up
+                call_s, kern = [], []
+                for _ in range(steps):
+                    arr, inc, got, b = device(problems)
+                    call_s.append(b)
+                    kern.append(ctx.round_bnb_wide_timing())
+                status, cols = got["status"], np.diff(got["col_off"])
+                n_inf = np.diff(arr["inf_off"])
+                fits = np.array([cluster_prep.bnb_wide_lds_bytes(int(r), int(e)) <= cluster_prep.BNB_WIDE_LDS_BYTES for r, e in zip(cols, n_inf)], bool)
+                classes = {}
+                for lo, hi in WIDE_CLASSES:
+                    sel = (cols >= lo) & (cols <= hi) & (arr["refused"] < 0)
+                    classes["%d-%d" % (lo, hi)] = {"problems": int(sel.sum()), "tables_do_not_fit": int((sel & ~fits).sum()), "taken": int((sel & (status != -2)).sum()),
+                                                   "proven": int((sel & ((status == 0) | (status == 1))).sum()), "unproven": int((sel & (status == 2)).sum()),
+                                                   "nodes": int(got["nodes"][sel].sum()), "capped_tasks": int(got["capped"][sel].sum()),
+                                                   "informative_segments_range": [int(n_inf[sel].min()), int(n_inf[sel].max())] if sel.any() else None}
+                row["caps"].append({"node_cap": node_cap, "depth": depth, "taken": got["n_taken"], "launches": got["n_launches"], "nodes": got["nodes_total"],
+                                    "classes": classes, "round_bnb_wide_call_ms": med(call_s) * 1e3, "call_spread_ms": [min(call_s) * 1e3, max(call_s) * 1e3],
+                                    "kernel_ms": {k: med([x[k] for x in kern]) for k in kern[0]}})
+                print("N = %d cap %d: %s" % (N, node_cap, json.dumps(row["caps"][-1])), file=sys.stderr, flush=True)
+            taken = np.flatnonzero(status != -2)
+            pick = taken[np.linspace(0, len(taken) - 1, min(host_sample, len(taken))).astype(int)].tolist() if len(taken) and host_sample else []
+            if pick:
+                jobs = []
+                for p in pick:
+                    t, q, rem = problems[p]
+                    model = cluster_prep.round_model(arr, p)
+                    model["garbage"] = [costs[t][i] for i in rem]; model["max_lg"] = sum(s[2] for s in tints[t]["segs"])
+                    jobs.append((model, settings))
+                t0 = time.perf_counter()
+                solved = pool.map(_solve_timed, jobs, chunksize=1)
+                row["solver"] = {"problems": len(pick), "columns": [int(cols[p]) for p in pick], "workers": threads, "wall_s": time.perf_counter() - t0,
+                                 "solve_s_sum": sum(x[2] for x in solved), "solve_s_longest": max(x[2] for x in solved),
+                                 "statuses": {k: sum(1 for x in solved if x[0] == k) for k in set(x[0] for x in solved)},
+                                 "proven_by_the_search_at_the_last_cap": int(sum(1 for p in pick if status[p] in (0, 1)))}
+                print("N = %d solver: %s" % (N, json.dumps(row["solver"])), file=sys.stderr, flush=True)
+            del tints
+            loops, records = [], {}
+            for run_no in range(loop_runs):
+                for wide_cols in (0, top):
+                    ls = cluster.ilp_settings(max_ilp=N, exact_cols=exact_cols, bnb_cols=bnb_cols, wide_cols=wide_cols)
+                    tints, part0, _ = cluster.stage_files(paths, ls, ctx, threads)
+                    jobs_n = [0]
+
+                    class CountingPool:
+                        def map(self, fn, items, chunksize=1):
+                            jobs_n[0] += len(items)
+                            return pool.map(fn, items, chunksize=chunksize)
+
+                    record = {}
+                    keep = lambda r: record.__setitem__((r["tint"]["id"], r["partition"], r["round"]),
+                                                        (r["status"], r["cost"], tuple(r["remaining"]), None if r["x"] is None else tuple(r["x"])))
+                    t0 = time.perf_counter()
+                    logs = cluster.cluster_tints(tints, part0, ctx, ls, pool=CountingPool(), on_round=keep)
+                    t1 = time.perf_counter()
+                    digest = hashlib.sha256(repr([(t["id"], t["isoforms"], t["garbage_rids"]) for t in tints]).encode() + repr(logs).encode()).hexdigest()[:16]
+                    loops.append({"wide_cols": wide_cols, "run": run_no, "loop_s": t1 - t0, "solver_jobs": jobs_n[0], "digest": digest,
+                                  "rounds": len(record), "statuses": {k: sum(1 for v in record.values() if v[0] == k) for k in set(v[0] for v in record.values())}})
+                    records[(run_no, wide_cols)] = record
+                    print("N = %d loop: %s" % (N, json.dumps(loops[-1])), file=sys.stderr, flush=True)
+                    del tints
+            if loops:
+                row["loop"] = {"runs": loops, "same_tints_and_logs": len(set(r["digest"] for r in loops)) == 1,
+                               "round_for_round": [_compare_rounds(records[(k, 0)], records[(k, top)]) for k in range(loop_runs)]}
+            rows.append(row)
+    ctx.close()
+    pool.close()
+    pool.join()
+    return {"metric": "a round's problems of 65 to min(N, 1024) columns: Context.round_bnb_wide against HiGHS on a sample of the same problems, and the whole loop",
+            "unit": "ms", "data": "synthetic", "source_hash": _build_hash(),
+            "config": {"workload": "cluster-" + workload, **WORKLOADS[workload], "files_taken": len(paths), "reads_written": n_reads, "gaps": "left out", "max_nodes": max_nodes,
+                       "steps": steps, "host_sample": host_sample, "solver_workers": threads, "loop_runs": loop_runs, "exact_cols": exact_cols, "bnb_cols": bnb_cols},
+            "sizes": rows}
+
+
 class _RoundClock:
     """A context that notes when each round starts (its first round_models call) and what the read-out's kernels took."""
 
@@ -867,7 +1025,8 @@ def main():
     ap.add_argument("--workload", default="many", choices=sorted(WORKLOADS))
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--partitions", action="store_true", help="measure Context.partition() against the host tail (FCLU_HOST_PARTITIONS=1)")
-    ap.add_argument("--host-sample", type=int, default=20, help="--partitions: tints the two partition_reads_batch() runs take")
+    ap.add_argument("--host-sample", type=int, default=None, help="--partitions: tints the two partition_reads_batch() runs take (default 20; --rounds 4, --incumbents 2, --exact 24, "
+                                                                  "--bnb 16, --wide 32)")
     ap.add_argument("--front", action="store_true", help="measure the host front + Context.partition against Context.partition_labels")
     ap.add_argument("--files", action="store_true", help="measure the native segment TSV reader + Context.partition_segment against read_segment + partition_labels")
     ap.add_argument("--baseline-steps", type=int, default=1, help="--files: runs of the Python baseline (it takes seconds a run)")
@@ -888,13 +1047,30 @@ def main():
     ap.add_argument("--bnb-node-cap", type=int, default=None, help="--bnb: nodes a task may count (default: cluster_solve.BNB_NODE_CAP)")
     ap.add_argument("--weak-budget", type=float, default=90.0, help="--bnb: seconds of the weak-bound mirror on the sample")
     ap.add_argument("--device-rounds", action="store_true", help="measure the whole cluster_tints loop with device_rounds off and on (profiles/cluster_device_rounds.txt)")
-    ap.add_argument("--sizes", default="24,64,1000", help="--device-rounds: the maximum_ilp_size values")
+    ap.add_argument("--sizes", default=None, help="--device-rounds: the maximum_ilp_size values (default 24,64,1000; --wide: 128,256,1000)")
     ap.add_argument("--runs", type=int, default=3, help="--device-rounds: runs of each setting")
     ap.add_argument("--max-rounds", type=int, default=30, help="--device-rounds: the loop's max_rounds")
     ap.add_argument("--tints", type=int, default=None, help="--device-rounds: the workload's first N files only (default: all)")
     ap.add_argument("--append", action="store_true", help="--device-rounds: add the result to --out instead of replacing it (a size a call, each under its own time limit)")
+    ap.add_argument("--wide", action="store_true", help="measure Context.round_bnb_wide under maximum_ilp_size 128, 256 and 1000 (--sizes) on the first --tints files "
+                                                         "(default 40) against HiGHS on a sample of the same problems (profiles/cluster_bnb_wide.txt)")
+    ap.add_argument("--wide-node-caps", default=None, help="--wide: node caps to run, comma separated (default: cluster_solve.bnb_wide_node_cap(N))")
+    ap.add_argument("--loop-runs", type=int, default=0, help="--wide: runs of the whole loop with and without --exact-wide (default: none)")
     args = ap.parse_args()
-    if args.device_rounds:
+    sample = lambda default: default if args.host_sample is None else args.host_sample
+    if args.wide:
+        args.sizes = args.sizes or "128,256,1000"
+        sizes = tuple(int(v) for v in args.sizes.split(","))
+        caps = tuple(int(v) for v in args.wide_node_caps.split(",")) if args.wide_node_caps else None
+        res = run_wide(args.workload, args.steps, sizes, args.tints or 40, node_caps=caps, host_sample=sample(32),
+                       threads=args.threads, loop_runs=args.loop_runs)
+        with open(args.out or os.path.join(ROOT, "profiles", "cluster_bnb_wide.txt"), "a" if args.append else "w") as f:
+            f.write("tools/cluster_bench.py --wide --workload %s --steps %d --sizes %s --wide-node-caps %s --loop-runs %d  (libfreddie_cluster.so source hash %s)\n" %
+                    (args.workload, args.steps, ",".join(map(str, sizes)), args.wide_node_caps, args.loop_runs, res["source_hash"]))
+            f.write(json.dumps(res, indent=1) + "\n")
+        print(json.dumps(res))
+    elif args.device_rounds:
+        args.sizes = args.sizes or "24,64,1000"
         sizes = tuple(int(v) for v in args.sizes.split(","))
         res = run_device_rounds(args.workload, sizes, args.runs, args.threads, args.max_rounds, n_tints=args.tints)
         with open(args.out or os.path.join(ROOT, "profiles", "cluster_device_rounds.txt"), "a" if args.append else "w") as f:
@@ -906,7 +1082,7 @@ def main():
             print(json.dumps({k: (v if not isinstance(v, dict) else {a: b for a, b in v.items() if a != "runs"}) for k, v in row.items()}))
     elif args.bnb:
         res = run_bnb(args.workload, args.steps, (args.exact_bnb,) if args.exact_bnb is not None else (32, 48, 64), max_nodes=args.bnb_nodes, depth=args.bnb_depth,
-                      node_cap=args.bnb_node_cap, host_sample=16 if args.host_sample == 20 else args.host_sample,
+                      node_cap=args.bnb_node_cap, host_sample=sample(16),
                       solve_budget=args.solve_budget if args.solve_budget != 120.0 else 240.0, weak_budget=args.weak_budget, threads=args.threads)
         with open(args.out or os.path.join(ROOT, "profiles", "cluster_bnb.txt"), "w") as f:
             f.write("tools/cluster_bench.py --bnb --workload %s --steps %d  (libfreddie_cluster.so source hash %s)\n" % (args.workload, args.steps, res["source_hash"]))
@@ -914,21 +1090,21 @@ def main():
         print(json.dumps(res))
     elif args.exact:
         res = run_exact(args.workload, args.steps, args.max_ilp, (args.exact_small,) if args.exact_small is not None else (8, 12, 16, 20, 24), args.exact_masks,
-                        host_sample=24 if args.host_sample == 20 else args.host_sample, solve_budget=args.solve_budget, threads=args.threads)
+                        host_sample=sample(24), solve_budget=args.solve_budget, threads=args.threads)
         with open(args.out or os.path.join(ROOT, "profiles", "cluster_exact.txt"), "w") as f:
             f.write("tools/cluster_bench.py --exact --workload %s --steps %d --max-ilp %d --exact-masks %d  (libfreddie_cluster.so source hash %s)\n" %
                     (args.workload, args.steps, args.max_ilp, args.exact_masks, res["source_hash"]))
             f.write(json.dumps(res, indent=1) + "\n")
         print(json.dumps(res))
     elif args.incumbents:
-        res = run_incumbents(args.workload, args.steps, host_sample=2 if args.host_sample == 20 else args.host_sample,
+        res = run_incumbents(args.workload, args.steps, host_sample=sample(2),
                              solve_budget=args.solve_budget if args.solve_budget != 120.0 else 300.0, threads=args.threads, max_seeds=args.max_seeds)
         with open(args.out or os.path.join(ROOT, "profiles", "cluster_incumbents.txt"), "w") as f:
             f.write("tools/cluster_bench.py --incumbents --workload %s --steps %d  (libfreddie_cluster.so source hash %s)\n" % (args.workload, args.steps, res["source_hash"]))
             f.write(json.dumps(res, indent=1) + "\n")
         print(json.dumps(res))
     elif args.rounds:
-        res = run_rounds(args.workload, args.steps, host_sample=min(args.host_sample, 4) if args.host_sample == 20 else args.host_sample,
+        res = run_rounds(args.workload, args.steps, host_sample=sample(4),
                          solve_budget=args.solve_budget, threads=args.threads)
         with open(args.out or os.path.join(ROOT, "profiles", "cluster_rounds.txt"), "w") as f:
             f.write("tools/cluster_bench.py --rounds --workload %s --steps %d\n" % (args.workload, args.steps))
@@ -939,7 +1115,7 @@ def main():
     elif args.front:
         print(json.dumps(run_front(args.workload, args.steps)))
     elif args.partitions:
-        print(json.dumps(run_partitions(args.workload, args.steps, host_sample=args.host_sample)))
+        print(json.dumps(run_partitions(args.workload, args.steps, host_sample=sample(20))))
     else:
         print(json.dumps(run(args.workload, args.steps)))
 
