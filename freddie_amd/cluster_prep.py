@@ -159,7 +159,7 @@ def split_list_evenly(l, m):
 # ---------------------------------------------------------------------------------------------------------------
 CLUSTER_SO = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libfreddie_cluster.so")
 CLUSTER_SRC = [os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "freddie_cluster.hip")]
-CLUSTER_HEADERS = [os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", n) for n in ("clu_incumbent.h", "clu_exact.h", "clu_bnb.h", "clu_bnb_wide.h", "clu_readout.h")]
+CLUSTER_HEADERS = [os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", n) for n in ("clu_incumbent.h", "clu_exact.h", "clu_bnb.h", "clu_bnb_wide.h", "clu_readout.h", "clu_plan.h")]
 EXPORTS = ["fclu_abi_version", "fclu_create", "fclu_destroy", "fclu_last_error", "fclu_compat_graph", "fclu_last_timing",
            "fclu_last_paths",
            "fclu_partition", "fclu_partition_adj", "fclu_partition_results", "fclu_partition_timing",
@@ -624,10 +624,14 @@ class Context:
                     grow_steps=_copy_out(i.grow_steps, P, np.int32), repair_steps=_copy_out(i.repair_steps, P, np.int32),
                     mem_off=_copy_out(i.mem_off, P + 1, np.int64), mem=_copy_out(i.mem, int(i.n_mem), np.int32))
 
+    def _times(self, entry, *names):
+        """What a *_timing entry point hands out, a float for each name."""
+        v = [ctypes.c_float() for _ in names]
+        entry(self._h, *[ctypes.byref(x) for x in v])
+        return {n: x.value for n, x in zip(names, v)}
+
     def round_incumbent_timing(self):
-        a, b, f = ctypes.c_float(), ctypes.c_float(), ctypes.c_float()
-        self._L.fclu_round_incumbent_timing(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(f))
-        return dict(conflict_ms=a.value, starts_ms=b.value, pick_ms=f.value)
+        return self._times(self._L.fclu_round_incumbent_timing, "conflict_ms", "starts_ms", "pick_ms")
 
     def round_exact(self, garbage, epsilon, offset, max_cols, max_masks):
         """The proven optimum of every small problem of the last round_models() call by enumeration, one device call
@@ -649,9 +653,7 @@ class Context:
                     n_taken=int(x.n_taken), n_masks=int(x.n_masks), n_launches=int(x.n_launches))
 
     def round_exact_timing(self):
-        a, b, f = ctypes.c_float(), ctypes.c_float(), ctypes.c_float()
-        self._L.fclu_round_exact_timing(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(f))
-        return dict(prep_ms=a.value, search_ms=b.value, longest_launch_ms=f.value)
+        return self._times(self._L.fclu_round_exact_timing, "prep_ms", "search_ms", "longest_launch_ms")
 
     def round_bnb(self, garbage, ub2, epsilon, offset, min_cols, max_cols, max_nodes, depth=cluster_solve.BNB_DEPTH, node_cap=cluster_solve.BNB_NODE_CAP):
         """A branch and bound over every problem of min_cols .. max_cols (<= 64) columns of the last round_models() call, one device call
@@ -661,26 +663,32 @@ class Context:
         1 infeasible, 2 unproven, -2 not taken or refused), cost2 (-1: no set found), mask (uint64, bit c = column c), nodes and capped per
         problem, col_off, and n_taken, n_launches, nodes_total; round_bnb_solution() cuts one problem out."""
         g2, col_off = self._garbage2("round_bnb", garbage)
+        out = self._round_search("round_bnb", g2, col_off, ub2, epsilon, offset, min_cols, max_cols, max_nodes, depth, node_cap, 1)
+        out["mask"] = out["mask"].reshape(-1)
+        return out
+
+    def _round_search(self, name, g2, col_off, ub2, epsilon, offset, min_cols, max_cols, max_nodes, depth, node_cap, words):
+        """round_bnb() and round_bnb_wide() behind their own arguments: the entry points fclu_<name> / fclu_<name>_results, the resolved
+        depth and node_cap, and the words of a problem's mask (fclu_bnb_wide has fclu_bnb's layout, so _Bnb reads both); mask comes
+        back as a (problems, words) array."""
         ub = np.ascontiguousarray(np.asarray(ub2, np.int64).reshape(-1))
         if ub.size != col_off.size - 1:
-            raise ClusterError("round_bnb: %d bounds for the %d problems of the last round_models() call" % (ub.size, col_off.size - 1))
-        rc = self._L.fclu_round_bnb(self._h, g2.ctypes.data if g2.size else None, ub.ctypes.data if ub.size else None, 1.0 - float(epsilon),
-                                    1.0 + float(epsilon), int(offset), int(min_cols), int(max_cols), int(depth), int(node_cap), int(max_nodes))
+            raise ClusterError("%s: %d bounds for the %d problems of the last round_models() call" % (name, ub.size, col_off.size - 1))
+        rc = getattr(self._L, "fclu_" + name)(self._h, g2.ctypes.data if g2.size else None, ub.ctypes.data if ub.size else None, 1.0 - float(epsilon),
+                                              1.0 + float(epsilon), int(offset), int(min_cols), int(max_cols), int(depth), int(node_cap), int(max_nodes))
         if rc != 0:
-            raise ClusterError("fclu_round_bnb: " + self._L.fclu_last_error(self._h).decode(), rc)
+            raise ClusterError("fclu_%s: " % name + self._L.fclu_last_error(self._h).decode(), rc)
         b = _Bnb()
-        rc = self._L.fclu_round_bnb_results(self._h, ctypes.byref(b))
+        rc = getattr(self._L, "fclu_%s_results" % name)(self._h, ctypes.byref(b))
         if rc != 0:
-            raise ClusterError("fclu_round_bnb_results: " + self._L.fclu_last_error(self._h).decode(), rc)
+            raise ClusterError("fclu_%s_results: " % name + self._L.fclu_last_error(self._h).decode(), rc)
         P = b.n_prob
         return dict(n_prob=P, col_off=col_off, status=_copy_out(b.status, P, np.int32), cost2=_copy_out(b.cost2, P, np.int64),
-                    mask=_copy_out(b.mask, P, np.uint64), nodes=_copy_out(b.nodes, P, np.int64), capped=_copy_out(b.capped, P, np.int32),
-                    n_taken=int(b.n_taken), n_launches=int(b.n_launches), nodes_total=int(b.nodes_total))
+                    mask=_copy_out(b.mask, P * words, np.uint64).reshape(P, words), nodes=_copy_out(b.nodes, P, np.int64),
+                    capped=_copy_out(b.capped, P, np.int32), n_taken=int(b.n_taken), n_launches=int(b.n_launches), nodes_total=int(b.nodes_total))
 
     def round_bnb_timing(self):
-        a, b, f = ctypes.c_float(), ctypes.c_float(), ctypes.c_float()
-        self._L.fclu_round_bnb_timing(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(f))
-        return dict(prep_ms=a.value, search_ms=b.value, longest_launch_ms=f.value)
+        return self._times(self._L.fclu_round_bnb_timing, "prep_ms", "search_ms", "longest_launch_ms")
 
     def round_bnb_wide(self, garbage, ub2, epsilon, offset, min_cols, max_cols, max_nodes, depth=None, node_cap=None):
         """round_bnb() for the problems of min_cols .. max_cols (<= 1024) columns whose tables fit (bnb_wide_lds_bytes), one device call
@@ -694,27 +702,12 @@ class Context:
             cols = np.diff(col_off)
             cols = cols[(cols >= int(min_cols)) & (cols <= int(max_cols))]
             node_cap = cluster_solve.bnb_wide_node_cap(int(cols.max()) if cols.size else int(max_cols))
-        ub = np.ascontiguousarray(np.asarray(ub2, np.int64).reshape(-1))
-        if ub.size != col_off.size - 1:
-            raise ClusterError("round_bnb_wide: %d bounds for the %d problems of the last round_models() call" % (ub.size, col_off.size - 1))
-        rc = self._L.fclu_round_bnb_wide(self._h, g2.ctypes.data if g2.size else None, ub.ctypes.data if ub.size else None, 1.0 - float(epsilon),
-                                         1.0 + float(epsilon), int(offset), int(min_cols), int(max_cols), int(depth), int(node_cap), int(max_nodes))
-        if rc != 0:
-            raise ClusterError("fclu_round_bnb_wide: " + self._L.fclu_last_error(self._h).decode(), rc)
-        b = _Bnb()                                           # (fclu_bnb_wide has fclu_bnb's layout; its mask holds 16 words a problem)
-        rc = self._L.fclu_round_bnb_wide_results(self._h, ctypes.byref(b))
-        if rc != 0:
-            raise ClusterError("fclu_round_bnb_wide_results: " + self._L.fclu_last_error(self._h).decode(), rc)
-        P = b.n_prob
-        return dict(n_prob=P, col_off=col_off, status=_copy_out(b.status, P, np.int32), cost2=_copy_out(b.cost2, P, np.int64),
-                    mask=_copy_out(b.mask, P * BNB_WIDE_WORDS, np.uint64).reshape(P, BNB_WIDE_WORDS), nodes=_copy_out(b.nodes, P, np.int64),
-                    capped=_copy_out(b.capped, P, np.int32), n_taken=int(b.n_taken), n_launches=int(b.n_launches), nodes_total=int(b.nodes_total),
-                    depth=int(depth), node_cap=int(node_cap))
+        out = self._round_search("round_bnb_wide", g2, col_off, ub2, epsilon, offset, min_cols, max_cols, max_nodes, depth, node_cap, BNB_WIDE_WORDS)
+        out.update(depth=int(depth), node_cap=int(node_cap))
+        return out
 
     def round_bnb_wide_timing(self):
-        a, b, f = ctypes.c_float(), ctypes.c_float(), ctypes.c_float()
-        self._L.fclu_round_bnb_wide_timing(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(f))
-        return dict(prep_ms=a.value, search_ms=b.value, longest_launch_ms=f.value)
+        return self._times(self._L.fclu_round_bnb_wide_timing, "prep_ms", "search_ms", "longest_launch_ms")
 
     def round_readout(self, sets):
         """The isoforms of the last round_models() call's problems (either form) from their accepted column sets, one device call
@@ -747,9 +740,7 @@ class Context:
                     e_off=_copy_out(o.e_off, P + 1, np.int64), e=_copy_out(o.e, int(o.n_e), np.uint8), sel=sel)
 
     def round_readout_timing(self):
-        a, b = ctypes.c_float(), ctypes.c_float()
-        self._L.fclu_round_readout_timing(self._h, ctypes.byref(a), ctypes.byref(b))
-        return dict(exons_ms=a.value, corr_ms=b.value)
+        return self._times(self._L.fclu_round_readout_timing, "exons_ms", "corr_ms")
 
     def readout_paths(self):
         """The launch census of the last round_readout() call (include/freddie_cluster.h, FCLU_PATH_READOUT_*): sets (problems with a
@@ -763,29 +754,19 @@ class Context:
         return dict(sets=sets, members=members, wide_stores=bool(stores & STORE_WIDE), byte_stores=bool(stores & STORE_BYTES))
 
     def round_timing(self):
-        a, b, f = ctypes.c_float(), ctypes.c_float(), ctypes.c_float()
-        self._L.fclu_round_timing(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(f))
-        return dict(count_ms=a.value, gaps_ms=b.value, fill_ms=f.value)
+        return self._times(self._L.fclu_round_timing, "count_ms", "gaps_ms", "fill_ms")
 
     def group_timing(self):
-        a, b = ctypes.c_float(), ctypes.c_float()
-        self._L.fclu_group_timing(self._h, ctypes.byref(a), ctypes.byref(b))
-        return dict(keys_ms=a.value, dedupe_ms=b.value)
+        return self._times(self._L.fclu_group_timing, "keys_ms", "dedupe_ms")
 
     def preprocess_timing(self):
-        a, b = ctypes.c_float(), ctypes.c_float()
-        self._L.fclu_preprocess_timing(self._h, ctypes.byref(a), ctypes.byref(b))
-        return dict(rows_ms=a.value, dedupe_ms=b.value)
+        return self._times(self._L.fclu_preprocess_timing, "rows_ms", "dedupe_ms")
 
     def partition_timing(self):
-        a, b = ctypes.c_float(), ctypes.c_float()
-        self._L.fclu_partition_timing(self._h, ctypes.byref(a), ctypes.byref(b))
-        return dict(components_ms=a.value, pairs_ms=b.value)
+        return self._times(self._L.fclu_partition_timing, "components_ms", "pairs_ms")
 
     def last_timing(self):
-        a, b = ctypes.c_float(), ctypes.c_float()
-        self._L.fclu_last_timing(self._h, ctypes.byref(a), ctypes.byref(b))
-        return dict(compat_ms=a.value, prune_ms=b.value)
+        return self._times(self._L.fclu_last_timing, "compat_ms", "prune_ms")
 
     def last_paths(self):
         """The launch census of the last call that built a graph (include/freddie_cluster.h, fclu_last_paths): compat_form "rank" /

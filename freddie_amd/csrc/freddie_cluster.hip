@@ -27,6 +27,7 @@
 #include "clu_bnb.h"
 #include "clu_bnb_wide.h"
 #include "clu_readout.h"
+#include "clu_plan.h"
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 
@@ -1405,42 +1406,46 @@ constexpr i64 kExactLaunchMasks = 1ll << 24;  // masks one launch evaluates (DES
 constexpr int kExactMaxLaunches = 4096;       // launches of one call (an event each)
 constexpr int kExactLdsBytes = 80 * 1024;     // the reduction's 4 keys, 2 x 9600 table words, 2 x 24 words of conflicts and g2
 
-// the support word of informative segment k (numbered through the batch); sup_off closes with n_sup, which the device array does not hold
-__device__ __forceinline__ unsigned exact_sup_word(i64 k, const i64 *sup_off, i64 n_inf, const int *sup_cols, i64 n_sup, int R) {
+// the support word (W: 32 bits for the exact solve, 64 for the branch and bound) of informative segment k (numbered through the batch);
+// sup_off closes with n_sup, which the device array does not hold
+template <typename W>
+__device__ __forceinline__ W sup_word(i64 k, const i64 *sup_off, i64 n_inf, const int *sup_cols, i64 n_sup, int R) {
     const i64 a = ex_clamp(sup_off[k], 0, n_sup), b = ex_clamp(k + 1 < n_inf ? sup_off[k + 1] : n_sup, a, n_sup);
-    unsigned m = 0u;
-    for (i64 s = a; s < b; ++s) { const int c = sup_cols[s]; if ((unsigned)c < (unsigned)R) m |= 1u << c; }
+    W m = 0;
+    for (i64 s = a; s < b; ++s) { const int c = sup_cols[s]; if ((unsigned)c < (unsigned)R) m |= W(1) << c; }
     return m;
 }
 
-// A workgroup per taken problem: its transposed table (zeroed before the launch: the support words are stored, the correction words and the
-// conflict words are ORed in, which does not depend on the order the atomics arrive in) and its groups' support words.
-__global__ void __launch_bounds__(256) k_exact_prep(const int *list, const ExactProb *probs, const int *inf_seg, const i64 *sup_off, i64 n_inf, const int *sup_cols,
-                                                    i64 n_sup, const i64 *corr_off, i64 n_cols, const int *corr_seg, i64 n_corr, const int2 *pairs,
-                                                    const i64 *grp_seg_off, const int *grp_seg, i64 n_grp_seg, unsigned *tab, unsigned *conf, unsigned *gsup) {
+// A workgroup per taken problem of at most 8 sizeof(W) columns: its transposed table (zeroed before the launch: the support words are stored,
+// the correction words and the conflict words are ORed in, which does not depend on the order the atomics arrive in) and its groups' support
+// words.  fclu_round_exact runs it with 32-bit words, fclu_round_bnb with 64-bit ones.
+template <typename W>
+__global__ void __launch_bounds__(256) k_narrow_prep(const int *list, const ExactProb *probs, const int *inf_seg, const i64 *sup_off, i64 n_inf, const int *sup_cols,
+                                                     i64 n_sup, const i64 *corr_off, i64 n_cols, const int *corr_seg, i64 n_corr, const int2 *pairs,
+                                                     const i64 *grp_seg_off, const int *grp_seg, i64 n_grp_seg, W *tab, W *conf, W *gsup) {
     const ExactProb d = probs[list[blockIdx.x]];
     const int R = d.n, E = d.n_inf, tid = threadIdx.x;
     const int *inf = inf_seg + d.inf0;
-    for (int k = tid; k < E; k += 256) tab[2 * (d.inf0 + k)] = exact_sup_word(d.inf0 + k, sup_off, n_inf, sup_cols, n_sup, R);
+    for (int k = tid; k < E; k += 256) tab[2 * (d.inf0 + k)] = sup_word<W>(d.inf0 + k, sup_off, n_inf, sup_cols, n_sup, R);
     for (int c = 0; c < R; ++c) {
         const i64 a = ex_clamp(corr_off[d.col0 + c], 0, n_corr), b = ex_clamp(d.col0 + c + 1 < n_cols ? corr_off[d.col0 + c + 1] : n_corr, a, n_corr);
         for (i64 x = a + tid; x < b; x += 256) {
             const int k = ex_find_seg(inf, E, corr_seg[x]);
-            if (k >= 0) atomicOr(&tab[2 * (d.inf0 + k) + 1], 1u << c);
+            if (k >= 0) atomicOr(&tab[2 * (d.inf0 + k) + 1], W(1) << c);
         }
     }
     for (i64 i = d.pair0 + tid; i < d.pair1; i += 256) {
         const int2 pr = pairs[i];
         if ((unsigned)pr.x < (unsigned)R && (unsigned)pr.y < (unsigned)R) {
-            atomicOr(&conf[d.col0 + pr.x], 1u << pr.y);
-            atomicOr(&conf[d.col0 + pr.y], 1u << pr.x);
+            atomicOr(&conf[d.col0 + pr.x], W(1) << pr.y);
+            atomicOr(&conf[d.col0 + pr.y], W(1) << pr.x);
         }
     }
     if (d.grp1 > d.grp0) {
         const i64 s0 = ex_clamp(grp_seg_off[d.grp0], 0, n_grp_seg), s1 = ex_clamp(grp_seg_off[d.grp1], s0, n_grp_seg);
         for (i64 s = s0 + tid; s < s1; s += 256) {
             const int k = ex_find_seg(inf, E, grp_seg[s]);
-            gsup[s] = k >= 0 ? exact_sup_word(d.inf0 + k, sup_off, n_inf, sup_cols, n_sup, R) : 0u;
+            gsup[s] = k >= 0 ? sup_word<W>(d.inf0 + k, sup_off, n_inf, sup_cols, n_sup, R) : W(0);
         }
     }
 }
@@ -1478,7 +1483,7 @@ __global__ void __launch_bounds__(256) k_exact_search(const int4 *items, const E
 // The branch and bound over a round's problems of up to 64 columns (fclu_round_bnb): a problem's first D = min(R, depth) columns are
 // fixed by a task number, a lane runs one task depth first with the bound, the row test and the leaf test of clu_bnb.h, and the
 // smallest (cost2, mask) over a problem's tasks is its proven optimum when no task ran into node_cap.  The definition is
-// cluster_solve.exact_bnb()'s docstring.  The tables are k_exact_prep's with 64-bit words; the problems' descriptor is ExactProb.
+// cluster_solve.exact_bnb()'s docstring.  The tables are k_narrow_prep's with 64-bit words; the problems' descriptor is ExactProb.
 // ================================================================================================================
 constexpr int kBnbWgTasks = 256;               // tasks one workgroup runs: one a lane
 constexpr i64 kBnbLaunchNodes = 1ll << 24;     // task-nodes of budget (tasks x node_cap) one launch holds (profiles/cluster_bnb.txt)
@@ -1487,44 +1492,6 @@ constexpr int kBnbMaxDepth = 20;               // 2^20 tasks a problem at the mo
 constexpr int kBnbLdsBytes = 160 * 1024;       // a workgroup's LDS on this part: 16 bytes an informative segment, 12 a column
 constexpr int kBnbMaxInf = (kBnbLdsBytes - 12 * kBnbMaxCols) / 16;      // 10 192 informative segments (a row holds 32 kMaxWords = 9 600: every model fits)
 static_assert(kBnbMaxInf < (1 << kBnbPlanes), "bnb_lb2 counts a column's corrections in kBnbPlanes bits");
-
-__device__ __forceinline__ u64 bnb_sup_word(i64 k, const i64 *sup_off, i64 n_inf, const int *sup_cols, i64 n_sup, int R) {
-    const i64 a = ex_clamp(sup_off[k], 0, n_sup), b = ex_clamp(k + 1 < n_inf ? sup_off[k + 1] : n_sup, a, n_sup);
-    u64 m = 0ull;
-    for (i64 s = a; s < b; ++s) { const int c = sup_cols[s]; if ((unsigned)c < (unsigned)R) m |= 1ull << c; }
-    return m;
-}
-
-// k_exact_prep with 64-bit words: a workgroup per taken problem; tab and conf are zeroed before the launch and ORed into.
-__global__ void __launch_bounds__(256) k_bnb_prep(const int *list, const ExactProb *probs, const int *inf_seg, const i64 *sup_off, i64 n_inf, const int *sup_cols,
-                                                  i64 n_sup, const i64 *corr_off, i64 n_cols, const int *corr_seg, i64 n_corr, const int2 *pairs,
-                                                  const i64 *grp_seg_off, const int *grp_seg, i64 n_grp_seg, u64 *tab, u64 *conf, u64 *gsup) {
-    const ExactProb d = probs[list[blockIdx.x]];
-    const int R = d.n, E = d.n_inf, tid = threadIdx.x;
-    const int *inf = inf_seg + d.inf0;
-    for (int k = tid; k < E; k += 256) tab[2 * (d.inf0 + k)] = bnb_sup_word(d.inf0 + k, sup_off, n_inf, sup_cols, n_sup, R);
-    for (int c = 0; c < R; ++c) {
-        const i64 a = ex_clamp(corr_off[d.col0 + c], 0, n_corr), b = ex_clamp(d.col0 + c + 1 < n_cols ? corr_off[d.col0 + c + 1] : n_corr, a, n_corr);
-        for (i64 x = a + tid; x < b; x += 256) {
-            const int k = ex_find_seg(inf, E, corr_seg[x]);
-            if (k >= 0) atomicOr(&tab[2 * (d.inf0 + k) + 1], 1ull << c);
-        }
-    }
-    for (i64 i = d.pair0 + tid; i < d.pair1; i += 256) {
-        const int2 pr = pairs[i];
-        if ((unsigned)pr.x < (unsigned)R && (unsigned)pr.y < (unsigned)R) {
-            atomicOr(&conf[d.col0 + pr.x], 1ull << pr.y);
-            atomicOr(&conf[d.col0 + pr.y], 1ull << pr.x);
-        }
-    }
-    if (d.grp1 > d.grp0) {
-        const i64 s0 = ex_clamp(grp_seg_off[d.grp0], 0, n_grp_seg), s1 = ex_clamp(grp_seg_off[d.grp1], s0, n_grp_seg);
-        for (i64 s = s0 + tid; s < s1; s += 256) {
-            const int k = ex_find_seg(inf, E, grp_seg[s]);
-            gsup[s] = k >= 0 ? bnb_sup_word(d.inf0 + k, sup_off, n_inf, sup_cols, n_sup, R) : 0ull;
-        }
-    }
-}
 
 struct BnbTask { i64 cost2; u64 mask; int nodes, capped; };      // a task's result (BnbResult of clu_bnb.h)
 
@@ -1866,11 +1833,12 @@ struct fclu_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
     // every event, one list to create and destroy; by stage: the graph (ev), fclu_partition (pev), _preprocess (qev), _group_reads (gev), _round_models (rev),
-    // _round_incumbents (iev), _round_exact's prep (xev; its search launches have an event each in xl_ev, created as a call needs them), _round_bnb's prep and reduction (bev; bl_ev likewise),
-    // _round_readout (oev), _round_bnb_wide's prep and reduction (wev; wl_ev as bl_ev)
+    // _round_incumbents (iev), _round_exact's prep (xev), _round_bnb's prep and reduction (bev), _round_readout (oev), _round_bnb_wide's prep and reduction (wev).
+    // launch_ev: an event in front of and behind every search launch of the round call that is running, created as a call needs them (the
+    // calls follow one another on the stream and each reads its times before it returns)
     hipEvent_t events[3 + 6 + 6 + 5 + 5 + 4 + 2 + 3 + 3 + 3] = {};
     hipEvent_t *const ev = events, *const pev = ev + 3, *const qev = pev + 6, *const gev = qev + 6, *const rev = gev + 5, *const iev = rev + 5, *const xev = iev + 4, *const bev = xev + 2, *const oev = bev + 3, *const wev = oev + 3;
-    std::vector<hipEvent_t> xl_ev, bl_ev, wl_ev;
+    std::vector<hipEvent_t> launch_ev;
     std::string err;
     float compat_ms = 0.f, prune_ms = 0.f;
     int32_t paths[FCLU_N_PATHS] = {};     // the last graph call's launch census and the last read-out's (fclu_last_paths)
@@ -1964,11 +1932,16 @@ struct fclu_ctx {
     float iconf_ms = 0.f, istart_ms = 0.f, ipick_ms = 0.f;
     fclu_incumbents incs = {};
     bool have_incs = false;
-    // fclu_round_exact(): the same input; device arrays (xd: the problems, the taken ones' list, the work items, the transposed tables, the
-    // conflict words, the groups' support words, g2, a key per problem) and the pinned copies fclu_round_exact_results() hands out (xh)
-    struct {
-        Buf<ExactProb> probs; Buf<int4> items; Buf<unsigned> tab, conf, gsup; Buf<u64> best;
-        Buf<int> list, g2;
+    // fclu_round_exact(), fclu_round_bnb(), fclu_round_bnb_wide(): the same input.  One driver serves the three (run_round_call and the
+    // helpers in front of it); a call owns its device arrays and the pinned copies its _results() hands out.  RoundCallBufs is what every call
+    // uploads (the work items, the taken problems' list, g2), SearchBufs what the two searches add (the bounds, per problem its first task and
+    // task count); SearchHost is the searches' pinned side (a result per problem as the device leaves it, and the arrays of fclu_bnb).
+    struct RoundCallBufs { Buf<int4> items; Buf<int> list, g2; };
+    struct SearchBufs : RoundCallBufs { Buf<i64> ub2, task_off, n_tasks; };
+    template <typename Out> struct SearchHost { HostBuf<Out> out; HostBuf<int64_t> cost2, nodes; HostBuf<uint64_t> mask; HostBuf<int32_t> status, capped; };
+    // fclu_round_exact(): xd adds the problems, the transposed tables, the conflict words, the groups' support words and a key per problem
+    struct : RoundCallBufs {
+        Buf<ExactProb> probs; Buf<unsigned> tab, conf, gsup; Buf<u64> best;
     } xd;
     struct {
         HostBuf<u64> best; HostBuf<int64_t> cost2; HostBuf<uint32_t> mask;
@@ -1976,29 +1949,20 @@ struct fclu_ctx {
     float xprep_ms = 0.f, xsearch_ms = 0.f, xlongest_ms = 0.f;
     fclu_exact exact = {};
     bool have_exact = false;
-    // fclu_round_bnb(): the same input; device arrays (bd: the problems, the taken ones' list, the work items, the 64-bit tables, conflict
-    // words and groups' support words, g2, the bounds, per problem its first task and task count, a result per task and per problem) and
-    // the pinned copies fclu_round_bnb_results() hands out (bh)
-    struct {
-        Buf<ExactProb> probs; Buf<int4> items; Buf<u64> tab, conf, gsup; Buf<i64> ub2, task_off, n_tasks; Buf<BnbTask> tasks; Buf<BnbOut> out;
-        Buf<int> list, g2;
+    // fclu_round_bnb(): bd adds the problems, the 64-bit tables, conflict words and groups' support words, a result per task and per problem
+    struct : SearchBufs {
+        Buf<ExactProb> probs; Buf<u64> tab, conf, gsup; Buf<BnbTask> tasks; Buf<BnbOut> out;
     } bd;
-    struct {
-        HostBuf<BnbOut> out; HostBuf<int64_t> cost2, nodes; HostBuf<uint64_t> mask; HostBuf<int32_t> status, capped;
-    } bh;
+    SearchHost<BnbOut> bh;
     float bprep_ms = 0.f, bsearch_ms = 0.f, blongest_ms = 0.f;
     fclu_bnb bnb = {};
     bool have_bnb = false;
-    // fclu_round_bnb_wide(): the same input; device arrays (wd: the problems, the taken ones' list, the work items, the tables by column,
-    // the conflict rows, the group segments' places, g2, the bounds, per problem its first task and task count, a result per task and per
-    // problem with its 16 mask words) and the pinned copies fclu_round_bnb_wide_results() hands out (wh)
-    struct {
-        Buf<BwProb> probs; Buf<int4> items; Buf<u64> tab, conf, out_mask; Buf<i64> ub2, task_off, n_tasks; Buf<BwTask> tasks; Buf<BwOut> out;
-        Buf<int> list, g2, gk;
+    // fclu_round_bnb_wide(): wd adds the problems, the tables by column, the conflict rows, the group segments' places, a result per task
+    // and per problem with its 16 mask words
+    struct : SearchBufs {
+        Buf<BwProb> probs; Buf<u64> tab, conf, out_mask; Buf<BwTask> tasks; Buf<BwOut> out; Buf<int> gk;
     } wd;
-    struct {
-        HostBuf<BwOut> out; HostBuf<int64_t> cost2, nodes; HostBuf<uint64_t> mask; HostBuf<int32_t> status, capped;
-    } wh;
+    SearchHost<BwOut> wh;
     float wprep_ms = 0.f, wsearch_ms = 0.f, wlongest_ms = 0.f;
     fclu_bnb_wide wide = {};
     bool have_wide = false;
@@ -2018,9 +1982,7 @@ struct fclu_ctx {
         (void)hipSetDevice(device);
         if (stream) { (void)hipStreamSynchronize(stream); (void)hipStreamDestroy(stream); }
         for (hipEvent_t e : events) if (e) (void)hipEventDestroy(e);
-        for (hipEvent_t e : xl_ev) if (e) (void)hipEventDestroy(e);
-        for (hipEvent_t e : bl_ev) if (e) (void)hipEventDestroy(e);
-        for (hipEvent_t e : wl_ev) if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : launch_ev) if (e) (void)hipEventDestroy(e);
     }
 };
 
@@ -2109,6 +2071,16 @@ int bits_for(i64 n) { int b = 1; while (b < 32 && (1ll << b) < n) ++b; return b;
 
 // the *_timing entry points: two times of the last call, each wanted or not
 int two_times(float *a, float va, float *b, float vb) { if (a) *a = va; if (b) *b = vb; return FCLU_OK; }
+
+int three_times(float *a, float va, float *b, float vb, float *d, float vd) { if (d) *d = vd; return two_times(a, va, b, vb); }
+
+// A round call's result struct, when the call stands (fclu_round_*_results; call: the entry point that makes it).
+template <typename Result>
+int round_call_results(fclu_ctx *c, bool have, const Result &r, Result *out, const char *call) {
+    if (!have || !c->have_rounds) return fail(c, FCLU_ERR_ARG, "%s_results: no result (the last %s call failed, none was made, or a later call ended it)", call, call);
+    *out = r;
+    return FCLU_OK;
+}
 
 // ---- staging of a batch ------------------------------------------------------------------------------------------------------
 // What the host derives from a batch's shape (stage_tints) and the graph kernels are launched with (compat_run).
@@ -3274,9 +3246,9 @@ int incumbents_device(fclu_ctx *c, const Knobs &k, const int32_t *g2, double lo_
     return FCLU_OK;
 }
 
-// ---- the exact solve of the last round's small problems (fclu_round_exact) ------------------------------------------------------
-// Problem p of the last round as fclu_round_exact and fclu_round_bnb describe it to their kernels, and whether its offsets lie inside
-// the round's arrays (asked only of a problem that is taken).
+// ---- the searches over the last round's problems (fclu_round_exact, fclu_round_bnb, fclu_round_bnb_wide): the shared driver -------
+// Problem p of the last round as the round calls describe it to their kernels, and whether its offsets lie inside the round's arrays
+// (asked only of a problem that is taken).
 void fill_exact_prob(const fclu_ctx *c, int p, ExactProb &d) {
     const fclu_rounds &o = c->rounds;
     const RoundProb &rp = c->r_probs[(size_t)p];
@@ -3293,22 +3265,157 @@ bool exact_prob_in_range(const fclu_ctx *c, int p, const ExactProb &d) {
              d.col0 + d.n > o.n_cols);
 }
 
+// What every round call checks before it touches the device, in the order the refusals fire: a round stands behind the call, the call's own
+// numbers (own_args), offset and the factors, g2 is there, the call's other arrays are (own_arrays), g2 is not negative, the host still
+// has the round's problems.  name: the entry point, for the message.
+template <typename OwnArgs, typename OwnArrays>
+int round_preconditions(fclu_ctx *c, const char *name, const int32_t *g2, double lo_f, double hi_f, int32_t offset, OwnArgs own_args, OwnArrays own_arrays) {
+    if (!c->have_rounds || !c->round_ready || !c->round_src_ok || !c->have_parts)
+        return fail(c, FCLU_ERR_ARG, "%s: no successful fclu_round_models() stands behind the call (none was made, it failed, or a later "
+                                     "call ended the rounds' source)", name);
+    const i64 C = c->rounds.n_cols;
+    RC_TRY(own_args());
+    if (offset < 0 || !(lo_f == lo_f) || !(hi_f == hi_f) || lo_f - lo_f != 0.0 || hi_f - hi_f != 0.0)
+        return fail(c, FCLU_ERR_ARG, "%s: offset is negative or a factor is not finite", name);
+    if (C > 0 && !g2) return fail(c, FCLU_ERR_ARG, "%s: g2 is null", name);
+    RC_TRY(own_arrays());
+    for (i64 x = 0; x < C; ++x) if (g2[x] < 0) return fail(c, FCLU_ERR_ARG, "%s: g2[%lld] is negative", name, x);
+    if ((int)c->r_probs.size() != c->rounds.n_prob) return fail(c, FCLU_ERR_ARG, "%s: the round's problems are gone", name);
+    return FCLU_OK;
+}
+
+// round_preconditions with what the two branch-and-bound calls add: the sizes (cols_limit: the most columns the call's kernels take), depth,
+// node_cap, max_nodes, and the bounds.
+int bnb_preconditions(fclu_ctx *c, const char *name, int cols_limit, const int32_t *g2, const int64_t *ub2, double lo_f, double hi_f, int32_t offset, int32_t min_cols,
+                      int32_t max_cols, int32_t depth, int32_t node_cap, int64_t max_nodes) {
+    return round_preconditions(c, name, g2, lo_f, hi_f, offset, [&]() -> int {
+        if (min_cols < 0 || max_cols < min_cols || max_cols > cols_limit)
+            return fail(c, FCLU_ERR_ARG, "%s: min_cols is %d and max_cols %d, they must be 0 <= min_cols <= max_cols <= %d", name, (int)min_cols, (int)max_cols, cols_limit);
+        if (depth < 0 || depth > kBnbMaxDepth) return fail(c, FCLU_ERR_ARG, "%s: depth is %d, it must lie in [0, %d]", name, (int)depth, kBnbMaxDepth);
+        if (node_cap < 1) return fail(c, FCLU_ERR_ARG, "%s: node_cap is %d, it must be at least 1", name, (int)node_cap);
+        if (max_nodes < 1) return fail(c, FCLU_ERR_ARG, "%s: max_nodes is %lld, it must be at least 1", name, (i64)max_nodes);
+        return FCLU_OK;
+    }, [&]() -> int { return c->rounds.n_prob > 0 && !ub2 ? fail(c, FCLU_ERR_ARG, "%s: ub2 is null", name) : (int)FCLU_OK; });
+}
+
+// Every problem's descriptor (at(p): where the caller keeps it) and the call's candidates: the problems that have a model and are not
+// outside the call's sizes (the caller's predicate), their offsets checked, in ascending (columns, problem).
+template <typename At, typename Outside>
+int select_probs(fclu_ctx *c, At at, Outside outside, std::vector<std::pair<int, int>> &order) {
+    const fclu_rounds &o = c->rounds;
+    for (int p = 0; p < o.n_prob; ++p) {
+        ExactProb &d = at(p);
+        fill_exact_prob(c, p, d);
+        if (o.refused[p] >= 0 || outside(d)) continue;       // no model, or not this call's: its result stays the default
+        if (!exact_prob_in_range(c, p, d)) return fail(c, FCLU_ERR_HIP, "problem %d: the round's offsets are out of range", p);
+        if (o.n_grp == 0) d.row0 = d.row1 = 0;               // (a row has a group: nothing to index without one)
+        order.emplace_back(d.n, p);
+    }
+    std::sort(order.begin(), order.end());
+    return FCLU_OK;
+}
+
+// A call issues max_launches launches at the most (units, budget: the refusal's words for what a launch holds and what to lower), with an
+// event in front of the first and behind each.
+int launches_ready(fclu_ctx *c, const char *name, const char *units, const char *budget, const LaunchPlan &plan, int max_launches) {
+    if (plan.n_launch() > (size_t)max_launches)
+        return fail(c, FCLU_ERR_UNSUPPORTED, "%s: %lld %s need %lld launches, a call issues %d at the most: lower %s", name, plan.total_units, units,
+                    (i64)plan.n_launch(), max_launches, budget);
+    while (c->launch_ev.size() < plan.n_launch() + 1) {
+        hipEvent_t e = nullptr;
+        HIP_TRY(c, hipEventCreate(&e));
+        c->launch_ev.push_back(e);
+    }
+    return FCLU_OK;
+}
+
+static_assert(sizeof(PlanItem) == sizeof(int4), "the kernels read a plan's items as int4");
+
+// What every call uploads: the problems, the taken ones' list, the work items, g2.
+template <typename Prob>
+int upload_plan(fclu_ctx *c, fclu_ctx::RoundCallBufs &D, Buf<Prob> &d_probs, const std::vector<Prob> &probs, const LaunchPlan &plan, const int32_t *g2) {
+    const size_t nP = probs.size(), nL = plan.list.size(), nI = plan.items.size(), nC = (size_t)c->rounds.n_cols;
+    hipStream_t s = c->stream;
+    HIP_TRY(c, d_probs.grow(nP)); HIP_TRY(c, D.list.grow(nL)); HIP_TRY(c, D.items.grow(nI)); HIP_TRY(c, D.g2.grow(nC));
+    if (nP) HIP_TRY(c, hipMemcpyAsync(d_probs.p, probs.data(), d_probs.bytes(nP), hipMemcpyHostToDevice, s));
+    if (nL) HIP_TRY(c, hipMemcpyAsync(D.list.p, plan.list.data(), D.list.bytes(nL), hipMemcpyHostToDevice, s));
+    if (nI) HIP_TRY(c, hipMemcpyAsync(D.items.p, plan.items.data(), D.items.bytes(nI), hipMemcpyHostToDevice, s));
+    if (nC) HIP_TRY(c, hipMemcpyAsync(D.g2.p, g2, D.g2.bytes(nC), hipMemcpyHostToDevice, s));
+    return FCLU_OK;
+}
+
+// What the two searches add: the bounds, per problem its first task and task count, the zeroed per-problem results; and room for the
+// results' pinned side (the mask words are the caller's).
+template <typename Out>
+int upload_search(fclu_ctx *c, fclu_ctx::SearchBufs &D, Buf<Out> &d_out, fclu_ctx::SearchHost<Out> &H, const int64_t *ub2, const LaunchPlan &plan) {
+    const size_t nP = plan.n_units.size();
+    hipStream_t s = c->stream;
+    HIP_TRY(c, D.ub2.grow(nP)); HIP_TRY(c, D.task_off.grow(nP)); HIP_TRY(c, D.n_tasks.grow(nP)); HIP_TRY(c, d_out.grow(nP));
+    HIP_TRY(c, H.out.grow(nP)); HIP_TRY(c, H.cost2.grow(nP)); HIP_TRY(c, H.nodes.grow(nP)); HIP_TRY(c, H.status.grow(nP)); HIP_TRY(c, H.capped.grow(nP));
+    if (nP) {
+        HIP_TRY(c, hipMemcpyAsync(D.ub2.p, ub2, D.ub2.bytes(nP), hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipMemcpyAsync(D.task_off.p, plan.unit_off.data(), D.task_off.bytes(nP), hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipMemcpyAsync(D.n_tasks.p, plan.n_units.data(), D.n_tasks.bytes(nP), hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipMemsetAsync(d_out.p, 0, d_out.bytes(nP), s));
+    }
+    return FCLU_OK;
+}
+
+// A call's kernels on the stream and its times: prep() between ev[0] and ev[1], launch(l) for each of the plan's launches with an event
+// behind it, behind() for what follows the last launch (a reduction and its event, the downloads); then the one wait of the call.
+template <typename Prep, typename Launch, typename Behind>
+int run_round_call(fclu_ctx *c, hipEvent_t *ev, size_t n_launch, float &prep_ms, float &search_ms, float &longest_ms, Prep prep, Launch launch, Behind behind) {
+    hipStream_t s = c->stream;
+    HIP_TRY(c, hipEventRecord(ev[0], s));
+    prep();
+    HIP_TRY(c, hipEventRecord(ev[1], s));
+    HIP_TRY(c, hipEventRecord(c->launch_ev[0], s));
+    for (size_t l = 0; l < n_launch; ++l) {
+        launch(l);
+        HIP_TRY(c, hipEventRecord(c->launch_ev[l + 1], s));
+    }
+    RC_TRY(behind());
+    HIP_TRY(c, hipStreamSynchronize(s));
+    HIP_TRY(c, hipGetLastError());
+    (void)hipEventElapsedTime(&prep_ms, ev[0], ev[1]);
+    if (n_launch) (void)hipEventElapsedTime(&search_ms, c->launch_ev[0], c->launch_ev[n_launch]);
+    for (size_t l = 0; l < n_launch; ++l) {
+        float ms = 0.f;
+        (void)hipEventElapsedTime(&ms, c->launch_ev[l], c->launch_ev[l + 1]);
+        longest_ms = std::max(longest_ms, ms);
+    }
+    return FCLU_OK;
+}
+
+// The two searches' results (fclu_bnb and fclu_bnb_wide have one layout): every problem's default, the taken ones' from what the device
+// left in H.out, and the call's totals.  The mask words are the caller's.
+template <typename Out, typename Result>
+void fold_search(int P, const LaunchPlan &plan, fclu_ctx::SearchHost<Out> &H, const int64_t *ub2, Result &r) {
+    for (int p = 0; p < P; ++p) { H.status.p[p] = FCLU_BNB_NOT_TAKEN; H.cost2.p[p] = -1; H.nodes.p[p] = 0; H.capped.p[p] = 0; }
+    i64 nodes_total = 0;
+    for (const int p : plan.list) {
+        const Out &t = H.out.p[p];
+        const bool found = t.cost2 >= 0;
+        H.cost2.p[p] = found ? t.cost2 : -1; H.nodes.p[p] = t.nodes; H.capped.p[p] = (int32_t)t.capped;
+        H.status.p[p] = t.capped > 0 ? FCLU_BNB_UNPROVEN : found ? FCLU_BNB_OPTIMAL : ub2[p] < 0 ? FCLU_BNB_INFEASIBLE : FCLU_BNB_UNPROVEN;
+        nodes_total += t.nodes;
+    }
+    r.n_prob = P; r.status = H.status.p; r.cost2 = H.cost2.p; r.mask = H.mask.p; r.nodes = H.nodes.p; r.capped = H.capped.p;
+    r.n_taken = (int64_t)plan.list.size(); r.n_launches = (int64_t)plan.n_launch(); r.nodes_total = nodes_total;
+}
+
+// ---- the exact solve of the last round's small problems (fclu_round_exact) ------------------------------------------------------
 int exact_device(fclu_ctx *c, const Knobs &k, const int32_t *g2, double lo_f, double hi_f, int32_t offset, int32_t max_cols, int64_t max_masks) {
     c->have_exact = false;
     c->xprep_ms = c->xsearch_ms = c->xlongest_ms = 0.f;
-    if (!c->have_rounds || !c->round_ready || !c->round_src_ok || !c->have_parts)
-        return fail(c, FCLU_ERR_ARG, "fclu_round_exact: no successful fclu_round_models() stands behind the call (none was made, it failed, or a later "
-                                     "call ended the rounds' source)");
+    RC_TRY(round_preconditions(c, "fclu_round_exact", g2, lo_f, hi_f, offset, [&]() -> int {
+        if (max_cols < 0 || max_cols > kExactMaxCols) return fail(c, FCLU_ERR_ARG, "fclu_round_exact: max_cols is %d, it must lie in [0, %d]", (int)max_cols, kExactMaxCols);
+        if (max_masks < 1) return fail(c, FCLU_ERR_ARG, "fclu_round_exact: max_masks is %lld, it must be at least 1", (i64)max_masks);
+        return FCLU_OK;
+    }, []() -> int { return FCLU_OK; }));
     const fclu_rounds &o = c->rounds;
     const int P = o.n_prob;
     const i64 C = o.n_cols, G = o.n_gap_rows;
-    if (max_cols < 0 || max_cols > kExactMaxCols) return fail(c, FCLU_ERR_ARG, "fclu_round_exact: max_cols is %d, it must lie in [0, %d]", (int)max_cols, kExactMaxCols);
-    if (max_masks < 1) return fail(c, FCLU_ERR_ARG, "fclu_round_exact: max_masks is %lld, it must be at least 1", (i64)max_masks);
-    if (offset < 0 || !(lo_f == lo_f) || !(hi_f == hi_f) || lo_f - lo_f != 0.0 || hi_f - hi_f != 0.0)
-        return fail(c, FCLU_ERR_ARG, "fclu_round_exact: offset is negative or a factor is not finite");
-    if (C > 0 && !g2) return fail(c, FCLU_ERR_ARG, "fclu_round_exact: g2 is null");
-    for (i64 x = 0; x < C; ++x) if (g2[x] < 0) return fail(c, FCLU_ERR_ARG, "fclu_round_exact: g2[%lld] is negative", x);
-    if ((int)c->r_probs.size() != P) return fail(c, FCLU_ERR_ARG, "fclu_round_exact: the round's problems are gone");
     HIP_TRY(c, hipSetDevice(c->device));
     auto &D = c->xd;
     auto &H = c->xh;
@@ -3317,87 +3424,42 @@ int exact_device(fclu_ctx *c, const Knobs &k, const int32_t *g2, double lo_f, do
     // ---- which problems are taken: ascending (R, problem) while the running total of 2^R stays inside the budget
     std::vector<ExactProb> probs((size_t)P);
     std::vector<std::pair<int, int>> order;
-    for (int p = 0; p < P; ++p) {
-        ExactProb &d = probs[(size_t)p];
-        fill_exact_prob(c, p, d);
-        if (o.refused[p] >= 0 || d.n > max_cols) continue;   // no model, or too many columns: cost2 -2
-        if (!exact_prob_in_range(c, p, d)) return fail(c, FCLU_ERR_HIP, "problem %d: the round's offsets are out of range", p);
-        if (o.n_grp == 0) d.row0 = d.row1 = 0;               // (a row has a group: nothing to index without one)
-        order.emplace_back(d.n, p);
-    }
-    std::sort(order.begin(), order.end());
+    RC_TRY(select_probs(c, [&](int p) -> ExactProb & { return probs[(size_t)p]; }, [&](const ExactProb &d) { return d.n > max_cols; }, order));
     const int wg_masks = k.exact_slice ? (int)k.exact_slice : kExactWgMasks;
     const i64 launch_masks = k.exact_slice ? 16 * k.exact_slice : kExactLaunchMasks;
-    std::vector<int> list;
-    std::vector<int4> items;
-    std::vector<size_t> launch_first;                        // a launch's first item; closed by the number of items
-    std::vector<size_t> launch_lds;
-    i64 n_masks = 0, in_launch = 0;
-    for (const auto &rp : order) {
-        const ExactProb &d = probs[(size_t)rp.second];
-        const i64 total = 1ll << d.n;
-        if (n_masks + total > max_masks) break;              // (ascending R: nothing behind it fits either)
-        n_masks += total;
-        list.push_back(rp.second);
-        const size_t lds = (size_t)(32 + 4 * (2 * d.n_inf + 2 * d.n) + 15) & ~(size_t)15;
-        for (i64 lo = 0; lo < total; lo += wg_masks) {
-            const i64 n = std::min<i64>(wg_masks, total - lo);
-            if (launch_first.empty() || in_launch + n > launch_masks) { launch_first.push_back(items.size()); launch_lds.push_back(0); in_launch = 0; }
-            items.push_back(make_int4(rp.second, (int)lo, (int)n, 0));
-            launch_lds.back() = std::max(launch_lds.back(), lds);
-            in_launch += n;
-        }
-    }
-    const size_t nL = list.size(), nI = items.size(), n_launch = launch_first.size(), nP = (size_t)P, nC = (size_t)C;
-    launch_first.push_back(nI);
-    if (n_launch > (size_t)kExactMaxLaunches)
-        return fail(c, FCLU_ERR_UNSUPPORTED, "fclu_round_exact: %lld masks need %lld launches, a call issues %d at the most: lower max_masks", n_masks, (i64)n_launch,
-                    kExactMaxLaunches);
-    while (c->xl_ev.size() < n_launch + 1) {
-        hipEvent_t e = nullptr;
-        HIP_TRY(c, hipEventCreate(&e));
-        c->xl_ev.push_back(e);
-    }
-    HIP_TRY(c, D.probs.grow(nP)); HIP_TRY(c, D.list.grow(nL)); HIP_TRY(c, D.items.grow(nI)); HIP_TRY(c, D.tab.grow(2 * (size_t)o.n_inf));
-    HIP_TRY(c, D.conf.grow(nC)); HIP_TRY(c, D.gsup.grow((size_t)o.n_grp_seg)); HIP_TRY(c, D.g2.grow(nC)); HIP_TRY(c, D.best.grow(nP));
+    const LaunchPlan plan = plan_launches(order, (size_t)P, [&](int p) { return 1ll << probs[(size_t)p].n; }, 1, max_masks, wg_masks, launch_masks, [&](int p) {
+        const ExactProb &d = probs[(size_t)p];
+        return (size_t)(32 + 4 * (2 * d.n_inf + 2 * d.n) + 15) & ~(size_t)15;
+    });
+    RC_TRY(launches_ready(c, "fclu_round_exact", "masks", "max_masks", plan, kExactMaxLaunches));
+    const size_t nL = plan.list.size(), nP = (size_t)P, nC = (size_t)C;
+    RC_TRY(upload_plan(c, D, D.probs, probs, plan, g2));
+    HIP_TRY(c, D.tab.grow(2 * (size_t)o.n_inf)); HIP_TRY(c, D.conf.grow(nC)); HIP_TRY(c, D.gsup.grow((size_t)o.n_grp_seg)); HIP_TRY(c, D.best.grow(nP));
     HIP_TRY(c, H.best.grow(nP)); HIP_TRY(c, H.cost2.grow(nP)); HIP_TRY(c, H.mask.grow(nP));
-    HIP_TRY(c, hipMemcpyAsync(D.probs.p, probs.data(), D.probs.bytes(nP), hipMemcpyHostToDevice, s));
-    if (nL) HIP_TRY(c, hipMemcpyAsync(D.list.p, list.data(), D.list.bytes(nL), hipMemcpyHostToDevice, s));
-    if (nI) HIP_TRY(c, hipMemcpyAsync(D.items.p, items.data(), D.items.bytes(nI), hipMemcpyHostToDevice, s));
-    if (C) HIP_TRY(c, hipMemcpyAsync(D.g2.p, g2, D.g2.bytes(nC), hipMemcpyHostToDevice, s));
     if (o.n_inf) HIP_TRY(c, hipMemsetAsync(D.tab.p, 0, D.tab.bytes(2 * (size_t)o.n_inf), s));
     if (C) HIP_TRY(c, hipMemsetAsync(D.conf.p, 0, D.conf.bytes(nC), s));
     HIP_TRY(c, hipMemsetAsync(D.best.p, 0xff, D.best.bytes(nP), s));            // kExactKeyNone
-    HIP_TRY(c, hipEventRecord(c->xev[0], s));
-    if (nL)
-        hipLaunchKernelGGL(k_exact_prep, dim3((unsigned)nL), dim3(256), 0, s, D.list.p, D.probs.p, RD.inf_seg.p, RD.sup_off.p, (i64)o.n_inf, RD.sup_cols.p, (i64)o.n_sup,
-                           RD.corr_off.p, C, RD.corr_seg.p, (i64)o.n_corr, RD.pairs.p, RD.grp_seg_off.p, RD.grp_seg.p, (i64)o.n_grp_seg, D.tab.p, D.conf.p, D.gsup.p);
-    HIP_TRY(c, hipEventRecord(c->xev[1], s));
-    HIP_TRY(c, hipEventRecord(c->xl_ev[0], s));
-    for (size_t l = 0; l < n_launch; ++l) {
-        hipLaunchKernelGGL(k_exact_search, dim3((unsigned)(launch_first[l + 1] - launch_first[l])), dim3(256), launch_lds[l], s, D.items.p + launch_first[l], D.probs.p,
-                           D.tab.p, D.conf.p, D.g2.p, RD.rows.p, G, RD.grp_seg_off.p, (i64)o.n_grp, (i64)o.n_grp_seg, D.gsup.p, RD.grp_len.p, lo_f, hi_f, (int)offset,
-                           D.best.p);
-        HIP_TRY(c, hipEventRecord(c->xl_ev[l + 1], s));
-    }
-    HIP_TRY(c, hipMemcpyAsync(H.best.p, D.best.p, D.best.bytes(nP), hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
-    HIP_TRY(c, hipGetLastError());
+    RC_TRY(run_round_call(c, c->xev, plan.n_launch(), c->xprep_ms, c->xsearch_ms, c->xlongest_ms, [&] {
+        if (nL)
+            hipLaunchKernelGGL(k_narrow_prep<unsigned>, dim3((unsigned)nL), dim3(256), 0, s, D.list.p, D.probs.p, RD.inf_seg.p, RD.sup_off.p, (i64)o.n_inf, RD.sup_cols.p,
+                               (i64)o.n_sup, RD.corr_off.p, C, RD.corr_seg.p, (i64)o.n_corr, RD.pairs.p, RD.grp_seg_off.p, RD.grp_seg.p, (i64)o.n_grp_seg, D.tab.p, D.conf.p,
+                               D.gsup.p);
+    }, [&](size_t l) {
+        hipLaunchKernelGGL(k_exact_search, dim3((unsigned)(plan.launch_first[l + 1] - plan.launch_first[l])), dim3(256), plan.launch_lds[l], s,
+                           D.items.p + plan.launch_first[l], D.probs.p, D.tab.p, D.conf.p, D.g2.p, RD.rows.p, G, RD.grp_seg_off.p, (i64)o.n_grp, (i64)o.n_grp_seg, D.gsup.p,
+                           RD.grp_len.p, lo_f, hi_f, (int)offset, D.best.p);
+    }, [&]() -> int {
+        HIP_TRY(c, hipMemcpyAsync(H.best.p, D.best.p, D.best.bytes(nP), hipMemcpyDeviceToHost, s));
+        return FCLU_OK;
+    }));
     for (int p = 0; p < P; ++p) { H.cost2.p[p] = -2; H.mask.p[p] = 0u; }
-    for (const int p : list) {
+    for (const int p : plan.list) {
         const u64 key = H.best.p[p];
         H.cost2.p[p] = key == kExactKeyNone ? -1 : ex_key_cost2(key);
         H.mask.p[p] = key == kExactKeyNone ? 0u : ex_key_mask(key);
     }
     fclu_exact &r = c->exact;
-    r.n_prob = P; r.cost2 = H.cost2.p; r.mask = H.mask.p; r.n_taken = (int64_t)nL; r.n_masks = n_masks; r.n_launches = (int64_t)n_launch;
-    (void)hipEventElapsedTime(&c->xprep_ms, c->xev[0], c->xev[1]);
-    if (n_launch) (void)hipEventElapsedTime(&c->xsearch_ms, c->xl_ev[0], c->xl_ev[n_launch]);
-    for (size_t l = 0; l < n_launch; ++l) {
-        float ms = 0.f;
-        (void)hipEventElapsedTime(&ms, c->xl_ev[l], c->xl_ev[l + 1]);
-        c->xlongest_ms = std::max(c->xlongest_ms, ms);
-    }
+    r.n_prob = P; r.cost2 = H.cost2.p; r.mask = H.mask.p; r.n_taken = (int64_t)nL; r.n_masks = plan.total_units; r.n_launches = (int64_t)plan.n_launch();
     c->have_exact = true;
     return FCLU_OK;
 }
@@ -3407,24 +3469,10 @@ int bnb_device(fclu_ctx *c, const Knobs &k, const int32_t *g2, const int64_t *ub
                int32_t depth, int32_t node_cap, int64_t max_nodes) {
     c->have_bnb = false;
     c->bprep_ms = c->bsearch_ms = c->blongest_ms = 0.f;
-    if (!c->have_rounds || !c->round_ready || !c->round_src_ok || !c->have_parts)
-        return fail(c, FCLU_ERR_ARG, "fclu_round_bnb: no successful fclu_round_models() stands behind the call (none was made, it failed, or a later "
-                                     "call ended the rounds' source)");
+    RC_TRY(bnb_preconditions(c, "fclu_round_bnb", kBnbMaxCols, g2, ub2, lo_f, hi_f, offset, min_cols, max_cols, depth, node_cap, max_nodes));
     const fclu_rounds &o = c->rounds;
     const int P = o.n_prob;
     const i64 C = o.n_cols, G = o.n_gap_rows;
-    if (min_cols < 0 || max_cols < min_cols || max_cols > kBnbMaxCols)
-        return fail(c, FCLU_ERR_ARG, "fclu_round_bnb: min_cols is %d and max_cols %d, they must be 0 <= min_cols <= max_cols <= %d", (int)min_cols, (int)max_cols,
-                    kBnbMaxCols);
-    if (depth < 0 || depth > kBnbMaxDepth) return fail(c, FCLU_ERR_ARG, "fclu_round_bnb: depth is %d, it must lie in [0, %d]", (int)depth, kBnbMaxDepth);
-    if (node_cap < 1) return fail(c, FCLU_ERR_ARG, "fclu_round_bnb: node_cap is %d, it must be at least 1", (int)node_cap);
-    if (max_nodes < 1) return fail(c, FCLU_ERR_ARG, "fclu_round_bnb: max_nodes is %lld, it must be at least 1", (i64)max_nodes);
-    if (offset < 0 || !(lo_f == lo_f) || !(hi_f == hi_f) || lo_f - lo_f != 0.0 || hi_f - hi_f != 0.0)
-        return fail(c, FCLU_ERR_ARG, "fclu_round_bnb: offset is negative or a factor is not finite");
-    if (C > 0 && !g2) return fail(c, FCLU_ERR_ARG, "fclu_round_bnb: g2 is null");
-    if (P > 0 && !ub2) return fail(c, FCLU_ERR_ARG, "fclu_round_bnb: ub2 is null");
-    for (i64 x = 0; x < C; ++x) if (g2[x] < 0) return fail(c, FCLU_ERR_ARG, "fclu_round_bnb: g2[%lld] is negative", x);
-    if ((int)c->r_probs.size() != P) return fail(c, FCLU_ERR_ARG, "fclu_round_bnb: the round's problems are gone");
     HIP_TRY(c, hipSetDevice(c->device));
     auto &D = c->bd;
     auto &H = c->bh;
@@ -3433,103 +3481,41 @@ int bnb_device(fclu_ctx *c, const Knobs &k, const int32_t *g2, const int64_t *ub
     // ---- which problems are taken: ascending (R, problem) while the running total of 2^D x node_cap stays inside the budget
     std::vector<ExactProb> probs((size_t)P);
     std::vector<std::pair<int, int>> order;
-    for (int p = 0; p < P; ++p) {
-        ExactProb &d = probs[(size_t)p];
-        fill_exact_prob(c, p, d);
-        if (o.refused[p] >= 0 || d.n < min_cols || d.n > max_cols || d.n_inf > kBnbMaxInf) continue;      // no model, outside the sizes, or tables beyond LDS
-        if (!exact_prob_in_range(c, p, d)) return fail(c, FCLU_ERR_HIP, "problem %d: the round's offsets are out of range", p);
-        if (o.n_grp == 0) d.row0 = d.row1 = 0;               // (a row has a group: nothing to index without one)
-        order.emplace_back(d.n, p);
-    }
-    std::sort(order.begin(), order.end());
+    RC_TRY(select_probs(c, [&](int p) -> ExactProb & { return probs[(size_t)p]; },
+                        [&](const ExactProb &d) { return d.n < min_cols || d.n > max_cols || d.n_inf > kBnbMaxInf; }, order));     // outside the sizes, or tables beyond LDS
     const i64 launch_tasks = k.bnb_slice ? k.bnb_slice : std::max<i64>(kBnbLaunchNodes / node_cap, 1);
     const i64 wg_tasks = std::min<i64>(kBnbWgTasks, launch_tasks);
-    std::vector<int> list;
-    std::vector<int4> items;
-    std::vector<size_t> launch_first;                        // a launch's first item; closed by the number of items
-    std::vector<size_t> launch_lds;
-    std::vector<i64> task_off((size_t)P, 0), n_tasks((size_t)P, 0);
-    i64 budget = 0, total_tasks = 0, in_launch = 0;
-    for (const auto &rp : order) {
-        const ExactProb &d = probs[(size_t)rp.second];
-        const i64 tasks = 1ll << std::min<int>(d.n, depth);
-        if (tasks > (max_nodes - budget) / node_cap) break;  // (ascending R: nothing behind it fits either; no product that could overflow)
-        budget += tasks * node_cap;
-        list.push_back(rp.second);
-        task_off[(size_t)rp.second] = total_tasks; n_tasks[(size_t)rp.second] = tasks;
-        total_tasks += tasks;
-        const size_t lds = (size_t)(16 * d.n_inf + 12 * d.n + 15) & ~(size_t)15;
-        for (i64 lo = 0; lo < tasks; lo += wg_tasks) {
-            const i64 n = std::min<i64>(wg_tasks, tasks - lo);
-            if (launch_first.empty() || in_launch + n > launch_tasks) { launch_first.push_back(items.size()); launch_lds.push_back(0); in_launch = 0; }
-            items.push_back(make_int4(rp.second, (int)lo, (int)n, 0));
-            launch_lds.back() = std::max(launch_lds.back(), lds);
-            in_launch += n;
-        }
-    }
-    const size_t nL = list.size(), nI = items.size(), n_launch = launch_first.size(), nP = (size_t)P, nC = (size_t)C, nT = (size_t)total_tasks;
-    launch_first.push_back(nI);
-    if (n_launch > (size_t)kBnbMaxLaunches)
-        return fail(c, FCLU_ERR_UNSUPPORTED, "fclu_round_bnb: %lld tasks need %lld launches, a call issues %d at the most: lower max_nodes", total_tasks, (i64)n_launch,
-                    kBnbMaxLaunches);
-    while (c->bl_ev.size() < n_launch + 1) {
-        hipEvent_t e = nullptr;
-        HIP_TRY(c, hipEventCreate(&e));
-        c->bl_ev.push_back(e);
-    }
-    HIP_TRY(c, D.probs.grow(nP)); HIP_TRY(c, D.list.grow(nL)); HIP_TRY(c, D.items.grow(nI)); HIP_TRY(c, D.tab.grow(2 * (size_t)o.n_inf));
-    HIP_TRY(c, D.conf.grow(nC)); HIP_TRY(c, D.gsup.grow((size_t)o.n_grp_seg)); HIP_TRY(c, D.g2.grow(nC)); HIP_TRY(c, D.ub2.grow(nP));
-    HIP_TRY(c, D.task_off.grow(nP)); HIP_TRY(c, D.n_tasks.grow(nP)); HIP_TRY(c, D.tasks.grow(nT)); HIP_TRY(c, D.out.grow(nP));
-    HIP_TRY(c, H.out.grow(nP)); HIP_TRY(c, H.cost2.grow(nP)); HIP_TRY(c, H.mask.grow(nP)); HIP_TRY(c, H.nodes.grow(nP)); HIP_TRY(c, H.status.grow(nP));
-    HIP_TRY(c, H.capped.grow(nP));
-    if (nP) {
-        HIP_TRY(c, hipMemcpyAsync(D.probs.p, probs.data(), D.probs.bytes(nP), hipMemcpyHostToDevice, s));
-        HIP_TRY(c, hipMemcpyAsync(D.ub2.p, ub2, D.ub2.bytes(nP), hipMemcpyHostToDevice, s));
-        HIP_TRY(c, hipMemcpyAsync(D.task_off.p, task_off.data(), D.task_off.bytes(nP), hipMemcpyHostToDevice, s));
-        HIP_TRY(c, hipMemcpyAsync(D.n_tasks.p, n_tasks.data(), D.n_tasks.bytes(nP), hipMemcpyHostToDevice, s));
-        HIP_TRY(c, hipMemsetAsync(D.out.p, 0, D.out.bytes(nP), s));
-    }
-    if (nL) HIP_TRY(c, hipMemcpyAsync(D.list.p, list.data(), D.list.bytes(nL), hipMemcpyHostToDevice, s));
-    if (nI) HIP_TRY(c, hipMemcpyAsync(D.items.p, items.data(), D.items.bytes(nI), hipMemcpyHostToDevice, s));
-    if (C) HIP_TRY(c, hipMemcpyAsync(D.g2.p, g2, D.g2.bytes(nC), hipMemcpyHostToDevice, s));
+    const LaunchPlan plan = plan_launches(order, (size_t)P, [&](int p) { return 1ll << std::min<int>(probs[(size_t)p].n, depth); }, node_cap, max_nodes, wg_tasks,
+                                          launch_tasks, [&](int p) {
+        const ExactProb &d = probs[(size_t)p];
+        return (size_t)(16 * d.n_inf + 12 * d.n + 15) & ~(size_t)15;
+    });
+    RC_TRY(launches_ready(c, "fclu_round_bnb", "tasks", "max_nodes", plan, kBnbMaxLaunches));
+    const size_t nL = plan.list.size(), nP = (size_t)P, nC = (size_t)C;
+    RC_TRY(upload_plan(c, D, D.probs, probs, plan, g2));
+    RC_TRY(upload_search(c, D, D.out, H, ub2, plan));
+    HIP_TRY(c, D.tab.grow(2 * (size_t)o.n_inf)); HIP_TRY(c, D.conf.grow(nC)); HIP_TRY(c, D.gsup.grow((size_t)o.n_grp_seg));
+    HIP_TRY(c, D.tasks.grow((size_t)plan.total_units)); HIP_TRY(c, H.mask.grow(nP));
     if (o.n_inf) HIP_TRY(c, hipMemsetAsync(D.tab.p, 0, D.tab.bytes(2 * (size_t)o.n_inf), s));
     if (C) HIP_TRY(c, hipMemsetAsync(D.conf.p, 0, D.conf.bytes(nC), s));
-    HIP_TRY(c, hipEventRecord(c->bev[0], s));
-    if (nL)
-        hipLaunchKernelGGL(k_bnb_prep, dim3((unsigned)nL), dim3(256), 0, s, D.list.p, D.probs.p, RD.inf_seg.p, RD.sup_off.p, (i64)o.n_inf, RD.sup_cols.p, (i64)o.n_sup,
-                           RD.corr_off.p, C, RD.corr_seg.p, (i64)o.n_corr, RD.pairs.p, RD.grp_seg_off.p, RD.grp_seg.p, (i64)o.n_grp_seg, D.tab.p, D.conf.p, D.gsup.p);
-    HIP_TRY(c, hipEventRecord(c->bev[1], s));
-    HIP_TRY(c, hipEventRecord(c->bl_ev[0], s));
-    for (size_t l = 0; l < n_launch; ++l) {
-        hipLaunchKernelGGL(k_bnb_search, dim3((unsigned)(launch_first[l + 1] - launch_first[l])), dim3(256), launch_lds[l], s, D.items.p + launch_first[l], D.probs.p,
-                           D.tab.p, D.conf.p, D.g2.p, D.ub2.p, RD.rows.p, G, RD.grp_seg_off.p, (i64)o.n_grp, (i64)o.n_grp_seg, D.gsup.p, RD.grp_len.p, lo_f, hi_f,
-                           (int)offset, (int)depth, (int)node_cap, D.task_off.p, D.tasks.p);
-        HIP_TRY(c, hipEventRecord(c->bl_ev[l + 1], s));
-    }
-    if (nL) hipLaunchKernelGGL(k_bnb_reduce, dim3((unsigned)nL), dim3(256), 0, s, D.list.p, D.task_off.p, D.n_tasks.p, D.tasks.p, D.out.p);
-    HIP_TRY(c, hipEventRecord(c->bev[2], s));
-    if (nP) HIP_TRY(c, hipMemcpyAsync(H.out.p, D.out.p, D.out.bytes(nP), hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
-    HIP_TRY(c, hipGetLastError());
-    for (int p = 0; p < P; ++p) { H.status.p[p] = FCLU_BNB_NOT_TAKEN; H.cost2.p[p] = -1; H.mask.p[p] = 0ull; H.nodes.p[p] = 0; H.capped.p[p] = 0; }
-    i64 nodes_total = 0;
-    for (const int p : list) {
-        const BnbOut &r = H.out.p[p];
-        const bool found = r.cost2 >= 0;
-        H.cost2.p[p] = found ? r.cost2 : -1; H.mask.p[p] = found ? r.mask : 0ull; H.nodes.p[p] = r.nodes; H.capped.p[p] = (int32_t)r.capped;
-        H.status.p[p] = r.capped > 0 ? FCLU_BNB_UNPROVEN : found ? FCLU_BNB_OPTIMAL : ub2[p] < 0 ? FCLU_BNB_INFEASIBLE : FCLU_BNB_UNPROVEN;
-        nodes_total += r.nodes;
-    }
-    fclu_bnb &r = c->bnb;
-    r.n_prob = P; r.status = H.status.p; r.cost2 = H.cost2.p; r.mask = H.mask.p; r.nodes = H.nodes.p; r.capped = H.capped.p;
-    r.n_taken = (int64_t)nL; r.n_launches = (int64_t)n_launch; r.nodes_total = nodes_total;
-    (void)hipEventElapsedTime(&c->bprep_ms, c->bev[0], c->bev[1]);
-    if (n_launch) (void)hipEventElapsedTime(&c->bsearch_ms, c->bl_ev[0], c->bl_ev[n_launch]);
-    for (size_t l = 0; l < n_launch; ++l) {
-        float ms = 0.f;
-        (void)hipEventElapsedTime(&ms, c->bl_ev[l], c->bl_ev[l + 1]);
-        c->blongest_ms = std::max(c->blongest_ms, ms);
-    }
+    RC_TRY(run_round_call(c, c->bev, plan.n_launch(), c->bprep_ms, c->bsearch_ms, c->blongest_ms, [&] {
+        if (nL)
+            hipLaunchKernelGGL(k_narrow_prep<u64>, dim3((unsigned)nL), dim3(256), 0, s, D.list.p, D.probs.p, RD.inf_seg.p, RD.sup_off.p, (i64)o.n_inf, RD.sup_cols.p,
+                               (i64)o.n_sup, RD.corr_off.p, C, RD.corr_seg.p, (i64)o.n_corr, RD.pairs.p, RD.grp_seg_off.p, RD.grp_seg.p, (i64)o.n_grp_seg, D.tab.p, D.conf.p,
+                               D.gsup.p);
+    }, [&](size_t l) {
+        hipLaunchKernelGGL(k_bnb_search, dim3((unsigned)(plan.launch_first[l + 1] - plan.launch_first[l])), dim3(256), plan.launch_lds[l], s,
+                           D.items.p + plan.launch_first[l], D.probs.p, D.tab.p, D.conf.p, D.g2.p, D.ub2.p, RD.rows.p, G, RD.grp_seg_off.p, (i64)o.n_grp, (i64)o.n_grp_seg,
+                           D.gsup.p, RD.grp_len.p, lo_f, hi_f, (int)offset, (int)depth, (int)node_cap, D.task_off.p, D.tasks.p);
+    }, [&]() -> int {
+        if (nL) hipLaunchKernelGGL(k_bnb_reduce, dim3((unsigned)nL), dim3(256), 0, s, D.list.p, D.task_off.p, D.n_tasks.p, D.tasks.p, D.out.p);
+        HIP_TRY(c, hipEventRecord(c->bev[2], s));
+        if (nP) HIP_TRY(c, hipMemcpyAsync(H.out.p, D.out.p, D.out.bytes(nP), hipMemcpyDeviceToHost, s));
+        return FCLU_OK;
+    }));
+    fold_search(P, plan, H, ub2, c->bnb);
+    for (int p = 0; p < P; ++p) H.mask.p[p] = 0ull;
+    for (const int p : plan.list) if (H.out.p[p].cost2 >= 0) H.mask.p[p] = H.out.p[p].mask;
     c->have_bnb = true;
     return FCLU_OK;
 }
@@ -3539,139 +3525,59 @@ int bnb_wide_device(fclu_ctx *c, const Knobs &k, const int32_t *g2, const int64_
                     int32_t max_cols, int32_t depth, int32_t node_cap, int64_t max_nodes) {
     c->have_wide = false;
     c->wprep_ms = c->wsearch_ms = c->wlongest_ms = 0.f;
-    if (!c->have_rounds || !c->round_ready || !c->round_src_ok || !c->have_parts)
-        return fail(c, FCLU_ERR_ARG, "fclu_round_bnb_wide: no successful fclu_round_models() stands behind the call (none was made, it failed, or a later "
-                                     "call ended the rounds' source)");
+    RC_TRY(bnb_preconditions(c, "fclu_round_bnb_wide", kBwMaxCols, g2, ub2, lo_f, hi_f, offset, min_cols, max_cols, depth, node_cap, max_nodes));
     const fclu_rounds &o = c->rounds;
     const int P = o.n_prob;
     const i64 C = o.n_cols, G = o.n_gap_rows;
-    if (min_cols < 0 || max_cols < min_cols || max_cols > kBwMaxCols)
-        return fail(c, FCLU_ERR_ARG, "fclu_round_bnb_wide: min_cols is %d and max_cols %d, they must be 0 <= min_cols <= max_cols <= %d", (int)min_cols,
-                    (int)max_cols, kBwMaxCols);
-    if (depth < 0 || depth > kBnbMaxDepth) return fail(c, FCLU_ERR_ARG, "fclu_round_bnb_wide: depth is %d, it must lie in [0, %d]", (int)depth, kBnbMaxDepth);
-    if (node_cap < 1) return fail(c, FCLU_ERR_ARG, "fclu_round_bnb_wide: node_cap is %d, it must be at least 1", (int)node_cap);
-    if (max_nodes < 1) return fail(c, FCLU_ERR_ARG, "fclu_round_bnb_wide: max_nodes is %lld, it must be at least 1", (i64)max_nodes);
-    if (offset < 0 || !(lo_f == lo_f) || !(hi_f == hi_f) || lo_f - lo_f != 0.0 || hi_f - hi_f != 0.0)
-        return fail(c, FCLU_ERR_ARG, "fclu_round_bnb_wide: offset is negative or a factor is not finite");
-    if (C > 0 && !g2) return fail(c, FCLU_ERR_ARG, "fclu_round_bnb_wide: g2 is null");
-    if (P > 0 && !ub2) return fail(c, FCLU_ERR_ARG, "fclu_round_bnb_wide: ub2 is null");
-    for (i64 x = 0; x < C; ++x) if (g2[x] < 0) return fail(c, FCLU_ERR_ARG, "fclu_round_bnb_wide: g2[%lld] is negative", x);
-    if ((int)c->r_probs.size() != P) return fail(c, FCLU_ERR_ARG, "fclu_round_bnb_wide: the round's problems are gone");
     HIP_TRY(c, hipSetDevice(c->device));
     auto &D = c->wd;
     auto &H = c->wh;
     auto &RD = c->rd;
     hipStream_t s = c->stream;
     // ---- which problems are taken: ascending (R, problem) while the running total of 2^D x node_cap stays inside the budget
-    std::vector<BwProb> probs((size_t)P);
+    std::vector<BwProb> probs((size_t)P);                    // (tab0 = conf0 = 0 until a problem is taken)
     std::vector<std::pair<int, int>> order;
-    for (int p = 0; p < P; ++p) {
-        BwProb &q = probs[(size_t)p];
-        ExactProb &d = q.b;
-        fill_exact_prob(c, p, d);
-        q.tab0 = q.conf0 = 0; q.W = bw_words(d.n); q.EW = bw_ewords(d.n_inf);
-        if (o.refused[p] >= 0 || d.n < min_cols || d.n > max_cols || d.n_inf < 0 || bw_lds_bytes(d.n, d.n_inf) > kBwLdsBytes) continue;   // no model, outside the sizes, or tables beyond LDS
-        if (!exact_prob_in_range(c, p, d)) return fail(c, FCLU_ERR_HIP, "problem %d: the round's offsets are out of range", p);
-        if (o.n_grp == 0) d.row0 = d.row1 = 0;               // (a row has a group: nothing to index without one)
-        order.emplace_back(d.n, p);
-    }
-    std::sort(order.begin(), order.end());
+    RC_TRY(select_probs(c, [&](int p) -> ExactProb & { return probs[(size_t)p].b; }, [&](const ExactProb &d) {
+        return d.n < min_cols || d.n > max_cols || d.n_inf < 0 || bw_lds_bytes(d.n, d.n_inf) > kBwLdsBytes;                         // outside the sizes, or tables beyond LDS
+    }, order));
+    for (BwProb &q : probs) { q.W = bw_words(q.b.n); q.EW = bw_ewords(q.b.n_inf); }
     const i64 launch_tasks = k.bnb_wide_slice ? k.bnb_wide_slice : std::max<i64>(kBwLaunchNodes / node_cap, 1);
     const i64 wg_tasks = std::min<i64>(kBwWaves, launch_tasks);
-    std::vector<int> list;
-    std::vector<int4> items;
-    std::vector<size_t> launch_first;                        // a launch's first item; closed by the number of items
-    std::vector<size_t> launch_lds;
-    std::vector<i64> task_off((size_t)P, 0), n_tasks((size_t)P, 0);
-    i64 budget = 0, total_tasks = 0, in_launch = 0, n_tab = 0, n_conf = 0;
-    for (const auto &rp : order) {
-        BwProb &q = probs[(size_t)rp.second];
-        const ExactProb &d = q.b;
-        const i64 tasks = 1ll << std::min<int>(d.n, depth);
-        if (tasks > (max_nodes - budget) / node_cap) break;  // (ascending R: nothing behind it fits either; no product that could overflow)
-        budget += tasks * node_cap;
-        list.push_back(rp.second);
-        task_off[(size_t)rp.second] = total_tasks; n_tasks[(size_t)rp.second] = tasks;
-        total_tasks += tasks;
+    const LaunchPlan plan = plan_launches(order, (size_t)P, [&](int p) { return 1ll << std::min<int>(probs[(size_t)p].b.n, depth); }, node_cap, max_nodes, wg_tasks,
+                                          launch_tasks, [&](int p) { return (size_t)bw_lds_bytes(probs[(size_t)p].b.n, probs[(size_t)p].b.n_inf); });
+    i64 n_tab = 0, n_conf = 0;
+    for (const int p : plan.list) {                          // the taken problems' tables and conflict rows, end to end
+        BwProb &q = probs[(size_t)p];
         q.tab0 = n_tab; q.conf0 = n_conf;
-        n_tab += bw_table_words(d.n, d.n_inf); n_conf += (i64)d.n * q.W;
-        const size_t lds = (size_t)bw_lds_bytes(d.n, d.n_inf);
-        for (i64 lo = 0; lo < tasks; lo += wg_tasks) {
-            const i64 n = std::min<i64>(wg_tasks, tasks - lo);
-            if (launch_first.empty() || in_launch + n > launch_tasks) { launch_first.push_back(items.size()); launch_lds.push_back(0); in_launch = 0; }
-            items.push_back(make_int4(rp.second, (int)lo, (int)n, 0));
-            launch_lds.back() = std::max(launch_lds.back(), lds);
-            in_launch += n;
-        }
+        n_tab += bw_table_words(q.b.n, q.b.n_inf); n_conf += (i64)q.b.n * q.W;
     }
-    const size_t nL = list.size(), nI = items.size(), n_launch = launch_first.size(), nP = (size_t)P, nC = (size_t)C, nT = (size_t)total_tasks;
-    launch_first.push_back(nI);
-    if (n_launch > (size_t)kBwMaxLaunches)
-        return fail(c, FCLU_ERR_UNSUPPORTED, "fclu_round_bnb_wide: %lld tasks need %lld launches, a call issues %d at the most: lower max_nodes", total_tasks,
-                    (i64)n_launch, kBwMaxLaunches);
-    while (c->wl_ev.size() < n_launch + 1) {
-        hipEvent_t e = nullptr;
-        HIP_TRY(c, hipEventCreate(&e));
-        c->wl_ev.push_back(e);
-    }
-    HIP_TRY(c, D.probs.grow(nP)); HIP_TRY(c, D.list.grow(nL)); HIP_TRY(c, D.items.grow(nI)); HIP_TRY(c, D.tab.grow((size_t)n_tab));
-    HIP_TRY(c, D.conf.grow((size_t)n_conf)); HIP_TRY(c, D.gk.grow((size_t)o.n_grp_seg)); HIP_TRY(c, D.g2.grow(nC)); HIP_TRY(c, D.ub2.grow(nP));
-    HIP_TRY(c, D.task_off.grow(nP)); HIP_TRY(c, D.n_tasks.grow(nP)); HIP_TRY(c, D.tasks.grow(nT)); HIP_TRY(c, D.out.grow(nP));
-    HIP_TRY(c, D.out_mask.grow(nP * kBwMaxWords));
-    HIP_TRY(c, H.out.grow(nP)); HIP_TRY(c, H.cost2.grow(nP)); HIP_TRY(c, H.mask.grow(nP * kBwMaxWords)); HIP_TRY(c, H.nodes.grow(nP)); HIP_TRY(c, H.status.grow(nP));
-    HIP_TRY(c, H.capped.grow(nP));
-    if (nP) {
-        HIP_TRY(c, hipMemcpyAsync(D.probs.p, probs.data(), D.probs.bytes(nP), hipMemcpyHostToDevice, s));
-        HIP_TRY(c, hipMemcpyAsync(D.ub2.p, ub2, D.ub2.bytes(nP), hipMemcpyHostToDevice, s));
-        HIP_TRY(c, hipMemcpyAsync(D.task_off.p, task_off.data(), D.task_off.bytes(nP), hipMemcpyHostToDevice, s));
-        HIP_TRY(c, hipMemcpyAsync(D.n_tasks.p, n_tasks.data(), D.n_tasks.bytes(nP), hipMemcpyHostToDevice, s));
-        HIP_TRY(c, hipMemsetAsync(D.out.p, 0, D.out.bytes(nP), s));
-        HIP_TRY(c, hipMemsetAsync(D.out_mask.p, 0, D.out_mask.bytes(nP * kBwMaxWords), s));
-    }
-    if (nL) HIP_TRY(c, hipMemcpyAsync(D.list.p, list.data(), D.list.bytes(nL), hipMemcpyHostToDevice, s));
-    if (nI) HIP_TRY(c, hipMemcpyAsync(D.items.p, items.data(), D.items.bytes(nI), hipMemcpyHostToDevice, s));
-    if (C) HIP_TRY(c, hipMemcpyAsync(D.g2.p, g2, D.g2.bytes(nC), hipMemcpyHostToDevice, s));
+    RC_TRY(launches_ready(c, "fclu_round_bnb_wide", "tasks", "max_nodes", plan, kBwMaxLaunches));
+    const size_t nL = plan.list.size(), nP = (size_t)P;
+    RC_TRY(upload_plan(c, D, D.probs, probs, plan, g2));
+    RC_TRY(upload_search(c, D, D.out, H, ub2, plan));
+    HIP_TRY(c, D.tab.grow((size_t)n_tab)); HIP_TRY(c, D.conf.grow((size_t)n_conf)); HIP_TRY(c, D.gk.grow((size_t)o.n_grp_seg));
+    HIP_TRY(c, D.tasks.grow((size_t)plan.total_units)); HIP_TRY(c, D.out_mask.grow(nP * kBwMaxWords)); HIP_TRY(c, H.mask.grow(nP * kBwMaxWords));
+    if (nP) HIP_TRY(c, hipMemsetAsync(D.out_mask.p, 0, D.out_mask.bytes(nP * kBwMaxWords), s));
     if (n_tab) HIP_TRY(c, hipMemsetAsync(D.tab.p, 0, D.tab.bytes((size_t)n_tab), s));
     if (n_conf) HIP_TRY(c, hipMemsetAsync(D.conf.p, 0, D.conf.bytes((size_t)n_conf), s));
-    HIP_TRY(c, hipEventRecord(c->wev[0], s));
-    if (nL)
-        hipLaunchKernelGGL(k_bw_prep, dim3((unsigned)nL), dim3(256), 0, s, D.list.p, D.probs.p, RD.inf_seg.p, RD.sup_off.p, (i64)o.n_inf, RD.sup_cols.p, (i64)o.n_sup,
-                           RD.corr_off.p, C, RD.corr_seg.p, (i64)o.n_corr, RD.pairs.p, RD.grp_seg_off.p, RD.grp_seg.p, (i64)o.n_grp_seg, D.tab.p, D.conf.p, D.gk.p);
-    HIP_TRY(c, hipEventRecord(c->wev[1], s));
-    HIP_TRY(c, hipEventRecord(c->wl_ev[0], s));
-    for (size_t l = 0; l < n_launch; ++l) {
-        hipLaunchKernelGGL(k_bw_search, dim3((unsigned)(launch_first[l + 1] - launch_first[l])), dim3(kBwThreads), launch_lds[l], s, D.items.p + launch_first[l],
-                           D.probs.p, D.tab.p, D.conf.p, D.g2.p, D.ub2.p, RD.rows.p, G, RD.grp_seg_off.p, (i64)o.n_grp, (i64)o.n_grp_seg, D.gk.p, RD.grp_len.p, lo_f,
-                           hi_f, (int)offset, (int)depth, (int)node_cap, D.task_off.p, D.tasks.p);
-        HIP_TRY(c, hipEventRecord(c->wl_ev[l + 1], s));
-    }
-    if (nL) hipLaunchKernelGGL(k_bw_reduce, dim3((unsigned)nL), dim3(256), 0, s, D.list.p, D.probs.p, D.task_off.p, D.n_tasks.p, D.tasks.p, D.out.p, D.out_mask.p);
-    HIP_TRY(c, hipEventRecord(c->wev[2], s));
-    if (nP) {
-        HIP_TRY(c, hipMemcpyAsync(H.out.p, D.out.p, D.out.bytes(nP), hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipMemcpyAsync(H.mask.p, D.out_mask.p, D.out_mask.bytes(nP * kBwMaxWords), hipMemcpyDeviceToHost, s));
-    }
-    HIP_TRY(c, hipStreamSynchronize(s));
-    HIP_TRY(c, hipGetLastError());
-    for (int p = 0; p < P; ++p) { H.status.p[p] = FCLU_BNB_NOT_TAKEN; H.cost2.p[p] = -1; H.nodes.p[p] = 0; H.capped.p[p] = 0; }
-    i64 nodes_total = 0;
-    for (const int p : list) {
-        const BwOut &r = H.out.p[p];
-        const bool found = r.cost2 >= 0;
-        H.cost2.p[p] = found ? r.cost2 : -1; H.nodes.p[p] = r.nodes; H.capped.p[p] = (int32_t)r.capped;
-        H.status.p[p] = r.capped > 0 ? FCLU_BNB_UNPROVEN : found ? FCLU_BNB_OPTIMAL : ub2[p] < 0 ? FCLU_BNB_INFEASIBLE : FCLU_BNB_UNPROVEN;
-        nodes_total += r.nodes;
-    }
-    fclu_bnb_wide &r = c->wide;
-    r.n_prob = P; r.status = H.status.p; r.cost2 = H.cost2.p; r.mask = H.mask.p; r.nodes = H.nodes.p; r.capped = H.capped.p;
-    r.n_taken = (int64_t)nL; r.n_launches = (int64_t)n_launch; r.nodes_total = nodes_total;
-    (void)hipEventElapsedTime(&c->wprep_ms, c->wev[0], c->wev[1]);
-    if (n_launch) (void)hipEventElapsedTime(&c->wsearch_ms, c->wl_ev[0], c->wl_ev[n_launch]);
-    for (size_t l = 0; l < n_launch; ++l) {
-        float ms = 0.f;
-        (void)hipEventElapsedTime(&ms, c->wl_ev[l], c->wl_ev[l + 1]);
-        c->wlongest_ms = std::max(c->wlongest_ms, ms);
-    }
+    RC_TRY(run_round_call(c, c->wev, plan.n_launch(), c->wprep_ms, c->wsearch_ms, c->wlongest_ms, [&] {
+        if (nL)
+            hipLaunchKernelGGL(k_bw_prep, dim3((unsigned)nL), dim3(256), 0, s, D.list.p, D.probs.p, RD.inf_seg.p, RD.sup_off.p, (i64)o.n_inf, RD.sup_cols.p, (i64)o.n_sup,
+                               RD.corr_off.p, C, RD.corr_seg.p, (i64)o.n_corr, RD.pairs.p, RD.grp_seg_off.p, RD.grp_seg.p, (i64)o.n_grp_seg, D.tab.p, D.conf.p, D.gk.p);
+    }, [&](size_t l) {
+        hipLaunchKernelGGL(k_bw_search, dim3((unsigned)(plan.launch_first[l + 1] - plan.launch_first[l])), dim3(kBwThreads), plan.launch_lds[l], s,
+                           D.items.p + plan.launch_first[l], D.probs.p, D.tab.p, D.conf.p, D.g2.p, D.ub2.p, RD.rows.p, G, RD.grp_seg_off.p, (i64)o.n_grp, (i64)o.n_grp_seg,
+                           D.gk.p, RD.grp_len.p, lo_f, hi_f, (int)offset, (int)depth, (int)node_cap, D.task_off.p, D.tasks.p);
+    }, [&]() -> int {
+        if (nL) hipLaunchKernelGGL(k_bw_reduce, dim3((unsigned)nL), dim3(256), 0, s, D.list.p, D.probs.p, D.task_off.p, D.n_tasks.p, D.tasks.p, D.out.p, D.out_mask.p);
+        HIP_TRY(c, hipEventRecord(c->wev[2], s));
+        if (nP) {
+            HIP_TRY(c, hipMemcpyAsync(H.out.p, D.out.p, D.out.bytes(nP), hipMemcpyDeviceToHost, s));
+            HIP_TRY(c, hipMemcpyAsync(H.mask.p, D.out_mask.p, D.out_mask.bytes(nP * kBwMaxWords), hipMemcpyDeviceToHost, s));
+        }
+        return FCLU_OK;
+    }));
+    fold_search(P, plan, H, ub2, c->wide);
     c->have_wide = true;
     return FCLU_OK;
 }
@@ -3986,9 +3892,7 @@ int fclu_round_results(fclu_ctx *c, fclu_rounds *out) {
 }
 
 int fclu_round_timing(fclu_ctx *c, float *count_ms, float *gaps_ms, float *fill_ms) {
-    if (!c) return FCLU_ERR_ARG;
-    if (fill_ms) *fill_ms = c->rfill_ms;
-    return two_times(count_ms, c->rcount_ms, gaps_ms, c->rgaps_ms);
+    return c ? three_times(count_ms, c->rcount_ms, gaps_ms, c->rgaps_ms, fill_ms, c->rfill_ms) : FCLU_ERR_ARG;
 }
 
 int fclu_round_incumbents(fclu_ctx *c, const int32_t *g2, double lo_f, double hi_f, int32_t offset, int32_t max_seeds) {
@@ -4004,27 +3908,17 @@ int fclu_round_incumbent_results(fclu_ctx *c, fclu_incumbents *out) {
 }
 
 int fclu_round_incumbent_timing(fclu_ctx *c, float *conflict_ms, float *starts_ms, float *pick_ms) {
-    if (!c) return FCLU_ERR_ARG;
-    if (pick_ms) *pick_ms = c->ipick_ms;
-    return two_times(conflict_ms, c->iconf_ms, starts_ms, c->istart_ms);
+    return c ? three_times(conflict_ms, c->iconf_ms, starts_ms, c->istart_ms, pick_ms, c->ipick_ms) : FCLU_ERR_ARG;
 }
 
 int fclu_round_exact(fclu_ctx *c, const int32_t *g2, double lo_f, double hi_f, int32_t offset, int32_t max_cols, int64_t max_masks) {
     return c ? exact_device(c, read_knobs(), g2, lo_f, hi_f, offset, max_cols, max_masks) : FCLU_ERR_ARG;
 }
 
-int fclu_round_exact_results(fclu_ctx *c, fclu_exact *out) {
-    if (!c || !out) return FCLU_ERR_ARG;
-    if (!c->have_exact || !c->have_rounds)
-        return fail(c, FCLU_ERR_ARG, "fclu_round_exact_results: no result (the last fclu_round_exact call failed, none was made, or a later call ended it)");
-    *out = c->exact;
-    return FCLU_OK;
-}
+int fclu_round_exact_results(fclu_ctx *c, fclu_exact *out) { return c && out ? round_call_results(c, c->have_exact, c->exact, out, "fclu_round_exact") : FCLU_ERR_ARG; }
 
 int fclu_round_exact_timing(fclu_ctx *c, float *prep_ms, float *search_ms, float *longest_launch_ms) {
-    if (!c) return FCLU_ERR_ARG;
-    if (longest_launch_ms) *longest_launch_ms = c->xlongest_ms;
-    return two_times(prep_ms, c->xprep_ms, search_ms, c->xsearch_ms);
+    return c ? three_times(prep_ms, c->xprep_ms, search_ms, c->xsearch_ms, longest_launch_ms, c->xlongest_ms) : FCLU_ERR_ARG;
 }
 
 int fclu_round_bnb(fclu_ctx *c, const int32_t *g2, const int64_t *ub2, double lo_f, double hi_f, int32_t offset, int32_t min_cols, int32_t max_cols,
@@ -4032,18 +3926,10 @@ int fclu_round_bnb(fclu_ctx *c, const int32_t *g2, const int64_t *ub2, double lo
     return c ? bnb_device(c, read_knobs(), g2, ub2, lo_f, hi_f, offset, min_cols, max_cols, depth, node_cap, max_nodes) : FCLU_ERR_ARG;
 }
 
-int fclu_round_bnb_results(fclu_ctx *c, fclu_bnb *out) {
-    if (!c || !out) return FCLU_ERR_ARG;
-    if (!c->have_bnb || !c->have_rounds)
-        return fail(c, FCLU_ERR_ARG, "fclu_round_bnb_results: no result (the last fclu_round_bnb call failed, none was made, or a later call ended it)");
-    *out = c->bnb;
-    return FCLU_OK;
-}
+int fclu_round_bnb_results(fclu_ctx *c, fclu_bnb *out) { return c && out ? round_call_results(c, c->have_bnb, c->bnb, out, "fclu_round_bnb") : FCLU_ERR_ARG; }
 
 int fclu_round_bnb_timing(fclu_ctx *c, float *prep_ms, float *search_ms, float *longest_launch_ms) {
-    if (!c) return FCLU_ERR_ARG;
-    if (longest_launch_ms) *longest_launch_ms = c->blongest_ms;
-    return two_times(prep_ms, c->bprep_ms, search_ms, c->bsearch_ms);
+    return c ? three_times(prep_ms, c->bprep_ms, search_ms, c->bsearch_ms, longest_launch_ms, c->blongest_ms) : FCLU_ERR_ARG;
 }
 
 int fclu_round_bnb_wide(fclu_ctx *c, const int32_t *g2, const int64_t *ub2, double lo_f, double hi_f, int32_t offset, int32_t min_cols, int32_t max_cols,
@@ -4051,18 +3937,10 @@ int fclu_round_bnb_wide(fclu_ctx *c, const int32_t *g2, const int64_t *ub2, doub
     return c ? bnb_wide_device(c, read_knobs(), g2, ub2, lo_f, hi_f, offset, min_cols, max_cols, depth, node_cap, max_nodes) : FCLU_ERR_ARG;
 }
 
-int fclu_round_bnb_wide_results(fclu_ctx *c, fclu_bnb_wide *out) {
-    if (!c || !out) return FCLU_ERR_ARG;
-    if (!c->have_wide || !c->have_rounds)
-        return fail(c, FCLU_ERR_ARG, "fclu_round_bnb_wide_results: no result (the last fclu_round_bnb_wide call failed, none was made, or a later call ended it)");
-    *out = c->wide;
-    return FCLU_OK;
-}
+int fclu_round_bnb_wide_results(fclu_ctx *c, fclu_bnb_wide *out) { return c && out ? round_call_results(c, c->have_wide, c->wide, out, "fclu_round_bnb_wide") : FCLU_ERR_ARG; }
 
 int fclu_round_bnb_wide_timing(fclu_ctx *c, float *prep_ms, float *search_ms, float *longest_launch_ms) {
-    if (!c) return FCLU_ERR_ARG;
-    if (longest_launch_ms) *longest_launch_ms = c->wlongest_ms;
-    return two_times(prep_ms, c->wprep_ms, search_ms, c->wsearch_ms);
+    return c ? three_times(prep_ms, c->wprep_ms, search_ms, c->wsearch_ms, longest_launch_ms, c->wlongest_ms) : FCLU_ERR_ARG;
 }
 
 int fclu_round_readout(fclu_ctx *c, const int64_t *sel_off, const int32_t *sel) { return c ? readout_device(c, sel_off, sel) : FCLU_ERR_ARG; }

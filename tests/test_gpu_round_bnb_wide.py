@@ -3,7 +3,7 @@
 nodes_total.  The single-word sizes on the grid (where the mirror is also the 64-column definition); families of 63 .. 129 columns and the
 two-optima tie in one call; a conflict pair, a gap row and a gap group beyond column 63; segment counts at the word and lane boundaries
 of the segment side; random problems of more than 64 columns, proven and capped; 1024 columns; node caps, one task a launch, the node
-budget, tables that do not fit, two rounds, a resident round, what stays valid behind the call, the refusals, the loop with device_rounds
+budget, tables that do not fit, two rounds, a resident round, what stays valid behind the call, a call's times, the refusals, the loop with device_rounds
 on a partition of more than 64 reps and the loop on files.
 
 A tint's first and last segment are always informative, so a staged problem has at least one informative segment: the count 0 is run by
@@ -337,6 +337,42 @@ def test_two_rounds_a_resident_round_and_what_stays_valid(ctx, boundary):
                 assert (int(got["status"][p]), int(got["cost2"][p]), int(got["mask"][p][0]), int(got["nodes"][p])) == (
                     int(bnb["status"][p]), int(bnb["cost2"][p]), int(bnb["mask"][p]), int(bnb["nodes"][p]))
         compare(ctx, tints, part0, problems, resident=True, depth=3)
+
+
+def test_a_calls_times_are_its_own(ctx, boundary, monkeypatch):
+    """The three searches one after another on one context, calls of many launches between calls of one: every call's times are finite
+    and not negative, stay what they were behind the later calls, and where a call had one launch its longest launch is its whole search
+    -- the elapsed time between the same two events, so equal to the bit."""
+    tints = [flips_tint(0, 12, 44)] + boundary[1:4]
+    part0 = stage(ctx, tints)
+    problems = whole(tints)
+    ctx.round_models([part0[t] + q for t, q, _ in problems], [rem for _, _, rem in problems])
+    garbage = garbage_of(tints, problems, SETTINGS)
+    ub2 = ctx.round_incumbents(garbage, SETTINGS["epsilon"], SETTINGS["offset"])["cost2"]
+    args = (SETTINGS["epsilon"], SETTINGS["offset"])
+
+    def sound(got, times):
+        assert all(np.isfinite(v) and v >= 0 for v in times.values()), times
+        if got["n_launches"] == 1:
+            assert times["longest_launch_ms"] == times["search_ms"], times
+        return times
+
+    monkeypatch.setenv("FCLU_EXACT_SLICE", "64")
+    exact = ctx.round_exact(garbage, *args, 12, 1 << 40)
+    t_exact = sound(exact, ctx.round_exact_timing())
+    assert exact["n_launches"] > 1
+    bnb = ctx.round_bnb(garbage, ub2, *args, 1, 64, BIG, 3, 4096)
+    t_bnb = sound(bnb, ctx.round_bnb_timing())
+    assert bnb["n_launches"] == 1 and bnb["n_taken"] >= 1
+    monkeypatch.setenv("FCLU_BNB_WIDE_SLICE", "1")
+    wide = ctx.round_bnb_wide(garbage, ub2, *args, 1, 1024, BIG, 3, 4096)
+    t_wide = sound(wide, ctx.round_bnb_wide_timing())
+    assert wide["n_launches"] > exact["n_launches"]
+    assert ctx.round_exact_timing() == t_exact and ctx.round_bnb_timing() == t_bnb
+    again = ctx.round_bnb(garbage, ub2, *args, 1, 64, BIG, 3, 4096)
+    t_again = sound(again, ctx.round_bnb_timing())
+    assert again["n_launches"] == 1
+    assert ctx.round_exact_timing() == t_exact and ctx.round_bnb_wide_timing() == t_wide and ctx.round_bnb_timing() == t_again
 
 
 def test_refusals(ctx):
