@@ -40,12 +40,14 @@ BNB_NODES = 1 << 30       # the default node budget of a round's branch and boun
                           # (profiles/cluster_bnb.txt)
 
 
+WIDE_MAX_PASSES = 16      # passes of a round's wide branch and bound at the most (cluster_prep.BNB_WIDE_MAX_PASSES, the library's limit)
 WIDE_NODES = 1 << 30      # the default node budget of a round's wide branch and bound: the sum of tasks x node cap over the problems it takes
                           # (profiles/cluster_bnb_wide.txt)
 
 
 def ilp_settings(recycle_model="constant", epsilon=0.2, offset=20, timeout=1, max_rounds=30, min_isoform_size=3, max_ilp=1000, incumbent="off",
-                 exact_cols=0, exact_masks=EXACT_MASKS, bnb_cols=0, bnb_nodes=BNB_NODES, device_rounds=False, wide_cols=0, wide_nodes=WIDE_NODES):
+                 exact_cols=0, exact_masks=EXACT_MASKS, bnb_cols=0, bnb_nodes=BNB_NODES, device_rounds=False, wide_cols=0, wide_nodes=WIDE_NODES,
+                 wide_passes=1):
     """incumbent: "off"; "cutoff": every round's greedy incumbents (Context.round_incumbents, one device call a round) bound the solves'
     objective; "fallback": and stand in for a solve that ends without a proven optimum (status INCUMBENT).
     exact_cols: 0, or the largest number of columns (<= 24) of a problem the GPU solves exactly by enumeration (Context.round_exact, one
@@ -57,12 +59,14 @@ def ilp_settings(recycle_model="constant", epsilon=0.2, offset=20, timeout=1, ma
     it needs exact_cols, bnb_cols or wide_cols, the calls that answer problems.
     wide_cols: 0, or the largest number of columns (<= 1024) of a problem the GPU searches by the branch and bound on sets of several words
     (Context.round_bnb_wide: the problems of max(exact_cols, bnb_cols) + 1 .. wide_cols columns whose tables fit); wide_nodes: that call's
-    budget, as bnb_nodes."""
+    budget, as bnb_nodes, a pass; wide_passes: 1 .. 16, the passes of that call (cluster_solve.exact_bnb_wide(passes=...)): beyond the
+    first, the open subtrees of the tasks that stopped at the node cap are searched as tasks of their own.  1: the single search."""
     if device_rounds and not (exact_cols > 0 or bnb_cols > 0 or wide_cols > 0):
         raise ValueError("device_rounds needs exact_cols, bnb_cols or wide_cols: without them no problem is answered on the device")
     return dict(recycle_model=recycle_model, K=2, epsilon=epsilon, offset=offset, timeout=timeout, max_rounds=max_rounds, threads=1,
                 min_isoform_size=min_isoform_size, max_ilp=max_ilp, incumbent=incumbent, exact_cols=exact_cols, exact_masks=exact_masks,
-                bnb_cols=bnb_cols, bnb_nodes=bnb_nodes, device_rounds=bool(device_rounds), wide_cols=wide_cols, wide_nodes=wide_nodes)
+                bnb_cols=bnb_cols, bnb_nodes=bnb_nodes, device_rounds=bool(device_rounds), wide_cols=wide_cols, wide_nodes=wide_nodes,
+                wide_passes=wide_passes)
 
 
 def check_exact(settings):
@@ -87,6 +91,9 @@ def check_wide(settings):
         raise ValueError("wide_cols is %r: 0 .. %d" % (cols, cluster_solve.BNB_WIDE_MAX_COLS))
     if cols and nodes < 1:
         raise ValueError("wide_nodes is %r: at least 1" % (nodes,))
+    passes = settings.get("wide_passes", 1)
+    if not (isinstance(passes, int) and 1 <= passes <= WIDE_MAX_PASSES):
+        raise ValueError("wide_passes is %r: 1 .. %d" % (passes, WIDE_MAX_PASSES))
 
 
 def check_device_rounds(settings):
@@ -274,8 +281,9 @@ def cluster_tints(tints, part0, ctx, settings, solve=cluster_solve.solve_round, 
             garbage = [g for s in todo for g in (tints[s["t"]]["garbage_cost"][i] for i in s["remaining"])]
             if greedy is None:
                 greedy = inc if inc is not None else ctx.round_incumbents(garbage, settings["epsilon"], settings["offset"])
-            wide = ctx.round_bnb_wide(garbage, greedy["cost2"], settings["epsilon"], settings["offset"], narrow_cols + 1, settings["wide_cols"],
-                                      settings.get("wide_nodes", WIDE_NODES))
+            passes = settings.get("wide_passes", 1)          # (1: the call of before, without the argument)
+            wide =ctx.round_bnb_wide(garbage, greedy["cost2"], settings["epsilon"], settings["offset"], narrow_cols + 1, settings["wide_cols"],
+                                      settings.get("wide_nodes", WIDE_NODES), **({"passes": passes} if passes > 1 else {}))
         # ---- every problem's answer from the device, once; under device rounds the answered ones get no model
         found = [_gpu_answer(exact, bnb, greedy, p, wide) for p in range(len(todo))]
         direct, host, out, source = {}, list(range(len(todo))), None, arr
@@ -394,6 +402,11 @@ WIDE_HELP = ("Recommended: 128 -- measured on an MI355X (profiles/cluster_bnb_wi
              "that N admits (4 096 up to 128 columns, 8 192 up to 256, 4 096 beyond), so a larger N changes the cap of the smaller problems too.")
 
 
+WIDE_PASSES_HELP = ("Measured per call on an MI355X (profiles/cluster_bnb_wide_passes.txt): under -mi 256, 4 096 nodes a task and 8 passes prove 80 of 80 "
+                    "problems of about 245 columns in 89 ms with no launch over 18 ms, where the single pass proves 4 of 80; under -mi 1000 nothing is "
+                    "proven with 8 passes either.  The whole loop with the flag has not been measured, so the default stays 1.")
+
+
 DEVICE_ROUNDS_HELP = ("Recommended together with --exact-small 24 --exact-bnb 64 at small maximum ILP sizes: measured on an MI355X "
                       "(profiles/cluster_device_rounds.txt; the first 40 of the cluster-many workload's 400 files, written without gaps, sixteen "
                       "workers, medians of three runs) the whole loop takes 10.3 s against 26.7 s under -mi 24 and 2.8 s against 18.1 s under "
@@ -448,6 +461,10 @@ def parse_args(argv=None):
                                  cluster_solve.BNB_WIDE_MAX_COLS, WIDE_HELP))
     parser.add_argument("--wide-nodes", type=int, default=WIDE_NODES, metavar="M",
                         help="Budget of a round's wide branch and bound, as --bnb-nodes.  Default: {}".format(WIDE_NODES))
+    parser.add_argument("--wide-passes", type=int, default=1, choices=range(1, WIDE_MAX_PASSES + 1), metavar="K",
+                        help="Passes of a round's wide branch and bound (1 .. {}): beyond the first, the open subtrees of the tasks that stopped at "
+                             "their node cap are searched as tasks of their own, bounded by the best set found so far, so that a launch stays "
+                             "one node cap long.  Default: 1 (the single search, nothing changes).  {}".format(WIDE_MAX_PASSES, WIDE_PASSES_HELP))
     parser.add_argument("--device-rounds", action="store_true",
                         help="Keep every round's models on the GPU and read the isoforms of the problems --exact-small / --exact-bnb / "
                              "--exact-wide have answered out there; only the other problems are modelled on the host, for the solver.  Needs "
@@ -480,7 +497,8 @@ def main(argv=None, make_context=None):
     args = parse_args(argv)
     args.segment_dir = args.segment_dir.rstrip("/")
     settings = ilp_settings(args.recycle_model, args.epsilon, args.gap_offset, args.timeout, args.max_rounds, args.min_isoform_size, args.max_ilp,
-                            args.incumbent, args.exact_small, args.exact_masks, args.exact_bnb, args.bnb_nodes, args.device_rounds, args.exact_wide, args.wide_nodes)
+                            args.incumbent, args.exact_small, args.exact_masks, args.exact_bnb, args.bnb_nodes, args.device_rounds, args.exact_wide, args.wide_nodes,
+                            args.wide_passes)
     cluster_solve.check_settings(settings)
     jobs = []
     for contig in os.listdir(args.segment_dir):

@@ -170,6 +170,7 @@ EXPORTS = ["fclu_abi_version", "fclu_create", "fclu_destroy", "fclu_last_error",
            "fclu_round_exact", "fclu_round_exact_results", "fclu_round_exact_timing",
            "fclu_round_bnb", "fclu_round_bnb_results", "fclu_round_bnb_timing",
            "fclu_round_bnb_wide", "fclu_round_bnb_wide_results", "fclu_round_bnb_wide_timing",
+           "fclu_round_bnb_wide_passes", "fclu_round_bnb_wide_pass_stats",
            "fclu_round_models_resident", "fclu_round_readout", "fclu_round_readout_results", "fclu_round_readout_timing"]
 ERR_UNSUPPORTED = 3
 _lib = None
@@ -343,6 +344,10 @@ def load():
     L.fclu_round_bnb_wide.argtypes = [vp, vp, vp, ctypes.c_double, ctypes.c_double] + [ctypes.c_int32] * 5 + [ctypes.c_int64]
     L.fclu_round_bnb_wide_results.restype = ctypes.c_int
     L.fclu_round_bnb_wide_results.argtypes = [vp, ctypes.POINTER(_Bnb)]
+    L.fclu_round_bnb_wide_passes.restype = ctypes.c_int
+    L.fclu_round_bnb_wide_passes.argtypes = [vp, vp, vp, ctypes.c_double, ctypes.c_double] + [ctypes.c_int32] * 5 + [ctypes.c_int64, ctypes.c_int32]
+    L.fclu_round_bnb_wide_pass_stats.restype = ctypes.c_int
+    L.fclu_round_bnb_wide_pass_stats.argtypes = [vp, vp, ctypes.c_int32]
     L.fclu_round_bnb_wide_timing.restype = ctypes.c_int
     L.fclu_round_bnb_wide_timing.argtypes = [vp] + [ctypes.POINTER(ctypes.c_float)] * 3
     L.fclu_round_models_resident.restype = ctypes.c_int
@@ -667,17 +672,18 @@ class Context:
         out["mask"] = out["mask"].reshape(-1)
         return out
 
-    def _round_search(self, name, g2, col_off, ub2, epsilon, offset, min_cols, max_cols, max_nodes, depth, node_cap, words):
+    def _round_search(self, name, g2, col_off, ub2, epsilon, offset, min_cols, max_cols, max_nodes, depth, node_cap, words, passes=None):
         """round_bnb() and round_bnb_wide() behind their own arguments: the entry points fclu_<name> / fclu_<name>_results, the resolved
         depth and node_cap, and the words of a problem's mask (fclu_bnb_wide has fclu_bnb's layout, so _Bnb reads both); mask comes
-        back as a (problems, words) array."""
+        back as a (problems, words) array.  passes: not None = through fclu_<name>_passes."""
         ub = np.ascontiguousarray(np.asarray(ub2, np.int64).reshape(-1))
         if ub.size != col_off.size - 1:
             raise ClusterError("%s: %d bounds for the %d problems of the last round_models() call" % (name, ub.size, col_off.size - 1))
-        rc = getattr(self._L, "fclu_" + name)(self._h, g2.ctypes.data if g2.size else None, ub.ctypes.data if ub.size else None, 1.0 - float(epsilon),
-                                              1.0 + float(epsilon), int(offset), int(min_cols), int(max_cols), int(depth), int(node_cap), int(max_nodes))
+        entry, more = ("fclu_" + name, ()) if passes is None else ("fclu_%s_passes" % name, (int(passes),))
+        rc = getattr(self._L, entry)(self._h, g2.ctypes.data if g2.size else None, ub.ctypes.data if ub.size else None, 1.0 - float(epsilon),
+                                     1.0 + float(epsilon), int(offset), int(min_cols), int(max_cols), int(depth), int(node_cap), int(max_nodes), *more)
         if rc != 0:
-            raise ClusterError("fclu_%s: " % name + self._L.fclu_last_error(self._h).decode(), rc)
+            raise ClusterError("%s: " % entry + self._L.fclu_last_error(self._h).decode(), rc)
         b = _Bnb()
         rc = getattr(self._L, "fclu_%s_results" % name)(self._h, ctypes.byref(b))
         if rc != 0:
@@ -690,21 +696,32 @@ class Context:
     def round_bnb_timing(self):
         return self._times(self._L.fclu_round_bnb_timing, "prep_ms", "search_ms", "longest_launch_ms")
 
-    def round_bnb_wide(self, garbage, ub2, epsilon, offset, min_cols, max_cols, max_nodes, depth=None, node_cap=None):
+    def round_bnb_wide(self, garbage, ub2, epsilon, offset, min_cols, max_cols, max_nodes, depth=None, node_cap=None, passes=1):
         """round_bnb() for the problems of min_cols .. max_cols (<= 1024) columns whose tables fit (bnb_wide_lds_bytes), one device call
         (include/freddie_cluster.h, fclu_bnb_wide; the definition is cluster_solve.exact_bnb_wide()).  depth None = cluster_solve.BNB_DEPTH;
         node_cap None = cluster_solve.bnb_wide_node_cap(R) of the round's largest problem of min_cols .. max_cols columns (a call has one
         cap: the measured defaults are per size, and the largest problem is the one that decides a launch's time).  Returns round_bnb()'s dict with mask as a (problems, 16) uint64 array,
-        low word first, and the depth and node_cap used; round_bnb_wide_solution() cuts one problem out."""
+        low word first, and the depth and node_cap used; round_bnb_wide_solution() cuts one problem out.  passes > 1: the capped tasks' open
+        subtrees are run as tasks of further passes (fclu_round_bnb_wide_passes; cluster_solve.exact_bnb_wide(passes=...)); capped then
+        counts the tasks still open, and round_bnb_wide_pass_stats() has a row a pass.  passes == 1 makes fclu_round_bnb_wide's call."""
         depth = cluster_solve.BNB_DEPTH if depth is None else depth
         g2, col_off = self._garbage2("round_bnb_wide", garbage)
         if node_cap is None:
             cols = np.diff(col_off)
             cols = cols[(cols >= int(min_cols)) & (cols <= int(max_cols))]
             node_cap = cluster_solve.bnb_wide_node_cap(int(cols.max()) if cols.size else int(max_cols))
-        out = self._round_search("round_bnb_wide", g2, col_off, ub2, epsilon, offset, min_cols, max_cols, max_nodes, depth, node_cap, BNB_WIDE_WORDS)
-        out.update(depth=int(depth), node_cap=int(node_cap))
+        out = self._round_search("round_bnb_wide", g2, col_off, ub2, epsilon, offset, min_cols, max_cols, max_nodes, depth, node_cap, BNB_WIDE_WORDS,
+                                 None if int(passes) == 1 else passes)
+        out.update(depth=int(depth), node_cap=int(node_cap), passes=int(passes))
         return out
+
+    def round_bnb_wide_pass_stats(self):
+        """The passes of the last round_bnb_wide() call that ran: a list of dict(tasks, nodes, capped, launches, problems)."""
+        rows = np.zeros((BNB_WIDE_MAX_PASSES, 5), np.int64)
+        rc = self._L.fclu_round_bnb_wide_pass_stats(self._h, rows.ctypes.data, BNB_WIDE_MAX_PASSES)
+        if rc != 0:
+            raise ClusterError("fclu_round_bnb_wide_pass_stats: " + self._L.fclu_last_error(self._h).decode(), rc)
+        return [dict(zip(("tasks", "nodes", "capped", "launches", "problems"), map(int, row))) for row in rows if row[0] > 0]
 
     def round_bnb_wide_timing(self):
         return self._times(self._L.fclu_round_bnb_wide_timing, "prep_ms", "search_ms", "longest_launch_ms")
@@ -963,6 +980,8 @@ def round_bnb_solution(arr, p):
 
 
 BNB_WIDE_WORDS = 16           # words of a set of Context.round_bnb_wide() (FCLU_BNB_WIDE_WORDS)
+BNB_WIDE_MAX_PASSES = 16      # passes of one Context.round_bnb_wide() call at the most
+BNB_WIDE_MAX_PASS_TASKS = 1 << 16   # a problem whose next pass would hold more tasks is not continued (exact_bnb_wide()'s max_tasks)
 BNB_WIDE_LDS_BYTES = 160 * 1024
 BNB_WIDE_WAVES = 8
 

@@ -370,11 +370,14 @@ def _bnb_leaf(tb, S):
     return cost2
 
 
-def bnb_task(tb, t, D, ub2=None, node_cap=BNB_NODE_CAP, weak=False):
-    """Task t of a problem's 2^D (exact_bnb()'s docstring): (cost2, mask, nodes, capped); cost2 -1 and mask 0 when it found no leaf."""
+def bnb_prefix_task(tb, P, L, best2=None, node_cap=BNB_NODE_CAP, weak=False):
+    """The task on the prefix (P, L) -- the columns 0 .. L - 1 are fixed and P is the set of them that are in -- of exact_bnb()'s and
+    exact_bnb_wide()'s docstrings: (cost2, mask, nodes, capped, open); cost2 -1 and mask 0 when it found no leaf.  best2: where the task's
+    best cost starts (None: no bound; a leaf of equal cost is still taken).  open: the open children (prefix, length) of a capped task, by
+    ascending level, at the top level the include child first; empty when the task is not capped."""
     R, conf = tb["R"], tb["conf"]
-    best2, mask, have, nodes = (_BNB_NONE if ub2 is None else ub2), 0, False, 1
-    S = t
+    best2, mask, have, nodes = (_BNB_NONE if best2 is None else best2), 0, False, 1
+    S = P
 
     def leaf(S):
         nonlocal best2, mask, have
@@ -383,16 +386,16 @@ def bnb_task(tb, t, D, ub2=None, node_cap=BNB_NODE_CAP, weak=False):
             best2, mask, have = cost2, S, True
 
     dead = any(conf[c] & S for c in _bits(S))
-    if not dead and D == R:
+    if not dead and L == R:
         leaf(S)
-    capped = False
-    if not dead and D < R and not _bnb_pruned(tb, S, D, best2, weak):
-        d, tried_in, tried_out = D, 0, 0                     # the stack: frame d is S's low d bits and two bits of progress
+    capped, opened = False, []
+    if not dead and L < R and not _bnb_pruned(tb, S, L, best2, weak):
+        d, tried_in, tried_out = L, 0, 0                     # the stack: frame d is S's low d bits and two bits of progress
         while True:
             bit = 1 << d
             Sd = S & (bit - 1)
             if tried_out & bit:                              # both children done: pop
-                if d == D:
+                if d == L:
                     break
                 d -= 1
                 continue
@@ -400,12 +403,17 @@ def bnb_task(tb, t, D, ub2=None, node_cap=BNB_NODE_CAP, weak=False):
                 tried_in |= bit
                 if conf[d] & Sd:
                     continue
-                child = Sd | bit
+                child, inc = Sd | bit, True
             else:
                 tried_out |= bit
-                child = Sd
+                child, inc = Sd, False
             if nodes >= node_cap:
                 capped = True
+                if inc:                                      # the child was not evaluated: its progress bit is taken back
+                    tried_in &= ~bit
+                else:
+                    tried_out &= ~bit
+                opened = bnb_open_children(conf, S, tried_in, tried_out, L, d)
                 break
             nodes += 1
             if d + 1 == R:
@@ -414,7 +422,28 @@ def bnb_task(tb, t, D, ub2=None, node_cap=BNB_NODE_CAP, weak=False):
                 S, d = child, d + 1
                 tried_in &= ~(1 << d)
                 tried_out &= ~(1 << d)
-    return (best2 if have else -1), (mask if have else 0), nodes, capped
+    return (best2 if have else -1), (mask if have else 0), nodes, capped, opened
+
+
+def bnb_open_children(conf, S, tried_in, tried_out, L, d):
+    """The open children of a task on a prefix of length L that was capped at level d, from its frame after the roll-back: the subtrees
+    its walk has not entered, as prefixes (set, length)."""
+    out = []
+    for j in range(L, d + 1):
+        Sj = S & ((1 << j) - 1)
+        if j == d and not tried_in >> j & 1:
+            if not conf[j] & Sj:
+                out.append((Sj | 1 << j, j + 1))
+            out.append((Sj, j + 1))
+        elif not tried_out >> j & 1:
+            out.append((Sj, j + 1))
+    return out
+
+
+def bnb_task(tb, t, D, ub2=None, node_cap=BNB_NODE_CAP, weak=False):
+    """Task t of a problem's 2^D (exact_bnb()'s docstring): (cost2, mask, nodes, capped); cost2 -1 and mask 0 when it found no leaf.  It
+    is bnb_prefix_task() on the prefix (t, D)."""
+    return bnb_prefix_task(tb, t, D, ub2, node_cap, weak)[:4]
 
 
 def exact_bnb(model, settings, ub2=None, depth=BNB_DEPTH, node_cap=BNB_NODE_CAP, weak=False):
@@ -447,19 +476,45 @@ def exact_bnb(model, settings, ub2=None, depth=BNB_DEPTH, node_cap=BNB_NODE_CAP,
     return _bnb_search(bnb_tables(model, settings), model, ub2, depth, node_cap, weak)
 
 
-def _bnb_search(tb, model, ub2, depth, node_cap, weak):
-    """exact_bnb()'s body on the tables tb: every task, and the result rule."""
+def bnb_pass_bound(ub2, best):
+    """The bound every task of a pass starts at: the smaller of ub2 and the best (cost2, mask) of the passes before, either may be None."""
+    return ub2 if best is None else best[0] if ub2 is None else min(ub2, best[0])
+
+
+def bnb_pass(tb, tasks, bound, node_cap, weak=False):
+    """One pass of exact_bnb_wide(): the tasks (prefix, length), each started at bound.  dict(best = the smallest (cost2, mask) or None,
+    nodes, capped, opened = the capped tasks' open children, stats = the pass's entry of pass_stats)."""
+    best, nodes, capped, opened = None, 0, 0, []
+    for P, L in tasks:
+        cost2, mask, n, cap, children = bnb_prefix_task(tb, P, L, bound, node_cap, weak)
+        nodes += n
+        capped += cap
+        opened += children
+        if cost2 >= 0 and (best is None or (cost2, mask) < best):
+            best = (cost2, mask)
+    return dict(best=best, nodes=nodes, capped=capped, opened=opened,
+                stats=dict(tasks=len(tasks), nodes=nodes, capped=capped, min_len=min(L for _, L in tasks), max_len=max(L for _, L in tasks)))
+
+
+def _bnb_search(tb, model, ub2, depth, node_cap, weak, passes=1, max_tasks=None):
+    """exact_bnb()'s body on the tables tb: every task, the passes of exact_bnb_wide(), and the result rule."""
     R = tb["R"]
     if depth < 0 or node_cap < 1:
         raise ValueError("depth %r, node_cap %r: at least 0 and 1" % (depth, node_cap))
+    if passes < 1 or (max_tasks is not None and max_tasks < 1):
+        raise ValueError("passes %r, max_tasks %r: at least 1" % (passes, max_tasks))
     D = min(R, depth)
-    best, nodes, capped = None, 0, 0
-    for t in range(1 << D):
-        cost2, mask, n, cap = bnb_task(tb, t, D, ub2, node_cap, weak)
-        nodes += n
-        capped += cap
-        if cost2 >= 0 and (best is None or (cost2, mask) < best):
-            best = (cost2, mask)
+    best, nodes, capped, stats = None, 0, 0, []
+    tasks = [(t, D) for t in range(1 << D)]
+    for k in range(passes):
+        one = bnb_pass(tb, tasks, bnb_pass_bound(ub2, best), node_cap, weak)
+        nodes, capped = nodes + one["nodes"], one["capped"]
+        if one["best"] is not None and (best is None or one["best"] < best):
+            best = one["best"]
+        stats.append(one["stats"])
+        tasks = one["opened"]
+        if not tasks or (max_tasks is not None and len(tasks) > max_tasks):
+            break
     status = "unproven" if capped or (best is None and ub2 is not None) else "optimal" if best is not None else "infeasible"
     out = dict(status=status, cost2=None, cost=None, mask=None, members=None, x=None, e=None, nodes=nodes, capped=capped)
     if best is not None:
@@ -467,6 +522,7 @@ def _bnb_search(tb, model, ub2, depth, node_cap, weak):
         x = [mask >> c & 1 for c in range(R)]
         out.update(cost2=cost2, cost=cost2 / 2.0, mask=mask, members=list(_bits(mask)), x=x,
                    e=[int(any(x[c] for c in support)) for support in model["support"]])
+    out["pass_stats"] = stats
     return out
 
 
@@ -481,13 +537,36 @@ def bnb_wide_node_cap(R):
     return BNB_NODE_CAP if R <= BNB_MAX_COLS else 8192 if 128 < R <= 256 else 4096
 
 
-def exact_bnb_wide(model, settings, ub2=None, depth=BNB_DEPTH, node_cap=None):
-    """exact_bnb() for a model of at most BNB_WIDE_MAX_COLS = 1024 columns -- the definition the GPU's fclu_round_bnb_wide reproduces
-    exactly, node counts included.  exact_bnb()'s docstring holds word for word (tables, node, bound LB2, lower-side row test, leaf, tasks,
-    cap, result rule, node counts); a mask is a Python integer of up to 1024 bits and the smallest mask is the smaller integer.  On a
-    model of at most 64 columns the two return equal dicts.  node_cap None = bnb_wide_node_cap(R)."""
+def exact_bnb_wide(model, settings, ub2=None, depth=BNB_DEPTH, node_cap=None, passes=1, max_tasks=None):
+    """exact_bnb() for a model of at most BNB_WIDE_MAX_COLS = 1024 columns -- the definition the GPU's fclu_round_bnb_wide and
+    fclu_round_bnb_wide_passes reproduce exactly, node counts included.  exact_bnb()'s docstring holds word for word (tables, node, bound
+    LB2, lower-side row test, leaf, tasks, cap, result rule, node counts); a mask is a Python integer of up to 1024 bits and the smallest
+    mask is the smaller integer.  On a model of at most 64 columns and with one pass the two return equal dicts (exact_bnb()'s has the one-pass pass_stats too).
+    node_cap None = bnb_wide_node_cap(R).
+
+    Passes: a capped task is not abandoned.  A task is a prefix (P, L): the columns 0 .. L - 1 are fixed, P of them in (bnb_prefix_task();
+        exact_bnb()'s task t is the prefix (t, D)).  It is dead on a pair inside P, counting one node; a leaf at L = R; else it is tested by
+        the pruning rules, the rows always among them, and searched depth first over the columns L .. R - 1.  Its best starts at the pass's
+        bound and a leaf of equal cost is still taken.
+    Open children: where a task's count has reached node_cap before a child at level d is evaluated, that child's progress bit is taken
+        back.  With Sj = the low j bits of S, the open children are, at the levels j = L .. d - 1, the exclude child (Sj, j + 1) where
+        tried_out bit j is clear; at j = d, where tried_in bit d is clear, the include child (Sj | bit j, j + 1) when conf[j] & Sj == 0 and
+        the exclude child (Sj, j + 1), and where only tried_out bit d is clear the exclude child alone.  The subtrees of the task's prefix
+        are exactly those its walk has finished, those under the open children and the nodes on the stack, which are no leaves.
+    Pass 1 is the 2^D tasks, bounded by ub2.  Pass k + 1 is the open children of pass k's capped tasks; each of them starts at B = the
+        smaller of ub2 and the best cost2 of every task of the passes before, and at nothing else.  The search ends when no task is open,
+        after ``passes`` passes, or when the next pass would hold more than max_tasks tasks (None: no limit): the problem is then not
+        continued and stays as it is.  No order among a pass's tasks enters: minima and sums only.
+    Result: the lexicographic minimum of (cost2, mask) over all tasks of all passes; nodes = all counts summed; capped = the tasks still
+        open at the end, that is the capped tasks of the last pass that ran; the status by exact_bnb()'s rule with those.  pass_stats: a
+        dict(tasks, nodes, capped, min_len, max_len) a pass that ran (the prefix lengths' range).
+    Why an "optimal" end is exact_small()'s (cost2, mask): pruning is strict (LB2 > best2) and every best2 used is at least the optimal
+        cost2 c* (it is ub2, which the result rule only trusts when a leaf is at or under it, or a leaf's cost), so no node above a set of
+        cost c* is ever dropped by the bound, and the row test drops only nodes without a feasible leaf.  Every set of cost c* therefore
+        lies in a finished subtree or under an open child; with no task open all were reached as leaves, each was taken unless the task
+        held an equal-cost smaller mask, and the minimum over the tasks is the smallest cost2, then the smallest mask."""
     tb = bnb_tables(model, settings, BNB_WIDE_MAX_COLS, "exact_bnb_wide")
-    return _bnb_search(tb, model, ub2, depth, bnb_wide_node_cap(tb["R"]) if node_cap is None else node_cap, False)
+    return _bnb_search(tb, model, ub2, depth, bnb_wide_node_cap(tb["R"]) if node_cap is None else node_cap, False, passes, max_tasks)
 
 
 def solve_round(model, settings):

@@ -182,21 +182,25 @@ EX_HD bool bw_leaf(const BwView &v, Wave &wv, const ex_u64 *S, ex_i64 *cost2) {
     return true;
 }
 
-struct BwResult { ex_i64 cost2; int nodes, capped; };        // cost2 -1: the task found no leaf; its set is the state's fifth array (zero without one)
+struct BwResult { ex_i64 cost2; int nodes, capped, d; };     // cost2 -1: the task found no leaf; its set is the state's fifth array (zero without one); d: the level a capped task stopped at
 
-// Task t of the problem's 2^D (D = min(R, depth) <= 20, 0 <= t < 2^D), ub2 < 0 = no bound, node_cap >= 1: bnb_task()'s walk, step for
-// step, on sets of W words.  The stack: frame d is S's low d bits and bit d of tried_in / tried_out.
+// The task on the prefix (prefix, L) -- the columns 0 .. L - 1 are fixed, the prefix's low L bits say which are in; n_prefix of its W
+// words are given, the others are empty; L is clamped to [0, R] -- ub2 < 0 = no bound, node_cap >= 1: bnb_prefix_task()'s walk, step for
+// step, on sets of W words.  The stack: frame d is S's low d bits and bit d of tried_in / tried_out.  A capped task takes the progress
+// bit of the child it did not evaluate back and leaves its frame in the state: S, tried_in and tried_out (the first, third and fourth
+// array) and res.d.
 template <class Wave>
-EX_HD BwResult bw_task(const BwView &v, Wave &wv, ex_u64 t, int D, ex_i64 ub2, int node_cap) {
+EX_HD BwResult bw_task_from(const BwView &v, Wave &wv, const ex_u64 *prefix, int n_prefix, int L, ex_i64 ub2, int node_cap) {
     const int R = v.R, W = v.W, n_st = bw_state_words(W, v.EW);
     ex_u64 *S = v.st, *child = S + W, *tin = child + W, *tout = tin + W, *best = tout + W;
     wv.sync();
     wv.each([&](int lane) { for (int x = lane; x < n_st; x += kBwLanes) v.st[x] = 0ull; });
     wv.sync();
-    BwResult res = {-1, 1, 0};
+    L = (int)ex_clamp(L, 0, R);
+    BwResult res = {-1, 1, 0, L};
     ex_i64 best2 = ub2 < 0 ? kBnbNone : ub2, cost2 = 0;
     bool have = false;
-    S[0] = t & bnb_low(D);
+    for (int w = 0; w < W && w < n_prefix; ++w) S[w] = 64 * w + 64 <= L ? prefix[w] : 64 * w < L ? prefix[w] & bnb_low(L - 64 * w) : 0ull;
     bw_cache(v, wv, S);
     const ex_u64 *blk = v.st + 7 * W;
     if (wv.any([&](int lane) {
@@ -205,20 +209,20 @@ EX_HD BwResult bw_task(const BwView &v, Wave &wv, ex_u64 t, int D, ex_i64 ub2, i
             return false;
         }))
         return res;
-    if (D >= R) {
+    if (L >= R) {
         if (bw_leaf(v, wv, S, &cost2) && cost2 <= best2) {
             res.cost2 = cost2;
             for (int w = 0; w < W; ++w) best[w] = S[w];
         }
         return res;
     }
-    if (bw_pruned(v, wv, S, D, best2, true)) return res;
-    int d = D;
+    if (bw_pruned(v, wv, S, L, best2, true)) return res;
+    int d = L;
     for (;;) {
         const int wd = d >> 6;
         const ex_u64 bit = 1ull << (d & 63);
         if (tout[wd] & bit) {                                // both children done: pop
-            if (d == D) break;
+            if (d == L) break;
             --d;
             continue;
         }
@@ -239,7 +243,11 @@ EX_HD BwResult bw_task(const BwView &v, Wave &wv, ex_u64 t, int D, ex_i64 ub2, i
             tout[wd] |= bit;
             in = false;
         }
-        if (res.nodes >= node_cap) { res.capped = 1; break; }
+        if (res.nodes >= node_cap) {                         // the child is not evaluated: its progress bit is taken back
+            if (in) tin[wd] &= ~bit; else tout[wd] &= ~bit;
+            res.capped = 1; res.d = d;
+            break;
+        }
         ++res.nodes;
         if (d + 1 == R) {
             if (bw_leaf(v, wv, child, &cost2) && (cost2 < best2 || (cost2 == best2 && (!have || bw_less(child, best, W))))) {
@@ -254,6 +262,68 @@ EX_HD BwResult bw_task(const BwView &v, Wave &wv, ex_u64 t, int D, ex_i64 ub2, i
     }
     if (have) res.cost2 = best2;
     return res;
+}
+
+// Task t of the problem's 2^D (D = min(R, depth) <= 20, 0 <= t < 2^D): the task on the prefix (t, D).
+template <class Wave>
+EX_HD BwResult bw_task(const BwView &v, Wave &wv, ex_u64 t, int D, ex_i64 ub2, int node_cap) {
+    const ex_u64 prefix = t & bnb_low(D);
+    return bw_task_from(v, wv, &prefix, 1, D, ub2, node_cap);
+}
+
+// ---- the open children of a capped task (cluster_solve.bnb_open_children) ---------------------------------------------------------
+// A capped task's frame: S, tried_in and tried_out of W words each (after the roll-back), the prefix length L and the level d it stopped
+// at, 0 <= L <= d < R.  A record is a prefix of the next pass: its length, then its W words.
+EX_HD int bw_record_words(int W) { return 1 + W; }
+EX_HD int bw_frame_words(int W) { return 3 * W + 1; }        // S, tried_in, tried_out, then L | d << 32
+
+// bits lo .. hi - 1 of word w
+EX_HD ex_u64 bw_range_word(int w, int lo, int hi) {
+    const int a = lo - 64 * w, b = hi - 64 * w;
+    if (b <= 0 || a >= 64) return 0ull;
+    return (b >= 64 ? ~0ull : bnb_low(b)) & ~(a <= 0 ? 0ull : bnb_low(a));
+}
+
+// the include child at level d is open: tried_in bit d is clear and no column of S's low d bits conflicts with column d
+template <class Wave>
+EX_HD bool bw_open_include(Wave &wv, const ex_u64 *conf_row, const ex_u64 *S, const ex_u64 *tin, int d, int W) {
+    if (bw_bit(tin, d)) return false;
+    return !wv.any([&](int lane) {
+        for (int w = lane; w < W; w += kBwLanes)
+            if (conf_row[w] & S[w] & bw_range_word(w, 0, d)) return true;
+        return false;
+    });
+}
+
+// The number of open children: the levels L .. d - 1 whose tried_out bit is clear, the exclude child at d (its tried_out bit is clear in
+// every capped frame) and the include child at d when it is open.
+EX_HD int bw_open_count(const ex_u64 *tout, int L, int d, int W, bool include_open) {
+    int n = include_open && !bw_bit(tout, d) ? 1 : 0;
+    for (int w = 0; w < W; ++w) n += bnb_popc(~tout[w] & bw_range_word(w, L, d + 1));
+    return n;
+}
+
+// Writes the open children as records of 1 + W words at rec, by ascending level, at level d the include child first; max_records bounds
+// what is written.  A lane writes every 64th word of a record.  Returns the records written.
+template <class Wave>
+EX_HD int bw_open_emit(Wave &wv, const ex_u64 *S, const ex_u64 *tout, int L, int d, int W, bool include_open, ex_u64 *rec, ex_i64 max_records) {
+    const int rw = bw_record_words(W);
+    int n = 0;
+    for (int w = 0; w < W; ++w)
+        for (ex_u64 m = ~tout[w] & bw_range_word(w, L, d + 1); m; m &= m - 1) {
+            const int j = 64 * w + bnb_ctz(m);
+            for (int inc = (j == d && include_open) ? 1 : 0; inc >= 0; --inc) {
+                if (n >= max_records) return n;
+                ex_u64 *out = rec + (ex_i64)n * rw;
+                wv.each([&](int lane) {
+                    if (lane == 0) out[0] = (ex_u64)(j + 1);
+                    for (int x = lane; x < W; x += kBwLanes)
+                        out[1 + x] = (S[x] & bw_range_word(x, 0, j)) | (inc && x == (j >> 6) ? 1ull << (j & 63) : 0ull);
+                });
+                ++n;
+            }
+        }
+    return n;
 }
 
 #endif

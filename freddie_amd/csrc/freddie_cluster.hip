@@ -1564,6 +1564,11 @@ __global__ void __launch_bounds__(256) k_bnb_reduce(const int *list, const i64 *
 constexpr i64 kBwLaunchNodes = 1ll << 26;      // task-nodes of budget (tasks x node_cap) one launch holds (profiles/cluster_bnb_wide.txt)
 constexpr int kBwMaxLaunches = 4096;           // launches of one call (an event each)
 constexpr int kBwThreads = kBwWaves * kBwLanes;
+constexpr int kBwMaxPasses = 16;               // passes of one fclu_round_bnb_wide_passes call
+constexpr i64 kBwMaxPassTasks = 1ll << 16;     // a problem whose next pass would hold more tasks is not continued
+constexpr int kBwFromItem = 8;                 // records a workgroup of a later pass walks, eight at a time.  Measured (profiles/cluster_bnb_wide_passes.txt): the
+                                               // open subtrees of this workload are long walks, so a wave's second turn doubles the launch -- 8 / 64 / 512 records
+                                               // an item give a longest launch of 29.7 / 88.2 / 88.5 ms at 490 columns and 4 096 nodes, and 18 ms each at 245
 
 struct BwProb {
     ExactProb b;
@@ -1628,15 +1633,24 @@ struct BwDevWave {
 
 struct BwTask { i64 cost2; int nodes, capped; u64 mask[kBwMaxWords]; };  // a task's result: cost2 -1 and an empty mask when it found no leaf
 
-// A workgroup per item = (problem, first task, tasks <= 8, -): the problem's tables by column and g2 are staged in LDS, wave i runs
-// task first + i on its own state words behind them and its first lane writes the result to the problem's place task_off[problem] +
-// task of the per-task array.  Tasks share nothing and no workgroup waits for another; every loop is bounded by R, the table sizes or
-// node_cap.  The items, the descriptors and their offsets (it.x, tab0, conf0, task_off) are the host's own, built and checked in
-// bnb_wide_device before the launch, and are used as they are, as in k_bnb_search; what comes from the round's arrays is clamped.
-__global__ void __launch_bounds__(kBwThreads) k_bw_search(const int4 *items, const BwProb *probs, const u64 *tab, const u64 *conf, const int *g2, const i64 *ub2,
-                                                          const int *rows, i64 n_rows, const i64 *grp_seg_off, i64 n_grp, i64 n_grp_seg, const int *gk,
-                                                          const int *grp_len, double lo_f, double hi_f, int offset, int depth, int node_cap, const i64 *task_off,
-                                                          BwTask *tasks) {
+// What a pass leaves for the next one (fclu_round_bnb_wide_passes; all null for a single pass): per capped task its frame -- S, tried_in,
+// tried_out of W words each and L | d << 32, at frame_off[problem] + task * (3 W + 1) words -- and per task the number of its open
+// children (0 where it is not capped).
+struct BwSplitOut { u64 *frames; const i64 *frame_off; int *open_cnt; };
+
+// The body of k_bw_search and k_bw_search_from.  A workgroup per item = (problem, first task, tasks, -): the problem's tables by column and
+// g2 are staged in LDS once, wave i runs the tasks first + i, first + i + 8, ... (k_bw_search's items hold at most 8) on its own state
+// words behind them and writes the result to the problem's place task_off[problem] + task of the per-task array.  kFrom: a task's prefix
+// and its length are a record of 1 + W words at rec_off[problem] + task * (1 + W); else task t is the prefix (t, D).  Tasks share nothing
+// and no workgroup waits for another; every loop is bounded by R, the table sizes, the item's tasks or node_cap.  The items, the
+// descriptors and their offsets (it.x, tab0, conf0, task_off, rec_off, frame_off) are the host's own, built and checked in
+// bnb_wide_device before the launch, and are used as they are, as in k_bnb_search; what comes from the round's arrays and from the
+// records is clamped.
+template <bool kFrom>
+__device__ __forceinline__ void bw_search_body(const int4 *items, const BwProb *probs, const u64 *tab, const u64 *conf, const int *g2, const i64 *bound,
+                                               const int *rows, i64 n_rows, const i64 *grp_seg_off, i64 n_grp, i64 n_grp_seg, const int *gk, const int *grp_len,
+                                               double lo_f, double hi_f, int offset, int depth, int node_cap, const i64 *task_off, BwTask *tasks, const u64 *rec,
+                                               const i64 *rec_off, BwSplitOut so) {
     extern __shared__ __attribute__((aligned(16))) u64 s_bw[];
     const int4 it = items[blockIdx.x];
     const BwProb q = probs[it.x];
@@ -1650,8 +1664,6 @@ __global__ void __launch_bounds__(kBwThreads) k_bw_search(const int4 *items, con
     for (int c = tid; c < R; c += kBwThreads) s_g2[c] = g2[d.col0 + c];
     __syncthreads();
     const int D = R < depth ? R : depth;
-    const u64 t = (u64)(unsigned)it.y + (u64)wave;
-    if (wave >= it.z || (t >> D)) return;                    // (no such task: the host cuts the items inside 2^D)
     BwView v;
     v.icol = s_bw; v.ccol = s_bw + (i64)R * EW; v.conf = conf + q.conf0; v.g2 = s_g2; v.E = E; v.R = R; v.W = W; v.EW = EW;
     v.r0 = ex_clamp(d.row0, 0, n_rows); v.r1 = ex_clamp(d.row1, v.r0, n_rows); v.rows = rows;
@@ -1659,11 +1671,104 @@ __global__ void __launch_bounds__(kBwThreads) k_bw_search(const int4 *items, con
     v.lo_f = lo_f; v.hi_f = hi_f; v.offset = offset; v.max_lg = d.max_lg;
     v.st = s_state + (i64)wave * n_st;
     BwDevWave wv = {tid % kBwLanes};
-    const BwResult r = bw_task(v, wv, t, D, ub2[it.x], node_cap);
-    wv.sync();
-    BwTask *out = tasks + task_off[it.x] + (i64)t;
-    if (wv.lane == 0) { out->cost2 = r.cost2; out->nodes = r.nodes; out->capped = r.capped; }
-    if (wv.lane < kBwMaxWords) out->mask[wv.lane] = r.cost2 >= 0 && wv.lane < W ? v.st[4 * W + wv.lane] : 0ull;
+    const i64 b2 = bound[it.x];
+    // (the first pass's items hold at most eight tasks: one turn, as before the passes)
+    for (int i = wave; i < it.z; i = kFrom ? i + kBwWaves : it.z) {
+        const u64 t = (u64)(unsigned)it.y + (u64)i;
+        int L = D;
+        BwResult r;
+        if (kFrom) {
+            const u64 *rc = rec + rec_off[it.x] + (i64)t * bw_record_words(W);
+            L = (int)ex_clamp((i64)rc[0], 0, R);
+            r = bw_task_from(v, wv, rc + 1, W, L, b2, node_cap);
+        } else {
+            if (t >> D) return;                              // (no such task: the host cuts the items inside 2^D)
+            r = bw_task(v, wv, t, D, b2, node_cap);
+        }
+        wv.sync();
+        BwTask *out = tasks + task_off[it.x] + (i64)t;
+        if (wv.lane == 0) { out->cost2 = r.cost2; out->nodes = r.nodes; out->capped = r.capped; }
+        if (wv.lane < kBwMaxWords) out->mask[wv.lane] = r.cost2 >= 0 && wv.lane < W ? v.st[4 * W + wv.lane] : 0ull;
+        if (so.open_cnt) {
+            int n_open = 0;
+            if (r.capped && R > 0) {
+                const u64 *S = v.st, *tin = S + 2 * W, *tout = S + 3 * W;
+                const int dl = (int)ex_clamp(r.d, L, R - 1);
+                n_open = bw_open_count(tout, L, dl, W, bw_open_include(wv, v.conf + (i64)dl * W, S, tin, dl, W));
+                u64 *fr = so.frames + so.frame_off[it.x] + (i64)t * bw_frame_words(W);
+                for (int x = wv.lane; x < W; x += kBwLanes) { fr[x] = S[x]; fr[W + x] = tin[x]; fr[2 * W + x] = tout[x]; }
+                if (wv.lane == 0) fr[3 * W] = (u64)(unsigned)L | (u64)(unsigned)dl << 32;
+            }
+            if (wv.lane == 0) so.open_cnt[task_off[it.x] + (i64)t] = n_open;
+        }
+    }
+}
+
+// The first pass: task t of a problem's 2^D is the prefix (t, D), bounded by ub2.
+__global__ void __launch_bounds__(kBwThreads) k_bw_search(const int4 *items, const BwProb *probs, const u64 *tab, const u64 *conf, const int *g2, const i64 *ub2,
+                                                          const int *rows, i64 n_rows, const i64 *grp_seg_off, i64 n_grp, i64 n_grp_seg, const int *gk,
+                                                          const int *grp_len, double lo_f, double hi_f, int offset, int depth, int node_cap, const i64 *task_off,
+                                                          BwTask *tasks, BwSplitOut so) {
+    bw_search_body<false>(items, probs, tab, conf, g2, ub2, rows, n_rows, grp_seg_off, n_grp, n_grp_seg, gk, grp_len, lo_f, hi_f, offset, depth, node_cap, task_off,
+                          tasks, nullptr, nullptr, so);
+}
+
+// A later pass: the tasks are the records k_bw_emit wrote, bounded per problem by the smaller of ub2 and the best cost2 found so far.
+__global__ void __launch_bounds__(kBwThreads) k_bw_search_from(const int4 *items, const BwProb *probs, const u64 *tab, const u64 *conf, const int *g2,
+                                                               const i64 *bound, const int *rows, i64 n_rows, const i64 *grp_seg_off, i64 n_grp, i64 n_grp_seg,
+                                                               const int *gk, const int *grp_len, double lo_f, double hi_f, int offset, int depth, int node_cap,
+                                                               const i64 *task_off, BwTask *tasks, const u64 *rec, const i64 *rec_off, BwSplitOut so) {
+    bw_search_body<true>(items, probs, tab, conf, g2, bound, rows, n_rows, grp_seg_off, n_grp, n_grp_seg, gk, grp_len, lo_f, hi_f, offset, depth, node_cap, task_off,
+                         tasks, rec, rec_off, so);
+}
+
+// Behind a pass's search, a workgroup per problem of the pass: the exclusive scan of its tasks' open counts (a task's first record among
+// the problem's) and their sum for the host, 256 tasks a step.
+__global__ void __launch_bounds__(256) k_bw_split(const int *list, const i64 *task_off, const i64 *n_tasks, const int *open_cnt, i64 *open_off, i64 *n_open) {
+    __shared__ i64 s_scan[256];
+    const int p = list[blockIdx.x], tid = threadIdx.x;
+    const i64 n = n_tasks[p], base = task_off[p];
+    i64 running = 0;
+    for (i64 lo = 0; lo < n; lo += 256) {
+        const i64 t = lo + tid;
+        const i64 mine = t < n ? ex_clamp(open_cnt[base + t], 0, kBwMaxCols + 1) : 0;
+        s_scan[tid] = mine;
+        __syncthreads();
+        for (int step = 1; step < 256; step <<= 1) {
+            const i64 add = tid >= step ? s_scan[tid - step] : 0;
+            __syncthreads();
+            s_scan[tid] += add;
+            __syncthreads();
+        }
+        if (t < n) open_off[base + t] = running + s_scan[tid] - mine;
+        running += s_scan[255];
+        __syncthreads();
+    }
+    if (tid == 0) n_open[p] = running;
+}
+
+// In front of a pass's search, a workgroup per item of the pass before: wave i writes the open children of the item's capped tasks
+// first + i, first + i + 8, ... as the records open_off[task] .. of the problem's range, which starts at rec_off[problem] (-1: the problem
+// is not continued) and holds n_open[problem] records.  What the frames hold is clamped, and no record is written outside the range.
+__global__ void __launch_bounds__(kBwThreads) k_bw_emit(const int4 *items, const BwProb *probs, const u64 *conf, const i64 *task_off, const u64 *frames,
+                                                        const i64 *frame_off, const int *open_cnt, const i64 *open_off, const i64 *n_open, u64 *rec,
+                                                        const i64 *rec_off) {
+    const int4 it = items[blockIdx.x];
+    const i64 r0 = rec_off[it.x], total = n_open[it.x];
+    if (r0 < 0) return;
+    const BwProb q = probs[it.x];
+    const int R = q.b.n, W = q.W, wave = threadIdx.x / kBwLanes;
+    if (R <= 0) return;
+    BwDevWave wv = {(int)threadIdx.x % kBwLanes};
+    for (int i = wave; i < it.z; i += kBwWaves) {
+        const i64 t = (i64)it.y + i, at = task_off[it.x] + t;
+        const i64 cnt = open_cnt[at], first = open_off[at];
+        if (cnt <= 0 || first < 0 || first >= total) continue;
+        const u64 *fr = frames + frame_off[it.x] + t * bw_frame_words(W);
+        const int L = (int)ex_clamp((i64)(fr[3 * W] & 0xffffffffull), 0, R - 1), d = (int)ex_clamp((i64)(fr[3 * W] >> 32), L, R - 1);
+        const bool inc = bw_open_include(wv, conf + q.conf0 + (i64)d * W, fr, fr + W, d, W);
+        bw_open_emit(wv, fr, fr + 2 * W, L, d, W, inc, rec + r0 + first * bw_record_words(W), cnt < total - first ? cnt : total - first);
+    }
 }
 
 struct BwOut { i64 cost2, task, nodes, capped; };             // a problem's result: cost2 -1 when no task found a leaf; task: the one whose set it is
@@ -1698,6 +1803,56 @@ __global__ void __launch_bounds__(256) k_bw_reduce(const int *list, const BwProb
     const BwOut r = s_part[0];
     if (tid == 0) out[p] = r;
     if (tid < kBwMaxWords) out_mask[(i64)p * kBwMaxWords + tid] = r.cost2 >= 0 ? mine[r.task].mask[tid] : 0ull;
+}
+
+// the bound a problem's next pass starts at: the smaller of ub2 (< 0: none) and the best cost2 found so far (< 0: none); -1: none
+__device__ __forceinline__ i64 bw_next_bound(i64 ub2, i64 cost2) { return cost2 < 0 ? ub2 : ub2 < 0 || cost2 < ub2 ? cost2 : ub2; }
+
+// Behind k_bw_reduce, a lane per problem of the first pass.
+__global__ void __launch_bounds__(256) k_bw_bound(const int *list, int n_list, const i64 *ub2, const BwOut *out, i64 *bound) {
+    const int x = blockIdx.x * 256 + threadIdx.x;
+    if (x >= n_list) return;
+    const int p = list[x];
+    bound[p] = bw_next_bound(ub2[p], out[p].cost2);
+}
+
+// k_bw_reduce for a later pass: a workgroup per problem of the pass folds its tasks as k_bw_reduce does and then folds that into the
+// problem's running result -- the smaller (cost2, mask), the nodes summed, the open tasks those of this pass -- and sets the next bound.
+__global__ void __launch_bounds__(256) k_bw_fold(const int *list, const BwProb *probs, const i64 *task_off, const i64 *n_tasks, const BwTask *tasks, const i64 *ub2,
+                                                 BwOut *out, u64 *out_mask, i64 *bound) {
+    __shared__ BwOut s_part[256];
+    __shared__ u64 s_prev[kBwMaxWords];
+    const int p = list[blockIdx.x], tid = threadIdx.x, W = probs[p].W;
+    const i64 n = n_tasks[p];
+    const BwTask *mine = tasks + task_off[p];
+    if (tid < kBwMaxWords) s_prev[tid] = out_mask[(i64)p * kBwMaxWords + tid];
+    BwOut acc = {-1, 0, 0, 0};
+    for (i64 t = tid; t < n; t += 256) {
+        const BwTask &r = mine[t];
+        if (bw_better(r.cost2, r.mask, acc.cost2, mine[acc.task].mask, W)) { acc.cost2 = r.cost2; acc.task = t; }
+        acc.nodes += r.nodes; acc.capped += r.capped ? 1 : 0;
+    }
+    s_part[tid] = acc;
+    __syncthreads();
+    for (int step = 128; step > 0; step >>= 1) {
+        if (tid < step) {
+            BwOut a = s_part[tid];
+            const BwOut b = s_part[tid + step];
+            if (bw_better(b.cost2, mine[b.task].mask, a.cost2, mine[a.task].mask, W)) { a.cost2 = b.cost2; a.task = b.task; }
+            a.nodes += b.nodes; a.capped += b.capped;
+            s_part[tid] = a;
+        }
+        __syncthreads();
+    }
+    const BwOut r = s_part[0], before = out[p];
+    const bool better = n > 0 && bw_better(r.cost2, mine[r.task].mask, before.cost2, s_prev, W);
+    __syncthreads();                                         // (every lane has read out[p] and s_prev)
+    const i64 cost2 = better ? r.cost2 : before.cost2;
+    if (tid == 0) {
+        out[p] = BwOut{cost2, r.task, before.nodes + r.nodes, r.capped};
+        bound[p] = bw_next_bound(ub2[p], cost2);
+    }
+    if (better && tid < kBwMaxWords) out_mask[(i64)p * kBwMaxWords + tid] = mine[r.task].mask[tid];
 }
 
 // ================================================================================================================
@@ -1959,10 +2114,16 @@ struct fclu_ctx {
     bool have_bnb = false;
     // fclu_round_bnb_wide(): wd adds the problems, the tables by column, the conflict rows, the group segments' places, a result per task
     // and per problem with its 16 mask words
+    // fclu_round_bnb_wide_passes(): what a pass leaves for the next (ps, by the pass's parity: the emit in front of pass k + 1 reads pass k's
+    // while pass k + 1's are sized), the records, and per problem their first word, the open children, the bound and the pass's task count
+    struct BwPassBufs { Buf<int4> items; Buf<i64> task_off, frame_off, open_off; Buf<u64> frames; Buf<int> open_cnt; };
     struct : SearchBufs {
         Buf<BwProb> probs; Buf<u64> tab, conf, out_mask; Buf<BwTask> tasks; Buf<BwOut> out; Buf<int> gk;
+        BwPassBufs ps[2]; Buf<u64> rec; Buf<i64> rec_off, n_open, bound;
     } wd;
     SearchHost<BwOut> wh;
+    HostBuf<int64_t> w_n_open;
+    std::vector<int64_t> w_pass_stats;                       // five numbers a pass that ran
     float wprep_ms = 0.f, wsearch_ms = 0.f, wlongest_ms = 0.f;
     fclu_bnb_wide wide = {};
     bool have_wide = false;
@@ -2020,7 +2181,9 @@ int fail(fclu_ctx *c, int code, const char *fmt, ...) {
 //                                            many slices and several launches
 //   FCLU_BNB_SLICE=n        bnb_slice        n > 0: fclu_round_bnb gives a launch n tasks (and a workgroup min(n, 256)), so that a problem crosses several launches
 //   FCLU_BNB_WIDE_SLICE=n   bnb_wide_slice   n > 0: fclu_round_bnb_wide gives a launch n tasks (and a workgroup min(n, 8)), so that a problem crosses several launches
-struct Knobs { bool part_lds, prune_lds, rank, prune_edges, round_lds; i64 prune_lds_words, round_lds_bytes, exact_slice, bnb_slice, bnb_wide_slice; unsigned hash_mask; };
+//                                            (every pass of fclu_round_bnb_wide_passes)
+//   FCLU_BNB_WIDE_ITEM=n    bnb_wide_item    0 < n <= 4096: the records a workgroup of a later pass of fclu_round_bnb_wide_passes walks (kBwFromItem; profiles)
+struct Knobs { bool part_lds, prune_lds, rank, prune_edges, round_lds; i64 prune_lds_words, round_lds_bytes, exact_slice, bnb_slice, bnb_wide_slice, bnb_wide_item; unsigned hash_mask; };
 
 Knobs read_knobs() {
     const auto off = [](const char *name) { const char *e = getenv(name); return e && e[0] == '0'; };
@@ -2037,6 +2200,8 @@ Knobs read_knobs() {
     k.bnb_slice = (bs && atoll(bs) > 0 && atoll(bs) < (1ll << 30)) ? atoll(bs) : 0;
     const char *ws = getenv("FCLU_BNB_WIDE_SLICE");
     k.bnb_wide_slice = (ws && atoll(ws) > 0 && atoll(ws) < (1ll << 30)) ? atoll(ws) : 0;
+    const char *wi = getenv("FCLU_BNB_WIDE_ITEM");
+    k.bnb_wide_item = (wi && atoll(wi) > 0 && atoll(wi) <= 4096) ? atoll(wi) : kBwFromItem;
     const char *hb = getenv("FCLU_HASH_BITS");
     k.hash_mask = (hb && hb[0] >= '0' && hb[0] <= '9' && atoi(hb) < 32) ? (1u << atoi(hb)) - 1u : 0xffffffffu;
     return k;
@@ -3520,12 +3685,19 @@ int bnb_device(fclu_ctx *c, const Knobs &k, const int32_t *g2, const int64_t *ub
     return FCLU_OK;
 }
 
-// ---- the same search over the last round's problems of up to 1024 columns (fclu_round_bnb_wide) ---------------------------------
+// ---- the same search over the last round's problems of up to 1024 columns (fclu_round_bnb_wide, fclu_round_bnb_wide_passes) -----
+// One pass is fclu_round_bnb_wide.  With more, a pass's search leaves the capped tasks' frames and open counts, k_bw_split scans them and
+// the host reads the per-problem counts back -- the one read-back of a pass -- plans the next pass from them (the problems of this pass
+// in their order, a task an open child) and k_bw_emit writes the records in front of its search.
 int bnb_wide_device(fclu_ctx *c, const Knobs &k, const int32_t *g2, const int64_t *ub2, double lo_f, double hi_f, int32_t offset, int32_t min_cols,
-                    int32_t max_cols, int32_t depth, int32_t node_cap, int64_t max_nodes) {
+                    int32_t max_cols, int32_t depth, int32_t node_cap, int64_t max_nodes, int32_t passes) {
     c->have_wide = false;
     c->wprep_ms = c->wsearch_ms = c->wlongest_ms = 0.f;
-    RC_TRY(bnb_preconditions(c, "fclu_round_bnb_wide", kBwMaxCols, g2, ub2, lo_f, hi_f, offset, min_cols, max_cols, depth, node_cap, max_nodes));
+    c->w_pass_stats.clear();
+    const char *name = passes < 0 ? "fclu_round_bnb_wide" : "fclu_round_bnb_wide_passes";
+    if (passes < 0) passes = 1;
+    else if (passes < 1 || passes > kBwMaxPasses) return fail(c, FCLU_ERR_ARG, "%s: passes is %d, it must lie in [1, %d]", name, (int)passes, kBwMaxPasses);
+    RC_TRY(bnb_preconditions(c, name, kBwMaxCols, g2, ub2, lo_f, hi_f, offset, min_cols, max_cols, depth, node_cap, max_nodes));
     const fclu_rounds &o = c->rounds;
     const int P = o.n_prob;
     const i64 C = o.n_cols, G = o.n_gap_rows;
@@ -3534,6 +3706,7 @@ int bnb_wide_device(fclu_ctx *c, const Knobs &k, const int32_t *g2, const int64_
     auto &H = c->wh;
     auto &RD = c->rd;
     hipStream_t s = c->stream;
+    const bool more = passes > 1;
     // ---- which problems are taken: ascending (R, problem) while the running total of 2^D x node_cap stays inside the budget
     std::vector<BwProb> probs((size_t)P);                    // (tab0 = conf0 = 0 until a problem is taken)
     std::vector<std::pair<int, int>> order;
@@ -3543,15 +3716,16 @@ int bnb_wide_device(fclu_ctx *c, const Knobs &k, const int32_t *g2, const int64_
     for (BwProb &q : probs) { q.W = bw_words(q.b.n); q.EW = bw_ewords(q.b.n_inf); }
     const i64 launch_tasks = k.bnb_wide_slice ? k.bnb_wide_slice : std::max<i64>(kBwLaunchNodes / node_cap, 1);
     const i64 wg_tasks = std::min<i64>(kBwWaves, launch_tasks);
-    const LaunchPlan plan = plan_launches(order, (size_t)P, [&](int p) { return 1ll << std::min<int>(probs[(size_t)p].b.n, depth); }, node_cap, max_nodes, wg_tasks,
-                                          launch_tasks, [&](int p) { return (size_t)bw_lds_bytes(probs[(size_t)p].b.n, probs[(size_t)p].b.n_inf); });
+    const auto lds_of = [&](int p) { return (size_t)bw_lds_bytes(probs[(size_t)p].b.n, probs[(size_t)p].b.n_inf); };
+    LaunchPlan plan = plan_launches(order, (size_t)P, [&](int p) { return 1ll << std::min<int>(probs[(size_t)p].b.n, depth); }, node_cap, max_nodes, wg_tasks,
+                                    launch_tasks, lds_of);
     i64 n_tab = 0, n_conf = 0;
     for (const int p : plan.list) {                          // the taken problems' tables and conflict rows, end to end
         BwProb &q = probs[(size_t)p];
         q.tab0 = n_tab; q.conf0 = n_conf;
         n_tab += bw_table_words(q.b.n, q.b.n_inf); n_conf += (i64)q.b.n * q.W;
     }
-    RC_TRY(launches_ready(c, "fclu_round_bnb_wide", "tasks", "max_nodes", plan, kBwMaxLaunches));
+    RC_TRY(launches_ready(c, name, "tasks", "max_nodes", plan, kBwMaxLaunches));
     const size_t nL = plan.list.size(), nP = (size_t)P;
     RC_TRY(upload_plan(c, D, D.probs, probs, plan, g2));
     RC_TRY(upload_search(c, D, D.out, H, ub2, plan));
@@ -3560,6 +3734,42 @@ int bnb_wide_device(fclu_ctx *c, const Knobs &k, const int32_t *g2, const int64_
     if (nP) HIP_TRY(c, hipMemsetAsync(D.out_mask.p, 0, D.out_mask.bytes(nP * kBwMaxWords), s));
     if (n_tab) HIP_TRY(c, hipMemsetAsync(D.tab.p, 0, D.tab.bytes((size_t)n_tab), s));
     if (n_conf) HIP_TRY(c, hipMemsetAsync(D.conf.p, 0, D.conf.bytes((size_t)n_conf), s));
+    // what a pass leaves for the next: the frames' places (a problem's tasks end to end, 3 W + 1 words each) and the per-task counts
+    std::vector<i64> frame_off((size_t)P, 0), rec_off((size_t)P, -1);
+    const auto size_pass = [&](const LaunchPlan &pl, fclu_ctx::BwPassBufs &B) -> int {
+        i64 n_frame = 0;
+        for (const int p : pl.list) { frame_off[(size_t)p] = n_frame; n_frame += pl.n_units[(size_t)p] * bw_frame_words(probs[(size_t)p].W); }
+        const size_t nT = (size_t)pl.total_units;
+        HIP_TRY(c, B.frames.grow((size_t)n_frame)); HIP_TRY(c, B.frame_off.grow(nP)); HIP_TRY(c, B.open_cnt.grow(nT)); HIP_TRY(c, B.open_off.grow(nT));
+        HIP_TRY(c, D.n_open.grow(nP)); HIP_TRY(c, D.bound.grow(nP)); HIP_TRY(c, c->w_n_open.grow(nP));
+        if (nP) HIP_TRY(c, hipMemcpyAsync(B.frame_off.p, frame_off.data(), B.frame_off.bytes(nP), hipMemcpyHostToDevice, s));
+        return FCLU_OK;
+    };
+    // behind a pass's reduction: the scan of the open counts and the per-problem counts' way to the host
+    const auto split_pass = [&](const LaunchPlan &pl, fclu_ctx::BwPassBufs &B, const i64 *task_off) -> int {
+        if (nP) HIP_TRY(c, hipMemsetAsync(D.n_open.p, 0, D.n_open.bytes(nP), s));       // (a problem outside this pass has no open child)
+        if (!pl.list.empty())
+            hipLaunchKernelGGL(k_bw_split, dim3((unsigned)pl.list.size()), dim3(256), 0, s, D.list.p, task_off, D.n_tasks.p, B.open_cnt.p, B.open_off.p, D.n_open.p);
+        if (nP) HIP_TRY(c, hipMemcpyAsync(c->w_n_open.p, D.n_open.p, D.n_open.bytes(nP), hipMemcpyDeviceToHost, s));
+        return FCLU_OK;
+    };
+    const auto download = [&]() -> int {
+        HIP_TRY(c, hipEventRecord(c->wev[2], s));
+        if (nP) {
+            HIP_TRY(c, hipMemcpyAsync(H.out.p, D.out.p, D.out.bytes(nP), hipMemcpyDeviceToHost, s));
+            HIP_TRY(c, hipMemcpyAsync(H.mask.p, D.out_mask.p, D.out_mask.bytes(nP * kBwMaxWords), hipMemcpyDeviceToHost, s));
+        }
+        return FCLU_OK;
+    };
+    // a pass's row of fclu_round_bnb_wide_pass_stats, from the running results before and behind it
+    std::vector<i64> nodes_before((size_t)P, 0);
+    const auto pass_row = [&](const LaunchPlan &pl) {
+        i64 nodes = 0, capped = 0;
+        for (const int p : pl.list) { nodes += H.out.p[p].nodes - nodes_before[(size_t)p]; capped += H.out.p[p].capped; nodes_before[(size_t)p] = H.out.p[p].nodes; }
+        for (const i64 x : {pl.total_units, nodes, capped, (i64)pl.n_launch(), (i64)pl.list.size()}) c->w_pass_stats.push_back(x);
+    };
+    if (more) RC_TRY(size_pass(plan, D.ps[1]));
+    const BwSplitOut none = {nullptr, nullptr, nullptr};
     RC_TRY(run_round_call(c, c->wev, plan.n_launch(), c->wprep_ms, c->wsearch_ms, c->wlongest_ms, [&] {
         if (nL)
             hipLaunchKernelGGL(k_bw_prep, dim3((unsigned)nL), dim3(256), 0, s, D.list.p, D.probs.p, RD.inf_seg.p, RD.sup_off.p, (i64)o.n_inf, RD.sup_cols.p, (i64)o.n_sup,
@@ -3567,17 +3777,70 @@ int bnb_wide_device(fclu_ctx *c, const Knobs &k, const int32_t *g2, const int64_
     }, [&](size_t l) {
         hipLaunchKernelGGL(k_bw_search, dim3((unsigned)(plan.launch_first[l + 1] - plan.launch_first[l])), dim3(kBwThreads), plan.launch_lds[l], s,
                            D.items.p + plan.launch_first[l], D.probs.p, D.tab.p, D.conf.p, D.g2.p, D.ub2.p, RD.rows.p, G, RD.grp_seg_off.p, (i64)o.n_grp, (i64)o.n_grp_seg,
-                           D.gk.p, RD.grp_len.p, lo_f, hi_f, (int)offset, (int)depth, (int)node_cap, D.task_off.p, D.tasks.p);
+                           D.gk.p, RD.grp_len.p, lo_f, hi_f, (int)offset, (int)depth, (int)node_cap, D.task_off.p, D.tasks.p,
+                           more ? BwSplitOut{D.ps[1].frames.p, D.ps[1].frame_off.p, D.ps[1].open_cnt.p} : none);
     }, [&]() -> int {
         if (nL) hipLaunchKernelGGL(k_bw_reduce, dim3((unsigned)nL), dim3(256), 0, s, D.list.p, D.probs.p, D.task_off.p, D.n_tasks.p, D.tasks.p, D.out.p, D.out_mask.p);
-        HIP_TRY(c, hipEventRecord(c->wev[2], s));
-        if (nP) {
-            HIP_TRY(c, hipMemcpyAsync(H.out.p, D.out.p, D.out.bytes(nP), hipMemcpyDeviceToHost, s));
-            HIP_TRY(c, hipMemcpyAsync(H.mask.p, D.out_mask.p, D.out_mask.bytes(nP * kBwMaxWords), hipMemcpyDeviceToHost, s));
-        }
-        return FCLU_OK;
+        if (more && nL) hipLaunchKernelGGL(k_bw_bound, dim3((unsigned)((nL + 255) / 256)), dim3(256), 0, s, D.list.p, (int)nL, D.ub2.p, D.out.p, D.bound.p);
+        if (more) RC_TRY(split_pass(plan, D.ps[1], D.task_off.p));
+        return download();
     }));
-    fold_search(P, plan, H, ub2, c->wide);
+    pass_row(plan);
+    LaunchPlan first;                                        // (the results cover the first pass's problems: fold_search's list)
+    first.list = plan.list;
+    i64 n_launches = (i64)plan.n_launch();
+    // ---- the later passes
+    const int4 *prev_items = D.items.p;
+    const i64 *prev_task_off = D.task_off.p;
+    for (int pass = 2; pass <= passes; ++pass) {
+        // the problems of the pass before, in their order, that have open children and not more than a pass may hold
+        std::vector<std::pair<int, int>> next;
+        for (const int p : plan.list) {
+            const i64 n = c->w_n_open.p[p];
+            if (n < 0 || n > plan.n_units[(size_t)p] * (i64)(kBwMaxCols + 1)) return fail(c, FCLU_ERR_HIP, "%s: problem %d: %lld open children of %lld tasks", name, p, n, plan.n_units[(size_t)p]);
+            if (n > 0 && n <= kBwMaxPassTasks) next.emplace_back(probs[(size_t)p].b.n, p);
+        }
+        const i64 wg_recs = std::min<i64>(k.bnb_wide_item, launch_tasks);
+        LaunchPlan pl = plan_launches(next, (size_t)P, [&](int p) { return (long long)c->w_n_open.p[p]; }, node_cap, max_nodes, wg_recs, launch_tasks, lds_of);
+        if (pl.list.empty()) break;                          // nothing is open, or the first open problem is beyond the budget: no launch
+        RC_TRY(launches_ready(c, name, "tasks", "max_nodes", pl, kBwMaxLaunches));
+        fclu_ctx::BwPassBufs &B = D.ps[pass & 1], &Bp = D.ps[(pass - 1) & 1];
+        const size_t nLk = pl.list.size(), nI = pl.items.size();
+        i64 n_rec = 0;
+        std::fill(rec_off.begin(), rec_off.end(), -1);
+        for (const int p : pl.list) { rec_off[(size_t)p] = n_rec; n_rec += pl.n_units[(size_t)p] * bw_record_words(probs[(size_t)p].W); }
+        const size_t prev_n_items = plan.items.size();
+        HIP_TRY(c, B.items.grow(nI)); HIP_TRY(c, B.task_off.grow(nP)); HIP_TRY(c, D.rec.grow((size_t)n_rec)); HIP_TRY(c, D.rec_off.grow(nP));
+        HIP_TRY(c, D.tasks.grow((size_t)pl.total_units));
+        HIP_TRY(c, hipMemcpyAsync(D.list.p, pl.list.data(), D.list.bytes(nLk), hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipMemcpyAsync(B.items.p, pl.items.data(), B.items.bytes(nI), hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipMemcpyAsync(B.task_off.p, pl.unit_off.data(), B.task_off.bytes(nP), hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipMemcpyAsync(D.n_tasks.p, pl.n_units.data(), D.n_tasks.bytes(nP), hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipMemcpyAsync(D.rec_off.p, rec_off.data(), D.rec_off.bytes(nP), hipMemcpyHostToDevice, s));
+        RC_TRY(size_pass(pl, B));
+        float prep_ms = 0.f, search_ms = 0.f;
+        RC_TRY(run_round_call(c, c->wev, pl.n_launch(), prep_ms, search_ms, c->wlongest_ms, [&] {
+            hipLaunchKernelGGL(k_bw_emit, dim3((unsigned)prev_n_items), dim3(kBwThreads), 0, s, prev_items, D.probs.p, D.conf.p, prev_task_off, Bp.frames.p, Bp.frame_off.p,
+                               Bp.open_cnt.p, Bp.open_off.p, D.n_open.p, D.rec.p, D.rec_off.p);
+        }, [&](size_t l) {
+            hipLaunchKernelGGL(k_bw_search_from, dim3((unsigned)(pl.launch_first[l + 1] - pl.launch_first[l])), dim3(kBwThreads), pl.launch_lds[l], s,
+                               B.items.p + pl.launch_first[l], D.probs.p, D.tab.p, D.conf.p, D.g2.p, D.bound.p, RD.rows.p, G, RD.grp_seg_off.p, (i64)o.n_grp,
+                               (i64)o.n_grp_seg, D.gk.p, RD.grp_len.p, lo_f, hi_f, (int)offset, (int)depth, (int)node_cap, B.task_off.p, D.tasks.p, D.rec.p, D.rec_off.p,
+                               BwSplitOut{B.frames.p, B.frame_off.p, B.open_cnt.p});
+        }, [&]() -> int {
+            hipLaunchKernelGGL(k_bw_fold, dim3((unsigned)nLk), dim3(256), 0, s, D.list.p, D.probs.p, B.task_off.p, D.n_tasks.p, D.tasks.p, D.ub2.p, D.out.p, D.out_mask.p,
+                               D.bound.p);
+            RC_TRY(split_pass(pl, B, B.task_off.p));
+            return download();
+        }));
+        c->wprep_ms += prep_ms; c->wsearch_ms += search_ms;
+        pass_row(pl);
+        n_launches += (i64)pl.n_launch();
+        prev_items = B.items.p; prev_task_off = B.task_off.p;
+        plan = std::move(pl);
+    }
+    fold_search(P, first, H, ub2, c->wide);
+    c->wide.n_launches = n_launches;
     c->have_wide = true;
     return FCLU_OK;
 }
@@ -3707,7 +3970,8 @@ int fclu_create(int device, fclu_ctx **out) {
         {reinterpret_cast<const void *>(k_inc_start<false>), (int)inc_lds_bytes(0, kMaxWords, (kIncMaxCols + 31) / 32, false)},
         {reinterpret_cast<const void *>(k_exact_search), kExactLdsBytes},
         {reinterpret_cast<const void *>(k_bnb_search), kBnbLdsBytes},
-        {reinterpret_cast<const void *>(k_bw_search), kBwLdsBytes}};
+        {reinterpret_cast<const void *>(k_bw_search), kBwLdsBytes},
+        {reinterpret_cast<const void *>(k_bw_search_from), kBwLdsBytes}};
     for (const auto &d : dyn) if (e == hipSuccess) e = hipFuncSetAttribute(d.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, d.lds);
     if (e != hipSuccess) {
         fail(nullptr, FCLU_ERR_HIP, "context creation failed: %s", hipGetErrorString(e));
@@ -3934,7 +4198,20 @@ int fclu_round_bnb_timing(fclu_ctx *c, float *prep_ms, float *search_ms, float *
 
 int fclu_round_bnb_wide(fclu_ctx *c, const int32_t *g2, const int64_t *ub2, double lo_f, double hi_f, int32_t offset, int32_t min_cols, int32_t max_cols,
                         int32_t depth, int32_t node_cap, int64_t max_nodes) {
-    return c ? bnb_wide_device(c, read_knobs(), g2, ub2, lo_f, hi_f, offset, min_cols, max_cols, depth, node_cap, max_nodes) : FCLU_ERR_ARG;
+    return c ? bnb_wide_device(c, read_knobs(), g2, ub2, lo_f, hi_f, offset, min_cols, max_cols, depth, node_cap, max_nodes, -1) : FCLU_ERR_ARG;
+}
+
+int fclu_round_bnb_wide_passes(fclu_ctx *c, const int32_t *g2, const int64_t *ub2, double lo_f, double hi_f, int32_t offset, int32_t min_cols, int32_t max_cols,
+                               int32_t depth, int32_t node_cap, int64_t max_nodes, int32_t passes) {
+    return c ? bnb_wide_device(c, read_knobs(), g2, ub2, lo_f, hi_f, offset, min_cols, max_cols, depth, node_cap, max_nodes, passes < 0 ? 0 : passes) : FCLU_ERR_ARG;
+}
+
+int fclu_round_bnb_wide_pass_stats(fclu_ctx *c, int64_t *out, int32_t n) {
+    if (!c || n < 0 || (n > 0 && !out)) return FCLU_ERR_ARG;
+    if (!c->have_wide || !c->have_rounds)
+        return fail(c, FCLU_ERR_ARG, "fclu_round_bnb_wide_pass_stats: no result (the last fclu_round_bnb_wide call failed, none was made, or a later call ended it)");
+    for (size_t x = 0; x < 5 * (size_t)n; ++x) out[x] = x < c->w_pass_stats.size() ? c->w_pass_stats[x] : 0;
+    return FCLU_OK;
 }
 
 int fclu_round_bnb_wide_results(fclu_ctx *c, fclu_bnb_wide *out) { return c && out ? round_call_results(c, c->have_wide, c->wide, out, "fclu_round_bnb_wide") : FCLU_ERR_ARG; }

@@ -445,8 +445,33 @@ typedef struct fclu_bnb_wide {
  * next call.  The round's, the incumbents', the exact call's and fclu_round_bnb's results stay valid behind it. */
 int fclu_round_bnb_wide_results(fclu_ctx *c, fclu_bnb_wide *out);
 
-/* Kernel time of the last fclu_round_bnb_wide() from HIP events (ms): the tables; all search launches; the longest of them. */
+/* Kernel time of the last fclu_round_bnb_wide() or fclu_round_bnb_wide_passes() from HIP events (ms): the tables and the later passes'
+ * records; all search launches of all passes; the longest of them. */
 int fclu_round_bnb_wide_timing(fclu_ctx *c, float *prep_ms, float *search_ms, float *longest_launch_ms);
+
+/* ---- the same search continued: a capped task's open subtrees become the tasks of a further pass ----
+ * fclu_round_bnb_wide() with up to `passes` passes (the definition is freddie_amd/cluster_solve.py exact_bnb_wide(passes=...), which the
+ * device reproduces exactly, node counts included).  Pass 1 is fclu_round_bnb_wide's search.  A task that stops at node_cap leaves its
+ * stack; every level of it whose exclude child was not tried, and the child it stopped in front of, is an open subtree.  Pass k + 1 runs
+ * the open subtrees of pass k's capped tasks as tasks of their own, node_cap nodes each at the most, every one bounded by the smaller of
+ * ub2 and the best cost2 any task of the problem found in the passes before.  Before a pass the host reads the per-problem numbers of
+ * open subtrees back (the one read-back of a pass) and takes the problems of the pass before in their order -- ascending (columns, problem
+ * index) -- while the running total of tasks * node_cap stays <= max_nodes; the first problem that does not fit ends the taking: it and
+ * every problem behind it are not continued in this or a later pass.  A problem whose next pass would hold more than 2^16 tasks is not
+ * continued either.  The call ends when no problem is continued or after `passes` passes.  A problem's result is the smallest (cost2,
+ * set) over all its tasks of all passes, its nodes are summed over the passes and `capped` counts the tasks still open, that is the capped
+ * tasks of the last pass it took part in; the status follows fclu_bnb's rule with those.  Results: fclu_round_bnb_wide_results(), whose
+ * layout is unchanged; n_launches counts the search launches of all passes.  passes == 1 equals fclu_round_bnb_wide() in every result
+ * word.  FCLU_ERR_ARG: fclu_round_bnb_wide's cases, and passes outside [1, 16].  FCLU_BNB_WIDE_SLICE applies to every pass. */
+int fclu_round_bnb_wide_passes(fclu_ctx *c, const int32_t *g2, const int64_t *ub2, double lo_f, double hi_f, int32_t offset, int32_t min_cols, int32_t max_cols,
+                               int32_t depth, int32_t node_cap, int64_t max_nodes, int32_t passes);
+
+#define FCLU_BNB_WIDE_PASS_STATS 5
+
+/* The passes of the last successful fclu_round_bnb_wide() / fclu_round_bnb_wide_passes(): out has room for n rows of
+ * FCLU_BNB_WIDE_PASS_STATS int64 -- a pass's tasks, their nodes, the capped ones, the search launches, the problems that took part --
+ * row k for pass k + 1; the rows of passes that did not run are zero (a pass that ran has at least one task). */
+int fclu_round_bnb_wide_pass_stats(fclu_ctx *c, int64_t *out, int32_t n);
 
 /* ---- the read-out of a round: run_ilp()'s isoform (:601-635) of every problem with an accepted column set, on the device ----
  * The batch is that of the context's last successful fclu_round_models() / fclu_round_models_resident().  Problem p's accepted columns are

@@ -16,7 +16,7 @@ synthetic preprocessed tints through include/freddie_cluster.h.
     python tools/cluster_bench.py --exact [--max-ilp K] [--exact-small N] [--exact-masks M] [--steps K] [--host-sample N] [--solve-budget S] [--out FILE]
                        (per problem size N = 8, 12, 16, 20, 24: Context.round_exact on every partition's first N reps -- the call, the kernels,
                         the longest launch, masks per second -- against HiGHS on a sample of the same problems; profiles/cluster_exact.txt)
-    python tools/cluster_bench.py --wide [--sizes 128,256,1000] [--tints 40] [--wide-node-caps A,B] [--loop-runs R] [--steps K] [--host-sample N] [--out FILE] [--append]
+    python tools/cluster_bench.py --wide [--sizes 128,256,1000] [--tints 40] [--wide-node-caps A,B] [--wide-passes A,B] [--loop-runs R] [--steps K] [--host-sample N] [--out FILE] [--append]
                        (per maximum_ilp_size: Context.round_bnb_wide on the first round's problems of 65 .. min(N, 1024) columns by column class --
                         taken, proven, unproven, nodes, ms a call, the longest launch --, HiGHS on a sample of the same problems, and optionally
                         the whole loop with and without --exact-wide; profiles/cluster_bnb_wide.txt)
@@ -789,7 +789,7 @@ WIDE_CLASSES = ((65, 128), (129, 256), (257, 512), (513, 1024))
 
 
 def run_wide(workload="many", steps=3, sizes=(128, 256, 1000), n_tints=40, max_nodes=None, depth=None, node_caps=None, host_sample=32, threads=16,
-             loop_runs=0, exact_cols=24, bnb_cols=64):
+             loop_runs=0, exact_cols=24, bnb_cols=64, passes_list=(1,)):
     """Per N of `sizes` the workload's first n_tints files, written without gaps, are staged with maximum_ilp_size = N and the FIRST round
     of every partition is the batch:
       device   Context.round_models, Context.round_incumbents (the bounds) and Context.round_bnb_wide with 65 .. min(N, 1024) columns, once
@@ -799,7 +799,10 @@ def run_wide(workload="many", steps=3, sizes=(128, 256, 1000), n_tints=40, max_n
       solver   HiGHS (cluster_solve.solve_round) with `threads` workers on `host_sample` of the taken problems, evenly spread: wall time of
                the pool, and the share of them the search proved at the default cap;
       loop     loop_runs > 0: the whole cluster_tints() loop under exact_cols / bnb_cols with and without wide_cols = min(N, 1024), in turn,
-               loop_runs times each: seconds, solver jobs, and whether tints and logs are the same."""
+               loop_runs times each: seconds, solver jobs, and whether tints and logs are the same.
+      passes   passes_list (--wide-passes A,B,...): every node cap is run once per number of passes (Context.round_bnb_wide(passes=...)),
+               with the rows of round_bnb_wide_pass_stats() -- a pass's tasks, nodes, capped tasks, launches, problems -- and the loop
+               once per number of passes (wide_passes) beside the loop without wide_cols."""
     import hashlib
     import tempfile
     from multiprocessing import Pool
@@ -820,13 +823,14 @@ def run_wide(workload="many", steps=3, sizes=(128, 256, 1000), n_tints=40, max_n
             costs = [cluster.garbage_costs(t, "constant") for t in tints]
             problems = [(t, q, list(rids)) for t, tint in enumerate(tints) for q, (rids, _) in enumerate(tint["partitions"])]
             row = {"N": N, "problems": len(problems), "caps": []}
-            for node_cap in (node_caps or (cluster_solve.bnb_wide_node_cap(top),)):
+            for node_cap, passes in ((c, k) for c in (node_caps or (cluster_solve.bnb_wide_node_cap(top),)) for k in passes_list):
                 def device(ps):
                     arr = ctx.round_models([part0[t] + q for t, q, _ in ps], [rem for _, _, rem in ps])
                     garbage = [costs[t][i] for t, _, rem in ps for i in rem]
                     inc = ctx.round_incumbents(garbage, settings["epsilon"], settings["offset"])
                     t1 = time.perf_counter()
-                    got = ctx.round_bnb_wide(garbage, inc["cost2"], settings["epsilon"], settings["offset"], 65, top, max_nodes, depth, node_cap)
+                    got = ctx.round_bnb_wide(garbage, inc["cost2"], settings["epsilon"], settings["offset"], 65, top, max_nodes, depth, node_cap,
+                                             **({"passes": passes} if passes > 1 else {}))
                     return arr, inc, got, time.perf_counter() - t1
 
                 device(problems)                                                  # warm-up
@@ -845,10 +849,11 @@ def run_wide(workload="many", steps=3, sizes=(128, 256, 1000), n_tints=40, max_n
                                                    "proven": int((sel & ((status == 0) | (status == 1))).sum()), "unproven": int((sel & (status == 2)).sum()),
                                                    "nodes": int(got["nodes"][sel].sum()), "capped_tasks": int(got["capped"][sel].sum()),
                                                    "informative_segments_range": [int(n_inf[sel].min()), int(n_inf[sel].max())] if sel.any() else None}
-                row["caps"].append({"node_cap": node_cap, "depth": depth, "taken": got["n_taken"], "launches": got["n_launches"], "nodes": got["nodes_total"],
+                row["caps"].append({"node_cap": node_cap, "depth": depth, "passes": passes, "pass_rows": ctx.round_bnb_wide_pass_stats(),
+                                    "proven": int(((status == 0) | (status == 1)).sum()), "taken": got["n_taken"], "launches": got["n_launches"], "nodes": got["nodes_total"],
                                     "classes": classes, "round_bnb_wide_call_ms": med(call_s) * 1e3, "call_spread_ms": [min(call_s) * 1e3, max(call_s) * 1e3],
                                     "kernel_ms": {k: med([x[k] for x in kern]) for k in kern[0]}})
-                print("N = %d cap %d: %s" % (N, node_cap, json.dumps(row["caps"][-1])), file=sys.stderr, flush=True)
+                print("N = %d cap %d passes %d: %s" % (N, node_cap, passes, json.dumps(row["caps"][-1])), file=sys.stderr, flush=True)
             taken = np.flatnonzero(status != -2)
             pick = taken[np.linspace(0, len(taken) - 1, min(host_sample, len(taken))).astype(int)].tolist() if len(taken) and host_sample else []
             if pick:
@@ -868,8 +873,8 @@ def run_wide(workload="many", steps=3, sizes=(128, 256, 1000), n_tints=40, max_n
             del tints
             loops, records = [], {}
             for run_no in range(loop_runs):
-                for wide_cols in (0, top):
-                    ls = cluster.ilp_settings(max_ilp=N, exact_cols=exact_cols, bnb_cols=bnb_cols, wide_cols=wide_cols)
+                for wide_cols, passes in [(0, 1)] + [(top, k) for k in passes_list]:
+                    ls = cluster.ilp_settings(max_ilp=N, exact_cols=exact_cols, bnb_cols=bnb_cols, wide_cols=wide_cols, wide_passes=passes)
                     tints, part0, _ = cluster.stage_files(paths, ls, ctx, threads)
                     jobs_n = [0]
 
@@ -885,14 +890,14 @@ def run_wide(workload="many", steps=3, sizes=(128, 256, 1000), n_tints=40, max_n
                     logs = cluster.cluster_tints(tints, part0, ctx, ls, pool=CountingPool(), on_round=keep)
                     t1 = time.perf_counter()
                     digest = hashlib.sha256(repr([(t["id"], t["isoforms"], t["garbage_rids"]) for t in tints]).encode() + repr(logs).encode()).hexdigest()[:16]
-                    loops.append({"wide_cols": wide_cols, "run": run_no, "loop_s": t1 - t0, "solver_jobs": jobs_n[0], "digest": digest,
+                    loops.append({"wide_cols": wide_cols, "wide_passes": passes, "run": run_no, "loop_s": t1 - t0, "solver_jobs": jobs_n[0], "digest": digest,
                                   "rounds": len(record), "statuses": {k: sum(1 for v in record.values() if v[0] == k) for k in set(v[0] for v in record.values())}})
-                    records[(run_no, wide_cols)] = record
+                    records[(run_no, wide_cols, passes)] = record
                     print("N = %d loop: %s" % (N, json.dumps(loops[-1])), file=sys.stderr, flush=True)
                     del tints
             if loops:
                 row["loop"] = {"runs": loops, "same_tints_and_logs": len(set(r["digest"] for r in loops)) == 1,
-                               "round_for_round": [_compare_rounds(records[(k, 0)], records[(k, top)]) for k in range(loop_runs)]}
+                               "round_for_round": [_compare_rounds(records[(k, 0, 1)], records[(k, top, passes_list[-1])]) for k in range(loop_runs)]}
             rows.append(row)
     ctx.close()
     pool.close()
@@ -1055,6 +1060,8 @@ def main():
     ap.add_argument("--wide", action="store_true", help="measure Context.round_bnb_wide under maximum_ilp_size 128, 256 and 1000 (--sizes) on the first --tints files "
                                                          "(default 40) against HiGHS on a sample of the same problems (profiles/cluster_bnb_wide.txt)")
     ap.add_argument("--wide-node-caps", default=None, help="--wide: node caps to run, comma separated (default: cluster_solve.bnb_wide_node_cap(N))")
+    ap.add_argument("--wide-passes", default=None, help="--wide: numbers of passes to run every node cap (and the loop) with, comma separated (default: 1; "
+                                                        "profiles/cluster_bnb_wide_passes.txt)")
     ap.add_argument("--loop-runs", type=int, default=0, help="--wide: runs of the whole loop with and without --exact-wide (default: none)")
     args = ap.parse_args()
     sample = lambda default: default if args.host_sample is None else args.host_sample
@@ -1062,11 +1069,14 @@ def main():
         args.sizes = args.sizes or "128,256,1000"
         sizes = tuple(int(v) for v in args.sizes.split(","))
         caps = tuple(int(v) for v in args.wide_node_caps.split(",")) if args.wide_node_caps else None
+        passes = tuple(int(v) for v in args.wide_passes.split(",")) if args.wide_passes else (1,)
         res = run_wide(args.workload, args.steps, sizes, args.tints or 40, node_caps=caps, host_sample=sample(32),
-                       threads=args.threads, loop_runs=args.loop_runs)
-        with open(args.out or os.path.join(ROOT, "profiles", "cluster_bnb_wide.txt"), "a" if args.append else "w") as f:
-            f.write("tools/cluster_bench.py --wide --workload %s --steps %d --sizes %s --wide-node-caps %s --loop-runs %d  (libfreddie_cluster.so source hash %s)\n" %
-                    (args.workload, args.steps, ",".join(map(str, sizes)), args.wide_node_caps, args.loop_runs, res["source_hash"]))
+                       threads=args.threads, loop_runs=args.loop_runs, passes_list=passes)
+        default_out = "cluster_bnb_wide_passes.txt" if args.wide_passes else "cluster_bnb_wide.txt"
+        with open(args.out or os.path.join(ROOT, "profiles", default_out), "a" if args.append else "w") as f:
+            f.write("tools/cluster_bench.py --wide --workload %s --steps %d --sizes %s --wide-node-caps %s%s --loop-runs %d  (libfreddie_cluster.so source hash %s)\n" %
+                    (args.workload, args.steps, ",".join(map(str, sizes)), args.wide_node_caps, " --wide-passes %s" % args.wide_passes if args.wide_passes else "",
+                     args.loop_runs, res["source_hash"]))
             f.write(json.dumps(res, indent=1) + "\n")
         print(json.dumps(res))
     elif args.device_rounds:
