@@ -71,7 +71,7 @@ EXPORTS = ["fseg_annotate", "fseg_annotation", "fseg_abi_version", "fseg_source_
 # the words of the `paths` tap (include/freddie_seg.h, FSEG_TAP_PATHS)
 PATHS = ("small_batch", "tiny_on", "wave_on", "fuse_on", "key32", "thr_part", "label_packed", "n_solve0", "n_solve1", "n_solve2",
          "n_wide0", "n_wide1", "n_wide2", "n_tiny", "n_work", "dpw", "wide16", "known", "solve8", "tiny_kernel", "score", "arena_dp",
-         "plan", "n_arena_prob", "n_score0", "n_score1", "n_score2", "hist16", "iv_threads", "smooth_r", "yraw16", "lane_sort")
+         "plan", "n_arena_prob", "n_score0", "n_score1", "n_score2", "hist16", "iv_threads", "smooth_r", "yraw16", "lane_sort", "iv_cand")
 
 TAPS = dict(pos_off=(1, np.int64), y_raw=(2, np.int32), y=(3, np.float64), threshold=(4, np.float64),
             cand_off=(5, np.int64), cand_y=(6, np.int32), fixed=(7, np.uint8), chosen=(8, np.uint8),

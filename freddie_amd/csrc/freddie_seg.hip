@@ -123,6 +123,7 @@ struct fseg_ctx {
     i64 label_grid = 0;        // FSEG_LABEL_GRID=<n> (tests): the label launch takes at most n workgroups, so that one walks several units; 0: 65 536
     int yraw16 = -1;           // FSEG_YRAW16=0 / 1: the histogram in device memory int32 always / uint16 wherever S1 runs packed; -1: the same as 1
     bool yraw_narrow = false;  // the resident batch's d_y_raw holds uint16 (hist_packed and the switch): S1's output, S2's and S6's input
+    int iv_cand = -1;          // FSEG_IV_CAND=0 / 1: S4 and S6 by intervals (k_fix, k_segments) always / by candidates (k_fix_cand, k_segments_cand) wherever iv_threads is 64; -1: from kIvCandFrom intervals on
     i64 max_part_lanes = 0;    // reads of the batch's largest partition (what bounds a DP sum: 32-bit keys below 2^18)
     int n_tiles = 0;
     bool expanded = false;
@@ -305,7 +306,7 @@ struct fseg_ctx {
     enum { PATH_SMALL_BATCH, PATH_TINY_ON, PATH_WAVE_ON, PATH_FUSE_ON, PATH_KEY32, PATH_THR_PART, PATH_LABEL_PACKED, PATH_N_SOLVE,
            PATH_N_WIDE = PATH_N_SOLVE + 3, PATH_N_TINY = PATH_N_WIDE + 3, PATH_N_WORK, PATH_DPW, PATH_WIDE16, PATH_KNOWN, PATH_SOLVE8,
            PATH_TINY_KERNEL, PATH_SCORE, PATH_ARENA_DP, PATH_PLAN, PATH_N_ARENA_PROB, PATH_N_SCORE, PATH_HIST16 = PATH_N_SCORE + 3, PATH_IV_THREADS,
-           PATH_SMOOTH_R, PATH_YRAW16, PATH_LANE_SORT, PATH_WORDS };
+           PATH_SMOOTH_R, PATH_YRAW16, PATH_LANE_SORT, PATH_IV_CAND, PATH_WORDS };
     int paths[PATH_WORDS] = {};
     // fseg_annotate: the uploaded reads (one allocation, mirrored by a pinned image), per-read work arrays, the emitted lists, and
     // the pinned buffers fseg_annotation() points into (own allocations: nothing of a run or of fseg_results* touches them)
@@ -629,6 +630,10 @@ struct Run {
     int *gsum = scan_single ? nullptr : c->d_gsum.p;
     i64 avg_len = c->NPOS / (c->K > 0 ? c->K : 1);        // positions per interval
     int iv_threads = avg_len > 65536 ? 1024 : (avg_len > 16384 ? 256 : 64);    // the block of k_fix and k_segments
+    // ... or both by candidates (k_fix_cand, k_segments_cand): batches of many short intervals, where a wave per interval walks many
+    // of them with a few lanes at work (seg_common.h: kIvCandFrom; profiles/iv_cand.txt).  One decision for S4 and S6.
+    bool iv_cand = iv_threads == 64 && (c->iv_cand == 1 || (c->iv_cand < 0 && c->K >= kIvCandFrom));
+    int iv_cand_grid = grid_for(c->NPOS / 64 / kIvCandOwn + 1, 1, 4096);       // (the kernels stride over the runs st->n_cand makes)
     int pg = prob_grid(c);
     // few candidates: the emit kernel scans by itself, one launch instead of three (never in a sized run: there the
     // host reads the scan's totals before the emit kernel is launched)
@@ -786,10 +791,15 @@ void launch_dp_waves(const Run &r, hipStream_t q_small, hipStream_t q_mid) {
 template <typename COUNT>
 void launch_refine(const Run &r) {
     fseg_ctx *c = r.c;
-    hipLaunchKernelGGL(k_segments<COUNT>, dim3(grid_for(c->K, 1, 8192)), dim3(r.iv_threads), 0, r.s, c->K, c->d_pos_off.p,
-                       c->d_cand_off.p, c->d_cand_y.p, c->d_y_raw.as<COUNT>(), c->d_blk_pre.p, c->d_tile_tot.p, c->d_iv_tile0.p,
-                       c->d_chosen.p, r.flag_final_bits, c->d_rseg_c.p,
-                       c->d_seg_prev.p, r.st);
+    if (r.iv_cand)
+        hipLaunchKernelGGL(k_segments_cand<COUNT>, dim3(r.iv_cand_grid), dim3(kIvCandThreads), 0, r.s, c->d_pos_off.p,
+                           c->d_cand_off.p, c->d_cand_y.p, c->d_seg_iv.p, c->d_y_raw.as<COUNT>(), c->d_blk_pre.p, c->d_tile_tot.p,
+                           c->d_iv_tile0.p, c->d_chosen.p, r.flag_final_bits, c->d_rseg_c.p, c->d_seg_prev.p, r.st);
+    else
+        hipLaunchKernelGGL(k_segments<COUNT>, dim3(grid_for(c->K, 1, 8192)), dim3(r.iv_threads), 0, r.s, c->K, c->d_pos_off.p,
+                           c->d_cand_off.p, c->d_cand_y.p, c->d_y_raw.as<COUNT>(), c->d_blk_pre.p, c->d_tile_tot.p, c->d_iv_tile0.p,
+                           c->d_chosen.p, r.flag_final_bits, c->d_rseg_c.p,
+                           c->d_seg_prev.p, r.st);
     hipLaunchKernelGGL(k_refine<COUNT>, dim3(2048), dim3(64), 0, r.s, r.st, c->d_seg_iv.p, c->d_rseg_c.p,
                        c->d_seg_prev.p, c->d_cand_y.p, c->d_pos_off.p, c->d_y_raw.as<COUNT>(),
                        c->d_w_refine.p, c->P.radius_refine, c->P.sigma, c->d_g.p, c->d_pk.p,
@@ -866,18 +876,27 @@ void seg_pre1(Run &r) {
     // S3b candidates
     hipLaunchKernelGGL(k_peaks_edges, dim3(grid_for(c->n_tiles, 256, 4096)), dim3(256), 0, s, c->n_tiles, c->d_tile_desc.p,
                        c->d_tile_defer.p, c->d_y.p, r.flag_cand_bits, c->d_part_has2.p, n_part);
-    launch_positions(r, r.flag_cand_bits, 1, &st->n_cand, c->d_cand_off.p, c->d_cand_y.p, nullptr, nullptr);
+    // (every candidate's interval with it: what k_fix_cand, k_prob_range, k_prob_emit, k_segments_cand and k_refine index by)
+    launch_positions(r, r.flag_cand_bits, 1, &st->n_cand, c->d_cand_off.p, c->d_cand_y.p, nullptr, c->d_seg_iv.p);
     r.end(ST_CANDIDATES);
     r.join(0);
     r.early_fork();
     r.begin(ST_FIX);
     // S4
     c->paths[fseg_ctx::PATH_IV_THREADS] = r.iv_threads;              // (k_segments, S6, is launched with the same block)
-    hipLaunchKernelGGL(k_fix, dim3(grid_for(K, 1, 8192)), dim3(r.iv_threads), 0, s, K, c->d_pos_off.p,
-                       c->d_iv_part.p, c->d_cand_off.p, c->d_cand_y.p, c->d_y.p,
-                       c->d_thr.p, c->P.max_problem_size, c->d_fixed0.p,
-                       c->d_added.p, c->d_fixed.p, c->d_chosen.p,
-                       c->d_cand_pn.p, c->d_seg_iv.p, st);
+    c->paths[fseg_ctx::PATH_IV_CAND] = r.iv_cand;
+    if (r.iv_cand)
+        hipLaunchKernelGGL(k_fix_cand, dim3(r.iv_cand_grid), dim3(kIvCandThreads), 0, s, c->d_pos_off.p,
+                           c->d_iv_part.p, c->d_cand_off.p, c->d_cand_y.p, c->d_y.p,
+                           c->d_thr.p, c->P.max_problem_size, c->d_fixed0.p,
+                           c->d_added.p, c->d_fixed.p, c->d_chosen.p,
+                           c->d_cand_pn.p, c->d_seg_iv.p, st);
+    else
+        hipLaunchKernelGGL(k_fix, dim3(grid_for(K, 1, 8192)), dim3(r.iv_threads), 0, s, K, c->d_pos_off.p,
+                           c->d_iv_part.p, c->d_cand_off.p, c->d_cand_y.p, c->d_y.p,
+                           c->d_thr.p, c->P.max_problem_size, c->d_fixed0.p,
+                           c->d_added.p, c->d_fixed.p, c->d_chosen.p,
+                           c->d_cand_pn.p, c->d_seg_iv.p, st);
     // (with the block sums of the problem scan when the scan is a launch of its own: k_prob_scan1 is the rescan's only)
     launch_prob_range(c, r.split, r.prob_bs);
     if (r.prob_bs) launch_prob_scan(c, r.split, r.prob_bs, false);
@@ -934,7 +953,7 @@ constexpr int kScoreCensus[] = {
     fseg_ctx::PATH_SOLVE8, fseg_ctx::PATH_TINY_KERNEL, fseg_ctx::PATH_SCORE, fseg_ctx::PATH_PLAN, fseg_ctx::PATH_N_ARENA_PROB,
     fseg_ctx::PATH_N_SCORE, fseg_ctx::PATH_N_SCORE + 1, fseg_ctx::PATH_N_SCORE + 2};
 constexpr int kOtherCensus[] = {fseg_ctx::PATH_THR_PART, fseg_ctx::PATH_LABEL_PACKED, fseg_ctx::PATH_ARENA_DP, fseg_ctx::PATH_HIST16,
-                                fseg_ctx::PATH_IV_THREADS, fseg_ctx::PATH_SMOOTH_R, fseg_ctx::PATH_YRAW16, fseg_ctx::PATH_LANE_SORT};
+                                fseg_ctx::PATH_IV_THREADS, fseg_ctx::PATH_SMOOTH_R, fseg_ctx::PATH_YRAW16, fseg_ctx::PATH_LANE_SORT, fseg_ctx::PATH_IV_CAND};
 constexpr bool census_covered() {
     int seen[fseg_ctx::PATH_WORDS] = {};
     for (int w : kScoreCensus) ++seen[w];
@@ -1543,6 +1562,7 @@ void read_switches(fseg_ctx *c) {
     env_tri("FSEG_THR_PART", c->thr_part);
     env_tri("FSEG_HIST16", c->hist16);
     env_tri("FSEG_YRAW16", c->yraw16);
+    env_tri("FSEG_IV_CAND", c->iv_cand);
     if (env_int("FSEG_LABEL_GRID", v) && v > 0) c->label_grid = v;
     if (env_int("FSEG_SYNC_TICKS", v) && v > 0) c->sync_ticks = (unsigned)v;
     if (env_flag("FSEG_NO_GRAPH")) c->use_graph = false;

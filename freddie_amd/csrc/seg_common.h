@@ -765,6 +765,15 @@ __device__ __forceinline__ void peak_from(i64 p, i64 last /* the interval's last
 // For each problem the kernel also finds the range of position-sorted reads that can overlap its
 // window and carves its share of the arenas (one wave-aggregated atomic per arena and tile).
 // ---------------------------------------------------------------------------------------------
+// k_fix_cand / k_segments_cand (S4, S6 by candidates): a workgroup owns a run of kIvCandOwn consecutive candidates of the batch and
+// stages the kIvCandHalo candidates in front of them, a thread per staged candidate.  The halo is 64 because k_fix's short path
+// takes intervals of at most 64 candidates: candidate 0 of an owned candidate's short interval lies at most 63 back.
+// kIvCandFrom: the batch takes them from this many intervals on (where iv_threads is 64; FSEG_IV_CAND=0 / 1 overrides) -- 0: no
+// size rule (profiles/iv_cand.txt has the measurement it follows from).
+constexpr int kIvCandOwn = 448, kIvCandHalo = 64, kIvCandThreads = kIvCandOwn + kIvCandHalo;
+constexpr long long kIvCandFrom = 0;
+static_assert(kIvCandHalo == 64 && kIvCandThreads % 64 == 0 && kIvCandThreads <= 1024, "a wave of halo, whole waves, one workgroup");
+
 struct ProblemArrays {
     int *iv;        // interval
     int *start;     // first candidate (index inside the interval)

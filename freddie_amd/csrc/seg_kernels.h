@@ -79,6 +79,11 @@ __global__ void k_fix(i64 K, const i64 *pos_off, const int *iv_part, const i64 *
                       unsigned char *fixed, unsigned char *chosen, int *cand_pn, int *cand_iv, Status *st);
 
 // seg_problems.hip
+__global__ void __launch_bounds__(kIvCandThreads) k_fix_cand(const i64 *pos_off, const int *iv_part, const i64 *cand_off, const int *cand_y,
+                      const double *yv, const double *thr_part, int mps, unsigned char *fixed0, unsigned char *added,
+                      unsigned char *fixed, unsigned char *chosen, int *cand_pn, const int *cand_iv, Status *st);
+
+// seg_problems.hip
 __global__ void __launch_bounds__(kRangeThreads) k_prob_range(Status *st, const int *cand_pn, const int *cand_iv, const int *cand_y,
                              const int *iv_part, const int *iv_start, const i64 *part_lane_off, const int *lane_start,
                              const int *lane_pmax, int *cand_ll, int *cand_ln, unsigned char *cand_wide,
@@ -210,6 +215,12 @@ template <typename Count>
 __global__ void k_segments(i64 K, const i64 *pos_off, const i64 *cand_off, const int *cand_y, const Count *__restrict__ y_raw,
                            const int *__restrict__ blk_pre, const int *tile_tot, const int *iv_tile0, const unsigned char *chosen, unsigned *final_flag, int *rseg_c, int *rseg_prev,
                            Status *st);
+
+// seg_tail.hip
+template <typename Count>
+__global__ void __launch_bounds__(kIvCandThreads) k_segments_cand(const i64 *pos_off, const i64 *cand_off, const int *cand_y, const int *cand_iv,
+                           const Count *__restrict__ y_raw, const int *__restrict__ blk_pre, const int *tile_tot, const int *iv_tile0,
+                           const unsigned char *chosen, unsigned *final_flag, int *rseg_c, int *rseg_prev, Status *st);
 
 // seg_tail.hip
 template <typename Count>

@@ -90,6 +90,137 @@ __global__ void k_fix(i64 K, const i64 *pos_off, const int *iv_part, const i64 *
     }
 }
 
+// k_fix's general path for ONE interval by ONE wave (k_fix_cand's long intervals): the arithmetic and the error codes of k_fix's
+// lines for T = 64, the previous flagged candidate from the wave's ballot (wg_prev_flagged for one wave, without its barriers), and
+// a workgroup-scope fence where k_fix has a barrier: lanes read fixed0 / added bytes that other lanes of the wave stored.
+__device__ __forceinline__ int wave_prev_flagged(bool f, int idx, int &carry) {
+    const int lane = lane_id();
+    const u64 mask = __ballot(f), below = mask & ((1ULL << lane) - 1ULL);
+    const int prev = below ? idx - lane + 63 - __clzll((long long)below) : carry;
+    if (mask) carry = idx - lane + 63 - __clzll((long long)mask);
+    return prev;
+}
+__device__ __forceinline__ void fix_interval_wave(i64 k, const i64 *pos_off, const int *iv_part, const i64 *cand_off, const int *cand_y,
+                                                  const double *yv, const double *thr_part, int mps, unsigned char *fixed0,
+                                                  unsigned char *added, unsigned char *fixed, unsigned char *chosen, int *cand_pn, Status *st) {
+    constexpr int T = 64;
+    const int lane = lane_id();
+    i64 c0 = cand_off[k];
+    int N = (int)(cand_off[k + 1] - c0);
+    const double *y = yv + pos_off[k];
+    const int *cy = cand_y + c0;
+    double thr = thr_part[iv_part[k]];
+    for (int c = lane; c < N; c += T) {
+        fixed0[c0 + c] = (c == 0 || c == N - 1 || y[cy[c]] > thr) ? 1 : 0;
+        added[c0 + c] = 0;
+    }
+    __threadfence_block();
+    // break_large_problems over the original consecutive fixed pairs; the thread that owns the
+    // right end of an oversized gap places its anchors
+    int carry = -1;
+    for (int t0 = 0; t0 < N; t0 += T) {
+        int c = t0 + lane;
+        bool f = c < N && fixed0[c0 + c];
+        int prev = wave_prev_flagged(f, c, carry);
+        if (f && prev >= 0) {
+            int size = c - prev + 1;
+            if (size > mps) {
+                int cnt = (int)ceil((double)size / (double)mps);
+                double step = (double)size / (double)cnt;
+                for (int i = 1; i < cnt; ++i) {
+                    int anchor = (int)((double)prev + __dmul_rn((double)i, step));
+                    double best = -INFINITY;
+                    int best_c = -1;
+                    bool bad = false;
+                    for (int cc = anchor - 5; cc < anchor + 5; ++cc) {
+                        int ci = cc < 0 ? cc + N : cc;          // Python negative-index wraparound
+                        if (ci < 0 || ci >= N) { bad = true; continue; }
+                        double val = y[cy[ci]];
+                        if (val > best) { best = val; best_c = cc; }
+                    }
+                    if (bad || !(best > 0.0) || best_c < 0) atomicOr(&st->err, kErrBreakAssert);
+                    else added[c0 + best_c] = 1;
+                }
+            }
+        }
+    }
+    __threadfence_block();
+    // final fixed set; the right end of every problem records the problem's size
+    carry = -1;
+    for (int t0 = 0; t0 < N; t0 += T) {
+        int c = t0 + lane;
+        bool f = c < N && (fixed0[c0 + c] | added[c0 + c]);
+        int prev = wave_prev_flagged(f, c, carry);
+        if (c < N) {
+            fixed[c0 + c] = f; chosen[c0 + c] = f;
+            int n = (f && prev >= 0 && c - prev + 1 >= 3) ? c - prev + 1 : 0;
+            if (n > kNGiant) atomicOr(&st->err, kErrProblemTooLarge);
+            cand_pn[c0 + c] = n;
+        }
+    }
+}
+
+// k_fix by candidates (batches of many intervals of few candidates: a 2 M-read config4 batch has 120 000 intervals of ten candidates on
+// average, four in ten of two, and a wave of k_fix walks fifteen of them one after the other with a few lanes at work).  A workgroup owns
+// the candidates [run * kIvCandOwn, (run + 1) * kIvCandOwn) of the batch and stages kIvCandHalo more in front of them, a thread per
+// staged candidate; cand_iv (the candidate's interval) was written by the compaction that emitted the candidates.
+//   short interval (k_fix's one-wave condition, N <= 64 && N <= mps): every candidate by its own thread.  The flags of the staged
+//     candidates are an LDS bit mask, a word per wave; the previous fixed candidate is the highest flag below the thread's own.  It
+//     lies in the same interval -- candidate 0 of every interval is flagged and at most 63 candidates lie back --, so in the thread's
+//     own word or the one before.  Halo candidates are evaluated and never stored.  Three rounds of loads, none under a condition.
+//   any other interval belongs to the workgroup that owns its candidate 0: that thread notes the interval in an LDS list, and after
+//     the candidate phase the workgroup's WAVES take the list's intervals in turn, each by k_fix's general path for one wave
+//     (fix_interval_wave).  (As first built the whole workgroup walked the list, T = blockDim.x, interval after interval: one config4
+//     interval in forty is long, every workgroup met one or more, and the kernel's floor was those serial walks -- 22.6 us at 250 k
+//     reads against k_fix's 14.1, profiles/iv_cand.txt.)  The list has a slot per owned candidate and every entry is an owned
+//     candidate 0, so it cannot overflow: no second sweep.
+__global__ void __launch_bounds__(kIvCandThreads) k_fix_cand(const i64 *pos_off, const int *iv_part, const i64 *cand_off, const int *cand_y,
+                      const double *yv, const double *thr_part, int mps, unsigned char *fixed0, unsigned char *added,
+                      unsigned char *fixed, unsigned char *chosen, int *cand_pn, const int *cand_iv, Status *st) {
+    __shared__ u64 mask_s[kIvCandThreads / 64];
+    __shared__ int list_s[kIvCandOwn], list_n;
+    const int lane = lane_id(), wave = threadIdx.x >> 6;
+    const i64 n_cand = (i64)st->n_cand;
+    for (i64 g0 = (i64)blockIdx.x * kIvCandOwn; g0 < n_cand; g0 += (i64)gridDim.x * kIvCandOwn) {       // (workgroup-uniform)
+        const i64 g = g0 - kIvCandHalo + threadIdx.x;
+        const bool valid = g >= 0 && g < n_cand, own = valid && threadIdx.x >= kIvCandHalo;
+        const i64 gc = g < 0 ? 0 : (g < n_cand ? g : n_cand - 1);
+        if (threadIdx.x == 0) list_n = 0;
+        // candidate -> interval -> signal and threshold, asked for by every staged candidate alike
+        const int k = cand_iv[gc], yy = cand_y[gc];
+        const i64 c0 = cand_off[k], c1 = cand_off[k + 1], po = pos_off[k];
+        const int part = iv_part[k];
+        const int N = (int)(c1 - c0), c = (int)(gc - c0);
+        // (an interval's two ends are fixed whatever the signal says -- one candidate in five of a config4 batch: they ask for
+        // position 0 of the batch, a hit, not for a line of their own; the address is selected, the load is not under a condition)
+        const bool end = !valid || c == 0 || c == N - 1;
+        const double val = yv[end ? 0 : po + yy], thr = thr_part[part];
+        const bool is_short = N <= 64 && N <= mps;
+        const bool f = valid && (c == 0 || c == N - 1 || val > thr);
+        const u64 mask = __ballot(f);
+        if (lane == 0) mask_s[wave] = mask;
+        __syncthreads();
+        if (own && !is_short && c == 0) list_s[atomicAdd(&list_n, 1)] = k;
+        if (own && is_short) {
+            int n = 0;
+            if (f && c > 0) {
+                // (c > 0: candidate 0 of the interval is flagged and staged, at most 63 below)
+                const u64 below = mask & ((1ULL << lane) - 1ULL);
+                const int back = below ? lane - (63 - __clzll((long long)below)) : lane + 1 + __clzll((long long)mask_s[wave - 1]);
+                n = back + 1 >= 3 ? back + 1 : 0;
+            }
+            fixed0[g] = f; added[g] = 0;
+            fixed[g] = f; chosen[g] = f;
+            cand_pn[g] = n;
+        }
+        __syncthreads();
+        const int n_list = list_n;
+        for (int li = wave; li < n_list; li += kIvCandThreads / 64)   // (wave-uniform)
+            fix_interval_wave(list_s[li], pos_off, iv_part, cand_off, cand_y, yv, thr_part, mps, fixed0, added, fixed, chosen, cand_pn, st);
+        __syncthreads();                                             // (the list is read: the next run may note its own)
+    }
+}
+
 // bs != nullptr: the workgroup's 1 024 candidates are a block of the problem scan, and it adds up the block's sizes itself when its
 // ranges are known -- what k_prob_scan1 (25 us of a config4 batch, most of it 147 workgroups starting, loading and ending) then
 // need not do.

@@ -39,17 +39,11 @@ __device__ __forceinline__ int end_blocks(const uint16_t *yr, int a0, int a, int
 }
 
 // Count: the histogram's element (int, or uint16_t where S1 ran packed), here and in k_refine
+// the inner-positions test of refine_segmentation (:258) for the segment (py, y] of interval k, whose first tile is tile0
+// (k_segments and k_segments_cand)
 template <typename Count>
-__global__ void k_segments(i64 K, const i64 *pos_off, const i64 *cand_off, const int *cand_y, const Count *__restrict__ y_raw,
-                           const int *__restrict__ blk_pre, const int *tile_tot, const int *iv_tile0, const unsigned char *chosen, unsigned *final_flag, int *rseg_c, int *rseg_prev,
-                           Status *st) {
-    __shared__ int lds[16];
-    __shared__ int cnt_s[16];
-    __shared__ u64 base_s;
-    const int T = blockDim.x;
-    int lane = lane_id(), wave = threadIdx.x >> 6, nw = (T + 63) >> 6;
-    // the inner-positions test of refine_segmentation (:258) for the segment (py, y] of interval k, whose first tile is tile0
-    auto inner_sum_ok = [&](i64 base, int tile0, int py, int y) -> bool {
+__device__ __forceinline__ bool inner_sum_ok(const Count *__restrict__ y_raw, const int *__restrict__ blk_pre, const int *tile_tot,
+                                             i64 base, int tile0, int py, int y) {
         // refine_segmentation's `sum(i_vals) < 20 -> continue` (:258), exactly, over the inner positions [py+20, y-21]:
         // k_smooth's prefix of the histogram at the start of a's and of b's block (inside their tiles), the tiles
         // between them, and the positions of those two blocks up to a (exclusive) / up to b (inclusive)
@@ -65,7 +59,17 @@ __global__ void k_segments(i64 K, const i64 *pos_off, const i64 *cand_off, const
         tot += end_blocks(yr, a0, a, b0, b);
         for (int q = ta; q < tb; ++q) tot += tt[q];
         return tot >= 20;
-    };
+}
+
+template <typename Count>
+__global__ void k_segments(i64 K, const i64 *pos_off, const i64 *cand_off, const int *cand_y, const Count *__restrict__ y_raw,
+                           const int *__restrict__ blk_pre, const int *tile_tot, const int *iv_tile0, const unsigned char *chosen, unsigned *final_flag, int *rseg_c, int *rseg_prev,
+                           Status *st) {
+    __shared__ int lds[16];
+    __shared__ int cnt_s[16];
+    __shared__ u64 base_s;
+    const int T = blockDim.x;
+    int lane = lane_id(), wave = threadIdx.x >> 6, nw = (T + 63) >> 6;
     for (i64 k = blockIdx.x; k < K; k += gridDim.x) {
         i64 c0 = cand_off[k];
         int N = (int)(cand_off[k + 1] - c0);
@@ -103,7 +107,7 @@ __global__ void k_segments(i64 K, const i64 *pos_off, const i64 *cand_off, const
                 if (mask) carry_y = __shfl(yv[u], 63 - __clzll((long long)mask));
             }
 #pragma unroll
-            for (int u = 0; u < kSegChunks; ++u) if (need[u]) need[u] = inner_sum_ok(base, tile0, pyv[u], yv[u]);
+            for (int u = 0; u < kSegChunks; ++u) if (need[u]) need[u] = inner_sum_ok(y_raw, blk_pre, tile_tot, base, tile0, pyv[u], yv[u]);
 #pragma unroll
             for (int u = 0; u < kSegChunks; ++u) {
                 const u64 m = __ballot(need[u]);
@@ -131,7 +135,7 @@ __global__ void k_segments(i64 K, const i64 *pos_off, const i64 *cand_off, const
                 if (prev >= 0) py = cand_y[c0 + prev];
             }
             bool need = f && py >= 0 && y - py > 40;                  // :252
-            if (need) need = inner_sum_ok(base, iv_tile0[k], py, y);
+            if (need) need = inner_sum_ok(y_raw, blk_pre, tile_tot, base, iv_tile0[k], py, y);
             u64 m = __ballot(need);
             if (lane == 0) cnt_s[wave] = __popcll(m);
             __syncthreads();
@@ -154,6 +158,66 @@ __global__ void k_segments(i64 K, const i64 *pos_off, const i64 *cand_off, const
 // from speculative loads of the four candidates below it, one slot atomic per workgroup: 2 300 waves instead of 61 000 and 20-21 us
 // either way.  With the pieces taken out: 11 us without the final flags and the inner sums, the sums 8, the flags 2 -- the kernel is four
 // or five levels of dependent L2 round trips and a drain whatever its shape.)
+
+// k_segments by candidates, for batches of many short intervals (what the trial above was not measured at: a 2 M-read config4 batch,
+// where a wave of k_segments walks sixty intervals one after the other).  The workgroups' shape is k_fix_cand's: kIvCandOwn owned
+// candidates, kIvCandHalo staged in front of them, a thread per staged candidate, its interval from cand_iv.  The previous chosen
+// candidate comes from the staged window -- an LDS bit mask of `chosen`, a word per wave, and the staged cand_y --; where the window
+// does not reach it (gaps grow with max_problem_size) the thread walks back in `chosen` itself, never below its interval's first
+// candidate.  One slot atomic per wave; the order of the segment list is whatever the atomics make it, as in k_segments.
+template <typename Count>
+__global__ void __launch_bounds__(kIvCandThreads) k_segments_cand(const i64 *pos_off, const i64 *cand_off, const int *cand_y, const int *cand_iv,
+                           const Count *__restrict__ y_raw, const int *__restrict__ blk_pre, const int *tile_tot, const int *iv_tile0,
+                           const unsigned char *chosen, unsigned *final_flag, int *rseg_c, int *rseg_prev, Status *st) {
+    __shared__ u64 mask_s[kIvCandThreads / 64];
+    __shared__ int y_s[kIvCandThreads];
+    const int lane = lane_id(), wave = threadIdx.x >> 6;
+    const i64 n_cand = (i64)st->n_cand;
+    for (i64 g0 = (i64)blockIdx.x * kIvCandOwn; g0 < n_cand; g0 += (i64)gridDim.x * kIvCandOwn) {       // (workgroup-uniform)
+        const i64 gs = g0 - kIvCandHalo, g = gs + threadIdx.x;     // the first staged candidate, this thread's
+        const bool valid = g >= 0 && g < n_cand;
+        const i64 gc = g < 0 ? 0 : (g < n_cand ? g : n_cand - 1);
+        // candidate -> interval, asked for by every staged candidate alike
+        const bool ch = valid && chosen[gc];
+        const int y = cand_y[gc], k = cand_iv[gc];
+        const i64 c0 = cand_off[k], base = pos_off[k];
+        const int tile0 = iv_tile0[k];
+        const u64 mask = __ballot(ch);
+        if (lane == 0) mask_s[wave] = mask;
+        y_s[threadIdx.x] = y;
+        __syncthreads();
+        const bool f = ch && threadIdx.x >= kIvCandHalo;
+        int py = -1;
+        if (f) {
+            set_flag(final_flag, base + y);
+            // the highest chosen candidate below this one in the staged window
+            u64 below = mask & ((1ULL << lane) - 1ULL);
+            int w = wave;
+            while (!below && w > 0) below = mask_s[--w];
+            if (below) {
+                const int pt = w * 64 + 63 - __clzll((long long)below);
+                if (gs + pt >= c0) py = y_s[pt];                   // (else it is an earlier interval's: this one has none below)
+            } else {
+                for (i64 q = gs - 1; q >= c0; --q)                 // beyond the halo: rare, and never below the interval's first candidate
+                    if (chosen[q]) { py = cand_y[q]; break; }
+            }
+        }
+        bool need = f && py >= 0 && y - py > 40;                   // :252
+        if (need) need = inner_sum_ok(y_raw, blk_pre, tile_tot, base, tile0, py, y);
+        const u64 m = __ballot(need);
+        if (m) {                                                   // (wave-uniform)
+            u64 slot0 = 0;
+            if (lane == 0) slot0 = atomicAdd(&st->n_rseg, (u64)__popcll(m));
+            slot0 = __shfl(slot0, 0);
+            if (need) {
+                const u64 slot = slot0 + __popcll(m & ((1ULL << lane) - 1ULL));
+                rseg_c[slot] = (int)g; rseg_prev[slot] = py;
+            }
+        }
+        __syncthreads();                                           // (the window is read: the next run may be staged)
+    }
+}
+
 template <typename Count>
 __global__ void __launch_bounds__(64) k_refine(const Status *st, const int *cand_iv, const int *rseg_c,
                                                const int *rseg_prev, const int *cand_y, const i64 *pos_off,
@@ -597,6 +661,8 @@ __global__ void __launch_bounds__(256) k_pack_labels(const uint4 *__restrict__ l
 __attribute__((used)) static const void *const kInstances[] = {
     reinterpret_cast<const void *>(&k_segments<int>),
     reinterpret_cast<const void *>(&k_segments<uint16_t>),
+    reinterpret_cast<const void *>(&k_segments_cand<int>),
+    reinterpret_cast<const void *>(&k_segments_cand<uint16_t>),
     reinterpret_cast<const void *>(&k_refine<int>),
     reinterpret_cast<const void *>(&k_refine<uint16_t>),
 };

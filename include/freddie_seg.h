@@ -249,8 +249,10 @@ enum {
      *   30 the histogram is uint16 in device memory (FSEG_YRAW16, where word 27 is 1; 0: int32)
      *   31 lane_sort: how the last upload ordered the reps -- 0 k_lanes sorted every partition in LDS, 1 the batch-wide radix sort
      *      and k_lane_blocks / k_lane_block_scan / k_lane_emit (a partition of more than 2 048 reps, or FSEG_GLOBAL_SORT=1);
-     *      written by fseg_upload, kept by every run and replay of the batch */
-    FSEG_TAP_PATHS = 18,       /* int32[32]                                                                            */
+     *      written by fseg_upload, kept by every run and replay of the batch
+     *   32 iv_cand: S4 and S6 ran by candidates (k_fix_cand, k_segments_cand: a thread per candidate; only where word 28 is 64,
+     *      from kIvCandFrom intervals on or under FSEG_IV_CAND=1); 0: by intervals (k_fix, k_segments) */
+    FSEG_TAP_PATHS = 18,       /* int32[33]                                                                            */
     /* the histogram chunks of the last upload, a row each: (p0, n, llo, lhi) -- the chunk's first batch position, its position
      * count, and the lanes [llo, lhi) of its partition that k_hist_ranges found able to reach it */
     FSEG_TAP_HIST_RANGES = 19  /* int64[n_hist_chunks][4]                                                              */
