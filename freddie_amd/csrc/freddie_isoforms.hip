@@ -1,7 +1,8 @@
 // freddie_isoforms.hip -- gfx950 kernels + C-ABI (include/freddie_isoforms.h) of the isoform-consensus stage's per-read
 // loops: the consensus counts of isoforms_cons() (py/freddie_isoforms.py:203-232) and the boundary votes of
 // correct_boundaries() (:129-137).  Integer work only; the layout is read-major label bytes, so the consensus kernel's
-// lanes (= consecutive segments of one read) load consecutive bytes.
+// lanes (= consecutive segments of one read) load consecutive bytes.  fiso_isoforms() (kernels: iso_decide.h) does both loops and
+// the decisions taken from their integers in one call, from one bit per label.
 #include "freddie_isoforms.h"
 
 #include <hip/hip_runtime.h>
@@ -341,6 +342,17 @@ __global__ void __launch_bounds__(256) k_votes(int n_iso, const i64 *iso_read_of
     }
 }
 
+#include "iso_decide.h"   // k_iso_exons, k_iso_correct: fiso_isoforms()
+
+// fiso_isoforms()'s results: one pinned block, kept (and grown) from call to call, and the pointers into it
+struct IsoResults {
+    void *pinned = nullptr;
+    size_t cap = 0;
+    bool valid = false;
+    fiso_isoforms_out out = {};
+    ~IsoResults() { if (pinned) (void)hipHostFree(pinned); }
+};
+
 }  // namespace
 
 struct fiso_ctx {
@@ -349,6 +361,7 @@ struct fiso_ctx {
     hipEvent_t ev[2] = {};
     std::string err;
     float kernel_ms = 0.f;
+    IsoResults iso;
 };
 
 namespace {
@@ -545,6 +558,139 @@ int fiso_boundary_votes(fiso_ctx *c, int32_t n_iso, const int64_t *iso_read_off,
 int fiso_last_kernel_ms(fiso_ctx *c, float *ms) {
     if (!c || !ms) return FISO_ERR_ARG;
     *ms = c->kernel_ms;
+    return FISO_OK;
+}
+
+int fiso_isoforms_limits(int32_t out[4]) {
+    if (!out) return FISO_ERR_ARG;
+    out[0] = kIsoRowMax; out[1] = kIsoReadTile; out[2] = kIsoBoundTile; out[3] = 0;
+    return FISO_OK;
+}
+
+int fiso_isoforms(fiso_ctx *c, const fiso_input *in, double majority_threshold, int32_t window) {
+    if (!c) return FISO_ERR_ARG;
+    c->iso.valid = false;
+    c->kernel_ms = 0.f;
+    if (!in) return fail(c, FISO_ERR_ARG, "input is NULL");
+    // ---- every refusal, before anything is allocated or launched
+    if (!(window >= 0 && window <= kIsoWindowMax)) return fail(c, FISO_ERR_ARG, "window %d is outside [0, %d] (py/freddie_isoforms.py:45)", window, kIsoWindowMax);
+    if (!(majority_threshold >= 0.5 && majority_threshold <= 1.0))
+        return fail(c, FISO_ERR_ARG, "majority_threshold %g is outside [0.5, 1] (py/freddie_isoforms.py:44)", majority_threshold);
+    const int n_tint = in->n_tint, n_iso = in->n_iso;
+    if (n_tint < 0 || n_iso < 0) return fail(c, FISO_ERR_ARG, "n_tint / n_iso is negative");
+    if (!in->tint_pos_off || !in->iso_read_off || !in->read_bits_off || !in->read_b_off || (n_iso && !in->iso_tint))
+        return fail(c, FISO_ERR_ARG, "an offset array or iso_tint is NULL");
+    TRY(check_offsets(c, "tint_pos_off", in->tint_pos_off, n_tint));
+    if (in->tint_pos_off[n_tint] && !in->pos) return fail(c, FISO_ERR_ARG, "pos is NULL");
+    for (int t = 0; t < n_tint; ++t) {
+        const i64 a = in->tint_pos_off[t], b = in->tint_pos_off[t + 1];
+        if (b - a < 1) return fail(c, FISO_ERR_ARG, "tint %d has no position", t);
+        for (i64 k = a + 1; k < b; ++k)
+            if (in->pos[k] <= in->pos[k - 1]) return fail(c, FISO_ERR_ARG, "tint %d: positions are not strictly ascending at %lld", t, k - a);
+    }
+    TRY(check_offsets(c, "iso_read_off", in->iso_read_off, n_iso));
+    const i64 R = in->iso_read_off[n_iso];
+    for (int i = 0; i < n_iso; ++i)
+        if (in->iso_tint[i] < 0 || in->iso_tint[i] >= n_tint) return fail(c, FISO_ERR_ARG, "iso_tint[%d] = %d is out of range", i, in->iso_tint[i]);
+    auto segments_of = [&](int i) { const int t = in->iso_tint[i]; return (i64)(in->tint_pos_off[t + 1] - in->tint_pos_off[t] - 1); };
+    for (int i = 0; i < n_iso; ++i)
+        if (segments_of(i) > kIsoRowMax)
+            return fail(c, FISO_ERR_UNSUPPORTED, "isoform %d has %lld segments, more than %d", i, segments_of(i), kIsoRowMax);
+    if (R && (!in->tail || !in->bits)) {
+        bool any_word = false;
+        for (int i = 0; i < n_iso && !any_word; ++i) any_word = segments_of(i) > 0 && in->iso_read_off[i + 1] > in->iso_read_off[i];
+        if (!in->tail || any_word) return fail(c, FISO_ERR_ARG, "tail or bits is NULL");
+    }
+    if (in->read_bits_off[0] != 0) return fail(c, FISO_ERR_ARG, "read_bits_off does not start at 0");
+    for (int i = 0; i < n_iso; ++i) {
+        const int M = (int)segments_of(i), W = (M + 63) >> 6;
+        const u64 beyond = (M & 63) ? ~0ULL << (M & 63) : 0ULL;            // bits of a row's last word past segment M - 1
+        for (i64 r = in->iso_read_off[i]; r < in->iso_read_off[i + 1]; ++r) {
+            if (in->read_bits_off[r + 1] - in->read_bits_off[r] != W)
+                return fail(c, FISO_ERR_ARG, "read_bits_off does not advance by %d words at read %lld (isoform %d)", W, r, i);
+            if (W && (in->bits[in->read_bits_off[r] + W - 1] & beyond))
+                return fail(c, FISO_ERR_ARG, "read %lld: a bit is set beyond segment %d (isoform %d)", r, M - 1, i);
+            if (in->tail[r] > 2) return fail(c, FISO_ERR_ARG, "read %lld: tail %d is above 2", r, (int)in->tail[r]);
+        }
+    }
+    TRY(check_offsets(c, "read_b_off", in->read_b_off, R));
+    const i64 Q = in->read_b_off[R];
+    if (Q && (!in->read_start || !in->read_end)) return fail(c, FISO_ERR_ARG, "read_start or read_end is NULL");
+    HIP_TRY(c, hipSetDevice(c->device));
+
+    // ---- results: one block, [exon_off][start][end][seg_first][seg_last][n_exon][tails][strand], the same on both sides
+    std::vector<i64> bits_off((size_t)n_iso + 1), q_off((size_t)n_iso + 1), e_off((size_t)n_iso + 1);
+    e_off[0] = 0;
+    for (int i = 0; i < n_iso; ++i) {
+        bits_off[i] = in->read_bits_off[in->iso_read_off[i]];
+        q_off[i] = in->read_b_off[in->iso_read_off[i]];
+        e_off[i + 1] = e_off[i] + (segments_of(i) + 1) / 2;
+    }
+    bits_off[n_iso] = in->read_bits_off[R]; q_off[n_iso] = Q;
+    const size_t E = (size_t)e_off[n_iso], n = (size_t)n_iso;
+    const size_t o_start = 8 * (n + 1), o_end = o_start + 4 * E, o_sf = o_end + 4 * E, o_sl = o_sf + 4 * E, o_ne = o_sl + 4 * E,
+                 o_tails = o_ne + 4 * n, o_strand = o_tails + 12 * n, total = o_strand + n;
+    IsoResults &res = c->iso;
+    if (res.cap < total) {
+        if (res.pinned) { (void)hipHostFree(res.pinned); res.pinned = nullptr; res.cap = 0; }
+        HIP_TRY(c, hipHostMalloc(&res.pinned, total + 64, hipHostMallocDefault));
+        res.cap = total;
+    }
+    char *hp = reinterpret_cast<char *>(res.pinned);
+    __builtin_memcpy(hp, e_off.data(), 8 * (n + 1));
+    hipStream_t s = c->stream;
+    if (n_iso) {
+        Dev d_tpo, d_pos, d_it, d_iro, d_ibo, d_bits, d_tail, d_iqo, d_rs, d_re, d_out;
+        TRY(to_device(c, d_tpo, in->tint_pos_off, (size_t)n_tint + 1));
+        TRY(to_device(c, d_pos, in->pos, (size_t)in->tint_pos_off[n_tint]));
+        TRY(to_device(c, d_it, in->iso_tint, n));
+        TRY(to_device(c, d_iro, in->iso_read_off, n + 1));
+        TRY(to_device(c, d_ibo, bits_off.data(), n + 1));
+        TRY(to_device(c, d_bits, in->bits, (size_t)bits_off[n_iso]));
+        TRY(to_device(c, d_tail, in->tail, (size_t)R));
+        TRY(to_device(c, d_iqo, q_off.data(), n + 1));
+        if (window) {
+            TRY(to_device(c, d_rs, in->read_start, (size_t)Q));
+            TRY(to_device(c, d_re, in->read_end, (size_t)Q));
+        }
+        HIP_TRY(c, hipMalloc(&d_out.p, total + 64));
+        char *dp = d_out.as<char>();
+        HIP_TRY(c, hipMemcpyAsync(dp, hp, o_start, hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipEventRecord(c->ev[0], s));
+        HIP_TRY(c, hipMemsetAsync(dp + o_start, 0, total - o_start, s));  // (slots an isoform does not use read 0)
+        const dim3 grid(n_iso < 8192 ? n_iso : 8192);
+        hipLaunchKernelGGL(k_iso_exons, grid, dim3(256), 0, s, n_iso, d_it.as<int>(), d_tpo.as<i64>(), d_pos.as<int>(), d_iro.as<i64>(),
+                           d_ibo.as<i64>(), d_bits.as<u64>(), d_tail.as<unsigned char>(), reinterpret_cast<i64 *>(dp),
+                           reinterpret_cast<int *>(dp + o_ne), reinterpret_cast<int *>(dp + o_start), reinterpret_cast<int *>(dp + o_end),
+                           reinterpret_cast<int *>(dp + o_sf), reinterpret_cast<int *>(dp + o_sl),
+                           reinterpret_cast<unsigned char *>(dp + o_strand), reinterpret_cast<int *>(dp + o_tails));
+        if (window)
+            hipLaunchKernelGGL(k_iso_correct, grid, dim3(256), 0, s, n_iso, d_iro.as<i64>(), d_iqo.as<i64>(), d_rs.as<int>(), d_re.as<int>(),
+                               reinterpret_cast<i64 *>(dp), reinterpret_cast<int *>(dp + o_ne), reinterpret_cast<int *>(dp + o_start),
+                               reinterpret_cast<int *>(dp + o_end), (int)window, majority_threshold);
+        HIP_TRY(c, hipEventRecord(c->ev[1], s));
+        HIP_TRY(c, hipMemcpyAsync(hp + o_start, dp + o_start, total - o_start, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipStreamSynchronize(s));
+        HIP_TRY(c, hipGetLastError());
+        (void)hipEventElapsedTime(&c->kernel_ms, c->ev[0], c->ev[1]);
+    }
+    res.out.n_iso = n_iso;
+    res.out.exon_off = reinterpret_cast<const int64_t *>(hp);
+    res.out.start = reinterpret_cast<const int32_t *>(hp + o_start);
+    res.out.end = reinterpret_cast<const int32_t *>(hp + o_end);
+    res.out.seg_first = reinterpret_cast<const int32_t *>(hp + o_sf);
+    res.out.seg_last = reinterpret_cast<const int32_t *>(hp + o_sl);
+    res.out.n_exon = reinterpret_cast<const int32_t *>(hp + o_ne);
+    res.out.tails = reinterpret_cast<const int32_t *>(hp + o_tails);
+    res.out.strand = reinterpret_cast<const uint8_t *>(hp + o_strand);
+    res.valid = true;
+    return FISO_OK;
+}
+
+int fiso_isoforms_results(fiso_ctx *c, fiso_isoforms_out *out) {
+    if (!c || !out) return FISO_ERR_ARG;
+    if (!c->iso.valid) return fail(c, FISO_ERR_ARG, "fiso_isoforms_results: no successful fiso_isoforms call behind it");
+    *out = c->iso.out;
     return FISO_OK;
 }
 

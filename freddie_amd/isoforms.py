@@ -9,6 +9,8 @@ Reference map (file:line of vpc-ccg/freddie ``py/freddie_isoforms.py``):
   read_split :143-156                 -> read_split()
   isoforms_cons :203-250              -> isoforms_cons_batch()      counts on the GPU, decisions here
   correct_boundaries :122-140         -> correct_boundaries_batch() votes on the GPU, decisions here
+                                      -> decide_gpu_batch()         --decide gpu: both, decisions included, in one
+                                                                    device call (Context.isoforms) from one bit per label
   get_gtf_records :72-119             -> get_gtf_records()
   run_consensus :50-69                -> run_consensus(), run_consensus_batch()
 """
@@ -24,19 +26,36 @@ from . import build as _build
 
 ISO_SO = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libfreddie_isoforms.so")
 ISO_SRC = [os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "freddie_isoforms.hip")]
+ISO_HDR = [os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "iso_decide.h")]
 EXPORTS = ["fiso_abi_version", "fiso_create", "fiso_destroy", "fiso_last_error", "fiso_consensus", "fiso_consensus_packed", "fiso_boundary_votes",
-           "fiso_last_kernel_ms"]
+           "fiso_last_kernel_ms", "fiso_isoforms", "fiso_isoforms_results", "fiso_isoforms_limits"]
 _lib = None
 _TAIL_CODE = {"N": 0, "S": 1, "E": 2}
+FISO_ERR_UNSUPPORTED = 3
+# --decide gpu: batches decided by the one device call, and batches it refused as unsupported that took the host path
+decide_stats = {"gpu_batches": 0, "fallback_batches": 0}
 
 
 class IsoformsError(RuntimeError):
-    pass
+    code = None                                      # the library's return code, where one was returned
+
+
+class FisoInput(ctypes.Structure):                   # fiso_input (include/freddie_isoforms.h)
+    _fields_ = [("n_tint", ctypes.c_int32), ("tint_pos_off", ctypes.c_void_p), ("pos", ctypes.c_void_p),
+                ("n_iso", ctypes.c_int32), ("iso_tint", ctypes.c_void_p), ("iso_read_off", ctypes.c_void_p),
+                ("read_bits_off", ctypes.c_void_p), ("bits", ctypes.c_void_p), ("tail", ctypes.c_void_p),
+                ("read_b_off", ctypes.c_void_p), ("read_start", ctypes.c_void_p), ("read_end", ctypes.c_void_p)]
+
+
+class FisoIsoformsOut(ctypes.Structure):             # fiso_isoforms_out
+    _fields_ = [("n_iso", ctypes.c_int32), ("exon_off", ctypes.c_void_p), ("n_exon", ctypes.c_void_p), ("start", ctypes.c_void_p),
+                ("end", ctypes.c_void_p), ("seg_first", ctypes.c_void_p), ("seg_last", ctypes.c_void_p), ("strand", ctypes.c_void_p),
+                ("tails", ctypes.c_void_p)]
 
 
 def build(force=False, verbose=False):
     cmd = ["hipcc", "-O3", "--offload-arch=gfx950", "-shared", "-fPIC", "-I", _build.INCLUDE, "-o", ISO_SO] + ISO_SRC
-    _build.build_stamped(ISO_SO, cmd, ISO_SRC + [os.path.join(_build.INCLUDE, "freddie_isoforms.h")], force, verbose)
+    _build.build_stamped(ISO_SO, cmd, ISO_SRC + ISO_HDR + [os.path.join(_build.INCLUDE, "freddie_isoforms.h")], force, verbose)
     return ISO_SO
 
 
@@ -64,6 +83,12 @@ def load():
     L.fiso_boundary_votes.argtypes = [vp, ctypes.c_int32, vp, vp, vp, vp, vp, ctypes.c_int32, vp]
     L.fiso_last_kernel_ms.restype = ctypes.c_int
     L.fiso_last_kernel_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
+    L.fiso_isoforms.restype = ctypes.c_int
+    L.fiso_isoforms.argtypes = [vp, ctypes.POINTER(FisoInput), ctypes.c_double, ctypes.c_int32]
+    L.fiso_isoforms_results.restype = ctypes.c_int
+    L.fiso_isoforms_results.argtypes = [vp, ctypes.POINTER(FisoIsoformsOut)]
+    L.fiso_isoforms_limits.restype = ctypes.c_int
+    L.fiso_isoforms_limits.argtypes = [ctypes.POINTER(ctypes.c_int32 * 4)]
     _lib = L
     return L
 
@@ -75,8 +100,28 @@ def pack_labels(labels):
     return (v[:, 0] | (v[:, 1] << 2) | (v[:, 2] << 4) | (v[:, 3] << 6)).astype(np.uint8)
 
 
+def pack_label_bits(rows, M):
+    """Byte rows (n, M) of labels -> (n, ceil(M / 64)) little-endian 64-bit words, bit j & 63 of word j >> 6 set where
+    label j == ord('1'): all that isoforms_cons() asks of a label ('X', '-', '0' and '2' alike are not '1')."""
+    rows = np.ascontiguousarray(rows, np.uint8)
+    rows = rows.reshape(-1, M) if rows.ndim != 2 else rows          # (a flat buffer of whole rows; needs M > 0)
+    assert rows.shape[1] == M, (rows.shape, M)
+    W = (M + 63) // 64
+    out = np.zeros((rows.shape[0], 8 * W), np.uint8)
+    if M:
+        out[:, :(M + 7) // 8] = np.packbits(rows == ord("1"), axis=1, bitorder="little")
+    return out.view("<u8")
+
+
 def _ptr(a):
     return a.ctypes.data if a.size else None
+
+
+def _copy_out(addr, count, dtype):
+    """A copy of ``count`` items at address ``addr`` (the library's pinned results: they are its own until its next call)."""
+    if not count:
+        return np.zeros(0, dtype)
+    return np.frombuffer(ctypes.string_at(addr, count * np.dtype(dtype).itemsize), dtype).copy()
 
 
 class Context:
@@ -124,6 +169,34 @@ class Context:
         self._ms()
         return votes[:int(a[1][-1])]
 
+    def isoforms(self, tint_pos_off, pos, iso_tint, iso_read_off, read_bits_off, bits, tail, read_b_off, read_start, read_end,
+                 majority_threshold, window):
+        """fiso_isoforms + fiso_isoforms_results: exons, strand and corrected boundaries of every isoform from one device
+        call.  Returns a dict of arrays (copies): exon_off (n_iso + 1; isoform i owns (M + 1) // 2 slots from exon_off[i]),
+        n_exon, start, end, seg_first, seg_last (per slot), strand (uint8: '+', '-', 0 without an exon), tails (n_iso, 3)."""
+        a = dict(tint_pos_off=np.ascontiguousarray(tint_pos_off, np.int64), pos=np.ascontiguousarray(pos, np.int32),
+                 iso_tint=np.ascontiguousarray(iso_tint, np.int32), iso_read_off=np.ascontiguousarray(iso_read_off, np.int64),
+                 read_bits_off=np.ascontiguousarray(read_bits_off, np.int64), bits=np.ascontiguousarray(bits, np.uint64),
+                 tail=np.ascontiguousarray(tail, np.uint8), read_b_off=np.ascontiguousarray(read_b_off, np.int64),
+                 read_start=np.ascontiguousarray(read_start, np.int32), read_end=np.ascontiguousarray(read_end, np.int32))
+        inp = FisoInput(n_tint=len(a["tint_pos_off"]) - 1, n_iso=len(a["iso_tint"]), **{k: _ptr(v) for k, v in a.items()})
+        rc = self._L.fiso_isoforms(self._h, ctypes.byref(inp), float(majority_threshold), int(window))
+        if rc != 0:
+            err = IsoformsError("fiso_isoforms: " + self._L.fiso_last_error(self._h).decode())
+            err.code = rc
+            raise err
+        self._ms()
+        o = FisoIsoformsOut()
+        if self._L.fiso_isoforms_results(self._h, ctypes.byref(o)) != 0:
+            raise IsoformsError("fiso_isoforms_results: " + self._L.fiso_last_error(self._h).decode())
+        n = o.n_iso
+        exon_off = _copy_out(o.exon_off, n + 1, np.int64)
+        E = int(exon_off[-1])
+        return dict(exon_off=exon_off, n_exon=_copy_out(o.n_exon, n, np.int32), start=_copy_out(o.start, E, np.int32),
+                    end=_copy_out(o.end, E, np.int32), seg_first=_copy_out(o.seg_first, E, np.int32),
+                    seg_last=_copy_out(o.seg_last, E, np.int32), strand=_copy_out(o.strand, n, np.uint8),
+                    tails=_copy_out(o.tails, 3 * n, np.int32).reshape(n, 3))
+
     def close(self):
         if getattr(self, "_h", None):
             self._L.fiso_destroy(self._h)
@@ -151,6 +224,9 @@ def parse_args(argv=None):
                     help="Path to output file. Default: freddie_isoforms.gtf")
     ap.add_argument("--device", type=int, default=0, help="GPU ordinal")
     ap.add_argument("--batch-tints", type=int, default=2000, help="Tints per device batch")
+    ap.add_argument("--decide", choices=["host", "gpu"], default="host",
+                    help="Where exon runs, strand and boundary corrections are decided: 'host' (counts and votes come back from the "
+                         "GPU, Python decides) or 'gpu' (one device call per batch returns the exons). Default: host")
     args = ap.parse_args(argv)
     assert 0.5 <= args.majority_threshold <= 1.0
     assert 0 <= args.correction_window <= 20
@@ -263,6 +339,84 @@ def correct_boundaries_batch(side, jobs, majority_threshold, correction_window, 
                     isoform[side][idx] = (k - correction_window) + iso_s
 
 
+def isoforms_input_rows(jobs):
+    """First half of the --decide gpu arguments, from (isoforms, segments, reads) jobs as read_cluster() leaves them: tints,
+    isoforms, reads (each isoform's in sorted(rids) order, as the host path sends them), label bits and tails.  Raises what
+    isoforms_cons_batch() raises, in its order: the row-length assert, the KeyError of an unknown tail."""
+    tint_index, tint_pos_off, pos = {}, [0], []
+    isos, iso_tint, iso_read_off, rids, tail, read_bits_off = [], [], [0], [], [], [0]
+    runs = []                                            # (M, label strings) of consecutive isoforms with rows of one length
+    for job, (isoforms, segments, reads) in enumerate(jobs):
+        for key, isoform in isoforms.items():
+            segs = segments[(key[0], key[1])]
+            M = len(segs)
+            tkey = (job, key[0], key[1])
+            if tkey not in tint_index:
+                tint_index[tkey] = len(tint_index)
+                pos.extend([s for s, _ in segs] + ([segs[-1][1]] if segs else [0]))
+                tint_pos_off.append(len(pos))
+            if not runs or runs[-1][0] != M:
+                runs.append((M, []))
+            W = (M + 63) // 64
+            for rid in sorted(isoform["rids"]):
+                read = reads[rid]
+                assert len(read["data"]) == M, (M, key, read)
+                runs[-1][1].append(read["data"])
+                tail.append(_TAIL_CODE[read["tail"]])           # KeyError for an unknown category, as tails[...] += 1 (:231)
+                rids.append((job, rid))
+                read_bits_off.append(read_bits_off[-1] + W)
+            isos.append(isoform); iso_tint.append(tint_index[tkey]); iso_read_off.append(len(rids))
+    packed = [pack_label_bits(np.frombuffer("".join(rows).encode("ascii"), np.uint8), M).reshape(-1) for M, rows in runs if rows and M]
+    return dict(isos=isos, rids=rids, tint_pos_off=np.asarray(tint_pos_off, np.int64), pos=np.asarray(pos, np.int64),
+                iso_tint=np.asarray(iso_tint, np.int32), iso_read_off=np.asarray(iso_read_off, np.int64),
+                read_bits_off=np.asarray(read_bits_off, np.int64), bits=np.concatenate(packed) if packed else np.zeros(0, np.uint64),
+                tail=np.asarray(tail, np.uint8), N=np.diff(np.asarray(iso_read_off, np.int64)))
+
+
+def isoforms_input_bounds(jobs, inp):
+    """Second half, after read_split(): the reads' alignment boundaries.  A read the split file lacks gets none and is noted
+    in inp['missing'] = [(isoform index, rid)]: the reference's KeyError comes up only for an isoform that has exons."""
+    read_b_off, starts, ends, missing = [0], [], [], []
+    iso_of = np.repeat(np.arange(len(inp["isos"])), inp["N"]).tolist()
+    for r, (job, rid) in enumerate(inp["rids"]):
+        read = jobs[job][2][rid]
+        if "starts" in read:
+            starts.extend(read["starts"]); ends.extend(read["ends"])
+        else:
+            missing.append((iso_of[r], rid))
+        read_b_off.append(len(starts))
+    inp.update(read_b_off=np.asarray(read_b_off, np.int64), read_start=np.asarray(starts, np.int64),
+               read_end=np.asarray(ends, np.int64), missing=missing)
+    return inp
+
+
+def isoforms_input(jobs):
+    """The arrays of one Context.isoforms() call for jobs that hold their reads' boundaries already."""
+    return isoforms_input_bounds(jobs, isoforms_input_rows(jobs))
+
+
+def decide_gpu_batch(inp, majority_threshold, correction_window, ctx):
+    """isoforms_cons() and both correct_boundaries() of the batch in one device call; the isoform dicts get 'starts', 'ends'
+    and 'strand' from the result arrays.  Positions are int32 on the device: a value outside it is refused here."""
+    for k in ("pos", "read_start", "read_end"):
+        if inp[k].size and (inp[k].min() < -2 ** 31 or inp[k].max() >= 2 ** 31):
+            raise IsoformsError("%s holds a value outside int32" % k)
+    res = ctx.isoforms(inp["tint_pos_off"], inp["pos"], inp["iso_tint"], inp["iso_read_off"], inp["read_bits_off"], inp["bits"],
+                       inp["tail"], inp["read_b_off"], inp["read_start"], inp["read_end"], majority_threshold, correction_window)
+    n_exon = res["n_exon"]
+    if correction_window != 0:
+        for i, _ in inp["missing"]:
+            if n_exon[i]:
+                raise KeyError("starts")                         # reads[rid]['starts'] of a read the split file lacks (:133)
+    off = res["exon_off"]
+    for i in np.flatnonzero(n_exon).tolist():
+        isoform = inp["isos"][i]
+        a, b = int(off[i]), int(off[i]) + int(n_exon[i])
+        isoform["strand"] = chr(res["strand"][i])
+        isoform["starts"], isoform["ends"] = res["start"][a:b].tolist(), res["end"][a:b].tolist()
+    return res
+
+
 def get_gtf_records(isoforms):
     """[((chrom, first start), text)]: one transcript line and its exon lines per isoform that has exons (:72-119)."""
     records = []
@@ -280,15 +434,48 @@ def get_gtf_records(isoforms):
     return records
 
 
-def run_consensus_batch(batch_args, ctx, verbose=True):
+def _run_decide_gpu(jobs, batch_args, ctx):
+    """The --decide gpu body of run_consensus_batch(): the same steps in the same order (rows, split files, boundaries), the
+    decisions by one Context.isoforms call.  A batch the library refuses as unsupported (an isoform of more segments than
+    fiso_isoforms_limits allows) takes the host path."""
+    triples = [(j[0], j[1], j[2]) for j in jobs]
+    inp = isoforms_input_rows(triples)
+    for j in jobs:
+        read_split(j[3], j[2])
+    if not batch_args or not inp["isos"]:
+        return
+    m, w = batch_args[0][4], batch_args[0][5]
+    assert all(a[4] == m and a[5] == w for a in batch_args)
+    isoforms_input_bounds(triples, inp)
+    try:
+        decide_gpu_batch(inp, m, w, ctx)
+        decide_stats["gpu_batches"] += 1
+    except IsoformsError as e:
+        if e.code != FISO_ERR_UNSUPPORTED:
+            raise
+        decide_stats["fallback_batches"] += 1
+        isoforms_cons_batch(triples, ctx)
+        for side in ("starts", "ends"):
+            correct_boundaries_batch(side, triples, m, w, ctx)
+
+
+def run_consensus_batch(batch_args, ctx, verbose=True, decide="host"):
     """run_consensus() (:50-69) of several (contig, tint_id, cluster_tsv, split_tsv, majority_threshold,
-    correction_window) tuples that share the last two values; returns the concatenated GTF records."""
+    correction_window) tuples that share the last two values; returns the concatenated GTF records.  decide: "host" (the
+    counts and votes come back and are decided here) or "gpu" (one device call decides the batch)."""
+    assert decide in ("host", "gpu"), decide
     jobs = []
     for contig, tint_id, cluster_tsv, split_tsv, _, _ in batch_args:
         if verbose:
             print("Building isoforms for contig {}".format(contig))
         segments, reads, isoforms = read_cluster(cluster_tsv)
         jobs.append([isoforms, segments, reads, split_tsv])
+    if decide == "gpu":
+        _run_decide_gpu(jobs, batch_args, ctx)
+        out = []
+        for j in jobs:
+            out.extend(get_gtf_records(j[0]))
+        return out
     isoforms_cons_batch([(j[0], j[1], j[2]) for j in jobs], ctx)
     for j in jobs:
         read_split(j[3], j[2])
@@ -328,7 +515,7 @@ def main(argv=None):
     gtf_records = []
     try:
         for i in range(0, len(consensus_args), max(1, args.batch_tints)):
-            gtf_records.extend(run_consensus_batch(consensus_args[i:i + args.batch_tints], ctx))
+            gtf_records.extend(run_consensus_batch(consensus_args[i:i + args.batch_tints], ctx, decide=args.decide))
     finally:
         ctx.close()
     gtf_records.sort()
