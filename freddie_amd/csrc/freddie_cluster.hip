@@ -2183,7 +2183,13 @@ int fail(fclu_ctx *c, int code, const char *fmt, ...) {
 //   FCLU_BNB_WIDE_SLICE=n   bnb_wide_slice   n > 0: fclu_round_bnb_wide gives a launch n tasks (and a workgroup min(n, 8)), so that a problem crosses several launches
 //                                            (every pass of fclu_round_bnb_wide_passes)
 //   FCLU_BNB_WIDE_ITEM=n    bnb_wide_item    0 < n <= 4096: the records a workgroup of a later pass of fclu_round_bnb_wide_passes walks (kBwFromItem; profiles)
-struct Knobs { bool part_lds, prune_lds, rank, prune_edges, round_lds; i64 prune_lds_words, round_lds_bytes, exact_slice, bnb_slice, bnb_wide_slice, bnb_wide_item; unsigned hash_mask; };
+//   FCLU_GRID_CAP=n         grid_cap         n >= 1: every launch of capped_grid() takes min(its own grid, n) workgroups, so that a small batch runs the
+//                                            kernels' grid-stride loops more than once (1: one workgroup does everything)
+struct Knobs {
+    bool part_lds, prune_lds, rank, prune_edges, round_lds;
+    i64 prune_lds_words, round_lds_bytes, exact_slice, bnb_slice, bnb_wide_slice, bnb_wide_item, grid_cap;
+    unsigned hash_mask;
+};
 
 Knobs read_knobs() {
     const auto off = [](const char *name) { const char *e = getenv(name); return e && e[0] == '0'; };
@@ -2204,7 +2210,29 @@ Knobs read_knobs() {
     k.bnb_wide_item = (wi && atoll(wi) > 0 && atoll(wi) <= 4096) ? atoll(wi) : kBwFromItem;
     const char *hb = getenv("FCLU_HASH_BITS");
     k.hash_mask = (hb && hb[0] >= '0' && hb[0] <= '9' && atoi(hb) < 32) ? (1u << atoi(hb)) - 1u : 0xffffffffu;
+    const char *gc = getenv("FCLU_GRID_CAP");
+    k.grid_cap = (gc && atoll(gc) >= 1 && atoll(gc) < (1ll << 30)) ? atoll(gc) : 0;
     return k;
+}
+
+// The grids that a constant caps: the kernel walks what lies beyond its grid in a grid-stride loop (no cluster kernel waits for another
+// workgroup, so any grid from one workgroup up computes the same).  The tests read these names.
+constexpr int kCapCompat = 8192;        // k_compat: a workgroup a tile
+constexpr int kCapDegree = 4096;        // k_degree, k_deg1: a wave a row / an adjacency word column
+constexpr int kCapPrune = 16384;        // k_prune: a wave a row
+constexpr int kCapPruneEdges = 65536;   // k_prune_edges: a wave a (row, chunk)
+constexpr int kCapRowGrid = 4096;       // a thread a row: k_cc_init, k_cc_jump, k_bounds, k_chunk, k_offsets
+constexpr int kCapWaveGrid = 65536;     // a wave a row: k_cc_hook, k_pairs, k_members
+constexpr int kCapItemGrid = 4096;      // a thread an item of the dedupe: k_heads, k_leader, k_nodes, k_mem_off, k_gleader, k_greps
+constexpr int kCapSlots = 65536;        // a lane a slot: k_rows, k_gkeys, k_readout_corr
+constexpr int kCapGather = 8192;        // k_ggather: a thread a label word
+constexpr int kCapGaps = 4096;          // a thread a column, gap row or group: k_gap_keys, k_gap_heads, k_gap_groups, k_gap_fill
+
+// the workgroups of such a launch: work units at share a workgroup, at most cap, and at most FCLU_GRID_CAP where that is set
+unsigned capped_grid(i64 work, i64 share, int cap, const Knobs &k) {
+    i64 grid = std::min<i64>((work + share - 1) / share, cap);
+    if (k.grid_cap > 0) grid = std::min(grid, k.grid_cap);
+    return (unsigned)grid;
 }
 
 // One burst: kBurst passes enqueued per host round trip, pass q gated on pass q - 1's "changed something" word, so the host reads the
@@ -2386,7 +2414,7 @@ int stage_tints(fclu_ctx *c, const Knobs &k, int T, const int64_t *row_off, cons
 // partition_device(); adj_out may be null.
 int compat_run(fclu_ctx *c, const Staged &st, const Knobs &k, int32_t prune, uint64_t *adj_out, int32_t *rounds_out) {
     hipStream_t s = c->stream;
-    const int grid = st.n_tiles < 8192 ? st.n_tiles : 8192;
+    const unsigned grid = capped_grid(st.n_tiles, 1, kCapCompat, k);
     // rows of at most kRankWords words: the rank tables ride along
     const bool rank = st.max_w <= kRankWords && k.rank;
     const size_t lds = (size_t)2 * kTile * (st.max_w | 1) * (rank ? 6 : 4);
@@ -2408,7 +2436,7 @@ int compat_run(fclu_ctx *c, const Staged &st, const Knobs &k, int32_t prune, uin
         // the loop of :240-255 usually ends after two or three passes
         const i64 R = st.R;
         const int T = st.T, n_words = (int)st.word_tint.size();
-        const int deg_grid = (int)((R + 3) / 4 < 4096 ? (R + 3) / 4 : 4096);
+        const unsigned deg_grid = capped_grid(R, 4, kCapDegree, k);
         // the pass edge by edge (k_prune_edges) when every tint of the per-pass kernels has rows of at most kEdgeChunks x 64 words
         const bool edge_walk = st.max_aw_large <= kEdgeChunks * 64 && k.prune_edges;
         const int edge_chunks = (st.max_aw_large + 63) / 64 > 0 ? (st.max_aw_large + 63) / 64 : 1;
@@ -2420,12 +2448,12 @@ int compat_run(fclu_ctx *c, const Staged &st, const Knobs &k, int32_t prune, uin
             const int from = cur ^ (q & 1), to = from ^ 1;
             hipLaunchKernelGGL(k_degree, dim3(deg_grid), dim3(256), 0, s, R, c->row_tint.p, c->tints.p, c->adj[from].p, c->deg.p, gate);
             if (edge_walk)
-                hipLaunchKernelGGL(k_prune_edges, dim3((int)((R * edge_chunks + 3) / 4 < 65536 ? (R * edge_chunks + 3) / 4 : 65536)), dim3(256), 0, s, R, edge_chunks,
+                hipLaunchKernelGGL(k_prune_edges, dim3(capped_grid(R * edge_chunks, 4, kCapPruneEdges, k)), dim3(256), 0, s, R, edge_chunks,
                                    c->row_tint.p, c->tints.p, c->adj[from].p, c->deg.p, c->adj[to].p, d_changed + (size_t)q * T, any, gate);
             else {
-                hipLaunchKernelGGL(k_deg1, dim3((n_words + 3) / 4 < 4096 ? (n_words + 3) / 4 : 4096), dim3(256), 0, s, n_words, c->word_tint.p, c->tints.p,
+                hipLaunchKernelGGL(k_deg1, dim3(capped_grid(n_words, 4, kCapDegree, k)), dim3(256), 0, s, n_words, c->word_tint.p, c->tints.p,
                                    c->deg.p, c->deg1.p, gate);
-                hipLaunchKernelGGL(k_prune, dim3((int)((R + 3) / 4 < 16384 ? (R + 3) / 4 : 16384)), dim3(256), 0, s, R, c->row_tint.p, c->tints.p, c->tint_word0.p,
+                hipLaunchKernelGGL(k_prune, dim3(capped_grid(R, 4, kCapPrune, k)), dim3(256), 0, s, R, c->row_tint.p, c->tints.p, c->tint_word0.p,
                                    c->adj[from].p, c->deg.p, c->deg1.p, c->adj[to].p, d_changed + (size_t)q * T, any, gate);
             }
         };
@@ -2546,7 +2574,7 @@ int part_empty(fclu_ctx *c, int T) {
 }
 
 // The work arrays, the members' upload (mem_off null: on the device already) and the connected components: c->parent behind it.
-int part_components(fclu_ctx *c, PartRun &p, const int64_t *mem_off, const int32_t *mem) {
+int part_components(fclu_ctx *c, const Knobs &k, PartRun &p, const int64_t *mem_off, const int32_t *mem) {
     hipStream_t s = c->stream;
     const i64 R = p.R;
     std::vector<int> small;
@@ -2577,7 +2605,7 @@ int part_components(fclu_ctx *c, PartRun &p, const int64_t *mem_off, const int32
     }
     if (!small.empty()) HIP_TRY(c, hipMemcpyAsync(c->small_tints.p, small.data(), c->small_tints.bytes(small.size()), hipMemcpyHostToDevice, s));
 
-    p.row_grid = (int)std::min<i64>((R + 256) / 256, 4096); p.wave_grid = (int)std::min<i64>((R + 3) / 4, 65536);
+    p.row_grid = (int)capped_grid(R + 1, 256, kCapRowGrid, k); p.wave_grid = (int)capped_grid(R, 4, kCapWaveGrid, k);    // (k_chunk: R + 1 entries)
     const u64 *d_adj = c->adj[c->adj_cur].p;
     HIP_TRY(c, hipEventRecord(c->pev[0], s));
     hipLaunchKernelGGL(k_cc_init, dim3(p.row_grid), dim3(256), 0, s, R, c->parent.p);
@@ -2600,7 +2628,7 @@ int part_components(fclu_ctx *c, PartRun &p, const int64_t *mem_off, const int32
 }
 
 // The even split, the members' positions and the pair counts: behind it p.P and p.n_pairs, the call's totals.
-int part_split(fclu_ctx *c, PartRun &p) {
+int part_split(fclu_ctx *c, const Knobs &k, PartRun &p) {
     hipStream_t s = c->stream;
     const i64 R = p.R;
     const size_t R1 = (size_t)R + 1;
@@ -2622,7 +2650,7 @@ int part_split(fclu_ctx *c, PartRun &p) {
     sb = p.scan_bytes;
     HIP_TRY(c, rocprim::exclusive_scan(c->tmp.p, sb, c->cnt.p, c->pair_base.p, (i64)0, R1, rocprim::plus<i64>(), s));
     const i64 RT = std::max<i64>(R, p.T);
-    hipLaunchKernelGGL(k_offsets, dim3((int)std::min<i64>((RT + 256) / 256, 4096)), dim3(256), 0, s, R, p.T, c->tints.p, c->head.p, c->part_id.p, c->rid_pos.p,
+    hipLaunchKernelGGL(k_offsets, dim3(capped_grid(RT + 1, 256, kCapRowGrid, k)), dim3(256), 0, s, R, p.T, c->tints.p, c->head.p, c->part_id.p, c->rid_pos.p,
                        c->pair_base.p, c->d_tint_part_off.p, c->d_part_node_off.p, c->d_part_rid_off.p, c->d_part_pair_off.p);
     HIP_TRY(c, hipMemcpyAsync(c->h_tot.p, c->part_id.p + R, c->h_tot.bytes(1), hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipMemcpyAsync(c->h_tot.p + 1, c->pair_base.p + R, c->h_tot.bytes(1), hipMemcpyDeviceToHost, s));
@@ -2657,15 +2685,15 @@ int part_emit(fclu_ctx *c, const PartRun &p) {
 
 // c->tints / c->h_tints / c->row_tint describe the batch and c->adj[c->adj_cur] holds its pruned matrices.  mem_off null: the members
 // are on the device already (c->mem_off, c->mem: n_mem_device rep ids), where the dedupe left them.
-int partition_device(fclu_ctx *c, int T, i64 R, const int64_t *mem_off, const int32_t *mem, i64 n_mem_device, int32_t maximum_ilp_size) {
+int partition_device(fclu_ctx *c, const Knobs &k, int T, i64 R, const int64_t *mem_off, const int32_t *mem, i64 n_mem_device, int32_t maximum_ilp_size) {
     HIP_TRY(c, hipSetDevice(c->device));
     c->components_ms = c->pairs_ms = 0.f;
     if (R == 0) RC_TRY(part_empty(c, T));
     else {
         PartRun p;
         p.T = T; p.R = R; p.max_size = maximum_ilp_size; p.n_mem = mem_off ? mem_off[R] : n_mem_device;
-        RC_TRY(part_components(c, p, mem_off, mem));
-        RC_TRY(part_split(c, p));
+        RC_TRY(part_components(c, k, p, mem_off, mem));
+        RC_TRY(part_split(c, k, p));
         RC_TRY(part_emit(c, p));
     }
     c->have_parts = true;
@@ -2674,7 +2702,7 @@ int partition_device(fclu_ctx *c, int T, i64 R, const int64_t *mem_off, const in
 
 // ---- the dedupe, once for its two users: reps -> nodes (prep_rows, prep_nodes) and reads -> reps (group_device) ----------------
 // An item is a rep there and a read here, a class a node and a rep.  The scratch is c->dd (see fclu_ctx).
-int item_grid(i64 n) { return (int)std::min<i64>((n + 255) / 256, 4096); }
+unsigned item_grid(i64 n, const Knobs &k) { return capped_grid(n, 256, kCapItemGrid, k); }
 
 // rocPRIM's stable sort of (key, value) pairs by the keys' low bits, tmp its temporary storage; need: no sort, only what it takes of tmp
 template <typename K>
@@ -2729,7 +2757,8 @@ int describe_rows(fclu_ctx *c, const char *entry, const char *noun, int T, const
 // the caller's needs no count from the host.  ev[0], ev[1]: around the key kernel; ev[2]: behind launch_offsets.  dd.id = the exclusive
 // scan of flag is the classes' numbering (N + 1 entries); behind the call, report_row_errors() says what dd.h_err holds.
 template <typename K, typename L, typename O>
-int dedupe_classes(fclu_ctx *c, int T, i64 N, hipEvent_t *ev, K &&launch_keys, L &&launch_leader, O &&launch_offsets, const i64 *d_off, int64_t *h_off) {
+int dedupe_classes(fclu_ctx *c, const Knobs &k, int T, i64 N, hipEvent_t *ev, K &&launch_keys, L &&launch_leader, O &&launch_offsets, const i64 *d_off,
+                   int64_t *h_off) {
     hipStream_t s = c->stream;
     auto &D = c->dd;
     const size_t n = (size_t)N, N1 = n + 1;
@@ -2751,7 +2780,7 @@ int dedupe_classes(fclu_ctx *c, int T, i64 N, hipEvent_t *ev, K &&launch_keys, L
     // refusals first: a tail above 2 or a label 3 has no meaning, and the sort's keys of such a batch are not needed
     HIP_TRY(c, hipMemcpyAsync(D.h_err.p, D.err.p, D.err.bytes(4), hipMemcpyDeviceToHost, s));
     RC_TRY(sort_pairs(c, D.tmp, nullptr, D.key.p, D.skey.p, D.val.p, D.sval.p, n, key_bits));
-    hipLaunchKernelGGL(k_heads, dim3(item_grid(N)), dim3(256), 0, s, N, D.skey.p, D.head.p);
+    hipLaunchKernelGGL(k_heads, dim3(item_grid(N, k)), dim3(256), 0, s, N, D.skey.p, D.head.p);
     size_t tb = D.tmp.cap;
     HIP_TRY(c, rocprim::inclusive_scan(D.tmp.p, tb, D.head.p, D.bstart.p, n, rocprim::maximum<int>(), s));
     launch_leader();
@@ -2767,10 +2796,10 @@ int dedupe_classes(fclu_ctx *c, int T, i64 N, hipEvent_t *ev, K &&launch_keys, L
 
 // The classes' member lists, behind the caller's numbering kernel (dd.nkey: an item's class, dd.nval: the item within its tint): the items
 // sorted (stable) by class are the lists end to end, each ascending (mem); class q's starts where its key first stands (mem_off).
-int dedupe_members(fclu_ctx *c, i64 N, i64 n_classes, int *mem, i64 *mem_off) {
+int dedupe_members(fclu_ctx *c, const Knobs &k, i64 N, i64 n_classes, int *mem, i64 *mem_off) {
     auto &D = c->dd;
     RC_TRY(sort_pairs(c, D.tmp, nullptr, D.nkey.p, D.snkey.p, D.nval.p, mem, (size_t)N, (unsigned)bits_for(N)));
-    hipLaunchKernelGGL(k_mem_off, dim3(item_grid(N + 1)), dim3(256), 0, c->stream, N, n_classes, D.snkey.p, mem_off);      // (k <= N)
+    hipLaunchKernelGGL(k_mem_off, dim3(item_grid(N + 1, k)), dim3(256), 0, c->stream, N, n_classes, D.snkey.p, mem_off);   // (N + 1 entries)
     return FCLU_OK;
 }
 
@@ -2833,17 +2862,17 @@ int prep_rows(fclu_ctx *c, const Knobs &k, const fclu_reads *rd, bool on_device,
             HIP_TRY(c, hipMemcpyAsync(D.tail.p, rd->tail, D.tail.bytes((size_t)N), hipMemcpyHostToDevice, s));
         }
         const auto keys = [&]() {
-            hipLaunchKernelGGL(k_rows, dim3((unsigned)std::min<i64>((n_slots + 255) / 256, 65536)), dim3(256), 0, s, T, n_slots, D.tints.p, D.labels.p, D.tail.p,
+            hipLaunchKernelGGL(k_rows, dim3(capped_grid(n_slots, 256, kCapSlots, k)), dim3(256), 0, s, T, n_slots, D.tints.p, D.labels.p, D.tail.p,
                                k.hash_mask, D.ibits.p, D.cbits.p, D.rfirst.p, D.rlast.p, D.first.p, D.last.p, D.rep_tint.p, S.key.p, S.val.p, S.err.p);
         };
         const auto leader = [&]() {
-            hipLaunchKernelGGL(k_leader, dim3(item_grid(N)), dim3(256), 0, s, N, S.skey.p, S.sval.p, S.bstart.p, D.tints.p, D.ibits.p, D.first.p, D.last.p,
+            hipLaunchKernelGGL(k_leader, dim3(item_grid(N, k)), dim3(256), 0, s, N, S.skey.p, S.sval.p, S.bstart.p, D.tints.p, D.ibits.p, D.first.p, D.last.p,
                                D.tail.p, S.leader.p, S.flag.p);
         };
         const auto offsets = [&]() {
             hipLaunchKernelGGL(k_class_off<PrepTint>, dim3((unsigned)(T + 256) / 256), dim3(256), 0, s, T, N, D.tints.p, S.id.p, D.row_off.p);
         };
-        RC_TRY(dedupe_classes(c, T, N, c->qev, keys, leader, offsets, D.row_off.p, h_row_off));
+        RC_TRY(dedupe_classes(c, k, T, N, c->qev, keys, leader, offsets, D.row_off.p, h_row_off));
         RC_TRY(report_row_errors(c, "rep", T, rd->rep_off, rd->n_seg, on_device ? nullptr : rd->tail));
     } else {
         memset(h_row_off, 0, H.row_off.bytes((size_t)T + 1));
@@ -2862,7 +2891,7 @@ int prep_rows(fclu_ctx *c, const Knobs &k, const fclu_reads *rd, bool on_device,
 
 // The nodes behind stage_tints(): c->bits / first / last / tail hold them in fclu_batch's layout, c->mem_off / c->mem their members, and
 // the pinned copies of everything fclu_prep names are on their way (the caller synchronises).
-int prep_nodes(fclu_ctx *c, const PrepRun &p) {
+int prep_nodes(fclu_ctx *c, const Knobs &k, const PrepRun &p) {
     hipStream_t s = c->stream;
     auto &D = c->pd;
     auto &H = c->ph;
@@ -2872,9 +2901,9 @@ int prep_nodes(fclu_ctx *c, const PrepRun &p) {
         auto &S = c->dd;
         HIP_TRY(c, c->mem_off.grow((size_t)R + 1));
         HIP_TRY(c, hipEventRecord(c->qev[3], s));
-        hipLaunchKernelGGL(k_nodes, dim3(item_grid(N + 1)), dim3(256), 0, s, N, D.rep_tint.p, D.tints.p, c->tints.p, S.leader.p, S.id.p, D.ibits.p, D.first.p,
+        hipLaunchKernelGGL(k_nodes, dim3(item_grid(N + 1, k)), dim3(256), 0, s, N, D.rep_tint.p, D.tints.p, c->tints.p, S.leader.p, S.id.p, D.ibits.p, D.first.p,
                            D.last.p, D.tail.p, D.rep_node.p, S.nkey.p, S.nval.p, D.node_rep.p, c->bits.p, c->first.p, c->last.p, c->tail.p);
-        RC_TRY(dedupe_members(c, N, R, c->mem.p, c->mem_off.p));
+        RC_TRY(dedupe_members(c, k, N, R, c->mem.p, c->mem_off.p));
         HIP_TRY(c, hipEventRecord(c->qev[4], s));
     }
     // the result set: {pinned buffer, device source, element count, fclu_prep's field}
@@ -2909,7 +2938,7 @@ int preprocess_device(fclu_ctx *c, const Knobs &k, const fclu_reads *rd, int32_t
     RC_TRY(prep_rows(c, k, rd, on_device, p));
     n_reps_out = p.N;
     RC_TRY(stage_tints(c, k, p.T, c->ph.row_off.p, rd->n_seg, c->ph.bits_off.p, c->ph.adj_off.p, prune, nullptr, st));
-    return prep_nodes(c, p);
+    return prep_nodes(c, k, p);
 }
 
 // the kernels' times of the call that has just synchronised
@@ -2967,19 +2996,19 @@ int group_device(fclu_ctx *c, const Knobs &k, const fclu_segment *in, bool gathe
         if (n_tok) HIP_TRY(c, hipMemcpyAsync(D.tok.p, in->tok, D.tok.bytes((size_t)n_tok), hipMemcpyHostToDevice, s));
         else HIP_TRY(c, hipMemsetAsync(D.tok.p, 0, D.tok.bytes(1), s));
         const auto keys = [&]() {
-            hipLaunchKernelGGL(k_gkeys, dim3((unsigned)std::min<i64>((n_slots + 255) / 256, 65536)), dim3(256), 0, s, T, n_slots, D.tints.p, D.labels.p, D.tok_off.p,
+            hipLaunchKernelGGL(k_gkeys, dim3(capped_grid(n_slots, 256, kCapSlots, k)), dim3(256), 0, s, T, n_slots, D.tints.p, D.labels.p, D.tok_off.p,
                                D.tok.p, D.tail.p, k.hash_mask, D.read_tint.p, S.key.p, S.val.p, S.err.p);
         };
         const auto leader = [&]() {
-            hipLaunchKernelGGL(k_gleader, dim3(item_grid(N)), dim3(256), 0, s, N, S.skey.p, S.sval.p, S.bstart.p, D.tints.p, D.labels.p, D.tok_off.p, D.tok.p,
+            hipLaunchKernelGGL(k_gleader, dim3(item_grid(N, k)), dim3(256), 0, s, N, S.skey.p, S.sval.p, S.bstart.p, D.tints.p, D.labels.p, D.tok_off.p, D.tok.p,
                                std::max<i64>(n_tok, 1), S.leader.p, S.flag.p);
         };
         const auto offsets = [&]() {                         // (the numbering needs no count from the host: in front of the synchronisation)
             hipLaunchKernelGGL(k_class_off<GroupTint>, dim3((unsigned)(T + 256) / 256), dim3(256), 0, s, T, N, D.tints.p, S.id.p, D.rep_off.p);
-            hipLaunchKernelGGL(k_greps, dim3(item_grid(N)), dim3(256), 0, s, N, D.read_tint.p, D.tints.p, S.leader.p, S.id.p, D.read_rep.p, S.nkey.p, S.nval.p,
+            hipLaunchKernelGGL(k_greps, dim3(item_grid(N, k)), dim3(256), 0, s, N, D.read_tint.p, D.tints.p, S.leader.p, S.id.p, D.read_rep.p, S.nkey.p, S.nval.p,
                                D.rep_first.p);
         };
-        RC_TRY(dedupe_classes(c, T, N, c->gev, keys, leader, offsets, D.rep_off.p, h_rep_off));
+        RC_TRY(dedupe_classes(c, k, T, N, c->gev, keys, leader, offsets, D.rep_off.p, h_rep_off));
         RC_TRY(report_row_errors(c, "read", T, in->read_off, in->n_seg, in->tail));
         // ---- the reps' rows as fclu_reads: their layout from the tints' rep counts
         h_rep_lab_off[0] = 0;
@@ -2995,9 +3024,9 @@ int group_device(fclu_ctx *c, const Knobs &k, const fclu_segment *in, bool gathe
             HIP_TRY(c, hipMemcpyAsync(D.rep_lab_off.p, h_rep_lab_off, D.rep_lab_off.bytes((size_t)T + 1), hipMemcpyHostToDevice, s));
         }
         HIP_TRY(c, hipEventRecord(c->gev[3], s));
-        RC_TRY(dedupe_members(c, N, n_reps, D.mem.p, D.mem_off.p));
+        RC_TRY(dedupe_members(c, k, N, n_reps, D.mem.p, D.mem_off.p));
         if (gather)
-            hipLaunchKernelGGL(k_ggather, dim3((unsigned)std::min<i64>((n_rep_lab + 255) / 256, 8192)), dim3(256), 0, s, T, n_rep_lab, D.tints.p, D.rep_off.p,
+            hipLaunchKernelGGL(k_ggather, dim3(capped_grid(n_rep_lab, 256, kCapGather, k)), dim3(256), 0, s, T, n_rep_lab, D.tints.p, D.rep_off.p,
                                D.rep_lab_off.p, D.rep_first.p, D.labels.p, D.tail.p, c->pd.labels.p, c->pd.tail.p);
         HIP_TRY(c, hipEventRecord(c->gev[4], s));
     } else {
@@ -3212,9 +3241,9 @@ int round_device(fclu_ctx *c, const Knobs &k, const fclu_round_batch *b, bool re
     HIP_TRY(c, rocprim::exclusive_scan(D.tmp.p, tb, D.cnt.p, D.scan.p, (i64)0, nCnt, rocprim::plus<i64>(), s));
     HIP_TRY(c, hipEventRecord(c->rev[1], s));
     // ---- the gap groups
-    const int row_grid = (int)std::min<i64>((std::max<i64>(G, P) + 256) / 256, 4096);
+    const unsigned row_grid = capped_grid(std::max<i64>(G, P) + 1, 256, kCapGaps, k);       // (k_gap_groups: P + 1 offsets)
     if (G) {
-        hipLaunchKernelGGL(k_gap_keys, dim3((unsigned)std::min<i64>((C + 255) / 256, 4096)), dim3(256), 0, s, C, D.col_prob.p, D.probs.p, D.rids.p, D.gap_off.p,
+        hipLaunchKernelGGL(k_gap_keys, dim3(capped_grid(C, 256, kCapGaps, k)), dim3(256), 0, s, C, D.col_prob.p, D.probs.p, D.rids.p, D.gap_off.p,
                            D.gaps.p, D.col_row_off.p, D.key.p, D.val.p, D.rows.p);
         RC_TRY(sort_pairs(c, D.tmp, nullptr, D.key.p, D.skey.p, D.val.p, D.sval.p, nG, key_bits));
         hipLaunchKernelGGL(k_gap_heads, dim3(row_grid), dim3(256), 0, s, G, D.skey.p, D.head.p);
@@ -3244,7 +3273,7 @@ int round_device(fclu_ctx *c, const Knobs &k, const fclu_round_batch *b, bool re
     HIP_TRY(c, hipEventRecord(c->rev[3], s));
     round_launch<true>(c, r);
     if (n_grp)
-        hipLaunchKernelGGL(k_gap_fill, dim3((unsigned)std::min<i64>((n_grp + 255) / 256, 4096)), dim3(256), 0, s, D.gid.p, G, D.grp.p, D.grp_prob.p, D.grp_seg_off.p,
+        hipLaunchKernelGGL(k_gap_fill, dim3(capped_grid(n_grp, 256, kCapGaps, k)), dim3(256), 0, s, D.gid.p, G, D.grp.p, D.grp_prob.p, D.grp_seg_off.p,
                            D.probs.p, D.inf_bits.p, D.seg_len.p, D.grp_seg.p, D.grp_len.p);
     HIP_TRY(c, hipEventRecord(c->rev[4], s));
     fclu_rounds &o = c->rounds;
@@ -3847,7 +3876,7 @@ int bnb_wide_device(fclu_ctx *c, const Knobs &k, const int32_t *g2, const int64_
 
 // ---- the read-out of the last round's accepted sets (fclu_round_readout) --------------------------------------------------------
 // Every refusal is the host's, before any launch: the kernels get sets that are inside their problems, and clamp what they read all the same.
-int readout_device(fclu_ctx *c, const int64_t *sel_off, const int32_t *sel) {
+int readout_device(fclu_ctx *c, const Knobs &k, const int64_t *sel_off, const int32_t *sel) {
     c->have_readout = false;
     c->oexon_ms = c->ocorr_ms = 0.f;
     c->paths[FCLU_PATH_READOUT_SETS] = c->paths[FCLU_PATH_READOUT_MEMBERS] = c->paths[FCLU_PATH_READOUT_STORES] = 0;
@@ -3917,7 +3946,7 @@ int readout_device(fclu_ctx *c, const int64_t *sel_off, const int32_t *sel) {
         hipLaunchKernelGGL(k_readout_exons, dim3((unsigned)nS), dim3(256), 0, s, D.probs.p, c->rd.rids.p, D.sel.p, c->pd.ibits.p, c->rd.inf_bits.p, D.ex_bits.p, D.exons.p,
                            D.e.p);
         HIP_TRY(c, hipEventRecord(c->oev[1], s));
-        hipLaunchKernelGGL(k_readout_corr, dim3((unsigned)std::min<i64>((n_slots + 255) / 256, 65536)), dim3(256), 0, s, (int)nS, n_slots, D.probs.p, c->rd.rids.p, D.sel.p,
+        hipLaunchKernelGGL(k_readout_corr, dim3(capped_grid(n_slots, 256, kCapSlots, k)), dim3(256), 0, s, (int)nS, n_slots, D.probs.p, c->rd.rids.p, D.sel.p,
                            c->pd.labels.p, c->pd.cbits.p, c->rd.inf_bits.p, D.ex_bits.p, D.corr.p);
         HIP_TRY(c, hipEventRecord(c->oev[2], s));
         if (n_exon) HIP_TRY(c, hipMemcpyAsync(H.exons.p, D.exons.p, (size_t)n_exon, hipMemcpyDeviceToHost, s));
@@ -4005,8 +4034,9 @@ int fclu_partition(fclu_ctx *c, const fclu_batch *b, const int64_t *mem_off, con
     c->round_src_ok = c->round_ready = c->have_rounds = false;
     if (b->n_tint <= 0) return fail(c, FCLU_ERR_ARG, "fclu_partition: empty batch");
     RC_TRY(check_members(c, b->row_off[b->n_tint], mem_off, mem, maximum_ilp_size));
-    RC_TRY(compat_device(c, read_knobs(), b, 1, nullptr, nullptr));
-    return partition_device(c, b->n_tint, b->row_off[b->n_tint], mem_off, mem, 0, maximum_ilp_size);
+    const Knobs k = read_knobs();
+    RC_TRY(compat_device(c, k, b, 1, nullptr, nullptr));
+    return partition_device(c, k, b->n_tint, b->row_off[b->n_tint], mem_off, mem, 0, maximum_ilp_size);
 }
 
 int fclu_partition_adj(fclu_ctx *c, int32_t n_tint, const int64_t *row_off, const int64_t *adj_off, const uint64_t *adj,
@@ -4044,7 +4074,7 @@ int fclu_partition_adj(fclu_ctx *c, int32_t n_tint, const int64_t *row_off, cons
         if (n_adj) HIP_TRY(c, hipMemcpyAsync(c->adj[0].p, adj, c->adj[0].bytes((size_t)n_adj), hipMemcpyHostToDevice, s));
         HIP_TRY(c, hipStreamSynchronize(s));              // (the host vectors go out of scope)
     }
-    return partition_device(c, T, R, mem_off, mem, 0, maximum_ilp_size);
+    return partition_device(c, k, T, R, mem_off, mem, 0, maximum_ilp_size);
 }
 
 int fclu_partition_results(fclu_ctx *c, fclu_parts *out) {
@@ -4083,7 +4113,7 @@ int fclu_partition_reads(fclu_ctx *c, const fclu_reads *reads, int32_t maximum_i
     else HIP_TRY(c, hipStreamSynchronize(c->stream));
     preprocess_times(c, n_reps);
     c->have_prep = true;
-    RC_TRY(partition_device(c, reads->n_tint, st.R, nullptr, nullptr, n_reps, maximum_ilp_size));
+    RC_TRY(partition_device(c, k, reads->n_tint, st.R, nullptr, nullptr, n_reps, maximum_ilp_size));
     round_source(c, reads);
     return FCLU_OK;
 }
@@ -4122,7 +4152,7 @@ int fclu_partition_segment(fclu_ctx *c, const fclu_segment *in, int32_t maximum_
         else HIP_TRY(c, hipStreamSynchronize(c->stream));
         preprocess_times(c, n_reps);
         c->have_prep = true;
-        return partition_device(c, in->n_tint, st.R, nullptr, nullptr, n_reps, maximum_ilp_size);
+        return partition_device(c, k, in->n_tint, st.R, nullptr, nullptr, n_reps, maximum_ilp_size);
     }();
     if (rc != FCLU_OK) c->have_groups = c->have_prep = false;
     else round_source(c, &rd);
@@ -4220,7 +4250,7 @@ int fclu_round_bnb_wide_timing(fclu_ctx *c, float *prep_ms, float *search_ms, fl
     return c ? three_times(prep_ms, c->wprep_ms, search_ms, c->wsearch_ms, longest_launch_ms, c->wlongest_ms) : FCLU_ERR_ARG;
 }
 
-int fclu_round_readout(fclu_ctx *c, const int64_t *sel_off, const int32_t *sel) { return c ? readout_device(c, sel_off, sel) : FCLU_ERR_ARG; }
+int fclu_round_readout(fclu_ctx *c, const int64_t *sel_off, const int32_t *sel) { return c ? readout_device(c, read_knobs(), sel_off, sel) : FCLU_ERR_ARG; }
 
 int fclu_round_readout_results(fclu_ctx *c, fclu_readout *out) {
     if (!c || !out) return FCLU_ERR_ARG;

@@ -72,7 +72,9 @@ typedef struct fclu_batch {
 } fclu_batch;
 
 /* Compatibility graph of every tint of the batch.  adj_out: adj_off[n_tint] uint64 words (caller-owned).
- * rounds_out (may be NULL): per tint, the number of pruning passes that removed at least one edge. */
+ * rounds_out (may be NULL): per tint, the number of pruning passes that removed at least one edge.
+ * FCLU_GRID_CAP=<n> (read at every call that launches kernels; tests): the launches whose grid a constant caps take at most n
+ * workgroups, so that a small batch runs their grid-stride loops more than once; the results do not depend on it. */
 int fclu_compat_graph(fclu_ctx *c, const fclu_batch *b, int32_t prune, uint64_t *adj_out, int32_t *rounds_out);
 
 /* Duration of the kernels of the last fclu_compat_graph() call, from HIP events on the library's stream (ms). */

@@ -80,6 +80,15 @@ def test_partition_reads_on_random_tints_against_the_reference(ctx):
             assert cu.canon_partitions(t) == parts, "seed %d, maximum_ilp_size %s" % (case["seed"], size)
 
 
+def batched_tints():
+    """The batch of test_random_tints_batched (and of the grid tests): every tile edge, a dense and a sparse graph."""
+    shapes = [(1, 5), (2, 1), (63, 31), (64, 32), (65, 33), (130, 64), (200, 65), (257, 100), (40, 300)]
+    tints = [cu.random_tint(100 + k, n, m) for k, (n, m) in enumerate(shapes)]
+    tints.append(cu.random_tint(200, 150, 20, n_isoforms=2, noise=0.0, tail_p=0.0))      # dense graph: heavy pruning input
+    tints.append(cu.random_tint(201, 120, 24, n_isoforms=12, noise=0.1, tail_p=0.6))     # sparse graph, many tails
+    return tints
+
+
 @pytest.mark.parametrize("rank_switch,prune_lds", [("1", "1"), ("0", "1"), ("1", "0"), ("1", "0,edges=0"), ("1", "words=300")],
                          ids=["rank-tables", "masked-sums", "per-pass-edge-walk", "per-pass-or-of-rows", "both-prunings-in-one-batch"])
 def test_random_tints_batched(ctx, rank_switch, prune_lds, monkeypatch):
@@ -94,10 +103,7 @@ def test_random_tints_batched(ctx, rank_switch, prune_lds, monkeypatch):
         monkeypatch.setenv("FCLU_PRUNE_LDS", prune_lds[0])
         if prune_lds.endswith("edges=0"):
             monkeypatch.setenv("FCLU_PRUNE_EDGES", "0")             # the per-pass kernels' older form: OR of the neighbours' rows
-    shapes = [(1, 5), (2, 1), (63, 31), (64, 32), (65, 33), (130, 64), (200, 65), (257, 100), (40, 300)]
-    tints = [cu.random_tint(100 + k, n, m) for k, (n, m) in enumerate(shapes)]
-    tints.append(cu.random_tint(200, 150, 20, n_isoforms=2, noise=0.0, tail_p=0.0))      # dense graph: heavy pruning input
-    tints.append(cu.random_tint(201, 120, 24, n_isoforms=12, noise=0.1, tail_p=0.6))     # sparse graph, many tails
+    tints = batched_tints()
     check_graphs(ctx, tints)
     want = copy.deepcopy(tints)
     for t in want:

@@ -106,10 +106,8 @@ def check_arrays(arr, t, row0, A, mult, labels, parts, what):
         assert np.array_equal(arr["pairs"][arr["part_pair_off"][q]:arr["part_pair_off"][q + 1]], np.asarray(pairs, np.int32).reshape(-1, 2)), what + ": pairs"
 
 
-@PATHS
-@pytest.mark.parametrize("size", [1, 2, 7, 64, 65, 1000])
-def test_crafted_graphs(ctx, size, part_lds, monkeypatch):
-    set_path(monkeypatch, part_lds)
+def check_crafted(ctx, size):
+    """crafted_batch() through partition_adj under maximum_ilp_size = size, against crafted_expected(size)."""
     mats, per_tint, members, (row_off, adj_off, adj) = crafted_batch()
     arr = ctx.partition_adj(row_off, adj_off, adj, members, size)
     assert arr["tint_part_off"][0] == 0 and arr["tint_part_off"][-1] == len(arr["part_node_off"]) - 1
@@ -124,6 +122,13 @@ def test_crafted_graphs(ctx, size, part_lds, monkeypatch):
         check_arrays(arr, t, r0, A, mult[r0:r0 + A.shape[0]], labels, parts, "%s of %d nodes, maximum_ilp_size %d" % (kinds[t] + (size,)))
     e = len(mats) // 2
     assert mats[e].shape[0] == 0 and arr["tint_part_off"][e] == arr["tint_part_off"][e + 1]     # the empty tint: no partition
+
+
+@PATHS
+@pytest.mark.parametrize("size", [1, 2, 7, 64, 65, 1000])
+def test_crafted_graphs(ctx, size, part_lds, monkeypatch):
+    set_path(monkeypatch, part_lds)
+    check_crafted(ctx, size)
 
 
 # ---- 3: a tint beyond one workgroup's LDS ---------------------------------------------------------------------------------

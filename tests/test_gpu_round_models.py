@@ -208,15 +208,20 @@ def big_tint(tid, n, M, seed):
     return ru.make_tint(tid, rows, gaps)
 
 
-def test_batch_of_both_paths_and_two_rounds(ctx, monkeypatch):
-    """300 small problems and one of 1 500 reps in one call (rows in LDS, rows in device memory); then round r + 1 on the same context
-    with other remaining sets; then everything again with the LDS path off and with a low LDS limit."""
-    rng = random.Random(2)
+def small_tints(rng, n):
+    """n tints of three to eight reps with gaps and tails, their segment counts around the word boundaries."""
     tints = []
-    for t in range(300):
+    for t in range(n):
         M = rng.choice([5, 31, 32, 33, 64, 65, 90])
         rows = ru.random_rows(rng, rng.randrange(3, 9), M)
         tints.append(ru.make_tint(t, rows, *ru.random_gaps(rng, rows)))
+    return tints
+
+
+def test_batch_of_both_paths_and_two_rounds(ctx, monkeypatch):
+    """300 small problems and one of 1 500 reps in one call (rows in LDS, rows in device memory); then round r + 1 on the same context
+    with other remaining sets; then everything again with the LDS path off and with a low LDS limit."""
+    tints = small_tints(random.Random(2), 300)
     tints.append(big_tint(300, 1500, 70, 9))
     part0 = stage(ctx, tints)
     assert max(len(rids) for rids, _ in tints[300]["partitions"]) == 1500
