@@ -27,7 +27,8 @@ CSRC = os.path.join(_HERE, "csrc")
 # (k_solve's three size classes are a unit each: the kernel is most of the build time -- 71 s as one file, ~25 s now on 8 cores).
 SEG_UNITS = ["freddie_seg", "seg_front", "seg_problems", "seg_score_arena", "seg_score_fused", "seg_solve16", "seg_solve32", "seg_solve60",
              "seg_tail", "seg_upload", "seg_annotate", "freddie_seg_sort"]
-SEG_HEADERS = [os.path.join(CSRC, h) for h in ("seg_common.h", "seg_kernels.h", "seg_solve.h", "seg_score_plan.h")]
+SEG_HEADERS = [os.path.join(CSRC, h) for h in ("seg_common.h", "seg_kernels.h", "seg_solve.h", "seg_score_plan.h", "seg_upload_plan.h",
+                                                     "seg_run_react.h")]
 SEG_SRC = [os.path.join(CSRC, u + ".hip") for u in SEG_UNITS] + SEG_HEADERS
 SEG_OBJ_DIR = os.path.join(CSRC, ".obj")
 HOST_SO = os.path.join(_HERE, "libfreddie_host.so")

@@ -105,6 +105,41 @@ enum : unsigned {
 hipError_t fseg_sort_pairs(void *tmp, size_t *tmp_bytes, const unsigned long long *keys_in, unsigned long long *keys_out,
                            const int *vals_in, int *vals_out, size_t n, unsigned end_bit, hipStream_t stream);   // freddie_seg_sort.hip
 
+// The host values that shape what enqueue_run launches and that the context changes between two runs of one batch: a captured
+// graph has them baked in, so it is valid for exactly the shape it was captured under (run_impl compares `shape` with the copy
+// kept beside the graph and recaptures when they differ; nobody drops a graph because one of these changed).  What else a
+// capture bakes in -- slab and arena pointers, capacities, parameters -- changes only where a resource's life ends, and those
+// places drop the graph themselves (alloc_arenas, fseg_upload, fseg_set_params).  Each member names its reader in Run / seg_*.
+// Compared as bytes: no padding (the static_assert), so the members are ordered by size and the tail is filled by hand.
+struct LaunchShape {
+    // what the lists of the resident batch hold (read from the status record; exact once the batch has run or been sized):
+    // launches over an empty list are skipped (score_facts)
+    i64 n_solve[3] = {0, 0, 0}, n_cls_work[4] = {0, 0, 0, 0}, n_arena_prob = 0, n_tiny = 0;
+    i64 n_wide[3] = {0, 0, 0};  // of n_solve: problems that need the 16-bit-counter instances
+    i64 scan_single_max = 512;  // scan blocks up to which the compactions use the single-pass look-back scan (FSEG_SCAN_SINGLE_MAX; Run::scan_single)
+    const void *d_labels = nullptr, *d_packed = nullptr;    // the label arenas' allocations as of this run (launch_dp, seg_post2)
+    int nm_big = kNMax;         // LDS carve-up of the big-problem kernels: largest problem of the batch, rounded up (nm_of)
+    int nm_giant = 0;           // a problem with more than kNHuge candidates: its size (rounded up: the LDS carve-up and scratch piece of the giant kernels); 0: none
+    bool counts_known = false;  // the list sizes above are this batch's (score_facts)
+    bool small_batch = false;   // one stream, one launch per stage over all classes (would_fork, score_facts)
+    bool tiny_on = false;       // many problems (> tiny_from): problems with <= kTiny candidates go to k_tiny (Run::split)
+    bool fuse_on = true;        // this batch's problems go to k_solve: decided per batch -- when its widest problem sees at most
+                                // kFuseLanes reads, i.e. all of them qualify (measured: a batch of 500-read partitions gains 8 %, while
+                                // batches whose problems straddle the limit run both paths side by side and lose up to 8 %)
+    bool wide_solve = true;     // some problem of the batch sees more than kFuseLanes reads: the 16-bit-counter instances of k_solve run too (score_facts)
+    bool prob_self_scan = false; // k_prob_emit adds up the candidate blocks itself (few candidates; Run::prob_bs)
+    bool have_huge = false;     // the batch has a problem with more than kNMax candidates: launch the huge kernels (seg_score, seg_post1)
+    bool dp_wide_counts = false; // some problem sees >= 65536 reads: DP stages 32-bit counts (seg_post1)
+    bool use_wave = true;       // FSEG_NO_WAVE=1, or a wave kernel met a read it cannot stage: k_tiny / k_solve<16> instead of the wave kernels (wave_on)
+    bool force_scan_stall = false;   // FSEG_FORCE_SCAN_STALL=1 (tests): the first look-back run reports a stall (seg_pre1)
+    bool profiling = false;     // fseg_set_profiling: the replay is two graphs around a bracketed scoring stage (run_impl), ...
+    bool profile_all = true;    // ... false (mode 2): only the interval-scoring stage is bracketed by events (Run::begin), ...
+    bool profile_plain = false; // ... mode 3: every stage bracketed on replays too, plain launches instead of the graph (run_impl)
+    char fill[3] = {0, 0, 0};
+    bool operator==(const LaunchShape &o) const { return memcmp(this, &o, sizeof o) == 0; }
+};
+static_assert(std::has_unique_object_representations_v<LaunchShape>, "LaunchShape is compared as bytes: no padding");
+
 struct fseg_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -113,20 +148,12 @@ struct fseg_ctx {
     bool fetched = false;        // the results of the last run are in the pinned result buffers
     fseg_params P{};
     std::vector<double> w_main, w_refine, h_table;
-    // batch metadata (host)
-    int n_part = 0;
-    i64 K = 0, R = 0, I = 0, NPOS = 0, LANES = 0;
-    i64 max_part_pos = 0;      // positions of the batch's largest partition (k_thr_part takes partitions of up to kThrPartMaxChunks * 8192)
+    BatchFacts batch;          // the resident batch's facts, assigned whole from the upload's plan (seg_upload_plan.h)
     int thr_part = -1;         // FSEG_THR_PART=0 / 1: the threshold per partition by one workgroup (k_thr_part) never / whenever possible; -1: batches of many partitions
     int hist16 = -1;           // FSEG_HIST16=0 / 1: S1 with 32-bit LDS counters always / with packed 16-bit ones wherever no count can overflow; -1: the same as 1
-    bool hist_packed = false;  // the resident batch's chunks were planned for k_hist<16> (kHistChunk16 positions, every count <= 65 535)
     i64 label_grid = 0;        // FSEG_LABEL_GRID=<n> (tests): the label launch takes at most n workgroups, so that one walks several units; 0: 65 536
     int yraw16 = -1;           // FSEG_YRAW16=0 / 1: the histogram in device memory int32 always / uint16 wherever S1 runs packed; -1: the same as 1
-    bool yraw_narrow = false;  // the resident batch's d_y_raw holds uint16 (hist_packed and the switch): S1's output, S2's and S6's input
     int iv_cand = -1;          // FSEG_IV_CAND=0 / 1: S4 and S6 by intervals (k_fix, k_segments) always / by candidates (k_fix_cand, k_segments_cand) wherever iv_threads is 64; -1: from kIvCandFrom intervals on
-    i64 max_part_lanes = 0;    // reads of the batch's largest partition (what bounds a DP sum: 32-bit keys below 2^18)
-    int n_tiles = 0;
-    bool expanded = false;
     std::vector<i64> part_iv_off, part_rep_off;
     // The three slabs and the buffers that live outside them.  Every DevBuf<T> below is a view into a slab, every OwnDev<T> /
     // Slab / Pinned<T> an owner that frees itself when the context goes (~fseg_ctx has the order).  Untyped (DevBuf<void> /
@@ -164,7 +191,6 @@ struct fseg_ctx {
     DevBuf<i64> d_hc_llo, d_hc_lhi, d_rb_esum, d_rb_ebase;
     DevBuf<u64> d_key_a, d_key_b;
     DevBuf<int2> d_lane_lx, d_lex;      // the exons again as one (ts, te) stream in lane order, and every lane's range in it
-    i64 max_rep_exons = 0;       // most exons of one rep in the resident batch
     OwnDev<double> d_w_main, d_w_refine, d_h_table;        // parameter tables (own allocations)
     OwnDev<int2> d_thr_tab;
     // device buffers: position-sized (slab_pos)
@@ -175,7 +201,6 @@ struct fseg_ctx {
     DevBuf<int> d_bsum, d_gsum, d_bsum_side, d_pk, d_part_has2;
     DevBuf<unsigned char> d_pf, d_kp;
     DevBuf<i64> d_voff, d_chunk_off, d_label_off;
-    int n_hist_chunks = 0, n_rep_blocks = 0;
     // candidate-sized (slab_pos)
     DevBuf<i64> d_cand_off, d_final_off, d_prob_bs;
     DevBuf<int> d_cand_y, d_final_y, d_final_pos, d_final_iv, d_blk_pre, d_tile_tot, d_seg_iv, d_seg_prev, d_rseg_c, d_cand_pn, d_cand_ll, d_cand_ln;
@@ -235,15 +260,8 @@ struct fseg_ctx {
     hsa_signal_t hsa_sig = {0};
     int hsa_cpu = 0;            // index of the CPU agent that owns the pinned result buffer ...
     const void *hsa_dst_base = nullptr;   // ... as asked for this allocation of it
-    bool profiling = false;
-    bool profile_all = true;    // false (fseg_set_profiling(ctx, 2)): only the interval-scoring stage is bracketed by events
-    bool have_huge = false;      // the batch has a problem with more than kNMax candidates: launch the huge kernels
-    int nm_giant = 0;            // ... with more than kNHuge: its size (rounded up: the LDS carve-up and scratch piece of the giant kernels); 0: none
-    OwnDev<void> d_giant;        // their scratch: kGiantWgs pieces of giant_scratch_bytes(nm_giant) (own allocation)
-    bool dp_wide_counts = false; // some problem sees >= 65536 reads: DP stages 32-bit counts
-    int nm_big = kNMax;         // LDS carve-up of the big-problem kernels: largest problem of the batch, rounded up
-    bool small_batch = false;
-    bool tiny_on = false;       // many problems (> tiny_from): problems with <= kTiny candidates go to k_tiny
+    LaunchShape shape;           // what a captured graph was launched under (above)
+    OwnDev<void> d_giant;        // the giant kernels' scratch: kGiantWgs pieces of giant_scratch_bytes(shape.nm_giant) (own allocation)
     bool use_graph = true;      // replay the launch sequence as hipGraphs from the second run of a batch on (FSEG_NO_GRAPH=1 disables)
     // ... when the run keeps to ONE stream (other contexts' batches in flight, small batches, FSEG_NO_FORK=1).  A run that
     // forks is replayed as plain launches: launching a graph with cross-stream edges costs the host 0.5-0.6 ms (ROCm 7.2,
@@ -254,13 +272,11 @@ struct fseg_ctx {
     bool run_linear = false;    // this run: one stream whatever else holds (a graph is being captured)
     bool use_sized = true;      // the first run of a batch stops twice to size its arenas exactly (FSEG_NO_SIZED=1: guess, and re-run on overflow)
     static constexpr i64 kProbSelfMax = 4 * kProbBlock;   // candidates up to which it does
-    bool prob_self_scan = false; // k_prob_emit adds up the candidate blocks itself (few candidates)
-    i64 scan_single_max = 512;  // scan blocks up to which the compactions use the single-pass look-back scan (FSEG_SCAN_SINGLE_MAX)
-    bool force_scan_stall = false;   // FSEG_FORCE_SCAN_STALL=1 (tests): the first look-back run reports a stall
     hipGraph_t graph[2] = {nullptr, nullptr};            // [0] whole pipeline, or before / after scoring when profiling
     hipGraphExec_t graph_exec[2] = {nullptr, nullptr};
-    bool profile_plain = false;   // fseg_set_profiling(3)
     int n_graphs = 0;
+    LaunchShape graph_shape;     // the shape the graphs were captured under: run_impl replays them only while `shape` equals it
+    unsigned graph_captures = 0; // captures this context has made (one per shape a replay met); FSEG_TAP_SYNC[9]
     bool last_sized = false;     // the pending run was launched stage by stage (per-stage events valid)
     hipEvent_t ev_b[ST_COUNT] = {}, ev_e[ST_COUNT] = {};
     hipEvent_t ev_g[4] = {};
@@ -277,7 +293,6 @@ struct fseg_ctx {
     bool force_key64 = false;
     bool wide_by_seen = false;  // FSEG_WIDE_BY_SEEN=1 (tests)
     char score_plan[kScorePlanChars + 1] = "gM|W|hB|gST";   // FSEG_SCORE_PLAN (see seg_score_plan.h; anything that does not name each class once = one stream)
-    bool use_wave = true;       // FSEG_NO_WAVE=1: k_tiny / k_solve<16> instead of the wave kernels (k_wave)
     bool use_fuse = true;       // FSEG_NO_FUSE=1: no problem goes to k_solve (everything that is not tiny takes the arena path)
     // Reads the widest problem of a batch may see for the batch's problems to be solved whole (k_solve / k_wave) instead of going
     // through the arena path; FSEG_FUSE_LANES=1023 admits batches of 1 000-read partitions (their widest problems see ~300 reads:
@@ -286,16 +301,6 @@ struct fseg_ctx {
     // turns are not (config3: 249 against 301 M reads/s; config5: equal) -- the few wide problems are long, thin launches -- so
     // the default keeps such batches on the arena path.
     int fuse_lanes = kFuseLanesDefault;
-    bool wide_solve = true;     // some problem of the batch sees more than kFuseLanes reads: the 16-bit-counter instances of k_solve run too
-    bool fuse_on = true;        // this batch's problems go to k_solve: decided per batch -- when its widest problem sees at most
-                                // kFuseLanes reads, i.e. all of them qualify (measured: a batch of 500-read partitions gains 8 %, while
-                                // batches whose problems straddle the limit run both paths side by side and lose up to 8 %)
-    // what the lists of the resident batch hold (read from the status record; exact once the batch has run or been sized):
-    // launches over an empty list are skipped
-    bool counts_known = false;
-    i64 n_solve[3] = {0, 0, 0}, n_cls_work[4] = {0, 0, 0, 0}, n_dp_cls[3] = {0, 0, 0}, n_arena_prob = 0, n_tiny = 0;
-    i64 n_wide[3] = {0, 0, 0};  // of n_solve: problems that need the 16-bit-counter instances
-    i64 max_ln = 0;             // reads the widest problem of the batch sees
     i64 tiny_from = 256;        // problems above which k_tiny is used (FSEG_TINY_FROM; tests force 0)
     bool trace = false;         // FSEG_TRACE=1: phase timers of upload / run on stderr
     bool force_global_sort = false;   // FSEG_GLOBAL_SORT=1 (tests): the batch-wide radix sort whatever the partition sizes
@@ -462,16 +467,16 @@ int alloc_arenas(fseg_ctx *c) {
     cv.add(c->d_out, (size_t)c->tri_cap);
     {
         size_t bytes = 0;
-        const int nms[3] = {kClsSmall, kClsMid, c->nm_big};
+        const int nms[3] = {kClsSmall, kClsMid, c->shape.nm_big};
         for (int q = 0; q < 3; ++q) {
-            const bool on = ((c->split_dp >> q) & 1) && c->counts_known && c->use_fuse && c->fuse_on && c->n_solve[q] > 0;
-            c->dpx_cnt[q] = (c->wide_solve && c->n_wide[q] > 0) ? 2 : 1;
+            const bool on = ((c->split_dp >> q) & 1) && c->shape.counts_known && c->use_fuse && c->shape.fuse_on && c->shape.n_solve[q] > 0;
+            c->dpx_cnt[q] = (c->shape.wide_solve && c->shape.n_wide[q] > 0) ? 2 : 1;
             c->dpx_stride[q] = (i64)dpx_slot_bytes(nms[q], c->dpx_cnt[q]);
-            c->dpx_n[q] = on ? c->n_solve[q] : 0;
+            c->dpx_n[q] = on ? c->shape.n_solve[q] : 0;
             c->dpx_base[q] = (i64)bytes;
             bytes += (size_t)c->dpx_n[q] * (size_t)c->dpx_stride[q];
         }
-        c->dpx_nm = c->nm_big;
+        c->dpx_nm = c->shape.nm_big;
         cv.add(c->d_dpx, bytes);
     }
     TRY(reserve(c, c->slab_arena, cv.total));
@@ -480,12 +485,9 @@ int alloc_arenas(fseg_ctx *c) {
     return FSEG_OK;
 }
 
-// look-back state of the three compactions (values, candidates, final positions): nb words each, zeroed per run
-inline i64 scan_blocks(i64 n) { return (n + kScanBlock - 1) / kScanBlock; }
-
 // the wave kernels need the exon stream's pieces to fit their LDS stage (k_wave): a batch with a rep of more exons keeps
 // k_tiny / k_solve for its small problems
-bool wave_on(const fseg_ctx *c) { return c->use_wave && c->max_rep_exons <= kWaveRepExons; }
+bool wave_on(const fseg_ctx *c) { return c->shape.use_wave && c->batch.max_rep_exons <= kWaveRepExons; }
 ProbSplit split_of(const fseg_ctx *c, bool tiny, bool fuse) {
     return ProbSplit{tiny ? kTiny : 0, (c->use_fuse && fuse) ? c->fuse_lanes : -1};
 }
@@ -509,7 +511,7 @@ static_assert(kScoreSide == fseg_ctx::kSide, "a plan's segments beyond the first
 #define FSEG_WG_TINY 4096
 #endif
 // the candidates a kernel of size class NM lays its LDS out for: the large class's follow the batch's largest problem
-template <int NM> int nm_of(const fseg_ctx *c) { return NM == kNMax ? c->nm_big : NM; }
+template <int NM> int nm_of(const fseg_ctx *c) { return NM == kNMax ? c->shape.nm_big : NM; }
 // a 16-bit instance over one class of a sized batch walks the class's wide problems through wide_items, the one launch over
 // every class's through wide_all
 const int *wide_list(const fseg_ctx *c, const ScoreFacts &f, const ScoreOp &op) {
@@ -584,19 +586,19 @@ void launch_class_op(fseg_ctx *c, hipStream_t q, const ScoreOp &op, const ScoreF
 }
 
 // the problem kernels' grid (k_prob_range, k_prob_scan1, k_prob_emit)
-int prob_grid(const fseg_ctx *c) { return grid_for(c->NPOS / 8 / kProbBlock + 1, 1, 1024); }
+int prob_grid(const fseg_ctx *c) { return grid_for(c->batch.NPOS / 8 / kProbBlock + 1, 1, 1024); }
 // what the scoring stage's decisions read (seg_score_plan.h), from the context
 ScoreFacts score_facts(const fseg_ctx *c, bool forking) {
     ScoreFacts f;
     // list sizes known (the batch has been sized or has run): launches over an empty list are left out
-    f.known = c->counts_known; f.small_batch = c->small_batch; f.any_arena = !f.known || c->n_arena_prob > 0; f.fuse = c->use_fuse && c->fuse_on;
-    f.tiny_on = c->tiny_on; f.wave = wave_on(c); f.forking = forking; f.wide_solve = c->wide_solve;
+    f.known = c->shape.counts_known; f.small_batch = c->shape.small_batch; f.any_arena = !f.known || c->shape.n_arena_prob > 0; f.fuse = c->use_fuse && c->shape.fuse_on;
+    f.tiny_on = c->shape.tiny_on; f.wave = wave_on(c); f.forking = forking; f.wide_solve = c->shape.wide_solve;
     // 32-bit DP keys (dp_solve_push) when no sum of a chain can reach 2^24: at most 32 links times the reads of the largest partition
-    f.key32 = c->max_part_lanes < kKey32Reads && !c->force_key64;     // (FSEG_FORCE_KEY64=1: the 64-bit instances whatever the batch)
-    for (int q = 0; q < 3; ++q) { f.n_solve[q] = c->n_solve[q]; f.n_wide[q] = c->n_wide[q]; f.dpx_n[q] = c->dpx_n[q]; f.dpx_cnt[q] = c->dpx_cnt[q]; }
-    for (int q = 0; q < 4; ++q) f.n_cls_work[q] = c->n_cls_work[q];
-    f.n_tiny = c->n_tiny; f.prob_cap = c->prob_cap; f.split_dp = c->split_dp;
-    f.dpx_nm_fits = c->dpx_nm == c->nm_big; f.dpx_arena = c->d_dpx.p != nullptr;
+    f.key32 = c->batch.max_part_lanes < kKey32Reads && !c->force_key64;     // (FSEG_FORCE_KEY64=1: the 64-bit instances whatever the batch)
+    for (int q = 0; q < 3; ++q) { f.n_solve[q] = c->shape.n_solve[q]; f.n_wide[q] = c->shape.n_wide[q]; f.dpx_n[q] = c->dpx_n[q]; f.dpx_cnt[q] = c->dpx_cnt[q]; }
+    for (int q = 0; q < 4; ++q) f.n_cls_work[q] = c->shape.n_cls_work[q];
+    f.n_tiny = c->shape.n_tiny; f.prob_cap = c->prob_cap; f.split_dp = c->split_dp;
+    f.dpx_nm_fits = c->dpx_nm == c->shape.nm_big; f.dpx_arena = c->d_dpx.p != nullptr;
     f.split_grid_cap = kSplitGridCap; f.wide_one_max = fseg_ctx::kWideOneMax;
     return f;
 }
@@ -611,38 +613,38 @@ struct Run {
     hipStream_t s = c->stream;
     Status *st = c->d_status.p;
     // the flag masks: Y > 0 | candidate | final position, flag_words(NPOS) words each
-    unsigned *flag_pos_bits = c->d_bits.p, *flag_cand_bits = flag_pos_bits + flag_words(c->NPOS), *flag_final_bits = flag_cand_bits + flag_words(c->NPOS);
-    bool stage_events = c->profiling && (sized || c->run_plain);   // the stages are bracketed by events (begin / end)
+    unsigned *flag_pos_bits = c->d_bits.p, *flag_cand_bits = flag_pos_bits + flag_words(c->batch.NPOS), *flag_final_bits = flag_cand_bits + flag_words(c->batch.NPOS);
+    bool stage_events = c->shape.profiling && (sized || c->run_plain);   // the stages are bracketed by events (begin / end)
     // Small batches (one partition, few problems) are chains of launch-latency-sized kernels: branches only add
     // cross-stream dependencies there (measured: config2 +4 %), so they stay on the one stream.
     bool forking = would_fork(c) && !c->run_linear;
     // look-back state of the three compactions (values, candidates, final positions): scan_nb words each of d_scan_state
-    i64 scan_nb = scan_blocks(c->NPOS);
+    i64 scan_nb = scan_blocks(c->batch.NPOS);
     int scan_grid = scan_nb > 0 ? (int)scan_nb : 1;       // exactly one workgroup per scan block (look-back)
     // single-pass look-back scan while the chain of blocks is short; block sums + one scanning workgroup beyond that
-    bool scan_single = scan_nb <= c->scan_single_max;
+    bool scan_single = scan_nb <= c->shape.scan_single_max;
     int *bsum_side = scan_single ? nullptr : c->d_bsum_side.p;     // block sums of the scan that runs on a side stream (values)
     // the two position compactions: blocks of kPosBlock positions (a quarter of the words of look-back state, same layout).  The
     // look-back chain keeps its limit in POSITIONS (FSEG_SCAN_SINGLE_MAX blocks of kScanBlock, as it was measured): beyond it
     // block sums + group sums that the emitting workgroups add up themselves (k_pos_count), no scanning workgroup between
-    int pos_grid = (int)std::max<i64>(pos_blocks(c->NPOS), 1);     // exactly one workgroup per block
+    int pos_grid = (int)std::max<i64>(pos_blocks(c->batch.NPOS), 1);     // exactly one workgroup per block
     int *bsum = scan_single ? nullptr : c->d_bsum.p;
     int *gsum = scan_single ? nullptr : c->d_gsum.p;
-    i64 avg_len = c->NPOS / (c->K > 0 ? c->K : 1);        // positions per interval
+    i64 avg_len = c->batch.NPOS / (c->batch.K > 0 ? c->batch.K : 1);        // positions per interval
     int iv_threads = avg_len > 65536 ? 1024 : (avg_len > 16384 ? 256 : 64);    // the block of k_fix and k_segments
     // ... or both by candidates (k_fix_cand, k_segments_cand): batches of many short intervals, where a wave per interval walks many
     // of them with a few lanes at work (seg_common.h: kIvCandFrom; profiles/iv_cand.txt).  One decision for S4 and S6.
-    bool iv_cand = iv_threads == 64 && (c->iv_cand == 1 || (c->iv_cand < 0 && c->K >= kIvCandFrom));
-    int iv_cand_grid = grid_for(c->NPOS / 64 / kIvCandOwn + 1, 1, 4096);       // (the kernels stride over the runs st->n_cand makes)
+    bool iv_cand = iv_threads == 64 && (c->iv_cand == 1 || (c->iv_cand < 0 && c->batch.K >= kIvCandFrom));
+    int iv_cand_grid = grid_for(c->batch.NPOS / 64 / kIvCandOwn + 1, 1, 4096);       // (the kernels stride over the runs st->n_cand makes)
     int pg = prob_grid(c);
     // few candidates: the emit kernel scans by itself, one launch instead of three (never in a sized run: there the
     // host reads the scan's totals before the emit kernel is launched)
-    i64 *prob_bs = (c->prob_self_scan && !sized) ? nullptr : c->d_prob_bs.p;
+    i64 *prob_bs = (c->shape.prob_self_scan && !sized) ? nullptr : c->d_prob_bs.p;
     ProblemArrays pr{c->d_prob_iv.p, c->d_prob_start.p, c->d_prob_n.p,
                      c->d_prob_pair_off.p, c->d_prob_tri_off.p, c->d_prob_flags.p,
                      c->d_prob_chain.p, c->d_prob_cov_off.p, c->d_prob_lane_lo.p,
                      c->d_prob_lane_n.p};
-    ProbSplit split = split_of(c, c->tiny_on, c->fuse_on);
+    ProbSplit split = split_of(c, c->shape.tiny_on, c->shape.fuse_on);
     // What the scoring stage of this enqueue launches -- which instance over which list on which stream, in which host order:
     // seg_score_plan.h has the rules and what was measured for them -- is decided HERE, the plan (FSEG_SCORE_PLAN) with it: with the
     // device-side fork (k_wait_word) a plan's side streams are forked in front of the stage's predecessors, so that the events'
@@ -658,7 +660,7 @@ struct Run {
     unsigned sync_gen = dev_sync ? ++c->sync_gen : 0;
     // (a context's first stages with waiters also load the stage's code objects and make the runtime allocate scratch for the side
     // streams' queues -- hundreds of microseconds, once: tools/waiter_probe.py)
-    unsigned sync_ticks = (unsigned)std::min<i64>((i64)c->sync_ticks * std::max<i64>(1, c->LANES >> 18), 2000000);
+    unsigned sync_ticks = (unsigned)std::min<i64>((i64)c->sync_ticks * std::max<i64>(1, c->batch.LANES >> 18), 2000000);
     i64 labels_n16 = (c->label_cap + 15) / 16;            // the arena is allocated in multiples of 16 bytes
     bool lab_packed = labels_packed(c);                   // (two-bit labels: the arena is cleared by a memset, nothing rides)
     // the label arena's '0' fill rides the big-problem DP launch as extra workgroups -- unless the run is being sized
@@ -672,8 +674,8 @@ struct Run {
     hipError_t fj_err = hipSuccess;
 
     Run(fseg_ctx *ctx, unsigned segs_, bool sized_) : c(ctx), segs(segs_), sized(sized_) { if (segs & SEG_SCORE) plan_score_ops(facts, ps, ops); }
-    void begin(int i) const { if (stage_events && (c->profile_all || i == ST_SCORE)) (void)hipEventRecord(c->ev_b[i], s); }
-    void end(int i) const { if (stage_events && (c->profile_all || i == ST_SCORE)) (void)hipEventRecord(c->ev_e[i], s); }
+    void begin(int i) const { if (stage_events && (c->shape.profile_all || i == ST_SCORE)) (void)hipEventRecord(c->ev_b[i], s); }
+    void end(int i) const { if (stage_events && (c->shape.profile_all || i == ST_SCORE)) (void)hipEventRecord(c->ev_e[i], s); }
     // fork(k): side stream k continues from here; join(k): the main stream waits for it.  Every fork is joined before
     // enqueue_run returns, so a capture of the main stream ends with all branches merged.
     hipEvent_t fj_event() { hipEvent_t e = c->fj[fj_next % fseg_ctx::kForkEvents]; ++fj_next; return e; }
@@ -716,7 +718,7 @@ struct Run {
 template <int BITS, typename OUT>
 void launch_hist(const Run &r) {
     fseg_ctx *c = r.c;
-    hipLaunchKernelGGL((k_hist<BITS, OUT>), dim3(grid_for(c->n_hist_chunks, 1, 16384)), dim3(512), 0, r.s, c->n_hist_chunks,
+    hipLaunchKernelGGL((k_hist<BITS, OUT>), dim3(grid_for(c->batch.n_hist_chunks, 1, 16384)), dim3(512), 0, r.s, c->batch.n_hist_chunks,
                        c->d_hc_part.p, c->d_hc_p0.p, c->d_hc_n.p, c->d_hc_glo.p,
                        c->d_hc_ghi.p, c->d_hc_llo.p, c->d_hc_lhi.p, c->d_part_iv_off.p, c->d_iv_start.p, c->d_iv_end.p,
                        c->d_pos_off.p, c->d_part_lane_off.p, c->d_lane_lx.p,
@@ -728,23 +730,23 @@ void launch_hist(const Run &r) {
 template <int RV, typename COUNT>
 void launch_smooth(const Run &r) {
     fseg_ctx *c = r.c;
-    hipLaunchKernelGGL((k_smooth<RV, COUNT>), dim3(grid_for(c->n_tiles, 1, 16384)), dim3(kSmoothThreads), 0, r.s, c->n_tiles, c->d_tile_desc.p,
+    hipLaunchKernelGGL((k_smooth<RV, COUNT>), dim3(grid_for(c->batch.n_tiles, 1, 16384)), dim3(kSmoothThreads), 0, r.s, c->batch.n_tiles, c->d_tile_desc.p,
                        c->d_y_raw.as<COUNT>(), c->d_w_main.p,
                        c->P.radius_main, c->d_y.p, r.flag_pos_bits,
                        r.flag_cand_bits, c->d_blk_pre.p, c->d_tile_tot.p, c->d_tile_defer.p);
 }
 template <int RV>
 void launch_smooth_as(const Run &r) {
-    if (r.c->yraw_narrow) launch_smooth<RV, uint16_t>(r); else launch_smooth<RV, int>(r);
+    if (r.c->batch.yraw_narrow) launch_smooth<RV, uint16_t>(r); else launch_smooth<RV, int>(r);
 }
 // A position compaction (`plane` 1: the candidates, 2: the final positions) on the main stream: the flagged positions' values,
 // positions and intervals into the lists, every interval's offset into off[0 .. K]
 void launch_positions(const Run &r, const unsigned *flags, int plane, u64 *total, i64 *off, int *out_y, int *out_pos, int *out_iv) {
     fseg_ctx *c = r.c;
     if (!r.scan_single)
-        hipLaunchKernelGGL(k_pos_count, dim3(grid_for(pos_groups(c->NPOS), 1, 4096)), dim3(kPosCountThreads), 0, r.s, flags, c->NPOS, r.bsum, r.gsum);
-    hipLaunchKernelGGL(k_scan_emit<kEmitPositions>, dim3(r.pos_grid), dim3(256), 0, r.s, flags, c->NPOS,
-                       r.bsum, r.gsum, c->d_scan_state.p + plane * r.scan_nb, total, off + c->K, &r.st->err, (const double *)nullptr, (double *)nullptr, c->K, c->d_pos_off.p,
+        hipLaunchKernelGGL(k_pos_count, dim3(grid_for(pos_groups(c->batch.NPOS), 1, 4096)), dim3(kPosCountThreads), 0, r.s, flags, c->batch.NPOS, r.bsum, r.gsum);
+    hipLaunchKernelGGL(k_scan_emit<kEmitPositions>, dim3(r.pos_grid), dim3(256), 0, r.s, flags, c->batch.NPOS,
+                       r.bsum, r.gsum, c->d_scan_state.p + plane * r.scan_nb, total, off + c->batch.K, &r.st->err, (const double *)nullptr, (double *)nullptr, c->batch.K, c->d_pos_off.p,
                        c->d_iv_start.p, c->d_blk_iv0.p, out_y, out_pos,
                        off, 0, out_iv);
 }
@@ -796,7 +798,7 @@ void launch_refine(const Run &r) {
                            c->d_cand_off.p, c->d_cand_y.p, c->d_seg_iv.p, c->d_y_raw.as<COUNT>(), c->d_blk_pre.p, c->d_tile_tot.p,
                            c->d_iv_tile0.p, c->d_chosen.p, r.flag_final_bits, c->d_rseg_c.p, c->d_seg_prev.p, r.st);
     else
-        hipLaunchKernelGGL(k_segments<COUNT>, dim3(grid_for(c->K, 1, 8192)), dim3(r.iv_threads), 0, r.s, c->K, c->d_pos_off.p,
+        hipLaunchKernelGGL(k_segments<COUNT>, dim3(grid_for(c->batch.K, 1, 8192)), dim3(r.iv_threads), 0, r.s, c->batch.K, c->d_pos_off.p,
                            c->d_cand_off.p, c->d_cand_y.p, c->d_y_raw.as<COUNT>(), c->d_blk_pre.p, c->d_tile_tot.p, c->d_iv_tile0.p,
                            c->d_chosen.p, r.flag_final_bits, c->d_rseg_c.p,
                            c->d_seg_prev.p, r.st);
@@ -811,18 +813,18 @@ void seg_pre1(Run &r) {
     fseg_ctx *c = r.c;
     hipStream_t s = r.s;
     Status *st = r.st;
-    const int n_part = c->n_part;
-    const i64 K = c->K, NPOS = c->NPOS;
+    const int n_part = c->batch.n_part;
+    const i64 K = c->batch.K, NPOS = c->batch.NPOS;
     {   // Status and the flag planes (OR-ed into: k_smooth, k_peaks_edges, k_segments, k_refine) by one launch (two memsets were three fill kernels)
         const i64 nw = 3 * (i64)flag_words(NPOS);
         hipLaunchKernelGGL(k_clear, dim3(grid_for(nw / 4 + 1, 256, 2048)), dim3(256), 0, s, st, c->d_bits.p, nw);
     }
     r.begin(ST_HIST);
     // S1
-    c->paths[fseg_ctx::PATH_HIST16] = c->hist_packed;
-    c->paths[fseg_ctx::PATH_YRAW16] = c->yraw_narrow;
-    if (c->yraw_narrow) launch_hist<16, uint16_t>(r);
-    else if (c->hist_packed) launch_hist<16, int>(r);
+    c->paths[fseg_ctx::PATH_HIST16] = c->batch.hist_packed;
+    c->paths[fseg_ctx::PATH_YRAW16] = c->batch.yraw_narrow;
+    if (c->batch.yraw_narrow) launch_hist<16, uint16_t>(r);
+    else if (c->batch.hist_packed) launch_hist<16, int>(r);
     else launch_hist<32, int>(r);
     r.end(ST_HIST); r.begin(ST_SMOOTH);
     // S2
@@ -833,14 +835,14 @@ void seg_pre1(Run &r) {
     r.end(ST_SMOOTH);
     // S3a threshold: needs only the smoothed signal, like the candidates (S3b) -- the two chains run side by side
     hipStream_t q = r.fork(0);
-    if (r.stage_events && c->profile_all) (void)hipEventRecord(c->ev_b[ST_THRESHOLD], q);
+    if (r.stage_events && c->shape.profile_all) (void)hipEventRecord(c->ev_b[ST_THRESHOLD], q);
     // batches of many partitions of moderate size: a workgroup per partition does the whole threshold (k_thr_part); a batch of a
     // few large partitions (config 2: one) keeps the batch-wide compaction and a workgroup per 8192-value chunk
     // (Until the end of round 5 a context that shares the device kept the chunk kernels: host memory -> host memory, eight contexts, the job
     // ran at 368 M reads/s with k_thr_part against 381 M without -- a difference inside that figure's box noise, as it turned out.
     // Over resident batches, three pairs of runs in one call: 527.6 / 530.8 / 531.5 with it, 524.1 / 524.4 / 503.7 without: one launch
     // of 47 us instead of seven that hold a hardware queue for 84.)
-    const bool thr_part_fits = c->max_part_pos <= (i64)kThrPartMaxChunks * 8192;
+    const bool thr_part_fits = c->batch.max_part_pos <= (i64)kThrPartMaxChunks * 8192;
     const bool thr_part = thr_part_fits && (c->thr_part == 1 || (c->thr_part < 0 && n_part >= 64));
     if (thr_part) {
         c->paths[fseg_ctx::PATH_THR_PART] = 1;
@@ -856,7 +858,7 @@ void seg_pre1(Run &r) {
         hipLaunchKernelGGL(k_scan_emit<kEmitValues>, dim3(r.scan_grid), dim3(256), 0, q, r.flag_pos_bits, NPOS,
                            r.bsum_side, (const int *)nullptr, scan_state, &st->n_vals, (i64 *)nullptr, &st->err, c->d_y.p, c->d_v.p, K, c->d_pos_off.p,
                            c->d_iv_start.p, c->d_blk_iv0.p, (int *)nullptr, (int *)nullptr, (i64 *)nullptr,
-                           c->force_scan_stall ? 1 : 0, (int *)nullptr);
+                           c->shape.force_scan_stall ? 1 : 0, (int *)nullptr);
         hipLaunchKernelGGL(k_voff, dim3(grid_for(n_part + 1, 1, 2048)), dim3(64), 0, q, n_part, c->d_part_iv_off.p,
                            c->d_pos_off.p, NPOS, r.flag_pos_bits, r.bsum_side, scan_state, &st->n_vals,
                            c->d_voff.p);
@@ -871,10 +873,10 @@ void seg_pre1(Run &r) {
                            c->d_chunk_off.p, csum0, csum1, c->P.variance_factor, c->d_mean.p,
                            c->d_thr.p, c->chunk_cap);
     }
-    if (r.stage_events && c->profile_all) (void)hipEventRecord(c->ev_e[ST_THRESHOLD], q);
+    if (r.stage_events && c->shape.profile_all) (void)hipEventRecord(c->ev_e[ST_THRESHOLD], q);
     r.begin(ST_CANDIDATES);
     // S3b candidates
-    hipLaunchKernelGGL(k_peaks_edges, dim3(grid_for(c->n_tiles, 256, 4096)), dim3(256), 0, s, c->n_tiles, c->d_tile_desc.p,
+    hipLaunchKernelGGL(k_peaks_edges, dim3(grid_for(c->batch.n_tiles, 256, 4096)), dim3(256), 0, s, c->batch.n_tiles, c->d_tile_desc.p,
                        c->d_tile_defer.p, c->d_y.p, r.flag_cand_bits, c->d_part_has2.p, n_part);
     // (every candidate's interval with it: what k_fix_cand, k_prob_range, k_prob_emit, k_segments_cand and k_refine index by)
     launch_positions(r, r.flag_cand_bits, 1, &st->n_cand, c->d_cand_off.p, c->d_cand_y.p, nullptr, c->d_seg_iv.p);
@@ -926,7 +928,7 @@ void seg_pre2(Run &r) {
         if (r.stage_events && (r.segs & SEG_SCORE)) { r.end(ST_SCORE_PREP); r.begin(ST_SCORE); r.score_begun = true; }
         const int work_grid = grid_for(c->work_cap, 1, 4096);
         const int cov_blocks = work_grid < 2048 ? work_grid : 2048;
-        const int pt_blocks = c->small_batch ? grid_for(c->prob_cap, 1, 512) : 0;       // fused only for small batches
+        const int pt_blocks = c->shape.small_batch ? grid_for(c->prob_cap, 1, 512) : 0;       // fused only for small batches
         if (!pt_blocks)
             hipLaunchKernelGGL(k_pair_thresholds, dim3(grid_for(c->prob_cap, 1, 2048)), dim3(256), 0, s, st, pr,
                                c->d_prob_desc.p, c->prob_cap, c->d_cand_off.p, c->d_cand_y.p,
@@ -972,12 +974,12 @@ void seg_score(Run &r) {
     const ScoreFacts &facts = r.facts;
     const ScorePlan &ps = r.ps;
     const bool known = facts.known, any_arena = facts.any_arena;
-    const int tiny_max = c->tiny_on ? kTiny : 0;
+    const int tiny_max = c->shape.tiny_on ? kTiny : 0;
     if (!r.score_begun) r.begin(ST_SCORE);
     int *const census = c->paths;
     for (int w : kScoreCensus) census[w] = 0;
-    census[fseg_ctx::PATH_SMALL_BATCH] = c->small_batch; census[fseg_ctx::PATH_TINY_ON] = c->tiny_on; census[fseg_ctx::PATH_WAVE_ON] = facts.wave;
-    census[fseg_ctx::PATH_FUSE_ON] = c->use_fuse && c->fuse_on; census[fseg_ctx::PATH_KNOWN] = known; census[fseg_ctx::PATH_PLAN] = ps.on;
+    census[fseg_ctx::PATH_SMALL_BATCH] = c->shape.small_batch; census[fseg_ctx::PATH_TINY_ON] = c->shape.tiny_on; census[fseg_ctx::PATH_WAVE_ON] = facts.wave;
+    census[fseg_ctx::PATH_FUSE_ON] = c->use_fuse && c->shape.fuse_on; census[fseg_ctx::PATH_KNOWN] = known; census[fseg_ctx::PATH_PLAN] = ps.on;
     if (c->prob_cap > 0) {
         // What the stage launches is the list r.ops (seg_score_plan.h: which instance over which list on which stream, and why),
         // made where the Run is built.  Here the side streams are forked, the list is walked -- its order is the host's
@@ -985,7 +987,7 @@ void seg_score(Run &r) {
         const bool sfork = any_arena;                               // (the arena path's work-item kernels keep their streams)
         // (forked here: a side stream continues from where it was forked)
         if (tiny_max > 0 && sfork) (void)r.fork(2);
-        if (!c->small_batch && sfork) { (void)r.fork(0); (void)r.fork(1); }
+        if (!c->shape.small_batch && sfork) { (void)r.fork(0); (void)r.fork(1); }
         if (ps.on) {
             // every side stream continues from HERE (the stage's begin event, when it is being recorded, is the first side
             // stream's fork: one marker packet less in front of everything -- each is ~5 us on its queue)
@@ -1004,17 +1006,17 @@ void seg_score(Run &r) {
         auto note_solve = [&](int cls, int cnt_bytes) {
             census[cnt_bytes == 2 ? fseg_ctx::PATH_WIDE16 : fseg_ctx::PATH_SOLVE8] |= cls < 0 ? 8 : 1 << cls;
             for (int q = 0; q < 3; ++q) if (cls < 0 || q == cls) {
-                census[fseg_ctx::PATH_N_SOLVE + q] = known ? (int)c->n_solve[q] : -1;
-                if (cnt_bytes == 2) census[fseg_ctx::PATH_N_WIDE + q] = known ? (int)c->n_wide[q] : -1;
+                census[fseg_ctx::PATH_N_SOLVE + q] = known ? (int)c->shape.n_solve[q] : -1;
+                if (cnt_bytes == 2) census[fseg_ctx::PATH_N_WIDE + q] = known ? (int)c->shape.n_wide[q] : -1;
             }
         };
         auto note_score = [&](int cls) {
             census[fseg_ctx::PATH_SCORE] |= cls < 0 ? 8 : 1 << cls;
-            census[fseg_ctx::PATH_N_WORK] = known ? (int)(c->n_cls_work[0] + c->n_cls_work[1] + c->n_cls_work[2] + c->n_cls_work[3]) : -1;
-            census[fseg_ctx::PATH_N_ARENA_PROB] = known ? (int)c->n_arena_prob : -1;
-            for (int q = 0; q < 3; ++q) if (cls < 0 || q == cls) census[fseg_ctx::PATH_N_SCORE + q] = known ? (int)c->n_cls_work[q] : -1;
+            census[fseg_ctx::PATH_N_WORK] = known ? (int)(c->shape.n_cls_work[0] + c->shape.n_cls_work[1] + c->shape.n_cls_work[2] + c->shape.n_cls_work[3]) : -1;
+            census[fseg_ctx::PATH_N_ARENA_PROB] = known ? (int)c->shape.n_arena_prob : -1;
+            for (int q = 0; q < 3; ++q) if (cls < 0 || q == cls) census[fseg_ctx::PATH_N_SCORE + q] = known ? (int)c->shape.n_cls_work[q] : -1;
         };
-        auto note_tiny = [&](int kernel) { census[fseg_ctx::PATH_TINY_KERNEL] = kernel; census[fseg_ctx::PATH_N_TINY] = known ? (int)c->n_tiny : -1; };
+        auto note_tiny = [&](int kernel) { census[fseg_ctx::PATH_TINY_KERNEL] = kernel; census[fseg_ctx::PATH_N_TINY] = known ? (int)c->shape.n_tiny : -1; };
         bool with_dpw = true;
 #ifdef FSEG_ABLATE_STAGE
         // diagnostic build (wrong results, honest timing): FSEG_ABLATE = bit mask of what a planned stage leaves out --
@@ -1066,21 +1068,21 @@ void seg_score(Run &r) {
             if (dev_mask) hipLaunchKernelGGL(k_wait_word, dim3(1), dim3(64), 0, s, st, r.sw->side_gen, dev_mask, r.sync_gen, r.sync_ticks);
         }
         // (the tiny problems' kernel is joined at the end of this stage, so the stage's time bracket covers all scoring work)
-        if (!c->small_batch && sfork) { r.join(0); r.join(1); }
-        if (c->have_huge && any_arena) {
+        if (!c->shape.small_batch && sfork) { r.join(0); r.join(1); }
+        if (c->shape.have_huge && any_arena) {
             census[fseg_ctx::PATH_SCORE] |= 16;
             hipLaunchKernelGGL(k_score_huge, dim3(256), dim3(512), kHugeScoreLds, s, st, c->d_dp_items.p, pr,
                                c->d_prob_desc.p, c->prob_cap, c->work_cap, c->d_cand_y.p,
                                c->d_cov.p, c->cov_cap, c->d_pair_thr.p, c->pair_cap,
                                c->d_out.p, c->tri_cap, c->d_amb.p);
         }
-        if (c->have_huge && c->nm_giant > 0 && any_arena && c->d_giant.p) {
+        if (c->shape.have_huge && c->shape.nm_giant > 0 && any_arena && c->d_giant.p) {
             census[fseg_ctx::PATH_SCORE] |= 32;
-            hipLaunchKernelGGL(k_score_giant, dim3(kGiantWgs), dim3(512), giant_score_lds(c->nm_giant), s, st, c->d_dp_items.p, pr,
+            hipLaunchKernelGGL(k_score_giant, dim3(kGiantWgs), dim3(512), giant_score_lds(c->shape.nm_giant), s, st, c->d_dp_items.p, pr,
                                c->d_prob_desc.p, c->prob_cap, c->work_cap, c->d_cand_y.p,
                                c->d_cov.p, c->cov_cap, c->d_pair_thr.p, c->pair_cap,
-                               c->d_out.p, c->tri_cap, c->d_amb.p, c->nm_giant,
-                               c->d_giant.as<unsigned char>(), (i64)giant_scratch_bytes(c->nm_giant));
+                               c->d_out.p, c->tri_cap, c->d_amb.p, c->shape.nm_giant,
+                               c->d_giant.as<unsigned char>(), (i64)giant_scratch_bytes(c->shape.nm_giant));
         }
         if (tiny_max > 0 && sfork) r.join(2);    // k_tiny is interval scoring too: inside the stage's time bracket
     }
@@ -1093,53 +1095,53 @@ void seg_post1(Run &r) {
     hipStream_t s = r.s;
     Status *st = r.st;
     const ProblemArrays &pr = r.pr;
-    const int tiny_max = c->tiny_on ? kTiny : 0;
+    const int tiny_max = c->shape.tiny_on ? kTiny : 0;
     r.begin(ST_DP);
     c->paths[fseg_ctx::PATH_ARENA_DP] = 0;
     if (c->prob_cap > 0 && r.facts.any_arena) {
-        c->paths[fseg_ctx::PATH_ARENA_DP] = c->dp_wide_counts ? 4 : 2;
+        c->paths[fseg_ctx::PATH_ARENA_DP] = c->shape.dp_wide_counts ? 4 : 2;
         int dp_grid = grid_for(c->prob_cap, 1, 1024);
         const int fill_blocks = r.ride_fill ? grid_for(r.labels_n16 / 8 + 1, 512, 512) : 0;
         // 16-bit count tables unless some problem sees >= 65536 reads;
         // 512 threads (8 waves share the c2 loop) when the tables of the largest problem leave room for their scratch.
         // small_batch: one launch over every problem; otherwise one launch per DP class list.
-        hipStream_t q_small = c->small_batch ? s : r.fork(0);    // the DP classes own disjoint problems
-        hipStream_t q_mid = c->small_batch ? s : r.fork(1);
-        const int big_class = c->small_batch ? -1 : 1;
-        if (c->dp_wide_counts) {
-            const bool wide_wg = dp_lds_for(c->nm_big, 4) + 8 * 1024 <= kLdsPerWg;
+        hipStream_t q_small = c->shape.small_batch ? s : r.fork(0);    // the DP classes own disjoint problems
+        hipStream_t q_mid = c->shape.small_batch ? s : r.fork(1);
+        const int big_class = c->shape.small_batch ? -1 : 1;
+        if (c->shape.dp_wide_counts) {
+            const bool wide_wg = dp_lds_for(c->shape.nm_big, 4) + 8 * 1024 <= kLdsPerWg;
             const int dp_blocks = dp_grid < 256 ? dp_grid : 256;
-            if (!c->small_batch) launch_dp_waves<unsigned>(r, q_small, q_mid);
+            if (!c->shape.small_batch) launch_dp_waves<unsigned>(r, q_small, q_mid);
             if (wide_wg) launch_dp<kNMax, 512, unsigned>(r, s, big_class, tiny_max, dp_blocks, fill_blocks);
             else launch_dp<kNMax, 256, unsigned>(r, s, big_class, tiny_max, dp_blocks, fill_blocks);
         } else {
-            if (!c->small_batch) launch_dp_waves<unsigned short>(r, q_small, q_mid);
+            if (!c->shape.small_batch) launch_dp_waves<unsigned short>(r, q_small, q_mid);
             launch_dp<kNMax, 512, unsigned short>(r, s, big_class, tiny_max, dp_grid < 512 ? dp_grid : 512, fill_blocks);
         }
-        if (!c->small_batch) { r.join(0); r.join(1); }
-        if (c->have_huge)
+        if (!c->shape.small_batch) { r.join(0); r.join(1); }
+        if (c->shape.have_huge)
             hipLaunchKernelGGL(k_dp_huge, dim3(dp_grid < 256 ? dp_grid : 256), dim3(512), kHugeDpLds, s, st, c->d_dp_items.p,
                                pr, c->d_prob_desc.p, c->prob_cap, c->d_cand_y.p, c->d_out.p,
                                c->tri_cap, c->d_amb.p, c->d_pair_thr.p, c->pair_cap,
                                c->P.min_read_support_outside, c->d_chosen.p);
-        if (c->have_huge && c->nm_giant > 0 && c->d_giant.p)
-            hipLaunchKernelGGL(k_dp_giant, dim3(kGiantWgs), dim3(512), giant_dp_lds(c->nm_giant), s, st, c->d_dp_items.p,
+        if (c->shape.have_huge && c->shape.nm_giant > 0 && c->d_giant.p)
+            hipLaunchKernelGGL(k_dp_giant, dim3(kGiantWgs), dim3(512), giant_dp_lds(c->shape.nm_giant), s, st, c->d_dp_items.p,
                                pr, c->d_prob_desc.p, c->prob_cap, c->d_cand_y.p, c->d_out.p,
                                c->tri_cap, c->d_amb.p, c->d_pair_thr.p, c->pair_cap,
-                               c->P.min_read_support_outside, c->d_chosen.p, c->nm_giant,
-                               c->d_giant.as<unsigned char>(), (i64)giant_scratch_bytes(c->nm_giant));
+                               c->P.min_read_support_outside, c->d_chosen.p, c->shape.nm_giant,
+                               c->d_giant.as<unsigned char>(), (i64)giant_scratch_bytes(c->shape.nm_giant));
     }
     r.end(ST_DP); r.begin(ST_REFINE);
     // S6
-    if (c->yraw_narrow) launch_refine<uint16_t>(r);
+    if (c->batch.yraw_narrow) launch_refine<uint16_t>(r);
     else launch_refine<int>(r);
     r.end(ST_REFINE); r.begin(ST_FINAL);
     launch_positions(r, r.flag_final_bits, 2, &st->n_final, c->d_final_off.p, c->d_final_y.p, c->d_final_pos.p, c->d_final_iv.p);
     // S7, first half: per-column thresholds and the label arena's plan
-    hipLaunchKernelGGL(k_label_cols, dim3(grid_for(c->NPOS / 8 + 1, 256, 2048)), dim3(256), 0, s, c->K, c->d_final_off.p,
+    hipLaunchKernelGGL(k_label_cols, dim3(grid_for(c->batch.NPOS / 8 + 1, 256, 2048)), dim3(256), 0, s, c->batch.K, c->d_final_off.p,
                        c->d_final_y.p, c->d_final_iv.p, c->d_iv_part.p, c->d_h_table.p, c->P.h_len,
                        c->P.threshold_rate, c->d_thr_tab.p, c->d_col_thr.p, c->d_col_zero.p,
-                       c->d_part_has2.p, c->n_part, c->d_part_iv_off.p, c->d_part_rep_off.p,
+                       c->d_part_has2.p, c->batch.n_part, c->d_part_iv_off.p, c->d_part_rep_off.p,
                        c->d_label_off.p, st, c->label_cap);
     r.end(ST_FINAL);
 }
@@ -1161,9 +1163,9 @@ void seg_post2(Run &r, i64 label_fill_bytes) {
             if (n16 > 0)
                 hipLaunchKernelGGL(k_label_zero, dim3(grid_for(n16 / 8 + 1, 256, 4096)), dim3(256), 0, s, c->d_labels.as<uint4>(), n16);
         }
-        const int lab_grid = grid_for((i64)c->n_rep_blocks * kLabelSplit, 1, c->label_grid > 0 && c->label_grid < 65536 ? c->label_grid : 65536);
-        hipLaunchKernelGGL(k_label_reads, dim3(lab_grid), dim3(256), 0, s, c->n_rep_blocks,
-                           c->d_rb_part.p, c->d_rb_r0.p, c->d_label_off.p, c->label_cap, c->n_part,
+        const int lab_grid = grid_for((i64)c->batch.n_rep_blocks * kLabelSplit, 1, c->label_grid > 0 && c->label_grid < 65536 ? c->label_grid : 65536);
+        hipLaunchKernelGGL(k_label_reads, dim3(lab_grid), dim3(256), 0, s, c->batch.n_rep_blocks,
+                           c->d_rb_part.p, c->d_rb_r0.p, c->d_label_off.p, c->label_cap, c->batch.n_part,
                            c->d_part_iv_off.p, c->d_part_rep_off.p, c->d_final_off.p,
                            c->d_final_pos.p, c->d_col_thr.p, c->d_rep_exon_off.p,
                            c->d_ex_ts.p, c->d_ex_te.p, c->d_col_zero.p,
@@ -1234,11 +1236,11 @@ int run_input_errors(fseg_ctx *c, const Status &s) {
 
 // the giant-problem kernels' LDS carve-up and scratch for a run whose largest problem has max_n candidates
 int prepare_giant(fseg_ctx *c, int max_n) {
-    if (max_n <= kNHuge || max_n > kNGiant) { if (max_n <= kNHuge) c->nm_giant = 0; return FSEG_OK; }
+    if (max_n <= kNHuge || max_n > kNGiant) { if (max_n <= kNHuge) c->shape.nm_giant = 0; return FSEG_OK; }
     int want = (max_n + 7) & ~7;
     if (want > kNGiant) want = kNGiant;
-    if (want > c->nm_giant || c->nm_giant == 0) { c->nm_giant = want; drop_graph(c); }
-    TRY(ensure(c, c->d_giant, (size_t)kGiantWgs * giant_scratch_bytes(c->nm_giant)));
+    if (want > c->shape.nm_giant || c->shape.nm_giant == 0) c->shape.nm_giant = want;
+    TRY(ensure(c, c->d_giant, (size_t)kGiantWgs * giant_scratch_bytes(c->shape.nm_giant)));
     const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_score_giant), hipFuncAttributeMaxDynamicSharedMemorySize, (int)giant_score_lds(kNGiant));
     if (e != hipSuccess) return fail(c, FSEG_ERR_HIP, "hipFuncSetAttribute(k_score_giant): %s", hipGetErrorString(e));
     return FSEG_OK;
@@ -1246,42 +1248,37 @@ int prepare_giant(fseg_ctx *c, int max_n) {
 
 // what the lists of the batch hold, from the status record of a run (or of the sizing pass)
 void note_counts(fseg_ctx *c, const Status &s) {
-    for (int q = 0; q < 3; ++q) { c->n_solve[q] = (i64)s.solve_cls[q]; c->n_dp_cls[q] = (i64)s.dp_cls[q]; }
-    c->n_tiny = (i64)s.n_tiny;
-    for (int q = 0; q < 3; ++q) c->n_wide[q] = (i64)s.wide_cls[q];
-    for (int q = 0; q < 4; ++q) c->n_cls_work[q] = (i64)s.cls_work[q];
-    c->n_arena_prob = (i64)s.dp_cls[0] + (i64)s.dp_cls[1] + (i64)s.dp_cls[2];
-    if (!c->counts_known) drop_graph(c);
-    c->counts_known = true;
+    for (int q = 0; q < 3; ++q) c->shape.n_solve[q] = (i64)s.solve_cls[q];
+    c->shape.n_tiny = (i64)s.n_tiny;
+    for (int q = 0; q < 3; ++q) c->shape.n_wide[q] = (i64)s.wide_cls[q];
+    for (int q = 0; q < 4; ++q) c->shape.n_cls_work[q] = (i64)s.cls_work[q];
+    c->shape.n_arena_prob = (i64)s.dp_cls[0] + (i64)s.dp_cls[1] + (i64)s.dp_cls[2];
+    c->shape.counts_known = true;
 }
 
 // launch parameters that follow from the sizes of a run (exact in a sized run, last run's otherwise)
 void adapt_to(fseg_ctx *c, const Status &s) {
-    const bool old_small = c->small_batch, old_self = c->prob_self_scan, old_tiny = c->tiny_on;
-    const int old_nm = c->nm_big;
-    c->small_batch = (i64)s.n_prob <= 256 && (i64)s.n_work <= 1024;
-    c->tiny_on = (i64)s.n_prob > c->tiny_from;                  // depends on the problem count only, which k_tiny does not change
-    const bool old_fuse = c->fuse_on;
-    c->fuse_on = (i64)s.max_ln <= c->fuse_lanes;                 // (the widest problem does not depend on the split either)
-    c->wide_solve = (i64)s.max_ln > kFuseLanes;                  // some problem needs the 16-bit counters
-    c->max_ln = (i64)s.max_ln;
+    const bool old_tiny = c->shape.tiny_on, old_fuse = c->shape.fuse_on;
+    c->shape.small_batch = (i64)s.n_prob <= 256 && (i64)s.n_work <= 1024;
+    c->shape.tiny_on = (i64)s.n_prob > c->tiny_from;                  // depends on the problem count only, which k_tiny does not change
+    c->shape.fuse_on = (i64)s.max_ln <= c->fuse_lanes;                 // (the widest problem does not depend on the split either)
+    c->shape.wide_solve = (i64)s.max_ln > kFuseLanes;                  // some problem needs the 16-bit counters
     // (the lists' sizes were counted under the old division of the problems: a run under the new one must not take them from the host --
     // an unsized first run of a batch with more than tiny_from problems turns k_tiny's share on for the replay, whose list bounds then
     // came from the run without it: kErrOverflowNm on every attempt, "arena sizing did not converge"; found in round 5)
-    if (old_fuse != c->fuse_on || old_tiny != c->tiny_on) { c->counts_known = false; drop_graph(c); }
-    c->prob_self_scan = (i64)s.n_cand <= fseg_ctx::kProbSelfMax;
+    if (old_fuse != c->shape.fuse_on || old_tiny != c->shape.tiny_on) c->shape.counts_known = false;
+    c->shape.prob_self_scan = (i64)s.n_cand <= fseg_ctx::kProbSelfMax;
     {   // the big-problem LDS carve-up: the largest problem (+ headroom, multiple of 4)
         int want = (int)s.max_n + 3;
         want = (want + 3) & ~3;
         if (want < kClsMid + 4) want = kClsMid + 4;
         if (want > kNMax) want = kNMax;
-        c->nm_big = want;
+        c->shape.nm_big = want;
     }
-    if (old_small != c->small_batch || old_nm != c->nm_big || old_self != c->prob_self_scan || old_tiny != c->tiny_on) drop_graph(c);
 }
 
 void collect_stage_times(fseg_ctx *c, int timed_graphs) {
-    if (!c->profiling) return;
+    if (!c->shape.profiling) return;
     for (int i = 0; i < ST_REPORTED; ++i) c->stage_ms[i] = 0.f;
     if (timed_graphs == 2) {
         (void)hipEventElapsedTime(&c->stage_ms[ST_GRAPH_PRE], c->ev_g[0], c->ev_g[1]);
@@ -1289,7 +1286,7 @@ void collect_stage_times(fseg_ctx *c, int timed_graphs) {
         (void)hipEventElapsedTime(&c->stage_ms[ST_GRAPH_POST], c->ev_g[2], c->ev_g[3]);
     } else if (c->last_sized || c->run_plain) {
         for (int i = 0; i < ST_COUNT; ++i) {
-            if (!c->profile_all && i != ST_SCORE) continue;
+            if (!c->shape.profile_all && i != ST_SCORE) continue;
             if (hipEventElapsedTime(&c->stage_ms[i], c->ev_b[i], c->ev_e[i]) != hipSuccess) { c->stage_ms[i] = 0.f; (void)hipGetLastError(); }
         }
     }
@@ -1306,7 +1303,6 @@ static void note_sync_timeout(fseg_ctx *c) {
     } else if (c->trace) fprintf(stderr, "[fseg] a device-side waiter reached its time limit: the run is redone with events\n");
 }
 
-// wait for the run; grow arenas and re-run if a capacity was exceeded (never after a sized run: its capacities are exact)
 static void set_in_flight(fseg_ctx *c, bool on) {
     if (!on) release_device(c);
     if (c->counted_in_flight == on || c->device < 0 || c->device >= 64) return;
@@ -1328,49 +1324,58 @@ static bool others_in_flight(const fseg_ctx *c) {
     return g_in_flight[c->device].load(std::memory_order_acquire) - (c->counted_in_flight ? 1 : 0) > 0;
 }
 // the run owns the device and is worth branching (see Run::forking)
-static bool would_fork(const fseg_ctx *c) { return c->use_fork && !c->small_batch && c->owns_device && c->side[0] != nullptr; }
+static bool would_fork(const fseg_ctx *c) { return c->use_fork && !c->shape.small_batch && c->owns_device && c->side[0] != nullptr; }
 static int finish_run_impl(fseg_ctx *c);
 int finish_run(fseg_ctx *c) {
     const int rc = finish_run_impl(c);
     if (!c->pending) set_in_flight(c, false);
     return rc;
 }
+// What the host does about the status record of a run of `kind`: seg_run_react.h decides (the table there has what each kind
+// does and where the kinds differ on purpose), this applies the adaptations to the context and says how the caller goes on --
+// Done: with the next piece, or the run is complete; Redo: enqueue the same again (after alloc_arenas where capacities may have
+// grown); Fail: return rc.  Both run paths end here: finish_run_impl (Replay) and run_sized (SizedA, SizedB).
+struct Verdict { Outcome outcome; int rc; bool uses_attempt; };
+Verdict react_to_status(fseg_ctx *c, const Status &s, RunKind kind) {
+    i64 *const caps[CAP_COUNT] = {&c->prob_cap, &c->work_cap, &c->pair_cap, &c->tri_cap, &c->label_cap, &c->chunk_cap, &c->cov_cap};
+    ReactFacts f;
+    f.have_huge = c->shape.have_huge; f.dp_wide_counts = c->shape.dp_wide_counts; f.run_events_only = c->run_events_only; f.nm_giant = c->shape.nm_giant;
+    for (int k = 0; k < CAP_COUNT; ++k) f.cap[k] = *caps[k];
+    const Reaction r = decide_reaction(s, f, kind);
+    if (r.scan_fallback) { c->shape.scan_single_max = 0; c->shape.force_scan_stall = false; }      // redo with the three-pass scan
+    if (r.wave_off) { c->shape.use_wave = false; c->shape.counts_known = false; }
+    if (r.sync_timeout) note_sync_timeout(c);
+    if (r.nm_big_max) c->shape.nm_big = kNMax;
+    c->shape.have_huge = r.have_huge; c->shape.dp_wide_counts = r.dp_wide_counts;
+    for (int k = 0; k < CAP_COUNT; ++k) *caps[k] = r.cap[k];
+    if (r.giant) { const int rc = prepare_giant(c, (int)s.max_n); if (rc) return {Outcome::Fail, rc, true}; }
+    if (r.adopt_counts) {
+        if (kind == RunKind::Replay) {                   // the run is complete
+            c->pending = false;
+            c->ran = true;
+            collect_stage_times(c, c->run_plain ? 0 : c->n_graphs);
+        }
+        note_counts(c, s);
+        adapt_to(c, s);
+    }
+    switch (r.fail) {
+        case FailKind::None: break;
+        case FailKind::Input:
+            if (kind != RunKind::Replay) { c->pending = false; c->ran = false; }
+            return {Outcome::Fail, run_input_errors(c, s), true};
+        case FailKind::SizedOverflow: return {Outcome::Fail, fail(c, FSEG_ERR_HIP, "internal: a sized run overflowed an arena (status %#x)", s.err), true};
+        case FailKind::TimeoutNoWaiters: return {Outcome::Fail, fail(c, FSEG_ERR_HIP, "internal: a waiter timed out in a run without waiters (status %#x)", s.err), true};
+    }
+    return {r.outcome, FSEG_OK, r.uses_attempt};
+}
+
+// wait for the run; grow arenas and re-run if a capacity was exceeded (never after a sized run: its capacities are exact)
 static int finish_run_impl(fseg_ctx *c) {
     for (int attempt = 0; attempt < 4; ++attempt) {
         HIP_TRY(c, wait_stream(c));
         TRY(check_prep(c));
-        const Status &s = *c->h_status;
-        unsigned ovf = s.err & (kErrOverflowPairs | kErrOverflowTri | kErrOverflowWork | kErrOverflowLabels |
-                                kErrOverflowProblems | kErrOverflowChunks | kErrOverflowCov);
-        if (s.err & kErrOverflowNm) { ovf |= kErrOverflowNm; c->nm_big = kNMax; }
-        if (s.err & kErrWaveStage) { ovf |= kErrWaveStage; c->use_wave = false; c->counts_known = false; drop_graph(c); }    // k_tiny / k_solve fetch exons read by read
-        if (s.err & kErrSyncTimeout) { ovf |= kErrSyncTimeout; note_sync_timeout(c); }   // a device-side waiter gave up (the stage was skipped): this run again, with events
-        if ((i64)s.max_ln >= 65536 && !c->dp_wide_counts) { ovf |= kErrNeedWideDp; c->dp_wide_counts = true; drop_graph(c); }
-        if (s.err & kErrScanStall) { ovf |= kErrScanStall; c->scan_single_max = 0; c->force_scan_stall = false; drop_graph(c); }
-        if (s.dp_cls[2] > 0 && !c->have_huge) { ovf |= kErrProblemTooLarge << 16; c->have_huge = true; drop_graph(c); }   // rerun with the huge-problem kernels
-        if ((int)s.max_n > kNHuge && (int)s.max_n <= kNGiant && (int)s.max_n > c->nm_giant) {                             // ... and the giant ones, sized for this run's largest problem
-            ovf |= kErrProblemTooLarge << 17; drop_graph(c);
-            TRY(prepare_giant(c, (int)s.max_n));
-        }
-        bool need = ovf != 0 || (i64)s.n_prob > c->prob_cap || (i64)s.n_work > c->work_cap ||
-                    (i64)s.pair_used > c->pair_cap || (i64)s.tri_used > c->tri_cap || (i64)s.label_bytes > c->label_cap ||
-                    (i64)s.n_vchunks > c->chunk_cap || (i64)s.cov_used > c->cov_cap;
-        if (!need) {
-            c->pending = false;
-            c->ran = true;
-            const int timed_graphs = c->run_plain ? 0 : c->n_graphs;
-            collect_stage_times(c, timed_graphs);
-            note_counts(c, s);
-            adapt_to(c, s);
-            return run_input_errors(c, s);
-        }
-        auto grow = [](i64 need_v, i64 cap) { return need_v > cap ? need_v + need_v / 8 + 64 : cap; };
-        c->prob_cap = grow((i64)s.n_prob, c->prob_cap);
-        c->work_cap = grow((i64)s.n_work, c->work_cap);
-        c->pair_cap = grow((i64)s.pair_used, c->pair_cap);
-        c->tri_cap = grow((i64)s.tri_used, c->tri_cap);
-        c->label_cap = grow((i64)s.label_bytes, c->label_cap);
-        c->cov_cap = grow((i64)s.cov_used, c->cov_cap);
+        const Verdict v = react_to_status(c, *c->h_status, RunKind::Replay);
+        if (v.outcome != Outcome::Redo) return v.rc;
         TRY(alloc_arenas(c));
         c->last_sized = false;
         TRY(enqueue_run(c, SEG_ALL));
@@ -1424,16 +1429,16 @@ int run_sized(fseg_ctx *c) {
         HIP_TRY(c, wait_stream(c));
         TRY(check_prep(c));
         Status s = *c->h_status;
-        if (s.err & kErrScanStall) { c->scan_single_max = 0; c->force_scan_stall = false; continue; }     // redo with the three-pass scan
-        {   // k_tiny's share of the problems was decided from the previous batch: if this batch decides otherwise, the
+        if (!(s.err & kErrScanStall)) {   // (a stalled scan has no totals: the reaction below redoes the piece)
+            // k_tiny's share of the problems was decided from the previous batch: if this batch decides otherwise, the
             // arena sizes change with it -- redo the (cheap) problem scan under the right setting
             const bool tiny = (i64)s.n_prob > c->tiny_from;
             const bool fuse = (i64)s.max_ln <= c->fuse_lanes;
-            if (tiny != c->tiny_on || fuse != c->fuse_on) {
+            if (tiny != c->shape.tiny_on || fuse != c->shape.fuse_on) {
                 if (c->trace) fprintf(stderr, "[fseg] problem split changed (tiny %d -> %d, fused %d -> %d; %llu problems, widest sees %u reads): rescan\n",
-                                      (int)c->tiny_on, (int)tiny, (int)c->fuse_on, (int)fuse, (unsigned long long)s.n_prob, s.max_ln);
-                const bool fuse_turned_on = fuse && !c->fuse_on;
-                c->tiny_on = tiny; c->fuse_on = fuse;
+                                      (int)c->shape.tiny_on, (int)tiny, (int)c->shape.fuse_on, (int)fuse, (unsigned long long)s.n_prob, s.max_ln);
+                const bool fuse_turned_on = fuse && !c->shape.fuse_on;
+                c->shape.tiny_on = tiny; c->shape.fuse_on = fuse;
                 const ProbSplit split = split_of(c, tiny, fuse);
                 Status *st = c->d_status.p;
                 if (fuse_turned_on) launch_prob_range(c, split, nullptr);   // the first pass did not count the reads the wide problems keep: nobody was going to ask
@@ -1446,40 +1451,18 @@ int run_sized(fseg_ctx *c) {
             }
         }
         t_a = tk.ms();
-        if ((s.err & (kErrExonInterval | kErrBreakAssert | kErrProblemTooLarge))) {     // the reference would have aborted here
-            c->pending = false; c->ran = false;
-            return run_input_errors(c, s);
-        }
-        auto atleast = [](i64 &cap, i64 v) { if (cap < v) cap = v; };
-        atleast(c->prob_cap, (i64)s.n_prob); atleast(c->work_cap, (i64)s.n_work); atleast(c->pair_cap, (i64)s.pair_used);
-        atleast(c->tri_cap, (i64)s.tri_used); atleast(c->cov_cap, (i64)s.cov_used);
-        c->have_huge = s.dp_cls[2] > 0;
-        TRY(prepare_giant(c, (int)s.max_n));
-        c->dp_wide_counts = (i64)s.max_ln >= 65536;
-        note_counts(c, s);
-        adapt_to(c, s);
+        const Verdict va = react_to_status(c, s, RunKind::SizedA);      // the capacities, the huge / giant / wide-count kernels, the list sizes
+        if (va.outcome == Outcome::Fail) return va.rc;
+        if (va.outcome == Outcome::Redo) continue;
         TRY(alloc_arenas(c));
         // B
         TRY(enqueue_run(c, SEG_PRE2 | SEG_SCORE | SEG_POST1 | SEG_STATUS, true));
         HIP_TRY(c, wait_stream(c));
         s = *c->h_status;
         t_b = tk.ms();
-        if (s.err & kErrScanStall) { c->scan_single_max = 0; c->force_scan_stall = false; continue; }
-        const unsigned bad = s.err & (kErrOverflowPairs | kErrOverflowTri | kErrOverflowWork | kErrOverflowProblems | kErrOverflowChunks |
-                                      kErrOverflowCov | kErrOverflowNm | kErrNeedWideDp);
-        if (bad) return fail(c, FSEG_ERR_HIP, "internal: a sized run overflowed an arena (status %#x)", s.err);
-        // (what B's scoring kernels can raise besides: a result that is garbage fails HERE, not after the label stage; a wave kernel
-        // that met a read it cannot stage turns the wave kernels off and the sized attempt starts over)
-        if (s.err & kErrSyncTimeout) {                       // a device-side waiter gave up (the stage was skipped): once more, with events
-            if (c->run_events_only) return fail(c, FSEG_ERR_HIP, "internal: a waiter timed out in a run without waiters (status %#x)", s.err);
-            note_sync_timeout(c); --attempt; continue;
-        }
-        if (s.err & kErrWideMissed) { c->pending = false; c->ran = false; return run_input_errors(c, s); }
-        if (s.err & kErrWaveStage) { c->use_wave = false; c->counts_known = false; drop_graph(c); continue; }
-        if ((s.err & (kErrExonInterval | kErrBreakAssert | kErrProblemTooLarge))) {
-            c->pending = false; c->ran = false;
-            return run_input_errors(c, s);
-        }
+        const Verdict vb = react_to_status(c, s, RunKind::SizedB);
+        if (vb.outcome == Outcome::Fail) return vb.rc;
+        if (vb.outcome == Outcome::Redo) { if (!vb.uses_attempt) --attempt; continue; }
         // C
         if ((i64)s.label_bytes > c->label_cap) {
             c->label_cap = (i64)s.label_bytes;
@@ -1568,7 +1551,7 @@ void read_switches(fseg_ctx *c) {
     if (env_flag("FSEG_NO_GRAPH")) c->use_graph = false;
     if (env_flag("FSEG_NO_FORK")) c->use_fork = false;
     if (env_flag("FSEG_NO_FUSE")) c->use_fuse = false;
-    if (env_flag("FSEG_NO_WAVE")) c->use_wave = false;
+    if (env_flag("FSEG_NO_WAVE")) c->shape.use_wave = false;
     if (env_flag("FSEG_FORCE_KEY64")) c->force_key64 = true;
     if (env_flag("FSEG_WIDE_BY_SEEN")) c->wide_by_seen = true;
     if (const char *s = env_str("FSEG_SPLIT_DP")) c->split_dp = atoi(s) & 15;       // (set but empty counts: 0, no class hands its DPs over)
@@ -1578,9 +1561,9 @@ void read_switches(fseg_ctx *c) {
     if (env_flag("FSEG_NO_SIZED")) c->use_sized = false;
     if (env_flag("FSEG_TRACE")) c->trace = true;
     if (env_flag("FSEG_GLOBAL_SORT")) c->force_global_sort = true;
-    if (env_flag("FSEG_FORCE_SCAN_STALL")) c->force_scan_stall = true;
+    if (env_flag("FSEG_FORCE_SCAN_STALL")) c->shape.force_scan_stall = true;
     if (env_int("FSEG_TINY_FROM", v)) c->tiny_from = v;
-    if (env_int("FSEG_SCAN_SINGLE_MAX", v)) c->scan_single_max = v;
+    if (env_int("FSEG_SCAN_SINGLE_MAX", v)) c->shape.scan_single_max = v;
 }
 
 }  // namespace
@@ -1681,7 +1664,7 @@ int fseg_set_params(fseg_ctx *c, const fseg_params *p) {
     for (int L = 1; L < p->h_len; ++L) if (!(c->h_table[(size_t)L] < 1.0)) c->label_has2 = true;
     c->have_params = true;
     c->ran = false;          // results of an earlier run belong to other parameters
-    c->counts_known = false; // ... and so do the sizes of its lists
+    c->shape.counts_known = false; // ... and so do the sizes of its lists
     return FSEG_OK;
 }
 
@@ -1695,6 +1678,10 @@ int fseg_upload(fseg_ctx *c, const fseg_batch *b) {
     if (rc != FSEG_OK && c) set_in_flight(c, false);     // nothing of this batch will run: the device's other contexts may fork again
     return rc;
 }
+static int launch_prep(fseg_ctx *c, const UploadPlan &pl);
+static int carve_work(fseg_ctx *c, const UploadPlan &pl);
+// plan (seg_upload_plan.h) | carve the input slab by the plan's counts | fill the derived tables | stage the caller's arrays |
+// one copy, the device-side preparation | the work slabs and arenas
 static int upload_impl(fseg_ctx *c, const fseg_batch *b) {
     if (!c || !b) return FSEG_ERR_ARG;
     if (b->n_part <= 0 || !b->part_iv_off || !b->iv_start || !b->iv_end || !b->part_rep_off || !b->rep_weight ||
@@ -1704,168 +1691,67 @@ static int upload_impl(fseg_ctx *c, const fseg_batch *b) {
     Tick tk;
     // the previous batch's work (and its copy out of the staging image) must be over before its buffers are reused
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    c->pending = false; c->have_batch = false; c->ran = false; c->fetched = false; c->counts_known = false;
+    c->pending = false; c->have_batch = false; c->ran = false; c->fetched = false; c->shape.counts_known = false;
     set_in_flight(c, true);                              // until the run that follows has completed (finish_run)
-    const int np = b->n_part;
-    const i64 K = b->part_iv_off[np], R = b->part_rep_off[np];
-    if (b->part_iv_off[0] != 0 || b->part_rep_off[0] != 0 || b->rep_exon_off[0] != 0)
-        return fail(c, FSEG_ERR_ARG, "fseg_upload: offsets must start at 0");
-    if (K <= 0 || R < 0) return fail(c, FSEG_ERR_ARG, "fseg_upload: bad offsets");
-    const i64 I = b->rep_exon_off[R];
-    if (I < 0) return fail(c, FSEG_ERR_ARG, "rep_exon_off not monotone");
-    if (I >= 0x7fffffffLL) return fail(c, FSEG_ERR_UNSUPPORTED, "batch has %lld exons; split it (limit 2^31-1 per upload)", (long long)I);
-    // ---- host pass 1: the partition / interval level (validation as read_split() asserts it, :138-140) and the counts
-    i64 NPOS = 0, n_tiles = 0, lanes = 0, n_rep_blocks = 0, max_part_reps = 0, max_rep_exons = 0;
-    bool expanded = false;
-    for (int p = 0; p < np; ++p) {
-        const i64 k0 = b->part_iv_off[p], k1 = b->part_iv_off[p + 1];
-        if (k1 <= k0) return fail(c, FSEG_ERR_INPUT, "partition %d has no intervals", p);
-        if (b->part_rep_off[p + 1] < b->part_rep_off[p]) return fail(c, FSEG_ERR_ARG, "part_rep_off not monotone");
-        for (i64 k = k0; k < k1; ++k) {
-            if (!(b->iv_start[k] < b->iv_end[k])) return fail(c, FSEG_ERR_INPUT, "partition %d: interval with start >= end (py/freddie_segment.py:140)", p);
-            if (k > k0 && !(b->iv_end[k - 1] < b->iv_start[k])) return fail(c, FSEG_ERR_INPUT, "partition %d: intervals overlap or are unordered (py/freddie_segment.py:138)", p);
-            const i64 len = (i64)b->iv_end[k] - b->iv_start[k] + 1;       // an interval owns positions s..e inclusive (:652-659)
-            NPOS += len;
-            n_tiles += (len + kSmoothTile - 1) / kSmoothTile;
-        }
-        n_rep_blocks += (b->part_rep_off[p + 1] - b->part_rep_off[p] + 255) / 256;
-        if (b->part_rep_off[p + 1] - b->part_rep_off[p] > max_part_reps) max_part_reps = b->part_rep_off[p + 1] - b->part_rep_off[p];
-    }
-    if (NPOS >= 0x7fffffffLL) return fail(c, FSEG_ERR_UNSUPPORTED, "batch has %lld positions; split it (limit 2^31-1 per upload)", (long long)NPOS);
-    for (i64 r = 0; r < R; ++r) {
-        const int w = b->rep_weight[r];
-        if (w < 1) return fail(c, FSEG_ERR_INPUT, "rep %lld has weight %d (< 1)", (long long)r, w);
-        if (w != 1) expanded = true;
-        lanes += w;
-        if (b->rep_exon_off[r + 1] < b->rep_exon_off[r]) return fail(c, FSEG_ERR_ARG, "rep_exon_off not monotone");
-        if (b->rep_exon_off[r + 1] - b->rep_exon_off[r] > max_rep_exons) max_rep_exons = b->rep_exon_off[r + 1] - b->rep_exon_off[r];
-    }
-    if (lanes >= 0x7fffffffLL) return fail(c, FSEG_ERR_UNSUPPORTED, "batch has %lld reads; split it (limit 2^31-1 per upload)", (long long)lanes);
-    // S1's counter width.  The packed instance (two 16-bit counters per LDS word, chunks of twice the positions) is taken where no
-    // position's count can exceed 65 535.  A read hits a position at most twice (an exon may end where the next begins), so a
-    // partition of up to 32 767 lanes cannot get there -- every partition of an ordinary batch.  A larger one is counted here:
-    // its reps' exon ends, sorted, each with its weight (ignore_ends only takes hits away).  One width per batch.
-    bool hist_packed = c->hist16 != 0;
-    for (int p = 0; p < np && hist_packed; ++p) {
-        const i64 r0 = b->part_rep_off[p], r1 = b->part_rep_off[p + 1];
-        i64 part_lanes = 0;
-        for (i64 r = r0; r < r1; ++r) part_lanes += b->rep_weight[r];
-        if (2 * part_lanes <= kHistCountMax16) continue;
-        std::vector<std::pair<int, int>> ends;
-        ends.reserve((size_t)(2 * (b->rep_exon_off[r1] - b->rep_exon_off[r0])));
-        for (i64 r = r0; r < r1; ++r)
-            for (i64 e = b->rep_exon_off[r]; e < b->rep_exon_off[r + 1]; ++e) {
-                ends.emplace_back(b->ex_ts[e], b->rep_weight[r]);
-                ends.emplace_back(b->ex_te[e], b->rep_weight[r]);
-            }
-        std::sort(ends.begin(), ends.end());
-        i64 count = 0;
-        for (size_t i = 0; i < ends.size() && hist_packed; ++i) {
-            count = (i > 0 && ends[i].first == ends[i - 1].first ? count : 0) + ends[i].second;
-            if (count > kHistCountMax16) hist_packed = false;
-        }
-    }
-    // The histogram's element in device memory follows: uint16 where the counters are (one width per batch, decided before the
-    // position slab is carved below), unless FSEG_YRAW16=0 keeps it int32.
-    const bool yraw_narrow = hist_packed && c->yraw16 != 0;
-    // histogram chunks: consecutive positions of one partition; as large as possible (fewer reads are visited twice)
-    // while still giving >= 512 workgroups
-    int hist_chunk = hist_packed ? kHistChunk16 : kHistChunk;
-    while (hist_chunk > 1024 && NPOS / hist_chunk < 512) hist_chunk >>= 1;
-    i64 n_chunks = 0;
-    {
-        i64 k = 0, pos = 0;
-        for (int p = 0; p < np; ++p) {
-            i64 Pp = 0;
-            for (k = b->part_iv_off[p]; k < b->part_iv_off[p + 1]; ++k) Pp += (i64)b->iv_end[k] - b->iv_start[k] + 1;
-            n_chunks += (Pp + hist_chunk - 1) / hist_chunk;
-            pos += Pp;
-        }
-        (void)pos;
-    }
-    const i64 nb = scan_blocks(NPOS), nbp = pos_blocks(NPOS);
-    if (n_tiles >= 0x7fffffffLL || n_chunks >= 0x7fffffffLL) return fail(c, FSEG_ERR_UNSUPPORTED, "batch too large");
+    const UploadPlan pl = plan_upload(*b, c->hist16, c->yraw16);
+    if (pl.rc != FSEG_OK) return fail(c, pl.rc, "%s", pl.msg);
+    const BatchFacts &f = pl.batch;
     // ---- the input slab: [uploaded part, mirrored by the pinned staging image][device-derived part]
     Carve in;
-    in.add(c->d_part_iv_off, np + 1); in.add(c->d_part_rep_off, np + 1); in.add(c->d_part_lane_off, np + 1);
-    in.add(c->d_iv_start, K); in.add(c->d_iv_end, K); in.add(c->d_pos_off, K + 1); in.add(c->d_iv_part, K); in.add(c->d_iv_tile0, K);
-    in.add(c->d_tile_desc, n_tiles);
-    in.add(c->d_blk_iv0, nbp + 1);
-    in.add(c->d_rb_part, n_rep_blocks); in.add(c->d_rb_r0, n_rep_blocks);
-    in.add(c->d_hc_part, n_chunks); in.add(c->d_hc_p0, n_chunks); in.add(c->d_hc_n, n_chunks); in.add(c->d_hc_glo, n_chunks); in.add(c->d_hc_ghi, n_chunks);
-    in.add(c->d_rep_exon_off, R + 1); in.add(c->d_rep_weight, R);
-    in.add(c->d_ex_ts, I, kExonPad); in.add(c->d_ex_te, I, kExonPad);
+    in.add(c->d_part_iv_off, pl.n.part_off); in.add(c->d_part_rep_off, pl.n.part_off); in.add(c->d_part_lane_off, pl.n.part_off);
+    in.add(c->d_iv_start, pl.n.iv); in.add(c->d_iv_end, pl.n.iv); in.add(c->d_pos_off, pl.n.pos_off); in.add(c->d_iv_part, pl.n.iv); in.add(c->d_iv_tile0, pl.n.iv);
+    in.add(c->d_tile_desc, pl.n.tiles);
+    in.add(c->d_blk_iv0, pl.n.blk_iv0);
+    in.add(c->d_rb_part, pl.n.rep_blocks); in.add(c->d_rb_r0, pl.n.rep_blocks);
+    in.add(c->d_hc_part, pl.n.chunks); in.add(c->d_hc_p0, pl.n.chunks); in.add(c->d_hc_n, pl.n.chunks); in.add(c->d_hc_glo, pl.n.chunks); in.add(c->d_hc_ghi, pl.n.chunks);
+    in.add(c->d_rep_exon_off, f.R + 1); in.add(c->d_rep_weight, f.R);
+    in.add(c->d_ex_ts, f.I, kExonPad); in.add(c->d_ex_te, f.I, kExonPad);
     const size_t up_bytes = in.total;
-    in.add(c->d_lane_ex, lanes); in.add(c->d_lane_start, lanes); in.add(c->d_lane_pmax, lanes);
-    in.add(c->d_hc_llo, n_chunks); in.add(c->d_hc_lhi, n_chunks);
-    in.add(c->d_key_a, R); in.add(c->d_key_b, R); in.add(c->d_val_a, R); in.add(c->d_val_b, R); in.add(c->d_rep_last, R);
-    in.add(c->d_rb_sum, n_rep_blocks); in.add(c->d_rb_base, n_rep_blocks); in.add(c->d_rb_max, n_rep_blocks); in.add(c->d_rb_cmax, n_rep_blocks);
-    in.add(c->d_rb_esum, n_rep_blocks); in.add(c->d_rb_ebase, n_rep_blocks);
-    in.add(c->d_lane_lx, lanes, 64); in.add(c->d_lex, I, kLexPad);
+    in.add(c->d_lane_ex, f.LANES); in.add(c->d_lane_start, f.LANES); in.add(c->d_lane_pmax, f.LANES);
+    in.add(c->d_hc_llo, pl.n.chunks); in.add(c->d_hc_lhi, pl.n.chunks);
+    in.add(c->d_key_a, f.R); in.add(c->d_key_b, f.R); in.add(c->d_val_a, f.R); in.add(c->d_val_b, f.R); in.add(c->d_rep_last, f.R);
+    in.add(c->d_rb_sum, pl.n.rep_blocks); in.add(c->d_rb_base, pl.n.rep_blocks); in.add(c->d_rb_max, pl.n.rep_blocks); in.add(c->d_rb_cmax, pl.n.rep_blocks);
+    in.add(c->d_rb_esum, pl.n.rep_blocks); in.add(c->d_rb_ebase, pl.n.rep_blocks);
+    in.add(c->d_lane_lx, f.LANES, 64); in.add(c->d_lex, f.I, kLexPad);
     TRY(reserve(c, c->slab_in, in.total));
     in.bind(c->slab_in.p);
     TRY(reserve_host(c, c->h_stage, up_bytes));
     const double t_plan = tk.ms();
-    // ---- host pass 2: the small derived tables, written straight into the staging image
-    {
-        i64 *h_pos_off = host_of(c, c->d_pos_off), *h_lane_off = host_of(c, c->d_part_lane_off), *h_hc_p0 = host_of(c, c->d_hc_p0);
-        int *h_iv_part = host_of(c, c->d_iv_part), *h_iv_tile0 = host_of(c, c->d_iv_tile0), *h_blk = host_of(c, c->d_blk_iv0);
-        TileDesc *h_tile = host_of(c, c->d_tile_desc);
-        int *h_rb_part = host_of(c, c->d_rb_part), *h_rb_r0 = host_of(c, c->d_rb_r0);
-        int *h_hc_part = host_of(c, c->d_hc_part), *h_hc_n = host_of(c, c->d_hc_n), *h_hc_glo = host_of(c, c->d_hc_glo), *h_hc_ghi = host_of(c, c->d_hc_ghi);
-        h_pos_off[0] = 0; h_lane_off[0] = 0; c->max_part_lanes = 0; c->max_part_pos = 0;
-        i64 t = 0, rb = 0, ch = 0, l = 0, bq = 0;
-        for (int p = 0; p < np; ++p) {
-            const i64 k0 = b->part_iv_off[p], k1 = b->part_iv_off[p + 1];
-            for (i64 k = k0; k < k1; ++k) {
-                const i64 len = (i64)b->iv_end[k] - b->iv_start[k] + 1;
-                h_iv_part[k] = p;
-                h_pos_off[k + 1] = h_pos_off[k] + len;
-                h_iv_tile0[k] = (int)t;
-                for (i64 y = 0; y < len; y += kSmoothTile) h_tile[t++] = TileDesc{h_pos_off[k], (int)y, (int)len};
-                // interval of the first position of every block of the position compactions
-                for (; bq < nbp && bq * kPosBlock < h_pos_off[k + 1]; ++bq) h_blk[bq] = (int)k;
-            }
-            for (i64 r = b->part_rep_off[p]; r < b->part_rep_off[p + 1]; r += 256) { h_rb_part[rb] = p; h_rb_r0[rb] = (int)r; ++rb; }
-            for (i64 r = b->part_rep_off[p]; r < b->part_rep_off[p + 1]; ++r) l += b->rep_weight[r];
-            h_lane_off[p + 1] = l;
-            if (l - h_lane_off[p] > c->max_part_lanes) c->max_part_lanes = l - h_lane_off[p];
-            // histogram chunks of the partition, with the genomic position of the chunk's first and last position (a
-            // chunk may span several intervals of its partition)
-            const i64 P0 = h_pos_off[k0], P1 = h_pos_off[k1];
-            if (P1 - P0 > c->max_part_pos) c->max_part_pos = P1 - P0;
-            i64 k = k0;
-            for (i64 q0 = P0; q0 < P1; q0 += hist_chunk) {
-                const i64 q1 = std::min<i64>(q0 + hist_chunk, P1) - 1;
-                while (h_pos_off[k + 1] <= q0) ++k;
-                i64 kk = k;
-                while (h_pos_off[kk + 1] <= q1) ++kk;
-                h_hc_part[ch] = p; h_hc_p0[ch] = q0; h_hc_n[ch] = (int)(q1 - q0 + 1);
-                h_hc_glo[ch] = b->iv_start[k] + (int)(q0 - h_pos_off[k]);
-                h_hc_ghi[ch] = b->iv_start[kk] + (int)(q1 - h_pos_off[kk]);
-                ++ch;
-            }
-        }
-        h_blk[nbp] = (int)(K - 1);
-    }
+    // ---- the small derived tables, written straight into the staging image
+    fill_upload_tables(*b, pl, UploadTables{host_of(c, c->d_pos_off), host_of(c, c->d_part_lane_off), host_of(c, c->d_iv_part), host_of(c, c->d_iv_tile0),
+                                            host_of(c, c->d_tile_desc), host_of(c, c->d_blk_iv0), host_of(c, c->d_rb_part), host_of(c, c->d_rb_r0),
+                                            host_of(c, c->d_hc_part), host_of(c, c->d_hc_p0), host_of(c, c->d_hc_n), host_of(c, c->d_hc_glo), host_of(c, c->d_hc_ghi)});
     const double t_tables = tk.ms();
     // ---- the caller's arrays
     auto stage_in = [&](const auto &d, const auto *src, size_t n) {
         static_assert(sizeof(*src) == sizeof(*d.p), "the caller's array and the buffer hold the same element");
         memcpy(host_of(c, d), src, d.bytes(n));
     };
-    stage_in(c->d_part_iv_off, b->part_iv_off, (size_t)np + 1); stage_in(c->d_part_rep_off, b->part_rep_off, (size_t)np + 1);
-    stage_in(c->d_iv_start, b->iv_start, (size_t)K); stage_in(c->d_iv_end, b->iv_end, (size_t)K);
-    stage_in(c->d_rep_exon_off, b->rep_exon_off, (size_t)R + 1); stage_in(c->d_rep_weight, b->rep_weight, (size_t)R);
-    stage_in(c->d_ex_ts, b->ex_ts, (size_t)I); stage_in(c->d_ex_te, b->ex_te, (size_t)I);
+    stage_in(c->d_part_iv_off, b->part_iv_off, pl.n.part_off); stage_in(c->d_part_rep_off, b->part_rep_off, pl.n.part_off);
+    stage_in(c->d_iv_start, b->iv_start, pl.n.iv); stage_in(c->d_iv_end, b->iv_end, pl.n.iv);
+    stage_in(c->d_rep_exon_off, b->rep_exon_off, (size_t)f.R + 1); stage_in(c->d_rep_weight, b->rep_weight, (size_t)f.R);
+    stage_in(c->d_ex_ts, b->ex_ts, (size_t)f.I); stage_in(c->d_ex_te, b->ex_te, (size_t)f.I);
     const double t_copy = tk.ms();
-    c->n_part = np; c->K = K; c->R = R; c->I = I; c->NPOS = NPOS; c->LANES = lanes; c->expanded = expanded;
-    if (c->max_part_lanes > lanes) c->max_part_lanes = lanes;
-    c->n_tiles = (int)n_tiles; c->n_hist_chunks = (int)n_chunks; c->hist_packed = hist_packed; c->yraw_narrow = yraw_narrow; c->n_rep_blocks = (int)n_rep_blocks; c->max_rep_exons = max_rep_exons;
-    c->part_iv_off.assign(b->part_iv_off, b->part_iv_off + np + 1);
-    c->part_rep_off.assign(b->part_rep_off, b->part_rep_off + np + 1);
+    c->batch = f;
+    c->part_iv_off.assign(b->part_iv_off, b->part_iv_off + f.n_part + 1);
+    c->part_rep_off.assign(b->part_rep_off, b->part_rep_off + f.n_part + 1);
+    HIP_TRY(c, hipMemcpyAsync(c->slab_in.p, c->h_stage.p, up_bytes, hipMemcpyHostToDevice, c->stream));
+    TRY(launch_prep(c, pl));
+    TRY(carve_work(c, pl));
+    drop_graph(c);
+    c->have_batch = true;
+    if (c->trace)
+        fprintf(stderr, "[fseg] upload: plan %.3f ms, tables %.3f ms, copy-in %.3f ms (%.1f MB), enqueue %.3f ms; %lld positions, %lld reps, %lld exons\n",
+                t_plan, t_tables, t_copy, up_bytes / 1e6, tk.ms(), (long long)f.NPOS, (long long)f.R, (long long)f.I);
+    return FSEG_OK;
+}
+
+// The device-side preparation of an uploaded batch: validation of every exon, the per-partition sort of the reps, the lane list,
+// the histogram chunks' lane ranges
+static int launch_prep(fseg_ctx *c, const UploadPlan &pl) {
+    const int np = pl.batch.n_part;
+    const i64 R = pl.batch.R, n_rep_blocks = pl.batch.n_rep_blocks, n_chunks = pl.batch.n_hist_chunks, max_part_reps = pl.max_part_reps;
     hipStream_t s = c->stream;
-    HIP_TRY(c, hipMemcpyAsync(c->slab_in.p, c->h_stage.p, up_bytes, hipMemcpyHostToDevice, s));
     // ---- device-side preparation
     {
         PrepStatus init;
@@ -1921,48 +1807,48 @@ static int upload_impl(fseg_ctx *c, const fseg_batch *b) {
                        c->d_lane_pmax.p, c->d_hc_llo.p, c->d_hc_lhi.p);
     HIP_TRY(c, hipMemcpyAsync(c->h_prep.p, c->d_prep.p, sizeof(PrepStatus), hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipGetLastError());
-    // ---- position- and candidate-sized work buffers (candidates and finals are distinct positions, so NPOS bounds them)
-    {
-        const size_t np8 = (size_t)NPOS + 64;
-        auto atleast = [](i64 &cap, i64 v) { if (cap < v) cap = v; };
-        atleast(c->chunk_cap, NPOS / 8192 + np + 8);              // an upper bound, not a guess
-        Carve cv;
-        cv.add(c->d_y_raw, np8 * (yraw_narrow ? sizeof(uint16_t) : sizeof(int))); cv.add(c->d_y, np8);      // (an array starts on a multiple of 256 bytes whatever the one before it holds)
-        cv.add(c->d_bits, 3 * flag_words(np8));
-        cv.add(c->d_v, np8);
-        cv.add(c->d_scan_state, ((size_t)nb * 3 + 1));
-        cv.add(c->d_bsum, ((size_t)nbp + 2));
-        cv.add(c->d_gsum, ((size_t)pos_groups(NPOS) + 2));
-        cv.add(c->d_bsum_side, ((size_t)nb + 2));
-        cv.add(c->d_g, np8); cv.add(c->d_pk, np8); cv.add(c->d_pf, np8); cv.add(c->d_kp, np8);
-        cv.add(c->d_part_has2, ((size_t)np + 1));
-        cv.add(c->d_tile_tot, ((size_t)n_tiles + 1));
-        cv.add(c->d_blk_pre, ((size_t)n_tiles + 1) * (kSmoothTile / kSumBlock));
-        cv.add(c->d_tile_defer, ((size_t)n_tiles + 1));
-        cv.add(c->d_voff, ((size_t)np + 2)); cv.add(c->d_chunk_off, ((size_t)np + 2));
-        cv.add(c->d_mean, ((size_t)np + 1)); cv.add(c->d_thr, ((size_t)np + 1));
-        cv.add(c->d_label_off, ((size_t)np + 2));
-        cv.add(c->d_csum, (size_t)c->chunk_cap * 2);     // chunk sums of both passes
-        cv.add(c->d_cand_off, ((size_t)K + 2)); cv.add(c->d_final_off, ((size_t)K + 2));
-        cv.add(c->d_cand_y, np8); cv.add(c->d_fixed0, np8); cv.add(c->d_added, np8);
-        cv.add(c->d_fixed, np8); cv.add(c->d_chosen, np8);
-        cv.add(c->d_final_y, np8); cv.add(c->d_final_pos, np8); cv.add(c->d_final_iv, np8); cv.add(c->d_col_thr, np8); cv.add(c->d_col_zero, np8);
-        cv.add(c->d_seg_iv, np8); cv.add(c->d_seg_prev, np8); cv.add(c->d_rseg_c, np8);
-        cv.add(c->d_cand_pn, np8); cv.add(c->d_cand_ll, np8); cv.add(c->d_cand_ln, np8); cv.add(c->d_cand_wide, np8);
-        cv.add(c->d_prob_bs, ((size_t)NPOS / kProbBlock + 2) * kProbCols);
-        TRY(reserve(c, c->slab_pos, cv.total));
-        cv.bind(c->slab_pos.p);
-        // arena capacities: a sized first run makes them exact; without it (FSEG_NO_SIZED) these are first guesses that
-        // finish_run() grows
-        atleast(c->prob_cap, 1024); atleast(c->work_cap, 1024); atleast(c->pair_cap, 1 << 16); atleast(c->tri_cap, 1 << 18);
-        atleast(c->label_cap, 1 << 16); atleast(c->cov_cap, 1 << 18);
-        TRY(alloc_arenas(c));
-    }
-    drop_graph(c);
-    c->have_batch = true;
-    if (c->trace)
-        fprintf(stderr, "[fseg] upload: plan %.3f ms, tables %.3f ms, copy-in %.3f ms (%.1f MB), enqueue %.3f ms; %lld positions, %lld reps, %lld exons\n",
-                t_plan, t_tables, t_copy, up_bytes / 1e6, tk.ms(), (long long)NPOS, (long long)R, (long long)I);
+    return FSEG_OK;
+}
+
+// The position- and candidate-sized work buffers (candidates and finals are distinct positions, so NPOS bounds them) and the arenas
+static int carve_work(fseg_ctx *c, const UploadPlan &pl) {
+    const int np = pl.batch.n_part;
+    const i64 NPOS = pl.batch.NPOS, K = pl.batch.K, n_tiles = pl.batch.n_tiles, nb = pl.nb, nbp = pl.nbp;
+    const bool yraw_narrow = pl.batch.yraw_narrow;
+    const size_t np8 = (size_t)NPOS + 64;
+    auto atleast = [](i64 &cap, i64 v) { if (cap < v) cap = v; };
+    atleast(c->chunk_cap, NPOS / 8192 + np + 8);              // an upper bound, not a guess
+    Carve cv;
+    cv.add(c->d_y_raw, np8 * (yraw_narrow ? sizeof(uint16_t) : sizeof(int))); cv.add(c->d_y, np8);      // (an array starts on a multiple of 256 bytes whatever the one before it holds)
+    cv.add(c->d_bits, 3 * flag_words(np8));
+    cv.add(c->d_v, np8);
+    cv.add(c->d_scan_state, ((size_t)nb * 3 + 1));
+    cv.add(c->d_bsum, ((size_t)nbp + 2));
+    cv.add(c->d_gsum, ((size_t)pos_groups(NPOS) + 2));
+    cv.add(c->d_bsum_side, ((size_t)nb + 2));
+    cv.add(c->d_g, np8); cv.add(c->d_pk, np8); cv.add(c->d_pf, np8); cv.add(c->d_kp, np8);
+    cv.add(c->d_part_has2, ((size_t)np + 1));
+    cv.add(c->d_tile_tot, ((size_t)n_tiles + 1));
+    cv.add(c->d_blk_pre, ((size_t)n_tiles + 1) * (kSmoothTile / kSumBlock));
+    cv.add(c->d_tile_defer, ((size_t)n_tiles + 1));
+    cv.add(c->d_voff, ((size_t)np + 2)); cv.add(c->d_chunk_off, ((size_t)np + 2));
+    cv.add(c->d_mean, ((size_t)np + 1)); cv.add(c->d_thr, ((size_t)np + 1));
+    cv.add(c->d_label_off, ((size_t)np + 2));
+    cv.add(c->d_csum, (size_t)c->chunk_cap * 2);     // chunk sums of both passes
+    cv.add(c->d_cand_off, ((size_t)K + 2)); cv.add(c->d_final_off, ((size_t)K + 2));
+    cv.add(c->d_cand_y, np8); cv.add(c->d_fixed0, np8); cv.add(c->d_added, np8);
+    cv.add(c->d_fixed, np8); cv.add(c->d_chosen, np8);
+    cv.add(c->d_final_y, np8); cv.add(c->d_final_pos, np8); cv.add(c->d_final_iv, np8); cv.add(c->d_col_thr, np8); cv.add(c->d_col_zero, np8);
+    cv.add(c->d_seg_iv, np8); cv.add(c->d_seg_prev, np8); cv.add(c->d_rseg_c, np8);
+    cv.add(c->d_cand_pn, np8); cv.add(c->d_cand_ll, np8); cv.add(c->d_cand_ln, np8); cv.add(c->d_cand_wide, np8);
+    cv.add(c->d_prob_bs, ((size_t)NPOS / kProbBlock + 2) * kProbCols);
+    TRY(reserve(c, c->slab_pos, cv.total));
+    cv.bind(c->slab_pos.p);
+    // arena capacities: a sized first run makes them exact; without it (FSEG_NO_SIZED) these are first guesses that
+    // finish_run() grows
+    atleast(c->prob_cap, 1024); atleast(c->work_cap, 1024); atleast(c->pair_cap, 1 << 16); atleast(c->tri_cap, 1 << 18);
+    atleast(c->label_cap, 1 << 16); atleast(c->cov_cap, 1 << 18);
+    TRY(alloc_arenas(c));
     return FSEG_OK;
 }
 
@@ -1999,17 +1885,17 @@ static int run_impl(fseg_ctx *c) {
     if (c->label_cap > 0) {
         // (the label arena of THIS run's form: a context whose parameters moved between threshold_rate < 1 -- two bits per label --
         // and threshold_rate = 1 -- bytes -- has so far only the other one; nothing to do otherwise)
-        void *before[2] = {c->d_labels.p, c->d_packed.p};
         TRY(ensure_label_arena(c));
-        if (before[0] != c->d_labels.p || before[1] != c->d_packed.p) drop_graph(c);
     }
+    c->shape.d_labels = c->d_labels.p; c->shape.d_packed = c->d_packed.p;
     c->last_sized = false;
-    c->run_plain = !c->use_graph || c->profile_plain || would_fork(c);
+    c->run_plain = !c->use_graph || c->shape.profile_plain || would_fork(c);
     if (!c->run_plain) {
         c->run_linear = true;
         struct Unset { fseg_ctx *c; ~Unset() { c->run_linear = false; } } unset{c};
+        if (c->n_graphs > 0 && !(c->shape == c->graph_shape)) drop_graph(c);     // captured under another shape: not this run's launches
         if (c->n_graphs == 0) {
-            const int want = c->profiling ? 2 : 1;
+            const int want = c->shape.profiling ? 2 : 1;
             bool ok = true;
             for (int g = 0; g < want && ok; ++g) {
                 HIP_TRY(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
@@ -2018,7 +1904,7 @@ static int run_impl(fseg_ctx *c) {
                 if (rc == FSEG_OK && e == hipSuccess) e = hipGraphInstantiate(&c->graph_exec[g], c->graph[g], nullptr, nullptr, 0);
                 ok = rc == FSEG_OK && e == hipSuccess;
             }
-            if (ok) c->n_graphs = want;
+            if (ok) { c->n_graphs = want; c->graph_shape = c->shape; ++c->graph_captures; }
             else {                                         // capture not possible: fall back to plain launches
                 (void)hipGetLastError();
                 drop_graph(c);
@@ -2065,7 +1951,7 @@ int fseg_get_sizes(fseg_ctx *c, fseg_sizes *out) {
     out->label_bytes = (int64_t)c->h_status->label_bytes;
     out->n_cand = (int64_t)c->h_status->n_cand;
     out->n_problems = (int64_t)c->h_status->n_prob;
-    out->n_positions = c->NPOS;
+    out->n_positions = c->batch.NPOS;
     out->max_problem_size = (int64_t)c->h_status->max_n;
     out->max_problem_reads = (int64_t)c->h_status->max_ln;
     return FSEG_OK;
@@ -2165,13 +2051,13 @@ static int results_impl(fseg_ctx *c, const int64_t **part_final_off, const int32
         const size_t nf = (size_t)c->h_status->n_final, lb = (size_t)c->h_status->label_bytes;
         size_t off = 0;
         auto take = [&](int i, size_t bytes) { c->res_off[i] = off; off = (off + bytes + 255) & ~(size_t)255; };
-        take(0, bytes_of(c->d_final_off, (size_t)c->K + 1)); take(1, bytes_of(c->d_final_pos, nf)); take(2, bytes_of(c->d_label_off, (size_t)c->n_part + 1));
+        take(0, bytes_of(c->d_final_off, (size_t)c->batch.K + 1)); take(1, bytes_of(c->d_final_pos, nf)); take(2, bytes_of(c->d_label_off, (size_t)c->batch.n_part + 1));
         take(3, packed ? bytes_of(c->d_packed, (lb + 15) / 16) : lb);
         TRY(reserve_host(c, c->h_res, off));
         char *h = c->h_res.p;
-        HIP_TRY(c, hipMemcpyAsync(h + c->res_off[0], c->d_final_off.p, bytes_of(c->d_final_off, (size_t)c->K + 1), hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipMemcpyAsync(h + c->res_off[0], c->d_final_off.p, bytes_of(c->d_final_off, (size_t)c->batch.K + 1), hipMemcpyDeviceToHost, s));
         if (nf) HIP_TRY(c, hipMemcpyAsync(h + c->res_off[1], c->d_final_pos.p, bytes_of(c->d_final_pos, nf), hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipMemcpyAsync(h + c->res_off[2], c->d_label_off.p, bytes_of(c->d_label_off, (size_t)c->n_part + 1), hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipMemcpyAsync(h + c->res_off[2], c->d_label_off.p, bytes_of(c->d_label_off, (size_t)c->batch.n_part + 1), hipMemcpyDeviceToHost, s));
         const void *big_src = nullptr;                       // the label matrix: on SDMA when it is large (see sdma_d2h)
         size_t big_bytes = 0;
         if (lb && !packed) { TRY(unpack_labels(c, lb)); big_src = c->d_labels.p; big_bytes = lb; }
@@ -2196,8 +2082,8 @@ static int results_impl(fseg_ctx *c, const int64_t **part_final_off, const int32
         else HIP_TRY(c, hipStreamSynchronize(s));
         if (!c->ran) return fail(c, FSEG_ERR_ARG, "no completed run");
         const i64 *fo = reinterpret_cast<const i64 *>(h + c->res_off[0]);
-        c->res_pfo.resize((size_t)c->n_part + 1);
-        for (int p = 0; p <= c->n_part; ++p) c->res_pfo[(size_t)p] = fo[(size_t)c->part_iv_off[(size_t)p]];
+        c->res_pfo.resize((size_t)c->batch.n_part + 1);
+        for (int p = 0; p <= c->batch.n_part; ++p) c->res_pfo[(size_t)p] = fo[(size_t)c->part_iv_off[(size_t)p]];
         c->fetched = true;
         c->fetched_packed = packed ? 1 : 0;
     }
@@ -2224,13 +2110,13 @@ int fseg_download(fseg_ctx *c, int64_t *part_final_off, int32_t *final_pos, int6
     if (!c->ran) return fail(c, FSEG_ERR_ARG, "no completed run");
     hipStream_t s = c->stream;
     if (part_final_off) {
-        std::vector<i64> fo((size_t)c->K + 1);
+        std::vector<i64> fo((size_t)c->batch.K + 1);
         HIP_TRY(c, hipMemcpyAsync(fo.data(), c->d_final_off.p, bytes_of(c->d_final_off, fo.size()), hipMemcpyDeviceToHost, s));
         HIP_TRY(c, hipStreamSynchronize(s));
-        for (int p = 0; p <= c->n_part; ++p) part_final_off[p] = fo[(size_t)c->part_iv_off[p]];
+        for (int p = 0; p <= c->batch.n_part; ++p) part_final_off[p] = fo[(size_t)c->part_iv_off[p]];
     }
     if (final_pos) HIP_TRY(c, hipMemcpyAsync(final_pos, c->d_final_pos.p, bytes_of(c->d_final_pos, (size_t)c->h_status->n_final), hipMemcpyDeviceToHost, s));
-    if (label_off) HIP_TRY(c, hipMemcpyAsync(label_off, c->d_label_off.p, bytes_of(c->d_label_off, (size_t)c->n_part + 1), hipMemcpyDeviceToHost, s));
+    if (label_off) HIP_TRY(c, hipMemcpyAsync(label_off, c->d_label_off.p, bytes_of(c->d_label_off, (size_t)c->batch.n_part + 1), hipMemcpyDeviceToHost, s));
     if (labels && c->h_status->label_bytes) {
         TRY(unpack_labels(c, (size_t)c->h_status->label_bytes));
         HIP_TRY(c, hipMemcpyAsync(labels, c->d_labels.p, (size_t)c->h_status->label_bytes, hipMemcpyDeviceToHost, s));
@@ -2265,7 +2151,7 @@ static int annotate_impl(fseg_ctx *c, const fseg_reads *rd, const int64_t *label
     if (n > 0 && (!rd->read_part || !rd->read_rep || !rd->strand || !rd->seq_len || !rd->seq_off || !rd->read_q_off || !rd->qs || !rd->qe ||
                   !rd->cig_off || !rd->cig_op || !rd->cig_len))
         return fail(c, FSEG_ERR_ARG, "fseg_annotate: null array");
-    const int np = c->n_part;
+    const int np = c->batch.n_part;
     // ---- argument checks: everything a kernel indexes with is bounded here
     const i64 *h_rep_exon_off = host_of(c, c->d_rep_exon_off);
     if (n > 0 && (rd->seq_off[0] != 0 || rd->read_q_off[0] != 0)) return fail(c, FSEG_ERR_ARG, "fseg_annotate: read 0: offsets must start at 0");
@@ -2462,26 +2348,26 @@ int fseg_tap(fseg_ctx *c, int what, void *dst, int64_t cap_bytes, int64_t *n_byt
         return FSEG_OK;
     };
     switch (what) {
-        case FSEG_TAP_POS_OFF: return from_dev(c->d_pos_off, c->K + 1);
+        case FSEG_TAP_POS_OFF: return from_dev(c->d_pos_off, c->batch.K + 1);
         case FSEG_TAP_Y_RAW: {                                             // int32 whatever the device holds: uint16 is widened here
-            if (!c->yraw_narrow) return from_dev(DevBuf<int32_t>{c->d_y_raw.as<int32_t>()}, c->NPOS);
-            const i64 bytes = (i64)DevBuf<int32_t>::bytes((size_t)c->NPOS);
+            if (!c->batch.yraw_narrow) return from_dev(DevBuf<int32_t>{c->d_y_raw.as<int32_t>()}, c->batch.NPOS);
+            const i64 bytes = (i64)DevBuf<int32_t>::bytes((size_t)c->batch.NPOS);
             *n_bytes = bytes;
             if (dst && cap_bytes > 0 && bytes > 0) {
-                std::vector<uint16_t> narrow((size_t)c->NPOS);
+                std::vector<uint16_t> narrow((size_t)c->batch.NPOS);
                 HIP_TRY(c, copy_sync(c, narrow.data(), c->d_y_raw.p, narrow.size() * sizeof(uint16_t), hipMemcpyDeviceToHost));
                 const i64 n = (bytes < cap_bytes ? bytes : cap_bytes) / (i64)sizeof(int32_t);
                 for (i64 i = 0; i < n; ++i) static_cast<int32_t *>(dst)[i] = (int32_t)narrow[(size_t)i];
             }
             return FSEG_OK;
         }
-        case FSEG_TAP_Y: return from_dev(c->d_y, c->NPOS);
-        case FSEG_TAP_THRESHOLD: return from_dev(c->d_thr, c->n_part);
-        case FSEG_TAP_CAND_OFF: return from_dev(c->d_cand_off, c->K + 1);
+        case FSEG_TAP_Y: return from_dev(c->d_y, c->batch.NPOS);
+        case FSEG_TAP_THRESHOLD: return from_dev(c->d_thr, c->batch.n_part);
+        case FSEG_TAP_CAND_OFF: return from_dev(c->d_cand_off, c->batch.K + 1);
         case FSEG_TAP_CAND_Y: return from_dev(c->d_cand_y, (i64)st.n_cand);
         case FSEG_TAP_FIXED: return from_dev(c->d_fixed, (i64)st.n_cand);
         case FSEG_TAP_CHOSEN: return from_dev(c->d_chosen, (i64)st.n_cand);
-        case FSEG_TAP_FINAL_OFF: return from_dev(c->d_final_off, c->K + 1);
+        case FSEG_TAP_FINAL_OFF: return from_dev(c->d_final_off, c->batch.K + 1);
         case FSEG_TAP_FINAL_Y: return from_dev(c->d_final_y, (i64)st.n_final);
         case FSEG_TAP_PROBLEMS: {                                          // a row per problem: interval, first candidate, candidates, chain
             const size_t n = (size_t)st.n_prob;
@@ -2493,21 +2379,22 @@ int fseg_tap(fseg_ctx *c, int what, void *dst, int64_t cap_bytes, int64_t *n_byt
             }
             return from_host(rows.data(), rows.size() * sizeof(int));
         }
-        case FSEG_TAP_LANE_START: return from_dev(c->d_lane_start, c->LANES);
-        case FSEG_TAP_LANE_PMAX: return from_dev(c->d_lane_pmax, c->LANES);
-        case FSEG_TAP_LANE_EXONS: return from_dev(c->d_lane_ex, c->LANES);
-        case FSEG_TAP_LANE_STREAM: return from_dev(c->d_lane_lx, c->LANES);
-        case FSEG_TAP_EXON_STREAM: return from_dev(c->d_lex, c->I);
+        case FSEG_TAP_LANE_START: return from_dev(c->d_lane_start, c->batch.LANES);
+        case FSEG_TAP_LANE_PMAX: return from_dev(c->d_lane_pmax, c->batch.LANES);
+        case FSEG_TAP_LANE_EXONS: return from_dev(c->d_lane_ex, c->batch.LANES);
+        case FSEG_TAP_LANE_STREAM: return from_dev(c->d_lane_lx, c->batch.LANES);
+        case FSEG_TAP_EXON_STREAM: return from_dev(c->d_lex, c->batch.I);
         case FSEG_TAP_SYNC: {
             SyncWords w{};
             HIP_TRY(c, copy_sync(c, &w, c->d_sync.p, sizeof w, hipMemcpyDeviceToHost));
             const int words[] = {(int)c->sync_gen, c->dev_sync ? 1 : 0, (int)w.emit_gen, (int)w.side_gen[0], (int)w.side_gen[1], (int)w.emit_ctr,
-                                 (int)c->sync_timeouts, (int)c->forked_runs, (c->side_probed ? 8 : 0) | (c->side_ok[0] ? 1 : 0) | (c->side_ok[1] ? 2 : 0) | (c->side_ok[2] ? 4 : 0)};
+                                 (int)c->sync_timeouts, (int)c->forked_runs, (c->side_probed ? 8 : 0) | (c->side_ok[0] ? 1 : 0) | (c->side_ok[1] ? 2 : 0) | (c->side_ok[2] ? 4 : 0),
+                                 (int)c->graph_captures};
             return from_host(words, sizeof words);
         }
         case FSEG_TAP_PATHS: return from_host(c->paths, sizeof c->paths);
         case FSEG_TAP_HIST_RANGES: {                                       // a row per histogram chunk: first position, positions, lane range
-            const size_t n = (size_t)c->n_hist_chunks;
+            const size_t n = (size_t)c->batch.n_hist_chunks;
             std::vector<i64> col(n), rows(n * 4);
             std::vector<int> cnt(n);
             const DevBuf<i64> *cols[3] = {&c->d_hc_p0, &c->d_hc_llo, &c->d_hc_lhi};
@@ -2525,10 +2412,9 @@ int fseg_tap(fseg_ctx *c, int what, void *dst, int64_t cap_bytes, int64_t *n_byt
 
 int fseg_set_profiling(fseg_ctx *c, int on) {
     if (!c) return FSEG_ERR_ARG;
-    if (c->profiling != (on != 0) || c->profile_all != (on != 2) || c->profile_plain != (on == 3)) drop_graph(c);
-    c->profiling = on != 0;
-    c->profile_all = on != 2;
-    c->profile_plain = on == 3;         // every stage bracketed on replays too: plain launches instead of the graph
+    c->shape.profiling = on != 0;
+    c->shape.profile_all = on != 2;
+    c->shape.profile_plain = on == 3;         // every stage bracketed on replays too: plain launches instead of the graph
     return FSEG_OK;
 }
 int fseg_n_stages(void) { return ST_REPORTED; }
@@ -2567,10 +2453,10 @@ int fseg_debug_timed_class(fseg_ctx *c, int cls) {
 int64_t fseg_scoring_algorithmic_bytes(fseg_ctx *c) {
     if (!c || !c->ran) return -1;
     // per partition 4*(N_p + K_p)*R_p + 4*R_p, R_p = read reps
-    std::vector<i64> co((size_t)c->K + 1);
+    std::vector<i64> co((size_t)c->batch.K + 1);
     if (copy_sync(c, co.data(), c->d_cand_off.p, bytes_of(c->d_cand_off, co.size()), hipMemcpyDeviceToHost) != hipSuccess) return -1;
     i64 total = 0;
-    for (int p = 0; p < c->n_part; ++p) {
+    for (int p = 0; p < c->batch.n_part; ++p) {
         i64 Np = co[(size_t)c->part_iv_off[p + 1]] - co[(size_t)c->part_iv_off[p]];
         i64 Kp = c->part_iv_off[p + 1] - c->part_iv_off[p];
         i64 Rp = c->part_rep_off[p + 1] - c->part_rep_off[p];

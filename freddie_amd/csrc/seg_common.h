@@ -22,20 +22,11 @@
 #include <vector>
 
 #include "freddie_seg.h"
+#include "seg_run_react.h"     // kNMax / kNHuge / kNGiant, the status record and its error bits: what the host's reaction to a run shares with the kernels
+#include "seg_upload_plan.h"   // i64 / u64, the tile / block / chunk sizes and TileDesc: what the upload's host plan shares with the kernels
 
 namespace fseg {
 
-
-typedef long long i64;
-
-typedef unsigned long long u64;
-
-
-constexpr int kSmoothShift = 9;
-
-constexpr int kSmoothTile = 1 << kSmoothShift;   // positions per smoothing tile: intervals average ~1.5 K positions in many-partition
-
-                                                 // batches, and a tile never spans two intervals -- 512 keeps the tiles ~95 % full
 constexpr int kSmoothThreads = kSmoothTile / 4;  // a thread computes 4 consecutive outputs
 
 constexpr int kSumShift = 4, kSumBlock = 1 << kSumShift;     // positions per block of the histogram's in-tile prefix sums (k_smooth -> k_segments)
@@ -44,31 +35,19 @@ static_assert(kSmoothTile / kSumBlock <= 64 && kSumBlock == 16, "a tile's block 
 
 constexpr int kMaxRadius = 200;        // sigma <= 50, truncate 4.0 (py/freddie_segment.py:106,:755)
 
-constexpr int kScanBlock = 8192;       // elements per scan workgroup (256 threads x one 32-bit word of flags): the Y > 0 values (k_scan_emit<kEmitValues>, k_voff)
-
 // The two position compactions (candidates, final positions) flag about one position in two hundred: their workgroup takes four flag
 // words a thread (one 16-byte load), a quarter of the workgroups and of their chains of dependent loads.  The block sums are kept
 // raw, with the sum of every group of kPosGroup blocks beside them (k_pos_count): an emitting workgroup adds the groups before its
 // own and the blocks before it inside the group in one round of loads, so no single workgroup scans the sums between the two.
-constexpr int kPosBlock = 32768;       // positions per workgroup of a position compaction (256 threads x four words)
+// (kPosBlock positions per workgroup, 256 threads x four words: seg_upload_plan.h)
 constexpr int kPosGroup = 64;          // blocks per group of the two-level sums: a wave of k_pos_count each four blocks
 constexpr int kPosCountThreads = 1024; // k_pos_count: a workgroup per group
 static_assert(kPosBlock % (64 * 128) == 0 && kPosGroup % (kPosCountThreads / 64) == 0 && kPosGroup <= 64,
               "k_pos_count: a wave takes whole blocks, 64 lanes x 16 bytes a round; k_scan_emit: a wave adds a group's block sums in one round");
-inline i64 pos_blocks(i64 n) { return (n + kPosBlock - 1) / kPosBlock; }
 inline i64 pos_groups(i64 n) { return (pos_blocks(n) + kPosGroup - 1) / kPosGroup; }
 
 inline size_t flag_words(i64 n_pos) { return ((size_t)n_pos + 31) / 32 + 64; }      // words of one flag mask (+ room for a tile's last word and the scans' last block)
 
-constexpr int kNMax = 60;              // largest DP problem handled by the LDS-resident scoring kernel
-
-constexpr int kNHuge = 128;            // 60 < n <= 128 (max_problem_size up to ~115): the global-count-table kernels k_score_huge / k_dp_huge
-
-                                       // (pair planes and the DP's tables in LDS)
-constexpr int kNGiant = 1024;          // 128 < n <= 1024 (max_problem_size up to 1 000: what the CLI accepts): k_score_giant / k_dp_giant,
-
-                                       // every per-pair table in global scratch -- slow, complete (the reference's own optimize() is
-                                       // O(n^3 R) Python there: nobody runs it for long)
 constexpr int kLaneChunk = 256;        // reads ("lanes") per scoring work item (u16 counters: must stay < 65536)
 
 constexpr int kSub = 64;               // reads per scoring sub-chunk (two 32-bit plane words)
@@ -86,27 +65,6 @@ constexpr int kFuseLanesWide = 1023;   // ... and for the 16-bit instances: part
                                        // in twenty-five of them more than 255); a problem that sees more than this is quicker spread
                                        // over the arena path's work items, and so is its whole batch
 
-// error bits of Status::err
-enum : unsigned {
-    kErrExonInterval = 1u,     // an exon is not inside one tint interval (py/freddie_segment.py:668)
-    kErrBreakAssert = 2u,      // break_large_problems: assert max_c_idx_y_v > 0 / index out of range (:640-643)
-    kErrProblemTooLarge = 4u,  // a DP problem has more than kNGiant candidates
-    kErrOverflowPairs = 8u,
-    kErrOverflowTri = 16u,
-    kErrOverflowWork = 32u,
-    kErrOverflowLabels = 64u,
-    kErrOverflowProblems = 128u,
-    kErrOverflowChunks = 256u,
-    kErrOverflowCov = 512u,
-    kErrOverflowNm = 1024u,
-    kErrWideMissed = 16384u,   // internal: a problem keeps more reads than k_prob_range counted for it (the 8-bit instance met it)
-    kErrWaveStage = 8192u,     // a wave kernel (k_wave) met a read with more exons than its LDS stage holds: rerun without them
-    kErrScanStall = 4096u,     // the look-back scan gave up waiting for a predecessor block: rerun with the three-pass scan
-    kErrSyncTimeout = 32768u,  // a device-side waiter of the scoring stage (k_wait_word) gave up: the stage was skipped, rerun with events
-    kErrNeedWideDp = 2048u,    // a problem sees >= 65536 reads: its DP needs the 32-bit count table    // a problem is larger than the LDS carve-up this launch was sized for
-};
-
-
 #ifdef FSEG_SCORE_TIMING
 constexpr size_t kTaccProbs = 1u << 17, kTaccBytes = 128 + kTaccProbs * 64;     // (a record per problem for k_solve / k_wave, another for k_dpw)
 
@@ -114,42 +72,6 @@ constexpr size_t kTaccProbs = 1u << 17, kTaccBytes = 128 + kTaccProbs * 64;     
 constexpr size_t kTaccBytes = 128;
 
 #endif
-struct Status {
-    unsigned err;
-    unsigned pad;
-    u64 n_vals;        // number of Y > 0 values (all partitions)
-    u64 n_vchunks;     // 8192-element chunks of the threshold reduction
-    u64 n_cand;
-    u64 n_prob;
-    u64 n_work;
-    u64 pair_used;
-    u64 tri_used;
-    u64 n_rseg;
-    u64 n_final;
-    u64 label_bytes;
-    u64 cov_used;      // elements of the coverage arena
-    unsigned max_n;    // largest DP problem of this run
-    unsigned max_ln;   // most reads any DP problem of this run examines (>= 65536: the DP needs 32-bit counts)
-    u64 cls_work[4];   // work items per problem-size class (n <= 16, <= 32, <= kNMax, <= kNHuge)
-    u64 cls_queue[3];  // dynamic work counters of the scoring kernels
-    u64 dp_cls[3];     // DP problems with n <= kDpSmall / <= kNMax / larger
-    u64 cov_queue;
-    u64 solve_cls[3];  // problems solved whole by k_solve (n <= 16 / <= 32 / <= kNMax)
-    u64 n_tiny;        // problems solved whole by k_tiny (their list follows the three solve lists)
-    unsigned list_cur[8];   // k_prob_emit's cursors into the four solve lists: [2 * list] from the front (expensive problems), [2 * list + 1] from the back
-    unsigned wide_cls[4];   // solve-list problems per size class that see more than kFuseLanes reads (16-bit counters); [3] unused
-    unsigned wide_cur[4];   // k_prob_emit's cursors into the per-class lists of those problems (wide_items); [3]: into the list of all of them (wide_all)
-    unsigned gate_wide;     // workgroups of the large class's 16-bit instance that have started ('h' in a plan: the 8-bit instance waits for them)
-    unsigned gate;          // large-class workgroups that have started (k_gate holds the small classes back until they are placed)
-                            // (a counter of the mid class's 2 000 workgroups, bumped by each as it started, cost that kernel 10 of
-                            // its 62 us: these two count a few hundred)
-    unsigned sync_abort;    // a device-side waiter timed out: the scoring kernels behind it end at once (their input may not exist yet)
-    unsigned pad2;
-    // (Round 6 tried a start counter for the mid class here -- a gate 'i' that holds the small class back until the mid class's first
-    // workgroups are placed.  Beside sync_abort, which every workgroup of the stage reads, eight counters took the stage from 0.125 to
-    // 0.151 ms; on 128-byte lines of their own they cost nothing, and the gate gained nothing: 0.120-0.127 ms.  Removed.)
-};
-
 // Words of the device-side fork / join of the scoring stage (own allocation, zeroed once; generations only grow): see k_wait_word.
 struct SyncWords {
     unsigned emit_gen;      // generation of the last scoring stage whose problem list is complete (published by the first launch behind
@@ -251,22 +173,7 @@ __device__ __forceinline__ void label_thresholds_tab(i64 L, const int2 *tab, con
 // order-free) which is then written out whole -- no global atomics and no memset of the histogram.
 // A lane is one read (reps are repeated rep_weight times in the lane list), so every hit adds 1.
 // ---------------------------------------------------------------------------------------------
-constexpr int kHistChunk = 8192;
-// The same 32 KB of LDS as two 16-bit counters per word (k_hist<16>: position i of the chunk is half i & 1 of word i >> 1) hold twice
-// the positions: half the chunks, so half the visits of a read that spans its partition, half the table stagings and barriers.
-// A low half never carries into its neighbour because the host takes this instance only for batches in which no position's
-// count can exceed 65 535 (upload_impl: hist_packed).
-// Such a batch's histogram is uint16 in device memory as well (FSEG_YRAW16, default on): the write-out is then a copy of the LDS
-// words.  For that the chunk's counters start at half-word p0 & 7 of the LDS array (p0: the chunk's first position in the batch), so
-// 16-byte group j of the array is 16-byte group (p0 >> 3) + j of the histogram -- aligned on both sides -- and the array is one group
-// longer.  Only a chunk's first and last group can hold a neighbouring chunk's positions: those leave as 2-byte stores.
-#ifndef FSEG_HIST_CHUNK16
-#define FSEG_HIST_CHUNK16 16384
-#endif
-constexpr int kHistChunk16 = FSEG_HIST_CHUNK16;
-static_assert(kHistChunk16 % 8 == 0, "the packed counters are zeroed sixteen bytes at a time");
-constexpr int kHistCountMax16 = 65535;
-
+// (kHistChunk, kHistChunk16 and kHistCountMax16 -- the chunk sizes of the two counter widths -- are in seg_upload_plan.h: the host plans the chunks)
 constexpr int kHistIv = 1024;     // intervals of a partition cached in LDS by k_hist
 
 
@@ -315,12 +222,7 @@ __device__ __forceinline__ int wg_exclusive_scan_lds(int v, int *lds /* >= 16 in
 
 // R > 0: radius known at compile time (the tap loop is fully unrolled: no window moves, no loop control, weights
 // in scalar registers); R == 0: any radius <= kMaxRadius.
-// One 16-byte record per tile (built on upload) instead of tile -> interval -> offsets: the per-tile set-up is one load.
-struct __align__(16) TileDesc {
-    i64 base;       // position of the interval's first element (pos_off[interval])
-    int y0;         // first position of the tile inside the interval
-    int len;        // interval length
-};
+// One 16-byte record per tile (TileDesc, built on upload: seg_upload_plan.h) instead of tile -> interval -> offsets: the per-tile set-up is one load.
 
 constexpr int kSmoothStage = (kSmoothTile + 2 * kMaxRadius + kSmoothThreads - 1) / kSmoothThreads;   // staged counts per thread, any radius
 

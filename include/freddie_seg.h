@@ -219,8 +219,11 @@ enum {
     FSEG_TAP_EXON_STREAM = 16, /* int32[I][2]    (ts, te) of every exon, the reps of a partition in lane order        */
     /* the scoring stage's device-side fork / join: stages enqueued with waiters so far, whether waiters are still in use
      * (0 after one timed out: events from then on), and the device's words (last problem-list generation, last generation of
-     * side streams 0 / 1, workgroup counter) */
-    FSEG_TAP_SYNC = 17,        /* int32[6]                                                                             */
+     * side streams 0 / 1, workgroup counter); then, of this context: [6] runs that lost a waiter to its time limit, [7] runs
+     * that owned the device (side streams in use), [8] the side streams probed (8) and found beside the main stream (1 | 2 | 4),
+     * [9] graph captures made so far -- a replay captures once per launch shape it meets (small / tiny / fused batch, huge,
+     * giant or wide-count problems, list sizes, profiling mode, label arena), so a resident batch replayed again adds none */
+    FSEG_TAP_SYNC = 17,        /* int32[10]                                                                            */
     /* the launch census of the last run: which kernel instances the host enqueued.  The masks and counts (words 4..16, 18..21, 23..30)
      * are written in the very branches that launch, not from what the FSEG_* switches asked for; words 0..3, 17 and 22 are the
      * batch's decisions those branches test, copied where the scoring stage begins; word 31 is written by fseg_upload.  Counts are

@@ -25,9 +25,6 @@ stop = False
 def a_results():
     while not stop:
         A.run(); A.results()
-def a_copy_only():
-    while not stop:
-        A.results()
 def a_run_only():
     while not stop:
         A.run(); A.sync()
@@ -48,7 +45,7 @@ def measure_upload(what, n=20):
         B.upload(**b1.arrays); B.sync()
     print("%-44s B upload+prep %.3f ms" % (what, (time.perf_counter() - t0) / n * 1e3))
 measure("B alone"); measure_upload("B alone")
-for fn, name in ((a_copy_only, "A: results only (FSEG_DEBUG_RECOPY=1)"), (a_run_only, "A: replay loop"), (a_results, "A: run + results (D2H 75 MB) loop"), (a_upload, "A: upload + prep loop"), (a_upload_run, "A: upload + first run loop")):
+for fn, name in ((a_run_only, "A: replay loop"), (a_results, "A: run + results (D2H 75 MB) loop"), (a_upload, "A: upload + prep loop"), (a_upload_run, "A: upload + first run loop")):
     stop = False
     t = threading.Thread(target=fn); t.start(); time.sleep(0.05)
     measure("beside " + name); measure_upload("beside " + name)
